@@ -5,13 +5,18 @@ RCCL all_gather of costs / controls afterwards).
 
 A "step" is one batch-iteration: every one of the B*N knot-iterations of the batch advanced once
 (backward Riccati sweep + closed-loop rollout + re-linearisation).  Inputs are
-resident in HBM before the timed region.  W warm-up steps, then R timed regions of exactly K steps
-each (repeated timed regions, median reported), every region bracketed by
-barrier + synchronize pairs and reduced with MAX over ranks.
+resident in HBM before the timed region.  W warm-up steps, then exactly K timed steps (`--steps`),
+split into R consecutive timed regions (repeated timed regions, median reported),
+every region bracketed by barrier + synchronize pairs and reduced with MAX over ranks.
+
+`--dump-outputs DIR` writes what the timed solve hands its caller after its last step (trajectories,
+controls, final cost, iteration count, status) as DIR/<name>.npy in float64, for a fixed seeded
+sample of the batch when all of it would exceed 64 MB.  The inputs are seeded, so the same
+arguments give the same inputs on every run and every build.
 
 Scaling (`--scaling`): "weak" (default, what the driver's `--gpus N` measures) gives every rank its own
-4096 trajectories, `value` = N * K / median region (in 4096-batch-iterations/s); "strong" splits ONE
-global batch (`--batch`, 4096) contiguously over the ranks, `value` = K / median region -- the fixed
+4096 trajectories, `value` = N / median seconds per step (in 4096-batch-iterations/s); "strong" splits ONE
+global batch (`--batch`, 4096) contiguously over the ranks, `value` = 1 / median seconds per step -- the fixed
 4096 x 200 problem of the metric name on 1/2/4/8 GPUs.  The JSON line says which.
 
 Secondary lines (never the headline): `--mode ss`, `--line-search`, `--workload drone400` (BASELINE config 5:
@@ -44,6 +49,8 @@ FP64_VALU_PEAK_TFLOPS = 78.6   # vendor fp64 vector peak
 ALG_FLOPS_PER_KNOT_ITER = 25e3  # dense count, SURVEY.md §8d (secondary figure)
 METRIC = "DDP iterations/sec at batch x horizon = 4096 x 200 (SE3 tracking)"
 RENDEZVOUS_TIMEOUT_S = 180     # init_process_group / collectives: a missing rank fails the others, it does not hang them
+DUMP_BYTES_MAX = 64 * 10 ** 6  # --dump-outputs: all files together, on disk
+DUMP_SEED = 20240                # --dump-outputs: the sample of trajectories when the whole batch does not fit
 
 
 def alg_bytes_per_knot_iter(m):
@@ -57,13 +64,17 @@ def alg_bytes_per_knot_iter(m):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps in all (the regions of --repeats split exactly this many)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=200,
-                    help="timed regions of --steps steps each (median reported); the default keeps the GPU busy for ~2.5 s at 4096 x 200")
-    ap.add_argument("--fresh-regions", type=int, default=8,
-                    help="headline only: additional regions that time iterations W..W+K of a FRESH solve each (the early-iteration "
-                         "regime; reported as config.fresh_solve, never as `value`); 0 = off")
+    ap.add_argument("--repeats", type=int, default=2,
+                    help="timed regions the --steps steps are split into (at most --steps; sizes differ by one at most): even ones "
+                         "carry per-kernel events, ms_per_step is the median of the others; one region carries the events")
+    ap.add_argument("--fresh-regions", type=int, default=0,
+                    help="headline only: additional regions that time iterations W..W+K/R of a FRESH solve each (the early-iteration "
+                         "regime; reported as config.fresh_solve, never as `value`; timed steps beyond --steps); 0 = off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed solve returns (rank 0's batch) as DIR/<name>.npy, float64, "
+                         "at most 64 MB in all (a fixed seeded sample of the trajectories when the batch is larger)")
     ap.add_argument("--batch", type=int, default=None, help="trajectories per GPU (weak) or in all (strong); default 4096 (se3) / 8192 (drone400)")
     ap.add_argument("--horizon", type=int, default=None, help="default 200 (se3) / 400 (drone400)")
     ap.add_argument("--workload", choices=["se3", "drone400", "so3", "al1024", "pendulum"], default="se3",
@@ -95,6 +106,8 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1,
                     help="(tests) with --dry-run: this rank exits 3 before the rendezvous")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0 or a.repeats < 1:
+        ap.error("--steps and --repeats must be >= 1, --warmup >= 0")
     if a.batch is None:
         a.batch = {"se3": 4096, "drone400": 8192, "so3": 1, "al1024": 1024, "pendulum": 4096}[a.workload]
     if a.horizon is None:
@@ -271,6 +284,48 @@ def executed_fp64_fraction(ms_step):
             return {"flops_per_step": flops, "frac": flops / (ms_step * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS, "kernels": seen,
                     "source": os.path.basename(f)}
     return None
+
+
+def region_sizes(K, R):
+    """K timed steps in min(R, K) consecutive regions whose sizes differ by one at most (the larger ones first)."""
+    R = min(R, K)
+    return [K // R + (1 if i < K % R else 0) for i in range(R)]
+
+
+def dump_sample(B, bytes_per_trajectory, budget=DUMP_BYTES_MAX):
+    """Rows of a B-trajectory batch whose outputs fit in `budget` bytes: all of them, or a sorted sample drawn with a
+    fixed seed (the same rows for the same arguments, on every run and every build)."""
+    import numpy as np
+    n = min(B, budget // bytes_per_trajectory)
+    if n < 1:
+        raise SystemExit("bench.py: one trajectory's outputs (%d bytes) exceed the %d-byte dump" % (bytes_per_trajectory, budget))
+    if n == B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False))
+
+
+def dump_outputs(res, out_dir):
+    """What the timed solve returns after its last step, as out_dir/<name>.npy (float64; integers are exact in it):
+    xs_q [n, N+1, 4, 4], xs_xi [n, N+1, 6], us [n, N, m], J [n] (the cost after the trajectory's last iteration),
+    iters [n], status [n], and trajectory_index [n], the rows of the batch they belong to."""
+    import numpy as np
+    import torch
+    B, N1, m = res.xs_q.shape[0], res.xs_q.shape[1], res.us.shape[2]
+    last = (res.iters.long().clamp(min=1) - 1).reshape(-1, 1)
+    per_row = {"xs_q": res.xs_q, "xs_xi": res.xs_xi, "us": res.us, "J": torch.gather(res.J_hist, 1, last).reshape(-1),
+               "iters": res.iters, "status": res.status}
+    row_bytes = 8 * (sum(t[0].numel() for t in per_row.values()) + 1)   # + trajectory_index
+    idx = dump_sample(B, row_bytes, DUMP_BYTES_MAX - 4096)                # room for the .npy headers
+    rows = torch.as_tensor(idx, device=res.xs_q.device)
+    arrays = {k: t.index_select(0, rows).double().cpu().numpy() for k, t in per_row.items()}
+    arrays["trajectory_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    files = sorted(k + ".npy" for k in arrays)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "files": files, "bytes": sum(os.path.getsize(os.path.join(out_dir, f)) for f in files),
+            "trajectories": len(idx), "of_batch": B, "horizon": N1 - 1, "m": m,
+            "sample": "all" if len(idx) == B else "numpy default_rng(%d).choice(%d, %d, replace=False), sorted" % (DUMP_SEED, B, len(idx))}
 
 
 def fresh_series(fresh, K, W, active, units, ms_step_headline):
@@ -461,7 +516,9 @@ def run_rank(args, rank, world):
     if multi:
         dist.init_process_group("nccl", device_id=dev, timeout=datetime.timedelta(seconds=RENDEZVOUS_TIMEOUT_S))
 
-    N, K, W, R = args.horizon, args.steps, args.warmup, max(1, args.repeats)
+    N, K, W = args.horizon, args.steps, args.warmup
+    sizes = region_sizes(K, args.repeats)   # exactly K timed steps in all
+    R = len(sizes)
     B, B_global = local_and_global_batch(args, rank, world)
     if B < 1:
         raise SystemExit("bench.py: --batch %d leaves rank %d without a trajectory" % (args.batch, rank))
@@ -515,7 +572,7 @@ def run_rank(args, rank, world):
         torch.cuda.synchronize(dev)
 
     headline = args.mode == "ms" and not args.line_search
-    regions, kern = [], []
+    regions, region_steps, kern = [], [], []
     fresh, fresh_active = [], None
     begin_kw = dict(mode=args.mode, tol_grad_norm=0.0, tol_d_norm=0.0, schedule=args.schedule, line_search=args.line_search,
                     rollout=args.rollout)
@@ -526,12 +583,12 @@ def run_rank(args, rank, world):
     # ms_per_step).  Both series are in the line.  With one region only (--repeats 1: the profiling runs) it carries the events.
     instrumented = []
 
-    def timed_region():
+    def timed_region(n):
         instr = len(regions) % 2 == 0
         solver.enable_timing(instr)
         barrier()
         t0 = time.perf_counter()
-        solver.solve_iterate(K)
+        solver.solve_iterate(n)
         barrier()
         t1 = time.perf_counter()
         if instr:
@@ -544,39 +601,41 @@ def run_rank(args, rank, world):
         if multi:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         regions.append(float(el.item()))
+        region_steps.append(n)
         instrumented.append(instr)
 
     if headline:
         # accept-always MS with tolerances 0: every trajectory does full work in every iteration of one long solve
-        total = W + R * K
+        total = W + K
         solver.solve_begin(x0_q_d, x0_xi_d, us0_d, n_iterations=total, **begin_kw)
         solver.solve_iterate(W)
-        for _ in range(R):
-            timed_region()
+        for n in sizes:
+            timed_region(n)
         res = solver.solve_end()
-        # The series above is ONE long solve: all but its first region time iterations of a converged solve, whose knots sit in
-        # the short tier of every series (tolg_lie.h) -- the cheapest regime.  A caller who solves a problem once spends its
-        # time in the FIRST iterations: each region of this second series is iterations W..W+K of a fresh solve (the protocol
-        # of the line-search lines), on the GPU the first series has warmed up.  Reported beside `value`, never as it.
+        # The series above is ONE long solve: with many steps its later regions time iterations of a converged solve, whose knots
+        # sit in the short tier of every series (tolg_lie.h) -- the cheapest regime.  A caller who solves a problem once spends
+        # its time in the FIRST iterations: each region of this second series is iterations W..W+sizes[0] of a fresh solve (the
+        # protocol of the line-search lines), on the GPU the first series has warmed up.  Reported beside `value`, never as it.
         n_head = len(regions)
         for _ in range(max(0, args.fresh_regions)):
-            solver.solve_begin(x0_q_d, x0_xi_d, us0_d, n_iterations=W + K, **begin_kw)
+            solver.solve_begin(x0_q_d, x0_xi_d, us0_d, n_iterations=W + sizes[0], **begin_kw)
             solver.solve_iterate(W)
-            timed_region()
+            timed_region(sizes[0])
             fres = solver.solve_end()
-            fresh_active = float((fres.iters == W + K).double().mean().item())
+            fresh_active = float((fres.iters == W + sizes[0]).double().mean().item())
         fresh = [(regions[i], instrumented[i], kern[i]) for i in range(n_head, len(regions))]
-        del regions[n_head:], instrumented[n_head:], kern[n_head:]
+        del regions[n_head:], region_steps[n_head:], instrumented[n_head:], kern[n_head:]
     else:
-        # line-search modes stop trajectories that find no descent: every region is iterations W .. W+K of a fresh
-        # solve, and the line reports how many trajectories were still being solved at the end of it
-        total = W + K
-        for _ in range(R):
+        # line-search modes stop trajectories that find no descent: every region is iterations W .. W+n of a fresh
+        # solve, and the line reports how many trajectories were still being solved at the end of the last one
+        for n in sizes:
+            total = W + n
             solver.solve_begin(x0_q_d, x0_xi_d, us0_d, n_iterations=total, **begin_kw)
             solver.solve_iterate(W)
-            timed_region()
+            timed_region(n)
             res = solver.solve_end()
     torch.cuda.synchronize(dev)
+    dumped = dump_outputs(res, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     active_end = float((res.iters == total).double().mean().item())
     # iterations the trajectories of this rank actually ran inside the last timed region (a stopped trajectory runs none): the
     # line-search lines report the rate over THAT work beside `value`, which counts every trajectory of the batch as iterated
@@ -611,15 +670,16 @@ def run_rank(args, rank, world):
             print("bench.py: WARNING: " + invalid, file=sys.stderr)
 
     if rank == 0:
-        plain = [r for r, ins in zip(regions, instrumented) if not ins]
-        with_ev = [r for r, ins in zip(regions, instrumented) if ins]
+        per_step = [r / n for r, n in zip(regions, region_steps)]   # seconds
+        plain = [s for s, ins in zip(per_step, instrumented) if not ins]
+        with_ev = [s for s, ins in zip(per_step, instrumented) if ins]
         med = statistics.median(plain if plain else with_ev)
         med_ev = statistics.median(with_ev)
-        imed = min((i for i in range(R) if instrumented[i]), key=lambda i: abs(regions[i] - med_ev))
+        imed = min((i for i in range(R) if instrumented[i]), key=lambda i: abs(per_step[i] - med_ev))
         kb, kr, kl = kern[imed]
-        # weak: every rank advanced its own --batch trajectories K times; strong: the one global batch K times
-        value = (world if args.scaling == "weak" else 1) * K / med
-        ms_step = med / K * 1e3
+        # weak: every rank advanced its own --batch trajectories once per step; strong: the one global batch
+        value = (world if args.scaling == "weak" else 1) / med
+        ms_step = med * 1e3
         alg_bytes = alg_bytes_per_knot_iter(m) * B * N          # per launch on this rank (what its kernels process)
         dominant, t_dom = max((("k_backward3", kb), ("k_rollout_lin" if kl == 0.0 else "k_rollout", kr),
                                ("k_linearize", kl)), key=lambda kv: kv[1])
@@ -660,21 +720,23 @@ def run_rank(args, rank, world):
                        "active_fraction_at_region_end": active_end, "all_finite": finite, "all_status_ok": clean,
                        **({"active_normalised": {
                            "trajectory_iterations_run_in_last_region_rank0": worked,
-                           "share_of_batch_x_steps": worked / (B * K),
+                           "share_of_batch_x_steps": worked / (B * region_steps[-1]),
                            "trajectory_iterations_per_s_rank0": worked / (regions[-1] if regions else float("nan")),
                            "note": "value x batch counts a stopped trajectory as iterated; this is the last region's rate over the "
                                    "iterations its trajectories really ran (rank 0's shard)"}} if worked is not None else {}),
                        **({"invalid": invalid} if invalid else {}),
-                       "timed_regions": {"repeats": R, "steps_each": K,
+                       "timed_regions": {"repeats": R, "steps_each": region_steps, "steps_in_all": sum(region_steps),
                                          "reported": ("median of the regions WITHOUT per-kernel events (odd ones); kernel_ms_per_step "
                                                       "from the median region WITH them (even ones)") if plain else
                                                      "the only region(s) carry the per-kernel events",
-                                         "ms_per_step": [r / K * 1e3 for r in regions],
+                                         "ms_per_step": [s * 1e3 for s in per_step],
                                          "with_kernel_events": instrumented,
-                                         "median_ms_per_step_with_kernel_events": med_ev / K * 1e3,
-                                         "min_ms_per_step": min(regions) / K * 1e3,
-                                         "max_ms_per_step": max(regions) / K * 1e3},
-                       **({"fresh_solve": fresh_series(fresh, K, W, fresh_active, world if args.scaling == "weak" else 1, ms_step)} if fresh else {}),
+                                         "median_ms_per_step_with_kernel_events": med_ev * 1e3,
+                                         "min_ms_per_step": min(per_step) * 1e3,
+                                         "max_ms_per_step": max(per_step) * 1e3},
+                       **({"fresh_solve": fresh_series(fresh, sizes[0], W, fresh_active, world if args.scaling == "weak" else 1, ms_step)}
+                          if fresh else {}),
+                       **({"dump_outputs": dumped} if dumped else {}),
                        "kernel_ms_per_step": {"backward": kb, "rollout": kr, "linearize": kl},
                        "kernel_ms_per_step_note": "a HIP event pair per launch (attached to the dispatch of the two hot kernels), measured in the "
                                                   "regions that carry them, whose median step is "

@@ -82,7 +82,7 @@ def test_dry_run_weak_scaling_and_drone_defaults():
     a = bench.parse_args(["--workload", "drone400"])
     assert (a.batch, a.horizon, a.scaling) == (8192, 400, "strong")
     a = bench.parse_args([])
-    assert (a.batch, a.horizon, a.scaling, a.repeats, a.mode) == (4096, 200, "weak", 200, "ms")
+    assert (a.batch, a.horizon, a.scaling, a.repeats, a.fresh_regions, a.mode) == (4096, 200, "weak", 2, 0, "ms")
     # BASELINE configs 2 and 4 at their stated sizes (secondary lines); the SO3 script runs the SS solver
     a = bench.parse_args(["--workload", "so3"])
     assert (a.batch, a.horizon, a.scaling, a.mode) == (1, 100, "weak", "ss")
@@ -137,3 +137,74 @@ def test_profile_lookups_pick_the_fast_sweep_and_fresh_series_shape():
     assert fr["kernel_ms_per_step"]["backward"] == pytest.approx(0.305) and fr["ratio_to_headline_ms_per_step"] == pytest.approx(0.5625 / 0.54)
     ex = bench.executed_fp64_fraction(0.54)   # from the committed profiles/*_sq_mix.json
     assert ex is None or (0.1 < ex["frac"] < 1.0 and len(ex["kernels"]) == 2)
+
+
+def test_steps_are_the_timed_steps_in_all():
+    """--steps K times exactly K steps: the regions of --repeats split them, sizes within one of each other."""
+    assert bench.region_sizes(20, 2) == [10, 10]
+    assert bench.region_sizes(7, 3) == [3, 2, 2]
+    assert bench.region_sizes(3, 200) == [1, 1, 1]
+    assert bench.region_sizes(1, 2) == [1]
+    for K in range(1, 40):
+        for R in (1, 2, 3, 5, 200):
+            s = bench.region_sizes(K, R)
+            assert sum(s) == K and max(s) - min(s) <= 1 and len(s) == min(K, R)
+    for bad in (["--steps", "0"], ["--repeats", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    np = pytest.importorskip("numpy")
+    assert list(bench.dump_sample(10, 100)) == list(range(10))
+    row = 8 * (201 * 22 + 200 * 6 + 4)   # SE3, N = 200: xs_q, xs_xi, us, J, iters, status, index
+    a, b = bench.dump_sample(4096, row), bench.dump_sample(4096, row)
+    assert np.array_equal(a, b) and len(a) * row <= bench.DUMP_BYTES_MAX < (len(a) + 1) * row
+    assert len(np.unique(a)) == len(a) and np.all(np.diff(a) > 0) and a[-1] < 4096
+
+
+def test_dump_outputs_writes_the_caller_arrays_in_float64(tmp_path):
+    """The writer on a result shaped like the solver's (host tensors): names, dtypes, the last iteration's cost."""
+    import types
+    import numpy as np
+    import torch
+    B, N, m, K = 5, 4, 6, 3
+    g = torch.Generator().manual_seed(0)
+    res = types.SimpleNamespace(xs_q=torch.rand(B, N + 1, 4, 4, generator=g, dtype=torch.float64),
+                                xs_xi=torch.rand(B, N + 1, 6, generator=g, dtype=torch.float64),
+                                us=torch.rand(B, N, m, generator=g, dtype=torch.float64),
+                                J_hist=torch.arange(B * K, dtype=torch.float64).reshape(B, K),
+                                iters=torch.tensor([3, 3, 1, 2, 3], dtype=torch.int32), status=torch.zeros(B, dtype=torch.int32))
+    info = bench.dump_outputs(res, str(tmp_path / "d"))
+    got = {f[:-4]: np.load(os.path.join(info["dir"], f)) for f in info["files"]}
+    assert set(got) == {"xs_q", "xs_xi", "us", "J", "iters", "status", "trajectory_index"}
+    assert all(a.dtype == np.float64 for a in got.values()) and info["trajectories"] == B and info["sample"] == "all"
+    assert np.array_equal(got["xs_q"], res.xs_q.numpy()) and np.array_equal(got["us"], res.us.numpy())
+    assert list(got["J"]) == [2.0, 5.0, 6.0, 10.0, 14.0] and list(got["iters"]) == [3, 3, 1, 2, 3]
+    assert info["bytes"] == sum(os.path.getsize(os.path.join(info["dir"], f)) for f in info["files"]) <= bench.DUMP_BYTES_MAX
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_whatever_the_region_split(tmp_path):
+    """Two runs with the same arguments but a different split of the timed steps compute the same outputs, bit for bit, and
+    the line counts exactly --steps timed steps; 2048 x 200 is larger than the 64 MB dump, so the seeded sample is taken."""
+    import numpy as np
+    lines, dumps = [], []
+    for rep in ("1", "3"):
+        d = str(tmp_path / ("r" + rep))
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--repeats", rep,
+                              "--batch", "2048", "--no-cpu-baseline", "--dump-outputs", d], env=_clean_env(), capture_output=True,
+                             text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0]))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    for ln, rep in zip(lines, (1, 3)):
+        tr = ln["config"]["timed_regions"]
+        assert ln["steps"] == 7 and tr["steps_in_all"] == 7 and tr["repeats"] == rep and ln["ms_per_step"] > 0
+        assert ln["config"]["dump_outputs"]["bytes"] <= bench.DUMP_BYTES_MAX
+    a, b = dumps
+    assert set(a) == set(b) == {"xs_q", "xs_xi", "us", "J", "iters", "status", "trajectory_index"}
+    assert 0 < len(a["trajectory_index"]) < 2048 and np.all(a["iters"] == 9) and np.all(a["status"] == 0)
+    assert sum(os.path.getsize(os.path.join(str(tmp_path / "r1"), f)) for f in os.listdir(str(tmp_path / "r1"))) <= bench.DUMP_BYTES_MAX
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k]), k
