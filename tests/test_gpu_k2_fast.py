@@ -1,6 +1,6 @@
 """The backward sweep in two kernels (csrc/tolg_backward3.h, FAST): a fast kernel with only the common path compiled in, the full
 kernel behind it for the groups of four trajectories it hands back (regularisation left on entry, a non-positive pivot at some
-knot, or a group whose last sweep needed the general path).  `TOLG_K2_FULL_ONLY=1` (read at every sweep) keeps every sweep on the
+knot, or a group whose last sweep needed the general path).  `TOLG_K2_FULL_ONLY=1` (read when the handle is created) keeps every sweep on the
 full kernel: the two schedules must take the same decisions and agree to rounding, and both with the oracle -- on a tame problem
 (nothing is ever handed back after the second sweep), on one whose sweeps keep needing the regularisation loop (indefinite R),
 and on a batch that mixes the two kinds inside groups of four."""

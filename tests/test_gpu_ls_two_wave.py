@@ -1,7 +1,7 @@
 """The rollouts of a line-search stage in two wavefronts per sixteen quads (k_rollout_ls2, round 4): one wave carries the twist
 chain (Log of the deviation -> control -> next twist), a second one the pose chain (Exp of the twist -> next pose), one step
 ahead, handing twist and pose over through an LDS ring; the merit search's factors (traopt_controller.py:2713-2716) are formed
-off the chain.  `TOLG_LS_ONEWAVE=1` (read at every stage) keeps the one-wave forms (K3 for the first try, k_rollout_ls): the
+off the chain.  `TOLG_LS_ONEWAVE=1` (read when the handle is created) keeps the one-wave forms (K3 for the first try, k_rollout_ls): the
 two must take the same decisions -- step size per iteration, exit code, iteration count -- and agree to rounding (each wave
 gates its own series evaluation; the one-wave step gates Log and Exp together), and both with the oracle.  Covered: the merit
 search (alpha < 1 steps with the factors) and the backtracking search, stages on the flags (first try) and on compacted lists,

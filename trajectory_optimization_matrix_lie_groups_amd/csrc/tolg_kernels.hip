@@ -3601,6 +3601,93 @@ __global__ void k_export_scalars(Params P, double* J, double* dn, double* grad, 
 // ================================================================================================
 using namespace tolg;
 
+// The kernels that serve one handle: which template instantiation runs for which model is decided once, here, when the
+// handle is created (kernel_table below).  Launch sites pick an entry by what changes from call to call -- the pass of
+// the sweep, AL terms on or off, the rollout form, the search kind, the stage -- and never test the model themselves.
+typedef void (*SearchKernel)(Params, int, int, int);
+typedef void (*SearchRollout)(Params, int, int, int, int);
+struct KernelTable {
+  void (*linearize)(Params, const double*, const double*, double*, double*, int, int, int, int, int);  // K1
+  void (*init_rollout)(Params);
+  void (*sweep[2][2])(Params, int, int);  // K2 [fast][AL terms]
+  void (*rollout_linear)(Params, double, int, int);  // K3: rollout = 'linear'
+  void (*rollout_alpha1)(Params, double, int, int);  //     alpha = 1 (or single shooting): no factors
+  void (*rollout_factor)(Params, double, int, int);
+  void (*rollout_lin)(Params, int);  // the fused accept-always rollout + K1; null where the model or the LDS rules it out
+  void (*ec_ring[2])(Params);        // expected change, ring form [STORE]
+  void (*ec_stmt[2])(Params);        //                  statement form [REDO]
+  void (*affine_commit)(Params, int, int);
+  struct Search {                    // per search kind: ls[0] backtracking (single shooting), ls[1] merit (multiple shooting)
+    struct { SearchRollout k; int nt; } wave2[2];  // k_rollout_ls2 [first try] and its NT (twist waves per pose wave)
+    SearchRollout wave1[2];          // the one-wave forms k_rollout_ls [linear]
+    SearchKernel eval_t[2];          // k_rollout_eval_t [linear]
+    SearchKernel eval, eval_affine;
+  } ls[2];
+};
+
+template <int M, bool MS, int PK>
+static KernelTable::Search search_kernels() {
+  KernelTable::Search s;
+  // the nonlinear rollouts, two wavefronts per sixteen quads: [1] the first try, [0] the stages behind it.  The first try is
+  // one chain (NT = 1; single shooting 542 -> 547 it/s) without factors (those of alpha = 1 are the identity).  The merit
+  // search's later stages are a few hundred quads -- one chain's length -- and a pose wave of its own per sixteen quads keeps
+  // that chain shortest (NT = 1; with NT = 3 merit 596 -> 526 it/s); single shooting's twelve step sizes fill the chip several
+  // times over and gain from fewer waves per quad (NT = 3: SS 517 -> 542).  The pendulum: NT = 1 in every stage.
+  s.wave2[1] = {k_rollout_ls2<M, false, 1, PK>, 1};
+  if constexpr (MS || PK == 1) s.wave2[0] = {k_rollout_ls2<M, MS, 1, PK>, 1};
+  else s.wave2[0] = {k_rollout_ls2<M, false, 3>, 3};
+  s.wave1[0] = k_rollout_ls<M, MS, false, PK>;
+  s.wave1[1] = k_rollout_ls<M, MS, true, PK>;
+  s.eval_t[0] = k_rollout_eval_t<M, MS, false>;
+  s.eval_t[1] = k_rollout_eval_t<M, MS, true>;
+  s.eval = k_ls_eval<M, MS>;
+  s.eval_affine = k_ls_eval_affine<M, MS>;
+  return s;
+}
+// GRAV: gravity; DENSE: inertia blocks that are not diagonal; PEND: Pendulum3dDyanmics (m = 6, gravity)
+template <int M, bool GRAV, bool DENSE, bool PEND>
+static KernelTable kernel_table(int lds_per_block) {
+  constexpr int PK = PEND ? 1 : 0;
+  KernelTable t;
+  t.linearize = k_linearize<M>;
+  t.init_rollout = k_init_rollout<M>;
+  if constexpr (!DENSE && !PEND) {
+    // diagonal inertia blocks and a constant input matrix (every reference script except the pendulum): the third form of
+    // the sweep (tolg_backward3.h)
+    t.sweep[0][0] = k_backward3<M, GRAV, false, false>; t.sweep[0][1] = k_backward3<M, GRAV, true, false>;
+    t.sweep[1][0] = k_backward3<M, GRAV, false, true>;  t.sweep[1][1] = k_backward3<M, GRAV, true, true>;
+  } else {  // dense inertia blocks, the pendulum: the general sweep (the AL terms are a run-time test in it)
+    t.sweep[0][0] = t.sweep[0][1] = k_backward<M, PEND, GRAV, PEND && !DENSE, false>;
+    t.sweep[1][0] = t.sweep[1][1] = k_backward<M, PEND, GRAV, PEND && !DENSE, true>;
+  }
+  t.rollout_linear = k_rollout<M, true, false>;  // (PK = 0 for the pendulum too)
+  t.rollout_alpha1 = k_rollout<M, false, true, PK>;
+  t.rollout_factor = k_rollout<M, false, false, PK>;
+  t.rollout_lin = nullptr;
+  if constexpr (!PEND)
+    if (rl_static_lds<M>() + sizeof(double) * RL_NH * 4 * 16 <= (size_t)lds_per_block) t.rollout_lin = k_rollout_lin<M>;
+  // the ring form reads the velocity block of F_x from the record run for dense inertia blocks and the pendulum, and for the
+  // pendulum also the knot's input-matrix block (VARB)
+  t.ec_ring[0] = k_expected_change_ring<M, GRAV, false, DENSE || PEND, PEND>;
+  t.ec_ring[1] = k_expected_change_ring<M, GRAV, true, DENSE || PEND, PEND>;
+  t.ec_stmt[0] = k_expected_change<M, PK>;
+  t.ec_stmt[1] = k_expected_change<M, PK, true>;
+  t.affine_commit = k_affine_commit<M>;
+  t.ls[0] = search_kernels<M, false, PK>();
+  t.ls[1] = search_kernels<M, true, PK>();
+  return t;
+}
+static KernelTable kernel_table_for(const tolg_problem& p, const Consts& c, int lds_per_block) {
+  const bool dense = c.diagJ == 0;
+  if (p.m == 4)  // the drone: gravity, always
+    return dense ? kernel_table<4, true, true, false>(lds_per_block) : kernel_table<4, true, false, false>(lds_per_block);
+  if (p.kind == TOLG_DYN_PENDULUM3D)
+    return dense ? kernel_table<6, true, true, true>(lds_per_block) : kernel_table<6, true, false, true>(lds_per_block);
+  if (c.grav != 0.0)
+    return dense ? kernel_table<6, true, true, false>(lds_per_block) : kernel_table<6, true, false, false>(lds_per_block);
+  return dense ? kernel_table<6, false, true, false>(lds_per_block) : kernel_table<6, false, false, false>(lds_per_block);
+}
+
 struct tolg_handle_s {
   tolg_problem prob;
   Consts hc;
@@ -3614,6 +3701,10 @@ struct tolg_handle_s {
   bool running;
   int lds_per_block;  // hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KB on MI355X)
   int rec_closed = 0; // the knot records were last written by the fused rollout (no defect field, see k_backward)
+  KernelTable kt;     // the model's kernels (kernel_table_for)
+  // A/B switches of the tests, read from the environment when the handle is created: every sweep the full kernel
+  // (TOLG_K2_FULL_ONLY=1), the one-wave forms of the line-search rollouts (TOLG_LS_ONEWAVE=1)
+  bool k2_full_only, ls_one_wave;
   const double *al_lb, *al_ub, *al_lambda, *al_imu;  // augmented-Lagrangian terms (null = off)
   // early exit of a sliced solve (tolg_solve_iterate_until): two device counters, their pinned host copies, two events
   int *d_cnt = nullptr, *h_cnt = nullptr;
@@ -3744,10 +3835,6 @@ __global__ __launch_bounds__(256) void k_poison_lds() {
   __syncthreads();
   if (junk[(threadIdx.x * 33) & 8191] == 0.0) __builtin_trap();  // keeps the stores alive; never true
 }
-static bool getenv_flag(const char* name) {  // (read at every call: a handful of launches per iteration; used by A/B tests only)
-  const char* e = getenv(name);
-  return e && e[0] == '1';
-}
 static bool poison_lds_mode() {
   static const bool v = [] { const char* e = getenv("TOLG_POISON_LDS"); return e && e[0] == '1'; }();
   return v;
@@ -3845,6 +3932,13 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
         }
         c.Llin[a][6 * i + j] = sacc * prob->dt;
       }
+  }
+  h->kt = kernel_table_for(*prob, c, h->lds_per_block);
+  {
+    const char* e = getenv("TOLG_K2_FULL_ONLY");
+    h->k2_full_only = e && e[0] == '1';
+    e = getenv("TOLG_LS_ONEWAVE");
+    h->ls_one_wave = e && e[0] == '1';
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   Consts* dc = nullptr;
@@ -3954,67 +4048,34 @@ static Params params_for(tolg_handle_s* h, int B) {
   return P;
 }
 
-template <int M>
 static int run_linearize(tolg_handle_s* h, const Params& P, hipStream_t st, const double* src, const double* src_u,
                          double* dst, double* dst_u, int ms, int i0 = 0, int ni = -1, int ls_list = -1, int ls_nslots = 0) {
   if (ni < 0) ni = P.N + 1;
   size_t n = (size_t)ni * P.Bp;
   h->rec_closed = 0;  // K1 writes the defect field
   Timed t(h, st, 2);
-  hipLaunchKernelGGL(k_linearize<M>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, src, src_u, dst, dst_u, ms,
+  hipLaunchKernelGGL(h->kt.linearize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, src, src_u, dst, dst_u, ms,
                      i0, ni, ls_list, ls_nslots);
   LAUNCH_CHECK();
   return 0;
 }
-template <int M>
 static int run_backward(tolg_handle_s* h, const Params& P, hipStream_t st, int it, int ms) {
-  const bool dj = h->hc.diagJ != 0;
   ms = (ms ? 1 : 0) | (h->rec_closed ? 2 : 0);
   const dim3 grid(P.Bp / 4), blk(64);
-  // diagonal inertia blocks and a constant input matrix (every reference script except the pendulum): the third form
-  // of the sweep (tolg_backward3.h).  Dense inertia and the pendulum keep k_backward.
-  if (dj && h->prob.kind != TOLG_DYN_PENDULUM3D) {
-    const bool al = P.al_lb != nullptr, grav = h->hc.grav != 0.0;
-    // From the second sweep of a solve on: the fast kernel (no general path compiled in: 254 registers instead of 395), then
-    // the full kernel for the groups it handed back (flag bit 2) -- usually none.  The first sweep starts from mu = 1
-    // (traopt_controller.py:2394): straight to the full kernel; so do the one-sweep entry points (it < 0).
-    const bool fast = it > 0 && !getenv_flag("TOLG_K2_FULL_ONLY");
-    for (int pass = fast ? 0 : 1; pass < 2; pass++) {
-      Timed t(h, st, 0, true);  // each pass is one launch: timed through its dispatch
-      t.count = (pass == 0) || !fast;
-      const int fl = ms | ((pass == 1 && fast) ? 4 : 0);
-      if (pass == 0) {
-        if (!grav) { if (al) t.launch(k_backward3<M, false, true, true>, grid, blk, P, it, fl); else t.launch(k_backward3<M, false, false, true>, grid, blk, P, it, fl); }
-        else { if (al) t.launch(k_backward3<M, true, true, true>, grid, blk, P, it, fl); else t.launch(k_backward3<M, true, false, true>, grid, blk, P, it, fl); }
-      } else {
-        if (!grav) { if (al) t.launch(k_backward3<M, false, true, false>, grid, blk, P, it, fl); else t.launch(k_backward3<M, false, false, false>, grid, blk, P, it, fl); }
-        else { if (al) t.launch(k_backward3<M, true, true, false>, grid, blk, P, it, fl); else t.launch(k_backward3<M, true, false, false>, grid, blk, P, it, fl); }
-      }
-      LAUNCH_CHECK();
-    }
-    return 0;
-  }
-  // dense inertia blocks, the pendulum: the general sweep, in the same two passes
-  const bool fast = it > 0 && !getenv_flag("TOLG_K2_FULL_ONLY");
+  const bool al = P.al_lb != nullptr;
+  // From the second sweep of a solve on: the fast kernel (the third form: no general path compiled in, 254 registers instead
+  // of 395), then the full kernel for the groups it handed back (flag bit 2) -- usually none.  The first sweep starts from
+  // mu = 1 (traopt_controller.py:2394): straight to the full kernel; so do the one-sweep entry points (it < 0).
+  const bool fast = it > 0 && !h->k2_full_only;
   for (int pass = fast ? 0 : 1; pass < 2; pass++) {
-    Timed t(h, st, 0, true);
+    Timed t(h, st, 0, true);  // each pass is one launch: timed through its dispatch
     t.count = (pass == 0) || !fast;
     const int fl = ms | ((pass == 1 && fast) ? 4 : 0);
-    if (M == 6 && h->prob.kind == TOLG_DYN_PENDULUM3D) {
-      if (pass == 0) { if (dj) t.launch(k_backward<6, true, true, true, true>, grid, blk, P, it, fl); else t.launch(k_backward<6, true, true, false, true>, grid, blk, P, it, fl); }
-      else { if (dj) t.launch(k_backward<6, true, true, true, false>, grid, blk, P, it, fl); else t.launch(k_backward<6, true, true, false, false>, grid, blk, P, it, fl); }
-    } else if (M == 6 && h->hc.grav == 0.0) {
-      if (pass == 0) t.launch(k_backward<6, false, false, false, true>, grid, blk, P, it, fl);
-      else t.launch(k_backward<6, false, false, false, false>, grid, blk, P, it, fl);
-    } else {
-      if (pass == 0) t.launch(k_backward<M, false, true, false, true>, grid, blk, P, it, fl);
-      else t.launch(k_backward<M, false, true, false, false>, grid, blk, P, it, fl);
-    }
+    t.launch(h->kt.sweep[pass == 0][al], grid, blk, P, it, fl);
     LAUNCH_CHECK();
   }
   return 0;
 }
-template <int M>
 static int run_rollout_ms(tolg_handle_s* h, const Params& P, hipStream_t st, double alpha, int linear, int ms = 1,
                           int i0 = 0, int i1 = -1) {
   if (i1 < 0) i1 = P.N;
@@ -4023,52 +4084,30 @@ static int run_rollout_ms(tolg_handle_s* h, const Params& P, hipStream_t st, dou
   // different CUs: the sweep streams ~16 KB per wave-step from HBM and one CU sustains ~10 B/cycle of
   // misses (4 waves on one CU: 0.96 ms instead of 0.47, SQ_VMEM_TA_*_FIFO_FULL x7)
   dim3 grid((P.Bp * 4 + 63) / 64), blk(64);
-  if (linear) hipLaunchKernelGGL((k_rollout<M, true, false>), grid, blk, 0, st, P, alpha, i0, i1);
-  else if (M == 6 && h->prob.kind == TOLG_DYN_PENDULUM3D) {
-    if (alpha == 1.0 || !ms) hipLaunchKernelGGL((k_rollout<6, false, true, 1>), grid, blk, 0, st, P, alpha, i0, i1);
-    else hipLaunchKernelGGL((k_rollout<6, false, false, 1>), grid, blk, 0, st, P, alpha, i0, i1);
-  }
-  else if (alpha == 1.0 || !ms) hipLaunchKernelGGL((k_rollout<M, false, true>), grid, blk, 0, st, P, alpha, i0, i1);
-  else hipLaunchKernelGGL((k_rollout<M, false, false>), grid, blk, 0, st, P, alpha, i0, i1);
+  const KernelTable& T = h->kt;
+  hipLaunchKernelGGL(linear ? T.rollout_linear : (alpha == 1.0 || !ms) ? T.rollout_alpha1 : T.rollout_factor, grid, blk, 0,
+                     st, P, alpha, i0, i1);
   LAUNCH_CHECK();
   return 0;
 }
-// the merit search's preparation in its ring form (tolg_expected_change.h): gravity / dense-inertia instantiations
-template <int M>
-static void launch_ec_ring(const tolg_handle_s* h, const Params& P, hipStream_t st) {
-  const dim3 gr(P.Bp / 4), blk(64);
-  const bool grav = h->hc.grav != 0.0, dense = P.fA22 >= 0;
-  if (M == 6 && h->prob.kind == TOLG_DYN_PENDULUM3D) {
-    hipLaunchKernelGGL((k_expected_change_ring<6, true, false, true, true>), gr, blk, 0, st, P);
-  } else if (dense) {
-    if (grav) hipLaunchKernelGGL((k_expected_change_ring<M, true, false, true>), gr, blk, 0, st, P);
-    else hipLaunchKernelGGL((k_expected_change_ring<M, false, false, true>), gr, blk, 0, st, P);
-  } else {
-    if (grav) hipLaunchKernelGGL((k_expected_change_ring<M, true>), gr, blk, 0, st, P);
-    else hipLaunchKernelGGL((k_expected_change_ring<M, false>), gr, blk, 0, st, P);
-  }
+// the merit search's expected cost change and defect weight (tolg_expected_change.h): the affine recursion in the backward
+// sweep's lane map, inputs through an LDS ring (STORE: e_i and du_i left in P.ED), and the statement-by-statement form, four
+// lanes per trajectory (REDO: only the trajectories the ring form handed back -- rotation deviations near pi)
+static void launch_ec_ring(const tolg_handle_s* h, const Params& P, hipStream_t st, bool store) {
+  hipLaunchKernelGGL(h->kt.ec_ring[store], dim3(P.Bp / 4), dim3(64), 0, st, P);
 }
-// rollout = 'linear', models of the third backward form: the alpha = 1 linear rollout as an affine recursion, e_i and du_i
-// left in P.ED (tolg_expected_change.h, STORE), plus -- what the kernel is named after -- the expected cost change and the
-// defect weight of the merit search.  The trajectories it hands back get their expected change from the statement form.
-template <int M>
+static void launch_ec_stmt(const tolg_handle_s* h, const Params& P, hipStream_t st, bool redo) {
+  hipLaunchKernelGGL(h->kt.ec_stmt[redo], dim3((P.Bp * 4 + 63) / 64), dim3(64), 0, st, P);
+}
+// rollout = 'linear': the alpha = 1 linear rollout as an affine recursion, e_i and du_i left in P.ED (the ring form, STORE),
+// plus -- what the kernel is named after -- the expected cost change and the defect weight of the merit search.  The
+// trajectories it hands back get their expected change from the statement form.
 static int run_affine_dev(tolg_handle_s* h, const Params& P, hipStream_t st, bool merit) {
   Timed t(h, st, 1);
-  const dim3 gr(P.Bp / 4), blk(64);
-  const bool pend = M == 6 && h->prob.kind == TOLG_DYN_PENDULUM3D;
-  if (pend) {  // (the knot's input-matrix block from the record run as well)
-    hipLaunchKernelGGL((k_expected_change_ring<6, true, true, true, true>), gr, blk, 0, st, P);
-  } else if (P.fA22 >= 0) {  // dense inertia blocks: the velocity block from the record run
-    if (h->hc.grav != 0.0) hipLaunchKernelGGL((k_expected_change_ring<M, true, true, true>), gr, blk, 0, st, P);
-    else hipLaunchKernelGGL((k_expected_change_ring<M, false, true, true>), gr, blk, 0, st, P);
-  } else {
-    if (h->hc.grav != 0.0) hipLaunchKernelGGL((k_expected_change_ring<M, true, true>), gr, blk, 0, st, P);
-    else hipLaunchKernelGGL((k_expected_change_ring<M, false, true>), gr, blk, 0, st, P);
-  }
+  launch_ec_ring(h, P, st, true);
   LAUNCH_CHECK();
   if (merit) {
-    if (pend) hipLaunchKernelGGL((k_expected_change<6, 1, true>), dim3((P.Bp * 4 + 63) / 64), dim3(64), 0, st, P);
-    else hipLaunchKernelGGL((k_expected_change<M, 0, true>), dim3((P.Bp * 4 + 63) / 64), dim3(64), 0, st, P);
+    launch_ec_stmt(h, P, st, true);
     LAUNCH_CHECK();
   }
   return 0;
@@ -4077,70 +4116,47 @@ static int run_affine_dev(tolg_handle_s* h, const Params& P, hipStream_t st, boo
 // stage = 0, 1, 2 ...: stage 0 takes the undecided trajectories from the flags (all active ones), stage s > 0 from the
 // list select s - 1 compacted (lists alternate: select s fills list s & 1 while this stage's kernels read the other).
 // A one-alpha stage writes its candidate in place (no slot, no copy).
-template <int M, bool MS>
+template <bool MS>
 static int run_ls_stage(tolg_handle_s* h, const Params& P, hipStream_t st, int stage, int a0, int n, int linear,
                         hipEvent_t before_select = nullptr, bool last = false) {
   const int direct = n == 1;
   if (n > NSLOT) return TOLG_E_ARG;
-  const bool pend = M == 6 && h->prob.kind == TOLG_DYN_PENDULUM3D;
+  const KernelTable::Search& S = h->kt.ls[MS];
   const int list_in = stage == 0 ? -1 : (stage - 1) & 1, list_out = stage & 1;
   // the first try, alpha = 1: x^+ = f(x^, u^) for single shooting (:2073-2080) and for the merit search alike (the
   // factors of :2713-2716 are the identity: note at the record layout) -- K3 itself, written straight into the candidate
   // arrays (every active trajectory is undecided at this point)
   const bool k3 = direct && a0 == 0 && !linear;
-  // the rollouts of a stage in two wavefronts per sixteen quads (k_rollout_ls2): the nonlinear rollouts of every model (PK = 1: the
-  // pendulum); TOLG_LS_ONEWAVE=1 keeps the one-wave forms (K3 for the first try, k_rollout_ls) for comparisons
-  const bool two = !linear && !getenv_flag("TOLG_LS_ONEWAVE");
+  // the nonlinear rollouts of a stage in two wavefronts per sixteen quads (k_rollout_ls2); TOLG_LS_ONEWAVE=1 keeps the
+  // one-wave forms (K3 for the first try, k_rollout_ls) for comparisons
+  const bool two = !linear && !h->ls_one_wave;
   if (k3 && !two) {
-    int rc = run_rollout_ms<M>(h, P, st, 1.0, 0, MS ? 1 : 0);
+    int rc = run_rollout_ms(h, P, st, 1.0, 0, MS ? 1 : 0);
     if (rc) return rc;
   }
   {
     Timed t(h, st, 1);
     if (!direct && (size_t)P.Bp * n > (size_t)LS_QUAD_MAX) {  // the thread form of a wide stage: runs when the list is long
                                                                // (ls_quad_form), leaves at once otherwise; not launched where no list of this batch can be that long
-      dim3 grid((P.Bp + 63) / 64, n), blk(64);
-      if (linear) hipLaunchKernelGGL((k_rollout_eval_t<M, MS, true>), grid, blk, 0, st, P, a0, n, list_in);
-      else hipLaunchKernelGGL((k_rollout_eval_t<M, MS, false>), grid, blk, 0, st, P, a0, n, list_in);
+      hipLaunchKernelGGL(S.eval_t[linear != 0], dim3((P.Bp + 63) / 64, n), dim3(64), 0, st, P, a0, n, list_in);
       LAUNCH_CHECK();
     }
-    {
-      dim3 grid((P.Bp * 4 + 63) / 64, n), blk(64);  // four lanes per (trajectory, alpha)
-      if (two) {
-        // twist waves per workgroup (k_rollout_ls2): the merit search's stages are a few hundred quads -- one chain's length, and
-        // a pose wave of its own per sixteen quads keeps that chain shortest (NT = 1; with NT = 3 merit 596 -> 526 it/s); single
-        // shooting's twelve step sizes fill the chip several times over and gain from fewer waves per quad (NT = 3: SS 517 -> 542)
-        if (pend) {  // (m = 6 only; one twist wave per pose wave in every stage)
-          const dim3 g2((P.Bp + 15) / 16, n), b2(128);
-          if (MS && !k3) hipLaunchKernelGGL((k_rollout_ls2<6, true, 1, 1>), g2, b2, 0, st, P, a0, n, direct, list_in);
-          else hipLaunchKernelGGL((k_rollout_ls2<6, false, 1, 1>), g2, b2, 0, st, P, a0, n, direct, list_in);
-        } else if (MS) {
-          const dim3 g2((P.Bp + 15) / 16, n), b2(128);
-          if (!k3) hipLaunchKernelGGL((k_rollout_ls2<M, true, 1>), g2, b2, 0, st, P, a0, n, direct, list_in);
-          else hipLaunchKernelGGL((k_rollout_ls2<M, false, 1>), g2, b2, 0, st, P, a0, n, direct, list_in);
-        } else if (direct) {  // (its first try is one chain again: NT = 1, 542 -> 547)
-          hipLaunchKernelGGL((k_rollout_ls2<M, false, 1>), dim3((P.Bp + 15) / 16, n), dim3(128), 0, st, P, a0, n, direct, list_in);
-        } else {
-          hipLaunchKernelGGL((k_rollout_ls2<M, false, 3>), dim3((P.Bp + 47) / 48, n), dim3(256), 0, st, P, a0, n, direct, list_in);
-        }
-      } else if (k3) {
-      } else if (pend) {
-        if (linear) hipLaunchKernelGGL((k_rollout_ls<6, MS, true, 1>), grid, blk, 0, st, P, a0, n, direct, list_in);
-        else hipLaunchKernelGGL((k_rollout_ls<6, MS, false, 1>), grid, blk, 0, st, P, a0, n, direct, list_in);
-      } else {
-        if (linear) hipLaunchKernelGGL((k_rollout_ls<M, MS, true, 0>), grid, blk, 0, st, P, a0, n, direct, list_in);
-        else hipLaunchKernelGGL((k_rollout_ls<M, MS, false, 0>), grid, blk, 0, st, P, a0, n, direct, list_in);
-      }
-      LAUNCH_CHECK();
+    if (two) {  // NT twist waves beside each pose wave, sixteen quads per twist wave
+      const int nt = S.wave2[k3].nt;
+      hipLaunchKernelGGL(S.wave2[k3].k, dim3((P.Bp + 16 * nt - 1) / (16 * nt), n), dim3(64 * (nt + 1)), 0, st, P, a0, n,
+                         direct, list_in);
+    } else if (!k3) {  // four lanes per (trajectory, alpha)
+      hipLaunchKernelGGL(S.wave1[linear != 0], dim3((P.Bp * 4 + 63) / 64, n), dim3(64), 0, st, P, a0, n, direct, list_in);
     }
+    LAUNCH_CHECK();
     const size_t nn = (size_t)(P.N + 1) * P.Bp;
     const unsigned evb = (unsigned)(P.N + 1) * (unsigned)((P.Bp + 255) / 256);  // (knot, 256 candidates) blocks: k_ls_eval
-    hipLaunchKernelGGL((k_ls_eval<M, MS>), dim3(evb, n), dim3(256), 0, st, P, n, direct, list_in);
+    hipLaunchKernelGGL(S.eval, dim3(evb, n), dim3(256), 0, st, P, n, direct, list_in);
     LAUNCH_CHECK();
     hipLaunchKernelGGL((k_ls_sum<MS>), dim3((unsigned)(((size_t)P.Bp * n + 63) / 64)), dim3(64), 0, st, P, a0, n, list_in, 0);
     LAUNCH_CHECK();
     if (P.affine) {  // the candidates that come from the affine recursion: built where they are evaluated
-      hipLaunchKernelGGL((k_ls_eval_affine<M, MS>), dim3(evb, n), dim3(256), 0, st, P, a0, n, list_in);
+      hipLaunchKernelGGL(S.eval_affine, dim3(evb, n), dim3(256), 0, st, P, a0, n, list_in);
       LAUNCH_CHECK();
       hipLaunchKernelGGL((k_ls_sum<MS>), dim3((unsigned)(((size_t)P.Bp * n + 63) / 64)), dim3(64), 0, st, P, a0, n, list_in, 1);
       LAUNCH_CHECK();
@@ -4159,7 +4175,7 @@ static int run_ls_stage(tolg_handle_s* h, const Params& P, hipStream_t st, int s
   }
   if (P.affine) {
     size_t nn = (size_t)(P.N + 1) * P.Bp;
-    hipLaunchKernelGGL(k_affine_commit<M>, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, P, a0, 0);
+    hipLaunchKernelGGL(h->kt.affine_commit, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, P, a0, 0);
     LAUNCH_CHECK();
   }
   if (!keep) {  // (kept: k_linearize still needs ls_slot AND the length of this stage's list, which decides where a candidate lies;
@@ -4171,42 +4187,40 @@ static int run_ls_stage(tolg_handle_s* h, const Params& P, hipStream_t st, int s
 }
 
 // iLQR_Tracking_SE3_MS loop body (traopt_controller.py:2522-2626)
-template <int M>
 static int iterate_ms(tolg_handle_s* h, const Params& P, const tolg_options* opt, hipStream_t st, int it0, int n) {
   int rc;
   for (int it = it0; it < it0 + n; it++) {
     int ls_list_last = -1, ls_n_last = 0;  // set by the merit search below: where its last stage left what it accepted
-    if ((rc = run_backward<M>(h, P, st, it, 1))) return rc;
-    if (!opt->line_search && !opt->rollout_linear && h->prob.kind != TOLG_DYN_PENDULUM3D &&
-        opt->schedule != TOLG_SCHED_SPLIT && rl_static_lds<M>() + sizeof(double) * RL_NH * 4 * 16 <= (size_t)h->lds_per_block) {
+    if ((rc = run_backward(h, P, st, it, 1))) return rc;
+    if (!opt->line_search && !opt->rollout_linear && opt->schedule != TOLG_SCHED_SPLIT && h->kt.rollout_lin) {
       // accept-always nonlinear rollout and the re-linearisation of the new trajectory in one launch
       {
         Timed t(h, st, 1, true);
-        t.launch(k_rollout_lin<M>, dim3((P.Bp + 15) / 16), dim3(256), P, it);
+        t.launch(h->kt.rollout_lin, dim3((P.Bp + 15) / 16), dim3(256), P, it);
         LAUNCH_CHECK();
         h->rec_closed = 1;  // its records carry no defect field (zero by construction): K2 reads zeros instead
       }
       continue;  // the fused launch also sums the costs and does the bookkeeping of k_reduce
     } else if (!opt->line_search) {
       if (P.affine) {  // x^ = x (+) e, u^ = u + du from the affine recursion; the statement form for what it hands back
-        if ((rc = run_affine_dev<M>(h, P, st, false))) return rc;
+        if ((rc = run_affine_dev(h, P, st, false))) return rc;
         Timed t(h, st, 1);
         const size_t nn = (size_t)(P.N + 1) * P.Bp;
-        hipLaunchKernelGGL(k_affine_commit<M>, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, P, 0, 1);
+        hipLaunchKernelGGL(h->kt.affine_commit, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, P, 0, 1);
         LAUNCH_CHECK();
       }
-      if ((rc = run_rollout_ms<M>(h, P, st, 1.0, opt->rollout_linear))) return rc;
+      if ((rc = run_rollout_ms(h, P, st, 1.0, opt->rollout_linear))) return rc;
     } else if (P.affine) {
       hipLaunchKernelGGL(k_ls_begin, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it == 0 ? 1 : 0);
       LAUNCH_CHECK();
-      if ((rc = run_affine_dev<M>(h, P, st, true))) return rc;
-      if ((rc = run_ls_stage<M, true>(h, P, st, 0, 0, 1, 1))) return rc;
-      if ((rc = run_ls_stage<M, true>(h, P, st, 1, 1, 4, 1))) return rc;
+      if ((rc = run_affine_dev(h, P, st, true))) return rc;
+      if ((rc = run_ls_stage<true>(h, P, st, 0, 0, 1, 1))) return rc;
+      if ((rc = run_ls_stage<true>(h, P, st, 1, 1, 4, 1))) return rc;
       // (8 + 7 here: on the affine path the deep stages are not empty -- a sixth of the benchmark's trajectories search to the
       // end -- and one stage of 15 was measured slower, 531 -> 487 it/s)
-      if ((rc = run_ls_stage<M, true>(h, P, st, 2, 5, 8, 1))) return rc;
+      if ((rc = run_ls_stage<true>(h, P, st, 2, 5, 8, 1))) return rc;
       if (!so3_family(h->prob.kind))
-        if ((rc = run_ls_stage<M, true>(h, P, st, 3, 13, 7, 1))) return rc;
+        if ((rc = run_ls_stage<true>(h, P, st, 3, 13, 7, 1))) return rc;
       hipLaunchKernelGGL(k_ls_finish, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it);
       LAUNCH_CHECK();
     } else {
@@ -4227,19 +4241,12 @@ static int iterate_ms(tolg_handle_s* h, const Params& P, const tolg_options* opt
         h->side_ev[0] = ev[0]; h->side_ev[1] = ev[1]; h->side = sd;
       }
       if (hipEventRecord(h->side_ev[0], st) != hipSuccess || hipStreamWaitEvent(h->side, h->side_ev[0], 0) != hipSuccess) return TOLG_E_LAUNCH;
-      if (M == 6 && h->prob.kind == TOLG_DYN_PENDULUM3D && opt->schedule == TOLG_SCHED_SPLIT)
-        hipLaunchKernelGGL((k_expected_change<6, 1>), dim3((P.Bp * 4 + 63) / 64), dim3(64), 0, h->side, P);
-      else if (opt->schedule != TOLG_SCHED_SPLIT) {
-        // the affine recursion in the backward sweep's lane map, inputs through an LDS ring (tolg_expected_change.h);
-        // behind it the statement-by-statement form for the trajectories it hands back (rotation deviations near pi)
-        launch_ec_ring<M>(h, P, h->side);
+      if (opt->schedule != TOLG_SCHED_SPLIT) {  // the ring form; behind it the statement form for what it hands back
+        launch_ec_ring(h, P, h->side, false);
         LAUNCH_CHECK();
-        if (M == 6 && h->prob.kind == TOLG_DYN_PENDULUM3D)
-          hipLaunchKernelGGL((k_expected_change<6, 1, true>), dim3((P.Bp * 4 + 63) / 64), dim3(64), 0, h->side, P);
-        else
-          hipLaunchKernelGGL((k_expected_change<M, 0, true>), dim3((P.Bp * 4 + 63) / 64), dim3(64), 0, h->side, P);
+        launch_ec_stmt(h, P, h->side, true);
       } else
-        hipLaunchKernelGGL((k_expected_change<M, 0>), dim3((P.Bp * 4 + 63) / 64), dim3(64), 0, h->side, P);
+        launch_ec_stmt(h, P, h->side, false);
       LAUNCH_CHECK();
       if (hipEventRecord(h->side_ev[1], h->side) != hipSuccess) return TOLG_E_LAUNCH;
       // staged: the first try alone (one quad rollout, written in place), then 4 + 8 (+ 7) alphas of the trajectories
@@ -4249,22 +4256,22 @@ static int iterate_ms(tolg_handle_s* h, const Params& P, const tolg_options* opt
       // (the first TWO step sizes in the first stage -- most trajectories that reject the first accept the second -- was
       // measured: 432 -> 387 it/s; 512 rollout waves of the general MS step beside the expected-change kernel cost more
       // than the nearly empty second stage saves)
-      if ((rc = run_ls_stage<M, true>(h, P, st, 0, 0, 1, opt->rollout_linear, h->side_ev[1]))) return rc;
+      if ((rc = run_ls_stage<true>(h, P, st, 0, 0, 1, opt->rollout_linear, h->side_ev[1]))) return rc;
       // (round 4: 1 + 12 + 7 instead of 1 + 4 + 8 + 7 -- one latency chain fewer -- measured: 455 -> 418 it/s; the twelve-wide
       // stage rolls out eight step sizes nobody needed for most of its trajectories)
       // (the last stage leaves what it accepted in its slots: the re-linearisation reads it there)
       const bool so3f = so3_family(h->prob.kind);
-      if ((rc = run_ls_stage<M, true>(h, P, st, 1, 1, 4, opt->rollout_linear))) return rc;
+      if ((rc = run_ls_stage<true>(h, P, st, 1, 1, 4, opt->rollout_linear))) return rc;
       // (round 4, end: the step sizes 5 .. 19 in ONE last stage instead of 8 + 7 -- both are nearly empty on every workload seen,
       // and an empty stage is still seven small launches, 0.05 ms of a 1.6 ms iteration)
-      if ((rc = run_ls_stage<M, true>(h, P, st, 2, 5, so3f ? 8 : 15, opt->rollout_linear, nullptr, true))) return rc;
+      if ((rc = run_ls_stage<true>(h, P, st, 2, 5, so3f ? 8 : 15, opt->rollout_linear, nullptr, true))) return rc;
       hipLaunchKernelGGL(k_ls_finish, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it);
       LAUNCH_CHECK();
       ls_list_last = 1;   // the list the last stage ran on: (stage - 1) & 1
       ls_n_last = so3f ? 8 : 15;
     }
     // the accepted candidate becomes the nominal trajectory while it is re-linearised
-    if ((rc = run_linearize<M>(h, P, st, P.cand, P.cand_u, P.cur, P.cur_u, 1, 0, -1, ls_list_last, ls_n_last))) return rc;
+    if ((rc = run_linearize(h, P, st, P.cand, P.cand_u, P.cur, P.cur_u, 1, 0, -1, ls_list_last, ls_n_last))) return rc;
     hipLaunchKernelGGL(k_reduce, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it);
     LAUNCH_CHECK();
   }
@@ -4273,24 +4280,23 @@ static int iterate_ms(tolg_handle_s* h, const Params& P, const tolg_options* opt
 
 // iLQR_Tracking_SE3 loop body (traopt_controller.py:1926-2007): gradient test and backward pass share
 // one sweep; 13-alpha backtracking in two speculative stages (the first try, then the other twelve)
-template <int M>
 static int iterate_ss(tolg_handle_s* h, const Params& P, const tolg_options* opt, hipStream_t st, int it0, int n) {
   int rc;
   for (int it = it0; it < it0 + n; it++) {
-    if ((rc = run_backward<M>(h, P, st, it, 0))) return rc;
+    if ((rc = run_backward(h, P, st, it, 0))) return rc;
     hipLaunchKernelGGL(k_ls_begin, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, 0);
     LAUNCH_CHECK();
-    if (P.affine && (rc = run_affine_dev<M>(h, P, st, false))) return rc;
-    if ((rc = run_ls_stage<M, false>(h, P, st, 0, 0, 1, opt->rollout_linear))) return rc;
+    if (P.affine && (rc = run_affine_dev(h, P, st, false))) return rc;
+    if ((rc = run_ls_stage<false>(h, P, st, 0, 0, 1, opt->rollout_linear))) return rc;
     // (1 + 4 + 8 like the merit search was measured: 405 -> 339 it/s on iterations 3..23 of the benchmark solve, whose
     // searches end at the 6th to 10th step size -- tools/ls_alpha_histogram.py; it would pay from iteration ~45 on, where
     // the median accepted step size is the second one)
-    if ((rc = run_ls_stage<M, false>(h, P, st, 1, 1, NALPHA_SS - 1, opt->rollout_linear, nullptr, true))) return rc;
+    if ((rc = run_ls_stage<false>(h, P, st, 1, 1, NALPHA_SS - 1, opt->rollout_linear, nullptr, true))) return rc;
     hipLaunchKernelGGL(k_ls_finish, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it);
     LAUNCH_CHECK();
     // (what the twelve-alpha stage accepted is read from its slots -- no k_ls_copy: 0.15-0.2 ms of a 2.4 ms iteration; on the
     // affine path the candidates are in the candidate arrays, where k_affine_commit wrote them)
-    if ((rc = run_linearize<M>(h, P, st, P.cand, P.cand_u, P.cur, P.cur_u, 0, 0, -1, 0, P.affine ? 0 : NALPHA_SS - 1))) return rc;
+    if ((rc = run_linearize(h, P, st, P.cand, P.cand_u, P.cur, P.cur_u, 0, 0, -1, 0, P.affine ? 0 : NALPHA_SS - 1))) return rc;
     hipLaunchKernelGGL(k_reduce, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it);
     LAUNCH_CHECK();
   }
@@ -4317,12 +4323,10 @@ extern "C" int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_
   hipLaunchKernelGGL(k_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, d_x0_q, d_x0_xi, d_us_init, ms);
   LAUNCH_CHECK();
   if (!ms) {  // SS: dynamically feasible initial trajectory (_init_rollout, traopt_controller.py:2015-2028)
-    if (P.m == 4) hipLaunchKernelGGL(k_init_rollout<4>, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
-    else hipLaunchKernelGGL(k_init_rollout<6>, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(h->kt.init_rollout, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
     LAUNCH_CHECK();
   }
-  int rc = (P.m == 4) ? run_linearize<4>(h, P, st, P.cur, P.cur_u, nullptr, nullptr, ms)
-                      : run_linearize<6>(h, P, st, P.cur, P.cur_u, nullptr, nullptr, ms);
+  int rc = run_linearize(h, P, st, P.cur, P.cur_u, nullptr, nullptr, ms);
   if (rc) return rc;
   hipLaunchKernelGGL(k_reduce, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, -1);
   LAUNCH_CHECK();
@@ -4334,13 +4338,8 @@ extern "C" int tolg_solve_iterate(tolg_handle_t h, int32_t n_iter, void* stream)
   if (!h || !h->running || n_iter < 0) return TOLG_E_ARG;
   if (h->run_it + n_iter > h->run_opt.max_iter) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc;
-  if (h->run_opt.mode == TOLG_MODE_MS)
-    rc = (h->run.m == 4) ? iterate_ms<4>(h, h->run, &h->run_opt, st, h->run_it, n_iter)
-                         : iterate_ms<6>(h, h->run, &h->run_opt, st, h->run_it, n_iter);
-  else
-    rc = (h->run.m == 4) ? iterate_ss<4>(h, h->run, &h->run_opt, st, h->run_it, n_iter)
-                         : iterate_ss<6>(h, h->run, &h->run_opt, st, h->run_it, n_iter);
+  const int rc = (h->run_opt.mode == TOLG_MODE_MS) ? iterate_ms(h, h->run, &h->run_opt, st, h->run_it, n_iter)
+                                                   : iterate_ss(h, h->run, &h->run_opt, st, h->run_it, n_iter);
   if (rc) return rc;
   h->run_it += n_iter;
   return 0;
@@ -4481,14 +4480,10 @@ extern "C" int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_r
                      (const double*)d_mu_delta);
   LAUNCH_CHECK();
   int rc;
-  if (P.m == 4) {
-    if ((rc = run_linearize<4>(h, P, st, P.cur, P.cur_u, nullptr, nullptr, ms))) return rc;
-  } else {
-    if ((rc = run_linearize<6>(h, P, st, P.cur, P.cur_u, nullptr, nullptr, ms))) return rc;
-  }
+  if ((rc = run_linearize(h, P, st, P.cur, P.cur_u, nullptr, nullptr, ms))) return rc;
   hipLaunchKernelGGL(k_reduce, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, -1);
   LAUNCH_CHECK();
-  if ((rc = (P.m == 4) ? run_backward<4>(h, P, st, -1, ms) : run_backward<6>(h, P, st, -1, ms))) return rc;
+  if ((rc = run_backward(h, P, st, -1, ms))) return rc;
   size_t ne = (size_t)(P.N + 1) * B;
   hipLaunchKernelGGL(k_export_lin, dim3((unsigned)((ne + 127) / 128)), dim3(128), 0, st, P, d_Fx, d_d, d_lx, d_lxx11,
                      d_k, d_K);
@@ -4509,8 +4504,7 @@ extern "C" int tolg_eval_knot(tolg_handle_t h, int32_t i, int32_t n, const doubl
   Params P = params_for(h, n);
   hipLaunchKernelGGL(k_probe_pack, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, i, d_x_q, d_x_xi, d_u);
   LAUNCH_CHECK();
-  int rc = (P.m == 4) ? run_linearize<4>(h, P, st, P.cur, P.cur_u, nullptr, nullptr, 2, i, 1)
-                      : run_linearize<6>(h, P, st, P.cur, P.cur_u, nullptr, nullptr, 2, i, 1);
+  int rc = run_linearize(h, P, st, P.cur, P.cur_u, nullptr, nullptr, 2, i, 1);
   if (rc) return rc;
   hipLaunchKernelGGL(k_probe_export, dim3((n + 63) / 64), dim3(64), 0, st, P, i, d_f_q, d_f_xi, d_Fx, d_Fu, d_l, d_lx,
                      d_lxx, d_lu, d_luu, d_err);
@@ -4535,25 +4529,16 @@ extern "C" int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, do
   if (!h || h->running || B < 1 || B > h->max_batch || form < 0 || form > 2) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
-  const bool pend = h->prob.kind == TOLG_DYN_PENDULUM3D;
   hipLaunchKernelGGL(k_clear_ecc, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(k_poison_lds, dim3(2048), dim3(256), 0, st);
   LAUNCH_CHECK();
-  const dim3 gq((P.Bp * 4 + 63) / 64), gr(P.Bp / 4), blk(64);
   if (form == 0) {
-    if (P.m == 4) hipLaunchKernelGGL((k_expected_change<4, 0>), gq, blk, 0, st, P);
-    else if (h->prob.kind == TOLG_DYN_PENDULUM3D) hipLaunchKernelGGL((k_expected_change<6, 1>), gq, blk, 0, st, P);
-    else hipLaunchKernelGGL((k_expected_change<6, 0>), gq, blk, 0, st, P);
+    launch_ec_stmt(h, P, st, false);
   } else {
-    if (P.m == 4) launch_ec_ring<4>(h, P, st);
-    else launch_ec_ring<6>(h, P, st);
+    launch_ec_ring(h, P, st, false);
     LAUNCH_CHECK();
-    if (form == 2) {
-      if (P.m == 4) hipLaunchKernelGGL((k_expected_change<4, 0, true>), gq, blk, 0, st, P);
-      else if (pend) hipLaunchKernelGGL((k_expected_change<6, 1, true>), gq, blk, 0, st, P);
-      else hipLaunchKernelGGL((k_expected_change<6, 0, true>), gq, blk, 0, st, P);
-    }
+    if (form == 2) launch_ec_stmt(h, P, st, true);
   }
   LAUNCH_CHECK();
   hipLaunchKernelGGL(k_export_ecc, dim3((B + 63) / 64), dim3(64), 0, st, P, d_ecc, d_flag);
@@ -4566,7 +4551,7 @@ extern "C" int tolg_rollout(tolg_handle_t h, int32_t ms, int32_t rollout_linear,
   if (!h || h->running || B < 1 || B > h->max_batch) return TOLG_E_ARG;  // overwrites the candidate arrays
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
-  int rc = (P.m == 4) ? run_rollout_ms<4>(h, P, st, alpha, rollout_linear, ms) : run_rollout_ms<6>(h, P, st, alpha, rollout_linear, ms);
+  int rc = run_rollout_ms(h, P, st, alpha, rollout_linear, ms);
   if (rc) return rc;
   size_t n = (size_t)(P.N + 1) * P.Bp;
   hipLaunchKernelGGL(k_unpack_traj, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, P.cand, P.cand_u, d_xs_q_new,
