@@ -146,6 +146,30 @@ int tolg_solve_active_count(tolg_handle_t h, int32_t* d_count, void* stream);
 int tolg_solve_peek(tolg_handle_t h, double* d_xs_q, double* d_xs_xi, double* d_us, int32_t* d_iters,
                     int32_t* d_status, int32_t* d_converged, void* stream);
 
+/* Per-trajectory reference paths (no reference counterpart: the reference tracks one path per controller).
+ * tolg_refs_bytes: bytes of the caller-owned buffer that holds the packed references of a batch of up to max_batch
+ * trajectories, (N+1) * 13 * Bp * 8 with Bp = max_batch rounded up to a multiple of 4; 0 for an invalid problem.
+ * tolg_set_refs: packs d_q_ref [B][N+1][16], d_xi_ref [B][N+1][6] (the layout of tolg_create) into d_refs on `stream`;
+ * from then on every batch entry point of the handle -- tolg_solve_batch, tolg_solve_begin (the MS initial guess: knots
+ * 1..N = trajectory b's own reference), iterate / iterate_until / peek / end, tolg_linearize_backward, tolg_rollout,
+ * tolg_expected_change -- tracks trajectory b's reference, and must be called with this B (else TOLG_E_ARG).
+ * tolg_al_update reads no reference; tolg_eval_knot keeps the reference of tolg_create.  Like tolg_set_al the buffer
+ * stays caller-owned and is read by later calls.  d_q_ref = NULL returns the handle to the reference of tolg_create.
+ * TOLG_E_ARG: B < 1 or B > max_batch, refs_bytes < tolg_refs_bytes(prob, B), a solve in flight (between
+ * tolg_solve_begin and tolg_solve_end).
+ *
+ * A receding-horizon loop (every trajectory its own window of a longer path):
+ *   for each step t:
+ *     pack the windows [t, t + N] of the B paths into d_q_ref / d_xi_ref
+ *     tolg_set_refs(h, B, d_q_ref, d_xi_ref, d_refs, refs_bytes, stream);
+ *     tolg_solve_begin(h, &opt, B, d_x0_q, d_x0_xi, d_us_warm, ...);   x0 = measured state, us_warm = last us shifted by one
+ *     tolg_solve_iterate_until(h, opt.max_iter, opt.check_every, NULL, stream);
+ *     tolg_solve_end(h, d_xs_q, d_xs_xi, d_us, d_iters, d_status, d_converged, stream);
+ *     apply d_us[b][0], shift d_us into d_us_warm (repeat the last control) */
+size_t tolg_refs_bytes(const tolg_problem* prob, int32_t max_batch);
+int tolg_set_refs(tolg_handle_t h, int32_t B, const double* d_q_ref, const double* d_xi_ref, void* d_refs, size_t refs_bytes,
+                  void* stream);
+
 /* Augmented-Lagrangian box input constraint lb <= u <= ub -- replaces ALConstrainedCost wrapping the
  * tracking cost with an InputConstraint (traoptlibrary/traopt_cost.py:1173-1320,
  * traoptlibrary/traopt_constraints.py:66-169).  d_lb/d_ub [m]; d_lambda, d_imu [B][N][2m] (multipliers
@@ -182,7 +206,8 @@ int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_reg, int32_t
  *   in : d_x_q [n][16], d_x_xi [n][6], d_u [n][m] (ignored at the terminal knot)
  *   out: d_f_q [n][16], d_f_xi [n][6], d_Fx [n][12][12], d_Fu [n][12][m], d_l [n], d_lx [n][12],
  *        d_lxx [n][12][12], d_lu [n][m], d_luu [n][m][m], d_err [n][12] = [Log(x x_ref^-1); xi - xi_ref].
- * Any output may be NULL.  Uses the handle's workspace: not to be called during a solve in flight. */
+ * Any output may be NULL.  Uses the handle's workspace: not to be called during a solve in flight.  The cost terms are those of
+ * the reference of tolg_create, also on a handle with per-trajectory references (tolg_set_refs). */
 int tolg_eval_knot(tolg_handle_t h, int32_t i, int32_t n, const double* d_x_q, const double* d_x_xi,
                    const double* d_u, double* d_f_q, double* d_f_xi, double* d_Fx, double* d_Fu, double* d_l,
                    double* d_lx, double* d_lxx, double* d_lu, double* d_luu, double* d_err, void* stream);

@@ -1,0 +1,311 @@
+"""Per-trajectory reference paths (tolg_set_refs): one batched solve in which trajectory b tracks its own reference.
+
+- broadcast: references that all equal the problem's give the bits of the shared-reference solve on a fresh handle;
+- grouped: distinct references on groups of four (the fast backward sweep's groups) give the bits of one
+  shared-reference handle per reference;
+- interleaved: distinct references against the CPU oracle on each trajectory's own problem;
+- the per-knot entry point, the full 4096 x 200 size, the handle's state and the argument errors."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import bridge as ob
+from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, _capi, workloads
+from tests.test_gpu_parity import _oracle_problem, _rel
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ("xs_q", "xs_xi", "us", "J_hist", "grad_hist", "defect_hist", "alpha_hist", "mu_hist", "iters", "status",
+          "converged")
+
+
+def _bits(t):
+    t = t.detach().contiguous()
+    return t.view(torch.int64) if t.dtype == torch.float64 else t
+
+
+def _assert_bitwise(a, b, rows_a=slice(None), rows_b=slice(None), what=""):
+    for name in FIELDS:
+        x, y = getattr(a, name), getattr(b, name)
+        if x is None and y is None:
+            continue
+        assert torch.equal(_bits(x[rows_a]), _bits(y[rows_b])), "%s %s differs" % (what, name)
+
+
+def _with_ref(prob, q_ref, xi_ref):
+    return TrackingProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, q_ref, xi_ref, prob.pend_mass,
+                           prob.pend_length)
+
+
+def _broadcast(prob, B):
+    return (np.broadcast_to(prob.q_ref, (B,) + prob.q_ref.shape).copy(),
+            np.broadcast_to(prob.xi_ref, (B,) + prob.xi_ref.shape).copy())
+
+
+def _dense(prob):
+    J = prob.J.copy()
+    J[:3, :3] = np.array([[0.5, 0.05, 0.02], [0.05, 0.7, 0.03], [0.02, 0.03, 0.9]])
+    return TrackingProblem(prob.kind, J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
+
+
+B13 = 13  # not a multiple of four: the padded lanes replicate trajectory 12
+
+
+def _case(name):
+    if name == "drone":
+        prob, q, xi, us = workloads.drone_tracking(B13, N=400)
+    elif name == "so3":
+        prob, q, xi, us = workloads.so3_tracking(B13, N=100)
+    elif name == "pendulum":
+        prob, q, xi, us = workloads.pendulum_swingup(B13)
+    else:
+        prob, q, xi, us = workloads.se3_tracking(B13, N=200)
+        if name == "dense":
+            prob = _dense(prob)
+    return prob, q, xi, us
+
+
+# (case, fit_batch keywords)
+BROADCAST = [
+    ("se3", dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0, schedule="auto")),
+    ("se3", dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0, schedule="split")),
+    ("se3", dict(mode="ms", n_iterations=25, line_search=True)),
+    ("se3", dict(mode="ss", n_iterations=25)),
+    ("se3", dict(mode="ms", n_iterations=25, line_search=True, rollout="linear")),
+    ("se3", dict(mode="ss", n_iterations=25, rollout="linear")),
+    ("drone", dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0)),
+    ("drone", dict(mode="ms", n_iterations=25, line_search=True)),
+    ("so3", dict(mode="ms", n_iterations=25, line_search=True)),
+    ("so3", dict(mode="ss", n_iterations=25)),
+    ("pendulum", dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0)),
+    ("pendulum", dict(mode="ms", n_iterations=25, line_search=True)),
+    ("dense", dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0)),
+    ("dense", dict(mode="ss", n_iterations=25)),
+]
+
+
+@pytest.mark.parametrize("case,kw", BROADCAST, ids=["%s-%d" % (c, i) for i, (c, _) in enumerate(BROADCAST)])
+def test_broadcast_reference_is_bitwise_the_shared_one(case, kw):
+    prob, q, xi, us = _case(case)
+    r0 = BatchedTrackingILQR(prob, B13).fit_batch(q, xi, us, **kw)
+    qr, xr = _broadcast(prob, B13)
+    r1 = BatchedTrackingILQR(prob, B13).fit_batch(q, xi, us, q_ref=qr, xi_ref=xr, **kw)
+    torch.cuda.synchronize()
+    _assert_bitwise(r0, r1, what=case)
+
+
+def test_broadcast_reference_one_call_entry_point():
+    prob, q, xi, us = _case("se3")
+    kw = dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0)
+    r0 = BatchedTrackingILQR(prob, B13).solve_batch_one_call(q, xi, us, **kw)
+    qr, xr = _broadcast(prob, B13)
+    r1 = BatchedTrackingILQR(prob, B13).solve_batch_one_call(q, xi, us, q_ref=qr, xi_ref=xr, **kw)
+    _assert_bitwise(r0, r1)
+
+
+def test_broadcast_reference_al():
+    prob, q, xi, us, lb, ub = workloads.al_tracking(B13, N=200)
+    kw = dict(n_al_iters=4, n_ilqr_iters=30)
+    r0, i0 = BatchedTrackingILQR(prob, B13).al_fit_batch(q, xi, us, lb, ub, **kw)
+    qr, xr = _broadcast(prob, B13)
+    r1, i1 = BatchedTrackingILQR(prob, B13).al_fit_batch(q, xi, us, lb, ub, q_ref=qr, xi_ref=xr, **kw)
+    torch.cuda.synchronize()
+    _assert_bitwise(r0, r1)
+    for k in ("lmbd", "Imu", "mu", "max_violation"):
+        assert torch.equal(_bits(i0[k]), _bits(i1[k])), k
+    assert i0["outer_iterations"] == i1["outer_iterations"]
+
+
+MODES = {
+    "ms": dict(mode="ms", n_iterations=15, tol_grad_norm=0.0, tol_d_norm=0.0),
+    "merit": dict(mode="ms", n_iterations=25, line_search=True),
+    "ss": dict(mode="ss", n_iterations=25),
+}
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+def test_grouped_references_match_one_handle_per_reference(mode):
+    B, R = 12, 3
+    idx = np.arange(B) // 4
+    prob, q, xi, us, q_ref, xi_ref, idx, G = workloads.se3_multiref(B, R, index=idx)
+    kw = MODES[mode]
+    r = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, q_ref=q_ref, xi_ref=xi_ref, **kw)
+    for g in range(R):
+        rows = slice(4 * g, 4 * g + 4)
+        pg = _with_ref(prob, q_ref[4 * g], xi_ref[4 * g])
+        rg = BatchedTrackingILQR(pg, 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
+        torch.cuda.synchronize()
+        _assert_bitwise(r, rg, rows_a=rows, what="reference %d" % g)
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+def test_interleaved_references_match_the_oracle(mode):
+    B, R = 13, 3
+    prob, q, xi, us, q_ref, xi_ref, idx, G = workloads.se3_multiref(B, R)
+    assert list(idx[:4]) == [0, 1, 2, 0]
+    kw = dict(MODES[mode])
+    K = kw["n_iterations"]
+    r = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, q_ref=q_ref, xi_ref=xi_ref, **kw)
+    torch.cuda.synchronize()
+    okw = dict(mode=kw["mode"], max_iter=K, tol_grad=kw.get("tol_grad_norm", 1e-6), tol_defect=kw.get("tol_d_norm", 1e-6),
+               line_search=kw.get("line_search", False))
+    for b in range(B):
+        o = ob.fit(_oracle_problem(_with_ref(prob, q_ref[b], xi_ref[b])), q[b], xi[b], us[b], **okw)
+        n = int(r.iters[b])
+        assert n == o["n_iters"] and int(r.status[b]) == o["status"], b
+        assert _rel(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
+        assert _rel(r.us[b].cpu(), o["us"]) < 1e-6, b
+
+
+def _near(q_ref, xi_ref, rng, spread=0.3):
+    xs_q = np.empty_like(q_ref)
+    for i in range(q_ref.shape[0]):
+        xs_q[i] = q_ref[i] @ ob.se3_exp(rng.normal(size=6) * spread)
+    return xs_q, xi_ref + rng.normal(size=xi_ref.shape) * spread
+
+
+@pytest.mark.parametrize("ms", [True, False])
+def test_linearize_backward_per_trajectory_reference(ms):
+    B, R = 5, 3
+    prob, *_, q_ref, xi_ref, idx, G = workloads.se3_multiref(B, R)
+    N = prob.N
+    assert N == 200
+    rng = np.random.default_rng(7)
+    xs_q = np.empty((B, N + 1, 4, 4)); xs_xi = np.empty((B, N + 1, 6))
+    for b in range(B):
+        xs_q[b], xs_xi[b] = _near(q_ref[b], xi_ref[b], rng)
+    us = rng.normal(size=(B, N, 6))
+    r = BatchedTrackingILQR(prob, B).linearize_backward(xs_q, xs_xi, us, ms=ms, q_ref=q_ref, xi_ref=xi_ref)
+    torch.cuda.synchronize()
+    for b in range(B):
+        o = ob.lin_backward(_oracle_problem(_with_ref(prob, q_ref[b], xi_ref[b])), xs_q[b], xs_xi[b], us[b], ms=ms)
+        assert _rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
+        assert _rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
+        assert _rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
+        assert float(r["J"][b]) == pytest.approx(o["J"], rel=1e-12)
+        assert _rel(r["K"][b].cpu(), o["K"]) < 1e-8
+        assert _rel(r["k"][b].cpu(), o["k"]) < 1e-8
+
+
+def test_full_size_64_references():
+    B, R, K = 4096, 64, 10
+    idx = np.arange(B) // 64
+    prob, q, xi, us, q_ref, xi_ref, idx, G = workloads.se3_multiref(B, R, index=idx)
+    kw = dict(mode="ms", n_iterations=K, tol_grad_norm=0.0, tol_d_norm=0.0)
+    solver = BatchedTrackingILQR(prob, B)
+    r = solver.fit_batch(q, xi, us, q_ref=torch.as_tensor(q_ref, device="cuda"), xi_ref=torch.as_tensor(xi_ref, device="cuda"),
+                         **kw)
+    torch.cuda.synchronize()
+    for name in ("xs_q", "xs_xi", "us", "J_hist", "defect_hist"):
+        assert bool(torch.isfinite(getattr(r, name)).all()), name
+    assert bool(torch.isfinite(r.grad_hist[:, :K]).all())  # (entry K: the gradient of an iteration that was not run)
+    assert bool((r.iters == K).all())
+    assert bool((r.status == _capi.ST_OK).all())
+    del solver
+    for g0 in (0, 64 * 17 + 8, 64 * 40 + 28, 64 * 63 + 60):  # groups of four inside references 0, 17, 40, 63
+        rows = slice(g0, g0 + 4)
+        rg = BatchedTrackingILQR(_with_ref(prob, q_ref[g0], xi_ref[g0]), 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
+        torch.cuda.synchronize()
+        _assert_bitwise(r, rg, rows_a=rows, what="rows %d.." % g0)
+
+
+def test_state_returns_to_the_shared_reference():
+    B, R = 13, 3
+    prob, q, xi, us, q_ref, xi_ref, idx, G = workloads.se3_multiref(B, R)
+    kw = dict(mode="ms", n_iterations=10, tol_grad_norm=0.0, tol_d_norm=0.0)
+    fresh = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, **kw)
+    s = BatchedTrackingILQR(prob, B)
+    own = s.fit_batch(q, xi, us, q_ref=q_ref, xi_ref=xi_ref, **kw)
+    torch.cuda.synchronize()
+    assert not torch.equal(own.us, fresh.us)
+    # Python: a call without references is a shared-reference call, whatever came before
+    again = s.fit_batch(q, xi, us, **kw)
+    torch.cuda.synchronize()
+    _assert_bitwise(fresh, again, what="python")
+    # C ABI: tolg_set_refs(..., NULL) after references were set
+    s.fit_batch(q, xi, us, q_ref=q_ref, xi_ref=xi_ref, **kw)
+    torch.cuda.synchronize()
+    assert s.lib.tolg_set_refs(s._h, B, None, None, None, 0, None) == 0
+    s._refs_set = False
+    again = s.solve_batch_one_call(q, xi, us, **kw)
+    fresh1 = BatchedTrackingILQR(prob, B).solve_batch_one_call(q, xi, us, **kw)
+    _assert_bitwise(fresh1, again, what="C")
+    # and references set again after that give the bits of a fresh handle with references
+    own2 = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, q_ref=q_ref, xi_ref=xi_ref, **kw)
+    own3 = s.fit_batch(q, xi, us, q_ref=q_ref, xi_ref=xi_ref, **kw)
+    torch.cuda.synchronize()
+    _assert_bitwise(own, own2)
+    _assert_bitwise(own, own3)
+
+
+def test_argument_errors():
+    B, R, N = 6, 2, 30
+    prob, q, xi, us, q_ref, xi_ref, idx, G = workloads.se3_multiref(B, R, N=N)
+    s = BatchedTrackingILQR(prob, 8)
+    lib, h, E = s.lib, s._h, -1
+    dev = dict(dtype=torch.float64, device=s.device)
+    qd = torch.as_tensor(q_ref.reshape(B, N + 1, 16), **dev)
+    xd = torch.as_tensor(xi_ref, **dev)
+    nbytes = int(lib.tolg_refs_bytes(C.byref(s._p), 8))
+    buf = torch.empty(nbytes // 8, **dev)
+    st = s._stream()
+    P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    assert lib.tolg_set_refs(h, 0, P(qd), P(xd), P(buf), nbytes, st) == E
+    assert lib.tolg_set_refs(h, 9, P(qd), P(xd), P(buf), nbytes, st) == E
+    small = (N + 1) * 13 * 8 * 8 - 8  # one double short of B = 6 (Bp = 8)
+    assert lib.tolg_set_refs(h, B, P(qd), P(xd), P(buf), small, st) == E
+    assert lib.tolg_set_refs(h, B, P(qd), P(xd), P(buf), small + 8, st) == 0
+    # a batch call with another B than the references were set for
+    x0q = torch.as_tensor(q.reshape(B, 16), **dev); x0xi = torch.as_tensor(xi, **dev); u0 = torch.as_tensor(us, **dev)
+    opt = _capi.Options(_capi.MODE_MS, 4, 0, 0, 0.0, 0.0, 1e10, _capi.SCHED_AUTO, 0)
+    nul = C.c_void_p(0)
+    assert lib.tolg_solve_begin(h, C.byref(opt), B - 1, P(x0q), P(x0xi), P(u0), *([nul] * 5), st) == E
+    xs_q = torch.as_tensor(np.broadcast_to(q[:, None], (B, N + 1, 4, 4)).copy(), **dev)
+    xs_xi = torch.as_tensor(np.broadcast_to(xi[:, None], (B, N + 1, 6)).copy(), **dev)
+    md = torch.ones(B, 2, **dev)
+    assert lib.tolg_linearize_backward(h, 1, 1e10, B - 1, P(xs_q), P(xs_xi), P(u0), P(md), *([nul] * 9), st) == E
+    assert lib.tolg_rollout(h, 1, 0, 1.0, B - 1, nul, nul, nul, st) == E
+    assert lib.tolg_expected_change(h, 2, B - 1, nul, nul, st) == E
+    # in flight: no tolg_set_refs between begin and end, not even back to the shared reference
+    assert lib.tolg_solve_begin(h, C.byref(opt), B, P(x0q), P(x0xi), P(u0), *([nul] * 5), st) == 0
+    assert lib.tolg_set_refs(h, B, P(qd), P(xd), P(buf), nbytes, st) == E
+    assert lib.tolg_set_refs(h, B, None, None, None, 0, st) == E
+    assert lib.tolg_solve_iterate(h, 4, st) == 0
+    out = [torch.empty(B, N + 1, 16, **dev), torch.empty(B, N + 1, 6, **dev), torch.empty(B, N, 6, **dev)]
+    ints = [torch.empty(B, dtype=torch.int32, device=s.device) for _ in range(3)]
+    assert lib.tolg_solve_end(h, *[P(t) for t in out + ints], st) == 0
+    assert lib.tolg_set_refs(h, B, None, None, None, 0, st) == 0
+    torch.cuda.synchronize()
+    # the Python layer: shapes are checked before anything reaches the device
+    with pytest.raises(ValueError):
+        s.fit_batch(q, xi, us, q_ref=q_ref[:, :-1], xi_ref=xi_ref[:, :-1])  # horizon N instead of N + 1 knots
+    with pytest.raises(ValueError):
+        s.fit_batch(q, xi, us, q_ref=q_ref[:-1], xi_ref=xi_ref[:-1])        # B - 1 references
+    with pytest.raises(ValueError):
+        s.fit_batch(q, xi, us, q_ref=q_ref)                                 # xi_ref missing
+    with pytest.raises(ValueError):
+        s.linearize_backward(xs_q.cpu().numpy(), xs_xi.cpu().numpy(), us, q_ref=q_ref[..., :3, :], xi_ref=xi_ref)
+    with pytest.raises(ValueError):
+        s.solve_begin(q, xi, us, q_ref=q_ref, xi_ref=xi_ref[..., :3])
+
+
+def test_mirror_fit_batch_refs():
+    """The mirror's MS controller solves several paths in one call: each initial state with its own (q_ref, xi_ref)."""
+    from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_controller import iLQR_Tracking_SE3_MS
+    from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_cost import SE3TrackingQuadraticGaussNewtonCost
+    from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_dynamics import SE3Dynamics
+    B, R, N = 6, 3, 60
+    prob, q, xi, us, q_ref, xi_ref, idx, G = workloads.se3_multiref(B, R, N=N)
+    dyn = SE3Dynamics(prob.J, prob.dt)
+    cost = SE3TrackingQuadraticGaussNewtonCost(prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
+    ctl = iLQR_Tracking_SE3_MS(dyn, cost, N, prob.q_ref, prob.xi_ref)
+    x0s = [[q[b], xi[b]] for b in range(B)]
+    refs = [(q_ref[b], xi_ref[b]) for b in range(B)]
+    r = ctl.fit_batch(x0s, us, n_iterations=10, refs=refs)
+    torch.cuda.synchronize()
+    direct = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, mode="ms", n_iterations=10, tol_grad_norm=ctl._default_tol,
+                                                    q_ref=q_ref, xi_ref=xi_ref, **ctl._options())
+    torch.cuda.synchronize()
+    _assert_bitwise(r, direct)

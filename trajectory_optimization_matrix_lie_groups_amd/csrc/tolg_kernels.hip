@@ -117,7 +117,8 @@ struct Params {
   double* cur_u;       // [m][N][Bp]
   double* cand;
   double* cand_u;
-  const double* ref;   // [N+1][13] reference pose (quat, pos) and twist, batch-shared
+  const double* ref;   // [N+1][13] reference pose (quat, pos) and twist, batch-shared; in the PTREF kernels [N+1][13][Bp]
+                       // (SIDX): trajectory b's own reference (tolg_set_refs)
   double* REC;         // [N+1][recF][Bp] compact knot records written by K1 (fields: REC_*)
   int recF, fLUU;      // fields per record for this model / solve (rec_fields()), field index of REC_LUU (AL only)
   int fA22, pad2;      // field index of the stored I + H dt block, -1 when the backward sweep rebuilds it from REC_XI
@@ -163,6 +164,19 @@ enum { NSLOT = 15, NALPHA_MS = 20, NALPHA_SS = 13 };  // slots: the widest stage
 // every array is knot-major [knot][field][Bp]: one knot of one field is a contiguous run over the batch
 #define SIDX(c, i, b) ((((size_t)(i)) * 13 + (size_t)(c)) * (size_t)P.Bp + (size_t)(b))
 #define UIDX(c, i, b) ((((size_t)(i)) * (size_t)P.m + (size_t)(c)) * (size_t)P.Bp + (size_t)(b))
+// field c of the reference of trajectory b at knot i, r[c]: the batch-shared array, or (PTREF) trajectory b's own in the
+// layout of the nominal trajectory -- a reference load is then a state load, coalesced over the batch
+template <bool PTREF> struct RefAt;
+template <> struct RefAt<false> {
+  const double* r;
+  TOLG_DEV RefAt(const double* ref, int i, int, int) : r(ref + 13 * (size_t)i) {}
+  TOLG_DEV double operator[](int c) const { return r[c]; }
+};
+template <> struct RefAt<true> {
+  const double* r; size_t s;
+  TOLG_DEV RefAt(const double* ref, int i, int b, int Bp) : r(ref + (size_t)i * 13 * (size_t)Bp + (size_t)b), s((size_t)Bp) {}
+  TOLG_DEV double operator[](int c) const { return r[(size_t)c * s]; }
+};
 
 // Raw buffer access for the sequential kernels: the descriptor (SRD) addresses one knot, the lane
 // supplies a 32-bit byte offset (its trajectory), the field offset is a wave-uniform SGPR -- no
@@ -454,9 +468,25 @@ __global__ void k_pack_ref(int N, const double* __restrict__ q_ref, const double
   r[0] = X.q.x; r[1] = X.q.y; r[2] = X.q.z; r[3] = X.q.w; r[4] = X.t.x; r[5] = X.t.y; r[6] = X.t.z;
   for (int a = 0; a < 6; a++) r[7 + a] = xi_ref[6 * (size_t)i + a];
 }
+// the same conversion for B references [B][N+1][16] / [B][N+1][6] into [N+1][13][Bp] (the PTREF kernels' P.ref); padded
+// trajectories b >= B replicate b = B-1
+__global__ void k_pack_refs(int B, int Bp, int N, const double* __restrict__ q_ref, const double* __restrict__ xi_ref,
+                            double* __restrict__ refs) {
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)(N + 1) * Bp) return;
+  int b = (int)(t % Bp), i = (int)(t / Bp);
+  int bs = b < B ? b : B - 1;
+  Pose X = pose_from_m16(q_ref + ((size_t)bs * (N + 1) + i) * 16);
+  const double* x = xi_ref + ((size_t)bs * (N + 1) + i) * 6;
+  double* r = refs + (size_t)i * 13 * Bp + b;
+  r[0] = X.q.x; r[Bp] = X.q.y; r[2 * (size_t)Bp] = X.q.z; r[3 * (size_t)Bp] = X.q.w;
+  r[4 * (size_t)Bp] = X.t.x; r[5 * (size_t)Bp] = X.t.y; r[6 * (size_t)Bp] = X.t.z;
+  for (int a = 0; a < 6; a++) r[(7 + a) * (size_t)Bp] = x[a];
+}
 
 // MS _initial_guess (traopt_controller.py:3123-3136): knot 0 = x0, knots 1..N = reference;
 // SS: only knot 0 (the rest comes from k_init_rollout).  Padded trajectories replicate b = B-1.
+template <bool PTREF>
 __global__ void k_init(Params P, const double* __restrict__ x0_q, const double* __restrict__ x0_xi,
                        const double* __restrict__ us_init, int ms) {
   size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -469,12 +499,14 @@ __global__ void k_init(Params P, const double* __restrict__ x0_q, const double* 
     const double* x = x0_xi + 6 * (size_t)bs;
     S.w = v3(x[0], x[1], x[2]);
     S.v = v3(x[3], x[4], x[5]);
-  } else {
+  } else if constexpr (!PTREF) {
     const double* r = P.ref + 13 * (size_t)i;
     S.X.q.x = r[0]; S.X.q.y = r[1]; S.X.q.z = r[2]; S.X.q.w = r[3];
     S.X.t = v3(r[4], r[5], r[6]);
     S.w = v3(r[7], r[8], r[9]);
     S.v = v3(r[10], r[11], r[12]);
+  } else {  // trajectory b's own reference (as for b's state, padded b replicates B-1 -- k_pack_refs did that)
+    S = load_state(P, P.ref, i, b);
   }
   if (i == 0 || ms) store_state(P, P.cur, i, b, S);
   if (i < P.N)
@@ -620,7 +652,7 @@ TOLG_DEV void rec_run(const Params& P, int i, int b, const double (&v)[N]) {
 // TERM: -1 = decided per lane (i == N), 0 / 1 = the caller knows that no / every lane it calls with sits on the
 // terminal knot.  With a wave-uniform answer the weight matrices below are selected once per wave and read with
 // scalar loads; a per-lane select turns every one of their ~150 reads into a vector-memory load of one address.
-template <int M, bool CLOSED = false, int TERM = -1, class CT, class NextFn>
+template <int M, bool CLOSED = false, int TERM = -1, bool PTREF = false, class CT, class NextFn>
 TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const State& S, const double (&u)[M],
                        NextFn next_state, double* lcost = nullptr) {
   const bool term = TERM < 0 ? (i == P.N) : (TERM == 1);
@@ -630,7 +662,7 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
   // One gate for all the series evaluations of the knot: the tracking error (Log, then V^-1 and Q at its angle,
   // which the Log bounds cover) and the step rotation (V, Q, Exp at dt w).
   const V3 wd = dt * S.w, vd = dt * S.v;
-  const double* r = P.ref + 13 * (size_t)i;
+  const RefAt<PTREF> r(P.ref, i, b, P.Bp);
   Pose Xr;
   Xr.q.x = r[0]; Xr.q.y = r[1]; Xr.q.z = r[2]; Xr.q.w = r[3];
   Xr.t = v3(r[4], r[5], r[6]);
@@ -866,7 +898,7 @@ TOLG_DEV bool ls_quad_form(const Params& P, int list, int nslots);  // (line-sea
 #ifndef TOLG_K1_WPE
 #define TOLG_K1_WPE 2
 #endif
-template <int M>
+template <int M, bool PTREF>
 __global__ __launch_bounds__(256, TOLG_K1_WPE) void k_linearize(Params P, const double* __restrict__ src,
                                                     const double* __restrict__ src_u, double* __restrict__ dst,
                                                     double* __restrict__ dst_u, int ms, int i0, int ni, int ls_list, int ls_nslots) {
@@ -900,7 +932,7 @@ __global__ __launch_bounds__(256, TOLG_K1_WPE) void k_linearize(Params P, const 
       if (dst_u) dst_u[UIDX(a, i, b)] = u[a];
     }
   }
-  lin_knot<M>(P, C, i, b, ms, S, u, [&]() { return load_state(P, src, i + 1, e); });
+  lin_knot<M, false, -1, PTREF>(P, C, i, b, ms, S, u, [&]() { return load_state(P, src, i + 1, e); });
 }
 
 // per-trajectory sums of the stage costs / squared defects, fixed order (deterministic);
@@ -2251,7 +2283,7 @@ TOLG_DEV State rl_in_state(const char* slot, int tt) {
 }
 template <int M>
 constexpr size_t rl_static_lds() { return (size_t)RL_DEPTH * RlIn<M>::SLOT + (size_t)RL_RING * RL_PAIRS * 256 + 32; }
-template <int M>
+template <int M, bool PTREF>
 __global__ __launch_bounds__(256) void k_rollout_lin(Params P, int it) {
   typedef RlIn<M> IN;
   const DConsts& C = *(const DConsts*)P.c;
@@ -2518,8 +2550,8 @@ __global__ __launch_bounds__(256) void k_rollout_lin(Params P, int it) {
       if (i > 0) store_state<TOLG_NT_CURST>(P, P.cur, i, b, S);  // the accepted candidate becomes the nominal trajectory
       // the terminal knot (in the last group only) goes separately: see lin_knot's TERM
       double lc = 0.0;
-      if (i < N) lin_knot<M, true, 0>(P, C, i, b, 1, S, u, [&]() { return S; }, &lc);
-      if (4 * g + 3 >= N && i == N) lin_knot<M, true, 1>(P, C, i, b, 1, S, u, [&]() { return S; }, &lc);
+      if (i < N) lin_knot<M, true, 0, PTREF>(P, C, i, b, 1, S, u, [&]() { return S; }, &lc);
+      if (4 * g + 3 >= N && i == N) lin_knot<M, true, 1, PTREF>(P, C, i, b, 1, S, u, [&]() { return S; }, &lc);
       jpart += lc;
     }
     done++;
@@ -2587,9 +2619,9 @@ TOLG_DEV bool ls_quad_form(const Params& P, int list, int nslots) { return list 
 
 // stage cost l(x, u, i) / terminal cost (traopt_cost.py:675-738)
 // FAST: the series forms of tolg_lie.h (what the rollouts and the linearisation use) in place of the closed-form Log
-template <int M, bool FAST = false>
+template <int M, bool FAST = false, bool PTREF = false>
 TOLG_DEV double knot_cost(const Params& P, const Consts& C, int i, int b, const State& S, const double (&u)[M], bool term) {
-  const double* r = P.ref + 13 * (size_t)i;
+  const RefAt<PTREF> r(P.ref, i, b, P.Bp);
   Pose Xr;
   Xr.q.x = r[0]; Xr.q.y = r[1]; Xr.q.z = r[2]; Xr.q.w = r[3];
   Xr.t = v3(r[4], r[5], r[6]);
@@ -2631,7 +2663,7 @@ TOLG_DEV double knot_cost(const Params& P, const Consts& C, int i, int b, const 
 // one thread per (trajectory, slot): rollout with alpha_{a0+slot}, its cost and (MS) defect norm on the chain -- the
 // form of a wide stage with MANY undecided trajectories (64 waves per alpha keep a 12-alpha stage within one wave per
 // SIMD whatever their number; ls_quad_form decides on the device, the quad form -- k_rollout_ls -- takes the short lists)
-template <int M, bool MS, bool LINEAR>
+template <int M, bool MS, bool LINEAR, bool PTREF>
 __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nslots, int list) {
   const Consts& C = *P.c;
   // (round 4: the series forms of tolg_lie.h in this kernel and in k_ls_eval were measured -- SS 414 -> 404, merit 500 -> 482: a
@@ -2670,7 +2702,7 @@ __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nsl
       du[a] = sacc;
       un[a] = u[a] + sacc;
     }
-    J += knot_cost<M>(P, C, i, b, Sn, un, false);
+    J += knot_cost<M, false, PTREF>(P, C, i, b, Sn, un, false);
     State Nx;
     if constexpr (!LINEAR) {
       State Fn = dyn_f<M>(C, Sn, un);
@@ -2722,7 +2754,7 @@ __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nsl
   double uz[M];
 #pragma unroll
   for (int a = 0; a < M; a++) uz[a] = 0;
-  J += knot_cost<M>(P, C, N, b, Sn, uz, true);
+  J += knot_cost<M, false, PTREF>(P, C, N, b, Sn, uz, true);
   P.Jtrial[(size_t)b * 20 + ai] = J;
   P.dtrial[(size_t)b * 20 + ai] = sqrt(d2);
 }
@@ -3061,7 +3093,7 @@ __global__ __launch_bounds__(64 * (NT + 1)) void k_rollout_ls2(Params P, int a0,
 // stage cost l(x^_i, u^_i) (traopt_cost.py:675-738) and, MS, the squared defect
 // |Log(x^_{i+1}^-1 f_q(x^_i, u^_i))|^2 + |f_xi - xi^_{i+1}|^2 (:2790-2812) of every stored candidate of the stage
 // (four waves per SIMD -- 127 registers and 28 bytes of scratch instead of 136 -- was measured: no change)
-template <int M, bool MS>
+template <int M, bool MS, bool PTREF>
 __global__ __launch_bounds__(256) void k_ls_eval(Params P, int nslots, int direct, int list) {
   const Consts& C = *P.c;
   const int slot = blockIdx.y, N = P.N;
@@ -3087,7 +3119,7 @@ __global__ __launch_bounds__(256) void k_ls_eval(Params P, int nslots, int direc
   double u[M];
 #pragma unroll
   for (int a = 0; a < M; a++) u[a] = (i < N) ? su[UIDX(a, i, e)] : 0.0;
-  P.LSC[((size_t)slot * (N + 1) + i) * P.Bp + e] = knot_cost<M>(P, C, i, b, S, u, i == N);
+  P.LSC[((size_t)slot * (N + 1) + i) * P.Bp + e] = knot_cost<M, false, PTREF>(P, C, i, b, S, u, i == N);
   if constexpr (MS) {
     if (i < N) {
       const State Nx = load_state(P, sx, i + 1, e), Fn = dyn_f<M>(C, S, u);
@@ -3163,7 +3195,7 @@ TOLG_DEV void affine_candidate(const Params& P, int i, int b, double alpha, Stat
     for (int a = 0; a < M; a++) u[a] = 0.0;
   }
 }
-template <int M, bool MS>
+template <int M, bool MS, bool PTREF>
 __global__ __launch_bounds__(256) void k_ls_eval_affine(Params P, int a0, int nslots, int list) {
   const Consts& C = *P.c;
   const int slot = blockIdx.y, N = P.N;
@@ -3180,7 +3212,7 @@ __global__ __launch_bounds__(256) void k_ls_eval_affine(Params P, int a0, int ns
   State S;
   double u[M];
   affine_candidate<M>(P, i, b, alpha, S, u);
-  P.LSC[((size_t)slot * (N + 1) + i) * P.Bp + e] = knot_cost<M>(P, C, i, b, S, u, i == N);
+  P.LSC[((size_t)slot * (N + 1) + i) * P.Bp + e] = knot_cost<M, false, PTREF>(P, C, i, b, S, u, i == N);
   if constexpr (MS) {
     if (i < N) {
       State Nx;
@@ -3604,9 +3636,13 @@ using namespace tolg;
 // The kernels that serve one handle: which template instantiation runs for which model is decided once, here, when the
 // handle is created (kernel_table below).  Launch sites pick an entry by what changes from call to call -- the pass of
 // the sweep, AL terms on or off, the rollout form, the search kind, the stage -- and never test the model themselves.
+// A handle holds two tables: the kernels that read the reference (K1, the fused launch, the line-search evaluations,
+// k_init) come in a second instantiation, PTREF, that reads trajectory b's own reference (tolg_set_refs); every other
+// entry is the same kernel in both.
 typedef void (*SearchKernel)(Params, int, int, int);
 typedef void (*SearchRollout)(Params, int, int, int, int);
 struct KernelTable {
+  void (*init)(Params, const double*, const double*, const double*, int);  // k_init
   void (*linearize)(Params, const double*, const double*, double*, double*, int, int, int, int, int);  // K1
   void (*init_rollout)(Params);
   void (*sweep[2][2])(Params, int, int);  // K2 [fast][AL terms]
@@ -3625,7 +3661,7 @@ struct KernelTable {
   } ls[2];
 };
 
-template <int M, bool MS, int PK>
+template <int M, bool MS, int PK, bool PTREF>
 static KernelTable::Search search_kernels() {
   KernelTable::Search s;
   // the nonlinear rollouts, two wavefronts per sixteen quads: [1] the first try, [0] the stages behind it.  The first try is
@@ -3638,18 +3674,20 @@ static KernelTable::Search search_kernels() {
   else s.wave2[0] = {k_rollout_ls2<M, false, 3>, 3};
   s.wave1[0] = k_rollout_ls<M, MS, false, PK>;
   s.wave1[1] = k_rollout_ls<M, MS, true, PK>;
-  s.eval_t[0] = k_rollout_eval_t<M, MS, false>;
-  s.eval_t[1] = k_rollout_eval_t<M, MS, true>;
-  s.eval = k_ls_eval<M, MS>;
-  s.eval_affine = k_ls_eval_affine<M, MS>;
+  s.eval_t[0] = k_rollout_eval_t<M, MS, false, PTREF>;
+  s.eval_t[1] = k_rollout_eval_t<M, MS, true, PTREF>;
+  s.eval = k_ls_eval<M, MS, PTREF>;
+  s.eval_affine = k_ls_eval_affine<M, MS, PTREF>;
   return s;
 }
-// GRAV: gravity; DENSE: inertia blocks that are not diagonal; PEND: Pendulum3dDyanmics (m = 6, gravity)
-template <int M, bool GRAV, bool DENSE, bool PEND>
+// GRAV: gravity; DENSE: inertia blocks that are not diagonal; PEND: Pendulum3dDyanmics (m = 6, gravity); PTREF: a
+// reference per trajectory
+template <int M, bool GRAV, bool DENSE, bool PEND, bool PTREF>
 static KernelTable kernel_table(int lds_per_block) {
   constexpr int PK = PEND ? 1 : 0;
   KernelTable t;
-  t.linearize = k_linearize<M>;
+  t.init = k_init<PTREF>;
+  t.linearize = k_linearize<M, PTREF>;
   t.init_rollout = k_init_rollout<M>;
   if constexpr (!DENSE && !PEND) {
     // diagonal inertia blocks and a constant input matrix (every reference script except the pendulum): the third form of
@@ -3665,7 +3703,7 @@ static KernelTable kernel_table(int lds_per_block) {
   t.rollout_factor = k_rollout<M, false, false, PK>;
   t.rollout_lin = nullptr;
   if constexpr (!PEND)
-    if (rl_static_lds<M>() + sizeof(double) * RL_NH * 4 * 16 <= (size_t)lds_per_block) t.rollout_lin = k_rollout_lin<M>;
+    if (rl_static_lds<M>() + sizeof(double) * RL_NH * 4 * 16 <= (size_t)lds_per_block) t.rollout_lin = k_rollout_lin<M, PTREF>;
   // the ring form reads the velocity block of F_x from the record run for dense inertia blocks and the pendulum, and for the
   // pendulum also the knot's input-matrix block (VARB)
   t.ec_ring[0] = k_expected_change_ring<M, GRAV, false, DENSE || PEND, PEND>;
@@ -3673,19 +3711,20 @@ static KernelTable kernel_table(int lds_per_block) {
   t.ec_stmt[0] = k_expected_change<M, PK>;
   t.ec_stmt[1] = k_expected_change<M, PK, true>;
   t.affine_commit = k_affine_commit<M>;
-  t.ls[0] = search_kernels<M, false, PK>();
-  t.ls[1] = search_kernels<M, true, PK>();
+  t.ls[0] = search_kernels<M, false, PK, PTREF>();
+  t.ls[1] = search_kernels<M, true, PK, PTREF>();
   return t;
 }
+template <bool PTREF>
 static KernelTable kernel_table_for(const tolg_problem& p, const Consts& c, int lds_per_block) {
   const bool dense = c.diagJ == 0;
   if (p.m == 4)  // the drone: gravity, always
-    return dense ? kernel_table<4, true, true, false>(lds_per_block) : kernel_table<4, true, false, false>(lds_per_block);
+    return dense ? kernel_table<4, true, true, false, PTREF>(lds_per_block) : kernel_table<4, true, false, false, PTREF>(lds_per_block);
   if (p.kind == TOLG_DYN_PENDULUM3D)
-    return dense ? kernel_table<6, true, true, true>(lds_per_block) : kernel_table<6, true, false, true>(lds_per_block);
+    return dense ? kernel_table<6, true, true, true, PTREF>(lds_per_block) : kernel_table<6, true, false, true, PTREF>(lds_per_block);
   if (c.grav != 0.0)
-    return dense ? kernel_table<6, true, true, false>(lds_per_block) : kernel_table<6, true, false, false>(lds_per_block);
-  return dense ? kernel_table<6, false, true, false>(lds_per_block) : kernel_table<6, false, false, false>(lds_per_block);
+    return dense ? kernel_table<6, true, true, false, PTREF>(lds_per_block) : kernel_table<6, true, false, false, PTREF>(lds_per_block);
+  return dense ? kernel_table<6, false, true, false, PTREF>(lds_per_block) : kernel_table<6, false, false, false, PTREF>(lds_per_block);
 }
 
 struct tolg_handle_s {
@@ -3701,7 +3740,11 @@ struct tolg_handle_s {
   bool running;
   int lds_per_block;  // hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KB on MI355X)
   int rec_closed = 0; // the knot records were last written by the fused rollout (no defect field, see k_backward)
-  KernelTable kt;     // the model's kernels (kernel_table_for)
+  KernelTable kt;     // the model's kernels for the solves to come: kt_ref[refs != null]
+  KernelTable kt_ref[2];  // kernel_table_for<PTREF>: [0] the batch-shared reference, [1] a reference per trajectory
+  const double* ref_shared;  // the reference packed by tolg_create (P.ref as carved)
+  const double* refs = nullptr;  // tolg_set_refs: the packed per-trajectory references (caller-owned), or null
+  int refs_B = 0;                // ... and the batch they were set for: every batch call must match it
   // A/B switches of the tests, read from the environment when the handle is created: every sweep the full kernel
   // (TOLG_K2_FULL_ONLY=1), the one-wave forms of the line-search rollouts (TOLG_LS_ONEWAVE=1)
   bool k2_full_only, ls_one_wave;
@@ -3933,7 +3976,9 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
         c.Llin[a][6 * i + j] = sacc * prob->dt;
       }
   }
-  h->kt = kernel_table_for(*prob, c, h->lds_per_block);
+  h->kt_ref[0] = kernel_table_for<false>(*prob, c, h->lds_per_block);
+  h->kt_ref[1] = kernel_table_for<true>(*prob, c, h->lds_per_block);
+  h->kt = h->kt_ref[0];
   {
     const char* e = getenv("TOLG_K2_FULL_ONLY");
     h->k2_full_only = e && e[0] == '1';
@@ -3945,6 +3990,7 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
   memset(&h->P, 0, sizeof h->P);
   carve_all(prob, h->Bp_max, h->ws, &h->P, &dc);
   h->P.N = prob->N; h->P.m = prob->m;
+  h->ref_shared = h->P.ref;
   if (hipMemcpyAsync(dc, &h->hc, sizeof(Consts), hipMemcpyHostToDevice, st) != hipSuccess) { tolg_destroy(h); return TOLG_E_LAUNCH; }
   int N = prob->N;
   hipLaunchKernelGGL(k_pack_ref, dim3((N + 1 + 63) / 64), dim3(64), 0, st, N, d_q_ref, d_xi_ref,
@@ -4037,6 +4083,7 @@ static Params params_for(tolg_handle_s* h, int B) {
   P.J_hist = P.grad_hist = P.defect_hist = P.alpha_hist = P.mu_hist = nullptr;
   P.max_iter = 0; P.tol_grad = 0; P.tol_defect = 0; P.max_reg = 1e10;
   P.al_lb = h->al_lb; P.al_ub = h->al_ub; P.al_lambda = h->al_lambda; P.al_imu = h->al_imu;
+  P.ref = h->refs ? h->refs : h->ref_shared;  // the layout h->kt's kernels read
   const bool grav = h->hc.grav != 0.0;
   // the velocity block of F_x is stored only for the models the third form of the backward sweep does not cover
   const bool a22 = !(h->hc.diagJ != 0 && h->prob.kind != TOLG_DYN_PENDULUM3D);
@@ -4049,12 +4096,13 @@ static Params params_for(tolg_handle_s* h, int B) {
 }
 
 static int run_linearize(tolg_handle_s* h, const Params& P, hipStream_t st, const double* src, const double* src_u,
-                         double* dst, double* dst_u, int ms, int i0 = 0, int ni = -1, int ls_list = -1, int ls_nslots = 0) {
+                         double* dst, double* dst_u, int ms, int i0 = 0, int ni = -1, int ls_list = -1, int ls_nslots = 0,
+                         decltype(KernelTable::linearize) kernel = nullptr) {  // kernel: another K1 than h->kt's
   if (ni < 0) ni = P.N + 1;
   size_t n = (size_t)ni * P.Bp;
   h->rec_closed = 0;  // K1 writes the defect field
   Timed t(h, st, 2);
-  hipLaunchKernelGGL(h->kt.linearize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, src, src_u, dst, dst_u, ms,
+  hipLaunchKernelGGL(kernel ? kernel : h->kt.linearize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, src, src_u, dst, dst_u, ms,
                      i0, ni, ls_list, ls_nslots);
   LAUNCH_CHECK();
   return 0;
@@ -4308,6 +4356,7 @@ extern "C" int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_
                                 double* d_grad_hist, double* d_defect_hist, double* d_alpha_hist, double* d_mu_hist,
                                 void* stream) {
   if (!h || !opt || B < 1 || B > h->max_batch || !d_x0_q || !d_x0_xi || !d_us_init) return TOLG_E_ARG;
+  if (h->refs && B != h->refs_B) return TOLG_E_ARG;
   if (opt->max_iter < 0) return TOLG_E_ARG;
   if (opt->mode != TOLG_MODE_MS && opt->mode != TOLG_MODE_SS) return TOLG_E_ARG;
   const int ms = opt->mode == TOLG_MODE_MS;
@@ -4320,7 +4369,7 @@ extern "C" int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_
   // TOLG_SCHED_SPLIT keeps the statement-form rollouts for every trajectory (the A/B partner in the tests)
   P.affine = (opt->rollout_linear && opt->schedule != TOLG_SCHED_SPLIT) ? 1 : 0;
   size_t n = (size_t)(P.N + 1) * P.Bp;
-  hipLaunchKernelGGL(k_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, d_x0_q, d_x0_xi, d_us_init, ms);
+  hipLaunchKernelGGL(h->kt.init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, d_x0_q, d_x0_xi, d_us_init, ms);
   LAUNCH_CHECK();
   if (!ms) {  // SS: dynamically feasible initial trajectory (_init_rollout, traopt_controller.py:2015-2028)
     hipLaunchKernelGGL(h->kt.init_rollout, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
@@ -4454,6 +4503,32 @@ extern "C" int tolg_set_al(tolg_handle_t h, const double* d_lb, const double* d_
   return 0;
 }
 
+static size_t refs_bytes_for(const tolg_problem* p, int B) {
+  return (size_t)(p->N + 1) * 13 * (size_t)((B + 3) / 4 * 4) * sizeof(double);
+}
+extern "C" size_t tolg_refs_bytes(const tolg_problem* prob, int32_t max_batch) {
+  if (check_problem(prob) || max_batch < 1) return 0;
+  return refs_bytes_for(prob, max_batch);
+}
+
+extern "C" int tolg_set_refs(tolg_handle_t h, int32_t B, const double* d_q_ref, const double* d_xi_ref, void* d_refs,
+                             size_t refs_bytes, void* stream) {
+  if (!h || h->running) return TOLG_E_ARG;
+  if (!d_q_ref) {  // back to the reference of tolg_create
+    h->refs = nullptr; h->refs_B = 0; h->kt = h->kt_ref[0];
+    return 0;
+  }
+  if (B < 1 || B > h->max_batch || !d_xi_ref || !d_refs || (reinterpret_cast<uintptr_t>(d_refs) & 7) != 0) return TOLG_E_ARG;
+  if (refs_bytes < refs_bytes_for(&h->prob, B)) return TOLG_E_ARG;
+  const int N = h->prob.N, Bp = (B + 3) / 4 * 4;
+  const size_t n = (size_t)(N + 1) * Bp;
+  hipLaunchKernelGGL(k_pack_refs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp, N,
+                     d_q_ref, d_xi_ref, static_cast<double*>(d_refs));
+  LAUNCH_CHECK();
+  h->refs = static_cast<const double*>(d_refs); h->refs_B = B; h->kt = h->kt_ref[1];
+  return 0;
+}
+
 extern "C" int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, const double* d_lb, const double* d_ub,
                               double* d_lambda, double* d_imu, double* d_mu, double mu_scale, double mu_max,
                               double tol_constr, double* d_maxviol, int32_t* d_al_converged, void* stream) {
@@ -4472,6 +4547,7 @@ extern "C" int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_r
                                        double* d_J, double* d_dnorm, double* d_grad, void* stream) {
   // uses the handle's workspace (k_pack_traj resets the trajectories, mu / delta, the masks): not during a solve
   if (!h || h->running || B < 1 || B > h->max_batch || !d_xs_q || !d_xs_xi || !d_us) return TOLG_E_ARG;
+  if (h->refs && B != h->refs_B) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   P.max_reg = max_reg;
@@ -4502,9 +4578,10 @@ extern "C" int tolg_eval_knot(tolg_handle_t h, int32_t i, int32_t n, const doubl
   if (i < h->prob.N && !d_u) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, n);
+  P.ref = h->ref_shared;  // the reference of tolg_create, whatever tolg_set_refs holds
   hipLaunchKernelGGL(k_probe_pack, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, i, d_x_q, d_x_xi, d_u);
   LAUNCH_CHECK();
-  int rc = run_linearize(h, P, st, P.cur, P.cur_u, nullptr, nullptr, 2, i, 1);
+  int rc = run_linearize(h, P, st, P.cur, P.cur_u, nullptr, nullptr, 2, i, 1, -1, 0, h->kt_ref[0].linearize);
   if (rc) return rc;
   hipLaunchKernelGGL(k_probe_export, dim3((n + 63) / 64), dim3(64), 0, st, P, i, d_f_q, d_f_xi, d_Fx, d_Fu, d_l, d_lx,
                      d_lxx, d_lu, d_luu, d_err);
@@ -4527,6 +4604,7 @@ __global__ void k_clear_ecc(Params P) {
 extern "C" int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, double* d_ecc, int32_t* d_flag, void* stream) {
   // works on what tolg_linearize_backward left in the workspace (trajectory, records, gains): not during a solve
   if (!h || h->running || B < 1 || B > h->max_batch || form < 0 || form > 2) return TOLG_E_ARG;
+  if (h->refs && B != h->refs_B) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   hipLaunchKernelGGL(k_clear_ecc, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
@@ -4549,6 +4627,7 @@ extern "C" int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, do
 extern "C" int tolg_rollout(tolg_handle_t h, int32_t ms, int32_t rollout_linear, double alpha, int32_t B,
                             double* d_xs_q_new, double* d_xs_xi_new, double* d_us_new, void* stream) {
   if (!h || h->running || B < 1 || B > h->max_batch) return TOLG_E_ARG;  // overwrites the candidate arrays
+  if (h->refs && B != h->refs_B) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   int rc = run_rollout_ms(h, P, st, alpha, rollout_linear, ms);

@@ -183,3 +183,34 @@ def al_tracking(B, N=200, seed=SEED):
     xi0 = np.array([0.0, 0.0, 0.1, 2.0, 0.0, 0.2])
     x0_q, x0_xi = perturbed_batch(q0, xi0, B, 0.3 * np.array([0.3, 0.3, 0.3, 0.5, 0.5, 0.5]), 0.05, seed)
     return prob, x0_q, x0_xi, np.zeros((B, N, 6)), -10.0 * np.ones(6), 10.0 * np.ones(6)
+
+
+def rigid_motions(R, seed=SEED, angle=np.pi, shift=2.0):
+    """R seeded rigid motions G_r = Exp([w; v]): w uniform in the ball of radius `angle` by axis and angle, v uniform in
+    [-shift, shift]^3 (the translation part of G_r is V(w) v)."""
+    rng = np.random.default_rng(seed)
+    G = np.empty((R, 4, 4))
+    for r in range(R):
+        ax = rng.normal(size=3)
+        ax /= np.linalg.norm(ax)
+        G[r] = _se3_exp(np.r_[ax * rng.uniform(0.0, angle), rng.uniform(-shift, shift, 3)])
+    return G
+
+
+def se3_multiref(B, R, N=200, index=None, seed=SEED):
+    """B trajectories tracking R distinct references: reference r is path_se3_generate_sine_2 (se3_tracking's path) moved
+    by the rigid motion G_r, q_ref_r[i] = G_r q_ref[i], with the same body twists xi_ref -- the same motion seen from
+    another frame, so each reference stays kinematically consistent.  Trajectory b tracks reference index[b] (default
+    b % R) and starts where se3_tracking places member b, moved by the same G_r: relative to its own reference's first
+    pose.  Returns (prob, x0_q, x0_xi, us0, q_ref [B, N+1, 4, 4], xi_ref [B, N+1, 6], index [B], G [R, 4, 4]); prob is
+    se3_tracking's problem (its shared reference is the unmoved path)."""
+    prob, x0_q, x0_xi, us0 = se3_tracking(B, N=N, seed=seed)
+    index = np.arange(B) % R if index is None else np.asarray(index, dtype=np.int64)
+    if index.shape != (B,) or index.min() < 0 or index.max() >= R:
+        raise ValueError("index must hold B = %d reference numbers in [0, %d)" % (B, R))
+    G = rigid_motions(R, seed=seed + 1)
+    q_refs = np.einsum("rab,ibc->riac", G, prob.q_ref)
+    q_ref = q_refs[index]
+    xi_ref = np.broadcast_to(prob.xi_ref, (B,) + prob.xi_ref.shape).copy()
+    x0_q = np.einsum("bac,bcd->bad", G[index], x0_q)
+    return prob, x0_q, x0_xi, us0, q_ref, xi_ref, index, G
