@@ -170,6 +170,24 @@ size_t tolg_refs_bytes(const tolg_problem* prob, int32_t max_batch);
 int tolg_set_refs(tolg_handle_t h, int32_t B, const double* d_q_ref, const double* d_xi_ref, void* d_refs, size_t refs_bytes,
                   void* stream);
 
+/* Per-trajectory cost weights (diagonal Q, P, R; the reference tunes one controller's weights by hand).
+ * tolg_weights_bytes: bytes of the caller-owned buffer that holds the packed weights of a batch of up to max_batch
+ * trajectories, (24 + m) * Bp * 8 with Bp = max_batch rounded up to a multiple of 4; 0 for an invalid problem.
+ * tolg_set_weights: packs d_q_diag [B][12] (the diagonal of Q: rows 0..5 are the pose block W1, rows 6..11 the twist block
+ * W2), d_p_diag [B][12] (the same for P) and d_r_diag [B][m] (the diagonal of R) into d_w on `stream`; from then on every
+ * batch entry point of the handle -- tolg_solve_batch, tolg_solve_begin, iterate / iterate_until / peek / end,
+ * tolg_linearize_backward, tolg_rollout, tolg_expected_change -- weights trajectory b's cost with its own diagonals, and
+ * must be called with this B (else TOLG_E_ARG).  The weights are not read here: any value the caller gives is used (0 is
+ * legal, a negative one makes the cost indefinite).  tolg_eval_knot keeps the weights of tolg_create.  Like tolg_set_refs
+ * the buffer stays caller-owned and is read by later calls; d_q_diag = NULL returns the handle to the weights of
+ * tolg_create.  Weights and references (tolg_set_refs) are set independently; when both are per trajectory they are for
+ * the same B.
+ * TOLG_E_ARG: B < 1 or B > max_batch, w_bytes < tolg_weights_bytes(prob, B), a solve in flight, references per
+ * trajectory for another B. */
+size_t tolg_weights_bytes(const tolg_problem* prob, int32_t max_batch);
+int tolg_set_weights(tolg_handle_t h, int32_t B, const double* d_q_diag, const double* d_p_diag, const double* d_r_diag,
+                     void* d_w, size_t w_bytes, void* stream);
+
 /* Augmented-Lagrangian box input constraint lb <= u <= ub -- replaces ALConstrainedCost wrapping the
  * tracking cost with an InputConstraint (traoptlibrary/traopt_cost.py:1173-1320,
  * traoptlibrary/traopt_constraints.py:66-169).  d_lb/d_ub [m]; d_lambda, d_imu [B][N][2m] (multipliers
@@ -207,7 +225,8 @@ int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_reg, int32_t
  *   out: d_f_q [n][16], d_f_xi [n][6], d_Fx [n][12][12], d_Fu [n][12][m], d_l [n], d_lx [n][12],
  *        d_lxx [n][12][12], d_lu [n][m], d_luu [n][m][m], d_err [n][12] = [Log(x x_ref^-1); xi - xi_ref].
  * Any output may be NULL.  Uses the handle's workspace: not to be called during a solve in flight.  The cost terms are those of
- * the reference of tolg_create, also on a handle with per-trajectory references (tolg_set_refs). */
+ * the reference and weights of tolg_create, also on a handle with per-trajectory references (tolg_set_refs) or weights
+ * (tolg_set_weights). */
 int tolg_eval_knot(tolg_handle_t h, int32_t i, int32_t n, const double* d_x_q, const double* d_x_xi,
                    const double* d_u, double* d_f_q, double* d_f_xi, double* d_Fx, double* d_Fu, double* d_l,
                    double* d_lx, double* d_lxx, double* d_lu, double* d_luu, double* d_err, void* stream);

@@ -1,0 +1,339 @@
+"""Per-trajectory cost weights (tolg_set_weights): one batched solve in which trajectory b is weighted with its own diagonal
+Q, P and R.
+
+- broadcast: weights that all equal the problem's give the bits of the shared-weight solve on a fresh handle;
+- grouped: distinct weight sets on groups of four (the backward sweep's and the expected change's groups) give the bits of
+  one shared-weight handle per set;
+- interleaved: distinct weights against the CPU oracle on each trajectory's own problem;
+- the per-knot entry point, the full 4096 x 200 size, the handle's state and the argument errors."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import bridge as ob
+from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, _capi, workloads
+from tests.test_gpu_multiref import B13, BROADCAST, MODES, _assert_bitwise, _broadcast, _case, _near, _with_ref
+from tests.test_gpu_parity import _oracle_problem, _rel
+
+pytestmark = pytest.mark.gpu
+
+
+def _rel_nan(a, b):
+    """_rel over the finite entries; NaN where the oracle has NaN (a diverging weight set diverges on both)"""
+    a = np.asarray(a); b = np.asarray(b)
+    assert np.array_equal(np.isnan(a), np.isnan(b))
+    f = ~np.isnan(b)
+    return _rel(a[f], b[f]) if f.any() else 0.0
+
+
+def _with_w(prob, Q, R, P):
+    return TrackingProblem(prob.kind, prob.J, prob.dt, Q, R, P, prob.q_ref, prob.xi_ref, prob.pend_mass, prob.pend_length)
+
+
+def _bw(prob, B):
+    """the problem's own weights, once per trajectory"""
+    t = lambda a: np.broadcast_to(np.asarray(a, float), (B,) + np.shape(a)).copy()  # noqa: E731
+    return dict(Q=t(prob.Q), P=t(prob.P), R=t(prob.R))
+
+
+@pytest.mark.parametrize("case,kw", BROADCAST, ids=["%s-%d" % (c, i) for i, (c, _) in enumerate(BROADCAST)])
+@pytest.mark.parametrize("refs", [False, True], ids=["shared-ref", "pt-ref"])
+def test_broadcast_weights_are_bitwise_the_shared_ones(case, kw, refs):
+    prob, q, xi, us = _case(case)
+    rk = {}
+    if refs:
+        qr, xr = _broadcast(prob, B13)
+        rk = dict(q_ref=qr, xi_ref=xr)
+    r0 = BatchedTrackingILQR(prob, B13).fit_batch(q, xi, us, **rk, **kw)
+    r1 = BatchedTrackingILQR(prob, B13).fit_batch(q, xi, us, **rk, **_bw(prob, B13), **kw)
+    torch.cuda.synchronize()
+    _assert_bitwise(r0, r1, what=case)
+
+
+def test_broadcast_weights_one_call_entry_point():
+    prob, q, xi, us = _case("se3")
+    kw = dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0)
+    r0 = BatchedTrackingILQR(prob, B13).solve_batch_one_call(q, xi, us, **kw)
+    r1 = BatchedTrackingILQR(prob, B13).solve_batch_one_call(q, xi, us, **_bw(prob, B13), **kw)
+    _assert_bitwise(r0, r1)
+
+
+def test_broadcast_weights_al():
+    prob, q, xi, us, lb, ub = workloads.al_tracking(B13, N=200)
+    kw = dict(n_al_iters=4, n_ilqr_iters=30)
+    r0, i0 = BatchedTrackingILQR(prob, B13).al_fit_batch(q, xi, us, lb, ub, **kw)
+    r1, i1 = BatchedTrackingILQR(prob, B13).al_fit_batch(q, xi, us, lb, ub, **_bw(prob, B13), **kw)
+    torch.cuda.synchronize()
+    _assert_bitwise(r0, r1)
+    for k in ("lmbd", "Imu", "mu", "max_violation"):
+        assert torch.equal(i0[k].view(torch.int64), i1[k].view(torch.int64)), k
+    assert i0["outer_iterations"] == i1["outer_iterations"]
+
+
+def _grouped(B, K, N=200):
+    prob, q, xi, us, Q, P, R, idx, sets = workloads.se3_weight_sweep(B, K, N=N)
+    order = np.arange(B) // (B // K)  # groups of B / K consecutive trajectories share a set
+    Qk, Pk, Rk = sets
+    return prob, q, xi, us, Qk[order], Pk[order], Rk[order], order
+
+
+@pytest.mark.parametrize("mode", list(MODES) + ["linear"])
+def test_grouped_weights_match_one_handle_per_set(mode):
+    B, K = 12, 3
+    prob, q, xi, us, Q, P, R, order = _grouped(B, K)
+    kw = dict(MODES.get(mode, dict(mode="ms", n_iterations=25, line_search=True, rollout="linear")))
+    r = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, Q=Q, P=P, R=R, **kw)
+    for g in range(K):
+        rows = slice(4 * g, 4 * g + 4)
+        rg = BatchedTrackingILQR(_with_w(prob, Q[4 * g], R[4 * g], P[4 * g]), 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
+        torch.cuda.synchronize()
+        _assert_bitwise(r, rg, rows_a=rows, what="set %d" % g)
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("refs", [False, True], ids=["shared-ref", "pt-ref"])
+def test_interleaved_weights_match_the_oracle(mode, refs):
+    B, K = 13, 3
+    prob, q, xi, us, Q, P, R, idx, sets = workloads.se3_weight_sweep(B, K)
+    assert list(idx[:4]) == [0, 1, 2, 0]
+    rk, q_ref, xi_ref = {}, None, None
+    if refs:
+        _, q, xi, us, q_ref, xi_ref, _, _ = workloads.se3_multiref(B, 2)
+        rk = dict(q_ref=q_ref, xi_ref=xi_ref)
+    kw = dict(MODES[mode])
+    K_it = kw["n_iterations"]
+    r = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, Q=Q, P=P, R=R, **rk, **kw)
+    torch.cuda.synchronize()
+    okw = dict(mode=kw["mode"], max_iter=K_it, tol_grad=kw.get("tol_grad_norm", 1e-6), tol_defect=kw.get("tol_d_norm", 1e-6),
+               line_search=kw.get("line_search", False))
+    for b in range(B):
+        pb = _with_w(prob, Q[b], R[b], P[b])
+        if refs:
+            pb = _with_ref(pb, q_ref[b], xi_ref[b])
+        o = ob.fit(_oracle_problem(pb), q[b], xi[b], us[b], **okw)
+        n = int(r.iters[b])
+        assert n == o["n_iters"] and int(r.status[b]) == o["status"], b
+        assert _rel_nan(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
+        assert _rel_nan(r.us[b].cpu(), o["us"]) < 1e-6, b
+
+
+def _scaled_sets(prob, K, seed=11, spread=2.0):
+    """K weight sets of any model: every diagonal entry of the problem's Q, P, R scaled by its own factor, log-uniform in
+    [1/spread, spread] (entries that are zero -- the SO(3) embedding's unused blocks -- stay zero)"""
+    rng = np.random.default_rng(seed)
+    ls = np.log(spread)
+    f = lambda A: np.stack([np.diag(np.diag(A) * np.exp(rng.uniform(-ls, ls, A.shape[0]))) for _ in range(K)])  # noqa: E731
+    return f(np.asarray(prob.Q, float)), f(np.asarray(prob.P, float)), f(np.asarray(prob.R, float))
+
+
+def _oracle_w(p):
+    return ob.OracleProblem(p.kind, p.J, p.dt, p.Q, p.R, p.P, p.q_ref, p.xi_ref, pend_mass=p.pend_mass,
+                            pend_length=p.pend_length)
+
+
+MODELS = ["drone", "dense", "pendulum", "so3"]  # k_backward3 (M = 4, SO3), k_backward (dense, pendulum), the ring's DENSE / VARB forms
+MODEL_MODES = {"ms": dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0),
+               "merit": dict(mode="ms", n_iterations=20, line_search=True)}
+
+
+@pytest.mark.parametrize("mode", list(MODEL_MODES))
+@pytest.mark.parametrize("case", MODELS)
+def test_grouped_weights_other_models(case, mode):
+    """sets on groups of four, one per workgroup of the sweeps and of the expected-change ring: the bits of one shared-weight
+    handle per set"""
+    B, K = 12, 3
+    prob, q, xi, us = _case(case)
+    q, xi, us = q[:B], xi[:B], us[:B]
+    Qk, Pk, Rk = _scaled_sets(prob, K)
+    order = np.arange(B) // 4
+    kw = MODEL_MODES[mode]
+    r = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, Q=Qk[order], P=Pk[order], R=Rk[order], **kw)
+    for g in range(K):
+        rows = slice(4 * g, 4 * g + 4)
+        rg = BatchedTrackingILQR(_with_w(prob, Qk[g], Rk[g], Pk[g]), 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
+        torch.cuda.synchronize()
+        _assert_bitwise(r, rg, rows_a=rows, what="%s set %d" % (case, g))
+
+
+@pytest.mark.parametrize("mode", list(MODEL_MODES))
+@pytest.mark.parametrize("case", MODELS)
+def test_interleaved_weights_other_models_match_the_oracle(case, mode):
+    """a different set on each of the four trajectories of a workgroup (b % 3): a kernel that read another group's table or
+    another trajectory's column would weight the wrong trajectory.  Accept-always: six iterations (longer, a few drone and
+    pendulum trajectories diverge under these sets, in the oracle as on the device), equal iterations and status.  Merit: the
+    cost history over the iterations both ran -- where the drone's line search gives up is decided by rounding, with the
+    shared weights as well (its iteration counts differ from the oracle's there), so only the common part is compared."""
+    prob, q, xi, us = _case(case)
+    K = 3
+    Qk, Pk, Rk = _scaled_sets(prob, K, spread=1.5)
+    idx = np.arange(B13) % K
+    kw = dict(MODEL_MODES[mode])
+    if mode == "ms":
+        kw["n_iterations"] = 6
+    r = BatchedTrackingILQR(prob, B13).fit_batch(q, xi, us, Q=Qk[idx], P=Pk[idx], R=Rk[idx], **kw)
+    torch.cuda.synchronize()
+    okw = dict(mode=kw["mode"], max_iter=kw["n_iterations"], tol_grad=kw.get("tol_grad_norm", 1e-6),
+               tol_defect=kw.get("tol_d_norm", 1e-6), line_search=kw.get("line_search", False))
+    for b in range(B13):
+        o = ob.fit(_oracle_w(_with_w(prob, Qk[idx[b]], Rk[idx[b]], Pk[idx[b]])), q[b], xi[b], us[b], **okw)
+        n = int(r.iters[b])
+        if mode == "ms":
+            assert n == o["n_iters"] and int(r.status[b]) == o["status"], b
+            if o["status"] != _capi.ST_OK:  # diverged (status and iteration agree; the blown-up values are not compared)
+                continue
+            assert _rel(r.us[b].cpu(), o["us"]) < 1e-6, b
+        n = min(n, o["n_iters"])
+        assert n >= 1
+        assert _rel_nan(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
+
+
+@pytest.mark.parametrize("ms", [True, False])
+def test_linearize_backward_per_trajectory_weights(ms):
+    B, K = 5, 3
+    prob, *_, Q, P, R, idx, sets = workloads.se3_weight_sweep(B, K)
+    N = prob.N
+    rng = np.random.default_rng(7)
+    xs_q = np.empty((B, N + 1, 4, 4)); xs_xi = np.empty((B, N + 1, 6))
+    for b in range(B):
+        xs_q[b], xs_xi[b] = _near(prob.q_ref, prob.xi_ref, rng)
+    us = rng.normal(size=(B, N, 6))
+    r = BatchedTrackingILQR(prob, B).linearize_backward(xs_q, xs_xi, us, ms=ms, Q=Q, P=P, R=R)
+    torch.cuda.synchronize()
+    for b in range(B):
+        o = ob.lin_backward(_oracle_problem(_with_w(prob, Q[b], R[b], P[b])), xs_q[b], xs_xi[b], us[b], ms=ms)
+        assert _rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
+        assert _rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
+        assert _rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
+        assert float(r["J"][b]) == pytest.approx(o["J"], rel=1e-12)
+        assert _rel(r["K"][b].cpu(), o["K"]) < 1e-8
+        assert _rel(r["k"][b].cpu(), o["k"]) < 1e-8
+
+
+def test_full_size_64_sets():
+    B, K, it = 4096, 64, 10
+    prob, q, xi, us, Q, P, R, order = _grouped(B, K)
+    kw = dict(mode="ms", n_iterations=it, tol_grad_norm=0.0, tol_d_norm=0.0)
+    solver = BatchedTrackingILQR(prob, B)
+    dev = lambda a: torch.as_tensor(a, device="cuda")  # noqa: E731
+    r = solver.fit_batch(q, xi, us, Q=dev(Q), P=dev(P), R=dev(R), **kw)
+    torch.cuda.synchronize()
+    # (accept-always MS diverges under a few of the 64 random sets and stops there, on the device as on one handle per set:
+    # the bits of the groups below are the test)
+    del solver
+    for g0 in (0, 64 * 17 + 8, 64 * 40 + 28, 64 * 63 + 60):  # groups of four inside sets 0, 17, 40, 63
+        rows = slice(g0, g0 + 4)
+        rg = BatchedTrackingILQR(_with_w(prob, Q[g0], R[g0], P[g0]), 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
+        torch.cuda.synchronize()
+        _assert_bitwise(r, rg, rows_a=rows, what="rows %d.." % g0)
+
+
+def test_state_returns_to_the_shared_weights():
+    B, K = 13, 3
+    prob, q, xi, us, Q, P, R, idx, sets = workloads.se3_weight_sweep(B, K)
+    kw = dict(mode="ms", n_iterations=10, tol_grad_norm=0.0, tol_d_norm=0.0)
+    fresh = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, **kw)
+    s = BatchedTrackingILQR(prob, B)
+    own = s.fit_batch(q, xi, us, Q=Q, P=P, R=R, **kw)
+    torch.cuda.synchronize()
+    assert not torch.equal(own.us, fresh.us)
+    again = s.fit_batch(q, xi, us, **kw)  # Python: a call without weights is a shared-weight call
+    torch.cuda.synchronize()
+    _assert_bitwise(fresh, again, what="python")
+    s.fit_batch(q, xi, us, Q=Q, P=P, R=R, **kw)
+    torch.cuda.synchronize()
+    assert s.lib.tolg_set_weights(s._h, B, None, None, None, None, 0, None) == 0  # C ABI: back to the shared weights
+    s.clear_per_trajectory()  # the solver's own record of what it set (the C call above bypassed it)
+    again = s.solve_batch_one_call(q, xi, us, **kw)
+    fresh1 = BatchedTrackingILQR(prob, B).solve_batch_one_call(q, xi, us, **kw)
+    _assert_bitwise(fresh1, again, what="C")
+    own2 = s.fit_batch(q, xi, us, Q=Q, P=P, R=R, **kw)
+    torch.cuda.synchronize()
+    _assert_bitwise(own, own2)
+
+
+def test_argument_errors():
+    B, K, N = 6, 2, 30
+    prob, q, xi, us, Q, P, R, idx, sets = workloads.se3_weight_sweep(B, K, N=N)
+    s = BatchedTrackingILQR(prob, 8)
+    lib, h, E = s.lib, s._h, -1
+    dev = dict(dtype=torch.float64, device=s.device)
+    qd = torch.as_tensor(np.diagonal(Q, axis1=1, axis2=2).copy(), **dev)
+    pd = torch.as_tensor(np.diagonal(P, axis1=1, axis2=2).copy(), **dev)
+    rd = torch.as_tensor(np.diagonal(R, axis1=1, axis2=2).copy(), **dev)
+    nbytes = int(lib.tolg_weights_bytes(C.byref(s._p), 8))
+    buf = torch.empty(nbytes // 8, **dev)
+    st = s._stream()
+    Pt = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    assert lib.tolg_set_weights(h, 0, Pt(qd), Pt(pd), Pt(rd), Pt(buf), nbytes, st) == E
+    assert lib.tolg_set_weights(h, 9, Pt(qd), Pt(pd), Pt(rd), Pt(buf), nbytes, st) == E
+    small = 30 * 8 * 8 - 8  # one double short of B = 6 (Bp = 8)
+    assert lib.tolg_set_weights(h, B, Pt(qd), Pt(pd), Pt(rd), Pt(buf), small, st) == E
+    # references per trajectory for another B
+    _, _, _, _, q_ref, xi_ref, _, _ = workloads.se3_multiref(B - 2, 2, N=N)
+    rbytes = int(lib.tolg_refs_bytes(C.byref(s._p), 8))
+    rbuf = torch.empty(rbytes // 8, **dev)
+    qr = torch.as_tensor(q_ref.reshape(B - 2, N + 1, 16), **dev); xr = torch.as_tensor(xi_ref, **dev)
+    assert lib.tolg_set_refs(h, B - 2, Pt(qr), Pt(xr), Pt(rbuf), rbytes, st) == 0
+    assert lib.tolg_set_weights(h, B, Pt(qd), Pt(pd), Pt(rd), Pt(buf), nbytes, st) == E
+    assert lib.tolg_set_refs(h, B, None, None, None, 0, st) == 0
+    assert lib.tolg_set_weights(h, B, Pt(qd), Pt(pd), Pt(rd), Pt(buf), small + 8, st) == 0
+    assert lib.tolg_set_refs(h, B - 2, Pt(qr), Pt(xr), Pt(rbuf), rbytes, st) == E
+    # a batch call with another B than the weights were set for
+    x0q = torch.as_tensor(q.reshape(B, 16), **dev); x0xi = torch.as_tensor(xi, **dev); u0 = torch.as_tensor(us, **dev)
+    opt = _capi.Options(_capi.MODE_MS, 4, 0, 0, 0.0, 0.0, 1e10, _capi.SCHED_AUTO, 0)
+    nul = C.c_void_p(0)
+    assert lib.tolg_solve_begin(h, C.byref(opt), B - 1, Pt(x0q), Pt(x0xi), Pt(u0), *([nul] * 5), st) == E
+    xs_q = torch.as_tensor(np.broadcast_to(q[:, None], (B, N + 1, 4, 4)).copy(), **dev)
+    xs_xi = torch.as_tensor(np.broadcast_to(xi[:, None], (B, N + 1, 6)).copy(), **dev)
+    md = torch.ones(B, 2, **dev)
+    assert lib.tolg_linearize_backward(h, 1, 1e10, B - 1, Pt(xs_q), Pt(xs_xi), Pt(u0), Pt(md), *([nul] * 9), st) == E
+    assert lib.tolg_rollout(h, 1, 0, 1.0, B - 1, nul, nul, nul, st) == E
+    assert lib.tolg_expected_change(h, 2, B - 1, nul, nul, st) == E
+    # in flight: no tolg_set_weights between begin and end
+    assert lib.tolg_solve_begin(h, C.byref(opt), B, Pt(x0q), Pt(x0xi), Pt(u0), *([nul] * 5), st) == 0
+    assert lib.tolg_set_weights(h, B, Pt(qd), Pt(pd), Pt(rd), Pt(buf), nbytes, st) == E
+    assert lib.tolg_set_weights(h, B, None, None, None, None, 0, st) == E
+    assert lib.tolg_solve_iterate(h, 4, st) == 0
+    out = [torch.empty(B, N + 1, 16, **dev), torch.empty(B, N + 1, 6, **dev), torch.empty(B, N, 6, **dev)]
+    ints = [torch.empty(B, dtype=torch.int32, device=s.device) for _ in range(3)]
+    assert lib.tolg_solve_end(h, *[Pt(t) for t in out + ints], st) == 0
+    assert lib.tolg_set_weights(h, B, None, None, None, None, 0, st) == 0
+    torch.cuda.synchronize()
+
+
+def test_zero_weights_are_legal():
+    """R = 0 (config 4 of the reference's benchmark) per trajectory: the C layer does not judge the values."""
+    B, K = 8, 2
+    prob, q, xi, us, Q, P, R, idx, sets = workloads.se3_weight_sweep(B, K)
+    R = R.copy(); R[::2] = 0.0
+    kw = dict(mode="ms", n_iterations=5, tol_grad_norm=0.0, tol_d_norm=0.0)
+    r = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, Q=Q, P=P, R=R, **kw)
+    torch.cuda.synchronize()
+    for b in (0, 1):
+        o = ob.fit(_oracle_problem(_with_w(prob, Q[b], R[b], P[b])), q[b], xi[b], us[b], mode="ms", max_iter=5, tol_grad=0.0,
+                   tol_defect=0.0)
+        n = int(r.iters[b])
+        assert n == o["n_iters"] and int(r.status[b]) == o["status"], b
+        if n:
+            assert _rel_nan(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
+
+
+def test_mirror_fit_batch_weights():
+    """The mirror's MS controller sweeps weights in one call: each initial state with its own (Q, R, P)."""
+    from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_controller import iLQR_Tracking_SE3_MS
+    from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_cost import SE3TrackingQuadraticGaussNewtonCost
+    from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_dynamics import SE3Dynamics
+    B, K, N = 6, 3, 60
+    prob, q, xi, us, Q, P, R, idx, sets = workloads.se3_weight_sweep(B, K, N=N)
+    dyn = SE3Dynamics(prob.J, prob.dt)
+    cost = SE3TrackingQuadraticGaussNewtonCost(prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
+    ctl = iLQR_Tracking_SE3_MS(dyn, cost, N, prob.q_ref, prob.xi_ref)
+    x0s = [[q[b], xi[b]] for b in range(B)]
+    r = ctl.fit_batch(x0s, us, n_iterations=10, weights=[(Q[b], R[b], P[b]) for b in range(B)])
+    torch.cuda.synchronize()
+    direct = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, mode="ms", n_iterations=10, tol_grad_norm=ctl._default_tol,
+                                                    Q=Q, P=P, R=R, **ctl._options())
+    torch.cuda.synchronize()
+    _assert_bitwise(r, direct)

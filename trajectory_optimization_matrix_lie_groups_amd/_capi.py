@@ -26,7 +26,7 @@ class Options(C.Structure):
 _lib = None
 SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_batch", "tolg_solve_begin",
            "tolg_solve_iterate", "tolg_solve_iterate_until", "tolg_solve_end", "tolg_solve_peek", "tolg_solve_active_count", "tolg_set_al", "tolg_al_update",
-           "tolg_refs_bytes", "tolg_set_refs", "tolg_eval_knot", "tolg_linearize_backward",
+           "tolg_refs_bytes", "tolg_set_refs", "tolg_weights_bytes", "tolg_set_weights", "tolg_eval_knot", "tolg_linearize_backward",
            "tolg_rollout", "tolg_expected_change", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
 
 
@@ -69,6 +69,10 @@ def load():
     lib.tolg_refs_bytes.argtypes = [C.POINTER(Problem), C.c_int32]
     lib.tolg_set_refs.restype = C.c_int
     lib.tolg_set_refs.argtypes = [vp, C.c_int32, dp, dp, vp, C.c_size_t, vp]
+    lib.tolg_weights_bytes.restype = C.c_size_t
+    lib.tolg_weights_bytes.argtypes = [C.POINTER(Problem), C.c_int32]
+    lib.tolg_set_weights.restype = C.c_int
+    lib.tolg_set_weights.argtypes = [vp, C.c_int32, dp, dp, dp, vp, C.c_size_t, vp]
     lib.tolg_al_update.restype = C.c_int
     lib.tolg_al_update.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_double, dp, ip, vp]
     lib.tolg_eval_knot.restype = C.c_int

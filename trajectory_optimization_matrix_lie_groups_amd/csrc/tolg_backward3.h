@@ -253,7 +253,9 @@ enum { B3_DATA = 5120, B3_ZBYTES = 256,
 // use a v_accvgpr copy); without them 254 and no AGPR -- 0.338 -> 0.304 ms at 4096 x 200 on one box (tools/ab_libs.sh;
 // profiles/r04_k2_fast_only_ab.txt), and two waves fit a SIMD at batches beyond 4096.  The first sweep of a solve (mu = 1) goes
 // to the full kernel directly; a sweep with nothing to redo pays one launch of waves that read a flag and leave.
-template <int M, bool GRAV, bool AL, bool FAST = false>
+// PTW: the weights of trajectory b (tolg_set_weights) in the per-lane 2 W2, Rt and terminal 2 P2 columns, read once per group
+// (the same values, and then the same arithmetic, as the batch-shared constants of a diagonal Q / P / R)
+template <int M, bool GRAV, bool AL, bool FAST = false, bool PTW = false>
 __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
   // flags: bit 0 multiple shooting; bit 1 the records come from the fused rollout, whose trajectories are closed
   // (x_{i+1} = f(x_i, u_i)): the defect field is not written there and reads as zero here
@@ -308,15 +310,22 @@ __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
 #pragma unroll
   for (int u = 0; u < M; u++) { bu[u] = fu_entry<M>(*P.c, urow<M>(u) - 6, u); ibu[u] = 1.0 / bu[u]; }  // generic pointer: note at DConsts
   double kBW[6], Rt[M], wm[M];
+  if constexpr (PTW) {
+    const double wd = (j >= 6 && j < 12) ? C.wts[(size_t)(WT_W2 + (j >= 6 && j < 12 ? j - 6 : 0)) * P.Bp + b] : 0.0;
 #pragma unroll
-  for (int r = 0; r < 6; r++) kBW[r] = (j >= 6 && j < 12) ? 2.0 * C.W2[6 * r + (j - 6)] : 0.0;
+    for (int r = 0; r < 6; r++) kBW[r] = (j >= 6 && j < 12) ? 2.0 * (r == j - 6 ? wd : 0.0) : 0.0;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 6; r++) kBW[r] = (j >= 6 && j < 12) ? 2.0 * C.W2[6 * r + (j - 6)] : 0.0;
+  }
   {
     double ibc = 0.0;
 #pragma unroll
     for (int u = 0; u < M; u++) if (mycol == u) ibc = ibu[u];
+    const double rd = (PTW && mycol >= 0) ? C.wts[(size_t)(WT_R + (mycol >= 0 ? mycol : 0)) * P.Bp + b] : 0.0;
 #pragma unroll
     for (int u = 0; u < M; u++) {
-      Rt[u] = (mycol >= 0) ? 2.0 * C.R[u * M + (mycol >= 0 ? mycol : 0)] * ibu[u] * ibc : 0.0;
+      Rt[u] = (mycol >= 0) ? 2.0 * (PTW ? (u == mycol ? rd : 0.0) : C.R[u * M + (mycol >= 0 ? mycol : 0)]) * ibu[u] * ibc : 0.0;
       wm[u] = (mycol > u) ? 1.0 : 0.0;
     }
   }
@@ -431,12 +440,13 @@ __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
   {
     __amdgpu_buffer_rsrc_t rR = mkbuf(P.REC + recStride * N, (unsigned)P.recF * sB);
     const unsigned OOB = 0x40000000u;
+    const double pd = (PTW && j >= 6 && j < 12) ? C.wts[(size_t)(WT_P2 + (j >= 6 && j < 12 ? j - 6 : 0)) * P.Bp + b] : 0.0;
 #pragma unroll
     for (int r = 0; r < 6; r++) {
       const int fl = (j < 6) ? REC_LXX + sym6(r, j) : REC_LX + r;
       double t1 = bld(rR, hL ? vr + FOFF(fl) : OOB, 0), t2 = bld(rR, isVec ? vr + FOFF(REC_LX + 6 + r) : OOB, 0);
       V[r] = t1;
-      double p2 = (j >= 6 && j < 12) ? 2.0 * C.P2[6 * r + (j - 6)] : 0.0;
+      double p2 = (j >= 6 && j < 12) ? 2.0 * (PTW ? (r == j - 6 ? pd : 0.0) : C.P2[6 * r + (j - 6)]) : 0.0;
       V[6 + r] = t2 + p2;
     }
   }

@@ -75,7 +75,8 @@ TOLG_DEV void ec_dma4(const void* sbase, unsigned v0, unsigned v1, unsigned v2, 
 // on the DMA ring add them up.
 // VARB (with DENSE and GRAV: Pendulum3dDyanmics): the input matrix differs from knot to knot -- its 3 x 3 block F_u[6:9, 0:3] is the
 // record's REC_BU (which takes REC_TRI's place; the block it displaces is zero for this model) and is read from the ring.
-template <int M, bool GRAV, bool STORE = false, bool DENSE = false, bool VARB = false>
+// PTW: the pinned 2 R, 2 W2 and 2 P2 rows are those of trajectory b (tolg_set_weights), loaded once per lane
+template <int M, bool GRAV, bool STORE = false, bool DENSE = false, bool VARB = false, bool PTW = false>
 __global__ __launch_bounds__(64) void k_expected_change_ring(Params P) {
   static_assert(!VARB || (DENSE && GRAV && M == 6), "VARB: the pendulum's instantiation");
   typedef EcLds<DENSE> L;
@@ -154,15 +155,18 @@ __global__ __launch_bounds__(64) void k_expected_change_ring(Params P) {
     for (int k = 0; k < 3; k++) oBU[k] = (vrow && j < 9) ? lg + FOFF(REC_BU + 3 * (j - 6) + k) : ZP;
   }
   double fuc[M], R2r[M], W2r[6], P2r[6];
+  // PTW: this lane's diagonal entries of R (row j < M) and of W2 / P2 (row j6) for trajectory b
+  const double rd = PTW ? G.wts[(size_t)(WT_R + (j < M ? j : 0)) * P.Bp + b] : 0.0;
+  const double wd = PTW ? G.wts[(size_t)(WT_W2 + j6) * P.Bp + b] : 0.0, pd = PTW ? G.wts[(size_t)(WT_P2 + j6) * P.Bp + b] : 0.0;
 #pragma unroll
   for (int k = 0; k < M; k++) {
     fuc[k] = (VARB && vrow && j < 9 && k < 3) ? 0.0 : mV * fu_entry<M>(G, j6, k);  // F_u[j][k]
-    R2r[k] = mU * 2.0 * G.R[(j < M ? j : 0) * M + k];  // l_uu row
+    R2r[k] = mU * 2.0 * (PTW ? ((j < M ? j : 0) == k ? rd : 0.0) : G.R[(j < M ? j : 0) * M + k]);  // l_uu row
   }
 #pragma unroll
   for (int c = 0; c < 6; c++) {
-    W2r[c] = mV * 2.0 * G.W2[6 * j6 + c];  // l_xx twist block, row j - 6 (traopt_cost.py:702)
-    P2r[c] = mV * 2.0 * G.P2[6 * j6 + c];
+    W2r[c] = mV * 2.0 * (PTW ? (j6 == c ? wd : 0.0) : G.W2[6 * j6 + c]);  // l_xx twist block, row j - 6 (traopt_cost.py:702)
+    P2r[c] = mV * 2.0 * (PTW ? (j6 == c ? pd : 0.0) : G.P2[6 * j6 + c]);
   }
   double LL[GRAV ? 3 : 1][3];  // gravity block A21 = sum_a rte_a Llin[a]: row j - 6, columns 0..2
   if constexpr (GRAV) {

@@ -45,6 +45,9 @@ struct Consts {
   // gravity block of F_x is linear in rte = R^T (0,0,-1): A21 = sum_a rte_a Llin[a] (times dt, 6x6
   // row-major each, no m*g: App. C-Q2)
   double Llin[3][36];
+  // per-trajectory cost weights (tolg_set_weights, caller-owned): [wt_fields(m)][Bp] (WT_*), read by the PT_W / PTW kernels only.
+  // Here and not in Params, whose size would move the kernel arguments behind it in every kernel; k_pack_weights sets it.
+  const double* wts;
 };
 
 // Device-side view of the constants used by the three hot kernels: address space 4 (constant), so
@@ -177,6 +180,33 @@ template <> struct RefAt<true> {
   TOLG_DEV RefAt(const double* ref, int i, int b, int Bp) : r(ref + (size_t)i * 13 * (size_t)Bp + (size_t)b), s((size_t)Bp) {}
   TOLG_DEV double operator[](int c) const { return r[(size_t)c * s]; }
 };
+// What a knot-level kernel reads per trajectory (template argument PT): PT_REF its reference (tolg_set_refs), PT_W its cost
+// weights (tolg_set_weights).  0 is the batch-shared form of every kernel.
+enum { PT_REF = 1, PT_W = 2 };
+// Per-trajectory cost weights (tolg_set_weights): the diagonals of W1, W2 (Q), P1, P2 (P) and R, packed [WT_F][Bp] (field
+// f of trajectory b at f * Bp + b: a weight load is coalesced over the batch like a state load)
+enum { WT_W1 = 0, WT_W2 = 6, WT_P1 = 12, WT_P2 = 18, WT_R = 24 };
+constexpr int wt_fields(int m) { return 24 + m; }  // fields per trajectory (even: m = 4 or 6)
+// A diagonal NN x NN weight block of one trajectory, read by the row-major index of the Consts array it stands for: the
+// diagonal entries from the packed weights (stride s), every other entry 0.0.  Loops written against the Consts arrays then
+// do the same arithmetic on the same values as the batch-shared form (an off-diagonal term is fma(0, x, s) = s there too).
+template <int NN> struct DiagAt {
+  const double* p; size_t s;
+  TOLG_DEV double operator[](int idx) const { return idx % (NN + 1) == 0 ? p[(size_t)(idx / (NN + 1)) * s] : 0.0; }
+};
+// a table of 2 x weights in LDS: the batch-shared NN x NN array, or (PTW) the diagonal of the thread's trajectory
+template <bool PTW, int NN>
+TOLG_DEV auto wtab(const double* diag, const double* full) {
+  if constexpr (PTW) return DiagAt<NN>{diag, 1};
+  else return full;
+}
+// the block a kernel reads: without PTW the Consts array (sel ? a : d, as the shared form has always selected it), with PTW
+// trajectory b's diagonal (fields fa / fd of the packed weights)
+template <bool PTW, int NN, class T>
+TOLG_DEV auto wblock(const double* wts, const Params& P, int b, bool sel, T* a, T* d, int fa, int fd) {
+  if constexpr (PTW) return DiagAt<NN>{wts + (size_t)(sel ? fa : fd) * P.Bp + b, (size_t)P.Bp};
+  else return sel ? a : d;
+}
 
 // Raw buffer access for the sequential kernels: the descriptor (SRD) addresses one knot, the lane
 // supplies a 32-bit byte offset (its trajectory), the field offset is a wave-uniform SGPR -- no
@@ -652,7 +682,7 @@ TOLG_DEV void rec_run(const Params& P, int i, int b, const double (&v)[N]) {
 // TERM: -1 = decided per lane (i == N), 0 / 1 = the caller knows that no / every lane it calls with sits on the
 // terminal knot.  With a wave-uniform answer the weight matrices below are selected once per wave and read with
 // scalar loads; a per-lane select turns every one of their ~150 reads into a vector-memory load of one address.
-template <int M, bool CLOSED = false, int TERM = -1, bool PTREF = false, class CT, class NextFn>
+template <int M, bool CLOSED = false, int TERM = -1, int PT = 0, class CT, class NextFn>
 TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const State& S, const double (&u)[M],
                        NextFn next_state, double* lcost = nullptr) {
   const bool term = TERM < 0 ? (i == P.N) : (TERM == 1);
@@ -662,7 +692,7 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
   // One gate for all the series evaluations of the knot: the tracking error (Log, then V^-1 and Q at its angle,
   // which the Log bounds cover) and the step rotation (V, Q, Exp at dt w).
   const V3 wd = dt * S.w, vd = dt * S.v;
-  const RefAt<PTREF> r(P.ref, i, b, P.Bp);
+  const RefAt<(PT & PT_REF) != 0> r(P.ref, i, b, P.Bp);
   Pose Xr;
   Xr.q.x = r[0]; Xr.q.y = r[1]; Xr.q.z = r[2]; Xr.q.w = r[3];
   Xr.t = v3(r[4], r[5], r[6]);
@@ -681,6 +711,10 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
     const auto W2 = term ? &C.P2[0] : &C.W2[0];
     const auto G1 = (term && !so3) ? &C.P1[0] : &C.W1[0];
     const auto G2 = (term && !so3) ? &C.P2[0] : &C.W2[0];
+    // PT_W: entry idx of an NN x NN block is trajectory b's diagonal (fields F.. of the packed weights, vector loads) or 0.0,
+    // in place of the array (the condition is a constant: the shared form compiles to exactly the array reads above)
+    constexpr bool PTW = (PT & PT_W) != 0;
+#define LK_W(arr, F, NN, idx) (PTW ? ((idx) % ((NN) + 1) == 0 ? C.wts[(size_t)((F) + (idx) / ((NN) + 1)) * P.Bp + b] : 0.0) : arr[idx])
     double e[6] = {ew.x, ew.y, ew.z, ev.x, ev.y, ev.z};
     double ve[6] = {S.w.x - r[7], S.w.y - r[8], S.w.z - r[9], S.v.x - r[10], S.v.y - r[11], S.v.z - r[12]};
     double th2 = dot(ew, ew);
@@ -718,7 +752,10 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
     for (int a = 0; a < 6; a++) {
       double s1 = 0, s2 = 0;
 #pragma unroll
-      for (int k = 0; k < 6; k++) { s1 += G1[6 * a + k] * e[k]; s2 += G2[6 * a + k] * ve[k]; }
+      for (int k = 0; k < 6; k++) {
+        s1 += LK_W(G1, (term && !so3) ? WT_P1 : WT_W1, 6, 6 * a + k) * e[k];
+        s2 += LK_W(G2, (term && !so3) ? WT_P2 : WT_W2, 6, 6 * a + k) * ve[k];
+      }
       We[a] = s1; W2v[a] = s2;
       l += e[a] * s1 + ve[a] * s2;
     }
@@ -726,7 +763,7 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
 #pragma unroll
       for (int a = 0; a < M; a++)
 #pragma unroll
-        for (int k = 0; k < M; k++) l += u[a] * C.R[a * M + k] * u[k];
+        for (int k = 0; k < M; k++) l += u[a] * LK_W(C.R, WT_R, M, a * M + k) * u[k];
     }
     if (!term) {  // l_u = 2 R u (traopt_cost.py:792-804)
       double lu[M], luu[M];
@@ -734,7 +771,7 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
       for (int a = 0; a < M; a++) {
         double sacc = 0;
 #pragma unroll
-        for (int k = 0; k < M; k++) sacc += 2.0 * C.R[a * M + k] * u[k];
+        for (int k = 0; k < M; k++) sacc += 2.0 * LK_W(C.R, WT_R, M, a * M + k) * u[k];
         lu[a] = sacc;
         luu[a] = 0.0;
       }
@@ -770,7 +807,7 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
       for (int c = 0; c < 6; c++) {
         double s = 0;
 #pragma unroll
-        for (int k = 0; k < 6; k++) s += W1[6 * a + k] * Je[6 * k + c];
+        for (int k = 0; k < 6; k++) s += LK_W(W1, term ? WT_P1 : WT_W1, 6, 6 * a + k) * Je[6 * k + c];
         WJ[6 * a + c] = s;
       }
     double lxx[21], lxv[12];
@@ -791,6 +828,7 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
     }
     rec_run<REC_LXX, 21, RP>(P, i, b, lxx);
     rec_run<REC_LX, 12, RP>(P, i, b, lxv);
+#undef LK_W
   }
   if (term) return;
   // ---------------- dynamics Jacobian blocks (traopt_dynamics.py:802-837, :1416-1469)
@@ -898,7 +936,7 @@ TOLG_DEV bool ls_quad_form(const Params& P, int list, int nslots);  // (line-sea
 #ifndef TOLG_K1_WPE
 #define TOLG_K1_WPE 2
 #endif
-template <int M, bool PTREF>
+template <int M, int PT>
 __global__ __launch_bounds__(256, TOLG_K1_WPE) void k_linearize(Params P, const double* __restrict__ src,
                                                     const double* __restrict__ src_u, double* __restrict__ dst,
                                                     double* __restrict__ dst_u, int ms, int i0, int ni, int ls_list, int ls_nslots) {
@@ -932,7 +970,7 @@ __global__ __launch_bounds__(256, TOLG_K1_WPE) void k_linearize(Params P, const 
       if (dst_u) dst_u[UIDX(a, i, b)] = u[a];
     }
   }
-  lin_knot<M, false, -1, PTREF>(P, C, i, b, ms, S, u, [&]() { return load_state(P, src, i + 1, e); });
+  lin_knot<M, false, -1, PT>(P, C, i, b, ms, S, u, [&]() { return load_state(P, src, i + 1, e); });
 }
 
 // per-trajectory sums of the stage costs / squared defects, fixed order (deterministic);
@@ -1370,7 +1408,9 @@ TOLG_DEV void ldl_solve(const double (&a)[M], const double (&rinv)[M], double (&
 // FAST (round 4): as for k_backward3 (tolg_backward3.h) -- only the first, unregularised attempt compiled in; a group that meets
 // anything else is flagged in P.k2_redo and redone by the full kernel launched behind (flag bit 2), P.k2_hint keeps groups whose
 // last sweep needed the retry loop away from the fast attempt.
-template <int M, bool VARB = false, bool GRAV = true, bool DIAGJ = false, bool FAST = false>
+// PTW: the weights of trajectory b (tolg_set_weights): the constant table KC is one per group of sixteen lanes (each group
+// writes its own), and the terminal 2 P2 column is the group's own
+template <int M, bool VARB = false, bool GRAV = true, bool DIAGJ = false, bool FAST = false, bool PTW = false>
 __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
   // flags: bit 0 multiple shooting; bit 1 the records come from the fused rollout, whose trajectories are closed
   // (x_{i+1} = f(x_i, u_i)): the defect field is not written there and reads as zero here; bit 2: only the groups the fast
@@ -1393,7 +1433,8 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
   // (FAST: 252 registers would let two workgroups share a SIMD, and the dispatcher then packs some SIMDs with two waves and
   // leaves others idle -- the dense-inertia SS bench ran this kernel at 0.62 ms against 0.41 with an even spread; the transpose
   // scratch is over-allocated to 35 KB so that a CU takes four workgroups, one per SIMD)
-  __shared__ double TR[FAST ? 28 : 4][12 * 13];
+  // (PTW: the four constant tables take 12 KB more; the padding shrinks by as much, so that a CU still takes four workgroups)
+  __shared__ double TR[FAST ? (PTW ? 18 : 28) : 4][12 * 13];
   __shared__ double TRZ[12];  // zeros: what the vector lanes "transpose-read" (see the symmetrisation below)
 
   // lane-dependent constants
@@ -1404,29 +1445,34 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
   // Per-lane constant columns (2 W2, 2 R, and the two views of F_u).  They live in LDS, not in 48 VGPRs:
   // the kernel is far over the 256 architectural registers and every value parked in an AGPR costs a
   // v_accvgpr copy per use, while LDS is otherwise idle here.  Row stride 25 doubles: conflict-free.
-  __shared__ double KC[16][31];
+  __shared__ double KC[PTW ? 4 : 1][16][31];
   // Lanes 0..M-1 and lanes 6..11 need different constants and never look at each other's: one slot
   // holds 2R (lanes < M) or the row view of F_u (lanes 6..11), the other the column view of F_u (lanes
   // < M) or 2 W2 (lanes 6..11).  Where a lane reads the "wrong" half the result is never used, except
   // in the l_xx update, which masks it.
   enum { KC_RB = 0, KC_BW = 6, KC_BT = 12, KC_BB = 21, KC_BD = 30 };  // KC_BT/BB: same in every row; KC_BD: B[6+j][j]
-  if (g == 0) {
+  if (PTW || g == 0) {
+    double (&KCw)[16][31] = KC[PTW ? g : 0];
+    // PTW: this lane's diagonal entries of W2 (lanes 6..11) and R (lanes < M) for trajectory b
+    const double wd = (PTW && j >= 6 && j < 12) ? C.wts[(size_t)(WT_W2 + (j >= 6 && j < 12 ? j - 6 : 0)) * P.Bp + b] : 0.0;
+    const double rd = (PTW && j < M) ? C.wts[(size_t)(WT_R + (j < M ? j : 0)) * P.Bp + b] : 0.0;
 #pragma unroll
     for (int r = 0; r < 6; r++) {
-      KC[j][KC_BW + r] = (j >= 6 && j < 12) ? 2.0 * C.W2[6 * r + (j - 6)] : (j < M) ? fu_entry<M>(*P.c, r, j) : 0.0;  // B[6+r][j]
+      KCw[j][KC_BW + r] = (j >= 6 && j < 12) ? 2.0 * (PTW ? (r == j - 6 ? wd : 0.0) : C.W2[6 * r + (j - 6)])
+                          : (j < M) ? fu_entry<M>(*P.c, r, j) : 0.0;  // B[6+r][j]
     }
 #pragma unroll
     for (int u = 0; u < 6; u++) {
-      KC[j][KC_RB + u] = (u < M && j < M) ? 2.0 * C.R[(u < M ? u : 0) * M + j]
-                         : (u < M && j >= 6 && j < 12) ? fu_entry<M>(*P.c, j - 6, u < M ? u : 0) : 0.0;  // B[j][u]
+      KCw[j][KC_RB + u] = (u < M && j < M) ? 2.0 * (PTW ? (u == j ? rd : 0.0) : C.R[(u < M ? u : 0) * M + j])
+                          : (u < M && j >= 6 && j < 12) ? fu_entry<M>(*P.c, j - 6, u < M ? u : 0) : 0.0;  // B[j][u]
     }
 #pragma unroll
-    for (int k = 0; k < 9; k++) { KC[j][KC_BT + k] = P.c->Bt[k]; KC[j][KC_BB + k] = P.c->Bb[k]; }
-    KC[j][KC_BD] = (j < M) ? fu_entry<M>(*P.c, j < 6 ? j : 0, j) : 0.0;
+    for (int k = 0; k < 9; k++) { KCw[j][KC_BT + k] = P.c->Bt[k]; KCw[j][KC_BB + k] = P.c->Bb[k]; }
+    KCw[j][KC_BD] = (j < M) ? fu_entry<M>(*P.c, j < 6 ? j : 0, j) : 0.0;
   }
   if (lane < 12) TRZ[lane] = 0.0;
   __builtin_amdgcn_wave_barrier();
-  const double* KCj = KC[j];
+  const double* KCj = KC[PTW ? g : 0][j];
   // V <- (V + V^T) / 2 for the matrix columns, V <- V for the vector columns, without a per-entry select: a vector
   // lane reads zeros for the transposed entry and scales by 1 instead of 1/2 (bitwise what the select gave)
   const double* trd = (j < 12) ? &TR[g][j * 13] : TRZ;
@@ -1479,11 +1525,12 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
   double V[12];
   {
     __amdgpu_buffer_rsrc_t rR = mkbuf(P.REC + recStride * N, (unsigned)P.recF * sB);
+    const double pd = (PTW && j >= 6 && j < 12) ? C.wts[(size_t)(WT_P2 + (j >= 6 && j < 12 ? j - 6 : 0)) * P.Bp + b] : 0.0;
 #pragma unroll
     for (int r = 0; r < 6; r++) {
       double t1 = bld(rR, vL[r], 0), t2 = bld(rR, vVec, FOFF(REC_LX + 6 + r));
       V[r] = t1;
-      double p2 = (j >= 6 && j < 12) ? 2.0 * C.P2[6 * r + (j - 6)] : 0.0;
+      double p2 = (j >= 6 && j < 12) ? 2.0 * (PTW ? (r == j - 6 ? pd : 0.0) : C.P2[6 * r + (j - 6)]) : 0.0;
       V[6 + r] = t2 + p2;
     }
   }
@@ -2283,7 +2330,7 @@ TOLG_DEV State rl_in_state(const char* slot, int tt) {
 }
 template <int M>
 constexpr size_t rl_static_lds() { return (size_t)RL_DEPTH * RlIn<M>::SLOT + (size_t)RL_RING * RL_PAIRS * 256 + 32; }
-template <int M, bool PTREF>
+template <int M, int PT>
 __global__ __launch_bounds__(256) void k_rollout_lin(Params P, int it) {
   typedef RlIn<M> IN;
   const DConsts& C = *(const DConsts*)P.c;
@@ -2550,8 +2597,8 @@ __global__ __launch_bounds__(256) void k_rollout_lin(Params P, int it) {
       if (i > 0) store_state<TOLG_NT_CURST>(P, P.cur, i, b, S);  // the accepted candidate becomes the nominal trajectory
       // the terminal knot (in the last group only) goes separately: see lin_knot's TERM
       double lc = 0.0;
-      if (i < N) lin_knot<M, true, 0, PTREF>(P, C, i, b, 1, S, u, [&]() { return S; }, &lc);
-      if (4 * g + 3 >= N && i == N) lin_knot<M, true, 1, PTREF>(P, C, i, b, 1, S, u, [&]() { return S; }, &lc);
+      if (i < N) lin_knot<M, true, 0, PT>(P, C, i, b, 1, S, u, [&]() { return S; }, &lc);
+      if (4 * g + 3 >= N && i == N) lin_knot<M, true, 1, PT>(P, C, i, b, 1, S, u, [&]() { return S; }, &lc);
       jpart += lc;
     }
     done++;
@@ -2619,9 +2666,10 @@ TOLG_DEV bool ls_quad_form(const Params& P, int list, int nslots) { return list 
 
 // stage cost l(x, u, i) / terminal cost (traopt_cost.py:675-738)
 // FAST: the series forms of tolg_lie.h (what the rollouts and the linearisation use) in place of the closed-form Log
-template <int M, bool FAST = false, bool PTREF = false>
+template <int M, bool FAST = false, int PT = 0>
 TOLG_DEV double knot_cost(const Params& P, const Consts& C, int i, int b, const State& S, const double (&u)[M], bool term) {
-  const RefAt<PTREF> r(P.ref, i, b, P.Bp);
+  constexpr bool PTW = (PT & PT_W) != 0;
+  const RefAt<(PT & PT_REF) != 0> r(P.ref, i, b, P.Bp);
   Pose Xr;
   Xr.q.x = r[0]; Xr.q.y = r[1]; Xr.q.z = r[2]; Xr.q.w = r[3];
   Xr.t = v3(r[4], r[5], r[6]);
@@ -2629,8 +2677,9 @@ TOLG_DEV double knot_cost(const Params& P, const Consts& C, int i, int b, const 
   if constexpr (FAST) se3_log_fast(se3_compose(S.X, se3_inverse(Xr)), ew, ev);
   else se3_log(se3_compose(S.X, se3_inverse(Xr)), ew, ev);
   const bool so3 = so3_family(C.kind);  // the SO3 terminal cost is weighted with Q (App. C-Q3)
-  const double* W1 = (term && !so3) ? C.P1 : C.W1;
-  const double* W2 = (term && !so3) ? C.P2 : C.W2;
+  const auto W1 = wblock<PTW, 6>(C.wts, P, b, term && !so3, C.P1, C.W1, WT_P1, WT_W1);
+  const auto W2 = wblock<PTW, 6>(C.wts, P, b, term && !so3, C.P2, C.W2, WT_P2, WT_W2);
+  const auto Rw = wblock<PTW, M>(C.wts, P, b, false, C.R, C.R, WT_R, WT_R);
   double e[6] = {ew.x, ew.y, ew.z, ev.x, ev.y, ev.z};
   double ve[6] = {S.w.x - r[7], S.w.y - r[8], S.w.z - r[9], S.v.x - r[10], S.v.y - r[11], S.v.z - r[12]};
   double l = 0;
@@ -2645,7 +2694,7 @@ TOLG_DEV double knot_cost(const Params& P, const Consts& C, int i, int b, const 
 #pragma unroll
     for (int a = 0; a < M; a++)
 #pragma unroll
-      for (int k = 0; k < M; k++) l += u[a] * C.R[a * M + k] * u[k];
+      for (int k = 0; k < M; k++) l += u[a] * Rw[a * M + k] * u[k];
     if (P.al_lb) {
       const int bs = b < P.B ? b : P.B - 1;
       const double* lam = P.al_lambda + ((size_t)bs * P.N + i) * 2 * M;
@@ -2663,7 +2712,7 @@ TOLG_DEV double knot_cost(const Params& P, const Consts& C, int i, int b, const 
 // one thread per (trajectory, slot): rollout with alpha_{a0+slot}, its cost and (MS) defect norm on the chain -- the
 // form of a wide stage with MANY undecided trajectories (64 waves per alpha keep a 12-alpha stage within one wave per
 // SIMD whatever their number; ls_quad_form decides on the device, the quad form -- k_rollout_ls -- takes the short lists)
-template <int M, bool MS, bool LINEAR, bool PTREF>
+template <int M, bool MS, bool LINEAR, int PT>
 __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nslots, int list) {
   const Consts& C = *P.c;
   // (round 4: the series forms of tolg_lie.h in this kernel and in k_ls_eval were measured -- SS 414 -> 404, merit 500 -> 482: a
@@ -2702,7 +2751,7 @@ __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nsl
       du[a] = sacc;
       un[a] = u[a] + sacc;
     }
-    J += knot_cost<M, false, PTREF>(P, C, i, b, Sn, un, false);
+    J += knot_cost<M, false, PT>(P, C, i, b, Sn, un, false);
     State Nx;
     if constexpr (!LINEAR) {
       State Fn = dyn_f<M>(C, Sn, un);
@@ -2754,7 +2803,7 @@ __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nsl
   double uz[M];
 #pragma unroll
   for (int a = 0; a < M; a++) uz[a] = 0;
-  J += knot_cost<M, false, PTREF>(P, C, N, b, Sn, uz, true);
+  J += knot_cost<M, false, PT>(P, C, N, b, Sn, uz, true);
   P.Jtrial[(size_t)b * 20 + ai] = J;
   P.dtrial[(size_t)b * 20 + ai] = sqrt(d2);
 }
@@ -3093,7 +3142,7 @@ __global__ __launch_bounds__(64 * (NT + 1)) void k_rollout_ls2(Params P, int a0,
 // stage cost l(x^_i, u^_i) (traopt_cost.py:675-738) and, MS, the squared defect
 // |Log(x^_{i+1}^-1 f_q(x^_i, u^_i))|^2 + |f_xi - xi^_{i+1}|^2 (:2790-2812) of every stored candidate of the stage
 // (four waves per SIMD -- 127 registers and 28 bytes of scratch instead of 136 -- was measured: no change)
-template <int M, bool MS, bool PTREF>
+template <int M, bool MS, int PT>
 __global__ __launch_bounds__(256) void k_ls_eval(Params P, int nslots, int direct, int list) {
   const Consts& C = *P.c;
   const int slot = blockIdx.y, N = P.N;
@@ -3119,7 +3168,7 @@ __global__ __launch_bounds__(256) void k_ls_eval(Params P, int nslots, int direc
   double u[M];
 #pragma unroll
   for (int a = 0; a < M; a++) u[a] = (i < N) ? su[UIDX(a, i, e)] : 0.0;
-  P.LSC[((size_t)slot * (N + 1) + i) * P.Bp + e] = knot_cost<M, false, PTREF>(P, C, i, b, S, u, i == N);
+  P.LSC[((size_t)slot * (N + 1) + i) * P.Bp + e] = knot_cost<M, false, PT>(P, C, i, b, S, u, i == N);
   if constexpr (MS) {
     if (i < N) {
       const State Nx = load_state(P, sx, i + 1, e), Fn = dyn_f<M>(C, S, u);
@@ -3195,7 +3244,7 @@ TOLG_DEV void affine_candidate(const Params& P, int i, int b, double alpha, Stat
     for (int a = 0; a < M; a++) u[a] = 0.0;
   }
 }
-template <int M, bool MS, bool PTREF>
+template <int M, bool MS, int PT>
 __global__ __launch_bounds__(256) void k_ls_eval_affine(Params P, int a0, int nslots, int list) {
   const Consts& C = *P.c;
   const int slot = blockIdx.y, N = P.N;
@@ -3212,7 +3261,7 @@ __global__ __launch_bounds__(256) void k_ls_eval_affine(Params P, int a0, int ns
   State S;
   double u[M];
   affine_candidate<M>(P, i, b, alpha, S, u);
-  P.LSC[((size_t)slot * (N + 1) + i) * P.Bp + e] = knot_cost<M, false, PTREF>(P, C, i, b, S, u, i == N);
+  P.LSC[((size_t)slot * (N + 1) + i) * P.Bp + e] = knot_cost<M, false, PT>(P, C, i, b, S, u, i == N);
   if constexpr (MS) {
     if (i < N) {
       State Nx;
@@ -3252,7 +3301,8 @@ __global__ __launch_bounds__(256) void k_affine_commit(Params P, int a0, int all
 // _expected_cost_change (:2756-2769), _update_defect_weight (:2774-2788).  Four lanes per trajectory, the step is
 // roll_step's linear form (round 2: one thread per trajectory, 3.9 ms per call -- half of a merit-search iteration).
 // REDO: only the trajectories k_expected_change_ring (tolg_expected_change.h) handed back.
-template <int M, int PK, bool REDO = false>
+// PTW: the weights of trajectory b (tolg_set_weights): the tables hold one diagonal per quad, read through DiagAt
+template <int M, int PK, bool REDO = false, bool PTW = false>
 __global__ __launch_bounds__(64) void k_expected_change(Params P) {
   const Consts& C = *P.c;  // generic pointer (note at DConsts)
   const int t = blockIdx.x * 64 + threadIdx.x;
@@ -3263,8 +3313,13 @@ __global__ __launch_bounds__(64) void k_expected_change(Params P) {
   // the constant weight blocks of the quadratic model, in LDS: read from the constants in memory they were ~100 loads per
   // knot on a chain that is nothing but load latencies.  Filled by the first 36 lanes of the wave BEFORE any quad
   // leaves: a quad that is inactive (or, with REDO, not handed back) must still write its share of the table.
-  __shared__ double sW2[36], sP2[36], sR2[36];
-  if (threadIdx.x < 36) {
+  // (PTW: per quad, 2 W2 | 2 P2 | 2 R diagonals of its trajectory, 18 doubles, filled by the quad's own four lanes)
+  __shared__ double sW2[PTW ? 16 * 18 : 36], sP2[PTW ? 1 : 36], sR2[PTW ? 1 : 36];
+  if constexpr (PTW) {
+    double* d = sW2 + 18 * (threadIdx.x >> 2);
+    for (int k = q; k < 12 + M; k += 4)
+      d[k] = 2.0 * C.wts[(size_t)(k < 6 ? WT_W2 + k : k < 12 ? WT_P2 + k - 6 : WT_R + k - 12) * P.Bp + b];
+  } else if (threadIdx.x < 36) {
     sW2[threadIdx.x] = 2.0 * C.W2[threadIdx.x]; sP2[threadIdx.x] = 2.0 * C.P2[threadIdx.x];
     sR2[threadIdx.x] = (threadIdx.x < M * M) ? 2.0 * C.R[threadIdx.x] : 0.0;
   }
@@ -3272,6 +3327,7 @@ __global__ __launch_bounds__(64) void k_expected_change(Params P) {
   __builtin_amdgcn_wave_barrier();
   if (!P.active[b]) return;  // quad-uniform
   if (REDO && !P.ec_redo[b]) return;
+  const auto R2 = wtab<PTW, M>(sW2 + 18 * (threadIdx.x >> 2) + 12, sR2);
   const bool writer = live && q == 0;
   const int N = P.N;
   const unsigned sB = (unsigned)P.Bp * 8u, vb = (unsigned)b * 8u;
@@ -3288,7 +3344,7 @@ __global__ __launch_bounds__(64) void k_expected_change(Params P) {
   // l_x e and e^T l_xx e with l_xx = blkdiag(l_xx11, 2 W2)
   auto state_terms = [&](int i, const double (&e)[12]) {
     __amdgpu_buffer_rsrc_t rR = mkbuf(P.REC + recStride * i, (unsigned)P.recF * sB);
-    const double* W2 = (i == N) ? sP2 : sW2;
+    const auto W2 = wtab<PTW, 6>(sW2 + 18 * (threadIdx.x >> 2) + (i == N ? 6 : 0), (i == N) ? sP2 : sW2);
 #pragma unroll
     for (int a = 0; a < 12; a++) c1 += bld(rR, REC_VR(b), FOFF(REC_LX + a)) * e[a];
 #pragma unroll
@@ -3313,7 +3369,7 @@ __global__ __launch_bounds__(64) void k_expected_change(Params P) {
     for (int a = 0; a < M; a++) {
       c1 += bld(rR, REC_VR(b), FOFF(REC_LU + a)) * pr.du[a];
 #pragma unroll
-      for (int k = 0; k < M; k++) c2 += pr.du[a] * sR2[a * M + k] * pr.du[k];
+      for (int k = 0; k < M; k++) c2 += pr.du[a] * R2[a * M + k] * pr.du[k];
       if (P.al_lb) c2 += pr.du[a] * bld(rR, REC_VR(b), FOFF(P.fLUU + a)) * pr.du[a];
     }
     Sn = Nx;
@@ -3636,9 +3692,11 @@ using namespace tolg;
 // The kernels that serve one handle: which template instantiation runs for which model is decided once, here, when the
 // handle is created (kernel_table below).  Launch sites pick an entry by what changes from call to call -- the pass of
 // the sweep, AL terms on or off, the rollout form, the search kind, the stage -- and never test the model themselves.
-// A handle holds two tables: the kernels that read the reference (K1, the fused launch, the line-search evaluations,
-// k_init) come in a second instantiation, PTREF, that reads trajectory b's own reference (tolg_set_refs); every other
-// entry is the same kernel in both.
+// A handle holds four tables, kt_pt[PT] with PT a set of PT_REF and PT_W.  PT_REF: the kernels that read the reference (K1,
+// the fused launch, the line-search evaluations, k_init) read trajectory b's own reference (tolg_set_refs).  PT_W: the
+// kernels that read the cost weights (K1, the fused launch, the line-search evaluations, both backward sweeps, both forms of
+// the expected change) read trajectory b's own diagonal weights (tolg_set_weights).  Every other entry is the same kernel in
+// all four.
 typedef void (*SearchKernel)(Params, int, int, int);
 typedef void (*SearchRollout)(Params, int, int, int, int);
 struct KernelTable {
@@ -3661,7 +3719,7 @@ struct KernelTable {
   } ls[2];
 };
 
-template <int M, bool MS, int PK, bool PTREF>
+template <int M, bool MS, int PK, int PT>
 static KernelTable::Search search_kernels() {
   KernelTable::Search s;
   // the nonlinear rollouts, two wavefronts per sixteen quads: [1] the first try, [0] the stages behind it.  The first try is
@@ -3674,57 +3732,58 @@ static KernelTable::Search search_kernels() {
   else s.wave2[0] = {k_rollout_ls2<M, false, 3>, 3};
   s.wave1[0] = k_rollout_ls<M, MS, false, PK>;
   s.wave1[1] = k_rollout_ls<M, MS, true, PK>;
-  s.eval_t[0] = k_rollout_eval_t<M, MS, false, PTREF>;
-  s.eval_t[1] = k_rollout_eval_t<M, MS, true, PTREF>;
-  s.eval = k_ls_eval<M, MS, PTREF>;
-  s.eval_affine = k_ls_eval_affine<M, MS, PTREF>;
+  s.eval_t[0] = k_rollout_eval_t<M, MS, false, PT>;
+  s.eval_t[1] = k_rollout_eval_t<M, MS, true, PT>;
+  s.eval = k_ls_eval<M, MS, PT>;
+  s.eval_affine = k_ls_eval_affine<M, MS, PT>;
   return s;
 }
-// GRAV: gravity; DENSE: inertia blocks that are not diagonal; PEND: Pendulum3dDyanmics (m = 6, gravity); PTREF: a
-// reference per trajectory
-template <int M, bool GRAV, bool DENSE, bool PEND, bool PTREF>
+// GRAV: gravity; DENSE: inertia blocks that are not diagonal; PEND: Pendulum3dDyanmics (m = 6, gravity); PT: PT_REF a
+// reference per trajectory, PT_W cost weights per trajectory
+template <int M, bool GRAV, bool DENSE, bool PEND, int PT>
 static KernelTable kernel_table(int lds_per_block) {
   constexpr int PK = PEND ? 1 : 0;
+  constexpr bool PTREF = (PT & PT_REF) != 0, PTW = (PT & PT_W) != 0;
   KernelTable t;
   t.init = k_init<PTREF>;
-  t.linearize = k_linearize<M, PTREF>;
+  t.linearize = k_linearize<M, PT>;
   t.init_rollout = k_init_rollout<M>;
   if constexpr (!DENSE && !PEND) {
     // diagonal inertia blocks and a constant input matrix (every reference script except the pendulum): the third form of
     // the sweep (tolg_backward3.h)
-    t.sweep[0][0] = k_backward3<M, GRAV, false, false>; t.sweep[0][1] = k_backward3<M, GRAV, true, false>;
-    t.sweep[1][0] = k_backward3<M, GRAV, false, true>;  t.sweep[1][1] = k_backward3<M, GRAV, true, true>;
+    t.sweep[0][0] = k_backward3<M, GRAV, false, false, PTW>; t.sweep[0][1] = k_backward3<M, GRAV, true, false, PTW>;
+    t.sweep[1][0] = k_backward3<M, GRAV, false, true, PTW>;  t.sweep[1][1] = k_backward3<M, GRAV, true, true, PTW>;
   } else {  // dense inertia blocks, the pendulum: the general sweep (the AL terms are a run-time test in it)
-    t.sweep[0][0] = t.sweep[0][1] = k_backward<M, PEND, GRAV, PEND && !DENSE, false>;
-    t.sweep[1][0] = t.sweep[1][1] = k_backward<M, PEND, GRAV, PEND && !DENSE, true>;
+    t.sweep[0][0] = t.sweep[0][1] = k_backward<M, PEND, GRAV, PEND && !DENSE, false, PTW>;
+    t.sweep[1][0] = t.sweep[1][1] = k_backward<M, PEND, GRAV, PEND && !DENSE, true, PTW>;
   }
   t.rollout_linear = k_rollout<M, true, false>;  // (PK = 0 for the pendulum too)
   t.rollout_alpha1 = k_rollout<M, false, true, PK>;
   t.rollout_factor = k_rollout<M, false, false, PK>;
   t.rollout_lin = nullptr;
   if constexpr (!PEND)
-    if (rl_static_lds<M>() + sizeof(double) * RL_NH * 4 * 16 <= (size_t)lds_per_block) t.rollout_lin = k_rollout_lin<M, PTREF>;
+    if (rl_static_lds<M>() + sizeof(double) * RL_NH * 4 * 16 <= (size_t)lds_per_block) t.rollout_lin = k_rollout_lin<M, PT>;
   // the ring form reads the velocity block of F_x from the record run for dense inertia blocks and the pendulum, and for the
   // pendulum also the knot's input-matrix block (VARB)
-  t.ec_ring[0] = k_expected_change_ring<M, GRAV, false, DENSE || PEND, PEND>;
-  t.ec_ring[1] = k_expected_change_ring<M, GRAV, true, DENSE || PEND, PEND>;
-  t.ec_stmt[0] = k_expected_change<M, PK>;
-  t.ec_stmt[1] = k_expected_change<M, PK, true>;
+  t.ec_ring[0] = k_expected_change_ring<M, GRAV, false, DENSE || PEND, PEND, PTW>;
+  t.ec_ring[1] = k_expected_change_ring<M, GRAV, true, DENSE || PEND, PEND, PTW>;
+  t.ec_stmt[0] = k_expected_change<M, PK, false, PTW>;
+  t.ec_stmt[1] = k_expected_change<M, PK, true, PTW>;
   t.affine_commit = k_affine_commit<M>;
-  t.ls[0] = search_kernels<M, false, PK, PTREF>();
-  t.ls[1] = search_kernels<M, true, PK, PTREF>();
+  t.ls[0] = search_kernels<M, false, PK, PT>();
+  t.ls[1] = search_kernels<M, true, PK, PT>();
   return t;
 }
-template <bool PTREF>
+template <int PT>
 static KernelTable kernel_table_for(const tolg_problem& p, const Consts& c, int lds_per_block) {
   const bool dense = c.diagJ == 0;
   if (p.m == 4)  // the drone: gravity, always
-    return dense ? kernel_table<4, true, true, false, PTREF>(lds_per_block) : kernel_table<4, true, false, false, PTREF>(lds_per_block);
+    return dense ? kernel_table<4, true, true, false, PT>(lds_per_block) : kernel_table<4, true, false, false, PT>(lds_per_block);
   if (p.kind == TOLG_DYN_PENDULUM3D)
-    return dense ? kernel_table<6, true, true, true, PTREF>(lds_per_block) : kernel_table<6, true, false, true, PTREF>(lds_per_block);
+    return dense ? kernel_table<6, true, true, true, PT>(lds_per_block) : kernel_table<6, true, false, true, PT>(lds_per_block);
   if (c.grav != 0.0)
-    return dense ? kernel_table<6, true, true, false, PTREF>(lds_per_block) : kernel_table<6, true, false, false, PTREF>(lds_per_block);
-  return dense ? kernel_table<6, false, true, false, PTREF>(lds_per_block) : kernel_table<6, false, false, false, PTREF>(lds_per_block);
+    return dense ? kernel_table<6, true, true, false, PT>(lds_per_block) : kernel_table<6, true, false, false, PT>(lds_per_block);
+  return dense ? kernel_table<6, false, true, false, PT>(lds_per_block) : kernel_table<6, false, false, false, PT>(lds_per_block);
 }
 
 struct tolg_handle_s {
@@ -3740,11 +3799,13 @@ struct tolg_handle_s {
   bool running;
   int lds_per_block;  // hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KB on MI355X)
   int rec_closed = 0; // the knot records were last written by the fused rollout (no defect field, see k_backward)
-  KernelTable kt;     // the model's kernels for the solves to come: kt_ref[refs != null]
-  KernelTable kt_ref[2];  // kernel_table_for<PTREF>: [0] the batch-shared reference, [1] a reference per trajectory
+  KernelTable kt;     // the model's kernels for the solves to come: kt_pt[(refs ? PT_REF : 0) | (wts ? PT_W : 0)]
+  KernelTable kt_pt[4];  // kernel_table_for<PT>: [0] batch-shared reference and weights, [PT_REF | PT_W] per trajectory
   const double* ref_shared;  // the reference packed by tolg_create (P.ref as carved)
   const double* refs = nullptr;  // tolg_set_refs: the packed per-trajectory references (caller-owned), or null
   int refs_B = 0;                // ... and the batch they were set for: every batch call must match it
+  const double* wts = nullptr;   // tolg_set_weights: the packed per-trajectory weights (caller-owned), or null
+  int wts_B = 0;                 // ... and their batch, as refs_B
   // A/B switches of the tests, read from the environment when the handle is created: every sweep the full kernel
   // (TOLG_K2_FULL_ONLY=1), the one-wave forms of the line-search rollouts (TOLG_LS_ONEWAVE=1)
   bool k2_full_only, ls_one_wave;
@@ -3976,9 +4037,11 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
         c.Llin[a][6 * i + j] = sacc * prob->dt;
       }
   }
-  h->kt_ref[0] = kernel_table_for<false>(*prob, c, h->lds_per_block);
-  h->kt_ref[1] = kernel_table_for<true>(*prob, c, h->lds_per_block);
-  h->kt = h->kt_ref[0];
+  h->kt_pt[0] = kernel_table_for<0>(*prob, c, h->lds_per_block);
+  h->kt_pt[PT_REF] = kernel_table_for<PT_REF>(*prob, c, h->lds_per_block);
+  h->kt_pt[PT_W] = kernel_table_for<PT_W>(*prob, c, h->lds_per_block);
+  h->kt_pt[PT_REF | PT_W] = kernel_table_for<PT_REF | PT_W>(*prob, c, h->lds_per_block);
+  h->kt = h->kt_pt[0];
   {
     const char* e = getenv("TOLG_K2_FULL_ONLY");
     h->k2_full_only = e && e[0] == '1';
@@ -4356,7 +4419,7 @@ extern "C" int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_
                                 double* d_grad_hist, double* d_defect_hist, double* d_alpha_hist, double* d_mu_hist,
                                 void* stream) {
   if (!h || !opt || B < 1 || B > h->max_batch || !d_x0_q || !d_x0_xi || !d_us_init) return TOLG_E_ARG;
-  if (h->refs && B != h->refs_B) return TOLG_E_ARG;
+  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;
   if (opt->max_iter < 0) return TOLG_E_ARG;
   if (opt->mode != TOLG_MODE_MS && opt->mode != TOLG_MODE_SS) return TOLG_E_ARG;
   const int ms = opt->mode == TOLG_MODE_MS;
@@ -4515,17 +4578,56 @@ extern "C" int tolg_set_refs(tolg_handle_t h, int32_t B, const double* d_q_ref, 
                              size_t refs_bytes, void* stream) {
   if (!h || h->running) return TOLG_E_ARG;
   if (!d_q_ref) {  // back to the reference of tolg_create
-    h->refs = nullptr; h->refs_B = 0; h->kt = h->kt_ref[0];
+    h->refs = nullptr; h->refs_B = 0; h->kt = h->kt_pt[h->wts ? PT_W : 0];
     return 0;
   }
   if (B < 1 || B > h->max_batch || !d_xi_ref || !d_refs || (reinterpret_cast<uintptr_t>(d_refs) & 7) != 0) return TOLG_E_ARG;
   if (refs_bytes < refs_bytes_for(&h->prob, B)) return TOLG_E_ARG;
+  if (h->wts && B != h->wts_B) return TOLG_E_ARG;  // references and weights per trajectory: one batch
   const int N = h->prob.N, Bp = (B + 3) / 4 * 4;
   const size_t n = (size_t)(N + 1) * Bp;
   hipLaunchKernelGGL(k_pack_refs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp, N,
                      d_q_ref, d_xi_ref, static_cast<double*>(d_refs));
   LAUNCH_CHECK();
-  h->refs = static_cast<const double*>(d_refs); h->refs_B = B; h->kt = h->kt_ref[1];
+  h->refs = static_cast<const double*>(d_refs); h->refs_B = B; h->kt = h->kt_pt[PT_REF | (h->wts ? PT_W : 0)];
+  return 0;
+}
+
+// d_q_diag [B][12], d_p_diag [B][12], d_r_diag [B][m] into [wt_fields(m)][Bp] (WT_*); padded trajectories b >= B replicate
+// b = B-1.  Thread 0 points the handle's constants at w (stream-ordered before the solves that read it).
+__global__ void k_pack_weights(int B, int Bp, int m, const double* __restrict__ q_diag, const double* __restrict__ p_diag,
+                               const double* __restrict__ r_diag, double* __restrict__ w, Consts* c) {
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t == 0) c->wts = w;
+  if (t >= (size_t)wt_fields(m) * Bp) return;
+  const int b = (int)(t % Bp), f = (int)(t / Bp);
+  const int bs = b < B ? b : B - 1;
+  w[t] = f < 12 ? q_diag[(size_t)bs * 12 + f] : f < 24 ? p_diag[(size_t)bs * 12 + f - 12] : r_diag[(size_t)bs * m + f - 24];
+}
+static size_t weights_bytes_for(const tolg_problem* p, int B) {
+  return (size_t)wt_fields(p->m) * (size_t)((B + 3) / 4 * 4) * sizeof(double);
+}
+extern "C" size_t tolg_weights_bytes(const tolg_problem* prob, int32_t max_batch) {
+  if (check_problem(prob) || max_batch < 1) return 0;
+  return weights_bytes_for(prob, max_batch);
+}
+
+extern "C" int tolg_set_weights(tolg_handle_t h, int32_t B, const double* d_q_diag, const double* d_p_diag,
+                                const double* d_r_diag, void* d_w, size_t w_bytes, void* stream) {
+  if (!h || h->running) return TOLG_E_ARG;
+  if (!d_q_diag) {  // back to the weights of tolg_create
+    h->wts = nullptr; h->wts_B = 0; h->kt = h->kt_pt[h->refs ? PT_REF : 0];
+    return 0;
+  }
+  if (B < 1 || B > h->max_batch || !d_p_diag || !d_r_diag || !d_w || (reinterpret_cast<uintptr_t>(d_w) & 7) != 0) return TOLG_E_ARG;
+  if (w_bytes < weights_bytes_for(&h->prob, B)) return TOLG_E_ARG;
+  if (h->refs && B != h->refs_B) return TOLG_E_ARG;  // references and weights per trajectory: one batch
+  const int Bp = (B + 3) / 4 * 4;
+  const size_t n = (size_t)wt_fields(h->prob.m) * Bp;
+  hipLaunchKernelGGL(k_pack_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp,
+                     h->prob.m, d_q_diag, d_p_diag, d_r_diag, static_cast<double*>(d_w), const_cast<Consts*>(h->P.c));
+  LAUNCH_CHECK();
+  h->wts = static_cast<const double*>(d_w); h->wts_B = B; h->kt = h->kt_pt[PT_W | (h->refs ? PT_REF : 0)];
   return 0;
 }
 
@@ -4547,7 +4649,7 @@ extern "C" int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_r
                                        double* d_J, double* d_dnorm, double* d_grad, void* stream) {
   // uses the handle's workspace (k_pack_traj resets the trajectories, mu / delta, the masks): not during a solve
   if (!h || h->running || B < 1 || B > h->max_batch || !d_xs_q || !d_xs_xi || !d_us) return TOLG_E_ARG;
-  if (h->refs && B != h->refs_B) return TOLG_E_ARG;
+  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   P.max_reg = max_reg;
@@ -4578,10 +4680,10 @@ extern "C" int tolg_eval_knot(tolg_handle_t h, int32_t i, int32_t n, const doubl
   if (i < h->prob.N && !d_u) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, n);
-  P.ref = h->ref_shared;  // the reference of tolg_create, whatever tolg_set_refs holds
+  P.ref = h->ref_shared;  // the reference of tolg_create, whatever tolg_set_refs holds (K1 below: the shared weights too)
   hipLaunchKernelGGL(k_probe_pack, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, i, d_x_q, d_x_xi, d_u);
   LAUNCH_CHECK();
-  int rc = run_linearize(h, P, st, P.cur, P.cur_u, nullptr, nullptr, 2, i, 1, -1, 0, h->kt_ref[0].linearize);
+  int rc = run_linearize(h, P, st, P.cur, P.cur_u, nullptr, nullptr, 2, i, 1, -1, 0, h->kt_pt[0].linearize);
   if (rc) return rc;
   hipLaunchKernelGGL(k_probe_export, dim3((n + 63) / 64), dim3(64), 0, st, P, i, d_f_q, d_f_xi, d_Fx, d_Fu, d_l, d_lx,
                      d_lxx, d_lu, d_luu, d_err);
@@ -4604,7 +4706,7 @@ __global__ void k_clear_ecc(Params P) {
 extern "C" int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, double* d_ecc, int32_t* d_flag, void* stream) {
   // works on what tolg_linearize_backward left in the workspace (trajectory, records, gains): not during a solve
   if (!h || h->running || B < 1 || B > h->max_batch || form < 0 || form > 2) return TOLG_E_ARG;
-  if (h->refs && B != h->refs_B) return TOLG_E_ARG;
+  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   hipLaunchKernelGGL(k_clear_ecc, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
@@ -4627,7 +4729,7 @@ extern "C" int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, do
 extern "C" int tolg_rollout(tolg_handle_t h, int32_t ms, int32_t rollout_linear, double alpha, int32_t B,
                             double* d_xs_q_new, double* d_xs_xi_new, double* d_us_new, void* stream) {
   if (!h || h->running || B < 1 || B > h->max_batch) return TOLG_E_ARG;  // overwrites the candidate arrays
-  if (h->refs && B != h->refs_B) return TOLG_E_ARG;
+  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   int rc = run_rollout_ms(h, P, st, alpha, rollout_linear, ms);

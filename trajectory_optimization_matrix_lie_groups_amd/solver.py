@@ -182,6 +182,60 @@ class BatchedTrackingILQR:
         _capi.check(rc, "tolg_set_refs")
         self._refs_set = True
 
+    def _check_weights(self, B, Q, P, R):
+        """Per-trajectory cost weights Q [B, 12, 12], P [B, 12, 12], R [B, m, m] (numpy or torch, the fields of TrackingProblem
+        per trajectory), checked on the host: ValueError before anything reaches the device for a wrong shape, an off-diagonal
+        entry that is not zero, a negative or non-finite weight.  Returns the diagonals (q [B, 12], p [B, 12], r [B, m], float64
+        numpy), or None when all three are omitted (the problem's shared weights)."""
+        if Q is None and P is None and R is None:
+            return None
+        if Q is None or P is None or R is None:
+            raise ValueError("per-trajectory weights need all three of Q, P and R")
+        out = []
+        for name, a, n in (("Q", Q, 12), ("P", P, 12), ("R", R, self.m)):
+            a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (B, n, n):
+                raise ValueError("%s has shape %s, expected (%d, %d, %d)" % (name, a.shape, B, n, n))
+            d = np.diagonal(a, axis1=1, axis2=2)
+            if not np.all(np.isfinite(a)):
+                raise ValueError("%s: per-trajectory weights must be finite" % name)
+            if np.any(a - d[:, :, None] * np.eye(n) != 0.0):
+                raise ValueError("%s: per-trajectory weights must be diagonal (a non-zero off-diagonal entry)" % name)
+            if np.any(d < 0.0):
+                raise ValueError("%s: per-trajectory weights must not be negative" % name)
+            out.append(np.ascontiguousarray(d))
+        return tuple(out)
+
+    def clear_per_trajectory(self):
+        """Return the handle to the problem's shared reference and weights (tolg_set_refs / tolg_set_weights with NULL).  The
+        solve calls do this themselves when they are given no per-trajectory inputs; this is for callers that drove the C
+        ABI on the handle directly."""
+        _capi.check(self.lib.tolg_set_weights(self._h, 0, None, None, None, None, 0, None), "tolg_set_weights")
+        _capi.check(self.lib.tolg_set_refs(self._h, 0, None, None, None, 0, None), "tolg_set_refs")
+        self._wts_set = self._refs_set = False
+
+    def _use_pt(self, B, refs, weights):
+        """Point the handle at this call's references (tolg_set_refs) and weights (tolg_set_weights), or back at the
+        problem's shared ones for what is None: every call states its own, nothing carries over from an earlier call.  The
+        weights are detached first, so that references for a new B never meet weights set for an earlier one."""
+        if getattr(self, "_wts_set", False):
+            _capi.check(self.lib.tolg_set_weights(self._h, 0, None, None, None, None, 0, None), "tolg_set_weights")
+            self._wts_set = False
+        self._use_refs(B, refs)
+        if weights is None:
+            return
+        q, p, r = (self._dev(a, a.shape) for a in weights)
+        if getattr(self, "_wts_buf", None) is None:
+            nbytes = int(self.lib.tolg_weights_bytes(C.byref(self._p), self.max_batch))
+            self._wts_buf = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tolg_set_weights(self._h, B, _ptr(q), _ptr(p), _ptr(r), _ptr(self._wts_buf),
+                                           C.c_size_t(self._wts_buf.numel() * 8), self._stream())
+        _capi.check(rc, "tolg_set_weights")
+        self._wts_set = True
+        self._wts_keep = (q, p, r)  # the packing kernel reads them on the stream
+
     # ------------------------------------------------------------------------------------------
     def _alloc_result(self, B, K, histories=True):
         f64 = dict(dtype=torch.float64, device=self.device)
@@ -196,15 +250,19 @@ class BatchedTrackingILQR:
 
     def solve_begin(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
                     tol_d_norm=1e-6, line_search=False, rollout="nonlinear", max_reg=1e10, histories=True,
-                    out: Optional[FitResult] = None, schedule="auto", q_ref=None, xi_ref=None) -> FitResult:
+                    out: Optional[FitResult] = None, schedule="auto", q_ref=None, xi_ref=None, Q=None, P=None,
+                    R=None) -> FitResult:
         """_initial_guess + first _linearization; leaves the batch resident in HBM.
         schedule: "auto" (rollout and re-linearisation fused in one launch where the mode allows it) or
         "split" (separate launches); launch structure only, same algorithm.
         q_ref [B, N+1, 4, 4], xi_ref [B, N+1, 6] (optional): trajectory b tracks its own reference in this solve
-        (tolg_set_refs); omitted, the problem's shared reference."""
+        (tolg_set_refs); omitted, the problem's shared reference.
+        Q [B, 12, 12], P [B, 12, 12], R [B, m, m] (optional, all three or none, diagonal): trajectory b's cost weights in this
+        solve (tolg_set_weights); omitted, the problem's shared weights."""
         x0_q = self._dev(x0_q, (-1, 16))
         B = x0_q.shape[0]
         refs = self._check_refs(B, q_ref, xi_ref)
+        wts = self._check_weights(B, Q, P, R)
         x0_xi = self._dev(x0_xi, (B, 6))
         if us_init is None:
             us_init = torch.zeros(B, self.N, self.m, dtype=torch.float64, device=self.device)
@@ -216,7 +274,7 @@ class BatchedTrackingILQR:
                           int(rollout == "linear"), float(tol_grad_norm), float(tol_d_norm),
                           float(max_reg if max_reg else 0.0),
                           {"auto": _capi.SCHED_AUTO, "split": _capi.SCHED_SPLIT}[schedule], 0)
-        self._use_refs(B, refs)
+        self._use_pt(B, refs, wts)
         with torch.cuda.device(self.device):
             rc = self.lib.tolg_solve_begin(self._h, C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(us_init),
                                            _ptr(out.J_hist), _ptr(out.grad_hist), _ptr(out.defect_hist),
@@ -269,28 +327,30 @@ class BatchedTrackingILQR:
     def fit_batch(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
                   tol_d_norm=1e-6, line_search=False, rollout="nonlinear", max_reg=1e10,
                   histories=True, out: Optional[FitResult] = None, schedule="auto", check_every=16, q_ref=None,
-                  xi_ref=None) -> FitResult:
+                  xi_ref=None, Q=None, P=None, R=None) -> FitResult:
         """B independent fits (the reference's joblib fan-out, visualization/perturb_all_compute.py:240).
         Inputs may be numpy arrays or tensors already on the device; outputs are device tensors.
         The iterations are issued in slices of `check_every`; behind each slice the number of trajectories still
         iterating is read back (overlapped with the next slice) and the loop stops when it reaches zero (the early
         exit of traopt_controller.py:2528-2532 for the whole batch).  check_every=0, or tolerances of zero, issue
         all n_iterations without a host read.  `iterations_issued` keeps how many were queued.
-        q_ref [B, N+1, 4, 4], xi_ref [B, N+1, 6] (optional, numpy or torch): a reference per trajectory for this fit."""
+        q_ref [B, N+1, 4, 4], xi_ref [B, N+1, 6] (optional, numpy or torch): a reference per trajectory for this fit.
+        Q [B, 12, 12], P [B, 12, 12], R [B, m, m] (optional, all three or none, diagonal): cost weights per trajectory."""
         self.solve_begin(x0_q, x0_xi, us_init, mode, n_iterations, tol_grad_norm, tol_d_norm, line_search, rollout,
-                         max_reg, histories, out, schedule, q_ref, xi_ref)
+                         max_reg, histories, out, schedule, q_ref, xi_ref, Q, P, R)
         self.iterations_issued = self.solve_iterate_until(int(n_iterations), int(check_every or 0))
         return self.solve_end()
 
     def solve_batch_one_call(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
                              tol_d_norm=1e-6, line_search=False, rollout="nonlinear", max_reg=1e10, schedule="auto",
-                             check_every=0, q_ref=None, xi_ref=None) -> FitResult:
+                             check_every=0, q_ref=None, xi_ref=None, Q=None, P=None, R=None) -> FitResult:
         """The same fit through the single entry point tolg_solve_batch (what a C / C++ caller binds): begin,
         iterations (tolg_options.check_every: 0 = all of them, never synchronising), end in one call.
-        q_ref / xi_ref: as for fit_batch."""
+        q_ref / xi_ref, Q / P / R: as for fit_batch."""
         x0_q = self._dev(x0_q, (-1, 16))
         B = x0_q.shape[0]
         refs = self._check_refs(B, q_ref, xi_ref)
+        wts = self._check_weights(B, Q, P, R)
         x0_xi = self._dev(x0_xi, (B, 6))
         if us_init is None:
             us_init = torch.zeros((B, self.N, self.m), dtype=torch.float64, device=self.device)
@@ -301,7 +361,7 @@ class BatchedTrackingILQR:
                           int(rollout == "linear"), float(tol_grad_norm), float(tol_d_norm),
                           float(max_reg if max_reg else 0.0),
                           {"auto": _capi.SCHED_AUTO, "split": _capi.SCHED_SPLIT}[schedule], int(check_every))
-        self._use_refs(B, refs)
+        self._use_pt(B, refs, wts)
         with torch.cuda.device(self.device):
             rc = self.lib.tolg_solve_batch(self._h, C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(us_init), _ptr(out.xs_q),
                                            _ptr(out.xs_xi), _ptr(out.us), _ptr(out.J_hist), _ptr(out.grad_hist),
@@ -326,14 +386,15 @@ class BatchedTrackingILQR:
 
     def al_fit_batch(self, x0_q, x0_xi, us_init, lb, ub, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
                      tol_d_norm=1e-6, tol_constr=1e-2, mu0=1e-2, mu_scale=10.0, mu_max=1e8, line_search=False,
-                     on_outer=None, q_ref=None, xi_ref=None):
+                     on_outer=None, q_ref=None, xi_ref=None, Q=None, P=None, R=None):
         """AL_iLQR_Tracking_SE3_MS.fit (reference traoptlibrary/traopt_controller.py:3218-3267) for B
         independent problems: every outer iteration re-solves from (x0, us_init) -- no warm start, as in
         the reference -- then updates multipliers on the device.  Returns (FitResult, info dict).
-        q_ref / xi_ref: a reference per trajectory, as for fit_batch."""
+        q_ref / xi_ref: a reference per trajectory, Q / P / R: weights per trajectory, as for fit_batch."""
         x0_q = self._dev(x0_q, (-1, 16))
         B = x0_q.shape[0]
         self._check_refs(B, q_ref, xi_ref)
+        self._check_weights(B, Q, P, R)
         f64 = dict(dtype=torch.float64, device=self.device)
         lam = torch.zeros(B, self.N, 2 * self.m, **f64)
         imu = torch.full((B, self.N, 2 * self.m), float(mu0), **f64)
@@ -349,7 +410,7 @@ class BatchedTrackingILQR:
             for outer in range(int(n_al_iters)):
                 res = self.fit_batch(x0_q, x0_xi, us_init, mode="ms", n_iterations=n_ilqr_iters,
                                      tol_grad_norm=tol_grad_norm, tol_d_norm=tol_d_norm, line_search=line_search,
-                                     rollout="nonlinear", q_ref=q_ref, xi_ref=xi_ref)
+                                     rollout="nonlinear", q_ref=q_ref, xi_ref=xi_ref, Q=Q, P=P, R=R)
                 if final is None:
                     final = res
                 else:  # problems that had already converged keep the result of their converging solve
@@ -374,12 +435,15 @@ class BatchedTrackingILQR:
         return final, dict(lmbd=lam, Imu=imu, mu=mu, max_violation=maxviol, al_converged=alconv, outer_iterations=outer + 1)
 
     # ------------------------------------------------------------------------------------------
-    def linearize_backward(self, xs_q, xs_xi, us, ms=True, mu=1.0, delta=2.0, max_reg=1e10, q_ref=None, xi_ref=None):
+    def linearize_backward(self, xs_q, xs_xi, us, ms=True, mu=1.0, delta=2.0, max_reg=1e10, q_ref=None, xi_ref=None, Q=None,
+                           P=None, R=None):
         """One _linearization + _backward_pass (+ gradient norm) on given trajectories.  q_ref / xi_ref: a reference per
-        trajectory, as for fit_batch (rollout / expected_change behind this call use the same references)."""
+        trajectory, Q / P / R: weights per trajectory, as for fit_batch (rollout / expected_change behind this call use the
+        same references and weights)."""
         xs_q = self._dev(xs_q, (-1, self.N + 1, 16))
         B = xs_q.shape[0]
         refs = self._check_refs(B, q_ref, xi_ref)
+        wts = self._check_weights(B, Q, P, R)
         xs_xi = self._dev(xs_xi, (B, self.N + 1, 6))
         us = self._dev(us, (B, self.N, self.m))
         f64 = dict(dtype=torch.float64, device=self.device)
@@ -390,7 +454,7 @@ class BatchedTrackingILQR:
                  lx=torch.empty(B, self.N + 1, 12, **f64), lxx11=torch.empty(B, self.N + 1, 6, 6, **f64),
                  k=torch.empty(B, self.N, self.m, **f64), K=torch.empty(B, self.N, self.m, 12, **f64),
                  J=torch.empty(B, **f64), dnorm=torch.empty(B, **f64), grad=torch.empty(B, **f64), mu_delta=md)
-        self._use_refs(B, refs)
+        self._use_pt(B, refs, wts)
         with torch.cuda.device(self.device):
             rc = self.lib.tolg_linearize_backward(self._h, int(ms), float(max_reg), B, _ptr(xs_q), _ptr(xs_xi), _ptr(us),
                                                   _ptr(md), _ptr(r["Fx"]), _ptr(r["d"]), _ptr(r["lx"]), _ptr(r["lxx11"]),

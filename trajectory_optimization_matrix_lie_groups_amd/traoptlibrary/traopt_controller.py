@@ -62,6 +62,18 @@ def _stack_refs(refs, B):
     return (np.stack([np.asarray(r[0], float) for r in refs]), np.stack([np.asarray(r[1], float) for r in refs]))
 
 
+def _stack_weights(weights, B):
+    """weights: None, or one (Q (12, 12), R (m, m), P (12, 12)) per initial state, diagonal -> (Q [B, 12, 12], P [B, 12, 12],
+    R [B, m, m]) for BatchedTrackingILQR (None x 3: the cost's own weights for every state)."""
+    if weights is None:
+        return None, None, None
+    weights = list(weights)
+    if len(weights) != B:
+        raise ValueError("weights holds %d weight sets for %d initial states" % (len(weights), B))
+    return (np.stack([np.asarray(w[0], float) for w in weights]), np.stack([np.asarray(w[2], float) for w in weights]),
+            np.stack([np.asarray(w[1], float) for w in weights]))
+
+
 def _xs_list(xs_q, xs_xi):
     return [[xs_q[i].copy(), xs_xi[i].copy()] for i in range(xs_q.shape[0])]
 
@@ -123,11 +135,11 @@ class _FusedController(BaseController):
         solver.set_al(self.cost.constr.lb, self.cost.constr.ub, lam, imu)
         return True
 
-    def fit_batch(self, x0s, us_init=None, n_iterations=100, tol_grad_norm=None, tol_d_norm=1e-6, refs=None):
+    def fit_batch(self, x0s, us_init=None, n_iterations=100, tol_grad_norm=None, tol_d_norm=1e-6, refs=None, weights=None):
         """B independent fits on the GPU.  x0s: list of [q (4,4), xi (6,)] or (q [B,4,4], xi [B,6]);
         us_init [B,N,m] or [N,m] (shared) or None (zeros); refs: None (the cost's reference) or one
-        (q_ref (N+1,4,4), xi_ref (N+1,6)) per initial state, each trajectory tracking its own.  Returns a FitResult of
-        device tensors."""
+        (q_ref (N+1,4,4), xi_ref (N+1,6)) per initial state, each trajectory tracking its own; weights: None (the cost's
+        weights) or one diagonal (Q, R, P) per initial state.  Returns a FitResult of device tensors."""
         if isinstance(x0s, tuple) and len(x0s) == 2 and np.ndim(x0s[0]) == 3:
             q, xi = np.asarray(x0s[0], float), np.asarray(x0s[1], float)
         else:
@@ -135,6 +147,7 @@ class _FusedController(BaseController):
             xi = np.stack([np.asarray(x[1], float) for x in x0s])
         B = q.shape[0]
         q_ref, xi_ref = _stack_refs(refs, B)
+        Qs, Ps, Rs = _stack_weights(weights, B)
         if us_init is not None and np.ndim(us_init) == 2:
             us_init = np.broadcast_to(np.asarray(us_init, float), (B,) + np.shape(us_init)).copy()
         solver = self._get_solver(B)
@@ -142,7 +155,7 @@ class _FusedController(BaseController):
         al = self._attach_al(solver, B)
         try:
             return solver.fit_batch(q, xi, us_init, mode=self._mode, n_iterations=n_iterations, tol_grad_norm=tol,
-                                    tol_d_norm=tol_d_norm, q_ref=q_ref, xi_ref=xi_ref, **self._options())
+                                    tol_d_norm=tol_d_norm, q_ref=q_ref, xi_ref=xi_ref, Q=Qs, P=Ps, R=Rs, **self._options())
         finally:
             if al:
                 solver.set_al(None)
@@ -304,12 +317,14 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
     action_size = property(lambda self: self._action_size)
 
     def fit_batch(self, x0s, us_init=None, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6, tol_constr=1e-2,
-                  on_outer=None, refs=None):
-        """refs: None or one (q_ref, xi_ref) per initial state, as for iLQR_Tracking_SE3_MS.fit_batch."""
+                  on_outer=None, refs=None, weights=None):
+        """refs: None or one (q_ref, xi_ref) per initial state, weights: None or one (Q, R, P) per initial state, as for
+        iLQR_Tracking_SE3_MS.fit_batch."""
         q = np.stack([np.asarray(x[0], float) for x in x0s])
         xi = np.stack([np.asarray(x[1], float) for x in x0s])
         B = q.shape[0]
         q_ref, xi_ref = _stack_refs(refs, B)
+        Qs, Ps, Rs = _stack_weights(weights, B)
         if us_init is not None and np.ndim(us_init) == 2:
             us_init = np.broadcast_to(np.asarray(us_init, float), (B,) + np.shape(us_init)).copy()
         solver = self.ilqr_solver._get_solver(B)
@@ -317,7 +332,7 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
                                    n_ilqr_iters=n_ilqr_iters, tol_grad_norm=tol_grad_norm, tol_constr=tol_constr,
                                    mu0=self._mu0, mu_scale=self._mu_scale, mu_max=self._mu_max,
                                    line_search=self.ilqr_solver._line_search, on_outer=on_outer, q_ref=q_ref,
-                                   xi_ref=xi_ref)
+                                   xi_ref=xi_ref, Q=Qs, P=Ps, R=Rs)
 
     def fit(self, x0, us_init, n_al_iters=100, n_ilqr_iters=200, tol_J=1e-6, tol_grad_norm=1e-6, tol_constr=1e-2,
             on_iteration_al=None, on_iteration_ilqr=None):

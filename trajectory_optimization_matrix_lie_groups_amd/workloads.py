@@ -214,3 +214,19 @@ def se3_multiref(B, R, N=200, index=None, seed=SEED):
     xi_ref = np.broadcast_to(prob.xi_ref, (B,) + prob.xi_ref.shape).copy()
     x0_q = np.einsum("bac,bcd->bad", G[index], x0_q)
     return prob, x0_q, x0_xi, us0, q_ref, xi_ref, index, G
+
+
+def se3_weight_sweep(B, K, N=200, spread=3.0, seed=SEED):
+    """B trajectories of se3_tracking's workload under K diagonal weight sets: set k scales each diagonal entry of the
+    headline Q, P and R by its own factor, log-uniform in [1/spread, spread] (seeded; set 0 as well).  Trajectory b uses set
+    b % K.  Returns (prob, x0_q, x0_xi, us0, Q [B, 12, 12], P [B, 12, 12], R [B, 6, 6], index [B], (Qk [K, 12, 12],
+    Pk [K, 12, 12], Rk [K, 6, 6])); prob is se3_tracking's problem with its shared weights."""
+    prob, x0_q, x0_xi, us0 = se3_tracking(B, N=N, seed=seed)
+    rng = np.random.default_rng(seed + 2)
+    ls = np.log(spread)
+    qd, pd, rd = np.diag(prob.Q), np.diag(prob.P), np.diag(prob.R)
+    Qk = np.stack([np.diag(qd * np.exp(rng.uniform(-ls, ls, 12))) for _ in range(K)])
+    Pk = np.stack([np.diag(pd * np.exp(rng.uniform(-ls, ls, 12))) for _ in range(K)])
+    Rk = np.stack([np.diag(rd * np.exp(rng.uniform(-ls, ls, 6))) for _ in range(K)])
+    index = np.arange(B) % K
+    return prob, x0_q, x0_xi, us0, Qk[index], Pk[index], Rk[index], index, (Qk, Pk, Rk)
