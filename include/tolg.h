@@ -245,6 +245,39 @@ int tolg_rollout(tolg_handle_t h, int32_t ms, int32_t rollout_linear, double alp
  * out: d_ecc [B][2] (first-order, second-order term), d_flag [B] (may be NULL). */
 int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, double* d_ecc, int32_t* d_flag, void* stream);
 
+/* The held policy: a nominal trajectory x*_i, u*_i and the time-varying feedback gains k_i, K_i about it, for one batch
+ * of B trajectories -- what the reference's fit leaves in self._k / self._K (traoptlibrary/traopt_controller.py:2636-2637,
+ * :2010-2011, :1322-1323, :692-693).  Two calls set it:
+ *   - tolg_solve_end (and tolg_solve_batch through it): the final trajectory and the gains of the solve's last backward
+ *     sweep.  For a trajectory that converged that sweep ran about its final trajectory; for one stopped by max_iter it ran
+ *     about the iterate BEFORE the final one (the sweep of the last iteration produced the step to the final iterate);
+ *   - tolg_linearize_backward: gains about exactly the trajectory it was given (the way to refresh the gains about the
+ *     final iterate).
+ * tolg_create and tolg_solve_begin clear it; so does tolg_eval_knot (it overwrites the nominal trajectory).  tolg_rollout
+ * (writes the candidate arrays only), tolg_expected_change, tolg_set_al, tolg_al_update, tolg_set_refs and
+ * tolg_set_weights leave it; the two calls below use the references and weights set when they run.
+ * Both calls return TOLG_E_ARG when no policy is held, during a solve in flight, for a B other than the held batch's, when
+ * references or weights per trajectory are set for another B, and (tolg_policy_rollout) for S < 1.  Neither modifies
+ * the held policy: repeated calls give the same bits, and a later solve is unaffected.
+ *
+ * tolg_solve_gains: the gains in the coordinates of tolg_linearize_backward's d_k / d_K:
+ *   out: d_k [B][N][m], d_K [B][N][m][12] (either may be NULL). */
+int tolg_solve_gains(tolg_handle_t h, int32_t B, double* d_k, double* d_K, void* stream);
+
+/* tolg_policy_rollout: S closed-loop rollouts per trajectory of the held policy -- the reference's _rollout with alpha = 0
+ * and rollout = 'nonlinear' (traopt_controller.py:2030-2082) from a perturbed start.  Sample (b, s):
+ *   x^_0 = x*_0 (+) dx0: pose q*_0 Exp(dx0[0:6]), twist xi*_0 + dx0[6:12] (the error coordinates of K: e_0 = dx0);
+ *   i < N: e_i = [Log(q*_i^-1 q^_i); xi^_i - xi*_i], u^_i = u*_i + K_i e_i, x^_{i+1} = f(x^_i, u^_i) with the model's exact
+ *          dynamics (whatever a solve's rollout option was), then xi^_{i+1} += w[b][s][i];
+ *   J = sum_{i<N} l(x^_i, u^_i, i) + l_N(x^_N): the tracking cost, with trajectory b's own reference and weights when
+ *       tolg_set_refs / tolg_set_weights are active; no augmented-Lagrangian terms (tolg_set_al does not change J).
+ *   in : d_dx0 [B][S][12] or NULL (= 0), d_w [B][S][N][6] or NULL (= 0)
+ *   out: d_J [B][S], d_status [B][S] (TOLG_ST_OK, or TOLG_ST_NONFINITE for a sample whose state, control or cost is not
+ *        finite), d_xs_q [B][S][N+1][16], d_xs_xi [B][S][N+1][6], d_us [B][S][N][m]; every output may be NULL.
+ * A sample's bits depend on neither S nor the other samples. */
+int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w, double* d_J,
+                        int32_t* d_status, double* d_xs_q, double* d_xs_xi, double* d_us, void* stream);
+
 /* Timing hook for bench.py: HIP-event time (ms) and launch count of the dominant kernel
  * (backward sweep) accumulated since the last call with reset != 0.  Synchronises the recorded
  * events only.  Timing is not free: an event pair per launch lengthens an accept-always iteration

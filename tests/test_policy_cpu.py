@@ -1,0 +1,88 @@
+"""Held policy and closed-loop rollouts (tolg_solve_gains, tolg_policy_rollout): the parts that need no GPU -- the C ABI
+surface, the Monte-Carlo workload, and the CPU restatement of a closed-loop rollout that tests/test_gpu_policy.py checks
+the kernel against."""
+import os
+import re
+
+import numpy as np
+
+from oracle import bridge as ob
+from trajectory_optimization_matrix_lie_groups_amd import _capi, workloads
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("tolg_solve_gains", "tolg_policy_rollout")
+
+
+def restate_policy(op, q_nom, xi_nom, u_nom, K, dx0=None, noise=None, S=1):
+    """S closed-loop rollouts of one trajectory's policy from oracle primitives only (ob.f, ob.cost, ob.se3_exp,
+    ob.rminus): x^_0 = x*_0 (+) dx0, u^_i = u*_i + K_i [x^_i (-) x*_i], x^_{i+1} = f(x^_i, u^_i) + twist noise.
+    q_nom [N+1, 4, 4], xi_nom [N+1, 6], u_nom [N, m], K [N, m, 12], dx0 [S, 12], noise [S, N, 6].
+    Returns J [S], xs_q [S, N+1, 4, 4], xs_xi [S, N+1, 6], us [S, N, m]."""
+    N, m = u_nom.shape
+    J = np.zeros(S)
+    xs_q = np.zeros((S, N + 1, 4, 4)); xs_xi = np.zeros((S, N + 1, 6)); us = np.zeros((S, N, m))
+    for s in range(S):
+        q, xi = np.array(q_nom[0], float), np.array(xi_nom[0], float)
+        if dx0 is not None:
+            q = q @ ob.se3_exp(dx0[s, :6])
+            xi = xi + dx0[s, 6:]
+        for i in range(N):
+            e = np.r_[ob.rminus(q, q_nom[i]), xi - xi_nom[i]]
+            u = u_nom[i] + K[i] @ e
+            xs_q[s, i], xs_xi[s, i], us[s, i] = q, xi, u
+            J[s] += ob.cost(op, q, xi, u, i)[0]
+            q, xi = ob.f(op, q, xi, u)
+            if noise is not None:
+                xi = xi + noise[s, i]
+        xs_q[s, N], xs_xi[s, N] = q, xi
+        J[s] += ob.cost(op, q, xi, None, N, terminal=True)[0]
+    return J, xs_q, xs_xi, us
+
+
+def test_new_symbols_in_header_capi_and_library():
+    hdr = open(os.path.join(ROOT, "include", "tolg.h")).read()
+    lib = _capi.load()
+    for name in NEW:
+        assert re.search(r"\bint %s\(" % name, hdr), name
+        assert name in _capi.SYMBOLS
+        assert hasattr(lib, name)
+
+
+def test_null_handle_is_an_argument_error():
+    lib = _capi.load()
+    assert lib.tolg_solve_gains(None, 1, None, None, None) == -1
+    assert lib.tolg_policy_rollout(None, 1, 1, None, None, None, None, None, None, None, None) == -1
+    assert lib.tolg_policy_rollout(None, 1, 0, None, None, None, None, None, None, None, None) == -1
+
+
+def test_policy_eval_workload_is_seeded_and_shaped():
+    a = workloads.se3_policy_eval(3, 5, N=40, sigma_pose=0.1, sigma_twist=0.2, sigma_noise=0.03, seed=11)
+    b = workloads.se3_policy_eval(3, 5, N=40, sigma_pose=0.1, sigma_twist=0.2, sigma_noise=0.03, seed=11)
+    c = workloads.se3_policy_eval(3, 5, N=40, sigma_pose=0.1, sigma_twist=0.2, sigma_noise=0.03, seed=12)
+    prob, q, xi, us, dx0, noise = a
+    assert prob.N == 40 and q.shape[0] == 3 and xi.shape == (3, 6) and us.shape == (3, 40, 6)
+    assert dx0.shape == (3, 5, 12) and noise.shape == (3, 5, 40, 6)
+    assert np.array_equal(dx0, b[4]) and np.array_equal(noise, b[5])
+    assert not np.array_equal(dx0, c[4])
+    assert 0.05 < dx0[..., :6].std() < 0.2 and 0.1 < dx0[..., 6:].std() < 0.4 and 0.02 < noise.std() < 0.04
+    z = workloads.se3_policy_eval(2, 3, N=10, sigma_pose=0.0, sigma_twist=0.0, sigma_noise=0.0)
+    assert not z[4].any() and not z[5].any()
+
+
+def test_restatement_with_zero_perturbation_and_gains_is_the_open_loop_rollout():
+    prob, q0, xi0, us = workloads.se3_tracking(1, N=30)
+    op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
+    N, m = prob.N, prob.m
+    rng = np.random.default_rng(3)
+    u = us[0] + rng.normal(size=(N, m)) * 0.1
+    q_ol = np.zeros((N + 1, 4, 4)); xi_ol = np.zeros((N + 1, 6))
+    q_ol[0], xi_ol[0] = np.asarray(q0[0], float).reshape(4, 4), xi0[0]
+    J = 0.0
+    for i in range(N):
+        J += ob.cost(op, q_ol[i], xi_ol[i], u[i], i)[0]
+        q_ol[i + 1], xi_ol[i + 1] = ob.f(op, q_ol[i], xi_ol[i], u[i])
+    J += ob.cost(op, q_ol[N], xi_ol[N], None, N, terminal=True)[0]
+    Jr, xq, xx, ur = restate_policy(op, q_ol, xi_ol, u, np.zeros((N, m, 12)), dx0=np.zeros((2, 12)), S=2)
+    for s in range(2):
+        assert np.array_equal(xq[s], q_ol) and np.array_equal(xx[s], xi_ol) and np.array_equal(ur[s], u)
+        assert Jr[s] == J

@@ -1,0 +1,128 @@
+"""What the closed-loop rollouts of the held policy cost (tolg_policy_rollout): S perturbed rollouts per trajectory of a
+solved 4096 x 200 SE3 tracking batch, J and status only.
+
+usage: python tools/bench_policy.py [--B 4096] [--N 200] [--S 1,16,64] [--rounds 7] [--iters 20] [--layouts samples,traj]
+                                    [--out FILE.json]
+
+One process.  The batch is solved once, untimed (multiple shooting, accept-always, 20 iterations), once per sample order of
+k_policy_rollout: `samples` (the default order, the samples of one trajectory side by side in a wavefront) and `traj`
+(TOLG_POLICY_TRAJ_FAST=1 when the handle is created: trajectory fastest, K3's order).  Then, round after round, every
+(S, layout) pair and tolg_rollout(ms = 0, alpha = 0) -- K3 on the same batch, the nearest existing kernel -- are timed in
+alternation: `iters` back-to-back calls between two events, through the C ABI (no host-side input checks).  Reported per
+pair: the median ms per call over the rounds, min and max, closed-loop knot steps per second (B S N per call), and the HBM
+bytes the call has to move at least (inputs, outputs, and the nominal data -- gains, controls, states: 97 doubles per knot
+and trajectory -- read once per wavefront that needs it: ceil(S / 16) times in `samples` order, S times in `traj` order)."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from trajectory_optimization_matrix_lie_groups_amd import workloads  # noqa: E402
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--B", type=int, default=4096)
+    ap.add_argument("--N", type=int, default=200)
+    ap.add_argument("--S", default="1,16,64")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=20, help="calls per timed region")
+    ap.add_argument("--layouts", default="samples,traj")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args(argv)
+    a.S = [int(s) for s in a.S.split(",")]
+    a.layouts = [x for x in ("samples", "traj") if x in a.layouts.split(",")]
+    if a.B < 1 or a.N < 1 or min(a.S) < 1 or a.rounds < 1 or a.iters < 1 or not a.layouts:
+        ap.error("B, N, S, rounds, iters >= 1; layouts from samples, traj")
+    return a
+
+
+def nominal_bytes(B, N, m, S, layout):
+    per = (13 * m + m + 13) * 8  # gains [K | k], nominal control and state of one knot of one trajectory
+    reads = -(-S // 16) if layout == "samples" else S
+    return B * N * per * reads
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    import torch
+    from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
+
+    B, N = a.B, a.N
+    prob, q, xi, us = workloads.se3_tracking(B, N=N)
+    m = prob.m
+    solvers = {}
+    for layout in a.layouts:
+        os.environ["TOLG_POLICY_TRAJ_FAST"] = "1" if layout == "traj" else "0"
+        s = BatchedTrackingILQR(prob, B)
+        s.fit_batch(q, xi, us, mode="ms", n_iterations=20, tol_grad_norm=0.0, tol_d_norm=0.0)
+        solvers[layout] = s
+    os.environ.pop("TOLG_POLICY_TRAJ_FAST", None)
+    torch.cuda.synchronize()
+    dev = solvers[a.layouts[0]].device
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    f64 = dict(dtype=torch.float64, device=dev)
+    inputs = {}
+    for S in a.S:
+        dx0 = torch.randn(B, S, 12, generator=g, **f64) * 0.05
+        w = torch.randn(B, S, N, 6, generator=g, **f64) * 0.01
+        inputs[S] = (dx0, w, torch.empty(B, S, **f64), torch.empty(B, S, dtype=torch.int32, device=dev))
+    ro = tuple(torch.empty(*shape, **f64) for shape in ((B, N + 1, 4, 4), (B, N + 1, 6), (B, N, m)))
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+
+    def call(name):
+        if name == "rollout":
+            s = solvers[a.layouts[0]]
+            return s.lib.tolg_rollout(s._h, 0, 0, 0.0, B, p(ro[0]), p(ro[1]), p(ro[2]), s._stream())
+        layout, S = name
+        s = solvers[layout]
+        dx0, w, J, st = inputs[S]
+        return s.lib.tolg_policy_rollout(s._h, B, S, p(dx0), p(w), p(J), p(st), None, None, None, s._stream())
+
+    names = [(layout, S) for S in a.S for layout in a.layouts] + ["rollout"]
+    for n in names:  # warm-up and argument check
+        if call(n) != 0:
+            raise RuntimeError("launch failed: %s" % (n,))
+    torch.cuda.synchronize()
+    times = {n: [] for n in names}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for r in range(a.rounds):
+        order = names[r % len(names):] + names[: r % len(names)]
+        for n in order:
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(a.iters):
+                call(n)
+            e1.record()
+            e1.synchronize()
+            times[n].append(e0.elapsed_time(e1) / a.iters)
+    rows = []
+    for n in names:
+        t = times[n]
+        med = statistics.median(t)
+        row = dict(kernel="tolg_rollout(ms=0, alpha=0)" if n == "rollout" else "tolg_policy_rollout",
+                   ms_median=med, ms_min=min(t), ms_max=max(t))
+        if n == "rollout":
+            row.update(S=1, steps_per_s=B * N / (med * 1e-3))
+        else:
+            layout, S = n
+            st = inputs[S][3]
+            nb = nominal_bytes(B, N, m, S, layout) + B * S * (12 + N * 6) * 8 + B * S * 12
+            row.update(layout=layout, S=S, steps_per_s=B * S * N / (med * 1e-3), hbm_bytes_est=nb,
+                       hbm_GBps_est=nb / (med * 1e-3) / 1e9, status_ok=int((st == 0).sum().item()),
+                       J_finite=int(torch.isfinite(inputs[S][2]).sum().item()))
+        rows.append(row)
+        print(json.dumps(row))
+    res = dict(B=B, N=N, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(dev), rows=rows)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    return res
+
+
+if __name__ == "__main__":
+    main()

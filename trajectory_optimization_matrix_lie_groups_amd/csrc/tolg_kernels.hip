@@ -2808,6 +2808,81 @@ __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nsl
   P.dtrial[(size_t)b * 20 + ai] = sqrt(d2);
 }
 
+// Closed-loop rollouts of the held policy (tolg_policy_rollout): S samples per trajectory, one quad per sample (b, s), the
+// step of K3 (roll_step: alpha = 0, exact dynamics, no factors) from x^_0 = x*_0 (+) dx0, twist noise added behind every
+// step, the tracking cost summed on the chain.  Sample order: traj_fast = 0 puts the samples of one
+// trajectory side by side (quad c = b S + s), so that its gains, nominal controls, states and reference are one address per
+// wave; traj_fast = 1 is K3's order (c = s B + b).  Every value a quad computes is its own: the series gates are wave-wide
+// only in which tiers run (tolg_lie.h), so a sample's bits do not depend on S, on the order or on its neighbours.
+// Generic constants pointer: cost and dynamics on one chain is the construct the note at DConsts warns about.
+template <int M, int PK, int PT>
+__global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj_fast, const double* __restrict__ dx0,
+                                                       const double* __restrict__ noise, double* __restrict__ Jout,
+                                                       int* __restrict__ status, double* __restrict__ xs_q,
+                                                       double* __restrict__ xs_xi, double* __restrict__ us) {
+  const Consts& C = *P.c;
+  const size_t n = (size_t)P.B * (size_t)S;
+  size_t c = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+  const int q = threadIdx.x & 3;
+  // quads past the last sample replay it (DPP needs whole quads alive) and store nothing
+  const bool live = c < n;
+  if (!live) c = n - 1;
+  const int b = traj_fast ? (int)(c % (size_t)P.B) : (int)(c / (size_t)S);
+  const size_t s = traj_fast ? c / (size_t)P.B : c % (size_t)S;
+  const size_t bs = (size_t)b * S + s;  // row of the [B][S] outputs
+  const bool writer = live && q == 0;
+  const int N = P.N;
+  const unsigned sB = (unsigned)P.Bp * 8u, vb = (unsigned)b * 8u;
+  const DynK DK = dynk_load(C);
+  State Sa = roll_load_state(P, 0, vb, sB), Sb = Sa;
+  State Sn = Sa;  // x^_0 = x*_0 (+) dx0: pose x*_0 Exp(dx0[0:6]), twist xi*_0 + dx0[6:12]
+  if (dx0) {
+    const double* d = dx0 + 12 * bs;
+    Sn.X = se3_project(se3_compose(Sa.X, se3_exp(v3(d[0], d[1], d[2]), v3(d[3], d[4], d[5]))));
+    Sn.w = Sa.w + v3(d[6], d[7], d[8]);
+    Sn.v = Sa.v + v3(d[9], d[10], d[11]);
+  }
+#ifdef TOLG_STAMPS
+  RStamps ST = {};
+#endif
+  double J = 0.0, un[M];
+  for (int i = 0; i < N; i++) {
+    if (i + 1 < N) Sb = roll_load_state(P, i + 1, vb, sB);
+    __builtin_amdgcn_sched_barrier(0);
+    const State Nx = roll_step<M, false, true, PK, false>(P, C, DK, i, b, q, false, vb, sB, 0.0, Sa, Sn, un,
+                                                           [&](RollIn<M>& R) { roll_load<M, true>(P, i, b, q, vb, sB, R); },
+                                                           nullptr RST_ARG);
+    J += knot_cost<M, true, PT>(P, C, i, b, Sn, un, false);
+    if (writer) {
+      const size_t k = bs * (size_t)(N + 1) + i;
+      if (xs_q) pose_to_m16(Sn.X, xs_q + 16 * k);
+      if (xs_xi) { double* x = xs_xi + 6 * k; x[0] = Sn.w.x; x[1] = Sn.w.y; x[2] = Sn.w.z; x[3] = Sn.v.x; x[4] = Sn.v.y; x[5] = Sn.v.z; }
+      if (us) {
+        double* u = us + (bs * (size_t)N + i) * M;
+#pragma unroll
+        for (int a = 0; a < M; a++) u[a] = un[a];
+      }
+    }
+    Sn = Nx;
+    if (noise) {
+      const double* w = noise + (bs * (size_t)N + i) * 6;
+      Sn.w = Sn.w + v3(w[0], w[1], w[2]);
+      Sn.v = Sn.v + v3(w[3], w[4], w[5]);
+    }
+    Sa = Sb;
+  }
+#pragma unroll
+  for (int a = 0; a < M; a++) un[a] = 0.0;
+  J += knot_cost<M, true, PT>(P, C, N, b, Sn, un, true);
+  if (writer) {
+    const size_t k = bs * (size_t)(N + 1) + N;
+    if (xs_q) pose_to_m16(Sn.X, xs_q + 16 * k);
+    if (xs_xi) { double* x = xs_xi + 6 * k; x[0] = Sn.w.x; x[1] = Sn.w.y; x[2] = Sn.w.z; x[3] = Sn.v.x; x[4] = Sn.v.y; x[5] = Sn.v.z; }
+    if (Jout) Jout[bs] = J;
+    if (status) status[bs] = isfinite(J) ? TOLG_ST_OK : TOLG_ST_NONFINITE;
+  }
+}
+
 // ---- line-search stages, round 3 form -----------------------------------------------------------------------------
 // A stage is three launches: (1) k_rollout_ls -- the closed-loop rollouts alone, the quad form of K3 (roll_step with
 // STORE), one quad per (undecided trajectory, alpha), the undecided trajectories taken from a compacted list so that a
@@ -3711,6 +3786,7 @@ struct KernelTable {
   void (*ec_ring[2])(Params);        // expected change, ring form [STORE]
   void (*ec_stmt[2])(Params);        //                  statement form [REDO]
   void (*affine_commit)(Params, int, int);
+  void (*policy_rollout)(Params, int, int, const double*, const double*, double*, int*, double*, double*, double*);  // tolg_policy_rollout
   struct Search {                    // per search kind: ls[0] backtracking (single shooting), ls[1] merit (multiple shooting)
     struct { SearchRollout k; int nt; } wave2[2];  // k_rollout_ls2 [first try] and its NT (twist waves per pose wave)
     SearchRollout wave1[2];          // the one-wave forms k_rollout_ls [linear]
@@ -3770,6 +3846,7 @@ static KernelTable kernel_table(int lds_per_block) {
   t.ec_stmt[0] = k_expected_change<M, PK, false, PTW>;
   t.ec_stmt[1] = k_expected_change<M, PK, true, PTW>;
   t.affine_commit = k_affine_commit<M>;
+  t.policy_rollout = k_policy_rollout<M, PK, PT>;
   t.ls[0] = search_kernels<M, false, PK, PT>();
   t.ls[1] = search_kernels<M, true, PK, PT>();
   return t;
@@ -3806,6 +3883,12 @@ struct tolg_handle_s {
   int refs_B = 0;                // ... and the batch they were set for: every batch call must match it
   const double* wts = nullptr;   // tolg_set_weights: the packed per-trajectory weights (caller-owned), or null
   int wts_B = 0;                 // ... and their batch, as refs_B
+  // The held policy (tolg_solve_gains, tolg_policy_rollout): nominal trajectory P.cur / P.cur_u and gains P.GK of a batch of
+  // pol_B trajectories, 0 = none.  Set by tolg_solve_end and tolg_linearize_backward; cleared by tolg_solve_begin and
+  // tolg_eval_knot (k_probe_pack writes P.cur); tolg_rollout (writes the candidate arrays) and tolg_expected_change (ED, ecc)
+  // leave it.
+  int pol_B = 0;
+  bool pol_traj_fast = false;    // A/B switch (TOLG_POLICY_TRAJ_FAST=1): k_policy_rollout in K3's sample order
   // A/B switches of the tests, read from the environment when the handle is created: every sweep the full kernel
   // (TOLG_K2_FULL_ONLY=1), the one-wave forms of the line-search rollouts (TOLG_LS_ONEWAVE=1)
   bool k2_full_only, ls_one_wave;
@@ -4047,6 +4130,8 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
     h->k2_full_only = e && e[0] == '1';
     e = getenv("TOLG_LS_ONEWAVE");
     h->ls_one_wave = e && e[0] == '1';
+    e = getenv("TOLG_POLICY_TRAJ_FAST");
+    h->pol_traj_fast = e && e[0] == '1';
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   Consts* dc = nullptr;
@@ -4424,6 +4509,7 @@ extern "C" int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_
   if (opt->mode != TOLG_MODE_MS && opt->mode != TOLG_MODE_SS) return TOLG_E_ARG;
   const int ms = opt->mode == TOLG_MODE_MS;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  h->pol_B = 0;  // the solve overwrites trajectory and gains
   Params P = params_for(h, B);
   P.J_hist = d_J_hist; P.grad_hist = d_grad_hist; P.defect_hist = d_defect_hist; P.alpha_hist = d_alpha_hist;
   P.mu_hist = d_mu_hist; P.max_iter = opt->max_iter; P.tol_grad = opt->tol_grad; P.tol_defect = opt->tol_defect;
@@ -4469,7 +4555,7 @@ static int solve_export(tolg_handle_t h, double* d_xs_q, double* d_xs_xi, double
   hipLaunchKernelGGL(k_export_scalars, dim3((P.B + 63) / 64), dim3(64), 0, st, P, nullptr, nullptr, nullptr, nullptr,
                      d_iters, d_status, d_converged);
   LAUNCH_CHECK();
-  if (end) h->running = false;
+  if (end) { h->running = false; h->pol_B = P.B; }  // the last sweep's gains stay with the final trajectory: the held policy
   return 0;
 }
 extern "C" int tolg_solve_end(tolg_handle_t h, double* d_xs_q, double* d_xs_xi, double* d_us, int32_t* d_iters,
@@ -4651,6 +4737,7 @@ extern "C" int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_r
   if (!h || h->running || B < 1 || B > h->max_batch || !d_xs_q || !d_xs_xi || !d_us) return TOLG_E_ARG;
   if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  h->pol_B = 0;  // held again once the sweep below is queued
   Params P = params_for(h, B);
   P.max_reg = max_reg;
   size_t n = (size_t)(P.N + 1) * P.Bp;
@@ -4669,6 +4756,7 @@ extern "C" int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_r
   hipLaunchKernelGGL(k_export_scalars, dim3((B + 63) / 64), dim3(64), 0, st, P, d_J, d_dnorm, d_grad, d_mu_delta,
                      nullptr, nullptr, nullptr);
   LAUNCH_CHECK();
+  h->pol_B = B;
   return 0;
 }
 
@@ -4679,6 +4767,7 @@ extern "C" int tolg_eval_knot(tolg_handle_t h, int32_t i, int32_t n, const doubl
   if (!h || h->running || n < 1 || n > h->max_batch || i < 0 || i > h->prob.N || !d_x_q || !d_x_xi) return TOLG_E_ARG;
   if (i < h->prob.N && !d_u) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  h->pol_B = 0;  // k_probe_pack overwrites knot i of the nominal trajectory
   Params P = params_for(h, n);
   P.ref = h->ref_shared;  // the reference of tolg_create, whatever tolg_set_refs holds (K1 below: the shared weights too)
   hipLaunchKernelGGL(k_probe_pack, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, i, d_x_q, d_x_xi, d_u);
@@ -4737,6 +4826,36 @@ extern "C" int tolg_rollout(tolg_handle_t h, int32_t ms, int32_t rollout_linear,
   size_t n = (size_t)(P.N + 1) * P.Bp;
   hipLaunchKernelGGL(k_unpack_traj, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, P.cand, P.cand_u, d_xs_q_new,
                      d_xs_xi_new, d_us_new);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// the held policy (h->pol_B): what both entry points below require
+static bool policy_ok(const tolg_handle_s* h, int B) {
+  if (!h || h->running || h->pol_B == 0 || B != h->pol_B) return false;
+  return !((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B));
+}
+extern "C" int tolg_solve_gains(tolg_handle_t h, int32_t B, double* d_k, double* d_K, void* stream) {
+  if (!policy_ok(h, B)) return TOLG_E_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Params P = params_for(h, B);
+  size_t ne = (size_t)(P.N + 1) * B;
+  hipLaunchKernelGGL(k_export_lin, dim3((unsigned)((ne + 127) / 128)), dim3(128), 0, st, P, nullptr, nullptr, nullptr, nullptr,
+                     d_k, d_K);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w, double* d_J,
+                                   int32_t* d_status, double* d_xs_q, double* d_xs_xi, double* d_us, void* stream) {
+  if (!policy_ok(h, B) || S < 1) return TOLG_E_ARG;
+  const size_t lanes = (size_t)B * (size_t)S * 4;
+  if (lanes > 0x7fffffc0ull) return TOLG_E_ARG;  // one launch, 64-lane groups
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Params P = params_for(h, B);
+  P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // J is the tracking cost: no augmented-Lagrangian terms
+  hipLaunchKernelGGL(h->kt.policy_rollout, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P, (int)S,
+                     h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us);
   LAUNCH_CHECK();
   return 0;
 }

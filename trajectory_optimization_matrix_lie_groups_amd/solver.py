@@ -81,6 +81,16 @@ class FitResult:
     extra: dict = field(default_factory=dict)
 
 
+@dataclass
+class PolicyRollout:
+    """S closed-loop rollouts per trajectory of the held policy (BatchedTrackingILQR.policy_rollout)."""
+    J: torch.Tensor        # [B, S] tracking cost of each sample
+    status: torch.Tensor   # [B, S] int32: ST_OK or ST_NONFINITE
+    xs_q: Optional[torch.Tensor] = None   # [B, S, N+1, 4, 4] (trajectories=True)
+    xs_xi: Optional[torch.Tensor] = None  # [B, S, N+1, 6]
+    us: Optional[torch.Tensor] = None     # [B, S, N, m]
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
@@ -279,6 +289,7 @@ class BatchedTrackingILQR:
             rc = self.lib.tolg_solve_begin(self._h, C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(us_init),
                                            _ptr(out.J_hist), _ptr(out.grad_hist), _ptr(out.defect_hist),
                                            _ptr(out.alpha_hist), _ptr(out.mu_hist), self._stream())
+        self._policy_B = 0  # the solve overwrites the held policy (also when it could not start)
         _capi.check(rc, "tolg_solve_begin")
         self._inflight = (out, (x0_q, x0_xi, us_init))  # keep the inputs alive until the stream has used them
         return out
@@ -322,6 +333,7 @@ class BatchedTrackingILQR:
             rc = self.lib.tolg_solve_end(self._h, _ptr(out.xs_q), _ptr(out.xs_xi), _ptr(out.us), _ptr(out.iters),
                                          _ptr(out.status), _ptr(out.converged), self._stream())
         _capi.check(rc, "tolg_solve_end")
+        self._policy_B = out.xs_q.shape[0]
         return out
 
     def fit_batch(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
@@ -367,7 +379,9 @@ class BatchedTrackingILQR:
                                            _ptr(out.xs_xi), _ptr(out.us), _ptr(out.J_hist), _ptr(out.grad_hist),
                                            _ptr(out.defect_hist), _ptr(out.alpha_hist), _ptr(out.mu_hist), _ptr(out.iters),
                                            _ptr(out.status), _ptr(out.converged), self._stream())
+        self._policy_B = 0
         _capi.check(rc, "tolg_solve_batch")
+        self._policy_B = B
         torch.cuda.current_stream(self.device).synchronize()  # the inputs above must outlive the queued work
         return out
 
@@ -460,7 +474,9 @@ class BatchedTrackingILQR:
                                                   _ptr(md), _ptr(r["Fx"]), _ptr(r["d"]), _ptr(r["lx"]), _ptr(r["lxx11"]),
                                                   _ptr(r["k"]), _ptr(r["K"]), _ptr(r["J"]), _ptr(r["dnorm"]),
                                                   _ptr(r["grad"]), self._stream())
+        self._policy_B = 0
         _capi.check(rc, "tolg_linearize_backward")
+        self._policy_B = B
         return r
 
     def eval_knot(self, i, x_q, x_xi, u=None):
@@ -482,6 +498,7 @@ class BatchedTrackingILQR:
             rc = self.lib.tolg_eval_knot(self._h, int(i), n, _ptr(x_q), _ptr(x_xi), _ptr(u_d), g("f_q"), g("f_xi"),
                                          g("Fx"), g("Fu"), g("l"), g("lx"), g("lxx"), g("lu"), g("luu"), g("err"),
                                          self._stream())
+        self._policy_B = 0  # the probe overwrites the nominal trajectory (include/tolg.h, held policy)
         _capi.check(rc, "tolg_eval_knot")
         return r
 
@@ -509,6 +526,75 @@ class BatchedTrackingILQR:
                                                _ptr(flag), self._stream())
         _capi.check(rc, "tolg_expected_change")
         return ecc, flag
+
+    # ------------------------------------------------------------------------------------------
+    def _held_B(self):
+        B = getattr(self, "_policy_B", 0)
+        if not B:
+            raise ValueError("no policy is held: it is left by solve_end / fit_batch / solve_batch_one_call or "
+                             "linearize_backward, and cleared by solve_begin and eval_knot")
+        return B
+
+    def gains(self):
+        """The feedback gains of the held policy (what the reference's fit leaves in self._k / self._K): {"k": [B, N, m],
+        "K": [B, N, m, 12]} device tensors, in the coordinates of linearize_backward's k / K.  After a solve they are the
+        gains of its last backward sweep (about the final trajectory for a converged trajectory, about the iterate before
+        it for one stopped by n_iterations); after linearize_backward, about the trajectory it was given."""
+        B = self._held_B()
+        f64 = dict(dtype=torch.float64, device=self.device)
+        k = torch.empty(B, self.N, self.m, **f64)
+        K = torch.empty(B, self.N, self.m, 12, **f64)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tolg_solve_gains(self._h, B, _ptr(k), _ptr(K), self._stream())
+        _capi.check(rc, "tolg_solve_gains")
+        return {"k": k, "K": K}
+
+    def _host_f64(self, name, a, shape):
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != len(shape) or any(n is not None and n != s for n, s in zip(shape, a.shape)):
+            raise ValueError("%s has shape %s, expected %s" % (name, tuple(a.shape), tuple("S" if n is None else n for n in shape)))
+        if not np.all(np.isfinite(a)):
+            raise ValueError("%s must be finite" % name)
+        return a
+
+    def policy_rollout(self, dx0=None, noise=None, S=None, trajectories=False) -> PolicyRollout:
+        """S closed-loop rollouts per trajectory of the held policy u = u*_i + K_i (x (-) x*_i) with exact dynamics
+        (tolg_policy_rollout).  dx0 [B, S, 12]: start perturbation in the error coordinates of K (pose x*_0 Exp(dx0[:6]),
+        twist xi*_0 + dx0[6:]); noise [B, S, N, 6]: added to the twist behind every step.  Either may be None (zero); S is
+        taken from them, or given when both are None.  J [B, S] is the tracking cost with the references and weights of the
+        held solve (no augmented-Lagrangian terms).  trajectories=True also returns xs_q, xs_xi, us."""
+        B = self._held_B()
+        shapes = []
+        if dx0 is not None:
+            dx0 = self._host_f64("dx0", dx0, (B, None, 12))
+            shapes.append(dx0.shape[1])
+        if noise is not None:
+            noise = self._host_f64("noise", noise, (B, None, self.N, 6))
+            shapes.append(noise.shape[1])
+        if S is not None:
+            shapes.append(int(S))
+        if not shapes:
+            raise ValueError("policy_rollout needs S, dx0 or noise")
+        if len(set(shapes)) != 1:
+            raise ValueError("the sample count differs between dx0, noise and S: %s" % shapes)
+        S = shapes[0]
+        if S < 1:
+            raise ValueError("S must be at least 1")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        d_dx0 = None if dx0 is None else self._dev(dx0, (B, S, 12))
+        d_w = None if noise is None else self._dev(noise, (B, S, self.N, 6))
+        r = PolicyRollout(J=torch.empty(B, S, **f64), status=torch.empty(B, S, dtype=torch.int32, device=self.device))
+        if trajectories:
+            r.xs_q = torch.empty(B, S, self.N + 1, 4, 4, **f64)
+            r.xs_xi = torch.empty(B, S, self.N + 1, 6, **f64)
+            r.us = torch.empty(B, S, self.N, self.m, **f64)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tolg_policy_rollout(self._h, B, S, _ptr(d_dx0), _ptr(d_w), _ptr(r.J), _ptr(r.status), _ptr(r.xs_q),
+                                              _ptr(r.xs_xi), _ptr(r.us), self._stream())
+        _capi.check(rc, "tolg_policy_rollout")
+        self._policy_keep = (d_dx0, d_w)  # the kernel reads them on the stream
+        return r
 
     # ------------------------------------------------------------------------------------------
     def enable_timing(self, on=True):

@@ -206,8 +206,10 @@ class GenericLieILQR:
         e = self._expand(xs, us)
         if ms:
             defect_hist.append(e["dnorm"])
+        self.k = self.K = None  # the gains of the last sweep (what the reference's fit leaves in self._k / self._K)
         for it in range(int(n_iterations)):
             k, K, grad, _ = self._sweep(e)
+            self.k, self.K = k, K
             if not ms:
                 grad_hist.append(grad)
             if grad < tol_grad_norm and (not ms or e["dnorm"] < tol_d_norm):

@@ -172,7 +172,20 @@ class _FusedController(BaseController):
         out = g.fit(x0, us_init, getattr(self, "_q_ref", None), getattr(self, "_xi_ref", None), n_iterations,
                     tol_grad_norm, tol_d_norm, on_iteration, self._append_grad_on_convergence)
         self._mu = g.mu
+        if g.K is not None:
+            self._k, self._K = g.k, g.K
         return out
+
+    def _store_gains(self, solver):
+        """self._k / self._K from the held policy of the solve that has just ended (traopt_controller.py:2636-2637, :2010-2011,
+        :1322-1323, :692-693), cut to the shapes the constructor gave them: the SO(3) embedding keeps the torque rows and
+        the rotation / body-rate columns of the 6 x 12 gain, as it keeps us[:, :3]."""
+        g = solver.gains()
+        k, K = _bridge.host(g["k"])[0], _bridge.host(g["K"])[0]
+        a, n = self._k.shape[1], self._K.shape[2]
+        cols = list(range(12)) if n == 12 else [0, 1, 2, 6, 7, 8]
+        self._k = k[:, :a].copy()
+        self._K = K[:, :a][:, :, cols].copy()
 
     # one trajectory, iteration by iteration, so that the callback sees what the reference shows it
     def _fit_single(self, x0, us_init, n_iterations, tol_grad_norm, tol_d_norm, on_iteration, ms):
@@ -233,6 +246,7 @@ class _FusedController(BaseController):
                 solver.solve_end()
             if al:
                 solver.set_al(None)
+        self._store_gains(solver)
         return xs, us, J_hist, xs_hist, us_hist, grad_hist, defect_hist
 
 

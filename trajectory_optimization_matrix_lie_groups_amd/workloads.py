@@ -230,3 +230,15 @@ def se3_weight_sweep(B, K, N=200, spread=3.0, seed=SEED):
     Rk = np.stack([np.diag(rd * np.exp(rng.uniform(-ls, ls, 6))) for _ in range(K)])
     index = np.arange(B) % K
     return prob, x0_q, x0_xi, us0, Qk[index], Pk[index], Rk[index], index, (Qk, Pk, Rk)
+
+
+def se3_policy_eval(B, S, N=200, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=0.01, seed=SEED):
+    """Monte-Carlo inputs for the closed loop of se3_tracking's workload (BatchedTrackingILQR.policy_rollout): S seeded
+    perturbations per trajectory.  Returns (prob, x0_q, x0_xi, us0, dx0 [B, S, 12], noise [B, S, N, 6]); dx0 is Gaussian
+    in the error coordinates of the gains, sigma_pose on the pose part (rotation, translation), sigma_twist on the twist,
+    and noise is a Gaussian twist disturbance with sigma_noise behind every step."""
+    prob, x0_q, x0_xi, us0 = se3_tracking(B, N=N, seed=seed)
+    rng = np.random.default_rng(seed + 3)
+    dx0 = np.concatenate([rng.normal(0.0, sigma_pose, (B, S, 6)), rng.normal(0.0, sigma_twist, (B, S, 6))], axis=2)
+    noise = rng.normal(0.0, sigma_noise, (B, S, N, 6))
+    return prob, x0_q, x0_xi, us0, dx0, noise
