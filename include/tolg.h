@@ -123,6 +123,15 @@ int tolg_solve_batch(tolg_handle_t h, const tolg_options* opt, int32_t B, const 
 int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_t B, const double* d_x0_q,
                      const double* d_x0_xi, const double* d_us_init, double* d_J_hist, double* d_grad_hist,
                      double* d_defect_hist, double* d_alpha_hist, double* d_mu_hist, void* stream);
+/* tolg_solve_begin with a warm start of the shooting states: in MS mode knots 1..N of the initial guess are
+ * d_xs_q_init [B][N+1][16] / d_xs_xi_init [B][N+1][6] (knot 0 is always x0; xs_init[b][0] is not read) in place of the
+ * reference.  In SS mode the initial rollout decides the states as in tolg_solve_begin, and d_xs_*_init are ignored (may be
+ * NULL).  Everything else -- the per-trajectory reference and weight rules, the held policy, the scalar reset, TOLG_E_ARG --
+ * is tolg_solve_begin's; MS with either d_xs_*_init NULL is TOLG_E_ARG.  With xs_init = x0 followed by the reference knots
+ * the solve is bitwise tolg_solve_begin's. */
+int tolg_solve_begin_warm(tolg_handle_t h, const tolg_options* opt, int32_t B, const double* d_x0_q, const double* d_x0_xi,
+                          const double* d_xs_q_init, const double* d_xs_xi_init, const double* d_us_init, double* d_J_hist,
+                          double* d_grad_hist, double* d_defect_hist, double* d_alpha_hist, double* d_mu_hist, void* stream);
 int tolg_solve_iterate(tolg_handle_t h, int32_t n_iter, void* stream);
 int tolg_solve_end(tolg_handle_t h, double* d_xs_q, double* d_xs_xi, double* d_us, int32_t* d_iters,
                    int32_t* d_status, int32_t* d_converged, void* stream);
@@ -158,17 +167,24 @@ int tolg_solve_peek(tolg_handle_t h, double* d_xs_q, double* d_xs_xi, double* d_
  * TOLG_E_ARG: B < 1 or B > max_batch, refs_bytes < tolg_refs_bytes(prob, B), a solve in flight (between
  * tolg_solve_begin and tolg_solve_end).
  *
- * A receding-horizon loop (every trajectory its own window of a longer path):
- *   for each step t:
- *     pack the windows [t, t + N] of the B paths into d_q_ref / d_xi_ref
- *     tolg_set_refs(h, B, d_q_ref, d_xi_ref, d_refs, refs_bytes, stream);
- *     tolg_solve_begin(h, &opt, B, d_x0_q, d_x0_xi, d_us_warm, ...);   x0 = measured state, us_warm = last us shifted by one
- *     tolg_solve_iterate_until(h, opt.max_iter, opt.check_every, NULL, stream);
- *     tolg_solve_end(h, d_xs_q, d_xs_xi, d_us, d_iters, d_status, d_converged, stream);
- *     apply d_us[b][0], shift d_us into d_us_warm (repeat the last control) */
+ * tolg_set_ref_windows: the same packing, gathered from B longer paths d_path_q [B][T+1][16], d_path_xi [B][T+1][6]: knot i
+ * of trajectory b's reference is knot min(t0[b] + t + i, T) of its path -- past the end the last knot is held, so any T >= 1
+ * is accepted, T < N included.  d_t0 [B] (int32, on the device; NULL = 0) is each trajectory's phase on its path, t the
+ * step.  Afterwards the handle is exactly as after tolg_set_refs with the windows (same buffer size, same B rules).
+ * TOLG_E_ARG: those of tolg_set_refs, a NULL path, T < 1, t < 0.
+ *
+ * A receding-horizon (MPC) loop, every trajectory its own path and phase, with no host work per step:
+ *   tolg_solve_begin + iterations + tolg_solve_end once from (x0, us_init) on window 0, then for each step t:
+ *     tolg_mpc_advance(h, B, d_w_t, d_x_q, d_x_xi, d_u_t, d_xs_q_w, d_xs_xi_w, d_us_w, d_J_cl, stream);  apply u*_0, step
+ *     tolg_set_ref_windows(h, B, d_path_q, d_path_xi, T, d_t0, t + 1, d_refs, refs_bytes, stream);
+ *     tolg_solve_begin_warm(h, &opt, B, d_x_q, d_x_xi, d_xs_q_w, d_xs_xi_w, d_us_w, ...);     the shifted solution
+ *     tolg_solve_iterate_until(h, n, opt.check_every, NULL, stream);       check_every = 0: a fixed count, no host read
+ *     tolg_solve_end(h, d_xs_q, d_xs_xi, d_us, d_iters, d_status, d_converged, stream); */
 size_t tolg_refs_bytes(const tolg_problem* prob, int32_t max_batch);
 int tolg_set_refs(tolg_handle_t h, int32_t B, const double* d_q_ref, const double* d_xi_ref, void* d_refs, size_t refs_bytes,
                   void* stream);
+int tolg_set_ref_windows(tolg_handle_t h, int32_t B, const double* d_path_q, const double* d_path_xi, int32_t T,
+                         const int32_t* d_t0, int32_t t, void* d_refs, size_t refs_bytes, void* stream);
 
 /* Per-trajectory cost weights (diagonal Q, P, R; the reference tunes one controller's weights by hand).
  * tolg_weights_bytes: bytes of the caller-owned buffer that holds the packed weights of a batch of up to max_batch
@@ -253,9 +269,10 @@ int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, double* d_ecc
  *     about the iterate BEFORE the final one (the sweep of the last iteration produced the step to the final iterate);
  *   - tolg_linearize_backward: gains about exactly the trajectory it was given (the way to refresh the gains about the
  *     final iterate).
- * tolg_create and tolg_solve_begin clear it; so does tolg_eval_knot (it overwrites the nominal trajectory).  tolg_rollout
- * (writes the candidate arrays only), tolg_expected_change, tolg_set_al, tolg_al_update, tolg_set_refs and
- * tolg_set_weights leave it; the two calls below use the references and weights set when they run.
+ * tolg_create, tolg_solve_begin and tolg_solve_begin_warm clear it; so does tolg_eval_knot (it overwrites the nominal
+ * trajectory).  tolg_rollout (writes the candidate arrays only), tolg_expected_change, tolg_set_al, tolg_al_update,
+ * tolg_set_refs, tolg_set_ref_windows, tolg_set_weights and tolg_mpc_advance leave it; the calls that read it use the
+ * references and weights set when they run.
  * Both calls return TOLG_E_ARG when no policy is held, during a solve in flight, for a B other than the held batch's, when
  * references or weights per trajectory are set for another B, and (tolg_policy_rollout) for S < 1.  Neither modifies
  * the held policy: repeated calls give the same bits, and a later solve is unaffected.
@@ -277,6 +294,22 @@ int tolg_solve_gains(tolg_handle_t h, int32_t B, double* d_k, double* d_K, void*
  * A sample's bits depend on neither S nor the other samples. */
 int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w, double* d_J,
                         int32_t* d_status, double* d_xs_q, double* d_xs_xi, double* d_us, void* stream);
+
+/* tolg_mpc_advance: one receding-horizon step on the held policy x*, u* (after tolg_solve_end):
+ *   x_{t+1} = f(x*_0, u*_0) with the model's exact dynamics (whatever the solve's rollout option was), then xi_{t+1} += w[b]
+ *   (the noise convention of tolg_policy_rollout); d_u_applied = u*_0;
+ *   d_J_cl[b] += l(x*_0, u*_0): the stage cost at knot 0 of the current window, with trajectory b's reference and weights when
+ *   set, no augmented-Lagrangian terms;
+ *   the warm start of the next step in the caller layout, what tolg_solve_begin_warm reads: xs_warm[0] = x_{t+1},
+ *   xs_warm[i] = x*_{i+1} (1 <= i < N), xs_warm[N] = f(x*_N, u*_{N-1}); us_warm[i] = u*_{i+1} (i < N-1), us_warm[N-1] = u*_{N-1}.
+ *   in : d_w [B][6] or NULL (= 0)
+ *   out: d_x_next_q [B][16], d_x_next_xi [B][6], d_u_applied [B][m], d_J_cl [B] (accumulated): each may be NULL;
+ *        d_xs_q_warm [B][N+1][16], d_xs_xi_warm [B][N+1][6], d_us_warm [B][N][m]: required.
+ * It does not modify the held policy (a second call gives the same bits) and returns TOLG_E_ARG under the conditions of
+ * tolg_solve_gains, or for a NULL warm buffer. */
+int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, double* d_x_next_q, double* d_x_next_xi,
+                     double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl,
+                     void* stream);
 
 /* Timing hook for bench.py: HIP-event time (ms) and launch count of the dominant kernel
  * (backward sweep) accumulated since the last call with reset != 0.  Synchronises the recorded

@@ -1,0 +1,331 @@
+"""Receding-horizon MPC: warm-started begins (tolg_solve_begin_warm), reference windows of longer paths
+(tolg_set_ref_windows), the plant step and shift on the held policy (tolg_mpc_advance), and the loop of
+BatchedTrackingILQR.mpc.
+
+- a warm start from x0 + the reference is tolg_solve_begin bit for bit; one from a solution starts where linearize_backward
+  says it is, and a converged one stops at once;
+- the windows are tolg_set_refs on host-sliced windows, bit for bit (clamping, per-trajectory phase, T < N, B % 4 != 0);
+- the advance against the CPU oracle on every model; the loop against a step-by-step oracle restatement;
+- warm states on a feasible path, the argument rules, and the full size."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import bridge as ob
+from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, _capi, workloads
+from trajectory_optimization_matrix_lie_groups_amd.solver import mpc_shift, mpc_window_index
+from tests.test_gpu_policy import MODELS, _case, _op
+from tests.test_mpc_cpu import restate_mpc_step, window_problem
+
+pytestmark = pytest.mark.gpu
+
+ZERO = dict(tol_grad_norm=0.0, tol_d_norm=0.0)
+
+
+def _h(t):
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+def _rel(a, b):
+    a = np.asarray(a); b = np.asarray(b)
+    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+
+
+def _same(a, b):
+    return np.array_equal(_h(a), _h(b), equal_nan=True)
+
+
+def _ref_guess(prob, q, xi, q_ref=None, xi_ref=None):
+    """x0 followed by the reference knots: the initial guess tolg_solve_begin builds in multiple shooting."""
+    B = q.shape[0]
+    qr = np.broadcast_to(prob.q_ref, (B,) + prob.q_ref.shape) if q_ref is None else q_ref
+    xr = np.broadcast_to(prob.xi_ref, (B,) + prob.xi_ref.shape) if xi_ref is None else xi_ref
+    xs_q = np.array(qr, dtype=float); xs_xi = np.array(xr, dtype=float)
+    xs_q[:, 0] = np.asarray(q).reshape(B, 4, 4); xs_xi[:, 0] = xi
+    return xs_q, xs_xi
+
+
+# 1 -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("refs", ["shared", "per_trajectory"])
+@pytest.mark.parametrize("kw", [dict(), dict(line_search=True), dict(rollout="linear")], ids=["accept", "merit", "linear"])
+def test_warm_begin_from_the_reference_is_begin(kw, refs):
+    B = 6
+    if refs == "shared":
+        prob, q, xi, us = workloads.se3_tracking(B, N=40)
+        q_ref = xi_ref = None
+    else:
+        prob, q, xi, us, q_ref, xi_ref, _, _ = workloads.se3_multiref(B, 3, N=40)
+    xs = _ref_guess(prob, q, xi, q_ref, xi_ref)
+    xs[0][:, 0] = np.nan  # knot 0 of xs_init is not read
+    xs[1][:, 0] = np.nan
+    s = BatchedTrackingILQR(prob, B)
+    a = s.fit_batch(q, xi, us, mode="ms", n_iterations=8, check_every=0, q_ref=q_ref, xi_ref=xi_ref, **ZERO, **kw)
+    a = {f: getattr(a, f).clone() for f in ("J_hist", "grad_hist", "defect_hist", "xs_q", "xs_xi", "us", "iters", "status")}
+    b = s.fit_batch(q, xi, us, mode="ms", n_iterations=8, check_every=0, q_ref=q_ref, xi_ref=xi_ref, xs_init=xs, **ZERO, **kw)
+    for f in a:
+        assert _same(a[f], getattr(b, f)), f
+
+
+# 2 -------------------------------------------------------------------------------------------------------------------
+def _converged(B, N=40):
+    prob, q, xi, us = workloads.se3_tracking(B, N=N)
+    s = BatchedTrackingILQR(prob, B)
+    r = s.fit_batch(q, xi, us, mode="ms", n_iterations=300, tol_grad_norm=1e-6, tol_d_norm=1e-6)
+    c = np.flatnonzero(_h(r.converged))
+    assert len(c) >= 2
+    return prob, s, r.xs_q[c].clone(), r.xs_xi[c].clone(), r.us[c].clone()
+
+
+def test_warm_begin_from_a_converged_solution_starts_where_it_is_and_stops():
+    prob, s, xq, xx, uu = _converged(5)
+    B = xq.shape[0]
+    s = BatchedTrackingILQR(prob, B)
+    lb = s.linearize_backward(xq, xx, uu, ms=True)
+    lb = {k: _h(lb[k]).copy() for k in ("dnorm", "grad")}
+    w = s.fit_batch(xq[:, 0], xx[:, 0], uu, mode="ms", n_iterations=10, tol_grad_norm=1e-6, tol_d_norm=1e-6, check_every=1,
+                    xs_init=(xq, xx))
+    assert _rel(_h(w.defect_hist)[:, 0], lb["dnorm"]) < 1e-12
+    assert _rel(_h(w.grad_hist)[:, 0], lb["grad"]) < 1e-12
+    assert _h(w.converged).all() and (_h(w.iters) <= 1).all(), (_h(w.converged), _h(w.iters))
+    assert _rel(_h(w.xs_q), _h(xq)) < 1e-12 and _rel(_h(w.xs_xi), _h(xx)) < 1e-12 and _rel(_h(w.us), _h(uu)) < 1e-12
+
+
+def test_warm_begin_from_perturbed_states_starts_where_linearize_backward_says():
+    prob, s, xq, xx, uu = _converged(5)
+    B = xq.shape[0]
+    s = BatchedTrackingILQR(prob, B)
+    rng = np.random.default_rng(7)
+    pq, px = _h(xq).copy(), _h(xx).copy()
+    for b in range(B):
+        for i in range(1, prob.N + 1):
+            pq[b, i] = pq[b, i] @ ob.se3_exp(rng.normal(0, 0.02, 6))
+    px[:, 1:] += rng.normal(0, 0.02, px[:, 1:].shape)
+    lb = s.linearize_backward(pq, px, uu, ms=True)
+    lb = {k: _h(lb[k]).copy() for k in ("dnorm", "grad")}
+    w = s.fit_batch(pq[:, 0], px[:, 0], uu, mode="ms", n_iterations=1, check_every=0, xs_init=(pq, px), **ZERO)
+    assert _rel(_h(w.defect_hist)[:, 0], lb["dnorm"]) < 1e-12
+    assert _rel(_h(w.grad_hist)[:, 0], lb["grad"]) < 1e-12
+
+
+# 3 -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T", [50, 8])
+def test_windows_are_set_refs_on_host_slices(T):
+    B, N = 6, 20
+    prob, q, xi, us, q_ref, xi_ref, _, _ = workloads.se3_multiref(B, 3, N=60)
+    prob = TrackingProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref[:N + 1], prob.xi_ref[:N + 1])
+    pq, px = q_ref[:, :T + 1].copy(), xi_ref[:, :T + 1].copy()
+    t0 = np.array([0, 3, 17, 40, 1, 29], dtype=np.int32) % (T + 1)
+    s = BatchedTrackingILQR(prob, B)
+    n = (N + 1) * 13 * ((B + 3) // 4 * 4)
+    for t in (0, 3, 25):
+        s.set_ref_windows(pq, px, t, t0=t0)
+        a = s._refs_buf[:n].clone()
+        idx = mpc_window_index(t0, t, N, T)
+        s._use_refs(B, (pq[np.arange(B)[:, None], idx], px[np.arange(B)[:, None], idx]))
+        assert _same(a, s._refs_buf[:n]), t
+    # a solve on the windows: the bits of fit_batch on the host-sliced windows
+    got = {}
+    r = s.mpc(q, xi, pq, px, 1, t0=t0, first_iters=6, warm="controls", check_every=0, **ZERO,
+              on_step=lambda t, out: got.update(xs_q=out.xs_q.clone(), us=out.us.clone(), J_hist=out.J_hist.clone()))
+    idx = mpc_window_index(t0, 0, N, T)
+    f = s.fit_batch(q, xi, None, mode="ms", n_iterations=6, check_every=0, q_ref=pq[np.arange(B)[:, None], idx],
+                    xi_ref=px[np.arange(B)[:, None], idx], **ZERO)
+    for k in got:
+        assert _same(got[k], getattr(f, k)), k
+    assert _same(r.us[:, 0], f.us[:, 0])
+
+
+# 4 -------------------------------------------------------------------------------------------------------------------
+def _check_advance(s, r, ops, w):
+    B, N = r.us.shape[0], s.N
+    J1 = torch.zeros(B, dtype=torch.float64, device=s.device)
+    a = s.mpc_advance(w, J_cl=J1)
+    xq, xx, uu = _h(r.xs_q), _h(r.xs_xi), _h(r.us)
+    fin = [b for b in range(B) if np.isfinite(xq[b]).all() and np.isfinite(xx[b]).all() and np.isfinite(uu[b]).all()]
+    assert len(fin) >= B // 2
+    for b in fin:
+        op = ops[b]
+        q1, x1 = ob.f(op, xq[b, 0], xx[b, 0], uu[b, 0])
+        assert _rel(_h(a["x_next_q"])[b], q1) < 1e-13 and _rel(_h(a["x_next_xi"])[b], x1 + w[b]) < 1e-13
+        qN, xN = ob.f(op, xq[b, N], xx[b, N], uu[b, N - 1])
+        assert _rel(_h(a["xs_q"])[b, N], qN) < 1e-13 and _rel(_h(a["xs_xi"])[b, N], xN) < 1e-13
+        assert abs(_h(J1)[b] / ob.cost(op, xq[b, 0], xx[b, 0], uu[b, 0], 0)[0] - 1) < 1e-12
+    # the shift: bitwise the host shift of solve_end's output
+    sq, su = mpc_shift(xq, uu, _h(a["x_next_q"]), _h(a["xs_q"])[:, N])
+    sx, _ = mpc_shift(xx, uu, _h(a["x_next_xi"]), _h(a["xs_xi"])[:, N])
+    for k, host in (("xs_q", sq), ("xs_xi", sx), ("us", su)):
+        diff = ~np.equal(_h(a[k]), host) & ~(np.isnan(_h(a[k])) & np.isnan(host))
+        assert not diff.any(), (k, sorted(set(zip(*np.nonzero(diff)[:2])))[:10])
+    assert _same(a["u"], uu[:, 0])
+    # twice: the same bits, the policy untouched (J_cl accumulates)
+    b2 = s.mpc_advance(w, J_cl=J1)
+    for k in ("x_next_q", "x_next_xi", "u", "xs_q", "xs_xi", "us"):
+        assert _same(a[k], b2[k]), k
+    assert _rel(_h(J1)[fin], 2 * np.array([ob.cost(ops[b], xq[b, 0], xx[b, 0], uu[b, 0], 0)[0] for b in fin])) < 1e-12
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_advance_against_the_oracle(model):
+    B = 5
+    prob, q, xi, us = _case(model, B)
+    s = BatchedTrackingILQR(prob, B)
+    r = s.fit_batch(q, xi, us, mode="ms", n_iterations=8, **ZERO)
+    w = np.random.default_rng(3).normal(0, 0.01, (B, 6))
+    if model in ("so3", "pendulum"):
+        w[:, 3:] = 0.0  # the embedding's linear twist stays zero
+    _check_advance(s, r, [_op(prob)] * B, w)
+
+
+def test_advance_with_references_and_weights_per_trajectory():
+    B = 5
+    prob, q, xi, us, q_ref, xi_ref, _, _ = workloads.se3_multiref(B, 3, N=40)
+    _, _, _, _, Q, P, R, _, _ = workloads.se3_weight_sweep(B, 3, N=40)
+    s = BatchedTrackingILQR(prob, B)
+    r = s.fit_batch(q, xi, us, mode="ss", n_iterations=6, q_ref=q_ref, xi_ref=xi_ref, Q=Q, P=P, R=R, **ZERO)
+    w = np.random.default_rng(4).normal(0, 0.01, (B, 6))
+    _check_advance(s, r, [_op(prob, q_ref[b], xi_ref[b], Q[b], R[b], P[b]) for b in range(B)], w)
+
+
+# 5 -------------------------------------------------------------------------------------------------------------------
+def test_loop_against_the_oracle_step_by_step():
+    B, N, steps, K0, K = 8, 40, 6, 10, 3
+    prob, q, xi, pq, px, t0, noise = workloads.se3_mpc(B, steps, N=N, sigma_noise=0.02, seed=21)
+    s = BatchedTrackingILQR(prob, B)
+    seen = []
+    r = s.mpc(q, xi, pq, px, steps, t0=t0, first_iters=K0, iters_per_step=K, warm="controls", noise=noise, check_every=0,
+              **ZERO, on_step=lambda t, out: seen.append((t, _h(out.xs_q).copy(), _h(out.xs_xi).copy(), _h(out.us).copy(),
+                                                  _h(out.J_hist).copy())))
+    assert [t for t, *_ in seen] == list(range(steps))
+    rq, rx, ru, J = _h(r.xs_q), _h(r.xs_xi), _h(r.us), _h(r.J)
+    assert np.array_equal(rq[:, 0], q) and np.array_equal(rx[:, 0], xi)
+    Jcl = np.zeros(B)
+    for t, xs_q, xs_xi, us, Jh in seen:
+        us_in = np.zeros((B, N, prob.m)) if t == 0 else mpc_shift(seen[t - 1][1], seen[t - 1][3], rq[:, t], rq[:, t])[1]
+        assert np.array_equal(ru[:, t], us[:, 0])  # the applied input is the step's u*_0
+        for b in range(B):
+            op = window_problem(prob, pq[b], px[b], int(t0[b]), t)
+            o = restate_mpc_step(op, rq[b, t], rx[b, t], us_in[b], K0 if t == 0 else K)
+            assert np.abs(Jh[b] / o["J_hist"] - 1).max() < 1e-9, (t, b)
+            assert np.abs(us[b] - o["us"]).max() / np.abs(o["us"]).max() < 1e-6, (t, b)
+            # the closed-loop state is the advance's x_next: f(x*_0, u*_0) + noise
+            q1, x1 = ob.f(op, xs_q[b, 0], xs_xi[b, 0], us[b, 0])
+            assert _rel(rq[b, t + 1], q1) < 1e-13 and _rel(rx[b, t + 1], x1 + noise[b, t]) < 1e-13
+            Jcl[b] += ob.cost(op, xs_q[b, 0], xs_xi[b, 0], us[b, 0], 0)[0]
+    assert _rel(J, Jcl) < 1e-12
+    assert (_h(r.status) == _capi.ST_OK).all()
+    assert (_h(r.iters)[:, 0] == K0).all() and (_h(r.iters)[:, 1:] == K).all()
+
+
+# 6 -------------------------------------------------------------------------------------------------------------------
+def _feasible_paths(prob, B, T, seed=9):
+    """Open-loop rollouts of the model under smooth inputs: dynamically feasible paths [B, T+1]."""
+    op = _op(prob)
+    rng = np.random.default_rng(seed)
+    pq = np.zeros((B, T + 1, 4, 4)); px = np.zeros((B, T + 1, 6))
+    for b in range(B):
+        pq[b, 0] = prob.q_ref[0] @ ob.se3_exp(rng.normal(0, 0.3, 6))
+        px[b, 0] = prob.xi_ref[0] + rng.normal(0, 0.1, 6)
+        a, ph = rng.normal(0, 0.3, 6), rng.uniform(0, 2 * np.pi, 6)
+        for i in range(T):
+            u = a * np.sin(0.05 * i + ph)
+            pq[b, i + 1], px[b, i + 1] = ob.f(op, pq[b, i], px[b, i], u)
+    return pq, px
+
+
+def test_warm_states_on_a_feasible_path_converge_in_a_few_iterations_and_track():
+    B, N, steps, K = 4, 30, 8, 5
+    prob, _, _, _ = workloads.se3_tracking(1, N=N)
+    prob = TrackingProblem(prob.kind, prob.J, prob.dt, prob.Q, np.eye(6) * 1e-3, prob.P, prob.q_ref, prob.xi_ref)
+    pq, px = _feasible_paths(prob, B, N + steps)
+    tol = dict(tol_grad_norm=1e-6, tol_d_norm=1e-6)
+    s = BatchedTrackingILQR(prob, B)
+    conv = []
+    r = s.mpc(pq[:, 0], px[:, 0], pq, px, steps, first_iters=50, iters_per_step=K, warm="states", check_every=1,
+              on_step=lambda t, out: conv.append(_h(out.converged).copy()), **tol)
+    st, it = _h(r.status), _h(r.iters)
+    assert (st == _capi.ST_OK).all()
+    assert all(c.all() for c in conv[1:]) and (it[:, 1:] <= K).all()
+    # one full-horizon solve on the same path: its largest pose error sets the scale
+    f = s.fit_batch(pq[:, 0], px[:, 0], None, mode="ms", n_iterations=100, q_ref=pq[:, :N + 1], xi_ref=px[:, :N + 1], **tol)
+    e_full = np.linalg.norm(_h(f.xs_q)[:, :, :3, 3] - pq[:, :N + 1, :3, 3], axis=-1).max()
+    e_cl = np.linalg.norm(_h(r.xs_q)[:, :, :3, 3] - pq[:, :steps + 1, :3, 3], axis=-1).max()
+    assert e_full > 0 and e_cl <= 10 * e_full + 1e-9, (e_cl, e_full)
+
+
+# 7 -------------------------------------------------------------------------------------------------------------------
+def _raw_advance(s, B):
+    f64 = dict(dtype=torch.float64, device=s.device)
+    xq, xx, uu = torch.empty(B, s.N + 1, 16, **f64), torch.empty(B, s.N + 1, 6, **f64), torch.empty(B, s.N, s.m, **f64)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    return s.lib.tolg_mpc_advance(s._h, B, None, None, None, None, p(xq), p(xx), p(uu), None, s._stream())
+
+
+def test_argument_rules():
+    B, N, steps = 4, 20, 3
+    prob, q, xi, pq, px, t0, noise = workloads.se3_mpc(B, steps, N=N)
+    s = BatchedTrackingILQR(prob, B)
+    us = np.zeros((B, N, 6))
+    xs = _ref_guess(prob, q, xi)
+    bad = [dict(xs_init=(xs[0][:, :N], xs[1])), dict(xs_init=(xs[0], xs[1][:, :, :3])), dict(xs_init=xs[0]),
+           dict(xs_init=xs, mode="ss")]
+    for kw in bad:
+        with pytest.raises(ValueError):
+            s.fit_batch(q, xi, us, **{"mode": "ms", **kw})
+        with pytest.raises(ValueError):
+            s.solve_begin(q, xi, us, **{"mode": "ms", **kw})
+    for kw in [dict(path_q=pq[:, :, :3]), dict(path_xi=px[:, :-1]), dict(path_q=pq[:, :1], path_xi=px[:, :1]),
+               dict(noise=noise[:, :2]), dict(t0=t0[:2]), dict(t0=t0.astype(float)), dict(t0=-t0 - 1),
+               dict(warm="states", mode="ss"), dict(warm="bogus"), dict(steps=0), dict(us_init=us[:, :5])]:
+        a = dict(path_q=pq, path_xi=px, steps=steps, noise=noise, t0=t0)
+        a.update(kw)
+        with pytest.raises(ValueError):
+            s.mpc(q, xi, a.pop("path_q"), a.pop("path_xi"), a.pop("steps"), first_iters=2, iters_per_step=1, **a)
+    lam = torch.zeros(B, N, 12, dtype=torch.float64, device=s.device)
+    s.set_al(-np.ones(6), np.ones(6), lam, lam.clone())
+    with pytest.raises(ValueError):
+        s.mpc(q, xi, pq, px, steps)
+    s.set_al(None)
+    # tolg_mpc_advance: no held policy, a solve in flight, another B
+    assert _raw_advance(s, B) == -1
+    with pytest.raises(ValueError):
+        s.mpc_advance()
+    s.solve_begin(q, xi, us, mode="ms", n_iterations=2, **ZERO)
+    assert _raw_advance(s, B) == -1
+    s.solve_iterate(2)
+    s.solve_end()
+    assert _raw_advance(s, B - 1) == -1 and _raw_advance(s, B) == 0
+    with pytest.raises(ValueError):
+        s.mpc_advance(w=np.zeros((B, 5)))
+    # after mpc() the handle is on the shared reference: a batch of another size begins
+    s.mpc(q, xi, pq, px, steps, t0=t0, first_iters=3, iters_per_step=1, noise=noise)
+    assert not s._refs_set and not getattr(s, "_wts_set", False)
+    o = s._options("ms", 1, False, "nonlinear", 0.0, 0.0, 1e10)
+    out = s._alloc_result(B - 1, 1)
+    x0q, x0x = s._dev(q[:B - 1], (B - 1, 16)), s._dev(xi[:B - 1], (B - 1, 6))
+    u0 = torch.zeros(B - 1, N, 6, dtype=torch.float64, device=s.device)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = s.lib.tolg_solve_begin(s._h, C.byref(o), B - 1, p(x0q), p(x0x), p(u0), p(out.J_hist), p(out.grad_hist),
+                                p(out.defect_hist), p(out.alpha_hist), p(out.mu_hist), s._stream())
+    assert rc == 0
+    s._inflight = (out, (x0q, x0x, u0))
+    s.solve_iterate(1)
+    e = s.solve_end()
+    f = BatchedTrackingILQR(prob, B).fit_batch(q[:B - 1], xi[:B - 1], None, mode="ms", n_iterations=1, check_every=0, **ZERO)
+    assert _same(e.xs_q, f.xs_q) and _same(e.us, f.us)
+    # set_ref_windows: bad arguments
+    for a in [(pq, px, -1), (pq[:, :1], px[:, :1], 0), (pq, px[:, :-1], 0)]:
+        with pytest.raises(ValueError):
+            s.set_ref_windows(*a)
+
+
+# 8 -------------------------------------------------------------------------------------------------------------------
+def test_full_size():
+    B, N, steps = 4096, 200, 3
+    prob, q, xi, pq, px, t0, noise = workloads.se3_mpc(B, steps, N=N)
+    s = BatchedTrackingILQR(prob, B)
+    r = s.mpc(q, xi, pq, px, steps, t0=t0, first_iters=20, iters_per_step=3, warm="states", noise=noise, check_every=0, **ZERO)
+    assert (_h(r.status) == _capi.ST_OK).all()
+    for f in ("xs_q", "xs_xi", "us", "J"):
+        assert np.isfinite(_h(getattr(r, f))).all(), f

@@ -1,0 +1,127 @@
+"""Receding-horizon MPC (tolg_solve_begin_warm, tolg_set_ref_windows, tolg_mpc_advance, BatchedTrackingILQR.mpc): the parts
+that need no GPU -- the C ABI surface, the window and shift helpers, the workload, and the CPU restatement of one MPC loop that
+tests/test_gpu_mpc.py checks the device loop against."""
+import os
+import re
+
+import numpy as np
+
+from oracle import bridge as ob
+from trajectory_optimization_matrix_lie_groups_amd import _capi, workloads
+from trajectory_optimization_matrix_lie_groups_amd.solver import mpc_shift, mpc_window_index
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("tolg_solve_begin_warm", "tolg_set_ref_windows", "tolg_mpc_advance")
+
+
+def window_problem(prob, path_q, path_xi, t0, t, Q=None, R=None, P=None):
+    """The OracleProblem of one trajectory's window at step t: knots min(t0 + t + i, T) of its path."""
+    idx = mpc_window_index([t0], t, prob.N, path_q.shape[0] - 1)[0]
+    return ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q if Q is None else Q, prob.R if R is None else R,
+                            prob.P if P is None else P, path_q[idx], path_xi[idx], pend_mass=prob.pend_mass,
+                            pend_length=prob.pend_length)
+
+
+def restate_mpc_step(op, x_q, x_xi, us, iters):
+    """One step's solve on the CPU: multiple shooting, accept-always, a fixed iteration count (zero tolerances), from the
+    measured state and the shifted controls, the MS states from the reference window (warm="controls")."""
+    return ob.fit(op, np.asarray(x_q).reshape(16), x_xi, us, mode="ms", max_iter=iters, tol_grad=0.0, tol_defect=0.0)
+
+
+def restate_mpc(prob, x0_q, x0_xi, path_q, path_xi, steps, t0=0, us_init=None, first_iters=50, iters_per_step=5,
+                noise=None):
+    """One trajectory's MPC loop (warm="controls") from oracle primitives only (ob.fit, ob.f, ob.cost): at step t a solve
+    on the window, u_t = u*_0, J += l(x*_0, u*_0), x_{t+1} = f(x*_0, u*_0) + [0; noise[t]], the controls shifted by one
+    knot (the last held).  Returns dict xs_q [steps+1, 4, 4], xs_xi [steps+1, 6], us [steps, m], J."""
+    N, m = prob.N, prob.m
+    x_q, x_xi = np.asarray(x0_q, float).reshape(4, 4), np.asarray(x0_xi, float)
+    us = np.zeros((N, m)) if us_init is None else np.asarray(us_init, float)
+    xs_q = np.zeros((steps + 1, 4, 4)); xs_xi = np.zeros((steps + 1, 6)); ua = np.zeros((steps, m))
+    xs_q[0], xs_xi[0] = x_q, x_xi
+    J = 0.0
+    for t in range(steps):
+        op = window_problem(prob, path_q, path_xi, t0, t)
+        r = restate_mpc_step(op, x_q, x_xi, us, first_iters if t == 0 else iters_per_step)
+        u0 = r["us"][0]
+        J += ob.cost(op, r["xs_q"][0], r["xs_xi"][0], u0, 0)[0]
+        x_q, x_xi = ob.f(op, r["xs_q"][0], r["xs_xi"][0], u0)
+        if noise is not None:
+            x_xi = x_xi + noise[t]
+        _, us = mpc_shift(r["xs_q"][None], r["us"][None], x_q[None], x_q[None])
+        us = us[0]
+        ua[t], xs_q[t + 1], xs_xi[t + 1] = u0, x_q, x_xi
+    return dict(xs_q=xs_q, xs_xi=xs_xi, us=ua, J=J)
+
+
+def test_new_symbols_in_header_capi_and_library():
+    hdr = open(os.path.join(ROOT, "include", "tolg.h")).read()
+    lib = _capi.load()
+    for name in NEW:
+        assert re.search(r"\bint %s\(" % name, hdr), name
+        assert name in _capi.SYMBOLS
+        assert hasattr(lib, name)
+
+
+def test_null_handle_is_an_argument_error():
+    lib = _capi.load()
+    o = _capi.Options(_capi.MODE_MS, 5, 0, 0, 0.0, 0.0, 1e10, _capi.SCHED_AUTO, 0)
+    import ctypes as C
+    assert lib.tolg_solve_begin_warm(None, C.byref(o), 1, *([None] * 10), None) == -1
+    assert lib.tolg_solve_begin_warm(None, None, 1, *([None] * 10), None) == -1
+    assert lib.tolg_set_ref_windows(None, 1, None, None, 4, None, 0, None, 0, None) == -1
+    assert lib.tolg_mpc_advance(None, 1, *([None] * 8), None) == -1
+
+
+def test_window_index_hand_built():
+    idx = mpc_window_index([0, 3, 7], 2, 4, 8)
+    assert np.array_equal(idx, [[2, 3, 4, 5, 6], [5, 6, 7, 8, 8], [8, 8, 8, 8, 8]])
+    assert np.array_equal(mpc_window_index([0], 0, 4, 2), [[0, 1, 2, 2, 2]])  # T < N: the last knot held
+    assert np.array_equal(mpc_window_index([1, 0], 0, 2, 1), [[1, 1, 1], [0, 1, 1]])
+
+
+def test_shift_hand_built():
+    B, N, m = 2, 4, 3
+    xs = np.arange(B * (N + 1) * 2, dtype=float).reshape(B, N + 1, 2)
+    us = 100 + np.arange(B * N * m, dtype=float).reshape(B, N, m)
+    xn, xt = -np.ones((B, 2)), -2 * np.ones((B, 2))
+    xw, uw = mpc_shift(xs, us, xn, xt)
+    assert xw.shape == xs.shape and uw.shape == us.shape
+    for b in range(B):
+        assert np.array_equal(xw[b, 0], xn[b]) and np.array_equal(xw[b, N], xt[b])
+        assert np.array_equal(xw[b, 1:N], xs[b, 2:N + 1])
+        assert np.array_equal(uw[b, :N - 1], us[b, 1:]) and np.array_equal(uw[b, N - 1], us[b, N - 1])
+    xw, uw = mpc_shift(xs[:, :2], us[:, :1], xn, xt)  # N = 1: no interior knot, the one input held
+    assert np.array_equal(xw[:, 0], xn) and np.array_equal(xw[:, 1], xt) and np.array_equal(uw, us[:, :1])
+
+
+def test_mpc_workload_is_seeded_and_shaped():
+    a = workloads.se3_mpc(5, 6, N=20, seed=3)
+    b = workloads.se3_mpc(5, 6, N=20, seed=3)
+    prob, x0_q, x0_xi, pq, pxi, t0, noise = a
+    T = 26
+    assert prob.N == 20 and x0_q.shape == (5, 4, 4) and x0_xi.shape == (5, 6)
+    assert pq.shape == (5, T + 1, 4, 4) and pxi.shape == (5, T + 1, 6) and t0.shape == (5,) and noise.shape == (5, 6, 6)
+    assert t0.dtype == np.int32 and t0.min() >= 0 and t0.max() < T // 4
+    for x, y in zip(a[1:], b[1:]):
+        assert np.array_equal(x, y)
+    # each path is rigidly moved: the same body twists, and the poses one motion apart from the unmoved path
+    rel0 = np.linalg.inv(pq[0, 0]) @ pq[0]
+    for b_ in range(5):
+        assert np.array_equal(pxi[b_], pxi[0])
+        assert np.allclose(np.linalg.inv(pq[b_, 0]) @ pq[b_], rel0, atol=1e-9)
+
+
+def test_restatement_is_a_closed_loop_of_its_own_solves():
+    """The restated loop applies each step's u*_0 and steps the model from x*_0 = the measured state."""
+    prob, x0_q, x0_xi, pq, pxi, t0, noise = workloads.se3_mpc(1, 4, N=20, sigma_noise=0.02, seed=4)
+    r = restate_mpc(prob, x0_q[0], x0_xi[0], pq[0], pxi[0], 4, t0=int(t0[0]), first_iters=10, iters_per_step=3,
+                    noise=noise[0])
+    assert np.isfinite(r["J"]) and r["J"] > 0
+    for t in range(4):
+        op = window_problem(prob, pq[0], pxi[0], int(t0[0]), t)
+        q1, xi1 = ob.f(op, r["xs_q"][t], r["xs_xi"][t], r["us"][t])
+        assert np.abs(q1 - r["xs_q"][t + 1]).max() < 1e-12
+        assert np.abs(xi1 + noise[0, t] - r["xs_xi"][t + 1]).max() < 1e-12
+    # the tracking error shrinks from the perturbed start: the loop closes on the path
+    e = [np.linalg.norm(r["xs_q"][t][:3, 3] - pq[0, t0[0] + t][:3, 3]) for t in range(5)]
+    assert e[-1] < e[0]

@@ -27,7 +27,8 @@ _lib = None
 SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_batch", "tolg_solve_begin",
            "tolg_solve_iterate", "tolg_solve_iterate_until", "tolg_solve_end", "tolg_solve_peek", "tolg_solve_active_count", "tolg_set_al", "tolg_al_update",
            "tolg_refs_bytes", "tolg_set_refs", "tolg_weights_bytes", "tolg_set_weights", "tolg_eval_knot", "tolg_linearize_backward",
-           "tolg_rollout", "tolg_expected_change", "tolg_solve_gains", "tolg_policy_rollout", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
+           "tolg_rollout", "tolg_expected_change", "tolg_solve_gains", "tolg_policy_rollout",
+           "tolg_solve_begin_warm", "tolg_set_ref_windows", "tolg_mpc_advance", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
 
 
 def load():
@@ -87,6 +88,12 @@ def load():
     lib.tolg_solve_gains.argtypes = [vp, C.c_int32, dp, dp, vp]
     lib.tolg_policy_rollout.restype = C.c_int
     lib.tolg_policy_rollout.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, ip, dp, dp, dp, vp]
+    lib.tolg_solve_begin_warm.restype = C.c_int
+    lib.tolg_solve_begin_warm.argtypes = [vp, C.POINTER(Options), C.c_int32] + [dp] * 10 + [vp]
+    lib.tolg_set_ref_windows.restype = C.c_int
+    lib.tolg_set_ref_windows.argtypes = [vp, C.c_int32, dp, dp, C.c_int32, ip, C.c_int32, vp, C.c_size_t, vp]
+    lib.tolg_mpc_advance.restype = C.c_int
+    lib.tolg_mpc_advance.argtypes = [vp, C.c_int32] + [dp] * 8 + [vp]
     lib.tolg_kernel_time.restype = C.c_int
     lib.tolg_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int64)]

@@ -513,6 +513,32 @@ __global__ void k_pack_refs(int B, int Bp, int N, const double* __restrict__ q_r
   r[4 * (size_t)Bp] = X.t.x; r[5 * (size_t)Bp] = X.t.y; r[6 * (size_t)Bp] = X.t.z;
   for (int a = 0; a < 6; a++) r[(7 + a) * (size_t)Bp] = x[a];
 }
+// the same layout gathered from B longer paths [B][T+1][16] / [B][T+1][6] (tolg_set_ref_windows): knot i of trajectory b's
+// window is knot min(t0[b] + t + i, T) of its path (t0 = null: 0), the last knot held past the end.  The statements are
+// k_pack_refs's with the source knot moved, so that the matrix -> quaternion conversion compiles the same way and the windows
+// are the bits tolg_set_refs packs from host-sliced windows.
+__global__ void k_pack_ref_windows(int B, int Bp, int N, int T, const double* __restrict__ path_q,
+                                   const double* __restrict__ path_xi, const int* __restrict__ t0, int t,
+                                   double* __restrict__ refs) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (size_t)(N + 1) * Bp) return;
+  int b = (int)(g % Bp), i = (int)(g / Bp);
+  int bs = b < B ? b : B - 1;
+  long long k = (long long)(t0 ? t0[bs] : 0) + t + i;
+  k = k < 0 ? 0 : (k > T ? T : k);  // a negative phase reads knot 0 (the loads stay inside the path)
+  Pose X = pose_from_m16(path_q + ((size_t)bs * (T + 1) + (size_t)k) * 16);
+  const double* x = path_xi + ((size_t)bs * (T + 1) + (size_t)k) * 6;
+  double* r = refs + (size_t)i * 13 * Bp + b;
+  r[0] = X.q.x; r[Bp] = X.q.y; r[2 * (size_t)Bp] = X.q.z; r[3 * (size_t)Bp] = X.q.w;
+  r[4 * (size_t)Bp] = X.t.x; r[5 * (size_t)Bp] = X.t.y; r[6 * (size_t)Bp] = X.t.z;
+  for (int a = 0; a < 6; a++) r[(7 + a) * (size_t)Bp] = x[a];
+}
+
+// the per-trajectory scalars a solve starts from (k_init, k_init_warm)
+TOLG_DEV void init_scalars(const Params& P, int b) {
+  P.mu[b] = 1.0; P.delta[b] = 2.0; P.active[b] = 1; P.iters[b] = 0; P.status[b] = 0; P.conv[b] = 0;
+  P.grad[b] = 0; P.Jc[b] = 0; P.dn[b] = 0; P.ls_alpha[b] = 1.0; P.ls_accept[b] = -1; P.ls_slot[b] = -1;
+}
 
 // MS _initial_guess (traopt_controller.py:3123-3136): knot 0 = x0, knots 1..N = reference;
 // SS: only knot 0 (the rest comes from k_init_rollout).  Padded trajectories replicate b = B-1.
@@ -541,10 +567,28 @@ __global__ void k_init(Params P, const double* __restrict__ x0_q, const double* 
   if (i == 0 || ms) store_state(P, P.cur, i, b, S);
   if (i < P.N)
     for (int a = 0; a < P.m; a++) P.cur_u[UIDX(a, i, b)] = us_init[((size_t)bs * P.N + i) * P.m + a];
-  if (i == 0) {
-    P.mu[b] = 1.0; P.delta[b] = 2.0; P.active[b] = 1; P.iters[b] = 0; P.status[b] = 0; P.conv[b] = 0;
-    P.grad[b] = 0; P.Jc[b] = 0; P.dn[b] = 0; P.ls_alpha[b] = 1.0; P.ls_accept[b] = -1; P.ls_slot[b] = -1;
-  }
+  if (i == 0) init_scalars(P, b);
+}
+
+// The warm form of k_init (tolg_solve_begin_warm, MS only): knot 0 = x0, knots 1..N from the caller's xs_init [B][N+1] (its
+// knot 0 is not read).  It reads no reference, so one kernel serves every kernel table.
+__global__ void k_init_warm(Params P, const double* __restrict__ x0_q, const double* __restrict__ x0_xi,
+                            const double* __restrict__ xs_q, const double* __restrict__ xs_xi, const double* __restrict__ us_init) {
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)(P.N + 1) * P.Bp) return;
+  int b = (int)(t % P.Bp), i = (int)(t / P.Bp);
+  int bs = b < P.B ? b : P.B - 1;
+  const size_t k = (size_t)bs * (P.N + 1) + i;
+  const double* q = i == 0 ? x0_q + 16 * (size_t)bs : xs_q + 16 * k;
+  const double* x = i == 0 ? x0_xi + 6 * (size_t)bs : xs_xi + 6 * k;
+  State S;
+  S.X = pose_from_m16(q);
+  S.w = v3(x[0], x[1], x[2]);
+  S.v = v3(x[3], x[4], x[5]);
+  store_state(P, P.cur, i, b, S);
+  if (i < P.N)
+    for (int a = 0; a < P.m; a++) P.cur_u[UIDX(a, i, b)] = us_init[((size_t)bs * P.N + i) * P.m + a];
+  if (i == 0) init_scalars(P, b);
 }
 
 // arbitrary trajectories in (unit-parity entry points)
@@ -584,6 +628,26 @@ __global__ void k_unpack_traj(Params P, const double* __restrict__ s, const doub
   }
   if (us && i < P.N)
     for (int a = 0; a < P.m; a++) us[((size_t)b * P.N + i) * P.m + a] = su[UIDX(a, i, b)];
+}
+
+// The interior of tolg_mpc_advance's warm start, the held trajectory shifted by one knot: xs_warm[i] = x*_{i+1} (0 < i < N),
+// us_warm[i] = u*_{i+1} with the last input held; one thread per (knot i < N, trajectory).  The statements are those of
+// k_unpack_traj, block for block, with the source knot moved by one: the compiler decides FP contraction from the blocks it
+// sees, and only this shape has been seen to give the quaternion -> matrix conversion of solve_end's export bit for bit.
+__global__ void k_mpc_shift(Params P, const double* __restrict__ s, const double* __restrict__ su, double* __restrict__ xs_q,
+                            double* __restrict__ xs_xi, double* __restrict__ us) {
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)P.N * P.Bp) return;
+  int b = (int)(t % P.Bp), i = (int)(t / P.Bp);
+  if (b >= P.B) return;
+  State S = load_state(P, s, i + 1, b);
+  if (xs_q && i > 0) pose_to_m16(S.X, xs_q + ((size_t)b * (P.N + 1) + i) * 16);
+  if (xs_xi && i > 0) {
+    double* x = xs_xi + ((size_t)b * (P.N + 1) + i) * 6;
+    x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z;
+  }
+  if (us)
+    for (int a = 0; a < P.m; a++) us[((size_t)b * P.N + i) * P.m + a] = su[UIDX(a, i + 1 < P.N ? i + 1 : P.N - 1, b)];
 }
 
 // SS _init_rollout (traopt_controller.py:2015-2028): x_{i+1} = f(x_i, u_i), one thread per trajectory
@@ -2883,6 +2947,45 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
   }
 }
 
+// One receding-horizon step on the held policy (tolg_mpc_advance), the two ends of the warm start: one thread per (end,
+// trajectory b), b fastest.  End 0 steps the plant, x_{t+1} = f(x*_0, u*_0) with the exact dynamics (the dyn_f_k step of the
+// rollouts), adds the twist disturbance and the stage cost l(x*_0, u*_0), and writes xs_warm[0] = x_{t+1}; end 1 propagates
+// the tail, xs_warm[N] = f(x*_N, u*_{N-1}).  k_mpc_shift writes the rest.  Reads the held policy only: calling it again gives
+// the same bits.  No LDS, no cross-lane operation.
+template <int M, int PK, int PT>
+__global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __restrict__ w, double* __restrict__ x_next_q,
+                                                     double* __restrict__ x_next_xi, double* __restrict__ u_applied,
+                                                     double* __restrict__ xs_q, double* __restrict__ xs_xi,
+                                                     double* __restrict__ J_cl) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= 2 * (size_t)P.B) return;
+  const int N = P.N, b = (int)(g % P.B), i = g < (size_t)P.B ? 0 : N;
+  const Consts& C = *P.c;
+  const DynK DK = dynk_load(C);
+  const State Sx = load_state(P, P.cur, i, b);
+  double u[M];
+#pragma unroll
+  for (int a = 0; a < M; a++) u[a] = P.cur_u[UIDX(a, i == 0 ? 0 : N - 1, b)];
+  State S = dyn_f_k<M, Consts, PK>(DK, C, Sx, u);
+  if (i == 0) {
+    if (w) {
+      const double* d = w + 6 * (size_t)b;
+      S.w = S.w + v3(d[0], d[1], d[2]);
+      S.v = S.v + v3(d[3], d[4], d[5]);
+    }
+    if (x_next_q) pose_to_m16(S.X, x_next_q + 16 * (size_t)b);
+    if (x_next_xi) { double* x = x_next_xi + 6 * (size_t)b; x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z; }
+    if (u_applied)
+#pragma unroll
+      for (int a = 0; a < M; a++) u_applied[(size_t)b * M + a] = u[a];
+    if (J_cl) J_cl[b] += knot_cost<M, false, PT>(P, C, 0, b, Sx, u, false);
+  }
+  const size_t k = (size_t)b * (N + 1) + i;
+  pose_to_m16(S.X, xs_q + 16 * k);
+  double* x = xs_xi + 6 * k;
+  x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z;
+}
+
 // ---- line-search stages, round 3 form -----------------------------------------------------------------------------
 // A stage is three launches: (1) k_rollout_ls -- the closed-loop rollouts alone, the quad form of K3 (roll_step with
 // STORE), one quad per (undecided trajectory, alpha), the undecided trajectories taken from a compacted list so that a
@@ -3776,6 +3879,7 @@ typedef void (*SearchKernel)(Params, int, int, int);
 typedef void (*SearchRollout)(Params, int, int, int, int);
 struct KernelTable {
   void (*init)(Params, const double*, const double*, const double*, int);  // k_init
+  void (*init_warm)(Params, const double*, const double*, const double*, const double*, const double*);  // k_init_warm
   void (*linearize)(Params, const double*, const double*, double*, double*, int, int, int, int, int);  // K1
   void (*init_rollout)(Params);
   void (*sweep[2][2])(Params, int, int);  // K2 [fast][AL terms]
@@ -3787,6 +3891,7 @@ struct KernelTable {
   void (*ec_stmt[2])(Params);        //                  statement form [REDO]
   void (*affine_commit)(Params, int, int);
   void (*policy_rollout)(Params, int, int, const double*, const double*, double*, int*, double*, double*, double*);  // tolg_policy_rollout
+  void (*mpc_advance)(Params, const double*, double*, double*, double*, double*, double*, double*);  // tolg_mpc_advance (+ k_mpc_shift)
   struct Search {                    // per search kind: ls[0] backtracking (single shooting), ls[1] merit (multiple shooting)
     struct { SearchRollout k; int nt; } wave2[2];  // k_rollout_ls2 [first try] and its NT (twist waves per pose wave)
     SearchRollout wave1[2];          // the one-wave forms k_rollout_ls [linear]
@@ -3822,6 +3927,7 @@ static KernelTable kernel_table(int lds_per_block) {
   constexpr bool PTREF = (PT & PT_REF) != 0, PTW = (PT & PT_W) != 0;
   KernelTable t;
   t.init = k_init<PTREF>;
+  t.init_warm = k_init_warm;
   t.linearize = k_linearize<M, PT>;
   t.init_rollout = k_init_rollout<M>;
   if constexpr (!DENSE && !PEND) {
@@ -3847,6 +3953,7 @@ static KernelTable kernel_table(int lds_per_block) {
   t.ec_stmt[1] = k_expected_change<M, PK, true, PTW>;
   t.affine_commit = k_affine_commit<M>;
   t.policy_rollout = k_policy_rollout<M, PK, PT>;
+  t.mpc_advance = k_mpc_advance<M, PK, PT>;
   t.ls[0] = search_kernels<M, false, PK, PT>();
   t.ls[1] = search_kernels<M, true, PK, PT>();
   return t;
@@ -3884,7 +3991,7 @@ struct tolg_handle_s {
   const double* wts = nullptr;   // tolg_set_weights: the packed per-trajectory weights (caller-owned), or null
   int wts_B = 0;                 // ... and their batch, as refs_B
   // The held policy (tolg_solve_gains, tolg_policy_rollout): nominal trajectory P.cur / P.cur_u and gains P.GK of a batch of
-  // pol_B trajectories, 0 = none.  Set by tolg_solve_end and tolg_linearize_backward; cleared by tolg_solve_begin and
+  // pol_B trajectories, 0 = none.  Set by tolg_solve_end and tolg_linearize_backward; cleared by tolg_solve_begin(_warm) and
   // tolg_eval_knot (k_probe_pack writes P.cur); tolg_rollout (writes the candidate arrays) and tolg_expected_change (ED, ecc)
   // leave it.
   int pol_B = 0;
@@ -4499,15 +4606,18 @@ static int iterate_ss(tolg_handle_s* h, const Params& P, const tolg_options* opt
   return 0;
 }
 
-extern "C" int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_t B, const double* d_x0_q,
-                                const double* d_x0_xi, const double* d_us_init, double* d_J_hist,
-                                double* d_grad_hist, double* d_defect_hist, double* d_alpha_hist, double* d_mu_hist,
-                                void* stream) {
+// tolg_solve_begin and tolg_solve_begin_warm: d_xs_q / d_xs_xi non-null (MS only) take knots 1..N of the initial guess from
+// the caller (k_init_warm) in place of the reference (k_init); everything behind the initial guess is the same
+static int solve_begin(tolg_handle_t h, const tolg_options* opt, int32_t B, const double* d_x0_q, const double* d_x0_xi,
+                       const double* d_xs_q, const double* d_xs_xi, const double* d_us_init, double* d_J_hist,
+                       double* d_grad_hist, double* d_defect_hist, double* d_alpha_hist, double* d_mu_hist, void* stream) {
   if (!h || !opt || B < 1 || B > h->max_batch || !d_x0_q || !d_x0_xi || !d_us_init) return TOLG_E_ARG;
   if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;
   if (opt->max_iter < 0) return TOLG_E_ARG;
   if (opt->mode != TOLG_MODE_MS && opt->mode != TOLG_MODE_SS) return TOLG_E_ARG;
   const int ms = opt->mode == TOLG_MODE_MS;
+  if (ms && d_xs_q && !d_xs_xi) return TOLG_E_ARG;
+  const bool warm = ms && d_xs_q;
   hipStream_t st = static_cast<hipStream_t>(stream);
   h->pol_B = 0;  // the solve overwrites trajectory and gains
   Params P = params_for(h, B);
@@ -4518,7 +4628,11 @@ extern "C" int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_
   // TOLG_SCHED_SPLIT keeps the statement-form rollouts for every trajectory (the A/B partner in the tests)
   P.affine = (opt->rollout_linear && opt->schedule != TOLG_SCHED_SPLIT) ? 1 : 0;
   size_t n = (size_t)(P.N + 1) * P.Bp;
-  hipLaunchKernelGGL(h->kt.init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, d_x0_q, d_x0_xi, d_us_init, ms);
+  if (warm)
+    hipLaunchKernelGGL(h->kt.init_warm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, d_x0_q, d_x0_xi, d_xs_q, d_xs_xi,
+                       d_us_init);
+  else
+    hipLaunchKernelGGL(h->kt.init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, d_x0_q, d_x0_xi, d_us_init, ms);
   LAUNCH_CHECK();
   if (!ms) {  // SS: dynamically feasible initial trajectory (_init_rollout, traopt_controller.py:2015-2028)
     hipLaunchKernelGGL(h->kt.init_rollout, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
@@ -4530,6 +4644,21 @@ extern "C" int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_
   LAUNCH_CHECK();
   h->run = P; h->run_opt = *opt; h->run_it = 0; h->running = true;
   return 0;
+}
+extern "C" int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_t B, const double* d_x0_q,
+                                const double* d_x0_xi, const double* d_us_init, double* d_J_hist,
+                                double* d_grad_hist, double* d_defect_hist, double* d_alpha_hist, double* d_mu_hist,
+                                void* stream) {
+  return solve_begin(h, opt, B, d_x0_q, d_x0_xi, nullptr, nullptr, d_us_init, d_J_hist, d_grad_hist, d_defect_hist,
+                     d_alpha_hist, d_mu_hist, stream);
+}
+extern "C" int tolg_solve_begin_warm(tolg_handle_t h, const tolg_options* opt, int32_t B, const double* d_x0_q,
+                                     const double* d_x0_xi, const double* d_xs_q_init, const double* d_xs_xi_init,
+                                     const double* d_us_init, double* d_J_hist, double* d_grad_hist, double* d_defect_hist,
+                                     double* d_alpha_hist, double* d_mu_hist, void* stream) {
+  if (opt && opt->mode == TOLG_MODE_MS && (!d_xs_q_init || !d_xs_xi_init)) return TOLG_E_ARG;
+  return solve_begin(h, opt, B, d_x0_q, d_x0_xi, d_xs_q_init, d_xs_xi_init, d_us_init, d_J_hist, d_grad_hist, d_defect_hist,
+                     d_alpha_hist, d_mu_hist, stream);
 }
 
 extern "C" int tolg_solve_iterate(tolg_handle_t h, int32_t n_iter, void* stream) {
@@ -4674,6 +4803,21 @@ extern "C" int tolg_set_refs(tolg_handle_t h, int32_t B, const double* d_q_ref, 
   const size_t n = (size_t)(N + 1) * Bp;
   hipLaunchKernelGGL(k_pack_refs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp, N,
                      d_q_ref, d_xi_ref, static_cast<double*>(d_refs));
+  LAUNCH_CHECK();
+  h->refs = static_cast<const double*>(d_refs); h->refs_B = B; h->kt = h->kt_pt[PT_REF | (h->wts ? PT_W : 0)];
+  return 0;
+}
+
+extern "C" int tolg_set_ref_windows(tolg_handle_t h, int32_t B, const double* d_path_q, const double* d_path_xi, int32_t T,
+                                    const int32_t* d_t0, int32_t t, void* d_refs, size_t refs_bytes, void* stream) {
+  if (!h || h->running || !d_path_q || !d_path_xi || T < 1 || t < 0) return TOLG_E_ARG;
+  if (B < 1 || B > h->max_batch || !d_refs || (reinterpret_cast<uintptr_t>(d_refs) & 7) != 0) return TOLG_E_ARG;
+  if (refs_bytes < refs_bytes_for(&h->prob, B)) return TOLG_E_ARG;
+  if (h->wts && B != h->wts_B) return TOLG_E_ARG;
+  const int N = h->prob.N, Bp = (B + 3) / 4 * 4;
+  const size_t n = (size_t)(N + 1) * Bp;
+  hipLaunchKernelGGL(k_pack_ref_windows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B,
+                     Bp, N, (int)T, d_path_q, d_path_xi, reinterpret_cast<const int*>(d_t0), (int)t, static_cast<double*>(d_refs));
   LAUNCH_CHECK();
   h->refs = static_cast<const double*>(d_refs); h->refs_B = B; h->kt = h->kt_pt[PT_REF | (h->wts ? PT_W : 0)];
   return 0;
@@ -4856,6 +5000,23 @@ extern "C" int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const 
   P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // J is the tracking cost: no augmented-Lagrangian terms
   hipLaunchKernelGGL(h->kt.policy_rollout, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P, (int)S,
                      h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, double* d_x_next_q, double* d_x_next_xi,
+                                double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm,
+                                double* d_J_cl, void* stream) {
+  if (!policy_ok(h, B) || !d_xs_q_warm || !d_xs_xi_warm || !d_us_warm) return TOLG_E_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Params P = params_for(h, B);
+  P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // the stage cost is the tracking cost: no augmented-Lagrangian terms
+  const size_t n = (size_t)P.N * P.Bp;
+  hipLaunchKernelGGL(k_mpc_shift, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, P.cur, P.cur_u, d_xs_q_warm,
+                     d_xs_xi_warm, d_us_warm);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(h->kt.mpc_advance, dim3((unsigned)((2 * (size_t)B + 255) / 256)), dim3(256), 0, st, P, d_w, d_x_next_q,
+                     d_x_next_xi, d_u_applied, d_xs_q_warm, d_xs_xi_warm, d_J_cl);
   LAUNCH_CHECK();
   return 0;
 }

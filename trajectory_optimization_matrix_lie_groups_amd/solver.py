@@ -91,6 +91,33 @@ class PolicyRollout:
     us: Optional[torch.Tensor] = None     # [B, S, N, m]
 
 
+@dataclass
+class MPCResult:
+    """`steps` closed-loop receding-horizon steps of B trajectories (BatchedTrackingILQR.mpc)."""
+    xs_q: torch.Tensor     # [B, steps+1, 4, 4] closed-loop states: x0, then the plant state after every step
+    xs_xi: torch.Tensor    # [B, steps+1, 6]
+    us: torch.Tensor       # [B, steps, m] the applied inputs u*_0 of every step
+    J: torch.Tensor        # [B] closed-loop cost: the sum of the stage costs l(x_t, u_t) against each step's window
+    iters: torch.Tensor    # [B, steps] int32: iterations of each step's solve
+    status: torch.Tensor   # [B, steps] int32: its status
+
+
+def mpc_window_index(t0, t, N, T):
+    """Knot of the path that knot i of step t's window tracks (tolg_set_ref_windows): min(t0[b] + t + i, T), [B, N+1]."""
+    t0 = np.asarray(t0, dtype=np.int64).reshape(-1)
+    return np.clip(t0[:, None] + int(t) + np.arange(N + 1)[None, :], 0, int(T))
+
+
+def mpc_shift(xs, us, x_next, x_tail):
+    """The warm start tolg_mpc_advance builds, on the host: xs [B, N+1, ...], us [B, N, m] a step's solution, x_next [B, ...]
+    the plant's next state, x_tail [B, ...] = f(x*_N, u*_{N-1}).  Returns (xs_warm, us_warm): xs_warm[0] = x_next,
+    xs_warm[i] = xs[i+1] (1 <= i < N), xs_warm[N] = x_tail; us_warm[i] = us[i+1], the last input held."""
+    xs, us = np.asarray(xs), np.asarray(us)
+    xs_w = np.concatenate([np.asarray(x_next)[:, None], xs[:, 2:], np.asarray(x_tail)[:, None]], axis=1)
+    us_w = np.concatenate([us[:, 1:], us[:, -1:]], axis=1)
+    return xs_w, us_w
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
@@ -261,18 +288,21 @@ class BatchedTrackingILQR:
     def solve_begin(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
                     tol_d_norm=1e-6, line_search=False, rollout="nonlinear", max_reg=1e10, histories=True,
                     out: Optional[FitResult] = None, schedule="auto", q_ref=None, xi_ref=None, Q=None, P=None,
-                    R=None) -> FitResult:
+                    R=None, xs_init=None) -> FitResult:
         """_initial_guess + first _linearization; leaves the batch resident in HBM.
         schedule: "auto" (rollout and re-linearisation fused in one launch where the mode allows it) or
         "split" (separate launches); launch structure only, same algorithm.
         q_ref [B, N+1, 4, 4], xi_ref [B, N+1, 6] (optional): trajectory b tracks its own reference in this solve
         (tolg_set_refs); omitted, the problem's shared reference.
         Q [B, 12, 12], P [B, 12, 12], R [B, m, m] (optional, all three or none, diagonal): trajectory b's cost weights in this
-        solve (tolg_set_weights); omitted, the problem's shared weights."""
+        solve (tolg_set_weights); omitted, the problem's shared weights.
+        xs_init (optional, multiple shooting only): (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6]), a warm start of the shooting
+        states (tolg_solve_begin_warm): knots 1..N of the initial guess in place of the reference; knot 0 is x0."""
         x0_q = self._dev(x0_q, (-1, 16))
         B = x0_q.shape[0]
         refs = self._check_refs(B, q_ref, xi_ref)
         wts = self._check_weights(B, Q, P, R)
+        xs = self._check_xs_init(B, xs_init, mode)
         x0_xi = self._dev(x0_xi, (B, 6))
         if us_init is None:
             us_init = torch.zeros(B, self.N, self.m, dtype=torch.float64, device=self.device)
@@ -280,18 +310,49 @@ class BatchedTrackingILQR:
         K = int(n_iterations)
         if out is None:
             out = self._alloc_result(B, K, histories)
-        o = _capi.Options(_capi.MODE_MS if mode == "ms" else _capi.MODE_SS, K, int(bool(line_search)),
-                          int(rollout == "linear"), float(tol_grad_norm), float(tol_d_norm),
-                          float(max_reg if max_reg else 0.0),
-                          {"auto": _capi.SCHED_AUTO, "split": _capi.SCHED_SPLIT}[schedule], 0)
+        o = self._options(mode, K, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg, schedule)
         self._use_pt(B, refs, wts)
+        return self._begin(o, B, x0_q, x0_xi, us_init, xs, out)
+
+    def _options(self, mode, K, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg, schedule="auto", check_every=0):
+        return _capi.Options(_capi.MODE_MS if mode == "ms" else _capi.MODE_SS, int(K), int(bool(line_search)),
+                             int(rollout == "linear"), float(tol_grad_norm), float(tol_d_norm),
+                             float(max_reg if max_reg else 0.0),
+                             {"auto": _capi.SCHED_AUTO, "split": _capi.SCHED_SPLIT}[schedule], int(check_every))
+
+    def _check_xs_init(self, B, xs_init, mode):
+        """xs_init = (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6]) checked on the host (ValueError before anything reaches the
+        device) and moved there as [B, N+1, 16] / [B, N+1, 6]; None when omitted."""
+        if xs_init is None:
+            return None
+        if mode != "ms":
+            raise ValueError("xs_init warm-starts the shooting states of multiple shooting: single shooting takes its states "
+                             "from the initial rollout")
+        if not isinstance(xs_init, (tuple, list)) or len(xs_init) != 2:
+            raise ValueError("xs_init is a pair (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6])")
+        q, xi = xs_init
+        qs, xs = tuple(np.shape(q)), tuple(np.shape(xi))
+        if qs != (B, self.N + 1, 4, 4):
+            raise ValueError("xs_init[0] has shape %s, expected (%d, %d, 4, 4)" % (qs, B, self.N + 1))
+        if xs != (B, self.N + 1, 6):
+            raise ValueError("xs_init[1] has shape %s, expected (%d, %d, 6)" % (xs, B, self.N + 1))
+        return self._dev(q, (B, self.N + 1, 16)), self._dev(xi, (B, self.N + 1, 6))
+
+    def _begin(self, o, B, x0_q, x0_xi, us_init, xs, out):
+        """tolg_solve_begin, or tolg_solve_begin_warm when xs = (xs_q, xs_xi) is given (device tensors, checked)."""
         with torch.cuda.device(self.device):
-            rc = self.lib.tolg_solve_begin(self._h, C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(us_init),
-                                           _ptr(out.J_hist), _ptr(out.grad_hist), _ptr(out.defect_hist),
-                                           _ptr(out.alpha_hist), _ptr(out.mu_hist), self._stream())
+            if xs is None:
+                rc = self.lib.tolg_solve_begin(self._h, C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(us_init),
+                                               _ptr(out.J_hist), _ptr(out.grad_hist), _ptr(out.defect_hist),
+                                               _ptr(out.alpha_hist), _ptr(out.mu_hist), self._stream())
+            else:
+                rc = self.lib.tolg_solve_begin_warm(self._h, C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(xs[0]), _ptr(xs[1]),
+                                                    _ptr(us_init), _ptr(out.J_hist), _ptr(out.grad_hist),
+                                                    _ptr(out.defect_hist), _ptr(out.alpha_hist), _ptr(out.mu_hist),
+                                                    self._stream())
         self._policy_B = 0  # the solve overwrites the held policy (also when it could not start)
-        _capi.check(rc, "tolg_solve_begin")
-        self._inflight = (out, (x0_q, x0_xi, us_init))  # keep the inputs alive until the stream has used them
+        _capi.check(rc, "tolg_solve_begin_warm" if xs is not None else "tolg_solve_begin")
+        self._inflight = (out, (x0_q, x0_xi, us_init, xs))  # keep the inputs alive until the stream has used them
         return out
 
     def solve_iterate(self, n_iter):
@@ -339,7 +400,7 @@ class BatchedTrackingILQR:
     def fit_batch(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
                   tol_d_norm=1e-6, line_search=False, rollout="nonlinear", max_reg=1e10,
                   histories=True, out: Optional[FitResult] = None, schedule="auto", check_every=16, q_ref=None,
-                  xi_ref=None, Q=None, P=None, R=None) -> FitResult:
+                  xi_ref=None, Q=None, P=None, R=None, xs_init=None) -> FitResult:
         """B independent fits (the reference's joblib fan-out, visualization/perturb_all_compute.py:240).
         Inputs may be numpy arrays or tensors already on the device; outputs are device tensors.
         The iterations are issued in slices of `check_every`; behind each slice the number of trajectories still
@@ -347,9 +408,10 @@ class BatchedTrackingILQR:
         exit of traopt_controller.py:2528-2532 for the whole batch).  check_every=0, or tolerances of zero, issue
         all n_iterations without a host read.  `iterations_issued` keeps how many were queued.
         q_ref [B, N+1, 4, 4], xi_ref [B, N+1, 6] (optional, numpy or torch): a reference per trajectory for this fit.
-        Q [B, 12, 12], P [B, 12, 12], R [B, m, m] (optional, all three or none, diagonal): cost weights per trajectory."""
+        Q [B, 12, 12], P [B, 12, 12], R [B, m, m] (optional, all three or none, diagonal): cost weights per trajectory.
+        xs_init (optional, mode="ms"): warm-start shooting states, as for solve_begin."""
         self.solve_begin(x0_q, x0_xi, us_init, mode, n_iterations, tol_grad_norm, tol_d_norm, line_search, rollout,
-                         max_reg, histories, out, schedule, q_ref, xi_ref, Q, P, R)
+                         max_reg, histories, out, schedule, q_ref, xi_ref, Q, P, R, xs_init)
         self.iterations_issued = self.solve_iterate_until(int(n_iterations), int(check_every or 0))
         return self.solve_end()
 
@@ -595,6 +657,164 @@ class BatchedTrackingILQR:
         _capi.check(rc, "tolg_policy_rollout")
         self._policy_keep = (d_dx0, d_w)  # the kernel reads them on the stream
         return r
+
+    # ------------------------------------------------------------------------------------------
+    def _check_paths(self, B, path_q, path_xi):
+        """Paths [B, T+1, 4, 4] / [B, T+1, 6] checked on the host and moved to the device as [B, T+1, 16] / [B, T+1, 6];
+        returns (q, xi, T)."""
+        qs, xs = tuple(np.shape(path_q)), tuple(np.shape(path_xi))
+        if len(qs) != 4 or qs[0] != B or qs[2:] != (4, 4) or qs[1] < 2:
+            raise ValueError("path_q has shape %s, expected (%d, T+1, 4, 4) with T >= 1" % (qs, B))
+        if xs != (B, qs[1], 6):
+            raise ValueError("path_xi has shape %s, expected (%d, %d, 6)" % (xs, B, qs[1]))
+        return self._dev(path_q, (B, qs[1], 16)), self._dev(path_xi, (B, qs[1], 6)), qs[1] - 1
+
+    def _check_t0(self, B, t0):
+        if t0 is None:
+            return None
+        a = t0.detach().cpu().numpy() if isinstance(t0, torch.Tensor) else np.asarray(t0)
+        if a.shape != (B,) or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("t0 must be an integer array of shape (%d,)" % B)
+        if (a < 0).any() or (a > np.iinfo(np.int32).max).any():
+            raise ValueError("t0 must be non-negative int32")
+        return torch.as_tensor(a.astype(np.int32), device=self.device)
+
+    def _set_ref_windows(self, B, q, xi, T, t0_d, t):
+        if getattr(self, "_refs_buf", None) is None:
+            nbytes = int(self.lib.tolg_refs_bytes(C.byref(self._p), self.max_batch))
+            self._refs_buf = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tolg_set_ref_windows(self._h, B, _ptr(q), _ptr(xi), int(T), _ptr(t0_d), int(t), _ptr(self._refs_buf),
+                                               C.c_size_t(self._refs_buf.numel() * 8), self._stream())
+        _capi.check(rc, "tolg_set_ref_windows")
+        self._refs_set = True
+        self._windows_keep = (q, xi, t0_d)  # the gather kernel reads them on the stream
+
+    def set_ref_windows(self, path_q, path_xi, t, t0=None):
+        """Point the handle at the windows of B longer paths (tolg_set_ref_windows): trajectory b tracks knots
+        min(t0[b] + t + i, T), i = 0..N, of its path, the last knot held past the end.  path_q [B, T+1, 4, 4], path_xi
+        [B, T+1, 6], t0 an int array [B] (None: 0).  Like tolg_set_refs it stays set for the calls on this handle that take
+        no references of their own (solve_begin / fit_batch without q_ref go back to the shared reference)."""
+        B = int(np.shape(path_q)[0]) if len(np.shape(path_q)) else 0
+        if not 1 <= B <= self.max_batch:
+            raise ValueError("path_q: batch %d outside 1..%d" % (B, self.max_batch))
+        if int(t) < 0:
+            raise ValueError("t must be non-negative")
+        q, xi, T = self._check_paths(B, path_q, path_xi)
+        self._set_ref_windows(B, q, xi, T, self._check_t0(B, t0), int(t))
+
+    def mpc_advance(self, w=None, J_cl=None):
+        """One receding-horizon step on the held policy (tolg_mpc_advance): x_next = f(x*_0, u*_0) + [0; w] with the exact
+        dynamics, u = u*_0, and the warm start of the next step (xs_q / xs_xi [B, N+1, ...], us [B, N, m]: the solution
+        shifted by one knot, x_next in front, the tail propagated with the last input).  w [B, 6] (None: 0) is added to the
+        twist.  J_cl (a float64 device tensor [B], optional) is accumulated with the stage cost l(x*_0, u*_0) at knot 0.
+        Returns a dict of device tensors: x_next_q [B, 4, 4], x_next_xi, u [B, m], xs_q, xs_xi, us, J_cl."""
+        B = self._held_B()
+        f64 = dict(dtype=torch.float64, device=self.device)
+        d_w = None if w is None else self._dev(self._host_f64("w", w, (B, 6)), (B, 6))
+        if J_cl is not None and (not isinstance(J_cl, torch.Tensor) or J_cl.dtype != torch.float64 or
+                                 tuple(J_cl.shape) != (B,) or J_cl.device != self.device or not J_cl.is_contiguous()):
+            raise ValueError("J_cl must be a contiguous float64 tensor of shape (%d,) on %s" % (B, self.device))
+        r = dict(x_next_q=torch.empty(B, 4, 4, **f64), x_next_xi=torch.empty(B, 6, **f64), u=torch.empty(B, self.m, **f64),
+                 xs_q=torch.empty(B, self.N + 1, 4, 4, **f64), xs_xi=torch.empty(B, self.N + 1, 6, **f64),
+                 us=torch.empty(B, self.N, self.m, **f64), J_cl=J_cl)
+        self._advance(B, d_w, r)
+        return r
+
+    def _advance(self, B, d_w, r):
+        with torch.cuda.device(self.device):
+            rc = self.lib.tolg_mpc_advance(self._h, B, _ptr(d_w), _ptr(r["x_next_q"]), _ptr(r["x_next_xi"]), _ptr(r["u"]),
+                                           _ptr(r["xs_q"]), _ptr(r["xs_xi"]), _ptr(r["us"]), _ptr(r["J_cl"]), self._stream())
+        _capi.check(rc, "tolg_mpc_advance")
+        self._advance_keep = d_w
+
+    def mpc(self, x0_q, x0_xi, path_q, path_xi, steps, us_init=None, t0=None, iters_per_step=5, first_iters=50,
+            warm="states", noise=None, mode="ms", line_search=False, rollout="nonlinear", tol_grad_norm=1e-6, tol_d_norm=1e-6,
+            check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None) -> MPCResult:
+        """Receding-horizon MPC: `steps` closed-loop steps of B trajectories, each tracking its own path from its own phase.
+        Step t: windows min(t0[b] + t + i, T) of the paths (tolg_set_ref_windows), a solve of first_iters (t = 0) or
+        iters_per_step iterations, then tolg_mpc_advance applies u*_0, steps the plant with the exact dynamics and adds the
+        twist disturbance noise[:, t] ([B, steps, 6], None: 0).  The next solve starts from the measured state and
+          warm="states":   the previous solution shifted by one knot, states and controls (tolg_solve_begin_warm; MS only);
+          warm="controls": the shifted controls only, MS states from the reference window (tolg_solve_begin).
+        The first solve starts from us_init (None: 0) and the reference window.  check_every = 0 issues a fixed count of
+        iterations with no host read in the whole loop; > 0 stops a step's solve early (solve_iterate_until).  Q / P / R:
+        weights per trajectory as for fit_batch.  on_step(t, FitResult) is called behind every step's solve (before the
+        plant step; the FitResult carries histories then).  Not with an augmented-Lagrangian constraint attached.  The handle is
+        left on the shared reference and weights.
+        x0_q [B, 4, 4], x0_xi [B, 6], path_q [B, T+1, 4, 4], path_xi [B, T+1, 6]."""
+        if getattr(self, "_al", None) is not None:
+            raise ValueError("mpc under an augmented-Lagrangian constraint is not supported: detach it with set_al(None)")
+        if warm not in ("states", "controls"):
+            raise ValueError("warm must be 'states' or 'controls'")
+        if mode not in ("ms", "ss"):
+            raise ValueError("mode must be 'ms' or 'ss'")
+        if warm == "states" and mode != "ms":
+            raise ValueError("warm='states' warm-starts the shooting states of multiple shooting; use warm='controls' "
+                             "with mode='ss'")
+        steps, K0, K = int(steps), int(first_iters), int(iters_per_step)
+        if steps < 1 or K0 < 0 or K < 0 or int(check_every) < 0:
+            raise ValueError("steps must be >= 1, first_iters, iters_per_step and check_every >= 0")
+        qs = tuple(np.shape(x0_q))
+        if len(qs) not in (2, 3) or qs[1:] not in ((4, 4), (16,)):
+            raise ValueError("x0_q has shape %s, expected (B, 4, 4)" % (qs,))
+        B = qs[0]
+        if not 1 <= B <= self.max_batch:
+            raise ValueError("batch %d outside 1..%d" % (B, self.max_batch))
+        if tuple(np.shape(x0_xi)) != (B, 6):
+            raise ValueError("x0_xi has shape %s, expected (%d, 6)" % (tuple(np.shape(x0_xi)), B))
+        x0_q, x0_xi = self._dev(x0_q, (B, 16)), self._dev(x0_xi, (B, 6))
+        if us_init is not None and tuple(np.shape(us_init)) != (B, self.N, self.m):
+            raise ValueError("us_init has shape %s, expected (%d, %d, %d)" % (tuple(np.shape(us_init)), B, self.N, self.m))
+        pq, pxi, T = self._check_paths(B, path_q, path_xi)
+        t0_d = self._check_t0(B, t0)
+        wts = self._check_weights(B, Q, P, R)
+        if noise is not None:
+            noise = self._host_f64("noise", noise, (B, steps, 6))
+            noise = self._dev(np.ascontiguousarray(noise.transpose(1, 0, 2)), (steps, B, 6))  # step t: one contiguous [B, 6]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        us = torch.zeros(B, self.N, self.m, **f64) if us_init is None else self._dev(us_init, (B, self.N, self.m))
+        res = MPCResult(xs_q=torch.empty(B, steps + 1, 4, 4, **f64), xs_xi=torch.empty(B, steps + 1, 6, **f64),
+                        us=torch.empty(B, steps, self.m, **f64), J=torch.zeros(B, **f64),
+                        iters=torch.empty(B, steps, dtype=torch.int32, device=self.device),
+                        status=torch.empty(B, steps, dtype=torch.int32, device=self.device))
+        res.xs_q[:, 0] = x0_q.reshape(B, 4, 4)
+        res.xs_xi[:, 0] = x0_xi
+        # the plant state and the warm start: written by tolg_mpc_advance, read by the next begin (stream-ordered)
+        adv = dict(x_next_q=torch.empty(B, 4, 4, **f64), x_next_xi=torch.empty(B, 6, **f64), u=torch.empty(B, self.m, **f64),
+                   xs_q=torch.empty(B, self.N + 1, 4, 4, **f64), xs_xi=torch.empty(B, self.N + 1, 6, **f64),
+                   us=torch.empty(B, self.N, self.m, **f64), J_cl=res.J)
+        x_q, x_xi = x0_q, x0_xi
+        try:
+            self._use_pt(B, None, wts)
+            for t in range(steps):
+                self._set_ref_windows(B, pq, pxi, T, t0_d, t)
+                n = K0 if t == 0 else K
+                o = self._options(mode, n, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg)
+                out = self._alloc_result(B, n, histories=on_step is not None)
+                xs = None
+                if t > 0:
+                    x_q, x_xi = adv["x_next_q"].reshape(B, 16), adv["x_next_xi"]
+                    us = adv["us"]
+                    if warm == "states":
+                        xs = (adv["xs_q"].reshape(B, self.N + 1, 16), adv["xs_xi"])
+                self._begin(o, B, x_q, x_xi, us, xs, out)
+                if check_every:
+                    self.solve_iterate_until(n, int(check_every))
+                else:
+                    self.solve_iterate(n)
+                out = self.solve_end()
+                res.iters[:, t] = out.iters
+                res.status[:, t] = out.status
+                if on_step is not None:
+                    on_step(t, out)
+                self._advance(B, None if noise is None else noise[t], adv)
+                res.us[:, t] = adv["u"]
+                res.xs_q[:, t + 1] = adv["x_next_q"]
+                res.xs_xi[:, t + 1] = adv["x_next_xi"]
+        finally:
+            self._use_pt(B, None, None)
+        return res
 
     # ------------------------------------------------------------------------------------------
     def enable_timing(self, on=True):

@@ -242,3 +242,31 @@ def se3_policy_eval(B, S, N=200, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=
     dx0 = np.concatenate([rng.normal(0.0, sigma_pose, (B, S, 6)), rng.normal(0.0, sigma_twist, (B, S, 6))], axis=2)
     noise = rng.normal(0.0, sigma_noise, (B, S, N, 6))
     return prob, x0_q, x0_xi, us0, dx0, noise
+
+
+def se3_mpc(B, steps, N=200, T=None, R=4, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=0.01, seed=SEED):
+    """Receding-horizon inputs (BatchedTrackingILQR.mpc) on se3_tracking's model: B trajectories, each following its own
+    path of T+1 knots (default T = N + steps) -- se3_tracking's path continued to T knots (_extend_reference) and moved by
+    one of R rigid motions (rigid_motions), as se3_multiref does -- from its own phase t0 in [0, T // 4).  Trajectory b
+    starts near knot t0[b] of its path (pose Exp-perturbed with sigma_pose, twist with sigma_twist), and a Gaussian twist
+    disturbance with sigma_noise follows every step.  Returns (prob, x0_q [B, 4, 4], x0_xi [B, 6], path_q [B, T+1, 4, 4],
+    path_xi [B, T+1, 6], t0 [B] int32, noise [B, steps, 6]); prob's shared reference is the first N+1 knots of the unmoved
+    path."""
+    prob, _, _, _ = se3_tracking(1, N=N, seed=seed)
+    T = N + steps if T is None else int(T)
+    q_ref, xi_ref, dt = load_reference("se3_sine2_n200")
+    if T + 1 > q_ref.shape[0]:
+        q_ref, xi_ref = _extend_reference(q_ref, xi_ref, dt, T)
+    q_ref, xi_ref = q_ref[: T + 1], xi_ref[: T + 1]
+    G = rigid_motions(R, seed=seed + 1)
+    index = np.arange(B) % R
+    path_q = np.einsum("bac,icd->biad", G[index], q_ref)
+    path_xi = np.broadcast_to(xi_ref, (B,) + xi_ref.shape).copy()
+    rng = np.random.default_rng(seed + 4)
+    t0 = rng.integers(0, max(T // 4, 1), B).astype(np.int32)
+    x0_q = np.empty((B, 4, 4))
+    for b in range(B):
+        x0_q[b] = path_q[b, t0[b]] @ _se3_exp(rng.normal(0.0, sigma_pose, 6))
+    x0_xi = path_xi[np.arange(B), t0] + rng.normal(0.0, sigma_twist, (B, 6))
+    noise = rng.normal(0.0, sigma_noise, (B, steps, 6))
+    return prob, x0_q, x0_xi, path_q, path_xi, t0, noise
