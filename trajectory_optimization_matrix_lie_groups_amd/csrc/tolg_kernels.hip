@@ -488,15 +488,39 @@ TOLG_DEV void pose_to_m16(Pose X, double* __restrict__ Mx) {
   Mx[8] = R[6]; Mx[9] = R[7]; Mx[10] = R[8]; Mx[11] = X.t.z;
   Mx[12] = 0; Mx[13] = 0; Mx[14] = 0; Mx[15] = 1;
 }
+// Knot k of the C ABI's layout, [..][16] pose matrices and [..][6] twists (w, v), to a State and back.  (These helpers and
+// pack_ref_knot take no __restrict__ and keep the order of their statements: the kernels that call them compile to the
+// code they had with the statements written out, which is what decides FP contraction and the bits of the conversions.)
+TOLG_DEV State state_from_m16(const double* q, const double* xi, size_t k) {
+  State S;
+  S.X = pose_from_m16(q + 16 * k);
+  const double* x = xi + 6 * k;
+  S.w = v3(x[0], x[1], x[2]);
+  S.v = v3(x[3], x[4], x[5]);
+  return S;
+}
+// (a null array is not written)
+TOLG_DEV void state_to_m16(const State& S, double* q, double* xi, size_t k) {
+  if (q) pose_to_m16(S.X, q + 16 * k);
+  if (xi) {
+    double* x = xi + 6 * k;
+    x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z;
+  }
+}
+// one reference knot, pose X (pose_from_m16) and twist xi[6], into the 13 fields of the device layout, field f at
+// r[f * stride]: every packing kernel goes through here, so that tolg_set_refs and tolg_set_ref_windows pack the same bits
+TOLG_DEV void pack_ref_knot(const Pose& X, const double* xi, double* r, int stride) {
+  r[0] = X.q.x; r[stride] = X.q.y; r[2 * (size_t)stride] = X.q.z; r[3 * (size_t)stride] = X.q.w;
+  r[4 * (size_t)stride] = X.t.x; r[5 * (size_t)stride] = X.t.y; r[6 * (size_t)stride] = X.t.z;
+  for (int a = 0; a < 6; a++) r[(7 + a) * (size_t)stride] = xi[a];
+}
 
 __global__ void k_pack_ref(int N, const double* __restrict__ q_ref, const double* __restrict__ xi_ref,
                            double* __restrict__ ref) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i > N) return;
   Pose X = pose_from_m16(q_ref + 16 * (size_t)i);
-  double* r = ref + 13 * (size_t)i;
-  r[0] = X.q.x; r[1] = X.q.y; r[2] = X.q.z; r[3] = X.q.w; r[4] = X.t.x; r[5] = X.t.y; r[6] = X.t.z;
-  for (int a = 0; a < 6; a++) r[7 + a] = xi_ref[6 * (size_t)i + a];
+  pack_ref_knot(X, xi_ref + 6 * (size_t)i, ref + 13 * (size_t)i, 1);
 }
 // the same conversion for B references [B][N+1][16] / [B][N+1][6] into [N+1][13][Bp] (the PTREF kernels' P.ref); padded
 // trajectories b >= B replicate b = B-1
@@ -507,16 +531,11 @@ __global__ void k_pack_refs(int B, int Bp, int N, const double* __restrict__ q_r
   int b = (int)(t % Bp), i = (int)(t / Bp);
   int bs = b < B ? b : B - 1;
   Pose X = pose_from_m16(q_ref + ((size_t)bs * (N + 1) + i) * 16);
-  const double* x = xi_ref + ((size_t)bs * (N + 1) + i) * 6;
-  double* r = refs + (size_t)i * 13 * Bp + b;
-  r[0] = X.q.x; r[Bp] = X.q.y; r[2 * (size_t)Bp] = X.q.z; r[3 * (size_t)Bp] = X.q.w;
-  r[4 * (size_t)Bp] = X.t.x; r[5 * (size_t)Bp] = X.t.y; r[6 * (size_t)Bp] = X.t.z;
-  for (int a = 0; a < 6; a++) r[(7 + a) * (size_t)Bp] = x[a];
+  pack_ref_knot(X, xi_ref + ((size_t)bs * (N + 1) + i) * 6, refs + (size_t)i * 13 * Bp + b, Bp);
 }
 // the same layout gathered from B longer paths [B][T+1][16] / [B][T+1][6] (tolg_set_ref_windows): knot i of trajectory b's
-// window is knot min(t0[b] + t + i, T) of its path (t0 = null: 0), the last knot held past the end.  The statements are
-// k_pack_refs's with the source knot moved, so that the matrix -> quaternion conversion compiles the same way and the windows
-// are the bits tolg_set_refs packs from host-sliced windows.
+// window is knot min(t0[b] + t + i, T) of its path (t0 = null: 0), the last knot held past the end: the bits tolg_set_refs
+// packs from host-sliced windows (pack_ref_knot).
 __global__ void k_pack_ref_windows(int B, int Bp, int N, int T, const double* __restrict__ path_q,
                                    const double* __restrict__ path_xi, const int* __restrict__ t0, int t,
                                    double* __restrict__ refs) {
@@ -527,11 +546,7 @@ __global__ void k_pack_ref_windows(int B, int Bp, int N, int T, const double* __
   long long k = (long long)(t0 ? t0[bs] : 0) + t + i;
   k = k < 0 ? 0 : (k > T ? T : k);  // a negative phase reads knot 0 (the loads stay inside the path)
   Pose X = pose_from_m16(path_q + ((size_t)bs * (T + 1) + (size_t)k) * 16);
-  const double* x = path_xi + ((size_t)bs * (T + 1) + (size_t)k) * 6;
-  double* r = refs + (size_t)i * 13 * Bp + b;
-  r[0] = X.q.x; r[Bp] = X.q.y; r[2 * (size_t)Bp] = X.q.z; r[3 * (size_t)Bp] = X.q.w;
-  r[4 * (size_t)Bp] = X.t.x; r[5 * (size_t)Bp] = X.t.y; r[6 * (size_t)Bp] = X.t.z;
-  for (int a = 0; a < 6; a++) r[(7 + a) * (size_t)Bp] = x[a];
+  pack_ref_knot(X, path_xi + ((size_t)bs * (T + 1) + (size_t)k) * 6, refs + (size_t)i * 13 * Bp + b, Bp);
 }
 
 // the per-trajectory scalars a solve starts from (k_init, k_init_warm)
@@ -550,7 +565,7 @@ __global__ void k_init(Params P, const double* __restrict__ x0_q, const double* 
   int b = (int)(t % P.Bp), i = (int)(t / P.Bp);
   int bs = b < P.B ? b : P.B - 1;
   State S;
-  if (i == 0) {
+  if (i == 0) {  // (written out, not state_from_m16: the helper compiles to other code in k_init<false>)
     S.X = pose_from_m16(x0_q + 16 * (size_t)bs);
     const double* x = x0_xi + 6 * (size_t)bs;
     S.w = v3(x[0], x[1], x[2]);
@@ -581,11 +596,7 @@ __global__ void k_init_warm(Params P, const double* __restrict__ x0_q, const dou
   const size_t k = (size_t)bs * (P.N + 1) + i;
   const double* q = i == 0 ? x0_q + 16 * (size_t)bs : xs_q + 16 * k;
   const double* x = i == 0 ? x0_xi + 6 * (size_t)bs : xs_xi + 6 * k;
-  State S;
-  S.X = pose_from_m16(q);
-  S.w = v3(x[0], x[1], x[2]);
-  S.v = v3(x[3], x[4], x[5]);
-  store_state(P, P.cur, i, b, S);
+  store_state(P, P.cur, i, b, state_from_m16(q, x, 0));
   if (i < P.N)
     for (int a = 0; a < P.m; a++) P.cur_u[UIDX(a, i, b)] = us_init[((size_t)bs * P.N + i) * P.m + a];
   if (i == 0) init_scalars(P, b);
@@ -598,12 +609,7 @@ __global__ void k_pack_traj(Params P, const double* __restrict__ xs_q, const dou
   if (t >= (size_t)(P.N + 1) * P.Bp) return;
   int b = (int)(t % P.Bp), i = (int)(t / P.Bp);
   int bs = b < P.B ? b : P.B - 1;
-  State S;
-  S.X = pose_from_m16(xs_q + ((size_t)bs * (P.N + 1) + i) * 16);
-  const double* x = xs_xi + ((size_t)bs * (P.N + 1) + i) * 6;
-  S.w = v3(x[0], x[1], x[2]);
-  S.v = v3(x[3], x[4], x[5]);
-  store_state(P, P.cur, i, b, S);
+  store_state(P, P.cur, i, b, state_from_m16(xs_q, xs_xi, (size_t)bs * (P.N + 1) + i));
   if (i < P.N)
     for (int a = 0; a < P.m; a++) P.cur_u[UIDX(a, i, b)] = us[((size_t)bs * P.N + i) * P.m + a];
   if (i == 0) {
@@ -620,6 +626,7 @@ __global__ void k_unpack_traj(Params P, const double* __restrict__ s, const doub
   if (t >= (size_t)(P.N + 1) * P.Bp) return;
   int b = (int)(t % P.Bp), i = (int)(t / P.Bp);
   if (b >= P.B) return;
+  // (written out, not state_to_m16: the helper's one knot offset in front of both stores compiles to other code here)
   State S = load_state(P, s, i, b);
   if (xs_q) pose_to_m16(S.X, xs_q + ((size_t)b * (P.N + 1) + i) * 16);
   if (xs_xi) {
@@ -640,6 +647,7 @@ __global__ void k_mpc_shift(Params P, const double* __restrict__ s, const double
   if (t >= (size_t)P.N * P.Bp) return;
   int b = (int)(t % P.Bp), i = (int)(t / P.Bp);
   if (b >= P.B) return;
+  // (written out, not state_to_m16, as in k_unpack_traj)
   State S = load_state(P, s, i + 1, b);
   if (xs_q && i > 0) pose_to_m16(S.X, xs_q + ((size_t)b * (P.N + 1) + i) * 16);
   if (xs_xi && i > 0) {
@@ -2918,9 +2926,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
                                                            nullptr RST_ARG);
     J += knot_cost<M, true, PT>(P, C, i, b, Sn, un, false);
     if (writer) {
-      const size_t k = bs * (size_t)(N + 1) + i;
-      if (xs_q) pose_to_m16(Sn.X, xs_q + 16 * k);
-      if (xs_xi) { double* x = xs_xi + 6 * k; x[0] = Sn.w.x; x[1] = Sn.w.y; x[2] = Sn.w.z; x[3] = Sn.v.x; x[4] = Sn.v.y; x[5] = Sn.v.z; }
+      state_to_m16(Sn, xs_q, xs_xi, bs * (size_t)(N + 1) + i);
       if (us) {
         double* u = us + (bs * (size_t)N + i) * M;
 #pragma unroll
@@ -2939,9 +2945,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
   for (int a = 0; a < M; a++) un[a] = 0.0;
   J += knot_cost<M, true, PT>(P, C, N, b, Sn, un, true);
   if (writer) {
-    const size_t k = bs * (size_t)(N + 1) + N;
-    if (xs_q) pose_to_m16(Sn.X, xs_q + 16 * k);
-    if (xs_xi) { double* x = xs_xi + 6 * k; x[0] = Sn.w.x; x[1] = Sn.w.y; x[2] = Sn.w.z; x[3] = Sn.v.x; x[4] = Sn.v.y; x[5] = Sn.v.z; }
+    state_to_m16(Sn, xs_q, xs_xi, bs * (size_t)(N + 1) + N);
     if (Jout) Jout[bs] = J;
     if (status) status[bs] = isfinite(J) ? TOLG_ST_OK : TOLG_ST_NONFINITE;
   }
@@ -2973,6 +2977,7 @@ __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __r
       S.w = S.w + v3(d[0], d[1], d[2]);
       S.v = S.v + v3(d[3], d[4], d[5]);
     }
+    // (both ends written out, not state_to_m16: the helper compiles to other code in this kernel)
     if (x_next_q) pose_to_m16(S.X, x_next_q + 16 * (size_t)b);
     if (x_next_xi) { double* x = x_next_xi + 6 * (size_t)b; x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z; }
     if (u_applied)
@@ -3685,12 +3690,7 @@ __global__ void k_probe_pack(Params P, int i, const double* __restrict__ x_q, co
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= P.Bp) return;
   int bs = b < P.B ? b : P.B - 1;
-  State S;
-  S.X = pose_from_m16(x_q + 16 * (size_t)bs);
-  const double* x = x_xi + 6 * (size_t)bs;
-  S.w = v3(x[0], x[1], x[2]);
-  S.v = v3(x[3], x[4], x[5]);
-  store_state(P, P.cur, i, b, S);
+  store_state(P, P.cur, i, b, state_from_m16(x_q, x_xi, bs));
   if (i < P.N)
     for (int a = 0; a < P.m; a++) P.cur_u[UIDX(a, i, b)] = u ? u[(size_t)bs * P.m + a] : 0.0;
   P.active[b] = 1;
@@ -3724,6 +3724,7 @@ __global__ void k_probe_export(Params P, int i, double* __restrict__ f_q, double
       for (int k = 0; k < m; k++)
         luu[((size_t)b * m + a) * m + k] = 2.0 * C.R[a * m + k] + ((a == k && P.al_lb) ? P.REC[RIDX(i, P.fLUU + a, b)] : 0.0);
   if (f_q || f_xi) {  // f(x, u) was left in knot i of the candidate array by the probe-mode linearisation
+    // (written out, not state_to_m16: the helper compiles to other code in this kernel)
     State F = load_state(P, P.cand, i, b);
     if (f_q) pose_to_m16(F.X, f_q + 16 * (size_t)b);
     if (f_xi) {
@@ -4014,6 +4015,16 @@ struct tolg_handle_s {
 };
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// the batch the device arrays are strided for: B rounded up to whole quads (the padded trajectories replicate b = B-1)
+static int padded_batch(int B) { return (B + 3) / 4 * 4; }
+
+// B trajectories fit the handle and the per-trajectory references and weights it holds (tolg_set_refs, tolg_set_weights):
+// what every batch call on the handle's workspace requires
+static bool batch_fits(const tolg_handle_s* h, int B) {
+  return B >= 1 && B <= h->max_batch && !(h->refs && B != h->refs_B) && !(h->wts && B != h->wts_B);
+}
+// the kernels of h->kt follow what per-trajectory inputs are set (kernel_table, PT)
+static void select_kernels(tolg_handle_s* h) { h->kt = h->kt_pt[(h->refs ? PT_REF : 0) | (h->wts ? PT_W : 0)]; }
 
 static int host_inv6(const double A[36], double Ai[36]) {
   double Mx[6][12];
@@ -4111,8 +4122,7 @@ static int check_problem(const tolg_problem* p) {
 
 extern "C" size_t tolg_workspace_bytes(const tolg_problem* prob, int32_t max_batch) {
   if (check_problem(prob) || max_batch < 1) return 0;
-  int Bp = (max_batch + 3) / 4 * 4;
-  return carve_all(prob, Bp, nullptr, nullptr, nullptr);
+  return carve_all(prob, padded_batch(max_batch), nullptr, nullptr, nullptr);
 }
 
 extern "C" const char* tolg_version(void) { return "tolg-hip 0.3 (gfx950)"; }
@@ -4150,12 +4160,12 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
   if (workspace_bytes < tolg_workspace_bytes(prob, max_batch)) return TOLG_E_WORKSPACE;
   if ((reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0) return TOLG_E_ARG;
   // one knot of records must stay below the out-of-range offset K2 uses for structurally-zero loads (1 GiB)
-  if ((size_t)((max_batch + 3) / 4 * 4) * REC_FMAX * 8 >= 0x40000000ull) return TOLG_E_ARG;
+  if ((size_t)padded_batch(max_batch) * REC_FMAX * 8 >= 0x40000000ull) return TOLG_E_ARG;
   tolg_handle_s* h = new (std::nothrow) tolg_handle_s();
   if (!h) return TOLG_E_ARG;
   h->prob = *prob;
   h->max_batch = max_batch;
-  h->Bp_max = (max_batch + 3) / 4 * 4;
+  h->Bp_max = padded_batch(max_batch);
   h->ws = static_cast<char*>(d_workspace);
   h->ws_bytes = workspace_bytes;
   h->timing = false;
@@ -4231,7 +4241,7 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
   h->kt_pt[PT_REF] = kernel_table_for<PT_REF>(*prob, c, h->lds_per_block);
   h->kt_pt[PT_W] = kernel_table_for<PT_W>(*prob, c, h->lds_per_block);
   h->kt_pt[PT_REF | PT_W] = kernel_table_for<PT_REF | PT_W>(*prob, c, h->lds_per_block);
-  h->kt = h->kt_pt[0];
+  select_kernels(h);
   {
     const char* e = getenv("TOLG_K2_FULL_ONLY");
     h->k2_full_only = e && e[0] == '1';
@@ -4334,7 +4344,7 @@ extern "C" int tolg_kernel_time(tolg_handle_t h, int32_t reset, double* ms_backw
 static Params params_for(tolg_handle_s* h, int B) {
   Params P = h->P;
   P.B = B;
-  P.Bp = (B + 3) / 4 * 4;
+  P.Bp = padded_batch(B);
   P.J_hist = P.grad_hist = P.defect_hist = P.alpha_hist = P.mu_hist = nullptr;
   P.max_iter = 0; P.tol_grad = 0; P.tol_defect = 0; P.max_reg = 1e10;
   P.al_lb = h->al_lb; P.al_ub = h->al_ub; P.al_lambda = h->al_lambda; P.al_imu = h->al_imu;
@@ -4611,8 +4621,7 @@ static int iterate_ss(tolg_handle_s* h, const Params& P, const tolg_options* opt
 static int solve_begin(tolg_handle_t h, const tolg_options* opt, int32_t B, const double* d_x0_q, const double* d_x0_xi,
                        const double* d_xs_q, const double* d_xs_xi, const double* d_us_init, double* d_J_hist,
                        double* d_grad_hist, double* d_defect_hist, double* d_alpha_hist, double* d_mu_hist, void* stream) {
-  if (!h || !opt || B < 1 || B > h->max_batch || !d_x0_q || !d_x0_xi || !d_us_init) return TOLG_E_ARG;
-  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;
+  if (!h || !opt || !batch_fits(h, B) || !d_x0_q || !d_x0_xi || !d_us_init) return TOLG_E_ARG;
   if (opt->max_iter < 0) return TOLG_E_ARG;
   if (opt->mode != TOLG_MODE_MS && opt->mode != TOLG_MODE_SS) return TOLG_E_ARG;
   const int ms = opt->mode == TOLG_MODE_MS;
@@ -4782,44 +4791,51 @@ extern "C" int tolg_set_al(tolg_handle_t h, const double* d_lb, const double* d_
 }
 
 static size_t refs_bytes_for(const tolg_problem* p, int B) {
-  return (size_t)(p->N + 1) * 13 * (size_t)((B + 3) / 4 * 4) * sizeof(double);
+  return (size_t)(p->N + 1) * 13 * (size_t)padded_batch(B) * sizeof(double);
 }
 extern "C" size_t tolg_refs_bytes(const tolg_problem* prob, int32_t max_batch) {
   if (check_problem(prob) || max_batch < 1) return 0;
   return refs_bytes_for(prob, max_batch);
 }
 
+// tolg_set_refs and tolg_set_ref_windows: d_refs can hold the packed references of B trajectories (8-byte aligned, refs_bytes
+// large enough), and B is the batch of the per-trajectory weights when they are set (references and weights: one batch)
+static bool refs_dest_ok(const tolg_handle_s* h, int B, const void* d_refs, size_t refs_bytes) {
+  return B >= 1 && B <= h->max_batch && d_refs && (reinterpret_cast<uintptr_t>(d_refs) & 7) == 0 &&
+         refs_bytes >= refs_bytes_for(&h->prob, B) && !(h->wts && B != h->wts_B);
+}
+// ... and what the packing kernel queued on the stream: the handle's references from now on
+static void hold_refs(tolg_handle_s* h, int B, const void* d_refs) {
+  h->refs = static_cast<const double*>(d_refs); h->refs_B = B; select_kernels(h);
+}
+
 extern "C" int tolg_set_refs(tolg_handle_t h, int32_t B, const double* d_q_ref, const double* d_xi_ref, void* d_refs,
                              size_t refs_bytes, void* stream) {
   if (!h || h->running) return TOLG_E_ARG;
   if (!d_q_ref) {  // back to the reference of tolg_create
-    h->refs = nullptr; h->refs_B = 0; h->kt = h->kt_pt[h->wts ? PT_W : 0];
+    h->refs = nullptr; h->refs_B = 0; select_kernels(h);
     return 0;
   }
-  if (B < 1 || B > h->max_batch || !d_xi_ref || !d_refs || (reinterpret_cast<uintptr_t>(d_refs) & 7) != 0) return TOLG_E_ARG;
-  if (refs_bytes < refs_bytes_for(&h->prob, B)) return TOLG_E_ARG;
-  if (h->wts && B != h->wts_B) return TOLG_E_ARG;  // references and weights per trajectory: one batch
-  const int N = h->prob.N, Bp = (B + 3) / 4 * 4;
+  if (!d_xi_ref || !refs_dest_ok(h, B, d_refs, refs_bytes)) return TOLG_E_ARG;
+  const int N = h->prob.N, Bp = padded_batch(B);
   const size_t n = (size_t)(N + 1) * Bp;
   hipLaunchKernelGGL(k_pack_refs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp, N,
                      d_q_ref, d_xi_ref, static_cast<double*>(d_refs));
   LAUNCH_CHECK();
-  h->refs = static_cast<const double*>(d_refs); h->refs_B = B; h->kt = h->kt_pt[PT_REF | (h->wts ? PT_W : 0)];
+  hold_refs(h, B, d_refs);
   return 0;
 }
 
 extern "C" int tolg_set_ref_windows(tolg_handle_t h, int32_t B, const double* d_path_q, const double* d_path_xi, int32_t T,
                                     const int32_t* d_t0, int32_t t, void* d_refs, size_t refs_bytes, void* stream) {
   if (!h || h->running || !d_path_q || !d_path_xi || T < 1 || t < 0) return TOLG_E_ARG;
-  if (B < 1 || B > h->max_batch || !d_refs || (reinterpret_cast<uintptr_t>(d_refs) & 7) != 0) return TOLG_E_ARG;
-  if (refs_bytes < refs_bytes_for(&h->prob, B)) return TOLG_E_ARG;
-  if (h->wts && B != h->wts_B) return TOLG_E_ARG;
-  const int N = h->prob.N, Bp = (B + 3) / 4 * 4;
+  if (!refs_dest_ok(h, B, d_refs, refs_bytes)) return TOLG_E_ARG;
+  const int N = h->prob.N, Bp = padded_batch(B);
   const size_t n = (size_t)(N + 1) * Bp;
   hipLaunchKernelGGL(k_pack_ref_windows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B,
                      Bp, N, (int)T, d_path_q, d_path_xi, reinterpret_cast<const int*>(d_t0), (int)t, static_cast<double*>(d_refs));
   LAUNCH_CHECK();
-  h->refs = static_cast<const double*>(d_refs); h->refs_B = B; h->kt = h->kt_pt[PT_REF | (h->wts ? PT_W : 0)];
+  hold_refs(h, B, d_refs);
   return 0;
 }
 
@@ -4835,7 +4851,7 @@ __global__ void k_pack_weights(int B, int Bp, int m, const double* __restrict__ 
   w[t] = f < 12 ? q_diag[(size_t)bs * 12 + f] : f < 24 ? p_diag[(size_t)bs * 12 + f - 12] : r_diag[(size_t)bs * m + f - 24];
 }
 static size_t weights_bytes_for(const tolg_problem* p, int B) {
-  return (size_t)wt_fields(p->m) * (size_t)((B + 3) / 4 * 4) * sizeof(double);
+  return (size_t)wt_fields(p->m) * (size_t)padded_batch(B) * sizeof(double);
 }
 extern "C" size_t tolg_weights_bytes(const tolg_problem* prob, int32_t max_batch) {
   if (check_problem(prob) || max_batch < 1) return 0;
@@ -4846,18 +4862,18 @@ extern "C" int tolg_set_weights(tolg_handle_t h, int32_t B, const double* d_q_di
                                 const double* d_r_diag, void* d_w, size_t w_bytes, void* stream) {
   if (!h || h->running) return TOLG_E_ARG;
   if (!d_q_diag) {  // back to the weights of tolg_create
-    h->wts = nullptr; h->wts_B = 0; h->kt = h->kt_pt[h->refs ? PT_REF : 0];
+    h->wts = nullptr; h->wts_B = 0; select_kernels(h);
     return 0;
   }
   if (B < 1 || B > h->max_batch || !d_p_diag || !d_r_diag || !d_w || (reinterpret_cast<uintptr_t>(d_w) & 7) != 0) return TOLG_E_ARG;
   if (w_bytes < weights_bytes_for(&h->prob, B)) return TOLG_E_ARG;
   if (h->refs && B != h->refs_B) return TOLG_E_ARG;  // references and weights per trajectory: one batch
-  const int Bp = (B + 3) / 4 * 4;
+  const int Bp = padded_batch(B);
   const size_t n = (size_t)wt_fields(h->prob.m) * Bp;
   hipLaunchKernelGGL(k_pack_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp,
                      h->prob.m, d_q_diag, d_p_diag, d_r_diag, static_cast<double*>(d_w), const_cast<Consts*>(h->P.c));
   LAUNCH_CHECK();
-  h->wts = static_cast<const double*>(d_w); h->wts_B = B; h->kt = h->kt_pt[PT_W | (h->refs ? PT_REF : 0)];
+  h->wts = static_cast<const double*>(d_w); h->wts_B = B; select_kernels(h);
   return 0;
 }
 
@@ -4878,8 +4894,7 @@ extern "C" int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_r
                                        double* d_d, double* d_lx, double* d_lxx11, double* d_k, double* d_K,
                                        double* d_J, double* d_dnorm, double* d_grad, void* stream) {
   // uses the handle's workspace (k_pack_traj resets the trajectories, mu / delta, the masks): not during a solve
-  if (!h || h->running || B < 1 || B > h->max_batch || !d_xs_q || !d_xs_xi || !d_us) return TOLG_E_ARG;
-  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;
+  if (!h || h->running || !batch_fits(h, B) || !d_xs_q || !d_xs_xi || !d_us) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   h->pol_B = 0;  // held again once the sweep below is queued
   Params P = params_for(h, B);
@@ -4938,8 +4953,7 @@ __global__ void k_clear_ecc(Params P) {
 }
 extern "C" int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, double* d_ecc, int32_t* d_flag, void* stream) {
   // works on what tolg_linearize_backward left in the workspace (trajectory, records, gains): not during a solve
-  if (!h || h->running || B < 1 || B > h->max_batch || form < 0 || form > 2) return TOLG_E_ARG;
-  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;
+  if (!h || h->running || !batch_fits(h, B) || form < 0 || form > 2) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   hipLaunchKernelGGL(k_clear_ecc, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
@@ -4961,8 +4975,7 @@ extern "C" int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, do
 
 extern "C" int tolg_rollout(tolg_handle_t h, int32_t ms, int32_t rollout_linear, double alpha, int32_t B,
                             double* d_xs_q_new, double* d_xs_xi_new, double* d_us_new, void* stream) {
-  if (!h || h->running || B < 1 || B > h->max_batch) return TOLG_E_ARG;  // overwrites the candidate arrays
-  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;
+  if (!h || h->running || !batch_fits(h, B)) return TOLG_E_ARG;  // overwrites the candidate arrays
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   int rc = run_rollout_ms(h, P, st, alpha, rollout_linear, ms);
@@ -4976,8 +4989,7 @@ extern "C" int tolg_rollout(tolg_handle_t h, int32_t ms, int32_t rollout_linear,
 
 // the held policy (h->pol_B): what both entry points below require
 static bool policy_ok(const tolg_handle_s* h, int B) {
-  if (!h || h->running || h->pol_B == 0 || B != h->pol_B) return false;
-  return !((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B));
+  return h && !h->running && h->pol_B != 0 && B == h->pol_B && batch_fits(h, B);
 }
 extern "C" int tolg_solve_gains(tolg_handle_t h, int32_t B, double* d_k, double* d_K, void* stream) {
   if (!policy_ok(h, B)) return TOLG_E_ARG;

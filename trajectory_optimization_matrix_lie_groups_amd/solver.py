@@ -122,6 +122,40 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _checked(name, a, shape, finite=False):
+    """The host-side check of a batch input: `a` (numpy, torch or nested sequences) has `shape` (None: any extent) and, with
+    finite=True, only finite values; ValueError otherwise, before anything reaches the device.  Returns `a` as given (nested
+    sequences as a float64 array), or with finite=True as a float64 numpy array (a device tensor is read back)."""
+    if finite:
+        a = np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+    elif not hasattr(a, "shape"):
+        a = np.asarray(a, dtype=np.float64)
+    s = tuple(a.shape)
+    if len(s) != len(shape) or any(n is not None and n != k for n, k in zip(shape, s)):
+        raise ValueError("%s has shape %s, expected (%s)" % (name, s, ", ".join("*" if n is None else str(n) for n in shape)))
+    if finite and not np.all(np.isfinite(a)):
+        raise ValueError("%s must be finite" % name)
+    return a
+
+
+# What a C call does to the held policy (include/tolg.h): "clear" before it runs (so also when it fails), "hold" the batch
+# of the call once it has succeeded.  gains / policy_rollout / mpc_advance need one held.
+_POLICY = {"tolg_solve_begin": "clear", "tolg_solve_begin_warm": "clear", "tolg_eval_knot": "clear",
+           "tolg_solve_batch": "clear hold", "tolg_linearize_backward": "clear hold", "tolg_solve_end": "hold"}
+
+
+@dataclass
+class _Batch:
+    """A batch's inputs, checked and on the device (BatchedTrackingILQR._stage)."""
+    B: int
+    x_q: torch.Tensor     # [B, 16] the initial states (linearize_backward: [B, N+1, 16], whole trajectories)
+    x_xi: torch.Tensor    # [B, 6] ([B, N+1, 6])
+    us: torch.Tensor      # [B, N, m]
+    refs: Optional[tuple] = None  # (q [B, N+1, 16], xi [B, N+1, 6]) per trajectory, or None: the problem's reference
+    wts: Optional[tuple] = None   # diagonals (q [B, 12], p [B, 12], r [B, m]) per trajectory, or None: the problem's weights
+    xs: Optional[tuple] = None    # warm-start shooting states (q [B, N+1, 16], xi [B, N+1, 6]), or None
+
+
 class BatchedTrackingILQR:
     """Batched iLQR_Tracking_SE3_MS / iLQR_Tracking_SE3 on one GPU (one process per GPU).
 
@@ -136,6 +170,11 @@ class BatchedTrackingILQR:
         self.problem = problem
         self.N, self.m = problem.N, problem.m
         self.max_batch = int(max_batch)
+        self._policy_B = 0         # batch of the held policy, 0 = none (_POLICY)
+        self._refs_set = self._wts_set = False  # the handle points at per-trajectory references / weights
+        self._refs_buf = self._wts_buf = None  # the packed per-trajectory references / weights the handle reads (_packed)
+        self._inflight = (None, None)  # the FitResult of the solve in flight; the inputs the stream may not have read (_hold)
+        self._al = None            # the augmented-Lagrangian terms the handle points at (set_al)
         p = _capi.Problem()
         p.kind, p.m, p.N, p.dt = _KIND[problem.kind], self.m, self.N, float(problem.dt)
         p.pend_mass, p.pend_length = float(problem.pend_mass), float(problem.pend_length)
@@ -177,47 +216,47 @@ class BatchedTrackingILQR:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _call(self, fn, *args, stream=True, batch=0):
+        """C entry point `fn` on the handle, checked.  stream=True: on the solver's device, its current stream appended as the
+        last argument.  The held policy follows _POLICY; `batch` is the one a "hold" call leaves."""
+        effect = _POLICY.get(fn, "")
+        if "clear" in effect:
+            self._policy_B = 0
+        if stream:
+            with torch.cuda.device(self.device):
+                rc = getattr(self.lib, fn)(self._h, *args, self._stream())
+        else:
+            rc = getattr(self.lib, fn)(self._h, *args)
+        _capi.check(rc, fn)
+        if "hold" in effect:
+            self._policy_B = int(batch)
+
     def _dev(self, a, shape):
         t = torch.as_tensor(a, dtype=torch.float64, device=self.device)
         return t.reshape(shape).contiguous()
 
+    def _hold(self, inputs):
+        """The one keep-alive: the device inputs of the last call, which the stream may not have read yet."""
+        self._inflight = (self._inflight[0], inputs)
+
+    def _packed(self, attr, nbytes_fn):
+        """The caller-owned buffer self.<attr> the handle reads packed per-trajectory references (_refs_buf,
+        tolg_refs_bytes) or weights (_wts_buf, tolg_weights_bytes) from, allocated for max_batch the first time it is needed.
+        Returns (pointer, bytes)."""
+        if getattr(self, attr) is None:
+            setattr(self, attr, torch.empty(int(nbytes_fn(C.byref(self._p), self.max_batch)) // 8, dtype=torch.float64,
+                                            device=self.device))
+        buf = getattr(self, attr)
+        return _ptr(buf), C.c_size_t(buf.numel() * 8)
+
     def _check_refs(self, B, q_ref, xi_ref):
-        """Shapes of per-trajectory references [B, N+1, 4, 4] / [B, N+1, 6], checked on the host: ValueError before anything
-        reaches the device.  None when both are omitted (the problem's shared reference)."""
+        """Per-trajectory references [B, N+1, 4, 4] / [B, N+1, 6], checked on the host: ValueError before anything reaches
+        the device.  None when both are omitted (the problem's shared reference)."""
         if q_ref is None and xi_ref is None:
             return None
         if q_ref is None or xi_ref is None:
             raise ValueError("per-trajectory references need both q_ref and xi_ref")
-        if not hasattr(q_ref, "shape"):
-            q_ref = np.asarray(q_ref, dtype=np.float64)
-        if not hasattr(xi_ref, "shape"):
-            xi_ref = np.asarray(xi_ref, dtype=np.float64)
-        qs, xs = tuple(q_ref.shape), tuple(xi_ref.shape)
-        if qs != (B, self.N + 1, 4, 4):
-            raise ValueError("q_ref has shape %s, expected (%d, %d, 4, 4) (batch, horizon N+1 = %d)" % (qs, B, self.N + 1, self.N + 1))
-        if xs != (B, self.N + 1, 6):
-            raise ValueError("xi_ref has shape %s, expected (%d, %d, 6)" % (xs, B, self.N + 1))
-        return q_ref, xi_ref
-
-    def _use_refs(self, B, refs):
-        """Point the handle at this call's references (tolg_set_refs), or back at the problem's shared one when refs is None:
-        every call states its own references, nothing carries over from an earlier call.  The packed buffer is allocated the
-        first time references are given, for max_batch."""
-        if refs is None:
-            if getattr(self, "_refs_set", False):
-                _capi.check(self.lib.tolg_set_refs(self._h, 0, None, None, None, 0, None), "tolg_set_refs")
-                self._refs_set = False
-            return
-        q = self._dev(refs[0], (B, self.N + 1, 16))
-        xi = self._dev(refs[1], (B, self.N + 1, 6))
-        if getattr(self, "_refs_buf", None) is None:
-            nbytes = int(self.lib.tolg_refs_bytes(C.byref(self._p), self.max_batch))
-            self._refs_buf = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_set_refs(self._h, B, _ptr(q), _ptr(xi), _ptr(self._refs_buf),
-                                        C.c_size_t(self._refs_buf.numel() * 8), self._stream())
-        _capi.check(rc, "tolg_set_refs")
-        self._refs_set = True
+        return _checked("q_ref", q_ref, (B, self.N + 1, 4, 4)), _checked("xi_ref", xi_ref, (B, self.N + 1, 6))
 
     def _check_weights(self, B, Q, P, R):
         """Per-trajectory cost weights Q [B, 12, 12], P [B, 12, 12], R [B, m, m] (numpy or torch, the fields of TrackingProblem
@@ -230,13 +269,8 @@ class BatchedTrackingILQR:
             raise ValueError("per-trajectory weights need all three of Q, P and R")
         out = []
         for name, a, n in (("Q", Q, 12), ("P", P, 12), ("R", R, self.m)):
-            a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-            a = np.asarray(a, dtype=np.float64)
-            if a.shape != (B, n, n):
-                raise ValueError("%s has shape %s, expected (%d, %d, %d)" % (name, a.shape, B, n, n))
+            a = _checked(name, a, (B, n, n), finite=True)
             d = np.diagonal(a, axis1=1, axis2=2)
-            if not np.all(np.isfinite(a)):
-                raise ValueError("%s: per-trajectory weights must be finite" % name)
             if np.any(a - d[:, :, None] * np.eye(n) != 0.0):
                 raise ValueError("%s: per-trajectory weights must be diagonal (a non-zero off-diagonal entry)" % name)
             if np.any(d < 0.0):
@@ -244,34 +278,65 @@ class BatchedTrackingILQR:
             out.append(np.ascontiguousarray(d))
         return tuple(out)
 
+    def _check_xs_init(self, B, xs_init, mode):
+        """xs_init = (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6]) checked on the host; None when omitted."""
+        if xs_init is None:
+            return None
+        if mode != "ms":
+            raise ValueError("xs_init warm-starts the shooting states of multiple shooting: single shooting takes its states "
+                             "from the initial rollout")
+        if not isinstance(xs_init, (tuple, list)) or len(xs_init) != 2:
+            raise ValueError("xs_init is a pair (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6])")
+        return _checked("xs_init[0]", xs_init[0], (B, self.N + 1, 4, 4)), _checked("xs_init[1]", xs_init[1], (B, self.N + 1, 6))
+
+    def _stage(self, x_q, x_xi, us, refs=(None, None), weights=(None, None, None), xs_init=None, mode="ms", traj=False):
+        """The one way a batch's inputs reach the device: x_q reshaped to [B, 16] gives B (traj=True: whole trajectories
+        [B, N+1, 16], linearize_backward), then the per-trajectory references (q_ref, xi_ref), weights (Q, P, R) and
+        xs_init are checked on the host, and everything moves to the device.  us = None: zeros (not for trajectories)."""
+        k = (self.N + 1,) if traj else ()
+        x_q = self._dev(x_q, (-1,) + k + (16,))
+        B = x_q.shape[0]
+        refs = self._check_refs(B, *refs)
+        wts = self._check_weights(B, *weights)
+        xs = self._check_xs_init(B, xs_init, mode)
+        x_xi = self._dev(x_xi, (B,) + k + (6,))
+        if us is None and not traj:
+            us = torch.zeros(B, self.N, self.m, dtype=torch.float64, device=self.device)
+        pair = lambda p: None if p is None else (self._dev(p[0], (B, self.N + 1, 16)), self._dev(p[1], (B, self.N + 1, 6)))  # noqa: E731
+        return _Batch(B, x_q, x_xi, self._dev(us, (B, self.N, self.m)), pair(refs),
+                      None if wts is None else tuple(self._dev(a, a.shape) for a in wts), pair(xs))
+
     def clear_per_trajectory(self):
         """Return the handle to the problem's shared reference and weights (tolg_set_refs / tolg_set_weights with NULL).  The
         solve calls do this themselves when they are given no per-trajectory inputs; this is for callers that drove the C
         ABI on the handle directly."""
-        _capi.check(self.lib.tolg_set_weights(self._h, 0, None, None, None, None, 0, None), "tolg_set_weights")
-        _capi.check(self.lib.tolg_set_refs(self._h, 0, None, None, None, 0, None), "tolg_set_refs")
+        self._call("tolg_set_weights", 0, None, None, None, None, 0, None, stream=False)
+        self._call("tolg_set_refs", 0, None, None, None, 0, None, stream=False)
         self._wts_set = self._refs_set = False
 
-    def _use_pt(self, B, refs, weights):
-        """Point the handle at this call's references (tolg_set_refs) and weights (tolg_set_weights), or back at the
-        problem's shared ones for what is None: every call states its own, nothing carries over from an earlier call.  The
-        weights are detached first, so that references for a new B never meet weights set for an earlier one."""
-        if getattr(self, "_wts_set", False):
-            _capi.check(self.lib.tolg_set_weights(self._h, 0, None, None, None, None, 0, None), "tolg_set_weights")
+    def _use_pt(self, B, refs, wts):
+        """Point the handle at this call's references (tolg_set_refs) and weights (tolg_set_weights), device tensors of a
+        _Batch, or back at the problem's shared ones for what is None: every call states its own, nothing carries over from
+        an earlier call.  The weights are detached first, so that references for a new B never meet weights set for an
+        earlier one."""
+        if self._wts_set:
+            self._call("tolg_set_weights", 0, None, None, None, None, 0, None, stream=False)
             self._wts_set = False
         self._use_refs(B, refs)
-        if weights is None:
-            return
-        q, p, r = (self._dev(a, a.shape) for a in weights)
-        if getattr(self, "_wts_buf", None) is None:
-            nbytes = int(self.lib.tolg_weights_bytes(C.byref(self._p), self.max_batch))
-            self._wts_buf = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_set_weights(self._h, B, _ptr(q), _ptr(p), _ptr(r), _ptr(self._wts_buf),
-                                           C.c_size_t(self._wts_buf.numel() * 8), self._stream())
-        _capi.check(rc, "tolg_set_weights")
-        self._wts_set = True
-        self._wts_keep = (q, p, r)  # the packing kernel reads them on the stream
+        if wts is not None:
+            self._call("tolg_set_weights", B, *map(_ptr, wts), *self._packed("_wts_buf", self.lib.tolg_weights_bytes))
+            self._wts_set = True
+
+    def _use_refs(self, B, refs):
+        """Point the handle at the references refs = (q [B, N+1, 4, 4], xi [B, N+1, 6]) (tolg_set_refs), or back at the
+        problem's shared one when refs is None."""
+        if refs is not None:
+            q, xi = self._dev(refs[0], (B, self.N + 1, 16)), self._dev(refs[1], (B, self.N + 1, 6))  # (staged: views)
+            self._call("tolg_set_refs", B, _ptr(q), _ptr(xi), *self._packed("_refs_buf", self.lib.tolg_refs_bytes))
+            self._refs_set = True
+        elif self._refs_set:
+            self._call("tolg_set_refs", 0, None, None, None, 0, None, stream=False)
+            self._refs_set = False
 
     # ------------------------------------------------------------------------------------------
     def _alloc_result(self, B, K, histories=True):
@@ -298,21 +363,9 @@ class BatchedTrackingILQR:
         solve (tolg_set_weights); omitted, the problem's shared weights.
         xs_init (optional, multiple shooting only): (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6]), a warm start of the shooting
         states (tolg_solve_begin_warm): knots 1..N of the initial guess in place of the reference; knot 0 is x0."""
-        x0_q = self._dev(x0_q, (-1, 16))
-        B = x0_q.shape[0]
-        refs = self._check_refs(B, q_ref, xi_ref)
-        wts = self._check_weights(B, Q, P, R)
-        xs = self._check_xs_init(B, xs_init, mode)
-        x0_xi = self._dev(x0_xi, (B, 6))
-        if us_init is None:
-            us_init = torch.zeros(B, self.N, self.m, dtype=torch.float64, device=self.device)
-        us_init = self._dev(us_init, (B, self.N, self.m))
-        K = int(n_iterations)
-        if out is None:
-            out = self._alloc_result(B, K, histories)
-        o = self._options(mode, K, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg, schedule)
-        self._use_pt(B, refs, wts)
-        return self._begin(o, B, x0_q, x0_xi, us_init, xs, out)
+        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R), xs_init, mode)
+        o = self._options(mode, n_iterations, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg, schedule)
+        return self._start(b, o, histories, out)
 
     def _options(self, mode, K, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg, schedule="auto", check_every=0):
         return _capi.Options(_capi.MODE_MS if mode == "ms" else _capi.MODE_SS, int(K), int(bool(line_search)),
@@ -320,82 +373,55 @@ class BatchedTrackingILQR:
                              float(max_reg if max_reg else 0.0),
                              {"auto": _capi.SCHED_AUTO, "split": _capi.SCHED_SPLIT}[schedule], int(check_every))
 
-    def _check_xs_init(self, B, xs_init, mode):
-        """xs_init = (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6]) checked on the host (ValueError before anything reaches the
-        device) and moved there as [B, N+1, 16] / [B, N+1, 6]; None when omitted."""
-        if xs_init is None:
-            return None
-        if mode != "ms":
-            raise ValueError("xs_init warm-starts the shooting states of multiple shooting: single shooting takes its states "
-                             "from the initial rollout")
-        if not isinstance(xs_init, (tuple, list)) or len(xs_init) != 2:
-            raise ValueError("xs_init is a pair (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6])")
-        q, xi = xs_init
-        qs, xs = tuple(np.shape(q)), tuple(np.shape(xi))
-        if qs != (B, self.N + 1, 4, 4):
-            raise ValueError("xs_init[0] has shape %s, expected (%d, %d, 4, 4)" % (qs, B, self.N + 1))
-        if xs != (B, self.N + 1, 6):
-            raise ValueError("xs_init[1] has shape %s, expected (%d, %d, 6)" % (xs, B, self.N + 1))
-        return self._dev(q, (B, self.N + 1, 16)), self._dev(xi, (B, self.N + 1, 6))
+    def _start(self, b, o, histories=True, out=None):
+        """solve_begin on a staged batch: the handle pointed at its references and weights, then its solve begun."""
+        if out is None:
+            out = self._alloc_result(b.B, o.max_iter, histories)
+        self._use_pt(b.B, b.refs, b.wts)
+        self._hold(b)
+        return self._begin(o, b.B, b.x_q, b.x_xi, b.us, b.xs, out)
 
     def _begin(self, o, B, x0_q, x0_xi, us_init, xs, out):
         """tolg_solve_begin, or tolg_solve_begin_warm when xs = (xs_q, xs_xi) is given (device tensors, checked)."""
-        with torch.cuda.device(self.device):
-            if xs is None:
-                rc = self.lib.tolg_solve_begin(self._h, C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(us_init),
-                                               _ptr(out.J_hist), _ptr(out.grad_hist), _ptr(out.defect_hist),
-                                               _ptr(out.alpha_hist), _ptr(out.mu_hist), self._stream())
-            else:
-                rc = self.lib.tolg_solve_begin_warm(self._h, C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(xs[0]), _ptr(xs[1]),
-                                                    _ptr(us_init), _ptr(out.J_hist), _ptr(out.grad_hist),
-                                                    _ptr(out.defect_hist), _ptr(out.alpha_hist), _ptr(out.mu_hist),
-                                                    self._stream())
-        self._policy_B = 0  # the solve overwrites the held policy (also when it could not start)
-        _capi.check(rc, "tolg_solve_begin_warm" if xs is not None else "tolg_solve_begin")
-        self._inflight = (out, (x0_q, x0_xi, us_init, xs))  # keep the inputs alive until the stream has used them
+        hist = (_ptr(out.J_hist), _ptr(out.grad_hist), _ptr(out.defect_hist), _ptr(out.alpha_hist), _ptr(out.mu_hist))
+        if xs is None:
+            self._call("tolg_solve_begin", C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(us_init), *hist)
+        else:
+            self._call("tolg_solve_begin_warm", C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(xs[0]), _ptr(xs[1]), _ptr(us_init),
+                       *hist)
+        self._inflight = (out, self._inflight[1])
         return out
 
     def solve_iterate(self, n_iter):
         """n_iter passes of the iteration body (backward sweep, rollout, re-linearisation)."""
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_solve_iterate(self._h, int(n_iter), self._stream())
-        _capi.check(rc, "tolg_solve_iterate")
+        self._call("tolg_solve_iterate", int(n_iter))
 
     def solve_iterate_until(self, n_iter, check_every) -> int:
         """Up to n_iter iterations in slices of check_every, stopping once no trajectory is iterating any more
         (tolg_solve_iterate_until: the read-back of one slice overlaps the next).  Returns the iterations queued."""
         n = C.c_int32(0)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_solve_iterate_until(self._h, int(n_iter), int(check_every), C.byref(n), self._stream())
-        _capi.check(rc, "tolg_solve_iterate_until")
+        self._call("tolg_solve_iterate_until", int(n_iter), int(check_every), C.byref(n))
         return int(n.value)
 
     def active_count(self) -> int:
         """Trajectories of the solve in flight that are still being iterated (one small kernel + a host read)."""
         if getattr(self, "_active_buf", None) is None:
             self._active_buf = torch.zeros(1, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_solve_active_count(self._h, _ptr(self._active_buf), self._stream())
-        _capi.check(rc, "tolg_solve_active_count")
+        self._call("tolg_solve_active_count", _ptr(self._active_buf))
         return int(self._active_buf.item())
+
+    def _export(self, fn):
+        out = self._inflight[0]
+        self._call(fn, _ptr(out.xs_q), _ptr(out.xs_xi), _ptr(out.us), _ptr(out.iters), _ptr(out.status), _ptr(out.converged),
+                   batch=out.xs_q.shape[0])
+        return out
 
     def solve_peek(self) -> FitResult:
         """Export the trajectories in flight (xs, us, iters, status) without ending the solve."""
-        out = self._inflight[0]
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_solve_peek(self._h, _ptr(out.xs_q), _ptr(out.xs_xi), _ptr(out.us), _ptr(out.iters),
-                                          _ptr(out.status), _ptr(out.converged), self._stream())
-        _capi.check(rc, "tolg_solve_peek")
-        return out
+        return self._export("tolg_solve_peek")
 
     def solve_end(self) -> FitResult:
-        out = self._inflight[0]
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_solve_end(self._h, _ptr(out.xs_q), _ptr(out.xs_xi), _ptr(out.us), _ptr(out.iters),
-                                         _ptr(out.status), _ptr(out.converged), self._stream())
-        _capi.check(rc, "tolg_solve_end")
-        self._policy_B = out.xs_q.shape[0]
-        return out
+        return self._export("tolg_solve_end")
 
     def fit_batch(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
                   tol_d_norm=1e-6, line_search=False, rollout="nonlinear", max_reg=1e10,
@@ -410,9 +436,13 @@ class BatchedTrackingILQR:
         q_ref [B, N+1, 4, 4], xi_ref [B, N+1, 6] (optional, numpy or torch): a reference per trajectory for this fit.
         Q [B, 12, 12], P [B, 12, 12], R [B, m, m] (optional, all three or none, diagonal): cost weights per trajectory.
         xs_init (optional, mode="ms"): warm-start shooting states, as for solve_begin."""
-        self.solve_begin(x0_q, x0_xi, us_init, mode, n_iterations, tol_grad_norm, tol_d_norm, line_search, rollout,
-                         max_reg, histories, out, schedule, q_ref, xi_ref, Q, P, R, xs_init)
-        self.iterations_issued = self.solve_iterate_until(int(n_iterations), int(check_every or 0))
+        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R), xs_init, mode)
+        o = self._options(mode, n_iterations, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg, schedule)
+        return self._fit(b, o, check_every, histories, out)
+
+    def _fit(self, b, o, check_every, histories=True, out=None):
+        self._start(b, o, histories, out)
+        self.iterations_issued = self.solve_iterate_until(o.max_iter, int(check_every or 0))
         return self.solve_end()
 
     def solve_batch_one_call(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
@@ -421,30 +451,16 @@ class BatchedTrackingILQR:
         """The same fit through the single entry point tolg_solve_batch (what a C / C++ caller binds): begin,
         iterations (tolg_options.check_every: 0 = all of them, never synchronising), end in one call.
         q_ref / xi_ref, Q / P / R: as for fit_batch."""
-        x0_q = self._dev(x0_q, (-1, 16))
-        B = x0_q.shape[0]
-        refs = self._check_refs(B, q_ref, xi_ref)
-        wts = self._check_weights(B, Q, P, R)
-        x0_xi = self._dev(x0_xi, (B, 6))
-        if us_init is None:
-            us_init = torch.zeros((B, self.N, self.m), dtype=torch.float64, device=self.device)
-        us_init = self._dev(us_init, (B, self.N, self.m))
+        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R))
         K = int(n_iterations)
-        out = self._alloc_result(B, K, True)
-        o = _capi.Options(_capi.MODE_MS if mode == "ms" else _capi.MODE_SS, K, int(bool(line_search)),
-                          int(rollout == "linear"), float(tol_grad_norm), float(tol_d_norm),
-                          float(max_reg if max_reg else 0.0),
-                          {"auto": _capi.SCHED_AUTO, "split": _capi.SCHED_SPLIT}[schedule], int(check_every))
-        self._use_pt(B, refs, wts)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_solve_batch(self._h, C.byref(o), B, _ptr(x0_q), _ptr(x0_xi), _ptr(us_init), _ptr(out.xs_q),
-                                           _ptr(out.xs_xi), _ptr(out.us), _ptr(out.J_hist), _ptr(out.grad_hist),
-                                           _ptr(out.defect_hist), _ptr(out.alpha_hist), _ptr(out.mu_hist), _ptr(out.iters),
-                                           _ptr(out.status), _ptr(out.converged), self._stream())
-        self._policy_B = 0
-        _capi.check(rc, "tolg_solve_batch")
-        self._policy_B = B
-        torch.cuda.current_stream(self.device).synchronize()  # the inputs above must outlive the queued work
+        out = self._alloc_result(b.B, K, True)
+        o = self._options(mode, K, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg, schedule, check_every)
+        self._use_pt(b.B, b.refs, b.wts)
+        self._hold(b)
+        self._call("tolg_solve_batch", C.byref(o), b.B, _ptr(b.x_q), _ptr(b.x_xi), _ptr(b.us), _ptr(out.xs_q), _ptr(out.xs_xi),
+                   _ptr(out.us), _ptr(out.J_hist), _ptr(out.grad_hist), _ptr(out.defect_hist), _ptr(out.alpha_hist),
+                   _ptr(out.mu_hist), _ptr(out.iters), _ptr(out.status), _ptr(out.converged), batch=b.B)
+        torch.cuda.current_stream(self.device).synchronize()  # the call returns with its results in place
         return out
 
     # ------------------------------------------------------------------------------------------
@@ -453,12 +469,11 @@ class BatchedTrackingILQR:
         (ALConstrainedCost + InputConstraint).  lam, imu: device tensors [B, N, 2m]."""
         if lb is None:
             self._al = None
-            rc = self.lib.tolg_set_al(self._h, None, None, None, None)
+            self._call("tolg_set_al", None, None, None, None, stream=False)
         else:
             lb = self._dev(lb, (self.m,)); ub = self._dev(ub, (self.m,))
-            self._al = (lb, ub, lam, imu)  # keep alive
-            rc = self.lib.tolg_set_al(self._h, _ptr(lb), _ptr(ub), _ptr(lam), _ptr(imu))
-        _capi.check(rc, "tolg_set_al")
+            self._al = (lb, ub, lam, imu)  # the handle reads them in every solve until they are detached
+            self._call("tolg_set_al", _ptr(lb), _ptr(ub), _ptr(lam), _ptr(imu), stream=False)
 
     def al_fit_batch(self, x0_q, x0_xi, us_init, lb, ub, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
                      tol_d_norm=1e-6, tol_constr=1e-2, mu0=1e-2, mu_scale=10.0, mu_max=1e8, line_search=False,
@@ -467,10 +482,9 @@ class BatchedTrackingILQR:
         independent problems: every outer iteration re-solves from (x0, us_init) -- no warm start, as in
         the reference -- then updates multipliers on the device.  Returns (FitResult, info dict).
         q_ref / xi_ref: a reference per trajectory, Q / P / R: weights per trajectory, as for fit_batch."""
-        x0_q = self._dev(x0_q, (-1, 16))
-        B = x0_q.shape[0]
-        self._check_refs(B, q_ref, xi_ref)
-        self._check_weights(B, Q, P, R)
+        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R))
+        B = b.B
+        o = self._options("ms", n_ilqr_iters, line_search, "nonlinear", tol_grad_norm, tol_d_norm, 1e10)
         f64 = dict(dtype=torch.float64, device=self.device)
         lam = torch.zeros(B, self.N, 2 * self.m, **f64)
         imu = torch.full((B, self.N, 2 * self.m), float(mu0), **f64)
@@ -484,9 +498,7 @@ class BatchedTrackingILQR:
         final = None
         try:
             for outer in range(int(n_al_iters)):
-                res = self.fit_batch(x0_q, x0_xi, us_init, mode="ms", n_iterations=n_ilqr_iters,
-                                     tol_grad_norm=tol_grad_norm, tol_d_norm=tol_d_norm, line_search=line_search,
-                                     rollout="nonlinear", q_ref=q_ref, xi_ref=xi_ref, Q=Q, P=P, R=R)
+                res = self._fit(b, o, 16)
                 if final is None:
                     final = res
                 else:  # problems that had already converged keep the result of their converging solve
@@ -499,11 +511,8 @@ class BatchedTrackingILQR:
                     final = res
                 if on_outer is not None:  # before the multiplier update, like on_iteration_al (:3253-3259)
                     on_outer(outer, final, lam, imu, mu)
-                with torch.cuda.device(self.device):
-                    rc = self.lib.tolg_al_update(self._h, B, _ptr(final.us), _ptr(lb_d), _ptr(ub_d), _ptr(lam), _ptr(imu),
-                                                 _ptr(mu), float(mu_scale), float(mu_max), float(tol_constr),
-                                                 _ptr(maxviol), _ptr(alconv), self._stream())
-                _capi.check(rc, "tolg_al_update")
+                self._call("tolg_al_update", B, _ptr(final.us), _ptr(lb_d), _ptr(ub_d), _ptr(lam), _ptr(imu), _ptr(mu),
+                           float(mu_scale), float(mu_max), float(tol_constr), _ptr(maxviol), _ptr(alconv))
                 if bool(alconv.all().item()):
                     break
         finally:
@@ -516,12 +525,8 @@ class BatchedTrackingILQR:
         """One _linearization + _backward_pass (+ gradient norm) on given trajectories.  q_ref / xi_ref: a reference per
         trajectory, Q / P / R: weights per trajectory, as for fit_batch (rollout / expected_change behind this call use the
         same references and weights)."""
-        xs_q = self._dev(xs_q, (-1, self.N + 1, 16))
-        B = xs_q.shape[0]
-        refs = self._check_refs(B, q_ref, xi_ref)
-        wts = self._check_weights(B, Q, P, R)
-        xs_xi = self._dev(xs_xi, (B, self.N + 1, 6))
-        us = self._dev(us, (B, self.N, self.m))
+        b = self._stage(xs_q, xs_xi, us, (q_ref, xi_ref), (Q, P, R), traj=True)
+        B = b.B
         f64 = dict(dtype=torch.float64, device=self.device)
         md = torch.empty(B, 2, **f64)
         md[:, 0] = mu
@@ -530,15 +535,10 @@ class BatchedTrackingILQR:
                  lx=torch.empty(B, self.N + 1, 12, **f64), lxx11=torch.empty(B, self.N + 1, 6, 6, **f64),
                  k=torch.empty(B, self.N, self.m, **f64), K=torch.empty(B, self.N, self.m, 12, **f64),
                  J=torch.empty(B, **f64), dnorm=torch.empty(B, **f64), grad=torch.empty(B, **f64), mu_delta=md)
-        self._use_pt(B, refs, wts)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_linearize_backward(self._h, int(ms), float(max_reg), B, _ptr(xs_q), _ptr(xs_xi), _ptr(us),
-                                                  _ptr(md), _ptr(r["Fx"]), _ptr(r["d"]), _ptr(r["lx"]), _ptr(r["lxx11"]),
-                                                  _ptr(r["k"]), _ptr(r["K"]), _ptr(r["J"]), _ptr(r["dnorm"]),
-                                                  _ptr(r["grad"]), self._stream())
-        self._policy_B = 0
-        _capi.check(rc, "tolg_linearize_backward")
-        self._policy_B = B
+        self._use_pt(B, b.refs, b.wts)
+        self._hold(b)
+        self._call("tolg_linearize_backward", int(ms), float(max_reg), B, _ptr(b.x_q), _ptr(b.x_xi), _ptr(b.us), _ptr(md),
+                   *(_ptr(r[k]) for k in ("Fx", "d", "lx", "lxx11", "k", "K", "J", "dnorm", "grad")), batch=B)
         return r
 
     def eval_knot(self, i, x_q, x_xi, u=None):
@@ -555,13 +555,8 @@ class BatchedTrackingILQR:
             r.update(f_q=torch.zeros(n, 4, 4, **f64), f_xi=torch.zeros(n, 6, **f64), Fx=torch.zeros(n, 12, 12, **f64),
                      Fu=torch.zeros(n, 12, self.m, **f64), lu=torch.zeros(n, self.m, **f64),
                      luu=torch.zeros(n, self.m, self.m, **f64))
-        g = lambda k: _ptr(r.get(k))  # noqa: E731
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_eval_knot(self._h, int(i), n, _ptr(x_q), _ptr(x_xi), _ptr(u_d), g("f_q"), g("f_xi"),
-                                         g("Fx"), g("Fu"), g("l"), g("lx"), g("lxx"), g("lu"), g("luu"), g("err"),
-                                         self._stream())
-        self._policy_B = 0  # the probe overwrites the nominal trajectory (include/tolg.h, held policy)
-        _capi.check(rc, "tolg_eval_knot")
+        self._call("tolg_eval_knot", int(i), n, _ptr(x_q), _ptr(x_xi), _ptr(u_d),
+                   *(_ptr(r.get(k)) for k in ("f_q", "f_xi", "Fx", "Fu", "l", "lx", "lxx", "lu", "luu", "err")))
         return r
 
     def rollout(self, B, alpha=1.0, ms=True, rollout="nonlinear"):
@@ -570,10 +565,7 @@ class BatchedTrackingILQR:
         xs_q = torch.empty(B, self.N + 1, 4, 4, **f64)
         xs_xi = torch.empty(B, self.N + 1, 6, **f64)
         us = torch.empty(B, self.N, self.m, **f64)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_rollout(self._h, int(ms), int(rollout == "linear"), float(alpha), B, _ptr(xs_q),
-                                       _ptr(xs_xi), _ptr(us), self._stream())
-        _capi.check(rc, "tolg_rollout")
+        self._call("tolg_rollout", int(ms), int(rollout == "linear"), float(alpha), B, _ptr(xs_q), _ptr(xs_xi), _ptr(us))
         return xs_q, xs_xi, us
 
     def expected_change(self, B, form="auto"):
@@ -583,19 +575,15 @@ class BatchedTrackingILQR:
         "auto" (ring + hand-back: what a solve runs).  Returns (ecc [B, 2], flag [B])."""
         ecc = torch.empty(B, 2, dtype=torch.float64, device=self.device)
         flag = torch.zeros(B, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_expected_change(self._h, {"statement": 0, "ring": 1, "auto": 2}[form], B, _ptr(ecc),
-                                               _ptr(flag), self._stream())
-        _capi.check(rc, "tolg_expected_change")
+        self._call("tolg_expected_change", {"statement": 0, "ring": 1, "auto": 2}[form], B, _ptr(ecc), _ptr(flag))
         return ecc, flag
 
     # ------------------------------------------------------------------------------------------
     def _held_B(self):
-        B = getattr(self, "_policy_B", 0)
-        if not B:
+        if not self._policy_B:
             raise ValueError("no policy is held: it is left by solve_end / fit_batch / solve_batch_one_call or "
                              "linearize_backward, and cleared by solve_begin and eval_knot")
-        return B
+        return self._policy_B
 
     def gains(self):
         """The feedback gains of the held policy (what the reference's fit leaves in self._k / self._K): {"k": [B, N, m],
@@ -606,19 +594,8 @@ class BatchedTrackingILQR:
         f64 = dict(dtype=torch.float64, device=self.device)
         k = torch.empty(B, self.N, self.m, **f64)
         K = torch.empty(B, self.N, self.m, 12, **f64)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_solve_gains(self._h, B, _ptr(k), _ptr(K), self._stream())
-        _capi.check(rc, "tolg_solve_gains")
+        self._call("tolg_solve_gains", B, _ptr(k), _ptr(K))
         return {"k": k, "K": K}
-
-    def _host_f64(self, name, a, shape):
-        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-        a = np.asarray(a, dtype=np.float64)
-        if a.ndim != len(shape) or any(n is not None and n != s for n, s in zip(shape, a.shape)):
-            raise ValueError("%s has shape %s, expected %s" % (name, tuple(a.shape), tuple("S" if n is None else n for n in shape)))
-        if not np.all(np.isfinite(a)):
-            raise ValueError("%s must be finite" % name)
-        return a
 
     def policy_rollout(self, dx0=None, noise=None, S=None, trajectories=False) -> PolicyRollout:
         """S closed-loop rollouts per trajectory of the held policy u = u*_i + K_i (x (-) x*_i) with exact dynamics
@@ -629,10 +606,10 @@ class BatchedTrackingILQR:
         B = self._held_B()
         shapes = []
         if dx0 is not None:
-            dx0 = self._host_f64("dx0", dx0, (B, None, 12))
+            dx0 = _checked("dx0", dx0, (B, None, 12), finite=True)
             shapes.append(dx0.shape[1])
         if noise is not None:
-            noise = self._host_f64("noise", noise, (B, None, self.N, 6))
+            noise = _checked("noise", noise, (B, None, self.N, 6), finite=True)
             shapes.append(noise.shape[1])
         if S is not None:
             shapes.append(int(S))
@@ -651,23 +628,21 @@ class BatchedTrackingILQR:
             r.xs_q = torch.empty(B, S, self.N + 1, 4, 4, **f64)
             r.xs_xi = torch.empty(B, S, self.N + 1, 6, **f64)
             r.us = torch.empty(B, S, self.N, self.m, **f64)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_policy_rollout(self._h, B, S, _ptr(d_dx0), _ptr(d_w), _ptr(r.J), _ptr(r.status), _ptr(r.xs_q),
-                                              _ptr(r.xs_xi), _ptr(r.us), self._stream())
-        _capi.check(rc, "tolg_policy_rollout")
-        self._policy_keep = (d_dx0, d_w)  # the kernel reads them on the stream
+        self._hold((d_dx0, d_w))
+        self._call("tolg_policy_rollout", B, S, _ptr(d_dx0), _ptr(d_w), _ptr(r.J), _ptr(r.status), _ptr(r.xs_q), _ptr(r.xs_xi),
+                   _ptr(r.us))
         return r
 
     # ------------------------------------------------------------------------------------------
-    def _check_paths(self, B, path_q, path_xi):
+    def _paths(self, B, path_q, path_xi):
         """Paths [B, T+1, 4, 4] / [B, T+1, 6] checked on the host and moved to the device as [B, T+1, 16] / [B, T+1, 6];
         returns (q, xi, T)."""
-        qs, xs = tuple(np.shape(path_q)), tuple(np.shape(path_xi))
-        if len(qs) != 4 or qs[0] != B or qs[2:] != (4, 4) or qs[1] < 2:
-            raise ValueError("path_q has shape %s, expected (%d, T+1, 4, 4) with T >= 1" % (qs, B))
-        if xs != (B, qs[1], 6):
-            raise ValueError("path_xi has shape %s, expected (%d, %d, 6)" % (xs, B, qs[1]))
-        return self._dev(path_q, (B, qs[1], 16)), self._dev(path_xi, (B, qs[1], 6)), qs[1] - 1
+        q = _checked("path_q", path_q, (B, None, 4, 4))
+        n = q.shape[1]
+        if n < 2:
+            raise ValueError("path_q has %d knots, expected T+1 >= 2" % n)
+        xi = _checked("path_xi", path_xi, (B, n, 6))
+        return self._dev(q, (B, n, 16)), self._dev(xi, (B, n, 6)), n - 1
 
     def _check_t0(self, B, t0):
         if t0 is None:
@@ -680,15 +655,8 @@ class BatchedTrackingILQR:
         return torch.as_tensor(a.astype(np.int32), device=self.device)
 
     def _set_ref_windows(self, B, q, xi, T, t0_d, t):
-        if getattr(self, "_refs_buf", None) is None:
-            nbytes = int(self.lib.tolg_refs_bytes(C.byref(self._p), self.max_batch))
-            self._refs_buf = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_set_ref_windows(self._h, B, _ptr(q), _ptr(xi), int(T), _ptr(t0_d), int(t), _ptr(self._refs_buf),
-                                               C.c_size_t(self._refs_buf.numel() * 8), self._stream())
-        _capi.check(rc, "tolg_set_ref_windows")
+        self._call("tolg_set_ref_windows", B, _ptr(q), _ptr(xi), int(T), _ptr(t0_d), int(t), *self._packed("_refs_buf", self.lib.tolg_refs_bytes))
         self._refs_set = True
-        self._windows_keep = (q, xi, t0_d)  # the gather kernel reads them on the stream
 
     def set_ref_windows(self, path_q, path_xi, t, t0=None):
         """Point the handle at the windows of B longer paths (tolg_set_ref_windows): trajectory b tracks knots
@@ -700,8 +668,10 @@ class BatchedTrackingILQR:
             raise ValueError("path_q: batch %d outside 1..%d" % (B, self.max_batch))
         if int(t) < 0:
             raise ValueError("t must be non-negative")
-        q, xi, T = self._check_paths(B, path_q, path_xi)
-        self._set_ref_windows(B, q, xi, T, self._check_t0(B, t0), int(t))
+        q, xi, T = self._paths(B, path_q, path_xi)
+        t0_d = self._check_t0(B, t0)
+        self._hold((q, xi, t0_d))
+        self._set_ref_windows(B, q, xi, T, t0_d, int(t))
 
     def mpc_advance(self, w=None, J_cl=None):
         """One receding-horizon step on the held policy (tolg_mpc_advance): x_next = f(x*_0, u*_0) + [0; w] with the exact
@@ -710,23 +680,24 @@ class BatchedTrackingILQR:
         twist.  J_cl (a float64 device tensor [B], optional) is accumulated with the stage cost l(x*_0, u*_0) at knot 0.
         Returns a dict of device tensors: x_next_q [B, 4, 4], x_next_xi, u [B, m], xs_q, xs_xi, us, J_cl."""
         B = self._held_B()
-        f64 = dict(dtype=torch.float64, device=self.device)
-        d_w = None if w is None else self._dev(self._host_f64("w", w, (B, 6)), (B, 6))
+        d_w = None if w is None else self._dev(_checked("w", w, (B, 6), finite=True), (B, 6))
         if J_cl is not None and (not isinstance(J_cl, torch.Tensor) or J_cl.dtype != torch.float64 or
                                  tuple(J_cl.shape) != (B,) or J_cl.device != self.device or not J_cl.is_contiguous()):
             raise ValueError("J_cl must be a contiguous float64 tensor of shape (%d,) on %s" % (B, self.device))
-        r = dict(x_next_q=torch.empty(B, 4, 4, **f64), x_next_xi=torch.empty(B, 6, **f64), u=torch.empty(B, self.m, **f64),
-                 xs_q=torch.empty(B, self.N + 1, 4, 4, **f64), xs_xi=torch.empty(B, self.N + 1, 6, **f64),
-                 us=torch.empty(B, self.N, self.m, **f64), J_cl=J_cl)
+        r = self._advance_out(B, J_cl)
+        self._hold(d_w)
         self._advance(B, d_w, r)
         return r
 
+    def _advance_out(self, B, J_cl):
+        f64 = dict(dtype=torch.float64, device=self.device)
+        return dict(x_next_q=torch.empty(B, 4, 4, **f64), x_next_xi=torch.empty(B, 6, **f64), u=torch.empty(B, self.m, **f64),
+                    xs_q=torch.empty(B, self.N + 1, 4, 4, **f64), xs_xi=torch.empty(B, self.N + 1, 6, **f64),
+                    us=torch.empty(B, self.N, self.m, **f64), J_cl=J_cl)
+
     def _advance(self, B, d_w, r):
-        with torch.cuda.device(self.device):
-            rc = self.lib.tolg_mpc_advance(self._h, B, _ptr(d_w), _ptr(r["x_next_q"]), _ptr(r["x_next_xi"]), _ptr(r["u"]),
-                                           _ptr(r["xs_q"]), _ptr(r["xs_xi"]), _ptr(r["us"]), _ptr(r["J_cl"]), self._stream())
-        _capi.check(rc, "tolg_mpc_advance")
-        self._advance_keep = d_w
+        self._call("tolg_mpc_advance", B, _ptr(d_w), *(_ptr(r[k]) for k in ("x_next_q", "x_next_xi", "u", "xs_q", "xs_xi", "us",
+                                                                           "J_cl")))
 
     def mpc(self, x0_q, x0_xi, path_q, path_xi, steps, us_init=None, t0=None, iters_per_step=5, first_iters=50,
             warm="states", noise=None, mode="ms", line_search=False, rollout="nonlinear", tol_grad_norm=1e-6, tol_d_norm=1e-6,
@@ -743,7 +714,7 @@ class BatchedTrackingILQR:
         plant step; the FitResult carries histories then).  Not with an augmented-Lagrangian constraint attached.  The handle is
         left on the shared reference and weights.
         x0_q [B, 4, 4], x0_xi [B, 6], path_q [B, T+1, 4, 4], path_xi [B, T+1, 6]."""
-        if getattr(self, "_al", None) is not None:
+        if self._al is not None:
             raise ValueError("mpc under an augmented-Lagrangian constraint is not supported: detach it with set_al(None)")
         if warm not in ("states", "controls"):
             raise ValueError("warm must be 'states' or 'controls'")
@@ -755,38 +726,32 @@ class BatchedTrackingILQR:
         steps, K0, K = int(steps), int(first_iters), int(iters_per_step)
         if steps < 1 or K0 < 0 or K < 0 or int(check_every) < 0:
             raise ValueError("steps must be >= 1, first_iters, iters_per_step and check_every >= 0")
-        qs = tuple(np.shape(x0_q))
-        if len(qs) not in (2, 3) or qs[1:] not in ((4, 4), (16,)):
-            raise ValueError("x0_q has shape %s, expected (B, 4, 4)" % (qs,))
-        B = qs[0]
+        x0_q = _checked("x0_q", x0_q, (None, 16) if np.ndim(x0_q) == 2 else (None, 4, 4))
+        B = x0_q.shape[0]
         if not 1 <= B <= self.max_batch:
             raise ValueError("batch %d outside 1..%d" % (B, self.max_batch))
-        if tuple(np.shape(x0_xi)) != (B, 6):
-            raise ValueError("x0_xi has shape %s, expected (%d, 6)" % (tuple(np.shape(x0_xi)), B))
-        x0_q, x0_xi = self._dev(x0_q, (B, 16)), self._dev(x0_xi, (B, 6))
-        if us_init is not None and tuple(np.shape(us_init)) != (B, self.N, self.m):
-            raise ValueError("us_init has shape %s, expected (%d, %d, %d)" % (tuple(np.shape(us_init)), B, self.N, self.m))
-        pq, pxi, T = self._check_paths(B, path_q, path_xi)
+        x0_xi = _checked("x0_xi", x0_xi, (B, 6))
+        if us_init is not None:
+            us_init = _checked("us_init", us_init, (B, self.N, self.m))
+        pq, pxi, T = self._paths(B, path_q, path_xi)
         t0_d = self._check_t0(B, t0)
-        wts = self._check_weights(B, Q, P, R)
+        b = self._stage(x0_q, x0_xi, us_init, weights=(Q, P, R))
         if noise is not None:
-            noise = self._host_f64("noise", noise, (B, steps, 6))
+            noise = _checked("noise", noise, (B, steps, 6), finite=True)
             noise = self._dev(np.ascontiguousarray(noise.transpose(1, 0, 2)), (steps, B, 6))  # step t: one contiguous [B, 6]
         f64 = dict(dtype=torch.float64, device=self.device)
-        us = torch.zeros(B, self.N, self.m, **f64) if us_init is None else self._dev(us_init, (B, self.N, self.m))
         res = MPCResult(xs_q=torch.empty(B, steps + 1, 4, 4, **f64), xs_xi=torch.empty(B, steps + 1, 6, **f64),
                         us=torch.empty(B, steps, self.m, **f64), J=torch.zeros(B, **f64),
                         iters=torch.empty(B, steps, dtype=torch.int32, device=self.device),
                         status=torch.empty(B, steps, dtype=torch.int32, device=self.device))
-        res.xs_q[:, 0] = x0_q.reshape(B, 4, 4)
-        res.xs_xi[:, 0] = x0_xi
+        res.xs_q[:, 0] = b.x_q.reshape(B, 4, 4)
+        res.xs_xi[:, 0] = b.x_xi
         # the plant state and the warm start: written by tolg_mpc_advance, read by the next begin (stream-ordered)
-        adv = dict(x_next_q=torch.empty(B, 4, 4, **f64), x_next_xi=torch.empty(B, 6, **f64), u=torch.empty(B, self.m, **f64),
-                   xs_q=torch.empty(B, self.N + 1, 4, 4, **f64), xs_xi=torch.empty(B, self.N + 1, 6, **f64),
-                   us=torch.empty(B, self.N, self.m, **f64), J_cl=res.J)
-        x_q, x_xi = x0_q, x0_xi
+        adv = self._advance_out(B, res.J)
+        self._hold((b, pq, pxi, t0_d, noise, adv))
+        x_q, x_xi, us = b.x_q, b.x_xi, b.us
         try:
-            self._use_pt(B, None, wts)
+            self._use_pt(B, None, b.wts)
             for t in range(steps):
                 self._set_ref_windows(B, pq, pxi, T, t0_d, t)
                 n = K0 if t == 0 else K
