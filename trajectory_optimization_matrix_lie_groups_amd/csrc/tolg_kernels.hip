@@ -3971,6 +3971,55 @@ static KernelTable kernel_table_for(const tolg_problem& p, const Consts& c, int 
   return dense ? kernel_table<6, false, true, false, PT>(lds_per_block) : kernel_table<6, false, false, false, PT>(lds_per_block);
 }
 
+// The line search of a solve: what runs between the backward sweep and the re-linearisation, chosen once by solve_begin
+// (ls_plan) and run by iterate.  ns = 0: no search (MS accept-always).
+struct LsPlan {
+  enum Prologue { NONE, RING, SIDE };
+  struct Stage { int a0, n; };  // step sizes a0 .. a0 + n - 1 (run_ls_stage)
+  int ms;        // 1 multiple shooting: the merit search; 0 single shooting: backtracking
+  bool fused;    // ns = 0: the accept-always rollout and the re-linearisation in one launch (h->kt.rollout_lin)
+  Prologue pro;  // before the first stage: RING run_affine_dev on the main stream, SIDE the expected change on the side stream,
+  bool split;    // ... there the statement form alone (TOLG_SCHED_SPLIT) instead of the ring form and the statement redo
+  int linear;    // 1: the stages roll out with rollout = 'linear'
+  int ns;
+  Stage st[4];
+};
+// The last stage of a search leaves its accepted candidates in its n slots, 0 when it does not: k_linearize reads them there (no
+// copy).  Not a one-alpha stage (its candidates are in place), not in a solve on the affine path (its candidates exist only
+// where k_affine_commit writes them)
+static int ls_kept_slots(const LsPlan& L, const Params& P) {
+  return (L.ns > 0 && L.st[L.ns - 1].n > 1 && !P.affine) ? L.st[L.ns - 1].n : 0;
+}
+// the list of undecided trajectories stage s runs on: stage 0 none (the flags), stage s > 0 the list select s - 1 filled
+static int ls_list_in(int s) { return s == 0 ? -1 : (s - 1) & 1; }
+
+// What a handle creates on first use, not in tolg_create: a stream, or a few device ints and their pinned host copies, with two
+// events.  All or nothing: the handle holds it only when every piece exists (a partial set-up left behind by a failed call
+// would be taken for a complete one by the next call).
+struct LazyRes {
+  hipStream_t stream = nullptr;
+  int *dev = nullptr, *host = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  void release() {
+    for (auto e : ev) if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (dev) (void)hipFree(dev);
+    if (host) (void)hipHostFree(host);
+    *this = LazyRes();
+  }
+};
+static int lazy_create(LazyRes& r, int n_ints) {  // n_ints = 0: the stream form
+  if (r.ev[1]) return 0;
+  LazyRes t;
+  bool ok = n_ints ? hipMalloc((void**)&t.dev, n_ints * sizeof(int)) == hipSuccess &&
+                         hipHostMalloc((void**)&t.host, n_ints * sizeof(int), hipHostMallocDefault) == hipSuccess
+                   : hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking) == hipSuccess;
+  for (int k = 0; ok && k < 2; k++) ok = hipEventCreateWithFlags(&t.ev[k], hipEventDisableTiming) == hipSuccess;
+  if (!ok) { t.release(); return TOLG_E_LAUNCH; }
+  r = t;
+  return 0;
+}
+
 struct tolg_handle_s {
   tolg_problem prob;
   Consts hc;
@@ -3980,6 +4029,7 @@ struct tolg_handle_s {
   Params P;  // pointers carved for Bp_max; per-solve Bp may be smaller (arrays are re-strided)
   Params run;         // parameters of the solve in flight (tolg_solve_begin .. tolg_solve_end)
   tolg_options run_opt;
+  LsPlan run_ls;      // ... and its line search
   int run_it;         // iterations issued so far
   bool running;
   int lds_per_block;  // hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KB on MI355X)
@@ -4002,11 +4052,9 @@ struct tolg_handle_s {
   bool k2_full_only, ls_one_wave;
   const double *al_lb, *al_ub, *al_lambda, *al_imu;  // augmented-Lagrangian terms (null = off)
   // early exit of a sliced solve (tolg_solve_iterate_until): two device counters, their pinned host copies, two events
-  int *d_cnt = nullptr, *h_cnt = nullptr;
-  hipEvent_t cnt_ev[2] = {nullptr, nullptr};
+  LazyRes cnt;
   // merit search: the linear alpha = 1 rollout (k_expected_change) runs on a side stream beside the first line-search stage
-  hipStream_t side = nullptr;
-  hipEvent_t side_ev[2] = {nullptr, nullptr};
+  LazyRes side;
   // timing
   bool timing;
   std::vector<hipEvent_t> ev;  // pairs
@@ -4017,6 +4065,10 @@ struct tolg_handle_s {
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // the batch the device arrays are strided for: B rounded up to whole quads (the padded trajectories replicate b = B-1)
 static int padded_batch(int B) { return (B + 3) / 4 * 4; }
+// the two recurring launch grids: one thread per padded trajectory in groups of 64, one thread per (knot, trajectory) in
+// groups of 256
+static dim3 traj_grid(const Params& P) { return dim3((P.Bp + 63) / 64); }
+static dim3 knot_grid(int knots, int Bp) { return dim3((unsigned)(((size_t)knots * Bp + 255) / 256)); }
 
 // B trajectories fit the handle and the per-trajectory references and weights it holds (tolg_set_refs, tolg_set_weights):
 // what every batch call on the handle's workspace requires
@@ -4056,58 +4108,47 @@ struct Carve {
   }
 };
 
-static size_t carve_all(const tolg_problem* pr, int Bp, char* base, Params* P, Consts** dc) {
+// the workspace arrays of P for a batch of Bp, in workspace order; base = null only counts the bytes (tolg_workspace_bytes)
+static size_t carve_all(const tolg_problem* pr, int Bp, char* base, Params& P) {
   Carve c{base, 0};
   size_t N = (size_t)pr->N, m = (size_t)pr->m, B = (size_t)Bp;
-  Consts* cc = c.take<Consts>(1);
-  double* ref = c.take<double>((N + 1) * 13);
-  double* cur = c.take<double>(13 * (N + 1) * B);
-  double* cur_u = c.take<double>(m * N * B);
-  double* cand = c.take<double>(13 * (N + 1) * B);
-  double* cand_u = c.take<double>(m * N * B);
-  double* REC = c.take<double>((N + 1) * (size_t)REC_FMAX * B);
-  double* SC = c.take<double>((N + 1) * B);
-  double* SD = c.take<double>(N * B);
-  double* GK = c.take<double>(N * m * B * 13);
-  double* mu = c.take<double>(B);
-  double* delta = c.take<double>(B);
-  double* Jc = c.take<double>(B);
-  double* dn = c.take<double>(B);
-  double* grad = c.take<double>(B);
-  int* active = c.take<int>(B);
-  int* iters = c.take<int>(B);
-  int* status = c.take<int>(B);
-  int* conv = c.take<int>(B);
-  double* slot_x = c.take<double>((size_t)NSLOT * 13 * (N + 1) * B);
-  double* slot_u = c.take<double>((size_t)NSLOT * m * N * B);
-  double* Jtrial = c.take<double>(20 * B);
-  double* dtrial = c.take<double>(20 * B);
-  double* ecc = c.take<double>(2 * B);
-  double* dweight = c.take<double>(2 * B);
-  double* ls_alpha = c.take<double>(B);
-  int* ls_accept = c.take<int>(B);
-  int* ls_slot = c.take<int>(B);
-  int* k2_redo = c.take<int>(B / 4 + 1);
-  int* k2_hint = c.take<int>(B / 4 + 1);
-  int* ec_redo = c.take<int>(B);
-  int* ls_list = c.take<int>(2 * B);
-  int* ls_count = c.take<int>(64);
-  int* ls_pos = c.take<int>(2 * B);
-  double* LSC = c.take<double>((size_t)NSLOT * (N + 1) * B);
-  double* LSD = c.take<double>((size_t)NSLOT * N * B);
-  double* ED = c.take<double>((N + 1) * 32 * B);
-  if (P) {
-    P->ED = ED; P->affine = 0; P->pad3 = 0;
-    P->k2_redo = k2_redo; P->k2_hint = k2_hint;
-    P->ec_redo = ec_redo;
-    P->ls_list = ls_list; P->ls_count = ls_count; P->ls_pos = ls_pos; P->LSC = LSC; P->LSD = LSD;
-    P->slot_x = slot_x; P->slot_u = slot_u; P->Jtrial = Jtrial; P->dtrial = dtrial; P->ecc = ecc;
-    P->dweight = dweight; P->ls_alpha = ls_alpha; P->ls_accept = ls_accept; P->ls_slot = ls_slot;
-    P->c = cc; P->ref = ref; P->cur = cur; P->cur_u = cur_u; P->cand = cand; P->cand_u = cand_u;
-    P->REC = REC; P->SC = SC; P->SD = SD; P->GK = GK; P->mu = mu; P->delta = delta; P->Jc = Jc;
-    P->dn = dn; P->grad = grad; P->active = active; P->iters = iters; P->status = status; P->conv = conv;
-  }
-  if (dc) *dc = cc;
+  P.c = c.take<Consts>(1);
+  P.ref = c.take<double>((N + 1) * 13);
+  P.cur = c.take<double>(13 * (N + 1) * B);
+  P.cur_u = c.take<double>(m * N * B);
+  P.cand = c.take<double>(13 * (N + 1) * B);
+  P.cand_u = c.take<double>(m * N * B);
+  P.REC = c.take<double>((N + 1) * (size_t)REC_FMAX * B);
+  P.SC = c.take<double>((N + 1) * B);
+  P.SD = c.take<double>(N * B);
+  P.GK = c.take<double>(N * m * B * 13);
+  P.mu = c.take<double>(B);
+  P.delta = c.take<double>(B);
+  P.Jc = c.take<double>(B);
+  P.dn = c.take<double>(B);
+  P.grad = c.take<double>(B);
+  P.active = c.take<int>(B);
+  P.iters = c.take<int>(B);
+  P.status = c.take<int>(B);
+  P.conv = c.take<int>(B);
+  P.slot_x = c.take<double>((size_t)NSLOT * 13 * (N + 1) * B);
+  P.slot_u = c.take<double>((size_t)NSLOT * m * N * B);
+  P.Jtrial = c.take<double>(20 * B);
+  P.dtrial = c.take<double>(20 * B);
+  P.ecc = c.take<double>(2 * B);
+  P.dweight = c.take<double>(2 * B);
+  P.ls_alpha = c.take<double>(B);
+  P.ls_accept = c.take<int>(B);
+  P.ls_slot = c.take<int>(B);
+  P.k2_redo = c.take<int>(B / 4 + 1);
+  P.k2_hint = c.take<int>(B / 4 + 1);
+  P.ec_redo = c.take<int>(B);
+  P.ls_list = c.take<int>(2 * B);
+  P.ls_count = c.take<int>(64);
+  P.ls_pos = c.take<int>(2 * B);
+  P.LSC = c.take<double>((size_t)NSLOT * (N + 1) * B);
+  P.LSD = c.take<double>((size_t)NSLOT * N * B);
+  P.ED = c.take<double>((N + 1) * 32 * B);
   return align_up(c.off, 256);
 }
 
@@ -4122,7 +4163,8 @@ static int check_problem(const tolg_problem* p) {
 
 extern "C" size_t tolg_workspace_bytes(const tolg_problem* prob, int32_t max_batch) {
   if (check_problem(prob) || max_batch < 1) return 0;
-  return carve_all(prob, padded_batch(max_batch), nullptr, nullptr, nullptr);
+  Params P;
+  return carve_all(prob, padded_batch(max_batch), nullptr, P);
 }
 
 extern "C" const char* tolg_version(void) { return "tolg-hip 0.3 (gfx950)"; }
@@ -4251,11 +4293,11 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
     h->pol_traj_fast = e && e[0] == '1';
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  Consts* dc = nullptr;
   memset(&h->P, 0, sizeof h->P);
-  carve_all(prob, h->Bp_max, h->ws, &h->P, &dc);
+  carve_all(prob, h->Bp_max, h->ws, h->P);
   h->P.N = prob->N; h->P.m = prob->m;
   h->ref_shared = h->P.ref;
+  Consts* dc = const_cast<Consts*>(h->P.c);
   if (hipMemcpyAsync(dc, &h->hc, sizeof(Consts), hipMemcpyHostToDevice, st) != hipSuccess) { tolg_destroy(h); return TOLG_E_LAUNCH; }
   int N = prob->N;
   hipLaunchKernelGGL(k_pack_ref, dim3((N + 1 + 63) / 64), dim3(64), 0, st, N, d_q_ref, d_xi_ref,
@@ -4266,14 +4308,9 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
 }
 
 extern "C" void tolg_destroy(tolg_handle_t h) {
-  if (h) {
-    if (h->d_cnt) (void)hipFree(h->d_cnt);
-    if (h->h_cnt) (void)hipHostFree(h->h_cnt);
-    for (int k = 0; k < 2; k++) if (h->cnt_ev[k]) (void)hipEventDestroy(h->cnt_ev[k]);
-    for (int k = 0; k < 2; k++) if (h->side_ev[k]) (void)hipEventDestroy(h->side_ev[k]);
-    if (h->side) (void)hipStreamDestroy(h->side);
-  }
   if (!h) return;
+  h->cnt.release();
+  h->side.release();
   for (auto e : h->ev) (void)hipEventDestroy(e);
   delete h;
 }
@@ -4364,11 +4401,10 @@ static int run_linearize(tolg_handle_s* h, const Params& P, hipStream_t st, cons
                          double* dst, double* dst_u, int ms, int i0 = 0, int ni = -1, int ls_list = -1, int ls_nslots = 0,
                          decltype(KernelTable::linearize) kernel = nullptr) {  // kernel: another K1 than h->kt's
   if (ni < 0) ni = P.N + 1;
-  size_t n = (size_t)ni * P.Bp;
   h->rec_closed = 0;  // K1 writes the defect field
   Timed t(h, st, 2);
-  hipLaunchKernelGGL(kernel ? kernel : h->kt.linearize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, src, src_u, dst, dst_u, ms,
-                     i0, ni, ls_list, ls_nslots);
+  hipLaunchKernelGGL(kernel ? kernel : h->kt.linearize, knot_grid(ni, P.Bp), dim3(256), 0, st, P, src, src_u, dst, dst_u, ms, i0,
+                     ni, ls_list, ls_nslots);
   LAUNCH_CHECK();
   return 0;
 }
@@ -4425,17 +4461,18 @@ static int run_affine_dev(tolg_handle_s* h, const Params& P, hipStream_t st, boo
   }
   return 0;
 }
-// One stage of the speculative line search: alphas a0 .. a0 + n - 1 of every still-undecided trajectory at once.
-// stage = 0, 1, 2 ...: stage 0 takes the undecided trajectories from the flags (all active ones), stage s > 0 from the
-// list select s - 1 compacted (lists alternate: select s fills list s & 1 while this stage's kernels read the other).
+// One stage of the speculative line search, stage s of the plan: alphas a0 .. a0 + n - 1 of every still-undecided trajectory
+// at once.  Stage 0 takes the undecided trajectories from the flags (all active ones), stage s > 0 from the list select s - 1
+// compacted (lists alternate: select s fills list s & 1 while this stage's kernels read the other).
 // A one-alpha stage writes its candidate in place (no slot, no copy).
 template <bool MS>
-static int run_ls_stage(tolg_handle_s* h, const Params& P, hipStream_t st, int stage, int a0, int n, int linear,
-                        hipEvent_t before_select = nullptr, bool last = false) {
+static int run_ls_stage(tolg_handle_s* h, const Params& P, hipStream_t st, const LsPlan& L, int s) {
+  const int a0 = L.st[s].a0, n = L.st[s].n, linear = L.linear;
   const int direct = n == 1;
   if (n > NSLOT) return TOLG_E_ARG;
   const KernelTable::Search& S = h->kt.ls[MS];
-  const int list_in = stage == 0 ? -1 : (stage - 1) & 1, list_out = stage & 1;
+  const int list_in = ls_list_in(s), list_out = s & 1;
+  const dim3 kg = knot_grid(P.N + 1, P.Bp);
   // the first try, alpha = 1: x^+ = f(x^, u^) for single shooting (:2073-2080) and for the merit search alike (the
   // factors of :2713-2716 are the identity: note at the record layout) -- K3 itself, written straight into the candidate
   // arrays (every active trajectory is undecided at this point)
@@ -4462,7 +4499,6 @@ static int run_ls_stage(tolg_handle_s* h, const Params& P, hipStream_t st, int s
       hipLaunchKernelGGL(S.wave1[linear != 0], dim3((P.Bp * 4 + 63) / 64, n), dim3(64), 0, st, P, a0, n, direct, list_in);
     }
     LAUNCH_CHECK();
-    const size_t nn = (size_t)(P.N + 1) * P.Bp;
     const unsigned evb = (unsigned)(P.N + 1) * (unsigned)((P.Bp + 255) / 256);  // (knot, 256 candidates) blocks: k_ls_eval
     hipLaunchKernelGGL(S.eval, dim3(evb, n), dim3(256), 0, st, P, n, direct, list_in);
     LAUNCH_CHECK();
@@ -4475,142 +4511,131 @@ static int run_ls_stage(tolg_handle_s* h, const Params& P, hipStream_t st, int s
       LAUNCH_CHECK();
     }
   }
-  if (before_select && hipStreamWaitEvent(st, before_select, 0) != hipSuccess) return TOLG_E_LAUNCH;
-  hipLaunchKernelGGL((k_ls_select<MS>), dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, a0, n, list_out);
+  // the expected change the side stream computes: the first stage's rollout does not need it, its select does
+  if (s == 0 && L.pro == LsPlan::SIDE && hipStreamWaitEvent(st, h->side.ev[1], 0) != hipSuccess) return TOLG_E_LAUNCH;
+  hipLaunchKernelGGL((k_ls_select<MS>), traj_grid(P), dim3(64), 0, st, P, a0, n, list_out);
   LAUNCH_CHECK();
-  // the last stage of a search leaves its accepted candidates in their slots: k_linearize reads them there (no copy).  Not in a
-  // solve on the affine path, whose candidates exist only where k_affine_commit writes them
-  const bool keep = last && !direct && !P.affine;
+  const bool keep = s == L.ns - 1 && ls_kept_slots(L, P);
   if (!direct && !keep) {
-    size_t nn = (size_t)(P.N + 1) * P.Bp;
-    hipLaunchKernelGGL(k_ls_copy, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, P, list_in, n);
+    hipLaunchKernelGGL(k_ls_copy, kg, dim3(256), 0, st, P, list_in, n);
     LAUNCH_CHECK();
   }
   if (P.affine) {
-    size_t nn = (size_t)(P.N + 1) * P.Bp;
-    hipLaunchKernelGGL(h->kt.affine_commit, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, P, a0, 0);
+    hipLaunchKernelGGL(h->kt.affine_commit, kg, dim3(256), 0, st, P, a0, 0);
     LAUNCH_CHECK();
   }
   if (!keep) {  // (kept: k_linearize still needs ls_slot AND the length of this stage's list, which decides where a candidate lies;
                 // k_ls_begin resets both at the top of the next iteration)
-    hipLaunchKernelGGL(k_ls_clear_slot, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, list_out ^ 1);
+    hipLaunchKernelGGL(k_ls_clear_slot, traj_grid(P), dim3(64), 0, st, P, list_out ^ 1);
     LAUNCH_CHECK();
   }
   return 0;
 }
 
-// iLQR_Tracking_SE3_MS loop body (traopt_controller.py:2522-2626)
-static int iterate_ms(tolg_handle_s* h, const Params& P, const tolg_options* opt, hipStream_t st, int it0, int n) {
-  int rc;
-  for (int it = it0; it < it0 + n; it++) {
-    int ls_list_last = -1, ls_n_last = 0;  // set by the merit search below: where its last stage left what it accepted
-    if ((rc = run_backward(h, P, st, it, 1))) return rc;
-    if (!opt->line_search && !opt->rollout_linear && opt->schedule != TOLG_SCHED_SPLIT && h->kt.rollout_lin) {
-      // accept-always nonlinear rollout and the re-linearisation of the new trajectory in one launch
-      {
-        Timed t(h, st, 1, true);
-        t.launch(h->kt.rollout_lin, dim3((P.Bp + 15) / 16), dim3(256), P, it);
-        LAUNCH_CHECK();
-        h->rec_closed = 1;  // its records carry no defect field (zero by construction): K2 reads zeros instead
-      }
-      continue;  // the fused launch also sums the costs and does the bookkeeping of k_reduce
-    } else if (!opt->line_search) {
-      if (P.affine) {  // x^ = x (+) e, u^ = u + du from the affine recursion; the statement form for what it hands back
-        if ((rc = run_affine_dev(h, P, st, false))) return rc;
-        Timed t(h, st, 1);
-        const size_t nn = (size_t)(P.N + 1) * P.Bp;
-        hipLaunchKernelGGL(h->kt.affine_commit, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, P, 0, 1);
-        LAUNCH_CHECK();
-      }
-      if ((rc = run_rollout_ms(h, P, st, 1.0, opt->rollout_linear))) return rc;
-    } else if (P.affine) {
-      hipLaunchKernelGGL(k_ls_begin, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it == 0 ? 1 : 0);
-      LAUNCH_CHECK();
-      if ((rc = run_affine_dev(h, P, st, true))) return rc;
-      if ((rc = run_ls_stage<true>(h, P, st, 0, 0, 1, 1))) return rc;
-      if ((rc = run_ls_stage<true>(h, P, st, 1, 1, 4, 1))) return rc;
-      // (8 + 7 here: on the affine path the deep stages are not empty -- a sixth of the benchmark's trajectories search to the
-      // end -- and one stage of 15 was measured slower, 531 -> 487 it/s)
-      if ((rc = run_ls_stage<true>(h, P, st, 2, 5, 8, 1))) return rc;
-      if (!so3_family(h->prob.kind))
-        if ((rc = run_ls_stage<true>(h, P, st, 3, 13, 7, 1))) return rc;
-      hipLaunchKernelGGL(k_ls_finish, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it);
-      LAUNCH_CHECK();
-    } else {
-      hipLaunchKernelGGL(k_ls_begin, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it == 0 ? 1 : 0);
-      LAUNCH_CHECK();
-      // the defect weight's linear rollout on a side stream: the first stage's rollout does not need it, its select does
-      // (both are 256-wave latency chains; side by side they take the longer one's time, not the sum)
-      if (!h->side) {  // all or nothing, as for the active-count buffers of tolg_solve_iterate_until
-        hipStream_t sd = nullptr;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        bool ok = hipStreamCreateWithFlags(&sd, hipStreamNonBlocking) == hipSuccess;
-        for (int k = 0; ok && k < 2; k++) ok = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-          for (int k = 0; k < 2; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
-          if (sd) (void)hipStreamDestroy(sd);
-          return TOLG_E_LAUNCH;
-        }
-        h->side_ev[0] = ev[0]; h->side_ev[1] = ev[1]; h->side = sd;
-      }
-      if (hipEventRecord(h->side_ev[0], st) != hipSuccess || hipStreamWaitEvent(h->side, h->side_ev[0], 0) != hipSuccess) return TOLG_E_LAUNCH;
-      if (opt->schedule != TOLG_SCHED_SPLIT) {  // the ring form; behind it the statement form for what it hands back
-        launch_ec_ring(h, P, h->side, false);
-        LAUNCH_CHECK();
-        launch_ec_stmt(h, P, h->side, true);
-      } else
-        launch_ec_stmt(h, P, h->side, false);
-      LAUNCH_CHECK();
-      if (hipEventRecord(h->side_ev[1], h->side) != hipSuccess) return TOLG_E_LAUNCH;
-      // staged: the first try alone (one quad rollout, written in place), then 4 + 8 (+ 7) alphas of the trajectories
-      // still undecided -- iLQR_Tracking_SO3_MS searches 13 alphas (:1160), the SE3 one 20 (:2472).  On the benchmark
-      // workload ~75 % of the active trajectories accept the first alpha, nearly all the others the second
-      // (tools/ls_alpha_histogram.py); one stage of 19 took 5.2 ms against 3 x 0.7 in round 2.
-      // (the first TWO step sizes in the first stage -- most trajectories that reject the first accept the second -- was
-      // measured: 432 -> 387 it/s; 512 rollout waves of the general MS step beside the expected-change kernel cost more
-      // than the nearly empty second stage saves)
-      if ((rc = run_ls_stage<true>(h, P, st, 0, 0, 1, opt->rollout_linear, h->side_ev[1]))) return rc;
-      // (round 4: 1 + 12 + 7 instead of 1 + 4 + 8 + 7 -- one latency chain fewer -- measured: 455 -> 418 it/s; the twelve-wide
-      // stage rolls out eight step sizes nobody needed for most of its trajectories)
-      // (the last stage leaves what it accepted in its slots: the re-linearisation reads it there)
-      const bool so3f = so3_family(h->prob.kind);
-      if ((rc = run_ls_stage<true>(h, P, st, 1, 1, 4, opt->rollout_linear))) return rc;
-      // (round 4, end: the step sizes 5 .. 19 in ONE last stage instead of 8 + 7 -- both are nearly empty on every workload seen,
-      // and an empty stage is still seven small launches, 0.05 ms of a 1.6 ms iteration)
-      if ((rc = run_ls_stage<true>(h, P, st, 2, 5, so3f ? 8 : 15, opt->rollout_linear, nullptr, true))) return rc;
-      hipLaunchKernelGGL(k_ls_finish, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it);
-      LAUNCH_CHECK();
-      ls_list_last = 1;   // the list the last stage ran on: (stage - 1) & 1
-      ls_n_last = so3f ? 8 : 15;
-    }
-    // the accepted candidate becomes the nominal trajectory while it is re-linearised
-    if ((rc = run_linearize(h, P, st, P.cand, P.cand_u, P.cur, P.cur_u, 1, 0, -1, ls_list_last, ls_n_last))) return rc;
-    hipLaunchKernelGGL(k_reduce, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it);
-    LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-// iLQR_Tracking_SE3 loop body (traopt_controller.py:1926-2007): gradient test and backward pass share
-// one sweep; 13-alpha backtracking in two speculative stages (the first try, then the other twelve)
-static int iterate_ss(tolg_handle_s* h, const Params& P, const tolg_options* opt, hipStream_t st, int it0, int n) {
-  int rc;
-  for (int it = it0; it < it0 + n; it++) {
-    if ((rc = run_backward(h, P, st, it, 0))) return rc;
-    hipLaunchKernelGGL(k_ls_begin, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, 0);
-    LAUNCH_CHECK();
-    if (P.affine && (rc = run_affine_dev(h, P, st, false))) return rc;
-    if ((rc = run_ls_stage<false>(h, P, st, 0, 0, 1, opt->rollout_linear))) return rc;
+// The line search of a solve (LsPlan), from the mode, the options, the affine path (P.affine) and the model
+static LsPlan ls_plan(const tolg_handle_s* h, const tolg_options* opt, const Params& P) {
+  LsPlan L = {};
+  L.ms = opt->mode == TOLG_MODE_MS;
+  L.linear = opt->rollout_linear != 0;
+  auto stage = [&L](int a0, int n) { L.st[L.ns++] = {a0, n}; };
+  if (!L.ms) {
+    // single shooting: 13-alpha backtracking in two speculative stages (the first try, then the other twelve; what the twelve-
+    // alpha stage accepted is read from its slots -- no k_ls_copy: 0.15-0.2 ms of a 2.4 ms iteration -- and on the affine path
+    // from the candidate arrays, where k_affine_commit wrote them)
     // (1 + 4 + 8 like the merit search was measured: 405 -> 339 it/s on iterations 3..23 of the benchmark solve, whose
     // searches end at the 6th to 10th step size -- tools/ls_alpha_histogram.py; it would pay from iteration ~45 on, where
     // the median accepted step size is the second one)
-    if ((rc = run_ls_stage<false>(h, P, st, 1, 1, NALPHA_SS - 1, opt->rollout_linear, nullptr, true))) return rc;
-    hipLaunchKernelGGL(k_ls_finish, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it);
+    L.pro = P.affine ? LsPlan::RING : LsPlan::NONE;
+    stage(0, 1);
+    stage(1, NALPHA_SS - 1);
+  } else if (!opt->line_search) {  // accept-always
+    L.fused = !opt->rollout_linear && opt->schedule != TOLG_SCHED_SPLIT && h->kt.rollout_lin;
+  } else if (P.affine) {
+    L.pro = LsPlan::RING;
+    stage(0, 1);
+    stage(1, 4);
+    // (8 + 7 here: on the affine path the deep stages are not empty -- a sixth of the benchmark's trajectories search to the
+    // end -- and one stage of 15 was measured slower, 531 -> 487 it/s)
+    stage(5, 8);
+    if (!so3_family(h->prob.kind)) stage(13, 7);
+  } else {
+    // the defect weight's linear rollout on a side stream beside the first stage (both are 256-wave latency chains; side by
+    // side they take the longer one's time, not the sum)
+    L.pro = LsPlan::SIDE;
+    L.split = opt->schedule == TOLG_SCHED_SPLIT;
+    // staged: the first try alone (one quad rollout, written in place), then 4 + 8 (+ 7) alphas of the trajectories
+    // still undecided -- iLQR_Tracking_SO3_MS searches 13 alphas (:1160), the SE3 one 20 (:2472).  On the benchmark
+    // workload ~75 % of the active trajectories accept the first alpha, nearly all the others the second
+    // (tools/ls_alpha_histogram.py); one stage of 19 took 5.2 ms against 3 x 0.7 in round 2.
+    // (the first TWO step sizes in the first stage -- most trajectories that reject the first accept the second -- was
+    // measured: 432 -> 387 it/s; 512 rollout waves of the general MS step beside the expected-change kernel cost more
+    // than the nearly empty second stage saves)
+    stage(0, 1);
+    // (round 4: 1 + 12 + 7 instead of 1 + 4 + 8 + 7 -- one latency chain fewer -- measured: 455 -> 418 it/s; the twelve-wide
+    // stage rolls out eight step sizes nobody needed for most of its trajectories)
+    stage(1, 4);
+    // (round 4, end: the step sizes 5 .. 19 in ONE last stage instead of 8 + 7 -- both are nearly empty on every workload seen,
+    // and an empty stage is still seven small launches, 0.05 ms of a 1.6 ms iteration)
+    stage(5, so3_family(h->prob.kind) ? 8 : 15);
+  }
+  return L;
+}
+
+// The merit search's expected change on the side stream, behind what the main stream has queued; side.ev[1] marks its end
+static int run_side_prologue(tolg_handle_s* h, const Params& P, hipStream_t st, bool split) {
+  if (lazy_create(h->side, 0)) return TOLG_E_LAUNCH;
+  const hipStream_t sd = h->side.stream;
+  if (hipEventRecord(h->side.ev[0], st) != hipSuccess || hipStreamWaitEvent(sd, h->side.ev[0], 0) != hipSuccess) return TOLG_E_LAUNCH;
+  if (!split) {  // the ring form; behind it the statement form for what it hands back
+    launch_ec_ring(h, P, sd, false);
     LAUNCH_CHECK();
-    // (what the twelve-alpha stage accepted is read from its slots -- no k_ls_copy: 0.15-0.2 ms of a 2.4 ms iteration; on the
-    // affine path the candidates are in the candidate arrays, where k_affine_commit wrote them)
-    if ((rc = run_linearize(h, P, st, P.cand, P.cand_u, P.cur, P.cur_u, 0, 0, -1, 0, P.affine ? 0 : NALPHA_SS - 1))) return rc;
-    hipLaunchKernelGGL(k_reduce, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, it);
+    launch_ec_stmt(h, P, sd, true);
+  } else
+    launch_ec_stmt(h, P, sd, false);
+  LAUNCH_CHECK();
+  if (hipEventRecord(h->side.ev[1], sd) != hipSuccess) return TOLG_E_LAUNCH;
+  return 0;
+}
+
+// n iterations of the solve in flight from iteration it0: the backward sweep, then MS accept-always or the planned line search,
+// then the re-linearisation of the accepted trajectory and k_reduce.
+// MS: iLQR_Tracking_SE3_MS loop body (traopt_controller.py:2522-2626).  SS: iLQR_Tracking_SE3 loop body
+// (traopt_controller.py:1926-2007), gradient test and backward pass share one sweep.
+static int iterate(tolg_handle_s* h, hipStream_t st, int it0, int n) {
+  const Params& P = h->run;
+  const LsPlan& L = h->run_ls;
+  int rc;
+  for (int it = it0; it < it0 + n; it++) {
+    if ((rc = run_backward(h, P, st, it, L.ms))) return rc;
+    if (L.fused) {  // accept-always nonlinear rollout and the re-linearisation of the new trajectory in one launch
+      Timed t(h, st, 1, true);
+      t.launch(h->kt.rollout_lin, dim3((P.Bp + 15) / 16), dim3(256), P, it);
+      LAUNCH_CHECK();
+      h->rec_closed = 1;  // its records carry no defect field (zero by construction): K2 reads zeros instead
+      continue;           // the fused launch also sums the costs and does the bookkeeping of k_reduce
+    } else if (L.ns == 0) {  // accept-always
+      if (P.affine) {  // x^ = x (+) e, u^ = u + du from the affine recursion; the statement form for what it hands back
+        if ((rc = run_affine_dev(h, P, st, false))) return rc;
+        Timed t(h, st, 1);
+        hipLaunchKernelGGL(h->kt.affine_commit, knot_grid(P.N + 1, P.Bp), dim3(256), 0, st, P, 0, 1);
+        LAUNCH_CHECK();
+      }
+      if ((rc = run_rollout_ms(h, P, st, 1.0, h->run_opt.rollout_linear))) return rc;
+    } else {
+      hipLaunchKernelGGL(k_ls_begin, traj_grid(P), dim3(64), 0, st, P, L.ms && it == 0 ? 1 : 0);
+      LAUNCH_CHECK();
+      if (L.pro == LsPlan::RING && (rc = run_affine_dev(h, P, st, L.ms))) return rc;
+      if (L.pro == LsPlan::SIDE && (rc = run_side_prologue(h, P, st, L.split))) return rc;
+      for (int s = 0; s < L.ns; s++)
+        if ((rc = L.ms ? run_ls_stage<true>(h, P, st, L, s) : run_ls_stage<false>(h, P, st, L, s))) return rc;
+      hipLaunchKernelGGL(k_ls_finish, traj_grid(P), dim3(64), 0, st, P, it);
+      LAUNCH_CHECK();
+    }
+    // the accepted candidate becomes the nominal trajectory while it is re-linearised; what a last stage kept in its slots is
+    // read there, by the list that stage ran on and its length
+    const int kept = ls_kept_slots(L, P);
+    if ((rc = run_linearize(h, P, st, P.cand, P.cand_u, P.cur, P.cur_u, L.ms, 0, -1, kept ? ls_list_in(L.ns - 1) : -1, kept))) return rc;
+    hipLaunchKernelGGL(k_reduce, traj_grid(P), dim3(64), 0, st, P, it);
     LAUNCH_CHECK();
   }
   return 0;
@@ -4636,22 +4661,20 @@ static int solve_begin(tolg_handle_t h, const tolg_options* opt, int32_t B, cons
   // rollout = 'linear' as an affine recursion (k_expected_change_ring<.., STORE>): every model since the end of round 4;
   // TOLG_SCHED_SPLIT keeps the statement-form rollouts for every trajectory (the A/B partner in the tests)
   P.affine = (opt->rollout_linear && opt->schedule != TOLG_SCHED_SPLIT) ? 1 : 0;
-  size_t n = (size_t)(P.N + 1) * P.Bp;
   if (warm)
-    hipLaunchKernelGGL(h->kt.init_warm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, d_x0_q, d_x0_xi, d_xs_q, d_xs_xi,
-                       d_us_init);
+    hipLaunchKernelGGL(h->kt.init_warm, knot_grid(P.N + 1, P.Bp), dim3(256), 0, st, P, d_x0_q, d_x0_xi, d_xs_q, d_xs_xi, d_us_init);
   else
-    hipLaunchKernelGGL(h->kt.init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, d_x0_q, d_x0_xi, d_us_init, ms);
+    hipLaunchKernelGGL(h->kt.init, knot_grid(P.N + 1, P.Bp), dim3(256), 0, st, P, d_x0_q, d_x0_xi, d_us_init, ms);
   LAUNCH_CHECK();
   if (!ms) {  // SS: dynamically feasible initial trajectory (_init_rollout, traopt_controller.py:2015-2028)
-    hipLaunchKernelGGL(h->kt.init_rollout, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(h->kt.init_rollout, traj_grid(P), dim3(64), 0, st, P);
     LAUNCH_CHECK();
   }
   int rc = run_linearize(h, P, st, P.cur, P.cur_u, nullptr, nullptr, ms);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_reduce, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, -1);
+  hipLaunchKernelGGL(k_reduce, traj_grid(P), dim3(64), 0, st, P, -1);
   LAUNCH_CHECK();
-  h->run = P; h->run_opt = *opt; h->run_it = 0; h->running = true;
+  h->run = P; h->run_opt = *opt; h->run_ls = ls_plan(h, opt, P); h->run_it = 0; h->running = true;
   return 0;
 }
 extern "C" int tolg_solve_begin(tolg_handle_t h, const tolg_options* opt, int32_t B, const double* d_x0_q,
@@ -4674,9 +4697,7 @@ extern "C" int tolg_solve_iterate(tolg_handle_t h, int32_t n_iter, void* stream)
   if (!h || !h->running || n_iter < 0) return TOLG_E_ARG;
   if (h->run_it + n_iter > h->run_opt.max_iter) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = (h->run_opt.mode == TOLG_MODE_MS) ? iterate_ms(h, h->run, &h->run_opt, st, h->run_it, n_iter)
-                                                   : iterate_ss(h, h->run, &h->run_opt, st, h->run_it, n_iter);
-  if (rc) return rc;
+  if (const int rc = iterate(h, st, h->run_it, n_iter)) return rc;
   h->run_it += n_iter;
   return 0;
 }
@@ -4686,9 +4707,7 @@ static int solve_export(tolg_handle_t h, double* d_xs_q, double* d_xs_xi, double
   if (!h || !h->running) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const Params& P = h->run;
-  size_t n = (size_t)(P.N + 1) * P.Bp;
-  hipLaunchKernelGGL(k_unpack_traj, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, P.cur, P.cur_u, d_xs_q,
-                     d_xs_xi, d_us);
+  hipLaunchKernelGGL(k_unpack_traj, knot_grid(P.N + 1, P.Bp), dim3(256), 0, st, P, P.cur, P.cur_u, d_xs_q, d_xs_xi, d_us);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(k_export_scalars, dim3((P.B + 63) / 64), dim3(64), 0, st, P, nullptr, nullptr, nullptr, nullptr,
                      d_iters, d_status, d_converged);
@@ -4727,22 +4746,7 @@ extern "C" int tolg_solve_iterate_until(tolg_handle_t h, int32_t n_iter, int32_t
     if (n_issued) *n_issued = n_iter;
     return 0;
   }
-  if (!h->d_cnt) {
-    // all or nothing: the handle sees the counters only when every piece exists (a partial set-up left behind by a failed
-    // call would be taken for a complete one by the next call)
-    int *dc = nullptr, *hc = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool ok = hipMalloc((void**)&dc, 2 * sizeof(int)) == hipSuccess &&
-              hipHostMalloc((void**)&hc, 2 * sizeof(int), hipHostMallocDefault) == hipSuccess;
-    for (int k = 0; ok && k < 2; k++) ok = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-      if (dc) (void)hipFree(dc);
-      if (hc) (void)hipHostFree(hc);
-      for (int k = 0; k < 2; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
-      return TOLG_E_LAUNCH;
-    }
-    h->h_cnt = hc; h->cnt_ev[0] = ev[0]; h->cnt_ev[1] = ev[1]; h->d_cnt = dc;
-  }
+  if ((rc = lazy_create(h->cnt, 2))) return rc;
   // Slices of check_every iterations; behind each, the count of trajectories still iterating goes to pinned host
   // memory.  The host looks at the count of the slice BEFORE the one it has just queued, so the device always has a
   // slice in its queue while the host waits: a converged batch costs at most one slice of launches whose workgroups
@@ -4753,14 +4757,14 @@ extern "C" int tolg_solve_iterate_until(tolg_handle_t h, int32_t n_iter, int32_t
     if ((rc = tolg_solve_iterate(h, step, stream))) return rc;
     done += step;
     const int k = slice & 1;
-    if (hipMemsetAsync(h->d_cnt + k, 0, sizeof(int), st) != hipSuccess) return TOLG_E_LAUNCH;
-    hipLaunchKernelGGL(k_active_count, dim3((h->run.B + 255) / 256), dim3(256), 0, st, h->run, h->d_cnt + k);
+    if (hipMemsetAsync(h->cnt.dev + k, 0, sizeof(int), st) != hipSuccess) return TOLG_E_LAUNCH;
+    hipLaunchKernelGGL(k_active_count, dim3((h->run.B + 255) / 256), dim3(256), 0, st, h->run, h->cnt.dev + k);
     LAUNCH_CHECK();
-    if (hipMemcpyAsync(h->h_cnt + k, h->d_cnt + k, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return TOLG_E_LAUNCH;
-    if (hipEventRecord(h->cnt_ev[k], st) != hipSuccess) return TOLG_E_LAUNCH;
+    if (hipMemcpyAsync(h->cnt.host + k, h->cnt.dev + k, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return TOLG_E_LAUNCH;
+    if (hipEventRecord(h->cnt.ev[k], st) != hipSuccess) return TOLG_E_LAUNCH;
     if (pending >= 0) {
-      if (hipEventSynchronize(h->cnt_ev[pending]) != hipSuccess) return TOLG_E_LAUNCH;
-      if (h->h_cnt[pending] == 0) break;
+      if (hipEventSynchronize(h->cnt.ev[pending]) != hipSuccess) return TOLG_E_LAUNCH;
+      if (h->cnt.host[pending] == 0) break;
     }
     pending = k;
     slice++;
@@ -4818,9 +4822,8 @@ extern "C" int tolg_set_refs(tolg_handle_t h, int32_t B, const double* d_q_ref, 
   }
   if (!d_xi_ref || !refs_dest_ok(h, B, d_refs, refs_bytes)) return TOLG_E_ARG;
   const int N = h->prob.N, Bp = padded_batch(B);
-  const size_t n = (size_t)(N + 1) * Bp;
-  hipLaunchKernelGGL(k_pack_refs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp, N,
-                     d_q_ref, d_xi_ref, static_cast<double*>(d_refs));
+  hipLaunchKernelGGL(k_pack_refs, knot_grid(N + 1, Bp), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp, N, d_q_ref, d_xi_ref,
+                     static_cast<double*>(d_refs));
   LAUNCH_CHECK();
   hold_refs(h, B, d_refs);
   return 0;
@@ -4831,8 +4834,7 @@ extern "C" int tolg_set_ref_windows(tolg_handle_t h, int32_t B, const double* d_
   if (!h || h->running || !d_path_q || !d_path_xi || T < 1 || t < 0) return TOLG_E_ARG;
   if (!refs_dest_ok(h, B, d_refs, refs_bytes)) return TOLG_E_ARG;
   const int N = h->prob.N, Bp = padded_batch(B);
-  const size_t n = (size_t)(N + 1) * Bp;
-  hipLaunchKernelGGL(k_pack_ref_windows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B,
+  hipLaunchKernelGGL(k_pack_ref_windows, knot_grid(N + 1, Bp), dim3(256), 0, static_cast<hipStream_t>(stream), B,
                      Bp, N, (int)T, d_path_q, d_path_xi, reinterpret_cast<const int*>(d_t0), (int)t, static_cast<double*>(d_refs));
   LAUNCH_CHECK();
   hold_refs(h, B, d_refs);
@@ -4899,13 +4901,11 @@ extern "C" int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_r
   h->pol_B = 0;  // held again once the sweep below is queued
   Params P = params_for(h, B);
   P.max_reg = max_reg;
-  size_t n = (size_t)(P.N + 1) * P.Bp;
-  hipLaunchKernelGGL(k_pack_traj, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, d_xs_q, d_xs_xi, d_us,
-                     (const double*)d_mu_delta);
+  hipLaunchKernelGGL(k_pack_traj, knot_grid(P.N + 1, P.Bp), dim3(256), 0, st, P, d_xs_q, d_xs_xi, d_us, (const double*)d_mu_delta);
   LAUNCH_CHECK();
   int rc;
   if ((rc = run_linearize(h, P, st, P.cur, P.cur_u, nullptr, nullptr, ms))) return rc;
-  hipLaunchKernelGGL(k_reduce, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, -1);
+  hipLaunchKernelGGL(k_reduce, traj_grid(P), dim3(64), 0, st, P, -1);
   LAUNCH_CHECK();
   if ((rc = run_backward(h, P, st, -1, ms))) return rc;
   size_t ne = (size_t)(P.N + 1) * B;
@@ -4929,7 +4929,7 @@ extern "C" int tolg_eval_knot(tolg_handle_t h, int32_t i, int32_t n, const doubl
   h->pol_B = 0;  // k_probe_pack overwrites knot i of the nominal trajectory
   Params P = params_for(h, n);
   P.ref = h->ref_shared;  // the reference of tolg_create, whatever tolg_set_refs holds (K1 below: the shared weights too)
-  hipLaunchKernelGGL(k_probe_pack, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P, i, d_x_q, d_x_xi, d_u);
+  hipLaunchKernelGGL(k_probe_pack, traj_grid(P), dim3(64), 0, st, P, i, d_x_q, d_x_xi, d_u);
   LAUNCH_CHECK();
   int rc = run_linearize(h, P, st, P.cur, P.cur_u, nullptr, nullptr, 2, i, 1, -1, 0, h->kt_pt[0].linearize);
   if (rc) return rc;
@@ -4956,7 +4956,7 @@ extern "C" int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, do
   if (!h || h->running || !batch_fits(h, B) || form < 0 || form > 2) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
-  hipLaunchKernelGGL(k_clear_ecc, dim3((P.Bp + 63) / 64), dim3(64), 0, st, P);
+  hipLaunchKernelGGL(k_clear_ecc, traj_grid(P), dim3(64), 0, st, P);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(k_poison_lds, dim3(2048), dim3(256), 0, st);
   LAUNCH_CHECK();
@@ -4980,8 +4980,7 @@ extern "C" int tolg_rollout(tolg_handle_t h, int32_t ms, int32_t rollout_linear,
   Params P = params_for(h, B);
   int rc = run_rollout_ms(h, P, st, alpha, rollout_linear, ms);
   if (rc) return rc;
-  size_t n = (size_t)(P.N + 1) * P.Bp;
-  hipLaunchKernelGGL(k_unpack_traj, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, P.cand, P.cand_u, d_xs_q_new,
+  hipLaunchKernelGGL(k_unpack_traj, knot_grid(P.N + 1, P.Bp), dim3(256), 0, st, P, P.cand, P.cand_u, d_xs_q_new,
                      d_xs_xi_new, d_us_new);
   LAUNCH_CHECK();
   return 0;
@@ -5023,8 +5022,7 @@ extern "C" int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, d
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // the stage cost is the tracking cost: no augmented-Lagrangian terms
-  const size_t n = (size_t)P.N * P.Bp;
-  hipLaunchKernelGGL(k_mpc_shift, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, P.cur, P.cur_u, d_xs_q_warm,
+  hipLaunchKernelGGL(k_mpc_shift, knot_grid(P.N, P.Bp), dim3(256), 0, st, P, P.cur, P.cur_u, d_xs_q_warm,
                      d_xs_xi_warm, d_us_warm);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(h->kt.mpc_advance, dim3((unsigned)((2 * (size_t)B + 255) / 256)), dim3(256), 0, st, P, d_w, d_x_next_q,
