@@ -222,6 +222,43 @@ int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, const double*
                    double* d_lambda, double* d_imu, double* d_mu, double mu_scale, double mu_max,
                    double tol_constr, double* d_maxviol, int32_t* d_al_converged, void* stream);
 
+/* Augmented-Lagrangian keep-out spheres, a state constraint (ALConstrainedCost wrapping the tracking cost with a
+ * BaseConstraint, traoptlibrary/traopt_cost.py:1173-1320, traoptlibrary/traopt_constraints.py:5-63).  Trajectory b keeps out of
+ * its own K spheres (c_k, r_k), 1 <= K <= TOLG_MAX_OBSTACLES, at every knot i = 0..N, terminal included:
+ *   g_k(x_i) = r_k^2 - |t_i - c_k|^2 <= 0      (t_i: the translation of the pose X_i = (R_i, t_i))
+ * In the error coordinates of l_x (right perturbation X Exp(delta), twist order [omega, v]: tolg_policy_rollout's dx0, d_lx of
+ * tolg_linearize_backward) g_x = [0_3, -2 (t - c)^T R, 0_6], g_u = 0, and the cost gains the reference's Gauss-Newton terms
+ *   l += lambda_ik g_k + I_ik g_k^2 / 2,  l_x[3:6] += g_x^T (lambda_ik + I_ik g_k),  l_xx[3:6,3:6] += I_ik g_x^T g_x.
+ * TOLG_DYN_SE3, _RIGIDBODY and _DRONE (diagonal or dense inertia); the SO3 family has no translation.
+ *
+ * tolg_obstacles_bytes: bytes of the caller-owned buffer that holds the packed geometry of a batch of up to max_batch
+ * trajectories with K spheres each, 4 K Bp 8 with Bp = max_batch rounded up to a multiple of 4; 0 for an invalid problem, a
+ * kind of the SO3 family or K out of range.
+ * tolg_set_al_obstacles: packs d_obs [B][K][4] = (cx, cy, cz, r) into d_packed on `stream` and attaches the multipliers
+ * d_lambda [B][N+1][K] and the diagonal of I_mu d_imu [B][N+1][K]; like tolg_set_al these stay caller-owned and are read by
+ * every later solve on the handle.  From then on every batch entry point -- tolg_solve_batch, tolg_solve_begin(_warm), iterate /
+ * iterate_until / peek / end, tolg_linearize_backward, tolg_rollout, tolg_expected_change -- adds the terms of trajectory b's
+ * spheres to its cost, and must be called with this B (else TOLG_E_ARG).  With tolg_set_al attached too the cost carries both
+ * sets of terms.  tolg_eval_knot ignores them (as it ignores per-trajectory references and weights); tolg_policy_rollout and
+ * tolg_mpc_advance report the tracking cost only.  d_obs = NULL detaches the spheres.  The held policy is left alone.
+ * TOLG_E_ARG: B < 1 or B > max_batch, K out of range, a NULL multiplier or buffer, packed_bytes < tolg_obstacles_bytes(prob, B,
+ * K), a solve in flight, references or weights per trajectory for another B, a kind of the SO3 family. */
+#define TOLG_MAX_OBSTACLES 16
+size_t tolg_obstacles_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K);
+int tolg_set_al_obstacles(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
+                          const double* d_imu, void* d_packed, size_t packed_bytes, void* stream);
+
+/* One outer iteration of AL_iLQR_Tracking_SE3_MS (traoptlibrary/traopt_controller.py:3242-3250, :3270-3290) over every
+ * constraint attached to the handle: the input box of tolg_set_al on d_us [B][N][m] and the spheres of tolg_set_al_obstacles
+ * on the positions of d_xs_q [B][N+1][16].  d_maxviol[b] = the largest g of them all (the box contributes its terminal rows
+ * g = 0); below tol_constr the problem is marked in d_al_converged[b] and left alone, otherwise both multiplier sets (the
+ * attached d_lambda / d_imu of either call) follow the rule of tolg_al_update with one mu per problem, d_mu[b].  d_us may be
+ * NULL without a box, d_xs_q without spheres.  tolg_al_update is unchanged.
+ * TOLG_E_ARG: nothing attached, B < 1 or B > max_batch, B other than the spheres' batch, a NULL input the attached
+ * constraints need. */
+int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu, double mu_scale,
+                         double mu_max, double tol_constr, double* d_maxviol, int32_t* d_al_converged, void* stream);
+
 /* One linearisation + backward pass on given trajectories (unit-parity entry point): replaces
  * iLQR_Tracking_SE3_MS._linearization + _backward_pass + _gradient_wrt_control
  * (traoptlibrary/traopt_controller.py:2823-3093; ms = 0: the SS variants :2098-2349).
@@ -242,7 +279,7 @@ int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_reg, int32_t
  *        d_lxx [n][12][12], d_lu [n][m], d_luu [n][m][m], d_err [n][12] = [Log(x x_ref^-1); xi - xi_ref].
  * Any output may be NULL.  Uses the handle's workspace: not to be called during a solve in flight.  The cost terms are those of
  * the reference and weights of tolg_create, also on a handle with per-trajectory references (tolg_set_refs) or weights
- * (tolg_set_weights). */
+ * (tolg_set_weights), and carry no keep-out sphere terms (tolg_set_al_obstacles). */
 int tolg_eval_knot(tolg_handle_t h, int32_t i, int32_t n, const double* d_x_q, const double* d_x_xi,
                    const double* d_u, double* d_f_q, double* d_f_xi, double* d_Fx, double* d_Fu, double* d_l,
                    double* d_lx, double* d_lxx, double* d_lu, double* d_luu, double* d_err, void* stream);
@@ -271,7 +308,8 @@ int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, double* d_ecc
  *     final iterate).
  * tolg_create, tolg_solve_begin and tolg_solve_begin_warm clear it; so does tolg_eval_knot (it overwrites the nominal
  * trajectory).  tolg_rollout (writes the candidate arrays only), tolg_expected_change, tolg_set_al, tolg_al_update,
- * tolg_set_refs, tolg_set_ref_windows, tolg_set_weights and tolg_mpc_advance leave it; the calls that read it use the
+ * tolg_set_refs, tolg_set_ref_windows, tolg_set_weights, tolg_set_al_obstacles, tolg_al_update_state and tolg_mpc_advance
+ * leave it; the calls that read it use the
  * references and weights set when they run.
  * Both calls return TOLG_E_ARG when no policy is held, during a solve in flight, for a B other than the held batch's, when
  * references or weights per trajectory are set for another B, and (tolg_policy_rollout) for S < 1.  Neither modifies

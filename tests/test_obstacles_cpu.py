@@ -1,0 +1,213 @@
+"""Keep-out spheres without a GPU: the C ABI's size query and argument errors, the seeded workload, the sign and frame of
+g_x (against central differences, calibrated on the oracle's tracking l_x), ConstraintStack, and the mirror's host AL path."""
+import ctypes
+import warnings
+
+import numpy as np
+import pytest
+
+from oracle import bridge as ob
+from trajectory_optimization_matrix_lie_groups_amd import _capi, workloads
+from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_constraints import (BaseConstraint, ConstraintStack,
+                                                                                            InputConstraint,
+                                                                                            SphereObstacleConstraint)
+from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_controller import (AL_iLQR_Tracking_SE3_MS,
+                                                                                           iLQR_Tracking_SE3_MS)
+from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_cost import ALConstrainedCost, BaseCost
+from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_dynamics import BaseDynamics
+
+_se3_exp = workloads._se3_exp
+
+
+def test_size_query_and_argument_errors_without_a_handle():
+    lib = _capi.load()
+    p = _capi.Problem()
+    p.kind, p.m, p.N, p.dt = _capi.DYN_SE3, 6, 40, 0.05
+    p.J[0] = p.J[7] = p.J[14] = p.J[21] = p.J[28] = p.J[35] = 1.0
+    assert lib.tolg_obstacles_bytes(ctypes.byref(p), 5, 3) == 4 * 3 * 8 * 8  # Bp = 8
+    assert lib.tolg_obstacles_bytes(ctypes.byref(p), 4096, 16) == 4 * 16 * 4096 * 8
+    for K in (0, _capi.MAX_OBSTACLES + 1):
+        assert lib.tolg_obstacles_bytes(ctypes.byref(p), 4, K) == 0
+    assert lib.tolg_obstacles_bytes(ctypes.byref(p), 0, 1) == 0
+    p.kind = _capi.DYN_SO3
+    assert lib.tolg_obstacles_bytes(ctypes.byref(p), 4, 1) == 0
+    p.kind, p.m = _capi.DYN_DRONE, 4
+    assert lib.tolg_obstacles_bytes(ctypes.byref(p), 4, 1) == 4 * 4 * 8
+    assert lib.tolg_set_al_obstacles(None, 1, 1, None, None, None, None, 0, None) == -1
+    assert lib.tolg_al_update_state(None, 1, None, None, None, 10.0, 1e8, 1e-2, None, None, None) == -1
+
+
+def test_workload_is_seeded_and_differs_per_trajectory():
+    a = workloads.se3_obstacle_field(3, 4, N=40, seed=5)
+    b = workloads.se3_obstacle_field(3, 4, N=40, seed=5)
+    c = workloads.se3_obstacle_field(3, 4, N=40, seed=6)
+    assert np.array_equal(a[4], b[4]) and not np.array_equal(a[4], c[4])
+    obs = a[4]
+    assert obs.shape == (3, 4, 4) and np.all(obs[..., 3] > 0)
+    assert not np.array_equal(obs[0], obs[1])
+    t = a[0].q_ref[:, :3, 3]
+    g = obs[:, None, :, 3] ** 2 - ((t[None, :, None, :] - obs[:, None, :, :3]) ** 2).sum(-1)
+    assert np.all(g.max(axis=1) > 0)                  # the reference path violates every sphere
+    assert np.all(g[:, 0] < 0) and np.all(g[:, -1] < 0)  # start and end clear
+    d = workloads.drone_obstacle_field(2, 8, N=400)
+    assert d[4].shape == (2, 8, 4) and d[0].N == 400
+
+
+def _state(seed):
+    rng = np.random.default_rng(seed)
+    X = _se3_exp(np.r_[rng.normal(size=3) * 0.7, rng.normal(size=3)])
+    return [X, rng.normal(size=6)]
+
+
+def _perturbed(x, j, h):
+    """x (+) h e_j in the error coordinates of l_x: pose X Exp(h e_j) for j < 6, twist xi + h e_{j-6} otherwise"""
+    X, xi = np.array(x[0]), np.array(x[1])
+    if j < 6:
+        d = np.zeros(6)
+        d[j] = h
+        X = X @ _se3_exp(d)
+    else:
+        xi[j - 6] += h
+    return [X, xi]
+
+
+def _central(f, x, h=1e-6):
+    return np.stack([(np.asarray(f(_perturbed(x, j, h))) - np.asarray(f(_perturbed(x, j, -h)))) / (2 * h) for j in range(12)],
+                    axis=-1)
+
+
+def test_g_x_against_central_differences_in_the_convention_of_the_tracking_l_x():
+    prob, *_ = workloads.se3_tracking(1, N=20, R_scale=1e-3)
+    op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
+    x = _state(1)
+    x[0][:3, 3] = prob.q_ref[7][:3, 3] + 0.2
+    u = np.zeros(6)
+    # the calibration: the same differencing reproduces the oracle's own tracking l_x (right perturbation, [omega, v])
+    lx = ob.cost(op, x[0], x[1], u, 7, False)[1]
+    fd = _central(lambda y: ob.cost(op, y[0], y[1], u, 7, False)[0], x)
+    assert np.abs(fd - lx).max() < 1e-6 * max(1.0, np.abs(lx).max())
+    c = SphereObstacleConstraint(np.array([[0.3, -0.2, 0.1], [1.0, 0.5, -0.4], x[0][:3, 3] + 0.05]), [0.5, 0.2, 0.3])
+    gx = c.g_x(x, u, 7)
+    assert gx.shape == (3, 12) and np.all(gx[:, :3] == 0) and np.all(gx[:, 6:] == 0)
+    assert np.abs(_central(lambda y: c.g(y, u, 7), x) - gx).max() < 1e-7 * max(1.0, np.abs(gx).max())
+    assert c.g_u(x, u, 7).shape == (3, 6) and not c.g_u(x, u, 7).any()
+    assert np.allclose(c.g(x, None, 20, terminal=True), c.g(x, u, 20))  # terminal included
+
+
+def test_constraint_stack_concatenates():
+    box = InputConstraint(-np.ones(6), np.ones(6))
+    sph = SphereObstacleConstraint(np.zeros((2, 3)), [1.0, 2.0])
+    st = ConstraintStack(box, sph)
+    x, u = _state(2), np.full(6, 0.5)
+    assert st.constr_size == 14
+    assert st.g(x, u, 0).shape == (14,) and st.g_x(x, u, 0).shape == (14, 12) and st.g_u(x, u, 0).shape == (14, 6)
+    assert np.array_equal(st.g(x, u, 0)[12:], sph.g(x, u, 0))
+    assert np.array_equal(st.g_u(x, u, 0)[:12], box.g_u(x, u, 0))
+
+
+class MyDynamics(BaseDynamics):
+    """A user-defined plugin evaluated by the oracle's per-knot functions (the pattern of test_generic_plugin_path.py)."""
+
+    def __init__(self, op, m):
+        self._op, self._m = op, m
+        self._error_state_size = 6
+
+    state_size = property(lambda self: 12)
+    action_size = property(lambda self: self._m)
+    has_hessians = property(lambda self: False)
+
+    def f(self, x, u, i):
+        q, xi = ob.f(self._op, x[0], x[1], u)
+        return [q, xi]
+
+    def f_x(self, x, u, i):
+        return ob.fx_fu(self._op, x[0], x[1], u)[0]
+
+    def f_u(self, x, u, i):
+        return ob.fx_fu(self._op, x[0], x[1], u)[1]
+
+    def f_xx(self, x, u, i): raise NotImplementedError  # noqa: E704
+    def f_ux(self, x, u, i): raise NotImplementedError  # noqa: E704
+    def f_uu(self, x, u, i): raise NotImplementedError  # noqa: E704
+
+
+class MyCost(BaseCost):
+    def __init__(self, op, m):
+        self._op, self._m = op, m
+
+    action_size = property(lambda self: self._m)
+
+    def _all(self, x, u, i, terminal):
+        return ob.cost(self._op, x[0], x[1], u, i, terminal)
+
+    def l(self, x, u, i, terminal=False): return self._all(x, u, i, terminal)[0]  # noqa: E704,E741
+    def l_x(self, x, u, i, terminal=False): return self._all(x, u, i, terminal)[1]  # noqa: E704
+    def l_u(self, x, u, i, terminal=False): return self._all(x, u, i, terminal)[3]  # noqa: E704
+    def l_xx(self, x, u, i, terminal=False): return self._all(x, u, i, terminal)[2]  # noqa: E704
+    def l_ux(self, x, u, i, terminal=False): return np.zeros((self._m, 12))  # noqa: E704
+    def l_uu(self, x, u, i, terminal=False): return self._all(x, u, i, terminal)[4]  # noqa: E704
+
+
+def _plugin_problem(N=30):
+    obs = workloads.se3_obstacle_field(1, 2, N=N, seed=11)[4]
+    prob, x0_q, x0_xi, us0 = workloads.se3_tracking(1, N=N, R_scale=1e-3)
+    op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
+    return prob, op, x0_q, x0_xi, us0, obs[0]
+
+
+def test_host_al_formulas_of_the_mirror():
+    prob, op, *_, obs = _plugin_problem()
+    N = prob.N
+    c = SphereObstacleConstraint(obs[:, :3], obs[:, 3])
+    al = ALConstrainedCost(MyCost(op, 6), c, N)
+    rng = np.random.default_rng(4)
+    al.lmbd = rng.uniform(0, 2, (N + 1, 2))
+    al.Imu = np.stack([np.diag(d) for d in rng.uniform(0, 5, (N + 1, 2))])
+    base = MyCost(op, 6)
+    for i, term in ((3, False), (N, True)):
+        x = [prob.q_ref[i].copy(), prob.xi_ref[i] + 0.1]
+        x[0][:3, 3] += 0.05
+        u = rng.normal(size=6)
+        g, gx = c.g(x, u, i), c.g_x(x, u, i)
+        lam, imu = al.lmbd[i], al.Imu[i]
+        assert al.l(x, u, i, term) == pytest.approx(base.l(x, u, i, term) + lam @ g + 0.5 * g @ imu @ g, rel=1e-14)
+        assert np.allclose(al.l_x(x, u, i, term), base.l_x(x, u, i, term) + gx.T @ (lam + imu @ g), rtol=1e-14, atol=0)
+        assert np.allclose(al.l_xx(x, u, i, term), base.l_xx(x, u, i, term) + gx.T @ imu @ gx, rtol=1e-14, atol=0)
+        assert np.array_equal(al.l_u(x, u, i, term), base.l_u(x, u, i, term))  # g_u = 0
+
+
+def _max_violation(c, xs):
+    return max(float(np.max(c.g(x, None, i))) for i, x in enumerate(xs))
+
+
+def test_plain_controller_runs_the_generic_path_with_fixed_multipliers():
+    prob, op, x0_q, x0_xi, us0, obs = _plugin_problem()
+    N = prob.N
+    c = SphereObstacleConstraint(obs[:, :3], obs[:, 3])
+    out = []
+    for lam, mu in ((0.0, 0.0), (1.0, 20.0)):
+        al = ALConstrainedCost(MyCost(op, 6), c, N)
+        al.lmbd[:] = lam
+        al.Imu[:] = mu * np.eye(2)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            ctl = iLQR_Tracking_SE3_MS(MyDynamics(op, 6), al, N, prob.q_ref, prob.xi_ref, rollout="nonlinear")
+            xs, us, J_hist, *_ = ctl.fit([x0_q[0], x0_xi[0]], us0[0], n_iterations=10, tol_grad_norm=0.0)
+        out.append(_max_violation(c, xs))
+    assert out[0] > 0.0          # unconstrained tracking goes through the spheres
+    assert out[1] < out[0]
+
+
+class _Unsupported(BaseConstraint):
+    constr_size = 1
+    def g(self, x, u, i, terminal=False): return np.zeros(1)  # noqa: E704
+    def g_x(self, x, u, i, terminal=False): return np.zeros((1, 12))  # noqa: E704
+    def g_u(self, x, u, i, terminal=False): return np.zeros((1, 6))  # noqa: E704
+
+
+def test_al_controller_rejects_a_constraint_it_cannot_route():
+    prob, op, *_ = _plugin_problem()
+    for bad in (_Unsupported(), ConstraintStack(SphereObstacleConstraint(np.zeros((1, 3)), [1.0]), _Unsupported()),
+                ConstraintStack(InputConstraint(-np.ones(6), np.ones(6)), InputConstraint(-np.ones(6), np.ones(6)))):
+        with pytest.raises(TypeError, match="SphereObstacleConstraint"):
+            AL_iLQR_Tracking_SE3_MS(MyDynamics(op, 6), MyCost(op, 6), bad, prob.N, prob.q_ref, prob.xi_ref)

@@ -48,6 +48,10 @@ struct Consts {
   // per-trajectory cost weights (tolg_set_weights, caller-owned): [wt_fields(m)][Bp] (WT_*), read by the PT_W / PTW kernels only.
   // Here and not in Params, whose size would move the kernel arguments behind it in every kernel; k_pack_weights sets it.
   const double* wts;
+  // keep-out spheres (tolg_set_al_obstacles, caller-owned), read by the PT_OBS kernels only: the packed geometry [4K][Bp]
+  // (OB_* fields of sphere k at (4k + f) * Bp + b), the multipliers and the diagonal of I_mu in the caller layout [B][N+1][K]
+  const double *obs, *obs_lam, *obs_imu;
+  int obsK, obs_pad;
 };
 
 // Device-side view of the constants used by the three hot kernels: address space 4 (constant), so
@@ -182,7 +186,8 @@ template <> struct RefAt<true> {
 };
 // What a knot-level kernel reads per trajectory (template argument PT): PT_REF its reference (tolg_set_refs), PT_W its cost
 // weights (tolg_set_weights).  0 is the batch-shared form of every kernel.
-enum { PT_REF = 1, PT_W = 2 };
+// PT_OBS: the augmented-Lagrangian terms of its keep-out spheres (tolg_set_al_obstacles; the cost-evaluating kernels only).
+enum { PT_REF = 1, PT_W = 2, PT_OBS = 4 };
 // Per-trajectory cost weights (tolg_set_weights): the diagonals of W1, W2 (Q), P1, P2 (P) and R, packed [WT_F][Bp] (field
 // f of trajectory b at f * Bp + b: a weight load is coalesced over the batch like a state load)
 enum { WT_W1 = 0, WT_W2 = 6, WT_P1 = 12, WT_P2 = 18, WT_R = 24 };
@@ -313,6 +318,36 @@ __host__ __device__ constexpr int rec_fields(int m, bool grav, bool al, bool a22
 #define GOFF(u, j, M_) ((((unsigned)(j)) * ((M_) / 2u) + (((unsigned)(u)) >> 1)) * 64u + (((unsigned)(u)) & 1u) * 8u)
 __host__ __device__ inline bool so3_family(int kind) { return kind == TOLG_DYN_SO3 || kind == TOLG_DYN_PENDULUM3D; }
 __host__ __device__ inline int sym6(int r, int c) { return r <= c ? c * (c + 1) / 2 + r : r * (r + 1) / 2 + c; }
+
+// Keep-out spheres of trajectory b (tolg_set_al_obstacles, PT_OBS): g_k = r_k^2 - |t - c_k|^2 <= 0 at every knot, terminal
+// included, and the augmented-Lagrangian terms of ALConstrainedCost (traopt_cost.py:1173-1320; Gauss-Newton, no g_xx).  In the
+// error coordinates of l_x (X Exp(delta), twist order [w, v]) g_x = [0, -2 (t - c)^T R, 0]: only its v part is not zero,
+// gv = -2 R^T (t - c).  Sums lambda g + g I g / 2 into l and, with ox / oxx given, gv (lambda + I g) into ox (l_x[3:6]) and
+// I gv gv^T into oxx (the v-v block of l_xx, upper triangle row by row: 00 01 02 11 12 22).  The callers add the sums after
+// the tracking arithmetic, so that with lambda = I = 0 every term is an exact zero and the tracking values keep their bits.
+template <class CT>
+TOLG_DEV void obs_terms(const Params& P, const CT& C, int i, int b, const Pose& X, double& l, double* ox, double* oxx) {
+  const int K = C.obsK, bs = b < P.B ? b : P.B - 1;  // the packed geometry replicates B-1 in padded lanes, the multipliers do not
+  const size_t row = ((size_t)bs * (P.N + 1) + i) * K, Bp = (size_t)P.Bp;
+  const double *lam = C.obs_lam + row, *imu = C.obs_imu + row, *geo = C.obs + b;
+  for (int k = 0; k < K; k++) {
+    const double* o = geo + (size_t)(4 * k) * Bp;
+    const V3 d = X.t - v3(o[0], o[Bp], o[2 * Bp]);
+    const double r = o[3 * Bp], lk = lam[k], ik = imu[k];
+    const double g = r * r - dot(d, d);
+    l += lk * g + 0.5 * (g * ik * g);
+    if (ox) {
+      const V3 gv = -2.0 * qrot_inv(X.q, d);
+      const double gw[3] = {gv.x, gv.y, gv.z}, s = lk + ik * g;
+#pragma unroll
+      for (int a = 0, n = 0; a < 3; a++) {
+        ox[a] += gw[a] * s;
+#pragma unroll
+        for (int c = a; c < 3; c++, n++) oxx[n] += ik * gw[a] * gw[c];
+      }
+    }
+  }
+}
 
 // ------------------------------------------------------------------------------------------------
 // shared per-thread dynamics pieces
@@ -771,6 +806,10 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
   const Pose De = se3_compose(S.X, se3_inverse(Xr));
   const double ye = quat_vec2(De.q), th2d = dot(wd, wd);
   const SeriesGate sg = series_gate(log_small(ye) && coef_small(th2d), log_dom(ye) && exp_dom(th2d));
+  // PT_OBS: the spheres' terms first, while little else is live (added to the tracking values at the end of the block)
+  constexpr bool PTO = (PT & PT_OBS) != 0;
+  double ol = 0.0, ox[3] = {0.0, 0.0, 0.0}, oxx[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if constexpr (PTO) obs_terms(P, C, i, b, S.X, ol, ox, oxx);
   // ---------------- cost: e = Log(X Xref^-1), J_e = Jr^-1(e) Ad(Xref)  (traopt_cost.py:659-839)
   {
     V3 ew, ev;
@@ -870,8 +909,10 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
         }
       }
     }
-    if (lcost) *lcost = l;
-    else P.SC[(size_t)i * P.Bp + b] = l;
+    if constexpr (!PTO) {
+      if (lcost) *lcost = l;
+      else P.SC[(size_t)i * P.Bp + b] = l;
+    }
     double WJ[36];
 #pragma unroll
     for (int a = 0; a < 6; a++)
@@ -897,6 +938,17 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
       for (int k = 0; k < 6; k++) s += Je[6 * k + a] * We[k];
       lxv[a] = 2 * s;
       lxv[6 + a] = 2 * W2v[a];
+    }
+    if constexpr (PTO) {  // the spheres' terms on top of the tracking values, then the cost goes where it goes above
+      l += ol;
+#pragma unroll
+      for (int a = 0, n = 0; a < 3; a++) {
+        lxv[3 + a] += ox[a];
+#pragma unroll
+        for (int c = a; c < 3; c++, n++) lxx[sym6(3 + a, 3 + c)] += oxx[n];
+      }
+      if (lcost) *lcost = l;
+      else P.SC[(size_t)i * P.Bp + b] = l;
     }
     rec_run<REC_LXX, 21, RP>(P, i, b, lxx);
     rec_run<REC_LX, 12, RP>(P, i, b, lxv);
@@ -2778,6 +2830,7 @@ TOLG_DEV double knot_cost(const Params& P, const Consts& C, int i, int b, const 
       }
     }
   }
+  if constexpr ((PT & PT_OBS) != 0) obs_terms(P, C, i, b, S.X, l, nullptr, nullptr);
   return l;
 }
 
@@ -3875,7 +3928,9 @@ using namespace tolg;
 // the fused launch, the line-search evaluations, k_init) read trajectory b's own reference (tolg_set_refs).  PT_W: the
 // kernels that read the cost weights (K1, the fused launch, the line-search evaluations, both backward sweeps, both forms of
 // the expected change) read trajectory b's own diagonal weights (tolg_set_weights).  Every other entry is the same kernel in
-// all four.
+// all four.  PT_OBS: the kernels that evaluate costs (K1, the fused launch, k_rollout_eval_t, k_ls_eval, k_ls_eval_affine) add
+// the augmented-Lagrangian terms of trajectory b's keep-out spheres (tolg_set_al_obstacles); every other entry of the four
+// tables with PT_OBS is the entry of the table without it.
 typedef void (*SearchKernel)(Params, int, int, int);
 typedef void (*SearchRollout)(Params, int, int, int, int);
 struct KernelTable {
@@ -3921,7 +3976,7 @@ static KernelTable::Search search_kernels() {
   return s;
 }
 // GRAV: gravity; DENSE: inertia blocks that are not diagonal; PEND: Pendulum3dDyanmics (m = 6, gravity); PT: PT_REF a
-// reference per trajectory, PT_W cost weights per trajectory
+// reference per trajectory, PT_W cost weights per trajectory, PT_OBS keep-out spheres per trajectory
 template <int M, bool GRAV, bool DENSE, bool PEND, int PT>
 static KernelTable kernel_table(int lds_per_block) {
   constexpr int PK = PEND ? 1 : 0;
@@ -3953,8 +4008,9 @@ static KernelTable kernel_table(int lds_per_block) {
   t.ec_stmt[0] = k_expected_change<M, PK, false, PTW>;
   t.ec_stmt[1] = k_expected_change<M, PK, true, PTW>;
   t.affine_commit = k_affine_commit<M>;
-  t.policy_rollout = k_policy_rollout<M, PK, PT>;
-  t.mpc_advance = k_mpc_advance<M, PK, PT>;
+  // (the held policy's rollouts report the tracking cost: the PT_OBS tables share the kernels of the table without it)
+  t.policy_rollout = k_policy_rollout<M, PK, PT & ~PT_OBS>;
+  t.mpc_advance = k_mpc_advance<M, PK, PT & ~PT_OBS>;
   t.ls[0] = search_kernels<M, false, PK, PT>();
   t.ls[1] = search_kernels<M, true, PK, PT>();
   return t;
@@ -4034,13 +4090,16 @@ struct tolg_handle_s {
   bool running;
   int lds_per_block;  // hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KB on MI355X)
   int rec_closed = 0; // the knot records were last written by the fused rollout (no defect field, see k_backward)
-  KernelTable kt;     // the model's kernels for the solves to come: kt_pt[(refs ? PT_REF : 0) | (wts ? PT_W : 0)]
-  KernelTable kt_pt[4];  // kernel_table_for<PT>: [0] batch-shared reference and weights, [PT_REF | PT_W] per trajectory
+  KernelTable kt;     // the model's kernels for the solves to come: kt_pt[(refs ? PT_REF : 0) | (wts ? PT_W : 0) | (obs ? PT_OBS : 0)]
+  KernelTable kt_pt[8];  // kernel_table_for<PT>: [0] batch-shared reference and weights, no spheres, [PT_REF | PT_W] per trajectory
   const double* ref_shared;  // the reference packed by tolg_create (P.ref as carved)
   const double* refs = nullptr;  // tolg_set_refs: the packed per-trajectory references (caller-owned), or null
   int refs_B = 0;                // ... and the batch they were set for: every batch call must match it
   const double* wts = nullptr;   // tolg_set_weights: the packed per-trajectory weights (caller-owned), or null
   int wts_B = 0;                 // ... and their batch, as refs_B
+  const double* obs = nullptr;   // tolg_set_al_obstacles: the packed sphere geometry (caller-owned), or null
+  int obs_B = 0, obs_K = 0;      // ... their batch, as refs_B, and the spheres per trajectory
+  double *obs_lam = nullptr, *obs_imu = nullptr;  // ... their multipliers [B][N+1][K] (caller-owned; tolg_al_update_state writes them)
   // The held policy (tolg_solve_gains, tolg_policy_rollout): nominal trajectory P.cur / P.cur_u and gains P.GK of a batch of
   // pol_B trajectories, 0 = none.  Set by tolg_solve_end and tolg_linearize_backward; cleared by tolg_solve_begin(_warm) and
   // tolg_eval_knot (k_probe_pack writes P.cur); tolg_rollout (writes the candidate arrays) and tolg_expected_change (ED, ecc)
@@ -4073,10 +4132,12 @@ static dim3 knot_grid(int knots, int Bp) { return dim3((unsigned)(((size_t)knots
 // B trajectories fit the handle and the per-trajectory references and weights it holds (tolg_set_refs, tolg_set_weights):
 // what every batch call on the handle's workspace requires
 static bool batch_fits(const tolg_handle_s* h, int B) {
-  return B >= 1 && B <= h->max_batch && !(h->refs && B != h->refs_B) && !(h->wts && B != h->wts_B);
+  return B >= 1 && B <= h->max_batch && !(h->refs && B != h->refs_B) && !(h->wts && B != h->wts_B) && !(h->obs && B != h->obs_B);
 }
 // the kernels of h->kt follow what per-trajectory inputs are set (kernel_table, PT)
-static void select_kernels(tolg_handle_s* h) { h->kt = h->kt_pt[(h->refs ? PT_REF : 0) | (h->wts ? PT_W : 0)]; }
+static void select_kernels(tolg_handle_s* h) {
+  h->kt = h->kt_pt[(h->refs ? PT_REF : 0) | (h->wts ? PT_W : 0) | (h->obs ? PT_OBS : 0)];
+}
 
 static int host_inv6(const double A[36], double Ai[36]) {
   double Mx[6][12];
@@ -4283,6 +4344,10 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
   h->kt_pt[PT_REF] = kernel_table_for<PT_REF>(*prob, c, h->lds_per_block);
   h->kt_pt[PT_W] = kernel_table_for<PT_W>(*prob, c, h->lds_per_block);
   h->kt_pt[PT_REF | PT_W] = kernel_table_for<PT_REF | PT_W>(*prob, c, h->lds_per_block);
+  h->kt_pt[PT_OBS] = kernel_table_for<PT_OBS>(*prob, c, h->lds_per_block);
+  h->kt_pt[PT_REF | PT_OBS] = kernel_table_for<PT_REF | PT_OBS>(*prob, c, h->lds_per_block);
+  h->kt_pt[PT_W | PT_OBS] = kernel_table_for<PT_W | PT_OBS>(*prob, c, h->lds_per_block);
+  h->kt_pt[PT_REF | PT_W | PT_OBS] = kernel_table_for<PT_REF | PT_W | PT_OBS>(*prob, c, h->lds_per_block);
   select_kernels(h);
   {
     const char* e = getenv("TOLG_K2_FULL_ONLY");
@@ -4806,7 +4871,7 @@ extern "C" size_t tolg_refs_bytes(const tolg_problem* prob, int32_t max_batch) {
 // large enough), and B is the batch of the per-trajectory weights when they are set (references and weights: one batch)
 static bool refs_dest_ok(const tolg_handle_s* h, int B, const void* d_refs, size_t refs_bytes) {
   return B >= 1 && B <= h->max_batch && d_refs && (reinterpret_cast<uintptr_t>(d_refs) & 7) == 0 &&
-         refs_bytes >= refs_bytes_for(&h->prob, B) && !(h->wts && B != h->wts_B);
+         refs_bytes >= refs_bytes_for(&h->prob, B) && !(h->wts && B != h->wts_B) && !(h->obs && B != h->obs_B);
 }
 // ... and what the packing kernel queued on the stream: the handle's references from now on
 static void hold_refs(tolg_handle_s* h, int B, const void* d_refs) {
@@ -4869,7 +4934,7 @@ extern "C" int tolg_set_weights(tolg_handle_t h, int32_t B, const double* d_q_di
   }
   if (B < 1 || B > h->max_batch || !d_p_diag || !d_r_diag || !d_w || (reinterpret_cast<uintptr_t>(d_w) & 7) != 0) return TOLG_E_ARG;
   if (w_bytes < weights_bytes_for(&h->prob, B)) return TOLG_E_ARG;
-  if (h->refs && B != h->refs_B) return TOLG_E_ARG;  // references and weights per trajectory: one batch
+  if ((h->refs && B != h->refs_B) || (h->obs && B != h->obs_B)) return TOLG_E_ARG;  // per-trajectory inputs: one batch
   const int Bp = padded_batch(B);
   const size_t n = (size_t)wt_fields(h->prob.m) * Bp;
   hipLaunchKernelGGL(k_pack_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp,
@@ -4887,6 +4952,112 @@ extern "C" int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, co
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(k_al_update, dim3((B + 63) / 64), dim3(64), 0, st, B, h->prob.N, h->prob.m, d_us, d_lb, d_ub,
                      d_lambda, d_imu, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, d_al_converged);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// d_obs [B][K][4] = (cx, cy, cz, r) into [4K][Bp] (field f = 4k + c of trajectory b at f * Bp + b); padded trajectories b >= B
+// replicate b = B-1.  Thread 0 points the handle's constants at the geometry and at the caller's multipliers (stream-ordered
+// before the solves that read them).
+__global__ void k_pack_obstacles(int B, int Bp, int K, const double* __restrict__ obs, const double* lam, const double* imu,
+                                 double* __restrict__ w, Consts* c) {
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; }
+  if (t >= (size_t)4 * K * Bp) return;
+  const int b = (int)(t % Bp), f = (int)(t / Bp);
+  const int bs = b < B ? b : B - 1;
+  w[t] = obs[(size_t)bs * 4 * K + f];
+}
+
+// One outer update over every constraint the handle holds (tolg_al_update_state): the input box of tolg_set_al on the
+// controls and the keep-out spheres of tolg_set_al_obstacles on the positions of xs_q [B][N+1][16], one thread per trajectory.
+// maxviol = the largest g of them all (the box contributes the zero rows of its terminal knot, traopt_constraints.py:160-161;
+// the spheres have no such rows), one mu per problem, the update rule of k_al_update for both multiplier sets
+// (traopt_controller.py:3242-3250, :3270-3290).
+__global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const double* __restrict__ xs_q, const double* __restrict__ us,
+                                  const double* __restrict__ lb, const double* __restrict__ ub, double* __restrict__ lam,
+                                  double* __restrict__ imu, const double* __restrict__ geo, double* __restrict__ olam,
+                                  double* __restrict__ oimu, double* __restrict__ mu, double mu_scale, double mu_max,
+                                  double tol_constr, double* __restrict__ maxviol, int* __restrict__ al_conv) {
+  int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B || al_conv[b]) return;  // a converged problem keeps its multipliers
+  auto gs = [&](int i, int k) {      // g_k at knot i: r^2 - |t - c|^2
+    const double* x = xs_q + ((size_t)b * (N + 1) + i) * 16;
+    const double* o = geo + (size_t)(4 * k) * Bp + b;
+    const double dx = x[3] - o[0], dy = x[7] - o[Bp], dz = x[11] - o[2 * (size_t)Bp], r = o[3 * (size_t)Bp];
+    return r * r - (dx * dx + dy * dy + dz * dz);
+  };
+  double mv = lb ? 0.0 : -INFINITY;
+  if (lb)
+    for (int i = 0; i < N; i++) {
+      const double* u = us + ((size_t)b * N + i) * m;
+      for (int k = 0; k < 2 * m; k++) mv = fmax(mv, (k < m) ? lb[k] - u[k] : u[k - m] - ub[k - m]);
+    }
+  if (geo)
+    for (int i = 0; i <= N; i++)
+      for (int k = 0; k < K; k++) mv = fmax(mv, gs(i, k));
+  maxviol[b] = mv;
+  if (mv < tol_constr) { al_conv[b] = 1; return; }
+  const double mu_new = fmin(mu[b] * mu_scale, mu_max);
+  auto upd = [&](double& l, double& im, double g) {
+    const double ln = fmax(0.0, l + im * g);
+    l = ln;
+    im = (g < 0.0 && ln == 0.0) ? 0.0 : mu_new;
+  };
+  if (lb)
+    for (int i = 0; i < N; i++) {
+      const double* u = us + ((size_t)b * N + i) * m;
+      const size_t o = ((size_t)b * N + i) * 2 * m;
+      for (int k = 0; k < 2 * m; k++) upd(lam[o + k], imu[o + k], (k < m) ? lb[k] - u[k] : u[k - m] - ub[k - m]);
+    }
+  if (geo)
+    for (int i = 0; i <= N; i++)
+      for (int k = 0; k < K; k++) {
+        const size_t o = ((size_t)b * (N + 1) + i) * K + k;
+        upd(olam[o], oimu[o], gs(i, k));
+      }
+  mu[b] = mu_new;
+}
+
+static size_t obstacles_bytes_for(int B, int K) { return (size_t)4 * K * (size_t)padded_batch(B) * sizeof(double); }
+extern "C" size_t tolg_obstacles_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K) {
+  if (check_problem(prob) || so3_family(prob->kind) || max_batch < 1 || K < 1 || K > TOLG_MAX_OBSTACLES) return 0;
+  return obstacles_bytes_for(max_batch, K);
+}
+
+extern "C" int tolg_set_al_obstacles(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
+                                     const double* d_imu, void* d_packed, size_t packed_bytes, void* stream) {
+  if (!h || h->running) return TOLG_E_ARG;
+  if (!d_obs) {  // detach
+    h->obs = nullptr; h->obs_B = h->obs_K = 0; h->obs_lam = h->obs_imu = nullptr; select_kernels(h);
+    return 0;
+  }
+  if (so3_family(h->prob.kind) || B < 1 || B > h->max_batch || K < 1 || K > TOLG_MAX_OBSTACLES) return TOLG_E_ARG;
+  if (!d_lambda || !d_imu || !d_packed || (reinterpret_cast<uintptr_t>(d_packed) & 7) != 0) return TOLG_E_ARG;
+  if (packed_bytes < obstacles_bytes_for(B, K)) return TOLG_E_ARG;
+  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;  // per-trajectory inputs: one batch
+  const int Bp = padded_batch(B);
+  const size_t n = (size_t)4 * K * Bp;
+  hipLaunchKernelGGL(k_pack_obstacles, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp, K,
+                     d_obs, d_lambda, d_imu, static_cast<double*>(d_packed), const_cast<Consts*>(h->P.c));
+  LAUNCH_CHECK();
+  h->obs = static_cast<const double*>(d_packed); h->obs_B = B; h->obs_K = K;
+  h->obs_lam = const_cast<double*>(d_lambda); h->obs_imu = const_cast<double*>(d_imu);
+  select_kernels(h);
+  return 0;
+}
+
+extern "C" int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu,
+                                    double mu_scale, double mu_max, double tol_constr, double* d_maxviol,
+                                    int32_t* d_al_converged, void* stream) {
+  if (!h || B < 1 || B > h->max_batch || !d_mu || !d_maxviol || !d_al_converged) return TOLG_E_ARG;
+  if (!h->al_lb && !h->obs) return TOLG_E_ARG;     // nothing attached to update
+  if (h->al_lb && !d_us) return TOLG_E_ARG;
+  if (h->obs && (B != h->obs_B || !d_xs_q)) return TOLG_E_ARG;
+  hipLaunchKernelGGL(k_al_update_state, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), B, padded_batch(B),
+                     h->prob.N, h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
+                     const_cast<double*>(h->al_imu), h->obs, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr, d_maxviol,
+                     d_al_converged);
   LAUNCH_CHECK();
   return 0;
 }

@@ -141,7 +141,8 @@ def _checked(name, a, shape, finite=False):
 # What a C call does to the held policy (include/tolg.h): "clear" before it runs (so also when it fails), "hold" the batch
 # of the call once it has succeeded.  gains / policy_rollout / mpc_advance need one held.
 _POLICY = {"tolg_solve_begin": "clear", "tolg_solve_begin_warm": "clear", "tolg_eval_knot": "clear",
-           "tolg_solve_batch": "clear hold", "tolg_linearize_backward": "clear hold", "tolg_solve_end": "hold"}
+           "tolg_solve_batch": "clear hold", "tolg_linearize_backward": "clear hold", "tolg_solve_end": "hold",
+           "tolg_set_al_obstacles": "", "tolg_al_update_state": ""}  # (the last two leave it: listed for completeness)
 
 
 @dataclass
@@ -175,6 +176,8 @@ class BatchedTrackingILQR:
         self._refs_buf = self._wts_buf = None  # the packed per-trajectory references / weights the handle reads (_packed)
         self._inflight = (None, None)  # the FitResult of the solve in flight; the inputs the stream may not have read (_hold)
         self._al = None            # the augmented-Lagrangian terms the handle points at (set_al)
+        self._obs = None           # ... and the keep-out spheres (set_al_obstacles): (obstacles, lam, imu) on the device
+        self._obs_buf = None       # the packed sphere geometry the handle reads (caller-owned, for max_batch x MAX_OBSTACLES)
         p = _capi.Problem()
         p.kind, p.m, p.N, p.dt = _KIND[problem.kind], self.m, self.N, float(problem.dt)
         p.pend_mass, p.pend_length = float(problem.pend_mass), float(problem.pend_length)
@@ -475,24 +478,99 @@ class BatchedTrackingILQR:
             self._al = (lb, ub, lam, imu)  # the handle reads them in every solve until they are detached
             self._call("tolg_set_al", _ptr(lb), _ptr(ub), _ptr(lam), _ptr(imu), stream=False)
 
-    def al_fit_batch(self, x0_q, x0_xi, us_init, lb, ub, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
+    def _check_obstacles(self, B, obstacles):
+        """Keep-out spheres [K, 4] (every trajectory the same) or [B, K, 4] rows (cx, cy, cz, r), checked on the host: ValueError
+        before anything reaches the device for a model without translation, a wrong shape, K outside 1..MAX_OBSTACLES, a
+        non-finite value or a radius that is not positive.  B = None takes B from a [B, K, 4] array.  Returns (B, [B, K, 4]
+        float64 numpy)."""
+        if self.problem.kind in ("so3", "pendulum3d"):
+            raise ValueError("keep-out spheres constrain the translation: the %s model has none" % self.problem.kind)
+        a = obstacles.detach().cpu().numpy() if isinstance(obstacles, torch.Tensor) else obstacles
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim not in (2, 3):
+            raise ValueError("obstacles has shape %s, expected (K, 4) or (B, K, 4)" % (a.shape,))
+        a = _checked("obstacles", a, (None,) * a.ndim, finite=True)
+        if a.ndim == 2:
+            if B is None:
+                raise ValueError("obstacles [K, 4] need the batch: give lam / imu [B, N+1, K] or obstacles [B, K, 4]")
+            a = np.broadcast_to(a, (B,) + a.shape)
+        B = a.shape[0] if B is None else B
+        a = _checked("obstacles", a, (B, None, 4))
+        if not 1 <= a.shape[1] <= _capi.MAX_OBSTACLES:
+            raise ValueError("obstacles: K = %d spheres per trajectory, expected 1..%d" % (a.shape[1], _capi.MAX_OBSTACLES))
+        if np.any(a[..., 3] <= 0.0):
+            raise ValueError("obstacles: every radius must be positive")
+        return B, np.ascontiguousarray(a)
+
+    def set_al_obstacles(self, obstacles=None, lam=None, imu=None):
+        """Attach (or detach with obstacles=None) keep-out spheres: the augmented-Lagrangian terms of g_k = r_k^2 - |t - c_k|^2
+        <= 0 at every knot, terminal included (tolg_set_al_obstacles).  obstacles [K, 4] (broadcast) or [B, K, 4] rows (cx, cy,
+        cz, r); lam, imu [B, N+1, K]: the multipliers and the diagonal of I_mu (device tensors the handle reads in every solve
+        until they are detached; None: zeros).  Every batch call must then be for this B."""
+        if obstacles is None:
+            self._obs = None
+            self._call("tolg_set_al_obstacles", 0, 0, None, None, None, None, 0, stream=True)
+            return
+        Bl = None if lam is None else int(lam.shape[0])
+        B, a = self._check_obstacles(Bl, obstacles)
+        K = a.shape[1]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        if lam is None:
+            lam = torch.zeros(B, self.N + 1, K, **f64)
+        if imu is None:
+            imu = torch.zeros(B, self.N + 1, K, **f64)
+        for name, t in (("lam", lam), ("imu", imu)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float64 tensor on %s" % (name, self.device))
+            _checked(name, t, (B, self.N + 1, K))
+        if not 1 <= B <= self.max_batch:
+            raise ValueError("obstacles for B = %d trajectories, expected 1..%d" % (B, self.max_batch))
+        if self._obs_buf is None:
+            n = self.lib.tolg_obstacles_bytes(C.byref(self._p), self.max_batch, _capi.MAX_OBSTACLES)
+            self._obs_buf = torch.empty(int(n) // 8, dtype=torch.float64, device=self.device)
+        d = self._dev(a, (B, K, 4))
+        self._obs = (d, lam, imu)  # the handle reads the multipliers in every solve until they are detached
+        self._call("tolg_set_al_obstacles", B, K, _ptr(d), _ptr(lam), _ptr(imu), _ptr(self._obs_buf),
+                   C.c_size_t(self._obs_buf.numel() * 8))
+
+    def al_fit_batch(self, x0_q, x0_xi, us_init, lb=None, ub=None, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
                      tol_d_norm=1e-6, tol_constr=1e-2, mu0=1e-2, mu_scale=10.0, mu_max=1e8, line_search=False,
-                     on_outer=None, q_ref=None, xi_ref=None, Q=None, P=None, R=None):
+                     on_outer=None, q_ref=None, xi_ref=None, Q=None, P=None, R=None, obstacles=None):
         """AL_iLQR_Tracking_SE3_MS.fit (reference traoptlibrary/traopt_controller.py:3218-3267) for B
         independent problems: every outer iteration re-solves from (x0, us_init) -- no warm start, as in
         the reference -- then updates multipliers on the device.  Returns (FitResult, info dict).
-        q_ref / xi_ref: a reference per trajectory, Q / P / R: weights per trajectory, as for fit_batch."""
+        q_ref / xi_ref: a reference per trajectory, Q / P / R: weights per trajectory, as for fit_batch.
+        Constraints: the input box lb <= u <= ub, keep-out spheres obstacles ([K, 4] or [B, K, 4], set_al_obstacles), or both
+        (one mu per problem, joint convergence: tolg_al_update_state).  With spheres the info dict also holds lmbd_obs and
+        Imu_obs [B, N+1, K]; max_violation covers every constraint."""
+        if (lb is None) != (ub is None):
+            raise ValueError("the input box needs both lb and ub")
+        if lb is None and obstacles is None:
+            raise ValueError("al_fit_batch needs a constraint: lb / ub, obstacles, or both")
         b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R))
         B = b.B
+        obs = None if obstacles is None else self._check_obstacles(B, obstacles)[1]
         o = self._options("ms", n_ilqr_iters, line_search, "nonlinear", tol_grad_norm, tol_d_norm, 1e10)
         f64 = dict(dtype=torch.float64, device=self.device)
-        lam = torch.zeros(B, self.N, 2 * self.m, **f64)
-        imu = torch.full((B, self.N, 2 * self.m), float(mu0), **f64)
+        box = lb is not None
+        lam = torch.zeros(B, self.N, 2 * self.m, **f64) if box else None
+        imu = torch.full((B, self.N, 2 * self.m), float(mu0), **f64) if box else None
         mu = torch.full((B,), float(mu0), **f64)
         maxviol = torch.zeros(B, **f64)
         alconv = torch.zeros(B, dtype=torch.int32, device=self.device)
-        lb_d = self._dev(lb, (self.m,)); ub_d = self._dev(ub, (self.m,))
-        self.set_al(lb_d, ub_d, lam, imu)
+        lam_o = imu_o = None
+        if box:
+            lb_d = self._dev(lb, (self.m,)); ub_d = self._dev(ub, (self.m,))
+            self.set_al(lb_d, ub_d, lam, imu)
+        if obs is not None:
+            lam_o = torch.zeros(B, self.N + 1, obs.shape[1], **f64)
+            imu_o = torch.full((B, self.N + 1, obs.shape[1]), float(mu0), **f64)
+            try:
+                self.set_al_obstacles(obs, lam_o, imu_o)
+            except Exception:
+                if box:
+                    self.set_al(None)
+                raise
         outer = 0
         res = None
         final = None
@@ -511,13 +589,23 @@ class BatchedTrackingILQR:
                     final = res
                 if on_outer is not None:  # before the multiplier update, like on_iteration_al (:3253-3259)
                     on_outer(outer, final, lam, imu, mu)
-                self._call("tolg_al_update", B, _ptr(final.us), _ptr(lb_d), _ptr(ub_d), _ptr(lam), _ptr(imu), _ptr(mu),
-                           float(mu_scale), float(mu_max), float(tol_constr), _ptr(maxviol), _ptr(alconv))
+                if obs is None:
+                    self._call("tolg_al_update", B, _ptr(final.us), _ptr(lb_d), _ptr(ub_d), _ptr(lam), _ptr(imu), _ptr(mu),
+                               float(mu_scale), float(mu_max), float(tol_constr), _ptr(maxviol), _ptr(alconv))
+                else:  # every attached constraint, one mu per problem
+                    self._call("tolg_al_update_state", B, _ptr(final.xs_q), _ptr(final.us), _ptr(mu), float(mu_scale),
+                               float(mu_max), float(tol_constr), _ptr(maxviol), _ptr(alconv))
                 if bool(alconv.all().item()):
                     break
         finally:
-            self.set_al(None)
-        return final, dict(lmbd=lam, Imu=imu, mu=mu, max_violation=maxviol, al_converged=alconv, outer_iterations=outer + 1)
+            if box:
+                self.set_al(None)
+            if obs is not None:
+                self.set_al_obstacles(None)
+        info = dict(lmbd=lam, Imu=imu, mu=mu, max_violation=maxviol, al_converged=alconv, outer_iterations=outer + 1)
+        if obs is not None:
+            info.update(lmbd_obs=lam_o, Imu_obs=imu_o)
+        return final, info
 
     # ------------------------------------------------------------------------------------------
     def linearize_backward(self, xs_q, xs_xi, us, ms=True, mu=1.0, delta=2.0, max_reg=1e10, q_ref=None, xi_ref=None, Q=None,
@@ -716,6 +804,8 @@ class BatchedTrackingILQR:
         x0_q [B, 4, 4], x0_xi [B, 6], path_q [B, T+1, 4, 4], path_xi [B, T+1, 6]."""
         if self._al is not None:
             raise ValueError("mpc under an augmented-Lagrangian constraint is not supported: detach it with set_al(None)")
+        if self._obs is not None:
+            raise ValueError("mpc with keep-out spheres is not supported: detach them with set_al_obstacles(None)")
         if warm not in ("states", "controls"):
             raise ValueError("warm must be 'states' or 'controls'")
         if mode not in ("ms", "ss"):

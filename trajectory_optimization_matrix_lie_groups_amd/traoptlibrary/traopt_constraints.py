@@ -54,3 +54,72 @@ class InputConstraint(BaseConstraint):
         if terminal:
             return np.zeros([self.constr_size, self.action_size])
         return np.vstack([-1 * np.identity(self.action_size), np.identity(self.action_size)])
+
+
+class SphereObstacleConstraint(BaseConstraint):
+    """Keep-out spheres g_k(x) = r_k^2 - |t - c_k|^2 <= 0 on the translation t of the pose X = (R, t) of x = [X, xi], at every
+    knot, terminal included; the reference's BaseConstraint interface (traopt_constraints.py:5-63).  In the error coordinates
+    of the SE(3) costs (right perturbation X Exp(delta), twist order [omega, v]) g_x = [0, -2 (t - c)^T R, 0], g_u = 0.
+    The augmented-Lagrangian terms of these spheres run on the device (tolg_set_al_obstacles / tolg_al_update_state)."""
+
+    def __init__(self, centers, radii, state_size=(6, 6), action_size=6):
+        self._centers = np.asarray(centers, dtype=np.float64).reshape(-1, 3)
+        self._radii = np.asarray(radii, dtype=np.float64).reshape(-1)
+        if self._radii.shape[0] != self._centers.shape[0]:
+            raise ValueError("one radius per center")
+        self._state_size = state_size[0] + state_size[1]
+        self._error_state_size = state_size[0]
+        self._vel_state_size = state_size[1]
+        self._action_size = action_size
+        self._constr_size = self._radii.shape[0]
+
+    centers = property(lambda self: self._centers)
+    radii = property(lambda self: self._radii)
+    constr_size = property(lambda self: self._constr_size)
+    state_size = property(lambda self: self._state_size)
+    error_state_size = property(lambda self: self._error_state_size)
+    vel_state_size = property(lambda self: self._vel_state_size)
+    action_size = property(lambda self: self._action_size)
+
+    def obstacles(self):
+        """The spheres as rows (cx, cy, cz, r) [K, 4]: the layout of tolg_set_al_obstacles."""
+        return np.concatenate([self._centers, self._radii[:, None]], axis=1)
+
+    def g(self, x, u, i, terminal=False, *args, **kwargs):
+        d = np.asarray(x[0])[:3, 3][None] - self._centers
+        return self._radii ** 2 - np.sum(d * d, axis=1)
+
+    def g_x(self, x, u, i, terminal=False, *args, **kwargs):
+        X = np.asarray(x[0])
+        d = X[:3, 3][None] - self._centers
+        gx = np.zeros((self._constr_size, self._state_size))
+        gx[:, 3:6] = -2.0 * d @ X[:3, :3]
+        return gx
+
+    def g_u(self, x, u, i, terminal=False, *args, **kwargs):
+        return np.zeros((self._constr_size, self._action_size))
+
+
+class ConstraintStack(BaseConstraint):
+    """Several constraints as one: g, g_x, g_u concatenated in the order given."""
+
+    def __init__(self, *constraints):
+        if not constraints:
+            raise ValueError("ConstraintStack needs at least one constraint")
+        self.constraints = tuple(constraints)
+        self._constr_size = sum(c.constr_size for c in constraints)
+        self._state_size = constraints[0].state_size
+        self._action_size = constraints[0].action_size
+
+    constr_size = property(lambda self: self._constr_size)
+    state_size = property(lambda self: self._state_size)
+    action_size = property(lambda self: self._action_size)
+
+    def g(self, x, u, i, terminal=False, *args, **kwargs):
+        return np.concatenate([c.g(x, u, i, terminal) for c in self.constraints])
+
+    def g_x(self, x, u, i, terminal=False, *args, **kwargs):
+        return np.vstack([c.g_x(x, u, i, terminal) for c in self.constraints])
+
+    def g_u(self, x, u, i, terminal=False, *args, **kwargs):
+        return np.vstack([c.g_u(x, u, i, terminal) for c in self.constraints])

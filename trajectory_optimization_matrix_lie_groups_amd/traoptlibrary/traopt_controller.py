@@ -33,6 +33,8 @@ class BaseController():
 def _fusable(dynamics, cost):
     """True when (dynamics, cost) is one of the closed-form triples the HIP path implements: exact types only,
     a subclass may override any method (SURVEY.md §8b 'What calls it')."""
+    if isinstance(cost, ALConstrainedCost) and cost._host:
+        return False  # a constraint the plain controllers do not route (ALConstrainedCost evaluates it on the host)
     base = cost.cost if isinstance(cost, ALConstrainedCost) else cost
     return type(dynamics) in _KIND and type(base) is SE3TrackingQuadraticGaussNewtonCost
 
@@ -299,14 +301,29 @@ class iLQR_Tracking_SE3_MS(_FusedController):
         return self._fit_single(x0, us_init, n_iterations, tol_grad_norm, tol_d_norm, on_iteration, ms=True)
 
 
+def _route_constraints(constraints):
+    """(InputConstraint or None, SphereObstacleConstraint or None) of what AL_iLQR_Tracking_SE3_MS solves on the device: an
+    InputConstraint, a SphereObstacleConstraint, or a ConstraintStack of one of each.  TypeError for anything else: no
+    constraint is ever treated as g_x = 0."""
+    from .traopt_constraints import ConstraintStack, InputConstraint, SphereObstacleConstraint
+    parts = constraints.constraints if type(constraints) is ConstraintStack else (constraints,)
+    box = [c for c in parts if type(c) is InputConstraint]
+    sph = [c for c in parts if type(c) is SphereObstacleConstraint]
+    if len(box) > 1 or len(sph) > 1 or len(box) + len(sph) != len(parts):
+        raise TypeError("AL_iLQR_Tracking_SE3_MS supports an InputConstraint, a SphereObstacleConstraint, or a ConstraintStack "
+                        "of one of each; got %s" % ", ".join(type(c).__name__ for c in parts))
+    return (box[0] if box else None), (sph[0] if sph else None)
+
+
 class AL_iLQR_Tracking_SE3_MS(BaseController):
-    """Multiple shooting with input box constraints through an augmented Lagrangian
+    """Multiple shooting with input box constraints and keep-out spheres through an augmented Lagrangian
     (traopt_controller.py:3139-3293).  The reference class does not run at HEAD (SURVEY App. C-Q7);
     this follows its source with the three breakages repaired: the inner fit returns 7 values, the
-    inner callback has the MS 15-argument signature, q_ref/xi_ref are stored."""
+    inner callback has the MS 15-argument signature, q_ref/xi_ref are stored.  Constraints: _route_constraints."""
 
     def __init__(self, dynamics, cost, constraints, N, q_ref, xi_ref, mu_scale=10., max_reg=1e10, hessians=False,
                  line_search=False, rollout='nonlinear', debug=None):
+        self._box, self._spheres = _route_constraints(constraints)
         self.dynamics = dynamics
         self.cost = cost
         self.constr = constraints
@@ -342,11 +359,12 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
         if us_init is not None and np.ndim(us_init) == 2:
             us_init = np.broadcast_to(np.asarray(us_init, float), (B,) + np.shape(us_init)).copy()
         solver = self.ilqr_solver._get_solver(B)
-        return solver.al_fit_batch(q, xi, us_init, self.constr.lb, self.constr.ub, n_al_iters=n_al_iters,
+        box, sph = self._box, self._spheres
+        return solver.al_fit_batch(q, xi, us_init, box.lb if box else None, box.ub if box else None, n_al_iters=n_al_iters,
                                    n_ilqr_iters=n_ilqr_iters, tol_grad_norm=tol_grad_norm, tol_constr=tol_constr,
                                    mu0=self._mu0, mu_scale=self._mu_scale, mu_max=self._mu_max,
                                    line_search=self.ilqr_solver._line_search, on_outer=on_outer, q_ref=q_ref,
-                                   xi_ref=xi_ref, Q=Qs, P=Ps, R=Rs)
+                                   xi_ref=xi_ref, Q=Qs, P=Ps, R=Rs, obstacles=sph.obstacles() if sph else None)
 
     def fit(self, x0, us_init, n_al_iters=100, n_ilqr_iters=200, tol_J=1e-6, tol_grad_norm=1e-6, tol_constr=1e-2,
             on_iteration_al=None, on_iteration_ilqr=None):
@@ -356,6 +374,8 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
         def outer(iteration, res, lam, imu, mu):
             if not on_iteration_al:
                 return
+            if self._spheres is not None:
+                raise NotImplementedError("on_iteration_al reports the input box only; keep-out spheres: use fit_batch(on_outer=)")
             us = _bridge.host(res.us)[0]
             g = np.concatenate([self.constr.lb - us, us - self.constr.ub], axis=1)
             constr_eval = np.vstack([g, np.zeros((1, 2 * m))])
@@ -367,7 +387,8 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
         # the reference's inner fit ignores the outer tol_grad_norm and uses 1e-6 (:3238-3240)
         res, info = self.fit_batch([x0], np.asarray(us_init, float), n_al_iters, n_ilqr_iters, 1e-6, tol_constr,
                                    on_outer=outer)
-        self.al.lmbd[: self.N] = _bridge.host(info["lmbd"])[0]
+        if self._box is not None and self._spheres is None:
+            self.al.lmbd[: self.N] = _bridge.host(info["lmbd"])[0]
         self.al.mu = float(info["mu"][0])
         xs = _xs_list(_bridge.host(res.xs_q)[0], _bridge.host(res.xs_xi)[0])
         us = _bridge.host(res.us)[0]

@@ -113,7 +113,10 @@ DroneTrackingQuadraticGaussNewtonCost = SE3TrackingQuadraticGaussNewtonCost  # t
 
 
 class ALConstrainedCost(BaseCost):
-    """LA = l + lambda^T g + g^T I_mu g / 2 (traopt_cost.py:1173-1320) for an InputConstraint."""
+    """LA = l + lambda^T g + g^T I_mu g / 2 (traopt_cost.py:1173-1320).  The closed-form tracking cost with an InputConstraint
+    evaluates on the device (tolg_set_al + tolg_eval_knot); any other constraint (BaseConstraint: g, g_x, g_u) or any other
+    cost evaluates on the host with the reference's formulas (_host), so a plain controller handed such a cost runs the
+    generic per-knot loop (_generic_lie.py)."""
 
     def __init__(self, cost, constraints, N, state_size=(6, 6), action_size=6, **kwargs):
         self._state_size = state_size[0] + state_size[1]
@@ -134,6 +137,17 @@ class ALConstrainedCost(BaseCost):
     action_size = property(lambda self: self._action_size)
     constr_size = property(lambda self: self._constr_size)
 
+    @property
+    def _host(self):
+        from .traopt_constraints import InputConstraint
+        return type(self.constr) is not InputConstraint or type(self.cost) is not SE3TrackingQuadraticGaussNewtonCost
+
+    def _terms(self, x, u, i, terminal):
+        """g, g_x, g_u, lambda_i, I_mu,i of the reference's formulas"""
+        c = self.constr
+        return (np.asarray(c.g(x, u, i, terminal=terminal), float), np.asarray(c.g_x(x, u, i, terminal=terminal), float),
+                np.asarray(c.g_u(x, u, i, terminal=terminal), float), self.lmbd[i], self.Imu[i])
+
     def _eval(self, x, u, i, terminal=False):
         import torch
         solver = self.cost._probe()
@@ -149,23 +163,41 @@ class ALConstrainedCost(BaseCost):
             solver.set_al(None)
 
     def l(self, x, u, i, terminal=False):
+        if self._host:
+            g, _, _, lam, imu = self._terms(x, u, i, terminal)
+            return self.cost.l(x, u, i, terminal=terminal) + lam @ g + 0.5 * (g @ imu @ g)
         return float(_bridge.host(self._eval(x, u, i, terminal)["l"])[0])
 
     def l_x(self, x, u, i, terminal=False):
-        return _bridge.host(self._eval(x, u, i, terminal)["lx"])[0]  # g_x = 0
+        if self._host:
+            g, gx, _, lam, imu = self._terms(x, u, i, terminal)
+            return self.cost.l_x(x, u, i, terminal=terminal) + gx.T @ (lam + imu @ g)
+        return _bridge.host(self._eval(x, u, i, terminal)["lx"])[0]  # an InputConstraint: g_x = 0
 
     def l_u(self, x, u, i, terminal=False):
+        if self._host:
+            g, _, gu, lam, imu = self._terms(x, u, i, terminal)
+            return self.cost.l_u(x, u, i, terminal=terminal) + gu.T @ (lam + imu @ g)
         if terminal:
             return np.zeros(self._action_size)
         return _bridge.host(self._eval(x, u, i)["lu"])[0]
 
     def l_xx(self, x, u, i, terminal=False):
+        if self._host:
+            _, gx, _, _, imu = self._terms(x, u, i, terminal)
+            return self.cost.l_xx(x, u, i, terminal=terminal) + gx.T @ imu @ gx
         return _bridge.host(self._eval(x, u, i, terminal)["lxx"])[0]
 
     def l_ux(self, x, u, i, terminal=False):
+        if self._host:
+            _, gx, gu, _, imu = self._terms(x, u, i, terminal)
+            return self.cost.l_ux(x, u, i, terminal=terminal) + gu.T @ imu @ gx
         return np.zeros((self.action_size, self.state_size))
 
     def l_uu(self, x, u, i, terminal=False):
+        if self._host:
+            _, _, gu, _, imu = self._terms(x, u, i, terminal)
+            return self.cost.l_uu(x, u, i, terminal=terminal) + gu.T @ imu @ gu
         if terminal:
             return 2 * self.cost.R
         return _bridge.host(self._eval(x, u, i)["luu"])[0]

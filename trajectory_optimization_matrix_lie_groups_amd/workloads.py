@@ -270,3 +270,39 @@ def se3_mpc(B, steps, N=200, T=None, R=4, sigma_pose=0.05, sigma_twist=0.05, sig
     x0_xi = path_xi[np.arange(B), t0] + rng.normal(0.0, sigma_twist, (B, 6))
     noise = rng.normal(0.0, sigma_noise, (B, steps, 6))
     return prob, x0_q, x0_xi, path_q, path_xi, t0, noise
+
+
+def _obstacle_field(q_ref, B, K, r_lo, r_hi, seed):
+    """K seeded keep-out spheres per trajectory on its reference path: sphere k of trajectory b is centred on the reference
+    position of a knot drawn from the middle half of the horizon (ordered, one per K-th of it), moved by at most 0.3 r, with a
+    radius r uniform in [r_lo, r_hi].  The path passes through every sphere, so the unconstrained tracking optimum violates
+    them; the start and the end of the path stay clear.  Returns obstacles [B, K, 4] rows (cx, cy, cz, r)."""
+    q_ref = np.asarray(q_ref)
+    N = q_ref.shape[-3] - 1
+    rng = np.random.default_rng(seed)
+    obs = np.empty((B, K, 4))
+    lo, span = N // 4, max(1, N // 2)
+    for b in range(B):
+        t = (q_ref[b] if q_ref.ndim == 4 else q_ref)[:, :3, 3]
+        for k in range(K):
+            i = lo + int(rng.integers(k * span // K, max(k * span // K + 1, (k + 1) * span // K)))
+            r = rng.uniform(r_lo, r_hi)
+            d = rng.normal(size=3)
+            obs[b, k, :3] = t[i] + 0.3 * r * rng.uniform() * d / np.linalg.norm(d)
+            obs[b, k, 3] = r
+    return obs
+
+
+def se3_obstacle_field(B, K, N=200, seed=SEED):
+    """se3_tracking's workload with K keep-out spheres per trajectory on its reference path (_obstacle_field; radii 0.2 .. 0.4,
+    two to four knots of the path), different for every trajectory.  Returns (prob, x0_q, x0_xi, us0, obstacles [B, K, 4])."""
+    prob, x0_q, x0_xi, us0 = se3_tracking(B, N=N, seed=seed)
+    return prob, x0_q, x0_xi, us0, _obstacle_field(prob.q_ref, B, K, 0.2, 0.4, seed + 3)
+
+
+def drone_obstacle_field(B, K, N=400, seed=SEED):
+    """The drone variant (config 5, drone_tracking's workload) with K keep-out spheres per trajectory on the racing path
+    (_obstacle_field; radii 0.1 .. 0.2, four to eight knots of the path: the drone tracks its path loosely, and a smaller
+    sphere would hardly be violated).  Returns (prob, x0_q, x0_xi, us0, obstacles [B, K, 4])."""
+    prob, x0_q, x0_xi, us0 = drone_tracking(B, N=N, seed=seed)
+    return prob, x0_q, x0_xi, us0, _obstacle_field(prob.q_ref, B, K, 0.1, 0.2, seed + 3)
