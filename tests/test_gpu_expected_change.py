@@ -67,6 +67,11 @@ def test_ring_kernel_matches_statement_kernel_on_random_trajectories(kind, B, N,
     reproducible; what it hands back, the statement kernel behind it fills in.  (The entry point poisons the LDS of
     every CU with NaNs first: the statement kernel once filled its constant table AFTER inactive quads had left, and
     passed wherever the previous launch had left the same table behind.)"""
+    check_ring_against_statement(kind, B, N, spread)
+
+
+def check_ring_against_statement(kind, B, N, spread):
+    """The body of the test above, for any kind / batch / horizon / spread."""
     prob, *_ = _problem(kind, 1, N)
     xs_q, xs_xi, us = _random_traj(prob, B, seed=3 + N, spread=spread)
     if B >= 5:  # two trajectories with rotation defects near pi: candidates for the hand-back

@@ -37,3 +37,13 @@ def test_seeds_the_campaigns_flagged(seed):
     assert worst_j <= pf.TOL_J and worst_u <= pf.TOL_U, (seed, cfg, worst_j, worst_u)
     if seed != 40265:
         assert not notes, (seed, cfg, notes)
+
+
+def test_edge_shape_cases_match_oracle():
+    """The opt-in edge draw of tools/parity_fuzz.py (horizons 1 .. 33, the batches of tests/test_gpu_shapes.py: padded lanes,
+    short last workgroups, the 64-wide grids), everything else drawn as above: twenty fixed seeds."""
+    import parity_fuzz as pf
+    for seed in range(3000, 3020):
+        cfg, worst_j, worst_u, notes, stats = pf.one(seed, shapes="edge")
+        assert not notes, (seed, cfg, notes)
+        assert worst_j <= pf.TOL_J and worst_u <= pf.TOL_U, (seed, cfg, worst_j, worst_u)

@@ -190,7 +190,12 @@ def test_advance_with_references_and_weights_per_trajectory():
 
 # 5 -------------------------------------------------------------------------------------------------------------------
 def test_loop_against_the_oracle_step_by_step():
-    B, N, steps, K0, K = 8, 40, 6, 10, 3
+    check_loop(B=8, N=40, steps=6, K0=10, K=3)
+
+
+def check_loop(B, N, steps, K0, K):
+    """mpc() on se3_mpc's paths against restate_mpc_step, step by step: every window's solve, the applied input, the
+    closed-loop state and cost."""
     prob, q, xi, pq, px, t0, noise = workloads.se3_mpc(B, steps, N=N, sigma_noise=0.02, seed=21)
     s = BatchedTrackingILQR(prob, B)
     seen = []

@@ -118,7 +118,8 @@ def test_linearisation_terms(name, pt):
     assert torch.equal(b["lxx11"][..., :3, :], a["lxx11"][..., :3, :]) and torch.equal(b["lxx11"][..., 3:, :3], a["lxx11"][..., 3:, :3])
 
 
-def _host_solve(prob, x0_q, x0_xi, us0, obs, lam, imu, kw):
+def _host_solve(prob, x0_q, x0_xi, us0, obs, lam, imu, kw, states=False):
+    """The mirror's host generic path with fixed sphere multipliers: (J per iteration, us[, xs]).  states: xs as well."""
     op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
     c = SphereObstacleConstraint(obs[:, :3], obs[:, 3])
     al = ALConstrainedCost(MyCost(op, prob.m), c, prob.N)
@@ -140,7 +141,7 @@ def _host_solve(prob, x0_q, x0_xi, us0, obs, lam, imu, kw):
         else:
             ctl = iLQR_Tracking_SE3(MyDynamics(op, prob.m), al, prob.N, rollout=rollout)
         xs, us, *_ = ctl.fit([x0_q, x0_xi], us0, n_iterations=kw["n_iterations"], tol_grad_norm=0.0, on_iteration=cb)
-    return np.array(J), us
+    return (np.array(J), us, xs) if states else (np.array(J), us)
 
 
 @pytest.mark.parametrize("kw", [dict(mode="ms", n_iterations=6), dict(mode="ms", n_iterations=6, line_search=True),

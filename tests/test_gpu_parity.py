@@ -44,6 +44,28 @@ def _random_traj(prob, B, seed, spread=0.3):
     return xs_q, xs_xi, us
 
 
+def check_linearize_backward(prob, xs_q, xs_xi, us, ms, solver=None):
+    """K1 + K2 (tolg_linearize_backward) on the given trajectories against the oracle's _linearization/_backward_pass,
+    trajectory by trajectory; solver: a handle on prob (default: a fresh one of the batch's size)."""
+    B = xs_q.shape[0]
+    solver = BatchedTrackingILQR(prob, B) if solver is None else solver
+    r = solver.linearize_backward(xs_q, xs_xi, us, ms=ms)
+    torch.cuda.synchronize()
+    op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref,
+                          pend_mass=prob.pend_mass, pend_length=prob.pend_length)
+    for b in range(B):
+        o = ob.lin_backward(op, xs_q[b], xs_xi[b], us[b], ms=ms)
+        assert _rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
+        assert np.abs(r["d"][b].cpu().numpy() - o["d"]).max() < 1e-11 * max(1.0, np.abs(o["d"]).max())
+        assert _rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
+        assert _rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
+        assert float(r["J"][b]) == pytest.approx(o["J"], rel=1e-12)
+        assert _rel(r["K"][b].cpu(), o["K"]) < 1e-8
+        assert _rel(r["k"][b].cpu(), o["k"]) < 1e-8
+        assert float(r["grad"][b]) == pytest.approx(o["grad"], rel=1e-9)
+        assert float(r["mu_delta"][b, 0]) == o["mu"] and float(r["mu_delta"][b, 1]) == o["delta"]
+
+
 @pytest.mark.parametrize("kind", ["se3", "drone", "rigidbody"])
 @pytest.mark.parametrize("ms", [True, False])
 def test_linearize_backward_elementwise(kind, ms):
@@ -57,21 +79,7 @@ def test_linearize_backward_elementwise(kind, ms):
             prob = TrackingProblem("rigidbody", prob.J, prob.dt, prob.Q, np.eye(6) * 1e-4, prob.P, prob.q_ref, prob.xi_ref)
     B = 5
     xs_q, xs_xi, us = _random_traj(prob, B, seed=11)
-    solver = BatchedTrackingILQR(prob, B)
-    r = solver.linearize_backward(xs_q, xs_xi, us, ms=ms)
-    torch.cuda.synchronize()
-    op = _oracle_problem(prob)
-    for b in range(B):
-        o = ob.lin_backward(op, xs_q[b], xs_xi[b], us[b], ms=ms)
-        assert _rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
-        assert np.abs(r["d"][b].cpu().numpy() - o["d"]).max() < 1e-11 * max(1.0, np.abs(o["d"]).max())
-        assert _rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
-        assert _rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
-        assert float(r["J"][b]) == pytest.approx(o["J"], rel=1e-12)
-        assert _rel(r["K"][b].cpu(), o["K"]) < 1e-8
-        assert _rel(r["k"][b].cpu(), o["k"]) < 1e-8
-        assert float(r["grad"][b]) == pytest.approx(o["grad"], rel=1e-9)
-        assert float(r["mu_delta"][b, 0]) == o["mu"] and float(r["mu_delta"][b, 1]) == o["delta"]
+    check_linearize_backward(prob, xs_q, xs_xi, us, ms)
 
 
 def test_full_inertia_block_general_path():

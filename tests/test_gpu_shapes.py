@@ -1,0 +1,290 @@
+"""Every solve path at the horizons and batches where the fixed tiles, rings and pipelines of the kernels take their edge
+branches, against the CPU oracle (or, where stated, bitwise against the same call elsewhere):
+
+1. horizons N = 1 .. 9, 12, 23 .. 25, 31 .. 33 at B = 5 (Bp = 8, one real lane in the second group): k_rollout_lin's
+   publish_loaded / need_inputs branches (N = 1, 2, 3, 4, >= 5), every N mod 4 and N mod 8, both sides of its 24-knot
+   state ring, K2's odd and even first step, the line-search stage ring (4) and the expected-change ring (4);
+2. batches B = 1 .. 4, 15 .. 17, 20, 63 .. 65, 68 at N = 3 and 25: padded lanes, k_rollout_lin's short last workgroup
+   (12, 0 and 4 trajectories), the 64-wide grids; a trajectory's bits do not depend on its lane;
+3. the unit entry points (linearize_backward, expected_change) at N = 1 .. 5, which localise a failure of 1 to one kernel;
+4. one handle reused across batch sizes, each call bitwise the same call on a fresh handle (a smaller Bp re-strides the
+   workspace over what the previous solve left there);
+5. MPC, the held policy and the augmented-Lagrangian outer loop at N = 1, 2, 3, 5.
+
+Iteration counts are chosen below the first no-descent exit of the oracle at every shape (the searches at N <= 5 stop
+with status 2 after 4 .. 7 iterations at a cost floor, where the exit is decided by rounding)."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import bridge as ob
+from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, workloads
+from trajectory_optimization_matrix_lie_groups_amd.solver import embed_pendulum3d
+from tests.test_gpu_expected_change import check_ring_against_statement
+from tests.test_gpu_fused import _assert_same
+from tests.test_gpu_mpc import _check_advance, check_loop
+from tests.test_gpu_multiref import _assert_bitwise, _dense
+from tests.test_gpu_obstacles import _host_solve, _update_restated
+from tests.test_gpu_parity import _al_oracle, _random_traj, check_linearize_backward
+from tests.test_gpu_policy import _check_restatement, _op, _pert
+
+pytestmark = pytest.mark.gpu
+
+HORIZONS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 23, 24, 25, 31, 32, 33]
+BATCHES = [1, 2, 3, 4, 15, 16, 17, 20, 63, 64, 65, 68]
+SHORT = [1, 2, 3, 4, 5]
+ZERO = dict(tol_grad_norm=0.0, tol_d_norm=0.0)
+
+
+def _rel(a, b):
+    a = np.asarray(a); b = np.asarray(b)
+    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+
+
+def _pendulum(B, N):
+    """Pendulum3dDyanmics on the first N + 1 knots of path_3dpendulum_swingup (pendulum_swingup's model and initial states)."""
+    _, q, xi, _ = workloads.pendulum_swingup(B)
+    R_ref, w_ref, dt = workloads.load_reference("pendulum_swingup_n80")
+    Q6 = np.diag([10.0, 10, 10, 1, 1, 1])
+    prob = embed_pendulum3d(np.diag([0.5, 0.7, 0.9]), 1.0, 0.5, dt, Q6, np.eye(3) * 1e-2, 10 * Q6, R_ref[:N + 1], w_ref[:N + 1])
+    return prob, q, xi, np.zeros((B, N, 6))
+
+
+def _model(name, B, N):
+    if name == "drone":
+        return workloads.drone_tracking(B, N=N)
+    if name == "so3":
+        return workloads.so3_tracking(B, N=N)
+    if name == "pendulum":
+        return _pendulum(B, N)
+    prob, q, xi, us = workloads.se3_tracking(B, N=N)
+    if name == "dense":
+        prob = _dense(prob)
+    elif name == "rigidbody":
+        prob = TrackingProblem("rigidbody", prob.J, prob.dt, prob.Q, np.eye(6) * 1e-4, prob.P, prob.q_ref, prob.xi_ref)
+    return prob, q, xi, us
+
+
+KEEP = ("xs_q", "xs_xi", "us", "J_hist", "grad_hist", "defect_hist", "mu_hist", "iters", "status", "converged")
+
+
+def _solve(s, q, xi, us, K, **kw):
+    r = s.fit_batch(q, xi, us, n_iterations=K, **ZERO, **kw)
+    torch.cuda.synchronize()
+    return {k: getattr(r, k).clone() for k in KEEP}
+
+
+def _against_oracle(g, o, tol_j, what):
+    """The assertions of test_line_search_and_linear_rollout_variants_match_oracle: exits exactly, costs over the
+    iterations taken, the final controls and twists."""
+    it = g["iters"].cpu().numpy()
+    np.testing.assert_array_equal(it, o["iters"], err_msg=what)
+    np.testing.assert_array_equal(g["status"].cpu().numpy(), o["status"], err_msg=what)
+    Jg = g["J_hist"].cpu().numpy()
+    for b in range(len(it)):
+        assert _rel(Jg[b, :it[b]], o["J_hist"][b, :it[b]]) < tol_j, (what, b)
+    assert _rel(g["us"].cpu(), o["us"]) < 1e-6, what
+    assert _rel(g["xs_xi"].cpu(), o["xs_xi"]) < 1e-6, what
+
+
+# (model, fit_batch keywords, iterations): K below the oracle's first no-descent exit at every horizon of the sweep
+SWEEP = [("se3", dict(mode="ms", schedule="auto"), 6),
+         ("se3", dict(mode="ss"), 4),
+         ("se3", dict(mode="ms", line_search=True), 4),
+         ("se3", dict(mode="ms", rollout="linear"), 6),
+         ("se3", dict(mode="ss", rollout="linear"), 4),
+         ("drone", dict(mode="ms"), 6),
+         ("drone", dict(mode="ss"), 3),
+         ("so3", dict(mode="ms"), 6),
+         ("so3", dict(mode="ss"), 6),
+         ("dense", dict(mode="ms"), 6),
+         ("dense", dict(mode="ms", line_search=True), 4),
+         ("pendulum", dict(mode="ms"), 6),
+         ("pendulum", dict(mode="ms", line_search=True), 4)]
+
+
+# 1 -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N", HORIZONS)
+def test_horizon_sweep_against_the_oracle(N):
+    B = 5
+    handles = {}
+    for name, kw, K in SWEEP:
+        if name not in handles:
+            m = _model(name, B, N)
+            handles[name] = (BatchedTrackingILQR(m[0], B),) + m
+        s, prob, q, xi, us = handles[name]
+        what = "%s %s N=%d" % (name, kw, N)
+        g = _solve(s, q, xi, us, K, **kw)
+        o = ob.fit_batch(_op(prob), q, xi, us, max_iter=K, mode=kw["mode"], line_search=kw.get("line_search", False),
+                         rollout=kw.get("rollout", "nonlinear"))
+        searching = kw.get("line_search", False) or kw["mode"] == "ss"
+        _against_oracle(g, o, 1e-8 if searching else 1e-9, what)
+        if kw.get("schedule") == "auto":  # the fused launch against the split schedule on the same handle
+            _assert_same(g, s.fit_batch(q, xi, us, n_iterations=K, schedule="split", **ZERO, mode="ms"))
+
+
+# 2 -------------------------------------------------------------------------------------------------------------------
+def _lanes(B):
+    """The trajectories compared with the oracle: all of a small batch; of a large one the first lanes, the first and last
+    lanes of each 16-wide workgroup and 64-wide block it touches, and the last real lanes (B - 1 included)."""
+    if B <= 20:
+        return np.arange(B)
+    return np.array(sorted({0, 1, 3, 4, 15, 16, 47, 48, B - 5, B - 4, B - 2, B - 1} & set(range(B))))
+
+
+@pytest.mark.parametrize("N", [3, 25])
+@pytest.mark.parametrize("B", BATCHES)
+def test_batch_sweep_against_the_oracle(B, N):
+    prob, q, xi, us = workloads.se3_tracking(B, N=N)
+    s = BatchedTrackingILQR(prob, B)
+    lanes = _lanes(B)
+    assert len(lanes) >= min(B, 8) and lanes[-1] == B - 1
+    for kw, K in ((dict(mode="ms"), 6), (dict(mode="ss"), 4), (dict(mode="ms", line_search=True), 4)):
+        g = _solve(s, q, xi, us, K, **kw)
+        o = ob.fit_batch(_op(prob), q[lanes], xi[lanes], us[lanes], max_iter=K, mode=kw["mode"],
+                         line_search=kw.get("line_search", False))
+        sub = {k: v[torch.as_tensor(lanes, device=v.device)] for k, v in g.items()}
+        _against_oracle(sub, o, 1e-9 if kw == dict(mode="ms") else 1e-8, "%s B=%d N=%d" % (kw, B, N))
+
+
+@pytest.mark.parametrize("N", [3, 25])
+def test_a_trajectory_does_not_depend_on_its_lane(N):
+    """Accept-always MS (the benign regime in which test_full_size_properties_4096x200 asserts the same): trajectory t alone
+    (B = 1) is bitwise the same trajectory at the last real lane of B = 17 (alone in k_rollout_lin's last workgroup and in
+    its group of four) and of B = 65 (past the first 64-wide block)."""
+    prob, q, xi, us = workloads.se3_tracking(65, N=N)
+    kw = dict(mode="ms", n_iterations=6, **ZERO)
+    for t in (0, 7):
+        r1 = BatchedTrackingILQR(prob, 1).fit_batch(q[t:t + 1], xi[t:t + 1], us[t:t + 1], **kw)
+        torch.cuda.synchronize()
+        for B in (17, 65):
+            qb, xb = q[:B].copy(), xi[:B].copy()
+            qb[B - 1], xb[B - 1] = q[t], xi[t]
+            rb = BatchedTrackingILQR(prob, B).fit_batch(qb, xb, us[:B], **kw)
+            torch.cuda.synchronize()
+            _assert_bitwise(r1, rb, slice(0, 1), slice(B - 1, B), what="t=%d at lane %d of B=%d" % (t, B - 1, B))
+
+
+# 3 -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N", SHORT)
+@pytest.mark.parametrize("name", ["se3", "drone", "rigidbody", "so3", "dense", "pendulum"])
+def test_linearize_backward_at_short_horizons(name, N):
+    B = 5
+    prob = _model(name, B, N)[0]
+    xs_q, xs_xi, us = _random_traj(prob, B, seed=11 + N)
+    if name in ("so3", "pendulum"):  # the embedding: translation, linear twist and inputs 3..5 are zero
+        xs_q[..., :3, 3] = 0.0
+        xs_xi[..., 3:] = 0.0
+        us[..., 3:] = 0.0
+    s = BatchedTrackingILQR(prob, B)
+    for ms in (True, False):
+        check_linearize_backward(prob, xs_q, xs_xi, us, ms, solver=s)
+
+
+@pytest.mark.parametrize("N", SHORT)
+@pytest.mark.parametrize("kind", ["se3", "drone", "so3", "se3_dense"])
+def test_expected_change_ring_form_at_short_horizons(kind, N):
+    for spread in (0.02, 0.15):
+        check_ring_against_statement(kind, 5, N, spread)
+
+
+# 4 -------------------------------------------------------------------------------------------------------------------
+def test_one_handle_across_batch_sizes():
+    """B = 68 merit search, 17 accept-always, 1 SS, 65 with a reference per trajectory, 5 accept-always, in that order on one
+    handle: each the bits of the same call on a fresh handle."""
+    N, MAXB = 25, 68
+    prob, q, xi, us, q_ref, xi_ref, _, _ = workloads.se3_multiref(MAXB, 3, N=N)
+    calls = [(68, dict(mode="ms", n_iterations=6, line_search=True)),
+             (17, dict(mode="ms", n_iterations=6, **ZERO)),
+             (1, dict(mode="ss", n_iterations=6)),
+             (65, dict(mode="ms", n_iterations=6, **ZERO, refs=True)),
+             (5, dict(mode="ms", n_iterations=6, **ZERO))]
+    s = BatchedTrackingILQR(prob, MAXB)
+    for B, kw in calls:
+        kw = dict(kw)
+        if kw.pop("refs", False):
+            kw.update(q_ref=q_ref[:B], xi_ref=xi_ref[:B])
+        a = s.fit_batch(q[:B], xi[:B], us[:B], **kw)
+        torch.cuda.synchronize()
+        f = BatchedTrackingILQR(prob, MAXB).fit_batch(q[:B], xi[:B], us[:B], **kw)
+        torch.cuda.synchronize()
+        _assert_bitwise(a, f, what="B=%d after the previous calls" % B)
+
+
+# 5 -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N", [1, 2, 3, 5])
+@pytest.mark.parametrize("name", ["se3", "drone", "so3", "pendulum"])
+def test_mpc_advance_and_policy_at_short_horizons(name, N):
+    B = 5
+    prob, q, xi, us = _model(name, B, N)
+    s = BatchedTrackingILQR(prob, B)
+    r = s.fit_batch(q, xi, us, mode="ms", n_iterations=8, **ZERO)
+    dx0, w = _pert(B, 4, N, seed=11, **(dict(pose=1e-3, twist=1e-3, noise=1e-4) if name == "pendulum" else {}))
+    if name in ("so3", "pendulum"):  # the embedding's translation and linear twist stay zero
+        dx0[..., 3:6] = dx0[..., 9:] = 0.0
+        w[..., 3:] = 0.0
+    _check_restatement(s, r, [_op(prob)] * B, dx0, w)
+    wa = np.random.default_rng(3).normal(0, 0.01, (B, 6))
+    if name in ("so3", "pendulum"):
+        wa[:, 3:] = 0.0
+    _check_advance(s, r, [_op(prob)] * B, wa)
+
+
+@pytest.mark.parametrize("N", [1, 2, 3, 5])
+def test_mpc_loop_at_short_horizons(N):
+    check_loop(B=5, N=N, steps=3, K0=6, K=3)
+
+
+@pytest.mark.parametrize("N", [1, 2, 3, 5])
+def test_al_input_box_at_short_horizons(N):
+    """al_fit_batch with an input box at half the unconstrained solution's largest input, against the restated outer loop."""
+    B = 3
+    prob, q, xi, us0 = workloads.se3_tracking(B, N=N, R_scale=1e-3)
+    s = BatchedTrackingILQR(prob, B)
+    free = s.fit_batch(q, xi, us0, mode="ms", n_iterations=30)
+    box = 0.5 * float(free.us.abs().max())
+    lb, ub = -box * np.ones(6), box * np.ones(6)
+    n_al, n_in, tol = 4, 30, 1e-2
+    res, info = s.al_fit_batch(q, xi, us0, lb, ub, n_al_iters=n_al, n_ilqr_iters=n_in, tol_constr=tol)
+    torch.cuda.synchronize()
+    for b in range(B):
+        o, lam, imu, mu, n_outer = _al_oracle(prob, q[b], xi[b], us0[b], lb, ub, n_al, n_in, tol)
+        assert _rel(res.us[b].cpu(), o["us"]) < 1e-6
+        assert _rel(res.xs_xi[b].cpu(), o["xs_xi"]) < 1e-6
+        assert _rel(info["lmbd"][b].cpu(), lam) < 1e-6
+        assert float(info["mu"][b]) == pytest.approx(mu)
+        np.testing.assert_array_equal(info["Imu"][b].cpu().numpy() == 0.0, imu == 0.0)
+
+
+@pytest.mark.parametrize("N", [1, 2, 3, 5])
+def test_al_keep_out_sphere_at_short_horizons(N):
+    """al_fit_batch with one keep-out sphere around each trajectory's initial position (a short horizon does not get far
+    from it), two outer iterations of fixed inner length, against the outer loop restated on the mirror's host generic path
+    (_host_solve) and the multiplier update (_update_restated)."""
+    B, n_al, n_in, mu0 = 2, 2, 6, 1.0
+    prob, q, xi, us0 = workloads.se3_tracking(B, N=N, R_scale=1e-3)
+    obs = np.zeros((B, 1, 4))
+    obs[:, 0, :3] = q[:, :3, 3] + np.array([0.1, -0.03, 0.02])
+    obs[:, 0, 3] = 0.3
+    s = BatchedTrackingILQR(prob, B)
+    res, info = s.al_fit_batch(q, xi, us0, n_al_iters=n_al, n_ilqr_iters=n_in, obstacles=obs, mu0=mu0, tol_constr=1e-12,
+                               **ZERO)
+    torch.cuda.synchronize()
+    assert info["outer_iterations"] == n_al
+    for b in range(B):
+        lam, imu, mu = np.zeros((N + 1, 1)), np.full((N + 1, 1), mu0), mu0
+        for it in range(n_al):
+            J, us, xs = _host_solve(prob, q[b], xi[b], us0[b], obs[b], lam, imu, dict(mode="ms", n_iterations=n_in),
+                                    states=True)
+            t = np.array([x[0][:3, 3] for x in xs])
+            g = obs[b, None, :, 3] ** 2 - np.sum((t[:, None, :] - obs[b, None, :, :3]) ** 2, axis=-1)
+            if it == 0:
+                assert g.max() > 1e-2  # the first solve violates
+            lam, imu = _update_restated(g, lam, imu, mu)
+            mu *= 10.0
+        assert int(res.iters[b]) == len(J) and int(res.status[b]) == 0
+        assert np.abs(res.J_hist[b, :len(J)].cpu().numpy() / J - 1).max() < 1e-9
+        assert np.abs(res.us[b].cpu().numpy() - us).max() < 1e-6 * max(1.0, np.abs(us).max())
+        assert np.abs(info["lmbd_obs"][b].cpu().numpy() - lam).max() <= 1e-9 * max(1.0, np.abs(lam).max())
+        np.testing.assert_array_equal(info["Imu_obs"][b].cpu().numpy() == 0.0, imu == 0.0)
+        assert float(info["mu"][b]) == pytest.approx(mu)

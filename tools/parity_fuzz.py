@@ -4,7 +4,7 @@
 step, the spread of the initial states and of the initial controls), each case against the oracle.  Looks for the rare
 paths the fixed cases do not visit (regularisation retries, the max-regularisation exit, the closed-form tiers of the
 series, deep backtracking).  Prints one line per disagreement with the seed that reproduces it.
-    python tools/parity_fuzz.py [--large] [cases] [first seed]"""
+    python tools/parity_fuzz.py [--large | --edge] [cases] [first seed]"""
 import os
 import sys
 
@@ -32,14 +32,23 @@ LARGE = False    # --large: batches of 500 .. 6 000 (the compacted lists and the
 NKINDS = 5       # model kinds drawn from: the first campaign (seeds 1000 .. 6999) drew among the first three, the second among four
 
 
-def draw(seed, nkinds=None):
+EDGE_BATCHES = (1, 2, 3, 4, 15, 16, 17, 20, 63, 64, 65, 68)   # shapes="edge": padded lanes, short last workgroups, the 64-wide grids
+
+
+def draw(seed, nkinds=None, shapes="default"):
+    """One random case: (cfg, prob or (prob, oracle problem), x0_q, x0_xi, us0).  shapes="edge" draws the horizon from
+    [1, 34) (every branch of the short-horizon rings and pipelines) and the batch from EDGE_BATCHES instead; every other
+    draw, and the default draws themselves, stay as they are."""
     rng = np.random.default_rng(seed)
     kind = ["se3", "rigidbody", "drone", "so3", "pendulum"][rng.integers(nkinds or NKINDS)]
     diag = bool(rng.integers(4) > 0)
     mode = ["ms", "ss"][rng.integers(2)]
     line_search = bool(rng.integers(2)) if mode == "ms" else False
     rollout = ["nonlinear", "linear"][int(rng.integers(4) == 0)]
-    B, N = int(rng.integers(1, 10)), int(rng.integers(3, 70))
+    if shapes == "edge":
+        B, N = EDGE_BATCHES[int(rng.integers(len(EDGE_BATCHES)))], int(rng.integers(1, 34))
+    else:
+        B, N = int(rng.integers(1, 10)), int(rng.integers(3, 70))
     if LARGE:
         B, N = int(rng.integers(500, 6000)), int(rng.integers(40, 201))
     if kind == "pendulum":
@@ -136,14 +145,22 @@ def pd_flip(b, solver, op, cfg, x0_q, x0_xi, us0, st, o, mu_g, mu_o, Jg):
         return False
 
 
-def one(seed, nkinds=None):
-    cfg, prob, x0_q, x0_xi, us0 = draw(seed, nkinds)
-    K, B = cfg["K"], cfg["B"]
+def one(seed, nkinds=None, shapes="default"):
+    cfg, prob, x0_q, x0_xi, us0 = draw(seed, nkinds, shapes)
     if isinstance(prob, tuple):
         prob, op = prob
     else:
         op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
-    solver = BatchedTrackingILQR(prob, B)
+    return (cfg,) + check(cfg, prob, op, x0_q, x0_xi, us0)
+
+
+def check(cfg, prob, op, x0_q, x0_xi, us0, solver=None):
+    """One case against the oracle: the GPU solve of cfg (mode, line_search, rollout, K = iterations, all of the batch) on
+    prob, the oracle's on op, every trajectory compared with the classes below.  solver: a handle on prob to solve on
+    (default: a fresh one of the case's batch).  Returns (worst_j, worst_u, notes, stats): the worst J / u distance in
+    units of TOL_J / TOL_U times those, the disagreements no class accepts, and the count of each oracle status / class."""
+    K, B = cfg["K"], cfg["B"]
+    solver = BatchedTrackingILQR(prob, B) if solver is None else solver
     r = solver.fit_batch(x0_q, x0_xi, us0, mode=cfg["mode"], n_iterations=K, tol_grad_norm=0.0, tol_d_norm=0.0,
                          line_search=cfg["line_search"], rollout=cfg["rollout"])
     kw = dict(mode=cfg["mode"], max_iter=K, line_search=cfg["line_search"], rollout=cfg["rollout"])
@@ -284,7 +301,7 @@ def one(seed, nkinds=None):
             elif ref is not None:
                 nfu = np.inf
             worst_u = max(worst_u, max(eu - slack, 0.0) / max(tol_u0, 10.0 * nfu) * TOL_U)
-    return cfg, worst_j, worst_u, notes, stats
+    return worst_j, worst_u, notes, stats
 
 
 def main():
@@ -292,6 +309,7 @@ def main():
     flags = [a for a in sys.argv[1:] if a.startswith("--")]
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     LARGE = "--large" in flags
+    shapes = "edge" if "--edge" in flags else "default"
     REFEREE = "--no-referee" not in flags
     for f in flags:
         if f.startswith("--kinds="):
@@ -301,7 +319,7 @@ def main():
     bad = 0
     status_total = {}
     for seed in range(s0, s0 + n):
-        cfg, wj, wu, notes, stats = one(seed)
+        cfg, wj, wu, notes, stats = one(seed, shapes=shapes)
         for k, v in stats.items():
             status_total[k] = status_total.get(k, 0) + v
         flag = wj > TOL_J or wu > TOL_U or notes
