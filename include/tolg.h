@@ -349,6 +349,32 @@ int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, double* d_x_
                      double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl,
                      void* stream);
 
+/* Plants: per-sample dynamics parameters that step the closed loops of tolg_policy_rollout and tolg_mpc_advance in place of
+ * the model's (model mismatch: a payload change, a mis-identified inertia, domain randomisation).  The planner's model stays
+ * the handle's tolg_problem, and so do dt, gravity, kind, m, the input map, the cost, the reference and the weights.
+ *   in : d_J [B][S][36] row-major 6x6 blkdiag(Ib, Jv), SPD, under the rule of tolg_problem.J (SO3 family: blkdiag(J_so3, I3));
+ *        d_pend [B][S][2] (pend_mass, pend_length) for TOLG_DYN_PENDULUM3D, NULL for every other kind.
+ *   form: TOLG_PLANT_DIAG is the caller's promise that every block is diagonal (only the diagonals are read);
+ *         TOLG_PLANT_DENSE takes any blkdiag(Ib, Jv), diagonal ones included.
+ * Row (b, s) derives Ibinv, Jvinv, Bt = Ibinv dt, mass = J[4][4], mass * grav and pend_k = pend_mass * pend_length / 2 as
+ * tolg_create derives the model's; the diagonal form's inverses are the correctly rounded 1.0 / d, so a diagonal plant equal
+ * to the model steps with the model's bits.  The rows are packed into the caller-owned d_packed (field-major over the B S
+ * rows, packed_bytes >= tolg_plant_bytes(prob, B, S)), which the handle reads until the plant is detached (d_J = NULL).
+ * While a plant is set:
+ *   tolg_policy_rollout(B, S') steps sample (b, s) with row (b, s) when S == S', with row (b, 0) for every sample when S == 1;
+ *     another S' or another B is TOLG_E_ARG.  Control law, noise and cost are unchanged: J is the tracking cost of the
+ *     trajectory the plant produced;
+ *   tolg_mpc_advance requires S == 1 (else TOLG_E_ARG): x_next (and xs_warm[0]) steps plant row b; the warm tail
+ *     xs_warm[N] = f(x*_N, u*_{N-1}) is the model's prediction; u_applied and J_cl are unchanged.
+ * Every other entry point ignores the plant (the same bits as with none).  It survives solves, tolg_set_refs and
+ * tolg_set_weights; tolg_create starts without one; tolg_set_plant leaves the held policy.
+ * TOLG_E_ARG: a solve in flight, B < 1 or B > max_batch, S < 1, an unknown form, a NULL or too small d_packed, a NULL d_pend
+ * for the pendulum or a non-NULL one for any other kind. */
+enum { TOLG_PLANT_DIAG = 0, TOLG_PLANT_DENSE = 1 };
+size_t tolg_plant_bytes(const tolg_problem* prob, int32_t max_batch, int32_t S);
+int tolg_set_plant(tolg_handle_t h, int32_t B, int32_t S, int32_t form, const double* d_J, const double* d_pend,
+                   double* d_packed, size_t packed_bytes, void* stream);
+
 /* Timing hook for bench.py: HIP-event time (ms) and launch count of the dominant kernel
  * (backward sweep) accumulated since the last call with reset != 0.  Synchronises the recorded
  * events only.  Timing is not free: an event pair per launch lengthens an accept-always iteration

@@ -506,6 +506,131 @@ TOLG_DEV State dyn_f_any(const DynK& K, const CT& C, const State& S, const doubl
 }
 
 // ------------------------------------------------------------------------------------------------
+// plants (tolg_set_plant): per-sample dynamics parameters that step the closed loops of tolg_policy_rollout and
+// tolg_mpc_advance only.  Rows r = b S_plant + s, packed by k_pack_plant field-major: field f of row r at f * R + r (R rows).
+// PL_NONE steps the model (the kernels as they were); PL_DIAG reads the diagonals of the blocks and their pre-divided constants
+// into the pinned DynK; PL_DENSE steps dyn_f on a per-lane view of the row (PlantC), read per step.
+// ------------------------------------------------------------------------------------------------
+enum { PL_NONE = 0, PL_DIAG = 1, PL_DENSE = 2 };
+// the diagonal form: diag(Ib), diag(Jv), Bt = diag(Ib)^-1 dt, diag(Jv)^-1, mass * grav, pend_k
+enum { PLD_IB = 0, PLD_JV = 3, PLD_BT = 6, PLD_JVI = 9, PLD_MG = 12, PLD_PK = 13, PLD_F = 14 };
+// the dense form: Ib, Jv, their inverses (row-major 3x3), mass, pend_k
+enum { PLN_IB = 0, PLN_JV = 9, PLN_IBI = 18, PLN_JVI = 27, PLN_MASS = 36, PLN_PK = 37, PLN_F = 38 };
+struct PlantArg {
+  const double* p;  // the packed rows
+  int rows, S;      // R = B S_plant; S_plant (1: row b serves every sample of trajectory b)
+};
+// one 3x3 block of a row, read by the row-major index of the Consts array it stands for
+struct PlantM3 {
+  const double* p; size_t s;
+  TOLG_DEV double operator[](int i) const { return p[(size_t)i * s]; }
+};
+TOLG_DEV V3 mv33(const PlantM3& A, V3 x) {
+  return v3(A[0] * x.x + A[1] * x.y + A[2] * x.z, A[3] * x.x + A[4] * x.y + A[5] * x.z,
+            A[6] * x.x + A[7] * x.y + A[8] * x.z);
+}
+// What dyn_f / dyn_twist_k read of the constants, for one plant row: the model's kind, dt and gravity, the plant's inertia and
+// pendulum.  The diagonal form takes pend_k alone from it (PlantPK); the dense form steps with all of it, with diagJ = 0, so
+// that dyn_f takes its dense branch (Bt is read in the diagonal branch alone: it views Ibinv).
+struct PlantC {
+  int kind, diagJ;
+  double dt, mass, grav, pend_k;
+  PlantM3 Ib, Jv, Ibinv, Jvinv, Bt;
+};
+TOLG_DEV size_t plant_row(const PlantArg& pa, int b, size_t bs) { return pa.S == 1 ? (size_t)b : bs; }
+template <int PL>
+TOLG_DEV PlantC plant_c(const Consts& C, const PlantArg& pa, size_t r) {
+  PlantC V = {};
+  if constexpr (PL == PL_NONE) return V;  // not read (plant_or_model)
+  V.kind = C.kind; V.dt = C.dt; V.grav = C.grav;
+  const size_t s = (size_t)pa.rows;
+  const double* p = pa.p + r;
+  if constexpr (PL == PL_DIAG) {
+    V.diagJ = 1; V.mass = 0.0;
+    V.pend_k = pin_v(p[PLD_PK * s]);
+    V.Ib = V.Jv = V.Ibinv = V.Jvinv = V.Bt = PlantM3{p, s};  // not read: the steps read the model's (plant_or_model)
+  } else if constexpr (PL == PL_DENSE) {
+    V.diagJ = 0;
+    V.mass = p[PLN_MASS * s];
+    V.pend_k = p[PLN_PK * s];
+    V.Ib = PlantM3{p + PLN_IB * s, s}; V.Jv = PlantM3{p + PLN_JV * s, s};
+    V.Ibinv = PlantM3{p + PLN_IBI * s, s}; V.Jvinv = PlantM3{p + PLN_JVI * s, s};
+    V.Bt = V.Ibinv;
+  }
+  return V;
+}
+TOLG_DEV bool opaque_true() {
+  int one = 1;
+  asm volatile("" : "+s"(one));
+  return one != 0;
+}
+// the DynK of a plant row: the diagonal form pins its constants as dynk_load pins the model's (same chain); the dense form
+// keeps dt alone (the series gate of the rollout step) and steps dyn_f.  PL_NONE: the model's, dynk_load.
+template <int PL>
+TOLG_DEV DynK plant_dynk(const Consts& C, const PlantArg& pa, size_t r) {
+  if constexpr (PL == PL_NONE) return dynk_load(C);
+  DynK K;
+  K.dt = pin_v(C.dt);
+  const size_t s = (size_t)pa.rows;
+  const double* p = pa.p + r;
+  if constexpr (PL == PL_DIAG) {
+    // true, but a run-time value as the model's C.diagJ is: with the dense branch of dyn_f_k / roll_step folded away, the
+    // compiler fuses other multiply-adds across the merged blocks, and a plant equal to the model would lose the model's bits
+    K.diag = opaque_true();
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      K.ib[a] = pin_v(p[(PLD_IB + a) * s]); K.jv[a] = pin_v(p[(PLD_JV + a) * s]);
+      K.bt[a] = pin_v(p[(PLD_BT + a) * s]); K.jvi[a] = pin_v(p[(PLD_JVI + a) * s]);
+    }
+    K.mg = pin_v(p[PLD_MG * s]);
+  } else {
+    K.diag = false;
+#pragma unroll
+    for (int a = 0; a < 3; a++) K.ib[a] = K.jv[a] = K.bt[a] = K.jvi[a] = 0.0;
+    K.mg = 0.0;
+  }
+  return K;
+}
+// The view one step of the dense form reads: its block pointers made opaque, so that the 36 loads of the blocks stay in the
+// step (L1 / L2 hits; the four lanes of a quad share the addresses) instead of being hoisted out of the knot loop and pinned
+// in a kernel that already runs at about 410 VGPRs.  The other forms: the view as it is.
+TOLG_DEV const double* opaque_ptr(const double* p) {
+  unsigned long long x = reinterpret_cast<unsigned long long>(p);
+  asm volatile("" : "+v"(x));
+  return reinterpret_cast<const double*>(x);
+}
+template <int PL>
+TOLG_DEV PlantC plant_step(const PlantC& V) {
+  PlantC W = V;
+  if constexpr (PL == PL_DENSE) {
+    W.Ib.p = opaque_ptr(V.Ib.p); W.Jv.p = opaque_ptr(V.Jv.p);
+    W.Ibinv.p = opaque_ptr(V.Ibinv.p); W.Jvinv.p = opaque_ptr(V.Jvinv.p);
+    W.Bt = W.Ibinv;
+  }
+  return W;
+}
+// the plant of a closed-loop kernel: its trailing argument, none for PL_NONE
+TOLG_DEV PlantArg plant_arg_of() { return PlantArg{nullptr, 0, 0}; }
+TOLG_DEV PlantArg plant_arg_of(const PlantArg& a) { return a; }
+// The diagonal form's view for the pendulum: the model's constants, by reference, with the plant row's pend_k.  (The diagonal
+// form steps with the pinned DynK; what else it reads of the constants must be the model's very loads, so that the compiler
+// lays out and fuses the step as it does the model's: a view of its own changed the fused multiply-adds of the step.)
+struct PlantPK {
+  const int &kind, &diagJ;
+  const double &dt, &mass, &grav;
+  double pend_k;
+  const double (&Ib)[9], (&Jv)[9], (&Ibinv)[9], (&Jvinv)[9], (&Bt)[9];
+};
+// the constants a closed-loop kernel steps with: the model's (PL_NONE; the diagonal form but for the pendulum's pend_k) or the
+// dense form's view of the plant row
+template <int PL, int PK>
+TOLG_DEV decltype(auto) plant_or_model(const Consts& C, const PlantC& V) {
+  if constexpr (PL == PL_NONE || (PL == PL_DIAG && PK != 1)) return (C);
+  else if constexpr (PL == PL_DIAG) return PlantPK{C.kind, C.diagJ, C.dt, C.mass, C.grav, V.pend_k, C.Ib, C.Jv, C.Ibinv, C.Jvinv, C.Bt};
+  else return (V);
+}
+
+// ------------------------------------------------------------------------------------------------
 // pack / unpack between the reference's 4x4 AoS layout (C ABI) and the device SoA layout
 // ------------------------------------------------------------------------------------------------
 TOLG_DEV Pose pose_from_m16(const double* __restrict__ Mx) {
@@ -2940,12 +3065,16 @@ __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nsl
 // wave; traj_fast = 1 is K3's order (c = s B + b).  Every value a quad computes is its own: the series gates are wave-wide
 // only in which tiers run (tolg_lie.h), so a sample's bits do not depend on S, on the order or on its neighbours.
 // Generic constants pointer: cost and dynamics on one chain is the construct the note at DConsts warns about.
-template <int M, int PK, int PT>
+// PL: the plant the samples are stepped with (tolg_set_plant, the one trailing argument pl: a PlantArg), PL_NONE the model
+// (no trailing argument: the kernel of the tables without a plant, its code unchanged by the plant forms).  The cost is the
+// model's in every form.
+template <int M, int PK, int PT, int PL = PL_NONE, class... PA>
 __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj_fast, const double* __restrict__ dx0,
                                                        const double* __restrict__ noise, double* __restrict__ Jout,
                                                        int* __restrict__ status, double* __restrict__ xs_q,
-                                                       double* __restrict__ xs_xi, double* __restrict__ us) {
+                                                       double* __restrict__ xs_xi, double* __restrict__ us, PA... pl) {
   const Consts& C = *P.c;
+  const PlantArg pa = plant_arg_of(pl...);
   const size_t n = (size_t)P.B * (size_t)S;
   size_t c = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
   const int q = threadIdx.x & 3;
@@ -2958,7 +3087,9 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
   const bool writer = live && q == 0;
   const int N = P.N;
   const unsigned sB = (unsigned)P.Bp * 8u, vb = (unsigned)b * 8u;
-  const DynK DK = dynk_load(C);
+  const size_t pr = PL == PL_NONE ? 0 : plant_row(pa, b, bs);
+  const DynK DK = plant_dynk<PL>(C, pa, pr);
+  const PlantC V = plant_c<PL>(C, pa, pr);  // what the steps read in place of the model's constants (PL_NONE: nothing)
   State Sa = roll_load_state(P, 0, vb, sB), Sb = Sa;
   State Sn = Sa;  // x^_0 = x*_0 (+) dx0: pose x*_0 Exp(dx0[0:6]), twist xi*_0 + dx0[6:12]
   if (dx0) {
@@ -2974,7 +3105,9 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
   for (int i = 0; i < N; i++) {
     if (i + 1 < N) Sb = roll_load_state(P, i + 1, vb, sB);
     __builtin_amdgcn_sched_barrier(0);
-    const State Nx = roll_step<M, false, true, PK, false>(P, C, DK, i, b, q, false, vb, sB, 0.0, Sa, Sn, un,
+    const PlantC Vi = plant_step<PL>(V);
+    const auto& CS = plant_or_model<PL, PK>(C, Vi);
+    const State Nx = roll_step<M, false, true, PK, false>(P, CS, DK, i, b, q, false, vb, sB, 0.0, Sa, Sn, un,
                                                            [&](RollIn<M>& R) { roll_load<M, true>(P, i, b, q, vb, sB, R); },
                                                            nullptr RST_ARG);
     J += knot_cost<M, true, PT>(P, C, i, b, Sn, un, false);
@@ -3008,12 +3141,13 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
 // trajectory b), b fastest.  End 0 steps the plant, x_{t+1} = f(x*_0, u*_0) with the exact dynamics (the dyn_f_k step of the
 // rollouts), adds the twist disturbance and the stage cost l(x*_0, u*_0), and writes xs_warm[0] = x_{t+1}; end 1 propagates
 // the tail, xs_warm[N] = f(x*_N, u*_{N-1}).  k_mpc_shift writes the rest.  Reads the held policy only: calling it again gives
-// the same bits.  No LDS, no cross-lane operation.
-template <int M, int PK, int PT>
+// the same bits.  No LDS, no cross-lane operation.  PL: end 0 steps plant row b (tolg_set_plant, S_plant = 1) instead of the
+// model; end 1, the tail of the warm start, is the model's prediction in every form.
+template <int M, int PK, int PT, int PL = PL_NONE, class... PA>
 __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __restrict__ w, double* __restrict__ x_next_q,
                                                      double* __restrict__ x_next_xi, double* __restrict__ u_applied,
                                                      double* __restrict__ xs_q, double* __restrict__ xs_xi,
-                                                     double* __restrict__ J_cl) {
+                                                     double* __restrict__ J_cl, PA... pl) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= 2 * (size_t)P.B) return;
   const int N = P.N, b = (int)(g % P.B), i = g < (size_t)P.B ? 0 : N;
@@ -3023,7 +3157,17 @@ __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __r
   double u[M];
 #pragma unroll
   for (int a = 0; a < M; a++) u[a] = P.cur_u[UIDX(a, i == 0 ? 0 : N - 1, b)];
-  State S = dyn_f_k<M, Consts, PK>(DK, C, Sx, u);
+  State S;
+  if constexpr (PL == PL_NONE) {
+    S = dyn_f_k<M, Consts, PK>(DK, C, Sx, u);
+  } else if (i == 0) {
+    const PlantArg pa = plant_arg_of(pl...);
+    const PlantC V = plant_c<PL>(C, pa, (size_t)b);
+    const auto& CS = plant_or_model<PL, PK>(C, V);
+    S = dyn_f_k<M, std::decay_t<decltype(CS)>, PK>(plant_dynk<PL>(C, pa, (size_t)b), CS, Sx, u);
+  } else {
+    S = dyn_f_k<M, Consts, PK>(DK, C, Sx, u);
+  }
   if (i == 0) {
     if (w) {
       const double* d = w + 6 * (size_t)b;
@@ -3042,6 +3186,53 @@ __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __r
   pose_to_m16(S.X, xs_q + 16 * k);
   double* x = xs_xi + 6 * k;
   x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z;
+}
+
+// d_J [B][S][36] (row-major 6x6 blkdiag(Ib, Jv)) and d_pend [B][S][2] (mass, length; the pendulum only, else null) into the
+// rows of form PL_DIAG or PL_DENSE (one thread per row; R = B S rows).  The constants are derived as tolg_create derives the
+// model's: Bt = Ib^-1 dt, mass = J[4][4], mass * grav, pend_k = mass * length / 2.  The diagonal form's inverses are the
+// correctly rounded 1.0 / d -- what host_inv6 gives a diagonal J -- so a plant equal to the model gives the model's bits; the
+// dense form inverts the two 3x3 blocks (cofactors over the determinant).
+TOLG_DEV void inv33(const double* A, double* Ai) {
+  const double c0 = A[4] * A[8] - A[5] * A[7], c1 = A[5] * A[6] - A[3] * A[8], c2 = A[3] * A[7] - A[4] * A[6];
+  const double id = 1.0 / (A[0] * c0 + A[1] * c1 + A[2] * c2);
+  Ai[0] = c0 * id; Ai[1] = (A[2] * A[7] - A[1] * A[8]) * id; Ai[2] = (A[1] * A[5] - A[2] * A[4]) * id;
+  Ai[3] = c1 * id; Ai[4] = (A[0] * A[8] - A[2] * A[6]) * id; Ai[5] = (A[2] * A[3] - A[0] * A[5]) * id;
+  Ai[6] = c2 * id; Ai[7] = (A[1] * A[6] - A[0] * A[7]) * id; Ai[8] = (A[0] * A[4] - A[1] * A[3]) * id;
+}
+__global__ void k_pack_plant(int R, int form, int kind, double dt, double grav, const double* __restrict__ J,
+                             const double* __restrict__ pend, double* __restrict__ out) {
+  const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= (size_t)R) return;
+  const double* Jr = J + 36 * r;
+  const size_t s = (size_t)R;
+  double* o = out + r;
+  const double pk = kind == TOLG_DYN_PENDULUM3D ? pend[2 * r] * pend[2 * r + 1] / 2 : 0.0;
+  const double mass = Jr[6 * 4 + 4];
+  if (form == TOLG_PLANT_DIAG) {
+    for (int a = 0; a < 3; a++) {
+      const double ib = Jr[7 * a], jv = Jr[7 * (a + 3)];
+      const double ibi = 1.0 / ib;
+      o[(PLD_IB + a) * s] = ib;
+      o[(PLD_JV + a) * s] = jv;
+      o[(PLD_BT + a) * s] = ibi * dt;
+      o[(PLD_JVI + a) * s] = 1.0 / jv;
+    }
+    o[PLD_MG * s] = mass * grav;
+    o[PLD_PK * s] = pk;
+  } else {
+    double Ib[9], Jv[9], Ibi[9], Jvi[9];
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) { Ib[3 * i + j] = Jr[6 * i + j]; Jv[3 * i + j] = Jr[6 * (i + 3) + j + 3]; }
+    inv33(Ib, Ibi);
+    inv33(Jv, Jvi);
+    for (int k = 0; k < 9; k++) {
+      o[(PLN_IB + k) * s] = Ib[k]; o[(PLN_JV + k) * s] = Jv[k];
+      o[(PLN_IBI + k) * s] = Ibi[k]; o[(PLN_JVI + k) * s] = Jvi[k];
+    }
+    o[PLN_MASS * s] = mass;
+    o[PLN_PK * s] = pk;
+  }
 }
 
 // ---- line-search stages, round 3 form -----------------------------------------------------------------------------
@@ -3948,6 +4139,9 @@ struct KernelTable {
   void (*affine_commit)(Params, int, int);
   void (*policy_rollout)(Params, int, int, const double*, const double*, double*, int*, double*, double*, double*);  // tolg_policy_rollout
   void (*mpc_advance)(Params, const double*, double*, double*, double*, double*, double*, double*);  // tolg_mpc_advance (+ k_mpc_shift)
+  // ... the same two with a plant (tolg_set_plant), [TOLG_PLANT_DIAG / TOLG_PLANT_DENSE]
+  void (*policy_rollout_plant[2])(Params, int, int, const double*, const double*, double*, int*, double*, double*, double*, PlantArg);
+  void (*mpc_advance_plant[2])(Params, const double*, double*, double*, double*, double*, double*, double*, PlantArg);
   struct Search {                    // per search kind: ls[0] backtracking (single shooting), ls[1] merit (multiple shooting)
     struct { SearchRollout k; int nt; } wave2[2];  // k_rollout_ls2 [first try] and its NT (twist waves per pose wave)
     SearchRollout wave1[2];          // the one-wave forms k_rollout_ls [linear]
@@ -4011,6 +4205,10 @@ static KernelTable kernel_table(int lds_per_block) {
   // (the held policy's rollouts report the tracking cost: the PT_OBS tables share the kernels of the table without it)
   t.policy_rollout = k_policy_rollout<M, PK, PT & ~PT_OBS>;
   t.mpc_advance = k_mpc_advance<M, PK, PT & ~PT_OBS>;
+  t.policy_rollout_plant[TOLG_PLANT_DIAG] = k_policy_rollout<M, PK, PT & ~PT_OBS, PL_DIAG, PlantArg>;
+  t.policy_rollout_plant[TOLG_PLANT_DENSE] = k_policy_rollout<M, PK, PT & ~PT_OBS, PL_DENSE, PlantArg>;
+  t.mpc_advance_plant[TOLG_PLANT_DIAG] = k_mpc_advance<M, PK, PT & ~PT_OBS, PL_DIAG, PlantArg>;
+  t.mpc_advance_plant[TOLG_PLANT_DENSE] = k_mpc_advance<M, PK, PT & ~PT_OBS, PL_DENSE, PlantArg>;
   t.ls[0] = search_kernels<M, false, PK, PT>();
   t.ls[1] = search_kernels<M, true, PK, PT>();
   return t;
@@ -4100,6 +4298,8 @@ struct tolg_handle_s {
   const double* obs = nullptr;   // tolg_set_al_obstacles: the packed sphere geometry (caller-owned), or null
   int obs_B = 0, obs_K = 0;      // ... their batch, as refs_B, and the spheres per trajectory
   double *obs_lam = nullptr, *obs_imu = nullptr;  // ... their multipliers [B][N+1][K] (caller-owned; tolg_al_update_state writes them)
+  const double* plant = nullptr;  // tolg_set_plant: the packed plant rows (caller-owned), or null: the closed loops step the model
+  int plant_B = 0, plant_S = 0, plant_form = 0;  // ... their batch, samples per trajectory and TOLG_PLANT_* form
   // The held policy (tolg_solve_gains, tolg_policy_rollout): nominal trajectory P.cur / P.cur_u and gains P.GK of a batch of
   // pol_B trajectories, 0 = none.  Set by tolg_solve_end and tolg_linearize_backward; cleared by tolg_solve_begin(_warm) and
   // tolg_eval_knot (k_probe_pack writes P.cur); tolg_rollout (writes the candidate arrays) and tolg_expected_change (ED, ecc)
@@ -5161,6 +5361,9 @@ extern "C" int tolg_rollout(tolg_handle_t h, int32_t ms, int32_t rollout_linear,
 static bool policy_ok(const tolg_handle_s* h, int B) {
   return h && !h->running && h->pol_B != 0 && B == h->pol_B && batch_fits(h, B);
 }
+// Plants (tolg_set_plant): rows of PLN_F doubles at most (the dense form's), field-major over the B S rows
+static size_t plant_bytes_for(int B, int S) { return (size_t)PLN_F * (size_t)B * (size_t)S * sizeof(double); }
+static PlantArg plant_arg(const tolg_handle_s* h) { return PlantArg{h->plant, h->plant_B * h->plant_S, h->plant_S}; }
 extern "C" int tolg_solve_gains(tolg_handle_t h, int32_t B, double* d_k, double* d_K, void* stream) {
   if (!policy_ok(h, B)) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -5177,11 +5380,16 @@ extern "C" int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const 
   if (!policy_ok(h, B) || S < 1) return TOLG_E_ARG;
   const size_t lanes = (size_t)B * (size_t)S * 4;
   if (lanes > 0x7fffffc0ull) return TOLG_E_ARG;  // one launch, 64-lane groups
+  if (h->plant && (B != h->plant_B || (h->plant_S != 1 && h->plant_S != S))) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // J is the tracking cost: no augmented-Lagrangian terms
-  hipLaunchKernelGGL(h->kt.policy_rollout, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P, (int)S,
-                     h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us);
+  if (h->plant)
+    hipLaunchKernelGGL(h->kt.policy_rollout_plant[h->plant_form], dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P,
+                       (int)S, h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, plant_arg(h));
+  else
+    hipLaunchKernelGGL(h->kt.policy_rollout, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P, (int)S,
+                       h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us);
   LAUNCH_CHECK();
   return 0;
 }
@@ -5190,15 +5398,44 @@ extern "C" int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, d
                                 double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm,
                                 double* d_J_cl, void* stream) {
   if (!policy_ok(h, B) || !d_xs_q_warm || !d_xs_xi_warm || !d_us_warm) return TOLG_E_ARG;
+  if (h->plant && (B != h->plant_B || h->plant_S != 1)) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // the stage cost is the tracking cost: no augmented-Lagrangian terms
   hipLaunchKernelGGL(k_mpc_shift, knot_grid(P.N, P.Bp), dim3(256), 0, st, P, P.cur, P.cur_u, d_xs_q_warm,
                      d_xs_xi_warm, d_us_warm);
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(h->kt.mpc_advance, dim3((unsigned)((2 * (size_t)B + 255) / 256)), dim3(256), 0, st, P, d_w, d_x_next_q,
-                     d_x_next_xi, d_u_applied, d_xs_q_warm, d_xs_xi_warm, d_J_cl);
+  const dim3 grid((unsigned)((2 * (size_t)B + 255) / 256));
+  if (h->plant)
+    hipLaunchKernelGGL(h->kt.mpc_advance_plant[h->plant_form], grid, dim3(256), 0, st, P, d_w, d_x_next_q, d_x_next_xi,
+                       d_u_applied, d_xs_q_warm, d_xs_xi_warm, d_J_cl, plant_arg(h));
+  else
+    hipLaunchKernelGGL(h->kt.mpc_advance, grid, dim3(256), 0, st, P, d_w, d_x_next_q, d_x_next_xi, d_u_applied, d_xs_q_warm,
+                       d_xs_xi_warm, d_J_cl);
   LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t tolg_plant_bytes(const tolg_problem* prob, int32_t max_batch, int32_t S) {
+  if (check_problem(prob) || max_batch < 1 || S < 1) return 0;
+  return plant_bytes_for(max_batch, S);
+}
+extern "C" int tolg_set_plant(tolg_handle_t h, int32_t B, int32_t S, int32_t form, const double* d_J, const double* d_pend,
+                              double* d_packed, size_t packed_bytes, void* stream) {
+  if (!h || h->running) return TOLG_E_ARG;
+  if (!d_J) {  // back to the model
+    h->plant = nullptr; h->plant_B = h->plant_S = h->plant_form = 0;
+    return 0;
+  }
+  if (B < 1 || B > h->max_batch || S < 1 || (form != TOLG_PLANT_DIAG && form != TOLG_PLANT_DENSE)) return TOLG_E_ARG;
+  if ((size_t)B * (size_t)S * 4 > 0x7fffffc0ull) return TOLG_E_ARG;  // rows are indexed in int, as the rollout's samples
+  if (!d_packed || (reinterpret_cast<uintptr_t>(d_packed) & 7) != 0 || packed_bytes < plant_bytes_for(B, S)) return TOLG_E_ARG;
+  if ((h->prob.kind == TOLG_DYN_PENDULUM3D) != (d_pend != nullptr)) return TOLG_E_ARG;
+  const int R = B * S;
+  hipLaunchKernelGGL(k_pack_plant, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), R, (int)form,
+                     h->prob.kind, h->hc.dt, h->hc.grav, d_J, d_pend, d_packed);
+  LAUNCH_CHECK();
+  h->plant = d_packed; h->plant_B = B; h->plant_S = S; h->plant_form = form;
   return 0;
 }
 

@@ -178,6 +178,7 @@ class BatchedTrackingILQR:
         self._al = None            # the augmented-Lagrangian terms the handle points at (set_al)
         self._obs = None           # ... and the keep-out spheres (set_al_obstacles): (obstacles, lam, imu) on the device
         self._obs_buf = None       # the packed sphere geometry the handle reads (caller-owned, for max_batch x MAX_OBSTACLES)
+        self._plant_buf = None     # the packed plant rows of the last call that stated one (tolg_set_plant; detached behind it)
         p = _capi.Problem()
         p.kind, p.m, p.N, p.dt = _KIND[problem.kind], self.m, self.N, float(problem.dt)
         p.pend_mass, p.pend_length = float(problem.pend_mass), float(problem.pend_length)
@@ -685,12 +686,84 @@ class BatchedTrackingILQR:
         self._call("tolg_solve_gains", B, _ptr(k), _ptr(K))
         return {"k": k, "K": K}
 
-    def policy_rollout(self, dx0=None, noise=None, S=None, trajectories=False) -> PolicyRollout:
+    def _check_plant(self, B, plant_J, plant_pend, per_sample):
+        """A plant (tolg_set_plant) checked on the host: ValueError before anything reaches the device.  plant_J [B, 6, 6], or
+        with per_sample [B, S, 6, 6] too ([..., 3, 3] for so3 and the pendulum: the inertia J_so3, embedded as the model's
+        blkdiag(J_so3, I3)); plant_pend [..., 2] = (mass, length), required for the pendulum and refused otherwise.  Each block
+        must be finite, symmetric and positive definite, the off-diagonal blocks of a 6x6 zero, the pendulum's parameters
+        positive.  Returns None when plant_J is None, else (J [B, S_plant, 36], pend [B, S_plant, 2] or None, form, S_plant)
+        with form TOLG_PLANT_DIAG when every off-diagonal entry is zero, TOLG_PLANT_DENSE otherwise."""
+        pend_kind = self.problem.kind == "pendulum3d"
+        if plant_J is None:
+            if plant_pend is not None:
+                raise ValueError("plant_pend needs plant_J")
+            return None
+        n = 3 if self.problem.kind in ("so3", "pendulum3d") else 6
+        a = plant_J.detach().cpu().numpy() if isinstance(plant_J, torch.Tensor) else np.asarray(plant_J)
+        shape = (B, None, n, n) if per_sample and a.ndim == 4 else (B, n, n)
+        a = _checked("plant_J", a, shape, finite=True)
+        a = a.reshape(B, -1, n, n)
+        Sp = a.shape[1]
+        if Sp < 1:
+            raise ValueError("plant_J has no samples")
+        if n == 3:
+            J = np.zeros((B, Sp, 6, 6))
+            J[:, :, :3, :3] = a
+            J[:, :, 3:, 3:] = np.eye(3)
+        else:
+            J = a
+            if np.any(J[:, :, :3, 3:] != 0.0) or np.any(J[:, :, 3:, :3] != 0.0):
+                raise ValueError("plant_J must be blkdiag(Ib, Jv): a non-zero off-diagonal block")
+        for blk in (J[:, :, :3, :3], J[:, :, 3:, 3:]):
+            if np.any(np.abs(blk - np.swapaxes(blk, -1, -2)) > 1e-12 * np.abs(blk).max(axis=(-1, -2), keepdims=True)):
+                raise ValueError("plant_J: the inertia blocks must be symmetric")
+            try:
+                np.linalg.cholesky(blk)
+            except np.linalg.LinAlgError:
+                raise ValueError("plant_J: the inertia blocks must be positive definite") from None
+        pend = None
+        if pend_kind:
+            if plant_pend is None:
+                raise ValueError("the pendulum's plant needs plant_pend = (mass, length)")
+            pend = _checked("plant_pend", plant_pend, (B, Sp, 2) if len(shape) == 4 else (B, 2), finite=True).reshape(B, Sp, 2)
+            if np.any(pend <= 0.0):
+                raise ValueError("plant_pend: mass and length must be positive")
+            pend = np.ascontiguousarray(pend)
+        elif plant_pend is not None:
+            raise ValueError("plant_pend is for the pendulum only")
+        off = J - np.diagonal(J, axis1=-2, axis2=-1)[..., None] * np.eye(6)
+        form = _capi.PLANT_DIAG if not np.any(off != 0.0) else _capi.PLANT_DENSE
+        return np.ascontiguousarray(J.reshape(B, Sp, 36)), pend, form, Sp
+
+    def _set_plant(self, B, plant):
+        """Point the handle at the checked plant (tolg_set_plant; packed into a buffer of its own, kept until the next one)."""
+        J, pend, form, Sp = plant
+        d_J, d_pend = self._dev(J, J.shape), None if pend is None else self._dev(pend, pend.shape)
+        self._plant_buf = torch.empty(int(self.lib.tolg_plant_bytes(C.byref(self._p), B, Sp)) // 8, dtype=torch.float64,
+                                      device=self.device)
+        self._call("tolg_set_plant", B, Sp, form, _ptr(d_J), _ptr(d_pend), _ptr(self._plant_buf),
+                   C.c_size_t(self._plant_buf.numel() * 8))
+        return d_J, d_pend
+
+    def _clear_plant(self):
+        self._call("tolg_set_plant", 0, 0, 0, None, None, None, 0, None, stream=False)
+
+    def _use_plant(self, B, plant):
+        """Point the handle at this call's plant, or detach it (plant None: the model steps): every call states its own.
+        Returns the device inputs the stream may not have read yet."""
+        if plant is None:
+            self._clear_plant()
+            return None
+        return self._set_plant(B, plant)
+
+    def policy_rollout(self, dx0=None, noise=None, S=None, trajectories=False, plant_J=None, plant_pend=None) -> PolicyRollout:
         """S closed-loop rollouts per trajectory of the held policy u = u*_i + K_i (x (-) x*_i) with exact dynamics
         (tolg_policy_rollout).  dx0 [B, S, 12]: start perturbation in the error coordinates of K (pose x*_0 Exp(dx0[:6]),
         twist xi*_0 + dx0[6:]); noise [B, S, N, 6]: added to the twist behind every step.  Either may be None (zero); S is
         taken from them, or given when both are None.  J [B, S] is the tracking cost with the references and weights of the
-        held solve (no augmented-Lagrangian terms).  trajectories=True also returns xs_q, xs_xi, us."""
+        held solve (no augmented-Lagrangian terms).  trajectories=True also returns xs_q, xs_xi, us.
+        plant_J / plant_pend: the plant the samples are stepped with (model mismatch, tolg_set_plant; None: the model), one per
+        sample [B, S, 6, 6] or one per trajectory [B, 6, 6] (see _check_plant).  The cost stays the model's."""
         B = self._held_B()
         shapes = []
         if dx0 is not None:
@@ -708,6 +781,9 @@ class BatchedTrackingILQR:
         S = shapes[0]
         if S < 1:
             raise ValueError("S must be at least 1")
+        plant = self._check_plant(B, plant_J, plant_pend, per_sample=True)
+        if plant is not None and plant[3] not in (1, S):
+            raise ValueError("plant_J has %d samples per trajectory, the rollout %d" % (plant[3], S))
         f64 = dict(dtype=torch.float64, device=self.device)
         d_dx0 = None if dx0 is None else self._dev(dx0, (B, S, 12))
         d_w = None if noise is None else self._dev(noise, (B, S, self.N, 6))
@@ -716,9 +792,14 @@ class BatchedTrackingILQR:
             r.xs_q = torch.empty(B, S, self.N + 1, 4, 4, **f64)
             r.xs_xi = torch.empty(B, S, self.N + 1, 6, **f64)
             r.us = torch.empty(B, S, self.N, self.m, **f64)
-        self._hold((d_dx0, d_w))
-        self._call("tolg_policy_rollout", B, S, _ptr(d_dx0), _ptr(d_w), _ptr(r.J), _ptr(r.status), _ptr(r.xs_q), _ptr(r.xs_xi),
-                   _ptr(r.us))
+        d_plant = self._use_plant(B, plant)
+        try:
+            self._hold((d_dx0, d_w, d_plant))
+            self._call("tolg_policy_rollout", B, S, _ptr(d_dx0), _ptr(d_w), _ptr(r.J), _ptr(r.status), _ptr(r.xs_q),
+                       _ptr(r.xs_xi), _ptr(r.us))
+        finally:
+            if plant is not None:
+                self._clear_plant()
         return r
 
     # ------------------------------------------------------------------------------------------
@@ -761,20 +842,28 @@ class BatchedTrackingILQR:
         self._hold((q, xi, t0_d))
         self._set_ref_windows(B, q, xi, T, t0_d, int(t))
 
-    def mpc_advance(self, w=None, J_cl=None):
+    def mpc_advance(self, w=None, J_cl=None, plant_J=None, plant_pend=None):
         """One receding-horizon step on the held policy (tolg_mpc_advance): x_next = f(x*_0, u*_0) + [0; w] with the exact
         dynamics, u = u*_0, and the warm start of the next step (xs_q / xs_xi [B, N+1, ...], us [B, N, m]: the solution
         shifted by one knot, x_next in front, the tail propagated with the last input).  w [B, 6] (None: 0) is added to the
         twist.  J_cl (a float64 device tensor [B], optional) is accumulated with the stage cost l(x*_0, u*_0) at knot 0.
+        plant_J [B, 6, 6] / plant_pend [B, 2]: the plant x_next is stepped with (model mismatch, tolg_set_plant; None: the
+        model); the warm tail stays the model's prediction, u and J_cl are unchanged.
         Returns a dict of device tensors: x_next_q [B, 4, 4], x_next_xi, u [B, m], xs_q, xs_xi, us, J_cl."""
         B = self._held_B()
         d_w = None if w is None else self._dev(_checked("w", w, (B, 6), finite=True), (B, 6))
         if J_cl is not None and (not isinstance(J_cl, torch.Tensor) or J_cl.dtype != torch.float64 or
                                  tuple(J_cl.shape) != (B,) or J_cl.device != self.device or not J_cl.is_contiguous()):
             raise ValueError("J_cl must be a contiguous float64 tensor of shape (%d,) on %s" % (B, self.device))
+        plant = self._check_plant(B, plant_J, plant_pend, per_sample=False)
         r = self._advance_out(B, J_cl)
-        self._hold(d_w)
-        self._advance(B, d_w, r)
+        d_plant = self._use_plant(B, plant)
+        try:
+            self._hold((d_w, d_plant))
+            self._advance(B, d_w, r)
+        finally:
+            if plant is not None:
+                self._clear_plant()
         return r
 
     def _advance_out(self, B, J_cl):
@@ -789,7 +878,7 @@ class BatchedTrackingILQR:
 
     def mpc(self, x0_q, x0_xi, path_q, path_xi, steps, us_init=None, t0=None, iters_per_step=5, first_iters=50,
             warm="states", noise=None, mode="ms", line_search=False, rollout="nonlinear", tol_grad_norm=1e-6, tol_d_norm=1e-6,
-            check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None) -> MPCResult:
+            check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None, plant_J=None, plant_pend=None) -> MPCResult:
         """Receding-horizon MPC: `steps` closed-loop steps of B trajectories, each tracking its own path from its own phase.
         Step t: windows min(t0[b] + t + i, T) of the paths (tolg_set_ref_windows), a solve of first_iters (t = 0) or
         iters_per_step iterations, then tolg_mpc_advance applies u*_0, steps the plant with the exact dynamics and adds the
@@ -799,8 +888,9 @@ class BatchedTrackingILQR:
         The first solve starts from us_init (None: 0) and the reference window.  check_every = 0 issues a fixed count of
         iterations with no host read in the whole loop; > 0 stops a step's solve early (solve_iterate_until).  Q / P / R:
         weights per trajectory as for fit_batch.  on_step(t, FitResult) is called behind every step's solve (before the
-        plant step; the FitResult carries histories then).  Not with an augmented-Lagrangian constraint attached.  The handle is
-        left on the shared reference and weights.
+        plant step; the FitResult carries histories then).  plant_J [B, 6, 6] / plant_pend [B, 2]: the plant every step's
+        x_next is stepped with (model mismatch, as mpc_advance; None: the model); the solves plan on the model.  Not with an
+        augmented-Lagrangian constraint attached.  The handle is left on the shared reference and weights, without a plant.
         x0_q [B, 4, 4], x0_xi [B, 6], path_q [B, T+1, 4, 4], path_xi [B, T+1, 6]."""
         if self._al is not None:
             raise ValueError("mpc under an augmented-Lagrangian constraint is not supported: detach it with set_al(None)")
@@ -826,6 +916,7 @@ class BatchedTrackingILQR:
         pq, pxi, T = self._paths(B, path_q, path_xi)
         t0_d = self._check_t0(B, t0)
         b = self._stage(x0_q, x0_xi, us_init, weights=(Q, P, R))
+        plant = self._check_plant(B, plant_J, plant_pend, per_sample=False)
         if noise is not None:
             noise = _checked("noise", noise, (B, steps, 6), finite=True)
             noise = self._dev(np.ascontiguousarray(noise.transpose(1, 0, 2)), (steps, B, 6))  # step t: one contiguous [B, 6]
@@ -838,9 +929,11 @@ class BatchedTrackingILQR:
         res.xs_xi[:, 0] = b.x_xi
         # the plant state and the warm start: written by tolg_mpc_advance, read by the next begin (stream-ordered)
         adv = self._advance_out(B, res.J)
-        self._hold((b, pq, pxi, t0_d, noise, adv))
         x_q, x_xi, us = b.x_q, b.x_xi, b.us
         try:
+            # the plant survives the solves of the loop (tolg_set_plant): set once, detached behind it
+            d_plant = self._use_plant(B, plant)
+            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant))
             self._use_pt(B, None, b.wts)
             for t in range(steps):
                 self._set_ref_windows(B, pq, pxi, T, t0_d, t)
@@ -869,6 +962,8 @@ class BatchedTrackingILQR:
                 res.xs_xi[:, t + 1] = adv["x_next_xi"]
         finally:
             self._use_pt(B, None, None)
+            if plant is not None:
+                self._clear_plant()
         return res
 
     # ------------------------------------------------------------------------------------------

@@ -244,6 +244,44 @@ def se3_policy_eval(B, S, N=200, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=
     return prob, x0_q, x0_xi, us0, dx0, noise
 
 
+def plant_mismatch(B, S, kind="se3", N=None, sigma_inertia=0.1, sigma_mass=0.1, rotate=False, seed=SEED):
+    """Model-mismatch inputs for the closed loop (BatchedTrackingILQR.policy_rollout with plant_J): se3_policy_eval's
+    perturbations on se3_tracking's (kind="se3", N default 200) or drone_tracking's (kind="drone", N default 400) workload,
+    plus a seeded plant per sample.  Returns (prob, x0_q, x0_xi, us0, dx0 [B, S, 12], noise [B, S, N, 6], plant_J
+    [B, S, 6, 6]).  Plant (b, s) is blkdiag(Ib, m I3) with the model's principal moments and mass each scaled by exp(N(0,
+    sigma_inertia^2)) resp. exp(N(0, sigma_mass^2)); rotate=True turns Ib into R diag R^T with a uniformly random rotation R
+    (dense blocks), else Ib stays diagonal."""
+    if kind not in ("se3", "drone"):
+        raise ValueError("kind must be 'se3' or 'drone'")
+    if kind == "se3":
+        prob, x0_q, x0_xi, us0 = se3_tracking(B, N=200 if N is None else N, seed=seed)
+    else:
+        prob, x0_q, x0_xi, us0 = drone_tracking(B, N=400 if N is None else N, seed=seed)
+    n = prob.N
+    rng = np.random.default_rng(seed + 5)
+    dx0 = np.concatenate([rng.normal(0.0, 0.05, (B, S, 6)), rng.normal(0.0, 0.05, (B, S, 6))], axis=2)
+    noise = rng.normal(0.0, 0.01, (B, S, n, 6))
+    J0 = np.asarray(prob.J, dtype=np.float64)
+    moments = np.diag(J0)[:3] * np.exp(rng.normal(0.0, sigma_inertia, (B, S, 3)))
+    mass = J0[4, 4] * np.exp(rng.normal(0.0, sigma_mass, (B, S)))
+    plant_J = np.zeros((B, S, 6, 6))
+    for b in range(B):
+        for s in range(S):
+            Ib = np.diag(moments[b, s])
+            if rotate:
+                q = rng.normal(size=4)
+                q /= np.linalg.norm(q)
+                w, x, y, z = q
+                R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                              [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                              [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+                Ib = R @ Ib @ R.T
+                Ib = 0.5 * (Ib + Ib.T)
+            plant_J[b, s, :3, :3] = Ib
+            plant_J[b, s, 3:, 3:] = mass[b, s] * np.eye(3)
+    return prob, x0_q, x0_xi, us0, dx0, noise, plant_J
+
+
 def se3_mpc(B, steps, N=200, T=None, R=4, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=0.01, seed=SEED):
     """Receding-horizon inputs (BatchedTrackingILQR.mpc) on se3_tracking's model: B trajectories, each following its own
     path of T+1 knots (default T = N + steps) -- se3_tracking's path continued to T knots (_extend_reference) and moved by
