@@ -308,8 +308,8 @@ int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, double* d_ecc
  *     final iterate).
  * tolg_create, tolg_solve_begin and tolg_solve_begin_warm clear it; so does tolg_eval_knot (it overwrites the nominal
  * trajectory).  tolg_rollout (writes the candidate arrays only), tolg_expected_change, tolg_set_al, tolg_al_update,
- * tolg_set_refs, tolg_set_ref_windows, tolg_set_weights, tolg_set_al_obstacles, tolg_al_update_state and tolg_mpc_advance
- * leave it; the calls that read it use the
+ * tolg_set_refs, tolg_set_ref_windows, tolg_set_weights, tolg_set_al_obstacles, tolg_al_update_state, tolg_mpc_advance and
+ * tolg_policy_covariance leave it; the calls that read it use the
  * references and weights set when they run.
  * Both calls return TOLG_E_ARG when no policy is held, during a solve in flight, for a B other than the held batch's, when
  * references or weights per trajectory are set for another B, and (tolg_policy_rollout) for S < 1.  Neither modifies
@@ -348,6 +348,33 @@ int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const double* d_d
 int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, double* d_x_next_q, double* d_x_next_xi,
                      double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl,
                      void* stream);
+
+/* tolg_policy_covariance: the closed-loop covariance of the held policy to first order ("LinCov"), the analytic companion of
+ * tolg_policy_rollout's sampling.  In the coordinates of tolg_policy_rollout and of K, e_i = [Log(q*_i^-1 q^_i); xi^_i - xi*_i]
+ * (twist order [omega, v]), about the held nominal x*_i, u*_i:
+ *   A_i = f_x(x*_i, u*_i), B_i = f_u(x*_i, u*_i)   the model's Jacobians, as tolg_eval_knot returns them, linearised by this
+ *                                                  call at the held nominal states (the workspace's knot records are not
+ *                                                  trusted: after a solve stopped by max_iter they belong to another iterate
+ *                                                  than the gains, see above);
+ *   Acl_i = A_i + B_i K_i
+ *   Sigma_{i+1} = Acl_i Sigma_i Acl_i^T + E W E^T,  E = [0; I6],  i = 0 .. N-1
+ * with Sigma_0 the covariance of the start error dx0 (12 x 12, PSD) and W the covariance of the twist disturbance w added after
+ * every step (6 x 6, PSD).  This is a covariance, not a mean: multiple-shooting defects of the nominal are ignored.  The loop is
+ * the linear, unsaturated one of the model: a plant (tolg_set_plant), an input box (tolg_set_al) and keep-out spheres
+ * (tolg_set_al_obstacles) are ignored -- the same bits with and without them.
+ *   in : d_Sigma0 [B][12][12] or NULL (= 0), d_W [B][6][6] or NULL (= 0); only the upper triangles are read
+ *   out: d_Sigma [B][N+1][12][12]   computed as a symmetric matrix and mirrored: equal to its transpose to the bit
+ *        d_var_x [B][N+1][12]       diag Sigma_i (the bits of d_Sigma's diagonal)
+ *        d_var_u [B][N][m]          diag K_i Sigma_i K_i^T: the input variance the feedback spends
+ *        d_pos_cov [B][N+1][6]      R*_i Sigma_i[3:6,3:6] R*_i^T, the position covariance in the world frame: xx xy xz yy yz zz
+ * Every output may be NULL, and a NULL output costs nothing (d_Sigma is 0.95 GB at 4096 x 200).  Sigma0 = W = 0 gives exact zeros;
+ * a trajectory's bits depend on neither B nor its neighbours, nor on which outputs are asked for.  For the SO3 family the state is
+ * carried in the SE(3) layout as everywhere in this header: rows / columns 3..5 and 9..11 are the unused translation and linear
+ * velocity (inputs 3..5 are zero and K's rows for them with it; pass zeros there, as tolg_policy_rollout's dx0 and w do).
+ * The call does not modify the held policy.  TOLG_E_ARG: the conditions of tolg_solve_gains; a non-NULL d_pos_cov for a kind of
+ * the SO3 family (no translation: the rule of tolg_set_al_obstacles). */
+int tolg_policy_covariance(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, double* d_Sigma, double* d_var_x,
+                           double* d_var_u, double* d_pos_cov, void* stream);
 
 /* Plants: per-sample dynamics parameters that step the closed loops of tolg_policy_rollout and tolg_mpc_advance in place of
  * the model's (model mismatch: a payload change, a mis-identified inertia, domain randomisation).  The planner's model stays

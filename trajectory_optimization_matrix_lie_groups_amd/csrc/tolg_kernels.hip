@@ -3188,6 +3188,223 @@ __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __r
   x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z;
 }
 
+// Closed-loop covariance of the held policy (tolg_policy_covariance): Sigma_{i+1} = Acl_i Sigma_i Acl_i^T + E W E^T with
+// Acl_i = f_x + f_u K_i linearised HERE at the held nominal (x*_i, u*_i) -- not read from the knot records, which after a solve
+// stopped by max_iter belong to another iterate than the gains.  One 16-lane row per trajectory as in K2 (four trajectories
+// per wavefront, one wavefront per block): lane j < 12 holds column j (= row j) of the symmetric Sigma_i in registers, lanes
+// 12..15 replay lane 11 and store nothing.  Every lane builds the blocks of f_x redundantly (the scalar chain of lin_knot's
+// dynamics part, closed-form coefficients: no wave-wide series gate, so a trajectory's bits depend on nothing but itself) and
+// lane 0 puts them into the row's LDS; the gains arrive through roll_load (lane q < M / 2 holds rows 2q, 2q + 1) and go to LDS
+// too; lane j then folds f_u K into column j of the dense lower half.  A knot is two applications of y = Acl x per lane with
+// one transpose through LDS between them:  T[:, j] = Acl Sigma[:, j];  Sigma'[j, :] = Acl T[j, :]^T.  Entry {r, c} of the next
+// Sigma is the one lane min(r, c) computed: every lane reads its column back from the upper triangle, so the matrix is
+// symmetric to the bit, and W (upper triangle read) is added by that lane alone.  f_x keeps its block form (rows 0..5: RI,
+// TRI, JR, QR; rows 6..11 dense with f_u K): 126 multiply-adds per application instead of 144.
+// LDS per trajectory (doubles): Sigma, T, the four pose blocks, the lower half of Acl, K, the partial sums of K Sigma K^T.
+enum { PC_SG = 0, PC_TT = 144, PC_TOP = 288, PC_BOT = 324, PC_K = 396, PC_PU = 468, PC_F = 540 };
+// y = Acl x from the row's LDS (a fixed summation order: the bits of a lane depend on its operands alone)
+TOLG_DEV void pc_apply(const double* L, const double (&x)[12], double (&y)[12]) {
+  const double *RI = L + PC_TOP, *TRI = RI + 9, *JR = RI + 18, *QR = RI + 27, *BOT = L + PC_BOT;  // 3x3 row-major; 6 x 12 row-major
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    double t = 0.0, m = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      t += RI[3 * r + c] * x[c] + JR[3 * r + c] * x[6 + c];
+      m += TRI[3 * r + c] * x[c] + RI[3 * r + c] * x[3 + c] + QR[3 * r + c] * x[6 + c] + JR[3 * r + c] * x[9 + c];
+    }
+    y[r] = t;
+    y[3 + r] = m;
+  }
+#pragma unroll
+  for (int r = 0; r < 6; r++) {
+    double t = 0.0;
+#pragma unroll
+    for (int c = 0; c < 12; c++) t += BOT[12 * r + c] * x[c];
+    y[6 + r] = t;
+  }
+}
+// the outputs of knot i from the row's Sigma in LDS (upper triangle); S: the nominal state of the knot (pos_cov's rotation)
+TOLG_DEV void pc_outputs(const double* L, bool live, int l, size_t bk, const State& S, double* __restrict__ Sig,
+                         double* __restrict__ var_x, double* __restrict__ pos_cov) {
+  if (!live) return;
+  const double* SG = L + PC_SG;
+  if (Sig) {  // 144 entries over 16 lanes, mirrored
+    double* o = Sig + bk * 144;
+#pragma unroll
+    for (int t = 0; t < 9; t++) {
+      const int e = l + 16 * t, r = e / 12, c = e - 12 * r;
+      o[e] = SG[r <= c ? 12 * r + c : 12 * c + r];
+    }
+  }
+  if (var_x && l < 12) var_x[bk * 12 + l] = SG[13 * l];
+  if (pos_cov && l == 0) {  // R Sigma[3:6, 3:6] R^T, upper triangle row by row
+    double R[9], Sp[9], Mx[9];
+    q_to_R(S.X.q, R);
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) Sp[3 * a + c] = a <= c ? SG[12 * (3 + a) + 3 + c] : SG[12 * (3 + c) + 3 + a];
+    mul33(R, Sp, Mx);
+    double* o = pos_cov + bk * 6;
+#pragma unroll
+    for (int a = 0, n = 0; a < 3; a++)
+#pragma unroll
+      for (int c = a; c < 3; c++, n++) o[n] = Mx[3 * a] * R[3 * c] + Mx[3 * a + 1] * R[3 * c + 1] + Mx[3 * a + 2] * R[3 * c + 2];
+  }
+}
+template <int M, int PK>
+__global__ __launch_bounds__(64) void k_policy_covariance(Params P, const double* __restrict__ Sigma0, const double* __restrict__ Wn,
+                                                          double* __restrict__ Sig, double* __restrict__ var_x,
+                                                          double* __restrict__ var_u, double* __restrict__ pos_cov) {
+  __shared__ double lds[4 * PC_F];
+  const Consts& C = *P.c;
+  const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+  int b = blockIdx.x * 4 + g;
+  // rows past the last trajectory replay it (the block's barriers need every lane) and store nothing
+  const bool live = b < P.B;
+  if (!live) b = P.B - 1;
+  const int j = l < 12 ? l : 11;
+  const bool col = l < 12;
+  double* L = lds + g * PC_F;
+  const int N = P.N;
+  const unsigned sB = (unsigned)P.Bp * 8u, vb = (unsigned)b * 8u;
+  const double dt = C.dt;
+  double s[12], wc[6];  // column j of Sigma_i; column j - 6 of W (zero in the lanes of the pose columns)
+#pragma unroll
+  for (int i = 0; i < 12; i++) s[i] = Sigma0 ? Sigma0[(size_t)b * 144 + (i <= j ? 12 * i + j : 12 * j + i)] : 0.0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const int jw = j >= 6 ? j - 6 : 0;
+    wc[i] = (Wn && j >= 6) ? Wn[(size_t)b * 36 + (i <= jw ? 6 * i + jw : 6 * jw + i)] : 0.0;
+  }
+  if (col) {
+#pragma unroll
+    for (int i = 0; i < 12; i++) L[PC_SG + 12 * j + i] = s[i];
+  }
+  // F_u's constant blocks (rows 6..8: columns 0..2, rows 9..11: columns 3..M-1), read once; the pendulum's upper block is the
+  // knot's (J^-1 skew(m rho) R^T dt, as lin_knot builds REC_BU)
+  double Bt[9], Bb[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) { Bt[k] = C.Bt[k]; Bb[k] = C.Bb[k]; }
+  State Sa = roll_load_state(P, 0, vb, sB), Sb = Sa;
+  __syncthreads();
+  for (int i = 0; i < N; i++) {
+    Sb = roll_load_state(P, i + 1, vb, sB);  // knot N too: the rotation of the last pos_cov
+    RollIn<M> Rin;
+    roll_load<M, true>(P, i, b, l, vb, sB, Rin);
+    pc_outputs(L, live, l, (size_t)b * (N + 1) + i, Sa, Sig, var_x, pos_cov);
+    // ---- the blocks of f_x at (x*_i, u*_i): lin_knot's dynamics part with the closed-form coefficients
+    const V3 wd = dt * Sa.w, vd = dt * Sa.v;
+    const SO3Coef kc = so3_coef(dot(wd, wd), true);
+    Pose E;
+    E.q = so3_exp(wd);
+    E.t = ljac_apply(wd, kc, vd);
+    const Pose Ei = se3_inverse(E);
+    double Ri[9], Ti[9], TR[9], Jr3[9], Qr[9], a22[36];
+    q_to_R(Ei.q, Ri);
+    skew(Ei.t, Ti);
+    mul33(Ti, Ri, TR);
+    ljac33(neg(wd), kc, Jr3);
+    Q33(neg(vd), neg(wd), kc, Qr);
+    a22_build(C, Sa.w, Sa.v, a22);
+    V3 rte = v3(0, 0, 0);
+    if constexpr (PK == 1) {
+      rte = qrot_inv(Sa.X.q, v3(Rin.u[0], Rin.u[1], Rin.u[2] - C.grav));
+      double Rm[9], SR[9], Bu[9];
+      q_to_R(Sa.X.q, Rm);
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        SR[c] = C.pend_k * Rm[3 * c + 1];
+        SR[3 + c] = -C.pend_k * Rm[3 * c + 0];
+        SR[6 + c] = 0.0;
+      }
+      mul33(C.Ibinv, SR, Bu);
+#pragma unroll
+      for (int k = 0; k < 9; k++) Bt[k] = dt * Bu[k];
+    } else if (C.grav != 0.0) {
+      rte = qrot_inv(Sa.X.q, v3(0, 0, -1.0));
+    }
+    if (l == 0) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) {
+        L[PC_TOP + k] = Ri[k]; L[PC_TOP + 9 + k] = TR[k];
+        L[PC_TOP + 18 + k] = dt * Jr3[k]; L[PC_TOP + 27 + k] = dt * Qr[k];
+      }
+#pragma unroll
+      for (int r = 0; r < 6; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          L[PC_BOT + 12 * r + c] = rte.x * C.Llin[0][6 * r + c] + rte.y * C.Llin[1][6 * r + c] + rte.z * C.Llin[2][6 * r + c];
+          L[PC_BOT + 12 * r + 3 + c] = 0.0;
+        }
+#pragma unroll
+        for (int c = 0; c < 6; c++) L[PC_BOT + 12 * r + 6 + c] = a22[6 * c + r];
+      }
+    }
+    if (2 * l < M) {  // gain rows 2l and 2l + 1
+#pragma unroll
+      for (int c = 0; c < 12; c++) { L[PC_K + 12 * (2 * l) + c] = Rin.G[0][c]; L[PC_K + 12 * (2 * l + 1) + c] = Rin.G[1][c]; }
+    }
+    __syncthreads();
+    {  // column j of the lower half: + f_u K
+      double kj[M], a[6];
+#pragma unroll
+      for (int u = 0; u < M; u++) kj[u] = L[PC_K + 12 * u + j];
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        double t = L[PC_BOT + 12 * r + j], m = L[PC_BOT + 12 * (3 + r) + j];
+#pragma unroll
+        for (int u = 0; u < 3; u++) t += Bt[3 * r + u] * kj[u];
+#pragma unroll
+        for (int u = 3; u < M; u++) m += Bb[3 * r + (u - 3)] * kj[u];
+        a[r] = t; a[3 + r] = m;
+      }
+      if (col) {
+#pragma unroll
+        for (int r = 0; r < 6; r++) L[PC_BOT + 12 * r + j] = a[r];
+      }
+      if (var_u) {  // diag K Sigma K^T: lane j's terms K[u][j] (Sigma[j, :] K[u, :]^T), summed over j by lane u
+#pragma unroll
+        for (int u = 0; u < M; u++) {
+          double p = 0.0;
+#pragma unroll
+          for (int c = 0; c < 12; c++) p += L[PC_K + 12 * u + c] * s[c];
+          if (col) L[PC_PU + M * j + u] = kj[u] * p;
+        }
+      }
+    }
+    __syncthreads();
+    if (var_u && live && l < M) {
+      double t = 0.0;
+#pragma unroll
+      for (int c = 0; c < 12; c++) t += L[PC_PU + M * c + l];
+      var_u[((size_t)b * N + i) * M + l] = t;
+    }
+    double x[12], y[12];
+    pc_apply(L, s, y);
+    if (col) {
+#pragma unroll
+      for (int r = 0; r < 12; r++) L[PC_TT + 12 * r + j] = y[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 12; k++) x[k] = L[PC_TT + 12 * j + k];
+    pc_apply(L, x, y);
+#pragma unroll
+    for (int k = 0; k < 6; k++) y[6 + k] += wc[k];
+    if (col) {
+#pragma unroll
+      for (int k = 0; k < 12; k++) L[PC_SG + 12 * j + k] = y[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = L[PC_SG + (k <= j ? 12 * k + j : 12 * j + k)];
+    Sa = Sb;
+  }
+  pc_outputs(L, live, l, (size_t)b * (N + 1) + N, Sa, Sig, var_x, pos_cov);
+}
+
 // d_J [B][S][36] (row-major 6x6 blkdiag(Ib, Jv)) and d_pend [B][S][2] (mass, length; the pendulum only, else null) into the
 // rows of form PL_DIAG or PL_DENSE (one thread per row; R = B S rows).  The constants are derived as tolg_create derives the
 // model's: Bt = Ib^-1 dt, mass = J[4][4], mass * grav, pend_k = mass * length / 2.  The diagonal form's inverses are the
@@ -4142,6 +4359,7 @@ struct KernelTable {
   // ... the same two with a plant (tolg_set_plant), [TOLG_PLANT_DIAG / TOLG_PLANT_DENSE]
   void (*policy_rollout_plant[2])(Params, int, int, const double*, const double*, double*, int*, double*, double*, double*, PlantArg);
   void (*mpc_advance_plant[2])(Params, const double*, double*, double*, double*, double*, double*, double*, PlantArg);
+  void (*policy_covariance)(Params, const double*, const double*, double*, double*, double*, double*);  // tolg_policy_covariance
   struct Search {                    // per search kind: ls[0] backtracking (single shooting), ls[1] merit (multiple shooting)
     struct { SearchRollout k; int nt; } wave2[2];  // k_rollout_ls2 [first try] and its NT (twist waves per pose wave)
     SearchRollout wave1[2];          // the one-wave forms k_rollout_ls [linear]
@@ -4209,6 +4427,7 @@ static KernelTable kernel_table(int lds_per_block) {
   t.policy_rollout_plant[TOLG_PLANT_DENSE] = k_policy_rollout<M, PK, PT & ~PT_OBS, PL_DENSE, PlantArg>;
   t.mpc_advance_plant[TOLG_PLANT_DIAG] = k_mpc_advance<M, PK, PT & ~PT_OBS, PL_DIAG, PlantArg>;
   t.mpc_advance_plant[TOLG_PLANT_DENSE] = k_mpc_advance<M, PK, PT & ~PT_OBS, PL_DENSE, PlantArg>;
+  t.policy_covariance = k_policy_covariance<M, PK>;  // (reads neither reference nor weights: one kernel for every PT)
   t.ls[0] = search_kernels<M, false, PK, PT>();
   t.ls[1] = search_kernels<M, true, PK, PT>();
   return t;
@@ -5390,6 +5609,17 @@ extern "C" int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const 
   else
     hipLaunchKernelGGL(h->kt.policy_rollout, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P, (int)S,
                        h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tolg_policy_covariance(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, double* d_Sigma,
+                                      double* d_var_x, double* d_var_u, double* d_pos_cov, void* stream) {
+  if (!policy_ok(h, B)) return TOLG_E_ARG;
+  if (d_pos_cov && so3_family(h->prob.kind)) return TOLG_E_ARG;  // no translation (the rule of tolg_set_al_obstacles)
+  const Params P = params_for(h, B);
+  hipLaunchKernelGGL(h->kt.policy_covariance, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, static_cast<hipStream_t>(stream), P,
+                     d_Sigma0, d_W, d_Sigma, d_var_x, d_var_u, d_pos_cov);
   LAUNCH_CHECK();
   return 0;
 }

@@ -92,6 +92,43 @@ class PolicyRollout:
 
 
 @dataclass
+class PolicyCovariance:
+    """First-order closed-loop covariance of the held policy (BatchedTrackingILQR.policy_covariance), in the error coordinates
+    of the gains; for so3 and the pendulum in the embedded 12-coordinate layout gains() uses (3..5 and 9..11 unused)."""
+    var_x: torch.Tensor                     # [B, N+1, 12] diag Sigma_i
+    var_u: torch.Tensor                     # [B, N, m] diag K_i Sigma_i K_i^T
+    pos_cov: Optional[torch.Tensor] = None  # [B, N+1, 3, 3] world-frame position covariance (None for so3 and the pendulum)
+    Sigma: Optional[torch.Tensor] = None    # [B, N+1, 12, 12] (full=True)
+
+
+def check_covariance(name, a, B, n, compact=None):
+    """A covariance input of policy_covariance checked on the host: `a` is [B, n, n] or [n, n] (broadcast over the batch), or
+    with compact = (k, index) also [B, k, k] / [k, k], embedded at rows / columns `index` of an n x n zero matrix.  It must be
+    finite, symmetric (to 1e-12 of its largest entry) and positive semi-definite (eigvalsh >= -1e-12 * its largest
+    eigenvalue); ValueError otherwise, before anything reaches the device.  Returns a float64 [B, n, n] numpy array."""
+    a = np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+    sizes = (n,) + ((compact[0],) if compact else ())
+    if a.ndim not in (2, 3) or a.shape[-1] != a.shape[-2] or a.shape[-1] not in sizes or (a.ndim == 3 and a.shape[0] != B):
+        raise ValueError("%s has shape %s, expected (%d, %s, %s) or (%s, %s) with n = %s"
+                         % (name, tuple(a.shape), B, "n", "n", "n", "n", " or ".join(map(str, sizes))))
+    if not np.all(np.isfinite(a)):
+        raise ValueError("%s must be finite" % name)
+    a = np.broadcast_to(a, (B,) + a.shape[-2:])
+    scale = np.abs(a).max(axis=(1, 2), keepdims=True)
+    if np.any(np.abs(a - np.swapaxes(a, 1, 2)) > 1e-12 * scale):
+        raise ValueError("%s must be symmetric" % name)
+    ev = np.linalg.eigvalsh(0.5 * (a + np.swapaxes(a, 1, 2)))
+    if np.any(ev[:, 0] < -1e-12 * np.maximum(ev[:, -1], 0.0)) or np.any(ev[:, -1] < 0.0):
+        raise ValueError("%s must be positive semi-definite" % name)
+    if a.shape[-1] != n:
+        idx = np.asarray(compact[1])
+        full = np.zeros((B, n, n))
+        full[:, idx[:, None], idx[None, :]] = a
+        a = full
+    return np.ascontiguousarray(a)
+
+
+@dataclass
 class MPCResult:
     """`steps` closed-loop receding-horizon steps of B trajectories (BatchedTrackingILQR.mpc)."""
     xs_q: torch.Tensor     # [B, steps+1, 4, 4] closed-loop states: x0, then the plant state after every step
@@ -800,6 +837,36 @@ class BatchedTrackingILQR:
         finally:
             if plant is not None:
                 self._clear_plant()
+        return r
+
+    def policy_covariance(self, Sigma0=None, W=None, full=False, pos=True) -> PolicyCovariance:
+        """The closed-loop covariance of the held policy to first order (tolg_policy_covariance), the analytic companion of
+        policy_rollout: Sigma_{i+1} = Acl_i Sigma_i Acl_i^T + E W E^T with Acl_i = f_x + f_u K_i at the held nominal, in the
+        error coordinates of K.  Sigma0 [B, 12, 12] or [12, 12] (broadcast): covariance of the start perturbation dx0; W
+        [B, 6, 6] or [6, 6]: covariance of the twist disturbance added behind every step; either may be None (zero).  Both are
+        checked on the host (check_covariance: shape, finite, symmetric, positive semi-definite).
+        so3 and the pendulum: the state is carried in 12 coordinates as in gains() ([rotation, 0, omega, 0]); Sigma0 may also be
+        given as [.., 6, 6] over (rotation, omega) and W as [.., 3, 3] over omega -- plant_J's convention for their inertia --
+        and are embedded at rows / columns (0..2, 6..8) resp. (0..2); the outputs keep the 12-coordinate layout.
+        Returns var_x [B, N+1, 12], var_u [B, N, m], pos_cov [B, N+1, 3, 3] (the world-frame position covariance; pos=False or a
+        model without translation: None) and, with full=True, Sigma [B, N+1, 12, 12] (0.95 GB at 4096 x 200).  A plant, an
+        input box and keep-out spheres are ignored: the loop is the model's linear, unsaturated one."""
+        B = self._held_B()
+        so3 = self.problem.kind in ("so3", "pendulum3d")
+        S0 = None if Sigma0 is None else check_covariance("Sigma0", Sigma0, B, 12, (6, [0, 1, 2, 6, 7, 8]) if so3 else None)
+        Wn = None if W is None else check_covariance("W", W, B, 6, (3, [0, 1, 2]) if so3 else None)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        d_S0 = None if S0 is None else self._dev(S0, (B, 12, 12))
+        d_W = None if Wn is None else self._dev(Wn, (B, 6, 6))
+        r = PolicyCovariance(var_x=torch.empty(B, self.N + 1, 12, **f64), var_u=torch.empty(B, self.N, self.m, **f64))
+        if full:
+            r.Sigma = torch.empty(B, self.N + 1, 12, 12, **f64)
+        pc = torch.empty(B, self.N + 1, 6, **f64) if (pos and not so3) else None
+        self._hold((d_S0, d_W))
+        self._call("tolg_policy_covariance", B, _ptr(d_S0), _ptr(d_W), _ptr(r.Sigma), _ptr(r.var_x), _ptr(r.var_u), _ptr(pc))
+        if pc is not None:
+            iu = torch.tensor([[0, 1, 2], [1, 3, 4], [2, 4, 5]], device=self.device)
+            r.pos_cov = pc[..., iu]
         return r
 
     # ------------------------------------------------------------------------------------------

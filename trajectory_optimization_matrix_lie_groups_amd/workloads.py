@@ -244,6 +244,30 @@ def se3_policy_eval(B, S, N=200, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=
     return prob, x0_q, x0_xi, us0, dx0, noise
 
 
+def se3_covariance(B, N=200, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=0.01, seed=SEED):
+    """Covariance inputs for the closed loop of se3_tracking's workload (BatchedTrackingILQR.policy_covariance), the analytic
+    counterpart of se3_policy_eval's samples.  Returns (prob, x0_q, x0_xi, us0, Sigma0 [B, 12, 12], W [B, 6, 6]): seeded, per
+    trajectory and not diagonal -- each is Q D Q^T with a random rotation Q (the orthogonal factor of a Gaussian matrix) of a
+    diagonal D whose standard deviations are sigma_pose (pose part) and sigma_twist (twist part) resp. sigma_noise, each
+    scaled by a factor drawn uniformly from [0.5, 1.5].  A sigma of zero gives a zero matrix."""
+    prob, x0_q, x0_xi, us0 = se3_tracking(B, N=N, seed=seed)
+    rng = np.random.default_rng(seed + 5)
+
+    def rotated(sig):
+        n = sig.shape[0]
+        out = np.zeros((B, n, n))
+        for b in range(B):
+            Q, _ = np.linalg.qr(rng.normal(size=(n, n)))
+            d = (sig * rng.uniform(0.5, 1.5, n)) ** 2
+            out[b] = (Q * d) @ Q.T
+            out[b] = 0.5 * (out[b] + out[b].T)
+        return out
+
+    Sigma0 = rotated(np.r_[[float(sigma_pose)] * 6, [float(sigma_twist)] * 6])
+    W = rotated(np.full(6, float(sigma_noise)))
+    return prob, x0_q, x0_xi, us0, Sigma0, W
+
+
 def plant_mismatch(B, S, kind="se3", N=None, sigma_inertia=0.1, sigma_mass=0.1, rotate=False, seed=SEED):
     """Model-mismatch inputs for the closed loop (BatchedTrackingILQR.policy_rollout with plant_J): se3_policy_eval's
     perturbations on se3_tracking's (kind="se3", N default 200) or drone_tracking's (kind="drone", N default 400) workload,
