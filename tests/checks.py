@@ -1,0 +1,211 @@
+"""Assertion-bearing checks that more than one test module calls, each with the tolerances of the test it came from."""
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import bridge as ob
+from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, _capi, workloads
+from trajectory_optimization_matrix_lie_groups_amd.solver import mpc_shift
+from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_constraints import SphereObstacleConstraint
+from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_controller import (iLQR_Tracking_SE3,
+                                                                                           iLQR_Tracking_SE3_MS)
+from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_cost import ALConstrainedCost
+from tests.restate import MyCost, MyDynamics, restate_mpc_step, restate_policy, window_problem
+from tests.support import ZERO, host, problem_of_kind, random_traj_embedded, rel, same
+
+
+def check_linearize_backward(prob, xs_q, xs_xi, us, ms, solver=None):
+    """K1 + K2 (tolg_linearize_backward) on the given trajectories against the oracle's _linearization/_backward_pass,
+    trajectory by trajectory; solver: a handle on prob (default: a fresh one of the batch's size)."""
+    B = xs_q.shape[0]
+    solver = BatchedTrackingILQR(prob, B) if solver is None else solver
+    r = solver.linearize_backward(xs_q, xs_xi, us, ms=ms)
+    torch.cuda.synchronize()
+    op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref,
+                          pend_mass=prob.pend_mass, pend_length=prob.pend_length)
+    for b in range(B):
+        o = ob.lin_backward(op, xs_q[b], xs_xi[b], us[b], ms=ms)
+        assert rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
+        assert np.abs(r["d"][b].cpu().numpy() - o["d"]).max() < 1e-11 * max(1.0, np.abs(o["d"]).max())
+        assert rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
+        assert rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
+        assert float(r["J"][b]) == pytest.approx(o["J"], rel=1e-12)
+        assert rel(r["K"][b].cpu(), o["K"]) < 1e-8
+        assert rel(r["k"][b].cpu(), o["k"]) < 1e-8
+        assert float(r["grad"][b]) == pytest.approx(o["grad"], rel=1e-9)
+        assert float(r["mu_delta"][b, 0]) == o["mu"] and float(r["mu_delta"][b, 1]) == o["delta"]
+
+
+def al_oracle(prob, x0_q, x0_xi, us0, lb, ub, n_al, n_ilqr, tol_constr, mu0=1e-2, mu_scale=10.0, mu_max=1e8):
+    """AL_iLQR_Tracking_SE3_MS.fit restated with the oracle as inner solver
+    (reference traoptlibrary/traopt_controller.py:3218-3293; the reference class itself does not
+    run at HEAD -- SURVEY App. C-Q7 -- so this is the specification: parity unpinned)."""
+    N, m = prob.N, prob.m
+    lam = np.zeros((N, 2 * m)); imu = np.full((N, 2 * m), mu0); mu = mu0
+    for it in range(n_al):
+        op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref,
+                              al=dict(lb=lb, ub=ub, lam=lam, imu=imu))
+        o = ob.fit(op, x0_q, x0_xi, us0, mode="ms", max_iter=n_ilqr, tol_grad=1e-6, tol_defect=1e-6)
+        g = np.concatenate([lb[None] - o["us"], o["us"] - ub[None]], axis=1)
+        if max(g.max(), 0.0) < tol_constr:
+            return o, lam, imu, mu, it + 1
+        mu_new = min(mu * mu_scale, mu_max)
+        lam_new = np.clip(lam + imu * g, 0.0, None)
+        imu = np.where((g < 0.0) & (lam_new == 0.0), 0.0, mu_new)
+        lam, mu = lam_new, mu_new
+    return o, lam, imu, mu, n_al
+
+
+def check_ring_against_statement(kind, B, N, spread):
+    """The body of test_ring_kernel_matches_statement_kernel_on_random_trajectories (tests/test_gpu_expected_change.py), for
+    any kind / batch / horizon / spread."""
+    prob, *_ = problem_of_kind(kind, 1, N)
+    xs_q, xs_xi, us = random_traj_embedded(prob, B, seed=3 + N, spread=spread)
+    if B >= 5:  # two trajectories with rotation defects near pi: candidates for the hand-back
+        wild, _, _ = random_traj_embedded(prob, B, seed=4 + N, spread=1.6)
+        xs_q[1], xs_q[4] = wild[1], wild[4]
+    solver = BatchedTrackingILQR(prob, B)
+    solver.linearize_backward(xs_q, xs_xi, us, ms=True)
+    es, _ = solver.expected_change(B, "statement")
+    er, flag = solver.expected_change(B, "ring")
+    er2, flag2 = solver.expected_change(B, "ring")
+    ea, _ = solver.expected_change(B, "auto")
+    torch.cuda.synchronize()
+    es, er, er2, ea, flag, flag2 = (t.cpu().numpy() for t in (es, er, er2, ea, flag, flag2))
+    np.testing.assert_array_equal(flag, flag2)
+    np.testing.assert_array_equal(er, er2)
+    keep = flag == 0
+    assert keep.sum() >= B // 2
+    assert np.isfinite(es).all()
+    scale = np.abs(es).max(axis=1, keepdims=True)
+    assert (np.abs(er[keep] - es[keep]) / scale[keep]).max() < 1e-11
+    assert np.isnan(er[~keep]).all()
+    np.testing.assert_array_equal(ea[~keep], es[~keep])
+    np.testing.assert_array_equal(ea[keep], er[keep])
+
+
+_TOL = {"J_hist": 1e-11, "xs_q": 1e-9, "xs_xi": 1e-9, "us": 1e-9, "mu_hist": 0.0}
+
+
+def assert_same(keep, rs):
+    for k, v in keep.items():
+        w = getattr(rs, k)
+        if not v.dtype.is_floating_point:
+            assert torch.equal(v, w), k
+            continue
+        assert torch.equal(torch.isnan(v), torch.isnan(w)), k  # untouched history entries are NaN on both sides
+        a = torch.nan_to_num(v, nan=0.0).cpu().numpy(); b = torch.nan_to_num(w, nan=0.0).cpu().numpy()
+        if k in ("grad_hist", "defect_hist"):  # rounding-level quantities once converged: absolute floor
+            assert np.abs(a - b).max() <= 1e-9 * np.abs(b).max() + 1e-11, (k, np.abs(a - b).max())
+        else:
+            assert rel(a, b) <= _TOL[k], (k, rel(a, b))
+
+
+def check_advance(s, r, ops, w):
+    B, N = r.us.shape[0], s.N
+    J1 = torch.zeros(B, dtype=torch.float64, device=s.device)
+    a = s.mpc_advance(w, J_cl=J1)
+    xq, xx, uu = host(r.xs_q), host(r.xs_xi), host(r.us)
+    fin = [b for b in range(B) if np.isfinite(xq[b]).all() and np.isfinite(xx[b]).all() and np.isfinite(uu[b]).all()]
+    assert len(fin) >= B // 2
+    for b in fin:
+        op = ops[b]
+        q1, x1 = ob.f(op, xq[b, 0], xx[b, 0], uu[b, 0])
+        assert rel(host(a["x_next_q"])[b], q1) < 1e-13 and rel(host(a["x_next_xi"])[b], x1 + w[b]) < 1e-13
+        qN, xN = ob.f(op, xq[b, N], xx[b, N], uu[b, N - 1])
+        assert rel(host(a["xs_q"])[b, N], qN) < 1e-13 and rel(host(a["xs_xi"])[b, N], xN) < 1e-13
+        assert abs(host(J1)[b] / ob.cost(op, xq[b, 0], xx[b, 0], uu[b, 0], 0)[0] - 1) < 1e-12
+    # the shift: bitwise the host shift of solve_end's output
+    sq, su = mpc_shift(xq, uu, host(a["x_next_q"]), host(a["xs_q"])[:, N])
+    sx, _ = mpc_shift(xx, uu, host(a["x_next_xi"]), host(a["xs_xi"])[:, N])
+    for k, shifted in (("xs_q", sq), ("xs_xi", sx), ("us", su)):
+        diff = ~np.equal(host(a[k]), shifted) & ~(np.isnan(host(a[k])) & np.isnan(shifted))
+        assert not diff.any(), (k, sorted(set(zip(*np.nonzero(diff)[:2])))[:10])
+    assert same(a["u"], uu[:, 0])
+    # twice: the same bits, the policy untouched (J_cl accumulates)
+    b2 = s.mpc_advance(w, J_cl=J1)
+    for k in ("x_next_q", "x_next_xi", "u", "xs_q", "xs_xi", "us"):
+        assert same(a[k], b2[k]), k
+    assert rel(host(J1)[fin], 2 * np.array([ob.cost(ops[b], xq[b, 0], xx[b, 0], uu[b, 0], 0)[0] for b in fin])) < 1e-12
+
+
+def check_loop(B, N, steps, K0, K):
+    """mpc() on se3_mpc's paths against restate_mpc_step, step by step: every window's solve, the applied input, the
+    closed-loop state and cost."""
+    prob, q, xi, pq, px, t0, noise = workloads.se3_mpc(B, steps, N=N, sigma_noise=0.02, seed=21)
+    s = BatchedTrackingILQR(prob, B)
+    seen = []
+    r = s.mpc(q, xi, pq, px, steps, t0=t0, first_iters=K0, iters_per_step=K, warm="controls", noise=noise, check_every=0,
+              **ZERO, on_step=lambda t, out: seen.append((t, host(out.xs_q).copy(), host(out.xs_xi).copy(), host(out.us).copy(),
+                                                  host(out.J_hist).copy())))
+    assert [t for t, *_ in seen] == list(range(steps))
+    rq, rx, ru, J = host(r.xs_q), host(r.xs_xi), host(r.us), host(r.J)
+    assert np.array_equal(rq[:, 0], q) and np.array_equal(rx[:, 0], xi)
+    Jcl = np.zeros(B)
+    for t, xs_q, xs_xi, us, Jh in seen:
+        us_in = np.zeros((B, N, prob.m)) if t == 0 else mpc_shift(seen[t - 1][1], seen[t - 1][3], rq[:, t], rq[:, t])[1]
+        assert np.array_equal(ru[:, t], us[:, 0])  # the applied input is the step's u*_0
+        for b in range(B):
+            op = window_problem(prob, pq[b], px[b], int(t0[b]), t)
+            o = restate_mpc_step(op, rq[b, t], rx[b, t], us_in[b], K0 if t == 0 else K)
+            assert np.abs(Jh[b] / o["J_hist"] - 1).max() < 1e-9, (t, b)
+            assert np.abs(us[b] - o["us"]).max() / np.abs(o["us"]).max() < 1e-6, (t, b)
+            # the closed-loop state is the advance's x_next: f(x*_0, u*_0) + noise
+            q1, x1 = ob.f(op, xs_q[b, 0], xs_xi[b, 0], us[b, 0])
+            assert rel(rq[b, t + 1], q1) < 1e-13 and rel(rx[b, t + 1], x1 + noise[b, t]) < 1e-13
+            Jcl[b] += ob.cost(op, xs_q[b, 0], xs_xi[b, 0], us[b, 0], 0)[0]
+    assert rel(J, Jcl) < 1e-12
+    assert (host(r.status) == _capi.ST_OK).all()
+    assert (host(r.iters)[:, 0] == K0).all() and (host(r.iters)[:, 1:] == K).all()
+
+
+def host_solve(prob, x0_q, x0_xi, us0, obs, lam, imu, kw, states=False):
+    """The mirror's host generic path with fixed sphere multipliers: (J per iteration, us[, xs]).  states: xs as well."""
+    op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
+    c = SphereObstacleConstraint(obs[:, :3], obs[:, 3])
+    al = ALConstrainedCost(MyCost(op, prob.m), c, prob.N)
+    al.lmbd = lam.copy()
+    al.Imu = np.stack([np.diag(d) for d in imu])
+    ms = kw["mode"] == "ms"
+    J = []
+
+    def cb(*a):
+        a[-5 if ms else -3].append(a[3])
+        J.append(a[3])
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        rollout = kw.get("rollout", "nonlinear")
+        if ms:
+            ctl = iLQR_Tracking_SE3_MS(MyDynamics(op, prob.m), al, prob.N, prob.q_ref, prob.xi_ref, rollout=rollout,
+                                       line_search=kw.get("line_search", False))
+        else:
+            ctl = iLQR_Tracking_SE3(MyDynamics(op, prob.m), al, prob.N, rollout=rollout)
+        xs, us, *_ = ctl.fit([x0_q, x0_xi], us0, n_iterations=kw["n_iterations"], tol_grad_norm=0.0, on_iteration=cb)
+    return (np.array(J), us, xs) if states else (np.array(J), us)
+
+
+def update_restated(g, lam, imu, mu, mu_scale=10.0):
+    mu_new = mu * mu_scale
+    ln = np.maximum(0.0, lam + imu * g)
+    return ln, np.where((g < 0) & (ln == 0), 0.0, mu_new)
+
+
+def check_restatement(s, r, ops, dx0, w):
+    g = s.gains()
+    p = s.policy_rollout(dx0, w, trajectories=True)
+    K = host(g["K"])
+    S = dx0.shape[1]
+    ok = 0
+    for b, op in enumerate(ops):
+        J, xq, xx, uu = restate_policy(op, host(r.xs_q)[b], host(r.xs_xi)[b], host(r.us)[b], K[b], dx0[b], w[b], S)
+        fin = np.isfinite(J)  # a sample the CPU sees diverge must diverge on the device, and be flagged there
+        assert np.array_equal(host(p.status)[b], np.where(fin, _capi.ST_OK, _capi.ST_NONFINITE))
+        assert np.abs(host(p.xs_q)[b][fin] - xq[fin]).max(initial=0) < 1e-10
+        assert np.abs(host(p.xs_xi)[b][fin] - xx[fin]).max(initial=0) < 1e-10
+        assert np.abs(host(p.us)[b][fin] - uu[fin]).max(initial=0) < 1e-8
+        assert np.abs(host(p.J)[b][fin] / J[fin] - 1).max(initial=0) < 1e-9
+        ok += int(fin.sum())
+    assert ok >= len(ops) * S // 2

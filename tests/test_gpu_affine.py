@@ -11,15 +11,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import bridge as ob  # noqa: E402  (test infrastructure)
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, workloads  # noqa: E402
-
-
-def _oracle_problem(p):
-    return ob.OracleProblem(p.kind, p.J, p.dt, p.Q, p.R, p.P, p.q_ref, p.xi_ref)
-
-
-def _rel(a, b):
-    a = np.asarray(a); b = np.asarray(b)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+from tests.support import oracle_problem, rel  # noqa: E402
 
 
 def _fit(prob, x0_q, x0_xi, us0, K, mode, line_search, schedule):
@@ -47,7 +39,7 @@ def test_affine_equals_statement_form_and_oracle(kind, mode, line_search, B, N):
     K = 5
     ra = _fit(prob, x0_q, x0_xi, us0, K, mode, line_search, "auto")
     rs = _fit(prob, x0_q, x0_xi, us0, K, mode, line_search, "split")
-    o = ob.fit_batch(_oracle_problem(prob), x0_q, x0_xi, us0, mode=mode, max_iter=K, line_search=line_search, rollout="linear")
+    o = ob.fit_batch(oracle_problem(prob), x0_q, x0_xi, us0, mode=mode, max_iter=K, line_search=line_search, rollout="linear")
     # the two GPU forms take the same decisions; against the oracle a search that has converged to rounding level may end on a
     # coin flip (the last step size of the merit search is 1.1^-361 = 1e-15: tests/test_gpu_matrix.py) -- the side that goes on
     # does so without moving the cost
@@ -62,13 +54,13 @@ def test_affine_equals_statement_form_and_oracle(kind, mode, line_search, B, N):
     assert same.sum() >= B - max(1, B // 50)
     n = int(min(o["iters"][same].min(), ra.iters.cpu().numpy()[same].min()))
     for r in (ra, rs):
-        assert _rel(r.J_hist.cpu().numpy()[same, :n], o["J_hist"][same, :n]) < 1e-9
-        assert _rel(r.us.cpu().numpy()[same], o["us"][same]) < 1e-6
-        assert _rel(r.xs_xi.cpu().numpy()[same], o["xs_xi"][same]) < 1e-6
+        assert rel(r.J_hist.cpu().numpy()[same, :n], o["J_hist"][same, :n]) < 1e-9
+        assert rel(r.us.cpu().numpy()[same], o["us"][same]) < 1e-6
+        assert rel(r.xs_xi.cpu().numpy()[same], o["xs_xi"][same]) < 1e-6
     Ja, Js = ra.J_hist.cpu().numpy(), rs.J_hist.cpu().numpy()   # (NaN = not reached: the same entries on both sides)
     assert np.array_equal(np.isnan(Ja), np.isnan(Js))
-    assert _rel(np.nan_to_num(Ja), np.nan_to_num(Js)) < 1e-10
-    assert _rel(ra.us.cpu().numpy(), rs.us.cpu().numpy()) < 1e-8
+    assert rel(np.nan_to_num(Ja), np.nan_to_num(Js)) < 1e-10
+    assert rel(ra.us.cpu().numpy(), rs.us.cpu().numpy()) < 1e-8
     if ra.alpha_hist is not None and (line_search or mode == "ss"):
         assert np.array_equal(np.nan_to_num(ra.alpha_hist.cpu().numpy()), np.nan_to_num(rs.alpha_hist.cpu().numpy()))
 
@@ -85,7 +77,7 @@ def test_trajectories_handed_back_take_the_statement_form():
     us0[wild] = rng.normal(size=(int(wild.sum()), N, 6)) * 3.0
     x0_xi = x0_xi.copy()
     x0_xi[wild, :3] += rng.normal(size=(int(wild.sum()), 3)) * 4.0
-    op = _oracle_problem(prob)
+    op = oracle_problem(prob)
     for mode, ls in (("ss", False), ("ms", True)):
         ra = _fit(prob, x0_q, x0_xi, us0, K, mode, ls, "auto")
         rs = _fit(prob, x0_q, x0_xi, us0, K, mode, ls, "split")
@@ -97,7 +89,7 @@ def test_trajectories_handed_back_take_the_statement_form():
             if n == 0 or not np.isfinite(jo).all() or np.abs(jo).max() > 1e12:
                 continue
             assert ra.iters[b].item() == rs.iters[b].item() == o["iters"][b], (mode, b)
-            assert _rel(ra.J_hist[b, :n].cpu().numpy(), jo) < 1e-8, (mode, b)
-            assert _rel(rs.J_hist[b, :n].cpu().numpy(), jo) < 1e-8, (mode, b)
+            assert rel(ra.J_hist[b, :n].cpu().numpy(), jo) < 1e-8, (mode, b)
+            assert rel(rs.J_hist[b, :n].cpu().numpy(), jo) < 1e-8, (mode, b)
             checked += 1
         assert checked >= B // 2

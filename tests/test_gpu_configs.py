@@ -6,21 +6,22 @@ import pytest
 
 from oracle import bridge as ob
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, workloads
-from tests.test_gpu_parity import _al_oracle, _oracle_problem, _rel
+from tests.checks import al_oracle
+from tests.support import oracle_problem, rel
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-6
 
 
 def _check_members(r, prob, x0_q, x0_xi, us0, members, K, mode="ms", **kw):
-    op = _oracle_problem(prob)
+    op = oracle_problem(prob)
     for b in members:
         o = ob.fit(op, x0_q[b], x0_xi[b], us0[b], mode=mode, max_iter=K, **kw)
         n = int(r.iters[b])
         assert n == o["n_iters"]
-        assert _rel(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < TOL
-        assert _rel(r.us[b].cpu(), o["us"]) < TOL
-        assert _rel(r.xs_xi[b].cpu(), o["xs_xi"]) < TOL
+        assert rel(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < TOL
+        assert rel(r.us[b].cpu(), o["us"]) < TOL
+        assert rel(r.xs_xi[b].cpu(), o["xs_xi"]) < TOL
         assert np.abs(r.xs_q[b].cpu().numpy() - o["xs_q"]).max() < TOL
 
 
@@ -35,8 +36,8 @@ def test_config2_so3_exact_tracking_b1_n100():
         o = ob.fit(op, x0_q[b], x0_xi[b], us0[b], mode="ss", max_iter=200, tol_grad=1e-6)
         n = int(r.iters[b])
         assert n == o["n_iters"] and bool(r.converged[b]) == o["converged"]
-        assert _rel(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < TOL
-        assert _rel(r.us[b].cpu(), o["us"]) < TOL
+        assert rel(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < TOL
+        assert rel(r.us[b].cpu(), o["us"]) < TOL
 
 
 def test_config3_se3_exact_tracking_b256_n200():
@@ -62,10 +63,10 @@ def test_config4_al_ddp_input_box_b1024_n200():
     viol_al = (res.us.abs() - 10.0).clamp(min=0).amax(dim=(1, 2))
     assert float(viol_al.median()) < 0.7 * float(viol_free.median())
     for b in (0, 3, 500, 1023):
-        o, lam, imu, mu, n_outer = _al_oracle(prob, x0_q[b], x0_xi[b], us0[b], lb, ub, n_al, n_in, 1e-2)
-        assert _rel(res.us[b].cpu(), o["us"]) < TOL
-        assert _rel(res.xs_xi[b].cpu(), o["xs_xi"]) < TOL
-        assert _rel(info["lmbd"][b].cpu(), lam) < TOL
+        o, lam, imu, mu, n_outer = al_oracle(prob, x0_q[b], x0_xi[b], us0[b], lb, ub, n_al, n_in, 1e-2)
+        assert rel(res.us[b].cpu(), o["us"]) < TOL
+        assert rel(res.xs_xi[b].cpu(), o["xs_xi"]) < TOL
+        assert rel(info["lmbd"][b].cpu(), lam) < TOL
         assert float(info["mu"][b]) == pytest.approx(mu)
 
 
@@ -81,7 +82,7 @@ def test_config5_drone_racing_shard_b1024_n400():
     r = solver.fit_batch(x0_q, x0_xi, us0, mode="ms", n_iterations=K, tol_grad_norm=0.0, tol_d_norm=0.0)
     # accept-always MS (line_search=False, benchmark_drone_racing_tracking.py:217) blows up on some of the
     # perturbed members; the reference algorithm does too -- the same members, with the same status
-    o = ob.fit_batch(_oracle_problem(prob), x0_q[:256], x0_xi[:256], us0[:256], mode="ms", max_iter=K)
+    o = ob.fit_batch(oracle_problem(prob), x0_q[:256], x0_xi[:256], us0[:256], mode="ms", max_iter=K)
     st = r.status.cpu().numpy()
     np.testing.assert_array_equal(st[:256], o["status"])
     np.testing.assert_array_equal(r.iters.cpu().numpy()[:256], o["iters"])
@@ -91,9 +92,9 @@ def test_config5_drone_racing_shard_b1024_n400():
     good = torch.as_tensor(st == 0, device=r.us.device)
     assert torch.isfinite(r.us[good]).all() and torch.isfinite(r.xs_xi[good]).all()
     for b in (ok[0], ok[len(ok) // 2], ok[-1]):
-        assert _rel(r.J_hist[b].cpu(), o["J_hist"][b]) < TOL
-        assert _rel(r.us[b].cpu(), o["us"][b]) < TOL
-        assert _rel(r.xs_xi[b].cpu(), o["xs_xi"][b]) < TOL
+        assert rel(r.J_hist[b].cpu(), o["J_hist"][b]) < TOL
+        assert rel(r.us[b].cpu(), o["us"][b]) < TOL
+        assert rel(r.xs_xi[b].cpu(), o["xs_xi"][b]) < TOL
 
 
 def torch_isfinite(r):

@@ -9,52 +9,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import bridge as ob  # noqa: E402  (test infrastructure)
-from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, workloads  # noqa: E402
-
-
-def _oracle_problem(p: TrackingProblem):
-    return ob.OracleProblem(p.kind, p.J, p.dt, p.Q, p.R, p.P, p.q_ref, p.xi_ref)
-
-
-def _rel(a, b):
-    a = np.asarray(a); b = np.asarray(b)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
-
-
-def _dense(prob):
-    """The same problem with full inertia blocks (a rotated body frame's inertia): the backward sweep and the ring kernel then read
-    I + H dt from the record (Params::fA22 >= 0) instead of rebuilding it from the twist."""
-    A = np.array([[0.10, -0.05, 0.02], [0.03, 0.12, -0.04], [-0.02, 0.06, 0.09]])
-    Jd = np.array(prob.J, dtype=float).copy()
-    Jd[:3, :3] += A @ A.T
-    if prob.kind == "se3":
-        Jd[3:, 3:] += 0.5 * (A @ A.T)
-    return TrackingProblem(prob.kind, Jd, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
-
-
-def _problem(kind, B, N):
-    if kind.endswith("_dense"):
-        prob, x0_q, x0_xi, us0 = _problem(kind[:-6], B, N)
-        return _dense(prob), x0_q, x0_xi, us0
-    if kind == "se3":
-        return workloads.se3_tracking(B, N=N, R_scale=1e-3)
-    if kind == "drone":
-        return workloads.drone_tracking(B, N=N, R_scale=1e-3)
-    prob, x0_q, x0_xi, us0 = workloads.so3_tracking(B, N=N)
-    return prob, x0_q, x0_xi, us0
-
-
-def _random_traj(prob, B, seed, spread):
-    rng = np.random.default_rng(seed)
-    N, m = prob.N, prob.m
-    xs_q = np.empty((B, N + 1, 4, 4)); xs_xi = np.empty((B, N + 1, 6)); us = rng.normal(size=(B, N, m)) * 0.3
-    for b in range(B):
-        for i in range(N + 1):
-            xs_q[b, i] = prob.q_ref[i] @ ob.se3_exp(rng.normal(size=6) * spread * (1 if prob.kind != "so3" else np.r_[1, 1, 1, 0, 0, 0]))
-            xs_xi[b, i] = prob.xi_ref[i] + rng.normal(size=6) * spread * (1 if prob.kind != "so3" else np.r_[1, 1, 1, 0, 0, 0])
-    if prob.kind == "so3":
-        us[:, :, 3:] = 0
-    return xs_q, xs_xi, us
+from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, workloads  # noqa: E402
+from tests.checks import check_ring_against_statement  # noqa: E402
+from tests.support import oracle_problem, problem_of_kind, random_traj_embedded, rel  # noqa: E402
 
 
 @pytest.mark.parametrize("kind,B,N", [("se3", 7, 33), ("se3", 64, 200), ("drone", 5, 60), ("drone", 12, 150), ("so3", 4, 40),
@@ -68,33 +25,6 @@ def test_ring_kernel_matches_statement_kernel_on_random_trajectories(kind, B, N,
     every CU with NaNs first: the statement kernel once filled its constant table AFTER inactive quads had left, and
     passed wherever the previous launch had left the same table behind.)"""
     check_ring_against_statement(kind, B, N, spread)
-
-
-def check_ring_against_statement(kind, B, N, spread):
-    """The body of the test above, for any kind / batch / horizon / spread."""
-    prob, *_ = _problem(kind, 1, N)
-    xs_q, xs_xi, us = _random_traj(prob, B, seed=3 + N, spread=spread)
-    if B >= 5:  # two trajectories with rotation defects near pi: candidates for the hand-back
-        wild, _, _ = _random_traj(prob, B, seed=4 + N, spread=1.6)
-        xs_q[1], xs_q[4] = wild[1], wild[4]
-    solver = BatchedTrackingILQR(prob, B)
-    solver.linearize_backward(xs_q, xs_xi, us, ms=True)
-    es, _ = solver.expected_change(B, "statement")
-    er, flag = solver.expected_change(B, "ring")
-    er2, flag2 = solver.expected_change(B, "ring")
-    ea, _ = solver.expected_change(B, "auto")
-    torch.cuda.synchronize()
-    es, er, er2, ea, flag, flag2 = (t.cpu().numpy() for t in (es, er, er2, ea, flag, flag2))
-    np.testing.assert_array_equal(flag, flag2)
-    np.testing.assert_array_equal(er, er2)
-    keep = flag == 0
-    assert keep.sum() >= B // 2
-    assert np.isfinite(es).all()
-    scale = np.abs(es).max(axis=1, keepdims=True)
-    assert (np.abs(er[keep] - es[keep]) / scale[keep]).max() < 1e-11
-    assert np.isnan(er[~keep]).all()
-    np.testing.assert_array_equal(ea[~keep], es[~keep])
-    np.testing.assert_array_equal(ea[keep], er[keep])
 
 
 def _fit(solver, x0_q, x0_xi, us0, K, schedule):
@@ -113,7 +43,7 @@ def _same_search(it_a, J_a, A_a, it_b, J_b, A_b, tol, what):
     for b in range(len(it_a)):
         n = min(int(it_a[b]), int(it_b[b]))
         if n:
-            assert _rel(J_a[b, :n], J_b[b, :n]) < tol, what
+            assert rel(J_a[b, :n], J_b[b, :n]) < tol, what
             if A_a is not None:
                 np.testing.assert_allclose(A_a[b, : n - 1], A_b[b, : n - 1], rtol=1e-14, err_msg=what)
         if it_a[b] == it_b[b]:
@@ -131,18 +61,18 @@ def test_ring_form_matches_statement_form_and_oracle(kind, B, N):
     """Same accepted step sizes, same costs (the two kernels differ by Exp/Log round trips and the order of two sums);
     B not a multiple of 4 exercises the padded group, N not a multiple of 4 the ring's tail steps."""
     K = 8
-    prob, x0_q, x0_xi, us0 = _problem(kind, B, N)
+    prob, x0_q, x0_xi, us0 = problem_of_kind(kind, B, N)
     solver = BatchedTrackingILQR(prob, B)
     ra = _fit(solver, x0_q, x0_xi, us0, K, "auto")
     Ja, Aa, ia, ua = ra.J_hist.cpu().numpy().copy(), ra.alpha_hist.cpu().numpy().copy(), ra.iters.cpu().numpy().copy(), ra.us.cpu().numpy().copy()
     rs = _fit(solver, x0_q, x0_xi, us0, K, "split")
     Js, As, is_, us_ = rs.J_hist.cpu().numpy(), rs.alpha_hist.cpu().numpy(), rs.iters.cpu().numpy(), rs.us.cpu().numpy()
-    o = ob.fit_batch(_oracle_problem(prob), x0_q, x0_xi, us0, mode="ms", max_iter=K, line_search=True)
+    o = ob.fit_batch(oracle_problem(prob), x0_q, x0_xi, us0, mode="ms", max_iter=K, line_search=True)
     same = _same_search(ia, Ja, Aa, is_, Js, As, 1e-10, "ring form vs statement form")
-    assert _rel(ua[same], us_[same]) < 1e-8
+    assert rel(ua[same], us_[same]) < 1e-8
     _same_search(is_, Js, None, o["iters"], o["J_hist"], None, 1e-8, "statement form vs oracle")
     same = _same_search(ia, Ja, None, o["iters"], o["J_hist"], None, 1e-8, "ring form vs oracle")
-    assert _rel(ua[same], o["us"][same]) < 1e-6
+    assert rel(ua[same], o["us"][same]) < 1e-6
 
 
 def test_large_rotation_deviation_is_handed_back():
@@ -161,11 +91,11 @@ def test_large_rotation_deviation_is_handed_back():
     Ja, ia, ua = ra.J_hist.cpu().numpy().copy(), ra.iters.cpu().numpy().copy(), ra.us.cpu().numpy().copy()
     Aa = ra.alpha_hist.cpu().numpy().copy()
     rs = _fit(solver, x0_q, x0_xi, us0, K, "split")
-    o = ob.fit_batch(_oracle_problem(prob), x0_q, x0_xi, us0, mode="ms", max_iter=K, line_search=True)
+    o = ob.fit_batch(oracle_problem(prob), x0_q, x0_xi, us0, mode="ms", max_iter=K, line_search=True)
     _same_search(ia, Ja, Aa, rs.iters.cpu().numpy(), rs.J_hist.cpu().numpy(), rs.alpha_hist.cpu().numpy(), 1e-10,
                  "ring form + hand-back vs statement form")
     same = _same_search(ia, Ja, None, o["iters"], o["J_hist"], None, 1e-8, "ring form + hand-back vs oracle")
-    assert _rel(ua[same], o["us"][same]) < 1e-6
+    assert rel(ua[same], o["us"][same]) < 1e-6
 
 
 @pytest.mark.parametrize("mode,line_search", [("ss", False), ("ms", True)])
@@ -200,7 +130,7 @@ def test_al_terms_in_both_forms_and_in_the_staged_search(kind):
     merit search with the ring form against one with the statement form (and single shooting, which has only the
     staged evaluation to differ in, against itself through both schedules)."""
     B, N, K = 6, 45, 5
-    prob, x0_q, x0_xi, us0 = _problem(kind, B, N)
+    prob, x0_q, x0_xi, us0 = problem_of_kind(kind, B, N)
     m = prob.m
     dev = torch.device("cuda")
     rng = np.random.default_rng(2)
@@ -208,7 +138,7 @@ def test_al_terms_in_both_forms_and_in_the_staged_search(kind):
     imu = torch.tensor(rng.uniform(0.5, 3.0, size=(B, N, 2 * m)), dtype=torch.float64, device=dev)
     solver = BatchedTrackingILQR(prob, B)
     solver.set_al(-0.4 * np.ones(m), 0.4 * np.ones(m), lam, imu)
-    xs_q, xs_xi, us = _random_traj(prob, B, seed=9, spread=0.05)
+    xs_q, xs_xi, us = random_traj_embedded(prob, B, seed=9, spread=0.05)
     solver.linearize_backward(xs_q, xs_xi, us, ms=True)
     es, _ = solver.expected_change(B, "statement")
     er, flag = solver.expected_change(B, "ring")

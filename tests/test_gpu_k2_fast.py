@@ -14,11 +14,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import bridge as ob  # noqa: E402  (test infrastructure)
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, workloads  # noqa: E402
-
-
-def _rel(a, b):
-    a = np.nan_to_num(np.asarray(a)); b = np.nan_to_num(np.asarray(b))
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+from tests.support import rel_nan0  # noqa: E402
 
 
 def _fit(prob, x0_q, x0_xi, us0, K, full_only, **kw):
@@ -38,9 +34,9 @@ def _fit(prob, x0_q, x0_xi, us0, K, full_only, **kw):
 def _same(ra, rb, tol=1e-11):
     assert torch.equal(ra.iters, rb.iters) and torch.equal(ra.status, rb.status)
     assert np.array_equal(np.isnan(ra.J_hist.cpu().numpy()), np.isnan(rb.J_hist.cpu().numpy()))
-    assert _rel(ra.J_hist.cpu().numpy(), rb.J_hist.cpu().numpy()) < tol
+    assert rel_nan0(ra.J_hist.cpu().numpy(), rb.J_hist.cpu().numpy()) < tol
     assert np.array_equal(np.nan_to_num(ra.mu_hist.cpu().numpy()), np.nan_to_num(rb.mu_hist.cpu().numpy()))
-    assert _rel(ra.us.cpu().numpy(), rb.us.cpu().numpy()) < 1e-9
+    assert rel_nan0(ra.us.cpu().numpy(), rb.us.cpu().numpy()) < 1e-9
 
 
 @pytest.mark.parametrize("kind,mode,B,N", [("se3", "ms", 37, 45), ("drone", "ms", 10, 60), ("se3", "ss", 9, 30), ("so3", "ms", 5, 40)])
@@ -54,7 +50,7 @@ def test_fast_and_full_sweeps_agree_on_tame_problems(kind, mode, B, N):
         o = ob.fit_batch(ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref), x0_q, x0_xi, us0,
                          mode=mode, max_iter=6)
         n = int(min(o["iters"].min(), ra.iters.min().item()))
-        assert _rel(ra.J_hist.cpu().numpy()[:, :n], o["J_hist"][:, :n]) < 1e-9
+        assert rel_nan0(ra.J_hist.cpu().numpy()[:, :n], o["J_hist"][:, :n]) < 1e-9
 
 
 def test_sweeps_that_keep_needing_the_general_path():
@@ -71,7 +67,7 @@ def test_sweeps_that_keep_needing_the_general_path():
                      mode="ms", max_iter=5)
     ok = np.isfinite(o["J_hist"]).all(axis=1) & (np.abs(o["J_hist"]).max(axis=1) < 1e12)
     assert ok.any()
-    assert _rel(ra.J_hist.cpu().numpy()[ok], o["J_hist"][ok]) < 1e-8
+    assert rel_nan0(ra.J_hist.cpu().numpy()[ok], o["J_hist"][ok]) < 1e-8
 
 
 def test_groups_of_four_that_mix_both_kinds():

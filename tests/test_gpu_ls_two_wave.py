@@ -17,11 +17,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import bridge as ob  # noqa: E402  (test infrastructure)
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, workloads  # noqa: E402
-
-
-def _rel(a, b):
-    a = np.nan_to_num(np.asarray(a)); b = np.nan_to_num(np.asarray(b))
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+from tests.support import rel_nan0  # noqa: E402
 
 
 def _fit(prob, x0_q, x0_xi, us0, K, onewave, **kw):
@@ -49,7 +45,7 @@ def _same(ra, rb, tol=1e-10):
     K = Ja.shape[1]
     mask = np.arange(K)[None, :] < n[:, None]
     assert np.array_equal(np.isnan(Ja) & mask, np.isnan(Jb) & mask)
-    assert _rel(np.where(mask, Ja, 0.0), np.where(mask, Jb, 0.0)) < tol
+    assert rel_nan0(np.where(mask, Ja, 0.0), np.where(mask, Jb, 0.0)) < tol
     # the step sizes of the common iterations that still moved the cost (at the floor the accepted step size is a coin flip too)
     fork = (ia != ib) | (sa != sb)
     with np.errstate(all="ignore"):
@@ -63,8 +59,8 @@ def _same(ra, rb, tol=1e-10):
         assert abs(Ja[b, k - 1] - Ja[b, k - 2]) <= 1e-11 * abs(Ja[b, k - 1]), (b, ia[b], ib[b], Ja[b, :k])
     assert fork.mean() <= 0.25
     ok = ~fork
-    assert _rel(ra.us.cpu().numpy()[ok], rb.us.cpu().numpy()[ok]) < 1e-8
-    assert _rel(ra.xs_q.cpu().numpy()[ok], rb.xs_q.cpu().numpy()[ok]) < 1e-8
+    assert rel_nan0(ra.us.cpu().numpy()[ok], rb.us.cpu().numpy()[ok]) < 1e-8
+    assert rel_nan0(ra.xs_q.cpu().numpy()[ok], rb.xs_q.cpu().numpy()[ok]) < 1e-8
 
 
 def _oracle(prob, x0_q, x0_xi, us0, K, mode):
@@ -83,7 +79,7 @@ def test_two_wave_rollouts_agree_with_the_one_wave_forms(kind, mode, B, N, K):
     o = _oracle(prob, x0_q, x0_xi, us0, K, mode)
     n = int(min(o["iters"].min(), ra.iters.min().item()))
     assert n >= 1
-    assert _rel(ra.J_hist.cpu().numpy()[:, :n], o["J_hist"][:, :n]) < 1e-9
+    assert rel_nan0(ra.J_hist.cpu().numpy()[:, :n], o["J_hist"][:, :n]) < 1e-9
     same_exit = (ra.iters.cpu().numpy() == o["iters"]) & (ra.status.cpu().numpy() == o["status"])
     assert same_exit.mean() > 0.9
 
@@ -128,7 +124,7 @@ def test_dense_inertia():
     _same(ra, rb)
     o = _oracle(pd, x0_q, x0_xi, us0, K, "ms")
     n = int(min(o["iters"].min(), ra.iters.min().item()))
-    assert _rel(ra.J_hist.cpu().numpy()[:, :n], o["J_hist"][:, :n]) < 1e-9
+    assert rel_nan0(ra.J_hist.cpu().numpy()[:, :n], o["J_hist"][:, :n]) < 1e-9
 
 
 @pytest.mark.parametrize("mode", ["ms", "ss"])

@@ -15,26 +15,11 @@ import torch
 
 from oracle import bridge as ob
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, _capi, workloads
-from trajectory_optimization_matrix_lie_groups_amd.solver import mpc_shift, mpc_window_index
-from tests.test_gpu_policy import MODELS, _case, _op
-from tests.test_mpc_cpu import restate_mpc_step, window_problem
+from trajectory_optimization_matrix_lie_groups_amd.solver import mpc_window_index
+from tests.checks import check_advance, check_loop
+from tests.support import MODELS, ZERO, host, model_case, op_of, rel, same
 
 pytestmark = pytest.mark.gpu
-
-ZERO = dict(tol_grad_norm=0.0, tol_d_norm=0.0)
-
-
-def _h(t):
-    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-
-
-def _rel(a, b):
-    a = np.asarray(a); b = np.asarray(b)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
-
-
-def _same(a, b):
-    return np.array_equal(_h(a), _h(b), equal_nan=True)
 
 
 def _ref_guess(prob, q, xi, q_ref=None, xi_ref=None):
@@ -65,7 +50,7 @@ def test_warm_begin_from_the_reference_is_begin(kw, refs):
     a = {f: getattr(a, f).clone() for f in ("J_hist", "grad_hist", "defect_hist", "xs_q", "xs_xi", "us", "iters", "status")}
     b = s.fit_batch(q, xi, us, mode="ms", n_iterations=8, check_every=0, q_ref=q_ref, xi_ref=xi_ref, xs_init=xs, **ZERO, **kw)
     for f in a:
-        assert _same(a[f], getattr(b, f)), f
+        assert same(a[f], getattr(b, f)), f
 
 
 # 2 -------------------------------------------------------------------------------------------------------------------
@@ -73,7 +58,7 @@ def _converged(B, N=40):
     prob, q, xi, us = workloads.se3_tracking(B, N=N)
     s = BatchedTrackingILQR(prob, B)
     r = s.fit_batch(q, xi, us, mode="ms", n_iterations=300, tol_grad_norm=1e-6, tol_d_norm=1e-6)
-    c = np.flatnonzero(_h(r.converged))
+    c = np.flatnonzero(host(r.converged))
     assert len(c) >= 2
     return prob, s, r.xs_q[c].clone(), r.xs_xi[c].clone(), r.us[c].clone()
 
@@ -83,13 +68,13 @@ def test_warm_begin_from_a_converged_solution_starts_where_it_is_and_stops():
     B = xq.shape[0]
     s = BatchedTrackingILQR(prob, B)
     lb = s.linearize_backward(xq, xx, uu, ms=True)
-    lb = {k: _h(lb[k]).copy() for k in ("dnorm", "grad")}
+    lb = {k: host(lb[k]).copy() for k in ("dnorm", "grad")}
     w = s.fit_batch(xq[:, 0], xx[:, 0], uu, mode="ms", n_iterations=10, tol_grad_norm=1e-6, tol_d_norm=1e-6, check_every=1,
                     xs_init=(xq, xx))
-    assert _rel(_h(w.defect_hist)[:, 0], lb["dnorm"]) < 1e-12
-    assert _rel(_h(w.grad_hist)[:, 0], lb["grad"]) < 1e-12
-    assert _h(w.converged).all() and (_h(w.iters) <= 1).all(), (_h(w.converged), _h(w.iters))
-    assert _rel(_h(w.xs_q), _h(xq)) < 1e-12 and _rel(_h(w.xs_xi), _h(xx)) < 1e-12 and _rel(_h(w.us), _h(uu)) < 1e-12
+    assert rel(host(w.defect_hist)[:, 0], lb["dnorm"]) < 1e-12
+    assert rel(host(w.grad_hist)[:, 0], lb["grad"]) < 1e-12
+    assert host(w.converged).all() and (host(w.iters) <= 1).all(), (host(w.converged), host(w.iters))
+    assert rel(host(w.xs_q), host(xq)) < 1e-12 and rel(host(w.xs_xi), host(xx)) < 1e-12 and rel(host(w.us), host(uu)) < 1e-12
 
 
 def test_warm_begin_from_perturbed_states_starts_where_linearize_backward_says():
@@ -97,16 +82,16 @@ def test_warm_begin_from_perturbed_states_starts_where_linearize_backward_says()
     B = xq.shape[0]
     s = BatchedTrackingILQR(prob, B)
     rng = np.random.default_rng(7)
-    pq, px = _h(xq).copy(), _h(xx).copy()
+    pq, px = host(xq).copy(), host(xx).copy()
     for b in range(B):
         for i in range(1, prob.N + 1):
             pq[b, i] = pq[b, i] @ ob.se3_exp(rng.normal(0, 0.02, 6))
     px[:, 1:] += rng.normal(0, 0.02, px[:, 1:].shape)
     lb = s.linearize_backward(pq, px, uu, ms=True)
-    lb = {k: _h(lb[k]).copy() for k in ("dnorm", "grad")}
+    lb = {k: host(lb[k]).copy() for k in ("dnorm", "grad")}
     w = s.fit_batch(pq[:, 0], px[:, 0], uu, mode="ms", n_iterations=1, check_every=0, xs_init=(pq, px), **ZERO)
-    assert _rel(_h(w.defect_hist)[:, 0], lb["dnorm"]) < 1e-12
-    assert _rel(_h(w.grad_hist)[:, 0], lb["grad"]) < 1e-12
+    assert rel(host(w.defect_hist)[:, 0], lb["dnorm"]) < 1e-12
+    assert rel(host(w.grad_hist)[:, 0], lb["grad"]) < 1e-12
 
 
 # 3 -------------------------------------------------------------------------------------------------------------------
@@ -124,7 +109,7 @@ def test_windows_are_set_refs_on_host_slices(T):
         a = s._refs_buf[:n].clone()
         idx = mpc_window_index(t0, t, N, T)
         s._use_refs(B, (pq[np.arange(B)[:, None], idx], px[np.arange(B)[:, None], idx]))
-        assert _same(a, s._refs_buf[:n]), t
+        assert same(a, s._refs_buf[:n]), t
     # a solve on the windows: the bits of fit_batch on the host-sliced windows
     got = {}
     r = s.mpc(q, xi, pq, px, 1, t0=t0, first_iters=6, warm="controls", check_every=0, **ZERO,
@@ -133,49 +118,23 @@ def test_windows_are_set_refs_on_host_slices(T):
     f = s.fit_batch(q, xi, None, mode="ms", n_iterations=6, check_every=0, q_ref=pq[np.arange(B)[:, None], idx],
                     xi_ref=px[np.arange(B)[:, None], idx], **ZERO)
     for k in got:
-        assert _same(got[k], getattr(f, k)), k
-    assert _same(r.us[:, 0], f.us[:, 0])
+        assert same(got[k], getattr(f, k)), k
+    assert same(r.us[:, 0], f.us[:, 0])
 
 
 # 4 -------------------------------------------------------------------------------------------------------------------
-def _check_advance(s, r, ops, w):
-    B, N = r.us.shape[0], s.N
-    J1 = torch.zeros(B, dtype=torch.float64, device=s.device)
-    a = s.mpc_advance(w, J_cl=J1)
-    xq, xx, uu = _h(r.xs_q), _h(r.xs_xi), _h(r.us)
-    fin = [b for b in range(B) if np.isfinite(xq[b]).all() and np.isfinite(xx[b]).all() and np.isfinite(uu[b]).all()]
-    assert len(fin) >= B // 2
-    for b in fin:
-        op = ops[b]
-        q1, x1 = ob.f(op, xq[b, 0], xx[b, 0], uu[b, 0])
-        assert _rel(_h(a["x_next_q"])[b], q1) < 1e-13 and _rel(_h(a["x_next_xi"])[b], x1 + w[b]) < 1e-13
-        qN, xN = ob.f(op, xq[b, N], xx[b, N], uu[b, N - 1])
-        assert _rel(_h(a["xs_q"])[b, N], qN) < 1e-13 and _rel(_h(a["xs_xi"])[b, N], xN) < 1e-13
-        assert abs(_h(J1)[b] / ob.cost(op, xq[b, 0], xx[b, 0], uu[b, 0], 0)[0] - 1) < 1e-12
-    # the shift: bitwise the host shift of solve_end's output
-    sq, su = mpc_shift(xq, uu, _h(a["x_next_q"]), _h(a["xs_q"])[:, N])
-    sx, _ = mpc_shift(xx, uu, _h(a["x_next_xi"]), _h(a["xs_xi"])[:, N])
-    for k, host in (("xs_q", sq), ("xs_xi", sx), ("us", su)):
-        diff = ~np.equal(_h(a[k]), host) & ~(np.isnan(_h(a[k])) & np.isnan(host))
-        assert not diff.any(), (k, sorted(set(zip(*np.nonzero(diff)[:2])))[:10])
-    assert _same(a["u"], uu[:, 0])
-    # twice: the same bits, the policy untouched (J_cl accumulates)
-    b2 = s.mpc_advance(w, J_cl=J1)
-    for k in ("x_next_q", "x_next_xi", "u", "xs_q", "xs_xi", "us"):
-        assert _same(a[k], b2[k]), k
-    assert _rel(_h(J1)[fin], 2 * np.array([ob.cost(ops[b], xq[b, 0], xx[b, 0], uu[b, 0], 0)[0] for b in fin])) < 1e-12
 
 
 @pytest.mark.parametrize("model", MODELS)
 def test_advance_against_the_oracle(model):
     B = 5
-    prob, q, xi, us = _case(model, B)
+    prob, q, xi, us = model_case(model, B)
     s = BatchedTrackingILQR(prob, B)
     r = s.fit_batch(q, xi, us, mode="ms", n_iterations=8, **ZERO)
     w = np.random.default_rng(3).normal(0, 0.01, (B, 6))
     if model in ("so3", "pendulum"):
         w[:, 3:] = 0.0  # the embedding's linear twist stays zero
-    _check_advance(s, r, [_op(prob)] * B, w)
+    check_advance(s, r, [op_of(prob)] * B, w)
 
 
 def test_advance_with_references_and_weights_per_trajectory():
@@ -185,7 +144,7 @@ def test_advance_with_references_and_weights_per_trajectory():
     s = BatchedTrackingILQR(prob, B)
     r = s.fit_batch(q, xi, us, mode="ss", n_iterations=6, q_ref=q_ref, xi_ref=xi_ref, Q=Q, P=P, R=R, **ZERO)
     w = np.random.default_rng(4).normal(0, 0.01, (B, 6))
-    _check_advance(s, r, [_op(prob, q_ref[b], xi_ref[b], Q[b], R[b], P[b]) for b in range(B)], w)
+    check_advance(s, r, [op_of(prob, q_ref[b], xi_ref[b], Q[b], R[b], P[b]) for b in range(B)], w)
 
 
 # 5 -------------------------------------------------------------------------------------------------------------------
@@ -193,40 +152,10 @@ def test_loop_against_the_oracle_step_by_step():
     check_loop(B=8, N=40, steps=6, K0=10, K=3)
 
 
-def check_loop(B, N, steps, K0, K):
-    """mpc() on se3_mpc's paths against restate_mpc_step, step by step: every window's solve, the applied input, the
-    closed-loop state and cost."""
-    prob, q, xi, pq, px, t0, noise = workloads.se3_mpc(B, steps, N=N, sigma_noise=0.02, seed=21)
-    s = BatchedTrackingILQR(prob, B)
-    seen = []
-    r = s.mpc(q, xi, pq, px, steps, t0=t0, first_iters=K0, iters_per_step=K, warm="controls", noise=noise, check_every=0,
-              **ZERO, on_step=lambda t, out: seen.append((t, _h(out.xs_q).copy(), _h(out.xs_xi).copy(), _h(out.us).copy(),
-                                                  _h(out.J_hist).copy())))
-    assert [t for t, *_ in seen] == list(range(steps))
-    rq, rx, ru, J = _h(r.xs_q), _h(r.xs_xi), _h(r.us), _h(r.J)
-    assert np.array_equal(rq[:, 0], q) and np.array_equal(rx[:, 0], xi)
-    Jcl = np.zeros(B)
-    for t, xs_q, xs_xi, us, Jh in seen:
-        us_in = np.zeros((B, N, prob.m)) if t == 0 else mpc_shift(seen[t - 1][1], seen[t - 1][3], rq[:, t], rq[:, t])[1]
-        assert np.array_equal(ru[:, t], us[:, 0])  # the applied input is the step's u*_0
-        for b in range(B):
-            op = window_problem(prob, pq[b], px[b], int(t0[b]), t)
-            o = restate_mpc_step(op, rq[b, t], rx[b, t], us_in[b], K0 if t == 0 else K)
-            assert np.abs(Jh[b] / o["J_hist"] - 1).max() < 1e-9, (t, b)
-            assert np.abs(us[b] - o["us"]).max() / np.abs(o["us"]).max() < 1e-6, (t, b)
-            # the closed-loop state is the advance's x_next: f(x*_0, u*_0) + noise
-            q1, x1 = ob.f(op, xs_q[b, 0], xs_xi[b, 0], us[b, 0])
-            assert _rel(rq[b, t + 1], q1) < 1e-13 and _rel(rx[b, t + 1], x1 + noise[b, t]) < 1e-13
-            Jcl[b] += ob.cost(op, xs_q[b, 0], xs_xi[b, 0], us[b, 0], 0)[0]
-    assert _rel(J, Jcl) < 1e-12
-    assert (_h(r.status) == _capi.ST_OK).all()
-    assert (_h(r.iters)[:, 0] == K0).all() and (_h(r.iters)[:, 1:] == K).all()
-
-
 # 6 -------------------------------------------------------------------------------------------------------------------
 def _feasible_paths(prob, B, T, seed=9):
     """Open-loop rollouts of the model under smooth inputs: dynamically feasible paths [B, T+1]."""
-    op = _op(prob)
+    op = op_of(prob)
     rng = np.random.default_rng(seed)
     pq = np.zeros((B, T + 1, 4, 4)); px = np.zeros((B, T + 1, 6))
     for b in range(B):
@@ -248,14 +177,14 @@ def test_warm_states_on_a_feasible_path_converge_in_a_few_iterations_and_track()
     s = BatchedTrackingILQR(prob, B)
     conv = []
     r = s.mpc(pq[:, 0], px[:, 0], pq, px, steps, first_iters=50, iters_per_step=K, warm="states", check_every=1,
-              on_step=lambda t, out: conv.append(_h(out.converged).copy()), **tol)
-    st, it = _h(r.status), _h(r.iters)
+              on_step=lambda t, out: conv.append(host(out.converged).copy()), **tol)
+    st, it = host(r.status), host(r.iters)
     assert (st == _capi.ST_OK).all()
     assert all(c.all() for c in conv[1:]) and (it[:, 1:] <= K).all()
     # one full-horizon solve on the same path: its largest pose error sets the scale
     f = s.fit_batch(pq[:, 0], px[:, 0], None, mode="ms", n_iterations=100, q_ref=pq[:, :N + 1], xi_ref=px[:, :N + 1], **tol)
-    e_full = np.linalg.norm(_h(f.xs_q)[:, :, :3, 3] - pq[:, :N + 1, :3, 3], axis=-1).max()
-    e_cl = np.linalg.norm(_h(r.xs_q)[:, :, :3, 3] - pq[:, :steps + 1, :3, 3], axis=-1).max()
+    e_full = np.linalg.norm(host(f.xs_q)[:, :, :3, 3] - pq[:, :N + 1, :3, 3], axis=-1).max()
+    e_cl = np.linalg.norm(host(r.xs_q)[:, :, :3, 3] - pq[:, :steps + 1, :3, 3], axis=-1).max()
     assert e_full > 0 and e_cl <= 10 * e_full + 1e-9, (e_cl, e_full)
 
 
@@ -318,7 +247,7 @@ def test_argument_rules():
     s.solve_iterate(1)
     e = s.solve_end()
     f = BatchedTrackingILQR(prob, B).fit_batch(q[:B - 1], xi[:B - 1], None, mode="ms", n_iterations=1, check_every=0, **ZERO)
-    assert _same(e.xs_q, f.xs_q) and _same(e.us, f.us)
+    assert same(e.xs_q, f.xs_q) and same(e.us, f.us)
     # set_ref_windows: bad arguments
     for a in [(pq, px, -1), (pq[:, :1], px[:, :1], 0), (pq, px[:, :-1], 0)]:
         with pytest.raises(ValueError):
@@ -331,6 +260,6 @@ def test_full_size():
     prob, q, xi, pq, px, t0, noise = workloads.se3_mpc(B, steps, N=N)
     s = BatchedTrackingILQR(prob, B)
     r = s.mpc(q, xi, pq, px, steps, t0=t0, first_iters=20, iters_per_step=3, warm="states", noise=noise, check_every=0, **ZERO)
-    assert (_h(r.status) == _capi.ST_OK).all()
+    assert (host(r.status) == _capi.ST_OK).all()
     for f in ("xs_q", "xs_xi", "us", "J"):
-        assert np.isfinite(_h(getattr(r, f))).all(), f
+        assert np.isfinite(host(getattr(r, f))).all(), f

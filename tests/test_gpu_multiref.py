@@ -12,117 +12,42 @@ import pytest
 import torch
 
 from oracle import bridge as ob
-from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, _capi, workloads
-from tests.test_gpu_parity import _oracle_problem, _rel
+from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, _capi, workloads
+from tests.support import B13, BROADCAST, MODES, assert_bitwise, bits, broadcast, case_b13, near, oracle_problem, rel, with_ref
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = ("xs_q", "xs_xi", "us", "J_hist", "grad_hist", "defect_hist", "alpha_hist", "mu_hist", "iters", "status",
-          "converged")
-
-
-def _bits(t):
-    t = t.detach().contiguous()
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
-def _assert_bitwise(a, b, rows_a=slice(None), rows_b=slice(None), what=""):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(b, name)
-        if x is None and y is None:
-            continue
-        assert torch.equal(_bits(x[rows_a]), _bits(y[rows_b])), "%s %s differs" % (what, name)
-
-
-def _with_ref(prob, q_ref, xi_ref):
-    return TrackingProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, q_ref, xi_ref, prob.pend_mass,
-                           prob.pend_length)
-
-
-def _broadcast(prob, B):
-    return (np.broadcast_to(prob.q_ref, (B,) + prob.q_ref.shape).copy(),
-            np.broadcast_to(prob.xi_ref, (B,) + prob.xi_ref.shape).copy())
-
-
-def _dense(prob):
-    J = prob.J.copy()
-    J[:3, :3] = np.array([[0.5, 0.05, 0.02], [0.05, 0.7, 0.03], [0.02, 0.03, 0.9]])
-    return TrackingProblem(prob.kind, J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
-
-
-B13 = 13  # not a multiple of four: the padded lanes replicate trajectory 12
-
-
-def _case(name):
-    if name == "drone":
-        prob, q, xi, us = workloads.drone_tracking(B13, N=400)
-    elif name == "so3":
-        prob, q, xi, us = workloads.so3_tracking(B13, N=100)
-    elif name == "pendulum":
-        prob, q, xi, us = workloads.pendulum_swingup(B13)
-    else:
-        prob, q, xi, us = workloads.se3_tracking(B13, N=200)
-        if name == "dense":
-            prob = _dense(prob)
-    return prob, q, xi, us
-
-
-# (case, fit_batch keywords)
-BROADCAST = [
-    ("se3", dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0, schedule="auto")),
-    ("se3", dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0, schedule="split")),
-    ("se3", dict(mode="ms", n_iterations=25, line_search=True)),
-    ("se3", dict(mode="ss", n_iterations=25)),
-    ("se3", dict(mode="ms", n_iterations=25, line_search=True, rollout="linear")),
-    ("se3", dict(mode="ss", n_iterations=25, rollout="linear")),
-    ("drone", dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0)),
-    ("drone", dict(mode="ms", n_iterations=25, line_search=True)),
-    ("so3", dict(mode="ms", n_iterations=25, line_search=True)),
-    ("so3", dict(mode="ss", n_iterations=25)),
-    ("pendulum", dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0)),
-    ("pendulum", dict(mode="ms", n_iterations=25, line_search=True)),
-    ("dense", dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0)),
-    ("dense", dict(mode="ss", n_iterations=25)),
-]
 
 
 @pytest.mark.parametrize("case,kw", BROADCAST, ids=["%s-%d" % (c, i) for i, (c, _) in enumerate(BROADCAST)])
 def test_broadcast_reference_is_bitwise_the_shared_one(case, kw):
-    prob, q, xi, us = _case(case)
+    prob, q, xi, us = case_b13(case)
     r0 = BatchedTrackingILQR(prob, B13).fit_batch(q, xi, us, **kw)
-    qr, xr = _broadcast(prob, B13)
+    qr, xr = broadcast(prob, B13)
     r1 = BatchedTrackingILQR(prob, B13).fit_batch(q, xi, us, q_ref=qr, xi_ref=xr, **kw)
     torch.cuda.synchronize()
-    _assert_bitwise(r0, r1, what=case)
+    assert_bitwise(r0, r1, what=case)
 
 
 def test_broadcast_reference_one_call_entry_point():
-    prob, q, xi, us = _case("se3")
+    prob, q, xi, us = case_b13("se3")
     kw = dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0)
     r0 = BatchedTrackingILQR(prob, B13).solve_batch_one_call(q, xi, us, **kw)
-    qr, xr = _broadcast(prob, B13)
+    qr, xr = broadcast(prob, B13)
     r1 = BatchedTrackingILQR(prob, B13).solve_batch_one_call(q, xi, us, q_ref=qr, xi_ref=xr, **kw)
-    _assert_bitwise(r0, r1)
+    assert_bitwise(r0, r1)
 
 
 def test_broadcast_reference_al():
     prob, q, xi, us, lb, ub = workloads.al_tracking(B13, N=200)
     kw = dict(n_al_iters=4, n_ilqr_iters=30)
     r0, i0 = BatchedTrackingILQR(prob, B13).al_fit_batch(q, xi, us, lb, ub, **kw)
-    qr, xr = _broadcast(prob, B13)
+    qr, xr = broadcast(prob, B13)
     r1, i1 = BatchedTrackingILQR(prob, B13).al_fit_batch(q, xi, us, lb, ub, q_ref=qr, xi_ref=xr, **kw)
     torch.cuda.synchronize()
-    _assert_bitwise(r0, r1)
+    assert_bitwise(r0, r1)
     for k in ("lmbd", "Imu", "mu", "max_violation"):
-        assert torch.equal(_bits(i0[k]), _bits(i1[k])), k
+        assert torch.equal(bits(i0[k]), bits(i1[k])), k
     assert i0["outer_iterations"] == i1["outer_iterations"]
-
-
-MODES = {
-    "ms": dict(mode="ms", n_iterations=15, tol_grad_norm=0.0, tol_d_norm=0.0),
-    "merit": dict(mode="ms", n_iterations=25, line_search=True),
-    "ss": dict(mode="ss", n_iterations=25),
-}
 
 
 @pytest.mark.parametrize("mode", list(MODES))
@@ -134,10 +59,10 @@ def test_grouped_references_match_one_handle_per_reference(mode):
     r = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, q_ref=q_ref, xi_ref=xi_ref, **kw)
     for g in range(R):
         rows = slice(4 * g, 4 * g + 4)
-        pg = _with_ref(prob, q_ref[4 * g], xi_ref[4 * g])
+        pg = with_ref(prob, q_ref[4 * g], xi_ref[4 * g])
         rg = BatchedTrackingILQR(pg, 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
         torch.cuda.synchronize()
-        _assert_bitwise(r, rg, rows_a=rows, what="reference %d" % g)
+        assert_bitwise(r, rg, rows_a=rows, what="reference %d" % g)
 
 
 @pytest.mark.parametrize("mode", list(MODES))
@@ -152,18 +77,11 @@ def test_interleaved_references_match_the_oracle(mode):
     okw = dict(mode=kw["mode"], max_iter=K, tol_grad=kw.get("tol_grad_norm", 1e-6), tol_defect=kw.get("tol_d_norm", 1e-6),
                line_search=kw.get("line_search", False))
     for b in range(B):
-        o = ob.fit(_oracle_problem(_with_ref(prob, q_ref[b], xi_ref[b])), q[b], xi[b], us[b], **okw)
+        o = ob.fit(oracle_problem(with_ref(prob, q_ref[b], xi_ref[b])), q[b], xi[b], us[b], **okw)
         n = int(r.iters[b])
         assert n == o["n_iters"] and int(r.status[b]) == o["status"], b
-        assert _rel(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
-        assert _rel(r.us[b].cpu(), o["us"]) < 1e-6, b
-
-
-def _near(q_ref, xi_ref, rng, spread=0.3):
-    xs_q = np.empty_like(q_ref)
-    for i in range(q_ref.shape[0]):
-        xs_q[i] = q_ref[i] @ ob.se3_exp(rng.normal(size=6) * spread)
-    return xs_q, xi_ref + rng.normal(size=xi_ref.shape) * spread
+        assert rel(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
+        assert rel(r.us[b].cpu(), o["us"]) < 1e-6, b
 
 
 @pytest.mark.parametrize("ms", [True, False])
@@ -175,18 +93,18 @@ def test_linearize_backward_per_trajectory_reference(ms):
     rng = np.random.default_rng(7)
     xs_q = np.empty((B, N + 1, 4, 4)); xs_xi = np.empty((B, N + 1, 6))
     for b in range(B):
-        xs_q[b], xs_xi[b] = _near(q_ref[b], xi_ref[b], rng)
+        xs_q[b], xs_xi[b] = near(q_ref[b], xi_ref[b], rng)
     us = rng.normal(size=(B, N, 6))
     r = BatchedTrackingILQR(prob, B).linearize_backward(xs_q, xs_xi, us, ms=ms, q_ref=q_ref, xi_ref=xi_ref)
     torch.cuda.synchronize()
     for b in range(B):
-        o = ob.lin_backward(_oracle_problem(_with_ref(prob, q_ref[b], xi_ref[b])), xs_q[b], xs_xi[b], us[b], ms=ms)
-        assert _rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
-        assert _rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
-        assert _rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
+        o = ob.lin_backward(oracle_problem(with_ref(prob, q_ref[b], xi_ref[b])), xs_q[b], xs_xi[b], us[b], ms=ms)
+        assert rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
+        assert rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
+        assert rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
         assert float(r["J"][b]) == pytest.approx(o["J"], rel=1e-12)
-        assert _rel(r["K"][b].cpu(), o["K"]) < 1e-8
-        assert _rel(r["k"][b].cpu(), o["k"]) < 1e-8
+        assert rel(r["K"][b].cpu(), o["K"]) < 1e-8
+        assert rel(r["k"][b].cpu(), o["k"]) < 1e-8
 
 
 def test_full_size_64_references():
@@ -206,9 +124,9 @@ def test_full_size_64_references():
     del solver
     for g0 in (0, 64 * 17 + 8, 64 * 40 + 28, 64 * 63 + 60):  # groups of four inside references 0, 17, 40, 63
         rows = slice(g0, g0 + 4)
-        rg = BatchedTrackingILQR(_with_ref(prob, q_ref[g0], xi_ref[g0]), 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
+        rg = BatchedTrackingILQR(with_ref(prob, q_ref[g0], xi_ref[g0]), 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
         torch.cuda.synchronize()
-        _assert_bitwise(r, rg, rows_a=rows, what="rows %d.." % g0)
+        assert_bitwise(r, rg, rows_a=rows, what="rows %d.." % g0)
 
 
 def test_state_returns_to_the_shared_reference():
@@ -223,7 +141,7 @@ def test_state_returns_to_the_shared_reference():
     # Python: a call without references is a shared-reference call, whatever came before
     again = s.fit_batch(q, xi, us, **kw)
     torch.cuda.synchronize()
-    _assert_bitwise(fresh, again, what="python")
+    assert_bitwise(fresh, again, what="python")
     # C ABI: tolg_set_refs(..., NULL) after references were set
     s.fit_batch(q, xi, us, q_ref=q_ref, xi_ref=xi_ref, **kw)
     torch.cuda.synchronize()
@@ -231,13 +149,13 @@ def test_state_returns_to_the_shared_reference():
     s._refs_set = False
     again = s.solve_batch_one_call(q, xi, us, **kw)
     fresh1 = BatchedTrackingILQR(prob, B).solve_batch_one_call(q, xi, us, **kw)
-    _assert_bitwise(fresh1, again, what="C")
+    assert_bitwise(fresh1, again, what="C")
     # and references set again after that give the bits of a fresh handle with references
     own2 = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, q_ref=q_ref, xi_ref=xi_ref, **kw)
     own3 = s.fit_batch(q, xi, us, q_ref=q_ref, xi_ref=xi_ref, **kw)
     torch.cuda.synchronize()
-    _assert_bitwise(own, own2)
-    _assert_bitwise(own, own3)
+    assert_bitwise(own, own2)
+    assert_bitwise(own, own3)
 
 
 def test_argument_errors():
@@ -308,4 +226,4 @@ def test_mirror_fit_batch_refs():
     direct = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, mode="ms", n_iterations=10, tol_grad_norm=ctl._default_tol,
                                                     q_ref=q_ref, xi_ref=xi_ref, **ctl._options())
     torch.cuda.synchronize()
-    _assert_bitwise(r, direct)
+    assert_bitwise(r, direct)

@@ -14,15 +14,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import bridge as ob  # noqa: E402  (test infrastructure)
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, workloads  # noqa: E402
-
-
-def _oracle_problem(p: TrackingProblem):
-    return ob.OracleProblem(p.kind, p.J, p.dt, p.Q, p.R, p.P, p.q_ref, p.xi_ref)
-
-
-def _rel(a, b):
-    a = np.asarray(a); b = np.asarray(b)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+from tests.checks import al_oracle, check_linearize_backward  # noqa: E402
+from tests.support import oracle_problem, random_traj, rel  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -31,39 +24,6 @@ def drone(golden_dir):
     log = json.load(open(os.path.join(golden_dir, "drone_n150_log.json")))
     prob = TrackingProblem("drone", g["J"], float(g["dt"]), g["Q"], g["R"], g["P"], g["q_ref"], g["xi_ref"])
     return g, log, prob
-
-
-def _random_traj(prob, B, seed, spread=0.3):
-    rng = np.random.default_rng(seed)
-    N, m = prob.N, prob.m
-    xs_q = np.empty((B, N + 1, 4, 4)); xs_xi = np.empty((B, N + 1, 6)); us = rng.normal(size=(B, N, m))
-    for b in range(B):
-        for i in range(N + 1):
-            xs_q[b, i] = prob.q_ref[i] @ ob.se3_exp(rng.normal(size=6) * spread)
-            xs_xi[b, i] = prob.xi_ref[i] + rng.normal(size=6) * spread
-    return xs_q, xs_xi, us
-
-
-def check_linearize_backward(prob, xs_q, xs_xi, us, ms, solver=None):
-    """K1 + K2 (tolg_linearize_backward) on the given trajectories against the oracle's _linearization/_backward_pass,
-    trajectory by trajectory; solver: a handle on prob (default: a fresh one of the batch's size)."""
-    B = xs_q.shape[0]
-    solver = BatchedTrackingILQR(prob, B) if solver is None else solver
-    r = solver.linearize_backward(xs_q, xs_xi, us, ms=ms)
-    torch.cuda.synchronize()
-    op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref,
-                          pend_mass=prob.pend_mass, pend_length=prob.pend_length)
-    for b in range(B):
-        o = ob.lin_backward(op, xs_q[b], xs_xi[b], us[b], ms=ms)
-        assert _rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
-        assert np.abs(r["d"][b].cpu().numpy() - o["d"]).max() < 1e-11 * max(1.0, np.abs(o["d"]).max())
-        assert _rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
-        assert _rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
-        assert float(r["J"][b]) == pytest.approx(o["J"], rel=1e-12)
-        assert _rel(r["K"][b].cpu(), o["K"]) < 1e-8
-        assert _rel(r["k"][b].cpu(), o["k"]) < 1e-8
-        assert float(r["grad"][b]) == pytest.approx(o["grad"], rel=1e-9)
-        assert float(r["mu_delta"][b, 0]) == o["mu"] and float(r["mu_delta"][b, 1]) == o["delta"]
 
 
 @pytest.mark.parametrize("kind", ["se3", "drone", "rigidbody"])
@@ -78,7 +38,7 @@ def test_linearize_backward_elementwise(kind, ms):
         if kind == "rigidbody":
             prob = TrackingProblem("rigidbody", prob.J, prob.dt, prob.Q, np.eye(6) * 1e-4, prob.P, prob.q_ref, prob.xi_ref)
     B = 5
-    xs_q, xs_xi, us = _random_traj(prob, B, seed=11)
+    xs_q, xs_xi, us = random_traj(prob, B, seed=11)
     check_linearize_backward(prob, xs_q, xs_xi, us, ms)
 
 
@@ -93,9 +53,9 @@ def test_full_inertia_block_general_path():
     prob = TrackingProblem("se3", J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
     solver = BatchedTrackingILQR(prob, 3)
     r = solver.fit_batch(x0_q, x0_xi, us0, mode="ms", n_iterations=8, tol_grad_norm=0.0, tol_d_norm=0.0)
-    o = ob.fit_batch(_oracle_problem(prob), x0_q, x0_xi, us0, mode="ms", max_iter=8)
-    assert _rel(r.J_hist.cpu(), o["J_hist"]) < 1e-9
-    assert _rel(r.us.cpu(), o["us"]) < 1e-6
+    o = ob.fit_batch(oracle_problem(prob), x0_q, x0_xi, us0, mode="ms", max_iter=8)
+    assert rel(r.J_hist.cpu(), o["J_hist"]) < 1e-9
+    assert rel(r.us.cpu(), o["us"]) < 1e-6
     # coupling blocks between rotation and translation are rejected, as the reference's G assumes
     Jbad = J.copy(); Jbad[0, 4] = Jbad[4, 0] = 0.01
     with pytest.raises(RuntimeError, match="bad argument"):
@@ -109,17 +69,17 @@ def test_regularisation_loop_nonpd_branch():
     R = np.diag([-30.0, 1e-3, 1e-3, -5.0, 1e-3, 1e-3])
     prob = TrackingProblem("se3", prob.J, prob.dt, prob.Q, R, prob.P, prob.q_ref, prob.xi_ref)
     B = 4
-    xs_q, xs_xi, us = _random_traj(prob, B, seed=5, spread=0.1)
+    xs_q, xs_xi, us = random_traj(prob, B, seed=5, spread=0.1)
     solver = BatchedTrackingILQR(prob, B)
     r = solver.linearize_backward(xs_q, xs_xi, us, ms=True)
-    op = _oracle_problem(prob)
+    op = oracle_problem(prob)
     fired = False
     for b in range(B):
         o = ob.lin_backward(op, xs_q[b], xs_xi[b], us[b], ms=True)
         fired |= o["mu"] > 1.0
         assert float(r["mu_delta"][b, 0]) == pytest.approx(o["mu"], rel=1e-15)
         assert float(r["mu_delta"][b, 1]) == pytest.approx(o["delta"], rel=1e-15)
-        assert _rel(r["K"][b].cpu(), o["K"]) < 1e-7
+        assert rel(r["K"][b].cpu(), o["K"]) < 1e-7
         assert float(r["grad"][b]) == pytest.approx(o["grad"], rel=1e-8)
     assert fired
 
@@ -144,10 +104,10 @@ def test_drone_ms_fit_reproduces_recorded_run(drone):
     # identical inputs -> bitwise identical outputs across the batch (no cross-talk, deterministic)
     assert torch.equal(r.us[0], r.us[1]) and torch.equal(r.xs_q[0], r.xs_q[2])
     # final trajectory against the oracle (north_star: <= 1e-6 relative)
-    o = ob.fit(_oracle_problem(prob), g["q0"], g["xi0"], g["us_init"], mode="ms", max_iter=200, tol_grad=1e-12)
-    assert _rel(r.us[0].cpu(), o["us"]) < 1e-6
-    assert _rel(r.xs_q[0].cpu(), o["xs_q"]) < 1e-6
-    assert _rel(r.xs_xi[0].cpu(), o["xs_xi"]) < 1e-6
+    o = ob.fit(oracle_problem(prob), g["q0"], g["xi0"], g["us_init"], mode="ms", max_iter=200, tol_grad=1e-12)
+    assert rel(r.us[0].cpu(), o["us"]) < 1e-6
+    assert rel(r.xs_q[0].cpu(), o["xs_q"]) < 1e-6
+    assert rel(r.xs_xi[0].cpu(), o["xs_xi"]) < 1e-6
 
 
 def test_se3_batch_matches_oracle_per_trajectory():
@@ -157,12 +117,12 @@ def test_se3_batch_matches_oracle_per_trajectory():
     solver = BatchedTrackingILQR(prob, B)
     K = 12
     r = solver.fit_batch(x0_q, x0_xi, us0, mode="ms", n_iterations=K, tol_grad_norm=0.0, tol_d_norm=0.0)
-    o = ob.fit_batch(_oracle_problem(prob), x0_q, x0_xi, us0, mode="ms", max_iter=K)
-    assert _rel(r.J_hist.cpu(), o["J_hist"]) < 1e-9
-    assert _rel(r.defect_hist.cpu()[:, 0], o["defect_hist"][:, 0]) < 1e-12
-    assert _rel(r.us.cpu(), o["us"]) < 1e-6
-    assert _rel(r.xs_q.cpu(), o["xs_q"]) < 1e-6
-    assert _rel(r.xs_xi.cpu(), o["xs_xi"]) < 1e-6
+    o = ob.fit_batch(oracle_problem(prob), x0_q, x0_xi, us0, mode="ms", max_iter=K)
+    assert rel(r.J_hist.cpu(), o["J_hist"]) < 1e-9
+    assert rel(r.defect_hist.cpu()[:, 0], o["defect_hist"][:, 0]) < 1e-12
+    assert rel(r.us.cpu(), o["us"]) < 1e-6
+    assert rel(r.xs_q.cpu(), o["xs_q"]) < 1e-6
+    assert rel(r.xs_xi.cpu(), o["xs_xi"]) < 1e-6
     assert (r.iters.cpu().numpy() == K).all()
 
 
@@ -172,7 +132,7 @@ def test_convergence_masks_freeze_finished_trajectories():
     prob, x0_q, x0_xi, us0 = workloads.se3_tracking(B, N=60, R_scale=1e-3)
     solver = BatchedTrackingILQR(prob, B)
     r = solver.fit_batch(x0_q, x0_xi, us0, mode="ms", n_iterations=60, tol_grad_norm=1e-7)
-    o = ob.fit_batch(_oracle_problem(prob), x0_q, x0_xi, us0, mode="ms", max_iter=60, tol_grad=1e-7, tol_defect=1e-6)
+    o = ob.fit_batch(oracle_problem(prob), x0_q, x0_xi, us0, mode="ms", max_iter=60, tol_grad=1e-7, tol_defect=1e-6)
     assert (r.converged.cpu().numpy() == 1).all()
     np.testing.assert_array_equal(r.iters.cpu().numpy(), o["iters"])
     # the closed defects must stay at rounding level for every later iteration (a quaternion
@@ -180,7 +140,7 @@ def test_convergence_masks_freeze_finished_trajectories():
     D = r.defect_hist.cpu().numpy()
     for b in range(B):
         assert np.nanmax(D[b, 1:]) < 1e-12
-    assert _rel(r.us.cpu(), o["us"]) < 1e-6
+    assert rel(r.us.cpu(), o["us"]) < 1e-6
 
 
 def test_full_size_properties_4096x200():
@@ -207,8 +167,8 @@ def test_full_size_properties_4096x200():
     rs = BatchedTrackingILQR(prob, len(sub)).fit_batch(x0_q[sub], x0_xi[sub], us0[sub], mode="ms", n_iterations=K,
                                                          tol_grad_norm=0.0, tol_d_norm=0.0)
     assert torch.equal(rs.us, us1[sub])
-    o = ob.fit_batch(_oracle_problem(prob), x0_q[sub], x0_xi[sub], us0[sub], mode="ms", max_iter=K)
-    assert _rel(rs.us.cpu(), o["us"]) < 1e-6
+    o = ob.fit_batch(oracle_problem(prob), x0_q[sub], x0_xi[sub], us0[sub], mode="ms", max_iter=K)
+    assert rel(rs.us.cpu(), o["us"]) < 1e-6
     # the MS nonlinear rollout closes the defects to rounding after the first iteration
     D = r1.defect_hist.cpu().numpy()
     assert (D[:, 0] > 1.0).all() and (D[:, 1:K + 1] < 1e-10).all()
@@ -233,8 +193,8 @@ def test_drone_ss_fit_reproduces_recorded_line_search(drone):
             assert G[b, k] == pytest.approx(it["grad"], rel=1e-9)
             assert J[b, k] == pytest.approx(it["cb_J"], rel=1e-11)
             assert A[b, k] == pytest.approx(it["cb_alpha"], rel=1e-14)
-    o = ob.fit(_oracle_problem(prob), g["q0"], g["xi0"], g["us_init"], mode="ss", max_iter=200, tol_grad=1e-12)
-    assert _rel(r.us[0].cpu(), o["us"]) < 1e-6 and _rel(r.xs_q[0].cpu(), o["xs_q"]) < 1e-6
+    o = ob.fit(oracle_problem(prob), g["q0"], g["xi0"], g["us_init"], mode="ss", max_iter=200, tol_grad=1e-12)
+    assert rel(r.us[0].cpu(), o["us"]) < 1e-6 and rel(r.xs_q[0].cpu(), o["xs_q"]) < 1e-6
 
 
 @pytest.mark.parametrize("mode,line_search,rollout", [("ss", False, "nonlinear"), ("ss", False, "linear"),
@@ -247,7 +207,7 @@ def test_line_search_and_linear_rollout_variants_match_oracle(mode, line_search,
     solver = BatchedTrackingILQR(prob, B)
     r = solver.fit_batch(x0_q, x0_xi, us0, mode=mode, n_iterations=K, tol_grad_norm=0.0, tol_d_norm=0.0,
                          line_search=line_search, rollout=rollout)
-    o = ob.fit_batch(_oracle_problem(prob), x0_q, x0_xi, us0, mode=mode, max_iter=K, line_search=line_search,
+    o = ob.fit_batch(oracle_problem(prob), x0_q, x0_xi, us0, mode=mode, max_iter=K, line_search=line_search,
                      rollout=rollout)
     it_g = r.iters.cpu().numpy()
     np.testing.assert_array_equal(it_g, o["iters"])
@@ -255,29 +215,9 @@ def test_line_search_and_linear_rollout_variants_match_oracle(mode, line_search,
     Jg = r.J_hist.cpu().numpy()
     for b in range(B):
         n = it_g[b]
-        assert _rel(Jg[b, :n], o["J_hist"][b, :n]) < 1e-8
-    assert _rel(r.us.cpu(), o["us"]) < 1e-6
-    assert _rel(r.xs_xi.cpu(), o["xs_xi"]) < 1e-6
-
-
-def _al_oracle(prob, x0_q, x0_xi, us0, lb, ub, n_al, n_ilqr, tol_constr, mu0=1e-2, mu_scale=10.0, mu_max=1e8):
-    """AL_iLQR_Tracking_SE3_MS.fit restated with the oracle as inner solver
-    (reference traoptlibrary/traopt_controller.py:3218-3293; the reference class itself does not
-    run at HEAD -- SURVEY App. C-Q7 -- so this is the specification: parity unpinned)."""
-    N, m = prob.N, prob.m
-    lam = np.zeros((N, 2 * m)); imu = np.full((N, 2 * m), mu0); mu = mu0
-    for it in range(n_al):
-        op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref,
-                              al=dict(lb=lb, ub=ub, lam=lam, imu=imu))
-        o = ob.fit(op, x0_q, x0_xi, us0, mode="ms", max_iter=n_ilqr, tol_grad=1e-6, tol_defect=1e-6)
-        g = np.concatenate([lb[None] - o["us"], o["us"] - ub[None]], axis=1)
-        if max(g.max(), 0.0) < tol_constr:
-            return o, lam, imu, mu, it + 1
-        mu_new = min(mu * mu_scale, mu_max)
-        lam_new = np.clip(lam + imu * g, 0.0, None)
-        imu = np.where((g < 0.0) & (lam_new == 0.0), 0.0, mu_new)
-        lam, mu = lam_new, mu_new
-    return o, lam, imu, mu, n_al
+        assert rel(Jg[b, :n], o["J_hist"][b, :n]) < 1e-8
+    assert rel(r.us.cpu(), o["us"]) < 1e-6
+    assert rel(r.xs_xi.cpu(), o["xs_xi"]) < 1e-6
 
 
 def test_augmented_lagrangian_input_box_matches_restated_outer_loop():
@@ -305,10 +245,10 @@ def test_augmented_lagrangian_input_box_matches_restated_outer_loop():
     assert int(info["al_converged"].sum()) == B
     assert float(res.us.max()) < 4.0 + 1e-2 and float(res.us.min()) > -4.0 - 1e-2
     for b in range(B):
-        o, lam, imu, mu, n_outer = _al_oracle(prob, x0_q[b], x0_xi[b], us0[b], lb, ub, 8, 60, 1e-2)
-        assert _rel(res.us[b].cpu(), o["us"]) < 1e-6
-        assert _rel(res.xs_xi[b].cpu(), o["xs_xi"]) < 1e-6
-        assert _rel(info["lmbd"][b].cpu(), lam) < 1e-6
+        o, lam, imu, mu, n_outer = al_oracle(prob, x0_q[b], x0_xi[b], us0[b], lb, ub, 8, 60, 1e-2)
+        assert rel(res.us[b].cpu(), o["us"]) < 1e-6
+        assert rel(res.xs_xi[b].cpu(), o["xs_xi"]) < 1e-6
+        assert rel(info["lmbd"][b].cpu(), lam) < 1e-6
         assert float(info["mu"][b]) == pytest.approx(mu)
         np.testing.assert_array_equal(info["Imu"][b].cpu().numpy() == 0.0, imu == 0.0)
 
@@ -342,7 +282,7 @@ def test_so3_ss_fit_reproduces_recorded_run(so3):
     assert float(r.us[:, :, 3:].abs().max()) == 0.0 and torch.equal(r.us[0], r.us[1])
     o = ob.fit(ob.embed_so3_problem(g["J"], float(g["dt"]), g["Q"], g["R"], g["P"], g["q_ref"], g["xi_ref"]), q0, xi0,
                np.zeros((249, 6)), mode="ss", max_iter=100, tol_grad=1e-12)
-    assert _rel(r.us[0].cpu(), o["us"]) < 1e-6 and _rel(r.xs_q[0].cpu(), o["xs_q"]) < 1e-6
+    assert rel(r.us[0].cpu(), o["us"]) < 1e-6 and rel(r.xs_q[0].cpu(), o["xs_q"]) < 1e-6
 
 
 def test_so3_ms_merit_search_reproduces_recorded_run(so3):
@@ -377,12 +317,12 @@ def test_so3_linearisation_matches_oracle(so3):
     for ms in (True, False):
         r = solver.linearize_backward(xs_q, xs_xi, us, ms=ms)
         o = ob.lin_backward(op, xs_q[0], xs_xi[0], us[0], ms=ms)
-        assert _rel(r["Fx"][0].cpu(), o["Fx"]) < 1e-12
-        assert _rel(r["lx"][0].cpu(), o["Lx"]) < 1e-11            # terminal l_x with Q
-        assert _rel(r["lxx11"][0].cpu(), o["Lxx"][:, :6, :6]) < 1e-11  # terminal l_xx with P
+        assert rel(r["Fx"][0].cpu(), o["Fx"]) < 1e-12
+        assert rel(r["lx"][0].cpu(), o["Lx"]) < 1e-11            # terminal l_x with Q
+        assert rel(r["lxx11"][0].cpu(), o["Lxx"][:, :6, :6]) < 1e-11  # terminal l_xx with P
         assert float(r["J"][0]) == pytest.approx(o["J"], rel=1e-12)
         assert float(r["grad"][0]) == pytest.approx(o["grad"], rel=1e-9)
-        assert _rel(r["K"][0].cpu(), o["K"]) < 1e-8
+        assert rel(r["K"][0].cpu(), o["K"]) < 1e-8
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -395,13 +335,13 @@ def test_edge_sizes_match_oracle(B, N, mode):
     solver = BatchedTrackingILQR(prob, B)
     K = 6
     r = solver.fit_batch(x0_q, x0_xi, us0, mode=mode, n_iterations=K, tol_grad_norm=0.0, tol_d_norm=0.0)
-    o = ob.fit_batch(_oracle_problem(prob), x0_q, x0_xi, us0, mode=mode, max_iter=K)
+    o = ob.fit_batch(oracle_problem(prob), x0_q, x0_xi, us0, mode=mode, max_iter=K)
     np.testing.assert_array_equal(r.iters.cpu().numpy(), o["iters"])
     np.testing.assert_array_equal(r.status.cpu().numpy(), o["status"])
     for b in range(B):
         n = int(r.iters[b])
-        assert _rel(r.J_hist[b, :n].cpu(), o["J_hist"][b, :n]) < 1e-8
-    assert _rel(r.us.cpu(), o["us"]) < 1e-6
+        assert rel(r.J_hist[b, :n].cpu(), o["J_hist"][b, :n]) < 1e-8
+    assert rel(r.us.cpu(), o["us"]) < 1e-6
     assert np.abs(r.xs_q.cpu().numpy() - o["xs_q"]).max() < 1e-6
 
 

@@ -13,54 +13,11 @@ import pytest
 import torch
 
 from oracle import bridge as ob
-from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, _capi, workloads
-from tests.test_policy_cpu import restate_policy
+from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, _capi, workloads
+from tests.checks import check_restatement
+from tests.support import MODELS, host, model_case, op_of, pert, rel, same
 
 pytestmark = pytest.mark.gpu
-
-MODELS = ["se3", "rigidbody", "drone", "so3", "pendulum", "dense"]
-
-
-def _case(name, B, N=40):
-    if name == "drone":
-        prob, q, xi, us = workloads.drone_tracking(B, N=N)
-    elif name == "so3":
-        prob, q, xi, us = workloads.so3_tracking(B, N=N)
-    elif name == "pendulum":
-        prob, q, xi, us = workloads.pendulum_swingup(B)
-    else:
-        prob, q, xi, us = workloads.se3_tracking(B, N=N)
-        if name == "dense":
-            J = prob.J.copy()
-            J[:3, :3] = np.array([[0.5, 0.05, 0.02], [0.05, 0.7, 0.03], [0.02, 0.03, 0.9]])
-            prob = TrackingProblem(prob.kind, J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
-        elif name == "rigidbody":
-            prob = TrackingProblem("rigidbody", prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
-    return prob, q, xi, us
-
-
-def _op(p, q_ref=None, xi_ref=None, Q=None, R=None, P=None):
-    return ob.OracleProblem(p.kind, p.J, p.dt, p.Q if Q is None else Q, p.R if R is None else R, p.P if P is None else P,
-                            p.q_ref if q_ref is None else q_ref, p.xi_ref if xi_ref is None else xi_ref,
-                            pend_mass=p.pend_mass, pend_length=p.pend_length)
-
-
-def _h(t):
-    return t.detach().cpu().numpy()
-
-
-def _rel(a, b):
-    a = np.asarray(a); b = np.asarray(b)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
-
-
-def _pert(B, S, N, seed=5, pose=0.05, twist=0.05, noise=0.01):
-    rng = np.random.default_rng(seed)
-    return rng.normal(0, 1, (B, S, 12)) * np.r_[[pose] * 6, [twist] * 6], rng.normal(0, noise, (B, S, N, 6))
-
-
-def _same(a, b):
-    return np.array_equal(_h(a), _h(b), equal_nan=True)
 
 
 # 1 -------------------------------------------------------------------------------------------------------------------
@@ -70,7 +27,7 @@ def test_gains_after_one_iteration_are_one_sweep_on_the_initial_guess(model, mod
     """The solve's sweep reads its trajectory in the device layout; linearize_backward reads the peeked 4 x 4 export of
     it, and the pose's matrix -> quaternion round trip is not exact: 1e-12 relative, not bits."""
     B = 5
-    prob, q, xi, us = _case(model, B)
+    prob, q, xi, us = model_case(model, B)
     s = BatchedTrackingILQR(prob, B)
     s.solve_begin(q, xi, us, mode=mode, n_iterations=1, tol_grad_norm=0.0, tol_d_norm=0.0)
     pk = s.solve_peek()
@@ -80,30 +37,30 @@ def test_gains_after_one_iteration_are_one_sweep_on_the_initial_guess(model, mod
     g = s.gains()
     r = s.linearize_backward(xq, xx, uu, ms=(mode == "ms"), mu=1.0, delta=2.0)
     torch.cuda.synchronize()
-    assert _rel(_h(g["K"]), _h(r["K"])) < 1e-12 and _rel(_h(g["k"]), _h(r["k"])) < 1e-12
+    assert rel(host(g["K"]), host(r["K"])) < 1e-12 and rel(host(g["k"]), host(r["k"])) < 1e-12
 
 
 # 2 -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("model,mode", [("se3", "ms"), ("se3", "ss"), ("drone", "ms"), ("so3", "ms"), ("so3", "ss")])
 def test_converged_gains_match_the_oracle_sweep_on_the_final_trajectory(model, mode):
     B = 4
-    prob, q, xi, us = _case(model, B)
+    prob, q, xi, us = model_case(model, B)
     s = BatchedTrackingILQR(prob, B)
     r = s.fit_batch(q, xi, us, mode=mode, n_iterations=100, tol_grad_norm=1e-5, tol_d_norm=1e-6)
     g = s.gains()
-    conv, iters = _h(r.converged), _h(r.iters)
+    conv, iters = host(r.converged), host(r.iters)
     assert conv.any()
-    op = _op(prob)
+    op = op_of(prob)
     for b in np.flatnonzero(conv):
         # the last sweep started from the mu / delta the last accepted iteration left (mu_hist[iters - 1]; 1 / 2 if none)
-        mu = float(_h(r.mu_hist)[b, iters[b] - 1]) if iters[b] > 0 else 1.0
+        mu = float(host(r.mu_hist)[b, iters[b] - 1]) if iters[b] > 0 else 1.0
         delta = 2.0 if iters[b] == 0 else None
         o = None
         for d in ([delta] if delta else [1.0, 2.0, 1.6, 1.6 ** 2]):
-            o = ob.lin_backward(op, _h(r.xs_q)[b], _h(r.xs_xi)[b], _h(r.us)[b], ms=(mode == "ms"), mu=mu, delta=d)
-            if _rel(_h(g["K"])[b], o["K"]) < 1e-8:
+            o = ob.lin_backward(op, host(r.xs_q)[b], host(r.xs_xi)[b], host(r.us)[b], ms=(mode == "ms"), mu=mu, delta=d)
+            if rel(host(g["K"])[b], o["K"]) < 1e-8:
                 break
-        assert _rel(_h(g["K"])[b], o["K"]) < 1e-8 and _rel(_h(g["k"])[b], o["k"]) < 1e-8
+        assert rel(host(g["K"])[b], o["K"]) < 1e-8 and rel(host(g["k"])[b], o["k"]) < 1e-8
 
 
 # 3 -------------------------------------------------------------------------------------------------------------------
@@ -113,71 +70,55 @@ def test_gains_and_rollouts_do_not_depend_on_the_batch():
     kw = dict(mode="ss", n_iterations=40, tol_grad_norm=1e-4)
     sb = BatchedTrackingILQR(prob, B)
     rb = sb.fit_batch(q, xi, us, **kw)
-    its = _h(rb.iters)
+    its = host(rb.iters)
     assert its.min() < its.max()  # the trajectories of the batch stop at different iterations
     j = int(np.argsort(its, kind="stable")[B // 2])
     s1 = BatchedTrackingILQR(prob, 1)
     s1.fit_batch(q[j:j + 1], xi[j:j + 1], us[j:j + 1], **kw)
     gb, g1 = sb.gains(), s1.gains()
-    assert _same(gb["K"][j], g1["K"][0]) and _same(gb["k"][j], g1["k"][0])
-    dx0, w = _pert(B, S, prob.N)
+    assert same(gb["K"][j], g1["K"][0]) and same(gb["k"][j], g1["k"][0])
+    dx0, w = pert(B, S, prob.N)
     pb = sb.policy_rollout(dx0, w, trajectories=True)
     p1 = s1.policy_rollout(dx0[j:j + 1], w[j:j + 1], trajectories=True)
     for f in ("J", "status", "xs_q", "xs_xi", "us"):
-        assert _same(getattr(pb, f)[j], getattr(p1, f)[0]), f
+        assert same(getattr(pb, f)[j], getattr(p1, f)[0]), f
     for s_ in (0, 7, 15):  # sample s alone: the same bits as inside S = 16
         ps = sb.policy_rollout(dx0[:, s_:s_ + 1], w[:, s_:s_ + 1], trajectories=True)
         for f in ("J", "xs_q", "xs_xi", "us"):
-            assert _same(getattr(ps, f)[:, 0], getattr(pb, f)[:, s_]), (f, s_)
+            assert same(getattr(ps, f)[:, 0], getattr(pb, f)[:, s_]), (f, s_)
 
 
 # 4 -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("model", MODELS)
 def test_zero_perturbation_reproduces_the_single_shooting_solution(model):
     B = 5
-    prob, q, xi, us = _case(model, B)
+    prob, q, xi, us = model_case(model, B)
     s = BatchedTrackingILQR(prob, B)
     r = s.fit_batch(q, xi, us, mode="ss", n_iterations=25)
     p = s.policy_rollout(S=1, trajectories=True)
-    its, st = _h(r.iters), _h(r.status)
-    Jh = _h(r.J_hist)
+    its, st = host(r.iters), host(r.status)
+    Jh = host(r.J_hist)
     for b in range(B):
-        assert _rel(_h(p.xs_q)[b, 0], _h(r.xs_q)[b]) < 1e-12 and _rel(_h(p.xs_xi)[b, 0], _h(r.xs_xi)[b]) < 1e-12
-        assert _rel(_h(p.us)[b, 0], _h(r.us)[b]) < 1e-12
+        assert rel(host(p.xs_q)[b, 0], host(r.xs_q)[b]) < 1e-12 and rel(host(p.xs_xi)[b, 0], host(r.xs_xi)[b]) < 1e-12
+        assert rel(host(p.us)[b, 0], host(r.us)[b]) < 1e-12
         if its[b] > 0 and st[b] == _capi.ST_OK:
-            assert abs(_h(p.J)[b, 0] / Jh[b, its[b] - 1] - 1) < 1e-12
-    assert (_h(p.status) == _capi.ST_OK).all()
+            assert abs(host(p.J)[b, 0] / Jh[b, its[b] - 1] - 1) < 1e-12
+    assert (host(p.status) == _capi.ST_OK).all()
 
 
 # 5 -------------------------------------------------------------------------------------------------------------------
-def _check_restatement(s, r, ops, dx0, w):
-    g = s.gains()
-    p = s.policy_rollout(dx0, w, trajectories=True)
-    K = _h(g["K"])
-    S = dx0.shape[1]
-    ok = 0
-    for b, op in enumerate(ops):
-        J, xq, xx, uu = restate_policy(op, _h(r.xs_q)[b], _h(r.xs_xi)[b], _h(r.us)[b], K[b], dx0[b], w[b], S)
-        fin = np.isfinite(J)  # a sample the CPU sees diverge must diverge on the device, and be flagged there
-        assert np.array_equal(_h(p.status)[b], np.where(fin, _capi.ST_OK, _capi.ST_NONFINITE))
-        assert np.abs(_h(p.xs_q)[b][fin] - xq[fin]).max(initial=0) < 1e-10
-        assert np.abs(_h(p.xs_xi)[b][fin] - xx[fin]).max(initial=0) < 1e-10
-        assert np.abs(_h(p.us)[b][fin] - uu[fin]).max(initial=0) < 1e-8
-        assert np.abs(_h(p.J)[b][fin] / J[fin] - 1).max(initial=0) < 1e-9
-        ok += int(fin.sum())
-    assert ok >= len(ops) * S // 2
 
 
 @pytest.mark.parametrize("model", MODELS)
 def test_rollouts_match_a_cpu_restatement(model):
     B, S = 3, 5
-    prob, q, xi, us = _case(model, B)
+    prob, q, xi, us = model_case(model, B)
     s = BatchedTrackingILQR(prob, B)
     r = s.fit_batch(q, xi, us, mode="ms", n_iterations=8, tol_grad_norm=0.0, tol_d_norm=0.0)
     # the swing-up's 8-iteration policy is far from converged: smaller disturbances keep most of its samples finite
     scale = dict(pose=1e-3, twist=1e-3, noise=1e-4) if model == "pendulum" else {}
-    dx0, w = _pert(B, S, prob.N, seed=11, **scale)
-    _check_restatement(s, r, [_op(prob)] * B, dx0, w)
+    dx0, w = pert(B, S, prob.N, seed=11, **scale)
+    check_restatement(s, r, [op_of(prob)] * B, dx0, w)
 
 
 def test_rollouts_match_a_cpu_restatement_with_references_and_weights_per_trajectory():
@@ -187,8 +128,8 @@ def test_rollouts_match_a_cpu_restatement_with_references_and_weights_per_trajec
     s = BatchedTrackingILQR(prob, B)
     r = s.fit_batch(q, xi, us, mode="ms", n_iterations=8, tol_grad_norm=0.0, tol_d_norm=0.0, q_ref=q_ref, xi_ref=xi_ref,
                     Q=Q, P=P, R=R)
-    dx0, w = _pert(B, S, prob.N, seed=12)
-    _check_restatement(s, r, [_op(prob, q_ref[b], xi_ref[b], Q[b], R[b], P[b]) for b in range(B)], dx0, w)
+    dx0, w = pert(B, S, prob.N, seed=12)
+    check_restatement(s, r, [op_of(prob, q_ref[b], xi_ref[b], Q[b], R[b], P[b]) for b in range(B)], dx0, w)
 
 
 # 6 -------------------------------------------------------------------------------------------------------------------
@@ -200,12 +141,12 @@ def test_broadcast_references_and_weights_give_the_shared_bits():
     s0, s1 = BatchedTrackingILQR(prob, B), BatchedTrackingILQR(prob, B)
     s0.fit_batch(q, xi, us, **kw)
     s1.fit_batch(q, xi, us, q_ref=t(prob.q_ref), xi_ref=t(prob.xi_ref), Q=t(prob.Q), P=t(prob.P), R=t(prob.R), **kw)
-    dx0, w = _pert(B, S, prob.N)
+    dx0, w = pert(B, S, prob.N)
     p0, p1 = s0.policy_rollout(dx0, w, trajectories=True), s1.policy_rollout(dx0, w, trajectories=True)
     for f in ("J", "status", "xs_q", "xs_xi", "us"):
-        assert _same(getattr(p0, f), getattr(p1, f)), f
+        assert same(getattr(p0, f), getattr(p1, f)), f
     g0, g1 = s0.gains(), s1.gains()
-    assert _same(g0["K"], g1["K"]) and _same(g0["k"], g1["k"])
+    assert same(g0["K"], g1["K"]) and same(g0["k"], g1["k"])
 
 
 # 7 -------------------------------------------------------------------------------------------------------------------
@@ -214,17 +155,17 @@ def test_a_non_finite_sample_stays_in_its_lane():
     prob, q, xi, us = workloads.se3_tracking(B, N=60)
     s = BatchedTrackingILQR(prob, B)
     s.fit_batch(q, xi, us, mode="ms", n_iterations=10, tol_grad_norm=0.0, tol_d_norm=0.0)
-    dx0, w = _pert(B, S, prob.N)
+    dx0, w = pert(B, S, prob.N)
     dx0[bad][6:9] = 1e200
     p = s.policy_rollout(dx0, w, trajectories=True)
-    st = _h(p.status)
+    st = host(p.status)
     assert st[bad] == _capi.ST_NONFINITE and (np.delete(st.reshape(-1), bad[0] * S + bad[1]) == _capi.ST_OK).all()
     keep = [k for k in range(S) if k != bad[1]]
     # the bad sample replaced by a good one: every other sample keeps its bits
     dx1 = dx0.copy(); dx1[bad] = dx0[bad[0], 0]
     q1 = s.policy_rollout(dx1, w, trajectories=True)
     for f in ("J", "xs_q", "xs_xi", "us"):
-        a, b = _h(getattr(p, f)), _h(getattr(q1, f))
+        a, b = host(getattr(p, f)), host(getattr(q1, f))
         for bb in range(B):
             ks = keep if bb == bad[0] else range(S)
             assert np.array_equal(a[bb, list(ks)], b[bb, list(ks)]), f
@@ -257,7 +198,7 @@ def test_handle_state_rules():
     r = s.solve_end()
     assert _raw(s, B) == (0, 0)
     assert _raw(s, B - 1) == (-1, -1) and _raw(s, B, S=0)[1] == -1
-    dx0, w = _pert(B, S, prob.N)
+    dx0, w = pert(B, S, prob.N)
     with pytest.raises(ValueError):
         s.policy_rollout(dx0, w[:, :2])
     with pytest.raises(ValueError):
@@ -270,14 +211,14 @@ def test_handle_state_rules():
     p0 = s.policy_rollout(dx0, w, trajectories=True)
     p1 = s.policy_rollout(dx0, w, trajectories=True)
     for f in ("J", "status", "xs_q", "xs_xi", "us"):
-        assert _same(getattr(p0, f), getattr(p1, f)), f
+        assert same(getattr(p0, f), getattr(p1, f)), f
     # tolg_rollout and tolg_expected_change leave the policy, tolg_eval_knot clears it
     s.rollout(B, alpha=0.5, ms=True)
     s.expected_change(B)
     g1 = s.gains()
-    assert _same(g0["K"], g1["K"]) and _same(g0["k"], g1["k"])
-    assert _same(s.policy_rollout(dx0, w).J, p0.J)
-    s.eval_knot(3, _h(r.xs_q)[:, 3], _h(r.xs_xi)[:, 3], _h(r.us)[:, 3])
+    assert same(g0["K"], g1["K"]) and same(g0["k"], g1["k"])
+    assert same(s.policy_rollout(dx0, w).J, p0.J)
+    s.eval_knot(3, host(r.xs_q)[:, 3], host(r.xs_xi)[:, 3], host(r.us)[:, 3])
     assert _raw(s, B) == (-1, -1)
     with pytest.raises(ValueError):
         s.gains()
@@ -292,7 +233,7 @@ def test_handle_state_rules():
     ra = s2.fit_batch(q, xi, us, **kw)
     rb = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, **kw)
     for f in ("xs_q", "xs_xi", "us", "J_hist", "grad_hist", "defect_hist", "iters", "status"):
-        assert _same(getattr(ra, f), getattr(rb, f)), f
+        assert same(getattr(ra, f), getattr(rb, f)), f
 
 
 # 9 -------------------------------------------------------------------------------------------------------------------
@@ -302,8 +243,8 @@ def test_full_size():
     s = BatchedTrackingILQR(prob, B)
     s.fit_batch(q, xi, us, mode="ms", n_iterations=20, tol_grad_norm=0.0, tol_d_norm=0.0)
     p = s.policy_rollout(dx0, w)
-    st = _h(p.status)
-    assert np.isfinite(_h(p.J)).all() and not (st == _capi.ST_INTERNAL).any() and (st == _capi.ST_OK).all()
+    st = host(p.status)
+    assert np.isfinite(host(p.J)).all() and not (st == _capi.ST_INTERNAL).any() and (st == _capi.ST_OK).all()
 
 
 # 10 ------------------------------------------------------------------------------------------------------------------
@@ -323,7 +264,7 @@ def test_mirror_fit_leaves_the_gains(golden_dir):
     assert ctl._k.shape == (150, 4) and ctl._K.shape == (150, 4, 12)
     assert np.abs(ctl._K).max() > 0 and np.abs(ctl._k).max() > 0
     gg = ctl._solver.gains()
-    assert np.array_equal(ctl._K, _h(gg["K"])[0]) and np.array_equal(ctl._k, _h(gg["k"])[0])
+    assert np.array_equal(ctl._K, host(gg["K"])[0]) and np.array_equal(ctl._k, host(gg["k"])[0])
 
     g = np.load(os.path.join(golden_dir, "so3_n249_problem.npz"))
     N = 249
@@ -335,5 +276,5 @@ def test_mirror_fit_leaves_the_gains(golden_dir):
     assert ctl._k.shape == (N, 3) and ctl._K.shape == (N, 3, 6)
     assert np.abs(ctl._K).max() > 0 and np.abs(ctl._k).max() > 0
     gg = ctl._solver.gains()
-    K = _h(gg["K"])[0]
-    assert np.array_equal(ctl._K, K[:, :3][:, :, [0, 1, 2, 6, 7, 8]]) and np.array_equal(ctl._k, _h(gg["k"])[0][:, :3])
+    K = host(gg["K"])[0]
+    assert np.array_equal(ctl._K, K[:, :3][:, :, [0, 1, 2, 6, 7, 8]]) and np.array_equal(ctl._k, host(gg["k"])[0][:, :3])

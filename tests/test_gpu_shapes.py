@@ -20,25 +20,15 @@ import torch
 from oracle import bridge as ob
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, workloads
 from trajectory_optimization_matrix_lie_groups_amd.solver import embed_pendulum3d
-from tests.test_gpu_expected_change import check_ring_against_statement
-from tests.test_gpu_fused import _assert_same
-from tests.test_gpu_mpc import _check_advance, check_loop
-from tests.test_gpu_multiref import _assert_bitwise, _dense
-from tests.test_gpu_obstacles import _host_solve, _update_restated
-from tests.test_gpu_parity import _al_oracle, _random_traj, check_linearize_backward
-from tests.test_gpu_policy import _check_restatement, _op, _pert
+from tests.checks import (al_oracle, assert_same, check_advance, check_linearize_backward, check_loop, check_restatement,
+                          check_ring_against_statement, host_solve, update_restated)
+from tests.support import ZERO, assert_bitwise, dense_fixed_block, op_of, pert, random_traj, rel
 
 pytestmark = pytest.mark.gpu
 
 HORIZONS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 23, 24, 25, 31, 32, 33]
 BATCHES = [1, 2, 3, 4, 15, 16, 17, 20, 63, 64, 65, 68]
 SHORT = [1, 2, 3, 4, 5]
-ZERO = dict(tol_grad_norm=0.0, tol_d_norm=0.0)
-
-
-def _rel(a, b):
-    a = np.asarray(a); b = np.asarray(b)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
 def _pendulum(B, N):
@@ -59,7 +49,7 @@ def _model(name, B, N):
         return _pendulum(B, N)
     prob, q, xi, us = workloads.se3_tracking(B, N=N)
     if name == "dense":
-        prob = _dense(prob)
+        prob = dense_fixed_block(prob)
     elif name == "rigidbody":
         prob = TrackingProblem("rigidbody", prob.J, prob.dt, prob.Q, np.eye(6) * 1e-4, prob.P, prob.q_ref, prob.xi_ref)
     return prob, q, xi, us
@@ -82,9 +72,9 @@ def _against_oracle(g, o, tol_j, what):
     np.testing.assert_array_equal(g["status"].cpu().numpy(), o["status"], err_msg=what)
     Jg = g["J_hist"].cpu().numpy()
     for b in range(len(it)):
-        assert _rel(Jg[b, :it[b]], o["J_hist"][b, :it[b]]) < tol_j, (what, b)
-    assert _rel(g["us"].cpu(), o["us"]) < 1e-6, what
-    assert _rel(g["xs_xi"].cpu(), o["xs_xi"]) < 1e-6, what
+        assert rel(Jg[b, :it[b]], o["J_hist"][b, :it[b]]) < tol_j, (what, b)
+    assert rel(g["us"].cpu(), o["us"]) < 1e-6, what
+    assert rel(g["xs_xi"].cpu(), o["xs_xi"]) < 1e-6, what
 
 
 # (model, fit_batch keywords, iterations): K below the oracle's first no-descent exit at every horizon of the sweep
@@ -115,12 +105,12 @@ def test_horizon_sweep_against_the_oracle(N):
         s, prob, q, xi, us = handles[name]
         what = "%s %s N=%d" % (name, kw, N)
         g = _solve(s, q, xi, us, K, **kw)
-        o = ob.fit_batch(_op(prob), q, xi, us, max_iter=K, mode=kw["mode"], line_search=kw.get("line_search", False),
+        o = ob.fit_batch(op_of(prob), q, xi, us, max_iter=K, mode=kw["mode"], line_search=kw.get("line_search", False),
                          rollout=kw.get("rollout", "nonlinear"))
         searching = kw.get("line_search", False) or kw["mode"] == "ss"
         _against_oracle(g, o, 1e-8 if searching else 1e-9, what)
         if kw.get("schedule") == "auto":  # the fused launch against the split schedule on the same handle
-            _assert_same(g, s.fit_batch(q, xi, us, n_iterations=K, schedule="split", **ZERO, mode="ms"))
+            assert_same(g, s.fit_batch(q, xi, us, n_iterations=K, schedule="split", **ZERO, mode="ms"))
 
 
 # 2 -------------------------------------------------------------------------------------------------------------------
@@ -141,7 +131,7 @@ def test_batch_sweep_against_the_oracle(B, N):
     assert len(lanes) >= min(B, 8) and lanes[-1] == B - 1
     for kw, K in ((dict(mode="ms"), 6), (dict(mode="ss"), 4), (dict(mode="ms", line_search=True), 4)):
         g = _solve(s, q, xi, us, K, **kw)
-        o = ob.fit_batch(_op(prob), q[lanes], xi[lanes], us[lanes], max_iter=K, mode=kw["mode"],
+        o = ob.fit_batch(op_of(prob), q[lanes], xi[lanes], us[lanes], max_iter=K, mode=kw["mode"],
                          line_search=kw.get("line_search", False))
         sub = {k: v[torch.as_tensor(lanes, device=v.device)] for k, v in g.items()}
         _against_oracle(sub, o, 1e-9 if kw == dict(mode="ms") else 1e-8, "%s B=%d N=%d" % (kw, B, N))
@@ -162,7 +152,7 @@ def test_a_trajectory_does_not_depend_on_its_lane(N):
             qb[B - 1], xb[B - 1] = q[t], xi[t]
             rb = BatchedTrackingILQR(prob, B).fit_batch(qb, xb, us[:B], **kw)
             torch.cuda.synchronize()
-            _assert_bitwise(r1, rb, slice(0, 1), slice(B - 1, B), what="t=%d at lane %d of B=%d" % (t, B - 1, B))
+            assert_bitwise(r1, rb, slice(0, 1), slice(B - 1, B), what="t=%d at lane %d of B=%d" % (t, B - 1, B))
 
 
 # 3 -------------------------------------------------------------------------------------------------------------------
@@ -171,7 +161,7 @@ def test_a_trajectory_does_not_depend_on_its_lane(N):
 def test_linearize_backward_at_short_horizons(name, N):
     B = 5
     prob = _model(name, B, N)[0]
-    xs_q, xs_xi, us = _random_traj(prob, B, seed=11 + N)
+    xs_q, xs_xi, us = random_traj(prob, B, seed=11 + N)
     if name in ("so3", "pendulum"):  # the embedding: translation, linear twist and inputs 3..5 are zero
         xs_q[..., :3, 3] = 0.0
         xs_xi[..., 3:] = 0.0
@@ -208,7 +198,7 @@ def test_one_handle_across_batch_sizes():
         torch.cuda.synchronize()
         f = BatchedTrackingILQR(prob, MAXB).fit_batch(q[:B], xi[:B], us[:B], **kw)
         torch.cuda.synchronize()
-        _assert_bitwise(a, f, what="B=%d after the previous calls" % B)
+        assert_bitwise(a, f, what="B=%d after the previous calls" % B)
 
 
 # 5 -------------------------------------------------------------------------------------------------------------------
@@ -219,15 +209,15 @@ def test_mpc_advance_and_policy_at_short_horizons(name, N):
     prob, q, xi, us = _model(name, B, N)
     s = BatchedTrackingILQR(prob, B)
     r = s.fit_batch(q, xi, us, mode="ms", n_iterations=8, **ZERO)
-    dx0, w = _pert(B, 4, N, seed=11, **(dict(pose=1e-3, twist=1e-3, noise=1e-4) if name == "pendulum" else {}))
+    dx0, w = pert(B, 4, N, seed=11, **(dict(pose=1e-3, twist=1e-3, noise=1e-4) if name == "pendulum" else {}))
     if name in ("so3", "pendulum"):  # the embedding's translation and linear twist stay zero
         dx0[..., 3:6] = dx0[..., 9:] = 0.0
         w[..., 3:] = 0.0
-    _check_restatement(s, r, [_op(prob)] * B, dx0, w)
+    check_restatement(s, r, [op_of(prob)] * B, dx0, w)
     wa = np.random.default_rng(3).normal(0, 0.01, (B, 6))
     if name in ("so3", "pendulum"):
         wa[:, 3:] = 0.0
-    _check_advance(s, r, [_op(prob)] * B, wa)
+    check_advance(s, r, [op_of(prob)] * B, wa)
 
 
 @pytest.mark.parametrize("N", [1, 2, 3, 5])
@@ -248,10 +238,10 @@ def test_al_input_box_at_short_horizons(N):
     res, info = s.al_fit_batch(q, xi, us0, lb, ub, n_al_iters=n_al, n_ilqr_iters=n_in, tol_constr=tol)
     torch.cuda.synchronize()
     for b in range(B):
-        o, lam, imu, mu, n_outer = _al_oracle(prob, q[b], xi[b], us0[b], lb, ub, n_al, n_in, tol)
-        assert _rel(res.us[b].cpu(), o["us"]) < 1e-6
-        assert _rel(res.xs_xi[b].cpu(), o["xs_xi"]) < 1e-6
-        assert _rel(info["lmbd"][b].cpu(), lam) < 1e-6
+        o, lam, imu, mu, n_outer = al_oracle(prob, q[b], xi[b], us0[b], lb, ub, n_al, n_in, tol)
+        assert rel(res.us[b].cpu(), o["us"]) < 1e-6
+        assert rel(res.xs_xi[b].cpu(), o["xs_xi"]) < 1e-6
+        assert rel(info["lmbd"][b].cpu(), lam) < 1e-6
         assert float(info["mu"][b]) == pytest.approx(mu)
         np.testing.assert_array_equal(info["Imu"][b].cpu().numpy() == 0.0, imu == 0.0)
 
@@ -260,7 +250,7 @@ def test_al_input_box_at_short_horizons(N):
 def test_al_keep_out_sphere_at_short_horizons(N):
     """al_fit_batch with one keep-out sphere around each trajectory's initial position (a short horizon does not get far
     from it), two outer iterations of fixed inner length, against the outer loop restated on the mirror's host generic path
-    (_host_solve) and the multiplier update (_update_restated)."""
+    (host_solve) and the multiplier update (update_restated)."""
     B, n_al, n_in, mu0 = 2, 2, 6, 1.0
     prob, q, xi, us0 = workloads.se3_tracking(B, N=N, R_scale=1e-3)
     obs = np.zeros((B, 1, 4))
@@ -274,13 +264,13 @@ def test_al_keep_out_sphere_at_short_horizons(N):
     for b in range(B):
         lam, imu, mu = np.zeros((N + 1, 1)), np.full((N + 1, 1), mu0), mu0
         for it in range(n_al):
-            J, us, xs = _host_solve(prob, q[b], xi[b], us0[b], obs[b], lam, imu, dict(mode="ms", n_iterations=n_in),
+            J, us, xs = host_solve(prob, q[b], xi[b], us0[b], obs[b], lam, imu, dict(mode="ms", n_iterations=n_in),
                                     states=True)
             t = np.array([x[0][:3, 3] for x in xs])
             g = obs[b, None, :, 3] ** 2 - np.sum((t[:, None, :] - obs[b, None, :, :3]) ** 2, axis=-1)
             if it == 0:
                 assert g.max() > 1e-2  # the first solve violates
-            lam, imu = _update_restated(g, lam, imu, mu)
+            lam, imu = update_restated(g, lam, imu, mu)
             mu *= 10.0
         assert int(res.iters[b]) == len(J) and int(res.status[b]) == 0
         assert np.abs(res.J_hist[b, :len(J)].cpu().numpy() / J - 1).max() < 1e-9

@@ -12,11 +12,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import bridge as ob  # noqa: E402  (test infrastructure)
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, workloads  # noqa: E402
-
-
-def _rel(a, b):
-    a = np.asarray(a); b = np.asarray(b)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+from tests.support import rel  # noqa: E402
 
 
 @pytest.mark.parametrize("kind,N,R", [("drone", 400, 1e-3), ("drone", 400, 1e-5), ("se3", 955, 1e-5), ("se3", 400, 1e-6)])
@@ -39,4 +35,4 @@ def test_sweep_with_four_knot_symmetrisation_matches_every_knot_oracle(kind, N, 
     oo = ob.fit_batch(op, x0_q, x0_xi, us0, mode="ms", max_iter=4)
     ok = np.isfinite(oo["J_hist"]).all(axis=1) & (np.abs(oo["J_hist"]).max(axis=1) < 1e12)
     assert ok.sum() >= 1
-    assert _rel(rr.J_hist.cpu().numpy()[ok], oo["J_hist"][ok]) < 1e-9
+    assert rel(rr.J_hist.cpu().numpy()[ok], oo["J_hist"][ok]) < 1e-9

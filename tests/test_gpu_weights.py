@@ -14,18 +14,10 @@ import torch
 
 from oracle import bridge as ob
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, _capi, workloads
-from tests.test_gpu_multiref import B13, BROADCAST, MODES, _assert_bitwise, _broadcast, _case, _near, _with_ref
-from tests.test_gpu_parity import _oracle_problem, _rel
+from tests.support import (B13, BROADCAST, MODES, assert_bitwise, broadcast, case_b13, near, oracle_problem, rel, rel_nan,
+                           with_ref)
 
 pytestmark = pytest.mark.gpu
-
-
-def _rel_nan(a, b):
-    """_rel over the finite entries; NaN where the oracle has NaN (a diverging weight set diverges on both)"""
-    a = np.asarray(a); b = np.asarray(b)
-    assert np.array_equal(np.isnan(a), np.isnan(b))
-    f = ~np.isnan(b)
-    return _rel(a[f], b[f]) if f.any() else 0.0
 
 
 def _with_w(prob, Q, R, P):
@@ -41,23 +33,23 @@ def _bw(prob, B):
 @pytest.mark.parametrize("case,kw", BROADCAST, ids=["%s-%d" % (c, i) for i, (c, _) in enumerate(BROADCAST)])
 @pytest.mark.parametrize("refs", [False, True], ids=["shared-ref", "pt-ref"])
 def test_broadcast_weights_are_bitwise_the_shared_ones(case, kw, refs):
-    prob, q, xi, us = _case(case)
+    prob, q, xi, us = case_b13(case)
     rk = {}
     if refs:
-        qr, xr = _broadcast(prob, B13)
+        qr, xr = broadcast(prob, B13)
         rk = dict(q_ref=qr, xi_ref=xr)
     r0 = BatchedTrackingILQR(prob, B13).fit_batch(q, xi, us, **rk, **kw)
     r1 = BatchedTrackingILQR(prob, B13).fit_batch(q, xi, us, **rk, **_bw(prob, B13), **kw)
     torch.cuda.synchronize()
-    _assert_bitwise(r0, r1, what=case)
+    assert_bitwise(r0, r1, what=case)
 
 
 def test_broadcast_weights_one_call_entry_point():
-    prob, q, xi, us = _case("se3")
+    prob, q, xi, us = case_b13("se3")
     kw = dict(mode="ms", n_iterations=12, tol_grad_norm=0.0, tol_d_norm=0.0)
     r0 = BatchedTrackingILQR(prob, B13).solve_batch_one_call(q, xi, us, **kw)
     r1 = BatchedTrackingILQR(prob, B13).solve_batch_one_call(q, xi, us, **_bw(prob, B13), **kw)
-    _assert_bitwise(r0, r1)
+    assert_bitwise(r0, r1)
 
 
 def test_broadcast_weights_al():
@@ -66,7 +58,7 @@ def test_broadcast_weights_al():
     r0, i0 = BatchedTrackingILQR(prob, B13).al_fit_batch(q, xi, us, lb, ub, **kw)
     r1, i1 = BatchedTrackingILQR(prob, B13).al_fit_batch(q, xi, us, lb, ub, **_bw(prob, B13), **kw)
     torch.cuda.synchronize()
-    _assert_bitwise(r0, r1)
+    assert_bitwise(r0, r1)
     for k in ("lmbd", "Imu", "mu", "max_violation"):
         assert torch.equal(i0[k].view(torch.int64), i1[k].view(torch.int64)), k
     assert i0["outer_iterations"] == i1["outer_iterations"]
@@ -89,7 +81,7 @@ def test_grouped_weights_match_one_handle_per_set(mode):
         rows = slice(4 * g, 4 * g + 4)
         rg = BatchedTrackingILQR(_with_w(prob, Q[4 * g], R[4 * g], P[4 * g]), 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
         torch.cuda.synchronize()
-        _assert_bitwise(r, rg, rows_a=rows, what="set %d" % g)
+        assert_bitwise(r, rg, rows_a=rows, what="set %d" % g)
 
 
 @pytest.mark.parametrize("mode", list(MODES))
@@ -111,12 +103,12 @@ def test_interleaved_weights_match_the_oracle(mode, refs):
     for b in range(B):
         pb = _with_w(prob, Q[b], R[b], P[b])
         if refs:
-            pb = _with_ref(pb, q_ref[b], xi_ref[b])
-        o = ob.fit(_oracle_problem(pb), q[b], xi[b], us[b], **okw)
+            pb = with_ref(pb, q_ref[b], xi_ref[b])
+        o = ob.fit(oracle_problem(pb), q[b], xi[b], us[b], **okw)
         n = int(r.iters[b])
         assert n == o["n_iters"] and int(r.status[b]) == o["status"], b
-        assert _rel_nan(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
-        assert _rel_nan(r.us[b].cpu(), o["us"]) < 1e-6, b
+        assert rel_nan(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
+        assert rel_nan(r.us[b].cpu(), o["us"]) < 1e-6, b
 
 
 def _scaled_sets(prob, K, seed=11, spread=2.0):
@@ -144,7 +136,7 @@ def test_grouped_weights_other_models(case, mode):
     """sets on groups of four, one per workgroup of the sweeps and of the expected-change ring: the bits of one shared-weight
     handle per set"""
     B, K = 12, 3
-    prob, q, xi, us = _case(case)
+    prob, q, xi, us = case_b13(case)
     q, xi, us = q[:B], xi[:B], us[:B]
     Qk, Pk, Rk = _scaled_sets(prob, K)
     order = np.arange(B) // 4
@@ -154,7 +146,7 @@ def test_grouped_weights_other_models(case, mode):
         rows = slice(4 * g, 4 * g + 4)
         rg = BatchedTrackingILQR(_with_w(prob, Qk[g], Rk[g], Pk[g]), 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
         torch.cuda.synchronize()
-        _assert_bitwise(r, rg, rows_a=rows, what="%s set %d" % (case, g))
+        assert_bitwise(r, rg, rows_a=rows, what="%s set %d" % (case, g))
 
 
 @pytest.mark.parametrize("mode", list(MODEL_MODES))
@@ -165,7 +157,7 @@ def test_interleaved_weights_other_models_match_the_oracle(case, mode):
     pendulum trajectories diverge under these sets, in the oracle as on the device), equal iterations and status.  Merit: the
     cost history over the iterations both ran -- where the drone's line search gives up is decided by rounding, with the
     shared weights as well (its iteration counts differ from the oracle's there), so only the common part is compared."""
-    prob, q, xi, us = _case(case)
+    prob, q, xi, us = case_b13(case)
     K = 3
     Qk, Pk, Rk = _scaled_sets(prob, K, spread=1.5)
     idx = np.arange(B13) % K
@@ -183,10 +175,10 @@ def test_interleaved_weights_other_models_match_the_oracle(case, mode):
             assert n == o["n_iters"] and int(r.status[b]) == o["status"], b
             if o["status"] != _capi.ST_OK:  # diverged (status and iteration agree; the blown-up values are not compared)
                 continue
-            assert _rel(r.us[b].cpu(), o["us"]) < 1e-6, b
+            assert rel(r.us[b].cpu(), o["us"]) < 1e-6, b
         n = min(n, o["n_iters"])
         assert n >= 1
-        assert _rel_nan(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
+        assert rel_nan(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
 
 
 @pytest.mark.parametrize("ms", [True, False])
@@ -197,18 +189,18 @@ def test_linearize_backward_per_trajectory_weights(ms):
     rng = np.random.default_rng(7)
     xs_q = np.empty((B, N + 1, 4, 4)); xs_xi = np.empty((B, N + 1, 6))
     for b in range(B):
-        xs_q[b], xs_xi[b] = _near(prob.q_ref, prob.xi_ref, rng)
+        xs_q[b], xs_xi[b] = near(prob.q_ref, prob.xi_ref, rng)
     us = rng.normal(size=(B, N, 6))
     r = BatchedTrackingILQR(prob, B).linearize_backward(xs_q, xs_xi, us, ms=ms, Q=Q, P=P, R=R)
     torch.cuda.synchronize()
     for b in range(B):
-        o = ob.lin_backward(_oracle_problem(_with_w(prob, Q[b], R[b], P[b])), xs_q[b], xs_xi[b], us[b], ms=ms)
-        assert _rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
-        assert _rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
-        assert _rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
+        o = ob.lin_backward(oracle_problem(_with_w(prob, Q[b], R[b], P[b])), xs_q[b], xs_xi[b], us[b], ms=ms)
+        assert rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
+        assert rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
+        assert rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
         assert float(r["J"][b]) == pytest.approx(o["J"], rel=1e-12)
-        assert _rel(r["K"][b].cpu(), o["K"]) < 1e-8
-        assert _rel(r["k"][b].cpu(), o["k"]) < 1e-8
+        assert rel(r["K"][b].cpu(), o["K"]) < 1e-8
+        assert rel(r["k"][b].cpu(), o["k"]) < 1e-8
 
 
 def test_full_size_64_sets():
@@ -226,7 +218,7 @@ def test_full_size_64_sets():
         rows = slice(g0, g0 + 4)
         rg = BatchedTrackingILQR(_with_w(prob, Q[g0], R[g0], P[g0]), 4).fit_batch(q[rows], xi[rows], us[rows], **kw)
         torch.cuda.synchronize()
-        _assert_bitwise(r, rg, rows_a=rows, what="rows %d.." % g0)
+        assert_bitwise(r, rg, rows_a=rows, what="rows %d.." % g0)
 
 
 def test_state_returns_to_the_shared_weights():
@@ -240,17 +232,17 @@ def test_state_returns_to_the_shared_weights():
     assert not torch.equal(own.us, fresh.us)
     again = s.fit_batch(q, xi, us, **kw)  # Python: a call without weights is a shared-weight call
     torch.cuda.synchronize()
-    _assert_bitwise(fresh, again, what="python")
+    assert_bitwise(fresh, again, what="python")
     s.fit_batch(q, xi, us, Q=Q, P=P, R=R, **kw)
     torch.cuda.synchronize()
     assert s.lib.tolg_set_weights(s._h, B, None, None, None, None, 0, None) == 0  # C ABI: back to the shared weights
     s.clear_per_trajectory()  # the solver's own record of what it set (the C call above bypassed it)
     again = s.solve_batch_one_call(q, xi, us, **kw)
     fresh1 = BatchedTrackingILQR(prob, B).solve_batch_one_call(q, xi, us, **kw)
-    _assert_bitwise(fresh1, again, what="C")
+    assert_bitwise(fresh1, again, what="C")
     own2 = s.fit_batch(q, xi, us, Q=Q, P=P, R=R, **kw)
     torch.cuda.synchronize()
-    _assert_bitwise(own, own2)
+    assert_bitwise(own, own2)
 
 
 def test_argument_errors():
@@ -312,12 +304,12 @@ def test_zero_weights_are_legal():
     r = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, Q=Q, P=P, R=R, **kw)
     torch.cuda.synchronize()
     for b in (0, 1):
-        o = ob.fit(_oracle_problem(_with_w(prob, Q[b], R[b], P[b])), q[b], xi[b], us[b], mode="ms", max_iter=5, tol_grad=0.0,
+        o = ob.fit(oracle_problem(_with_w(prob, Q[b], R[b], P[b])), q[b], xi[b], us[b], mode="ms", max_iter=5, tol_grad=0.0,
                    tol_defect=0.0)
         n = int(r.iters[b])
         assert n == o["n_iters"] and int(r.status[b]) == o["status"], b
         if n:
-            assert _rel_nan(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
+            assert rel_nan(r.J_hist[b, :n].cpu(), o["J_hist"][:n]) < 1e-9, b
 
 
 def test_mirror_fit_batch_weights():
@@ -336,4 +328,4 @@ def test_mirror_fit_batch_weights():
     direct = BatchedTrackingILQR(prob, B).fit_batch(q, xi, us, mode="ms", n_iterations=10, tol_grad_norm=ctl._default_tol,
                                                     Q=Q, P=P, R=R, **ctl._options())
     torch.cuda.synchronize()
-    _assert_bitwise(r, direct)
+    assert_bitwise(r, direct)

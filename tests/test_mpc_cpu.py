@@ -9,48 +9,10 @@ import numpy as np
 from oracle import bridge as ob
 from trajectory_optimization_matrix_lie_groups_amd import _capi, workloads
 from trajectory_optimization_matrix_lie_groups_amd.solver import mpc_shift, mpc_window_index
+from tests.restate import restate_mpc, window_problem
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("tolg_solve_begin_warm", "tolg_set_ref_windows", "tolg_mpc_advance")
-
-
-def window_problem(prob, path_q, path_xi, t0, t, Q=None, R=None, P=None):
-    """The OracleProblem of one trajectory's window at step t: knots min(t0 + t + i, T) of its path."""
-    idx = mpc_window_index([t0], t, prob.N, path_q.shape[0] - 1)[0]
-    return ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q if Q is None else Q, prob.R if R is None else R,
-                            prob.P if P is None else P, path_q[idx], path_xi[idx], pend_mass=prob.pend_mass,
-                            pend_length=prob.pend_length)
-
-
-def restate_mpc_step(op, x_q, x_xi, us, iters):
-    """One step's solve on the CPU: multiple shooting, accept-always, a fixed iteration count (zero tolerances), from the
-    measured state and the shifted controls, the MS states from the reference window (warm="controls")."""
-    return ob.fit(op, np.asarray(x_q).reshape(16), x_xi, us, mode="ms", max_iter=iters, tol_grad=0.0, tol_defect=0.0)
-
-
-def restate_mpc(prob, x0_q, x0_xi, path_q, path_xi, steps, t0=0, us_init=None, first_iters=50, iters_per_step=5,
-                noise=None):
-    """One trajectory's MPC loop (warm="controls") from oracle primitives only (ob.fit, ob.f, ob.cost): at step t a solve
-    on the window, u_t = u*_0, J += l(x*_0, u*_0), x_{t+1} = f(x*_0, u*_0) + [0; noise[t]], the controls shifted by one
-    knot (the last held).  Returns dict xs_q [steps+1, 4, 4], xs_xi [steps+1, 6], us [steps, m], J."""
-    N, m = prob.N, prob.m
-    x_q, x_xi = np.asarray(x0_q, float).reshape(4, 4), np.asarray(x0_xi, float)
-    us = np.zeros((N, m)) if us_init is None else np.asarray(us_init, float)
-    xs_q = np.zeros((steps + 1, 4, 4)); xs_xi = np.zeros((steps + 1, 6)); ua = np.zeros((steps, m))
-    xs_q[0], xs_xi[0] = x_q, x_xi
-    J = 0.0
-    for t in range(steps):
-        op = window_problem(prob, path_q, path_xi, t0, t)
-        r = restate_mpc_step(op, x_q, x_xi, us, first_iters if t == 0 else iters_per_step)
-        u0 = r["us"][0]
-        J += ob.cost(op, r["xs_q"][0], r["xs_xi"][0], u0, 0)[0]
-        x_q, x_xi = ob.f(op, r["xs_q"][0], r["xs_xi"][0], u0)
-        if noise is not None:
-            x_xi = x_xi + noise[t]
-        _, us = mpc_shift(r["xs_q"][None], r["us"][None], x_q[None], x_q[None])
-        us = us[0]
-        ua[t], xs_q[t + 1], xs_xi[t + 1] = u0, x_q, x_xi
-    return dict(xs_q=xs_q, xs_xi=xs_xi, us=ua, J=J)
 
 
 def test_new_symbols_in_header_capi_and_library():

@@ -1,7 +1,7 @@
 """max-regularisation LU branch, unit level: gains of one backward sweep, GPU vs fp64 oracle vs long-double oracle (the set-up of
 tests/test_gpu_parity.py::test_regularisation_loop_nonpd_branch: an indefinite R makes Q_uu non-PD)."""
 import sys, numpy as np
-sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
+sys.path.insert(0, '.')
 np.set_printoptions(precision=2, linewidth=220)
 from oracle import bridge as ob, bridge_ld as obl
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, workloads
@@ -10,8 +10,8 @@ R = np.diag([-30.0, 1e-3, 1e-3, -5.0, 1e-3, 1e-3])
 prob = TrackingProblem("se3", prob.J, prob.dt, prob.Q, R, prob.P, prob.q_ref, prob.xi_ref)
 B = 4
 rng = np.random.default_rng(5)
-from test_gpu_parity import _random_traj
-xs_q, xs_xi, us = _random_traj(prob, B, seed=5, spread=0.1)
+from tests.support import random_traj
+xs_q, xs_xi, us = random_traj(prob, B, seed=5, spread=0.1)
 op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
 r = BatchedTrackingILQR(prob, B).linearize_backward(xs_q, xs_xi, us, ms=True)
 for b in range(B):

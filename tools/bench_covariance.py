@@ -10,23 +10,17 @@ checks).  Cases: the covariance with its reduced outputs only (var_x, var_u, pos
 Reported per case: the median ms per call over the rounds, min and max, and the ratio to tolg_policy_rollout at S = 1."""
 import argparse
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trajectory_optimization_matrix_lie_groups_amd import workloads  # noqa: E402
+from _benchlib import add_common_args, emit, event_rounds, print_row, stats_row  # noqa: E402
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--B", type=int, default=4096)
-    ap.add_argument("--N", type=int, default=200)
-    ap.add_argument("--S", default="1,16,64")
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--iters", type=int, default=10, help="calls per timed region")
-    ap.add_argument("--out", default=None)
+    add_common_args(ap, "B", "N", "S", "rounds", "iters", "out", iters=10)
     a = ap.parse_args(argv)
     a.S = [int(s) for s in a.S.split(",")]
     if a.B < 1 or a.N < 1 or min(a.S) < 1 or a.rounds < 1 or a.iters < 1:
@@ -70,37 +64,19 @@ def main(argv=None):
         return s.lib.tolg_policy_rollout(s._h, B, name, p(dx0), p(w), p(J), p(st), None, None, None, s._stream())
 
     names = ["reduced", "full"] + list(a.S)
-    for n in names:  # warm-up and argument check
-        if call(n) != 0:
-            raise RuntimeError("launch failed: %s" % (n,))
-    torch.cuda.synchronize()
-    times = {n: [] for n in names}
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for r in range(a.rounds):
-        order = names[r % len(names):] + names[: r % len(names)]
-        for n in order:
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(a.iters):
-                call(n)
-            e1.record()
-            e1.synchronize()
-            times[n].append(e0.elapsed_time(e1) / a.iters)
-    base = statistics.median(times[1])
+    times = event_rounds(names, call, a.rounds, a.iters)
+    base = stats_row(times[1])["ms_median"]
     rows = []
     for n in names:
-        t = times[n]
-        med = statistics.median(t)
         row = dict(case="tolg_policy_covariance (%s)" % n if isinstance(n, str) else "tolg_policy_rollout S=%d" % n,
-                   ms_median=med, ms_min=min(t), ms_max=max(t), ratio_to_rollout_S1=med / base)
+                   **stats_row(times[n]))
+        row["ratio_to_rollout_S1"] = row["ms_median"] / base
         rows.append(row)
-        print(json.dumps(row))
+        print_row(row)
     finite = bool(torch.isfinite(var_x).all().item() and torch.isfinite(var_u).all().item() and torch.isfinite(pos).all().item())
     res = dict(B=B, N=N, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(dev), outputs_finite=finite, rows=rows)
-    print(json.dumps(dict(outputs_finite=finite)))
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    print_row(dict(outputs_finite=finite))
+    emit(res, a.out)
     return res
 
 

@@ -17,7 +17,6 @@ shooting, accept-always.
   alternated `tol-rounds` times.  Reported: mean iterations per step over steps 1.. (step 0 is cold for both), its maximum,
   the fraction of (trajectory, step) solves that stopped below the cap, and ms per step."""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -25,19 +24,20 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trajectory_optimization_matrix_lie_groups_amd import workloads  # noqa: E402
+from _benchlib import add_common_args, emit, print_row, rotated, stats_row  # noqa: E402
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--B", type=int, default=4096)
+    add_common_args(ap, "B")
     ap.add_argument("--N", default="200,50")
     ap.add_argument("--iters", default="0,1,3,5")
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=5)
+    add_common_args(ap, "rounds", rounds=5)
     ap.add_argument("--tol-steps", type=int, default=10)
     ap.add_argument("--tol-rounds", type=int, default=2)
     ap.add_argument("--max-iters", type=int, default=30)
-    ap.add_argument("--out", default=None)
+    add_common_args(ap, "out")
     a = ap.parse_args(argv)
     a.N = [int(x) for x in a.N.split(",")]
     a.iters = [int(x) for x in a.iters.split(",")]
@@ -77,19 +77,18 @@ def main(argv=None):
     times = {p: [] for p in pairs}
     status_ok = {}
     for r in range(a.rounds):
-        for p in pairs[r % len(pairs):] + pairs[: r % len(pairs)]:
+        for p in rotated(pairs, r):
             ms, res = timed(*p)
             times[p].append(ms)
             status_ok[p] = int((res.status == 0).sum().item())
     rows = []
     for p in pairs:
-        t = times[p]
-        med = statistics.median(t)
-        row = dict(part="step_time", N=p[0], iters_per_step=p[1], ms_per_step_median=med, ms_per_step_min=min(t),
-                   ms_per_step_max=max(t), mpc_steps_per_s=1e3 / med, trajectory_steps_per_s=B * 1e3 / med,
-                   status_ok=status_ok[p], solves=B * a.steps)
+        st = stats_row(times[p], "ms_per_step")
+        med = st["ms_per_step_median"]
+        row = dict(part="step_time", N=p[0], iters_per_step=p[1], **st, mpc_steps_per_s=1e3 / med,
+                   trajectory_steps_per_s=B * 1e3 / med, status_ok=status_ok[p], solves=B * a.steps)
         rows.append(row)
-        print(json.dumps(row))
+        print_row(row)
 
     tol = dict(tol_grad_norm=1e-6, tol_d_norm=1e-6)
     for N in a.N:
@@ -114,11 +113,9 @@ def main(argv=None):
                        same_iters_every_round=all((x[1] == acc[warm][0][1]).all() for x in acc[warm]),
                        status_ok=acc[warm][-1][2], solves=B * a.tol_steps)
             rows.append(row)
-            print(json.dumps(row))
+            print_row(row)
     res = dict(B=B, N=a.N, steps=a.steps, rounds=a.rounds, device=torch.cuda.get_device_name(0), rows=rows)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(res, a.out)
     return res
 
 

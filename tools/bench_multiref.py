@@ -16,35 +16,24 @@ the like-for-like one there, `active` says how many were still being solved at t
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trajectory_optimization_matrix_lie_groups_amd import workloads  # noqa: E402
+from _benchlib import LINES, add_common_args, emit, print_row, rate_rounds, require_gpu, solve_rate_region, summary  # noqa: E402
 
-LINES = {
-    "headline": (dict(mode="ms", line_search=False, schedule="auto"), 300),
-    "merit": (dict(mode="ms", line_search=True, schedule="auto"), 100),
-    "ss": (dict(mode="ss", line_search=False, schedule="auto"), 60),
-}
 VARIANTS = ("shared", "broadcast", "distinct")
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--lines", default="headline,merit,ss")
+    add_common_args(ap, "lines")
     ap.add_argument("--variants", default=",".join(VARIANTS), help="a subset: one variant per process under a profiler")
-    ap.add_argument("--B", type=int, default=4096)
-    ap.add_argument("--N", type=int, default=200)
+    add_common_args(ap, "B", "N")
     ap.add_argument("--refs", type=int, default=64)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--steps", type=int, default=0, help="timed iterations per region (0: the line's default)")
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--dry", action="store_true", help="build the inputs and print the plan; no GPU")
+    add_common_args(ap, "rounds", "steps", "warmup", "out", "dry")
     a = ap.parse_args(argv)
     a.lines = a.lines.split(",")
     a.variants = tuple(v for v in VARIANTS if v in a.variants.split(","))
@@ -65,51 +54,31 @@ def inputs(a):
     return prob, us, {"shared": (q0, xi0, None, None), "broadcast": (q0, xi0, q_bc, xi_bc), "distinct": (q, xi, q_ref, xi_ref)}
 
 
-def summary(rates):
-    med = statistics.median(rates)
-    return dict(median=med, min=min(rates), max=max(rates), spread=(max(rates) - min(rates)) / med, runs=rates)
-
-
 def run_line(name, a, prob, us, variants):
     import torch
     from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
     kw, K0 = LINES[name]
     K, W = a.steps or K0, a.warmup
     solver = BatchedTrackingILQR(prob, a.B)
-    dev = solver.device
-    f64 = dict(dtype=torch.float64, device=dev)
+    f64 = dict(dtype=torch.float64, device=solver.device)
     us_d = torch.as_tensor(us, **f64)
     dev_in = {v: tuple(None if x is None else torch.as_tensor(x, **f64) for x in t) for v, t in variants.items()}
     V = a.variants
-    rates = {v: [] for v in V}
     active, status_ok = {}, {}
 
     def region(v):
         q_d, xi_d, qr, xr = dev_in[v]
-        solver.solve_begin(q_d, xi_d, us_d, n_iterations=W + K, tol_grad_norm=0.0, tol_d_norm=0.0, q_ref=qr, xi_ref=xr,
-                           **kw)
-        solver.solve_iterate(W)
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        solver.solve_iterate(K)
-        torch.cuda.synchronize(dev)
-        t1 = time.perf_counter()
-        res = solver.solve_end()
-        torch.cuda.synchronize(dev)
+        rate, res = solve_rate_region(solver, (q_d, xi_d, us_d), dict(q_ref=qr, xi_ref=xr, **kw), W, K)
         active[v] = float((res.iters == W + K).double().mean().item())
         status_ok[v] = float((res.status == 0).double().mean().item())
-        return K / (t1 - t0)
+        return rate
 
-    for v in V:  # warm-up: every kernel of every variant loaded and run once
-        region(v)
-    for r in range(a.rounds):
-        order = V[r % len(V):] + V[:r % len(V)]
-        for v in order:
-            rates[v].append(region(v))
+    rates = rate_rounds(V, region, a.rounds)
     out = dict(line=name, B=a.B, N=a.N, refs=a.refs, steps=K, warmup=W, rounds=a.rounds, unit="batch-iterations/s",
                variants={v: dict(summary(rates[v]), active=active[v], status_ok=status_ok[v]) for v in V})
     base = out["variants"]["shared"]["median"] if "shared" in V else float("nan")
     out["ratio_to_shared"] = {v: out["variants"][v]["median"] / base for v in V}
+    dev = solver.device
     del solver
     torch.cuda.synchronize(dev)
     return out
@@ -123,14 +92,12 @@ def main(argv=None):
                               steps={n: a.steps or LINES[n][1] for n in a.lines}, warmup=a.warmup,
                               distinct_references=int(len(np.unique(variants["distinct"][2][:, 0, 0, 3]))))))
         return 0
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_multiref: no GPU visible (there is nothing to time on the CPU)")
+    require_gpu("bench_multiref")
     results = []
     for name in a.lines:
         r = run_line(name, a, prob, us, variants)
         results.append(r)
-        print(json.dumps(r), flush=True)
+        print_row(r)
     print("%-9s %-10s %10s %10s %10s %8s %7s %7s %7s" % ("line", "variant", "median", "min", "max", "spread", "ratio", "active",
                                                        "ok"))
     for r in results:
@@ -139,10 +106,7 @@ def main(argv=None):
             print("%-9s %-10s %10.1f %10.1f %10.1f %7.2f%% %7.4f %7.3f %7.3f" % (
                 r["line"], v, s["median"], s["min"], s["max"], 100 * s["spread"], r["ratio_to_shared"][v], s["active"],
                 s["status_ok"]))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(results, f, indent=1)
+    emit(results, a.out)
     return 0
 
 

@@ -6,52 +6,35 @@ usage: python tools/bench_obstacles.py [--lines headline,merit,ss] [--Ks 0,1,4,8
                                        [--steps K] [--warmup W] [--al] [--out FILE.json] [--dry]
 
 One process, one handle per line; the variants are timed in alternation, round after round (the order rotates every round),
-each region being iterations W .. W+K of a fresh solve between two device synchronisations (tools/bench_weights.py's
-method).  The multipliers are fixed (lambda 0.1, I_mu 1e-2: what the first outer iteration of al_fit_batch sees, with
-lambda > 0 so that no term is zero).  Per variant the line reports the median rate (batch iterations per second), the
-lowest and highest, the spread (max - min) / median, and the median over the no-sphere variant's."""
+each region being iterations W .. W+K of a fresh solve between two device synchronisations (tools/_benchlib.py's
+solve_rate_region and rate_rounds, as in tools/bench_weights.py).  The multipliers are fixed (lambda 0.1, I_mu 1e-2: what
+the first outer iteration of al_fit_batch sees, with lambda > 0 so that no term is zero).  Per variant the line reports the
+median rate (batch iterations per second), the lowest and highest, the spread (max - min) / median, and the median over the
+no-sphere variant's."""
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
-import numpy as np
-
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trajectory_optimization_matrix_lie_groups_amd import workloads  # noqa: E402
-
-LINES = {
-    "headline": (dict(mode="ms", line_search=False, schedule="auto"), 300),
-    "merit": (dict(mode="ms", line_search=True, schedule="auto"), 100),
-    "ss": (dict(mode="ss", line_search=False, schedule="auto"), 60),
-}
+from _benchlib import LINES, add_common_args, emit, print_row, rate_rounds, require_gpu, solve_rate_region, summary  # noqa: E402
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--lines", default="headline,merit,ss")
+    add_common_args(ap, "lines")
     ap.add_argument("--Ks", default="0,1,4,8", help="spheres per trajectory of each variant (0: none attached)")
-    ap.add_argument("--B", type=int, default=4096)
-    ap.add_argument("--N", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--steps", type=int, default=0, help="timed iterations per region (0: the line's default)")
-    ap.add_argument("--warmup", type=int, default=5)
+    add_common_args(ap, "B", "N", "rounds", "steps", "warmup")
     ap.add_argument("--al", action="store_true", help="also time one al_fit_batch on the K = max(Ks) field")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--dry", action="store_true", help="build the inputs and print the plan; no GPU")
+    add_common_args(ap, "out", "dry")
     a = ap.parse_args(argv)
     a.lines = a.lines.split(",")
     a.Ks = tuple(int(k) for k in a.Ks.split(","))
     if any(x not in LINES for x in a.lines) or any(not 0 <= k <= 16 for k in a.Ks) or a.B < 1 or a.rounds < 1:
         ap.error("lines from %s; 0 <= K <= 16; B, rounds >= 1" % sorted(LINES))
     return a
-
-
-def summary(rates):
-    med = statistics.median(rates)
-    return dict(median=med, min=min(rates), max=max(rates), spread=(max(rates) - min(rates)) / med, runs=rates)
 
 
 def run_line(name, a, prob, q0, xi0, us, obs):
@@ -64,30 +47,17 @@ def run_line(name, a, prob, q0, xi0, us, obs):
     f64 = dict(dtype=torch.float64, device=dev)
     q_d, xi_d, us_d = (torch.as_tensor(x, **f64) for x in (q0, xi0, us))
     mult = {k: (torch.full((a.B, a.N + 1, k), 0.1, **f64), torch.full((a.B, a.N + 1, k), 1e-2, **f64)) for k in a.Ks if k}
-    rates = {k: [] for k in a.Ks}
 
     def region(k):
         if k:
             solver.set_al_obstacles(obs[:, :k], *mult[k])
-        solver.solve_begin(q_d, xi_d, us_d, n_iterations=W + K, tol_grad_norm=0.0, tol_d_norm=0.0, **kw)
-        solver.solve_iterate(W)
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        solver.solve_iterate(K)
-        torch.cuda.synchronize(dev)
-        t1 = time.perf_counter()
-        solver.solve_end()
+        rate, _ = solve_rate_region(solver, (q_d, xi_d, us_d), kw, W, K)
         if k:
             solver.set_al_obstacles(None)
-        torch.cuda.synchronize(dev)
-        return K / (t1 - t0)
+            torch.cuda.synchronize(dev)
+        return rate
 
-    for k in a.Ks:  # warm-up
-        region(k)
-    for r in range(a.rounds):
-        order = a.Ks[r % len(a.Ks):] + a.Ks[:r % len(a.Ks)]
-        for k in order:
-            rates[k].append(region(k))
+    rates = rate_rounds(a.Ks, region, a.rounds)
     out = dict(line=name, B=a.B, N=a.N, steps=K, warmup=W, rounds=a.rounds, unit="batch-iterations/s",
                variants={"K=%d" % k: summary(rates[k]) for k in a.Ks})
     if 0 in a.Ks:
@@ -121,27 +91,22 @@ def main(argv=None):
         print(json.dumps(dict(plan=a.lines, Ks=a.Ks, B=a.B, N=prob.N, rounds=a.rounds, al=a.al,
                               steps={n: a.steps or LINES[n][1] for n in a.lines}, warmup=a.warmup)))
         return 0
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_obstacles: no GPU visible (there is nothing to time on the CPU)")
+    require_gpu("bench_obstacles")
     results = []
     for name in a.lines:
         r = run_line(name, a, prob, q0, xi0, us, obs)
         results.append(r)
-        print(json.dumps(r), flush=True)
+        print_row(r)
     if a.al:
         r = run_al(a, prob, q0, xi0, us, obs)
         results.append(r)
-        print(json.dumps(r), flush=True)
+        print_row(r)
     print("%-9s %-6s %10s %10s %10s %8s %7s" % ("line", "K", "median", "min", "max", "spread", "ratio"))
     for r in results:
         for v, s in r.get("variants", {}).items():
             print("%-9s %-6s %10.1f %10.1f %10.1f %7.2f%% %7.4f" % (r["line"], v, s["median"], s["min"], s["max"],
                                                                    100 * s["spread"], r.get("ratio_to_none", {}).get(v, float("nan"))))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(results, f, indent=1)
+    emit(results, a.out)
     return 0
 
 

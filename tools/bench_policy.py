@@ -14,24 +14,19 @@ bytes the call has to move at least (inputs, outputs, and the nominal data -- ga
 and trajectory -- read once per wavefront that needs it: ceil(S / 16) times in `samples` order, S times in `traj` order)."""
 import argparse
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trajectory_optimization_matrix_lie_groups_amd import workloads  # noqa: E402
+from _benchlib import add_common_args, emit, event_rounds, print_row, stats_row  # noqa: E402
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--B", type=int, default=4096)
-    ap.add_argument("--N", type=int, default=200)
-    ap.add_argument("--S", default="1,16,64")
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--iters", type=int, default=20, help="calls per timed region")
+    add_common_args(ap, "B", "N", "S", "rounds", "iters")
     ap.add_argument("--layouts", default="samples,traj")
-    ap.add_argument("--out", default=None)
+    add_common_args(ap, "out")
     a = ap.parse_args(argv)
     a.S = [int(s) for s in a.S.split(",")]
     a.layouts = [x for x in ("samples", "traj") if x in a.layouts.split(",")]
@@ -84,28 +79,11 @@ def main(argv=None):
         return s.lib.tolg_policy_rollout(s._h, B, S, p(dx0), p(w), p(J), p(st), None, None, None, s._stream())
 
     names = [(layout, S) for S in a.S for layout in a.layouts] + ["rollout"]
-    for n in names:  # warm-up and argument check
-        if call(n) != 0:
-            raise RuntimeError("launch failed: %s" % (n,))
-    torch.cuda.synchronize()
-    times = {n: [] for n in names}
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for r in range(a.rounds):
-        order = names[r % len(names):] + names[: r % len(names)]
-        for n in order:
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(a.iters):
-                call(n)
-            e1.record()
-            e1.synchronize()
-            times[n].append(e0.elapsed_time(e1) / a.iters)
+    times = event_rounds(names, call, a.rounds, a.iters)
     rows = []
     for n in names:
-        t = times[n]
-        med = statistics.median(t)
-        row = dict(kernel="tolg_rollout(ms=0, alpha=0)" if n == "rollout" else "tolg_policy_rollout",
-                   ms_median=med, ms_min=min(t), ms_max=max(t))
+        row = dict(kernel="tolg_rollout(ms=0, alpha=0)" if n == "rollout" else "tolg_policy_rollout", **stats_row(times[n]))
+        med = row["ms_median"]
         if n == "rollout":
             row.update(S=1, steps_per_s=B * N / (med * 1e-3))
         else:
@@ -116,11 +94,9 @@ def main(argv=None):
                        hbm_GBps_est=nb / (med * 1e-3) / 1e9, status_ok=int((st == 0).sum().item()),
                        J_finite=int(torch.isfinite(inputs[S][2]).sum().item()))
         rows.append(row)
-        print(json.dumps(row))
+        print_row(row)
     res = dict(B=B, N=N, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(dev), rows=rows)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(res, a.out)
     return res
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised parity sweep of the augmented-Lagrangian outer loop (AL_iLQR_Tracking_SE3_MS, traopt_controller.py:3218-3293)
-on the GPU against the outer loop restated around the oracle (tests/test_gpu_parity.py::_al_oracle -- the reference class
+on the GPU against the outer loop restated around the oracle (tests/checks.py::al_oracle -- the reference class
 does not run at HEAD, SURVEY App. C-Q7, so parity is unpinned here as everywhere for this class): random constant-twist
 references, weights, box bounds that the unconstrained solution violates, penalty schedules, horizons, batches.
     python tools/parity_fuzz_al.py [cases] [first seed]"""
@@ -11,7 +11,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tests.test_gpu_parity import _al_oracle  # noqa: E402
+from tests.checks import al_oracle  # noqa: E402
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, workloads  # noqa: E402
 from trajectory_optimization_matrix_lie_groups_amd.workloads import _se3_exp  # noqa: E402
 
@@ -47,7 +47,7 @@ def one(seed):
     worst = dict(J=0.0, u=0.0, lam=0.0)
     notes = []
     for b in range(B):
-        o, lam, imu, mu, n_outer = _al_oracle(prob, x0_q[b], x0_xi[b], us0[b], lb, ub, n_al, n_in, kw["tol_constr"], mu0=kw["mu0"],
+        o, lam, imu, mu, n_outer = al_oracle(prob, x0_q[b], x0_xi[b], us0[b], lb, ub, n_al, n_in, kw["tol_constr"], mu0=kw["mu0"],
                                               mu_scale=kw["mu_scale"])
         n = int(res.iters[b])
         if n != o["n_iters"]:
