@@ -308,8 +308,8 @@ int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, double* d_ecc
  *     final iterate).
  * tolg_create, tolg_solve_begin and tolg_solve_begin_warm clear it; so does tolg_eval_knot (it overwrites the nominal
  * trajectory).  tolg_rollout (writes the candidate arrays only), tolg_expected_change, tolg_set_al, tolg_al_update,
- * tolg_set_refs, tolg_set_ref_windows, tolg_set_weights, tolg_set_al_obstacles, tolg_al_update_state, tolg_mpc_advance and
- * tolg_policy_covariance leave it; the calls that read it use the
+ * tolg_set_refs, tolg_set_ref_windows, tolg_set_weights, tolg_set_al_obstacles, tolg_al_update_state, tolg_mpc_advance,
+ * tolg_policy_covariance and tolg_policy_value leave it; the calls that read it use the
  * references and weights set when they run.
  * Both calls return TOLG_E_ARG when no policy is held, during a solve in flight, for a B other than the held batch's, when
  * references or weights per trajectory are set for another B, and (tolg_policy_rollout) for S < 1.  Neither modifies
@@ -375,6 +375,45 @@ int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, double* d_x_
  * the SO3 family (no translation: the rule of tolg_set_al_obstacles). */
 int tolg_policy_covariance(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, double* d_Sigma, double* d_var_x,
                            double* d_var_u, double* d_pos_cov, void* stream);
+
+/* tolg_policy_value: the cost-to-go of the held policy, V_i(e) ~ p_i . e + e^T P_i e / 2, the backward companion of
+ * tolg_policy_covariance.  In the same coordinates, e_i = [Log(q*_i^-1 q^_i); xi^_i - xi*_i] (twist order [omega, v]), about
+ * the held nominal x*_i, u*_i:
+ *   A_i, B_i, Acl_i = A_i + B_i K_i        as in tolg_policy_covariance: linearised by this call at the held nominal
+ *   l_x, l_xx, l_u, l_uu at (x*_i, u*_i)   the tracking cost's derivatives as tolg_eval_knot gives them (Gauss-Newton l_xx,
+ *                                          l_ux = 0), with trajectory b's own reference and weights when tolg_set_refs /
+ *                                          tolg_set_weights are active; no augmented-Lagrangian or keep-out terms (the rule
+ *                                          of tolg_policy_rollout's J)
+ *   M_i = l_xx + K_i^T l_uu K_i  (i < N),  M_N = l_xx^N
+ *   P_N = M_N,  p_N = l_x^N
+ *   P_i = M_i + Acl_i^T P_{i+1} Acl_i,  p_i = l_x + K_i^T l_u + Acl_i^T p_{i+1}      i = N-1 .. 0
+ *   price_i = tr(P_{i+1}[6:12,6:12] W) / 2      what the twist disturbance added after step i costs, i = 0 .. N-1
+ *   excess  = tr(P_0 Sigma0) / 2 + sum_i price_i   the expected closed-loop cost above the unperturbed one under (Sigma0, W),
+ *                                                  to second order in the model's linearisation
+ * p_0 is the gradient of the closed-loop cost with respect to the start error dx0, and excess equals
+ * sum_{i <= N} tr(M_i Sigma_i) / 2 with tolg_policy_covariance's Sigma_i (an exact identity of the two recursions).
+ * This is the cost-to-go of the MODEL THE SOLVER PLANS WITH: the reference's Jacobians (its f_x and the Jacobian of its
+ * tracking error are approximate) and Gauss-Newton Hessians, not exact derivatives.  Measured on the CPU restatement
+ * (se3_tracking, N = 20) against central differences of the closed-loop cost: p_N[6:12] agrees to 2e-11 (the terminal cost is
+ * quadratic in the twist), p_0 to 1.5e-3 of max |p_0| on an off-nominal policy and 6e-5 on a converged one, interior knots
+ * to ~1e-4 -- a gap that does not shrink with the step of the difference; v^T P_0 v is within 1.3 % of the second difference.
+ * Multiple-shooting defects of the nominal are ignored, as in the covariance; a plant, an input box and keep-out spheres
+ * too -- the same bits with and without them.
+ *   in : d_Sigma0 [B][12][12] or NULL (= 0), d_W [B][6][6] or NULL (= 0); only the upper triangles are read
+ *   out: d_P [B][N+1][12][12]     computed as a symmetric matrix and mirrored: equal to its transpose to the bit
+ *        d_p [B][N+1][12]
+ *        d_diag_P [B][N+1][12]    diag P_i (the bits of d_P's diagonal)
+ *        d_price [B][N]
+ *        d_excess [B]
+ * Every output may be NULL, and a NULL output costs nothing (d_P is 0.95 GB at 4096 x 200).  Sigma0 = W = 0, or both NULL,
+ * gives exact zeros in d_price and d_excess; P and p do not depend on Sigma0 or W.  A trajectory's bits depend on neither B
+ * nor its neighbours, nor on which outputs are asked for.  For the SO3 family the state is carried in the SE(3) layout as
+ * everywhere in this header: rows / columns 3..5 and 9..11 (the unused translation and linear velocity) carry no cost --
+ * they hold exact zeros when the weights and the gains' columns of those coordinates are zero, as they are for the embedded
+ * problems; pass zeros there in Sigma0 and W.
+ * The call does not modify the held policy.  TOLG_E_ARG: the conditions of tolg_solve_gains. */
+int tolg_policy_value(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, double* d_P, double* d_p,
+                      double* d_diag_P, double* d_price, double* d_excess, void* stream);
 
 /* Plants: per-sample dynamics parameters that step the closed loops of tolg_policy_rollout and tolg_mpc_advance in place of
  * the model's (model mismatch: a payload change, a mis-identified inertia, domain randomisation).  The planner's model stays

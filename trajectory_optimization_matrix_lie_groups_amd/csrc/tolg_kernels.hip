@@ -3224,6 +3224,84 @@ TOLG_DEV void pc_apply(const double* L, const double (&x)[12], double (&y)[12]) 
     y[6 + r] = t;
   }
 }
+// The closed loop's Acl_i = f_x + f_u K_i at the held nominal into the row's LDS, in two steps with a barrier between them
+// (shared by k_policy_covariance and k_policy_value).  Step one, every lane redundantly: the blocks of f_x at (x*_i, u*_i) --
+// lin_knot's dynamics part with the closed-form coefficients -- stored by lane 0, and the gain rows the lanes hold; the
+// pendulum's input block of the knot goes to Bt.
+template <int M, int PK>
+TOLG_DEV void pc_build_acl(const Consts& C, double dt, const State& Sa, const RollIn<M>& Rin, int l, double* L, double (&Bt)[9]) {
+  const V3 wd = dt * Sa.w, vd = dt * Sa.v;
+  const SO3Coef kc = so3_coef(dot(wd, wd), true);
+  Pose E;
+  E.q = so3_exp(wd);
+  E.t = ljac_apply(wd, kc, vd);
+  const Pose Ei = se3_inverse(E);
+  double Ri[9], Ti[9], TR[9], Jr3[9], Qr[9], a22[36];
+  q_to_R(Ei.q, Ri);
+  skew(Ei.t, Ti);
+  mul33(Ti, Ri, TR);
+  ljac33(neg(wd), kc, Jr3);
+  Q33(neg(vd), neg(wd), kc, Qr);
+  a22_build(C, Sa.w, Sa.v, a22);
+  V3 rte = v3(0, 0, 0);
+  if constexpr (PK == 1) {
+    rte = qrot_inv(Sa.X.q, v3(Rin.u[0], Rin.u[1], Rin.u[2] - C.grav));
+    double Rm[9], SR[9], Bu[9];
+    q_to_R(Sa.X.q, Rm);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      SR[c] = C.pend_k * Rm[3 * c + 1];
+      SR[3 + c] = -C.pend_k * Rm[3 * c + 0];
+      SR[6 + c] = 0.0;
+    }
+    mul33(C.Ibinv, SR, Bu);
+#pragma unroll
+    for (int k = 0; k < 9; k++) Bt[k] = dt * Bu[k];
+  } else if (C.grav != 0.0) {
+    rte = qrot_inv(Sa.X.q, v3(0, 0, -1.0));
+  }
+  if (l == 0) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+      L[PC_TOP + k] = Ri[k]; L[PC_TOP + 9 + k] = TR[k];
+      L[PC_TOP + 18 + k] = dt * Jr3[k]; L[PC_TOP + 27 + k] = dt * Qr[k];
+    }
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        L[PC_BOT + 12 * r + c] = rte.x * C.Llin[0][6 * r + c] + rte.y * C.Llin[1][6 * r + c] + rte.z * C.Llin[2][6 * r + c];
+        L[PC_BOT + 12 * r + 3 + c] = 0.0;
+      }
+#pragma unroll
+      for (int c = 0; c < 6; c++) L[PC_BOT + 12 * r + 6 + c] = a22[6 * c + r];
+    }
+  }
+  if (2 * l < M) {  // gain rows 2l and 2l + 1
+#pragma unroll
+    for (int c = 0; c < 12; c++) { L[PC_K + 12 * (2 * l) + c] = Rin.G[0][c]; L[PC_K + 12 * (2 * l + 1) + c] = Rin.G[1][c]; }
+  }
+}
+// Step two: lane j folds f_u K into column j of the dense lower half (col: the lane stores); kj: column j of K
+template <int M>
+TOLG_DEV void pc_fold_fuk(double* L, int j, bool col, const double (&Bt)[9], const double (&Bb)[9], double (&kj)[M]) {
+  double a[6];
+#pragma unroll
+  for (int u = 0; u < M; u++) kj[u] = L[PC_K + 12 * u + j];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    double t = L[PC_BOT + 12 * r + j], m = L[PC_BOT + 12 * (3 + r) + j];
+#pragma unroll
+    for (int u = 0; u < 3; u++) t += Bt[3 * r + u] * kj[u];
+#pragma unroll
+    for (int u = 3; u < M; u++) m += Bb[3 * r + (u - 3)] * kj[u];
+    a[r] = t; a[3 + r] = m;
+  }
+  if (col) {
+#pragma unroll
+    for (int r = 0; r < 6; r++) L[PC_BOT + 12 * r + j] = a[r];
+  }
+}
 // the outputs of knot i from the row's Sigma in LDS (upper triangle); S: the nominal state of the knot (pos_cov's rotation)
 TOLG_DEV void pc_outputs(const double* L, bool live, int l, size_t bk, const State& S, double* __restrict__ Sig,
                          double* __restrict__ var_x, double* __restrict__ pos_cov) {
@@ -3294,76 +3372,11 @@ __global__ __launch_bounds__(64) void k_policy_covariance(Params P, const double
     RollIn<M> Rin;
     roll_load<M, true>(P, i, b, l, vb, sB, Rin);
     pc_outputs(L, live, l, (size_t)b * (N + 1) + i, Sa, Sig, var_x, pos_cov);
-    // ---- the blocks of f_x at (x*_i, u*_i): lin_knot's dynamics part with the closed-form coefficients
-    const V3 wd = dt * Sa.w, vd = dt * Sa.v;
-    const SO3Coef kc = so3_coef(dot(wd, wd), true);
-    Pose E;
-    E.q = so3_exp(wd);
-    E.t = ljac_apply(wd, kc, vd);
-    const Pose Ei = se3_inverse(E);
-    double Ri[9], Ti[9], TR[9], Jr3[9], Qr[9], a22[36];
-    q_to_R(Ei.q, Ri);
-    skew(Ei.t, Ti);
-    mul33(Ti, Ri, TR);
-    ljac33(neg(wd), kc, Jr3);
-    Q33(neg(vd), neg(wd), kc, Qr);
-    a22_build(C, Sa.w, Sa.v, a22);
-    V3 rte = v3(0, 0, 0);
-    if constexpr (PK == 1) {
-      rte = qrot_inv(Sa.X.q, v3(Rin.u[0], Rin.u[1], Rin.u[2] - C.grav));
-      double Rm[9], SR[9], Bu[9];
-      q_to_R(Sa.X.q, Rm);
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        SR[c] = C.pend_k * Rm[3 * c + 1];
-        SR[3 + c] = -C.pend_k * Rm[3 * c + 0];
-        SR[6 + c] = 0.0;
-      }
-      mul33(C.Ibinv, SR, Bu);
-#pragma unroll
-      for (int k = 0; k < 9; k++) Bt[k] = dt * Bu[k];
-    } else if (C.grav != 0.0) {
-      rte = qrot_inv(Sa.X.q, v3(0, 0, -1.0));
-    }
-    if (l == 0) {
-#pragma unroll
-      for (int k = 0; k < 9; k++) {
-        L[PC_TOP + k] = Ri[k]; L[PC_TOP + 9 + k] = TR[k];
-        L[PC_TOP + 18 + k] = dt * Jr3[k]; L[PC_TOP + 27 + k] = dt * Qr[k];
-      }
-#pragma unroll
-      for (int r = 0; r < 6; r++) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-          L[PC_BOT + 12 * r + c] = rte.x * C.Llin[0][6 * r + c] + rte.y * C.Llin[1][6 * r + c] + rte.z * C.Llin[2][6 * r + c];
-          L[PC_BOT + 12 * r + 3 + c] = 0.0;
-        }
-#pragma unroll
-        for (int c = 0; c < 6; c++) L[PC_BOT + 12 * r + 6 + c] = a22[6 * c + r];
-      }
-    }
-    if (2 * l < M) {  // gain rows 2l and 2l + 1
-#pragma unroll
-      for (int c = 0; c < 12; c++) { L[PC_K + 12 * (2 * l) + c] = Rin.G[0][c]; L[PC_K + 12 * (2 * l + 1) + c] = Rin.G[1][c]; }
-    }
+    pc_build_acl<M, PK>(C, dt, Sa, Rin, l, L, Bt);  // the blocks of f_x at (x*_i, u*_i), the gains
     __syncthreads();
     {  // column j of the lower half: + f_u K
-      double kj[M], a[6];
-#pragma unroll
-      for (int u = 0; u < M; u++) kj[u] = L[PC_K + 12 * u + j];
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        double t = L[PC_BOT + 12 * r + j], m = L[PC_BOT + 12 * (3 + r) + j];
-#pragma unroll
-        for (int u = 0; u < 3; u++) t += Bt[3 * r + u] * kj[u];
-#pragma unroll
-        for (int u = 3; u < M; u++) m += Bb[3 * r + (u - 3)] * kj[u];
-        a[r] = t; a[3 + r] = m;
-      }
-      if (col) {
-#pragma unroll
-        for (int r = 0; r < 6; r++) L[PC_BOT + 12 * r + j] = a[r];
-      }
+      double kj[M];
+      pc_fold_fuk<M>(L, j, col, Bt, Bb, kj);
       if (var_u) {  // diag K Sigma K^T: lane j's terms K[u][j] (Sigma[j, :] K[u, :]^T), summed over j by lane u
 #pragma unroll
         for (int u = 0; u < M; u++) {
@@ -3403,6 +3416,287 @@ __global__ __launch_bounds__(64) void k_policy_covariance(Params P, const double
     Sa = Sb;
   }
   pc_outputs(L, live, l, (size_t)b * (N + 1) + N, Sa, Sig, var_x, pos_cov);
+}
+
+// Cost-to-go of the held policy (tolg_policy_value): V_i(e) ~ p_i . e + e^T P_i e / 2 about the held nominal, the backward twin
+// of k_policy_covariance on the same plan: one 16-lane row per trajectory, lane j < 12 holds column j (= row j) of the
+// symmetric P in registers, Acl_i = f_x + f_u K_i built HERE at (x*_i, u*_i) by the covariance kernel's device functions
+// (pc_build_acl, pc_fold_fuk) with the closed-form coefficients -- a trajectory's bits depend on nothing but itself.  Walking
+// i = N .. 0, a knot is two applications of y = Acl^T x per lane with one transpose through LDS between them:
+//   T[:, j] = Acl^T P[:, j];  P'[j, :] = Acl^T T[j, :]^T + M_i[j, :],  M_i = l_xx + K^T l_uu K  (M_N = l_xx^N).
+// Entry {r, c} of the next P is the one lane min(r, c) computed, M's entry included: every lane reads its column back from
+// the upper triangle, so P is symmetric to the bit.  p_i = l_x + K^T l_u + Acl^T p_{i+1} is one more application, done by every
+// lane of the row alike (no cross-lane traffic; skipped when d_p is NULL -- nothing else depends on p).
+// price_i = tr(P_{i+1}[6:12, 6:12] W) / 2 is summed by lane 0 from the six partial sums of the twist lanes, in lane order.
+// The cost derivatives (pv_cost) are the tracking cost's as lin_knot states them -- RefAt / wblock, J_e = Jr^-1(e) Ad(Xref),
+// Gauss-Newton l_xx = 2 J_e^T W J_e, the weight selection of the terminal knot -- with the closed-form Log and coefficients
+// and without augmented-Lagrangian or keep-out terms (the rule of tolg_policy_rollout's J).
+// LDS per trajectory (doubles): the covariance kernel's fields (PC_SG holds P, PC_TT holds T), then the knot's cost terms.
+enum { PV_LXX = PC_F, PV_LTT = PV_LXX + 36, PV_LX = PV_LTT + 36, PV_LU = PV_LX + 12, PV_LUU = PV_LU + 6, PV_Q = PV_LUU + 36,
+       PV_F = PV_Q + 12 };
+// y = Acl^T x from the row's LDS: the transpose twin of pc_apply, the same block form (126 multiply-adds), a fixed order
+TOLG_DEV void pv_apply_t(const double* L, const double (&x)[12], double (&y)[12]) {
+  const double *RI = L + PC_TOP, *TRI = RI + 9, *JR = RI + 18, *QR = RI + 27, *BOT = L + PC_BOT;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      t0 += RI[3 * r + c] * x[r] + TRI[3 * r + c] * x[3 + r];
+      t1 += RI[3 * r + c] * x[3 + r];
+      t2 += JR[3 * r + c] * x[r] + QR[3 * r + c] * x[3 + r];
+      t3 += JR[3 * r + c] * x[3 + r];
+    }
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+      t0 += BOT[12 * r + c] * x[6 + r];
+      t1 += BOT[12 * r + 3 + c] * x[6 + r];
+      t2 += BOT[12 * r + 6 + c] * x[6 + r];
+      t3 += BOT[12 * r + 9 + c] * x[6 + r];
+    }
+    y[c] = t0; y[3 + c] = t1; y[6 + c] = t2; y[9 + c] = t3;
+  }
+}
+// l_x, l_xx (pose block and twist block, each 6 x 6 and symmetric), l_u, l_uu of knot i at (S, u) into the row's LDS; every
+// lane computes them, `writer` stores
+template <int M, int PT>
+TOLG_DEV void pv_cost(const Params& P, const Consts& C, int i, int b, const State& S, const double (&u)[M], bool term, bool writer,
+                      double* L) {
+  constexpr bool PTW = (PT & PT_W) != 0;
+  const RefAt<(PT & PT_REF) != 0> r(P.ref, i, b, P.Bp);
+  Pose Xr;
+  Xr.q.x = r[0]; Xr.q.y = r[1]; Xr.q.z = r[2]; Xr.q.w = r[3];
+  Xr.t = v3(r[4], r[5], r[6]);
+  V3 ew, ev;
+  se3_log(se3_compose(S.X, se3_inverse(Xr)), ew, ev);
+  // weights: l_xx switches to P at the terminal knot; l_x too, except for the SO3 cost which keeps Q there (lin_knot)
+  const bool so3 = so3_family(C.kind);
+  const auto W1 = wblock<PTW, 6>(C.wts, P, b, term, C.P1, C.W1, WT_P1, WT_W1);
+  const auto W2 = wblock<PTW, 6>(C.wts, P, b, term, C.P2, C.W2, WT_P2, WT_W2);
+  const auto G1 = wblock<PTW, 6>(C.wts, P, b, term && !so3, C.P1, C.W1, WT_P1, WT_W1);
+  const auto G2 = wblock<PTW, 6>(C.wts, P, b, term && !so3, C.P2, C.W2, WT_P2, WT_W2);
+  const double e[6] = {ew.x, ew.y, ew.z, ev.x, ev.y, ev.z};
+  const double ve[6] = {S.w.x - r[7], S.w.y - r[8], S.w.z - r[9], S.v.x - r[10], S.v.y - r[11], S.v.z - r[12]};
+  const double th2 = dot(ew, ew);
+  double Ji[9], Qr[9], T1[9], Bm[9], Rr[9], Tr[9], Ja[9], Jb[9];
+  ljacinv33(neg(ew), ljacinv_coef(th2), Ji);  // Jr^-1(w) = Jl^-1(-w)
+  Q33(neg(ev), neg(ew), so3_coef(th2, true), Qr);
+  mul33(Ji, Qr, T1);
+  mul33(T1, Ji, Bm);  // rjacinv lower-left block = -Bm
+  q_to_R(Xr.q, Rr);
+  skew(Xr.t, Tr);
+  mul33(Ji, Rr, Ja);
+  mul33(Ji, Tr, T1);
+#pragma unroll
+  for (int k = 0; k < 9; k++) T1[k] -= Bm[k];
+  mul33(T1, Rr, Jb);
+  double Je[36];  // J_e = [[Ja, 0],[Jb, Ja]]
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      Je[6 * a + c] = Ja[3 * a + c];
+      Je[6 * a + c + 3] = 0;
+      Je[6 * (a + 3) + c] = Jb[3 * a + c];
+      Je[6 * (a + 3) + c + 3] = Ja[3 * a + c];
+    }
+  double We[6], W2v[6], WJ[36];
+#pragma unroll
+  for (int a = 0; a < 6; a++) {
+    double s1 = 0, s2 = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) { s1 += G1[6 * a + k] * e[k]; s2 += G2[6 * a + k] * ve[k]; }
+    We[a] = s1; W2v[a] = s2;
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      double s = 0;
+#pragma unroll
+      for (int k = 0; k < 6; k++) s += W1[6 * a + k] * Je[6 * k + c];
+      WJ[6 * a + c] = s;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 6; a++) {
+#pragma unroll
+    for (int c = a; c < 6; c++) {  // upper triangles, mirrored: 2 x the symmetric part
+      double s = 0, s2 = 0;
+#pragma unroll
+      for (int k = 0; k < 6; k++) { s += Je[6 * k + a] * WJ[6 * k + c]; s2 += Je[6 * k + c] * WJ[6 * k + a]; }
+      const double xx = s + s2, tt = W2[6 * a + c] + W2[6 * c + a];
+      if (writer) { L[PV_LXX + 6 * a + c] = xx; L[PV_LXX + 6 * c + a] = xx; L[PV_LTT + 6 * a + c] = tt; L[PV_LTT + 6 * c + a] = tt; }
+    }
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) s += Je[6 * k + a] * We[k];
+    if (writer) { L[PV_LX + a] = 2 * s; L[PV_LX + 6 + a] = 2 * W2v[a]; }
+  }
+  if (!term) {  // l_u = 2 R u, l_uu = 2 R
+    const auto Rw = wblock<PTW, M>(C.wts, P, b, false, C.R, C.R, WT_R, WT_R);
+#pragma unroll
+    for (int a = 0; a < M; a++) {
+      double sacc = 0;
+#pragma unroll
+      for (int k = 0; k < M; k++) {
+        sacc += 2.0 * Rw[a * M + k] * u[k];
+        if (writer) L[PV_LUU + a * M + k] = Rw[a * M + k] + Rw[k * M + a];
+      }
+      if (writer) L[PV_LU + a] = sacc;
+    }
+  }
+}
+// knot i's outputs: P from the row's LDS (upper triangle, mirrored), its diagonal, p from the lane's registers
+TOLG_DEV void pv_outputs(const double* L, bool live, int l, size_t bk, const double (&pv)[12], double* __restrict__ Pout,
+                         double* __restrict__ pout, double* __restrict__ diag) {
+  if (!live) return;
+  const double* SG = L + PC_SG;
+  if (Pout) {  // 144 entries over 16 lanes
+    double* o = Pout + bk * 144;
+#pragma unroll
+    for (int t = 0; t < 9; t++) {
+      const int e = l + 16 * t, r = e / 12, c = e - 12 * r;
+      o[e] = SG[r <= c ? 12 * r + c : 12 * c + r];
+    }
+  }
+  if (diag && l < 12) diag[bk * 12 + l] = SG[13 * l];
+  if (pout && l == 0) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) pout[bk * 12 + k] = pv[k];
+  }
+}
+template <int M, int PK, int PT>
+__global__ __launch_bounds__(64) void k_policy_value(Params P, const double* __restrict__ Sigma0, const double* __restrict__ Wn,
+                                                     double* __restrict__ Pout, double* __restrict__ pout,
+                                                     double* __restrict__ diag, double* __restrict__ price,
+                                                     double* __restrict__ excess) {
+  __shared__ double lds[4 * PV_F];
+  const Consts& C = *P.c;
+  const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+  int b = blockIdx.x * 4 + g;
+  // rows past the last trajectory replay it (the block's barriers need every lane) and store nothing
+  const bool live = b < P.B;
+  if (!live) b = P.B - 1;
+  const int j = l < 12 ? l : 11;
+  const bool col = l < 12;
+  double* L = lds + g * PV_F;
+  const int N = P.N;
+  const unsigned sB = (unsigned)P.Bp * 8u, vb = (unsigned)b * 8u;
+  const double dt = C.dt;
+  double s[12], pv[12], wc[6];  // column j of P_{i+1}; p_{i+1}; column j - 6 of W (zero in the lanes of the pose columns)
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const int jw = j >= 6 ? j - 6 : 0;
+    wc[i] = (Wn && j >= 6) ? Wn[(size_t)b * 36 + (i <= jw ? 6 * i + jw : 6 * jw + i)] : 0.0;
+  }
+  double Bt[9], Bb[9];  // F_u's constant blocks, as in k_policy_covariance
+#pragma unroll
+  for (int k = 0; k < 9; k++) { Bt[k] = C.Bt[k]; Bb[k] = C.Bb[k]; }
+  const int jb = j < 6 ? j : j - 6;
+  const double* Mrow = L + (j < 6 ? PV_LXX : PV_LTT) + 6 * jb;  // row j of l_xx: its block's row, zeros beside it
+  {  // ---- knot N: P_N = l_xx^N, p_N = l_x^N
+    const State SN = roll_load_state(P, N, vb, sB);
+    double uz[M];
+#pragma unroll
+    for (int a = 0; a < M; a++) uz[a] = 0.0;
+    pv_cost<M, PT>(P, C, N, b, SN, uz, true, l == 0, L);
+    __syncthreads();
+    if (col) {
+#pragma unroll
+      for (int c = 0; c < 12; c++) L[PC_SG + 12 * j + c] = ((c < 6) == (j < 6)) ? Mrow[c < 6 ? c : c - 6] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) pv[k] = L[PV_LX + k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = L[PC_SG + (k <= j ? 12 * k + j : 12 * j + k)];
+    pv_outputs(L, live, l, (size_t)b * (N + 1) + N, pv, Pout, pout, diag);
+  }
+  double ex = 0.0;
+  for (int i = N - 1; i >= 0; i--) {
+    const State Sa = roll_load_state(P, i, vb, sB);
+    RollIn<M> Rin;
+    roll_load<M, true>(P, i, b, l, vb, sB, Rin);
+    pc_build_acl<M, PK>(C, dt, Sa, Rin, l, L, Bt);  // the blocks of f_x at (x*_i, u*_i), the gains
+    pv_cost<M, PT>(P, C, i, b, Sa, Rin.u, false, l == 0, L);
+    if (col) {  // lane j's part of tr(P_{i+1}[6:12, 6:12] W): exact zeros in the pose lanes and for W = 0
+      double q = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; k++) q += s[6 + k] * wc[k];
+      L[PV_Q + j] = q;
+    }
+    __syncthreads();
+    double kj[M];
+    pc_fold_fuk<M>(L, j, col, Bt, Bb, kj);  // column j of the lower half: + f_u K
+    if (live && l == 0) {
+      double t = 0.0;
+#pragma unroll
+      for (int k = 6; k < 12; k++) t += L[PV_Q + k];
+      t *= 0.5;
+      ex += t;
+      if (price) price[(size_t)b * N + i] = t;
+    }
+    __syncthreads();
+    double x[12], y[12];
+    pv_apply_t(L, s, y);
+    if (col) {
+#pragma unroll
+      for (int r = 0; r < 12; r++) L[PC_TT + 12 * r + j] = y[r];
+    }
+    if (pout) {  // p_i = l_x + K^T l_u + Acl^T p_{i+1}
+      pv_apply_t(L, pv, y);
+#pragma unroll
+      for (int r = 0; r < 12; r++) {
+        double t = L[PV_LX + r];
+#pragma unroll
+        for (int u = 0; u < M; u++) t += L[PC_K + 12 * u + r] * L[PV_LU + u];
+        pv[r] = t + y[r];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 12; k++) x[k] = L[PC_TT + 12 * j + k];
+    pv_apply_t(L, x, y);
+    {  // + row j of M_i = l_xx + K^T l_uu K
+      double t[M];
+#pragma unroll
+      for (int v = 0; v < M; v++) {
+        double a = 0.0;
+#pragma unroll
+        for (int u = 0; u < M; u++) a += kj[u] * L[PV_LUU + u * M + v];
+        t[v] = a;
+      }
+#pragma unroll
+      for (int c = 0; c < 12; c++) {
+        double a = ((c < 6) == (j < 6)) ? Mrow[c < 6 ? c : c - 6] : 0.0;
+#pragma unroll
+        for (int v = 0; v < M; v++) a += t[v] * L[PC_K + 12 * v + c];
+        y[c] += a;
+      }
+    }
+    if (col) {
+#pragma unroll
+      for (int k = 0; k < 12; k++) L[PC_SG + 12 * j + k] = y[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = L[PC_SG + (k <= j ? 12 * k + j : 12 * j + k)];
+    pv_outputs(L, live, l, (size_t)b * (N + 1) + i, pv, Pout, pout, diag);
+  }
+  if (excess) {  // + tr(P_0 Sigma0) / 2: lane j's column of both (the upper triangle of Sigma0 read), summed in lane order
+    double q = 0.0;
+    if (Sigma0) {
+#pragma unroll
+      for (int k = 0; k < 12; k++) q += s[k] * Sigma0[(size_t)b * 144 + (k <= j ? 12 * k + j : 12 * j + k)];
+    }
+    __syncthreads();
+    if (col) L[PV_Q + j] = q;
+    __syncthreads();
+    if (live && l == 0) {
+      double t = 0.0;
+#pragma unroll
+      for (int k = 0; k < 12; k++) t += L[PV_Q + k];
+      excess[b] = ex + 0.5 * t;
+    }
+  }
 }
 
 // d_J [B][S][36] (row-major 6x6 blkdiag(Ib, Jv)) and d_pend [B][S][2] (mass, length; the pendulum only, else null) into the
@@ -4360,6 +4654,7 @@ struct KernelTable {
   void (*policy_rollout_plant[2])(Params, int, int, const double*, const double*, double*, int*, double*, double*, double*, PlantArg);
   void (*mpc_advance_plant[2])(Params, const double*, double*, double*, double*, double*, double*, double*, PlantArg);
   void (*policy_covariance)(Params, const double*, const double*, double*, double*, double*, double*);  // tolg_policy_covariance
+  void (*policy_value)(Params, const double*, const double*, double*, double*, double*, double*, double*);  // tolg_policy_value
   struct Search {                    // per search kind: ls[0] backtracking (single shooting), ls[1] merit (multiple shooting)
     struct { SearchRollout k; int nt; } wave2[2];  // k_rollout_ls2 [first try] and its NT (twist waves per pose wave)
     SearchRollout wave1[2];          // the one-wave forms k_rollout_ls [linear]
@@ -4428,6 +4723,7 @@ static KernelTable kernel_table(int lds_per_block) {
   t.mpc_advance_plant[TOLG_PLANT_DIAG] = k_mpc_advance<M, PK, PT & ~PT_OBS, PL_DIAG, PlantArg>;
   t.mpc_advance_plant[TOLG_PLANT_DENSE] = k_mpc_advance<M, PK, PT & ~PT_OBS, PL_DENSE, PlantArg>;
   t.policy_covariance = k_policy_covariance<M, PK>;  // (reads neither reference nor weights: one kernel for every PT)
+  t.policy_value = k_policy_value<M, PK, PT & ~PT_OBS>;  // (the tracking cost's derivatives: reference and weights, no spheres)
   t.ls[0] = search_kernels<M, false, PK, PT>();
   t.ls[1] = search_kernels<M, true, PK, PT>();
   return t;
@@ -5620,6 +5916,16 @@ extern "C" int tolg_policy_covariance(tolg_handle_t h, int32_t B, const double* 
   const Params P = params_for(h, B);
   hipLaunchKernelGGL(h->kt.policy_covariance, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, static_cast<hipStream_t>(stream), P,
                      d_Sigma0, d_W, d_Sigma, d_var_x, d_var_u, d_pos_cov);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tolg_policy_value(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, double* d_P, double* d_p,
+                                 double* d_diag_P, double* d_price, double* d_excess, void* stream) {
+  if (!policy_ok(h, B)) return TOLG_E_ARG;
+  const Params P = params_for(h, B);
+  hipLaunchKernelGGL(h->kt.policy_value, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, static_cast<hipStream_t>(stream), P, d_Sigma0,
+                     d_W, d_P, d_p, d_diag_P, d_price, d_excess);
   LAUNCH_CHECK();
   return 0;
 }

@@ -101,6 +101,17 @@ class PolicyCovariance:
     Sigma: Optional[torch.Tensor] = None    # [B, N+1, 12, 12] (full=True)
 
 
+@dataclass
+class PolicyValue:
+    """Cost-to-go of the held policy (BatchedTrackingILQR.policy_value), V_i(e) ~ p_i . e + e^T P_i e / 2 in the error
+    coordinates of the gains; for so3 and the pendulum in the embedded 12-coordinate layout gains() uses (3..5 and 9..11 unused)."""
+    p: torch.Tensor                     # [B, N+1, 12]; p[:, 0] is the gradient of the closed-loop cost in the start error
+    diag_P: torch.Tensor                # [B, N+1, 12] diag P_i
+    price: torch.Tensor                 # [B, N] tr(P_{i+1}[6:12, 6:12] W) / 2: what the disturbance behind step i costs
+    excess: torch.Tensor                # [B] tr(P_0 Sigma0) / 2 + sum_i price_i: expected closed-loop cost above the nominal's
+    P: Optional[torch.Tensor] = None    # [B, N+1, 12, 12] (full=True)
+
+
 def check_covariance(name, a, B, n, compact=None):
     """A covariance input of policy_covariance checked on the host: `a` is [B, n, n] or [n, n] (broadcast over the batch), or
     with compact = (k, index) also [B, k, k] / [k, k], embedded at rows / columns `index` of an n x n zero matrix.  It must be
@@ -867,6 +878,38 @@ class BatchedTrackingILQR:
         if pc is not None:
             iu = torch.tensor([[0, 1, 2], [1, 3, 4], [2, 4, 5]], device=self.device)
             r.pos_cov = pc[..., iu]
+        return r
+
+    def policy_value(self, Sigma0=None, W=None, full=False) -> PolicyValue:
+        """The cost-to-go of the held policy (tolg_policy_value), the backward companion of policy_covariance:
+        P_i = M_i + Acl_i^T P_{i+1} Acl_i with M_i = l_xx + K_i^T l_uu K_i and p_i = l_x + K_i^T l_u + Acl_i^T p_{i+1}, from
+        P_N = l_xx^N, p_N = l_x^N, with Acl_i = f_x + f_u K_i and the tracking cost's derivatives at the held nominal (the
+        model's Jacobians and Gauss-Newton Hessians; trajectory b's own reference and weights where they are set; no
+        augmented-Lagrangian terms).  Sigma0 and W as in policy_covariance (checked by check_covariance; so3 and the pendulum
+        also in their compact forms): price[b, i] = tr(P_{i+1}[6:12, 6:12] W) / 2 and excess[b] = tr(P_0 Sigma0) / 2 +
+        sum_i price[b, i], the expected closed-loop cost above the unperturbed one -- one sweep where policy_rollout needs S
+        samples.  Neither P nor p depends on Sigma0 or W.  Returns p [B, N+1, 12], diag_P [B, N+1, 12], price [B, N], excess [B]
+        and, with full=True, P [B, N+1, 12, 12] (0.95 GB at 4096 x 200).  A plant, an input box and keep-out spheres are ignored."""
+        B = self._held_B()
+        so3 = self.problem.kind in ("so3", "pendulum3d")
+        S0 = None if Sigma0 is None else check_covariance("Sigma0", Sigma0, B, 12, (6, [0, 1, 2, 6, 7, 8]) if so3 else None)
+        Wn = None if W is None else check_covariance("W", W, B, 6, (3, [0, 1, 2]) if so3 else None)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        d_S0 = None if S0 is None else self._dev(S0, (B, 12, 12))
+        d_W = None if Wn is None else self._dev(Wn, (B, 6, 6))
+        r = PolicyValue(p=torch.empty(B, self.N + 1, 12, **f64), diag_P=torch.empty(B, self.N + 1, 12, **f64),
+                        price=torch.empty(B, self.N, **f64), excess=torch.empty(B, **f64))
+        if full:
+            r.P = torch.empty(B, self.N + 1, 12, 12, **f64)
+        self._hold((d_S0, d_W))
+        try:
+            self._call("tolg_policy_value", B, _ptr(d_S0), _ptr(d_W), _ptr(r.P), _ptr(r.p), _ptr(r.diag_P), _ptr(r.price),
+                       _ptr(r.excess))
+        except RuntimeError as e:  # TOLG_E_ARG behind the host's own bookkeeping: the handle's state rules (tolg_solve_gains)
+            if "rc=-1" not in str(e):
+                raise
+            raise ValueError("tolg_policy_value refused the call: the held policy's batch, and the batch per-trajectory "
+                             "references and weights are set for, must both be %d" % B) from e
         return r
 
     # ------------------------------------------------------------------------------------------
