@@ -203,3 +203,40 @@ MODES = {
     "merit": dict(mode="ms", n_iterations=25, line_search=True),
     "ss": dict(mode="ss", n_iterations=25),
 }
+
+
+# the held policy of the covariance and value tests, and their seeded Sigma0 / W
+KW = dict(n_iterations=4, **ZERO)
+
+
+def psd(B, n, sigma, seed):
+    """B seeded n x n covariances that are not diagonal: a random rotation of a diagonal with deviations about sigma."""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((B, n, n))
+    for b in range(B):
+        Q, _ = np.linalg.qr(rng.normal(size=(n, n)))
+        M = (Q * (sigma * rng.uniform(0.5, 1.5, n)) ** 2) @ Q.T
+        out[b] = 0.5 * (M + M.T)
+    return out
+
+
+def embed(a, idx, n):
+    out = np.zeros((a.shape[0], n, n))
+    out[:, np.asarray(idx)[:, None], np.asarray(idx)[None, :]] = a
+    return out
+
+
+def moment_inputs(prob, B, seed=7, sigma=0.05, noise=0.01):
+    """(Sigma0, W) as the solver takes them and as the restatement reads them: so3 and the pendulum in their compact form."""
+    if prob.kind in ("so3", "pendulum3d"):
+        S0, W = psd(B, 6, sigma, seed), psd(B, 3, noise, seed + 1)
+        return S0, W, embed(S0, [0, 1, 2, 6, 7, 8], 12), embed(W, [0, 1, 2], 6)
+    S0, W = psd(B, 12, sigma, seed), psd(B, 6, noise, seed + 1)
+    return S0, W, S0, W
+
+
+def held_policy(s, q, xi, us, mode, **per_traj):
+    """A few iterations, then linearize_backward on the result: gains and nominal belong together."""
+    r = s.fit_batch(q, xi, us, mode=mode, **KW, **per_traj)
+    s.linearize_backward(r.xs_q, r.xs_xi, r.us, ms=(mode == "ms"), **per_traj)
+    return r

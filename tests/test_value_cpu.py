@@ -1,5 +1,5 @@
 """Cost-to-go of the held policy (tolg_policy_value): the parts that need no GPU -- the C ABI surface, the host checks, and
-the CPU restatement of the recursion (tests/restate_value.py) that tests/test_gpu_value.py checks the kernel against, itself
+the CPU restatement of the recursion (tests/restate.py) that tests/test_gpu_value.py checks the kernel against, itself
 checked against the covariance recursion (an exact duality) and against finite differences of the closed-loop cost."""
 import os
 import re
@@ -9,8 +9,7 @@ import pytest
 
 from oracle import bridge as ob
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, _capi, workloads
-from tests.restate import restate_covariance, restate_policy
-from tests.restate_value import restate_stage_weights, restate_value
+from tests.restate import restate_covariance, restate_policy, restate_stage_weights, restate_value
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = "tolg_policy_value"

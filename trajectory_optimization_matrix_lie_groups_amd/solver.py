@@ -850,6 +850,15 @@ class BatchedTrackingILQR:
                 self._clear_plant()
         return r
 
+    def _stage_moments(self, B, Sigma0, W):
+        """Sigma0 and W (either may be None) checked on the host and moved to the device: (d_S0, d_W).  Owns the keep-alive."""
+        so3 = self.problem.kind in ("so3", "pendulum3d")
+        S0 = None if Sigma0 is None else check_covariance("Sigma0", Sigma0, B, 12, (6, [0, 1, 2, 6, 7, 8]) if so3 else None)
+        Wn = None if W is None else check_covariance("W", W, B, 6, (3, [0, 1, 2]) if so3 else None)
+        d = (None if S0 is None else self._dev(S0, (B, 12, 12)), None if Wn is None else self._dev(Wn, (B, 6, 6)))
+        self._hold(d)
+        return d
+
     def policy_covariance(self, Sigma0=None, W=None, full=False, pos=True) -> PolicyCovariance:
         """The closed-loop covariance of the held policy to first order (tolg_policy_covariance), the analytic companion of
         policy_rollout: Sigma_{i+1} = Acl_i Sigma_i Acl_i^T + E W E^T with Acl_i = f_x + f_u K_i at the held nominal, in the
@@ -863,17 +872,12 @@ class BatchedTrackingILQR:
         model without translation: None) and, with full=True, Sigma [B, N+1, 12, 12] (0.95 GB at 4096 x 200).  A plant, an
         input box and keep-out spheres are ignored: the loop is the model's linear, unsaturated one."""
         B = self._held_B()
-        so3 = self.problem.kind in ("so3", "pendulum3d")
-        S0 = None if Sigma0 is None else check_covariance("Sigma0", Sigma0, B, 12, (6, [0, 1, 2, 6, 7, 8]) if so3 else None)
-        Wn = None if W is None else check_covariance("W", W, B, 6, (3, [0, 1, 2]) if so3 else None)
+        d_S0, d_W = self._stage_moments(B, Sigma0, W)
         f64 = dict(dtype=torch.float64, device=self.device)
-        d_S0 = None if S0 is None else self._dev(S0, (B, 12, 12))
-        d_W = None if Wn is None else self._dev(Wn, (B, 6, 6))
         r = PolicyCovariance(var_x=torch.empty(B, self.N + 1, 12, **f64), var_u=torch.empty(B, self.N, self.m, **f64))
         if full:
             r.Sigma = torch.empty(B, self.N + 1, 12, 12, **f64)
-        pc = torch.empty(B, self.N + 1, 6, **f64) if (pos and not so3) else None
-        self._hold((d_S0, d_W))
+        pc = torch.empty(B, self.N + 1, 6, **f64) if pos and self.problem.kind not in ("so3", "pendulum3d") else None
         self._call("tolg_policy_covariance", B, _ptr(d_S0), _ptr(d_W), _ptr(r.Sigma), _ptr(r.var_x), _ptr(r.var_u), _ptr(pc))
         if pc is not None:
             iu = torch.tensor([[0, 1, 2], [1, 3, 4], [2, 4, 5]], device=self.device)
@@ -891,17 +895,12 @@ class BatchedTrackingILQR:
         samples.  Neither P nor p depends on Sigma0 or W.  Returns p [B, N+1, 12], diag_P [B, N+1, 12], price [B, N], excess [B]
         and, with full=True, P [B, N+1, 12, 12] (0.95 GB at 4096 x 200).  A plant, an input box and keep-out spheres are ignored."""
         B = self._held_B()
-        so3 = self.problem.kind in ("so3", "pendulum3d")
-        S0 = None if Sigma0 is None else check_covariance("Sigma0", Sigma0, B, 12, (6, [0, 1, 2, 6, 7, 8]) if so3 else None)
-        Wn = None if W is None else check_covariance("W", W, B, 6, (3, [0, 1, 2]) if so3 else None)
+        d_S0, d_W = self._stage_moments(B, Sigma0, W)
         f64 = dict(dtype=torch.float64, device=self.device)
-        d_S0 = None if S0 is None else self._dev(S0, (B, 12, 12))
-        d_W = None if Wn is None else self._dev(Wn, (B, 6, 6))
         r = PolicyValue(p=torch.empty(B, self.N + 1, 12, **f64), diag_P=torch.empty(B, self.N + 1, 12, **f64),
                         price=torch.empty(B, self.N, **f64), excess=torch.empty(B, **f64))
         if full:
             r.P = torch.empty(B, self.N + 1, 12, 12, **f64)
-        self._hold((d_S0, d_W))
         try:
             self._call("tolg_policy_value", B, _ptr(d_S0), _ptr(d_W), _ptr(r.P), _ptr(r.p), _ptr(r.diag_P), _ptr(r.price),
                        _ptr(r.excess))
