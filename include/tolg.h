@@ -248,6 +248,23 @@ size_t tolg_obstacles_bytes(const tolg_problem* prob, int32_t max_batch, int32_t
 int tolg_set_al_obstacles(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
                           const double* d_imu, void* d_packed, size_t packed_bytes, void* stream);
 
+/* Keep-out spheres that move: the same constraint with its geometry given per knot, so that another vehicle's predicted path, a
+ * sphere that exists around some knots only, or a radius inflated by the knot's position covariance (tolg_policy_covariance)
+ * can be stated.  d_obs is [B][N+1][K][4] = (cx, cy, cz, r) of trajectory b at knot i, terminal knot included:
+ *   g_k(x_i) = r_ik^2 - |t_i - c_ik|^2 <= 0
+ * tolg_obstacles_moving_bytes: (N+1) 4 K Bp 8, the packed size ([N+1][4K][Bp]: field f = 4k + c of knot i of trajectory b at
+ * (i 4K + f) Bp + b, padded trajectories replicate B-1); 0 under the rules of tolg_obstacles_bytes.
+ * tolg_set_al_obstacles_moving: everything else is tolg_set_al_obstacles' -- the caller-owned multipliers [B][N+1][K], the batch
+ * entry points that add the terms and demand this B, tolg_eval_knot / tolg_policy_* / tolg_mpc_advance ignoring them, the held
+ * policy left alone, and its TOLG_E_ARG list with packed_bytes checked against tolg_obstacles_moving_bytes(prob, B, K).
+ * Attaching either form replaces the other; d_obs = NULL in either call detaches.  tolg_al_update_state reads whichever form is
+ * attached.  The kernels are those of the static form: the geometry address gains a knot stride, 0 there and 4 K Bp here.
+ * Cost: 211 MB of packed geometry at 4096 x 200 with K = 8, and where the static form reads the same 4K values at every knot
+ * (cached), this one streams 4K new values per knot and trajectory; see INTEGRATION.md 3k for what was measured. */
+size_t tolg_obstacles_moving_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K);
+int tolg_set_al_obstacles_moving(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
+                                 const double* d_imu, void* d_packed, size_t packed_bytes, void* stream);
+
 /* One outer iteration of AL_iLQR_Tracking_SE3_MS (traoptlibrary/traopt_controller.py:3242-3250, :3270-3290) over every
  * constraint attached to the handle: the input box of tolg_set_al on d_us [B][N][m] and the spheres of tolg_set_al_obstacles
  * on the positions of d_xs_q [B][N+1][16].  d_maxviol[b] = the largest g of them all (the box contributes its terminal rows

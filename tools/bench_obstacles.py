@@ -3,14 +3,18 @@
 (al_fit_batch(obstacles=...)) on the K = 8 field: its outer-iteration count and time.
 
 usage: python tools/bench_obstacles.py [--lines headline,merit,ss] [--Ks 0,1,4,8] [--B 4096] [--N 200] [--rounds 7]
-                                       [--steps K] [--warmup W] [--al] [--out FILE.json] [--dry]
+                                       [--steps K] [--warmup W] [--al] [--moving] [--out FILE.json] [--dry]
 
 One process, one handle per line; the variants are timed in alternation, round after round (the order rotates every round),
 each region being iterations W .. W+K of a fresh solve between two device synchronisations (tools/_benchlib.py's
 solve_rate_region and rate_rounds, as in tools/bench_weights.py).  The multipliers are fixed (lambda 0.1, I_mu 1e-2: what
 the first outer iteration of al_fit_batch sees, with lambda > 0 so that no term is zero).  Per variant the line reports the
 median rate (batch iterations per second), the lowest and highest, the spread (max - min) / median, and the median over the
-no-sphere variant's."""
+no-sphere variant's.
+
+--moving sends the same field of each K, repeated over the N + 1 knots, through tolg_set_al_obstacles_moving ([B, N+1, K, 4]):
+the same arithmetic on geometry that is streamed per knot instead of read from 4K cached values, so the lines beside the
+static ones show what the streaming costs."""
 import argparse
 import json
 import os
@@ -28,6 +32,7 @@ def parse_args(argv=None):
     ap.add_argument("--Ks", default="0,1,4,8", help="spheres per trajectory of each variant (0: none attached)")
     add_common_args(ap, "B", "N", "rounds", "steps", "warmup")
     ap.add_argument("--al", action="store_true", help="also time one al_fit_batch on the K = max(Ks) field")
+    ap.add_argument("--moving", action="store_true", help="attach each field per knot (tolg_set_al_obstacles_moving)")
     add_common_args(ap, "out", "dry")
     a = ap.parse_args(argv)
     a.lines = a.lines.split(",")
@@ -48,9 +53,13 @@ def run_line(name, a, prob, q0, xi0, us, obs):
     q_d, xi_d, us_d = (torch.as_tensor(x, **f64) for x in (q0, xi0, us))
     mult = {k: (torch.full((a.B, a.N + 1, k), 0.1, **f64), torch.full((a.B, a.N + 1, k), 1e-2, **f64)) for k in a.Ks if k}
 
+    field = {}
+    if a.moving:  # the field of each K at every knot, on the device once
+        field = {k: torch.as_tensor(obs[:, None, :k], **f64).expand(a.B, a.N + 1, k, 4).contiguous() for k in a.Ks if k}
+
     def region(k):
         if k:
-            solver.set_al_obstacles(obs[:, :k], *mult[k])
+            solver.set_al_obstacles(field[k] if a.moving else obs[:, :k], *mult[k])
         rate, _ = solve_rate_region(solver, (q_d, xi_d, us_d), kw, W, K)
         if k:
             solver.set_al_obstacles(None)
@@ -58,7 +67,7 @@ def run_line(name, a, prob, q0, xi0, us, obs):
         return rate
 
     rates = rate_rounds(a.Ks, region, a.rounds)
-    out = dict(line=name, B=a.B, N=a.N, steps=K, warmup=W, rounds=a.rounds, unit="batch-iterations/s",
+    out = dict(line=name, B=a.B, N=a.N, steps=K, warmup=W, rounds=a.rounds, moving=a.moving, unit="batch-iterations/s",
                variants={"K=%d" % k: summary(rates[k]) for k in a.Ks})
     if 0 in a.Ks:
         base = out["variants"]["K=0"]["median"]
@@ -88,7 +97,7 @@ def main(argv=None):
     kmax = max(max(a.Ks), 1)
     prob, q0, xi0, us, obs = workloads.se3_obstacle_field(a.B, kmax, N=a.N)
     if a.dry:
-        print(json.dumps(dict(plan=a.lines, Ks=a.Ks, B=a.B, N=prob.N, rounds=a.rounds, al=a.al,
+        print(json.dumps(dict(plan=a.lines, Ks=a.Ks, B=a.B, N=prob.N, rounds=a.rounds, al=a.al, moving=a.moving,
                               steps={n: a.steps or LINES[n][1] for n in a.lines}, warmup=a.warmup)))
         return 0
     require_gpu("bench_obstacles")

@@ -30,7 +30,8 @@ SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_ba
            "tolg_solve_iterate", "tolg_solve_iterate_until", "tolg_solve_end", "tolg_solve_peek", "tolg_solve_active_count", "tolg_set_al", "tolg_al_update",
            "tolg_refs_bytes", "tolg_set_refs", "tolg_weights_bytes", "tolg_set_weights", "tolg_eval_knot", "tolg_linearize_backward",
            "tolg_rollout", "tolg_expected_change", "tolg_solve_gains", "tolg_policy_rollout",
-           "tolg_solve_begin_warm", "tolg_set_ref_windows", "tolg_mpc_advance", "tolg_obstacles_bytes", "tolg_set_al_obstacles", "tolg_al_update_state", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
+           "tolg_solve_begin_warm", "tolg_set_ref_windows", "tolg_mpc_advance", "tolg_obstacles_bytes", "tolg_set_al_obstacles", "tolg_obstacles_moving_bytes", "tolg_set_al_obstacles_moving",
+           "tolg_al_update_state", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
 
 
 def load():
@@ -100,6 +101,10 @@ def load():
     lib.tolg_obstacles_bytes.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32]
     lib.tolg_set_al_obstacles.restype = C.c_int
     lib.tolg_set_al_obstacles.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, vp, C.c_size_t, vp]
+    lib.tolg_obstacles_moving_bytes.restype = C.c_size_t
+    lib.tolg_obstacles_moving_bytes.argtypes = lib.tolg_obstacles_bytes.argtypes
+    lib.tolg_set_al_obstacles_moving.restype = C.c_int
+    lib.tolg_set_al_obstacles_moving.argtypes = lib.tolg_set_al_obstacles.argtypes
     lib.tolg_al_update_state.restype = C.c_int
     lib.tolg_al_update_state.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_double, C.c_double, C.c_double, dp, ip, vp]
     lib.tolg_plant_bytes.restype = C.c_size_t

@@ -52,6 +52,9 @@ struct Consts {
   // (OB_* fields of sphere k at (4k + f) * Bp + b), the multipliers and the diagonal of I_mu in the caller layout [B][N+1][K]
   const double *obs, *obs_lam, *obs_imu;
   int obsK, obs_pad;
+  // ... and the geometry's knot stride in doubles: 0 (one [4K][Bp] block for every knot) or 4 K Bp (tolg_set_al_obstacles_moving:
+  // [N+1][4K][Bp], knot i's block at i * 4 K Bp); the pack kernels set it
+  size_t obs_stride;
 };
 
 // Device-side view of the constants used by the three hot kernels: address space 4 (constant), so
@@ -319,7 +322,8 @@ __host__ __device__ constexpr int rec_fields(int m, bool grav, bool al, bool a22
 __host__ __device__ inline bool so3_family(int kind) { return kind == TOLG_DYN_SO3 || kind == TOLG_DYN_PENDULUM3D; }
 __host__ __device__ inline int sym6(int r, int c) { return r <= c ? c * (c + 1) / 2 + r : r * (r + 1) / 2 + c; }
 
-// Keep-out spheres of trajectory b (tolg_set_al_obstacles, PT_OBS): g_k = r_k^2 - |t - c_k|^2 <= 0 at every knot, terminal
+// Keep-out spheres of trajectory b (tolg_set_al_obstacles, or per knot tolg_set_al_obstacles_moving: the geometry of knot i
+// lies i * C.obs_stride doubles on; PT_OBS): g_k = r_k^2 - |t - c_k|^2 <= 0 at every knot, terminal
 // included, and the augmented-Lagrangian terms of ALConstrainedCost (traopt_cost.py:1173-1320; Gauss-Newton, no g_xx).  In the
 // error coordinates of l_x (X Exp(delta), twist order [w, v]) g_x = [0, -2 (t - c)^T R, 0]: only its v part is not zero,
 // gv = -2 R^T (t - c).  Sums lambda g + g I g / 2 into l and, with ox / oxx given, gv (lambda + I g) into ox (l_x[3:6]) and
@@ -329,7 +333,7 @@ template <class CT>
 TOLG_DEV void obs_terms(const Params& P, const CT& C, int i, int b, const Pose& X, double& l, double* ox, double* oxx) {
   const int K = C.obsK, bs = b < P.B ? b : P.B - 1;  // the packed geometry replicates B-1 in padded lanes, the multipliers do not
   const size_t row = ((size_t)bs * (P.N + 1) + i) * K, Bp = (size_t)P.Bp;
-  const double *lam = C.obs_lam + row, *imu = C.obs_imu + row, *geo = C.obs + b;
+  const double *lam = C.obs_lam + row, *imu = C.obs_imu + row, *geo = C.obs + b + (size_t)i * C.obs_stride;
   for (int k = 0; k < K; k++) {
     const double* o = geo + (size_t)(4 * k) * Bp;
     const V3 d = X.t - v3(o[0], o[Bp], o[2 * Bp]);
@@ -4812,6 +4816,7 @@ struct tolg_handle_s {
   int wts_B = 0;                 // ... and their batch, as refs_B
   const double* obs = nullptr;   // tolg_set_al_obstacles: the packed sphere geometry (caller-owned), or null
   int obs_B = 0, obs_K = 0;      // ... their batch, as refs_B, and the spheres per trajectory
+  size_t obs_stride = 0;         // ... the knot stride of the geometry in doubles (Consts::obs_stride): 0, or 4 K Bp for the moving form
   double *obs_lam = nullptr, *obs_imu = nullptr;  // ... their multipliers [B][N+1][K] (caller-owned; tolg_al_update_state writes them)
   const double* plant = nullptr;  // tolg_set_plant: the packed plant rows (caller-owned), or null: the closed loops step the model
   int plant_B = 0, plant_S = 0, plant_form = 0;  // ... their batch, samples per trajectory and TOLG_PLANT_* form
@@ -5677,28 +5682,43 @@ extern "C" int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, co
 __global__ void k_pack_obstacles(int B, int Bp, int K, const double* __restrict__ obs, const double* lam, const double* imu,
                                  double* __restrict__ w, Consts* c) {
   size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; }
+  if (t == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; c->obs_stride = 0; }
   if (t >= (size_t)4 * K * Bp) return;
   const int b = (int)(t % Bp), f = (int)(t / Bp);
   const int bs = b < B ? b : B - 1;
   w[t] = obs[(size_t)bs * 4 * K + f];
 }
 
+// The same per knot (tolg_set_al_obstacles_moving): d_obs [B][N+1][K][4] into [N+1][4K][Bp], field f of knot i of trajectory b
+// at (i * 4K + f) * Bp + b, padded trajectories as above; the knot stride 4 K Bp goes into the constants.
+__global__ void k_pack_obstacles_moving(int B, int Bp, int K, int N, const double* __restrict__ obs, const double* lam,
+                                        const double* imu, double* __restrict__ w, Consts* c) {
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t knot = (size_t)4 * K * Bp;
+  if (t == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; c->obs_stride = knot; }
+  if (t >= knot * (size_t)(N + 1)) return;
+  const size_t i = t / knot, r = t % knot;
+  const int b = (int)(r % Bp), f = (int)(r / Bp);
+  const int bs = b < B ? b : B - 1;
+  w[t] = obs[((size_t)bs * (N + 1) + i) * 4 * K + f];
+}
+
 // One outer update over every constraint the handle holds (tolg_al_update_state): the input box of tolg_set_al on the
-// controls and the keep-out spheres of tolg_set_al_obstacles on the positions of xs_q [B][N+1][16], one thread per trajectory.
+// controls and the keep-out spheres of tolg_set_al_obstacles (geo_stride 0) or tolg_set_al_obstacles_moving (knot i's geometry
+// i * geo_stride doubles on) on the positions of xs_q [B][N+1][16], one thread per trajectory.
 // maxviol = the largest g of them all (the box contributes the zero rows of its terminal knot, traopt_constraints.py:160-161;
 // the spheres have no such rows), one mu per problem, the update rule of k_al_update for both multiplier sets
 // (traopt_controller.py:3242-3250, :3270-3290).
 __global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const double* __restrict__ xs_q, const double* __restrict__ us,
                                   const double* __restrict__ lb, const double* __restrict__ ub, double* __restrict__ lam,
-                                  double* __restrict__ imu, const double* __restrict__ geo, double* __restrict__ olam,
+                                  double* __restrict__ imu, const double* __restrict__ geo, size_t geo_stride, double* __restrict__ olam,
                                   double* __restrict__ oimu, double* __restrict__ mu, double mu_scale, double mu_max,
                                   double tol_constr, double* __restrict__ maxviol, int* __restrict__ al_conv) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B || al_conv[b]) return;  // a converged problem keeps its multipliers
   auto gs = [&](int i, int k) {      // g_k at knot i: r^2 - |t - c|^2
     const double* x = xs_q + ((size_t)b * (N + 1) + i) * 16;
-    const double* o = geo + (size_t)(4 * k) * Bp + b;
+    const double* o = geo + (size_t)i * geo_stride + (size_t)(4 * k) * Bp + b;
     const double dx = x[3] - o[0], dy = x[7] - o[Bp], dz = x[11] - o[2 * (size_t)Bp], r = o[3 * (size_t)Bp];
     return r * r - (dx * dx + dy * dy + dz * dz);
   };
@@ -5740,26 +5760,50 @@ extern "C" size_t tolg_obstacles_bytes(const tolg_problem* prob, int32_t max_bat
   return obstacles_bytes_for(max_batch, K);
 }
 
+// Attach either form (the checks of tolg_set_al_obstacles; `moving`: d_obs holds a field per knot and the packed size is N + 1
+// times the static one).  Each replaces the other: one geometry pointer, one stride.
+static int attach_obstacles(tolg_handle_t h, int B, int K, bool moving, const double* d_obs, const double* d_lambda,
+                            const double* d_imu, void* d_packed, size_t packed_bytes, void* stream) {
+  if (so3_family(h->prob.kind) || B < 1 || B > h->max_batch || K < 1 || K > TOLG_MAX_OBSTACLES) return TOLG_E_ARG;
+  if (!d_lambda || !d_imu || !d_packed || (reinterpret_cast<uintptr_t>(d_packed) & 7) != 0) return TOLG_E_ARG;
+  const size_t knots = moving ? (size_t)(h->prob.N + 1) : 1;
+  if (packed_bytes < knots * obstacles_bytes_for(B, K)) return TOLG_E_ARG;
+  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;  // per-trajectory inputs: one batch
+  const int Bp = padded_batch(B);
+  const size_t knot = (size_t)4 * K * Bp, n = knots * knot;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double* w = static_cast<double*>(d_packed);
+  Consts* c = const_cast<Consts*>(h->P.c);
+  if (moving) hipLaunchKernelGGL(k_pack_obstacles_moving, grid, dim3(256), 0, st, B, Bp, K, h->prob.N, d_obs, d_lambda, d_imu, w, c);
+  else hipLaunchKernelGGL(k_pack_obstacles, grid, dim3(256), 0, st, B, Bp, K, d_obs, d_lambda, d_imu, w, c);
+  LAUNCH_CHECK();
+  h->obs = w; h->obs_B = B; h->obs_K = K; h->obs_stride = moving ? knot : 0;
+  h->obs_lam = const_cast<double*>(d_lambda); h->obs_imu = const_cast<double*>(d_imu);
+  select_kernels(h);
+  return 0;
+}
+
 extern "C" int tolg_set_al_obstacles(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
                                      const double* d_imu, void* d_packed, size_t packed_bytes, void* stream) {
   if (!h || h->running) return TOLG_E_ARG;
   if (!d_obs) {  // detach
-    h->obs = nullptr; h->obs_B = h->obs_K = 0; h->obs_lam = h->obs_imu = nullptr; select_kernels(h);
+    h->obs = nullptr; h->obs_B = h->obs_K = 0; h->obs_stride = 0; h->obs_lam = h->obs_imu = nullptr; select_kernels(h);
     return 0;
   }
-  if (so3_family(h->prob.kind) || B < 1 || B > h->max_batch || K < 1 || K > TOLG_MAX_OBSTACLES) return TOLG_E_ARG;
-  if (!d_lambda || !d_imu || !d_packed || (reinterpret_cast<uintptr_t>(d_packed) & 7) != 0) return TOLG_E_ARG;
-  if (packed_bytes < obstacles_bytes_for(B, K)) return TOLG_E_ARG;
-  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;  // per-trajectory inputs: one batch
-  const int Bp = padded_batch(B);
-  const size_t n = (size_t)4 * K * Bp;
-  hipLaunchKernelGGL(k_pack_obstacles, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp, K,
-                     d_obs, d_lambda, d_imu, static_cast<double*>(d_packed), const_cast<Consts*>(h->P.c));
-  LAUNCH_CHECK();
-  h->obs = static_cast<const double*>(d_packed); h->obs_B = B; h->obs_K = K;
-  h->obs_lam = const_cast<double*>(d_lambda); h->obs_imu = const_cast<double*>(d_imu);
-  select_kernels(h);
-  return 0;
+  return attach_obstacles(h, B, K, false, d_obs, d_lambda, d_imu, d_packed, packed_bytes, stream);
+}
+
+extern "C" size_t tolg_obstacles_moving_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K) {
+  const size_t knot = tolg_obstacles_bytes(prob, max_batch, K);  // (its rules; check_problem has seen N >= 1)
+  return knot ? (size_t)(prob->N + 1) * knot : 0;
+}
+
+extern "C" int tolg_set_al_obstacles_moving(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
+                                            const double* d_imu, void* d_packed, size_t packed_bytes, void* stream) {
+  if (!d_obs) return tolg_set_al_obstacles(h, B, K, nullptr, d_lambda, d_imu, d_packed, packed_bytes, stream);  // detach
+  if (!h || h->running) return TOLG_E_ARG;
+  return attach_obstacles(h, B, K, true, d_obs, d_lambda, d_imu, d_packed, packed_bytes, stream);
 }
 
 extern "C" int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu,
@@ -5771,7 +5815,7 @@ extern "C" int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_
   if (h->obs && (B != h->obs_B || !d_xs_q)) return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_update_state, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), B, padded_batch(B),
                      h->prob.N, h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
-                     const_cast<double*>(h->al_imu), h->obs, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr, d_maxviol,
+                     const_cast<double*>(h->al_imu), h->obs, h->obs_stride, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr, d_maxviol,
                      d_al_converged);
   LAUNCH_CHECK();
   return 0;

@@ -150,6 +150,27 @@ class MPCResult:
     status: torch.Tensor   # [B, steps] int32: its status
 
 
+def inflate_obstacles(obstacles, xs_q, pos_cov, kappa):
+    """Keep-out spheres with a margin for the closed-loop spread: obstacles [K, 4], [B, K, 4] or [B, N+1, K, 4] rows (cx, cy,
+    cz, r), xs_q [B, N+1, 4, 4] the nominal plan, pos_cov [B, N+1, 3, 3] its position covariance (policy_covariance().pos_cov).
+    Returns [B, N+1, K, 4] (numpy) with the radii r_ik + kappa sqrt(n_ik^T pos_cov_i n_ik), n_ik the unit vector from c_ik to
+    the nominal position t_i: kappa standard deviations of the position along the line to the sphere, a radius per knot,
+    which is what al_fit_batch(obstacles=...) takes."""
+    host = lambda a: np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)  # noqa: E731
+    t, cov, o = host(xs_q)[..., :3, 3], host(pos_cov), host(obstacles)
+    B, N1 = t.shape[:2]
+    if o.ndim < 4:
+        o = np.broadcast_to(o if o.ndim == 2 else o[:, None], (B, N1) + o.shape[-2:])
+    if o.shape[:2] != (B, N1) or o.shape[-1] != 4 or cov.shape != (B, N1, 3, 3):
+        raise ValueError("inflate_obstacles: obstacles %s and pos_cov %s do not fit xs_q [%d, %d, 4, 4]" % (o.shape, cov.shape, B, N1))
+    n = t[:, :, None, :] - o[..., :3]
+    n = n / np.maximum(np.linalg.norm(n, axis=-1, keepdims=True), 1e-300)
+    var = np.einsum("bika,biac,bikc->bik", n, cov, n)
+    out = o.copy()
+    out[..., 3] += float(kappa) * np.sqrt(np.maximum(var, 0.0))
+    return out
+
+
 def mpc_window_index(t0, t, N, T):
     """Knot of the path that knot i of step t's window tracks (tolg_set_ref_windows): min(t0[b] + t + i, T), [B, N+1]."""
     t0 = np.asarray(t0, dtype=np.int64).reshape(-1)
@@ -190,7 +211,8 @@ def _checked(name, a, shape, finite=False):
 # of the call once it has succeeded.  gains / policy_rollout / mpc_advance need one held.
 _POLICY = {"tolg_solve_begin": "clear", "tolg_solve_begin_warm": "clear", "tolg_eval_knot": "clear",
            "tolg_solve_batch": "clear hold", "tolg_linearize_backward": "clear hold", "tolg_solve_end": "hold",
-           "tolg_set_al_obstacles": "", "tolg_al_update_state": ""}  # (the last two leave it: listed for completeness)
+           "tolg_set_al_obstacles": "", "tolg_set_al_obstacles_moving": "",
+           "tolg_al_update_state": ""}  # (the last three leave it: listed for completeness)
 
 
 @dataclass
@@ -226,6 +248,7 @@ class BatchedTrackingILQR:
         self._al = None            # the augmented-Lagrangian terms the handle points at (set_al)
         self._obs = None           # ... and the keep-out spheres (set_al_obstacles): (obstacles, lam, imu) on the device
         self._obs_buf = None       # the packed sphere geometry the handle reads (caller-owned, for max_batch x MAX_OBSTACLES)
+        self._obs_mov_buf = None   # ... and of the per-knot form (for the largest B x K asked for so far)
         self._plant_buf = None     # the packed plant rows of the last call that stated one (tolg_set_plant; detached behind it)
         p = _capi.Problem()
         p.kind, p.m, p.N, p.dt = _KIND[problem.kind], self.m, self.N, float(problem.dt)
@@ -528,25 +551,26 @@ class BatchedTrackingILQR:
             self._call("tolg_set_al", _ptr(lb), _ptr(ub), _ptr(lam), _ptr(imu), stream=False)
 
     def _check_obstacles(self, B, obstacles):
-        """Keep-out spheres [K, 4] (every trajectory the same) or [B, K, 4] rows (cx, cy, cz, r), checked on the host: ValueError
-        before anything reaches the device for a model without translation, a wrong shape, K outside 1..MAX_OBSTACLES, a
-        non-finite value or a radius that is not positive.  B = None takes B from a [B, K, 4] array.  Returns (B, [B, K, 4]
+        """Keep-out spheres [K, 4] (every trajectory the same), [B, K, 4], or per knot [B, N+1, K, 4], rows (cx, cy, cz, r),
+        checked on the host: ValueError before anything reaches the device for a model without translation, a wrong shape (the
+        per-knot form must have N + 1 knots), K outside 1..MAX_OBSTACLES, a non-finite value or a radius that is not positive
+        at any knot.  B = None takes B from a [B, K, 4] or [B, N+1, K, 4] array.  Returns (B, [B, K, 4] or [B, N+1, K, 4]
         float64 numpy)."""
         if self.problem.kind in ("so3", "pendulum3d"):
             raise ValueError("keep-out spheres constrain the translation: the %s model has none" % self.problem.kind)
         a = obstacles.detach().cpu().numpy() if isinstance(obstacles, torch.Tensor) else obstacles
         a = np.asarray(a, dtype=np.float64)
-        if a.ndim not in (2, 3):
-            raise ValueError("obstacles has shape %s, expected (K, 4) or (B, K, 4)" % (a.shape,))
+        if a.ndim not in (2, 3, 4):
+            raise ValueError("obstacles has shape %s, expected (K, 4), (B, K, 4) or (B, N+1, K, 4)" % (a.shape,))
         a = _checked("obstacles", a, (None,) * a.ndim, finite=True)
         if a.ndim == 2:
             if B is None:
                 raise ValueError("obstacles [K, 4] need the batch: give lam / imu [B, N+1, K] or obstacles [B, K, 4]")
             a = np.broadcast_to(a, (B,) + a.shape)
         B = a.shape[0] if B is None else B
-        a = _checked("obstacles", a, (B, None, 4))
-        if not 1 <= a.shape[1] <= _capi.MAX_OBSTACLES:
-            raise ValueError("obstacles: K = %d spheres per trajectory, expected 1..%d" % (a.shape[1], _capi.MAX_OBSTACLES))
+        a = _checked("obstacles", a, (B, None, 4) if a.ndim == 3 else (B, self.N + 1, None, 4))
+        if not 1 <= a.shape[-2] <= _capi.MAX_OBSTACLES:
+            raise ValueError("obstacles: K = %d spheres per trajectory, expected 1..%d" % (a.shape[-2], _capi.MAX_OBSTACLES))
         if np.any(a[..., 3] <= 0.0):
             raise ValueError("obstacles: every radius must be positive")
         return B, np.ascontiguousarray(a)
@@ -554,7 +578,8 @@ class BatchedTrackingILQR:
     def set_al_obstacles(self, obstacles=None, lam=None, imu=None):
         """Attach (or detach with obstacles=None) keep-out spheres: the augmented-Lagrangian terms of g_k = r_k^2 - |t - c_k|^2
         <= 0 at every knot, terminal included (tolg_set_al_obstacles).  obstacles [K, 4] (broadcast) or [B, K, 4] rows (cx, cy,
-        cz, r); lam, imu [B, N+1, K]: the multipliers and the diagonal of I_mu (device tensors the handle reads in every solve
+        cz, r), or [B, N+1, K, 4]: spheres that move, the geometry of every knot (tolg_set_al_obstacles_moving; its packed
+        buffer, N + 1 times the static one, is allocated for the B and K asked for); lam, imu [B, N+1, K]: the multipliers and the diagonal of I_mu (device tensors the handle reads in every solve
         until they are detached; None: zeros).  Every batch call must then be for this B."""
         if obstacles is None:
             self._obs = None
@@ -562,7 +587,7 @@ class BatchedTrackingILQR:
             return
         Bl = None if lam is None else int(lam.shape[0])
         B, a = self._check_obstacles(Bl, obstacles)
-        K = a.shape[1]
+        K, moving = a.shape[-2], a.ndim == 4
         f64 = dict(dtype=torch.float64, device=self.device)
         if lam is None:
             lam = torch.zeros(B, self.N + 1, K, **f64)
@@ -574,13 +599,19 @@ class BatchedTrackingILQR:
             _checked(name, t, (B, self.N + 1, K))
         if not 1 <= B <= self.max_batch:
             raise ValueError("obstacles for B = %d trajectories, expected 1..%d" % (B, self.max_batch))
-        if self._obs_buf is None:
-            n = self.lib.tolg_obstacles_bytes(C.byref(self._p), self.max_batch, _capi.MAX_OBSTACLES)
-            self._obs_buf = torch.empty(int(n) // 8, dtype=torch.float64, device=self.device)
-        d = self._dev(a, (B, K, 4))
+        if moving:
+            n = int(self.lib.tolg_obstacles_moving_bytes(C.byref(self._p), B, K)) // 8
+            if self._obs_mov_buf is None or self._obs_mov_buf.numel() < n:
+                self._obs_mov_buf = torch.empty(n, **f64)
+            buf, fn = self._obs_mov_buf, "tolg_set_al_obstacles_moving"
+        else:
+            if self._obs_buf is None:
+                n = self.lib.tolg_obstacles_bytes(C.byref(self._p), self.max_batch, _capi.MAX_OBSTACLES)
+                self._obs_buf = torch.empty(int(n) // 8, **f64)
+            buf, fn = self._obs_buf, "tolg_set_al_obstacles"
+        d = self._dev(a, a.shape)
         self._obs = (d, lam, imu)  # the handle reads the multipliers in every solve until they are detached
-        self._call("tolg_set_al_obstacles", B, K, _ptr(d), _ptr(lam), _ptr(imu), _ptr(self._obs_buf),
-                   C.c_size_t(self._obs_buf.numel() * 8))
+        self._call(fn, B, K, _ptr(d), _ptr(lam), _ptr(imu), _ptr(buf), C.c_size_t(buf.numel() * 8))
 
     def al_fit_batch(self, x0_q, x0_xi, us_init, lb=None, ub=None, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
                      tol_d_norm=1e-6, tol_constr=1e-2, mu0=1e-2, mu_scale=10.0, mu_max=1e8, line_search=False,
@@ -589,7 +620,8 @@ class BatchedTrackingILQR:
         independent problems: every outer iteration re-solves from (x0, us_init) -- no warm start, as in
         the reference -- then updates multipliers on the device.  Returns (FitResult, info dict).
         q_ref / xi_ref: a reference per trajectory, Q / P / R: weights per trajectory, as for fit_batch.
-        Constraints: the input box lb <= u <= ub, keep-out spheres obstacles ([K, 4] or [B, K, 4], set_al_obstacles), or both
+        Constraints: the input box lb <= u <= ub, keep-out spheres obstacles ([K, 4], [B, K, 4] or per knot [B, N+1, K, 4],
+        set_al_obstacles), or both
         (one mu per problem, joint convergence: tolg_al_update_state).  With spheres the info dict also holds lmbd_obs and
         Imu_obs [B, N+1, K]; max_violation covers every constraint."""
         if (lb is None) != (ub is None):
@@ -612,8 +644,8 @@ class BatchedTrackingILQR:
             lb_d = self._dev(lb, (self.m,)); ub_d = self._dev(ub, (self.m,))
             self.set_al(lb_d, ub_d, lam, imu)
         if obs is not None:
-            lam_o = torch.zeros(B, self.N + 1, obs.shape[1], **f64)
-            imu_o = torch.full((B, self.N + 1, obs.shape[1]), float(mu0), **f64)
+            lam_o = torch.zeros(B, self.N + 1, obs.shape[-2], **f64)
+            imu_o = torch.full((B, self.N + 1, obs.shape[-2]), float(mu0), **f64)
             try:
                 self.set_al_obstacles(obs, lam_o, imu_o)
             except Exception:
@@ -655,6 +687,71 @@ class BatchedTrackingILQR:
         if obs is not None:
             info.update(lmbd_obs=lam_o, Imu_obs=imu_o)
         return final, info
+
+    def plan_fleet(self, x0_q, x0_xi, us_init, q_ref, xi_ref, fleet, separation, obstacles=None, lb=None, ub=None, **al_kw):
+        """Prioritised planning for F = B / fleet independent fleets in one batch: trajectory b is member p = b % fleet of
+        fleet b // fleet.  Round p = 0 .. fleet-1 solves the F members p, each on its own reference (q_ref [B, N+1, 4, 4],
+        xi_ref [B, N+1, 6]), keeping out of the caller's static `obstacles` ([K0, 4] or [B, K0, 4]) and of p moving spheres of
+        radius `separation` centred on the positions of members 0..p-1 of its fleet as their rounds left them
+        (al_fit_batch with a per-knot field; lb / ub and al_kw -- n_al_iters, n_ilqr_iters, tol_constr, mu0, ..., Q / P / R
+        [B, ...] -- go to it).  Round 0 with neither obstacles nor a box is a plain fit_batch with al_fit_batch's inner options.
+        The constraint holds at the knots, not between them: two members may pass closer than `separation` between two knots.
+        A lower-priority member yields to a higher one: member 0 plans as if alone, and whether member p finds a way round the
+        others is its own round's convergence.  K0 + fleet - 1 <= MAX_OBSTACLES.
+        Returns (FitResult in batch order, info): min_separation [F] the smallest centre distance over knots and pairs of
+        the final plans (inf for fleet = 1), max_violation [B], al_converged [B] int32 (rounds without a constraint: 0 and
+        1), outer_iterations [fleet] (python ints)."""
+        G = int(fleet)
+        x0_q, x0_xi = (a if hasattr(a, "shape") else np.asarray(a, dtype=np.float64) for a in (x0_q, x0_xi))
+        B = int(x0_q.shape[0])
+        if G < 1 or B % G != 0:
+            raise ValueError("plan_fleet: B = %d trajectories are not whole fleets of %d" % (B, G))
+        if not float(separation) > 0.0:
+            raise ValueError("plan_fleet: separation must be positive")
+        F = B // G
+        q_ref, xi_ref = self._check_refs(B, q_ref, xi_ref) or (None, None)
+        if q_ref is None:
+            raise ValueError("plan_fleet needs a reference per trajectory: q_ref and xi_ref")
+        static = None if obstacles is None else self._check_obstacles(B, obstacles)[1]
+        if static is not None and static.ndim != 3:
+            raise ValueError("plan_fleet: obstacles are static, [K0, 4] or [B, K0, 4]")
+        K0 = 0 if static is None else static.shape[1]
+        if K0 + G - 1 > _capi.MAX_OBSTACLES:
+            raise ValueError("plan_fleet: %d spheres + %d other members exceed %d spheres per trajectory"
+                             % (K0, G - 1, _capi.MAX_OBSTACLES))
+        if us_init is None:
+            us_init = np.zeros((B, self.N, self.m))
+        per = {k: al_kw.pop(k) for k in ("Q", "P", "R") if k in al_kw}
+        f64 = dict(dtype=torch.float64, device=self.device)
+        maxviol = torch.zeros(B, **f64)
+        alconv = torch.ones(B, dtype=torch.int32, device=self.device)
+        outers, rounds, pos = [], [], []
+        for p in range(G):
+            sl = slice(p, None, G)
+            kw = dict(q_ref=q_ref[sl], xi_ref=xi_ref[sl], **{k: None if v is None else v[sl] for k, v in per.items()})
+            field = [] if static is None else [np.broadcast_to(static[sl][:, None], (F, self.N + 1, K0, 4))]
+            for t in pos:  # the members before p: [F, N+1, 3] each
+                field.append(np.concatenate([t, np.full((F, self.N + 1, 1), float(separation))], axis=-1)[:, :, None])
+            if not pos and static is None and lb is None:
+                o = {k: al_kw[k] for k in ("tol_grad_norm", "tol_d_norm", "line_search") if k in al_kw}
+                res = self.fit_batch(x0_q[sl], x0_xi[sl], us_init[sl], mode="ms", n_iterations=al_kw.get("n_ilqr_iters", 200),
+                                     **o, **kw)
+                outers.append(1)
+            else:
+                obs = np.concatenate(field, axis=2) if pos else None if static is None else static[sl]
+                res, info = self.al_fit_batch(x0_q[sl], x0_xi[sl], us_init[sl], lb, ub, obstacles=obs, **al_kw, **kw)
+                maxviol[sl], alconv[sl] = info["max_violation"], info["al_converged"]
+                outers.append(info["outer_iterations"])
+            rounds.append(res)
+            pos.append(res.xs_q[:, :, :3, 3].cpu().numpy())
+        batch = lambda name: torch.stack([getattr(r, name) for r in rounds], dim=1).flatten(0, 1)  # noqa: E731
+        out = FitResult(**{n: batch(n) for n in ("xs_q", "xs_xi", "us", "J_hist", "grad_hist", "defect_hist", "alpha_hist",
+                                                "mu_hist", "iters", "status", "converged")})
+        t = out.xs_q[:, :, :3, 3].reshape(F, G, self.N + 1, 3)
+        d = (t[:, :, None] - t[:, None]).norm(dim=-1)                       # [F, G, G, N+1]
+        d = d + torch.diag(torch.full((G,), float("inf"), **f64))[None, :, :, None]
+        return out, dict(min_separation=d.amin(dim=(1, 2, 3)), max_violation=maxviol, al_converged=alconv,
+                         outer_iterations=outers)
 
     # ------------------------------------------------------------------------------------------
     def linearize_backward(self, xs_q, xs_xi, us, ms=True, mu=1.0, delta=2.0, max_reg=1e10, q_ref=None, xi_ref=None, Q=None,

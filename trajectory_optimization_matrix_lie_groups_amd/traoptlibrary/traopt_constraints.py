@@ -85,19 +85,48 @@ class SphereObstacleConstraint(BaseConstraint):
         """The spheres as rows (cx, cy, cz, r) [K, 4]: the layout of tolg_set_al_obstacles."""
         return np.concatenate([self._centers, self._radii[:, None]], axis=1)
 
+    def _at(self, i):
+        """(centers [K, 3], radii [K]) at knot i"""
+        return self._centers, self._radii
+
     def g(self, x, u, i, terminal=False, *args, **kwargs):
-        d = np.asarray(x[0])[:3, 3][None] - self._centers
-        return self._radii ** 2 - np.sum(d * d, axis=1)
+        c, r = self._at(i)
+        d = np.asarray(x[0])[:3, 3][None] - c
+        return r ** 2 - np.sum(d * d, axis=1)
 
     def g_x(self, x, u, i, terminal=False, *args, **kwargs):
         X = np.asarray(x[0])
-        d = X[:3, 3][None] - self._centers
+        d = X[:3, 3][None] - self._at(i)[0]
         gx = np.zeros((self._constr_size, self._state_size))
         gx[:, 3:6] = -2.0 * d @ X[:3, :3]
         return gx
 
     def g_u(self, x, u, i, terminal=False, *args, **kwargs):
         return np.zeros((self._constr_size, self._action_size))
+
+
+class MovingSphereObstacleConstraint(SphereObstacleConstraint):
+    """Keep-out spheres whose geometry depends on the knot: g_k(x, i) = r_ik^2 - |t - c_ik|^2 <= 0 with centers [N+1, K, 3] and
+    radii [N+1, K] (or [K]: the same at every knot), terminal knot included.  g and g_x are SphereObstacleConstraint's on the
+    geometry of knot i (_at); on the device these are the terms of tolg_set_al_obstacles_moving."""
+
+    def __init__(self, centers, radii, state_size=(6, 6), action_size=6):
+        c = np.asarray(centers, dtype=np.float64)
+        if c.ndim != 3 or c.shape[2] != 3:
+            raise ValueError("centers has shape %s, expected (N+1, K, 3)" % (c.shape,))
+        r = np.asarray(radii, dtype=np.float64)
+        if r.shape not in (c.shape[:2], c.shape[1:2]):
+            raise ValueError("radii has shape %s, expected (N+1, K) or (K,)" % (r.shape,))
+        super().__init__(c[0], np.broadcast_to(r, c.shape[:2])[0], state_size, action_size)  # (sizes; knot 0's geometry)
+        self._centers = c.copy()                             # [N+1, K, 3]
+        self._radii = np.broadcast_to(r, c.shape[:2]).copy()  # [N+1, K]
+
+    def obstacles(self):
+        """The spheres as rows (cx, cy, cz, r) per knot [N+1, K, 4]: a trajectory's slice of tolg_set_al_obstacles_moving."""
+        return np.concatenate([self._centers, self._radii[..., None]], axis=2)
+
+    def _at(self, i):
+        return self._centers[i], self._radii[i]
 
 
 class ConstraintStack(BaseConstraint):

@@ -303,12 +303,12 @@ class iLQR_Tracking_SE3_MS(_FusedController):
 
 def _route_constraints(constraints):
     """(InputConstraint or None, SphereObstacleConstraint or None) of what AL_iLQR_Tracking_SE3_MS solves on the device: an
-    InputConstraint, a SphereObstacleConstraint, or a ConstraintStack of one of each.  TypeError for anything else: no
-    constraint is ever treated as g_x = 0."""
-    from .traopt_constraints import ConstraintStack, InputConstraint, SphereObstacleConstraint
+    InputConstraint, a SphereObstacleConstraint (or its per-knot form, MovingSphereObstacleConstraint), or a ConstraintStack of
+    one of each.  TypeError for anything else: no constraint is ever treated as g_x = 0."""
+    from .traopt_constraints import ConstraintStack, InputConstraint, MovingSphereObstacleConstraint, SphereObstacleConstraint
     parts = constraints.constraints if type(constraints) is ConstraintStack else (constraints,)
     box = [c for c in parts if type(c) is InputConstraint]
-    sph = [c for c in parts if type(c) is SphereObstacleConstraint]
+    sph = [c for c in parts if type(c) in (SphereObstacleConstraint, MovingSphereObstacleConstraint)]
     if len(box) > 1 or len(sph) > 1 or len(box) + len(sph) != len(parts):
         raise TypeError("AL_iLQR_Tracking_SE3_MS supports an InputConstraint, a SphereObstacleConstraint, or a ConstraintStack "
                         "of one of each; got %s" % ", ".join(type(c).__name__ for c in parts))
@@ -360,11 +360,14 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
             us_init = np.broadcast_to(np.asarray(us_init, float), (B,) + np.shape(us_init)).copy()
         solver = self.ilqr_solver._get_solver(B)
         box, sph = self._box, self._spheres
+        obstacles = sph.obstacles() if sph else None
+        if obstacles is not None and obstacles.ndim == 3:  # a field per knot [N+1, K, 4]: the same for every trajectory
+            obstacles = np.broadcast_to(obstacles, (B,) + obstacles.shape)
         return solver.al_fit_batch(q, xi, us_init, box.lb if box else None, box.ub if box else None, n_al_iters=n_al_iters,
                                    n_ilqr_iters=n_ilqr_iters, tol_grad_norm=tol_grad_norm, tol_constr=tol_constr,
                                    mu0=self._mu0, mu_scale=self._mu_scale, mu_max=self._mu_max,
                                    line_search=self.ilqr_solver._line_search, on_outer=on_outer, q_ref=q_ref,
-                                   xi_ref=xi_ref, Q=Qs, P=Ps, R=Rs, obstacles=sph.obstacles() if sph else None)
+                                   xi_ref=xi_ref, Q=Qs, P=Ps, R=Rs, obstacles=obstacles)
 
     def fit(self, x0, us_init, n_al_iters=100, n_ilqr_iters=200, tol_J=1e-6, tol_grad_norm=1e-6, tol_constr=1e-2,
             on_iteration_al=None, on_iteration_ilqr=None):

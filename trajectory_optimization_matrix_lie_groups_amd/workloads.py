@@ -368,3 +368,51 @@ def drone_obstacle_field(B, K, N=400, seed=SEED):
     sphere would hardly be violated).  Returns (prob, x0_q, x0_xi, us0, obstacles [B, K, 4])."""
     prob, x0_q, x0_xi, us0 = drone_tracking(B, N=N, seed=seed)
     return prob, x0_q, x0_xi, us0, _obstacle_field(prob.q_ref, B, K, 0.1, 0.2, seed + 3)
+
+
+def se3_moving_obstacle_field(B, K, N=200, seed=SEED):
+    """se3_obstacle_field's workload with its spheres in motion: sphere k of trajectory b drifts with a constant seeded velocity
+    (0.5 .. 1.5 radii over a quarter of the horizon) and is at its static centre -- on the reference path -- at the knot whose
+    reference position is nearest to that centre, so the path violates it there; a velocity is halved until the sphere is
+    clear of the reference positions of knots 0 and N.  Returns (prob, x0_q, x0_xi, us0, obstacles [B, N+1, K, 4]), the
+    per-knot rows (cx, cy, cz, r) of set_al_obstacles."""
+    prob, x0_q, x0_xi, us0, obs = se3_obstacle_field(B, K, N=N, seed=seed)
+    rng = np.random.default_rng(seed + 4)
+    t = prob.q_ref[:, :3, 3]
+    s = np.arange(N + 1, dtype=np.float64)
+    mov = np.empty((B, N + 1, K, 4))
+    for b in range(B):
+        for k in range(K):
+            c, r = obs[b, k, :3], obs[b, k, 3]
+            i0 = int(np.argmin(np.sum((t - c) ** 2, axis=1)))
+            d = rng.normal(size=3)
+            v = rng.uniform(0.5, 1.5) * r / max(1, N // 4) * d / np.linalg.norm(d)  # per knot
+            while True:
+                ck = c + (s - i0)[:, None] * v
+                if all(np.sum((t[i] - ck[i]) ** 2) > r * r for i in (0, N)):
+                    break
+                v = 0.5 * v
+            mov[b, :, k, :3], mov[b, :, k, 3] = ck, r
+    return prob, x0_q, x0_xi, us0, mov
+
+
+def se3_crossing_fleet(F, G, N=40, separation=0.3, seed=SEED):
+    """F fleets of G members whose paths cross: member p tracks g_p q_ref, with g_p the rotation by p pi / G about world z
+    through the reference's position at knot N // 2 plus a z shift of 0.3 separation p -- every pair of paths passes within
+    less than `separation` near the middle knot.  xi_ref is shared (body twists do not change under a left multiplication);
+    member (f, p) starts at g_p applied to fleet f's perturbed start of se3_tracking(F, N, R_scale=1e-3).  Batch index
+    f * G + p.  Returns (prob, x0_q, x0_xi, us0, q_ref [F G, N+1, 4, 4], xi_ref [F G, N+1, 6])."""
+    prob, q, xi, _ = se3_tracking(F, N=N, R_scale=1e-3, seed=seed)
+    c = prob.q_ref[N // 2][:3, 3]
+    B = F * G
+    x0_q, x0_xi = np.empty((B, 4, 4)), np.empty((B, 6))
+    q_ref, xi_ref = np.empty((B, N + 1, 4, 4)), np.empty((B, N + 1, 6))
+    for p in range(G):
+        g = np.eye(4)
+        g[:3, :3] = _so3_exp(np.array([0.0, 0.0, p * np.pi / G]))
+        g[:3, 3] = c - g[:3, :3] @ c + np.array([0.0, 0.0, 0.3 * separation * p])
+        for f in range(F):
+            b = f * G + p
+            x0_q[b], x0_xi[b] = g @ q[f], xi[f]
+            q_ref[b], xi_ref[b] = g @ prob.q_ref, prob.xi_ref
+    return prob, x0_q, x0_xi, np.zeros((B, N, 6)), q_ref, xi_ref
