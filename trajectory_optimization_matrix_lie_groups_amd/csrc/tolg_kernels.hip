@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/tolg.h"
@@ -4410,38 +4411,6 @@ __global__ void k_ls_finish(Params P, int it) {
   if (P.defect_hist) P.defect_hist[(size_t)b * (P.max_iter + 1) + it + 1] = P.dn[b];
 }
 
-// Augmented-Lagrangian outer update (AL_iLQR_Tracking_SE3_MS._al_update_param,
-// traopt_controller.py:3270-3290) and the constraint evaluation of :3242-3250, one thread per
-// trajectory: lambda <- max(0, lambda + I_mu g), mu <- min(mu_scale mu, mu_max),
-// I_mu <- 0 where (g < 0 and lambda_new == 0) else mu_new; maxviol = max g over all knots.
-__global__ void k_al_update(int B, int N, int m, const double* __restrict__ us, const double* __restrict__ lb,
-                            const double* __restrict__ ub, double* __restrict__ lam, double* __restrict__ imu,
-                            double* __restrict__ mu, double mu_scale, double mu_max, double tol_constr,
-                            double* __restrict__ maxviol, int* __restrict__ al_conv) {
-  int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B || al_conv[b]) return;  // a converged problem keeps its multipliers
-  double mv = 0.0;                   // the terminal knot contributes g = 0
-  for (int i = 0; i < N; i++) {
-    const double* u = us + ((size_t)b * N + i) * m;
-    for (int k = 0; k < 2 * m; k++) mv = fmax(mv, (k < m) ? lb[k] - u[k] : u[k - m] - ub[k - m]);
-  }
-  maxviol[b] = mv;
-  if (mv < tol_constr) { al_conv[b] = 1; return; }  // traopt_controller.py:3250, :3262-3263
-  const double mu_new = fmin(mu[b] * mu_scale, mu_max);
-  for (int i = 0; i < N; i++) {
-    const double* u = us + ((size_t)b * N + i) * m;
-    double* l = lam + ((size_t)b * N + i) * 2 * m;
-    double* im = imu + ((size_t)b * N + i) * 2 * m;
-    for (int k = 0; k < 2 * m; k++) {
-      double g = (k < m) ? lb[k] - u[k] : u[k - m] - ub[k - m];
-      double ln = fmax(0.0, l[k] + im[k] * g);
-      l[k] = ln;
-      im[k] = (g < 0.0 && ln == 0.0) ? 0.0 : mu_new;
-    }
-  }
-  mu[b] = mu_new;
-}
-
 // ---- single-knot probe (tolg_eval_knot): the reference's per-knot plugin methods f, f_x, f_u, l, l_x,
 // l_u, l_xx, l_uu, _err evaluated for n states at knot i
 __global__ void k_probe_pack(Params P, int i, const double* __restrict__ x_q, const double* __restrict__ x_xi,
@@ -4630,13 +4599,15 @@ using namespace tolg;
 // The kernels that serve one handle: which template instantiation runs for which model is decided once, here, when the
 // handle is created (kernel_table below).  Launch sites pick an entry by what changes from call to call -- the pass of
 // the sweep, AL terms on or off, the rollout form, the search kind, the stage -- and never test the model themselves.
-// A handle holds four tables, kt_pt[PT] with PT a set of PT_REF and PT_W.  PT_REF: the kernels that read the reference (K1,
-// the fused launch, the line-search evaluations, k_init) read trajectory b's own reference (tolg_set_refs).  PT_W: the
+// A handle holds eight tables, kt_pt[PT] with PT a set of PT_REF, PT_W and PT_OBS: bit 1 << k is set when the handle holds
+// the per-trajectory input pt[k] (Held, below).  PT_REF: the kernels that read the reference (K1, the fused launch, the
+// line-search evaluations, k_init) read trajectory b's own reference (tolg_set_refs, tolg_set_ref_windows).  PT_W: the
 // kernels that read the cost weights (K1, the fused launch, the line-search evaluations, both backward sweeps, both forms of
 // the expected change) read trajectory b's own diagonal weights (tolg_set_weights).  Every other entry is the same kernel in
-// all four.  PT_OBS: the kernels that evaluate costs (K1, the fused launch, k_rollout_eval_t, k_ls_eval, k_ls_eval_affine) add
-// the augmented-Lagrangian terms of trajectory b's keep-out spheres (tolg_set_al_obstacles); every other entry of the four
-// tables with PT_OBS is the entry of the table without it.
+// all of them.  PT_OBS: the kernels that evaluate costs (K1, the fused launch, k_rollout_eval_t, k_ls_eval, k_ls_eval_affine)
+// add the augmented-Lagrangian terms of trajectory b's keep-out spheres (tolg_set_al_obstacles, tolg_set_al_obstacles_moving);
+// every other entry of the four tables with PT_OBS is the entry of the table without it.  The plant (tolg_set_plant) selects
+// no table: the two closed-loop entries that step it are in every table.
 typedef void (*SearchKernel)(Params, int, int, int);
 typedef void (*SearchRollout)(Params, int, int, int, int);
 struct KernelTable {
@@ -4793,33 +4764,43 @@ static int lazy_create(LazyRes& r, int n_ints) {  // n_ints = 0: the stream form
   return 0;
 }
 
+// An input a caller attaches to the handle: the packed buffer the kernels read (caller-owned; null: nothing held) and the
+// batch it was set for.
+struct Held {
+  const double* p = nullptr;
+  int B = 0;
+};
+// The per-trajectory inputs, pt[k] the one whose PT_* bit is 1 << k: references, weights, keep-out spheres
+enum { H_REFS, H_WTS, H_OBS, H_PT };
+static_assert(PT_REF == 1 << H_REFS && PT_W == 1 << H_WTS && PT_OBS == 1 << H_OBS, "pt[k] is the input of PT bit 1 << k");
+
 struct tolg_handle_s {
-  tolg_problem prob;
-  Consts hc;
-  int max_batch, Bp_max;
-  char* ws;
-  size_t ws_bytes;
-  Params P;  // pointers carved for Bp_max; per-solve Bp may be smaller (arrays are re-strided)
-  Params run;         // parameters of the solve in flight (tolg_solve_begin .. tolg_solve_end)
-  tolg_options run_opt;
-  LsPlan run_ls;      // ... and its line search
-  int run_it;         // iterations issued so far
-  bool running;
-  int lds_per_block;  // hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KB on MI355X)
-  int rec_closed = 0; // the knot records were last written by the fused rollout (no defect field, see k_backward)
-  KernelTable kt;     // the model's kernels for the solves to come: kt_pt[(refs ? PT_REF : 0) | (wts ? PT_W : 0) | (obs ? PT_OBS : 0)]
-  KernelTable kt_pt[8];  // kernel_table_for<PT>: [0] batch-shared reference and weights, no spheres, [PT_REF | PT_W] per trajectory
-  const double* ref_shared;  // the reference packed by tolg_create (P.ref as carved)
-  const double* refs = nullptr;  // tolg_set_refs: the packed per-trajectory references (caller-owned), or null
-  int refs_B = 0;                // ... and the batch they were set for: every batch call must match it
-  const double* wts = nullptr;   // tolg_set_weights: the packed per-trajectory weights (caller-owned), or null
-  int wts_B = 0;                 // ... and their batch, as refs_B
-  const double* obs = nullptr;   // tolg_set_al_obstacles: the packed sphere geometry (caller-owned), or null
-  int obs_B = 0, obs_K = 0;      // ... their batch, as refs_B, and the spheres per trajectory
-  size_t obs_stride = 0;         // ... the knot stride of the geometry in doubles (Consts::obs_stride): 0, or 4 K Bp for the moving form
+  tolg_problem prob{};
+  Consts hc{};
+  int max_batch = 0, Bp_max = 0;
+  char* ws = nullptr;
+  size_t ws_bytes = 0;
+  Params P{};  // pointers carved for Bp_max; per-solve Bp may be smaller (arrays are re-strided)
+  Params run{};           // parameters of the solve in flight (tolg_solve_begin .. tolg_solve_end)
+  tolg_options run_opt{};
+  LsPlan run_ls{};        // ... and its line search
+  int run_it = 0;         // iterations issued so far
+  bool running = false;
+  int lds_per_block = 0;  // hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KB on MI355X)
+  int rec_closed = 0;     // the knot records were last written by the fused rollout (no defect field, see k_backward)
+  KernelTable kt{};       // the model's kernels for the solves to come: kt_pt[the PT bits of the pt[k] held] (select_kernels)
+  KernelTable kt_pt[1 << H_PT] = {};  // kernel_table_for<PT>: [0] batch-shared reference and weights, no spheres
+  const double* ref_shared = nullptr;  // the reference packed by tolg_create (P.ref as carved)
+  // pt[H_REFS] tolg_set_refs / tolg_set_ref_windows, pt[H_WTS] tolg_set_weights, pt[H_OBS] tolg_set_al_obstacles(_moving).
+  // One batch: every batch call, and every further pt[k], must be for the B of those held (one_batch)
+  Held pt[H_PT];
+  int obs_K = 0;          // pt[H_OBS]: the spheres per trajectory,
+  size_t obs_stride = 0;  // ... the knot stride of the geometry in doubles (Consts::obs_stride): 0, or 4 K Bp for the moving form
   double *obs_lam = nullptr, *obs_imu = nullptr;  // ... their multipliers [B][N+1][K] (caller-owned; tolg_al_update_state writes them)
-  const double* plant = nullptr;  // tolg_set_plant: the packed plant rows (caller-owned), or null: the closed loops step the model
-  int plant_B = 0, plant_S = 0, plant_form = 0;  // ... their batch, samples per trajectory and TOLG_PLANT_* form
+  // tolg_set_plant: the packed plant rows, or nothing held: the closed loops step the model.  Outside the one-batch rule (its
+  // B is checked against the policy call's) and outside PT
+  Held plant;
+  int plant_S = 0, plant_form = 0;  // ... its samples per trajectory and TOLG_PLANT_* form
   // The held policy (tolg_solve_gains, tolg_policy_rollout): nominal trajectory P.cur / P.cur_u and gains P.GK of a batch of
   // pol_B trajectories, 0 = none.  Set by tolg_solve_end and tolg_linearize_backward; cleared by tolg_solve_begin(_warm) and
   // tolg_eval_knot (k_probe_pack writes P.cur); tolg_rollout (writes the candidate arrays) and tolg_expected_change (ED, ecc)
@@ -4828,17 +4809,17 @@ struct tolg_handle_s {
   bool pol_traj_fast = false;    // A/B switch (TOLG_POLICY_TRAJ_FAST=1): k_policy_rollout in K3's sample order
   // A/B switches of the tests, read from the environment when the handle is created: every sweep the full kernel
   // (TOLG_K2_FULL_ONLY=1), the one-wave forms of the line-search rollouts (TOLG_LS_ONEWAVE=1)
-  bool k2_full_only, ls_one_wave;
-  const double *al_lb, *al_ub, *al_lambda, *al_imu;  // augmented-Lagrangian terms (null = off)
+  bool k2_full_only = false, ls_one_wave = false;
+  const double *al_lb = nullptr, *al_ub = nullptr, *al_lambda = nullptr, *al_imu = nullptr;  // tolg_set_al: the input box (null = off)
   // early exit of a sliced solve (tolg_solve_iterate_until): two device counters, their pinned host copies, two events
   LazyRes cnt;
   // merit search: the linear alpha = 1 rollout (k_expected_change) runs on a side stream beside the first line-search stage
   LazyRes side;
   // timing
-  bool timing;
+  bool timing = false;
   std::vector<hipEvent_t> ev;  // pairs
   std::vector<int> ev_kind;    // 0 backward, 1 rollout, 2 linearize
-  size_t ev_used;
+  size_t ev_used = 0;
 };
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -4849,14 +4830,43 @@ static int padded_batch(int B) { return (B + 3) / 4 * 4; }
 static dim3 traj_grid(const Params& P) { return dim3((P.Bp + 63) / 64); }
 static dim3 knot_grid(int knots, int Bp) { return dim3((unsigned)(((size_t)knots * Bp + 255) / 256)); }
 
-// B trajectories fit the handle and the per-trajectory references and weights it holds (tolg_set_refs, tolg_set_weights):
-// what every batch call on the handle's workspace requires
-static bool batch_fits(const tolg_handle_s* h, int B) {
-  return B >= 1 && B <= h->max_batch && !(h->refs && B != h->refs_B) && !(h->wts && B != h->wts_B) && !(h->obs && B != h->obs_B);
+// The rules of the held inputs, each stated once.
+// Per-trajectory inputs: one batch.  B agrees with every pt[k] held other than `except` (the setter's own, which it replaces):
+// kernels never read arrays strided for different Bp
+static bool one_batch(const tolg_handle_s* h, int B, const Held* except = nullptr) {
+  for (const Held& r : h->pt) if (&r != except && r.p && B != r.B) return false;
+  return true;
 }
-// the kernels of h->kt follow what per-trajectory inputs are set (kernel_table, PT)
+// B trajectories fit the handle and the per-trajectory inputs it holds: what every batch call on the handle's workspace requires
+static bool batch_fits(const tolg_handle_s* h, int B) { return B >= 1 && B <= h->max_batch && one_batch(h, B); }
+// A setter's destination: 1 <= B <= max_batch, d non-null, 8-byte aligned and of at least need(prob, B, n) bytes
+// (refs_bytes_for and its like: what the tolg_*_bytes calls return; n the spheres or samples per trajectory)
+typedef size_t (*BytesFor)(const tolg_problem*, int B, int n);
+static bool dest_ok(const tolg_handle_s* h, int B, const void* d, size_t bytes, BytesFor need, int n = 0) {
+  return B >= 1 && B <= h->max_batch && d && (reinterpret_cast<uintptr_t>(d) & 7) == 0 && bytes >= need(&h->prob, B, n);
+}
+// the kernels of h->kt follow what per-trajectory inputs are held (kernel_table, PT)
 static void select_kernels(tolg_handle_s* h) {
-  h->kt = h->kt_pt[(h->refs ? PT_REF : 0) | (h->wts ? PT_W : 0) | (h->obs ? PT_OBS : 0)];
+  int pt = 0;
+  for (int k = 0; k < H_PT; k++) if (h->pt[k].p) pt |= 1 << k;
+  h->kt = h->kt_pt[pt];
+}
+// kt_pt[PT] = kernel_table_for<PT>, for every set PT of the PT_* bits (tolg_create)
+template <int... PT>
+static void fill_kernel_tables(tolg_handle_s* h, std::integer_sequence<int, PT...>) {
+  ((h->kt_pt[PT] = kernel_table_for<PT>(h->prob, h->hc, h->lds_per_block)), ...);
+}
+// What a setter's packing kernel queued on the stream: the handle's input r from now on ...
+static void hold(tolg_handle_s* h, Held& r, const void* d, int B) {
+  r = Held{static_cast<const double*>(d), B};
+  select_kernels(h);
+}
+// ... and back to what tolg_create left, r's extras with it.  (Both reselect the kernels: nothing changes for the plant.)
+static void drop(tolg_handle_s* h, Held& r) {
+  r = Held();
+  if (&r == &h->pt[H_OBS]) { h->obs_K = 0; h->obs_stride = 0; h->obs_lam = h->obs_imu = nullptr; }
+  if (&r == &h->plant) h->plant_S = h->plant_form = 0;
+  select_kernels(h);
 }
 
 static int host_inv6(const double A[36], double Ai[36]) {
@@ -4991,11 +5001,6 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
   h->Bp_max = padded_batch(max_batch);
   h->ws = static_cast<char*>(d_workspace);
   h->ws_bytes = workspace_bytes;
-  h->timing = false;
-  h->ev_used = 0;
-  h->running = false;
-  h->run_it = 0;
-  h->al_lb = h->al_ub = h->al_lambda = h->al_imu = nullptr;
   {
     int dev = 0, lds = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -5060,14 +5065,7 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
         c.Llin[a][6 * i + j] = sacc * prob->dt;
       }
   }
-  h->kt_pt[0] = kernel_table_for<0>(*prob, c, h->lds_per_block);
-  h->kt_pt[PT_REF] = kernel_table_for<PT_REF>(*prob, c, h->lds_per_block);
-  h->kt_pt[PT_W] = kernel_table_for<PT_W>(*prob, c, h->lds_per_block);
-  h->kt_pt[PT_REF | PT_W] = kernel_table_for<PT_REF | PT_W>(*prob, c, h->lds_per_block);
-  h->kt_pt[PT_OBS] = kernel_table_for<PT_OBS>(*prob, c, h->lds_per_block);
-  h->kt_pt[PT_REF | PT_OBS] = kernel_table_for<PT_REF | PT_OBS>(*prob, c, h->lds_per_block);
-  h->kt_pt[PT_W | PT_OBS] = kernel_table_for<PT_W | PT_OBS>(*prob, c, h->lds_per_block);
-  h->kt_pt[PT_REF | PT_W | PT_OBS] = kernel_table_for<PT_REF | PT_W | PT_OBS>(*prob, c, h->lds_per_block);
+  fill_kernel_tables(h, std::make_integer_sequence<int, 1 << H_PT>());
   select_kernels(h);
   {
     const char* e = getenv("TOLG_K2_FULL_ONLY");
@@ -5170,7 +5168,7 @@ static Params params_for(tolg_handle_s* h, int B) {
   P.J_hist = P.grad_hist = P.defect_hist = P.alpha_hist = P.mu_hist = nullptr;
   P.max_iter = 0; P.tol_grad = 0; P.tol_defect = 0; P.max_reg = 1e10;
   P.al_lb = h->al_lb; P.al_ub = h->al_ub; P.al_lambda = h->al_lambda; P.al_imu = h->al_imu;
-  P.ref = h->refs ? h->refs : h->ref_shared;  // the layout h->kt's kernels read
+  P.ref = h->pt[H_REFS].p ? h->pt[H_REFS].p : h->ref_shared;  // the layout h->kt's kernels read
   const bool grav = h->hc.grav != 0.0;
   // the velocity block of F_x is stored only for the models the third form of the backward sweep does not cover
   const bool a22 = !(h->hc.diagJ != 0 && h->prob.kind != TOLG_DYN_PENDULUM3D);
@@ -5579,7 +5577,7 @@ extern "C" int tolg_set_al(tolg_handle_t h, const double* d_lb, const double* d_
   return 0;
 }
 
-static size_t refs_bytes_for(const tolg_problem* p, int B) {
+static size_t refs_bytes_for(const tolg_problem* p, int B, int = 0) {
   return (size_t)(p->N + 1) * 13 * (size_t)padded_batch(B) * sizeof(double);
 }
 extern "C" size_t tolg_refs_bytes(const tolg_problem* prob, int32_t max_batch) {
@@ -5587,42 +5585,30 @@ extern "C" size_t tolg_refs_bytes(const tolg_problem* prob, int32_t max_batch) {
   return refs_bytes_for(prob, max_batch);
 }
 
-// tolg_set_refs and tolg_set_ref_windows: d_refs can hold the packed references of B trajectories (8-byte aligned, refs_bytes
-// large enough), and B is the batch of the per-trajectory weights when they are set (references and weights: one batch)
-static bool refs_dest_ok(const tolg_handle_s* h, int B, const void* d_refs, size_t refs_bytes) {
-  return B >= 1 && B <= h->max_batch && d_refs && (reinterpret_cast<uintptr_t>(d_refs) & 7) == 0 &&
-         refs_bytes >= refs_bytes_for(&h->prob, B) && !(h->wts && B != h->wts_B) && !(h->obs && B != h->obs_B);
-}
-// ... and what the packing kernel queued on the stream: the handle's references from now on
-static void hold_refs(tolg_handle_s* h, int B, const void* d_refs) {
-  h->refs = static_cast<const double*>(d_refs); h->refs_B = B; select_kernels(h);
-}
-
 extern "C" int tolg_set_refs(tolg_handle_t h, int32_t B, const double* d_q_ref, const double* d_xi_ref, void* d_refs,
                              size_t refs_bytes, void* stream) {
   if (!h || h->running) return TOLG_E_ARG;
-  if (!d_q_ref) {  // back to the reference of tolg_create
-    h->refs = nullptr; h->refs_B = 0; select_kernels(h);
-    return 0;
-  }
-  if (!d_xi_ref || !refs_dest_ok(h, B, d_refs, refs_bytes)) return TOLG_E_ARG;
+  Held& r = h->pt[H_REFS];
+  if (!d_q_ref) { drop(h, r); return 0; }  // back to the reference of tolg_create
+  if (!d_xi_ref || !dest_ok(h, B, d_refs, refs_bytes, refs_bytes_for) || !one_batch(h, B, &r)) return TOLG_E_ARG;
   const int N = h->prob.N, Bp = padded_batch(B);
   hipLaunchKernelGGL(k_pack_refs, knot_grid(N + 1, Bp), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp, N, d_q_ref, d_xi_ref,
                      static_cast<double*>(d_refs));
   LAUNCH_CHECK();
-  hold_refs(h, B, d_refs);
+  hold(h, r, d_refs, B);
   return 0;
 }
 
 extern "C" int tolg_set_ref_windows(tolg_handle_t h, int32_t B, const double* d_path_q, const double* d_path_xi, int32_t T,
                                     const int32_t* d_t0, int32_t t, void* d_refs, size_t refs_bytes, void* stream) {
   if (!h || h->running || !d_path_q || !d_path_xi || T < 1 || t < 0) return TOLG_E_ARG;
-  if (!refs_dest_ok(h, B, d_refs, refs_bytes)) return TOLG_E_ARG;
+  Held& r = h->pt[H_REFS];
+  if (!dest_ok(h, B, d_refs, refs_bytes, refs_bytes_for) || !one_batch(h, B, &r)) return TOLG_E_ARG;
   const int N = h->prob.N, Bp = padded_batch(B);
   hipLaunchKernelGGL(k_pack_ref_windows, knot_grid(N + 1, Bp), dim3(256), 0, static_cast<hipStream_t>(stream), B,
                      Bp, N, (int)T, d_path_q, d_path_xi, reinterpret_cast<const int*>(d_t0), (int)t, static_cast<double*>(d_refs));
   LAUNCH_CHECK();
-  hold_refs(h, B, d_refs);
+  hold(h, r, d_refs, B);
   return 0;
 }
 
@@ -5637,7 +5623,7 @@ __global__ void k_pack_weights(int B, int Bp, int m, const double* __restrict__ 
   const int bs = b < B ? b : B - 1;
   w[t] = f < 12 ? q_diag[(size_t)bs * 12 + f] : f < 24 ? p_diag[(size_t)bs * 12 + f - 12] : r_diag[(size_t)bs * m + f - 24];
 }
-static size_t weights_bytes_for(const tolg_problem* p, int B) {
+static size_t weights_bytes_for(const tolg_problem* p, int B, int = 0) {
   return (size_t)wt_fields(p->m) * (size_t)padded_batch(B) * sizeof(double);
 }
 extern "C" size_t tolg_weights_bytes(const tolg_problem* prob, int32_t max_batch) {
@@ -5648,67 +5634,43 @@ extern "C" size_t tolg_weights_bytes(const tolg_problem* prob, int32_t max_batch
 extern "C" int tolg_set_weights(tolg_handle_t h, int32_t B, const double* d_q_diag, const double* d_p_diag,
                                 const double* d_r_diag, void* d_w, size_t w_bytes, void* stream) {
   if (!h || h->running) return TOLG_E_ARG;
-  if (!d_q_diag) {  // back to the weights of tolg_create
-    h->wts = nullptr; h->wts_B = 0; select_kernels(h);
-    return 0;
-  }
-  if (B < 1 || B > h->max_batch || !d_p_diag || !d_r_diag || !d_w || (reinterpret_cast<uintptr_t>(d_w) & 7) != 0) return TOLG_E_ARG;
-  if (w_bytes < weights_bytes_for(&h->prob, B)) return TOLG_E_ARG;
-  if ((h->refs && B != h->refs_B) || (h->obs && B != h->obs_B)) return TOLG_E_ARG;  // per-trajectory inputs: one batch
+  Held& r = h->pt[H_WTS];
+  if (!d_q_diag) { drop(h, r); return 0; }  // back to the weights of tolg_create
+  if (!d_p_diag || !d_r_diag || !dest_ok(h, B, d_w, w_bytes, weights_bytes_for) || !one_batch(h, B, &r)) return TOLG_E_ARG;
   const int Bp = padded_batch(B);
   const size_t n = (size_t)wt_fields(h->prob.m) * Bp;
   hipLaunchKernelGGL(k_pack_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp,
                      h->prob.m, d_q_diag, d_p_diag, d_r_diag, static_cast<double*>(d_w), const_cast<Consts*>(h->P.c));
   LAUNCH_CHECK();
-  h->wts = static_cast<const double*>(d_w); h->wts_B = B; select_kernels(h);
+  hold(h, r, d_w, B);
   return 0;
 }
 
-extern "C" int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, const double* d_lb, const double* d_ub,
-                              double* d_lambda, double* d_imu, double* d_mu, double mu_scale, double mu_max,
-                              double tol_constr, double* d_maxviol, int32_t* d_al_converged, void* stream) {
-  if (!h || B < 1 || !d_us || !d_lb || !d_ub || !d_lambda || !d_imu || !d_mu || !d_maxviol || !d_al_converged)
-    return TOLG_E_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_al_update, dim3((B + 63) / 64), dim3(64), 0, st, B, h->prob.N, h->prob.m, d_us, d_lb, d_ub,
-                     d_lambda, d_imu, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, d_al_converged);
-  LAUNCH_CHECK();
-  return 0;
-}
-
-// d_obs [B][K][4] = (cx, cy, cz, r) into [4K][Bp] (field f = 4k + c of trajectory b at f * Bp + b); padded trajectories b >= B
-// replicate b = B-1.  Thread 0 points the handle's constants at the geometry and at the caller's multipliers (stream-ordered
-// before the solves that read them).
-__global__ void k_pack_obstacles(int B, int Bp, int K, const double* __restrict__ obs, const double* lam, const double* imu,
-                                 double* __restrict__ w, Consts* c) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; c->obs_stride = 0; }
-  if (t >= (size_t)4 * K * Bp) return;
-  const int b = (int)(t % Bp), f = (int)(t / Bp);
-  const int bs = b < B ? b : B - 1;
-  w[t] = obs[(size_t)bs * 4 * K + f];
-}
-
-// The same per knot (tolg_set_al_obstacles_moving): d_obs [B][N+1][K][4] into [N+1][4K][Bp], field f of knot i of trajectory b
-// at (i * 4K + f) * Bp + b, padded trajectories as above; the knot stride 4 K Bp goes into the constants.
-__global__ void k_pack_obstacles_moving(int B, int Bp, int K, int N, const double* __restrict__ obs, const double* lam,
-                                        const double* imu, double* __restrict__ w, Consts* c) {
+// d_obs [B][knots][K][4] = (cx, cy, cz, r) into [knots][4K][Bp]: field f = 4k + c of knot i of trajectory b at (i * 4K + f) * Bp
+// + b; padded trajectories b >= B replicate b = B-1.  knots = 1 is the static form (tolg_set_al_obstacles: one [4K][Bp] block
+// for every knot, `stride` 0), knots = N + 1 the per-knot form (tolg_set_al_obstacles_moving: `stride` 4 K Bp).  Thread 0 points
+// the handle's constants at the geometry, its knot stride and the caller's multipliers (stream-ordered before the solves that
+// read them).
+__global__ void k_pack_obstacles_moving(int B, int Bp, int K, int knots, size_t stride, const double* __restrict__ obs,
+                                        const double* lam, const double* imu, double* __restrict__ w, Consts* c) {
   size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t knot = (size_t)4 * K * Bp;
-  if (t == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; c->obs_stride = knot; }
-  if (t >= knot * (size_t)(N + 1)) return;
+  if (t == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; c->obs_stride = stride; }
+  if (t >= knot * (size_t)knots) return;
   const size_t i = t / knot, r = t % knot;
   const int b = (int)(r % Bp), f = (int)(r / Bp);
   const int bs = b < B ? b : B - 1;
-  w[t] = obs[((size_t)bs * (N + 1) + i) * 4 * K + f];
+  w[t] = obs[((size_t)bs * knots + i) * 4 * K + f];
 }
 
-// One outer update over every constraint the handle holds (tolg_al_update_state): the input box of tolg_set_al on the
-// controls and the keep-out spheres of tolg_set_al_obstacles (geo_stride 0) or tolg_set_al_obstacles_moving (knot i's geometry
-// i * geo_stride doubles on) on the positions of xs_q [B][N+1][16], one thread per trajectory.
-// maxviol = the largest g of them all (the box contributes the zero rows of its terminal knot, traopt_constraints.py:160-161;
-// the spheres have no such rows), one mu per problem, the update rule of k_al_update for both multiplier sets
-// (traopt_controller.py:3242-3250, :3270-3290).
+// The augmented-Lagrangian outer update (AL_iLQR_Tracking_SE3_MS._al_update_param, traopt_controller.py:3270-3290) and the
+// constraint evaluation of :3242-3250 over every constraint it is given, one thread per trajectory: the input box lb / ub
+// with its multipliers lam / imu on the controls, and the keep-out spheres geo (null: none; geo_stride 0 for
+// tolg_set_al_obstacles, else knot i's geometry i * geo_stride doubles on) with olam / oimu on the positions of xs_q
+// [B][N+1][16].  lambda <- max(0, lambda + I_mu g), mu <- min(mu_scale mu, mu_max), I_mu <- 0 where (g < 0 and lambda_new ==
+// 0) else mu_new for both multiplier sets; maxviol = the largest g of them all (the box contributes the zero rows of its
+// terminal knot, traopt_constraints.py:160-161; the spheres have no such rows), one mu per problem.  tolg_al_update passes
+// the box of its own arguments and no geometry, tolg_al_update_state what the handle holds.
 __global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const double* __restrict__ xs_q, const double* __restrict__ us,
                                   const double* __restrict__ lb, const double* __restrict__ ub, double* __restrict__ lam,
                                   double* __restrict__ imu, const double* __restrict__ geo, size_t geo_stride, double* __restrict__ olam,
@@ -5754,69 +5716,71 @@ __global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const doub
   mu[b] = mu_new;
 }
 
-static size_t obstacles_bytes_for(int B, int K) { return (size_t)4 * K * (size_t)padded_batch(B) * sizeof(double); }
+static size_t obstacles_bytes_for(const tolg_problem*, int B, int K) { return (size_t)4 * K * (size_t)padded_batch(B) * sizeof(double); }
+static size_t obstacles_moving_bytes_for(const tolg_problem* p, int B, int K) { return (size_t)(p->N + 1) * obstacles_bytes_for(p, B, K); }
 extern "C" size_t tolg_obstacles_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K) {
   if (check_problem(prob) || so3_family(prob->kind) || max_batch < 1 || K < 1 || K > TOLG_MAX_OBSTACLES) return 0;
-  return obstacles_bytes_for(max_batch, K);
+  return obstacles_bytes_for(prob, max_batch, K);
+}
+extern "C" size_t tolg_obstacles_moving_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K) {
+  return tolg_obstacles_bytes(prob, max_batch, K) ? obstacles_moving_bytes_for(prob, max_batch, K) : 0;  // (its rules)
 }
 
-// Attach either form (the checks of tolg_set_al_obstacles; `moving`: d_obs holds a field per knot and the packed size is N + 1
-// times the static one).  Each replaces the other: one geometry pointer, one stride.
-static int attach_obstacles(tolg_handle_t h, int B, int K, bool moving, const double* d_obs, const double* d_lambda,
-                            const double* d_imu, void* d_packed, size_t packed_bytes, void* stream) {
-  if (so3_family(h->prob.kind) || B < 1 || B > h->max_batch || K < 1 || K > TOLG_MAX_OBSTACLES) return TOLG_E_ARG;
-  if (!d_lambda || !d_imu || !d_packed || (reinterpret_cast<uintptr_t>(d_packed) & 7) != 0) return TOLG_E_ARG;
-  const size_t knots = moving ? (size_t)(h->prob.N + 1) : 1;
-  if (packed_bytes < knots * obstacles_bytes_for(B, K)) return TOLG_E_ARG;
-  if ((h->refs && B != h->refs_B) || (h->wts && B != h->wts_B)) return TOLG_E_ARG;  // per-trajectory inputs: one batch
-  const int Bp = padded_batch(B);
-  const size_t knot = (size_t)4 * K * Bp, n = knots * knot;
-  const dim3 grid((unsigned)((n + 255) / 256));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  double* w = static_cast<double*>(d_packed);
-  Consts* c = const_cast<Consts*>(h->P.c);
-  if (moving) hipLaunchKernelGGL(k_pack_obstacles_moving, grid, dim3(256), 0, st, B, Bp, K, h->prob.N, d_obs, d_lambda, d_imu, w, c);
-  else hipLaunchKernelGGL(k_pack_obstacles, grid, dim3(256), 0, st, B, Bp, K, d_obs, d_lambda, d_imu, w, c);
+// Both forms (`moving`: d_obs holds a field per knot and the packed size is N + 1 times the static one); d_obs = null detaches
+// through either.  Each replaces the other: one geometry pointer, one stride.
+static int set_obstacles(tolg_handle_t h, int B, int K, bool moving, const double* d_obs, const double* d_lambda,
+                         const double* d_imu, void* d_packed, size_t packed_bytes, void* stream) {
+  if (!h || h->running) return TOLG_E_ARG;
+  Held& r = h->pt[H_OBS];
+  if (!d_obs) { drop(h, r); return 0; }
+  if (so3_family(h->prob.kind) || K < 1 || K > TOLG_MAX_OBSTACLES || !d_lambda || !d_imu) return TOLG_E_ARG;
+  if (!dest_ok(h, B, d_packed, packed_bytes, moving ? obstacles_moving_bytes_for : obstacles_bytes_for, K) || !one_batch(h, B, &r))
+    return TOLG_E_ARG;
+  const int Bp = padded_batch(B), knots = moving ? h->prob.N + 1 : 1;
+  const size_t knot = (size_t)4 * K * Bp;
+  hipLaunchKernelGGL(k_pack_obstacles_moving, dim3((unsigned)((knots * knot + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     B, Bp, K, knots, moving ? knot : 0, d_obs, d_lambda, d_imu, static_cast<double*>(d_packed),
+                     const_cast<Consts*>(h->P.c));
   LAUNCH_CHECK();
-  h->obs = w; h->obs_B = B; h->obs_K = K; h->obs_stride = moving ? knot : 0;
+  h->obs_K = K; h->obs_stride = moving ? knot : 0;
   h->obs_lam = const_cast<double*>(d_lambda); h->obs_imu = const_cast<double*>(d_imu);
-  select_kernels(h);
+  hold(h, r, d_packed, B);
   return 0;
 }
-
 extern "C" int tolg_set_al_obstacles(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
                                      const double* d_imu, void* d_packed, size_t packed_bytes, void* stream) {
-  if (!h || h->running) return TOLG_E_ARG;
-  if (!d_obs) {  // detach
-    h->obs = nullptr; h->obs_B = h->obs_K = 0; h->obs_stride = 0; h->obs_lam = h->obs_imu = nullptr; select_kernels(h);
-    return 0;
-  }
-  return attach_obstacles(h, B, K, false, d_obs, d_lambda, d_imu, d_packed, packed_bytes, stream);
+  return set_obstacles(h, B, K, false, d_obs, d_lambda, d_imu, d_packed, packed_bytes, stream);
 }
-
-extern "C" size_t tolg_obstacles_moving_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K) {
-  const size_t knot = tolg_obstacles_bytes(prob, max_batch, K);  // (its rules; check_problem has seen N >= 1)
-  return knot ? (size_t)(prob->N + 1) * knot : 0;
-}
-
 extern "C" int tolg_set_al_obstacles_moving(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
                                             const double* d_imu, void* d_packed, size_t packed_bytes, void* stream) {
-  if (!d_obs) return tolg_set_al_obstacles(h, B, K, nullptr, d_lambda, d_imu, d_packed, packed_bytes, stream);  // detach
-  if (!h || h->running) return TOLG_E_ARG;
-  return attach_obstacles(h, B, K, true, d_obs, d_lambda, d_imu, d_packed, packed_bytes, stream);
+  return set_obstacles(h, B, K, true, d_obs, d_lambda, d_imu, d_packed, packed_bytes, stream);
+}
+
+// the box of the call's own arguments, no geometry (Bp, K = 0: nothing reads them)
+extern "C" int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, const double* d_lb, const double* d_ub,
+                              double* d_lambda, double* d_imu, double* d_mu, double mu_scale, double mu_max,
+                              double tol_constr, double* d_maxviol, int32_t* d_al_converged, void* stream) {
+  if (!h || B < 1 || !d_us || !d_lb || !d_ub || !d_lambda || !d_imu || !d_mu || !d_maxviol || !d_al_converged)
+    return TOLG_E_ARG;
+  hipLaunchKernelGGL(k_al_update_state, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), B, 0, h->prob.N,
+                     h->prob.m, 0, (const double*)nullptr, d_us, d_lb, d_ub, d_lambda, d_imu, (const double*)nullptr, (size_t)0,
+                     (double*)nullptr, (double*)nullptr, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, d_al_converged);
+  LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu,
                                     double mu_scale, double mu_max, double tol_constr, double* d_maxviol,
                                     int32_t* d_al_converged, void* stream) {
   if (!h || B < 1 || B > h->max_batch || !d_mu || !d_maxviol || !d_al_converged) return TOLG_E_ARG;
-  if (!h->al_lb && !h->obs) return TOLG_E_ARG;     // nothing attached to update
+  const Held& obs = h->pt[H_OBS];
+  if (!h->al_lb && !obs.p) return TOLG_E_ARG;     // nothing attached to update
   if (h->al_lb && !d_us) return TOLG_E_ARG;
-  if (h->obs && (B != h->obs_B || !d_xs_q)) return TOLG_E_ARG;
+  if (obs.p && (B != obs.B || !d_xs_q)) return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_update_state, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), B, padded_batch(B),
                      h->prob.N, h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
-                     const_cast<double*>(h->al_imu), h->obs, h->obs_stride, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr, d_maxviol,
-                     d_al_converged);
+                     const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
+                     d_maxviol, d_al_converged);
   LAUNCH_CHECK();
   return 0;
 }
@@ -5921,8 +5885,8 @@ static bool policy_ok(const tolg_handle_s* h, int B) {
   return h && !h->running && h->pol_B != 0 && B == h->pol_B && batch_fits(h, B);
 }
 // Plants (tolg_set_plant): rows of PLN_F doubles at most (the dense form's), field-major over the B S rows
-static size_t plant_bytes_for(int B, int S) { return (size_t)PLN_F * (size_t)B * (size_t)S * sizeof(double); }
-static PlantArg plant_arg(const tolg_handle_s* h) { return PlantArg{h->plant, h->plant_B * h->plant_S, h->plant_S}; }
+static size_t plant_bytes_for(const tolg_problem*, int B, int S) { return (size_t)PLN_F * (size_t)B * (size_t)S * sizeof(double); }
+static PlantArg plant_arg(const tolg_handle_s* h) { return PlantArg{h->plant.p, h->plant.B * h->plant_S, h->plant_S}; }
 extern "C" int tolg_solve_gains(tolg_handle_t h, int32_t B, double* d_k, double* d_K, void* stream) {
   if (!policy_ok(h, B)) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -5939,11 +5903,11 @@ extern "C" int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const 
   if (!policy_ok(h, B) || S < 1) return TOLG_E_ARG;
   const size_t lanes = (size_t)B * (size_t)S * 4;
   if (lanes > 0x7fffffc0ull) return TOLG_E_ARG;  // one launch, 64-lane groups
-  if (h->plant && (B != h->plant_B || (h->plant_S != 1 && h->plant_S != S))) return TOLG_E_ARG;
+  if (h->plant.p && (B != h->plant.B || (h->plant_S != 1 && h->plant_S != S))) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // J is the tracking cost: no augmented-Lagrangian terms
-  if (h->plant)
+  if (h->plant.p)
     hipLaunchKernelGGL(h->kt.policy_rollout_plant[h->plant_form], dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P,
                        (int)S, h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, plant_arg(h));
   else
@@ -5978,7 +5942,7 @@ extern "C" int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, d
                                 double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm,
                                 double* d_J_cl, void* stream) {
   if (!policy_ok(h, B) || !d_xs_q_warm || !d_xs_xi_warm || !d_us_warm) return TOLG_E_ARG;
-  if (h->plant && (B != h->plant_B || h->plant_S != 1)) return TOLG_E_ARG;
+  if (h->plant.p && (B != h->plant.B || h->plant_S != 1)) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // the stage cost is the tracking cost: no augmented-Lagrangian terms
@@ -5986,7 +5950,7 @@ extern "C" int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, d
                      d_xs_xi_warm, d_us_warm);
   LAUNCH_CHECK();
   const dim3 grid((unsigned)((2 * (size_t)B + 255) / 256));
-  if (h->plant)
+  if (h->plant.p)
     hipLaunchKernelGGL(h->kt.mpc_advance_plant[h->plant_form], grid, dim3(256), 0, st, P, d_w, d_x_next_q, d_x_next_xi,
                        d_u_applied, d_xs_q_warm, d_xs_xi_warm, d_J_cl, plant_arg(h));
   else
@@ -5998,24 +5962,22 @@ extern "C" int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, d
 
 extern "C" size_t tolg_plant_bytes(const tolg_problem* prob, int32_t max_batch, int32_t S) {
   if (check_problem(prob) || max_batch < 1 || S < 1) return 0;
-  return plant_bytes_for(max_batch, S);
+  return plant_bytes_for(prob, max_batch, S);
 }
 extern "C" int tolg_set_plant(tolg_handle_t h, int32_t B, int32_t S, int32_t form, const double* d_J, const double* d_pend,
                               double* d_packed, size_t packed_bytes, void* stream) {
   if (!h || h->running) return TOLG_E_ARG;
-  if (!d_J) {  // back to the model
-    h->plant = nullptr; h->plant_B = h->plant_S = h->plant_form = 0;
-    return 0;
-  }
-  if (B < 1 || B > h->max_batch || S < 1 || (form != TOLG_PLANT_DIAG && form != TOLG_PLANT_DENSE)) return TOLG_E_ARG;
+  if (!d_J) { drop(h, h->plant); return 0; }  // back to the model
+  if (S < 1 || (form != TOLG_PLANT_DIAG && form != TOLG_PLANT_DENSE)) return TOLG_E_ARG;
+  if (!dest_ok(h, B, d_packed, packed_bytes, plant_bytes_for, S)) return TOLG_E_ARG;  // (no one_batch: the policy calls check B)
   if ((size_t)B * (size_t)S * 4 > 0x7fffffc0ull) return TOLG_E_ARG;  // rows are indexed in int, as the rollout's samples
-  if (!d_packed || (reinterpret_cast<uintptr_t>(d_packed) & 7) != 0 || packed_bytes < plant_bytes_for(B, S)) return TOLG_E_ARG;
   if ((h->prob.kind == TOLG_DYN_PENDULUM3D) != (d_pend != nullptr)) return TOLG_E_ARG;
   const int R = B * S;
   hipLaunchKernelGGL(k_pack_plant, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), R, (int)form,
                      h->prob.kind, h->hc.dt, h->hc.grav, d_J, d_pend, d_packed);
   LAUNCH_CHECK();
-  h->plant = d_packed; h->plant_B = B; h->plant_S = S; h->plant_form = form;
+  h->plant_S = S; h->plant_form = form;
+  hold(h, h->plant, d_packed, B);
   return 0;
 }
 

@@ -213,6 +213,11 @@ _POLICY = {"tolg_solve_begin": "clear", "tolg_solve_begin_warm": "clear", "tolg_
            "tolg_solve_batch": "clear hold", "tolg_linearize_backward": "clear hold", "tolg_solve_end": "hold",
            "tolg_set_al_obstacles": "", "tolg_set_al_obstacles_moving": "",
            "tolg_al_update_state": ""}  # (the last three leave it: listed for completeness)
+# A setter's detach call (BatchedTrackingILQR._detach): its arguments behind the handle with the source pointer null, the
+# stream's place included.  tolg_set_al_obstacles detaches the per-knot form too.
+_DETACH = {"tolg_set_refs": (0, None, None, None, 0, None), "tolg_set_weights": (0, None, None, None, None, 0, None),
+           "tolg_set_al_obstacles": (0, 0, None, None, None, None, 0, None), "tolg_set_al": (None, None, None, None),
+           "tolg_set_plant": (0, 0, 0, None, None, None, 0, None)}
 
 
 @dataclass
@@ -243,13 +248,12 @@ class BatchedTrackingILQR:
         self.max_batch = int(max_batch)
         self._policy_B = 0         # batch of the held policy, 0 = none (_POLICY)
         self._refs_set = self._wts_set = False  # the handle points at per-trajectory references / weights
-        self._refs_buf = self._wts_buf = None  # the packed per-trajectory references / weights the handle reads (_packed)
+        # the packed inputs the handle reads (_packed): per-trajectory references, weights and static spheres for max_batch
+        # (x MAX_OBSTACLES), per-knot spheres and plant rows for the largest call so far
+        self._refs_buf = self._wts_buf = self._obs_buf = self._obs_mov_buf = self._plant_buf = None
         self._inflight = (None, None)  # the FitResult of the solve in flight; the inputs the stream may not have read (_hold)
         self._al = None            # the augmented-Lagrangian terms the handle points at (set_al)
         self._obs = None           # ... and the keep-out spheres (set_al_obstacles): (obstacles, lam, imu) on the device
-        self._obs_buf = None       # the packed sphere geometry the handle reads (caller-owned, for max_batch x MAX_OBSTACLES)
-        self._obs_mov_buf = None   # ... and of the per-knot form (for the largest B x K asked for so far)
-        self._plant_buf = None     # the packed plant rows of the last call that stated one (tolg_set_plant; detached behind it)
         p = _capi.Problem()
         p.kind, p.m, p.N, p.dt = _KIND[problem.kind], self.m, self.N, float(problem.dt)
         p.pend_mass, p.pend_length = float(problem.pend_mass), float(problem.pend_length)
@@ -314,15 +318,20 @@ class BatchedTrackingILQR:
         """The one keep-alive: the device inputs of the last call, which the stream may not have read yet."""
         self._inflight = (self._inflight[0], inputs)
 
-    def _packed(self, attr, nbytes_fn):
-        """The caller-owned buffer self.<attr> the handle reads packed per-trajectory references (_refs_buf,
-        tolg_refs_bytes) or weights (_wts_buf, tolg_weights_bytes) from, allocated for max_batch the first time it is needed.
-        Returns (pointer, bytes)."""
-        if getattr(self, attr) is None:
-            setattr(self, attr, torch.empty(int(nbytes_fn(C.byref(self._p), self.max_batch)) // 8, dtype=torch.float64,
-                                            device=self.device))
+    def _packed(self, attr, nbytes_fn, *n, B=None):
+        """The caller-owned buffer self.<attr> a setter packs into and the handle reads, of nbytes_fn(problem, B, *n) bytes (the
+        setter's tolg_*_bytes).  B = None: for max_batch, allocated once (references, weights, static spheres); B given: for
+        this call, kept and grown when a later call needs more (per-knot spheres, plants).  Returns (pointer, bytes)."""
+        need = int(nbytes_fn(C.byref(self._p), self.max_batch if B is None else B, *n)) // 8
         buf = getattr(self, attr)
+        if buf is None or buf.numel() < need:
+            buf = torch.empty(need, dtype=torch.float64, device=self.device)
+            setattr(self, attr, buf)
         return _ptr(buf), C.c_size_t(buf.numel() * 8)
+
+    def _detach(self, fn):
+        """Return the handle to what tolg_create left for setter `fn` (_DETACH)."""
+        self._call(fn, *_DETACH[fn], stream=False)
 
     def _check_refs(self, B, q_ref, xi_ref):
         """Per-trajectory references [B, N+1, 4, 4] / [B, N+1, 6], checked on the host: ValueError before anything reaches
@@ -385,8 +394,8 @@ class BatchedTrackingILQR:
         """Return the handle to the problem's shared reference and weights (tolg_set_refs / tolg_set_weights with NULL).  The
         solve calls do this themselves when they are given no per-trajectory inputs; this is for callers that drove the C
         ABI on the handle directly."""
-        self._call("tolg_set_weights", 0, None, None, None, None, 0, None, stream=False)
-        self._call("tolg_set_refs", 0, None, None, None, 0, None, stream=False)
+        self._detach("tolg_set_weights")
+        self._detach("tolg_set_refs")
         self._wts_set = self._refs_set = False
 
     def _use_pt(self, B, refs, wts):
@@ -395,7 +404,7 @@ class BatchedTrackingILQR:
         an earlier call.  The weights are detached first, so that references for a new B never meet weights set for an
         earlier one."""
         if self._wts_set:
-            self._call("tolg_set_weights", 0, None, None, None, None, 0, None, stream=False)
+            self._detach("tolg_set_weights")
             self._wts_set = False
         self._use_refs(B, refs)
         if wts is not None:
@@ -410,7 +419,7 @@ class BatchedTrackingILQR:
             self._call("tolg_set_refs", B, _ptr(q), _ptr(xi), *self._packed("_refs_buf", self.lib.tolg_refs_bytes))
             self._refs_set = True
         elif self._refs_set:
-            self._call("tolg_set_refs", 0, None, None, None, 0, None, stream=False)
+            self._detach("tolg_set_refs")
             self._refs_set = False
 
     # ------------------------------------------------------------------------------------------
@@ -544,7 +553,7 @@ class BatchedTrackingILQR:
         (ALConstrainedCost + InputConstraint).  lam, imu: device tensors [B, N, 2m]."""
         if lb is None:
             self._al = None
-            self._call("tolg_set_al", None, None, None, None, stream=False)
+            self._detach("tolg_set_al")
         else:
             lb = self._dev(lb, (self.m,)); ub = self._dev(ub, (self.m,))
             self._al = (lb, ub, lam, imu)  # the handle reads them in every solve until they are detached
@@ -583,7 +592,7 @@ class BatchedTrackingILQR:
         until they are detached; None: zeros).  Every batch call must then be for this B."""
         if obstacles is None:
             self._obs = None
-            self._call("tolg_set_al_obstacles", 0, 0, None, None, None, None, 0, stream=True)
+            self._detach("tolg_set_al_obstacles")
             return
         Bl = None if lam is None else int(lam.shape[0])
         B, a = self._check_obstacles(Bl, obstacles)
@@ -599,19 +608,11 @@ class BatchedTrackingILQR:
             _checked(name, t, (B, self.N + 1, K))
         if not 1 <= B <= self.max_batch:
             raise ValueError("obstacles for B = %d trajectories, expected 1..%d" % (B, self.max_batch))
-        if moving:
-            n = int(self.lib.tolg_obstacles_moving_bytes(C.byref(self._p), B, K)) // 8
-            if self._obs_mov_buf is None or self._obs_mov_buf.numel() < n:
-                self._obs_mov_buf = torch.empty(n, **f64)
-            buf, fn = self._obs_mov_buf, "tolg_set_al_obstacles_moving"
-        else:
-            if self._obs_buf is None:
-                n = self.lib.tolg_obstacles_bytes(C.byref(self._p), self.max_batch, _capi.MAX_OBSTACLES)
-                self._obs_buf = torch.empty(int(n) // 8, **f64)
-            buf, fn = self._obs_buf, "tolg_set_al_obstacles"
+        dest = (self._packed("_obs_mov_buf", self.lib.tolg_obstacles_moving_bytes, K, B=B) if moving else
+                self._packed("_obs_buf", self.lib.tolg_obstacles_bytes, _capi.MAX_OBSTACLES))
         d = self._dev(a, a.shape)
         self._obs = (d, lam, imu)  # the handle reads the multipliers in every solve until they are detached
-        self._call(fn, B, K, _ptr(d), _ptr(lam), _ptr(imu), _ptr(buf), C.c_size_t(buf.numel() * 8))
+        self._call("tolg_set_al_obstacles" + ("_moving" if moving else ""), B, K, _ptr(d), _ptr(lam), _ptr(imu), *dest)
 
     def al_fit_batch(self, x0_q, x0_xi, us_init, lb=None, ub=None, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
                      tol_d_norm=1e-6, tol_constr=1e-2, mu0=1e-2, mu_scale=10.0, mu_max=1e8, line_search=False,
@@ -881,17 +882,14 @@ class BatchedTrackingILQR:
         return np.ascontiguousarray(J.reshape(B, Sp, 36)), pend, form, Sp
 
     def _set_plant(self, B, plant):
-        """Point the handle at the checked plant (tolg_set_plant; packed into a buffer of its own, kept until the next one)."""
+        """Point the handle at the checked plant (tolg_set_plant; packed into _plant_buf)."""
         J, pend, form, Sp = plant
         d_J, d_pend = self._dev(J, J.shape), None if pend is None else self._dev(pend, pend.shape)
-        self._plant_buf = torch.empty(int(self.lib.tolg_plant_bytes(C.byref(self._p), B, Sp)) // 8, dtype=torch.float64,
-                                      device=self.device)
-        self._call("tolg_set_plant", B, Sp, form, _ptr(d_J), _ptr(d_pend), _ptr(self._plant_buf),
-                   C.c_size_t(self._plant_buf.numel() * 8))
+        self._call("tolg_set_plant", B, Sp, form, _ptr(d_J), _ptr(d_pend), *self._packed("_plant_buf", self.lib.tolg_plant_bytes, Sp, B=B))
         return d_J, d_pend
 
     def _clear_plant(self):
-        self._call("tolg_set_plant", 0, 0, 0, None, None, None, 0, None, stream=False)
+        self._detach("tolg_set_plant")
 
     def _use_plant(self, B, plant):
         """Point the handle at this call's plant, or detach it (plant None: the model steps): every call states its own.
