@@ -5,7 +5,7 @@
 // STATUS: the second measured negative result on "two waves per SIMD" (all 104 GPU parity tests pass with it;
 // profiles/r03_k5_*).  It does what it was built for -- no duplicated instructions (560 per knot and group against
 // k_backward3's 571), wave B's critical path 3 470 cycles per knot against 4 180, both measured at the same 1.97 GHz
-// in one run (tools/k5_stamps.py, tools/k2_stamps.py) -- and the LAUNCH is slower: 0.455 ms against 0.343 under
+// in one run (tools/attic/k5_stamps.py, tools/k2_stamps.py) -- and the LAUNCH is slower: 0.455 ms against 0.343 under
 // rocprofv3, 0.40-0.42 against 0.355 in the bench (two-wave workgroups, roles by wave index).  The two waves of a pair
 // are unequal (A: 180 vector instructions per knot, B: 350 on the critical path), so which waves share a SIMD matters;
 // the form below makes that exact -- four-wave workgroups, roles from the SIMD a wave finds itself on, one A and one B

@@ -461,10 +461,7 @@ __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
       for (int u = 0; u < M; u += 2) bst2_gk(rGs, vG, GOFF(u, 0, M), Kst[u], Kst[u + 1]);
     }
   };
-#ifdef TOLG_STAMPS
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t = __builtin_amdgcn_s_memtime();
-  const unsigned long long st_rt0 = __builtin_amdgcn_s_memrealtime(), st_ct0 = st_t;
-#endif
+  Stamps<8> ST;
 
   bool failed = false;  // (FAST) a knot the fast path could not settle: wave-uniform
   // ---- one knot.  SLOT (compile time): the LDS slot that holds knot i; the loop below is unrolled by two.
@@ -512,7 +509,7 @@ __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
     const f64x2* kc = reinterpret_cast<const f64x2*>(lds + oKC);
     const f64x2 c0 = kc[0], c1 = kc[1], c2 = kc[2];  // aA0 bA0 | aB0 bB0 | bA1 bB1
     const f64x2 mk0 = kc[3], mk1 = kc[4], mk2 = kc[5];  // (row r == kA, row r == kB), r = 0..2
-    STAMP(0)
+    TOLG_STAMP(ST, 0)
     // ---- Z = V [F_x | d]  (+ V_x in the vector column -> w = V_x + V_xx d; the adjoint passes through)
     double Z[12];
 #pragma unroll
@@ -526,25 +523,19 @@ __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
       A[8] = fma(mk2.y, eB0, fma(mk2.x, eA0, A[8])); A[11] = fma(mk2.y, eB1, fma(mk2.x, eA1, A[11]));
     }
     rank1_bk3_6_nn(Z, V, A[6], A[7], A[8]); rank1_bk3_9_nn(Z, V, A[9], A[10], A[11]);
-    STAMP(1)
+    TOLG_STAMP(ST, 1)
     // the slot is consumed (every ds_read above has returned: Z needed them): last knot's gains go out, then the
     // records of knot i - 2 come into this slot.  Stores first: the wait at the top of a step covers both, in order.
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef TOLG_STAMPS2  // finer split of this phase: (1) ends behind the wait, (2) is the gain stores alone, the DMA issue counts into (3)
-    STAMP(1)
-#endif
+    TOLG_STAMP_FINE(ST, 1)  // finer split of this phase: (1) ends behind the wait, (2) is the gain stores alone, the DMA issue counts into (3)
     gk_run -= gStride;
     if (i < N - 1) store_gains(gk_run);
-#ifdef TOLG_STAMPS2
-    STAMP(2)
-#endif
+    TOLG_STAMP_FINE(ST, 2)
     rec_run -= recStrideB;
     if (i >= 2) dma_from(rec_run, SLOT);
     __builtin_amdgcn_sched_barrier(0);
-#ifndef TOLG_STAMPS2
-    STAMP(2)
-#endif
+    TOLG_STAMP_COARSE(ST, 2)
     // ---- regularised G = rows S of (V + mu I)[F_x | d] (+ D^-1 l_u in the vector columns), Mt; PD test
     // (traopt_controller.py:2964-2995, :3052-3060)
     bool use_lu = false;
@@ -654,7 +645,7 @@ __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
     // traopt_controller.py:2998-3004 for the exact gains), back substitution in place, gains [K | k] = D^-1 nx
     auto finish = [&](double (&Y)[M], const double (&Uf)[M], double (&nri)[M]) {
       grad_term(Y);
-      STAMP(4)
+      TOLG_STAMP(ST, 4)
       if (!ms) {  // the single-shooting adjoint lane takes no gain correction
 #pragma unroll
         for (int u = 0; u < M; u++) nri[u] = (j == 13) ? 0.0 : nri[u];
@@ -662,7 +653,7 @@ __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
       double zn[M], nx[M];
       ldl3_forward<M>(Uf, nri, Y, zn);
       symmetrise();
-      STAMP(5)
+      TOLG_STAMP(ST, 5)
       if constexpr (M == 6) rank1_bi_x6_nn(Qh, Y, zn);
       else rank1_bi_x4_nn(Qh, Y, zn);
       ldl3_backward_nx<M>(Uf, nri, Y, zn, nx);
@@ -688,7 +679,7 @@ __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
       }
       ldl3_factor<M>(Uf, nri, dv, wm);
       const bool pd = ldl3_all_positive<M>(dv);
-      STAMP(3)
+      TOLG_STAMP(ST, 3)
       if (!__any(act && !pd)) {
         if (act) { delta = fmin(1.0, delta) * 0.5; mu = 0.0; }  // schedule(true) with mu == 0 (:2986-2991)
         finish(Y, Uf, nri);
@@ -759,7 +750,7 @@ __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
     }
 #pragma unroll
     for (int r = 0; r < 12; r++) V[r] = Qh[r];
-    STAMP(6)
+    TOLG_STAMP(ST, 6)
   };
 
   // prologue: knots N-1 and N-2 into the two slots
@@ -791,14 +782,8 @@ __global__ __launch_bounds__(64) void k_backward3(Params P, int it, int flags) {
     if (lane == 0) { const int hn = (it == 0) ? 0 : P.k2_hint[blockIdx.x]; P.k2_hint[blockIdx.x] = anyf ? 8 : (hn > 0 ? hn - 1 : 0); }
   }
   store_gains(P.GK);
-#ifdef TOLG_STAMPS
-  STAMP(7)
-  if (blockIdx.x == 7 && lane == 0 && P.mu_hist) {
-    for (int k = 0; k < 8; k++) P.mu_hist[(size_t)28 * P.max_iter + k] = (double)st_acc[k];
-    P.mu_hist[(size_t)29 * P.max_iter + 0] = (double)(__builtin_amdgcn_s_memrealtime() - st_rt0);  // 100 MHz ticks
-    P.mu_hist[(size_t)29 * P.max_iter + 1] = (double)(__builtin_amdgcn_s_memtime() - st_ct0);
-  }
-#endif
+  TOLG_STAMP(ST, 7)
+  stamps_flush(P, ST, blockIdx.x == ST_BLOCK_K2 && lane == 0, P.mu_hist, ST_ROW_K2, ST_ROW_K2_CLOCK);
   // ---- epilogue: gradient norm, convergence test (traopt_controller.py:2527-2532, :1937-1942)
   double grad = (ms ? bcast<12>(gsum) : bcast<13>(gsum)) / (double)N;
   if (act && j == 0) {

@@ -172,6 +172,8 @@ struct Params {
 };
 enum { NSLOT = 15, NALPHA_MS = 20, NALPHA_SS = 13 };  // slots: the widest stage (the merit search's last: step sizes 5 .. 19; the first alpha goes straight to the candidate arrays)
 
+#include "tolg_stamps.h"
+
 // every array is knot-major [knot][field][Bp]: one knot of one field is a contiguous run over the batch
 #define SIDX(c, i, b) ((((size_t)(i)) * 13 + (size_t)(c)) * (size_t)P.Bp + (size_t)(b))
 #define UIDX(c, i, b) ((((size_t)(i)) * (size_t)P.m + (size_t)(c)) * (size_t)P.Bp + (size_t)(b))
@@ -1789,12 +1791,7 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
     }
   }
   double gsum = 0;
-#ifdef TOLG_STAMPS
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t = __builtin_amdgcn_s_memtime();
-#define STAMP(k) { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_t; st_t = t_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define STAMP(k)
-#endif
+  Stamps<8> ST;
 
   // Raw loads of one knot (column j of [F_x | d], of [l_xx | l_x], the controls), issued one knot
   // ahead of their use.  Nothing here may consume a loaded value: that would put the wait for the
@@ -1854,7 +1851,7 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
     for (int r = 0; r < 6; r++) { Lc[r] = in.lt[r]; Lc[6 + r] = in.lb[r]; }  // + 2 W2: added to Qh below
 #pragma unroll
     for (int a = 0; a < M; a++) lu[a] = in.lu[a];  // l_u = 2 R u rides in the vector columns (zero elsewhere)
-    STAMP(0)
+    TOLG_STAMP(ST, 0)
     // ---- Z = V [F_x | d]  (+ V_x in the vector column -> w = V_x + V_xx d; adjoint passes through)
     double Z[12];
 #pragma unroll
@@ -1863,7 +1860,7 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
     // broadcast side: only lanes 0..11 are ever sources of rank1_bk.
     rank1_bk3_0(Z, V, A[0], A[1], A[2]); rank1_bk3_3(Z, V, A[3], A[4], A[5]);
     rank1_bk3_6(Z, V, A[6], A[7], A[8]); rank1_bk3_9(Z, V, A[9], A[10], A[11]);
-    STAMP(1)
+    TOLG_STAMP(ST, 1)
     // ---- Qh = [l_xx | l_x] + F_x^T Z
     double Qh[12];
 #pragma unroll
@@ -1883,7 +1880,7 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
     // regularisation / Cholesky / gain / V-update half of the step runs.  One buffer instead of a
     // ping-pong pair keeps the loads in VGPRs (with two, the allocator parked them in AGPRs and had to
     // wait for them right away to copy them back).
-    STAMP(2)
+    TOLG_STAMP(ST, 2)
     // Constants of the second half, requested BEFORE the prefetch so that their LDS / scalar-cache
     // latency passes while the 31 buffer loads issue (read where they are used, each cost an exposed
     // lgkmcnt(0) wait: ~10 per knot).
@@ -1918,7 +1915,7 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int r = 0; r < 6; r++) Qh[6 + r] += mW2 * kBW[r];
-    STAMP(3)
+    TOLG_STAMP(ST, 3)
     // ---- regularised Q_ux | Q_u, Q_uu; PD test; gains   (traopt_controller.py:2964-2995, :3052-3060)
     double Quh[M], Kh[M], Uf[M], rinv[M];
     bool use_lu = false;
@@ -2008,7 +2005,7 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
         }
       }
     }
-    STAMP(4)
+    TOLG_STAMP(ST, 4)
     // gradient term: ||Q_u|| in the MS vector lane, ||l_u + F_u^T p|| in the SS adjoint lane
     {
       double s = 0;
@@ -2041,7 +2038,7 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
     for (int u = 0; u < M; u++) Kh[u] = kneg * Kh[u];
 #pragma unroll
     for (int u = 0; u < M; u++) Kst[u] = Kh[u];
-    STAMP(5)
+    TOLG_STAMP(ST, 5)
     // ---- V <- Qh + Q_ux^T [K | k]   (== Eq. 11b/11c of traopt_controller.py:2998-3003 for the
     // exact gains), then symmetrise the matrix columns through LDS (traopt_controller.py:3004)
     double Vn[12];
@@ -2060,7 +2057,7 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int r = 0; r < 12; r++) V[r] = hsym * (Vn[r] + trd[r]);
-    STAMP(6)
+    TOLG_STAMP(ST, 6)
   };
 
   BwdIn in;
@@ -2076,10 +2073,8 @@ __global__ __launch_bounds__(64) void k_backward(Params P, int it, int flags) {
     if (lane == 0) { const int hn = (it == 0) ? 0 : P.k2_hint[blockIdx.x]; P.k2_hint[blockIdx.x] = failed ? 8 : (hn > 0 ? hn - 1 : 0); }
   }
   store_gains(0);
-#ifdef TOLG_STAMPS
-  STAMP(7)
-  if (blockIdx.x == 7 && lane == 0 && P.mu_hist) { for (int k = 0; k < 8; k++) P.mu_hist[(size_t)28 * P.max_iter + k] = (double)st_acc[k]; }
-#endif
+  TOLG_STAMP(ST, 7)
+  stamps_flush(P, ST, blockIdx.x == ST_BLOCK_K2 && lane == 0, P.mu_hist, ST_ROW_K2);
   // ---- epilogue: gradient norm, convergence test (traopt_controller.py:2527-2532, :1937-1942)
   double grad = (ms ? bcast<12>(gsum) : bcast<13>(gsum)) / (double)N;
   if (act && j == 0) {
@@ -2211,16 +2206,38 @@ TOLG_DEV void roll_load(const Params& P, int i, int b, int q, unsigned vb, unsig
   for (int a = 0; a < M; a++) R.u[a] = bld(rU, vb, a * sB);
 }
 
-#ifdef TOLG_STAMPS
-struct RStamps { unsigned long long acc[8], t; };
-#define RSTAMP(k) { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); ST.acc[k] += t_ - ST.t; ST.t = t_; __builtin_amdgcn_sched_barrier(0); }
-#define RST_PARAM , RStamps& ST
-#define RST_ARG , ST
-#else
-#define RSTAMP(k)
-#define RST_PARAM
-#define RST_ARG
-#endif
+// ---- pieces of a chain step that more than one rollout kernel runs, written once where that leaves every caller's
+// code instruction for instruction what the written-out form gives (tools/symbol_diff.py: `identical`; a kernel that only
+// kept its instructions up to register numbers and order changed the last bits of a solve: profiles/rollout_step_ab.txt).
+// roll_deviation: roll_step, roll_step_twist, k_rollout_ls2's twist wave, k_rollout_eval_t.  roll_control: roll_step_twist
+// and k_rollout_ls2's twist wave -- roll_step keeps a copy of its own, which must match it expression for expression.
+// state deviation [Log(q^-1 q_new); xi_new - xi]   (traopt_controller.py:2680-2687), from the two halves (ew, ev) of the Log.
+// (The Log itself stays with the caller: a step runs it under its own series gate, the thread form in closed form -- and a
+// helper that also took the gate moved the fused launch's code.)
+TOLG_DEV void roll_deviation(const V3& ew, const V3& ev, const State& So, const State& Sn, double (&e)[12]) {
+  e[0] = ew.x; e[1] = ew.y; e[2] = ew.z; e[3] = ev.x; e[4] = ev.y; e[5] = ev.z;
+  e[6] = Sn.w.x - So.w.x; e[7] = Sn.w.y - So.w.y; e[8] = Sn.w.z - So.w.z;
+  e[9] = Sn.v.x - So.v.x; e[10] = Sn.v.y - So.v.y; e[11] = Sn.v.z - So.v.z;
+}
+// du = alpha k + K dx: this lane's two rows, then quad broadcast (identical bits in all four lanes); u^ = u + du.
+// UNIT: alpha = 1 at compile time, no product, called without alpha (the fused rollout's step); otherwise the product with
+// the run-time alpha stays, whatever its value.
+template <int M, bool UNIT>
+TOLG_DEV void roll_control(const RollIn<M>& R, const double (&e)[12], double (&un)[M], double (&du)[M], double alpha = 1.0) {
+  double mine[2];
+#pragma unroll
+  for (int sidx = 0; sidx < 2; sidx++) {
+    double sacc = UNIT ? R.G[sidx][12] : alpha * R.G[sidx][12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) sacc += R.G[sidx][k] * e[k];
+    mine[sidx] = sacc;
+  }
+  du[0] = quad_bcast<0>(mine[0]); du[1] = quad_bcast<0>(mine[1]);
+  du[2] = quad_bcast<1>(mine[0]); du[3] = quad_bcast<1>(mine[1]);
+  if constexpr (M == 6) { du[4] = quad_bcast<2>(mine[0]); du[5] = quad_bcast<2>(mine[1]); }
+#pragma unroll
+  for (int a = 0; a < M; a++) un[a] = R.u[a] + du[a];
+}
 // STORE: the writer lane stores u^_i and x^_{i+1} to the candidate arrays; otherwise the caller takes them
 // (un_out and the return value) -- the fused rollout hands them to its linearisation wavefronts through LDS.
 // load_in(R): requests this step's gains and controls (from HBM, or from the LDS input ring of the fused kernel).
@@ -2233,14 +2250,13 @@ struct RollPre { bool have_d = false, have_x = false; double d[12]; State Sx; };
 template <int M, bool LINEAR, bool ALPHA1, int PK, bool STORE, class CT, class LoadFn>
 TOLG_DEV State roll_step(const Params& P, const CT& C, const DynK& DK, int i, int b, int q, bool writer, unsigned vb,
                          unsigned sB, double alpha, const State& So, const State& Sn, double (&un_out)[M],
-                         LoadFn load_in, RollProbe<M>* probe RST_PARAM, const RollPre& pre = RollPre()) {
+                         LoadFn load_in, RollProbe<M>* probe, Stamps<8>& ST, const RollPre& pre = RollPre()) {
   const size_t stStride = (size_t)13 * P.Bp, recStride = (size_t)P.recF * P.Bp, uStride = (size_t)M * P.Bp;
-  RSTAMP(0)
+  TOLG_STAMP(ST, 0)
   RollIn<M> R;
   load_in(R);  // in flight while Log runs
   __builtin_amdgcn_sched_barrier(0);
-  RSTAMP(1)
-  // state deviation [Log(q^-1 q_new); xi_new - xi]   (traopt_controller.py:2680-2687)
+  TOLG_STAMP(ST, 1)
   // one gate for the two series evaluations of the step (Log here, Exp in the pose half of the dynamics)
   V3 ew, ev;
   const Pose Dx = se3_compose(se3_inverse(So.X), Sn.X);
@@ -2248,14 +2264,15 @@ TOLG_DEV State roll_step(const Params& P, const CT& C, const DynK& DK, int i, in
   const double yl = quat_vec2(Dx.q), th2e = dot(wdt, wdt);
   const SeriesGate sg = series_gate(log_small(yl) && exp_small(th2e), log_dom(yl) && exp_dom(th2e));
   se3_log_fast(Dx, ew, ev, sg);
-  double e[12] = {ew.x, ew.y, ew.z, ev.x, ev.y, ev.z, Sn.w.x - So.w.x, Sn.w.y - So.w.y, Sn.w.z - So.w.z,
-                  Sn.v.x - So.v.x, Sn.v.y - So.v.y, Sn.v.z - So.v.z};
-  // du = alpha k + K dx: this lane's two rows, then quad broadcast (identical bits in all four lanes)
+  double e[12];
+  roll_deviation(ew, ev, So, Sn, e);
   // the pose half of f(x^, u^) does not depend on u^: it runs here, ahead of the gain product, and gives
   // the gain loads issued at the top of the step another ~700 cycles to land
   State Fn;
   if (!LINEAR && DK.diag) Fn.X = dyn_pose_k(DK, Sn, sg);
-  RSTAMP(2)
+  TOLG_STAMP(ST, 2)
+  // du = alpha k + K dx, u^ = u + du: roll_control<M, false> written out, the same expressions in the same order (as a call
+  // it left K3 and the one-wave stages their instructions up to register numbers and order, and changed a solve's last bits)
   double mine[2];
 #pragma unroll
   for (int sidx = 0; sidx < 2; sidx++) {
@@ -2276,7 +2293,7 @@ TOLG_DEV State roll_step(const Params& P, const CT& C, const DynK& DK, int i, in
 #pragma unroll
     for (int a = 0; a < M; a++) probe->du[a] = du[a];
   }
-  RSTAMP(3)
+  TOLG_STAMP(ST, 3)
   State Nx;
   if constexpr (!LINEAR) {
     if (DK.diag) dyn_twist_k<M, CT, PK>(DK, C, Sn, un, Fn);
@@ -2285,7 +2302,7 @@ TOLG_DEV State roll_step(const Params& P, const CT& C, const DynK& DK, int i, in
     if constexpr (ALPHA1) {
       // alpha = 1 (and single shooting): the factors of :2713-2716 are the identity and zero up to rounding
       // (see the note at the record layout), the step is x^_{i+1} = f(x^_i, u^_i)
-      RSTAMP(4)
+      TOLG_STAMP(ST, 4)
       Nx = Fn;
     } else {
       // line-search step (traopt_controller.py:2713-2716): x^_{i+1} = x_{i+1} Exp(alpha d_q) f_q(x_i,u_i)^-1 f_q(x^_i,u^_i),
@@ -2310,7 +2327,7 @@ TOLG_DEV State roll_step(const Params& P, const CT& C, const DynK& DK, int i, in
                                   se3_inverse(Sx.X));
       const V3 cw = am1 * v3(dms[6], dms[7], dms[8]);
       const V3 cv = am1 * v3(dms[9], dms[10], dms[11]);
-      RSTAMP(4)
+      TOLG_STAMP(ST, 4)
       Nx.X = se3_project(se3_compose(Mx, Fn.X));
       Nx.w = cw + Fn.w;
       Nx.v = cv + Fn.v;
@@ -2327,7 +2344,7 @@ TOLG_DEV State roll_step(const Params& P, const CT& C, const DynK& DK, int i, in
     Nx.w = Sx.w + v3(lin[6] + d[6], lin[7] + d[7], lin[8] + d[8]);
     Nx.v = Sx.v + v3(lin[9] + d[9], lin[10] + d[10], lin[11] + d[11]);
   }
-  RSTAMP(5)
+  TOLG_STAMP(ST, 5)
   if constexpr (STORE) {
     if (writer) {
       __amdgpu_buffer_rsrc_t rCU = mkbuf(P.cand_u + uStride * i, M * sB);
@@ -2338,51 +2355,39 @@ TOLG_DEV State roll_step(const Params& P, const CT& C, const DynK& DK, int i, in
   }
 #pragma unroll
   for (int a = 0; a < M; a++) un_out[a] = un[a];
-  RSTAMP(6)
+  TOLG_STAMP(ST, 6)
   return Nx;
 }
 
 // The fused rollout's step (accept-always, alpha = 1): the twist half of roll_step.  The pose half of the dynamics,
 // X_{i+1} = project(X_i Exp(xi_i dt)), depends on the state alone; a second wavefront runs that chain one step ahead
 // (k_rollout_lin) and get_pose() hands over X_i.  Sn holds xi_i on entry (its pose is filled in here) and xi_{i+1}
-// on return.  Same expressions in the same order as roll_step.
+// on return.  Same expressions in the same order as roll_step: the deviation and the control are the shared helpers
+// (roll_step's written-out control matches roll_control), the Log runs under a gate of its own.
 template <int M, class CT, class LoadFn, class PoseFn>
 TOLG_DEV void roll_step_twist(const CT& C, const DynK& DK, const State& So, State& Sn, double (&un_out)[M],
-                              LoadFn load_in, PoseFn get_pose RST_PARAM) {
-  RSTAMP(0)
+                              LoadFn load_in, PoseFn get_pose, Stamps<8>& ST) {
+  TOLG_STAMP(ST, 0)
   RollIn<M> R;
   load_in(R);  // in flight while Log runs
   __builtin_amdgcn_sched_barrier(0);
-  RSTAMP(1)
+  TOLG_STAMP(ST, 1)
   Sn.X = get_pose();
-  RSTAMP(5)
-  // state deviation [Log(q^-1 q_new); xi_new - xi]   (traopt_controller.py:2680-2687)
+  TOLG_STAMP(ST, 5)
   V3 ew, ev;
   const Pose Dx = se3_compose(se3_inverse(So.X), Sn.X);
   const double yl = quat_vec2(Dx.q);
   se3_log_fast(Dx, ew, ev, series_gate(log_small(yl), log_dom(yl)));
-  const double e[12] = {ew.x, ew.y, ew.z, ev.x, ev.y, ev.z, Sn.w.x - So.w.x, Sn.w.y - So.w.y, Sn.w.z - So.w.z,
-                        Sn.v.x - So.v.x, Sn.v.y - So.v.y, Sn.v.z - So.v.z};
-  RSTAMP(2)
-  double mine[2];
-#pragma unroll
-  for (int sidx = 0; sidx < 2; sidx++) {
-    double sacc = R.G[sidx][12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) sacc += R.G[sidx][k] * e[k];
-    mine[sidx] = sacc;
-  }
+  double e[12];
+  roll_deviation(ew, ev, So, Sn, e);
+  TOLG_STAMP(ST, 2)
   double un[M], du[M];
-  du[0] = quad_bcast<0>(mine[0]); du[1] = quad_bcast<0>(mine[1]);
-  du[2] = quad_bcast<1>(mine[0]); du[3] = quad_bcast<1>(mine[1]);
-  if constexpr (M == 6) { du[4] = quad_bcast<2>(mine[0]); du[5] = quad_bcast<2>(mine[1]); }
-#pragma unroll
-  for (int a = 0; a < M; a++) un[a] = R.u[a] + du[a];
-  RSTAMP(3)
+  roll_control<M, true>(R, e, un, du);
+  TOLG_STAMP(ST, 3)
   State Fn;
   if (DK.diag) dyn_twist_k<M, CT, 0>(DK, C, Sn, un, Fn);
   else Fn = dyn_f<M, CT, 0>(C, Sn, un);
-  RSTAMP(4)
+  TOLG_STAMP(ST, 4)
   Sn.w = Fn.w;
   Sn.v = Fn.v;
 #pragma unroll
@@ -2413,27 +2418,21 @@ __global__ __launch_bounds__(64) void k_rollout(Params P, double alpha, int i0, 
     Sn = load_state_b(mkbuf(P.cand + (size_t)13 * P.Bp * i0, 13 * sB), vb, sB);
   }
   const DynK DK = dynk_load(*P.c);  // generic pointer: see the note at DConsts
-#ifdef TOLG_STAMPS
-  RStamps ST;
-  for (int k = 0; k < 8; k++) ST.acc[k] = 0;
-  ST.t = __builtin_amdgcn_s_memtime();
-#endif
+  Stamps<8> ST;
   State Sa = roll_load_state(P, i0, vb, sB), Sb = Sa;
   double un_[M];
   for (int i = i0; i < i1; i += 2) {
     if (i + 1 < i1) Sb = roll_load_state(P, i + 1, vb, sB);
     __builtin_amdgcn_sched_barrier(0);
     Sn = roll_step<M, LINEAR, ALPHA1, PK, true>(P, C, DK, i, b, q, writer, vb, sB, alpha, Sa, Sn, un_,
-                                                [&](RollIn<M>& R) { roll_load<M, ALPHA1>(P, i, b, q, vb, sB, R); }, nullptr RST_ARG);
+                                                [&](RollIn<M>& R) { roll_load<M, ALPHA1>(P, i, b, q, vb, sB, R); }, nullptr, ST);
     if (i + 1 >= i1) break;
     if (i + 2 < i1) Sa = roll_load_state(P, i + 2, vb, sB);
     __builtin_amdgcn_sched_barrier(0);
     Sn = roll_step<M, LINEAR, ALPHA1, PK, true>(P, C, DK, i + 1, b, q, writer, vb, sB, alpha, Sb, Sn, un_,
-                                                [&](RollIn<M>& R) { roll_load<M, ALPHA1>(P, i + 1, b, q, vb, sB, R); }, nullptr RST_ARG);
+                                                [&](RollIn<M>& R) { roll_load<M, ALPHA1>(P, i + 1, b, q, vb, sB, R); }, nullptr, ST);
   }
-#ifdef TOLG_STAMPS
-  if (blockIdx.x == 5 && threadIdx.x == 0 && P.alpha_hist) { for (int k = 0; k < 8; k++) P.alpha_hist[(size_t)80 * P.max_iter + k] = (double)ST.acc[k]; }
-#endif
+  stamps_flush(P, ST, blockIdx.x == ST_BLOCK_ROLL && threadIdx.x == 0, P.alpha_hist, ST_ROW_ROLL);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2638,11 +2637,7 @@ __global__ __launch_bounds__(256) void k_rollout_lin(Params P, int it) {
     const DynK DK = dynk_load(*P.c);  // generic pointer: see the note at DConsts
     State Sa = Sn, Sb = Sn;
     double un[M];
-#ifdef TOLG_STAMPS
-    RStamps ST;
-    for (int k = 0; k < 8; k++) ST.acc[k] = 0;
-    ST.t = __builtin_amdgcn_s_memtime();
-#endif
+    Stamps<8> ST;
     // The pose of x^_i comes from the pose wavefront (sync[7] = poses published).  It is read speculatively
     // right after this wave's own publish of step i - 1 -- counter first, then the data: LDS operations execute in
     // order, so a counter value >= i vouches for the data read behind it -- and only re-read after a poll if the
@@ -2702,11 +2697,11 @@ __global__ __launch_bounds__(256) void k_rollout_lin(Params P, int it) {
                              Xspec = rl_get_pose(ring[i % RL_RING], tt);
                            }
                            return Xspec;
-                         } RST_ARG);
+                         }, ST);
       if (!got) return false;
       if (i + 1 < N && !ahead(i + 1, So)) return false;
       finish_step(i);
-      RSTAMP(7)
+      TOLG_STAMP(ST, 7)
       return true;
     };
     ok = ahead(0, Sb);
@@ -2715,9 +2710,7 @@ __global__ __launch_bounds__(256) void k_rollout_lin(Params P, int it) {
       if (i + 1 >= N) break;
       if (!(ok = step(i + 1, Sb))) break;
     }
-#ifdef TOLG_STAMPS
-    if (blockIdx.x == 5 && threadIdx.x == 0 && P.alpha_hist) { for (int k = 0; k < 8; k++) P.alpha_hist[(size_t)80 * P.max_iter + k] = (double)ST.acc[k]; }
-#endif
+    stamps_flush(P, ST, blockIdx.x == ST_BLOCK_ROLL && threadIdx.x == 0, P.alpha_hist, ST_ROW_ROLL);
     if (!ok && writer && b0 + tt < P.Bp) P.status[b0 + tt] = TOLG_ST_INTERNAL;
     return;
   }
@@ -2781,35 +2774,27 @@ __global__ __launch_bounds__(256) void k_rollout_lin(Params P, int it) {
     const bool writer = (lane & 3) == 0;
     const DynK DK = dynk_load(*P.c);  // generic pointer: see the note at DConsts
     State S = rl_in_state<M>(inring[0], tt);  // x^_0 = x_0
-#ifdef TOLG_STAMPS
-    unsigned long long pw[3] = {0, 0, 0}, pw_t = __builtin_amdgcn_s_memtime();
-#define PSTAMP(k) { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); pw[k] += t_ - pw_t; pw_t = t_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define PSTAMP(k)
-#endif
+    Stamps<3> PW;  // waiting for the twist | input DMA issue + publish | pose chain + publish
     for (int i = 0; i < N; i++) {
       if (i > 0) {
         bool seen = false;
         for (int n = 0; n < RL_POLLS && !(seen = __builtin_amdgcn_readfirstlane(vs[0]) >= i); n++) __builtin_amdgcn_s_sleep(1);
         if (!seen) return;  // wave 0 reports the failure (its own poll of sync[7] runs out)
         asm volatile("" ::: "memory");
-        PSTAMP(0)
+        TOLG_STAMP(PW, 0)
         rl_get_twist(ring[i % RL_RING], tt, S.w, S.v);
         if (issued < N) issue(issued++);  // knot i + 4, into the slot step i - 1 has finished with
         publish_loaded(i + 3 < N ? i + 3 : N);
-        PSTAMP(1)
+        TOLG_STAMP(PW, 1)
       }
       S.X = dyn_pose_k(DK, S);
       if (writer) rl_put_pose(ring[(i + 1) % RL_RING], tt, S.X);
       asm volatile("" ::: "memory");
       __builtin_amdgcn_wave_barrier();
       if (lane == 0) vs[7] = i + 1;
-      PSTAMP(2)
+      TOLG_STAMP(PW, 2)
     }
-#ifdef TOLG_STAMPS
-    if (blockIdx.x == 5 && lane == 0 && P.alpha_hist)
-      for (int k = 0; k < 3; k++) P.alpha_hist[(size_t)83 * P.max_iter + k] = (double)pw[k];
-#endif
+    stamps_flush(P, PW, blockIdx.x == ST_BLOCK_ROLL && lane == 0, P.alpha_hist, ST_ROW_POSE);
     return;
   }
   // ---------------- linearisation helpers: pass g covers knots 4g .. 4g+3 (lane / 16) of the 16 trajectories (lane % 16)
@@ -2818,22 +2803,16 @@ __global__ __launch_bounds__(256) void k_rollout_lin(Params P, int it) {
   const int ngroups = (N + 1 + 3) / 4;
   int done = 0;
   double jpart = 0.0;  // stage costs of this lane's knots (kk, kk + 8, ... of helper 0; kk + 4, kk + 12, ... of helper 1)
-#ifdef TOLG_STAMPS
-  unsigned long long hs_wait = 0, hs_work = 0, hs_t = __builtin_amdgcn_s_memtime();
-#endif
+  Stamps<2> HS;  // waiting for the rollout | working (the passes of helper h: every RL_NH-th of the ngroups)
   for (int g = h; g < ngroups; g += RL_NH) {
     const int need = (4 * g + 4 < N) ? 4 * g + 4 : N;  // the last state this pass reads
-#ifdef TOLG_STAMPS
-    { unsigned long long t_ = __builtin_amdgcn_s_memtime(); hs_work += t_ - hs_t; hs_t = t_; }
-#endif
+    TOLG_STAMP(HS, 1)
     if (!rl_wait_ge(vs, need) || !rl_wait_ge(vs + 7, need)) {  // twists (wave 0) and poses (wave 1) up to `need`
       if (mine && kk == 0) P.status[b] = TOLG_ST_INTERNAL;
       return;
     }
     asm volatile("" ::: "memory");
-#ifdef TOLG_STAMPS
-    { unsigned long long t_ = __builtin_amdgcn_s_memtime(); hs_wait += t_ - hs_t; hs_t = t_; }
-#endif
+    TOLG_STAMP(HS, 0)
     const int i = 4 * g + kk;
     if (mine && i <= N) {
       const double* slot = ring[i % RL_RING];
@@ -2888,13 +2867,7 @@ __global__ __launch_bounds__(256) void k_rollout_lin(Params P, int it) {
       if (!(J == J) || isinf(J)) { P.status[b] = TOLG_ST_NONFINITE; P.active[b] = 0; }
     }
   }
-#ifdef TOLG_STAMPS
-  if (blockIdx.x == 5 && lane == 0 && P.alpha_hist) {
-    P.alpha_hist[(size_t)(81 + h) * P.max_iter + 0] = (double)hs_wait;
-    P.alpha_hist[(size_t)(81 + h) * P.max_iter + 1] = (double)hs_work;
-    P.alpha_hist[(size_t)(81 + h) * P.max_iter + 2] = (double)done;
-  }
-#endif
+  stamps_flush(P, HS, blockIdx.x == ST_BLOCK_ROLL && lane == 0, P.alpha_hist, ST_ROW_HELPER + h);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2994,8 +2967,8 @@ __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nsl
     State So = load_state_b(mkbuf(P.cur + stStride * i, 13 * sB), vb, sB);
     V3 ew, ev;
     se3_log(se3_compose(se3_inverse(So.X), Sn.X), ew, ev);
-    double e[12] = {ew.x, ew.y, ew.z, ev.x, ev.y, ev.z, Sn.w.x - So.w.x, Sn.w.y - So.w.y, Sn.w.z - So.w.z,
-                    Sn.v.x - So.v.x, Sn.v.y - So.v.y, Sn.v.z - So.v.z};
+    double e[12];
+    roll_deviation(ew, ev, So, Sn, e);
     double u[M], un[M], du[M];
 #pragma unroll
     for (int a = 0; a < M; a++) {
@@ -3026,6 +2999,8 @@ __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nsl
         Nx = Fn;  // SS: x^_{i+1} = f(x^_i, u^_i) (traopt_controller.py:2073-2080)
       }
       if constexpr (MS) {  // new defect Log(x^_{i+1}^-1 f_q(x^_i,u^_i)), f_xi - xi^_{i+1}
+        // (written out here and in the LINEAR branch below: one local lambda for both changed this kernel's instructions,
+        // which no test can follow with a bit comparison -- no test reaches its list length)
         V3 dw, dv;
         se3_log(se3_compose(se3_inverse(Nx.X), Fn.X), dw, dv);
         V3 xw = Fn.w - Nx.w, xv = Fn.v - Nx.v;
@@ -3078,6 +3053,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
                                                        const double* __restrict__ noise, double* __restrict__ Jout,
                                                        int* __restrict__ status, double* __restrict__ xs_q,
                                                        double* __restrict__ xs_xi, double* __restrict__ us, PA... pl) {
+  Stamps<8> ST;
   const Consts& C = *P.c;
   const PlantArg pa = plant_arg_of(pl...);
   const size_t n = (size_t)P.B * (size_t)S;
@@ -3103,9 +3079,6 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
     Sn.w = Sa.w + v3(d[6], d[7], d[8]);
     Sn.v = Sa.v + v3(d[9], d[10], d[11]);
   }
-#ifdef TOLG_STAMPS
-  RStamps ST = {};
-#endif
   double J = 0.0, un[M];
   for (int i = 0; i < N; i++) {
     if (i + 1 < N) Sb = roll_load_state(P, i + 1, vb, sB);
@@ -3114,7 +3087,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
     const auto& CS = plant_or_model<PL, PK>(C, Vi);
     const State Nx = roll_step<M, false, true, PK, false>(P, CS, DK, i, b, q, false, vb, sB, 0.0, Sa, Sn, un,
                                                            [&](RollIn<M>& R) { roll_load<M, true>(P, i, b, q, vb, sB, R); },
-                                                           nullptr RST_ARG);
+                                                           nullptr, ST);
     J += knot_cost<M, true, PT>(P, C, i, b, Sn, un, false);
     if (writer) {
       state_to_m16(Sn, xs_q, xs_xi, bs * (size_t)(N + 1) + i);
@@ -3800,11 +3773,7 @@ __global__ __launch_bounds__(64) void k_rollout_ls(Params P, int a0, int nslots,
   State Sn = load_state_b(mkbuf(P.cur, 13 * sB), vb, sB);
   if (writer) store_state_b(mkbuf(sx, 13 * sB), vs, sB, Sn);
   const DynK DK = dynk_load(*P.c);  // generic pointer: see the note at DConsts
-#ifdef TOLG_STAMPS
-  RStamps ST;
-  for (int k = 0; k < 8; k++) ST.acc[k] = 0;
-  ST.t = __builtin_amdgcn_s_memtime();
-#endif
+  Stamps<8> ST;
   double un[M];
   auto store = [&](int i) {  // u^_i and x^_{i+1}, at the candidate's place (vs)
     if (writer) {
@@ -3844,14 +3813,14 @@ __global__ __launch_bounds__(64) void k_rollout_ls(Params P, int a0, int nslots,
     if (i + 1 < N) { Sb = roll_load_state(P, i + 1, vb, sB); load_d(i + 1, dB); }
     __builtin_amdgcn_sched_barrier(0);
     Sn = roll_step<M, LINEAR, !MS, PK, false>(P, C, DK, i, b, q, writer, vb, sB, alpha, Sa, Sn, un,
-                                               [&](RollIn<M>& R) { roll_load<M, !MS>(P, i, b, q, vb, sB, R); }, nullptr RST_ARG,
+                                               [&](RollIn<M>& R) { roll_load<M, !MS>(P, i, b, q, vb, sB, R); }, nullptr, ST,
                                                mkpre(dA, Sb, i + 1 < N));
     store(i);
     if (i + 1 >= N) break;
     if (i + 2 < N) { Sa = roll_load_state(P, i + 2, vb, sB); load_d(i + 2, dA); }
     __builtin_amdgcn_sched_barrier(0);
     Sn = roll_step<M, LINEAR, !MS, PK, false>(P, C, DK, i + 1, b, q, writer, vb, sB, alpha, Sb, Sn, un,
-                                               [&](RollIn<M>& R) { roll_load<M, !MS>(P, i + 1, b, q, vb, sB, R); }, nullptr RST_ARG,
+                                               [&](RollIn<M>& R) { roll_load<M, !MS>(P, i + 1, b, q, vb, sB, R); }, nullptr, ST,
                                                mkpre(dB, Sa, i + 2 < N));
     store(i + 1);
   }
@@ -3951,22 +3920,9 @@ __global__ __launch_bounds__(64 * (NT + 1)) void k_rollout_ls2(Params P, int a0,
       const Pose Dx = se3_compose(se3_inverse(So.X), Sn.X);
       const double yl = quat_vec2(Dx.q);
       se3_log_fast(Dx, ew, ev, series_gate(log_small(yl), log_dom(yl)));
-      const double e[12] = {ew.x, ew.y, ew.z, ev.x, ev.y, ev.z, Sn.w.x - So.w.x, Sn.w.y - So.w.y, Sn.w.z - So.w.z,
-                            Sn.v.x - So.v.x, Sn.v.y - So.v.y, Sn.v.z - So.v.z};
-      double mine[2];
-#pragma unroll
-      for (int sidx = 0; sidx < 2; sidx++) {
-        double sacc = alpha * R.G[sidx][12];
-#pragma unroll
-        for (int k = 0; k < 12; k++) sacc += R.G[sidx][k] * e[k];
-        mine[sidx] = sacc;
-      }
-      double un[M], du[M];
-      du[0] = quad_bcast<0>(mine[0]); du[1] = quad_bcast<0>(mine[1]);
-      du[2] = quad_bcast<1>(mine[0]); du[3] = quad_bcast<1>(mine[1]);
-      if constexpr (M == 6) { du[4] = quad_bcast<2>(mine[0]); du[5] = quad_bcast<2>(mine[1]); }
-#pragma unroll
-      for (int a = 0; a < M; a++) un[a] = R.u[a] + du[a];
+      double e[12], un[M], du[M];
+      roll_deviation(ew, ev, So, Sn, e);
+      roll_control<M, false>(R, e, un, du, alpha);
       State Fn;
       if (DK.diag) dyn_twist_k<M, DConsts, PK>(DK, C, Sn, un, Fn);
       else Fn = dyn_f<M, DConsts, PK>(C, Sn, un);
@@ -4279,11 +4235,7 @@ __global__ __launch_bounds__(64) void k_expected_change(Params P) {
   const DynK DK = dynk_load(C);
   double c1 = 0, c2 = 0;
   State So = roll_load_state(P, 0, vb, sB);
-#ifdef TOLG_STAMPS
-  RStamps ST;
-  for (int k = 0; k < 8; k++) ST.acc[k] = 0;
-  ST.t = __builtin_amdgcn_s_memtime();
-#endif
+  Stamps<8> ST;
   // l_x e and e^T l_xx e with l_xx = blkdiag(l_xx11, 2 W2)
   auto state_terms = [&](int i, const double (&e)[12]) {
     __amdgpu_buffer_rsrc_t rR = mkbuf(P.REC + recStride * i, (unsigned)P.recF * sB);
@@ -4305,7 +4257,7 @@ __global__ __launch_bounds__(64) void k_expected_change(Params P) {
     double un[M];
     RollProbe<M> pr;
     const State Nx = roll_step<M, true, false, PK, false>(P, C, DK, i, b, q, writer, vb, sB, 1.0, Sx, Sn, un,
-                                                          [&](RollIn<M>& R) { roll_load<M, false>(P, i, b, q, vb, sB, R); }, &pr RST_ARG);
+                                                          [&](RollIn<M>& R) { roll_load<M, false>(P, i, b, q, vb, sB, R); }, &pr, ST);
     state_terms(i, pr.e);
     __amdgpu_buffer_rsrc_t rR = mkbuf(P.REC + recStride * i, (unsigned)P.recF * sB);
 #pragma unroll
