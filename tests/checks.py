@@ -16,26 +16,54 @@ from tests.restate import MyCost, MyDynamics, restate_mpc_step, restate_policy, 
 from tests.support import ZERO, host, problem_of_kind, random_traj_embedded, rel, same
 
 
-def check_linearize_backward(prob, xs_q, xs_xi, us, ms, solver=None):
+K1_FIELDS = ("Fx", "d", "lx", "lxx11", "J")   # what the linearisation alone produces (the sweep's K, k, grad, mu_delta follow)
+
+
+def check_linearize_backward(prob, xs_q, xs_xi, us, ms, solver=None, fields=None, bounds=None):
     """K1 + K2 (tolg_linearize_backward) on the given trajectories against the oracle's _linearization/_backward_pass,
-    trajectory by trajectory; solver: a handle on prob (default: a fresh one of the batch's size)."""
+    trajectory by trajectory; solver: a handle on prob (default: a fresh one of the batch's size).  fields: the subset to
+    compare (default: all of Fx, d, lx, lxx11, J, K, k, grad, mu_delta).  bounds: {field: [B] or scalar} in place of a
+    field's bound below, for trajectories on which the reference itself is known to be further from exact than that.
+    Returns the worst figure per field."""
     B = xs_q.shape[0]
     solver = BatchedTrackingILQR(prob, B) if solver is None else solver
     r = solver.linearize_backward(xs_q, xs_xi, us, ms=ms)
     torch.cuda.synchronize()
     op = ob.OracleProblem(prob.kind, prob.J, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref,
                           pend_mass=prob.pend_mass, pend_length=prob.pend_length)
+    want = lambda f: fields is None or f in fields  # noqa: E731
+    worst = {}
+
+    def bound(f, b, default):
+        v = default if bounds is None or f not in bounds else bounds[f]
+        return float(v[b]) if np.ndim(v) else float(v)
+
+    def within(f, b, err, default):
+        worst[f] = max(worst.get(f, 0.0), float(err))
+        assert err < bound(f, b, default), (f, b, float(err), bound(f, b, default))
+
     for b in range(B):
         o = ob.lin_backward(op, xs_q[b], xs_xi[b], us[b], ms=ms)
-        assert rel(r["Fx"][b].cpu(), o["Fx"]) < 1e-12
-        assert np.abs(r["d"][b].cpu().numpy() - o["d"]).max() < 1e-11 * max(1.0, np.abs(o["d"]).max())
-        assert rel(r["lx"][b].cpu(), o["Lx"]) < 1e-11
-        assert rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]) < 1e-11
-        assert float(r["J"][b]) == pytest.approx(o["J"], rel=1e-12)
-        assert rel(r["K"][b].cpu(), o["K"]) < 1e-8
-        assert rel(r["k"][b].cpu(), o["k"]) < 1e-8
-        assert float(r["grad"][b]) == pytest.approx(o["grad"], rel=1e-9)
-        assert float(r["mu_delta"][b, 0]) == o["mu"] and float(r["mu_delta"][b, 1]) == o["delta"]
+        if want("Fx"):
+            within("Fx", b, rel(r["Fx"][b].cpu(), o["Fx"]), 1e-12)
+        if want("d"):
+            within("d", b, np.abs(r["d"][b].cpu().numpy() - o["d"]).max() / max(1.0, np.abs(o["d"]).max()), 1e-11)
+        if want("lx"):
+            within("lx", b, rel(r["lx"][b].cpu(), o["Lx"]), 1e-11)
+        if want("lxx11"):
+            within("lxx11", b, rel(r["lxx11"][b].cpu(), o["Lxx"][:, :6, :6]), 1e-11)
+        if want("J"):
+            assert float(r["J"][b]) == pytest.approx(o["J"], rel=bound("J", b, 1e-12))
+            worst["J"] = max(worst.get("J", 0.0), abs(float(r["J"][b]) / o["J"] - 1))
+        if want("K"):
+            within("K", b, rel(r["K"][b].cpu(), o["K"]), 1e-8)
+        if want("k"):
+            within("k", b, rel(r["k"][b].cpu(), o["k"]), 1e-8)
+        if want("grad"):
+            assert float(r["grad"][b]) == pytest.approx(o["grad"], rel=1e-9)
+        if want("mu_delta"):
+            assert float(r["mu_delta"][b, 0]) == o["mu"] and float(r["mu_delta"][b, 1]) == o["delta"]
+    return worst
 
 
 def al_oracle(prob, x0_q, x0_xi, us0, lb, ub, n_al, n_ilqr, tol_constr, mu0=1e-2, mu_scale=10.0, mu_max=1e8):
@@ -193,7 +221,8 @@ def update_restated(g, lam, imu, mu, mu_scale=10.0):
     return ln, np.where((g < 0) & (ln == 0), 0.0, mu_new)
 
 
-def check_restatement(s, r, ops, dx0, w):
+def check_restatement(s, r, ops, dx0, w, min_finite=None):
+    """min_finite: the share of samples the restatement must keep finite, as (numerator, denominator); default a half."""
     g = s.gains()
     p = s.policy_rollout(dx0, w, trajectories=True)
     K = host(g["K"])
@@ -208,4 +237,5 @@ def check_restatement(s, r, ops, dx0, w):
         assert np.abs(host(p.us)[b][fin] - uu[fin]).max(initial=0) < 1e-8
         assert np.abs(host(p.J)[b][fin] / J[fin] - 1).max(initial=0) < 1e-9
         ok += int(fin.sum())
-    assert ok >= len(ops) * S // 2
+    num, den = (1, 2) if min_finite is None else min_finite
+    assert ok >= len(ops) * S * num // den, (ok, len(ops) * S)

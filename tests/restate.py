@@ -34,6 +34,41 @@ def restate_policy(op, q_nom, xi_nom, u_nom, K, dx0=None, noise=None, S=1):
     return J, xs_q, xs_xi, us
 
 
+def restate_rollout(op, q, xi, u, k, K, alpha=1.0, ms=True, linear=False):
+    """One closed-loop rollout of the line search (oracle/tolg_oracle.c:876-972) about the trajectory (q, xi, u) with the
+    gains (k, K), from oracle primitives and matrix products: the deviation e_i = [Log(x_i^-1 x^_i); xi^_i - xi_i],
+    u^_i = u_i + alpha k_i + K_i e_i, and the step
+      MS nonlinear: x^_{i+1} = x_{i+1} Exp(alpha d_q) f_q(x_i, u_i)^-1 f_q(x^_i, u^_i),
+                    xi^_{i+1} = xi_{i+1} + f_xi(x^_i, u^_i) - f_xi(x_i, u_i) + alpha d_xi,
+      MS linear:    x^_{i+1} = x_{i+1} Exp(F_x e + F_u du + alpha d), the twist rows added to xi_{i+1},
+      SS nonlinear: x^_{i+1} = f(x^_i, u^_i);   SS linear: the MS form without the defect,
+    with d_i = [Log(x_{i+1}^-1 f_q(x_i, u_i)); f_xi(x_i, u_i) - xi_{i+1}] and F_x, F_u at (x_i, u_i), all computed here.
+    q [N+1, 4, 4], xi [N+1, 6], u [N, m], k [N, m], K [N, m, 12].  Returns xs_q [N+1, 4, 4], xs_xi [N+1, 6], us [N, m]."""
+    N, m = u.shape
+    nq = np.zeros((N + 1, 4, 4)); nxi = np.zeros((N + 1, 6)); nu = np.zeros((N, m))
+    nq[0], nxi[0] = np.asarray(q[0], float).reshape(4, 4), xi[0]
+    for i in range(N):
+        e = np.r_[ob.rminus(nq[i], q[i]), nxi[i] - xi[i]]
+        du = alpha * k[i] + K[i] @ e
+        nu[i] = u[i] + du
+        if not ms and not linear:
+            nq[i + 1], nxi[i + 1] = ob.f(op, nq[i], nxi[i], nu[i])
+            continue
+        fq, fxi = ob.f(op, q[i], xi[i], u[i])
+        d = np.r_[ob.rminus(fq, q[i + 1]), fxi - xi[i + 1]] if ms else np.zeros(12)
+        qn = np.asarray(q[i + 1], float).reshape(4, 4)
+        if linear:
+            Fx, Fu = ob.fx_fu(op, q[i], xi[i], u[i])
+            lin = Fx @ e + Fu @ du + alpha * d
+            nq[i + 1], nxi[i + 1] = qn @ ob.se3_exp(lin[:6]), xi[i + 1] + lin[6:]
+        else:
+            fqn, fxin = ob.f(op, nq[i], nxi[i], nu[i])
+            fi = np.eye(4); fi[:3, :3] = fq[:3, :3].T; fi[:3, 3] = -fq[:3, :3].T @ fq[:3, 3]
+            nq[i + 1] = qn @ ob.se3_exp(alpha * d[:6]) @ fi @ fqn
+            nxi[i + 1] = xi[i + 1] + fxin - fxi + alpha * d[6:]
+    return nq, nxi, nu
+
+
 def restate_covariance(op, q_nom, xi_nom, u_nom, K, Sigma0=None, W=None):
     """Sigma_{i+1} = Acl_i Sigma_i Acl_i^T + E W E^T, Acl_i = f_x + f_u K_i at (x*_i, u*_i), E = [0; I6], from ob.fx_fu only.
     q_nom [N+1, 4, 4], xi_nom [N+1, 6], u_nom [N, m], K [N, m, 12], Sigma0 [12, 12], W [6, 6] (None: zero).

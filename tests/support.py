@@ -240,3 +240,269 @@ def held_policy(s, q, xi, us, mode, **per_traj):
     r = s.fit_batch(q, xi, us, mode=mode, **KW, **per_traj)
     s.linearize_backward(r.xs_q, r.xs_xi, r.us, ms=(mode == "ms"), **per_traj)
     return r
+
+
+# ---- large rotations: the case grid of tests/test_gpu_large_rotation.py ---------------------------------------------------
+ORACLE_CANCEL = 1e-2  # angles below this: the oracle's closed forms lose digits to cancellation (see knot_buckets)
+NEAR_PI = 2e-3  # deviations closer to pi than this: the Log's rotation part may come out with either sign
+
+
+def _both_sides(e):
+    return [e * (1 - 1e-6), e * (1 + 1e-6), 0.9 * e, 1.1 * e]
+
+
+def rotation_grid(n_random=4, seed=0):
+    """Deviation angles on both sides of every threshold the kernels branch on (csrc/tolg_lie.h), step rotations |omega| dt
+    built the same way, and the axes to lay them along: (angles, steps, axes).  A threshold in y = |q_v|^2 is the angle
+    2 asin sqrt(y), one in th2 the angle sqrt(th2); each is taken at e (1 +- 1e-6), 0.9 e and 1.1 e of its own quantity."""
+    ang = []
+    for y in (1e-10, 1e-3, 0.25):                       # manif's small-angle switch, Log short tier, Log domain
+        ang += [2 * np.arcsin(np.sqrt(v)) for v in _both_sides(y)]
+    for th2 in (1e-10, 0.01, 0.04, 1.21):               # t^2 switch; ljinv / coef short tiers and domain at the Log's angle
+        ang += [np.sqrt(v) for v in _both_sides(th2)]
+    ang += [1.5, 2.1, 2.5, 3.0, 3.13, np.pi - NEAR_PI]
+    steps = []
+    for th2 in (1e-10, 0.04, 1.0):                      # Exp: small-angle switch, short tier, domain
+        steps += [np.sqrt(v) for v in _both_sides(th2)]
+    steps += [1.5, 2.5, 3.5, 4.0]                       # the last two beyond pi: se3_exp's quaternion has w < 0
+    rng = np.random.default_rng(seed)
+    ax = rng.normal(size=(n_random, 3))
+    axes = np.r_[np.eye(3), -np.eye(3), ax / np.linalg.norm(ax, axis=1, keepdims=True)]
+    return np.array(ang), np.array(steps), axes
+
+
+def r_to_q(R):
+    """R_to_q of csrc/tolg_lie.h:72-86 (scipy's from_matrix) in numpy: (unit quaternion xyzw, branch 0..3)."""
+    R = np.asarray(R, float)[:3, :3]
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr >= R[0, 0] and tr >= R[1, 1] and tr >= R[2, 2]:
+        q, br = [R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1], 1 + tr], 0
+    elif R[0, 0] >= R[1, 1] and R[0, 0] >= R[2, 2]:
+        q, br = [1 - tr + 2 * R[0, 0], R[1, 0] + R[0, 1], R[2, 0] + R[0, 2], R[2, 1] - R[1, 2]], 1
+    elif R[1, 1] >= R[2, 2]:
+        q, br = [R[0, 1] + R[1, 0], 1 - tr + 2 * R[1, 1], R[2, 1] + R[1, 2], R[0, 2] - R[2, 0]], 2
+    else:
+        q, br = [R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], 1 - tr + 2 * R[2, 2], R[1, 0] - R[0, 1]], 3
+    q = np.array(q)
+    return q / np.sqrt(q @ q), br
+
+
+def qmul(a, b):
+    """qmul of csrc/tolg_lie.h (xyzw)"""
+    return np.array([a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1],
+                     a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2],
+                     a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0],
+                     a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2]])
+
+
+def qconj(a):
+    return np.array([-a[0], -a[1], -a[2], a[3]])
+
+
+def exp_q(w):
+    """so3_exp of csrc/tolg_lie.h: the quaternion of Exp(w), w = cos(|w| / 2) (negative beyond pi)"""
+    t = np.linalg.norm(w)
+    return np.r_[0.5 * np.asarray(w), 1.0] if t * t <= 1e-10 else np.r_[np.sin(t / 2) / t * np.asarray(w), np.cos(t / 2)]
+
+
+LOG_TIERS = ("log_tiny", "log_short", "log_long", "log_closed")
+EXP_TIERS = ("exp_tiny", "exp_short", "exp_long", "exp_closed", "exp_beyond_pi")
+
+
+def log_tier(y):
+    """The tier se3_log_fast gives a lane whose product quaternion has |q_v|^2 = y."""
+    return 0 if not y > 1e-10 else 1 if y < 1e-3 else 2 if y < 0.25 else 3
+
+
+def exp_tier(th2):
+    """The tier se3_exp_fast / so3_exp_fast give a lane with step rotation^2 th2 (4: closed form beyond pi, w < 0)."""
+    return 0 if not th2 > 1e-10 else 1 if th2 < 0.04 else 2 if th2 < 1.0 else 3 if th2 < np.pi ** 2 else 4
+
+
+def product_quaternion(Ra, Rb, left=True):
+    """The quaternion whose Log the kernels take between two poses given as matrices, with the signs R_to_q gives the
+    factors: q_a q_b^-1 (left: lin_knot's tracking error) or q_b^-1 q_a (roll_step's deviation).  Returns (q, y, angle)."""
+    qa, qb = r_to_q(Ra)[0], r_to_q(Rb)[0]
+    q = qmul(qa, qconj(qb)) if left else qmul(qconj(qb), qa)
+    y = float(q[:3] @ q[:3])
+    return q, y, 2.0 * np.arctan2(np.sqrt(y), abs(q[3]))
+
+
+# the orientations of the large-rotation reference: both sides of 90 degrees and up to 179.9 about the coordinate axes, their
+# negatives (beyond 90 degrees about a negative axis R_to_q returns w < 0) and a generic axis; all four branches of R_to_q
+_G = np.array([0.48, -0.6, 0.64])
+ORIENT_AXES = np.r_[np.eye(3)[[0, 0, 1, 1, 2, 2]] * np.array([1, -1, 1, -1, 1, -1])[:, None], _G[None] / np.linalg.norm(_G)]
+ORIENT_DEG = (89.0, 91.0, 179.9, 135.0, 30.0)
+ORIENTATIONS = [(a, d) for d in ORIENT_DEG for a in ORIENT_AXES]   # knot i takes entry (8 i) mod 35
+
+
+def orientation_of_knot(i):
+    return ORIENTATIONS[(8 * i) % len(ORIENTATIONS)]
+
+
+def large_rotation_problem(prob):
+    """prob (its J, dt and weights; workloads.se3_tracking's for se3) with the rotation of q_ref[i] replaced by
+    orientation_of_knot(i): absolute orientations that R_to_q converts through all of its branches.  Translations and the
+    twist reference stay."""
+    q_ref = np.array(prob.q_ref, float).copy()
+    for i in range(q_ref.shape[0]):
+        a, d = orientation_of_knot(i)
+        q_ref[i, :3, :3] = ob.se3_exp(np.r_[a * np.deg2rad(d), 0, 0, 0])[:3, :3]
+    return with_ref(prob, q_ref, prob.xi_ref)
+
+
+def knot_buckets(R_state, R_ref, wdt):
+    """The coverage buckets one state of an eval_knot call falls into: names from LOG_TIERS, EXP_TIERS, "conv0".."conv3",
+    "wneg_small" (product quaternion w < 0, deviation below 0.06 rad), "wneg_large" (w < 0, above pi / 3), "near_pi"."""
+    q, y, ang = product_quaternion(R_state, R_ref, left=True)
+    out = {LOG_TIERS[log_tier(y)], EXP_TIERS[exp_tier(float(np.dot(wdt, wdt)))], "conv%d" % r_to_q(R_state)[1]}
+    if q[3] < 0 and ang < 0.06:
+        out.add("wneg_small")
+    if q[3] < 0 and ang > np.pi / 3:
+        out.add("wneg_large")
+    if np.pi - ang < NEAR_PI * (1 - 1e-9):
+        out.add("near_pi")
+    # where the fp64 ORACLE is the noisy side: its closed-form coefficients ((t^2 + 2 cos t - 2) / 2 t^4 and the like) cancel
+    # for a small angle above manif's switch, and its tiny branch divides a product quaternion's rounding by the angle
+    if ang < ORACLE_CANCEL:
+        out.add("log_cancel")
+    if 1e-10 < float(np.dot(wdt, wdt)) < ORACLE_CANCEL ** 2:
+        out.add("exp_cancel")
+    return out
+
+
+KNOT_BUCKETS = LOG_TIERS + ("wneg_small", "wneg_large", "conv0", "conv1", "conv2", "conv3") + EXP_TIERS
+
+
+def assert_coverage(tags, need=KNOT_BUCKETS, least=4):
+    """The coverage guard: every bucket of `need` holds at least `least` of the states (tags: one set of names per state)."""
+    count = {k: sum(k in t for t in tags) for k in need}
+    short = {k: c for k, c in count.items() if c < least}
+    assert not short, "buckets short of %d states: %s" % (least, short)
+    return count
+
+
+def knot_states(prob, i, seed=1, wave=64):
+    """The states of the eval_knot parity at knot i of a large_rotation_problem: poses Exp(dev) q_ref[i] with the deviations
+    of rotation_grid (and, about the reference's own axis, the ones that carry the state across a sign change of R_to_q),
+    twists whose step rotation |omega| dt runs over the grid's steps.  Laid out uniform: `wave` consecutive states from one
+    bucket, bucket after bucket (a wave of the Log / conversion buckets holds short-tier step rotations only, a wave of the
+    Exp buckets short-tier deviations only, so a wave's gate is the bucket's); "mixed" is a seeded shuffle of the same
+    states.  Returns dict(x_q [n, 4, 4], x_xi [n, 6], u [n, m], tags [n sets], waves [bucket per wave], mixed [n])."""
+    ang, steps, axes = rotation_grid()
+    rng = np.random.default_rng(seed + 7 * i)
+    so3 = prob.kind in ("so3", "pendulum3d")
+    dt, Xr, a_r = prob.dt, np.asarray(prob.q_ref[i], float), orientation_of_knot(i)[0]
+    unit = lambda v: v / np.linalg.norm(v)  # noqa: E731
+
+    def pose(dev):
+        t = np.zeros(3) if so3 else rng.normal(size=3) * 0.3
+        return ob.se3_exp(np.r_[dev, t]) @ Xr
+
+    def omega(step):
+        return unit(rng.normal(size=3)) * step / dt
+
+    short_step = lambda: rng.uniform(0.02, 0.19)  # noqa: E731
+    # candidates (pose, omega): the Log grid with short steps ...
+    cand = [(pose(a * x), omega(short_step())) for a in ang for x in axes]
+    cand += [(pose(unit(rng.normal(size=3)) * a), omega(short_step())) for a in np.logspace(-6, np.log10(3.1), 40)]
+    for sgn in (1.0, -1.0):  # ... across R_to_q's sign change: about the reference's axis, both ways, small and large
+        for lo, hi in ((0.02, 0.058), (1.1, 3.0)):
+            cand += [(pose(unit(sgn * a_r + rng.normal(size=3) * 0.003) * rng.uniform(lo, hi)), omega(short_step()))
+                     for _ in range(wave)]
+    cand += [(pose(x * (np.pi - g)), omega(short_step())) for g in (1e-3, 1e-5, 1e-7) for x in axes]   # the band at pi
+    n_log = len(cand)
+    # ... and the Exp grid with short-tier deviations
+    small_dev = lambda: unit(rng.normal(size=3)) * rng.uniform(1e-3, 0.05)  # noqa: E731
+    cand += [(pose(small_dev()), x * s / dt) for s in steps for x in axes]
+    cand += [(pose(small_dev()), omega(s)) for s in np.r_[np.logspace(-7, np.log10(4.0), 40), rng.uniform(np.pi, 4.0, 8)]]
+    tags = [knot_buckets(X, Xr, dt * w) for X, w in cand]
+    order, waves = [], []
+    for bucket in KNOT_BUCKETS + ("near_pi",):
+        pool = [k for k, t in enumerate(tags) if bucket in t and
+                (("exp_short" in t and (bucket == "near_pi" or "near_pi" not in t) and k < n_log) if not bucket.startswith("exp_")
+                 else ("log_short" in t and k >= n_log))]
+        assert len(pool) >= 4, (bucket, len(pool))
+        order += list(np.resize(rng.permutation(pool), wave))
+        waves.append(bucket)
+    n = len(order)
+    x_q = np.array([cand[k][0] for k in order])
+    x_xi = np.zeros((n, 6))
+    x_xi[:, :3] = np.array([cand[k][1] for k in order])
+    u = rng.normal(size=(n, prob.m)) * 0.3
+    if so3:
+        u[:, 3:] = 0.0
+    else:
+        x_xi[:, 3:] = np.asarray(prob.xi_ref[i], float)[3:] + rng.normal(size=(n, 3)) * 0.3
+    return dict(x_q=x_q, x_xi=x_xi, u=u, tags=[tags[k] for k in order], waves=waves, mixed=rng.permutation(n))
+
+
+def large_rotation_trajectories(prob, B, seed, twists="moderate"):
+    """B trajectories on a large_rotation_problem for linearize_backward and the rollouts behind it.  Even trajectories lay
+    the deviations of rotation_grid along the knots, x_i = Exp(dev) q_ref[i], so that one block of K1 mixes every tier;
+    odd ones are chained, x_{i+1} = f_q(x_i, u_i) Exp(-delta): b = 1 mod 4 with |delta| between 0.5 and 3 rad, multiple-shooting
+    defects that are themselves large; b = 3 mod 4 with defects of the short and the long Log tier in turn, so that a rollout
+    about them meets small deviations too.  twists: "moderate" (xi_ref + N(0, 1): the backward sweep stays unregularised),
+    "tiers" (|omega| dt of every knot from the grid's steps) or "sparse" (moderate, with a grid step at knots 2 and
+    N - 1 only: the rollouts that follow the stored twists see every Exp tier, and no closed loop has to carry 80 rad/s
+    through the horizon -- explicit Euler steps of the rigid body do not survive that).
+    Returns xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6], us [B, N, m]."""
+    ang, steps, axes = rotation_grid()
+    rng = np.random.default_rng(seed)
+    N, m, dt = prob.N, prob.m, prob.dt
+    so3 = prob.kind in ("so3", "pendulum3d")
+    keep = np.r_[1, 1, 1, 0, 0, 0] if so3 else np.ones(6)
+    op = op_of(prob)
+    devs = [a * x for a in ang for x in axes]
+    devs = [devs[k] for k in rng.permutation(len(devs))]
+    # angles below ORACLE_CANCEL, where the oracle's own rounding sets the bounds, go to every fourth trajectory only
+    plain = [d for d in devs if np.linalg.norm(d) >= ORACLE_CANCEL]
+    xs_q = np.empty((B, N + 1, 4, 4)); xs_xi = np.empty((B, N + 1, 6)); us = rng.normal(size=(B, N, m)) * 0.3
+    if so3:
+        us[:, :, 3:] = 0.0
+    n = 0
+    for b in range(B):
+        for i in range(N + 1):
+            xs_xi[b, i] = prob.xi_ref[i] + rng.normal(size=6) * keep
+            if twists == "tiers" or (twists == "sparse" and i in (2, N - 1)):
+                # (sparse: about a principal axis of the inertia, where J omega x omega vanishes)
+                ax = rng.normal(size=3) if twists == "tiers" else axes[rng.integers(6)]
+                xs_xi[b, i, :3] = ax / np.linalg.norm(ax) * steps[(n + b) % len(steps)] / dt
+            if b % 2 == 0 or i == 0:
+                for skip in range(len(devs)):  # (the next deviation, should this one leave a defect in the band at pi)
+                    dev = devs[(n + skip) % len(devs)] if b % 4 == 0 else plain[(n + skip) % len(plain)]
+                    xs_q[b, i] = ob.se3_exp(np.r_[dev, rng.normal(size=3) * 0.3] * keep) @ prob.q_ref[i]
+                    if i == 0 or np.pi - np.linalg.norm(ob.rminus(
+                            ob.f(op, xs_q[b, i - 1], xs_xi[b, i - 1], us[b, i - 1])[0], xs_q[b, i])[:3]) > 4 * NEAR_PI:
+                        break
+            else:
+                fq, fxi = ob.f(op, xs_q[b, i - 1], xs_xi[b, i - 1], us[b, i - 1])
+                ax = rng.normal(size=3)
+                lo, hi = (0.5, 3.0) if b % 4 == 1 else ((1e-3, 0.05), (0.1, 0.9))[i % 2]
+                delta = np.r_[ax / np.linalg.norm(ax) * rng.uniform(lo, hi), rng.normal(size=3) * 0.3 * hi / 3.0] * keep
+                xs_q[b, i] = fq @ ob.se3_exp(-delta)
+            n += 1
+    return xs_q, xs_xi, us
+
+
+def trajectory_buckets(prob, xs_q, xs_xi):
+    """Coverage tags of every (trajectory, knot) under K1: the tracking error's Log tier, the conversion branch, the step
+    rotation's Exp tier, and of the defect Log(x_{i+1}^-1 f_q(x_i, u_i)) "defect_large" (0.5 to 3 rad) and "defect_wneg"
+    (its product quaternion, q(x_{i+1})^-1 (q(x_i) q(Exp(omega_i dt))), has w < 0); "defect_near_pi": within NEAR_PI of pi."""
+    tags = []
+    B, N1 = xs_q.shape[:2]
+    for b in range(B):
+        for i in range(N1):
+            t = knot_buckets(xs_q[b, i], prob.q_ref[i], prob.dt * xs_xi[b, i, :3])
+            if i + 1 < N1:
+                qf = qmul(r_to_q(xs_q[b, i])[0], exp_q(prob.dt * xs_xi[b, i, :3]))
+                qd = qmul(qconj(r_to_q(xs_q[b, i + 1])[0]), qf)
+                a = 2.0 * np.arctan2(np.linalg.norm(qd[:3]), abs(qd[3]))
+                if 0.5 <= a <= 3.0:
+                    t.add("defect_large")
+                if qd[3] < 0:
+                    t.add("defect_wneg")
+                if np.pi - a < NEAR_PI:
+                    t.add("defect_near_pi")
+            tags.append(t)
+    return tags

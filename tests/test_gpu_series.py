@@ -2,7 +2,8 @@
 a long-double reference, with arguments on both sides of every tier / domain boundary sharing a wavefront ("mixed-lane
 gates"): a wave whose gate says "some lane needs the long tier / the closed form" must still give every lane the value its
 own argument asks for, and a shared gate (the one lin_knot builds) must not shorten a series for a lane that needs it.
-Through the C ABI (tolg_selftest_series)."""
+A second block of arguments runs from 1.3 rad to 2 pi - 0.4 on both sides of pi: the closed forms behind g.any_fb, Exp
+quaternions with w < 0 and the Log's principal value.  Through the C ABI (tolg_selftest_series)."""
 import ctypes as C
 import os
 import sys
@@ -90,7 +91,63 @@ def _args():
             v = rng.uniform(-1, 1, 3)
             th2s = float(rng.choice([1e-12, 0.005, 0.0399, 0.0401, 0.2, 0.99, 1.2]))  # step rotation: all tiers
             rows.append(np.r_[w, v, th2s, mode])
+    return np.r_[np.array(rows), _large_args()]
+
+
+# Angles of 1.3 rad and more: the floor is the distance of the closed forms in numpy fp64 from the same expressions in long
+# double over _large_args (exp.q 3.3e-16, exp.t 4.5e-16, log.w 1.7e-15, log.v 5.0e-16, coef.a 4.3e-15, coef.b 2.9e-16, coef.c2
+# 9.6e-16, coef.c3 3.8e-15, ljinv 3.8e-15); a quantity keeps the tolerance it has below 1.3 rad where eight times its floor is
+# below that (log.v, coef.c3) and takes eight times its floor otherwise.
+TOL_LARGE = {"exp.q": 8 * 3.3e-16, "exp.t": 8 * 4.5e-16, "log.w": 8 * 1.7e-15, "log.v": 3e-14, "coef.a": 8 * 4.3e-15,
+             "coef.b": 8 * 2.9e-16, "coef.c2": 8 * 9.6e-16, "coef.c3": 3e-13, "ljinv": 8 * 3.8e-15}
+PI_BAND = 2e-3   # Log's rotation part may come out with either sign this close to pi
+LARGE = 1.305    # the angles of _large_args lie above, those of the first block (th2 <= 1.7) below: their tolerances stay
+
+
+def _large_args():
+    """Angles from 1.3 rad to 2 pi - 0.4 on both sides of pi (outside the band at pi), 48 to a wave with 16 lanes of small
+    and long-tier angles among them: beyond pi se3_exp's quaternion has w < 0 and the Log is the principal value."""
+    rng = np.random.default_rng(11)
+    ang = np.r_[1.5, 2.1, 2.5, 3.0, 3.13, np.pi - 1.5 * PI_BAND, np.pi + 1.5 * PI_BAND, 3.5, 4.0, 2 * np.pi - 0.4,
+                np.linspace(1.31, np.pi - 0.01, 19), np.linspace(np.pi + 0.01, 2 * np.pi - 0.41, 19)]
+    assert len(ang) == 48
+    rows = []
+    for mode in (0.0, 1.0):
+        th = np.r_[ang, np.sqrt(rng.uniform(1e-4, 0.9, 16))][rng.permutation(64)]
+        for t in th:
+            ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
+            th2s = float(rng.choice([1e-12, 0.005, 0.0399, 0.0401, 0.2, 0.99, 1.2]))
+            rows.append(np.r_[ax * t, rng.uniform(-1, 1, 3), th2s, mode])
     return np.array(rows)
+
+
+def _V(w, T=LD):
+    """V(w) = I + a W + b W^2 in the closed forms, evaluated in type T"""
+    w = np.asarray(w, T)
+    th2 = np.dot(w, w); t = np.sqrt(th2)
+    W = _skew(w).astype(T)
+    return np.eye(3, dtype=T) + (1 - np.cos(t)) / th2 * W + (t - np.sin(t)) / (th2 * t) * (W @ W)
+
+
+def _principal_log(w, v, T=LD):
+    """Log(Exp(w, v)) for |w| > pi: w' = w (1 - 2 pi / |w|), v' = V(w')^-1 V(w) v, in type T (pi to T's precision)"""
+    w, v = np.asarray(w, T), np.asarray(v, T)
+    t = np.sqrt(np.dot(w, w))
+    pi = T(np.arctan(T(1))) * 4
+    wp = w * (1 - 2 * pi / t)
+    return wp, _solve3(_V(wp, T), _V(w, T) @ v)
+
+
+def _solve3(A, b):
+    """A^-1 b by Cramer's rule in the type of A (numpy's solvers do not take long double)"""
+    det = lambda M: (M[0, 0] * (M[1, 1] * M[2, 2] - M[1, 2] * M[2, 1]) - M[0, 1] * (M[1, 0] * M[2, 2] - M[1, 2] * M[2, 0])  # noqa: E731
+                     + M[0, 2] * (M[1, 0] * M[2, 1] - M[1, 1] * M[2, 0]))
+    d = det(A)
+    out = []
+    for k in range(3):
+        M = A.copy(); M[:, k] = b
+        out.append(det(M) / d)
+    return np.array(out, dtype=A.dtype)
 
 
 def _rel(a, b, floor=1e-300):
@@ -108,7 +165,10 @@ def test_series_forms_match_long_double_reference_with_mixed_lane_gates():
     rc = lib.tolg_selftest_series(n, C.c_void_p(d_a.data_ptr()), C.c_void_p(d_o.data_ptr()), None)
     assert rc == 0
     torch.cuda.synchronize()
-    O = d_o.cpu().numpy()
+    _check_rows(A, d_o.cpu().numpy())
+
+
+def _check_rows(A, O):
     worst = {}
 
     def chk(name, got, ref, tol, floor=1e-300):
@@ -130,25 +190,35 @@ def test_series_forms_match_long_double_reference_with_mixed_lane_gates():
         else:  # manif's small-angle Exp: q = normalise(w/2, 1), V = I + W/2
             q_ref = np.r_[w / 2, LD(1)]; q_ref = q_ref / np.sqrt(np.dot(q_ref, q_ref))
             t_ref = v + LD(0.5) * (W @ v)
+        big = float(t) >= LARGE
         for k in range(4):
-            chk("exp.q", o[6 + k], q_ref[k], 4e-16, floor=1.0)
+            chk("exp.q" + (":large" if big else ""), o[6 + k], q_ref[k], TOL_LARGE["exp.q"] if big else 4e-16, floor=1.0)
         for k in range(3):
-            chk("exp.t", o[10 + k], t_ref[k], 1e-15, floor=1.0)
-        # --- Log(Exp(w, v)) = (w, v) up to the conditioning of the round trip (angles < 1.3 rad)
+            chk("exp.t" + (":large" if big else ""), o[10 + k], t_ref[k], TOL_LARGE["exp.t"] if big else 1e-15, floor=1.0)
+        # --- Log(Exp(w, v)) = (w, v) up to the conditioning of the round trip; beyond pi the principal value
+        lw_ref, lv_ref = (w, v) if float(t) < np.pi else _principal_log(w, v)
         for k in range(3):
             # (|q_v|^2 <= 1e-10, i.e. angle^2 <= 4e-10, takes manif's small-angle Log 2 q_v and V^-1 = I - W/2)
-            chk("log.w", o[13 + k], w[k], 2e-15 if th2 > 5e-10 else 1e-9, floor=max(float(t), 1e-8))
-            chk("log.v", o[16 + k], v[k], 3e-14 if th2 > 5e-10 else 1e-9, floor=1.0)
+            chk("log.w" + (":large" if big else ""), o[13 + k], lw_ref[k], TOL_LARGE["log.w"] if big else 2e-15 if th2 > 5e-10 else 1e-9,
+                floor=max(float(np.sqrt(np.dot(lw_ref, lw_ref))), 1e-8))
+            chk("log.v" + (":large" if big else ""), o[16 + k], lv_ref[k], TOL_LARGE["log.v"] if big else 3e-14 if th2 > 5e-10 else 1e-9,
+                floor=1.0)
         # --- coefficient series at the rotation's own angle (own gates) or at the Log's angle (shared gate)
         th2k = float(np.dot(o[13:16], o[13:16])) if shared else th2
         ra, rb, rc2, rc3 = _coef_ref(th2k)
-        if th2k > EPS:
+        bigk = th2k >= LARGE * LARGE
+        if bigk:
+            for name, got, ref in (("coef.a", o[0], ra), ("coef.b", o[1], rb), ("coef.c2", o[3], rc2), ("coef.c3", o[4], rc3),
+                                   ("ljinv", o[5], _ljinv_ref(th2k)), ("coef.c1", o[2], rb)):
+                chk(name + ":large", got, ref, TOL_LARGE[name if name != "coef.c1" else "coef.b"])
+        elif th2k > EPS:
             chk("coef.a", o[0], ra, 5e-16); chk("coef.b", o[1], rb, 5e-16)
             chk("coef.c2", o[3], rc2, 6e-15 if th2k > 1.0 else 5e-16); chk("coef.c3", o[4], rc3, 3e-13 if th2k > 1.0 else 5e-16)
             chk("ljinv", o[5], _ljinv_ref(th2k), 2e-14 if th2k > 0.26 else 5e-16)
         else:
             assert o[0] == 0.5 and o[1] == 0.0 and o[5] == 0.0
-        chk("coef.c1", o[2], rb if th2k > EPS else LD(1) / 6, 5e-16 if th2k > EPS else 1e-10)
+        if not bigk:
+            chk("coef.c1", o[2], rb if th2k > EPS else LD(1) / 6, 5e-16 if th2k > EPS else 1e-10)
         # --- step rotation about the same axis, angle^2 = th2s
         ts = np.sqrt(LD(th2s))
         ax = (w / t) if th2 > 0 else w

@@ -190,7 +190,10 @@ TOLG_DEV void se3_log(Pose X, V3& w, V3& v) {
     if (two * two <= TOLG_EPS) cl = 0.0;  // manif's small-angle V^-1 = I - W/2
   } else {
     c = (q.w < 0.0) ? -2.0 : 2.0;
-    cl = 0.0;
+    // manif switches V^-1 on the angle^2 = 4 s2 of the small-angle Log: above it the W^2 term stays (two series terms are exact
+    // to 1e-20 here; the closed form cancels)
+    const double t2 = 4.0 * s2;
+    cl = (t2 <= TOLG_EPS) ? 0.0 : 1.0 / 12 + t2 * (1.0 / 720);
   }
   w = v3(c * q.x, c * q.y, c * q.z);
   v = ljacinv_apply(w, cl, X.t);
@@ -363,7 +366,9 @@ TOLG_DEV void se3_log_fast(Pose X, V3& w, V3& v, SeriesGate g) {
   const double t2 = c * c * y;                        // angle^2 (< 4.1e-3 when sm)
   double cl = horner2<5>(L, t2, sm, g.any_long);
   if (tiny) c = 2.0;                      // manif's small-angle Log: 2 q_v
-  if (tiny || t2 <= TOLG_EPS) cl = 0.0;   // and its small-angle V^-1 = I - W/2
+  // and its small-angle V^-1 = I - W/2, which manif switches on the ANGLE^2 = 4 y: for y in (2.5e-11, 1e-10] the Log is the
+  // small-angle one and V^-1 keeps its W^2 term (t2 of the series c is 4 y to 1e-10 relative)
+  if (t2 <= TOLG_EPS) cl = 0.0;
   if (q.w < 0.0) c = -c;                  // q and -q are the same rotation: take the w > 0 representative
   w = v3(c * q.x, c * q.y, c * q.z);
   v = ljacinv_apply(w, cl, X.t);
