@@ -326,7 +326,8 @@ int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, double* d_ecc
  * tolg_create, tolg_solve_begin and tolg_solve_begin_warm clear it; so does tolg_eval_knot (it overwrites the nominal
  * trajectory).  tolg_rollout (writes the candidate arrays only), tolg_expected_change, tolg_set_al, tolg_al_update,
  * tolg_set_refs, tolg_set_ref_windows, tolg_set_weights, tolg_set_al_obstacles, tolg_al_update_state, tolg_mpc_advance,
- * tolg_policy_covariance and tolg_policy_value leave it; the calls that read it use the
+ * tolg_policy_covariance, tolg_policy_value, tolg_policy_rollout_limited and tolg_mpc_advance_limited leave it; the calls that
+ * read it use the
  * references and weights set when they run.
  * Both calls return TOLG_E_ARG when no policy is held, during a solve in flight, for a B other than the held batch's, when
  * references or weights per trajectory are set for another B, and (tolg_policy_rollout) for S < 1.  Neither modifies
@@ -365,6 +366,50 @@ int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const double* d_d
 int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, double* d_x_next_q, double* d_x_next_xi,
                      double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl,
                      void* stream);
+
+/* The two closed loops under an actuator box, and the clearance of the rollouts from the keep-out spheres the handle holds: the
+ * check of the margins tolg_policy_covariance supplies to first order (a box tightened by the input variance the feedback
+ * spends, radii inflated by the position covariance).  A real actuator clips, and a clipped loop is no longer the linear one
+ * the covariance describes.  The box is an argument of each call and never held by the handle (tolg_set_al's box is the
+ * planner's and is not read here).  Everything not named below is the rule of tolg_policy_rollout / tolg_mpc_advance: the sample
+ * definition, the noise convention, references and weights per trajectory, the plant rules of tolg_set_plant, the status, NULL
+ * outputs costing nothing, the TOLG_E_ARG conditions of tolg_solve_gains, the held policy left alone (repeated calls give the
+ * same bits; a sample's bits depend on neither S nor the other samples).
+ *
+ * tolg_policy_rollout_limited: the commanded input is u~_i = u*_i + K_i e_i, the applied one
+ *   u^_i[a] = u~ < lb ? lb : (u~ > ub ? ub : u~)   (not fmin / fmax: a NaN command stays NaN and TOLG_ST_NONFINITE shows it)
+ * with trajectory b's box lb = d_u_lb[b], ub = d_u_ub[b].  u^_i is what the dynamics step on, what the stage cost is evaluated
+ * at and what d_us holds.  -inf / +inf mean no limit on that input; the library does not read the box on the host, lb <= ub
+ * is the caller's promise; for the SO3 family the box rows 3..5 must contain 0 (those inputs are zero).  J stays the tracking
+ * cost alone.
+ *   in : d_dx0, d_w as tolg_policy_rollout; d_u_lb, d_u_ub [B][m] each, or both NULL: no clamp, the call is then the clearance
+ *        report alone
+ *   out: d_J, d_status, d_xs_q, d_xs_xi, d_us as tolg_policy_rollout;
+ *        d_n_sat [B][S]       the number of pairs (i, a) with u^ != u~ (a command outside the box; a NaN command is not one)
+ *        d_u_excess [B][S]    max_{i,a} max(lb - u~, u~ - ub, 0): the margin the box would have needed (0 inside it; NaN
+ *                             distances are passed over)
+ *        d_clear [B][S]       min_{i = 0..N, k < K} (|t^_i - c_ik| - r_ik) over the spheres attached to the handle, the static
+ *                             form with one geometry for every knot, the moving form with knot i's own; negative: penetration
+ *                             (+inf if no distance is a number)
+ *        d_clear_knot [B][S]  the first knot that attains the minimum (strict <, knots ascending, spheres ascending)
+ *        every output may be NULL.
+ * TOLG_E_ARG: the conditions of tolg_policy_rollout; exactly one NULL bound; a non-NULL d_clear or d_clear_knot with no spheres
+ * attached (spheres attached for another B refuse every batch call, this one included).
+ * Cost on an MI355X: see INTEGRATION.md 3l (the clamp is 2 m compare-selects per knot on a chain of over a microsecond per
+ * knot; the clearance adds 4 K loads and a square root per knot).
+ *
+ * tolg_mpc_advance_limited: tolg_mpc_advance with the plant's input clipped: d_u_applied = clamp(u*_0) by trajectory b's box;
+ * x_next and xs_warm[0] step with it, on the plant row where one is set; d_J_cl[b] += l(x*_0, u_applied); d_n_sat[b] (may be
+ * NULL) counts the inputs of this step the box moved.  The warm tail xs_warm[N] and us_warm are tolg_mpc_advance's: the model
+ * and the unclamped shift (the planner stays unconstrained, only the plant clips).
+ * TOLG_E_ARG: the conditions of tolg_mpc_advance; a NULL bound (tolg_mpc_advance is the unclamped form). */
+int tolg_policy_rollout_limited(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w,
+                                const double* d_u_lb, const double* d_u_ub, double* d_J, int32_t* d_status, double* d_xs_q,
+                                double* d_xs_xi, double* d_us, int32_t* d_n_sat, double* d_u_excess, double* d_clear,
+                                int32_t* d_clear_knot, void* stream);
+int tolg_mpc_advance_limited(tolg_handle_t h, int32_t B, const double* d_w, const double* d_u_lb, const double* d_u_ub,
+                             double* d_x_next_q, double* d_x_next_xi, double* d_u_applied, double* d_xs_q_warm,
+                             double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl, int32_t* d_n_sat, void* stream);
 
 /* tolg_policy_covariance: the closed-loop covariance of the held policy to first order ("LinCov"), the analytic companion of
  * tolg_policy_rollout's sampling.  In the coordinates of tolg_policy_rollout and of K, e_i = [Log(q*_i^-1 q^_i); xi^_i - xi*_i]

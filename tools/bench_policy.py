@@ -2,7 +2,7 @@
 solved 4096 x 200 SE3 tracking batch, J and status only.
 
 usage: python tools/bench_policy.py [--B 4096] [--N 200] [--S 1,16,64] [--rounds 7] [--iters 20] [--layouts samples,traj]
-                                    [--out FILE.json]
+                                    [--limits] [--out FILE.json]
 
 One process.  The batch is solved once, untimed (multiple shooting, accept-always, 20 iterations), once per sample order of
 k_policy_rollout: `samples` (the default order, the samples of one trajectory side by side in a wavefront) and `traj`
@@ -11,7 +11,12 @@ k_policy_rollout: `samples` (the default order, the samples of one trajectory si
 alternation: `iters` back-to-back calls between two events, through the C ABI (no host-side input checks).  Reported per
 pair: the median ms per call over the rounds, min and max, closed-loop knot steps per second (B S N per call), and the HBM
 bytes the call has to move at least (inputs, outputs, and the nominal data -- gains, controls, states: 97 doubles per knot
-and trajectory -- read once per wavefront that needs it: ceil(S / 16) times in `samples` order, S times in `traj` order)."""
+and trajectory -- read once per wavefront that needs it: ceil(S / 16) times in `samples` order, S times in `traj` order).
+
+--limits: instead, per S and in the first layout, tolg_policy_rollout and tolg_policy_rollout_limited back to back in the same
+alternating rounds: `unlimited` (tolg_policy_rollout), `box` (the box alone: the input range of every trajectory's unperturbed
+sample, which the perturbed ones leave; n_sat and u_excess written) and `box+clearance` (the box and the clearance from K = 8 static keep-out
+spheres per trajectory, placed about its nominal path; clearance and its knot written too).  J and status in all three."""
 import argparse
 import ctypes as C
 import os
@@ -26,6 +31,7 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     add_common_args(ap, "B", "N", "S", "rounds", "iters")
     ap.add_argument("--layouts", default="samples,traj")
+    ap.add_argument("--limits", action="store_true", help="time tolg_policy_rollout_limited beside tolg_policy_rollout")
     add_common_args(ap, "out")
     a = ap.parse_args(argv)
     a.S = [int(s) for s in a.S.split(",")]
@@ -78,6 +84,8 @@ def main(argv=None):
         dx0, w, J, st = inputs[S]
         return s.lib.tolg_policy_rollout(s._h, B, S, p(dx0), p(w), p(J), p(st), None, None, None, s._stream())
 
+    if a.limits:
+        return limits(a, solvers[a.layouts[0]], a.layouts[0], inputs, p)
     names = [(layout, S) for S in a.S for layout in a.layouts] + ["rollout"]
     times = event_rounds(names, call, a.rounds, a.iters)
     rows = []
@@ -96,6 +104,68 @@ def main(argv=None):
         rows.append(row)
         print_row(row)
     res = dict(B=B, N=N, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(dev), rows=rows)
+    emit(res, a.out)
+    return res
+
+
+LIMIT_FORMS = ("unlimited", "box", "box+clearance")
+LIMIT_K = 8
+
+
+def limit_spheres(t, K=LIMIT_K):
+    """K static spheres per trajectory about its nominal positions t [B, N+1, 3]: centred 0.5 beside K knots spread over the
+    path, radius 0.45 -- the nominal passes 0.05 clear of each, a perturbed sample may not.  [B, K, 4]."""
+    import torch
+    B, N1 = t.shape[:2]
+    knots = torch.linspace(0, N1 - 1, K + 2, device=t.device).long()[1:-1]
+    sp = torch.empty(B, K, 4, dtype=t.dtype, device=t.device)
+    sp[:, :, :3] = t[:, knots]
+    sp[:, :, 2] += 0.5
+    sp[:, :, 3] = 0.45
+    return sp
+
+
+def limits(a, s, layout, inputs, p):
+    import torch
+    B, N = a.B, a.N
+    f64 = dict(dtype=torch.float64, device=s.device)
+    nom = s.policy_rollout(S=1, trajectories=True)  # the held nominal: the unperturbed sample
+    lb, ub = nom.us[:, 0].amin(dim=1).contiguous(), nom.us[:, 0].amax(dim=1).contiguous()
+    s.set_al_obstacles(limit_spheres(nom.xs_q[:, 0, :, :3, 3]))
+    outs = {S: (torch.empty(B, S, dtype=torch.int32, device=s.device), torch.empty(B, S, **f64), torch.empty(B, S, **f64),
+                torch.empty(B, S, dtype=torch.int32, device=s.device)) for S in a.S}
+
+    def call(name):
+        S, form = name
+        dx0, w, J, st = inputs[S]
+        if form == "unlimited":
+            return s.lib.tolg_policy_rollout(s._h, B, S, p(dx0), p(w), p(J), p(st), None, None, None, s._stream())
+        ns, ex, cl, ck = outs[S]
+        clear = (p(cl), p(ck)) if form == "box+clearance" else (None, None)
+        return s.lib.tolg_policy_rollout_limited(s._h, B, S, p(dx0), p(w), p(lb), p(ub), p(J), p(st), None, None, None, p(ns),
+                                                 p(ex), *clear, s._stream())
+
+    names = [(S, form) for S in a.S for form in LIMIT_FORMS]
+    times = event_rounds(names, call, a.rounds, a.iters)
+    rows = []
+    for S in a.S:
+        base = stats_row(times[(S, "unlimited")])
+        for form in LIMIT_FORMS:
+            row = dict(kernel="tolg_policy_rollout" if form == "unlimited" else "tolg_policy_rollout_limited", form=form,
+                       layout=layout, S=S, **stats_row(times[(S, form)]))
+            row.update(steps_per_s=B * S * N / (row["ms_median"] * 1e-3), vs_unlimited=row["ms_median"] / base["ms_median"] - 1,
+                       unlimited_spread=(base["ms_max"] - base["ms_min"]) / base["ms_median"])
+            if form != "unlimited":
+                call((S, form))
+                torch.cuda.synchronize()
+                ns, ex, cl, ck = outs[S]
+                row.update(saturated_samples=int((ns > 0).sum().item()), status_ok=int((inputs[S][3] == 0).sum().item()))
+                if form == "box+clearance":
+                    row.update(K=LIMIT_K, penetrating_samples=int((cl < 0).sum().item()))
+            rows.append(row)
+            print_row(row)
+    s.set_al_obstacles(None)
+    res = dict(B=B, N=N, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(s.device), rows=rows)
     emit(res, a.out)
     return res
 

@@ -89,6 +89,12 @@ class PolicyRollout:
     xs_q: Optional[torch.Tensor] = None   # [B, S, N+1, 4, 4] (trajectories=True)
     xs_xi: Optional[torch.Tensor] = None  # [B, S, N+1, 6]
     us: Optional[torch.Tensor] = None     # [B, S, N, m]
+    # policy_rollout(u_lb=, u_ub=): the applied inputs that differ from the commanded ones, and the margin the box lacked
+    n_sat: Optional[torch.Tensor] = None           # [B, S] int32
+    u_excess: Optional[torch.Tensor] = None        # [B, S]
+    # policy_rollout(clearance=True): min over knots and spheres of |t - c| - r, and the first knot that attains it
+    clearance: Optional[torch.Tensor] = None       # [B, S]
+    clearance_knot: Optional[torch.Tensor] = None  # [B, S] int32
 
 
 @dataclass
@@ -148,6 +154,34 @@ class MPCResult:
     J: torch.Tensor        # [B] closed-loop cost: the sum of the stage costs l(x_t, u_t) against each step's window
     iters: torch.Tensor    # [B, steps] int32: iterations of each step's solve
     status: torch.Tensor   # [B, steps] int32: its status
+    n_sat: Optional[torch.Tensor] = None  # [B, steps] int32 (mpc(u_lb=, u_ub=)): the inputs of each step the box moved
+
+
+def check_box(u_lb, u_ub, B, m, so3=False):
+    """An actuator box checked on the host: u_lb, u_ub of shape [m] (every trajectory the same) or [B, m]; -inf / +inf mean
+    no limit, NaN is refused, and lb <= ub must hold in every entry; ValueError otherwise, before anything reaches the device.
+    so3: the problem is of the SO3 family (m = 6 with inputs 3..5 unused and zero) and the bounds may also be [3] or [B, 3], the
+    unused rows then filled with -inf / +inf.  Returns (lb, ub) as float64 [B, m] numpy arrays."""
+    out = []
+    for name, a, fill in (("u_lb", u_lb, -np.inf), ("u_ub", u_ub, np.inf)):
+        if a is None:
+            raise ValueError("u_lb and u_ub come together: %s is missing" % name)
+        a = np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+        sizes = (m, 3) if so3 else (m,)
+        if a.ndim not in (1, 2) or a.shape[-1] not in sizes or (a.ndim == 2 and a.shape[0] != B):
+            raise ValueError("%s has shape %s, expected (%s) or (%d, %s)" % (name, tuple(a.shape), " or ".join(map(str, sizes)),
+                                                                          B, " or ".join(map(str, sizes))))
+        if np.isnan(a).any():
+            raise ValueError("%s must not hold NaN (-inf / +inf mean no limit)" % name)
+        a = np.broadcast_to(a, (B, a.shape[-1]))
+        if a.shape[-1] != m:
+            a = np.concatenate([a, np.full((B, m - a.shape[-1]), fill)], axis=1)
+        out.append(np.ascontiguousarray(a))
+    if np.any(out[0] > out[1]):
+        raise ValueError("u_lb must not exceed u_ub")
+    if so3 and (np.any(out[0][:, 3:] > 0.0) or np.any(out[1][:, 3:] < 0.0)):
+        raise ValueError("inputs 3..5 of the %s are unused and zero: their bounds must contain 0" % "SO3 family")
+    return out[0], out[1]
 
 
 def inflate_obstacles(obstacles, xs_q, pos_cov, kappa):
@@ -899,15 +933,32 @@ class BatchedTrackingILQR:
             return None
         return self._set_plant(B, plant)
 
-    def policy_rollout(self, dx0=None, noise=None, S=None, trajectories=False, plant_J=None, plant_pend=None) -> PolicyRollout:
+    def _box(self, B, u_lb, u_ub):
+        """(lb, ub) [B, m] on the device from check_box, or None when neither bound is given."""
+        if u_lb is None and u_ub is None:
+            return None
+        lb, ub = check_box(u_lb, u_ub, B, self.m, so3=self.problem.kind in ("so3", "pendulum3d"))
+        return self._dev(lb, (B, self.m)), self._dev(ub, (B, self.m))
+
+    def policy_rollout(self, dx0=None, noise=None, S=None, trajectories=False, plant_J=None, plant_pend=None, u_lb=None,
+                       u_ub=None, clearance=False) -> PolicyRollout:
         """S closed-loop rollouts per trajectory of the held policy u = u*_i + K_i (x (-) x*_i) with exact dynamics
         (tolg_policy_rollout).  dx0 [B, S, 12]: start perturbation in the error coordinates of K (pose x*_0 Exp(dx0[:6]),
         twist xi*_0 + dx0[6:]); noise [B, S, N, 6]: added to the twist behind every step.  Either may be None (zero); S is
         taken from them, or given when both are None.  J [B, S] is the tracking cost with the references and weights of the
         held solve (no augmented-Lagrangian terms).  trajectories=True also returns xs_q, xs_xi, us.
         plant_J / plant_pend: the plant the samples are stepped with (model mismatch, tolg_set_plant; None: the model), one per
-        sample [B, S, 6, 6] or one per trajectory [B, 6, 6] (see _check_plant).  The cost stays the model's."""
+        sample [B, S, 6, 6] or one per trajectory [B, 6, 6] (see _check_plant).  The cost stays the model's.
+        u_lb / u_ub [m] or [B, m] (check_box; both or neither): the actuator's box -- the commanded u*_i + K_i e_i is clamped
+        to it before the dynamics step, J and us take the clamped input (tolg_policy_rollout_limited); the result then carries
+        n_sat [B, S], how many inputs of the sample the box moved, and u_excess [B, S], the largest distance by which a command
+        left it.  clearance=True: the result carries clearance [B, S], min over knots and spheres of |t - c| - r for the
+        keep-out spheres attached by set_al_obstacles (negative: the sample entered one), and clearance_knot, the first knot
+        that attains it; ValueError when none are attached.  With none of the three the call is tolg_policy_rollout."""
         B = self._held_B()
+        if clearance and self._obs is None:
+            raise ValueError("clearance=True needs keep-out spheres: attach them with set_al_obstacles")
+        box = self._box(B, u_lb, u_ub)
         shapes = []
         if dx0 is not None:
             dx0 = _checked("dx0", dx0, (B, None, 12), finite=True)
@@ -935,11 +986,24 @@ class BatchedTrackingILQR:
             r.xs_q = torch.empty(B, S, self.N + 1, 4, 4, **f64)
             r.xs_xi = torch.empty(B, S, self.N + 1, 6, **f64)
             r.us = torch.empty(B, S, self.N, self.m, **f64)
+        limited = box is not None or clearance
+        if box is not None:
+            r.n_sat = torch.empty(B, S, dtype=torch.int32, device=self.device)
+            r.u_excess = torch.empty(B, S, **f64)
+        if clearance:
+            r.clearance = torch.empty(B, S, **f64)
+            r.clearance_knot = torch.empty(B, S, dtype=torch.int32, device=self.device)
         d_plant = self._use_plant(B, plant)
         try:
-            self._hold((d_dx0, d_w, d_plant))
-            self._call("tolg_policy_rollout", B, S, _ptr(d_dx0), _ptr(d_w), _ptr(r.J), _ptr(r.status), _ptr(r.xs_q),
-                       _ptr(r.xs_xi), _ptr(r.us))
+            self._hold((d_dx0, d_w, d_plant, box))
+            if limited:
+                lb, ub = box if box is not None else (None, None)
+                self._call("tolg_policy_rollout_limited", B, S, _ptr(d_dx0), _ptr(d_w), _ptr(lb), _ptr(ub), _ptr(r.J),
+                           _ptr(r.status), _ptr(r.xs_q), _ptr(r.xs_xi), _ptr(r.us), _ptr(r.n_sat), _ptr(r.u_excess),
+                           _ptr(r.clearance), _ptr(r.clearance_knot))
+            else:
+                self._call("tolg_policy_rollout", B, S, _ptr(d_dx0), _ptr(d_w), _ptr(r.J), _ptr(r.status), _ptr(r.xs_q),
+                           _ptr(r.xs_xi), _ptr(r.us))
         finally:
             if plant is not None:
                 self._clear_plant()
@@ -1046,43 +1110,52 @@ class BatchedTrackingILQR:
         self._hold((q, xi, t0_d))
         self._set_ref_windows(B, q, xi, T, t0_d, int(t))
 
-    def mpc_advance(self, w=None, J_cl=None, plant_J=None, plant_pend=None):
+    def mpc_advance(self, w=None, J_cl=None, plant_J=None, plant_pend=None, u_lb=None, u_ub=None):
         """One receding-horizon step on the held policy (tolg_mpc_advance): x_next = f(x*_0, u*_0) + [0; w] with the exact
         dynamics, u = u*_0, and the warm start of the next step (xs_q / xs_xi [B, N+1, ...], us [B, N, m]: the solution
         shifted by one knot, x_next in front, the tail propagated with the last input).  w [B, 6] (None: 0) is added to the
         twist.  J_cl (a float64 device tensor [B], optional) is accumulated with the stage cost l(x*_0, u*_0) at knot 0.
         plant_J [B, 6, 6] / plant_pend [B, 2]: the plant x_next is stepped with (model mismatch, tolg_set_plant; None: the
         model); the warm tail stays the model's prediction, u and J_cl are unchanged.
+        u_lb / u_ub [m] or [B, m] (check_box; both or neither): the actuator's box (tolg_mpc_advance_limited) -- u is
+        clamp(u*_0), x_next and xs_q[:, 0] step with it, J_cl takes l(x*_0, u); the rest of the warm start is the unclamped
+        one, and the dict also holds n_sat [B] int32, the inputs the box moved.
         Returns a dict of device tensors: x_next_q [B, 4, 4], x_next_xi, u [B, m], xs_q, xs_xi, us, J_cl."""
         B = self._held_B()
+        box = self._box(B, u_lb, u_ub)
         d_w = None if w is None else self._dev(_checked("w", w, (B, 6), finite=True), (B, 6))
         if J_cl is not None and (not isinstance(J_cl, torch.Tensor) or J_cl.dtype != torch.float64 or
                                  tuple(J_cl.shape) != (B,) or J_cl.device != self.device or not J_cl.is_contiguous()):
             raise ValueError("J_cl must be a contiguous float64 tensor of shape (%d,) on %s" % (B, self.device))
         plant = self._check_plant(B, plant_J, plant_pend, per_sample=False)
-        r = self._advance_out(B, J_cl)
+        r = self._advance_out(B, J_cl, limited=box is not None)
         d_plant = self._use_plant(B, plant)
         try:
-            self._hold((d_w, d_plant))
-            self._advance(B, d_w, r)
+            self._hold((d_w, d_plant, box))
+            self._advance(B, d_w, r, box)
         finally:
             if plant is not None:
                 self._clear_plant()
         return r
 
-    def _advance_out(self, B, J_cl):
+    def _advance_out(self, B, J_cl, limited=False):
         f64 = dict(dtype=torch.float64, device=self.device)
+        more = dict(n_sat=torch.empty(B, dtype=torch.int32, device=self.device)) if limited else {}
         return dict(x_next_q=torch.empty(B, 4, 4, **f64), x_next_xi=torch.empty(B, 6, **f64), u=torch.empty(B, self.m, **f64),
                     xs_q=torch.empty(B, self.N + 1, 4, 4, **f64), xs_xi=torch.empty(B, self.N + 1, 6, **f64),
-                    us=torch.empty(B, self.N, self.m, **f64), J_cl=J_cl)
+                    us=torch.empty(B, self.N, self.m, **f64), J_cl=J_cl, **more)
 
-    def _advance(self, B, d_w, r):
-        self._call("tolg_mpc_advance", B, _ptr(d_w), *(_ptr(r[k]) for k in ("x_next_q", "x_next_xi", "u", "xs_q", "xs_xi", "us",
-                                                                           "J_cl")))
+    def _advance(self, B, d_w, r, box=None):
+        out = tuple(_ptr(r[k]) for k in ("x_next_q", "x_next_xi", "u", "xs_q", "xs_xi", "us", "J_cl"))
+        if box is None:
+            self._call("tolg_mpc_advance", B, _ptr(d_w), *out)
+        else:
+            self._call("tolg_mpc_advance_limited", B, _ptr(d_w), _ptr(box[0]), _ptr(box[1]), *out, _ptr(r["n_sat"]))
 
     def mpc(self, x0_q, x0_xi, path_q, path_xi, steps, us_init=None, t0=None, iters_per_step=5, first_iters=50,
             warm="states", noise=None, mode="ms", line_search=False, rollout="nonlinear", tol_grad_norm=1e-6, tol_d_norm=1e-6,
-            check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None, plant_J=None, plant_pend=None) -> MPCResult:
+            check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None, plant_J=None, plant_pend=None, u_lb=None,
+            u_ub=None) -> MPCResult:
         """Receding-horizon MPC: `steps` closed-loop steps of B trajectories, each tracking its own path from its own phase.
         Step t: windows min(t0[b] + t + i, T) of the paths (tolg_set_ref_windows), a solve of first_iters (t = 0) or
         iters_per_step iterations, then tolg_mpc_advance applies u*_0, steps the plant with the exact dynamics and adds the
@@ -1093,7 +1166,9 @@ class BatchedTrackingILQR:
         iterations with no host read in the whole loop; > 0 stops a step's solve early (solve_iterate_until).  Q / P / R:
         weights per trajectory as for fit_batch.  on_step(t, FitResult) is called behind every step's solve (before the
         plant step; the FitResult carries histories then).  plant_J [B, 6, 6] / plant_pend [B, 2]: the plant every step's
-        x_next is stepped with (model mismatch, as mpc_advance; None: the model); the solves plan on the model.  Not with an
+        x_next is stepped with (model mismatch, as mpc_advance; None: the model); the solves plan on the model.  u_lb / u_ub [m] or
+        [B, m]: the actuator's box (as mpc_advance: every step applies clamp(u*_0); the planner stays unconstrained, only the
+        plant clips), the result then carries n_sat [B, steps].  Not with an
         augmented-Lagrangian constraint attached.  The handle is left on the shared reference and weights, without a plant.
         x0_q [B, 4, 4], x0_xi [B, 6], path_q [B, T+1, 4, 4], path_xi [B, T+1, 6]."""
         if self._al is not None:
@@ -1121,6 +1196,7 @@ class BatchedTrackingILQR:
         t0_d = self._check_t0(B, t0)
         b = self._stage(x0_q, x0_xi, us_init, weights=(Q, P, R))
         plant = self._check_plant(B, plant_J, plant_pend, per_sample=False)
+        box = self._box(B, u_lb, u_ub)
         if noise is not None:
             noise = _checked("noise", noise, (B, steps, 6), finite=True)
             noise = self._dev(np.ascontiguousarray(noise.transpose(1, 0, 2)), (steps, B, 6))  # step t: one contiguous [B, 6]
@@ -1132,12 +1208,14 @@ class BatchedTrackingILQR:
         res.xs_q[:, 0] = b.x_q.reshape(B, 4, 4)
         res.xs_xi[:, 0] = b.x_xi
         # the plant state and the warm start: written by tolg_mpc_advance, read by the next begin (stream-ordered)
-        adv = self._advance_out(B, res.J)
+        adv = self._advance_out(B, res.J, limited=box is not None)
+        if box is not None:
+            res.n_sat = torch.empty(B, steps, dtype=torch.int32, device=self.device)
         x_q, x_xi, us = b.x_q, b.x_xi, b.us
         try:
             # the plant survives the solves of the loop (tolg_set_plant): set once, detached behind it
             d_plant = self._use_plant(B, plant)
-            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant))
+            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box))
             self._use_pt(B, None, b.wts)
             for t in range(steps):
                 self._set_ref_windows(B, pq, pxi, T, t0_d, t)
@@ -1160,7 +1238,9 @@ class BatchedTrackingILQR:
                 res.status[:, t] = out.status
                 if on_step is not None:
                     on_step(t, out)
-                self._advance(B, None if noise is None else noise[t], adv)
+                self._advance(B, None if noise is None else noise[t], adv, box)
+                if box is not None:
+                    res.n_sat[:, t] = adv["n_sat"]
                 res.us[:, t] = adv["u"]
                 res.xs_q[:, t + 1] = adv["x_next_q"]
                 res.xs_xi[:, t + 1] = adv["x_next_xi"]
