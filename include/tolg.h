@@ -276,6 +276,39 @@ int tolg_set_al_obstacles_moving(tolg_handle_t h, int32_t B, int32_t K, const do
 int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu, double mu_scale,
                          double mu_max, double tol_constr, double* d_maxviol, int32_t* d_al_converged, void* stream);
 
+/* Constrained receding-horizon MPC: the multipliers follow the window.  tolg_al_mpc_step is the outer update of one MPC step
+ * over everything attached to the handle, without tolg_al_update_state's sticky d_al_converged -- in a closed loop every step is
+ * a new problem -- followed, with shift == 1, by a one-knot shift of both multiplier sets, in place in the caller-owned buffers
+ * the handle points at: the warm start of the duals, as tolg_mpc_advance's shift is that of the states and controls.
+ * The rows g of trajectory b are tolg_al_update_state's: the box rows [lb - u_i; u_i - ub], i < N, and the sphere rows
+ * r_ik^2 - |t_i - c_ik|^2, i <= N, of whichever geometry form is attached when the call runs.  Then
+ *   mv = max g        (the box contributes its terminal zero rows: mv starts at 0 with a box, at -inf without; NaN is passed over)
+ *   d_maxviol[b] = mv (d_maxviol may be NULL)
+ *   mu_new = mv < tol_constr ? mu[b] : min(mu_scale mu[b], mu_max)
+ *   every row, whatever mv is:  lambda' = max(0, lambda + I_mu g),  I_mu' = (g < 0 and lambda' == 0) ? 0 : mu_new
+ *   d_mu[b] = mu_new
+ * so a satisfied problem still lets its multipliers relax and only mu stops growing.  With shift == 1
+ *   box multipliers    [B][N][2m]:  row i takes row' i+1, i = 0..N-2, row N-1 keeps row' N-1;
+ *   sphere multipliers [B][N+1][K]: row i takes row' i+1, i = 0..N-1, row N keeps row' N
+ * (the last knot held, as tolg_set_ref_windows and us_warm hold theirs).  d_us may be NULL without a box, d_xs_q without
+ * spheres.  The held policy is left alone: tolg_mpc_advance behind this call gives the bits it gave before it.
+ * tolg_al_update and tolg_al_update_state are unchanged.  One workgroup per trajectory; cost: INTEGRATION.md 3m.
+ * TOLG_E_ARG: nothing attached, B < 1 or B > max_batch, B other than the spheres' batch, a NULL input the attached constraints
+ * need, a NULL d_mu, shift other than 0 or 1, a solve in flight. */
+int tolg_al_mpc_step(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu, double mu_scale,
+                     double mu_max, double tol_constr, double* d_maxviol, int32_t shift, void* stream);
+
+/* tolg_set_al_obstacle_windows: the moving spheres of step t gathered on the device from world-time paths, d_path_obs
+ * [B][T+1][K][4] = (cx, cy, cz, r) of trajectory b's spheres at world knot s: knot i of the window takes world knot
+ * min(t0[b] + t + i, T) (tolg_set_ref_windows' rule; d_t0 NULL: 0; any T >= 1, T < N included).  Afterwards the handle is
+ * exactly as after tolg_set_al_obstacles_moving with the gathered [B][N+1][K][4] array: the same packed bytes
+ * (tolg_obstacles_moving_bytes), the same multipliers, the same rules for B.  d_path_obs = NULL detaches.  The held policy is
+ * left alone.
+ * TOLG_E_ARG: those of tolg_set_al_obstacles_moving, T < 1, t < 0. */
+int tolg_set_al_obstacle_windows(tolg_handle_t h, int32_t B, int32_t K, const double* d_path_obs, int32_t T,
+                                 const int32_t* d_t0, int32_t t, const double* d_lambda, const double* d_imu, void* d_packed,
+                                 size_t packed_bytes, void* stream);
+
 /* One linearisation + backward pass on given trajectories (unit-parity entry point): replaces
  * iLQR_Tracking_SE3_MS._linearization + _backward_pass + _gradient_wrt_control
  * (traoptlibrary/traopt_controller.py:2823-3093; ms = 0: the SS variants :2098-2349).

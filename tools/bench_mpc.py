@@ -3,6 +3,7 @@ against warm controls.
 
 usage: python tools/bench_mpc.py [--B 4096] [--N 200,50] [--iters 0,1,3,5] [--steps 20] [--rounds 5]
                                  [--tol-steps 10] [--tol-rounds 2] [--max-iters 30] [--out FILE.json]
+       python tools/bench_mpc.py --constrained [--B 4096] [--N 200] [--K 4] [--iters 5] [--steps 20] [--rounds 5]
 
 One process, se3_mpc's workload (every trajectory its own path and phase, twist disturbances behind every step), multiple
 shooting, accept-always.
@@ -15,7 +16,13 @@ shooting, accept-always.
 - Iterations per step: `tol-steps` steps under tolerances (tol_grad_norm = tol_d_norm = 1e-6, check_every = 1, at most
   `max-iters` iterations a step, the first step 50), warm="states" and warm="controls" on the same paths and disturbances,
   alternated `tol-rounds` times.  Reported: mean iterations per step over steps 1.. (step 0 is cold for both), its maximum,
-  the fraction of (trajectory, step) solves that stopped below the cap, and ms per step."""
+  the fraction of (trajectory, step) solves that stopped below the cap, and ms per step.
+- --constrained: se3_mpc_obstacles' workload instead.  For every N and k the unconstrained loop and the loops with the planner's
+  box (the 90th percentile of the unconstrained loop's inputs), with K spheres per trajectory on world-time paths (a device
+  tensor, as the reference paths), and with both (first_al_iters = al_iters_per_step = 1: the same iteration count) alternate
+  round after round in one process; reported as above, with each loop's solves of status OK, its last step's largest violation
+  and its least clearance.  Then the step kernel alone: tolg_al_mpc_step (shift = 1) on the last
+  plan with both multiplier sets attached, `steps` calls between two device synchronisations."""
 import argparse
 import os
 import statistics
@@ -37,6 +44,8 @@ def parse_args(argv=None):
     ap.add_argument("--tol-steps", type=int, default=10)
     ap.add_argument("--tol-rounds", type=int, default=2)
     ap.add_argument("--max-iters", type=int, default=30)
+    ap.add_argument("--constrained", action="store_true")
+    ap.add_argument("--K", type=int, default=4)
     add_common_args(ap, "out")
     a = ap.parse_args(argv)
     a.N = [int(x) for x in a.N.split(",")]
@@ -46,8 +55,78 @@ def parse_args(argv=None):
     return a
 
 
+def constrained(a):
+    """The constrained loop beside the unconstrained one (--constrained)"""
+    import numpy as np
+    import torch
+    from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
+
+    B, zero, rows = a.B, dict(tol_grad_norm=0.0, tol_d_norm=0.0), []
+    for N in a.N:
+        prob, q, xi, pq, px, t0, noise, obs, mov = workloads.se3_mpc_obstacles(B, a.steps, N=N, K=a.K)
+        s = BatchedTrackingILQR(prob, B)
+        dev = lambda x: torch.as_tensor(x, device=s.device)  # noqa: E731
+        inp = dict(x0_q=q, x0_xi=xi, path_q=dev(pq), path_xi=dev(px), t0=t0, noise=noise, steps=a.steps, warm="states",
+                   check_every=0, **zero)
+        mov_d = dev(mov)
+        for k in a.iters:
+            free = s.mpc(first_iters=k, iters_per_step=k, **inp)
+            u = np.abs(free.us.cpu().numpy())
+            lim = np.percentile(u[np.isfinite(u).all(axis=(1, 2))].reshape(-1, prob.m), 90, axis=0)
+            al = dict(first_al_iters=1, al_iters_per_step=1)
+            loops = {"unconstrained": {}, "box": dict(lb=-lim, ub=lim, **al), "spheres": dict(obstacle_paths=mov_d, **al),
+                     "box+spheres": dict(lb=-lim, ub=lim, obstacle_paths=mov_d, **al)}
+            times = {name: [] for name in loops}
+            last = {}
+            for r in range(a.rounds + 1):  # round 0 warms up
+                for name in rotated(list(times), r):
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    last[name] = s.mpc(first_iters=k, iters_per_step=k, **loops[name], **inp)
+                    torch.cuda.synchronize()
+                    if r:
+                        times[name].append((time.perf_counter() - t) * 1e3 / a.steps)
+            for name, res in last.items():
+                st = stats_row(times[name], "ms_per_step")
+                row = dict(part="constrained_step_time", loop=name, N=N, K=a.K, iters_per_step=k, **st,
+                           status_ok=int((res.status == 0).sum().item()), solves=B * a.steps)
+                if res.max_violation is not None:
+                    row.update(max_violation_last_step=float(res.max_violation[:, -1].max().item()), mu_max=float(res.mu.max().item()))
+                if res.clearance is not None:
+                    row.update(min_clearance=float(res.clearance.min().item()))
+                rows.append(row)
+                print_row(row)
+        # the step kernel alone, on a plan and both multiplier sets
+        f64 = dict(dtype=torch.float64, device=s.device)
+        plan = s.fit_batch(q, xi, None, n_iterations=3, check_every=0, **zero)
+        lam, imu = torch.zeros(B, N, 2 * prob.m, **f64), torch.full((B, N, 2 * prob.m), 1e-2, **f64)
+        s.set_al(-lim, lim, lam, imu)
+        s.set_al_obstacle_windows(mov_d, 0, t0=t0, lam=None, imu=torch.full((B, N + 1, a.K), 1e-2, **f64))
+        mu = torch.full((B,), 1e-2, **f64)
+        ms = []
+        for r in range(a.rounds + 1):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(a.steps):
+                s.al_mpc_step(plan.xs_q, plan.us, mu, shift=True)
+            torch.cuda.synchronize()
+            if r:
+                ms.append((time.perf_counter() - t) * 1e3 / a.steps)
+        s.set_al(None)
+        s.set_al_obstacles(None)
+        moved = 8 * B * (2 * 2 * (N * 2 * prob.m + (N + 1) * a.K) + 2 * N * prob.m + 2 * (3 + 4 * a.K) * (N + 1))
+        row = dict(part="al_mpc_step_alone", N=N, K=a.K, **stats_row(ms, "ms_per_call"), bytes_needed=moved)
+        rows.append(row)
+        print_row(row)
+    res = dict(B=B, N=a.N, K=a.K, steps=a.steps, rounds=a.rounds, device=torch.cuda.get_device_name(0), rows=rows)
+    emit(res, a.out)
+    return res
+
+
 def main(argv=None):
     a = parse_args(argv)
+    if a.constrained:
+        return constrained(a)
     import torch
     from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
 

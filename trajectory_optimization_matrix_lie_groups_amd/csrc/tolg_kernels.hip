@@ -5816,21 +5816,54 @@ extern "C" int tolg_set_weights(tolg_handle_t h, int32_t B, const double* d_q_di
   return 0;
 }
 
-// d_obs [B][knots][K][4] = (cx, cy, cz, r) into [knots][4K][Bp]: field f = 4k + c of knot i of trajectory b at (i * 4K + f) * Bp
+// d_obs [B][src_knots][K][4] = (cx, cy, cz, r) into [knots][4K][Bp]: field f = 4k + c of knot i of trajectory b at (i * 4K + f) * Bp
 // + b; padded trajectories b >= B replicate b = B-1.  knots = 1 is the static form (tolg_set_al_obstacles: one [4K][Bp] block
-// for every knot, `stride` 0), knots = N + 1 the per-knot form (tolg_set_al_obstacles_moving: `stride` 4 K Bp).  Thread 0 points
-// the handle's constants at the geometry, its knot stride and the caller's multipliers (stream-ordered before the solves that
-// read them).
-__global__ void k_pack_obstacles_moving(int B, int Bp, int K, int knots, size_t stride, const double* __restrict__ obs,
-                                        const double* lam, const double* imu, double* __restrict__ w, Consts* c) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+// for every knot, `stride` 0), knots = N + 1 the per-knot form (tolg_set_al_obstacles_moving: `stride` 4 K Bp).  Knot i is
+// read from source knot i (t < 0: src_knots = knots), or gathered from a world-time path of src_knots = T + 1 knots
+// (tolg_set_al_obstacle_windows, t >= 0): source knot min(t0[b] + t + i, T), t0 = null: 0 -- k_pack_ref_windows' rule, the
+// same packed bits as the per-knot form on host-sliced windows.  Thread 0 points the handle's constants at the geometry, its
+// knot stride and the caller's multipliers (stream-ordered before the solves that read them).
+__global__ void k_pack_obstacles_moving(int B, int Bp, int K, int knots, size_t stride, const double* __restrict__ obs, int src_knots,
+                                        const int* __restrict__ t0, int t, const double* lam, const double* imu,
+                                        double* __restrict__ w, Consts* c) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t knot = (size_t)4 * K * Bp;
-  if (t == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; c->obs_stride = stride; }
-  if (t >= knot * (size_t)knots) return;
-  const size_t i = t / knot, r = t % knot;
+  if (g == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; c->obs_stride = stride; }
+  if (g >= knot * (size_t)knots) return;
+  const size_t i = g / knot, r = g % knot;
   const int b = (int)(r % Bp), f = (int)(r / Bp);
   const int bs = b < B ? b : B - 1;
-  w[t] = obs[((size_t)bs * knots + i) * 4 * K + f];
+  size_t src = i;
+  if (t >= 0) {
+    long long k = (long long)(t0 ? t0[bs] : 0) + t + (long long)i;
+    src = (size_t)(k < 0 ? 0 : (k > src_knots - 1 ? src_knots - 1 : k));  // a negative phase reads knot 0 (the loads stay inside the path)
+  }
+  w[g] = obs[((size_t)bs * src_knots + src) * 4 * K + f];
+}
+
+// The row arithmetic of the outer updates, stated once for k_al_update_state and k_al_mpc_step: the constraint rows of
+// trajectory b -- box row k of knot i, [lb - u_i; u_i - ub], and sphere k at knot i, r^2 - |t - c|^2, from the packed geometry
+// (geo_stride 0: one block for every knot) -- and the multiplier rule.
+struct AlRows {
+  int b, Bp, N, m, K;
+  const double *xs_q, *us, *lb, *ub, *geo;
+  size_t geo_stride;
+  TOLG_DEV double g_box(int i, int k) const {
+    const double* u = us + ((size_t)b * N + i) * m;
+    return (k < m) ? lb[k] - u[k] : u[k - m] - ub[k - m];
+  }
+  TOLG_DEV double g_sphere(int i, int k) const {
+    const double* x = xs_q + ((size_t)b * (N + 1) + i) * 16;
+    const double* o = geo + (size_t)i * geo_stride + (size_t)(4 * k) * Bp + b;
+    const double dx = x[3] - o[0], dy = x[7] - o[Bp], dz = x[11] - o[2 * (size_t)Bp], r = o[3 * (size_t)Bp];
+    return r * r - (dx * dx + dy * dy + dz * dz);
+  }
+};
+// lambda <- max(0, lambda + I_mu g), I_mu <- 0 where (g < 0 and lambda_new == 0) else mu_new
+TOLG_DEV void al_row_update(double& l, double& im, double g, double mu_new) {
+  const double ln = fmax(0.0, l + im * g);
+  l = ln;
+  im = (g < 0.0 && ln == 0.0) ? 0.0 : mu_new;
 }
 
 // The augmented-Lagrangian outer update (AL_iLQR_Tracking_SE3_MS._al_update_param, traopt_controller.py:3270-3290) and the
@@ -5848,42 +5881,118 @@ __global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const doub
                                   double tol_constr, double* __restrict__ maxviol, int* __restrict__ al_conv) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B || al_conv[b]) return;  // a converged problem keeps its multipliers
-  auto gs = [&](int i, int k) {      // g_k at knot i: r^2 - |t - c|^2
-    const double* x = xs_q + ((size_t)b * (N + 1) + i) * 16;
-    const double* o = geo + (size_t)i * geo_stride + (size_t)(4 * k) * Bp + b;
-    const double dx = x[3] - o[0], dy = x[7] - o[Bp], dz = x[11] - o[2 * (size_t)Bp], r = o[3 * (size_t)Bp];
-    return r * r - (dx * dx + dy * dy + dz * dz);
-  };
+  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride};
   double mv = lb ? 0.0 : -INFINITY;
   if (lb)
-    for (int i = 0; i < N; i++) {
-      const double* u = us + ((size_t)b * N + i) * m;
-      for (int k = 0; k < 2 * m; k++) mv = fmax(mv, (k < m) ? lb[k] - u[k] : u[k - m] - ub[k - m]);
-    }
+    for (int i = 0; i < N; i++)
+      for (int k = 0; k < 2 * m; k++) mv = fmax(mv, R.g_box(i, k));
   if (geo)
     for (int i = 0; i <= N; i++)
-      for (int k = 0; k < K; k++) mv = fmax(mv, gs(i, k));
+      for (int k = 0; k < K; k++) mv = fmax(mv, R.g_sphere(i, k));
   maxviol[b] = mv;
   if (mv < tol_constr) { al_conv[b] = 1; return; }
   const double mu_new = fmin(mu[b] * mu_scale, mu_max);
-  auto upd = [&](double& l, double& im, double g) {
-    const double ln = fmax(0.0, l + im * g);
-    l = ln;
-    im = (g < 0.0 && ln == 0.0) ? 0.0 : mu_new;
-  };
   if (lb)
     for (int i = 0; i < N; i++) {
-      const double* u = us + ((size_t)b * N + i) * m;
       const size_t o = ((size_t)b * N + i) * 2 * m;
-      for (int k = 0; k < 2 * m; k++) upd(lam[o + k], imu[o + k], (k < m) ? lb[k] - u[k] : u[k - m] - ub[k - m]);
+      for (int k = 0; k < 2 * m; k++) al_row_update(lam[o + k], imu[o + k], R.g_box(i, k), mu_new);
     }
   if (geo)
     for (int i = 0; i <= N; i++)
       for (int k = 0; k < K; k++) {
         const size_t o = ((size_t)b * (N + 1) + i) * K + k;
-        upd(olam[o], oimu[o], gs(i, k));
+        al_row_update(olam[o], oimu[o], R.g_sphere(i, k), mu_new);
       }
   mu[b] = mu_new;
+}
+
+// The outer update of a receding-horizon step (tolg_al_mpc_step): k_al_update_state's rows and rule without the sticky
+// al_converged -- every step is a new problem: below tol_constr mu stops growing, the multipliers still relax -- followed by the
+// one-knot shift of both multiplier sets, in place.  One workgroup of AL_STEP_THREADS lanes per trajectory; the lanes run along
+// the contiguous rows of trajectory b ([N][2m], then [N+1][K]) in tiles of AL_STEP_TILE doubles, a pair per lane.
+//   pass 1: mv = max g over every row (the rows' inputs only: controls, positions, geometry), a wave reduction and one over the
+//           group's waves in LDS; mu_new follows from it;
+//   pass 2: g again (the same loads, from cache) with the multipliers, read and written once: al_row_update, then the store at
+//           the shifted place.
+// The shift: updated row i goes to row i - 1, the last row to its own place as well (held), updated row 0 is dropped.  A tile's
+// stores land at most one row below its own loads, on elements this tile or an earlier one has loaded: tiles ascend, and a
+// barrier stands between a tile's loads and its stores.  No size is assumed of N: nothing is staged.
+constexpr int AL_STEP_THREADS = 256, AL_STEP_TILE = 2 * AL_STEP_THREADS;
+
+// two consecutive doubles at p (8-byte aligned): one 16-byte access where p allows it (wave-uniform: the lanes' p differ by
+// multiples of 16 bytes)
+TOLG_DEV double2 al_ld2(const double* p) {
+  if (reinterpret_cast<uintptr_t>(p) & 15) return make_double2(p[0], p[1]);
+  return *reinterpret_cast<const double2*>(p);
+}
+TOLG_DEV void al_st2(double* p, double2 v) {
+  if (reinterpret_cast<uintptr_t>(p) & 15) { p[0] = v.x; p[1] = v.y; }
+  else *reinterpret_cast<double2*>(p) = v;
+}
+
+// max over the group (fmax: NaN is passed over); red holds one double per wave
+TOLG_DEV double al_group_max(double v, double* red) {
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) red[wave] = v;
+  __syncthreads();
+  v = red[0];
+  for (int k = 1; k < AL_STEP_THREADS / 64; k++) v = fmax(v, red[k]);
+  return v;
+}
+
+// One multiplier set of trajectory b in pass 2: n = rows * W doubles at l / im, g(e) the row value of element e.
+template <class G>
+TOLG_DEV void al_step_rows(double* __restrict__ l, double* __restrict__ im, int n, int W, double mu_new, int shift, G g) {
+  for (int base = 0; base < n; base += AL_STEP_TILE) {
+    const int e = base + 2 * (int)threadIdx.x;
+    const int cnt = n - e < 2 ? n - e : 2;  // <= 0: nothing left for this lane
+    double2 lv = make_double2(0.0, 0.0), iv = lv;
+    if (cnt == 2) { lv = al_ld2(l + e); iv = al_ld2(im + e); }
+    else if (cnt == 1) { lv.x = l[e]; iv.x = im[e]; }
+    if (cnt >= 1) al_row_update(lv.x, iv.x, g(e), mu_new);
+    if (cnt == 2) al_row_update(lv.y, iv.y, g(e + 1), mu_new);
+    __syncthreads();  // every load of this tile is done: its stores may land on them
+    if (!shift) {
+      if (cnt == 2) { al_st2(l + e, lv); al_st2(im + e, iv); }
+      else if (cnt == 1) { l[e] = lv.x; im[e] = iv.x; }
+      continue;
+    }
+    // element x goes to x - W (x >= W), and stays as well where it is of the last row (x >= n - W)
+    if (cnt == 2 && e >= W) { al_st2(l + e - W, lv); al_st2(im + e - W, iv); }
+    else {
+      if (cnt >= 1 && e >= W) { l[e - W] = lv.x; im[e - W] = iv.x; }
+      if (cnt == 2 && e + 1 >= W) { l[e + 1 - W] = lv.y; im[e + 1 - W] = iv.y; }
+    }
+    if (cnt == 2 && e >= n - W) { al_st2(l + e, lv); al_st2(im + e, iv); }
+    else {
+      if (cnt >= 1 && e >= n - W) { l[e] = lv.x; im[e] = iv.x; }
+      if (cnt == 2 && e + 1 >= n - W) { l[e + 1] = lv.y; im[e + 1] = iv.y; }
+    }
+  }
+}
+
+__global__ __launch_bounds__(AL_STEP_THREADS) void k_al_mpc_step(
+    int Bp, int N, int m, int K, const double* __restrict__ xs_q, const double* __restrict__ us, const double* __restrict__ lb,
+    const double* __restrict__ ub, double* __restrict__ lam, double* __restrict__ imu, const double* __restrict__ geo,
+    size_t geo_stride, double* __restrict__ olam, double* __restrict__ oimu, double* __restrict__ mu, double mu_scale,
+    double mu_max, double tol_constr, double* __restrict__ maxviol, int shift) {
+  __shared__ double red[AL_STEP_THREADS / 64];
+  const int b = blockIdx.x;
+  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride};
+  const int W = 2 * m, nb = lb ? N * W : 0, no = geo ? (N + 1) * K : 0;
+  const double mu_old = mu[b];
+  double mv = lb ? 0.0 : -INFINITY;
+  for (int e = threadIdx.x; e < nb; e += AL_STEP_THREADS) mv = fmax(mv, R.g_box(e / W, e % W));
+  for (int e = threadIdx.x; e < no; e += AL_STEP_THREADS) mv = fmax(mv, R.g_sphere(e / K, e % K));
+  mv = al_group_max(mv, red);
+  const double mu_new = (mv < tol_constr) ? mu_old : fmin(mu_old * mu_scale, mu_max);
+  if (nb) al_step_rows(lam + (size_t)b * nb, imu + (size_t)b * nb, nb, W, mu_new, shift, [&](int e) { return R.g_box(e / W, e % W); });
+  if (no) al_step_rows(olam + (size_t)b * no, oimu + (size_t)b * no, no, K, mu_new, shift, [&](int e) { return R.g_sphere(e / K, e % K); });
+  if (threadIdx.x == 0) {
+    if (maxviol) maxviol[b] = mv;
+    mu[b] = mu_new;
+  }
 }
 
 static size_t obstacles_bytes_for(const tolg_problem*, int B, int K) { return (size_t)4 * K * (size_t)padded_batch(B) * sizeof(double); }
@@ -5898,8 +6007,11 @@ extern "C" size_t tolg_obstacles_moving_bytes(const tolg_problem* prob, int32_t 
 
 // Both forms (`moving`: d_obs holds a field per knot and the packed size is N + 1 times the static one); d_obs = null detaches
 // through either.  Each replaces the other: one geometry pointer, one stride.
+// The window form (tolg_set_al_obstacle_windows) is the moving one gathered from a path of T + 1 knots at step t >= 0 (the
+// others: t = -1).
 static int set_obstacles(tolg_handle_t h, int B, int K, bool moving, const double* d_obs, const double* d_lambda,
-                         const double* d_imu, void* d_packed, size_t packed_bytes, void* stream) {
+                         const double* d_imu, void* d_packed, size_t packed_bytes, void* stream, int T = 0,
+                         const int32_t* d_t0 = nullptr, int t = -1) {
   if (!h || h->running) return TOLG_E_ARG;
   Held& r = h->pt[H_OBS];
   if (!d_obs) { drop(h, r); return 0; }
@@ -5909,8 +6021,8 @@ static int set_obstacles(tolg_handle_t h, int B, int K, bool moving, const doubl
   const int Bp = padded_batch(B), knots = moving ? h->prob.N + 1 : 1;
   const size_t knot = (size_t)4 * K * Bp;
   hipLaunchKernelGGL(k_pack_obstacles_moving, dim3((unsigned)((knots * knot + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     B, Bp, K, knots, moving ? knot : 0, d_obs, d_lambda, d_imu, static_cast<double*>(d_packed),
-                     const_cast<Consts*>(h->P.c));
+                     B, Bp, K, knots, moving ? knot : 0, d_obs, t >= 0 ? T + 1 : knots, reinterpret_cast<const int*>(d_t0), t,
+                     d_lambda, d_imu, static_cast<double*>(d_packed), const_cast<Consts*>(h->P.c));
   LAUNCH_CHECK();
   h->obs_K = K; h->obs_stride = moving ? knot : 0;
   h->obs_lam = const_cast<double*>(d_lambda); h->obs_imu = const_cast<double*>(d_imu);
@@ -5924,6 +6036,12 @@ extern "C" int tolg_set_al_obstacles(tolg_handle_t h, int32_t B, int32_t K, cons
 extern "C" int tolg_set_al_obstacles_moving(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
                                             const double* d_imu, void* d_packed, size_t packed_bytes, void* stream) {
   return set_obstacles(h, B, K, true, d_obs, d_lambda, d_imu, d_packed, packed_bytes, stream);
+}
+extern "C" int tolg_set_al_obstacle_windows(tolg_handle_t h, int32_t B, int32_t K, const double* d_path_obs, int32_t T,
+                                            const int32_t* d_t0, int32_t t, const double* d_lambda, const double* d_imu,
+                                            void* d_packed, size_t packed_bytes, void* stream) {
+  if (d_path_obs && (T < 1 || t < 0)) return TOLG_E_ARG;
+  return set_obstacles(h, B, K, true, d_path_obs, d_lambda, d_imu, d_packed, packed_bytes, stream, T, d_t0, t);
 }
 
 // the box of the call's own arguments, no geometry (Bp, K = 0: nothing reads them)
@@ -5951,6 +6069,23 @@ extern "C" int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_
                      h->prob.N, h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
                      const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
                      d_maxviol, d_al_converged);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// tolg_al_update_state's conditions, and: not during a solve (the solve reads the multipliers this call moves)
+extern "C" int tolg_al_mpc_step(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu,
+                                double mu_scale, double mu_max, double tol_constr, double* d_maxviol, int32_t shift,
+                                void* stream) {
+  if (!h || h->running || B < 1 || B > h->max_batch || !d_mu || (shift != 0 && shift != 1)) return TOLG_E_ARG;
+  const Held& obs = h->pt[H_OBS];
+  if (!h->al_lb && !obs.p) return TOLG_E_ARG;     // nothing attached to update
+  if (h->al_lb && !d_us) return TOLG_E_ARG;
+  if (obs.p && (B != obs.B || !d_xs_q)) return TOLG_E_ARG;
+  hipLaunchKernelGGL(k_al_mpc_step, dim3(B), dim3(AL_STEP_THREADS), 0, static_cast<hipStream_t>(stream), padded_batch(B), h->prob.N,
+                     h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
+                     const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
+                     d_maxviol, (int)shift);
   LAUNCH_CHECK();
   return 0;
 }

@@ -155,6 +155,11 @@ class MPCResult:
     iters: torch.Tensor    # [B, steps] int32: iterations of each step's solve
     status: torch.Tensor   # [B, steps] int32: its status
     n_sat: Optional[torch.Tensor] = None  # [B, steps] int32 (mpc(u_lb=, u_ub=)): the inputs of each step the box moved
+    # mpc(lb=, ub=, obstacles=, obstacle_paths=): the planner's constraints
+    max_violation: Optional[torch.Tensor] = None  # [B, steps] the largest g of each step's last plan (tolg_al_mpc_step)
+    mu: Optional[torch.Tensor] = None             # [B] the penalty the loop ended with
+    # ... with spheres: min_k |t_s - c_k(s)| - r_k(s) of the realised states at their world knots (negative: inside one)
+    clearance: Optional[torch.Tensor] = None      # [B, steps+1]
 
 
 def check_box(u_lb, u_ub, B, m, so3=False):
@@ -246,7 +251,8 @@ def _checked(name, a, shape, finite=False):
 _POLICY = {"tolg_solve_begin": "clear", "tolg_solve_begin_warm": "clear", "tolg_eval_knot": "clear",
            "tolg_solve_batch": "clear hold", "tolg_linearize_backward": "clear hold", "tolg_solve_end": "hold",
            "tolg_set_al_obstacles": "", "tolg_set_al_obstacles_moving": "",
-           "tolg_al_update_state": ""}  # (the last three leave it: listed for completeness)
+           "tolg_al_update_state": "", "tolg_al_mpc_step": "",
+           "tolg_set_al_obstacle_windows": ""}  # (the last five leave it: listed for completeness)
 # A setter's detach call (BatchedTrackingILQR._detach): its arguments behind the handle with the source pointer null, the
 # stream's place included.  tolg_set_al_obstacles detaches the per-knot form too.
 _DETACH = {"tolg_set_refs": (0, None, None, None, 0, None), "tolg_set_weights": (0, None, None, None, None, 0, None),
@@ -631,6 +637,15 @@ class BatchedTrackingILQR:
         Bl = None if lam is None else int(lam.shape[0])
         B, a = self._check_obstacles(Bl, obstacles)
         K, moving = a.shape[-2], a.ndim == 4
+        lam, imu = self._obs_multipliers(B, K, lam, imu)
+        dest = (self._packed("_obs_mov_buf", self.lib.tolg_obstacles_moving_bytes, K, B=B) if moving else
+                self._packed("_obs_buf", self.lib.tolg_obstacles_bytes, _capi.MAX_OBSTACLES))
+        d = self._dev(a, a.shape)
+        self._obs = (d, lam, imu)  # the handle reads the multipliers in every solve until they are detached
+        self._call("tolg_set_al_obstacles" + ("_moving" if moving else ""), B, K, _ptr(d), _ptr(lam), _ptr(imu), *dest)
+
+    def _obs_multipliers(self, B, K, lam, imu):
+        """The spheres' multipliers lam, imu [B, N+1, K] checked (contiguous float64 on the device; None: zeros), and B."""
         f64 = dict(dtype=torch.float64, device=self.device)
         if lam is None:
             lam = torch.zeros(B, self.N + 1, K, **f64)
@@ -642,11 +657,76 @@ class BatchedTrackingILQR:
             _checked(name, t, (B, self.N + 1, K))
         if not 1 <= B <= self.max_batch:
             raise ValueError("obstacles for B = %d trajectories, expected 1..%d" % (B, self.max_batch))
-        dest = (self._packed("_obs_mov_buf", self.lib.tolg_obstacles_moving_bytes, K, B=B) if moving else
-                self._packed("_obs_buf", self.lib.tolg_obstacles_bytes, _capi.MAX_OBSTACLES))
+        return lam, imu
+
+    def _check_obstacle_paths(self, B, path_obs):
+        """World-time sphere paths [B, T+1, K, 4], rows (cx, cy, cz, r), checked under _check_obstacles' rules (T >= 1 in place of
+        the horizon).  The paths are large (116 MB at 4096 x 220, K = 4): a tensor that is on the solver's device already is
+        checked there -- two reductions and one flag read back -- and never copied through the host; anything else is checked
+        on the host.  B = None takes it from the array.  Returns (B, the paths: that device tensor, or a float64 numpy array)."""
+        if self.problem.kind in ("so3", "pendulum3d"):
+            raise ValueError("keep-out spheres constrain the translation: the %s model has none" % self.problem.kind)
+        on_device = isinstance(path_obs, torch.Tensor) and path_obs.device == self.device
+        a = _checked("obstacle_paths", path_obs, (B, None, None, 4), finite=not on_device)
+        if a.shape[1] < 2:
+            raise ValueError("obstacle_paths has %d knots, expected T+1 >= 2" % a.shape[1])
+        if not 1 <= a.shape[2] <= _capi.MAX_OBSTACLES:
+            raise ValueError("obstacle_paths: K = %d spheres per trajectory, expected 1..%d" % (a.shape[2], _capi.MAX_OBSTACLES))
+        if on_device:
+            v = a.detach()
+            finite, positive = (bool(f) for f in torch.stack([torch.isfinite(v).all(), (v[..., 3] > 0.0).all()]).tolist())
+        else:
+            finite, positive = True, not np.any(a[..., 3] <= 0.0)  # (_checked has refused a non-finite value)
+        if not finite:
+            raise ValueError("obstacle_paths must be finite")
+        if not positive:
+            raise ValueError("obstacle_paths: every radius must be positive")
+        return a.shape[0], a if on_device else np.ascontiguousarray(a)
+
+    def _set_obstacle_windows(self, B, d_paths, t0_d, t, lam, imu):
+        K, T = d_paths.shape[2], d_paths.shape[1] - 1
+        self._obs = (d_paths, lam, imu)
+        self._call("tolg_set_al_obstacle_windows", B, K, _ptr(d_paths), int(T), _ptr(t0_d), int(t), _ptr(lam), _ptr(imu),
+                   *self._packed("_obs_mov_buf", self.lib.tolg_obstacles_moving_bytes, K, B=B))
+
+    def set_al_obstacle_windows(self, path_obs, t, t0=None, lam=None, imu=None):
+        """Attach the moving keep-out spheres of step t, gathered on the device from world-time paths
+        (tolg_set_al_obstacle_windows): path_obs [B, T+1, K, 4] rows (cx, cy, cz, r) of trajectory b's spheres at world knot s;
+        knot i of the window takes world knot min(t0[b] + t + i, T), set_ref_windows' rule (t0 an int array [B], None: 0).  The
+        handle is then as after set_al_obstacles with the gathered [B, N+1, K, 4] field; lam, imu [B, N+1, K] as there.
+        path_obs = None detaches."""
+        if path_obs is None:
+            return self.set_al_obstacles(None)
+        if int(t) < 0:
+            raise ValueError("t must be non-negative")
+        B, a = self._check_obstacle_paths(None if lam is None else int(lam.shape[0]), path_obs)
+        lam, imu = self._obs_multipliers(B, a.shape[2], lam, imu)
+        t0_d = self._check_t0(B, t0)
         d = self._dev(a, a.shape)
-        self._obs = (d, lam, imu)  # the handle reads the multipliers in every solve until they are detached
-        self._call("tolg_set_al_obstacles" + ("_moving" if moving else ""), B, K, _ptr(d), _ptr(lam), _ptr(imu), *dest)
+        self._hold((d, t0_d))
+        self._set_obstacle_windows(B, d, t0_d, int(t), lam, imu)
+
+    def al_mpc_step(self, xs_q, us, mu, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2, shift=True):
+        """The outer augmented-Lagrangian update of one MPC step over everything attached (tolg_al_mpc_step): the multipliers
+        of set_al / set_al_obstacles follow lambda <- max(0, lambda + I_mu g) on the controls us [B, N, m] and the positions of
+        xs_q [B, N+1, 4, 4] (device tensors; either may be None where nothing attached reads it), mu [B] (a float64 device
+        tensor, updated in place) grows by mu_scale up to mu_max where the largest g reaches tol_constr, and with shift both
+        multiplier sets then move one knot towards the start, the last knot held.  Nothing is sticky: a satisfied problem's
+        multipliers still relax.  The held policy is left alone.  Returns max_violation [B]."""
+        if not isinstance(mu, torch.Tensor) or mu.dtype != torch.float64 or mu.device != self.device or mu.dim() != 1 \
+                or not mu.is_contiguous():
+            raise ValueError("mu must be a contiguous float64 tensor of shape (B,) on %s" % self.device)
+        B = int(mu.shape[0])
+        xs_q = None if xs_q is None else self._dev(xs_q, (B, self.N + 1, 16))
+        us = None if us is None else self._dev(us, (B, self.N, self.m))
+        maxviol = torch.empty(B, dtype=torch.float64, device=self.device)
+        self._hold((xs_q, us))
+        self._al_step(B, xs_q, us, mu, mu_scale, mu_max, tol_constr, maxviol, shift)
+        return maxviol
+
+    def _al_step(self, B, xs_q, us, mu, mu_scale, mu_max, tol_constr, maxviol, shift):
+        self._call("tolg_al_mpc_step", B, _ptr(xs_q), _ptr(us), _ptr(mu), float(mu_scale), float(mu_max), float(tol_constr),
+                   _ptr(maxviol), int(bool(shift)))
 
     def al_fit_batch(self, x0_q, x0_xi, us_init, lb=None, ub=None, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
                      tol_d_norm=1e-6, tol_constr=1e-2, mu0=1e-2, mu_scale=10.0, mu_max=1e8, line_search=False,
@@ -1155,7 +1235,8 @@ class BatchedTrackingILQR:
     def mpc(self, x0_q, x0_xi, path_q, path_xi, steps, us_init=None, t0=None, iters_per_step=5, first_iters=50,
             warm="states", noise=None, mode="ms", line_search=False, rollout="nonlinear", tol_grad_norm=1e-6, tol_d_norm=1e-6,
             check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None, plant_J=None, plant_pend=None, u_lb=None,
-            u_ub=None) -> MPCResult:
+            u_ub=None, lb=None, ub=None, obstacles=None, obstacle_paths=None, first_al_iters=3, al_iters_per_step=1, mu0=1e-2,
+            mu_scale=10.0, mu_max=1e8, tol_constr=1e-2) -> MPCResult:
         """Receding-horizon MPC: `steps` closed-loop steps of B trajectories, each tracking its own path from its own phase.
         Step t: windows min(t0[b] + t + i, T) of the paths (tolg_set_ref_windows), a solve of first_iters (t = 0) or
         iters_per_step iterations, then tolg_mpc_advance applies u*_0, steps the plant with the exact dynamics and adds the
@@ -1167,10 +1248,20 @@ class BatchedTrackingILQR:
         weights per trajectory as for fit_batch.  on_step(t, FitResult) is called behind every step's solve (before the
         plant step; the FitResult carries histories then).  plant_J [B, 6, 6] / plant_pend [B, 2]: the plant every step's
         x_next is stepped with (model mismatch, as mpc_advance; None: the model); the solves plan on the model.  u_lb / u_ub [m] or
-        [B, m]: the actuator's box (as mpc_advance: every step applies clamp(u*_0); the planner stays unconstrained, only the
-        plant clips), the result then carries n_sat [B, steps].  Not with an
-        augmented-Lagrangian constraint attached.  The handle is left on the shared reference and weights, without a plant.
-        x0_q [B, 4, 4], x0_xi [B, 6], path_q [B, T+1, 4, 4], path_xi [B, T+1, 6]."""
+        [B, m]: the actuator's box (as mpc_advance: every step applies clamp(u*_0); it clips the plant only and is independent
+        of the planner's lb / ub), the result then carries n_sat [B, steps].  Not with an
+        augmented-Lagrangian constraint the caller attached.  The handle is left on the shared reference and weights, without a
+        plant, with no constraint attached.
+        x0_q [B, 4, 4], x0_xi [B, 6], path_q [B, T+1, 4, 4], path_xi [B, T+1, 6].
+        The planner's constraints (augmented Lagrangian, mode="ms" only; with none of them the loop is the one above): lb / ub
+        [m], the input box of set_al (the SO3 family takes the box only); obstacles [K, 4] or [B, K, 4], static keep-out
+        spheres, or obstacle_paths [B, T_o+1, K, 4], spheres in world time indexed with the same t0 (window t is gathered by
+        tolg_set_al_obstacle_windows); at most one of the two.  Step t then runs first_al_iters (t = 0) or al_iters_per_step
+        outer rounds: each a solve as above followed by tolg_al_mpc_step, which shifts the multipliers by one knot behind the
+        step's last round; round 0 starts as above, round a > 0 from round a-1's solution under the `warm` rule.  The
+        multipliers start at lambda = 0, I_mu = mu = mu0 (mu_scale, mu_max, tol_constr: al_fit_batch's).  The result carries
+        max_violation [B, steps] (each step's last round), mu [B] and, with spheres, clearance [B, steps+1] of the realised
+        states.  iters and status are those of each step's last round."""
         if self._al is not None:
             raise ValueError("mpc under an augmented-Lagrangian constraint is not supported: detach it with set_al(None)")
         if self._obs is not None:
@@ -1185,6 +1276,15 @@ class BatchedTrackingILQR:
         steps, K0, K = int(steps), int(first_iters), int(iters_per_step)
         if steps < 1 or K0 < 0 or K < 0 or int(check_every) < 0:
             raise ValueError("steps must be >= 1, first_iters, iters_per_step and check_every >= 0")
+        if (lb is None) != (ub is None):
+            raise ValueError("the input box needs both lb and ub")
+        if obstacles is not None and obstacle_paths is not None:
+            raise ValueError("give obstacles (static) or obstacle_paths (world time), not both")
+        constrained = lb is not None or obstacles is not None or obstacle_paths is not None
+        if constrained and mode != "ms":
+            raise ValueError("the augmented-Lagrangian constraints need mode='ms'")
+        if constrained and (int(first_al_iters) < 1 or int(al_iters_per_step) < 1):
+            raise ValueError("first_al_iters and al_iters_per_step must be >= 1")
         x0_q = _checked("x0_q", x0_q, (None, 16) if np.ndim(x0_q) == 2 else (None, 4, 4))
         B = x0_q.shape[0]
         if not 1 <= B <= self.max_batch:
@@ -1201,6 +1301,21 @@ class BatchedTrackingILQR:
             noise = _checked("noise", noise, (B, steps, 6), finite=True)
             noise = self._dev(np.ascontiguousarray(noise.transpose(1, 0, 2)), (steps, B, 6))  # step t: one contiguous [B, 6]
         f64 = dict(dtype=torch.float64, device=self.device)
+        # the planner's constraints, checked before anything is attached: (lb, ub, lam, imu), (geometry, lam, imu, in world time)
+        al = obs = mu = maxviol = None
+        if lb is not None:
+            al = (self._dev(_checked("lb", lb, (self.m,)), (self.m,)), self._dev(_checked("ub", ub, (self.m,)), (self.m,)),
+                  torch.zeros(B, self.N, 2 * self.m, **f64), torch.full((B, self.N, 2 * self.m), float(mu0), **f64))
+        if obstacles is not None or obstacle_paths is not None:
+            geo = (self._check_obstacles(B, obstacles)[1] if obstacles is not None else
+                   self._check_obstacle_paths(B, obstacle_paths)[1])
+            if obstacles is not None and geo.ndim != 3:
+                raise ValueError("mpc: obstacles are static, [K, 4] or [B, K, 4]; spheres that move are obstacle_paths")
+            Ko = geo.shape[-2]
+            obs = (self._dev(geo, geo.shape), torch.zeros(B, self.N + 1, Ko, **f64),
+                   torch.full((B, self.N + 1, Ko), float(mu0), **f64), obstacle_paths is not None)
+        if constrained:
+            mu, maxviol = torch.full((B,), float(mu0), **f64), torch.empty(B, **f64)
         res = MPCResult(xs_q=torch.empty(B, steps + 1, 4, 4, **f64), xs_xi=torch.empty(B, steps + 1, 6, **f64),
                         us=torch.empty(B, steps, self.m, **f64), J=torch.zeros(B, **f64),
                         iters=torch.empty(B, steps, dtype=torch.int32, device=self.device),
@@ -1215,25 +1330,42 @@ class BatchedTrackingILQR:
         try:
             # the plant survives the solves of the loop (tolg_set_plant): set once, detached behind it
             d_plant = self._use_plant(B, plant)
-            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box))
+            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box, al, obs, mu, maxviol))
             self._use_pt(B, None, b.wts)
+            if al is not None:
+                self.set_al(*al)
+            if obs is not None and not obs[3]:
+                self.set_al_obstacles(*obs[:3])
+            if constrained:
+                res.max_violation, res.mu = torch.empty(B, steps, **f64), mu
             for t in range(steps):
                 self._set_ref_windows(B, pq, pxi, T, t0_d, t)
+                if obs is not None and obs[3]:
+                    self._set_obstacle_windows(B, obs[0], t0_d, t, obs[1], obs[2])
                 n = K0 if t == 0 else K
                 o = self._options(mode, n, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg)
-                out = self._alloc_result(B, n, histories=on_step is not None)
                 xs = None
                 if t > 0:
                     x_q, x_xi = adv["x_next_q"].reshape(B, 16), adv["x_next_xi"]
                     us = adv["us"]
                     if warm == "states":
                         xs = (adv["xs_q"].reshape(B, self.N + 1, 16), adv["xs_xi"])
-                self._begin(o, B, x_q, x_xi, us, xs, out)
-                if check_every:
-                    self.solve_iterate_until(n, int(check_every))
-                else:
-                    self.solve_iterate(n)
-                out = self.solve_end()
+                rounds = (int(first_al_iters) if t == 0 else int(al_iters_per_step)) if constrained else 1
+                for a in range(rounds):
+                    if a > 0:  # from the round before, under the rule of `warm`
+                        us = out.us
+                        xs = (out.xs_q.reshape(B, self.N + 1, 16), out.xs_xi) if warm == "states" else None
+                    out = self._alloc_result(B, n, histories=on_step is not None)
+                    self._begin(o, B, x_q, x_xi, us, xs, out)
+                    if check_every:
+                        self.solve_iterate_until(n, int(check_every))
+                    else:
+                        self.solve_iterate(n)
+                    out = self.solve_end()
+                    if constrained:
+                        self._al_step(B, out.xs_q, out.us, mu, mu_scale, mu_max, tol_constr, maxviol, a == rounds - 1)
+                if constrained:
+                    res.max_violation[:, t] = maxviol
                 res.iters[:, t] = out.iters
                 res.status[:, t] = out.status
                 if on_step is not None:
@@ -1244,10 +1376,23 @@ class BatchedTrackingILQR:
                 res.us[:, t] = adv["u"]
                 res.xs_q[:, t + 1] = adv["x_next_q"]
                 res.xs_xi[:, t + 1] = adv["x_next_xi"]
+            if obs is not None:  # the realised state s of trajectory b is at world knot t0[b] + s
+                geo = obs[0]
+                if obs[3]:
+                    s = torch.arange(steps + 1, device=self.device)[None, :] + (0 if t0_d is None else t0_d.long()[:, None])
+                    geo = geo[torch.arange(B, device=self.device)[:, None], s.clamp(max=geo.shape[1] - 1).expand(B, steps + 1)]
+                else:
+                    geo = geo[:, None]
+                d = (res.xs_q[:, :, None, :3, 3] - geo[..., :3]).norm(dim=-1) - geo[..., 3]
+                res.clearance = d.amin(dim=-1)
         finally:
             self._use_pt(B, None, None)
             if plant is not None:
                 self._clear_plant()
+            if self._al is not None:
+                self.set_al(None)
+            if self._obs is not None:
+                self.set_al_obstacles(None)
         return res
 
     # ------------------------------------------------------------------------------------------

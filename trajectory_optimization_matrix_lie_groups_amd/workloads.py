@@ -396,6 +396,40 @@ def se3_moving_obstacle_field(B, K, N=200, seed=SEED):
     return prob, x0_q, x0_xi, us0, mov
 
 
+def se3_mpc_obstacles(B, steps, N=200, K=1, seed=SEED, **mpc_kw):
+    """se3_mpc's inputs (mpc_kw: its T, R and sigmas) plus K keep-out spheres per trajectory on its own path, where the closed
+    loop reaches them within `steps`: sphere k of trajectory b is placed by _obstacle_field's rule (radii 0.2 .. 0.4, moved by at
+    most 0.3 r off the path) on the stretch of world knots t0[b] .. t0[b] + steps that the loop travels, so its knot lies in
+    t0[b] + [steps // 4, 3 * steps // 4).  The drifting variant follows se3_moving_obstacle_field's rule in world time: a constant
+    seeded velocity (0.5 .. 1.5 radii over a quarter of the horizon, N // 4 knots), the sphere at its static centre at the world knot of that stretch
+    nearest to it, the velocity halved until the sphere is clear of the path at world knots t0[b] and t0[b] + steps.
+    Returns (prob, x0_q, x0_xi, path_q, path_xi, t0, noise, obstacles [B, K, 4], obstacle_paths [B, T+1, K, 4]): the first
+    seven are se3_mpc's, the last two what mpc(obstacles=) and mpc(obstacle_paths=) take."""
+    prob, x0_q, x0_xi, path_q, path_xi, t0, noise = se3_mpc(B, steps, N=N, seed=seed, **mpc_kw)
+    T = path_q.shape[1] - 1
+    world = np.clip(t0[:, None].astype(np.int64) + np.arange(steps + 1)[None, :], 0, T)   # [B, steps+1]
+    stretch = path_q[np.arange(B)[:, None], world]
+    obs = _obstacle_field(stretch, B, K, 0.2, 0.4, seed + 3)
+    rng = np.random.default_rng(seed + 6)
+    s = np.arange(T + 1, dtype=np.float64)
+    mov = np.empty((B, T + 1, K, 4))
+    for b in range(B):
+        t = stretch[b][:, :3, 3]
+        for k in range(K):
+            c, r = obs[b, k, :3], obs[b, k, 3]
+            i0 = int(world[b, int(np.argmin(np.sum((t - c) ** 2, axis=1)))])
+            d = rng.normal(size=3)
+            v = rng.uniform(0.5, 1.5) * r / max(1, N // 4) * d / np.linalg.norm(d)  # per knot
+            covered = any(np.sum((t[j] - c) ** 2) <= r * r for j in (0, steps))  # a stretch so short that no drift clears its ends
+            while True:
+                ck = c + (s - i0)[:, None] * v
+                if covered or all(np.sum((t[j] - ck[world[b, j]]) ** 2) > r * r for j in (0, steps)):
+                    break
+                v = 0.5 * v
+            mov[b, :, k, :3], mov[b, :, k, 3] = ck, r
+    return prob, x0_q, x0_xi, path_q, path_xi, t0, noise, obs, mov
+
+
 def se3_crossing_fleet(F, G, N=40, separation=0.3, seed=SEED):
     """F fleets of G members whose paths cross: member p tracks g_p q_ref, with g_p the rotation by p pi / G about world z
     through the reference's position at knot N // 2 plus a z shift of 0.3 separation p -- every pair of paths passes within
