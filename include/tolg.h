@@ -241,12 +241,38 @@ int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, const double*
  * spheres to its cost, and must be called with this B (else TOLG_E_ARG).  With tolg_set_al attached too the cost carries both
  * sets of terms.  tolg_eval_knot ignores them (as it ignores per-trajectory references and weights); tolg_policy_rollout and
  * tolg_mpc_advance report the tracking cost only.  d_obs = NULL detaches the spheres.  The held policy is left alone.
+ * With tolg_set_al_obstacle_kinds (below) slot k is a keep-in sphere (|d|^2 - r^2), a half-space (n.t - o, fields nx ny nz o) or
+ * a vertical column (r^2 - (dx^2 + dy^2)) instead, with clearances r - |d|, o - n.t and sqrt(dx^2 + dy^2) - r; this call, the
+ * moving form and the window form keep the kinds when K is the K attached and reset them to keep-out spheres otherwise.
  * TOLG_E_ARG: B < 1 or B > max_batch, K out of range, a NULL multiplier or buffer, packed_bytes < tolg_obstacles_bytes(prob, B,
  * K), a solve in flight, references or weights per trajectory for another B, a kind of the SO3 family. */
 #define TOLG_MAX_OBSTACLES 16
 size_t tolg_obstacles_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K);
 int tolg_set_al_obstacles(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
                           const double* d_imu, void* d_packed, size_t packed_bytes, void* stream);
+
+/* Position constraints beyond the keep-out sphere: every slot k of the K attached has a kind, the same for every trajectory and
+ * every knot (batch-shared, so no wave diverges on it).  The four fields (f0, f1, f2, f3) of a slot stay where the three
+ * tolg_set_al_obstacles* calls put them and are read per kind; with d = t - (f0, f1, f2):
+ *   kind                   fields            row g <= 0              grad_t g          clearance (>= 0 inside the allowed set)
+ *   TOLG_OBS_KEEP_OUT  0   cx cy cz r        r^2 - |d|^2             -2 d              |d| - r
+ *   TOLG_OBS_KEEP_IN   1   cx cy cz r        |d|^2 - r^2              2 d              r - |d|             (a geofence)
+ *   TOLG_OBS_HALF_SPACE 2  nx ny nz o        n.t - o                  n                o - n.t             (|n| = 1, as given)
+ *   TOLG_OBS_COLUMN_Z  3   cx cy -  r        r^2 - (dx^2 + dy^2)     -2 (dx, dy, 0)    sqrt(dx^2 + dy^2) - r   (axis along world z)
+ * Each depends on the position alone, so in the error coordinates g_x = [0_3, (grad_t g)^T R, 0_6]: the block the sphere fills,
+ * and the cost terms are the sphere's with that g and g_x.  The half-space normal is not rescaled: o is measured along it.
+ * tolg_set_al_obstacle_kinds: kinds [K] on the HOST, each one of TOLG_OBS_*; NULL makes every slot a keep-out sphere again.
+ * Called after an attach (tolg_set_al_obstacles, _moving or _windows), for the K attached; stream-ordered like the attach.
+ * Attaching again with the same K, in any of the three forms, keeps the kinds (an MPC loop attaches every step); attaching
+ * with another K, or detaching, makes every slot TOLG_OBS_KEEP_OUT.  A handle on which it was never called runs keep-out
+ * spheres.  The multiplier rule, the multiplier shape [B][N+1][K] and the packed layout are unchanged.  The held policy is
+ * left alone.
+ * TOLG_E_ARG: nothing attached, K other than the attached K, a kind outside 0..3, a solve in flight. */
+#define TOLG_OBS_KEEP_OUT 0
+#define TOLG_OBS_KEEP_IN 1
+#define TOLG_OBS_HALF_SPACE 2
+#define TOLG_OBS_COLUMN_Z 3
+int tolg_set_al_obstacle_kinds(tolg_handle_t h, int32_t K, const int32_t* kinds, void* stream);
 
 /* Keep-out spheres that move: the same constraint with its geometry given per knot, so that another vehicle's predicted path, a
  * sphere that exists around some knots only, or a radius inflated by the knot's position covariance (tolg_policy_covariance)
@@ -270,7 +296,8 @@ int tolg_set_al_obstacles_moving(tolg_handle_t h, int32_t B, int32_t K, const do
  * on the positions of d_xs_q [B][N+1][16].  d_maxviol[b] = the largest g of them all (the box contributes its terminal rows
  * g = 0); below tol_constr the problem is marked in d_al_converged[b] and left alone, otherwise both multiplier sets (the
  * attached d_lambda / d_imu of either call) follow the rule of tolg_al_update with one mu per problem, d_mu[b].  d_us may be
- * NULL without a box, d_xs_q without spheres.  tolg_al_update is unchanged.
+ * NULL without a box, d_xs_q without spheres.  tolg_al_update is unchanged.  The row of slot k is the row of its kind
+ * (tolg_set_al_obstacle_kinds: r^2 - |d|^2, |d|^2 - r^2, n.t - o or r^2 - (dx^2 + dy^2)); the rule is the same for all.
  * TOLG_E_ARG: nothing attached, B < 1 or B > max_batch, B other than the spheres' batch, a NULL input the attached
  * constraints need. */
 int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu, double mu_scale,
@@ -281,7 +308,8 @@ int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_xs_q, const
  * a new problem -- followed, with shift == 1, by a one-knot shift of both multiplier sets, in place in the caller-owned buffers
  * the handle points at: the warm start of the duals, as tolg_mpc_advance's shift is that of the states and controls.
  * The rows g of trajectory b are tolg_al_update_state's: the box rows [lb - u_i; u_i - ub], i < N, and the sphere rows
- * r_ik^2 - |t_i - c_ik|^2, i <= N, of whichever geometry form is attached when the call runs.  Then
+ * r_ik^2 - |t_i - c_ik|^2, i <= N, of whichever geometry form is attached when the call runs (a slot of another kind: the row
+ * of that kind, tolg_set_al_obstacle_kinds: |d|^2 - r^2, n.t - o or r^2 - (dx^2 + dy^2)).  Then
  *   mv = max g        (the box contributes its terminal zero rows: mv starts at 0 with a box, at -inf without; NaN is passed over)
  *   d_maxviol[b] = mv (d_maxviol may be NULL)
  *   mu_new = mv < tol_constr ? mu[b] : min(mu_scale mu[b], mu_max)
@@ -423,7 +451,9 @@ int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, double* d_x_
  *                             distances are passed over)
  *        d_clear [B][S]       min_{i = 0..N, k < K} (|t^_i - c_ik| - r_ik) over the spheres attached to the handle, the static
  *                             form with one geometry for every knot, the moving form with knot i's own; negative: penetration
- *                             (+inf if no distance is a number)
+ *                             (+inf if no distance is a number).  A slot of another kind (tolg_set_al_obstacle_kinds)
+ *                             enters with the clearance of its kind: r - |d| (keep-in), o - n.t (half-space),
+ *                             sqrt(dx^2 + dy^2) - r (column); negative: outside the allowed set
  *        d_clear_knot [B][S]  the first knot that attains the minimum (strict <, knots ascending, spheres ascending)
  *        every output may be NULL.
  * TOLG_E_ARG: the conditions of tolg_policy_rollout; exactly one NULL bound; a non-NULL d_clear or d_clear_knot with no spheres

@@ -3,7 +3,7 @@
 (al_fit_batch(obstacles=...)) on the K = 8 field: its outer-iteration count and time.
 
 usage: python tools/bench_obstacles.py [--lines headline,merit,ss] [--Ks 0,1,4,8] [--B 4096] [--N 200] [--rounds 7]
-                                       [--steps K] [--warmup W] [--al] [--moving] [--out FILE.json] [--dry]
+                                       [--steps K] [--warmup W] [--al] [--moving] [--kinds] [--out FILE.json] [--dry]
 
 One process, one handle per line; the variants are timed in alternation, round after round (the order rotates every round),
 each region being iterations W .. W+K of a fresh solve between two device synchronisations (tools/_benchlib.py's
@@ -14,7 +14,12 @@ no-sphere variant's.
 
 --moving sends the same field of each K, repeated over the N + 1 knots, through tolg_set_al_obstacles_moving ([B, N+1, K, 4]):
 the same arithmetic on geometry that is streamed per knot instead of read from 4K cached values, so the lines beside the
-static ones show what the streaming costs."""
+static ones show what the streaming costs.
+
+--kinds times what the per-slot kind costs (tolg_set_al_obstacle_kinds) at K = 6 slots in place of the K sweep: no slots, all
+keep-out spheres (workloads.se3_obstacle_field with K = 6: the K = 6 run of this tool without the flag), the corridor mix
+(workloads.se3_corridor: two half-spaces, a geofence, two columns, a sphere) and all half-spaces (the tangent planes of the
+spheres that face the start of the path).  One line per mix for every solve line asked for."""
 import argparse
 import json
 import os
@@ -33,6 +38,7 @@ def parse_args(argv=None):
     add_common_args(ap, "B", "N", "rounds", "steps", "warmup")
     ap.add_argument("--al", action="store_true", help="also time one al_fit_batch on the K = max(Ks) field")
     ap.add_argument("--moving", action="store_true", help="attach each field per knot (tolg_set_al_obstacles_moving)")
+    ap.add_argument("--kinds", action="store_true", help="time the kind mixes at K = 6 (spheres, corridor, half-spaces)")
     add_common_args(ap, "out", "dry")
     a = ap.parse_args(argv)
     a.lines = a.lines.split(",")
@@ -77,6 +83,50 @@ def run_line(name, a, prob, q0, xi0, us, obs):
     return out
 
 
+KIND_MIXES = ("none", "spheres", "corridor", "half_spaces")
+
+
+def kind_mixes(a):
+    """{mix: (obstacles [B, 6, 4], kinds)} on se3_tracking's workload, which se3_obstacle_field and se3_corridor share"""
+    import numpy as np
+    prob, q0, xi0, us, sph = workloads.se3_obstacle_field(a.B, 6, N=a.N)
+    cor, kinds = workloads.se3_corridor(a.B, N=a.N)[4:]
+    n = sph[..., :3] - prob.q_ref[0, :3, 3]
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    planes = np.concatenate([n, np.sum(n * sph[..., :3], axis=-1, keepdims=True) - sph[..., 3:]], axis=-1)
+    return (prob, q0, xi0, us), {"spheres": (sph, None), "corridor": (cor, kinds), "half_spaces": (planes, ("half_space",) * 6)}
+
+
+def run_kinds_line(name, a, prob, q0, xi0, us, mixes):
+    import torch
+    from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
+    kw, K0 = LINES[name]
+    K, W = a.steps or K0, a.warmup
+    solver = BatchedTrackingILQR(prob, a.B)
+    dev = solver.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    q_d, xi_d, us_d = (torch.as_tensor(x, **f64) for x in (q0, xi0, us))
+    mult = (torch.full((a.B, a.N + 1, 6), 0.1, **f64), torch.full((a.B, a.N + 1, 6), 1e-2, **f64))
+
+    def region(mix):
+        if mix != "none":
+            solver.set_al_obstacles(mixes[mix][0], *mult, kinds=mixes[mix][1])
+        rate, _ = solve_rate_region(solver, (q_d, xi_d, us_d), kw, W, K)
+        if mix != "none":
+            solver.set_al_obstacles(None)
+            torch.cuda.synchronize(dev)
+        return rate
+
+    rates = rate_rounds(KIND_MIXES, region, a.rounds)
+    out = dict(line=name, B=a.B, N=a.N, K=6, steps=K, warmup=W, rounds=a.rounds, unit="batch-iterations/s",
+               variants={m: summary(rates[m]) for m in KIND_MIXES})
+    base = out["variants"]["none"]["median"]
+    out["ratio_to_none"] = {v: s["median"] / base for v, s in out["variants"].items()}
+    del solver
+    torch.cuda.synchronize(dev)
+    return out
+
+
 def run_al(a, prob, q0, xi0, us, obs):
     import torch
     from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
@@ -96,14 +146,17 @@ def main(argv=None):
     a = parse_args(argv)
     kmax = max(max(a.Ks), 1)
     prob, q0, xi0, us, obs = workloads.se3_obstacle_field(a.B, kmax, N=a.N)
+    if a.kinds:
+        (prob, q0, xi0, us), mixes = kind_mixes(a)
     if a.dry:
         print(json.dumps(dict(plan=a.lines, Ks=a.Ks, B=a.B, N=prob.N, rounds=a.rounds, al=a.al, moving=a.moving,
+                              kinds=list(KIND_MIXES) if a.kinds else None,
                               steps={n: a.steps or LINES[n][1] for n in a.lines}, warmup=a.warmup)))
         return 0
     require_gpu("bench_obstacles")
     results = []
     for name in a.lines:
-        r = run_line(name, a, prob, q0, xi0, us, obs)
+        r = run_kinds_line(name, a, prob, q0, xi0, us, mixes) if a.kinds else run_line(name, a, prob, q0, xi0, us, obs)
         results.append(r)
         print_row(r)
     if a.al:

@@ -52,7 +52,10 @@ struct Consts {
   // keep-out spheres (tolg_set_al_obstacles, caller-owned), read by the PT_OBS kernels only: the packed geometry [4K][Bp]
   // (OB_* fields of sphere k at (4k + f) * Bp + b), the multipliers and the diagonal of I_mu in the caller layout [B][N+1][K]
   const double *obs, *obs_lam, *obs_imu;
-  int obsK, obs_pad;
+  // obs_kinds: the kind of every slot (TOLG_OBS_*), 2 bits each, slot k at bits 2k (tolg_set_al_obstacle_kinds; 0: every slot
+  // a keep-out sphere).  Batch-shared, so a wave reads one kind per slot; every value of the word is sixteen defined kinds.
+  int obsK;
+  unsigned obs_kinds;
   // ... and the geometry's knot stride in doubles: 0 (one [4K][Bp] block for every knot) or 4 K Bp (tolg_set_al_obstacles_moving:
   // [N+1][4K][Bp], knot i's block at i * 4 K Bp); the pack kernels set it
   size_t obs_stride;
@@ -325,34 +328,71 @@ __host__ __device__ constexpr int rec_fields(int m, bool grav, bool al, bool a22
 __host__ __device__ inline bool so3_family(int kind) { return kind == TOLG_DYN_SO3 || kind == TOLG_DYN_PENDULUM3D; }
 __host__ __device__ inline int sym6(int r, int c) { return r <= c ? c * (c + 1) / 2 + r : r * (r + 1) / 2 + c; }
 
-// Keep-out spheres of trajectory b (tolg_set_al_obstacles, or per knot tolg_set_al_obstacles_moving: the geometry of knot i
-// lies i * C.obs_stride doubles on; PT_OBS): g_k = r_k^2 - |t - c_k|^2 <= 0 at every knot, terminal
+// The kind of slot k in the word of Consts::obs_kinds (wave-uniform: the word is batch-shared).
+TOLG_DEV unsigned obs_kind(unsigned kinds, int k) { return (kinds >> (2 * k)) & 3u; }
+// One position row of kind kd with fields f0..f3 at position t: g, and its gradient in t as s w (include/tolg.h has the table).
+// The keep-out sphere's arithmetic is the one every kind shares -- w = t - c, g = r^2 - |w|^2, s = -2: the column drops w.z
+// ahead of it (an exact zero term in the sum), the keep-in sphere changes the signs of g and s behind it, and only the
+// half-space has a row of its own, w = n, g = n.t - o, s = 1.  kd is wave-uniform: the branches do not diverge.
+TOLG_DEV void obs_row(unsigned kd, double f0, double f1, double f2, double f3, const V3& t, V3& w, double& g, double& s) {
+  if (kd == TOLG_OBS_HALF_SPACE) {
+    w = v3(f0, f1, f2);
+    g = dot(w, t) - f3;
+    s = 1.0;
+    return;
+  }
+  w = t - v3(f0, f1, f2);
+  if (kd == TOLG_OBS_COLUMN_Z) w.z = 0.0;
+  g = f3 * f3 - dot(w, w);
+  s = -2.0;
+  if (kd == TOLG_OBS_KEEP_IN) { g = -g; s = 2.0; }
+}
+
+// Position constraints of trajectory b (tolg_set_al_obstacles, or per knot tolg_set_al_obstacles_moving: the geometry of knot i
+// lies i * C.obs_stride doubles on; PT_OBS), slot k of the kind tolg_set_al_obstacle_kinds gave it (none: a keep-out sphere,
+// g_k = r_k^2 - |t - c_k|^2): g_k <= 0 at every knot, terminal
 // included, and the augmented-Lagrangian terms of ALConstrainedCost (traopt_cost.py:1173-1320; Gauss-Newton, no g_xx).  In the
-// error coordinates of l_x (X Exp(delta), twist order [w, v]) g_x = [0, -2 (t - c)^T R, 0]: only its v part is not zero,
-// gv = -2 R^T (t - c).  Sums lambda g + g I g / 2 into l and, with ox / oxx given, gv (lambda + I g) into ox (l_x[3:6]) and
+// error coordinates of l_x (X Exp(delta), twist order [w, v]) g_x = [0, (grad_t g)^T R, 0]: only its v part is not zero,
+// gv = R^T grad_t g (the sphere: -2 R^T (t - c)).  Sums lambda g + g I g / 2 into l and, with ox / oxx given, gv (lambda + I g) into ox (l_x[3:6]) and
 // I gv gv^T into oxx (the v-v block of l_xx, upper triangle row by row: 00 01 02 11 12 22).  The callers add the sums after
 // the tracking arithmetic, so that with lambda = I = 0 every term is an exact zero and the tracking values keep their bits.
+// One slot's terms.  KINDS = false: the slot is a keep-out sphere whatever kd says -- obs_row folds to the sphere's row and the
+// scale to its literal, the instructions of the loop before there were kinds.
+template <bool KINDS>
+TOLG_DEV void obs_slot(unsigned kd, const double* o, size_t Bp, double lk, double ik, const Pose& X, double& l, double* ox, double* oxx) {
+  V3 d;
+  double g, s2;
+  obs_row(KINDS ? kd : (unsigned)TOLG_OBS_KEEP_OUT, o[0], o[Bp], o[2 * Bp], o[3 * Bp], X.t, d, g, s2);
+  l += lk * g + 0.5 * (g * ik * g);
+  if (ox) {
+    // the scale by its literal under a uniform branch: as a product with s2 the fused launch with every per-trajectory
+    // input (M = 6) spilled two registers more
+    V3 gv = qrot_inv(X.q, d);
+    if (s2 == -2.0) gv = -2.0 * gv;
+    else if (s2 == 2.0) gv = 2.0 * gv;
+    const double gw[3] = {gv.x, gv.y, gv.z}, s = lk + ik * g;
+#pragma unroll
+    for (int a = 0, n = 0; a < 3; a++) {
+      ox[a] += gw[a] * s;
+#pragma unroll
+      for (int c = a; c < 3; c++, n++) oxx[n] += ik * gw[a] * gw[c];
+    }
+  }
+}
 template <class CT>
 TOLG_DEV void obs_terms(const Params& P, const CT& C, int i, int b, const Pose& X, double& l, double* ox, double* oxx) {
   const int K = C.obsK, bs = b < P.B ? b : P.B - 1;  // the packed geometry replicates B-1 in padded lanes, the multipliers do not
   const size_t row = ((size_t)bs * (P.N + 1) + i) * K, Bp = (size_t)P.Bp;
   const double *lam = C.obs_lam + row, *imu = C.obs_imu + row, *geo = C.obs + b + (size_t)i * C.obs_stride;
-  for (int k = 0; k < K; k++) {
-    const double* o = geo + (size_t)(4 * k) * Bp;
-    const V3 d = X.t - v3(o[0], o[Bp], o[2 * Bp]);
-    const double r = o[3 * Bp], lk = lam[k], ik = imu[k];
-    const double g = r * r - dot(d, d);
-    l += lk * g + 0.5 * (g * ik * g);
-    if (ox) {
-      const V3 gv = -2.0 * qrot_inv(X.q, d);
-      const double gw[3] = {gv.x, gv.y, gv.z}, s = lk + ik * g;
-#pragma unroll
-      for (int a = 0, n = 0; a < 3; a++) {
-        ox[a] += gw[a] * s;
-#pragma unroll
-        for (int c = a; c < 3; c++, n++) oxx[n] += ik * gw[a] * gw[c];
-      }
-    }
+  const unsigned kinds = C.obs_kinds;
+  // A word of zeros is a scene of keep-out spheres (every handle on which tolg_set_al_obstacle_kinds was never called): one
+  // uniform branch a knot, then the loop without the per-slot decode and branches, which cost the fused launch 1.4 % at K = 6.
+  // Only where the derivatives are asked for: the cost-only callers (ox null at compile time) have little to skip, and
+  // their two-wave rollout spilled two registers more with both loops in it.
+  if (ox && kinds == 0) {
+    for (int k = 0; k < K; k++) obs_slot<false>(0u, geo + (size_t)(4 * k) * Bp, Bp, lam[k], imu[k], X, l, ox, oxx);
+  } else {
+    for (int k = 0; k < K; k++) obs_slot<true>(obs_kind(kinds, k), geo + (size_t)(4 * k) * Bp, Bp, lam[k], imu[k], X, l, ox, oxx);
   }
 }
 
@@ -3129,7 +3169,8 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
 //    inside the step (roll_step's limit): u^ = u~ < lb ? lb : (u~ > ub ? ub : u~), a NaN command stays NaN.  The four lanes of
 //    a quad hold the same u~ and count the same: n_sat the pairs (i, a) with u~ outside the box, excess the largest distance
 //    by which one left it (fmax: a NaN distance is passed over);
-//  - with L.clearance, min over knots i <= N and spheres k of |t^_i - c_ik| - r_ik on the state the step starts from, geometry
+//  - with L.clearance, min over knots i <= N and slots k of the clearance of slot k's kind (the keep-out sphere:
+//    |t^_i - c_ik| - r_ik; include/tolg.h has the table) on the state the step starts from, geometry
 //    read as obs_terms reads it (field 4k + c of knot i at (i obs_stride + (4k + c) Bp + b): one address per wave in the
 //    default sample order), strict < with knots and spheres ascending: the first knot that attains the minimum.  It stands
 //    behind the step in the source and depends on the state alone, not on the gains or the control.
@@ -3146,20 +3187,29 @@ struct PolicyLim {
 TOLG_DEV void clear_knot_min(const Consts& C, size_t Bp, int b, int i, const V3& t, double& cmin, int& cknot) {
   const double* geo = C.obs + b + (size_t)i * C.obs_stride;
   const int K = C.obsK;
-  // four spheres at a time, their sixteen loads in flight together (one sphere per trip paid a load latency each: 1.8 us per
-  // knot at K = 8); a trip past K replays sphere K - 1, whose distance is not below itself
+  const unsigned kinds = C.obs_kinds;
+  // four slots at a time, their sixteen loads in flight together (one slot per trip paid a load latency each: 1.8 us per
+  // knot at K = 8); a trip past K replays slot K - 1 with its own kind, whose clearance is not below itself
   for (int k0 = 0; k0 < K; k0 += 4) {
     double g[4][4];
+    unsigned kd[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const int k = k0 + j < K ? k0 + j : K - 1;
       const double* o = geo + (size_t)(4 * k) * Bp;
       g[j][0] = o[0]; g[j][1] = o[Bp]; g[j][2] = o[2 * Bp]; g[j][3] = o[3 * Bp];
+      kd[j] = obs_kind(kinds, k);
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      const V3 d = t - v3(g[j][0], g[j][1], g[j][2]);
-      const double c = sqrt(dot(d, d)) - g[j][3];
+      double c;
+      if (kd[j] == TOLG_OBS_HALF_SPACE) c = g[j][3] - dot(v3(g[j][0], g[j][1], g[j][2]), t);
+      else {
+        V3 d = t - v3(g[j][0], g[j][1], g[j][2]);
+        if (kd[j] == TOLG_OBS_COLUMN_Z) d.z = 0.0;
+        c = sqrt(dot(d, d)) - g[j][3];
+        if (kd[j] == TOLG_OBS_KEEP_IN) c = -c;
+      }
       if (c < cmin) { cmin = c; cknot = i; }
     }
   }
@@ -4964,7 +5014,8 @@ struct tolg_handle_s {
   // pt[H_REFS] tolg_set_refs / tolg_set_ref_windows, pt[H_WTS] tolg_set_weights, pt[H_OBS] tolg_set_al_obstacles(_moving).
   // One batch: every batch call, and every further pt[k], must be for the B of those held (one_batch)
   Held pt[H_PT];
-  int obs_K = 0;          // pt[H_OBS]: the spheres per trajectory,
+  int obs_K = 0;          // pt[H_OBS]: the slots per trajectory,
+  unsigned obs_kinds = 0; // ... their kinds (Consts::obs_kinds; tolg_set_al_obstacle_kinds), kept while K stays,
   size_t obs_stride = 0;  // ... the knot stride of the geometry in doubles (Consts::obs_stride): 0, or 4 K Bp for the moving form
   double *obs_lam = nullptr, *obs_imu = nullptr;  // ... their multipliers [B][N+1][K] (caller-owned; tolg_al_update_state writes them)
   // tolg_set_plant: the packed plant rows, or nothing held: the closed loops step the model.  Outside the one-batch rule (its
@@ -5034,7 +5085,7 @@ static void hold(tolg_handle_s* h, Held& r, const void* d, int B) {
 // ... and back to what tolg_create left, r's extras with it.  (Both reselect the kernels: nothing changes for the plant.)
 static void drop(tolg_handle_s* h, Held& r) {
   r = Held();
-  if (&r == &h->pt[H_OBS]) { h->obs_K = 0; h->obs_stride = 0; h->obs_lam = h->obs_imu = nullptr; }
+  if (&r == &h->pt[H_OBS]) { h->obs_K = 0; h->obs_kinds = 0; h->obs_stride = 0; h->obs_lam = h->obs_imu = nullptr; }
   if (&r == &h->plant) h->plant_S = h->plant_form = 0;
   select_kernels(h);
 }
@@ -5822,13 +5873,13 @@ extern "C" int tolg_set_weights(tolg_handle_t h, int32_t B, const double* d_q_di
 // read from source knot i (t < 0: src_knots = knots), or gathered from a world-time path of src_knots = T + 1 knots
 // (tolg_set_al_obstacle_windows, t >= 0): source knot min(t0[b] + t + i, T), t0 = null: 0 -- k_pack_ref_windows' rule, the
 // same packed bits as the per-knot form on host-sliced windows.  Thread 0 points the handle's constants at the geometry, its
-// knot stride and the caller's multipliers (stream-ordered before the solves that read them).
+// knot stride, the caller's multipliers and the handle's kind word (stream-ordered before the solves that read them).
 __global__ void k_pack_obstacles_moving(int B, int Bp, int K, int knots, size_t stride, const double* __restrict__ obs, int src_knots,
                                         const int* __restrict__ t0, int t, const double* lam, const double* imu,
-                                        double* __restrict__ w, Consts* c) {
+                                        double* __restrict__ w, Consts* c, unsigned kinds) {
   size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t knot = (size_t)4 * K * Bp;
-  if (g == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; c->obs_stride = stride; }
+  if (g == 0) { c->obs = w; c->obs_lam = lam; c->obs_imu = imu; c->obsK = K; c->obs_kinds = kinds; c->obs_stride = stride; }
   if (g >= knot * (size_t)knots) return;
   const size_t i = g / knot, r = g % knot;
   const int b = (int)(r % Bp), f = (int)(r / Bp);
@@ -5842,12 +5893,14 @@ __global__ void k_pack_obstacles_moving(int B, int Bp, int K, int knots, size_t 
 }
 
 // The row arithmetic of the outer updates, stated once for k_al_update_state and k_al_mpc_step: the constraint rows of
-// trajectory b -- box row k of knot i, [lb - u_i; u_i - ub], and sphere k at knot i, r^2 - |t - c|^2, from the packed geometry
-// (geo_stride 0: one block for every knot) -- and the multiplier rule.
+// trajectory b -- box row k of knot i, [lb - u_i; u_i - ub], and slot k at knot i, the row of its kind (obs_kind of `kinds`;
+// the keep-out sphere: r^2 - |t - c|^2), from the packed geometry (geo_stride 0: one block for every knot) -- and the
+// multiplier rule.
 struct AlRows {
   int b, Bp, N, m, K;
   const double *xs_q, *us, *lb, *ub, *geo;
   size_t geo_stride;
+  unsigned kinds;
   TOLG_DEV double g_box(int i, int k) const {
     const double* u = us + ((size_t)b * N + i) * m;
     return (k < m) ? lb[k] - u[k] : u[k - m] - ub[k - m];
@@ -5855,8 +5908,12 @@ struct AlRows {
   TOLG_DEV double g_sphere(int i, int k) const {
     const double* x = xs_q + ((size_t)b * (N + 1) + i) * 16;
     const double* o = geo + (size_t)i * geo_stride + (size_t)(4 * k) * Bp + b;
-    const double dx = x[3] - o[0], dy = x[7] - o[Bp], dz = x[11] - o[2 * (size_t)Bp], r = o[3 * (size_t)Bp];
-    return r * r - (dx * dx + dy * dy + dz * dz);
+    const unsigned kd = obs_kind(kinds, k);
+    const double f0 = o[0], f1 = o[Bp], f2 = o[2 * (size_t)Bp], r = o[3 * (size_t)Bp];
+    if (kd == TOLG_OBS_HALF_SPACE) return (f0 * x[3] + f1 * x[7] + f2 * x[11]) - r;
+    const double dx = x[3] - f0, dy = x[7] - f1, dz = kd == TOLG_OBS_COLUMN_Z ? 0.0 : x[11] - f2;
+    const double g = r * r - (dx * dx + dy * dy + dz * dz);
+    return kd == TOLG_OBS_KEEP_IN ? -g : g;
   }
 };
 // lambda <- max(0, lambda + I_mu g), I_mu <- 0 where (g < 0 and lambda_new == 0) else mu_new
@@ -5876,12 +5933,12 @@ TOLG_DEV void al_row_update(double& l, double& im, double g, double mu_new) {
 // the box of its own arguments and no geometry, tolg_al_update_state what the handle holds.
 __global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const double* __restrict__ xs_q, const double* __restrict__ us,
                                   const double* __restrict__ lb, const double* __restrict__ ub, double* __restrict__ lam,
-                                  double* __restrict__ imu, const double* __restrict__ geo, size_t geo_stride, double* __restrict__ olam,
-                                  double* __restrict__ oimu, double* __restrict__ mu, double mu_scale, double mu_max,
-                                  double tol_constr, double* __restrict__ maxviol, int* __restrict__ al_conv) {
+                                  double* __restrict__ imu, const double* __restrict__ geo, size_t geo_stride, unsigned kinds,
+                                  double* __restrict__ olam, double* __restrict__ oimu, double* __restrict__ mu, double mu_scale,
+                                  double mu_max, double tol_constr, double* __restrict__ maxviol, int* __restrict__ al_conv) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B || al_conv[b]) return;  // a converged problem keeps its multipliers
-  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride};
+  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride, kinds};
   double mv = lb ? 0.0 : -INFINITY;
   if (lb)
     for (int i = 0; i < N; i++)
@@ -5975,11 +6032,11 @@ TOLG_DEV void al_step_rows(double* __restrict__ l, double* __restrict__ im, int 
 __global__ __launch_bounds__(AL_STEP_THREADS) void k_al_mpc_step(
     int Bp, int N, int m, int K, const double* __restrict__ xs_q, const double* __restrict__ us, const double* __restrict__ lb,
     const double* __restrict__ ub, double* __restrict__ lam, double* __restrict__ imu, const double* __restrict__ geo,
-    size_t geo_stride, double* __restrict__ olam, double* __restrict__ oimu, double* __restrict__ mu, double mu_scale,
-    double mu_max, double tol_constr, double* __restrict__ maxviol, int shift) {
+    size_t geo_stride, unsigned kinds, double* __restrict__ olam, double* __restrict__ oimu, double* __restrict__ mu,
+    double mu_scale, double mu_max, double tol_constr, double* __restrict__ maxviol, int shift) {
   __shared__ double red[AL_STEP_THREADS / 64];
   const int b = blockIdx.x;
-  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride};
+  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride, kinds};
   const int W = 2 * m, nb = lb ? N * W : 0, no = geo ? (N + 1) * K : 0;
   const double mu_old = mu[b];
   double mv = lb ? 0.0 : -INFINITY;
@@ -6020,9 +6077,10 @@ static int set_obstacles(tolg_handle_t h, int B, int K, bool moving, const doubl
     return TOLG_E_ARG;
   const int Bp = padded_batch(B), knots = moving ? h->prob.N + 1 : 1;
   const size_t knot = (size_t)4 * K * Bp;
+  if (K != h->obs_K) h->obs_kinds = 0;  // the kinds stay with a re-attach of the same K (an MPC loop's, every step)
   hipLaunchKernelGGL(k_pack_obstacles_moving, dim3((unsigned)((knots * knot + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      B, Bp, K, knots, moving ? knot : 0, d_obs, t >= 0 ? T + 1 : knots, reinterpret_cast<const int*>(d_t0), t,
-                     d_lambda, d_imu, static_cast<double*>(d_packed), const_cast<Consts*>(h->P.c));
+                     d_lambda, d_imu, static_cast<double*>(d_packed), const_cast<Consts*>(h->P.c), h->obs_kinds);
   LAUNCH_CHECK();
   h->obs_K = K; h->obs_stride = moving ? knot : 0;
   h->obs_lam = const_cast<double*>(d_lambda); h->obs_imu = const_cast<double*>(d_imu);
@@ -6044,6 +6102,23 @@ extern "C" int tolg_set_al_obstacle_windows(tolg_handle_t h, int32_t B, int32_t 
   return set_obstacles(h, B, K, true, d_path_obs, d_lambda, d_imu, d_packed, packed_bytes, stream, T, d_t0, t);
 }
 
+// The kinds of the K slots attached (kinds = null: keep-out spheres again), packed 2 bits a slot into the word the handle keeps
+// and the constants carry: one store, stream-ordered among the solves like the attach itself.  The held policy stays: its
+// gains belong to the problem that was solved.
+__global__ void k_set_obstacle_kinds(Consts* c, unsigned kinds) { c->obs_kinds = kinds; }
+extern "C" int tolg_set_al_obstacle_kinds(tolg_handle_t h, int32_t K, const int32_t* kinds, void* stream) {
+  if (!h || h->running || !h->pt[H_OBS].p || K != h->obs_K) return TOLG_E_ARG;
+  unsigned word = 0;
+  for (int k = 0; kinds && k < K; k++) {
+    if (kinds[k] < TOLG_OBS_KEEP_OUT || kinds[k] > TOLG_OBS_COLUMN_Z) return TOLG_E_ARG;
+    word |= (unsigned)kinds[k] << (2 * k);
+  }
+  hipLaunchKernelGGL(k_set_obstacle_kinds, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), const_cast<Consts*>(h->P.c), word);
+  LAUNCH_CHECK();
+  h->obs_kinds = word;
+  return 0;
+}
+
 // the box of the call's own arguments, no geometry (Bp, K = 0: nothing reads them)
 extern "C" int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, const double* d_lb, const double* d_ub,
                               double* d_lambda, double* d_imu, double* d_mu, double mu_scale, double mu_max,
@@ -6052,7 +6127,7 @@ extern "C" int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, co
     return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_update_state, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), B, 0, h->prob.N,
                      h->prob.m, 0, (const double*)nullptr, d_us, d_lb, d_ub, d_lambda, d_imu, (const double*)nullptr, (size_t)0,
-                     (double*)nullptr, (double*)nullptr, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, d_al_converged);
+                     0u, (double*)nullptr, (double*)nullptr, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, d_al_converged);
   LAUNCH_CHECK();
   return 0;
 }
@@ -6067,7 +6142,7 @@ extern "C" int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_
   if (obs.p && (B != obs.B || !d_xs_q)) return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_update_state, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), B, padded_batch(B),
                      h->prob.N, h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
-                     const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
+                     const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_kinds, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
                      d_maxviol, d_al_converged);
   LAUNCH_CHECK();
   return 0;
@@ -6084,7 +6159,7 @@ extern "C" int tolg_al_mpc_step(tolg_handle_t h, int32_t B, const double* d_xs_q
   if (obs.p && (B != obs.B || !d_xs_q)) return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_mpc_step, dim3(B), dim3(AL_STEP_THREADS), 0, static_cast<hipStream_t>(stream), padded_batch(B), h->prob.N,
                      h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
-                     const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
+                     const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_kinds, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
                      d_maxviol, (int)shift);
   LAUNCH_CHECK();
   return 0;

@@ -92,7 +92,8 @@ class PolicyRollout:
     # policy_rollout(u_lb=, u_ub=): the applied inputs that differ from the commanded ones, and the margin the box lacked
     n_sat: Optional[torch.Tensor] = None           # [B, S] int32
     u_excess: Optional[torch.Tensor] = None        # [B, S]
-    # policy_rollout(clearance=True): min over knots and spheres of |t - c| - r, and the first knot that attains it
+    # policy_rollout(clearance=True): min over knots and slots of the clearance of the slot's kind (a keep-out sphere: |t - c| - r;
+    # kind_clearance), and the first knot that attains it
     clearance: Optional[torch.Tensor] = None       # [B, S]
     clearance_knot: Optional[torch.Tensor] = None  # [B, S] int32
 
@@ -189,12 +190,71 @@ def check_box(u_lb, u_ub, B, m, so3=False):
     return out[0], out[1]
 
 
-def inflate_obstacles(obstacles, xs_q, pos_cov, kappa):
+# The kinds of a constraint slot (TOLG_OBS_*, include/tolg.h has the table of rows and clearances), by number or by name
+OBSTACLE_KINDS = {"sphere": _capi.OBS_KEEP_OUT, "keep_in": _capi.OBS_KEEP_IN, "half_space": _capi.OBS_HALF_SPACE,
+                  "column": _capi.OBS_COLUMN_Z}
+
+
+def check_kinds(kinds, K):
+    """The kinds of K slots as a tuple of ints 0..3: a length-K sequence of ints or of OBSTACLE_KINDS names; None: K keep-out
+    spheres.  ValueError for another length or an unknown kind."""
+    if kinds is None:
+        return (0,) * int(K)
+    kinds = list(kinds)
+    if len(kinds) != int(K):
+        raise ValueError("kinds has %d entries, expected one per slot: K = %d" % (len(kinds), K))
+    out = []
+    for k in kinds:
+        if isinstance(k, str):
+            if k not in OBSTACLE_KINDS:
+                raise ValueError("unknown obstacle kind %r, expected one of %s" % (k, sorted(OBSTACLE_KINDS)))
+            out.append(OBSTACLE_KINDS[k])
+        elif isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 0 <= int(k) <= 3:
+            out.append(int(k))
+        else:
+            raise ValueError("unknown obstacle kind %r, expected 0..3 or one of %s" % (k, sorted(OBSTACLE_KINDS)))
+    return tuple(out)
+
+
+def check_kind_geometry(name, a, kinds):
+    """The fields of every slot under its kind, a [..., K, 4] numpy or torch: a positive radius in the spheres and the column,
+    a unit normal (||n| - 1| <= 1e-9, never rescaled: the offset is measured along it) in a half-space, whose offset may be
+    any finite number.  ValueError otherwise."""
+    for k, kd in enumerate(kinds):
+        s = a[..., k, :]
+        if kd == _capi.OBS_HALF_SPACE:
+            n2 = (s[..., :3] ** 2).sum(-1)
+            if bool((abs(n2 ** 0.5 - 1.0) > 1e-9).any()):
+                raise ValueError("%s: slot %d is a half-space and needs a unit normal (nx, ny, nz), | |n| - 1 | <= 1e-9" % (name, k))
+        elif bool((s[..., 3] <= 0.0).any()):
+            raise ValueError("%s: every radius must be positive (slot %d)" % (name, k))
+
+
+def kind_clearance(t, geo, kinds):
+    """The clearance of positions t [..., 3] from slots geo [..., K, 4] (shapes that broadcast) under `kinds`, [..., K], numpy
+    or torch alike: >= 0 inside the allowed set (tolg_policy_rollout_limited's d_clear is its minimum)."""
+    out = []
+    for k, kd in enumerate(kinds):
+        f = geo[..., k, :]
+        if kd == _capi.OBS_HALF_SPACE:
+            out.append(f[..., 3] - (f[..., :3] * t).sum(-1))
+            continue
+        d = t - f[..., :3]
+        d2 = (d[..., :2] ** 2).sum(-1) if kd == _capi.OBS_COLUMN_Z else (d ** 2).sum(-1)
+        c = d2 ** 0.5 - f[..., 3]
+        out.append(-c if kd == _capi.OBS_KEEP_IN else c)
+    return (torch if isinstance(out[0], torch.Tensor) else np).stack(out, -1)
+
+
+def inflate_obstacles(obstacles, xs_q, pos_cov, kappa, kinds=None):
     """Keep-out spheres with a margin for the closed-loop spread: obstacles [K, 4], [B, K, 4] or [B, N+1, K, 4] rows (cx, cy,
     cz, r), xs_q [B, N+1, 4, 4] the nominal plan, pos_cov [B, N+1, 3, 3] its position covariance (policy_covariance().pos_cov).
     Returns [B, N+1, K, 4] (numpy) with the radii r_ik + kappa sqrt(n_ik^T pos_cov_i n_ik), n_ik the unit vector from c_ik to
     the nominal position t_i: kappa standard deviations of the position along the line to the sphere, a radius per knot,
-    which is what al_fit_batch(obstacles=...) takes."""
+    which is what al_fit_batch(obstacles=...) takes.
+    kinds (check_kinds; None: all keep-out spheres): with sigma = sqrt(n^T pos_cov n) a keep-in sphere shrinks, r - kappa sigma
+    (ValueError where a radius stops being positive); a half-space moves in along its own normal n, o - kappa sigma; a column
+    grows, r + kappa sigma, with n the horizontal unit vector from its axis to t_i."""
     host = lambda a: np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)  # noqa: E731
     t, cov, o = host(xs_q)[..., :3, 3], host(pos_cov), host(obstacles)
     B, N1 = t.shape[:2]
@@ -202,11 +262,17 @@ def inflate_obstacles(obstacles, xs_q, pos_cov, kappa):
         o = np.broadcast_to(o if o.ndim == 2 else o[:, None], (B, N1) + o.shape[-2:])
     if o.shape[:2] != (B, N1) or o.shape[-1] != 4 or cov.shape != (B, N1, 3, 3):
         raise ValueError("inflate_obstacles: obstacles %s and pos_cov %s do not fit xs_q [%d, %d, 4, 4]" % (o.shape, cov.shape, B, N1))
+    kd = np.asarray(check_kinds(kinds, o.shape[2]))
     n = t[:, :, None, :] - o[..., :3]
+    n[..., 2] = np.where(kd == _capi.OBS_COLUMN_Z, 0.0, n[..., 2])
     n = n / np.maximum(np.linalg.norm(n, axis=-1, keepdims=True), 1e-300)
+    n = np.where((kd == _capi.OBS_HALF_SPACE)[:, None], o[..., :3], n)
     var = np.einsum("bika,biac,bikc->bik", n, cov, n)
     out = o.copy()
-    out[..., 3] += float(kappa) * np.sqrt(np.maximum(var, 0.0))
+    sign = np.where((kd == _capi.OBS_KEEP_IN) | (kd == _capi.OBS_HALF_SPACE), -1.0, 1.0)
+    out[..., 3] += sign * (float(kappa) * np.sqrt(np.maximum(var, 0.0)))
+    if np.any(out[..., kd == _capi.OBS_KEEP_IN, 3] <= 0.0):
+        raise ValueError("inflate_obstacles: a keep-in radius is not positive once kappa sigma is taken off")
     return out
 
 
@@ -252,7 +318,7 @@ _POLICY = {"tolg_solve_begin": "clear", "tolg_solve_begin_warm": "clear", "tolg_
            "tolg_solve_batch": "clear hold", "tolg_linearize_backward": "clear hold", "tolg_solve_end": "hold",
            "tolg_set_al_obstacles": "", "tolg_set_al_obstacles_moving": "",
            "tolg_al_update_state": "", "tolg_al_mpc_step": "",
-           "tolg_set_al_obstacle_windows": ""}  # (the last five leave it: listed for completeness)
+           "tolg_set_al_obstacle_windows": "", "tolg_set_al_obstacle_kinds": ""}  # (the last six leave it: listed for completeness)
 # A setter's detach call (BatchedTrackingILQR._detach): its arguments behind the handle with the source pointer null, the
 # stream's place included.  tolg_set_al_obstacles detaches the per-knot form too.
 _DETACH = {"tolg_set_refs": (0, None, None, None, 0, None), "tolg_set_weights": (0, None, None, None, None, 0, None),
@@ -294,6 +360,7 @@ class BatchedTrackingILQR:
         self._inflight = (None, None)  # the FitResult of the solve in flight; the inputs the stream may not have read (_hold)
         self._al = None            # the augmented-Lagrangian terms the handle points at (set_al)
         self._obs = None           # ... and the keep-out spheres (set_al_obstacles): (obstacles, lam, imu) on the device
+        self._obs_kinds = ()       # ... with the kinds the handle holds for them (tolg_set_al_obstacle_kinds), one per slot
         p = _capi.Problem()
         p.kind, p.m, p.N, p.dt = _KIND[problem.kind], self.m, self.N, float(problem.dt)
         p.pend_mass, p.pend_length = float(problem.pend_mass), float(problem.pend_length)
@@ -599,12 +666,13 @@ class BatchedTrackingILQR:
             self._al = (lb, ub, lam, imu)  # the handle reads them in every solve until they are detached
             self._call("tolg_set_al", _ptr(lb), _ptr(ub), _ptr(lam), _ptr(imu), stream=False)
 
-    def _check_obstacles(self, B, obstacles):
+    def _check_obstacles(self, B, obstacles, kinds=None):
         """Keep-out spheres [K, 4] (every trajectory the same), [B, K, 4], or per knot [B, N+1, K, 4], rows (cx, cy, cz, r),
         checked on the host: ValueError before anything reaches the device for a model without translation, a wrong shape (the
         per-knot form must have N + 1 knots), K outside 1..MAX_OBSTACLES, a non-finite value or a radius that is not positive
         at any knot.  B = None takes B from a [B, K, 4] or [B, N+1, K, 4] array.  Returns (B, [B, K, 4] or [B, N+1, K, 4]
-        float64 numpy)."""
+        float64 numpy).  kinds: the slots' kinds (check_kinds), which decide how the four fields are read and checked
+        (check_kind_geometry)."""
         if self.problem.kind in ("so3", "pendulum3d"):
             raise ValueError("keep-out spheres constrain the translation: the %s model has none" % self.problem.kind)
         a = obstacles.detach().cpu().numpy() if isinstance(obstacles, torch.Tensor) else obstacles
@@ -620,22 +688,35 @@ class BatchedTrackingILQR:
         a = _checked("obstacles", a, (B, None, 4) if a.ndim == 3 else (B, self.N + 1, None, 4))
         if not 1 <= a.shape[-2] <= _capi.MAX_OBSTACLES:
             raise ValueError("obstacles: K = %d spheres per trajectory, expected 1..%d" % (a.shape[-2], _capi.MAX_OBSTACLES))
-        if np.any(a[..., 3] <= 0.0):
-            raise ValueError("obstacles: every radius must be positive")
+        check_kind_geometry("obstacles", a, check_kinds(kinds, a.shape[-2]))
         return B, np.ascontiguousarray(a)
 
-    def set_al_obstacles(self, obstacles=None, lam=None, imu=None):
+    def _set_kinds(self, K, kinds):
+        """Behind an attach of K slots: the handle keeps its kinds over a re-attach with the same K and resets them otherwise
+        (tolg_set_al_obstacle_kinds), so the call is made only where what it holds is not `kinds`."""
+        held = self._obs_kinds if len(self._obs_kinds) == K else (0,) * K
+        if kinds != held:
+            arr = (C.c_int32 * K)(*kinds)
+            self._call("tolg_set_al_obstacle_kinds", K, arr if any(kinds) else None)
+        self._obs_kinds = kinds
+
+    def set_al_obstacles(self, obstacles=None, lam=None, imu=None, kinds=None):
         """Attach (or detach with obstacles=None) keep-out spheres: the augmented-Lagrangian terms of g_k = r_k^2 - |t - c_k|^2
         <= 0 at every knot, terminal included (tolg_set_al_obstacles).  obstacles [K, 4] (broadcast) or [B, K, 4] rows (cx, cy,
         cz, r), or [B, N+1, K, 4]: spheres that move, the geometry of every knot (tolg_set_al_obstacles_moving; its packed
         buffer, N + 1 times the static one, is allocated for the B and K asked for); lam, imu [B, N+1, K]: the multipliers and the diagonal of I_mu (device tensors the handle reads in every solve
-        until they are detached; None: zeros).  Every batch call must then be for this B."""
+        until they are detached; None: zeros).  Every batch call must then be for this B.
+        kinds: a length-K sequence of ints or of "sphere" | "keep_in" | "half_space" | "column" (OBSTACLE_KINDS), the kind of
+        slot k in every trajectory and at every knot; None: keep-out spheres.  The fields of a slot are then read per kind:
+        (cx, cy, cz, r) with g = |d|^2 - r^2 for a keep-in sphere, (nx, ny, nz, o) with |n| = 1 and g = n.t - o for a
+        half-space, (cx, cy, -, r) with g = r^2 - (dx^2 + dy^2) for a vertical column."""
         if obstacles is None:
-            self._obs = None
+            self._obs, self._obs_kinds = None, ()
             self._detach("tolg_set_al_obstacles")
             return
         Bl = None if lam is None else int(lam.shape[0])
-        B, a = self._check_obstacles(Bl, obstacles)
+        B, a = self._check_obstacles(Bl, obstacles, kinds)
+        kinds = check_kinds(kinds, a.shape[-2])
         K, moving = a.shape[-2], a.ndim == 4
         lam, imu = self._obs_multipliers(B, K, lam, imu)
         dest = (self._packed("_obs_mov_buf", self.lib.tolg_obstacles_moving_bytes, K, B=B) if moving else
@@ -643,6 +724,7 @@ class BatchedTrackingILQR:
         d = self._dev(a, a.shape)
         self._obs = (d, lam, imu)  # the handle reads the multipliers in every solve until they are detached
         self._call("tolg_set_al_obstacles" + ("_moving" if moving else ""), B, K, _ptr(d), _ptr(lam), _ptr(imu), *dest)
+        self._set_kinds(K, kinds)
 
     def _obs_multipliers(self, B, K, lam, imu):
         """The spheres' multipliers lam, imu [B, N+1, K] checked (contiguous float64 on the device; None: zeros), and B."""
@@ -659,7 +741,7 @@ class BatchedTrackingILQR:
             raise ValueError("obstacles for B = %d trajectories, expected 1..%d" % (B, self.max_batch))
         return lam, imu
 
-    def _check_obstacle_paths(self, B, path_obs):
+    def _check_obstacle_paths(self, B, path_obs, kinds=None):
         """World-time sphere paths [B, T+1, K, 4], rows (cx, cy, cz, r), checked under _check_obstacles' rules (T >= 1 in place of
         the horizon).  The paths are large (116 MB at 4096 x 220, K = 4): a tensor that is on the solver's device already is
         checked there -- two reductions and one flag read back -- and never copied through the host; anything else is checked
@@ -672,39 +754,45 @@ class BatchedTrackingILQR:
             raise ValueError("obstacle_paths has %d knots, expected T+1 >= 2" % a.shape[1])
         if not 1 <= a.shape[2] <= _capi.MAX_OBSTACLES:
             raise ValueError("obstacle_paths: K = %d spheres per trajectory, expected 1..%d" % (a.shape[2], _capi.MAX_OBSTACLES))
-        if on_device:
+        kinds = check_kinds(kinds, a.shape[2])
+        if on_device and not any(kinds):
             v = a.detach()
             finite, positive = (bool(f) for f in torch.stack([torch.isfinite(v).all(), (v[..., 3] > 0.0).all()]).tolist())
+        elif on_device:
+            finite, positive = bool(torch.isfinite(a.detach()).all()), True
         else:
-            finite, positive = True, not np.any(a[..., 3] <= 0.0)  # (_checked has refused a non-finite value)
+            finite, positive = True, not (np.any(a[..., 3] <= 0.0) and not any(kinds))  # (_checked has refused a non-finite value)
         if not finite:
             raise ValueError("obstacle_paths must be finite")
         if not positive:
             raise ValueError("obstacle_paths: every radius must be positive")
+        if any(kinds):
+            check_kind_geometry("obstacle_paths", a.detach() if on_device else a, kinds)
         return a.shape[0], a if on_device else np.ascontiguousarray(a)
 
-    def _set_obstacle_windows(self, B, d_paths, t0_d, t, lam, imu):
+    def _set_obstacle_windows(self, B, d_paths, t0_d, t, lam, imu, kinds=None):
         K, T = d_paths.shape[2], d_paths.shape[1] - 1
         self._obs = (d_paths, lam, imu)
         self._call("tolg_set_al_obstacle_windows", B, K, _ptr(d_paths), int(T), _ptr(t0_d), int(t), _ptr(lam), _ptr(imu),
                    *self._packed("_obs_mov_buf", self.lib.tolg_obstacles_moving_bytes, K, B=B))
+        self._set_kinds(K, check_kinds(kinds, K))
 
-    def set_al_obstacle_windows(self, path_obs, t, t0=None, lam=None, imu=None):
+    def set_al_obstacle_windows(self, path_obs, t, t0=None, lam=None, imu=None, kinds=None):
         """Attach the moving keep-out spheres of step t, gathered on the device from world-time paths
         (tolg_set_al_obstacle_windows): path_obs [B, T+1, K, 4] rows (cx, cy, cz, r) of trajectory b's spheres at world knot s;
         knot i of the window takes world knot min(t0[b] + t + i, T), set_ref_windows' rule (t0 an int array [B], None: 0).  The
-        handle is then as after set_al_obstacles with the gathered [B, N+1, K, 4] field; lam, imu [B, N+1, K] as there.
-        path_obs = None detaches."""
+        handle is then as after set_al_obstacles with the gathered [B, N+1, K, 4] field; lam, imu [B, N+1, K] and kinds as
+        there.  path_obs = None detaches."""
         if path_obs is None:
             return self.set_al_obstacles(None)
         if int(t) < 0:
             raise ValueError("t must be non-negative")
-        B, a = self._check_obstacle_paths(None if lam is None else int(lam.shape[0]), path_obs)
+        B, a = self._check_obstacle_paths(None if lam is None else int(lam.shape[0]), path_obs, kinds)
         lam, imu = self._obs_multipliers(B, a.shape[2], lam, imu)
         t0_d = self._check_t0(B, t0)
         d = self._dev(a, a.shape)
         self._hold((d, t0_d))
-        self._set_obstacle_windows(B, d, t0_d, int(t), lam, imu)
+        self._set_obstacle_windows(B, d, t0_d, int(t), lam, imu, kinds)
 
     def al_mpc_step(self, xs_q, us, mu, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2, shift=True):
         """The outer augmented-Lagrangian update of one MPC step over everything attached (tolg_al_mpc_step): the multipliers
@@ -730,13 +818,13 @@ class BatchedTrackingILQR:
 
     def al_fit_batch(self, x0_q, x0_xi, us_init, lb=None, ub=None, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
                      tol_d_norm=1e-6, tol_constr=1e-2, mu0=1e-2, mu_scale=10.0, mu_max=1e8, line_search=False,
-                     on_outer=None, q_ref=None, xi_ref=None, Q=None, P=None, R=None, obstacles=None):
+                     on_outer=None, q_ref=None, xi_ref=None, Q=None, P=None, R=None, obstacles=None, obstacle_kinds=None):
         """AL_iLQR_Tracking_SE3_MS.fit (reference traoptlibrary/traopt_controller.py:3218-3267) for B
         independent problems: every outer iteration re-solves from (x0, us_init) -- no warm start, as in
         the reference -- then updates multipliers on the device.  Returns (FitResult, info dict).
         q_ref / xi_ref: a reference per trajectory, Q / P / R: weights per trajectory, as for fit_batch.
         Constraints: the input box lb <= u <= ub, keep-out spheres obstacles ([K, 4], [B, K, 4] or per knot [B, N+1, K, 4],
-        set_al_obstacles), or both
+        set_al_obstacles; obstacle_kinds: its kinds=, a kind per slot -- keep-in sphere, half-space, column), or both
         (one mu per problem, joint convergence: tolg_al_update_state).  With spheres the info dict also holds lmbd_obs and
         Imu_obs [B, N+1, K]; max_violation covers every constraint."""
         if (lb is None) != (ub is None):
@@ -745,7 +833,9 @@ class BatchedTrackingILQR:
             raise ValueError("al_fit_batch needs a constraint: lb / ub, obstacles, or both")
         b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R))
         B = b.B
-        obs = None if obstacles is None else self._check_obstacles(B, obstacles)[1]
+        if obstacles is None and obstacle_kinds is not None:
+            raise ValueError("obstacle_kinds describe obstacles: none were given")
+        obs = None if obstacles is None else self._check_obstacles(B, obstacles, obstacle_kinds)[1]
         o = self._options("ms", n_ilqr_iters, line_search, "nonlinear", tol_grad_norm, tol_d_norm, 1e10)
         f64 = dict(dtype=torch.float64, device=self.device)
         box = lb is not None
@@ -762,7 +852,7 @@ class BatchedTrackingILQR:
             lam_o = torch.zeros(B, self.N + 1, obs.shape[-2], **f64)
             imu_o = torch.full((B, self.N + 1, obs.shape[-2]), float(mu0), **f64)
             try:
-                self.set_al_obstacles(obs, lam_o, imu_o)
+                self.set_al_obstacles(obs, lam_o, imu_o, obstacle_kinds)
             except Exception:
                 if box:
                     self.set_al(None)
@@ -803,7 +893,8 @@ class BatchedTrackingILQR:
             info.update(lmbd_obs=lam_o, Imu_obs=imu_o)
         return final, info
 
-    def plan_fleet(self, x0_q, x0_xi, us_init, q_ref, xi_ref, fleet, separation, obstacles=None, lb=None, ub=None, **al_kw):
+    def plan_fleet(self, x0_q, x0_xi, us_init, q_ref, xi_ref, fleet, separation, obstacles=None, lb=None, ub=None,
+                   obstacle_kinds=None, **al_kw):
         """Prioritised planning for F = B / fleet independent fleets in one batch: trajectory b is member p = b % fleet of
         fleet b // fleet.  Round p = 0 .. fleet-1 solves the F members p, each on its own reference (q_ref [B, N+1, 4, 4],
         xi_ref [B, N+1, 6]), keeping out of the caller's static `obstacles` ([K0, 4] or [B, K0, 4]) and of p moving spheres of
@@ -812,7 +903,8 @@ class BatchedTrackingILQR:
         [B, ...] -- go to it).  Round 0 with neither obstacles nor a box is a plain fit_batch with al_fit_batch's inner options.
         The constraint holds at the knots, not between them: two members may pass closer than `separation` between two knots.
         A lower-priority member yields to a higher one: member 0 plans as if alone, and whether member p finds a way round the
-        others is its own round's convergence.  K0 + fleet - 1 <= MAX_OBSTACLES.
+        others is its own round's convergence.  K0 + fleet - 1 <= MAX_OBSTACLES.  obstacle_kinds: the kinds of the caller's K0
+        static slots (set_al_obstacles' kinds=); the member spheres behind them are keep-out spheres.
         Returns (FitResult in batch order, info): min_separation [F] the smallest centre distance over knots and pairs of
         the final plans (inf for fleet = 1), max_violation [B], al_converged [B] int32 (rounds without a constraint: 0 and
         1), outer_iterations [fleet] (python ints)."""
@@ -827,10 +919,13 @@ class BatchedTrackingILQR:
         q_ref, xi_ref = self._check_refs(B, q_ref, xi_ref) or (None, None)
         if q_ref is None:
             raise ValueError("plan_fleet needs a reference per trajectory: q_ref and xi_ref")
-        static = None if obstacles is None else self._check_obstacles(B, obstacles)[1]
+        if obstacles is None and obstacle_kinds is not None:
+            raise ValueError("obstacle_kinds describe obstacles: none were given")
+        static = None if obstacles is None else self._check_obstacles(B, obstacles, obstacle_kinds)[1]
         if static is not None and static.ndim != 3:
             raise ValueError("plan_fleet: obstacles are static, [K0, 4] or [B, K0, 4]")
         K0 = 0 if static is None else static.shape[1]
+        kinds0 = check_kinds(obstacle_kinds, K0)
         if K0 + G - 1 > _capi.MAX_OBSTACLES:
             raise ValueError("plan_fleet: %d spheres + %d other members exceed %d spheres per trajectory"
                              % (K0, G - 1, _capi.MAX_OBSTACLES))
@@ -854,7 +949,8 @@ class BatchedTrackingILQR:
                 outers.append(1)
             else:
                 obs = np.concatenate(field, axis=2) if pos else None if static is None else static[sl]
-                res, info = self.al_fit_batch(x0_q[sl], x0_xi[sl], us_init[sl], lb, ub, obstacles=obs, **al_kw, **kw)
+                res, info = self.al_fit_batch(x0_q[sl], x0_xi[sl], us_init[sl], lb, ub, obstacles=obs,
+                                              obstacle_kinds=None if obs is None else kinds0 + (0,) * len(pos), **al_kw, **kw)
                 maxviol[sl], alconv[sl] = info["max_violation"], info["al_converged"]
                 outers.append(info["outer_iterations"])
             rounds.append(res)
@@ -1033,7 +1129,8 @@ class BatchedTrackingILQR:
         to it before the dynamics step, J and us take the clamped input (tolg_policy_rollout_limited); the result then carries
         n_sat [B, S], how many inputs of the sample the box moved, and u_excess [B, S], the largest distance by which a command
         left it.  clearance=True: the result carries clearance [B, S], min over knots and spheres of |t - c| - r for the
-        keep-out spheres attached by set_al_obstacles (negative: the sample entered one), and clearance_knot, the first knot
+        keep-out spheres attached by set_al_obstacles (negative: the sample entered one; a slot of another kind enters with
+        the clearance of its kind, kind_clearance), and clearance_knot, the first knot
         that attains it; ValueError when none are attached.  With none of the three the call is tolg_policy_rollout."""
         B = self._held_B()
         if clearance and self._obs is None:
@@ -1235,8 +1332,8 @@ class BatchedTrackingILQR:
     def mpc(self, x0_q, x0_xi, path_q, path_xi, steps, us_init=None, t0=None, iters_per_step=5, first_iters=50,
             warm="states", noise=None, mode="ms", line_search=False, rollout="nonlinear", tol_grad_norm=1e-6, tol_d_norm=1e-6,
             check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None, plant_J=None, plant_pend=None, u_lb=None,
-            u_ub=None, lb=None, ub=None, obstacles=None, obstacle_paths=None, first_al_iters=3, al_iters_per_step=1, mu0=1e-2,
-            mu_scale=10.0, mu_max=1e8, tol_constr=1e-2) -> MPCResult:
+            u_ub=None, lb=None, ub=None, obstacles=None, obstacle_paths=None, obstacle_kinds=None, first_al_iters=3,
+            al_iters_per_step=1, mu0=1e-2, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2) -> MPCResult:
         """Receding-horizon MPC: `steps` closed-loop steps of B trajectories, each tracking its own path from its own phase.
         Step t: windows min(t0[b] + t + i, T) of the paths (tolg_set_ref_windows), a solve of first_iters (t = 0) or
         iters_per_step iterations, then tolg_mpc_advance applies u*_0, steps the plant with the exact dynamics and adds the
@@ -1256,7 +1353,8 @@ class BatchedTrackingILQR:
         The planner's constraints (augmented Lagrangian, mode="ms" only; with none of them the loop is the one above): lb / ub
         [m], the input box of set_al (the SO3 family takes the box only); obstacles [K, 4] or [B, K, 4], static keep-out
         spheres, or obstacle_paths [B, T_o+1, K, 4], spheres in world time indexed with the same t0 (window t is gathered by
-        tolg_set_al_obstacle_windows); at most one of the two.  Step t then runs first_al_iters (t = 0) or al_iters_per_step
+        tolg_set_al_obstacle_windows); at most one of the two; obstacle_kinds: the kind of each of their K slots
+        (set_al_obstacles' kinds=; the clearance is then each kind's own).  Step t then runs first_al_iters (t = 0) or al_iters_per_step
         outer rounds: each a solve as above followed by tolg_al_mpc_step, which shifts the multipliers by one knot behind the
         step's last round; round 0 starts as above, round a > 0 from round a-1's solution under the `warm` rule.  The
         multipliers start at lambda = 0, I_mu = mu = mu0 (mu_scale, mu_max, tol_constr: al_fit_batch's).  The result carries
@@ -1280,6 +1378,8 @@ class BatchedTrackingILQR:
             raise ValueError("the input box needs both lb and ub")
         if obstacles is not None and obstacle_paths is not None:
             raise ValueError("give obstacles (static) or obstacle_paths (world time), not both")
+        if obstacle_kinds is not None and obstacles is None and obstacle_paths is None:
+            raise ValueError("obstacle_kinds describe obstacles: none were given")
         constrained = lb is not None or obstacles is not None or obstacle_paths is not None
         if constrained and mode != "ms":
             raise ValueError("the augmented-Lagrangian constraints need mode='ms'")
@@ -1307,11 +1407,12 @@ class BatchedTrackingILQR:
             al = (self._dev(_checked("lb", lb, (self.m,)), (self.m,)), self._dev(_checked("ub", ub, (self.m,)), (self.m,)),
                   torch.zeros(B, self.N, 2 * self.m, **f64), torch.full((B, self.N, 2 * self.m), float(mu0), **f64))
         if obstacles is not None or obstacle_paths is not None:
-            geo = (self._check_obstacles(B, obstacles)[1] if obstacles is not None else
-                   self._check_obstacle_paths(B, obstacle_paths)[1])
+            geo = (self._check_obstacles(B, obstacles, obstacle_kinds)[1] if obstacles is not None else
+                   self._check_obstacle_paths(B, obstacle_paths, obstacle_kinds)[1])
             if obstacles is not None and geo.ndim != 3:
                 raise ValueError("mpc: obstacles are static, [K, 4] or [B, K, 4]; spheres that move are obstacle_paths")
             Ko = geo.shape[-2]
+            kinds = check_kinds(obstacle_kinds, Ko)
             obs = (self._dev(geo, geo.shape), torch.zeros(B, self.N + 1, Ko, **f64),
                    torch.full((B, self.N + 1, Ko), float(mu0), **f64), obstacle_paths is not None)
         if constrained:
@@ -1335,13 +1436,13 @@ class BatchedTrackingILQR:
             if al is not None:
                 self.set_al(*al)
             if obs is not None and not obs[3]:
-                self.set_al_obstacles(*obs[:3])
+                self.set_al_obstacles(*obs[:3], kinds)
             if constrained:
                 res.max_violation, res.mu = torch.empty(B, steps, **f64), mu
             for t in range(steps):
                 self._set_ref_windows(B, pq, pxi, T, t0_d, t)
                 if obs is not None and obs[3]:
-                    self._set_obstacle_windows(B, obs[0], t0_d, t, obs[1], obs[2])
+                    self._set_obstacle_windows(B, obs[0], t0_d, t, obs[1], obs[2], kinds)
                 n = K0 if t == 0 else K
                 o = self._options(mode, n, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg)
                 xs = None
@@ -1383,7 +1484,10 @@ class BatchedTrackingILQR:
                     geo = geo[torch.arange(B, device=self.device)[:, None], s.clamp(max=geo.shape[1] - 1).expand(B, steps + 1)]
                 else:
                     geo = geo[:, None]
-                d = (res.xs_q[:, :, None, :3, 3] - geo[..., :3]).norm(dim=-1) - geo[..., 3]
+                if any(kinds):
+                    d = kind_clearance(res.xs_q[:, :, :3, 3], geo, kinds)
+                else:
+                    d = (res.xs_q[:, :, None, :3, 3] - geo[..., :3]).norm(dim=-1) - geo[..., 3]
                 res.clearance = d.amin(dim=-1)
         finally:
             self._use_pt(B, None, None)

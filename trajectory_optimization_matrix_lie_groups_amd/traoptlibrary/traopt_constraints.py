@@ -129,6 +129,68 @@ class MovingSphereObstacleConstraint(SphereObstacleConstraint):
         return self._centers[i], self._radii[i]
 
 
+class PositionObstacleConstraint(BaseConstraint):
+    """Position constraints of a kind per slot (tolg_set_al_obstacle_kinds), beside SphereObstacleConstraint and with its
+    interface: obstacles [K, 4], or [N+1, K, 4] with the geometry of every knot, rows (f0, f1, f2, f3) read per kind, kinds a
+    length-K sequence of 0..3.  With d = t - (f0, f1, f2):
+      0 keep-out sphere  g = r^2 - |d|^2          grad_t g = -2 d
+      1 keep-in sphere   g = |d|^2 - r^2          grad_t g = 2 d
+      2 half-space       g = n.t - o, |n| = 1     grad_t g = n
+      3 vertical column  g = r^2 - (dx^2 + dy^2)  grad_t g = -2 (dx, dy, 0)
+    In the error coordinates (X Exp(delta), twist order [omega, v]) g_x = [0, (grad_t g)^T R, 0], g_u = 0."""
+
+    def __init__(self, obstacles, kinds, state_size=(6, 6), action_size=6):
+        o = np.asarray(obstacles, dtype=np.float64)
+        if o.ndim not in (2, 3) or o.shape[-1] != 4:
+            raise ValueError("obstacles has shape %s, expected (K, 4) or (N+1, K, 4)" % (o.shape,))
+        k = np.asarray(kinds)
+        if k.shape != (o.shape[-2],) or not np.issubdtype(k.dtype, np.integer) or np.any(k < 0) or np.any(k > 3):
+            raise ValueError("kinds: one of 0..3 per slot")
+        self._obs = o.copy()
+        self._kinds = k.astype(np.int64)
+        self._state_size = state_size[0] + state_size[1]
+        self._error_state_size = state_size[0]
+        self._vel_state_size = state_size[1]
+        self._action_size = action_size
+        self._constr_size = o.shape[-2]
+
+    kinds = property(lambda self: self._kinds)
+    constr_size = property(lambda self: self._constr_size)
+    state_size = property(lambda self: self._state_size)
+    error_state_size = property(lambda self: self._error_state_size)
+    vel_state_size = property(lambda self: self._vel_state_size)
+    action_size = property(lambda self: self._action_size)
+
+    def obstacles(self):
+        """The slots as given, [K, 4] or [N+1, K, 4]: a trajectory's slice of tolg_set_al_obstacles(_moving)."""
+        return self._obs
+
+    def _rows(self, x, i):
+        """(g [K], grad_t g [K, 3]) at knot i"""
+        o = self._obs if self._obs.ndim == 2 else self._obs[i]
+        t = np.asarray(x[0])[:3, 3]
+        kd = self._kinds
+        d = t[None] - o[:, :3]
+        d[kd == 3, 2] = 0.0
+        g = o[:, 3] ** 2 - np.sum(d * d, axis=1)
+        grad = -2.0 * d
+        g[kd == 1], grad[kd == 1] = -g[kd == 1], -grad[kd == 1]
+        hs = kd == 2
+        g[hs], grad[hs] = o[hs, :3] @ t - o[hs, 3], o[hs, :3]
+        return g, grad
+
+    def g(self, x, u, i, terminal=False, *args, **kwargs):
+        return self._rows(x, i)[0]
+
+    def g_x(self, x, u, i, terminal=False, *args, **kwargs):
+        gx = np.zeros((self._constr_size, self._state_size))
+        gx[:, 3:6] = self._rows(x, i)[1] @ np.asarray(x[0])[:3, :3]
+        return gx
+
+    def g_u(self, x, u, i, terminal=False, *args, **kwargs):
+        return np.zeros((self._constr_size, self._action_size))
+
+
 class ConstraintStack(BaseConstraint):
     """Several constraints as one: g, g_x, g_u concatenated in the order given."""
 

@@ -370,6 +370,59 @@ def drone_obstacle_field(B, K, N=400, seed=SEED):
     return prob, x0_q, x0_xi, us0, _obstacle_field(prob.q_ref, B, K, 0.1, 0.2, seed + 3)
 
 
+CORRIDOR_KINDS = ("half_space", "half_space", "keep_in", "column", "column", "sphere")
+
+
+def _corridor(q_ref, x0_q, r_lo, r_hi, seed):
+    """The six slots of a flight corridor per trajectory (kinds CORRIDOR_KINDS, tolg_set_al_obstacle_kinds), laid over the
+    middle half of the reference path so that the path breaks each of them while the start x0 of every trajectory keeps them:
+      floor    (0, 0, -1, -z_f): z >= z_f, a quarter of the middle half's height above its lowest knot, but below the start;
+      ceiling  (0, 0, 1, z_c):   z <= z_c, a quarter of that height below its highest knot, but above the start;
+      geofence of radius D, the distance from the start to the knot p furthest from it, centred 0.05 D behind the start on
+               the line from p: the start lies deep inside and p 0.05 D outside;
+      two columns through knots of the second and third quarter, radius in [r_lo, r_hi] and at most half the horizontal
+               distance to the start;
+      one keep-out sphere of _obstacle_field.
+    Returns obstacles [B, 6, 4]."""
+    t = np.asarray(q_ref)[:, :3, 3]
+    N = t.shape[0] - 1
+    B = x0_q.shape[0]
+    rng = np.random.default_rng(seed)
+    mid = t[N // 4: N // 4 + max(2, N // 2)]
+    zlo, zhi = mid[:, 2].min(), mid[:, 2].max()
+    h = zhi - zlo
+    obs = np.empty((B, 6, 4))
+    obs[:, 5] = _obstacle_field(q_ref, B, 1, r_lo, r_hi, seed + 1)[:, 0]
+    for b in range(B):
+        s = np.asarray(x0_q[b]).reshape(4, 4)[:3, 3]
+        obs[b, 0] = (0.0, 0.0, -1.0, -min(zlo + 0.25 * h, s[2] - 0.1 * h))
+        obs[b, 1] = (0.0, 0.0, 1.0, max(zhi - 0.25 * h, s[2] + 0.1 * h))
+        p = mid[np.argmax(np.linalg.norm(mid - s, axis=1))]
+        D = np.linalg.norm(p - s)
+        obs[b, 2, :3], obs[b, 2, 3] = s - 0.05 * (p - s), D
+        for k in range(2):
+            c = mid[int(rng.integers(k * len(mid) // 2, (k + 1) * len(mid) // 2))]
+            r = min(rng.uniform(r_lo, r_hi), 0.5 * np.linalg.norm(c[:2] - s[:2]))
+            obs[b, 3 + k] = (c[0], c[1], 0.0, r)
+    return obs
+
+
+def se3_corridor(B, N=200, seed=SEED):
+    """se3_tracking's workload inside a flight corridor of six slots of four kinds (_corridor: floor, ceiling, geofence, two
+    columns of radius 0.15 .. 0.3, one keep-out sphere), different for every trajectory; the unconstrained tracking optimum
+    breaks them.  Returns (prob, x0_q, x0_xi, us0, obstacles [B, 6, 4], kinds): what al_fit_batch(obstacles=,
+    obstacle_kinds=) takes."""
+    prob, x0_q, x0_xi, us0 = se3_tracking(B, N=N, seed=seed)
+    return prob, x0_q, x0_xi, us0, _corridor(prob.q_ref, x0_q, 0.15, 0.3, seed + 7), CORRIDOR_KINDS
+
+
+def drone_corridor(B, N=400, seed=SEED):
+    """The drone variant (drone_tracking's workload) of se3_corridor, columns and sphere of radius 0.08 .. 0.15.  Returns
+    (prob, x0_q, x0_xi, us0, obstacles [B, 6, 4], kinds)."""
+    prob, x0_q, x0_xi, us0 = drone_tracking(B, N=N, seed=seed)
+    return prob, x0_q, x0_xi, us0, _corridor(prob.q_ref, x0_q, 0.08, 0.15, seed + 7), CORRIDOR_KINDS
+
+
 def se3_moving_obstacle_field(B, K, N=200, seed=SEED):
     """se3_obstacle_field's workload with its spheres in motion: sphere k of trajectory b drifts with a constant seeded velocity
     (0.5 .. 1.5 radii over a quarter of the horizon) and is at its static centre -- on the reference path -- at the knot whose
