@@ -540,6 +540,75 @@ int tolg_policy_covariance(tolg_handle_t h, int32_t B, const double* d_Sigma0, c
 int tolg_policy_value(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, double* d_P, double* d_p,
                       double* d_diag_P, double* d_price, double* d_excess, void* stream);
 
+/* Output feedback: the held policy acting on a Kalman filter's estimate instead of the true state.  Every closed loop above
+ * feeds the true state into u = u*_i + K_i e_i; a vehicle knows its state through noisy sensors only, and the covariance of
+ * tolg_policy_covariance (and the margins derived from its d_pos_cov) is optimistic by what the estimate adds.  The two calls
+ * below are the analytic recursion and its sampled check, in the error coordinates of K and of tolg_policy_rollout:
+ * e = [Log(q*^-1 q); xi - xi*], twist order [omega, v], right perturbation x (+) d = (q Exp(d[0:6]), xi + d[6:12]).
+ *
+ * The measurement model, shared by both: coordinates of the error state, measured at every knot 0..N.
+ *   mask      int32, 12 bits: bit j set = coordinate j is measured.  A host argument shared by the batch (as
+ *             tolg_set_al_obstacle_kinds' kinds word); 0 is legal (no sensor).  SO3 family: bits 3..5 and 9..11 must be clear.
+ *   d_V       [B][12] measurement-noise variances (diagonal noise covariance), > 0 and finite on the measured coordinates by
+ *             the caller's promise; entries of unmeasured coordinates are not read; may be NULL when mask == 0.
+ *
+ * tolg_policy_covariance_estimated: one forward sweep.  A_i, B_i, Acl_i = A_i + B_i K_i are linearised by this call at the held
+ * nominal exactly as tolg_policy_covariance does.  P is the covariance of the estimation error e - e^, S^ that of the estimate's
+ * deviation e^; the filter's prior at knot 0 is the nominal: P_0^- = Sigma0, S^_0^- = 0.
+ *   at knot i = 0..N:
+ *     Sigma_i = S^_i^- + P_i^-                                             the true state's covariance
+ *     P^+ = P_i^-; for each measured j ascending: s = P^+[j][j] + V[j], c = P^+[:, j], P^+ -= c c^T / s
+ *     L_i[:, j] = P^+[:, j] / V[j] (measured j), 0 (unmeasured j)          the Kalman gain, no matrix inverse
+ *     S^_i^+ = S^_i^- + (P_i^- - P^+)
+ *   for i < N:
+ *     var_u_i = diag K_i S^_i^+ K_i^T
+ *     P_{i+1}^- = A_i P^+ A_i^T + E W E^T,  E = [0; I6];    S^_{i+1}^- = Acl_i S^_i^+ Acl_i^T
+ * (sequential scalar updates are exact for a diagonal V; Sigma = S^ + P rests on the orthogonality of estimate and error.)
+ * The recursion is first order in the MODEL's Jacobians, the ones the solver plans with (the note at tolg_policy_value): the
+ * reference's f_x is approximate in its twist columns, by an amount that grows with the nominal twist (against central
+ * differences of f: 4e-3 at |xi| = 0.1, 0.4 at |xi| = 3).  Perfect-state feedback suppresses what that leaves; a filter without
+ * a twist sensor carries the twist's estimation error open loop through those columns, and on a fast nominal the sampled
+ * loop below can differ from this recursion by far more than its sampling error.  Check with tolg_policy_rollout_estimated.
+ *   in : d_Sigma0, d_W as tolg_policy_covariance (NULL = 0, upper triangles only); mask, d_V above
+ *   out: d_Sigma [B][N+1][12][12]    the true state's covariance, equal to its transpose to the bit
+ *        d_P_post [B][N+1][12][12]   P^+_i, equal to its transpose to the bit
+ *        d_L [B][N+1][12][12]        the Kalman gains (what tolg_policy_rollout_estimated takes)
+ *        d_var_x [B][N+1][12]        diag Sigma_i (the bits of d_Sigma's diagonal)
+ *        d_var_est [B][N+1][12]      diag P^+_i (the bits of d_P_post's diagonal)
+ *        d_var_u [B][N][m]           the input variance the feedback spends
+ *        d_pos_cov [B][N+1][6]       as tolg_policy_covariance, from Sigma
+ * Every output may be NULL, and a NULL output costs nothing.  A trajectory's bits depend on neither B nor its neighbours, nor on
+ * which outputs are asked for.  Sigma0 = W = 0 gives exact zeros; mask = 0 gives L = 0, var_u = 0 and P_post = the prior.  A plant,
+ * an input box and constraint geometry are ignored; the held policy is left alone.
+ * TOLG_E_ARG: the conditions of tolg_solve_gains; a mask outside 12 bits; SO3-family bits 3..5 / 9..11; a NULL d_V with
+ * mask != 0; a non-NULL d_pos_cov for the SO3 family.
+ *
+ * tolg_policy_rollout_estimated: S samples per trajectory of the nonlinear loop with a filter of scheduled gains.  Sample (b, s):
+ *   x_0 = x*_0 (+) dx0,  x^_0 = x*_0
+ *   at knot i = 0..N:
+ *     y = x_i (+) n[b][s][i]
+ *     r[j] = ([Log(q^^-1 q_y); xi_y - xi^])[j] for measured j, 0 otherwise
+ *     x^ <- x^ (+) L_i r
+ *   for i < N:
+ *     e^ = [Log(q*_i^-1 q^); xi^ - xi*_i],  u = u*_i + K_i e^
+ *     x_{i+1} = f(x_i, u), then xi += w[b][s][i];   x^_{i+1} = f(x^, u)         both on the model's exact dynamics
+ * J is the tracking cost of the TRUE trajectory and the applied u, under the rules of tolg_policy_rollout.
+ *   in : d_L [B][N+1][12][12] required: the call above's d_L or the caller's own (columns of unmeasured coordinates are not read);
+ *        d_dx0 [B][S][12], d_w [B][S][N][6] as tolg_policy_rollout; d_n [B][S][N+1][12] measurement noise; each NULL = 0
+ *   out: d_J, d_status, d_xs_q, d_xs_xi, d_us as tolg_policy_rollout (the true trajectory);
+ *        d_est_q [B][S][N+1][16], d_est_xi [B][S][N+1][6]   the posterior estimates x^_i
+ *        every output may be NULL.
+ * A sample's bits depend on neither S nor the other samples; the held policy is left alone.  This call steps both chains with
+ * the MODEL: an attached plant (tolg_set_plant) is ignored, as by every entry point outside the two rollouts, and the call
+ * takes no input box.
+ * TOLG_E_ARG: the conditions of tolg_policy_rollout; a bad mask (above); a NULL d_L. */
+int tolg_policy_covariance_estimated(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, int32_t mask,
+                                     const double* d_V, double* d_Sigma, double* d_P_post, double* d_L, double* d_var_x,
+                                     double* d_var_est, double* d_var_u, double* d_pos_cov, void* stream);
+int tolg_policy_rollout_estimated(tolg_handle_t h, int32_t B, int32_t S, int32_t mask, const double* d_L, const double* d_dx0,
+                                  const double* d_w, const double* d_n, double* d_J, int32_t* d_status, double* d_xs_q,
+                                  double* d_xs_xi, double* d_us, double* d_est_q, double* d_est_xi, void* stream);
+
 /* Plants: per-sample dynamics parameters that step the closed loops of tolg_policy_rollout and tolg_mpc_advance in place of
  * the model's (model mismatch: a payload change, a mis-identified inertia, domain randomisation).  The planner's model stays
  * the handle's tolg_problem, and so do dt, gravity, kind, m, the input map, the cost, the reference and the weights.

@@ -1,0 +1,93 @@
+"""What output feedback costs: tolg_policy_covariance_estimated beside tolg_policy_covariance, and tolg_policy_rollout_estimated
+beside tolg_policy_rollout, on a solved 4096 x 200 SE3 tracking batch.
+
+usage: python tools/bench_estimated.py [--B 4096] [--N 200] [--S 16] [--mask 0x03F] [--rounds 7] [--iters 10] [--out FILE.json]
+
+One process.  The batch is solved once, untimed (multiple shooting, accept-always, 20 iterations), and the Kalman gains the
+estimated rollout takes come from one untimed call of the estimated covariance.  Then, round after round, the four cases are
+timed in alternation: `iters` back-to-back calls between two events, through the C ABI (no host-side input checks).  The two
+covariance calls write their reduced outputs (var_x, var_u, pos_cov; the estimated one var_est too), the two rollouts J and
+status.  Reported per case: the median ms per call over the rounds, min and max, and the ratio to the existing call it stands
+beside."""
+import argparse
+import ctypes as C
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from trajectory_optimization_matrix_lie_groups_amd import workloads  # noqa: E402
+from _benchlib import add_common_args, emit, event_rounds, print_row, stats_row  # noqa: E402
+
+CASES = {"covariance": "tolg_policy_covariance (var_x, var_u, pos_cov)",
+         "covariance_est": "tolg_policy_covariance_estimated (var_x, var_est, var_u, pos_cov)",
+         "rollout": "tolg_policy_rollout S=%d", "rollout_est": "tolg_policy_rollout_estimated S=%d"}
+BESIDE = {"covariance_est": "covariance", "rollout_est": "rollout"}
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    add_common_args(ap, "B", "N", "S", "rounds", "iters", "out", iters=10, S="16")
+    ap.add_argument("--mask", default="0x03F", help="the measured coordinates (12 bits)")
+    a = ap.parse_args(argv)
+    a.S, a.mask = int(a.S), int(a.mask, 0)
+    if a.B < 1 or a.N < 1 or a.S < 1 or a.rounds < 1 or a.iters < 1 or not 0 <= a.mask <= 0xFFF:
+        ap.error("B, N, S, rounds, iters >= 1 and a 12-bit mask")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    import torch
+    from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
+
+    B, N, S, mask = a.B, a.N, a.S, a.mask
+    prob, q, xi, us, S0, W, V = workloads.se3_estimated(B, N=N)
+    m = prob.m
+    s = BatchedTrackingILQR(prob, B)
+    s.fit_batch(q, xi, us, mode="ms", n_iterations=20, tol_grad_norm=0.0, tol_d_norm=0.0)
+    L = s.policy_covariance_estimated(S0, W, mask, V, gains=True, pos=False).L
+    torch.cuda.synchronize()
+    dev = s.device
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    f64 = dict(dtype=torch.float64, device=dev)
+    d_S0, d_W, d_V = torch.as_tensor(S0, **f64), torch.as_tensor(W, **f64), torch.as_tensor(V, **f64)
+    var_x, var_est = torch.empty(B, N + 1, 12, **f64), torch.empty(B, N + 1, 12, **f64)
+    var_u, pos = torch.empty(B, N, m, **f64), torch.empty(B, N + 1, 6, **f64)
+    dx0 = torch.randn(B, S, 12, generator=g, **f64) * 0.05
+    w = torch.randn(B, S, N, 6, generator=g, **f64) * 0.01
+    keep = torch.tensor([float((mask >> j) & 1) for j in range(12)], **f64)
+    n = torch.randn(B, S, N + 1, 12, generator=g, **f64) * (d_V.sqrt() * keep)[:, None, None, :]
+    J, st = torch.empty(B, S, **f64), torch.empty(B, S, dtype=torch.int32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+
+    def call(name):
+        if name == "covariance":
+            return s.lib.tolg_policy_covariance(s._h, B, p(d_S0), p(d_W), None, p(var_x), p(var_u), p(pos), s._stream())
+        if name == "covariance_est":
+            return s.lib.tolg_policy_covariance_estimated(s._h, B, p(d_S0), p(d_W), mask, p(d_V), None, None, None, p(var_x),
+                                                          p(var_est), p(var_u), p(pos), s._stream())
+        if name == "rollout":
+            return s.lib.tolg_policy_rollout(s._h, B, S, p(dx0), p(w), p(J), p(st), None, None, None, s._stream())
+        return s.lib.tolg_policy_rollout_estimated(s._h, B, S, mask, p(L), p(dx0), p(w), p(n), p(J), p(st), None, None, None,
+                                                   None, None, s._stream())
+
+    names = list(CASES)
+    times = event_rounds(names, call, a.rounds, a.iters)
+    rows = {}
+    for name in names:
+        rows[name] = dict(case=CASES[name] % S if "%d" in CASES[name] else CASES[name], **stats_row(times[name]))
+    for name, base in BESIDE.items():
+        rows[name]["ratio_to_" + base] = rows[name]["ms_median"] / rows[base]["ms_median"]
+    for name in names:
+        print_row(rows[name])
+    finite = bool(all(torch.isfinite(t).all().item() for t in (var_x, var_est, var_u, pos, J)))
+    res = dict(B=B, N=N, S=S, mask="%#05x" % mask, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(dev),
+               outputs_finite=finite, rows=[rows[n_] for n_ in names])
+    print_row(dict(outputs_finite=finite))
+    emit(res, a.out)
+    return res
+
+
+if __name__ == "__main__":
+    main()

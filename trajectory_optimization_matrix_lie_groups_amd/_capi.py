@@ -32,7 +32,7 @@ SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_ba
            "tolg_refs_bytes", "tolg_set_refs", "tolg_weights_bytes", "tolg_set_weights", "tolg_eval_knot", "tolg_linearize_backward",
            "tolg_rollout", "tolg_expected_change", "tolg_solve_gains", "tolg_policy_rollout",
            "tolg_solve_begin_warm", "tolg_set_ref_windows", "tolg_mpc_advance", "tolg_obstacles_bytes", "tolg_set_al_obstacles", "tolg_obstacles_moving_bytes", "tolg_set_al_obstacles_moving",
-           "tolg_al_update_state", "tolg_al_mpc_step", "tolg_set_al_obstacle_windows", "tolg_set_al_obstacle_kinds", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_policy_rollout_limited", "tolg_mpc_advance_limited", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
+           "tolg_al_update_state", "tolg_al_mpc_step", "tolg_set_al_obstacle_windows", "tolg_set_al_obstacle_kinds", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_policy_covariance_estimated", "tolg_policy_rollout_estimated", "tolg_policy_rollout_limited", "tolg_mpc_advance_limited", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
 
 
 def load():
@@ -122,6 +122,10 @@ def load():
     lib.tolg_policy_covariance.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, dp, vp]
     lib.tolg_policy_value.restype = C.c_int
     lib.tolg_policy_value.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, dp, dp, vp]
+    lib.tolg_policy_covariance_estimated.restype = C.c_int
+    lib.tolg_policy_covariance_estimated.argtypes = [vp, C.c_int32, dp, dp, C.c_int32] + [dp] * 8 + [vp]
+    lib.tolg_policy_rollout_estimated.restype = C.c_int
+    lib.tolg_policy_rollout_estimated.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, ip, dp, dp, dp, dp, dp, vp]
     lib.tolg_policy_rollout_limited.restype = C.c_int
     lib.tolg_policy_rollout_limited.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, ip, dp, dp, dp, ip, dp, dp, ip, vp]
     lib.tolg_mpc_advance_limited.restype = C.c_int

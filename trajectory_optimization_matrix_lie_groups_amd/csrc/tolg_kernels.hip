@@ -3163,6 +3163,128 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
   }
 }
 
+// Output feedback, sampled (tolg_policy_rollout_estimated): k_policy_rollout's samples with the loop closed on an estimate.
+// One quad per sample (b, s) in k_policy_rollout's sample order carries two chains, the true state x and the estimate x^:
+//   y = x_i (+) n_i;  r = [Log(q^^-1 q_y); xi_y - xi^] on the measured coordinates;  x^ <- x^ (+) L_i r          (knots 0..N)
+//   e^ = [Log(q*_i^-1 q^); xi^ - xi*_i];  u = u*_i + K_i e^;  x <- f(x, u), xi += w_i;  x^ <- f(x^, u)           (knots 0..N-1)
+// from the pieces the rollout kernels share (roll_load, roll_deviation, roll_control, dyn_f, knot_cost) -- roll_step itself
+// takes its control from the state it steps and is not used.  L_i r: lane q of the quad owns rows q, q + 4 and q + 8 of L_i (36
+// loads per lane at most; with the samples of a trajectory side by side one address per wave), the columns of unmeasured
+// coordinates are neither read nor multiplied (mask is a kernel argument: wave-uniform branches), the three sums go round the
+// quad by DPP as roll_control's two do.  Both chains stay in one quad (registers and scratch per form: DESIGN.md).
+// J is the tracking cost of the TRUE trajectory and the applied inputs.  The model steps both chains: no plant, no box.
+template <int M, int PK, int PT>
+__global__ __launch_bounds__(64) void k_policy_rollout_est(Params P, int S, int traj_fast, int mask, const double* __restrict__ Lg,
+                                                           const double* __restrict__ dx0, const double* __restrict__ noise,
+                                                           const double* __restrict__ mnoise, double* __restrict__ Jout,
+                                                           int* __restrict__ status, double* __restrict__ xs_q,
+                                                           double* __restrict__ xs_xi, double* __restrict__ us,
+                                                           double* __restrict__ est_q, double* __restrict__ est_xi) {
+  const Consts& C = *P.c;
+  const size_t n = (size_t)P.B * (size_t)S;
+  size_t c = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+  const int q = threadIdx.x & 3;
+  // quads past the last sample replay it (DPP needs whole quads alive) and store nothing
+  const bool live = c < n;
+  if (!live) c = n - 1;
+  const int b = traj_fast ? (int)(c % (size_t)P.B) : (int)(c / (size_t)S);
+  const size_t s = traj_fast ? c / (size_t)P.B : c % (size_t)S;
+  const size_t bs = (size_t)b * S + s;  // row of the [B][S] outputs
+  const bool writer = live && q == 0;
+  const int N = P.N;
+  const unsigned sB = (unsigned)P.Bp * 8u, vb = (unsigned)b * 8u;
+  // (dyn_f on the constants as they are, not dyn_f_k on constants pinned in vector registers as k_policy_rollout steps: the 30
+  // registers of the pinned set are the ones two chains do not have)
+  // (no nominal state a knot ahead, as k_policy_rollout keeps one: two chains leave no registers for it.  Knot i's is requested
+  // between the gain product and the estimate's update, whose Exp it arrives behind.)
+  State Sa = roll_load_state(P, 0, vb, sB);
+  State St = Sa, Se = Sa;  // x_0 = x*_0 (+) dx0, x^_0 = x*_0
+  if (dx0) {
+    const double* d = dx0 + 12 * bs;
+    St.X = se3_project(se3_compose(Sa.X, se3_exp(v3(d[0], d[1], d[2]), v3(d[3], d[4], d[5]))));
+    St.w = Sa.w + v3(d[6], d[7], d[8]);
+    St.v = Sa.v + v3(d[9], d[10], d[11]);
+  }
+  double J = 0.0, un[M];
+  for (int i = 0; i <= N; i++) {
+    const size_t k = bs * (size_t)(N + 1) + i;
+    if (!mask && i > 0 && i < N) Sa = roll_load_state(P, i, vb, sB);
+    if (mask) {
+      State Y = St;
+      if (mnoise) {
+        const double* m = mnoise + 12 * k;
+        Y.X = se3_project(se3_compose(St.X, se3_exp_fast(v3(m[0], m[1], m[2]), v3(m[3], m[4], m[5]))));
+        Y.w = St.w + v3(m[6], m[7], m[8]);
+        Y.v = St.v + v3(m[9], m[10], m[11]);
+      }
+      V3 rw, rv;
+      se3_log_fast(se3_compose(se3_inverse(Se.X), Y.X), rw, rv);
+      double r[12], mine[3], d[12];
+      roll_deviation(rw, rv, Se, Y, r);
+      // this lane's three rows of L_i, requested behind the Log (ahead of it they are 72 more registers across it, and the two
+      // chains leave none: the forms with a reference per trajectory spilled)
+      __builtin_amdgcn_sched_barrier(0);
+      const double* Lr = Lg + ((size_t)b * (N + 1) + i) * 144 + 12 * q;
+#pragma unroll
+      for (int t = 0; t < 3; t++) mine[t] = 0.0;
+#pragma unroll
+      for (int a = 0; a < 12; a++) {
+        if (!((mask >> a) & 1)) continue;
+#pragma unroll
+        for (int t = 0; t < 3; t++) mine[t] += Lr[48 * t + a] * r[a];
+      }
+#pragma unroll
+      for (int t = 0; t < 3; t++) {
+        d[4 * t] = quad_bcast<0>(mine[t]); d[4 * t + 1] = quad_bcast<1>(mine[t]);
+        d[4 * t + 2] = quad_bcast<2>(mine[t]); d[4 * t + 3] = quad_bcast<3>(mine[t]);
+      }
+      if (i > 0 && i < N) Sa = roll_load_state(P, i, vb, sB);
+      __builtin_amdgcn_sched_barrier(0);
+      Se.X = se3_project(se3_compose(Se.X, se3_exp_fast(v3(d[0], d[1], d[2]), v3(d[3], d[4], d[5]))));
+      Se.w = Se.w + v3(d[6], d[7], d[8]);
+      Se.v = Se.v + v3(d[9], d[10], d[11]);
+    }
+    if (writer) {
+      state_to_m16(St, xs_q, xs_xi, k);
+      state_to_m16(Se, est_q, est_xi, k);
+    }
+    if (i == N) break;
+    // (scheduling barriers between the phases: left to itself the scheduler raises the gain loads above the estimate's update
+    // and the cost's reference and weight loads above the control, and the kernel no longer fits its registers)
+    __builtin_amdgcn_sched_barrier(0);
+    RollIn<M> R;
+    roll_load<M, true>(P, i, b, q, vb, sB, R);  // in flight while Log runs, as in roll_step
+    __builtin_amdgcn_sched_barrier(0);
+    V3 ew, ev;
+    se3_log_fast(se3_compose(se3_inverse(Sa.X), Se.X), ew, ev);
+    double e[12], du[M];
+    roll_deviation(ew, ev, Sa, Se, e);
+    roll_control<M, false>(R, e, un, du, 0.0);
+    __builtin_amdgcn_sched_barrier(0);
+    J += knot_cost<M, true, PT>(P, C, i, b, St, un, false);
+    __builtin_amdgcn_sched_barrier(0);
+    if (writer && us) {
+      double* u = us + (bs * (size_t)N + i) * M;
+#pragma unroll
+      for (int a = 0; a < M; a++) u[a] = un[a];
+    }
+    St = dyn_f<M, Consts, PK>(C, St, un);
+    if (noise) {
+      const double* w = noise + (bs * (size_t)N + i) * 6;
+      St.w = St.w + v3(w[0], w[1], w[2]);
+      St.v = St.v + v3(w[3], w[4], w[5]);
+    }
+    Se = dyn_f<M, Consts, PK>(C, Se, un);
+  }
+#pragma unroll
+  for (int a = 0; a < M; a++) un[a] = 0.0;
+  J += knot_cost<M, true, PT>(P, C, N, b, St, un, true);
+  if (writer) {
+    if (Jout) Jout[bs] = J;
+    if (status) status[bs] = isfinite(J) ? TOLG_ST_OK : TOLG_ST_NONFINITE;
+  }
+}
+
 // tolg_policy_rollout_limited: k_policy_rollout under an actuator box, with the clearance from the handle's keep-out spheres.
 // The same chain (sample order, start, noise, cost, stores), with two additions that stay inside the quad:
 //  - the box [lb, ub] of trajectory b, 2 M values in registers from ahead of the knot loop (a null bound: -inf / +inf), applied
@@ -3434,6 +3556,11 @@ __global__ __launch_bounds__(256) void k_mpc_advance_lim(Params P, const double*
 // LDS per trajectory (doubles): Sigma, T, the four pose blocks, the lower half of Acl, K, the partial sums of K Sigma K^T.
 enum { PC_SG = 0, PC_TT = 144, PC_TOP = 288, PC_BOT = 324, PC_K = 396, PC_PU = 468, PC_F = 540 };
 // y = Acl x from the row's LDS (a fixed summation order: the bits of a lane depend on its operands alone)
+// TAG, here and on the three helpers below: which kernel family calls.  The helpers are internal functions to the device
+// compiler, whose interprocedural passes run before they are inlined and merge what every caller passes: with a third caller
+// on the same instance the two existing kernels came out with other instructions (tools/symbol_diff.py).  A family of callers
+// that must not move the others takes an instance of its own (TAG = 1: k_policy_covariance_est).
+template <int TAG = 0>
 TOLG_DEV void pc_apply(const double* L, const double (&x)[12], double (&y)[12]) {
   const double *RI = L + PC_TOP, *TRI = RI + 9, *JR = RI + 18, *QR = RI + 27, *BOT = L + PC_BOT;  // 3x3 row-major; 6 x 12 row-major
 #pragma unroll
@@ -3459,7 +3586,7 @@ TOLG_DEV void pc_apply(const double* L, const double (&x)[12], double (&y)[12]) 
 // (shared by k_policy_covariance and k_policy_value).  Step one, every lane redundantly: the blocks of f_x at (x*_i, u*_i) --
 // lin_knot's dynamics part with the closed-form coefficients -- stored by lane 0, and the gain rows the lanes hold; the
 // pendulum's input block of the knot goes to Bt.
-template <int M, int PK>
+template <int M, int PK, int TAG = 0>
 TOLG_DEV void pc_build_acl(const Consts& C, double dt, const State& Sa, const RollIn<M>& Rin, int l, double* L, double (&Bt)[9]) {
   const V3 wd = dt * Sa.w, vd = dt * Sa.v;
   const SO3Coef kc = so3_coef(dot(wd, wd), true);
@@ -3514,7 +3641,7 @@ TOLG_DEV void pc_build_acl(const Consts& C, double dt, const State& Sa, const Ro
   }
 }
 // Step two: lane j folds f_u K into column j of the dense lower half (col: the lane stores); kj: column j of K
-template <int M>
+template <int M, int TAG = 0>
 TOLG_DEV void pc_fold_fuk(double* L, int j, bool col, const double (&Bt)[9], const double (&Bb)[9], double (&kj)[M]) {
   double a[6];
 #pragma unroll
@@ -3534,6 +3661,7 @@ TOLG_DEV void pc_fold_fuk(double* L, int j, bool col, const double (&Bt)[9], con
   }
 }
 // the outputs of knot i from the row's Sigma in LDS (upper triangle); S: the nominal state of the knot (pos_cov's rotation)
+template <int TAG = 0>
 TOLG_DEV void pc_outputs(const double* L, bool live, int l, size_t bk, const State& S, double* __restrict__ Sig,
                          double* __restrict__ var_x, double* __restrict__ pos_cov) {
   if (!live) return;
@@ -3647,6 +3775,183 @@ __global__ __launch_bounds__(64) void k_policy_covariance(Params P, const double
     Sa = Sb;
   }
   pc_outputs(L, live, l, (size_t)b * (N + 1) + N, Sa, Sig, var_x, pos_cov);
+}
+
+// Output feedback (tolg_policy_covariance_estimated): the covariance of the loop u = u*_i + K_i e^_i that acts on the estimate
+// of a Kalman filter with coordinate measurements (mask, diagonal V), on the plan of k_policy_covariance: one 16-lane row per
+// trajectory, lane j < 12 holds column j (= row j) of BOTH symmetric matrices in registers -- P, the covariance of the
+// estimation error e - e^, and S^, the covariance of the estimate's deviation e^ -- and the knot's blocks go to the row's LDS
+// through pc_build_acl / pc_fold_fuk.  A knot:
+//   Sigma_i = S^- + P^-                          entry by entry, lane by lane (two matrices symmetric to the bit: so is the sum)
+//   P^+: for each measured coordinate c ascending, s = P[c][c] + V[c], P -= P[:, c] P[c, :] / s.  Column c lives in lane c: its
+//        twelve entries go round the row by DPP (row_newbcast:c on the two halves of each double, as quad_bcast moves one; no
+//        LDS, no barrier -- measured against the row's LDS in tools/rank1_bcast_microbench.hip).  Lane j forms
+//        (col[k] * col[j]) * (1 / s): the product of the two column entries is rounded before anything else touches it, so
+//        lanes j and k get the same bits for entries {k, j} and {j, k} and P stays symmetric to the bit without a read-back.
+//        mask is a kernel argument: every branch on it is wave-uniform.
+//   L_i[:, c] = P^+[:, c] / V[c] (lane c stores its column; 0 for an unmeasured c),  S^+ = S^- + (P^- - P^+)
+//   var_u = diag K S^+ K^T                        as k_policy_covariance does it, on S^+
+//   P^-_{i+1} = A P^+ A^T + E W E^T              pc_apply twice with the transpose through LDS, BEFORE f_u K is folded in
+//   S^-_{i+1} = Acl S^+ Acl^T                     the same, AFTER the fold (pc_fold_fuk)
+// Both propagated matrices are read back from the upper triangle (the entry lane min(r, c) computed), as Sigma is there.
+// LDS per trajectory (doubles): k_policy_covariance's fields, then one more 12 x 12 (P^+ for its outputs, then S^-_{i+1}).
+enum { PE_S2 = PC_F, PE_F = PE_S2 + 144 };
+template <int C>
+TOLG_DEV double row_bcast(double x) {  // value of x in lane C of this lane's 16-lane row (on the halves: see quad_bcast)
+  constexpr int ctrl = 0x150 + C;  // row_newbcast:C
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, ctrl, 0xf, 0xf, false);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), ctrl, 0xf, 0xf, false);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+// the measurement updates of one knot on column j of P (p), coordinates C .. 11 in turn; vm: the noise variances
+template <int C = 0>
+TOLG_DEV void pe_measure(double (&p)[12], int mask, const double (&vm)[12]) {
+  if constexpr (C < 12) {
+    if ((mask >> C) & 1) {
+      double cc[12];
+#pragma unroll
+      for (int k = 0; k < 12; k++) cc[k] = row_bcast<C>(p[k]);
+      const double is = 1.0 / (cc[C] + vm[C]), cj = p[C];  // (P[c][j] = P[j][c]: this lane's own entry)
+#pragma unroll
+      for (int k = 0; k < 12; k++) p[k] -= (cc[k] * cj) * is;
+    }
+    pe_measure<C + 1>(p, mask, vm);
+  }
+}
+template <int M, int PK>
+__global__ __launch_bounds__(64) void k_policy_covariance_est(Params P, const double* __restrict__ Sigma0, const double* __restrict__ Wn,
+                                                              int mask, const double* __restrict__ Vm, double* __restrict__ Sig,
+                                                              double* __restrict__ Ppost, double* __restrict__ Lout,
+                                                              double* __restrict__ var_x, double* __restrict__ var_est,
+                                                              double* __restrict__ var_u, double* __restrict__ pos_cov) {
+  __shared__ double lds[4 * PE_F];
+  const Consts& C = *P.c;
+  const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+  int b = blockIdx.x * 4 + g;
+  // rows past the last trajectory replay it (the block's barriers need every lane) and store nothing
+  const bool live = b < P.B;
+  if (!live) b = P.B - 1;
+  const int j = l < 12 ? l : 11;
+  const bool col = l < 12;
+  double* L = lds + g * PE_F;
+  const int N = P.N;
+  const unsigned sB = (unsigned)P.Bp * 8u, vb = (unsigned)b * 8u;
+  const double dt = C.dt;
+  double p[12], sh[12], wc[6];  // column j of P and of S^; column j - 6 of W (zero in the lanes of the pose columns)
+#pragma unroll
+  for (int i = 0; i < 12; i++) {
+    p[i] = Sigma0 ? Sigma0[(size_t)b * 144 + (i <= j ? 12 * i + j : 12 * j + i)] : 0.0;
+    sh[i] = 0.0;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const int jw = j >= 6 ? j - 6 : 0;
+    wc[i] = (Wn && j >= 6) ? Wn[(size_t)b * 36 + (i <= jw ? 6 * i + jw : 6 * jw + i)] : 0.0;
+  }
+  // the measured coordinates' noise variances, one read each (an unmeasured coordinate's entry is not read)
+  double vm[12];
+#pragma unroll
+  for (int c = 0; c < 12; c++) vm[c] = ((mask >> c) & 1) ? Vm[(size_t)b * 12 + c] : 1.0;
+  const bool meas_j = ((mask >> j) & 1) != 0;
+  const double ivj = meas_j ? 1.0 / Vm[(size_t)b * 12 + j] : 0.0;
+  double Bt[9], Bb[9];  // F_u's constant blocks, as in k_policy_covariance
+#pragma unroll
+  for (int k = 0; k < 9; k++) { Bt[k] = C.Bt[k]; Bb[k] = C.Bb[k]; }
+  State Sa = roll_load_state(P, 0, vb, sB), Sb = Sa;
+  // Sigma_i and its outputs, the measurement update and its outputs, S^+: what every knot 0..N does.  Leaves a barrier behind
+  // its last LDS read only through the callers' next one (the regions it touches: PC_SG, PE_S2).
+  auto measure = [&](int i, const State& S) {
+    const size_t bk = (size_t)b * (N + 1) + i;
+    if (col) {
+#pragma unroll
+      for (int k = 0; k < 12; k++) L[PC_SG + 12 * j + k] = sh[k] + p[k];
+    }
+    __syncthreads();
+    pc_outputs<1>(L, live, l, bk, S, Sig, var_x, pos_cov);
+    double pm[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) pm[k] = p[k];
+    pe_measure(p, mask, vm);
+    if (Ppost || var_est) {
+      if (col) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) L[PE_S2 + 12 * j + k] = p[k];
+      }
+      __syncthreads();
+      if (live) {
+        if (Ppost) {  // 144 entries over 16 lanes (every entry was stored by its column's lane: no mirroring needed)
+          double* o = Ppost + bk * 144;
+#pragma unroll
+          for (int t = 0; t < 9; t++) o[l + 16 * t] = L[PE_S2 + l + 16 * t];
+        }
+        if (var_est && col) var_est[bk * 12 + l] = L[PE_S2 + 13 * l];
+      }
+    }
+    if (Lout && live && col) {  // column j of the gain
+      double* o = Lout + bk * 144 + j;
+#pragma unroll
+      for (int k = 0; k < 12; k++) o[12 * k] = meas_j ? p[k] * ivj : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) sh[k] += pm[k] - p[k];
+  };
+  // column j of X <- F X F^T (+ wadd on the twist rows) with F the row's LDS blocks, through PC_TT and the 12 x 12 at `out`
+  auto push = [&](double (&x)[12], int out, bool addw) {
+    double t[12], y[12];
+    pc_apply<1>(L, x, y);
+    if (col) {
+#pragma unroll
+      for (int r = 0; r < 12; r++) L[PC_TT + 12 * r + j] = y[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 12; k++) t[k] = L[PC_TT + 12 * j + k];
+    pc_apply<1>(L, t, y);
+    if (addw) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) y[6 + k] += wc[k];
+    }
+    if (col) {
+#pragma unroll
+      for (int k = 0; k < 12; k++) L[out + 12 * j + k] = y[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 12; k++) x[k] = L[out + (k <= j ? 12 * k + j : 12 * j + k)];
+  };
+  for (int i = 0; i < N; i++) {
+    Sb = roll_load_state(P, i + 1, vb, sB);  // knot N too: the rotation of the last pos_cov
+    RollIn<M> Rin;
+    roll_load<M, true>(P, i, b, l, vb, sB, Rin);
+    measure(i, Sa);
+    pc_build_acl<M, PK, 1>(C, dt, Sa, Rin, l, L, Bt);  // the blocks of f_x at (x*_i, u*_i), the gains
+    __syncthreads();
+    push(p, PC_SG, true);  // A_i P^+ A_i^T + E W E^T: f_u K is not in the lower half yet
+    {  // column j of the lower half: + f_u K
+      double kj[M];
+      pc_fold_fuk<M, 1>(L, j, col, Bt, Bb, kj);
+      if (var_u) {  // diag K S^+ K^T: lane j's terms K[u][j] (S^+[j, :] K[u, :]^T), summed over j by lane u
+#pragma unroll
+        for (int u = 0; u < M; u++) {
+          double q = 0.0;
+#pragma unroll
+          for (int c = 0; c < 12; c++) q += L[PC_K + 12 * u + c] * sh[c];
+          if (col) L[PC_PU + M * j + u] = kj[u] * q;
+        }
+      }
+    }
+    __syncthreads();
+    if (var_u && live && l < M) {
+      double t = 0.0;
+#pragma unroll
+      for (int c = 0; c < 12; c++) t += L[PC_PU + M * c + l];
+      var_u[((size_t)b * N + i) * M + l] = t;
+    }
+    push(sh, PE_S2, false);  // Acl_i S^+ Acl_i^T
+    Sa = Sb;
+  }
+  measure(N, Sa);
 }
 
 // Cost-to-go of the held policy (tolg_policy_value): V_i(e) ~ p_i . e + e^T P_i e / 2 about the held nominal, the backward twin
@@ -4843,6 +5148,11 @@ struct KernelTable {
                                    const double*, int*, PlantArg);
   void (*policy_covariance)(Params, const double*, const double*, double*, double*, double*, double*);  // tolg_policy_covariance
   void (*policy_value)(Params, const double*, const double*, double*, double*, double*, double*, double*);  // tolg_policy_value
+  // output feedback: tolg_policy_covariance_estimated, tolg_policy_rollout_estimated
+  void (*policy_covariance_est)(Params, const double*, const double*, int, const double*, double*, double*, double*, double*, double*,
+                                double*, double*);
+  void (*policy_rollout_est)(Params, int, int, int, const double*, const double*, const double*, const double*, double*, int*,
+                             double*, double*, double*, double*, double*);
   struct Search {                    // per search kind: ls[0] backtracking (single shooting), ls[1] merit (multiple shooting)
     struct { SearchRollout k; int nt; } wave2[2];  // k_rollout_ls2 [first try] and its NT (twist waves per pose wave)
     SearchRollout wave1[2];          // the one-wave forms k_rollout_ls [linear]
@@ -4919,6 +5229,8 @@ static KernelTable kernel_table(int lds_per_block) {
   t.mpc_advance_lim_plant[TOLG_PLANT_DENSE] = k_mpc_advance_lim<M, PK, PT & ~PT_OBS, PL_DENSE, PlantArg>;
   t.policy_covariance = k_policy_covariance<M, PK>;  // (reads neither reference nor weights: one kernel for every PT)
   t.policy_value = k_policy_value<M, PK, PT & ~PT_OBS>;  // (the tracking cost's derivatives: reference and weights, no spheres)
+  t.policy_covariance_est = k_policy_covariance_est<M, PK>;
+  t.policy_rollout_est = k_policy_rollout_est<M, PK, PT & ~PT_OBS>;
   t.ls[0] = search_kernels<M, false, PK, PT>();
   t.ls[1] = search_kernels<M, true, PK, PT>();
   return t;
@@ -6340,6 +6652,40 @@ extern "C" int tolg_policy_value(tolg_handle_t h, int32_t B, const double* d_Sig
   const Params P = params_for(h, B);
   hipLaunchKernelGGL(h->kt.policy_value, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, static_cast<hipStream_t>(stream), P, d_Sigma0,
                      d_W, d_P, d_p, d_diag_P, d_price, d_excess);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// the measurement model of the two estimated calls: twelve bits, none on a coordinate the SO3 family does not carry
+static bool mask_ok(const tolg_handle_s* h, int32_t mask) {
+  return mask >= 0 && mask <= 0xfff && !(so3_family(h->prob.kind) && (mask & 0xe38));
+}
+extern "C" int tolg_policy_covariance_estimated(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, int32_t mask,
+                                                const double* d_V, double* d_Sigma, double* d_P_post, double* d_L,
+                                                double* d_var_x, double* d_var_est, double* d_var_u, double* d_pos_cov,
+                                                void* stream) {
+  if (!policy_ok(h, B) || !mask_ok(h, mask) || (mask != 0 && !d_V)) return TOLG_E_ARG;
+  if (d_pos_cov && so3_family(h->prob.kind)) return TOLG_E_ARG;  // no translation (the rule of tolg_policy_covariance)
+  const Params P = params_for(h, B);
+  hipLaunchKernelGGL(h->kt.policy_covariance_est, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, static_cast<hipStream_t>(stream), P,
+                     d_Sigma0, d_W, (int)mask, d_V, d_Sigma, d_P_post, d_L, d_var_x, d_var_est, d_var_u, d_pos_cov);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tolg_policy_rollout_estimated(tolg_handle_t h, int32_t B, int32_t S, int32_t mask, const double* d_L,
+                                             const double* d_dx0, const double* d_w, const double* d_n, double* d_J,
+                                             int32_t* d_status, double* d_xs_q, double* d_xs_xi, double* d_us, double* d_est_q,
+                                             double* d_est_xi, void* stream) {
+  if (!policy_ok(h, B) || S < 1 || !mask_ok(h, mask) || !d_L) return TOLG_E_ARG;
+  const size_t lanes = (size_t)B * (size_t)S * 4;
+  if (lanes > 0x7fffffc0ull) return TOLG_E_ARG;  // one launch, 64-lane groups
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Params P = params_for(h, B);
+  P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // J is the tracking cost: no augmented-Lagrangian terms
+  hipLaunchKernelGGL(h->kt.policy_rollout_est, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P, (int)S,
+                     h->pol_traj_fast ? 1 : 0, (int)mask, d_L, d_dx0, d_w, d_n, d_J, d_status, d_xs_q, d_xs_xi, d_us, d_est_q,
+                     d_est_xi);
   LAUNCH_CHECK();
   return 0;
 }

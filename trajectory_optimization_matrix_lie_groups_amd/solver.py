@@ -96,6 +96,23 @@ class PolicyRollout:
     # kind_clearance), and the first knot that attains it
     clearance: Optional[torch.Tensor] = None       # [B, S]
     clearance_knot: Optional[torch.Tensor] = None  # [B, S] int32
+    # policy_rollout_estimated(estimates=True): the filter's posterior estimates x^_i (xs_q / xs_xi hold the true states)
+    est_q: Optional[torch.Tensor] = None           # [B, S, N+1, 4, 4]
+    est_xi: Optional[torch.Tensor] = None          # [B, S, N+1, 6]
+
+
+@dataclass
+class PolicyCovarianceEstimated:
+    """Covariance of the held policy under output feedback (BatchedTrackingILQR.policy_covariance_estimated): the loop acts on
+    the estimate of a Kalman filter with coordinate measurements.  Coordinates and layout as PolicyCovariance."""
+    var_x: torch.Tensor                     # [B, N+1, 12] diag Sigma_i, the true state's variance
+    var_est: torch.Tensor                   # [B, N+1, 12] diag P^+_i, the estimation error's variance after the knot's update
+    var_u: torch.Tensor                     # [B, N, m] diag K_i S^_i^+ K_i^T
+    mask: int = 0                           # the measured coordinates, as the device took them
+    pos_cov: Optional[torch.Tensor] = None  # [B, N+1, 3, 3] world-frame position covariance from Sigma: what inflate_obstacles takes
+    Sigma: Optional[torch.Tensor] = None    # [B, N+1, 12, 12] (full=True)
+    P_post: Optional[torch.Tensor] = None   # [B, N+1, 12, 12] (full=True)
+    L: Optional[torch.Tensor] = None        # [B, N+1, 12, 12] the Kalman gains (gains=True): policy_rollout_estimated's input
 
 
 @dataclass
@@ -144,6 +161,60 @@ def check_covariance(name, a, B, n, compact=None):
         full[:, idx[:, None], idx[None, :]] = a
         a = full
     return np.ascontiguousarray(a)
+
+
+_SO3_COORDS = [0, 1, 2, 6, 7, 8]  # where the SO3 family's (rotation, omega) sit in the 12-coordinate layout
+
+
+def measurement_mask(mask, so3=False):
+    """The measured coordinates as the 12-bit int the device takes: `mask` is such an int, or an iterable of coordinate indices
+    0..11; ValueError for anything else, and for coordinates 3..5 / 9..11 of the SO3 family (so3: no translation)."""
+    if isinstance(mask, (int, np.integer)) and not isinstance(mask, bool):
+        m = int(mask)
+        if m < 0 or m > 0xFFF:
+            raise ValueError("mask has 12 bits, one per coordinate of the error state: %r" % (mask,))
+    else:
+        m = 0
+        try:
+            idx = [j for j in mask]
+        except TypeError:
+            raise ValueError("mask must be an int or an iterable of coordinate indices: %r" % (mask,)) from None
+        for j in idx:
+            if not isinstance(j, (int, np.integer)) or isinstance(j, bool) or j < 0 or j > 11:
+                raise ValueError("mask holds coordinate indices 0..11: %r" % (j,))
+            m |= 1 << int(j)
+    if so3 and (m & 0xE38):
+        raise ValueError("the SO3 family has no translation or linear velocity: coordinates 3..5 and 9..11 cannot be measured")
+    return m
+
+
+def check_measurement(mask, V, B, so3=False):
+    """The measurement model of policy_covariance_estimated / policy_rollout_estimated checked on the host; ValueError before
+    anything reaches the device.  mask: an int whose bit j says that coordinate j of the error state is measured (12 bits), or an
+    iterable of coordinate indices 0..11.  V: the measurement-noise variances, [12] (every trajectory the same) or [B, 12]; on a
+    measured coordinate finite and > 0, on an unmeasured one ignored (whatever it holds; it goes to the device as 0); None is
+    allowed when nothing is measured.  so3: the problem is of the SO3 family -- the translation and linear-velocity coordinates
+    3..5 and 9..11 cannot be measured, and V may also be [6] or [B, 6] over (rotation, omega), embedded at 0..2 and 6..8 as
+    check_covariance embeds Sigma0.  Returns (mask as int, V as float64 [B, 12] numpy array or None)."""
+    m = measurement_mask(mask, so3)
+    if V is None:
+        if m:
+            raise ValueError("V is needed: mask %#05x measures something" % m)
+        return m, None
+    a = np.asarray(V.detach().cpu().numpy() if isinstance(V, torch.Tensor) else V, dtype=np.float64)
+    sizes = (12, 6) if so3 else (12,)
+    if a.ndim not in (1, 2) or a.shape[-1] not in sizes or (a.ndim == 2 and a.shape[0] != B):
+        raise ValueError("V has shape %s, expected (%s) or (%d, %s)" % (tuple(a.shape), " or ".join(map(str, sizes)), B,
+                                                                      " or ".join(map(str, sizes))))
+    a = np.broadcast_to(a, (B, a.shape[-1]))
+    if a.shape[-1] != 12:
+        full = np.zeros((B, 12))
+        full[:, _SO3_COORDS] = a
+        a = full
+    meas = np.array([(m >> j) & 1 for j in range(12)], dtype=bool)
+    if not np.all(np.isfinite(a[:, meas])) or np.any(a[:, meas] <= 0.0):
+        raise ValueError("V must be finite and positive on every measured coordinate")
+    return m, np.ascontiguousarray(np.where(meas[None, :], a, 0.0))
 
 
 @dataclass
@@ -1218,6 +1289,95 @@ class BatchedTrackingILQR:
         if pc is not None:
             iu = torch.tensor([[0, 1, 2], [1, 3, 4], [2, 4, 5]], device=self.device)
             r.pos_cov = pc[..., iu]
+        return r
+
+    def _so3(self):
+        return self.problem.kind in ("so3", "pendulum3d")
+
+    def policy_covariance_estimated(self, Sigma0, W, mask, V, full=False, gains=False, pos=True) -> PolicyCovarianceEstimated:
+        """The covariance of the held policy under OUTPUT feedback (tolg_policy_covariance_estimated): the loop
+        u = u*_i + K_i e^_i acts on the estimate of a Kalman filter that measures the coordinates `mask` of the error state at
+        every knot with noise variances V (check_measurement), instead of on the true state as policy_covariance assumes.  With P
+        the covariance of the estimation error and S^ that of the estimate's deviation (P_0^- = Sigma0, S^_0^- = 0), at every knot
+        Sigma_i = S^- + P^-, the sequential scalar measurement updates give P^+ and the gains L_i[:, j] = P^+[:, j] / V[j],
+        S^+ = S^- + (P^- - P^+), and P_{i+1}^- = A_i P^+ A_i^T + E W E^T, S^_{i+1}^- = Acl_i S^+ Acl_i^T (include/tolg.h has the
+        statement).  Sigma0 and W as in policy_covariance (either may be None; so3 and the pendulum also in compact form).
+        Returns var_x, var_est (diag P^+), var_u, pos_cov [B, N+1, 3, 3] (the shape inflate_obstacles takes; pos=False or a model
+        without translation: None); full=True adds Sigma and P_post [B, N+1, 12, 12], gains=True adds L [B, N+1, 12, 12], the
+        input of policy_rollout_estimated.  A plant, an input box and constraint geometry are ignored."""
+        B = self._held_B()
+        m, Vn = check_measurement(mask, V, B, so3=self._so3())
+        d_S0, d_W = self._stage_moments(B, Sigma0, W)
+        d_V = None if Vn is None else self._dev(Vn, (B, 12))
+        self._hold((d_S0, d_W, d_V))
+        f64 = dict(dtype=torch.float64, device=self.device)
+        n1 = self.N + 1
+        r = PolicyCovarianceEstimated(var_x=torch.empty(B, n1, 12, **f64), var_est=torch.empty(B, n1, 12, **f64),
+                                      var_u=torch.empty(B, self.N, self.m, **f64), mask=m)
+        if full:
+            r.Sigma, r.P_post = torch.empty(B, n1, 12, 12, **f64), torch.empty(B, n1, 12, 12, **f64)
+        if gains:
+            r.L = torch.empty(B, n1, 12, 12, **f64)
+        pc = torch.empty(B, n1, 6, **f64) if pos and not self._so3() else None
+        self._call("tolg_policy_covariance_estimated", B, _ptr(d_S0), _ptr(d_W), m, _ptr(d_V), _ptr(r.Sigma), _ptr(r.P_post),
+                   _ptr(r.L), _ptr(r.var_x), _ptr(r.var_est), _ptr(r.var_u), _ptr(pc))
+        if pc is not None:
+            iu = torch.tensor([[0, 1, 2], [1, 3, 4], [2, 4, 5]], device=self.device)
+            r.pos_cov = pc[..., iu]
+        return r
+
+    def policy_rollout_estimated(self, L, mask, dx0=None, w=None, meas_noise=None, S=None, trajectories=False,
+                                 estimates=False) -> PolicyRollout:
+        """S sampled closed loops per trajectory of the held policy under output feedback (tolg_policy_rollout_estimated), the
+        Monte-Carlo check of policy_covariance_estimated: the true state starts at x*_0 (+) dx0, the estimate at x*_0; at every
+        knot the filter takes y = x (+) meas_noise on the coordinates `mask` and corrects x^ <- x^ (+) L_i r with the residual
+        r = [Log(q^^-1 q_y); xi_y - xi^]; the input u = u*_i + K_i e^ is computed from the ESTIMATE and steps both the true state
+        (twist noise w added behind the step) and the estimate, on the model's exact dynamics.
+        L [B, N+1, 12, 12]: the gains (policy_covariance_estimated(gains=True).L, or the caller's own; columns of unmeasured
+        coordinates are not read).  dx0 [B, S, 12], w [B, S, N, 6], meas_noise [B, S, N+1, 12]: each may be None (zero); S is
+        taken from them, or given when all are None.  J [B, S] is the tracking cost of the true trajectory and the applied
+        inputs.  trajectories=True also returns xs_q, xs_xi, us (the true states); estimates=True est_q, est_xi (the posterior
+        estimates).  An attached plant is ignored and the call takes no input box."""
+        B = self._held_B()
+        m = measurement_mask(mask, so3=self._so3())
+        if L is None:
+            raise ValueError("policy_rollout_estimated needs the gains L [B, N+1, 12, 12]")
+        L = _checked("L", L, (B, self.N + 1, 12, 12))
+        shapes = []
+        if dx0 is not None:
+            dx0 = _checked("dx0", dx0, (B, None, 12), finite=True)
+            shapes.append(dx0.shape[1])
+        if w is not None:
+            w = _checked("w", w, (B, None, self.N, 6), finite=True)
+            shapes.append(w.shape[1])
+        if meas_noise is not None:
+            meas_noise = _checked("meas_noise", meas_noise, (B, None, self.N + 1, 12), finite=True)
+            shapes.append(meas_noise.shape[1])
+        if S is not None:
+            shapes.append(int(S))
+        if not shapes:
+            raise ValueError("policy_rollout_estimated needs S, dx0, w or meas_noise")
+        if len(set(shapes)) != 1:
+            raise ValueError("the sample count differs between dx0, w, meas_noise and S: %s" % shapes)
+        S = shapes[0]
+        if S < 1:
+            raise ValueError("S must be at least 1")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        d_L = self._dev(L, (B, self.N + 1, 12, 12))
+        d_dx0 = None if dx0 is None else self._dev(dx0, (B, S, 12))
+        d_w = None if w is None else self._dev(w, (B, S, self.N, 6))
+        d_n = None if meas_noise is None else self._dev(meas_noise, (B, S, self.N + 1, 12))
+        r = PolicyRollout(J=torch.empty(B, S, **f64), status=torch.empty(B, S, dtype=torch.int32, device=self.device))
+        if trajectories:
+            r.xs_q = torch.empty(B, S, self.N + 1, 4, 4, **f64)
+            r.xs_xi = torch.empty(B, S, self.N + 1, 6, **f64)
+            r.us = torch.empty(B, S, self.N, self.m, **f64)
+        if estimates:
+            r.est_q = torch.empty(B, S, self.N + 1, 4, 4, **f64)
+            r.est_xi = torch.empty(B, S, self.N + 1, 6, **f64)
+        self._hold((d_L, d_dx0, d_w, d_n))
+        self._call("tolg_policy_rollout_estimated", B, S, m, _ptr(d_L), _ptr(d_dx0), _ptr(d_w), _ptr(d_n), _ptr(r.J),
+                   _ptr(r.status), _ptr(r.xs_q), _ptr(r.xs_xi), _ptr(r.us), _ptr(r.est_q), _ptr(r.est_xi))
         return r
 
     def policy_value(self, Sigma0=None, W=None, full=False) -> PolicyValue:

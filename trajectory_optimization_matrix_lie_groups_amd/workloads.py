@@ -268,6 +268,19 @@ def se3_covariance(B, N=200, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=0.01
     return prob, x0_q, x0_xi, us0, Sigma0, W
 
 
+def se3_estimated(B, N=200, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=0.01, seed=SEED):
+    """Output-feedback inputs for the closed loop of se3_tracking's workload (BatchedTrackingILQR.policy_covariance_estimated):
+    se3_covariance's (prob, x0_q, x0_xi, us0, Sigma0, W) plus seeded measurement-noise variances V [B, 12] =
+    diag(Sigma0) * U[0.25, 4] -- a sensor between twice as good and twice as bad, in standard deviation, as the start
+    knowledge of each coordinate.  Which coordinates are measured (the mask) is the caller's choice; a Sigma0 of zero gives
+    V = 0, which no coordinate may then be measured with."""
+    prob, x0_q, x0_xi, us0, Sigma0, W = se3_covariance(B, N=N, sigma_pose=sigma_pose, sigma_twist=sigma_twist,
+                                                       sigma_noise=sigma_noise, seed=seed)
+    rng = np.random.default_rng(seed + 9)
+    V = np.einsum("bii->bi", Sigma0) * rng.uniform(0.25, 4.0, (B, 12))
+    return prob, x0_q, x0_xi, us0, Sigma0, W, V
+
+
 def plant_mismatch(B, S, kind="se3", N=None, sigma_inertia=0.1, sigma_mass=0.1, rotate=False, seed=SEED):
     """Model-mismatch inputs for the closed loop (BatchedTrackingILQR.policy_rollout with plant_J): se3_policy_eval's
     perturbations on se3_tracking's (kind="se3", N default 200) or drone_tracking's (kind="drone", N default 400) workload,
