@@ -13,6 +13,8 @@ from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_controll
                                                                                            iLQR_Tracking_SE3_MS)
 from trajectory_optimization_matrix_lie_groups_amd.traoptlibrary.traopt_cost import ALConstrainedCost
 from tests.restate import MyCost, MyDynamics, restate_mpc_step, restate_policy, window_problem
+from tests.limits import near_bound, restate_limited_batch
+from tests.support import (EXP_TIERS, LOG_TIERS, assert_coverage, determined, nudged, policy_rollout_tags, sample_spread)
 from tests.support import ZERO, host, problem_of_kind, random_traj_embedded, rel, same
 
 
@@ -239,3 +241,78 @@ def check_restatement(s, r, ops, dx0, w, min_finite=None):
         ok += int(fin.sum())
     num, den = (1, 2) if min_finite is None else min_finite
     assert ok >= len(ops) * S * num // den, (ok, len(ops) * S)
+
+
+# the limited closed loops (tolg_policy_rollout_limited) against tests/limits.py::restate_policy_limited
+def limited_conditions(R, lb, ub):
+    """The conditions a parity case must meet, on the restatement alone.  Returns (finite [B, S], near a bound [B, S])."""
+    fin = np.array([np.isfinite(r["J"]) for r in R])
+    ns = np.array([r["n_sat"] for r in R])
+    near = np.array([near_bound(r["uc"], lb[b], ub[b]) for b, r in enumerate(R)]) & fin
+    nf = int(fin.sum())
+    print("restatement: finite %d of %d, saturated %d, free %d, near a bound %d"
+          % (nf, fin.size, int((ns[fin] > 0).sum()), int((ns[fin] == 0).sum()), int(near.sum())))
+    assert nf >= fin.size // 2
+    assert 4 * int((ns[fin] > 0).sum()) >= nf
+    assert (ns[fin] == 0).any()
+    assert 4 * int(near.sum()) <= nf
+    return fin, near
+
+
+def compare_limited(p, R, fin, near, keep=None):
+    """keep [B, S] (default: all): the samples whose values are compared; the status of every sample is."""
+    worst = dict(xs_q=0.0, xs_xi=0.0, us=0.0, J=0.0, u_excess=0.0)
+    if keep is not None:
+        fin, full = fin & keep, fin
+    for b, r in enumerate(R):
+        f = fin[b]
+        assert np.array_equal(host(p.status)[b], np.where(f if keep is None else full[b], _capi.ST_OK, _capi.ST_NONFINITE))
+        worst["xs_q"] = max(worst["xs_q"], np.abs(host(p.xs_q)[b][f] - r["xs_q"][f]).max(initial=0))
+        worst["xs_xi"] = max(worst["xs_xi"], np.abs(host(p.xs_xi)[b][f] - r["xs_xi"][f]).max(initial=0))
+        worst["us"] = max(worst["us"], np.abs(host(p.us)[b][f] - r["us"][f]).max(initial=0))
+        worst["J"] = max(worst["J"], np.abs(host(p.J)[b][f] / r["J"][f] - 1).max(initial=0))
+        worst["u_excess"] = max(worst["u_excess"], np.abs(host(p.u_excess)[b][f] - r["u_excess"][f]).max(initial=0))
+    print("device against restatement:", worst)
+    assert worst["xs_q"] < 1e-10 and worst["xs_xi"] < 1e-10 and worst["us"] < 1e-8 and worst["J"] < 1e-9   # check_restatement's
+    assert worst["u_excess"] < 1e-8
+    for b, r in enumerate(R):
+        exact = fin[b] & ~near[b]
+        assert np.array_equal(host(p.n_sat)[b][exact], r["n_sat"][exact]), b
+    return worst
+
+
+def compare_estimated(p, R, keep):
+    """tolg_policy_rollout_estimated's outputs p (trajectories and estimates asked for) against the restatement R
+    (tests/estimated.py::restate_estimated_batch), at check_restatement's bounds: the status of every sample, the values of the
+    samples in keep [B, S] that are finite.  Returns the worst figure per field."""
+    worst = dict(xs_q=0.0, xs_xi=0.0, est_q=0.0, est_xi=0.0, us=0.0, J=0.0)
+    for b, r in enumerate(R):
+        fin = np.isfinite(r["J"])  # a sample the CPU sees diverge must diverge on the device, and be flagged there
+        assert np.array_equal(host(p.status)[b], np.where(fin, _capi.ST_OK, _capi.ST_NONFINITE)), b
+        fin = fin & keep[b]
+        for name, tol in (("xs_q", 1e-10), ("xs_xi", 1e-10), ("est_q", 1e-10), ("est_xi", 1e-10), ("us", 1e-8)):
+            e = np.abs(host(getattr(p, name))[b][fin] - r[name][fin]).max(initial=0)
+            worst[name] = max(worst[name], float(e))
+            assert e < tol, (b, name, e)
+        e = np.abs(host(p.J)[b][fin] / r["J"][fin] - 1).max(initial=0)
+        worst["J"] = max(worst["J"], float(e))
+        assert e < 1e-9, (b, "J", e)
+    return worst
+
+
+def limited_guard(op, prob, nom, K, dx0, w, widen):
+    """The conditions and the coverage guard of the limited loop at large rotations, on the restatement alone: the box from
+    the unlimited restatement, limited_conditions under it, the Log tier of every start deviation and the Exp tier of every
+    knot's twist as test (d) of tests/test_gpu_large_rotation.py counts them, and the samples the restatement determines
+    (tests/support.py::determined, the gains moved in their last place): three quarters at least, with the same n_sat.
+    Returns (lb, ub, the restatement, keep [B, S], the spread per field [B, S])."""
+    B = dx0.shape[0]
+    lb, ub, R = restate_limited_batch([op] * B, nom, K, dx0, w, widen=widen)
+    limited_conditions(R, lb, ub)
+    tags = [t for b, r in enumerate(R) for t in policy_rollout_tags(prob, nom.xs_q[b, 0], r["xs_q"], r["xs_xi"])]
+    assert_coverage(tags, need=LOG_TIERS + EXP_TIERS[1:])
+    _, _, R2 = restate_limited_batch([op] * B, nom, nudged(K, np.random.default_rng(5)), dx0, w, box=(lb, ub))
+    sp = sample_spread(R, R2)
+    keep = determined(sp) & np.array([a["n_sat"] == b["n_sat"] for a, b in zip(R, R2)])
+    assert 4 * int(keep.sum()) >= 3 * keep.size, (int(keep.sum()), keep.size)
+    return lb, ub, R, keep, sp

@@ -4,7 +4,8 @@ A plain module (pytest does not collect it)."""
 import numpy as np
 
 from oracle import bridge as ob
-from tests.support import KW, embed, op_of, psd
+from tests.support import (KW, assert_coverage, determined, embed, estimated_need, estimated_site_tags, nudged, op_of, psd,
+                           sample_spread)
 
 SO3_COORDS = [0, 1, 2, 6, 7, 8]
 MC_SIGMA = (1e-3, 1e-3, 2e-4)  # pose, twist, noise: the scales of tests/test_covariance_cpu.py's sampled check
@@ -205,3 +206,39 @@ def estimated_inputs(prob, B, seed=7, sigma=0.005, noise=0.1):
     S0, W = psd(B, 12, sigma, seed), psd(B, 6, noise, seed + 1)
     V = np.einsum("bii->bi", S0) * rng.uniform(0.25, 4.0, (B, 12))
     return S0, W, V, S0, W, V
+
+
+ESTIMATED_FIELDS = ("J", "xs_q", "xs_xi", "us", "est_q", "est_xi")
+
+
+def restate_estimated_batch(ops, nom, K, L, mask, dx0, w, n):
+    """restate_rollout_estimated for every trajectory of a batch: a list of dicts over ESTIMATED_FIELDS.  ops: one OracleProblem
+    per trajectory; nom: xs_q / xs_xi / us [B, ...] (numpy); K [B, N, m, 12]; L [B, N+1, 12, 12]; dx0, w, n [B, S, ...]."""
+    with np.errstate(all="ignore"):
+        return [dict(zip(ESTIMATED_FIELDS, restate_rollout_estimated(op, nom.xs_q[b], nom.xs_xi[b], nom.us[b], K[b], L[b], mask,
+                                                                     dx0[b], w[b], n[b], dx0.shape[1])))
+                for b, op in enumerate(ops)]
+
+
+def estimated_guard(op, prob, nom, K, L, mask, dx0, w, n, least=4):
+    """The coverage guard and the caps of the estimated loop at large rotations, on the restatement alone: every site of
+    k_policy_rollout_est holds at least `least` samples in every tier of estimated_need (least = 0: not asked), counted over the
+    samples the restatement determines (tests/support.py::determined, gains K and L moved in their last place); three quarters
+    of the samples stay finite, and three quarters are determined.
+    Returns (the restatement, keep [B, S], the spread per field [B, S])."""
+    B, S = dx0.shape[:2]
+    R = restate_estimated_batch([op] * B, nom, K, L, mask, dx0, w, n)
+    rng = np.random.default_rng(5)
+    sp = sample_spread(R, restate_estimated_batch([op] * B, nom, nudged(K, rng), nudged(L, rng), mask, dx0, w, n))
+    keep = determined(sp)
+    if least:
+        tags = []
+        for b in range(B):
+            r = {f: v[keep[b]] for f, v in R[b].items()}
+            tags += estimated_site_tags(op, prob, nom.xs_q[b], nom.xs_xi[b], L[b], mask, n[b][keep[b]],
+                                        *(r[f] for f in ESTIMATED_FIELDS[1:]))
+        assert_coverage(tags, need=estimated_need(prob.N, mask), least=least)
+    fin = sum(int(np.isfinite(r["J"]).sum()) for r in R)
+    assert 4 * fin >= 3 * B * S, (fin, B * S)
+    assert 4 * int(keep.sum()) >= 3 * B * S, (int(keep.sum()), B * S)
+    return R, keep, sp

@@ -79,15 +79,34 @@ def restate_policy_limited(op, q_nom, xi_nom, u_nom, K, lb, ub, dx0=None, noise=
     return out
 
 
-def box_from_unlimited(u_nom, uc, fin):
+def box_from_unlimited(u_nom, uc, fin, widen=0.5):
     """The box of the parity tests, from the unlimited restatement of one trajectory: the nominal range of every input over
-    the knots, widened by half the largest excursion the finite samples' commands make beyond it.  u_nom [N, m], uc [S, N, m],
-    fin [S] bool.  Returns (lb [m], ub [m])."""
+    the knots, widened by half (`widen`) the largest excursion the finite samples' commands make beyond it.  u_nom [N, m],
+    uc [S, N, m], fin [S] bool.  Returns (lb [m], ub [m])."""
     lo, hi = u_nom.min(axis=0), u_nom.max(axis=0)
     exc = np.fmax(np.fmax(lo - uc[fin], uc[fin] - hi), 0.0).max(initial=0.0)
-    return lo - 0.5 * exc, hi + 0.5 * exc
+    return lo - widen * exc, hi + widen * exc
 
 
 def near_bound(uc, lb, ub, tol=1e-8):
     """[S] bool: some commanded input of the sample lies within tol of a bound (its n_sat may differ by rounding)."""
     return ((np.abs(uc - lb) < tol) | (np.abs(uc - ub) < tol)).any(axis=(-1, -2))
+
+
+def restate_limited_batch(ops, nom, K, dx0, w, box=None, widen=0.5):
+    """Per trajectory: the box (given as (lb [B, m], ub [B, m]), or box_from_unlimited on the unlimited restatement) and the
+    limited restatement under it.  ops: one OracleProblem per trajectory; nom: xs_q / xs_xi / us [B, ...] (numpy).
+    Returns (lb [B, m], ub [B, m], [restate_policy_limited's dict per trajectory])."""
+    S = dx0.shape[1]
+    lbs, ubs, out = [], [], []
+    with np.errstate(all="ignore"):
+        for b, op in enumerate(ops):
+            a = (op, nom.xs_q[b], nom.xs_xi[b], nom.us[b], K[b])
+            if box is None:
+                free = restate_policy_limited(*a, None, None, dx0[b], w[b], S)
+                lb, ub = box_from_unlimited(nom.us[b], free["uc"], np.isfinite(free["J"]), widen)
+            else:
+                lb, ub = box[0][b], box[1][b]
+            out.append(restate_policy_limited(*a, lb, ub, dx0[b], w[b], S))
+            lbs.append(lb); ubs.append(ub)
+    return np.array(lbs), np.array(ubs), out

@@ -1,10 +1,12 @@
 """Comparisons and problem builders shared by the test modules.  A plain module (pytest does not collect it): test modules
 import from here, from tests/restate.py and from tests/checks.py, never from each other."""
+import os
+
 import numpy as np
 import torch
 
 from oracle import bridge as ob
-from trajectory_optimization_matrix_lie_groups_amd import TrackingProblem, workloads
+from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, TrackingProblem, workloads
 
 
 ZERO = dict(tol_grad_norm=0.0, tol_d_norm=0.0)
@@ -506,3 +508,229 @@ def trajectory_buckets(prob, xs_q, xs_xi):
                     t.add("defect_near_pi")
             tags.append(t)
     return tags
+
+
+# ---- large perturbations of a held policy: tests/test_gpu_large_rotation.py (d) and tests/test_gpu_large_rotation_policy.py
+def policy_perturbations(prob, B, S, layout, seed):
+    """dx0 rotations from the grid's angles -- uniform: a trajectory's 16-sample groups each hold one Log tier; mixed: a seeded
+    shuffle -- and twist noise that moves |omega| dt across the Exp tiers."""
+    ang, steps, axes = rotation_grid()
+    rng = np.random.default_rng(seed)
+    so3 = prob.kind in ("so3", "pendulum3d")
+    by_tier = [[a for a in ang if log_tier(np.sin(a / 2) ** 2) == t and a < np.pi - 2 * NEAR_PI] for t in range(4)]
+    dx0 = np.zeros((B, S, 12)); w = np.zeros((B, S, prob.N, 6))
+    for b in range(B):
+        for smp in range(S):
+            tier = (b + smp // 16) % 4
+            ax = axes[rng.integers(len(axes))]
+            dx0[b, smp, :3] = ax * by_tier[tier][rng.integers(len(by_tier[tier]))]
+            if not so3:
+                dx0[b, smp, 3:6] = rng.normal(size=3) * 0.05
+            dx0[b, smp, 6:9] = rng.normal(size=3) * 0.05
+            for i in range(prob.N):
+                ax = rng.normal(size=3)
+                w[b, smp, i, :3] = ax / np.linalg.norm(ax) * steps[rng.integers(len(steps))] / prob.dt
+        if layout == "mixed":
+            p = rng.permutation(S)
+            dx0[b], w[b] = dx0[b, p], w[b, p]
+    return dx0, w
+
+
+def policy_handle(prob, B, fast):
+    old = os.environ.pop("TOLG_POLICY_TRAJ_FAST", None)
+    try:
+        if fast:
+            os.environ["TOLG_POLICY_TRAJ_FAST"] = "1"
+        return BatchedTrackingILQR(prob, B)
+    finally:
+        os.environ.pop("TOLG_POLICY_TRAJ_FAST", None)
+        if old is not None:
+            os.environ["TOLG_POLICY_TRAJ_FAST"] = old
+
+
+class Nominal:
+    def __init__(self, xs_q, xs_xi, us):
+        self.xs_q, self.xs_xi, self.us = xs_q, xs_xi, us
+
+
+# ---- large rotations for the newer policy kernels: tests/test_gpu_large_rotation_policy.py and its CPU twin ---------------
+POLICY_B, POLICY_S = 5, 32
+MEAS_DIAG = (0.9, 0.5, 1.0, 0.2)   # the filter gain on a measured coordinate, by knot: from most of the innovation to a fifth of it
+MEAS_FACTORS = (0.3, 0.3, 0.3, 1.0)  # of the grid's angles in the measurement noise, by sample (see measurement_noise)
+
+
+def is_so3(prob):
+    return prob.kind in ("so3", "pendulum3d")
+
+
+def large_policy_case(kind, N, layout, S=POLICY_S):
+    """The inputs of test (d) of tests/test_gpu_large_rotation.py: (prob, Nominal, dx0 [5, S, 12], w [5, S, N, 6])."""
+    prob = large_rotation_problem(problem_of_kind(kind, 1, N)[0])
+    nom = Nominal(*large_rotation_trajectories(prob, POLICY_B, seed=7 + N, twists="moderate"))
+    dx0, w = policy_perturbations(prob, POLICY_B, S, layout, seed=11 + N)
+    return prob, nom, dx0, w
+
+
+def large_estimated_case(kind, N, layout, pose_only, S=POLICY_S):
+    """The inputs of the estimated loop at large rotations: (prob, Nominal, dx0, w, n [5, S, N+1, 12], mask, L)."""
+    prob, nom, dx0, w = large_policy_case(kind, N, layout, S)
+    mask = measurement_masks(prob)[int(pose_only)]
+    return prob, nom, dx0, w, measurement_noise(prob, dx0, seed=23 + N), mask, filter_gains(prob, POLICY_B, mask, seed=31 + N)
+
+
+def measurement_masks(prob):
+    """(every coordinate measured, the pose alone: the twist estimate runs open loop)"""
+    return (0x1C7, 0x007) if is_so3(prob) else (0xFFF, 0x03F)
+
+
+def filter_gains(prob, B, mask, seed):
+    """L [B, N+1, 12, 12] for tolg_policy_rollout_estimated, the caller's own: MEAS_DIAG by knot on the measured coordinates
+    plus 0.05 N(0, 1) in their columns (the SO3 family: in the rows of its coordinates only).  With such gains the estimate
+    jumps most of the way to a measurement radians off, where policy_covariance_estimated's would keep every update small."""
+    rng = np.random.default_rng(seed)
+    rows = np.array([0, 1, 2, 6, 7, 8] if is_so3(prob) else range(12))
+    meas = np.array([j for j in range(12) if (mask >> j) & 1])
+    L = np.zeros((B, prob.N + 1, 12, 12))
+    L[:, :, rows[:, None], meas[None, :]] = 0.05 * rng.normal(size=(B, prob.N + 1, len(rows), len(meas)))
+    for i in range(prob.N + 1):
+        L[:, i, meas, meas] += MEAS_DIAG[i % 4]
+    return L
+
+
+def measurement_noise(prob, dx0, seed):
+    """n [B, S, N+1, 12]: rotation parts along the grid's axes, the grid's angles times MEAS_FACTORS[sample % 4] (0.3 keeps a
+    measurement within a radian of the state; every fourth sample takes the angles as they are, up to the closed-form tier of
+    Exp); the other coordinates N(0, 0.01).  Half of the samples whose dx0 is of the tiny Log tier are measured exactly: with
+    noise on it no innovation stays below the small-angle switch."""
+    ang, _, axes = rotation_grid()
+    rng = np.random.default_rng(seed)
+    B, S = dx0.shape[:2]
+    n = rng.normal(size=(B, S, prob.N + 1, 12)) * 0.01
+    for b in range(B):
+        for smp in range(S):
+            for i in range(prob.N + 1):
+                n[b, smp, i, :3] = axes[rng.integers(len(axes))] * ang[rng.integers(len(ang))] * MEAS_FACTORS[smp % 4]
+            if log_tier(np.sin(np.linalg.norm(dx0[b, smp, :3]) / 2) ** 2) == 0 and rng.integers(2):
+                n[b, smp] = 0.0
+    if is_so3(prob):
+        n[..., [3, 4, 5, 9, 10, 11]] = 0.0
+    return n
+
+
+def estimated_site_tags(op, prob, nom_q, nom_xi, L, mask, n, xs_q, xs_xi, us, est_q, est_xi):
+    """The tiers one trajectory's samples put every Exp / Log site of k_policy_rollout_est in, from the restatement's outputs
+    (tests/estimated.py::restate_rollout_estimated): one set per finite sample, names "<site>:<tier>" with the sites
+    innov (Log(x^^-1 y)), dev (Log(x*_i^-1 x^_i)), gain (Exp of the rotation part of L_i r), noise (Exp of the measurement
+    noise's), step and est_step (Exp(omega dt) of the two chains)."""
+    keep = np.array([(mask >> j) & 1 for j in range(12)], float)
+    dt2 = prob.dt ** 2
+    tags = []
+    for s in range(xs_xi.shape[0]):
+        if not all(np.isfinite(a[s]).all() for a in (xs_q, xs_xi, us, est_q, est_xi)):
+            continue
+        t = set()
+        for i in range(prob.N + 1):
+            qh, xih = (nom_q[0], nom_xi[0]) if i == 0 else ob.f(op, est_q[s, i - 1], est_xi[s, i - 1], us[s, i - 1])
+            qy, xiy = xs_q[s, i] @ ob.se3_exp(n[s, i, :6]), xs_xi[s, i] + n[s, i, 6:]
+            t.add("innov:" + LOG_TIERS[log_tier(product_quaternion(qy, qh, left=False)[1])])
+            d = L[i] @ (np.r_[ob.rminus(qy, qh), xiy - xih] * keep)
+            t.add("gain:" + EXP_TIERS[exp_tier(float(d[:3] @ d[:3]))])
+            t.add("noise:" + EXP_TIERS[exp_tier(float(n[s, i, :3] @ n[s, i, :3]))])
+            if i < prob.N:
+                t.add("dev:" + LOG_TIERS[log_tier(product_quaternion(est_q[s, i], nom_q[i], left=False)[1])])
+                t.add("step:" + EXP_TIERS[exp_tier(dt2 * float(xs_xi[s, i, :3] @ xs_xi[s, i, :3]))])
+                t.add("est_step:" + EXP_TIERS[exp_tier(dt2 * float(est_xi[s, i, :3] @ est_xi[s, i, :3]))])
+        tags.append(t)
+    return tags
+
+
+def estimated_need(N, mask):
+    """What estimated_site_tags must hold for the coverage guard: every tier a site can reach with these inputs.
+    innov: every Log tier (the tiny one from the samples measured exactly).  dev: LOG_TIERS[1:] (the estimate leaves the nominal
+    at knot 0's update; the zero-perturbation test of tests/test_gpu_estimated.py holds the tiny tier).  noise: its angles end
+    below pi.  gain: with the twist measured, 0.05 N(0, 1) of a twist innovation of |w| = step / dt is radians and more, every
+    tier; with the pose alone it is at most MEAS_DIAG's 1.0 of an innovation below pi.  step, est_step: at N = 1 the one step
+    carries x*_0's moderate twist plus dx0's 0.05; at N = 4 the true chain's twist takes w across every tier, and the
+    estimate's follows it where the twist is measured; where it is not, the model alone moves it (the drone's, at dt = 0.004,
+    never leaves the short tier)."""
+    full = bool(mask & 0x1C0)
+    need = ["innov:" + t for t in LOG_TIERS] + ["dev:" + t for t in LOG_TIERS[1:]]
+    need += ["noise:" + t for t in EXP_TIERS[1:4]] + ["gain:" + t for t in (EXP_TIERS[1:] if full else EXP_TIERS[1:4])]
+    if N == 1:
+        return tuple(need + ["step:exp_short", "est_step:exp_short"])
+    need += ["step:" + t for t in EXP_TIERS[1:]]
+    return tuple(need + ["est_step:" + t for t in (EXP_TIERS[1:] if full else EXP_TIERS[1:2])])
+
+
+def policy_rollout_tags(prob, q0, xs_q, xs_xi):
+    """The guard of test (d): per sample of one trajectory, the Log tier of its start deviation from q0 = x*_0 and the Exp tier
+    of the twist at every knot (xs_q [S, N+1, 4, 4], xs_xi [S, N+1, 6] from a restatement)."""
+    return [{LOG_TIERS[log_tier(product_quaternion(xs_q[s, 0], q0, left=False)[1])]} |
+            {EXP_TIERS[exp_tier(prob.dt ** 2 * float(xs_xi[s, i, :3] @ xs_xi[s, i, :3]))] for i in range(prob.N + 1)
+             if np.isfinite(xs_xi[s, i]).all()} for s in range(xs_xi.shape[0])]
+
+
+def box_widen(kind, N):
+    """The share of the largest excursion by which tests/limits.py::box_from_unlimited widens the nominal range: a half, as
+    in tests/test_gpu_policy_limits.py, but a quarter for the drone at N = 4, where a half leaves 37 (uniform) and 32 (mixed)
+    of 160 samples saturated, short of the quarter that limited_conditions asks for; a quarter leaves 79 and 73."""
+    return 0.25 if (kind, N) == ("drone", 4) else 0.5
+
+
+VALUE_N, VALUE_B, VALUE_SEED = 24, 8, 600
+# every bucket but "wneg_small": large_rotation_trajectories lays its deviations along the grid's axes, not about the
+# reference's own, and none of them carries a deviation below 0.06 rad across R_to_q's sign change (knot_states does, for
+# eval_knot); w < 0 is reached through "wneg_large"
+VALUE_NEED = tuple(k for k in KNOT_BUCKETS if k != "wneg_small")
+
+
+def large_value_case(kind, twists):
+    """The nominal of the covariance / value parity on large rotations: (prob, xs_q, xs_xi, us, tags).  "sparse" has two grid
+    steps per trajectory, 16 in the batch over the 16 steps of the grid: its guard asks for one knot per bucket, "tiers" for
+    four."""
+    prob = large_rotation_problem(problem_of_kind(kind, 1, VALUE_N)[0])
+    xs_q, xs_xi, us = large_rotation_trajectories(prob, VALUE_B, seed=VALUE_SEED, twists=twists)
+    tags = trajectory_buckets(prob, xs_q, xs_xi)
+    return prob, xs_q, xs_xi, us, tags
+
+
+def value_guard(tags, twists):
+    return assert_coverage(tags, need=VALUE_NEED, least=1 if twists == "sparse" else 4)
+
+
+# check_restatement's bounds, by field of a sampled restatement (J relative, the others absolute)
+RESTATEMENT_BOUNDS = dict(xs_q=1e-10, xs_xi=1e-10, est_q=1e-10, est_xi=1e-10, us=1e-8, u_excess=1e-8, J=1e-9)
+
+
+def nudged(a, rng, eps=1e-15):
+    """a with every entry moved by eps relative, seeded signs: a change in the last place."""
+    return a * (1 + eps * rng.choice([-1, 1], np.shape(a)))
+
+
+def sample_spread(A, A2):
+    """The spread of a sampled restatement: per field of RESTATEMENT_BOUNDS that it holds, the largest difference of every
+    sample between two restatements (lists of dicts, one per trajectory, arrays [S, ...]) whose gains differ in the last
+    place; inf for a sample that is not finite in both.  Returns {field: [B, S]}."""
+    out = {}
+    with np.errstate(all="ignore"):
+        for f in RESTATEMENT_BOUNDS:
+            if f not in A[0]:
+                continue
+            rows = []
+            for a, b in zip(A, A2):
+                d = np.abs(a[f] - b[f]) / (np.abs(a[f]) if f == "J" else 1.0)
+                d = d.reshape(d.shape[0], -1).max(axis=1)
+                rows.append(np.where(np.isfinite(a["J"]) & np.isfinite(b["J"]) & np.isfinite(d), d, np.inf))
+            out[f] = np.array(rows)
+    return out
+
+
+def determined(sp):
+    """[B, S] bool: the samples a restatement determines to the project's bounds -- eight times its spread (sample_spread) is
+    below the bound in every field, the rule of tests/test_gpu_large_rotation.py's rollouts.  The others are compared in
+    status only: no bound is ever wider than the project's."""
+    return np.all([8 * v < RESTATEMENT_BOUNDS[f] for f, v in sp.items()], axis=0)
+
+
+def worst_spread(sp, keep):
+    return {f: float(v[keep].max(initial=0)) for f, v in sp.items()}

@@ -34,7 +34,6 @@ the floor, in that bucket only.  Floors, all measured on the CPU on the states o
     below for the figures and for which rollouts are compared.
 The worst figures of a GPU run are printed by every test and kept in profiles/large_rotation_parity.txt."""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -44,9 +43,9 @@ from oracle import bridge as ob
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
 from tests.checks import K1_FIELDS, check_linearize_backward, check_restatement
 from tests.restate import restate_policy, restate_rollout
-from tests.support import (EXP_TIERS, KNOT_BUCKETS, LOG_TIERS, MODELS, NEAR_PI, assert_coverage, exp_tier, host, knot_states,
-                           large_rotation_problem, large_rotation_trajectories, log_tier, model_case, op_of, problem_of_kind,
-                           product_quaternion, rel, rotation_grid, same, trajectory_buckets)
+from tests.support import (EXP_TIERS, KNOT_BUCKETS, LOG_TIERS, MODELS, Nominal, assert_coverage, exp_tier, host, knot_states,
+                           large_rotation_problem, large_rotation_trajectories, log_tier, model_case, op_of, policy_handle,
+                           policy_perturbations, problem_of_kind, product_quaternion, rel, same, trajectory_buckets)
 
 pytestmark = pytest.mark.gpu
 
@@ -297,48 +296,6 @@ def test_rollout_matches_restatement(kind, B, twists):
 
 
 # ---- d. tolg_policy_rollout -----------------------------------------------------------------------------------------------
-def _policy_perturbations(prob, B, S, layout, seed):
-    """dx0 rotations from the grid's angles -- uniform: a trajectory's 16-sample groups each hold one Log tier; mixed: a seeded
-    shuffle -- and twist noise that moves |omega| dt across the Exp tiers."""
-    ang, steps, axes = rotation_grid()
-    rng = np.random.default_rng(seed)
-    so3 = prob.kind in ("so3", "pendulum3d")
-    by_tier = [[a for a in ang if log_tier(np.sin(a / 2) ** 2) == t and a < np.pi - 2 * NEAR_PI] for t in range(4)]
-    dx0 = np.zeros((B, S, 12)); w = np.zeros((B, S, prob.N, 6))
-    for b in range(B):
-        for smp in range(S):
-            tier = (b + smp // 16) % 4
-            ax = axes[rng.integers(len(axes))]
-            dx0[b, smp, :3] = ax * by_tier[tier][rng.integers(len(by_tier[tier]))]
-            if not so3:
-                dx0[b, smp, 3:6] = rng.normal(size=3) * 0.05
-            dx0[b, smp, 6:9] = rng.normal(size=3) * 0.05
-            for i in range(prob.N):
-                ax = rng.normal(size=3)
-                w[b, smp, i, :3] = ax / np.linalg.norm(ax) * steps[rng.integers(len(steps))] / prob.dt
-        if layout == "mixed":
-            p = rng.permutation(S)
-            dx0[b], w[b] = dx0[b, p], w[b, p]
-    return dx0, w
-
-
-def _policy_handle(prob, B, fast):
-    old = os.environ.pop("TOLG_POLICY_TRAJ_FAST", None)
-    try:
-        if fast:
-            os.environ["TOLG_POLICY_TRAJ_FAST"] = "1"
-        return BatchedTrackingILQR(prob, B)
-    finally:
-        os.environ.pop("TOLG_POLICY_TRAJ_FAST", None)
-        if old is not None:
-            os.environ["TOLG_POLICY_TRAJ_FAST"] = old
-
-
-class _Nominal:
-    def __init__(self, xs_q, xs_xi, us):
-        self.xs_q, self.xs_xi, self.us = xs_q, xs_xi, us
-
-
 @pytest.mark.parametrize("layout", ["uniform", "mixed"])
 @pytest.mark.parametrize("N", [1, 4])
 @pytest.mark.parametrize("kind", ["se3", "drone", "so3"])
@@ -348,7 +305,7 @@ def test_policy_rollout_with_large_perturbations(kind, N, layout):
     B, S = 5, 32
     prob = large_rotation_problem(problem_of_kind(kind, 1, N)[0])
     xs_q, xs_xi, us = large_rotation_trajectories(prob, B, seed=7 + N, twists="moderate")
-    dx0, w = _policy_perturbations(prob, B, S, layout, seed=11 + N)
+    dx0, w = policy_perturbations(prob, B, S, layout, seed=11 + N)
     op = op_of(prob)
     # the coverage guard: the Log tier of every start deviation, the Exp tier of every step, from the restatement's samples
     tags = []
@@ -364,9 +321,9 @@ def test_policy_rollout_with_large_perturbations(kind, N, layout):
     assert_coverage(tags, need=LOG_TIERS + EXP_TIERS[1:])
     out = []
     for fast in (False, True):
-        s = _policy_handle(prob, B, fast)
+        s = policy_handle(prob, B, fast)
         s.linearize_backward(xs_q, xs_xi, us, ms=True)
-        check_restatement(s, _Nominal(xs_q, xs_xi, us), [op] * B, dx0, w, min_finite=(3, 4))
+        check_restatement(s, Nominal(xs_q, xs_xi, us), [op] * B, dx0, w, min_finite=(3, 4))
         out.append(s.policy_rollout(dx0, w, trajectories=True))
     for f in ("J", "status", "xs_q", "xs_xi", "us"):
         assert same(getattr(out[0], f), getattr(out[1], f)), f

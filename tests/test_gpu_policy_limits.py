@@ -17,6 +17,7 @@ import torch
 
 from oracle import bridge as ob
 from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, _capi, workloads
+from tests.checks import compare_limited, limited_conditions
 from tests.limits import box_from_unlimited, clamp, clearance_of, near_bound, restate_policy_limited
 from tests.restate import plant_problem
 from tests.support import host, model_case, op_of, pert, same
@@ -24,7 +25,7 @@ from tests.support import host, model_case, op_of, pert, same
 pytestmark = pytest.mark.gpu
 
 KW = dict(mode="ms", n_iterations=8, tol_grad_norm=0.0, tol_d_norm=0.0)
-TOL_X, TOL_U, TOL_J = 1e-10, 1e-8, 1e-9  # tests/checks.py::check_restatement
+TOL_X, TOL_U, TOL_J = 1e-10, 1e-8, 1e-9  # tests/checks.py::check_restatement, compare_limited
 FIELDS = ("J", "status", "xs_q", "xs_xi", "us")
 LIMITED = FIELDS + ("n_sat", "u_excess")
 
@@ -64,39 +65,6 @@ def _restated(prob, nom, dx0, w, plants=None, box=None):
     return np.array(lbs), np.array(ubs), out
 
 
-def _conditions(R, lb, ub):
-    """The conditions a parity case must meet, on the restatement alone.  Returns (finite [B, S], near a bound [B, S])."""
-    fin = np.array([np.isfinite(r["J"]) for r in R])
-    ns = np.array([r["n_sat"] for r in R])
-    near = np.array([near_bound(r["uc"], lb[b], ub[b]) for b, r in enumerate(R)]) & fin
-    nf = int(fin.sum())
-    print("restatement: finite %d of %d, saturated %d, free %d, near a bound %d"
-          % (nf, fin.size, int((ns[fin] > 0).sum()), int((ns[fin] == 0).sum()), int(near.sum())))
-    assert nf >= fin.size // 2
-    assert 4 * int((ns[fin] > 0).sum()) >= nf
-    assert (ns[fin] == 0).any()
-    assert 4 * int(near.sum()) <= nf
-    return fin, near
-
-
-def _compare(p, R, fin, near):
-    worst = dict(xs_q=0.0, xs_xi=0.0, us=0.0, J=0.0, u_excess=0.0)
-    for b, r in enumerate(R):
-        f = fin[b]
-        assert np.array_equal(host(p.status)[b], np.where(f, _capi.ST_OK, _capi.ST_NONFINITE))
-        worst["xs_q"] = max(worst["xs_q"], np.abs(host(p.xs_q)[b][f] - r["xs_q"][f]).max(initial=0))
-        worst["xs_xi"] = max(worst["xs_xi"], np.abs(host(p.xs_xi)[b][f] - r["xs_xi"][f]).max(initial=0))
-        worst["us"] = max(worst["us"], np.abs(host(p.us)[b][f] - r["us"][f]).max(initial=0))
-        worst["J"] = max(worst["J"], np.abs(host(p.J)[b][f] / r["J"][f] - 1).max(initial=0))
-        worst["u_excess"] = max(worst["u_excess"], np.abs(host(p.u_excess)[b][f] - r["u_excess"][f]).max(initial=0))
-    print("device against restatement:", worst)
-    assert worst["xs_q"] < TOL_X and worst["xs_xi"] < TOL_X and worst["us"] < TOL_U and worst["J"] < TOL_J
-    assert worst["u_excess"] < TOL_U
-    for b, r in enumerate(R):
-        exact = fin[b] & ~near[b]
-        assert np.array_equal(host(p.n_sat)[b][exact], r["n_sat"][exact]), b
-
-
 # 1 -------------------------------------------------------------------------------------------------------------------
 # The perturbation seeds: 11 is tests/test_gpu_policy.py's.  On the restatement it gives se3 and drone 6 saturated samples of
 # 15 finite and so3 8; for the pendulum (trajectory 0 of its 8-iteration solve is not finite: 10 finite samples) only 2 of 10,
@@ -110,9 +78,9 @@ def test_limited_rollouts_match_the_cpu_restatement(model):
     prob, s, nom = _solved(model, B)
     dx0, w = pert(B, S, prob.N, seed=SEEDS[model], **_scale(model))
     lb, ub, R = _restated(prob, nom, dx0, w)
-    fin, near = _conditions(R, lb, ub)
+    fin, near = limited_conditions(R, lb, ub)
     p = s.policy_rollout(dx0, w, trajectories=True, u_lb=lb, u_ub=ub)
-    _compare(p, R, fin, near)
+    compare_limited(p, R, fin, near)
     assert p.clearance is None and p.clearance_knot is None
 
 
@@ -131,9 +99,9 @@ def test_limited_rollouts_on_plants_match_the_cpu_restatement(kind):
         J6 = workloads.plant_mismatch(B, S, N=prob.N, sigma_inertia=0.2, sigma_mass=0.1, rotate=True, seed=2)[6]
     plants = [[plant_problem(prob, J6[b, k]) for k in range(S)] for b in range(B)]
     lb, ub, R = _restated(prob, nom, dx0, w, plants=plants)
-    fin, near = _conditions(R, lb, ub)
+    fin, near = limited_conditions(R, lb, ub)
     p = s.policy_rollout(dx0, w, trajectories=True, plant_J=J6, u_lb=lb, u_ub=ub)
-    _compare(p, R, fin, near)
+    compare_limited(p, R, fin, near)
     free = s.policy_rollout(dx0, w, u_lb=lb, u_ub=ub)
     assert not same(p.J, free.J)  # the plant stepped, not the model
 
@@ -155,7 +123,7 @@ def test_shapes(B, S, N):
     near = np.array([near_bound(r["uc"], lb[b], ub[b]) for b, r in enumerate(R)])
     assert fin.sum() >= fin.size // 2
     p = s.policy_rollout(dx0, w, trajectories=True, u_lb=lb, u_ub=ub)
-    _compare(p, R, fin, near)
+    compare_limited(p, R, fin, near)
     assert sum(int(r["n_sat"].sum()) for r in R) > 0
 
 
