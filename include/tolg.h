@@ -204,6 +204,30 @@ size_t tolg_weights_bytes(const tolg_problem* prob, int32_t max_batch);
 int tolg_set_weights(tolg_handle_t h, int32_t B, const double* d_q_diag, const double* d_p_diag, const double* d_r_diag,
                      void* d_w, size_t w_bytes, void* stream);
 
+/* Pose schedule: a factor s[b][i][k] >= 0 on entry k = 0..5 of the pose-weight diagonal (the first six diagonal entries of
+ * Q / P: rotation error, then translation error) that knot i = 0..N of trajectory b reads -- gates or waypoints weighted
+ * tightly at chosen knots, pose tracking switched off over a stretch.  Wherever a kernel reads that entry for knot i it uses
+ * s[b][i][k] times it, whichever of Q and P the knot selects (the terminal knot's rules included): l, l_x, l_xx of the
+ * linearisation, the cost of every rollout and line search, l_x and l_xx of tolg_policy_value.  Twist weights, R and the
+ * augmented-Lagrangian terms are untouched: the backward sweeps keep them as per-lane constants for the whole horizon, and
+ * the pose block reaches them through the knot records, so a pose schedule changes no sweep.
+ * The schedule sits on top of held per-trajectory weights (tolg_set_weights) and nothing else: every entry point that
+ * reads trajectory b's weights reads its schedule too; tolg_eval_knot keeps the weights of tolg_create.
+ * tolg_pose_schedule_bytes: bytes of the caller-owned buffer that holds the packed factors, (N+1) * 6 * Bp * 8 with
+ * Bp = max_batch rounded up to a multiple of 4; 0 for an invalid problem or max_batch < 1.
+ * tolg_set_pose_schedule: packs d_scale [B][N+1][6] into d_packed on `stream`.  The factors are not read here (a negative
+ * one makes the cost indefinite).  The buffer stays caller-owned and is read by later calls.  d_scale = NULL detaches the
+ * schedule; so does tolg_set_weights with d_q_diag = NULL.
+ * TOLG_E_ARG: a solve in flight; no per-trajectory weights held, or held for another B; B < 1 or B > max_batch;
+ * bytes < tolg_pose_schedule_bytes(prob, B).
+ * tolg_set_pose_schedule_windows: the same packing gathered from B longer schedules d_path_scale [B][T+1][6] by the rule
+ * of tolg_set_ref_windows: knot i of trajectory b takes source knot min(t0[b] + t + i, T), d_t0 = NULL: 0.
+ * TOLG_E_ARG: those above, a NULL path, T < 1, t < 0. */
+size_t tolg_pose_schedule_bytes(const tolg_problem* prob, int32_t max_batch);
+int tolg_set_pose_schedule(tolg_handle_t h, int32_t B, const double* d_scale, void* d_packed, size_t bytes, void* stream);
+int tolg_set_pose_schedule_windows(tolg_handle_t h, int32_t B, const double* d_path_scale, int32_t T, const int32_t* d_t0,
+                                   int32_t t, void* d_packed, size_t bytes, void* stream);
+
 /* Augmented-Lagrangian box input constraint lb <= u <= ub -- replaces ALConstrainedCost wrapping the
  * tracking cost with an InputConstraint (traoptlibrary/traopt_cost.py:1173-1320,
  * traoptlibrary/traopt_constraints.py:66-169).  d_lb/d_ub [m]; d_lambda, d_imu [B][N][2m] (multipliers

@@ -29,7 +29,8 @@ class Options(C.Structure):
 _lib = None
 SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_batch", "tolg_solve_begin",
            "tolg_solve_iterate", "tolg_solve_iterate_until", "tolg_solve_end", "tolg_solve_peek", "tolg_solve_active_count", "tolg_set_al", "tolg_al_update",
-           "tolg_refs_bytes", "tolg_set_refs", "tolg_weights_bytes", "tolg_set_weights", "tolg_eval_knot", "tolg_linearize_backward",
+           "tolg_refs_bytes", "tolg_set_refs", "tolg_weights_bytes", "tolg_set_weights",
+           "tolg_pose_schedule_bytes", "tolg_set_pose_schedule", "tolg_set_pose_schedule_windows", "tolg_eval_knot", "tolg_linearize_backward",
            "tolg_rollout", "tolg_expected_change", "tolg_solve_gains", "tolg_policy_rollout",
            "tolg_solve_begin_warm", "tolg_set_ref_windows", "tolg_mpc_advance", "tolg_obstacles_bytes", "tolg_set_al_obstacles", "tolg_obstacles_moving_bytes", "tolg_set_al_obstacles_moving",
            "tolg_al_update_state", "tolg_al_mpc_step", "tolg_set_al_obstacle_windows", "tolg_set_al_obstacle_kinds", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_policy_covariance_estimated", "tolg_policy_rollout_estimated", "tolg_policy_rollout_limited", "tolg_mpc_advance_limited", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
@@ -78,6 +79,12 @@ def load():
     lib.tolg_weights_bytes.argtypes = [C.POINTER(Problem), C.c_int32]
     lib.tolg_set_weights.restype = C.c_int
     lib.tolg_set_weights.argtypes = [vp, C.c_int32, dp, dp, dp, vp, C.c_size_t, vp]
+    lib.tolg_pose_schedule_bytes.restype = C.c_size_t
+    lib.tolg_pose_schedule_bytes.argtypes = [C.POINTER(Problem), C.c_int32]
+    lib.tolg_set_pose_schedule.restype = C.c_int
+    lib.tolg_set_pose_schedule.argtypes = [vp, C.c_int32, dp, vp, C.c_size_t, vp]
+    lib.tolg_set_pose_schedule_windows.restype = C.c_int
+    lib.tolg_set_pose_schedule_windows.argtypes = [vp, C.c_int32, dp, C.c_int32, ip, C.c_int32, vp, C.c_size_t, vp]
     lib.tolg_al_update.restype = C.c_int
     lib.tolg_al_update.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_double, dp, ip, vp]
     lib.tolg_eval_knot.restype = C.c_int

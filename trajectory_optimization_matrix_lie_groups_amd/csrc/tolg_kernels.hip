@@ -59,6 +59,10 @@ struct Consts {
   // ... and the geometry's knot stride in doubles: 0 (one [4K][Bp] block for every knot) or 4 K Bp (tolg_set_al_obstacles_moving:
   // [N+1][4K][Bp], knot i's block at i * 4 K Bp); the pack kernels set it
   size_t obs_stride;
+  // pose schedule (tolg_set_pose_schedule, caller-owned), read by the PT_W / PTW kernels only: the factor on entry k of the pose
+  // weights of knot i of trajectory b, [N+1][6][Bp], at (6 i + k) * Bp + b; null (tolg_create; the detach): no schedule.  Last:
+  // no other member moves.
+  const double* psched;
 };
 
 // Device-side view of the constants used by the three hot kernels: address space 4 (constant), so
@@ -208,6 +212,50 @@ template <int NN> struct DiagAt {
   const double* p; size_t s;
   TOLG_DEV double operator[](int idx) const { return idx % (NN + 1) == 0 ? p[(size_t)(idx / (NN + 1)) * s] : 0.0; }
 };
+// Pose schedule (tolg_set_pose_schedule; the PTW kernels only): the six pose weights knot i of trajectory b reads, its schedule
+// factors times the diagonal entries `field`.. of the packed weights (W1 or P1, whichever the knot selects) -- the product
+// first: a knot reads the weights s (.) Q.  Nothing attached (Consts::psched null: one wave-uniform branch per knot, as
+// obs_stride is): the entries themselves, so that path runs the loads the kernels have always run and nothing more.  The shared
+// form is empty: no kernel without PTW names psched.
+// Two steps, so that a long knot (lin_knot) can issue the factors' loads ahead of the work that hides them: `factors`, then
+// `weights` where the entries are read.
+template <bool PTW> struct PoseW {
+  TOLG_DEV PoseW() {}
+  template <class CT> TOLG_DEV PoseW(const CT&, const Params&, int, int, int) {}
+};
+template <> struct PoseW<true> {
+  double w[6];
+  bool sched;
+  TOLG_DEV PoseW() {}
+  template <class CT> TOLG_DEV void factors(const CT& C, const Params& P, int i, int b) {
+    const double* ps = C.psched;
+    sched = ps != nullptr;
+    if (sched) {  // one branch around the six loads, not a select per load (each would wait for its own)
+      ps += (size_t)i * 6 * (size_t)P.Bp + b;
+#pragma unroll
+      for (int k = 0; k < 6; k++) w[k] = ps[(size_t)k * P.Bp];
+    }
+  }
+  template <class CT> TOLG_DEV void weights(const CT& C, const Params& P, int b, int field) {
+    const double* wp = C.wts + (size_t)field * (size_t)P.Bp + b;
+    if (sched) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) w[k] = w[k] * wp[(size_t)k * P.Bp];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 6; k++) w[k] = wp[(size_t)k * P.Bp];
+    }
+  }
+  template <class CT> TOLG_DEV PoseW(const CT& C, const Params& P, int i, int b, int field) {
+    factors(C, P, i, b);
+    weights(C, P, b, field);
+  }
+};
+// DiagAt<6> of a pose block under a schedule: diagonal entry k is w[k] (PoseW), every other entry 0.0
+struct PoseDiagAt {
+  const double* w;
+  TOLG_DEV double operator[](int idx) const { return idx % 7 == 0 ? w[idx / 7] : 0.0; }
+};
 // a table of 2 x weights in LDS: the batch-shared NN x NN array, or (PTW) the diagonal of the thread's trajectory
 template <bool PTW, int NN>
 TOLG_DEV auto wtab(const double* diag, const double* full) {
@@ -219,6 +267,12 @@ TOLG_DEV auto wtab(const double* diag, const double* full) {
 template <bool PTW, int NN, class T>
 TOLG_DEV auto wblock(const double* wts, const Params& P, int b, bool sel, T* a, T* d, int fa, int fd) {
   if constexpr (PTW) return DiagAt<NN>{wts + (size_t)(sel ? fa : fd) * P.Bp + b, (size_t)P.Bp};
+  else return sel ? a : d;
+}
+// ... and a pose block (W1 / P1) of a knot: with PTW its scheduled diagonal pw = PoseW(.., sel ? WT_P1 : WT_W1)
+template <bool PTW, class T>
+TOLG_DEV auto wblock_pose(bool sel, T* a, T* d, const PoseW<PTW>& pw) {
+  if constexpr (PTW) return PoseDiagAt{pw.w};
   else return sel ? a : d;
 }
 
@@ -740,6 +794,14 @@ __global__ void k_pack_refs(int B, int Bp, int N, const double* __restrict__ q_r
   Pose X = pose_from_m16(q_ref + ((size_t)bs * (N + 1) + i) * 16);
   pack_ref_knot(X, xi_ref + ((size_t)bs * (N + 1) + i) * 6, refs + (size_t)i * 13 * Bp + b, Bp);
 }
+// The window rule of every input gathered from a world-time path of T + 1 knots (tolg_set_ref_windows,
+// tolg_set_al_obstacle_windows, tolg_set_pose_schedule_windows): knot i of the window of a trajectory whose phase is t0 (null:
+// 0), at step t, is path knot min(t0 + t + i, T) -- the last knot held past the end; a negative phase reads knot 0 (the loads
+// stay inside the path).
+TOLG_DEV size_t window_knot(const int* __restrict__ t0, int bs, int t, long long i, int T) {
+  const long long k = (long long)(t0 ? t0[bs] : 0) + t + i;
+  return (size_t)(k < 0 ? 0 : (k > T ? T : k));
+}
 // the same layout gathered from B longer paths [B][T+1][16] / [B][T+1][6] (tolg_set_ref_windows): knot i of trajectory b's
 // window is knot min(t0[b] + t + i, T) of its path (t0 = null: 0), the last knot held past the end: the bits tolg_set_refs
 // packs from host-sliced windows (pack_ref_knot).
@@ -750,10 +812,9 @@ __global__ void k_pack_ref_windows(int B, int Bp, int N, int T, const double* __
   if (g >= (size_t)(N + 1) * Bp) return;
   int b = (int)(g % Bp), i = (int)(g / Bp);
   int bs = b < B ? b : B - 1;
-  long long k = (long long)(t0 ? t0[bs] : 0) + t + i;
-  k = k < 0 ? 0 : (k > T ? T : k);  // a negative phase reads knot 0 (the loads stay inside the path)
-  Pose X = pose_from_m16(path_q + ((size_t)bs * (T + 1) + (size_t)k) * 16);
-  pack_ref_knot(X, path_xi + ((size_t)bs * (T + 1) + (size_t)k) * 6, refs + (size_t)i * 13 * Bp + b, Bp);
+  const size_t k = window_knot(t0, bs, t, i, T);
+  Pose X = pose_from_m16(path_q + ((size_t)bs * (T + 1) + k) * 16);
+  pack_ref_knot(X, path_xi + ((size_t)bs * (T + 1) + k) * 6, refs + (size_t)i * 13 * Bp + b, Bp);
 }
 
 // the per-trajectory scalars a solve starts from (k_init, k_init_warm)
@@ -978,6 +1039,9 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
   const Pose De = se3_compose(S.X, se3_inverse(Xr));
   const double ye = quat_vec2(De.q), th2d = dot(wd, wd);
   const SeriesGate sg = series_gate(log_small(ye) && coef_small(th2d), log_dom(ye) && exp_dom(th2d));
+  // PT_W: the knot's schedule factors, if a schedule is attached (PoseW): loads issued here, read at the cost loops below
+  PoseW<(PT & PT_W) != 0> px;
+  if constexpr ((PT & PT_W) != 0) px.factors(C, P, i, b);
   // PT_OBS: the spheres' terms first, while little else is live (added to the tracking values at the end of the block)
   constexpr bool PTO = (PT & PT_OBS) != 0;
   double ol = 0.0, ox[3] = {0.0, 0.0, 0.0}, oxx[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -998,6 +1062,8 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
     // in place of the array (the condition is a constant: the shared form compiles to exactly the array reads above)
     constexpr bool PTW = (PT & PT_W) != 0;
 #define LK_W(arr, F, NN, idx) (PTW ? ((idx) % ((NN) + 1) == 0 ? C.wts[(size_t)((F) + (idx) / ((NN) + 1)) * P.Bp + b] : 0.0) : arr[idx])
+    // ... and of a pose block (W1 / P1) entry idx / 7 of wp, the knot's six scheduled diagonal entries (formed below, once)
+#define LK_WP(arr, wp, idx) (PTW ? ((idx) % 7 == 0 ? wp[(idx) / 7] : 0.0) : arr[idx])
     double e[6] = {ew.x, ew.y, ew.z, ev.x, ev.y, ev.z};
     double ve[6] = {S.w.x - r[7], S.w.y - r[8], S.w.z - r[9], S.v.x - r[10], S.v.y - r[11], S.v.z - r[12]};
     double th2 = dot(ew, ew);
@@ -1030,13 +1096,37 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
       for (int a = 0; a < 6; a++) { ed[a] = e[a]; ed[6 + a] = ve[a]; }
       rec_run<REC_D, 12, RP>(P, i, b, ed);
     }
+    // PT_W: the scheduled pose weights of the knot (PoseW), wpx what l_xx reads, wpg what l and l_x read -- the same six
+    // values wherever both select the same block
+    double wpx[6], wpg[6];
+    if constexpr (PTW) {
+      const int fx = term ? WT_P1 : WT_W1, fg = (term && !so3) ? WT_P1 : WT_W1;
+      if (fg != fx) {  // the SO3 family's terminal knot: the same factors on the other block
+        PoseW<true> pg;
+        pg.sched = px.sched;
+        if (px.sched) {
+#pragma unroll
+          for (int k = 0; k < 6; k++) pg.w[k] = px.w[k];
+        }
+        pg.weights(C, P, b, fg);
+#pragma unroll
+        for (int k = 0; k < 6; k++) wpg[k] = pg.w[k];
+      }
+      px.weights(C, P, b, fx);
+#pragma unroll
+      for (int k = 0; k < 6; k++) wpx[k] = px.w[k];
+      if (fg == fx) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) wpg[k] = wpx[k];
+      }
+    }
     double We[6], W2v[6], l = 0;
 #pragma unroll
     for (int a = 0; a < 6; a++) {
       double s1 = 0, s2 = 0;
 #pragma unroll
       for (int k = 0; k < 6; k++) {
-        s1 += LK_W(G1, (term && !so3) ? WT_P1 : WT_W1, 6, 6 * a + k) * e[k];
+        s1 += LK_WP(G1, wpg, 6 * a + k) * e[k];
         s2 += LK_W(G2, (term && !so3) ? WT_P2 : WT_W2, 6, 6 * a + k) * ve[k];
       }
       We[a] = s1; W2v[a] = s2;
@@ -1092,7 +1182,7 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
       for (int c = 0; c < 6; c++) {
         double s = 0;
 #pragma unroll
-        for (int k = 0; k < 6; k++) s += LK_W(W1, term ? WT_P1 : WT_W1, 6, 6 * a + k) * Je[6 * k + c];
+        for (int k = 0; k < 6; k++) s += LK_WP(W1, wpx, 6 * a + k) * Je[6 * k + c];
         WJ[6 * a + c] = s;
       }
     double lxx[21], lxv[12];
@@ -1125,6 +1215,7 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
     rec_run<REC_LXX, 21, RP>(P, i, b, lxx);
     rec_run<REC_LX, 12, RP>(P, i, b, lxv);
 #undef LK_W
+#undef LK_WP
   }
   if (term) return;
   // ---------------- dynamics Jacobian blocks (traopt_dynamics.py:802-837, :1416-1469)
@@ -2952,7 +3043,8 @@ TOLG_DEV double knot_cost(const Params& P, const Consts& C, int i, int b, const 
   if constexpr (FAST) se3_log_fast(se3_compose(S.X, se3_inverse(Xr)), ew, ev);
   else se3_log(se3_compose(S.X, se3_inverse(Xr)), ew, ev);
   const bool so3 = so3_family(C.kind);  // the SO3 terminal cost is weighted with Q (App. C-Q3)
-  const auto W1 = wblock<PTW, 6>(C.wts, P, b, term && !so3, C.P1, C.W1, WT_P1, WT_W1);
+  const PoseW<PTW> pw(C, P, i, b, (term && !so3) ? WT_P1 : WT_W1);
+  const auto W1 = wblock_pose<PTW>(term && !so3, C.P1, C.W1, pw);
   const auto W2 = wblock<PTW, 6>(C.wts, P, b, term && !so3, C.P2, C.W2, WT_P2, WT_W2);
   const auto Rw = wblock<PTW, M>(C.wts, P, b, false, C.R, C.R, WT_R, WT_R);
   double e[6] = {ew.x, ew.y, ew.z, ev.x, ev.y, ev.z};
@@ -4007,9 +4099,10 @@ TOLG_DEV void pv_cost(const Params& P, const Consts& C, int i, int b, const Stat
   se3_log(se3_compose(S.X, se3_inverse(Xr)), ew, ev);
   // weights: l_xx switches to P at the terminal knot; l_x too, except for the SO3 cost which keeps Q there (lin_knot)
   const bool so3 = so3_family(C.kind);
-  const auto W1 = wblock<PTW, 6>(C.wts, P, b, term, C.P1, C.W1, WT_P1, WT_W1);
+  const PoseW<PTW> pw(C, P, i, b, term ? WT_P1 : WT_W1), pg(C, P, i, b, (term && !so3) ? WT_P1 : WT_W1);
+  const auto W1 = wblock_pose<PTW>(term, C.P1, C.W1, pw);
   const auto W2 = wblock<PTW, 6>(C.wts, P, b, term, C.P2, C.W2, WT_P2, WT_W2);
-  const auto G1 = wblock<PTW, 6>(C.wts, P, b, term && !so3, C.P1, C.W1, WT_P1, WT_W1);
+  const auto G1 = wblock_pose<PTW>(term && !so3, C.P1, C.W1, pg);
   const auto G2 = wblock<PTW, 6>(C.wts, P, b, term && !so3, C.P2, C.W2, WT_P2, WT_W2);
   const double e[6] = {ew.x, ew.y, ew.z, ev.x, ev.y, ev.z};
   const double ve[6] = {S.w.x - r[7], S.w.y - r[8], S.w.z - r[9], S.v.x - r[10], S.v.y - r[11], S.v.z - r[12]};
@@ -5326,6 +5419,10 @@ struct tolg_handle_s {
   // pt[H_REFS] tolg_set_refs / tolg_set_ref_windows, pt[H_WTS] tolg_set_weights, pt[H_OBS] tolg_set_al_obstacles(_moving).
   // One batch: every batch call, and every further pt[k], must be for the B of those held (one_batch)
   Held pt[H_PT];
+  // tolg_set_pose_schedule(_windows): the packed factors on the pose weights, or nothing held.  Rides on pt[H_WTS] (set only while
+  // weights are held, dropped with them) and is under the one-batch rule; no PT bit of its own: the PT_W kernels test
+  // Consts::psched
+  Held sched;
   int obs_K = 0;          // pt[H_OBS]: the slots per trajectory,
   unsigned obs_kinds = 0; // ... their kinds (Consts::obs_kinds; tolg_set_al_obstacle_kinds), kept while K stays,
   size_t obs_stride = 0;  // ... the knot stride of the geometry in doubles (Consts::obs_stride): 0, or 4 K Bp for the moving form
@@ -5368,6 +5465,7 @@ static dim3 knot_grid(int knots, int Bp) { return dim3((unsigned)(((size_t)knots
 // kernels never read arrays strided for different Bp
 static bool one_batch(const tolg_handle_s* h, int B, const Held* except = nullptr) {
   for (const Held& r : h->pt) if (&r != except && r.p && B != r.B) return false;
+  if (&h->sched != except && h->sched.p && B != h->sched.B) return false;
   return true;
 }
 // B trajectories fit the handle and the per-trajectory inputs it holds: what every batch call on the handle's workspace requires
@@ -6164,11 +6262,16 @@ extern "C" size_t tolg_weights_bytes(const tolg_problem* prob, int32_t max_batch
   return weights_bytes_for(prob, max_batch);
 }
 
+static int detach_pose_schedule(tolg_handle_s* h, void* stream);  // the schedule rides on the weights (below)
 extern "C" int tolg_set_weights(tolg_handle_t h, int32_t B, const double* d_q_diag, const double* d_p_diag,
                                 const double* d_r_diag, void* d_w, size_t w_bytes, void* stream) {
   if (!h || h->running) return TOLG_E_ARG;
   Held& r = h->pt[H_WTS];
-  if (!d_q_diag) { drop(h, r); return 0; }  // back to the weights of tolg_create
+  if (!d_q_diag) {  // back to the weights of tolg_create; the schedule on them goes too
+    const int rc = detach_pose_schedule(h, stream);
+    drop(h, r);
+    return rc;
+  }
   if (!d_p_diag || !d_r_diag || !dest_ok(h, B, d_w, w_bytes, weights_bytes_for) || !one_batch(h, B, &r)) return TOLG_E_ARG;
   const int Bp = padded_batch(B);
   const size_t n = (size_t)wt_fields(h->prob.m) * Bp;
@@ -6177,6 +6280,61 @@ extern "C" int tolg_set_weights(tolg_handle_t h, int32_t B, const double* d_q_di
   LAUNCH_CHECK();
   hold(h, r, d_w, B);
   return 0;
+}
+
+// d_scale [B][src_knots][6] into [N+1][6][Bp]: factor k of knot i of trajectory b at (6 i + k) * Bp + b; padded trajectories
+// b >= B replicate b = B-1.  Knot i is read from source knot i (t < 0: src_knots = N + 1) or gathered from a world-time path
+// (t >= 0: window_knot).  Thread 0 points the handle's constants at the packed factors (stream-ordered before the solves that
+// read them); w = null only detaches.
+__global__ void k_pack_pose_schedule(int B, int Bp, int N, const double* __restrict__ scale, int src_knots, const int* __restrict__ t0,
+                                     int t, double* __restrict__ w, Consts* c) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g == 0) c->psched = w;
+  if (!w || g >= (size_t)(N + 1) * 6 * Bp) return;
+  const int b = (int)(g % Bp), k = (int)(g / Bp % 6);
+  const size_t i = g / Bp / 6;
+  const int bs = b < B ? b : B - 1;
+  const size_t src = t >= 0 ? window_knot(t0, bs, t, (long long)i, src_knots - 1) : i;
+  w[g] = scale[((size_t)bs * src_knots + src) * 6 + k];
+}
+static size_t pose_schedule_bytes_for(const tolg_problem* p, int B, int = 0) {
+  return (size_t)(p->N + 1) * 6 * (size_t)padded_batch(B) * sizeof(double);
+}
+extern "C" size_t tolg_pose_schedule_bytes(const tolg_problem* prob, int32_t max_batch) {
+  if (check_problem(prob) || max_batch < 1) return 0;
+  return pose_schedule_bytes_for(prob, max_batch);
+}
+// no schedule from here on in stream order (the kernels read Consts::psched)
+static int detach_pose_schedule(tolg_handle_s* h, void* stream) {
+  if (!h->sched.p) return 0;
+  hipLaunchKernelGGL(k_pack_pose_schedule, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), 0, 0, 0, (const double*)nullptr, 0,
+                     (const int*)nullptr, -1, (double*)nullptr, const_cast<Consts*>(h->P.c));
+  LAUNCH_CHECK();
+  drop(h, h->sched);
+  return 0;
+}
+// t < 0: d_scale holds the N + 1 knots themselves (tolg_set_pose_schedule)
+static int set_pose_schedule(tolg_handle_t h, int B, const double* d_scale, int src_knots, const int32_t* d_t0, int t, void* d_packed,
+                             size_t bytes, void* stream) {
+  const Held& w = h->pt[H_WTS];
+  // on top of held weights only, and for their batch
+  if (!w.p || B != w.B || !dest_ok(h, B, d_packed, bytes, pose_schedule_bytes_for) || !one_batch(h, B, &h->sched)) return TOLG_E_ARG;
+  const int N = h->prob.N, Bp = padded_batch(B);
+  hipLaunchKernelGGL(k_pack_pose_schedule, knot_grid((N + 1) * 6, Bp), dim3(256), 0, static_cast<hipStream_t>(stream), B, Bp, N, d_scale,
+                     src_knots, reinterpret_cast<const int*>(d_t0), t, static_cast<double*>(d_packed), const_cast<Consts*>(h->P.c));
+  LAUNCH_CHECK();
+  hold(h, h->sched, d_packed, B);
+  return 0;
+}
+extern "C" int tolg_set_pose_schedule(tolg_handle_t h, int32_t B, const double* d_scale, void* d_packed, size_t bytes, void* stream) {
+  if (!h || h->running) return TOLG_E_ARG;
+  if (!d_scale) return detach_pose_schedule(h, stream);
+  return set_pose_schedule(h, B, d_scale, h->prob.N + 1, nullptr, -1, d_packed, bytes, stream);
+}
+extern "C" int tolg_set_pose_schedule_windows(tolg_handle_t h, int32_t B, const double* d_path_scale, int32_t T, const int32_t* d_t0,
+                                              int32_t t, void* d_packed, size_t bytes, void* stream) {
+  if (!h || h->running || !d_path_scale || T < 1 || t < 0) return TOLG_E_ARG;
+  return set_pose_schedule(h, B, d_path_scale, T + 1, d_t0, t, d_packed, bytes, stream);
 }
 
 // d_obs [B][src_knots][K][4] = (cx, cy, cz, r) into [knots][4K][Bp]: field f = 4k + c of knot i of trajectory b at (i * 4K + f) * Bp
@@ -6197,10 +6355,7 @@ __global__ void k_pack_obstacles_moving(int B, int Bp, int K, int knots, size_t 
   const int b = (int)(r % Bp), f = (int)(r / Bp);
   const int bs = b < B ? b : B - 1;
   size_t src = i;
-  if (t >= 0) {
-    long long k = (long long)(t0 ? t0[bs] : 0) + t + (long long)i;
-    src = (size_t)(k < 0 ? 0 : (k > src_knots - 1 ? src_knots - 1 : k));  // a negative phase reads knot 0 (the loads stay inside the path)
-  }
+  if (t >= 0) src = window_knot(t0, bs, t, (long long)i, src_knots - 1);
   w[g] = obs[((size_t)bs * src_knots + src) * 4 * K + f];
 }
 

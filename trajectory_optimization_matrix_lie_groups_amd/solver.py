@@ -393,6 +393,7 @@ _POLICY = {"tolg_solve_begin": "clear", "tolg_solve_begin_warm": "clear", "tolg_
 # A setter's detach call (BatchedTrackingILQR._detach): its arguments behind the handle with the source pointer null, the
 # stream's place included.  tolg_set_al_obstacles detaches the per-knot form too.
 _DETACH = {"tolg_set_refs": (0, None, None, None, 0, None), "tolg_set_weights": (0, None, None, None, None, 0, None),
+           "tolg_set_pose_schedule": (0, None, None, 0, None),
            "tolg_set_al_obstacles": (0, 0, None, None, None, None, 0, None), "tolg_set_al": (None, None, None, None),
            "tolg_set_plant": (0, 0, 0, None, None, None, 0, None)}
 
@@ -407,6 +408,8 @@ class _Batch:
     refs: Optional[tuple] = None  # (q [B, N+1, 16], xi [B, N+1, 6]) per trajectory, or None: the problem's reference
     wts: Optional[tuple] = None   # diagonals (q [B, 12], p [B, 12], r [B, m]) per trajectory, or None: the problem's weights
     xs: Optional[tuple] = None    # warm-start shooting states (q [B, N+1, 16], xi [B, N+1, 6]), or None
+    # the pose schedule on wts: the factors ([B, N+1, 6],), or staged windows (paths [B, T+1, 6], T, t0 or None, t), or None
+    sched: Optional[tuple] = None
 
 
 class BatchedTrackingILQR:
@@ -427,7 +430,8 @@ class BatchedTrackingILQR:
         self._refs_set = self._wts_set = False  # the handle points at per-trajectory references / weights
         # the packed inputs the handle reads (_packed): per-trajectory references, weights and static spheres for max_batch
         # (x MAX_OBSTACLES), per-knot spheres and plant rows for the largest call so far
-        self._refs_buf = self._wts_buf = self._obs_buf = self._obs_mov_buf = self._plant_buf = None
+        self._refs_buf = self._wts_buf = self._obs_buf = self._obs_mov_buf = self._plant_buf = self._sched_buf = None
+        self._sched_next = None    # set_pose_schedule_windows: the staged windows the next batch call takes (_Batch.sched)
         self._inflight = (None, None)  # the FitResult of the solve in flight; the inputs the stream may not have read (_hold)
         self._al = None            # the augmented-Lagrangian terms the handle points at (set_al)
         self._obs = None           # ... and the keep-out spheres (set_al_obstacles): (obstacles, lam, imu) on the device
@@ -508,8 +512,12 @@ class BatchedTrackingILQR:
         return _ptr(buf), C.c_size_t(buf.numel() * 8)
 
     def _detach(self, fn):
-        """Return the handle to what tolg_create left for setter `fn` (_DETACH)."""
-        self._call(fn, *_DETACH[fn], stream=False)
+        """Return the handle to what tolg_create left for setter `fn` (_DETACH).  On the solver's stream where the setter takes
+        one: detaching the weights or the schedule writes the device constants in stream order."""
+        if fn == "tolg_set_al":
+            self._call(fn, *_DETACH[fn], stream=False)
+        else:
+            self._call(fn, *_DETACH[fn][:-1])
 
     def _check_refs(self, B, q_ref, xi_ref):
         """Per-trajectory references [B, N+1, 4, 4] / [B, N+1, 6], checked on the host: ValueError before anything reaches
@@ -540,6 +548,43 @@ class BatchedTrackingILQR:
             out.append(np.ascontiguousarray(d))
         return tuple(out)
 
+    def _check_pose_scale(self, B, pose_scale):
+        """A pose schedule: the factor on the six pose weights (the first six diagonal entries of Q / P: rotation error, then
+        translation error) that knot i of trajectory b reads.  [B, N+1, 6]; [N+1, 6], every trajectory the same; [B, N+1] or
+        [N+1], one factor for all six coordinates (a 2-D array of shape (N+1, 6) is read as [N+1, 6]).  Checked on the host:
+        ValueError for another shape, a non-finite or a negative entry.  Returns [B, N+1, 6] float64 numpy, or None when
+        omitted (no schedule)."""
+        if pose_scale is None:
+            return None
+        a = _checked("pose_scale", pose_scale, (None,) * np.ndim(pose_scale), finite=True)
+        n = self.N + 1
+        if a.shape == (B, n, 6):
+            pass
+        elif a.shape == (n, 6):
+            a = np.broadcast_to(a, (B, n, 6))
+        elif a.shape == (B, n):
+            a = np.broadcast_to(a[:, :, None], (B, n, 6))
+        elif a.shape == (n,):
+            a = np.broadcast_to(a[None, :, None], (B, n, 6))
+        else:
+            raise ValueError("pose_scale has shape %s, expected (%d, %d, 6), (%d, 6), (%d, %d) or (%d,)"
+                             % (tuple(a.shape), B, n, n, B, n, n))
+        if np.any(a < 0.0):
+            raise ValueError("pose_scale must not be negative")
+        return np.ascontiguousarray(a)
+
+    def _own_weights(self, B):
+        """The problem's own Q, P, R as per-trajectory diagonals (q [B, 12], p [B, 12], r [B, m]): what a pose schedule sits
+        on when the caller gives no weights.  ValueError when one of them is not diagonal: the per-trajectory kernels read
+        diagonals only."""
+        out = []
+        for name, a, n in (("Q", self.problem.Q, 12), ("P", self.problem.P, 12), ("R", self.problem.R, self.m)):
+            a = np.asarray(a, dtype=np.float64).reshape(n, n)
+            if np.any(a - np.diag(np.diag(a)) != 0.0):
+                raise ValueError("a pose schedule sits on per-trajectory (diagonal) weights: the problem's %s is not diagonal" % name)
+            out.append(np.ascontiguousarray(np.broadcast_to(np.diag(a), (B, n))))
+        return tuple(out)
+
     def _check_xs_init(self, B, xs_init, mode):
         """xs_init = (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6]) checked on the host; None when omitted."""
         if xs_init is None:
@@ -551,36 +596,52 @@ class BatchedTrackingILQR:
             raise ValueError("xs_init is a pair (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6])")
         return _checked("xs_init[0]", xs_init[0], (B, self.N + 1, 4, 4)), _checked("xs_init[1]", xs_init[1], (B, self.N + 1, 6))
 
-    def _stage(self, x_q, x_xi, us, refs=(None, None), weights=(None, None, None), xs_init=None, mode="ms", traj=False):
+    def _stage(self, x_q, x_xi, us, refs=(None, None), weights=(None, None, None), xs_init=None, mode="ms", traj=False,
+               pose_scale=None):
         """The one way a batch's inputs reach the device: x_q reshaped to [B, 16] gives B (traj=True: whole trajectories
-        [B, N+1, 16], linearize_backward), then the per-trajectory references (q_ref, xi_ref), weights (Q, P, R) and
-        xs_init are checked on the host, and everything moves to the device.  us = None: zeros (not for trajectories)."""
+        [B, N+1, 16], linearize_backward), then the per-trajectory references (q_ref, xi_ref), weights (Q, P, R), the pose
+        schedule and xs_init are checked on the host, and everything moves to the device.  us = None: zeros (not for
+        trajectories).  A schedule without weights sits on the problem's own (_own_weights); with no pose_scale the call
+        takes the windows set_pose_schedule_windows staged for it, if any."""
         k = (self.N + 1,) if traj else ()
         x_q = self._dev(x_q, (-1,) + k + (16,))
         B = x_q.shape[0]
         refs = self._check_refs(B, *refs)
         wts = self._check_weights(B, *weights)
+        sched = self._check_pose_scale(B, pose_scale)
+        staged, self._sched_next = self._sched_next, None
+        if sched is not None:
+            sched = (self._dev(sched, sched.shape),)
+        elif staged is not None:
+            if staged[0].shape[0] != B:
+                raise ValueError("set_pose_schedule_windows staged a schedule for %d trajectories, this call has %d"
+                                 % (staged[0].shape[0], B))
+            sched = staged
+        if sched is not None and wts is None:
+            wts = self._own_weights(B)
         xs = self._check_xs_init(B, xs_init, mode)
         x_xi = self._dev(x_xi, (B,) + k + (6,))
         if us is None and not traj:
             us = torch.zeros(B, self.N, self.m, dtype=torch.float64, device=self.device)
         pair = lambda p: None if p is None else (self._dev(p[0], (B, self.N + 1, 16)), self._dev(p[1], (B, self.N + 1, 6)))  # noqa: E731
         return _Batch(B, x_q, x_xi, self._dev(us, (B, self.N, self.m)), pair(refs),
-                      None if wts is None else tuple(self._dev(a, a.shape) for a in wts), pair(xs))
+                      None if wts is None else tuple(self._dev(a, a.shape) for a in wts), pair(xs), sched)
 
     def clear_per_trajectory(self):
-        """Return the handle to the problem's shared reference and weights (tolg_set_refs / tolg_set_weights with NULL).  The
-        solve calls do this themselves when they are given no per-trajectory inputs; this is for callers that drove the C
-        ABI on the handle directly."""
+        """Return the handle to the problem's shared reference and weights, without a pose schedule (tolg_set_pose_schedule /
+        tolg_set_refs / tolg_set_weights with NULL).  The solve calls do this themselves when they are given no per-trajectory
+        inputs; this is for callers that drove the C ABI on the handle directly."""
+        self._sched_next = None
+        self._detach("tolg_set_pose_schedule")
         self._detach("tolg_set_weights")
         self._detach("tolg_set_refs")
         self._wts_set = self._refs_set = False
 
-    def _use_pt(self, B, refs, wts):
-        """Point the handle at this call's references (tolg_set_refs) and weights (tolg_set_weights), device tensors of a
-        _Batch, or back at the problem's shared ones for what is None: every call states its own, nothing carries over from
-        an earlier call.  The weights are detached first, so that references for a new B never meet weights set for an
-        earlier one."""
+    def _use_pt(self, B, refs, wts, sched=None):
+        """Point the handle at this call's references (tolg_set_refs), weights (tolg_set_weights) and the pose schedule on
+        them (_Batch.sched), device tensors of a _Batch, or back at the problem's shared ones for what is None: every call
+        states its own, nothing carries over from an earlier call.  The weights are detached first (their schedule goes with
+        them), so that references for a new B never meet weights set for an earlier one."""
         if self._wts_set:
             self._detach("tolg_set_weights")
             self._wts_set = False
@@ -588,6 +649,17 @@ class BatchedTrackingILQR:
         if wts is not None:
             self._call("tolg_set_weights", B, *map(_ptr, wts), *self._packed("_wts_buf", self.lib.tolg_weights_bytes))
             self._wts_set = True
+        if sched is not None:
+            self._set_pose_schedule(B, sched)
+
+    def _set_pose_schedule(self, B, sched):
+        """tolg_set_pose_schedule(_windows) of a _Batch.sched on the weights the handle holds for B."""
+        dest = self._packed("_sched_buf", self.lib.tolg_pose_schedule_bytes)
+        if len(sched) == 1:
+            self._call("tolg_set_pose_schedule", B, _ptr(sched[0]), *dest)
+        else:
+            path, T, t0_d, t = sched
+            self._call("tolg_set_pose_schedule_windows", B, _ptr(path), int(T), _ptr(t0_d), int(t), *dest)
 
     def _use_refs(self, B, refs):
         """Point the handle at the references refs = (q [B, N+1, 4, 4], xi [B, N+1, 6]) (tolg_set_refs), or back at the
@@ -615,7 +687,7 @@ class BatchedTrackingILQR:
     def solve_begin(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
                     tol_d_norm=1e-6, line_search=False, rollout="nonlinear", max_reg=1e10, histories=True,
                     out: Optional[FitResult] = None, schedule="auto", q_ref=None, xi_ref=None, Q=None, P=None,
-                    R=None, xs_init=None) -> FitResult:
+                    R=None, xs_init=None, pose_scale=None) -> FitResult:
         """_initial_guess + first _linearization; leaves the batch resident in HBM.
         schedule: "auto" (rollout and re-linearisation fused in one launch where the mode allows it) or
         "split" (separate launches); launch structure only, same algorithm.
@@ -623,9 +695,13 @@ class BatchedTrackingILQR:
         (tolg_set_refs); omitted, the problem's shared reference.
         Q [B, 12, 12], P [B, 12, 12], R [B, m, m] (optional, all three or none, diagonal): trajectory b's cost weights in this
         solve (tolg_set_weights); omitted, the problem's shared weights.
+        pose_scale (optional): a schedule on the pose weights, a factor per knot (_check_pose_scale: [B, N+1, 6], [N+1, 6],
+        [B, N+1] or [N+1]; tolg_set_pose_schedule): knot i of trajectory b weights its pose error with pose_scale[b, i] times
+        the first six diagonal entries of Q (of P where the knot reads P).  Pose weights only: twist weights and R stay
+        constant along the horizon.  Without Q / P / R it sits on the problem's own weights, which must then be diagonal.
         xs_init (optional, multiple shooting only): (xs_q [B, N+1, 4, 4], xs_xi [B, N+1, 6]), a warm start of the shooting
         states (tolg_solve_begin_warm): knots 1..N of the initial guess in place of the reference; knot 0 is x0."""
-        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R), xs_init, mode)
+        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R), xs_init, mode, pose_scale=pose_scale)
         o = self._options(mode, n_iterations, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg, schedule)
         return self._start(b, o, histories, out)
 
@@ -639,7 +715,7 @@ class BatchedTrackingILQR:
         """solve_begin on a staged batch: the handle pointed at its references and weights, then its solve begun."""
         if out is None:
             out = self._alloc_result(b.B, o.max_iter, histories)
-        self._use_pt(b.B, b.refs, b.wts)
+        self._use_pt(b.B, b.refs, b.wts, b.sched)
         self._hold(b)
         return self._begin(o, b.B, b.x_q, b.x_xi, b.us, b.xs, out)
 
@@ -688,7 +764,7 @@ class BatchedTrackingILQR:
     def fit_batch(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
                   tol_d_norm=1e-6, line_search=False, rollout="nonlinear", max_reg=1e10,
                   histories=True, out: Optional[FitResult] = None, schedule="auto", check_every=16, q_ref=None,
-                  xi_ref=None, Q=None, P=None, R=None, xs_init=None) -> FitResult:
+                  xi_ref=None, Q=None, P=None, R=None, xs_init=None, pose_scale=None) -> FitResult:
         """B independent fits (the reference's joblib fan-out, visualization/perturb_all_compute.py:240).
         Inputs may be numpy arrays or tensors already on the device; outputs are device tensors.
         The iterations are issued in slices of `check_every`; behind each slice the number of trajectories still
@@ -697,8 +773,9 @@ class BatchedTrackingILQR:
         all n_iterations without a host read.  `iterations_issued` keeps how many were queued.
         q_ref [B, N+1, 4, 4], xi_ref [B, N+1, 6] (optional, numpy or torch): a reference per trajectory for this fit.
         Q [B, 12, 12], P [B, 12, 12], R [B, m, m] (optional, all three or none, diagonal): cost weights per trajectory.
+        pose_scale (optional): a per-knot schedule on the pose weights, as for solve_begin.
         xs_init (optional, mode="ms"): warm-start shooting states, as for solve_begin."""
-        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R), xs_init, mode)
+        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R), xs_init, mode, pose_scale=pose_scale)
         o = self._options(mode, n_iterations, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg, schedule)
         return self._fit(b, o, check_every, histories, out)
 
@@ -709,15 +786,15 @@ class BatchedTrackingILQR:
 
     def solve_batch_one_call(self, x0_q, x0_xi, us_init=None, mode="ms", n_iterations=100, tol_grad_norm=1e-6,
                              tol_d_norm=1e-6, line_search=False, rollout="nonlinear", max_reg=1e10, schedule="auto",
-                             check_every=0, q_ref=None, xi_ref=None, Q=None, P=None, R=None) -> FitResult:
+                             check_every=0, q_ref=None, xi_ref=None, Q=None, P=None, R=None, pose_scale=None) -> FitResult:
         """The same fit through the single entry point tolg_solve_batch (what a C / C++ caller binds): begin,
         iterations (tolg_options.check_every: 0 = all of them, never synchronising), end in one call.
-        q_ref / xi_ref, Q / P / R: as for fit_batch."""
-        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R))
+        q_ref / xi_ref, Q / P / R, pose_scale: as for fit_batch."""
+        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R), pose_scale=pose_scale)
         K = int(n_iterations)
         out = self._alloc_result(b.B, K, True)
         o = self._options(mode, K, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg, schedule, check_every)
-        self._use_pt(b.B, b.refs, b.wts)
+        self._use_pt(b.B, b.refs, b.wts, b.sched)
         self._hold(b)
         self._call("tolg_solve_batch", C.byref(o), b.B, _ptr(b.x_q), _ptr(b.x_xi), _ptr(b.us), _ptr(out.xs_q), _ptr(out.xs_xi),
                    _ptr(out.us), _ptr(out.J_hist), _ptr(out.grad_hist), _ptr(out.defect_hist), _ptr(out.alpha_hist),
@@ -889,11 +966,13 @@ class BatchedTrackingILQR:
 
     def al_fit_batch(self, x0_q, x0_xi, us_init, lb=None, ub=None, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
                      tol_d_norm=1e-6, tol_constr=1e-2, mu0=1e-2, mu_scale=10.0, mu_max=1e8, line_search=False,
-                     on_outer=None, q_ref=None, xi_ref=None, Q=None, P=None, R=None, obstacles=None, obstacle_kinds=None):
+                     on_outer=None, q_ref=None, xi_ref=None, Q=None, P=None, R=None, obstacles=None, obstacle_kinds=None,
+                     pose_scale=None):
         """AL_iLQR_Tracking_SE3_MS.fit (reference traoptlibrary/traopt_controller.py:3218-3267) for B
         independent problems: every outer iteration re-solves from (x0, us_init) -- no warm start, as in
         the reference -- then updates multipliers on the device.  Returns (FitResult, info dict).
-        q_ref / xi_ref: a reference per trajectory, Q / P / R: weights per trajectory, as for fit_batch.
+        q_ref / xi_ref: a reference per trajectory, Q / P / R: weights per trajectory, pose_scale: a per-knot schedule on the
+        pose weights, as for fit_batch.
         Constraints: the input box lb <= u <= ub, keep-out spheres obstacles ([K, 4], [B, K, 4] or per knot [B, N+1, K, 4],
         set_al_obstacles; obstacle_kinds: its kinds=, a kind per slot -- keep-in sphere, half-space, column), or both
         (one mu per problem, joint convergence: tolg_al_update_state).  With spheres the info dict also holds lmbd_obs and
@@ -902,7 +981,7 @@ class BatchedTrackingILQR:
             raise ValueError("the input box needs both lb and ub")
         if lb is None and obstacles is None:
             raise ValueError("al_fit_batch needs a constraint: lb / ub, obstacles, or both")
-        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R))
+        b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R), pose_scale=pose_scale)
         B = b.B
         if obstacles is None and obstacle_kinds is not None:
             raise ValueError("obstacle_kinds describe obstacles: none were given")
@@ -965,7 +1044,7 @@ class BatchedTrackingILQR:
         return final, info
 
     def plan_fleet(self, x0_q, x0_xi, us_init, q_ref, xi_ref, fleet, separation, obstacles=None, lb=None, ub=None,
-                   obstacle_kinds=None, **al_kw):
+                   obstacle_kinds=None, pose_scale=None, **al_kw):
         """Prioritised planning for F = B / fleet independent fleets in one batch: trajectory b is member p = b % fleet of
         fleet b // fleet.  Round p = 0 .. fleet-1 solves the F members p, each on its own reference (q_ref [B, N+1, 4, 4],
         xi_ref [B, N+1, 6]), keeping out of the caller's static `obstacles` ([K0, 4] or [B, K0, 4]) and of p moving spheres of
@@ -975,7 +1054,8 @@ class BatchedTrackingILQR:
         The constraint holds at the knots, not between them: two members may pass closer than `separation` between two knots.
         A lower-priority member yields to a higher one: member 0 plans as if alone, and whether member p finds a way round the
         others is its own round's convergence.  K0 + fleet - 1 <= MAX_OBSTACLES.  obstacle_kinds: the kinds of the caller's K0
-        static slots (set_al_obstacles' kinds=); the member spheres behind them are keep-out spheres.
+        static slots (set_al_obstacles' kinds=); the member spheres behind them are keep-out spheres.  pose_scale: a per-knot
+        schedule on the pose weights in batch order (fit_batch's; every round takes its members' rows).
         Returns (FitResult in batch order, info): min_separation [F] the smallest centre distance over knots and pairs of
         the final plans (inf for fleet = 1), max_violation [B], al_converged [B] int32 (rounds without a constraint: 0 and
         1), outer_iterations [fleet] (python ints)."""
@@ -1003,6 +1083,7 @@ class BatchedTrackingILQR:
         if us_init is None:
             us_init = np.zeros((B, self.N, self.m))
         per = {k: al_kw.pop(k) for k in ("Q", "P", "R") if k in al_kw}
+        per["pose_scale"] = self._check_pose_scale(B, pose_scale)
         f64 = dict(dtype=torch.float64, device=self.device)
         maxviol = torch.zeros(B, **f64)
         alconv = torch.ones(B, dtype=torch.int32, device=self.device)
@@ -1037,11 +1118,11 @@ class BatchedTrackingILQR:
 
     # ------------------------------------------------------------------------------------------
     def linearize_backward(self, xs_q, xs_xi, us, ms=True, mu=1.0, delta=2.0, max_reg=1e10, q_ref=None, xi_ref=None, Q=None,
-                           P=None, R=None):
+                           P=None, R=None, pose_scale=None):
         """One _linearization + _backward_pass (+ gradient norm) on given trajectories.  q_ref / xi_ref: a reference per
-        trajectory, Q / P / R: weights per trajectory, as for fit_batch (rollout / expected_change behind this call use the
-        same references and weights)."""
-        b = self._stage(xs_q, xs_xi, us, (q_ref, xi_ref), (Q, P, R), traj=True)
+        trajectory, Q / P / R: weights per trajectory, pose_scale: a per-knot schedule on the pose weights, as for fit_batch
+        (rollout / expected_change behind this call use the same references, weights and schedule)."""
+        b = self._stage(xs_q, xs_xi, us, (q_ref, xi_ref), (Q, P, R), traj=True, pose_scale=pose_scale)
         B = b.B
         f64 = dict(dtype=torch.float64, device=self.device)
         md = torch.empty(B, 2, **f64)
@@ -1051,7 +1132,7 @@ class BatchedTrackingILQR:
                  lx=torch.empty(B, self.N + 1, 12, **f64), lxx11=torch.empty(B, self.N + 1, 6, 6, **f64),
                  k=torch.empty(B, self.N, self.m, **f64), K=torch.empty(B, self.N, self.m, 12, **f64),
                  J=torch.empty(B, **f64), dnorm=torch.empty(B, **f64), grad=torch.empty(B, **f64), mu_delta=md)
-        self._use_pt(B, b.refs, b.wts)
+        self._use_pt(B, b.refs, b.wts, b.sched)
         self._hold(b)
         self._call("tolg_linearize_backward", int(ms), float(max_reg), B, _ptr(b.x_q), _ptr(b.x_xi), _ptr(b.us), _ptr(md),
                    *(_ptr(r[k]) for k in ("Fx", "d", "lx", "lxx11", "k", "K", "J", "dnorm", "grad")), batch=B)
@@ -1447,6 +1528,35 @@ class BatchedTrackingILQR:
         self._hold((q, xi, t0_d))
         self._set_ref_windows(B, q, xi, T, t0_d, int(t))
 
+    def _schedule_paths(self, B, path_scale):
+        """World-time schedules [B, T+1, 6] checked on the host (finite, not negative, T >= 1) and moved to the device;
+        returns (paths, T)."""
+        a = _checked("pose_scale_path", path_scale, (B, None, 6), finite=True)
+        if a.shape[1] < 2:
+            raise ValueError("pose_scale_path has %d knots, expected T+1 >= 2" % a.shape[1])
+        if np.any(a < 0.0):
+            raise ValueError("pose_scale_path must not be negative")
+        return self._dev(a, a.shape), a.shape[1] - 1
+
+    def set_pose_schedule_windows(self, path_scale, t, t0=None):
+        """Stage the pose schedule of the next batch call (solve_begin / fit_batch / solve_batch_one_call / al_fit_batch /
+        linearize_backward, given no pose_scale of its own) as windows of B longer schedules in world time: path_scale
+        [B, T+1, 6]; knot i of trajectory b takes path knot min(t0[b] + t + i, T), set_ref_windows' rule (t0 an int array [B],
+        None: 0).  That call gathers the windows on the device behind its weights (tolg_set_pose_schedule_windows) -- the
+        schedule sits on per-trajectory weights, and every call states its own -- and is then exactly the call with
+        pose_scale= the host-gathered windows; the call after it is unscheduled again.  path_scale = None withdraws what is
+        staged."""
+        if path_scale is None:
+            self._sched_next = None
+            return
+        B = int(np.shape(path_scale)[0]) if len(np.shape(path_scale)) else 0
+        if not 1 <= B <= self.max_batch:
+            raise ValueError("path_scale: batch %d outside 1..%d" % (B, self.max_batch))
+        if int(t) < 0:
+            raise ValueError("t must be non-negative")
+        d, T = self._schedule_paths(B, path_scale)
+        self._sched_next = (d, T, self._check_t0(B, t0), int(t))
+
     def mpc_advance(self, w=None, J_cl=None, plant_J=None, plant_pend=None, u_lb=None, u_ub=None):
         """One receding-horizon step on the held policy (tolg_mpc_advance): x_next = f(x*_0, u*_0) + [0; w] with the exact
         dynamics, u = u*_0, and the warm start of the next step (xs_q / xs_xi [B, N+1, ...], us [B, N, m]: the solution
@@ -1493,7 +1603,7 @@ class BatchedTrackingILQR:
             warm="states", noise=None, mode="ms", line_search=False, rollout="nonlinear", tol_grad_norm=1e-6, tol_d_norm=1e-6,
             check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None, plant_J=None, plant_pend=None, u_lb=None,
             u_ub=None, lb=None, ub=None, obstacles=None, obstacle_paths=None, obstacle_kinds=None, first_al_iters=3,
-            al_iters_per_step=1, mu0=1e-2, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2) -> MPCResult:
+            al_iters_per_step=1, mu0=1e-2, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2, pose_scale_path=None) -> MPCResult:
         """Receding-horizon MPC: `steps` closed-loop steps of B trajectories, each tracking its own path from its own phase.
         Step t: windows min(t0[b] + t + i, T) of the paths (tolg_set_ref_windows), a solve of first_iters (t = 0) or
         iters_per_step iterations, then tolg_mpc_advance applies u*_0, steps the plant with the exact dynamics and adds the
@@ -1502,7 +1612,9 @@ class BatchedTrackingILQR:
           warm="controls": the shifted controls only, MS states from the reference window (tolg_solve_begin).
         The first solve starts from us_init (None: 0) and the reference window.  check_every = 0 issues a fixed count of
         iterations with no host read in the whole loop; > 0 stops a step's solve early (solve_iterate_until).  Q / P / R:
-        weights per trajectory as for fit_batch.  on_step(t, FitResult) is called behind every step's solve (before the
+        weights per trajectory as for fit_batch.  pose_scale_path [B, T_s+1, 6]: a schedule on the pose weights in world time,
+        gathered every step with the same t0 as the reference windows (tolg_set_pose_schedule_windows; without Q / P / R on the
+        problem's own weights); the handle is left without one.  on_step(t, FitResult) is called behind every step's solve (before the
         plant step; the FitResult carries histories then).  plant_J [B, 6, 6] / plant_pend [B, 2]: the plant every step's
         x_next is stepped with (model mismatch, as mpc_advance; None: the model); the solves plan on the model.  u_lb / u_ub [m] or
         [B, m]: the actuator's box (as mpc_advance: every step applies clamp(u*_0); it clips the plant only and is independent
@@ -1554,7 +1666,11 @@ class BatchedTrackingILQR:
             us_init = _checked("us_init", us_init, (B, self.N, self.m))
         pq, pxi, T = self._paths(B, path_q, path_xi)
         t0_d = self._check_t0(B, t0)
+        self._sched_next = None  # the loop's schedule is pose_scale_path
         b = self._stage(x0_q, x0_xi, us_init, weights=(Q, P, R))
+        spath = None if pose_scale_path is None else self._schedule_paths(B, pose_scale_path)
+        if spath is not None and b.wts is None:
+            b.wts = tuple(self._dev(a, a.shape) for a in self._own_weights(B))
         plant = self._check_plant(B, plant_J, plant_pend, per_sample=False)
         box = self._box(B, u_lb, u_ub)
         if noise is not None:
@@ -1591,7 +1707,7 @@ class BatchedTrackingILQR:
         try:
             # the plant survives the solves of the loop (tolg_set_plant): set once, detached behind it
             d_plant = self._use_plant(B, plant)
-            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box, al, obs, mu, maxviol))
+            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box, al, obs, mu, maxviol, spath))
             self._use_pt(B, None, b.wts)
             if al is not None:
                 self.set_al(*al)
@@ -1601,6 +1717,8 @@ class BatchedTrackingILQR:
                 res.max_violation, res.mu = torch.empty(B, steps, **f64), mu
             for t in range(steps):
                 self._set_ref_windows(B, pq, pxi, T, t0_d, t)
+                if spath is not None:
+                    self._set_pose_schedule(B, (spath[0], spath[1], t0_d, t))
                 if obs is not None and obs[3]:
                     self._set_obstacle_windows(B, obs[0], t0_d, t, obs[1], obs[2], kinds)
                 n = K0 if t == 0 else K

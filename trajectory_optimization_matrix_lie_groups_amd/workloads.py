@@ -232,6 +232,37 @@ def se3_weight_sweep(B, K, N=200, spread=3.0, seed=SEED):
     return prob, x0_q, x0_xi, us0, Qk[index], Pk[index], Rk[index], index, (Qk, Pk, Rk)
 
 
+def gate_knots(N, gates):
+    """The knots of `gates` gates spread evenly inside the horizon: round((g + 1) N / (gates + 1)), g = 0 .. gates-1."""
+    if not 1 <= gates < N:
+        raise ValueError("gates must be in 1..N-1")
+    k = np.rint((np.arange(gates) + 1.0) * N / (gates + 1.0)).astype(np.int64)
+    if len(np.unique(k)) != gates or k[0] < 1 or k[-1] > N - 1:
+        raise ValueError("%d gates do not fit %d knots" % (gates, N))
+    return k
+
+
+def se3_gates(B, N=200, gates=3, gate_gain=64.0, seed=SEED):
+    """Gates on se3_tracking's path: the pose is tracked loosely (pose weights a hundredth of se3_tracking's, Q = diag(0.25 x 3,
+    0.1 x 3, 1 x 6), P = 1.5 Q) except at `gates` gate knots, where a pose schedule multiplies the pose weights by gate_gain:
+    pass the gates tightly, track loosely between them.  The gates of member 0 sit at gate_knots(N, gates); those of the other
+    members are moved by up to a quarter of the gate spacing (at most two knots) either way, seeded, so that every trajectory
+    has its own schedule.  The reference passes through every gate: q_ref at a gate knot is the gate's pose.
+    Returns (prob, x0_q, x0_xi, us0, pose_scale [B, N+1, 6], knots [B, gates]): fit_batch(x0_q, x0_xi, us0,
+    pose_scale=pose_scale) on a solver for prob; pose_scale is 1 everywhere and gate_gain at the gate knots."""
+    base, x0_q, x0_xi, us0 = se3_tracking(B, N=N, seed=seed)
+    Q = np.diag([0.25, 0.25, 0.25, 0.1, 0.1, 0.1, 1, 1, 1, 1, 1, 1])
+    prob = TrackingProblem("se3", base.J, base.dt, Q, base.R, 1.5 * Q, base.q_ref, base.xi_ref)
+    k0 = gate_knots(N, gates)
+    jitter = min(2, (N // (gates + 1)) // 4)
+    rng = np.random.default_rng(seed + 5)
+    knots = k0[None, :] + rng.integers(-jitter, jitter + 1, size=(B, gates))
+    knots[0] = k0
+    pose_scale = np.ones((B, N + 1, 6))
+    pose_scale[np.arange(B)[:, None], knots] = float(gate_gain)
+    return prob, x0_q, x0_xi, us0, pose_scale, knots
+
+
 def se3_policy_eval(B, S, N=200, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=0.01, seed=SEED):
     """Monte-Carlo inputs for the closed loop of se3_tracking's workload (BatchedTrackingILQR.policy_rollout): S seeded
     perturbations per trajectory.  Returns (prob, x0_q, x0_xi, us0, dx0 [B, S, 12], noise [B, S, N, 6]); dx0 is Gaussian
