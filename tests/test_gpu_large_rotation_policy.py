@@ -1,7 +1,7 @@
 """Large-rotation and per-trajectory parity of the newer policy kernels, which tests/test_gpu_large_rotation.py does not reach:
-k_policy_rollout_est (its own Log and Exp sites, dyn_f, two chains in a quad), k_policy_rollout_lim (roll_step with the clamp
+k_policy_rollout_est (its own Log and Exp sites, dyn_f, two chains in a quad), k_policy_rollout under a box (roll_step with the clamp
 inside), pc_build_acl behind k_policy_covariance, k_policy_value and k_policy_covariance_est (closed-form so3_coef, so3_exp),
-pv_cost of the value kernel, and the forms of the first two and of k_mpc_advance_lim with a reference and / or weights per
+pv_cost of the value kernel, and the forms of the first two and of k_mpc_advance under a box with a reference and / or weights per
 trajectory, in both sample orders.  The inputs and their guards are tests/support.py's (large_policy_case, large_estimated_case,
 large_value_case), the guards themselves are asserted on the CPU restatements before the first launch, and
 tests/test_large_rotation_policy_cpu.py asserts them again with the oracle's gains, where no device is needed.

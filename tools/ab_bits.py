@@ -1,7 +1,9 @@
 """Do two builds of the library compute the same bits?  One sha256 per case over what a solve (xs_q, xs_xi, us, J_hist,
-alpha_hist, iters, status) or a closed-loop rollout (J, status, xs_q, xs_xi, us) returns, on small cases that between them
-run every rollout kernel: the fused launch, K3 alone, the one- and two-wave line-search stages of both searches, the
-statement-form LINEAR steps, the pendulum, a dense inertia, the closed loop with and without a plant.
+alpha_hist, iters, status), a closed-loop rollout (J, status, xs_q, xs_xi, us; under a box with clearance also n_sat, u_excess,
+clearance, clearance_knot) or a receding-horizon step (every tensor of mpc_advance's dict) returns, on small cases that between
+them run every rollout kernel: the fused launch, K3 alone, the one- and two-wave line-search stages of both searches, the
+statement-form LINEAR steps, the pendulum, a dense inertia, the closed loop and the receding-horizon step with and without a
+plant, free and under an actuator box (a case whose box moves no input fails: it would not have run the clamp).
 
 usage: python tools/ab_bits.py                    the cases on the library TOLG_HIP_LIB selects (default: the in-tree one)
        python tools/ab_bits.py LIB [LIB ...]      each LIB (a path, or `intree`) in a fresh child process under its own time
@@ -63,16 +65,62 @@ def cases():
         pd = TrackingProblem("se3", Jd, prob.dt, prob.Q, prob.R, prob.P, prob.q_ref, prob.xi_ref)
         return fit(pd, q, xi, us, ["ms"], line_search=True)
 
+    def solved(kind):
+        """The closed-loop cases' workload and solve: B = 9, S = 3 is 27 quads, so the last wavefront is partial and replays
+        the last sample"""
+        prob, q, xi, us, dx0, noise, plant_J = workloads.plant_mismatch(9, 3, kind=kind, N=20, rotate=True)
+        s = BatchedTrackingILQR(prob, 9)
+        r = s.fit_batch(q, xi, us, mode="ms", n_iterations=6, tol_grad_norm=0.0, tol_d_norm=0.0)
+        torch.cuda.synchronize()
+        return prob, s, r.xs_q.cpu().numpy(), r.us.cpu().numpy(), dx0, noise, plant_J
+
     def policy(kind):
         def run():
-            prob, q, xi, us, dx0, noise, plant_J = workloads.plant_mismatch(9, 3, kind=kind, N=20, rotate=True)
-            s = BatchedTrackingILQR(prob, 9)
-            s.fit_batch(q, xi, us, mode="ms", n_iterations=6, tol_grad_norm=0.0, tol_d_norm=0.0)
+            prob, s, xs_q, us, dx0, noise, plant_J = solved(kind)
             out = []
             for plant in (None, plant_J):
                 r = s.policy_rollout(dx0=dx0, noise=noise, trajectories=True, plant_J=plant)
                 torch.cuda.synchronize()
                 out += [r.J, r.status, r.xs_q, r.xs_xi, r.us]
+            return out
+        return run
+
+    def policy_limited(kind):
+        def run():
+            prob, s, xs_q, us, dx0, noise, plant_J = solved(kind)
+            lb, ub = us.min(axis=1), us.max(axis=1)  # the nominal input range: perturbed samples leave it somewhere
+            # K = 3 static spheres about the nominal position at the middle knot: one touches it from above, two stand off
+            off, rad = np.array([[-0.4, 2.0, 0.6], [1.5, 0.3, 0.0], [0.0, 0.0, 0.4]]), np.array([0.7, 0.5, 0.4])
+            sp = np.concatenate([xs_q[:, xs_q.shape[1] // 2, None, :3, 3] + off[None], np.broadcast_to(rad, (9, 3))[..., None]], axis=2)
+            s.set_al_obstacles(sp)
+            out = []
+            for plant in (None, plant_J):
+                r = s.policy_rollout(dx0=dx0, noise=noise, trajectories=True, plant_J=plant, u_lb=lb, u_ub=ub, clearance=True)
+                torch.cuda.synchronize()
+                if int(r.n_sat.sum()) == 0:
+                    raise RuntimeError("the box moved no input: the clamp did not run")
+                out += [r.J, r.status, r.xs_q, r.xs_xi, r.us, r.n_sat, r.u_excess, r.clearance, r.clearance_knot]
+            return out
+        return run
+
+    def advance(kind):
+        def run():
+            prob, s, xs_q, us, dx0, noise, plant_J = solved(kind)
+            # the middle half of the nominal input range: u*_0 of some trajectory is outside it
+            lo, hi = us.min(axis=1), us.max(axis=1)
+            lb, ub = lo + 0.25 * (hi - lo), hi - 0.25 * (hi - lo)
+            diag = np.array(np.broadcast_to(np.asarray(prob.J, float), (9, 6, 6)))
+            diag[:, range(3), range(3)] *= np.random.default_rng(2).uniform(0.8, 1.2, (9, 3))  # a diagonal plant per trajectory
+            out, moved = [], 0
+            for plant in (None, diag, plant_J[:, 0]):
+                for box in ({}, dict(u_lb=lb, u_ub=ub)):
+                    J_cl = torch.zeros(9, dtype=torch.float64, device=s.device)
+                    a = s.mpc_advance(noise[:, 0, 0], J_cl=J_cl, plant_J=plant, **box)
+                    torch.cuda.synchronize()
+                    moved += int(a["n_sat"].sum()) if box else 0
+                    out += [a[k] for k in sorted(a)]
+            if moved == 0:
+                raise RuntimeError("the box moved no input: the clamp did not run")
             return out
         return run
 
@@ -92,6 +140,10 @@ def cases():
                                                                 line_search=True)),
         ("se3 B9 N20 policy_rollout S3, model and dense plant", policy("se3")),
         ("drone B9 N20 policy_rollout S3, model and dense plant", policy("drone")),
+        ("se3 B9 N20 policy_rollout S3 under a box with clearance, model and dense plant", policy_limited("se3")),
+        ("drone B9 N20 policy_rollout S3 under a box with clearance, model and dense plant", policy_limited("drone")),
+        ("se3 B9 N20 mpc_advance free and under a box: model, diagonal and dense plant", advance("se3")),
+        ("drone B9 N20 mpc_advance free and under a box: model, diagonal and dense plant", advance("drone")),
     ]
 
 

@@ -1,4 +1,5 @@
-"""Compare the device code of two builds of the library symbol by symbol: python tools/symbol_diff.py A.so B.so [substring ...]
+"""Compare the device code of two builds of the library symbol by symbol:
+    python tools/symbol_diff.py [--rename PATTERN REPLACEMENT ...] A.so B.so [substring ...]
 
 Per symbol one of
   identical          the same instructions with the same operands in the same order (addresses stripped)
@@ -6,7 +7,12 @@ Per symbol one of
                      of independent instructions moved, the operations did not
   different          anything else (a symbol only one side has included)
 then the three counts.  Exit status 1 if a symbol is different.  With substrings: only the symbols whose demangled name
-holds one of them."""
+holds one of them.
+
+Symbols pair by name, so one that B.so spells otherwise shows as two different ones.  --rename (any number of them, applied
+in order) rewrites the demangled names of A.so with re.sub before the pairing:
+    --rename 'k_policy_rollout_lim<(\\d+, \\d+, \\d+, \\d+)' 'k_policy_rollout<\\1, tolg::PolicyLim'
+pairs k_policy_rollout_lim<4, 0, 0, 0> of A.so with k_policy_rollout<4, 0, 0, 0, tolg::PolicyLim> of B.so."""
 import os
 import re
 import subprocess
@@ -42,6 +48,15 @@ def symbols(lib):
     return out
 
 
+def by_name(syms):
+    """{mangled symbol: instructions} -> {demangled name: instructions}.  The name stops ahead of the argument list where that
+    still tells the symbols of the library apart, and keeps it where two of them share the rest."""
+    full = subprocess.check_output(["c++filt"], input="\n".join(syms).encode()).decode().splitlines() if syms else []
+    short = [f.split("(")[0] for f in full]
+    shared = {n for n, k in Counter(short).items() if k > 1}
+    return {(f if s in shared else s): syms[sym] for sym, f, s in zip(syms, full, short)}
+
+
 def classify(a, b):
     if a == b:
         return "identical"
@@ -53,18 +68,26 @@ def classify(a, b):
     return "same instructions" if norm(a) == norm(b) else "different"
 
 
+def pair(A, B, renames=()):
+    """A, B: {name: instructions}; renames: (pattern, replacement) pairs applied in order to the names of A.
+    -> [(name, class, instructions of A or None, of B or None)] sorted by name, a renamed symbol under its name in B."""
+    for pat, repl in renames:
+        A = {re.sub(pat, repl, n): ins for n, ins in A.items()}
+    return [(n, classify(A.get(n), B.get(n)), A.get(n), B.get(n)) for n in sorted(set(A) | set(B))]
+
+
 def main():
-    A, B, pats = symbols(sys.argv[1]), symbols(sys.argv[2]), sys.argv[3:]
-    names = sorted(set(A) | set(B))
-    dem = subprocess.check_output(["c++filt"], input="\n".join(names).encode()).decode().splitlines()
+    args, renames = sys.argv[1:], []
+    while args and args[0] == "--rename":
+        renames.append((args[1], args[2]))
+        args = args[3:]
+    A, B, pats = by_name(symbols(args[0])), by_name(symbols(args[1])), args[2:]
     counts = Counter()
-    for sym, name in zip(names, dem):
-        name = name.split("(")[0]
+    for name, c, a, b in pair(A, B, renames):
         if pats and not any(p in name for p in pats):
             continue
-        c = classify(A.get(sym), B.get(sym))
         counts[c] += 1
-        print("%-18s %6d %6d  %s" % (c, len(A.get(sym) or ()), len(B.get(sym) or ()), name))
+        print("%-18s %6d %6d  %s" % (c, len(a or ()), len(b or ()), name))
     print("symbols %d: identical %d, same instructions %d, different %d"
           % (sum(counts.values()), counts["identical"], counts["same instructions"], counts["different"]))
     sys.exit(1 if counts["different"] else 0)

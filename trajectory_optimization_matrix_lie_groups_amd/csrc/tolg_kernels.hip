@@ -710,9 +710,18 @@ TOLG_DEV PlantC plant_step(const PlantC& V) {
   }
   return W;
 }
-// the plant of a closed-loop kernel: its trailing argument, none for PL_NONE
-TOLG_DEV PlantArg plant_arg_of() { return PlantArg{nullptr, 0, 0}; }
-TOLG_DEV PlantArg plant_arg_of(const PlantArg& a) { return a; }
+// The trailing arguments of a closed-loop kernel, `PA... pl`: its actuator limit if it has one (PolicyLim, MpcLim), then its
+// plant unless PL_NONE (PlantArg) -- none, either or both.  pack_arg<T>(pl...) is the one of type T, a value-initialised T
+// where the pack holds none; pack_has<T, PA...> says which.
+template <class T, class... PA>
+constexpr bool pack_has = (std::is_same_v<T, PA> || ...);
+template <class T>
+TOLG_DEV T pack_arg() { return T{}; }
+template <class T, class A, class... R>
+TOLG_DEV T pack_arg(const A& a, const R&... r) {
+  if constexpr (std::is_same_v<T, A>) return a;
+  else return pack_arg<T>(r...);
+}
 // The diagonal form's view for the pendulum: the model's constants, by reference, with the plant row's pend_k.  (The diagonal
 // form steps with the pinned DynK; what else it reads of the constants must be the model's very loads, so that the compiler
 // lays out and fuses the step as it does the model's: a view of its own changed the fused multiply-adds of the step.)
@@ -2380,7 +2389,8 @@ struct RollProbe { double e[12], du[M]; State Fn; };
 struct RollPre { bool have_d = false, have_x = false; double d[12]; State Sx; };
 // limit(un): what the actuator makes of the commanded input, between the control and the twist half of the dynamics -- the
 // dynamics step on it, the caller gets it back in un_out.  The default leaves the command (no code: every kernel that does not
-// pass one keeps its instructions); tolg_policy_rollout_limited's kernel clamps to its box here.
+// pass one keeps its instructions, and so does k_policy_rollout without a box, whose limit is empty); under a box
+// (tolg_policy_rollout_limited) k_policy_rollout clamps here.
 struct RollNoLimit {
   template <int M> TOLG_DEV void operator()(double (&)[M]) const {}
 };
@@ -3185,17 +3195,71 @@ __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nsl
 // wave; traj_fast = 1 is K3's order (c = s B + b).  Every value a quad computes is its own: the series gates are wave-wide
 // only in which tiers run (tolg_lie.h), so a sample's bits do not depend on S, on the order or on its neighbours.
 // Generic constants pointer: cost and dynamics on one chain is the construct the note at DConsts warns about.
-// PL: the plant the samples are stepped with (tolg_set_plant, the one trailing argument pl: a PlantArg), PL_NONE the model
-// (no trailing argument: the kernel of the tables without a plant, its code unchanged by the plant forms).  The cost is the
-// model's in every form.
+// PL: the plant the samples are stepped with (tolg_set_plant, the trailing argument of type PlantArg), PL_NONE the model (no
+// such argument).  The cost is the model's in every form.
+// The trailing arguments pl (pack_arg) select the form: none is the kernel of the tables without a plant, and neither the
+// plant forms nor the limited ones change its name, its arguments or its code.  With a PolicyLim in front (LIM) the same chain
+// runs under an actuator box and reports the clearance from the handle's keep-out spheres (tolg_policy_rollout_limited), two
+// additions that stay inside the quad:
+//  - the box [lb, ub] of trajectory b, 2 M values in registers from ahead of the knot loop (a null bound: -inf / +inf), applied
+//    inside the step (roll_step's limit): u^ = u~ < lb ? lb : (u~ > ub ? ub : u~), a NaN command stays NaN.  The four lanes of
+//    a quad hold the same u~ and count the same: n_sat the pairs (i, a) with u~ outside the box, excess the largest distance
+//    by which one left it (fmax: a NaN distance is passed over);
+//  - with L.clearance, min over knots i <= N and slots k of the clearance of slot k's kind (the keep-out sphere:
+//    |t^_i - c_ik| - r_ik; include/tolg.h has the table) on the state the step starts from, geometry
+//    read as obs_terms reads it (field 4k + c of knot i at (i obs_stride + (4k + c) Bp + b): one address per wave in the
+//    default sample order), strict < with knots and spheres ascending: the first knot that attains the minimum.  It stands
+//    behind the step in the source and depends on the state alone, not on the gains or the control.
+// The geometry pointer, K and the knot stride come from the constants at run time (the host refuses L.clearance with no
+// spheres attached): one limited kernel per model and plant form, in every table.
+struct PolicyLim {
+  const double *lb, *ub;  // [B][M], or both null
+  int* n_sat;             // [B][S] outputs, each may be null
+  double* u_excess;
+  double* clear;
+  int* clear_knot;
+  int clearance;          // clear or clear_knot asked for
+};
+TOLG_DEV void clear_knot_min(const Consts& C, size_t Bp, int b, int i, const V3& t, double& cmin, int& cknot) {
+  const double* geo = C.obs + b + (size_t)i * C.obs_stride;
+  const int K = C.obsK;
+  const unsigned kinds = C.obs_kinds;
+  // four slots at a time, their sixteen loads in flight together (one slot per trip paid a load latency each: 1.8 us per
+  // knot at K = 8); a trip past K replays slot K - 1 with its own kind, whose clearance is not below itself
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    double g[4][4];
+    unsigned kd[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int k = k0 + j < K ? k0 + j : K - 1;
+      const double* o = geo + (size_t)(4 * k) * Bp;
+      g[j][0] = o[0]; g[j][1] = o[Bp]; g[j][2] = o[2 * Bp]; g[j][3] = o[3 * Bp];
+      kd[j] = obs_kind(kinds, k);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      double c;
+      if (kd[j] == TOLG_OBS_HALF_SPACE) c = g[j][3] - dot(v3(g[j][0], g[j][1], g[j][2]), t);
+      else {
+        V3 d = t - v3(g[j][0], g[j][1], g[j][2]);
+        if (kd[j] == TOLG_OBS_COLUMN_Z) d.z = 0.0;
+        c = sqrt(dot(d, d)) - g[j][3];
+        if (kd[j] == TOLG_OBS_KEEP_IN) c = -c;
+      }
+      if (c < cmin) { cmin = c; cknot = i; }
+    }
+  }
+}
 template <int M, int PK, int PT, int PL = PL_NONE, class... PA>
 __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj_fast, const double* __restrict__ dx0,
                                                        const double* __restrict__ noise, double* __restrict__ Jout,
                                                        int* __restrict__ status, double* __restrict__ xs_q,
                                                        double* __restrict__ xs_xi, double* __restrict__ us, PA... pl) {
+  constexpr bool LIM = pack_has<PolicyLim, PA...>;
   Stamps<8> ST;
   const Consts& C = *P.c;
-  const PlantArg pa = plant_arg_of(pl...);
+  const PlantArg pa = pack_arg<PlantArg>(pl...);
+  const PolicyLim L = pack_arg<PolicyLim>(pl...);
   const size_t n = (size_t)P.B * (size_t)S;
   size_t c = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
   const int q = threadIdx.x & 3;
@@ -3211,6 +3275,30 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
   const size_t pr = PL == PL_NONE ? 0 : plant_row(pa, b, bs);
   const DynK DK = plant_dynk<PL>(C, pa, pr);
   const PlantC V = plant_c<PL>(C, pa, pr);  // what the steps read in place of the model's constants (PL_NONE: nothing)
+  double lb[M], ub[M];
+  if constexpr (LIM) {
+#pragma unroll
+    for (int a = 0; a < M; a++) {
+      lb[a] = L.lb ? L.lb[(size_t)b * M + a] : -INFINITY;
+      ub[a] = L.ub ? L.ub[(size_t)b * M + a] : INFINITY;
+    }
+  }
+  int nsat = 0, cknot = 0;
+  double excess = 0.0, cmin = INFINITY;
+  auto limit = [&](double (&u)[M]) {  // (not LIM: no code, roll_step's default)
+    if constexpr (LIM) {
+#pragma unroll
+      for (int a = 0; a < M; a++) {
+        const double uc = u[a];
+        const bool lo = uc < lb[a], hi = uc > ub[a];
+        nsat += (lo || hi) ? 1 : 0;
+        const double v = lo ? lb[a] : (hi ? ub[a] : uc);
+        // |u^ - u~| is lb - u~ below the box, u~ - ub above it and 0 inside: max(lb - u~, u~ - ub, 0) in one difference
+        excess = fmax(excess, fabs(v - uc));
+        u[a] = v;
+      }
+    }
+  };
   State Sa = roll_load_state(P, 0, vb, sB), Sb = Sa;
   State Sn = Sa;  // x^_0 = x*_0 (+) dx0: pose x*_0 Exp(dx0[0:6]), twist xi*_0 + dx0[6:12]
   if (dx0) {
@@ -3227,7 +3315,9 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
     const auto& CS = plant_or_model<PL, PK>(C, Vi);
     const State Nx = roll_step<M, false, true, PK, false>(P, CS, DK, i, b, q, false, vb, sB, 0.0, Sa, Sn, un,
                                                            [&](RollIn<M>& R) { roll_load<M, true>(P, i, b, q, vb, sB, R); },
-                                                           nullptr, ST);
+                                                           nullptr, ST, RollPre(), limit);
+    if constexpr (LIM)
+      if (L.clearance) clear_knot_min(C, (size_t)P.Bp, b, i, Sn.X.t, cmin, cknot);
     J += knot_cost<M, true, PT>(P, C, i, b, Sn, un, false);
     if (writer) {
       state_to_m16(Sn, xs_q, xs_xi, bs * (size_t)(N + 1) + i);
@@ -3247,11 +3337,19 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
   }
 #pragma unroll
   for (int a = 0; a < M; a++) un[a] = 0.0;
+  if constexpr (LIM)
+    if (L.clearance) clear_knot_min(C, (size_t)P.Bp, b, N, Sn.X.t, cmin, cknot);
   J += knot_cost<M, true, PT>(P, C, N, b, Sn, un, true);
   if (writer) {
     state_to_m16(Sn, xs_q, xs_xi, bs * (size_t)(N + 1) + N);
     if (Jout) Jout[bs] = J;
     if (status) status[bs] = isfinite(J) ? TOLG_ST_OK : TOLG_ST_NONFINITE;
+    if constexpr (LIM) {
+      if (L.n_sat) L.n_sat[bs] = nsat;
+      if (L.u_excess) L.u_excess[bs] = excess;
+      if (L.clear) L.clear[bs] = cmin;
+      if (L.clear_knot) L.clear_knot[bs] = cknot;
+    }
   }
 }
 
@@ -3377,157 +3475,20 @@ __global__ __launch_bounds__(64) void k_policy_rollout_est(Params P, int S, int 
   }
 }
 
-// tolg_policy_rollout_limited: k_policy_rollout under an actuator box, with the clearance from the handle's keep-out spheres.
-// The same chain (sample order, start, noise, cost, stores), with two additions that stay inside the quad:
-//  - the box [lb, ub] of trajectory b, 2 M values in registers from ahead of the knot loop (a null bound: -inf / +inf), applied
-//    inside the step (roll_step's limit): u^ = u~ < lb ? lb : (u~ > ub ? ub : u~), a NaN command stays NaN.  The four lanes of
-//    a quad hold the same u~ and count the same: n_sat the pairs (i, a) with u~ outside the box, excess the largest distance
-//    by which one left it (fmax: a NaN distance is passed over);
-//  - with L.clearance, min over knots i <= N and slots k of the clearance of slot k's kind (the keep-out sphere:
-//    |t^_i - c_ik| - r_ik; include/tolg.h has the table) on the state the step starts from, geometry
-//    read as obs_terms reads it (field 4k + c of knot i at (i obs_stride + (4k + c) Bp + b): one address per wave in the
-//    default sample order), strict < with knots and spheres ascending: the first knot that attains the minimum.  It stands
-//    behind the step in the source and depends on the state alone, not on the gains or the control.
-// The geometry pointer, K and the knot stride come from the constants at run time (the host refuses L.clearance with no
-// spheres attached): one kernel per model and plant form, in every table.
-struct PolicyLim {
-  const double *lb, *ub;  // [B][M], or both null
-  int* n_sat;             // [B][S] outputs, each may be null
-  double* u_excess;
-  double* clear;
-  int* clear_knot;
-  int clearance;          // clear or clear_knot asked for
-};
-TOLG_DEV void clear_knot_min(const Consts& C, size_t Bp, int b, int i, const V3& t, double& cmin, int& cknot) {
-  const double* geo = C.obs + b + (size_t)i * C.obs_stride;
-  const int K = C.obsK;
-  const unsigned kinds = C.obs_kinds;
-  // four slots at a time, their sixteen loads in flight together (one slot per trip paid a load latency each: 1.8 us per
-  // knot at K = 8); a trip past K replays slot K - 1 with its own kind, whose clearance is not below itself
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    double g[4][4];
-    unsigned kd[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int k = k0 + j < K ? k0 + j : K - 1;
-      const double* o = geo + (size_t)(4 * k) * Bp;
-      g[j][0] = o[0]; g[j][1] = o[Bp]; g[j][2] = o[2 * Bp]; g[j][3] = o[3 * Bp];
-      kd[j] = obs_kind(kinds, k);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      double c;
-      if (kd[j] == TOLG_OBS_HALF_SPACE) c = g[j][3] - dot(v3(g[j][0], g[j][1], g[j][2]), t);
-      else {
-        V3 d = t - v3(g[j][0], g[j][1], g[j][2]);
-        if (kd[j] == TOLG_OBS_COLUMN_Z) d.z = 0.0;
-        c = sqrt(dot(d, d)) - g[j][3];
-        if (kd[j] == TOLG_OBS_KEEP_IN) c = -c;
-      }
-      if (c < cmin) { cmin = c; cknot = i; }
-    }
-  }
-}
-template <int M, int PK, int PT, int PL = PL_NONE, class... PA>
-__global__ __launch_bounds__(64) void k_policy_rollout_lim(Params P, int S, int traj_fast, const double* __restrict__ dx0,
-                                                           const double* __restrict__ noise, double* __restrict__ Jout,
-                                                           int* __restrict__ status, double* __restrict__ xs_q,
-                                                           double* __restrict__ xs_xi, double* __restrict__ us, PolicyLim L,
-                                                           PA... pl) {
-  Stamps<8> ST;
-  const Consts& C = *P.c;
-  const PlantArg pa = plant_arg_of(pl...);
-  const size_t n = (size_t)P.B * (size_t)S;
-  size_t c = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-  const int q = threadIdx.x & 3;
-  // quads past the last sample replay it (DPP needs whole quads alive) and store nothing
-  const bool live = c < n;
-  if (!live) c = n - 1;
-  const int b = traj_fast ? (int)(c % (size_t)P.B) : (int)(c / (size_t)S);
-  const size_t s = traj_fast ? c / (size_t)P.B : c % (size_t)S;
-  const size_t bs = (size_t)b * S + s;  // row of the [B][S] outputs
-  const bool writer = live && q == 0;
-  const int N = P.N;
-  const unsigned sB = (unsigned)P.Bp * 8u, vb = (unsigned)b * 8u;
-  const size_t pr = PL == PL_NONE ? 0 : plant_row(pa, b, bs);
-  const DynK DK = plant_dynk<PL>(C, pa, pr);
-  const PlantC V = plant_c<PL>(C, pa, pr);
-  double lb[M], ub[M];
-#pragma unroll
-  for (int a = 0; a < M; a++) {
-    lb[a] = L.lb ? L.lb[(size_t)b * M + a] : -INFINITY;
-    ub[a] = L.ub ? L.ub[(size_t)b * M + a] : INFINITY;
-  }
-  int nsat = 0, cknot = 0;
-  double excess = 0.0, cmin = INFINITY;
-  auto limit = [&](double (&u)[M]) {
-#pragma unroll
-    for (int a = 0; a < M; a++) {
-      const double uc = u[a];
-      const bool lo = uc < lb[a], hi = uc > ub[a];
-      nsat += (lo || hi) ? 1 : 0;
-      const double v = lo ? lb[a] : (hi ? ub[a] : uc);
-      // |u^ - u~| is lb - u~ below the box, u~ - ub above it and 0 inside: max(lb - u~, u~ - ub, 0) in one difference
-      excess = fmax(excess, fabs(v - uc));
-      u[a] = v;
-    }
-  };
-  State Sa = roll_load_state(P, 0, vb, sB), Sb = Sa;
-  State Sn = Sa;  // x^_0 = x*_0 (+) dx0: pose x*_0 Exp(dx0[0:6]), twist xi*_0 + dx0[6:12]
-  if (dx0) {
-    const double* d = dx0 + 12 * bs;
-    Sn.X = se3_project(se3_compose(Sa.X, se3_exp(v3(d[0], d[1], d[2]), v3(d[3], d[4], d[5]))));
-    Sn.w = Sa.w + v3(d[6], d[7], d[8]);
-    Sn.v = Sa.v + v3(d[9], d[10], d[11]);
-  }
-  double J = 0.0, un[M];
-  for (int i = 0; i < N; i++) {
-    if (i + 1 < N) Sb = roll_load_state(P, i + 1, vb, sB);
-    __builtin_amdgcn_sched_barrier(0);
-    const PlantC Vi = plant_step<PL>(V);
-    const auto& CS = plant_or_model<PL, PK>(C, Vi);
-    const State Nx = roll_step<M, false, true, PK, false>(P, CS, DK, i, b, q, false, vb, sB, 0.0, Sa, Sn, un,
-                                                           [&](RollIn<M>& R) { roll_load<M, true>(P, i, b, q, vb, sB, R); },
-                                                           nullptr, ST, RollPre(), limit);
-    if (L.clearance) clear_knot_min(C, (size_t)P.Bp, b, i, Sn.X.t, cmin, cknot);
-    J += knot_cost<M, true, PT>(P, C, i, b, Sn, un, false);
-    if (writer) {
-      state_to_m16(Sn, xs_q, xs_xi, bs * (size_t)(N + 1) + i);
-      if (us) {
-        double* u = us + (bs * (size_t)N + i) * M;
-#pragma unroll
-        for (int a = 0; a < M; a++) u[a] = un[a];
-      }
-    }
-    Sn = Nx;
-    if (noise) {
-      const double* w = noise + (bs * (size_t)N + i) * 6;
-      Sn.w = Sn.w + v3(w[0], w[1], w[2]);
-      Sn.v = Sn.v + v3(w[3], w[4], w[5]);
-    }
-    Sa = Sb;
-  }
-#pragma unroll
-  for (int a = 0; a < M; a++) un[a] = 0.0;
-  if (L.clearance) clear_knot_min(C, (size_t)P.Bp, b, N, Sn.X.t, cmin, cknot);
-  J += knot_cost<M, true, PT>(P, C, N, b, Sn, un, true);
-  if (writer) {
-    state_to_m16(Sn, xs_q, xs_xi, bs * (size_t)(N + 1) + N);
-    if (Jout) Jout[bs] = J;
-    if (status) status[bs] = isfinite(J) ? TOLG_ST_OK : TOLG_ST_NONFINITE;
-    if (L.n_sat) L.n_sat[bs] = nsat;
-    if (L.u_excess) L.u_excess[bs] = excess;
-    if (L.clear) L.clear[bs] = cmin;
-    if (L.clear_knot) L.clear_knot[bs] = cknot;
-  }
-}
-
 // One receding-horizon step on the held policy (tolg_mpc_advance), the two ends of the warm start: one thread per (end,
 // trajectory b), b fastest.  End 0 steps the plant, x_{t+1} = f(x*_0, u*_0) with the exact dynamics (the dyn_f_k step of the
 // rollouts), adds the twist disturbance and the stage cost l(x*_0, u*_0), and writes xs_warm[0] = x_{t+1}; end 1 propagates
 // the tail, xs_warm[N] = f(x*_N, u*_{N-1}).  k_mpc_shift writes the rest.  Reads the held policy only: calling it again gives
 // the same bits.  No LDS, no cross-lane operation.  PL: end 0 steps plant row b (tolg_set_plant, S_plant = 1) instead of the
 // model; end 1, the tail of the warm start, is the model's prediction in every form.
+// The trailing arguments pl (pack_arg) select the form, as k_policy_rollout's do.  With an MpcLim in front
+// (tolg_mpc_advance_limited) the applied input is clamped to trajectory b's box [lb, ub] ([B][M]) at end 0 -- the plant (or the
+// model) steps on clamp(u*_0), a NaN input stays NaN, u_applied and the stage cost take it, n_sat[b] counts the inputs the box
+// moved.  End 1 is untouched by the box: the model's prediction with the unclamped u*_{N-1}.
+struct MpcLim {
+  const double *lb, *ub;  // [B][M]
+  int* n_sat;             // [B], may be null
+};
 template <int M, int PK, int PT, int PL = PL_NONE, class... PA>
 __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __restrict__ w, double* __restrict__ x_next_q,
                                                      double* __restrict__ x_next_xi, double* __restrict__ u_applied,
@@ -3542,11 +3503,25 @@ __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __r
   double u[M];
 #pragma unroll
   for (int a = 0; a < M; a++) u[a] = P.cur_u[UIDX(a, i == 0 ? 0 : N - 1, b)];
+  if constexpr (pack_has<MpcLim, PA...>) {
+    if (i == 0) {
+      const MpcLim L = pack_arg<MpcLim>(pl...);
+      int ns = 0;
+#pragma unroll
+      for (int a = 0; a < M; a++) {
+        const double uc = u[a], l = L.lb[(size_t)b * M + a], h = L.ub[(size_t)b * M + a];
+        const bool lo = uc < l, hi = uc > h;
+        ns += (lo || hi) ? 1 : 0;
+        u[a] = lo ? l : (hi ? h : uc);
+      }
+      if (L.n_sat) L.n_sat[b] = ns;
+    }
+  }
   State S;
   if constexpr (PL == PL_NONE) {
     S = dyn_f_k<M, Consts, PK>(DK, C, Sx, u);
   } else if (i == 0) {
-    const PlantArg pa = plant_arg_of(pl...);
+    const PlantArg pa = pack_arg<PlantArg>(pl...);
     const PlantC V = plant_c<PL>(C, pa, (size_t)b);
     const auto& CS = plant_or_model<PL, PK>(C, V);
     S = dyn_f_k<M, std::decay_t<decltype(CS)>, PK>(plant_dynk<PL>(C, pa, (size_t)b), CS, Sx, u);
@@ -3560,66 +3535,6 @@ __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __r
       S.v = S.v + v3(d[3], d[4], d[5]);
     }
     // (both ends written out, not state_to_m16: the helper compiles to other code in this kernel)
-    if (x_next_q) pose_to_m16(S.X, x_next_q + 16 * (size_t)b);
-    if (x_next_xi) { double* x = x_next_xi + 6 * (size_t)b; x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z; }
-    if (u_applied)
-#pragma unroll
-      for (int a = 0; a < M; a++) u_applied[(size_t)b * M + a] = u[a];
-    if (J_cl) J_cl[b] += knot_cost<M, false, PT>(P, C, 0, b, Sx, u, false);
-  }
-  const size_t k = (size_t)b * (N + 1) + i;
-  pose_to_m16(S.X, xs_q + 16 * k);
-  double* x = xs_xi + 6 * k;
-  x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z;
-}
-
-// tolg_mpc_advance_limited: k_mpc_advance with the applied input clamped to trajectory b's box [lb, ub] ([B][M]) at end 0 --
-// the plant (or the model) steps on clamp(u*_0), u_applied and the stage cost take it, n_sat[b] counts the inputs the box
-// moved.  End 1, the tail of the warm start, is k_mpc_advance's: the model's prediction with the unclamped u*_{N-1}.
-template <int M, int PK, int PT, int PL = PL_NONE, class... PA>
-__global__ __launch_bounds__(256) void k_mpc_advance_lim(Params P, const double* __restrict__ w, double* __restrict__ x_next_q,
-                                                         double* __restrict__ x_next_xi, double* __restrict__ u_applied,
-                                                         double* __restrict__ xs_q, double* __restrict__ xs_xi,
-                                                         double* __restrict__ J_cl, const double* __restrict__ lb,
-                                                         const double* __restrict__ ub, int* __restrict__ n_sat, PA... pl) {
-  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= 2 * (size_t)P.B) return;
-  const int N = P.N, b = (int)(g % P.B), i = g < (size_t)P.B ? 0 : N;
-  const Consts& C = *P.c;
-  const DynK DK = dynk_load(C);
-  const State Sx = load_state(P, P.cur, i, b);
-  double u[M];
-#pragma unroll
-  for (int a = 0; a < M; a++) u[a] = P.cur_u[UIDX(a, i == 0 ? 0 : N - 1, b)];
-  if (i == 0) {
-    int ns = 0;
-#pragma unroll
-    for (int a = 0; a < M; a++) {
-      const double uc = u[a], l = lb[(size_t)b * M + a], h = ub[(size_t)b * M + a];
-      const bool lo = uc < l, hi = uc > h;
-      ns += (lo || hi) ? 1 : 0;
-      u[a] = lo ? l : (hi ? h : uc);
-    }
-    if (n_sat) n_sat[b] = ns;
-  }
-  // (the rest as k_mpc_advance has it, statement for statement: the tail is to keep that kernel's bits)
-  State S;
-  if constexpr (PL == PL_NONE) {
-    S = dyn_f_k<M, Consts, PK>(DK, C, Sx, u);
-  } else if (i == 0) {
-    const PlantArg pa = plant_arg_of(pl...);
-    const PlantC V = plant_c<PL>(C, pa, (size_t)b);
-    const auto& CS = plant_or_model<PL, PK>(C, V);
-    S = dyn_f_k<M, std::decay_t<decltype(CS)>, PK>(plant_dynk<PL>(C, pa, (size_t)b), CS, Sx, u);
-  } else {
-    S = dyn_f_k<M, Consts, PK>(DK, C, Sx, u);
-  }
-  if (i == 0) {
-    if (w) {
-      const double* d = w + 6 * (size_t)b;
-      S.w = S.w + v3(d[0], d[1], d[2]);
-      S.v = S.v + v3(d[3], d[4], d[5]);
-    }
     if (x_next_q) pose_to_m16(S.X, x_next_q + 16 * (size_t)b);
     if (x_next_xi) { double* x = x_next_xi + 6 * (size_t)b; x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z; }
     if (u_applied)
@@ -5210,9 +5125,16 @@ using namespace tolg;
 // all of them.  PT_OBS: the kernels that evaluate costs (K1, the fused launch, k_rollout_eval_t, k_ls_eval, k_ls_eval_affine)
 // add the augmented-Lagrangian terms of trajectory b's keep-out spheres (tolg_set_al_obstacles, tolg_set_al_obstacles_moving);
 // every other entry of the four tables with PT_OBS is the entry of the table without it.  The plant (tolg_set_plant) selects
-// no table: the two closed-loop entries that step it are in every table.
+// no table: the closed-loop entries that step it (ClosedLoop) are in every table.
 typedef void (*SearchKernel)(Params, int, int, int);
 typedef void (*SearchRollout)(Params, int, int, int, int);
+// a closed-loop kernel with the arguments A: stepping the model, and stepping a plant (tolg_set_plant) in the form
+// [TOLG_PLANT_DIAG / TOLG_PLANT_DENSE], the PlantArg appended
+template <class... A>
+struct ClosedLoop {
+  void (*model)(A...);
+  void (*plant[2])(A..., PlantArg);
+};
 struct KernelTable {
   void (*init)(Params, const double*, const double*, const double*, int);  // k_init
   void (*init_warm)(Params, const double*, const double*, const double*, const double*, const double*);  // k_init_warm
@@ -5226,19 +5148,12 @@ struct KernelTable {
   void (*ec_ring[2])(Params);        // expected change, ring form [STORE]
   void (*ec_stmt[2])(Params);        //                  statement form [REDO]
   void (*affine_commit)(Params, int, int);
-  void (*policy_rollout)(Params, int, int, const double*, const double*, double*, int*, double*, double*, double*);  // tolg_policy_rollout
-  void (*mpc_advance)(Params, const double*, double*, double*, double*, double*, double*, double*);  // tolg_mpc_advance (+ k_mpc_shift)
-  // ... the same two with a plant (tolg_set_plant), [TOLG_PLANT_DIAG / TOLG_PLANT_DENSE]
-  void (*policy_rollout_plant[2])(Params, int, int, const double*, const double*, double*, int*, double*, double*, double*, PlantArg);
-  void (*mpc_advance_plant[2])(Params, const double*, double*, double*, double*, double*, double*, double*, PlantArg);
-  // ... and the four under an actuator box (tolg_policy_rollout_limited, tolg_mpc_advance_limited)
-  void (*policy_rollout_lim)(Params, int, int, const double*, const double*, double*, int*, double*, double*, double*, PolicyLim);
-  void (*policy_rollout_lim_plant[2])(Params, int, int, const double*, const double*, double*, int*, double*, double*, double*,
-                                      PolicyLim, PlantArg);
-  void (*mpc_advance_lim)(Params, const double*, double*, double*, double*, double*, double*, double*, const double*, const double*,
-                          int*);
-  void (*mpc_advance_lim_plant[2])(Params, const double*, double*, double*, double*, double*, double*, double*, const double*,
-                                   const double*, int*, PlantArg);
+  // k_policy_rollout (tolg_policy_rollout) and k_mpc_advance (tolg_mpc_advance, behind k_mpc_shift), free and under an
+  // actuator box (tolg_policy_rollout_limited, tolg_mpc_advance_limited), each on the model and on a plant
+  ClosedLoop<Params, int, int, const double*, const double*, double*, int*, double*, double*, double*> policy_rollout;
+  ClosedLoop<Params, int, int, const double*, const double*, double*, int*, double*, double*, double*, PolicyLim> policy_rollout_lim;
+  ClosedLoop<Params, const double*, double*, double*, double*, double*, double*, double*> mpc_advance;
+  ClosedLoop<Params, const double*, double*, double*, double*, double*, double*, double*, MpcLim> mpc_advance_lim;
   void (*policy_covariance)(Params, const double*, const double*, double*, double*, double*, double*);  // tolg_policy_covariance
   void (*policy_value)(Params, const double*, const double*, double*, double*, double*, double*, double*);  // tolg_policy_value
   // output feedback: tolg_policy_covariance_estimated, tolg_policy_rollout_estimated
@@ -5306,20 +5221,19 @@ static KernelTable kernel_table(int lds_per_block) {
   t.ec_stmt[0] = k_expected_change<M, PK, false, PTW>;
   t.ec_stmt[1] = k_expected_change<M, PK, true, PTW>;
   t.affine_commit = k_affine_commit<M>;
-  // (the held policy's rollouts report the tracking cost: the PT_OBS tables share the kernels of the table without it)
-  t.policy_rollout = k_policy_rollout<M, PK, PT & ~PT_OBS>;
-  t.mpc_advance = k_mpc_advance<M, PK, PT & ~PT_OBS>;
-  t.policy_rollout_plant[TOLG_PLANT_DIAG] = k_policy_rollout<M, PK, PT & ~PT_OBS, PL_DIAG, PlantArg>;
-  t.policy_rollout_plant[TOLG_PLANT_DENSE] = k_policy_rollout<M, PK, PT & ~PT_OBS, PL_DENSE, PlantArg>;
-  t.mpc_advance_plant[TOLG_PLANT_DIAG] = k_mpc_advance<M, PK, PT & ~PT_OBS, PL_DIAG, PlantArg>;
-  t.mpc_advance_plant[TOLG_PLANT_DENSE] = k_mpc_advance<M, PK, PT & ~PT_OBS, PL_DENSE, PlantArg>;
-  // (the limited forms likewise: the clearance reads the geometry through the constants, whatever the table)
-  t.policy_rollout_lim = k_policy_rollout_lim<M, PK, PT & ~PT_OBS>;
-  t.policy_rollout_lim_plant[TOLG_PLANT_DIAG] = k_policy_rollout_lim<M, PK, PT & ~PT_OBS, PL_DIAG, PlantArg>;
-  t.policy_rollout_lim_plant[TOLG_PLANT_DENSE] = k_policy_rollout_lim<M, PK, PT & ~PT_OBS, PL_DENSE, PlantArg>;
-  t.mpc_advance_lim = k_mpc_advance_lim<M, PK, PT & ~PT_OBS>;
-  t.mpc_advance_lim_plant[TOLG_PLANT_DIAG] = k_mpc_advance_lim<M, PK, PT & ~PT_OBS, PL_DIAG, PlantArg>;
-  t.mpc_advance_lim_plant[TOLG_PLANT_DENSE] = k_mpc_advance_lim<M, PK, PT & ~PT_OBS, PL_DENSE, PlantArg>;
+  // (the held policy's rollouts report the tracking cost: the PT_OBS tables share the kernels of the table without it -- the
+  // limited forms too, whose clearance reads the geometry through the constants, whatever the table)
+  constexpr int PTC = PT & ~PT_OBS;
+  static_assert(TOLG_PLANT_DIAG == 0 && TOLG_PLANT_DENSE == 1, "the order of ClosedLoop::plant below");
+  t.policy_rollout = {k_policy_rollout<M, PK, PTC>,
+                      {k_policy_rollout<M, PK, PTC, PL_DIAG, PlantArg>, k_policy_rollout<M, PK, PTC, PL_DENSE, PlantArg>}};
+  t.policy_rollout_lim = {k_policy_rollout<M, PK, PTC, PL_NONE, PolicyLim>,
+                          {k_policy_rollout<M, PK, PTC, PL_DIAG, PolicyLim, PlantArg>,
+                           k_policy_rollout<M, PK, PTC, PL_DENSE, PolicyLim, PlantArg>}};
+  t.mpc_advance = {k_mpc_advance<M, PK, PTC>,
+                   {k_mpc_advance<M, PK, PTC, PL_DIAG, PlantArg>, k_mpc_advance<M, PK, PTC, PL_DENSE, PlantArg>}};
+  t.mpc_advance_lim = {k_mpc_advance<M, PK, PTC, PL_NONE, MpcLim>,
+                       {k_mpc_advance<M, PK, PTC, PL_DIAG, MpcLim, PlantArg>, k_mpc_advance<M, PK, PTC, PL_DENSE, MpcLim, PlantArg>}};
   t.policy_covariance = k_policy_covariance<M, PK>;  // (reads neither reference nor weights: one kernel for every PT)
   t.policy_value = k_policy_value<M, PK, PT & ~PT_OBS>;  // (the tracking cost's derivatives: reference and weights, no spheres)
   t.policy_covariance_est = k_policy_covariance_est<M, PK>;
@@ -6745,23 +6659,33 @@ extern "C" int tolg_solve_gains(tolg_handle_t h, int32_t B, double* d_k, double*
   return 0;
 }
 
-extern "C" int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w, double* d_J,
-                                   int32_t* d_status, double* d_xs_q, double* d_xs_xi, double* d_us, void* stream) {
+// launches a closed-loop kernel: the model's form, or with a plant held the form of that plant with plant_arg(h) appended
+template <class... A, class... V>
+static int launch_closed_loop(const tolg_handle_s* h, const ClosedLoop<A...>& k, dim3 grid, dim3 block, hipStream_t st, V... args) {
+  if (h->plant.p) hipLaunchKernelGGL(k.plant[h->plant_form], grid, block, 0, st, args..., plant_arg(h));
+  else hipLaunchKernelGGL(k.model, grid, block, 0, st, args...);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// tolg_policy_rollout and tolg_policy_rollout_limited: the rules both share, then the kernel of k with lim (none, or the
+// PolicyLim) behind the rollout's arguments
+template <class K, class... LIM>
+static int policy_rollout(tolg_handle_t h, const K& k, int32_t B, int32_t S, const double* d_dx0, const double* d_w, double* d_J,
+                          int32_t* d_status, double* d_xs_q, double* d_xs_xi, double* d_us, void* stream, LIM... lim) {
   if (!policy_ok(h, B) || S < 1) return TOLG_E_ARG;
   const size_t lanes = (size_t)B * (size_t)S * 4;
   if (lanes > 0x7fffffc0ull) return TOLG_E_ARG;  // one launch, 64-lane groups
   if (h->plant.p && (B != h->plant.B || (h->plant_S != 1 && h->plant_S != S))) return TOLG_E_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   Params P = params_for(h, B);
   P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // J is the tracking cost: no augmented-Lagrangian terms
-  if (h->plant.p)
-    hipLaunchKernelGGL(h->kt.policy_rollout_plant[h->plant_form], dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P,
-                       (int)S, h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, plant_arg(h));
-  else
-    hipLaunchKernelGGL(h->kt.policy_rollout, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P, (int)S,
-                       h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us);
-  LAUNCH_CHECK();
-  return 0;
+  return launch_closed_loop(h, k, dim3((unsigned)((lanes + 63) / 64)), dim3(64), static_cast<hipStream_t>(stream), P, (int)S,
+                            h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, lim...);
+}
+extern "C" int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w, double* d_J,
+                                   int32_t* d_status, double* d_xs_q, double* d_xs_xi, double* d_us, void* stream) {
+  if (!h) return TOLG_E_ARG;
+  return policy_rollout(h, h->kt.policy_rollout, B, S, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, stream);
 }
 
 // The box is an argument of the call and never held by the handle; the spheres are the ones it holds (policy_ok: for this B).
@@ -6769,25 +6693,11 @@ extern "C" int tolg_policy_rollout_limited(tolg_handle_t h, int32_t B, int32_t S
                                            const double* d_u_lb, const double* d_u_ub, double* d_J, int32_t* d_status,
                                            double* d_xs_q, double* d_xs_xi, double* d_us, int32_t* d_n_sat, double* d_u_excess,
                                            double* d_clear, int32_t* d_clear_knot, void* stream) {
-  if (!policy_ok(h, B) || S < 1) return TOLG_E_ARG;
-  const size_t lanes = (size_t)B * (size_t)S * 4;
-  if (lanes > 0x7fffffc0ull) return TOLG_E_ARG;  // one launch, 64-lane groups
-  if (h->plant.p && (B != h->plant.B || (h->plant_S != 1 && h->plant_S != S))) return TOLG_E_ARG;
-  if ((d_u_lb == nullptr) != (d_u_ub == nullptr)) return TOLG_E_ARG;
+  if (!h || (d_u_lb == nullptr) != (d_u_ub == nullptr)) return TOLG_E_ARG;
   const bool clearance = d_clear || d_clear_knot;
   if (clearance && !h->pt[H_OBS].p) return TOLG_E_ARG;  // (spheres for another B: policy_ok)
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  Params P = params_for(h, B);
-  P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // J is the tracking cost: no augmented-Lagrangian terms
-  const PolicyLim L{d_u_lb, d_u_ub, d_n_sat, d_u_excess, d_clear, d_clear_knot, clearance ? 1 : 0};
-  if (h->plant.p)
-    hipLaunchKernelGGL(h->kt.policy_rollout_lim_plant[h->plant_form], dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P,
-                       (int)S, h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, L, plant_arg(h));
-  else
-    hipLaunchKernelGGL(h->kt.policy_rollout_lim, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P, (int)S,
-                       h->pol_traj_fast ? 1 : 0, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, L);
-  LAUNCH_CHECK();
-  return 0;
+  return policy_rollout(h, h->kt.policy_rollout_lim, B, S, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, stream,
+                        PolicyLim{d_u_lb, d_u_ub, d_n_sat, d_u_excess, d_clear, d_clear_knot, clearance ? 1 : 0});
 }
 
 extern "C" int tolg_policy_covariance(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, double* d_Sigma,
@@ -6845,9 +6755,12 @@ extern "C" int tolg_policy_rollout_estimated(tolg_handle_t h, int32_t B, int32_t
   return 0;
 }
 
-extern "C" int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, double* d_x_next_q, double* d_x_next_xi,
-                                double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm,
-                                double* d_J_cl, void* stream) {
+// tolg_mpc_advance and tolg_mpc_advance_limited: the rules both share and the shift (of the unclamped solution in either),
+// then the kernel of k with lim (none, or the MpcLim) behind the step's arguments
+template <class K, class... LIM>
+static int mpc_advance(tolg_handle_t h, const K& k, int32_t B, const double* d_w, double* d_x_next_q, double* d_x_next_xi,
+                       double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl,
+                       void* stream, LIM... lim) {
   if (!policy_ok(h, B) || !d_xs_q_warm || !d_xs_xi_warm || !d_us_warm) return TOLG_E_ARG;
   if (h->plant.p && (B != h->plant.B || h->plant_S != 1)) return TOLG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -6856,37 +6769,23 @@ extern "C" int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, d
   hipLaunchKernelGGL(k_mpc_shift, knot_grid(P.N, P.Bp), dim3(256), 0, st, P, P.cur, P.cur_u, d_xs_q_warm,
                      d_xs_xi_warm, d_us_warm);
   LAUNCH_CHECK();
-  const dim3 grid((unsigned)((2 * (size_t)B + 255) / 256));
-  if (h->plant.p)
-    hipLaunchKernelGGL(h->kt.mpc_advance_plant[h->plant_form], grid, dim3(256), 0, st, P, d_w, d_x_next_q, d_x_next_xi,
-                       d_u_applied, d_xs_q_warm, d_xs_xi_warm, d_J_cl, plant_arg(h));
-  else
-    hipLaunchKernelGGL(h->kt.mpc_advance, grid, dim3(256), 0, st, P, d_w, d_x_next_q, d_x_next_xi, d_u_applied, d_xs_q_warm,
-                       d_xs_xi_warm, d_J_cl);
-  LAUNCH_CHECK();
-  return 0;
+  return launch_closed_loop(h, k, dim3((unsigned)((2 * (size_t)B + 255) / 256)), dim3(256), st, P, d_w, d_x_next_q, d_x_next_xi,
+                            d_u_applied, d_xs_q_warm, d_xs_xi_warm, d_J_cl, lim...);
+}
+extern "C" int tolg_mpc_advance(tolg_handle_t h, int32_t B, const double* d_w, double* d_x_next_q, double* d_x_next_xi,
+                                double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm,
+                                double* d_J_cl, void* stream) {
+  if (!h) return TOLG_E_ARG;
+  return mpc_advance(h, h->kt.mpc_advance, B, d_w, d_x_next_q, d_x_next_xi, d_u_applied, d_xs_q_warm, d_xs_xi_warm, d_us_warm,
+                     d_J_cl, stream);
 }
 
 extern "C" int tolg_mpc_advance_limited(tolg_handle_t h, int32_t B, const double* d_w, const double* d_u_lb, const double* d_u_ub,
                                         double* d_x_next_q, double* d_x_next_xi, double* d_u_applied, double* d_xs_q_warm,
                                         double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl, int32_t* d_n_sat, void* stream) {
-  if (!policy_ok(h, B) || !d_xs_q_warm || !d_xs_xi_warm || !d_us_warm || !d_u_lb || !d_u_ub) return TOLG_E_ARG;
-  if (h->plant.p && (B != h->plant.B || h->plant_S != 1)) return TOLG_E_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  Params P = params_for(h, B);
-  P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // the stage cost is the tracking cost: no augmented-Lagrangian terms
-  hipLaunchKernelGGL(k_mpc_shift, knot_grid(P.N, P.Bp), dim3(256), 0, st, P, P.cur, P.cur_u, d_xs_q_warm,
-                     d_xs_xi_warm, d_us_warm);  // (the unclamped shift)
-  LAUNCH_CHECK();
-  const dim3 grid((unsigned)((2 * (size_t)B + 255) / 256));
-  if (h->plant.p)
-    hipLaunchKernelGGL(h->kt.mpc_advance_lim_plant[h->plant_form], grid, dim3(256), 0, st, P, d_w, d_x_next_q, d_x_next_xi,
-                       d_u_applied, d_xs_q_warm, d_xs_xi_warm, d_J_cl, d_u_lb, d_u_ub, d_n_sat, plant_arg(h));
-  else
-    hipLaunchKernelGGL(h->kt.mpc_advance_lim, grid, dim3(256), 0, st, P, d_w, d_x_next_q, d_x_next_xi, d_u_applied, d_xs_q_warm,
-                       d_xs_xi_warm, d_J_cl, d_u_lb, d_u_ub, d_n_sat);
-  LAUNCH_CHECK();
-  return 0;
+  if (!h || !d_u_lb || !d_u_ub) return TOLG_E_ARG;
+  return mpc_advance(h, h->kt.mpc_advance_lim, B, d_w, d_x_next_q, d_x_next_xi, d_u_applied, d_xs_q_warm, d_xs_xi_warm,
+                     d_us_warm, d_J_cl, stream, MpcLim{d_u_lb, d_u_ub, d_n_sat});
 }
 
 extern "C" size_t tolg_plant_bytes(const tolg_problem* prob, int32_t max_batch, int32_t S) {
