@@ -315,6 +315,47 @@ size_t tolg_obstacles_moving_bytes(const tolg_problem* prob, int32_t max_batch, 
 int tolg_set_al_obstacles_moving(tolg_handle_t h, int32_t B, int32_t K, const double* d_obs, const double* d_lambda,
                                  const double* d_imu, void* d_packed, size_t packed_bytes, void* stream);
 
+/* Pose constraints: where the vehicle points.  A second slot family beside the position slots of tolg_set_al_obstacles* and
+ * independent of them, with its own geometry, kinds and multipliers: trajectory b has K slots, 1 <= K <=
+ * TOLG_MAX_POSE_CONSTRAINTS, of four fields each, g_k(R_i, t_i) <= 0 at every knot i = 0..N, terminal included.  The kind of
+ * slot k is the same for every trajectory and every knot (batch-shared: no wave diverges on it).  The body axes are fixed: e3 =
+ * (0, 0, 1) is the thrust axis of TOLG_DYN_DRONE, e1 = (1, 0, 0) is forward.  In the error coordinates of l_x (right
+ * perturbation X Exp(delta), twist order [omega, v]) g_x = [g_omega, g_v, 0_6], g_u = 0:
+ *   kind                    fields                     row g <= 0                        g_omega        g_v               margin (>= 0 inside)
+ *   TOLG_POSE_TILT_CONE 0   nx ny nz c = cos(max tilt) c - n^T R e3                      (R^T n) x e3   0                 n^T R e3 - c
+ *   TOLG_POSE_VIEW_CONE 1   px py pz c = cos(half angle) c |b| - e1^T b, b = R^T (p - t) b x e1         e1 - c b / |b|    e1^T b / |b| - c
+ * n is a world axis of unit norm, used as given; p is a world target.  -1 < c < 1.  The cost gains the reference's Gauss-Newton
+ * terms (ALConstrainedCost, no g_xx), as for the spheres:
+ *   l += lambda_ik g_k + I_ik g_k^2 / 2,  l_x[0:6] += g_x (lambda_ik + I_ik g_k),  l_xx[0:6,0:6] += I_ik g_x g_x^T.
+ * The knot record, both backward sweeps, the gains and the held policy are those of every other solve: the pose block of l_xx
+ * is stored whole already.  Two degenerate points: the tilt gradient vanishes at the antipode of the axis (R e3 = -n, where g
+ * is largest), so a solve started exactly there is not pushed out by this row; the view row is not differentiable at t = p
+ * (b = 0: g_v divides by |b|), so the target must stay off the path.  Constraints on the twist are not offered: the twist
+ * block of l_xx is a per-lane constant of the sweeps.
+ *
+ * tolg_pose_constraints_bytes: bytes of the caller-owned buffer that holds the packed geometry, 4 K Bp 8 with Bp = max_batch
+ * rounded up to a multiple of 4, times N + 1 with per_knot; 0 for an invalid problem, a kind of the SO3 family or K out of range.
+ * tolg_set_al_pose_constraints: kinds [K] on the HOST, each TOLG_POSE_*; packs d_geo [B][K][4], or with per_knot != 0
+ * [B][N+1][K][4] (the geometry of every knot: a view target that moves, a tilt limit that tightens near a gate), into d_packed
+ * on `stream` ([knots][4K][Bp], coalesced over the batch, padded trajectories replicate B-1) and attaches the multipliers
+ * d_lambda [B][N+1][K] and the diagonal of I_mu d_imu [B][N+1][K], caller-owned and read by every later solve on the handle.
+ * From then on every batch entry point that adds the terms of the position slots adds these too and must be called with this B;
+ * the handle runs the kernels it runs with position slots attached, whether any are or not.  tolg_al_update_state evaluates
+ * the pose rows on the poses it is handed and moves these multipliers under its one rule, the one mu per problem, the joint
+ * d_maxviol and d_al_converged.  tolg_eval_knot, the policy rollouts, the covariance and the value sweep ignore the family, as
+ * they ignore the spheres.  tolg_al_mpc_step refuses while the family is attached.  d_geo = NULL detaches.  The held policy is
+ * left alone.
+ * TOLG_E_ARG: K outside 1..TOLG_MAX_POSE_CONSTRAINTS, a kind outside 0..1, NULL kinds, multipliers or buffer, B < 1 or B >
+ * max_batch, packed_bytes below tolg_pose_constraints_bytes(prob, B, K, per_knot), a solve in flight, another per-trajectory
+ * input held for another B, a kind of the SO3 family.  A refused call changes nothing. */
+#define TOLG_MAX_POSE_CONSTRAINTS 8
+#define TOLG_POSE_TILT_CONE 0
+#define TOLG_POSE_VIEW_CONE 1
+size_t tolg_pose_constraints_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K, int32_t per_knot);
+int tolg_set_al_pose_constraints(tolg_handle_t h, int32_t B, int32_t K, const int32_t* kinds, const double* d_geo,
+                                 int32_t per_knot, const double* d_lambda, const double* d_imu, void* d_packed,
+                                 size_t packed_bytes, void* stream);
+
 /* One outer iteration of AL_iLQR_Tracking_SE3_MS (traoptlibrary/traopt_controller.py:3242-3250, :3270-3290) over every
  * constraint attached to the handle: the input box of tolg_set_al on d_us [B][N][m] and the spheres of tolg_set_al_obstacles
  * on the positions of d_xs_q [B][N+1][16].  d_maxviol[b] = the largest g of them all (the box contributes its terminal rows
@@ -322,8 +363,10 @@ int tolg_set_al_obstacles_moving(tolg_handle_t h, int32_t B, int32_t K, const do
  * attached d_lambda / d_imu of either call) follow the rule of tolg_al_update with one mu per problem, d_mu[b].  d_us may be
  * NULL without a box, d_xs_q without spheres.  tolg_al_update is unchanged.  The row of slot k is the row of its kind
  * (tolg_set_al_obstacle_kinds: r^2 - |d|^2, |d|^2 - r^2, n.t - o or r^2 - (dx^2 + dy^2)); the rule is the same for all.
- * TOLG_E_ARG: nothing attached, B < 1 or B > max_batch, B other than the spheres' batch, a NULL input the attached
- * constraints need. */
+ * Pose slots (tolg_set_al_pose_constraints) are a third row set under the same rule: c - n^T R e3 or c |b| - e1^T b on the
+ * whole pose of d_xs_q, with their own multipliers.
+ * TOLG_E_ARG: nothing attached, B < 1 or B > max_batch, B other than the spheres' or the pose slots' batch, a NULL input the
+ * attached constraints need. */
 int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu, double mu_scale,
                          double mu_max, double tol_constr, double* d_maxviol, int32_t* d_al_converged, void* stream);
 
@@ -346,7 +389,7 @@ int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_xs_q, const
  * spheres.  The held policy is left alone: tolg_mpc_advance behind this call gives the bits it gave before it.
  * tolg_al_update and tolg_al_update_state are unchanged.  One workgroup per trajectory; cost: INTEGRATION.md 3m.
  * TOLG_E_ARG: nothing attached, B < 1 or B > max_batch, B other than the spheres' batch, a NULL input the attached constraints
- * need, a NULL d_mu, shift other than 0 or 1, a solve in flight. */
+ * need, a NULL d_mu, shift other than 0 or 1, a solve in flight, pose constraints attached (tolg_set_al_pose_constraints). */
 int tolg_al_mpc_step(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu, double mu_scale,
                      double mu_max, double tol_constr, double* d_maxviol, int32_t shift, void* stream);
 

@@ -3,7 +3,7 @@
 (al_fit_batch(obstacles=...)) on the K = 8 field: its outer-iteration count and time.
 
 usage: python tools/bench_obstacles.py [--lines headline,merit,ss] [--Ks 0,1,4,8] [--B 4096] [--N 200] [--rounds 7]
-                                       [--steps K] [--warmup W] [--al] [--moving] [--kinds] [--out FILE.json] [--dry]
+                                       [--steps K] [--warmup W] [--al] [--moving] [--kinds] [--pose] [--out FILE.json] [--dry]
 
 One process, one handle per line; the variants are timed in alternation, round after round (the order rotates every round),
 each region being iterations W .. W+K of a fresh solve between two device synchronisations (tools/_benchlib.py's
@@ -19,7 +19,11 @@ static ones show what the streaming costs.
 --kinds times what the per-slot kind costs (tolg_set_al_obstacle_kinds) at K = 6 slots in place of the K sweep: no slots, all
 keep-out spheres (workloads.se3_obstacle_field with K = 6: the K = 6 run of this tool without the flag), the corridor mix
 (workloads.se3_corridor: two half-spaces, a geofence, two columns, a sphere) and all half-spaces (the tangent planes of the
-spheres that face the start of the path).  One line per mix for every solve line asked for."""
+spheres that face the start of the path).  One line per mix for every solve line asked for.
+
+--pose times what the second slot family costs (tolg_set_al_pose_constraints) in place of the K sweep: nothing attached, the
+two pose slots of workloads.se3_inspection (a tilt cone and a view cone whose target drifts: the per-knot form), six keep-out
+spheres, and both families together."""
 import argparse
 import json
 import os
@@ -39,6 +43,7 @@ def parse_args(argv=None):
     ap.add_argument("--al", action="store_true", help="also time one al_fit_batch on the K = max(Ks) field")
     ap.add_argument("--moving", action="store_true", help="attach each field per knot (tolg_set_al_obstacles_moving)")
     ap.add_argument("--kinds", action="store_true", help="time the kind mixes at K = 6 (spheres, corridor, half-spaces)")
+    ap.add_argument("--pose", action="store_true", help="time two pose slots (tilt cone, view cone) alone and beside six spheres")
     add_common_args(ap, "out", "dry")
     a = ap.parse_args(argv)
     a.lines = a.lines.split(",")
@@ -127,6 +132,42 @@ def run_kinds_line(name, a, prob, q0, xi0, us, mixes):
     return out
 
 
+POSE_MIXES = ("none", "pose", "spheres", "both")
+
+
+def run_pose_line(name, a, prob, q0, xi0, us, sph, slots, kinds):
+    import torch
+    from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
+    kw, K0 = LINES[name]
+    K, W = a.steps or K0, a.warmup
+    solver = BatchedTrackingILQR(prob, a.B)
+    dev = solver.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    q_d, xi_d, us_d = (torch.as_tensor(x, **f64) for x in (q0, xi0, us))
+    mult = {k: (torch.full((a.B, a.N + 1, k), 0.1, **f64), torch.full((a.B, a.N + 1, k), 1e-2, **f64)) for k in (2, 6)}
+    slots_d = torch.as_tensor(slots, **f64)
+
+    def region(mix):
+        if mix in ("spheres", "both"):
+            solver.set_al_obstacles(sph, *mult[6])
+        if mix in ("pose", "both"):
+            solver.set_al_pose_constraints(slots_d, kinds, *mult[2])
+        rate, _ = solve_rate_region(solver, (q_d, xi_d, us_d), kw, W, K)
+        solver.set_al_pose_constraints(None)
+        solver.set_al_obstacles(None)
+        torch.cuda.synchronize(dev)
+        return rate
+
+    rates = rate_rounds(POSE_MIXES, region, a.rounds)
+    out = dict(line=name, B=a.B, N=a.N, K=6, pose_K=2, steps=K, warmup=W, rounds=a.rounds, unit="batch-iterations/s",
+               variants={m: summary(rates[m]) for m in POSE_MIXES})
+    base = out["variants"]["none"]["median"]
+    out["ratio_to_none"] = {v: s["median"] / base for v, s in out["variants"].items()}
+    del solver
+    torch.cuda.synchronize(dev)
+    return out
+
+
 def run_al(a, prob, q0, xi0, us, obs):
     import torch
     from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
@@ -148,15 +189,21 @@ def main(argv=None):
     prob, q0, xi0, us, obs = workloads.se3_obstacle_field(a.B, kmax, N=a.N)
     if a.kinds:
         (prob, q0, xi0, us), mixes = kind_mixes(a)
+    if a.pose:  # (se3_tracking's starts and path under both workloads: the slots fit the sphere field's problem)
+        prob, q0, xi0, us, sph6 = workloads.se3_obstacle_field(a.B, 6, N=a.N)
+        slots, pose_kinds = workloads.se3_inspection(a.B, N=a.N)[4:]
     if a.dry:
         print(json.dumps(dict(plan=a.lines, Ks=a.Ks, B=a.B, N=prob.N, rounds=a.rounds, al=a.al, moving=a.moving,
-                              kinds=list(KIND_MIXES) if a.kinds else None,
+                              kinds=list(KIND_MIXES) if a.kinds else None, pose=list(POSE_MIXES) if a.pose else None,
                               steps={n: a.steps or LINES[n][1] for n in a.lines}, warmup=a.warmup)))
         return 0
     require_gpu("bench_obstacles")
     results = []
     for name in a.lines:
-        r = run_kinds_line(name, a, prob, q0, xi0, us, mixes) if a.kinds else run_line(name, a, prob, q0, xi0, us, obs)
+        if a.pose:
+            r = run_pose_line(name, a, prob, q0, xi0, us, sph6, slots, pose_kinds)
+        else:
+            r = run_kinds_line(name, a, prob, q0, xi0, us, mixes) if a.kinds else run_line(name, a, prob, q0, xi0, us, obs)
         results.append(r)
         print_row(r)
     if a.al:

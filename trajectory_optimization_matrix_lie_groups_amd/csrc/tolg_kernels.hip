@@ -60,9 +60,17 @@ struct Consts {
   // [N+1][4K][Bp], knot i's block at i * 4 K Bp); the pack kernels set it
   size_t obs_stride;
   // pose schedule (tolg_set_pose_schedule, caller-owned), read by the PT_W / PTW kernels only: the factor on entry k of the pose
-  // weights of knot i of trajectory b, [N+1][6][Bp], at (6 i + k) * Bp + b; null (tolg_create; the detach): no schedule.  Last:
-  // no other member moves.
+  // weights of knot i of trajectory b, [N+1][6][Bp], at (6 i + k) * Bp + b; null (tolg_create; the detach): no schedule.
   const double* psched;
+  // pose constraints (tolg_set_al_pose_constraints, caller-owned), the second slot family of the PT_OBS kernels: the packed
+  // geometry [4K][Bp] (field f of slot k at (4k + f) * Bp + b; per knot: knot i's block pose_stride = 4 K Bp doubles on), the
+  // multipliers and the diagonal of I_mu in the caller layout [B][N+1][K], the slots per trajectory (0: none attached, what
+  // tolg_create and the detach leave -- the one wave-uniform test of pose_terms) and their kinds (TOLG_POSE_*), 1 bit each,
+  // slot k at bit k, batch-shared like obs_kinds.  Behind every older member: none of them moves.
+  const double *pose, *pose_lam, *pose_imu;
+  size_t pose_stride;
+  int poseK;
+  unsigned pose_kinds;
 };
 
 // Device-side view of the constants used by the three hot kernels: address space 4 (constant), so
@@ -433,8 +441,62 @@ TOLG_DEV void obs_slot(unsigned kd, const double* o, size_t Bp, double lk, doubl
     }
   }
 }
+// One pose row of kind kd (wave-uniform) with fields f0..f3 at the pose X = (R, t): g, and its gradient in the error coordinates
+// of l_x (X Exp(delta), twist order [w, v]) as gw | gv (include/tolg.h has the table).  Body axes e3 (thrust) and e1 (forward):
+//   tilt cone  a = R^T n:        g = c - a.e3,       gw = a x e3,  gv = 0        (gw vanishes at a = -e3 as at a = e3)
+//   view cone  b = R^T (p - t):  g = c |b| - e1.b,   gw = b x e1,  gv = e1 - c b / |b|   (not differentiable at t = p: |b| = 0)
+TOLG_DEV void pose_row(unsigned kd, double f0, double f1, double f2, double f3, const Pose& X, double& g, V3& gw, V3& gv) {
+  if (kd == TOLG_POSE_VIEW_CONE) {
+    const V3 b = qrot_inv(X.q, v3(f0, f1, f2) - X.t);
+    const double nb = sqrt(dot(b, b)), s = f3 / nb;
+    g = f3 * nb - b.x;
+    gw = v3(0.0, b.z, -b.y);
+    gv = v3(1.0 - s * b.x, -(s * b.y), -(s * b.z));
+    return;
+  }
+  const V3 a = qrot_inv(X.q, v3(f0, f1, f2));
+  g = f3 - a.z;
+  gw = v3(a.y, -a.x, 0.0);
+  gv = v3(0.0, 0.0, 0.0);
+}
+// Pose constraints of trajectory b (tolg_set_al_pose_constraints; K = C.poseK > 0 of them, the caller's test): g_k(R, t) <= 0
+// at every knot, terminal included, with ALConstrainedCost's Gauss-Newton terms as for the position slots.  Sums lambda g +
+// g I g / 2 into l and, with px / pxx given, g_x (lambda + I g) into px (l_x[0:6]) and I g_x g_x^T into pxx (the pose block of
+// l_xx, packed as REC_LXX: entry (a, c) at sym6(a, c)).  With lambda = I = 0 every term is an exact zero.
+template <class CT>
+TOLG_DEV void pose_terms(const Params& P, const CT& C, int K, int i, int b, const Pose& X, double& l, double* px, double* pxx) {
+  const int bs = b < P.B ? b : P.B - 1;  // (as obs_terms: padded lanes replicate the geometry, not the multipliers)
+  const size_t row = ((size_t)bs * (P.N + 1) + i) * K, Bp = (size_t)P.Bp;
+  const double *lam = C.pose_lam + row, *imu = C.pose_imu + row, *geo = C.pose + b + (size_t)i * C.pose_stride;
+  const unsigned kinds = C.pose_kinds;
+  for (int k = 0; k < K; k++) {
+    const double* o = geo + (size_t)(4 * k) * Bp;
+    const double lk = lam[k], ik = imu[k];
+    double g;
+    V3 gw, gv;
+    pose_row((kinds >> k) & 1u, o[0], o[Bp], o[2 * Bp], o[3 * Bp], X, g, gw, gv);
+    l += lk * g + 0.5 * (g * ik * g);
+    if (px) {
+      const double gx[6] = {gw.x, gw.y, gw.z, gv.x, gv.y, gv.z}, s = lk + ik * g;
+#pragma unroll
+      for (int a = 0; a < 6; a++) {
+        px[a] += gx[a] * s;
+#pragma unroll
+        for (int c = a; c < 6; c++) pxx[sym6(a, c)] += ik * gx[a] * gx[c];
+      }
+    }
+  }
+}
+
+// The pose constraints (pose_terms) ride on the PT_OBS forms behind one wave-uniform test of their count: the cost-only callers
+// (ox null at compile time) take them here, ahead of the position slots; lin_knot takes them where it adds the position sums to the
+// tracking values, straight into l_x and l_xx -- carried from up here as ox / oxx are, their 27 sums would stay live across the
+// whole tracking block.  C.obsK is 0 when the pose family alone selected the PT_OBS forms.
 template <class CT>
 TOLG_DEV void obs_terms(const Params& P, const CT& C, int i, int b, const Pose& X, double& l, double* ox, double* oxx) {
+  if (!ox) {
+    if (const int pk = C.poseK) pose_terms(P, C, pk, i, b, X, l, nullptr, nullptr);
+  }
   const int K = C.obsK, bs = b < P.B ? b : P.B - 1;  // the packed geometry replicates B-1 in padded lanes, the multipliers do not
   const size_t row = ((size_t)bs * (P.N + 1) + i) * K, Bp = (size_t)P.Bp;
   const double *lam = C.obs_lam + row, *imu = C.obs_imu + row, *geo = C.obs + b + (size_t)i * C.obs_stride;
@@ -1218,6 +1280,8 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
 #pragma unroll
         for (int c = a; c < 3; c++, n++) lxx[sym6(3 + a, 3 + c)] += oxx[n];
       }
+      // ... and the pose constraints' (obs_terms has the note): l_x[0:6] and the whole pose block of l_xx
+      if (const int pk = C.poseK) pose_terms(P, C, pk, i, b, S.X, l, lxv, lxx);
       if (lcost) *lcost = l;
       else P.SC[(size_t)i * P.Bp + b] = l;
     }
@@ -5341,6 +5405,13 @@ struct tolg_handle_s {
   unsigned obs_kinds = 0; // ... their kinds (Consts::obs_kinds; tolg_set_al_obstacle_kinds), kept while K stays,
   size_t obs_stride = 0;  // ... the knot stride of the geometry in doubles (Consts::obs_stride): 0, or 4 K Bp for the moving form
   double *obs_lam = nullptr, *obs_imu = nullptr;  // ... their multipliers [B][N+1][K] (caller-owned; tolg_al_update_state writes them)
+  // tolg_set_al_pose_constraints: the packed geometry of the pose slots, or nothing held.  Under the one-batch rule; no PT bit
+  // of its own: held, it selects the PT_OBS tables as pt[H_OBS] does (select_kernels), and those kernels test Consts::poseK
+  Held posec;
+  int pose_K = 0;           // ... the slots per trajectory,
+  unsigned pose_kinds = 0;  // ... their kinds (Consts::pose_kinds),
+  size_t pose_stride = 0;   // ... the knot stride of the geometry in doubles: 0, or 4 K Bp for the per-knot form
+  double *pose_lam = nullptr, *pose_imu = nullptr;  // ... their multipliers [B][N+1][K] (caller-owned; tolg_al_update_state writes them)
   // tolg_set_plant: the packed plant rows, or nothing held: the closed loops step the model.  Outside the one-batch rule (its
   // B is checked against the policy call's) and outside PT
   Held plant;
@@ -5380,6 +5451,7 @@ static dim3 knot_grid(int knots, int Bp) { return dim3((unsigned)(((size_t)knots
 static bool one_batch(const tolg_handle_s* h, int B, const Held* except = nullptr) {
   for (const Held& r : h->pt) if (&r != except && r.p && B != r.B) return false;
   if (&h->sched != except && h->sched.p && B != h->sched.B) return false;
+  if (&h->posec != except && h->posec.p && B != h->posec.B) return false;
   return true;
 }
 // B trajectories fit the handle and the per-trajectory inputs it holds: what every batch call on the handle's workspace requires
@@ -5394,6 +5466,7 @@ static bool dest_ok(const tolg_handle_s* h, int B, const void* d, size_t bytes, 
 static void select_kernels(tolg_handle_s* h) {
   int pt = 0;
   for (int k = 0; k < H_PT; k++) if (h->pt[k].p) pt |= 1 << k;
+  if (h->posec.p) pt |= PT_OBS;  // the pose slots ride on the forms of the position slots (Consts::obsK = 0 without those)
   h->kt = h->kt_pt[pt];
 }
 // kt_pt[PT] = kernel_table_for<PT>, for every set PT of the PT_* bits (tolg_create)
@@ -5410,6 +5483,7 @@ static void hold(tolg_handle_s* h, Held& r, const void* d, int B) {
 static void drop(tolg_handle_s* h, Held& r) {
   r = Held();
   if (&r == &h->pt[H_OBS]) { h->obs_K = 0; h->obs_kinds = 0; h->obs_stride = 0; h->obs_lam = h->obs_imu = nullptr; }
+  if (&r == &h->posec) { h->pose_K = 0; h->pose_kinds = 0; h->pose_stride = 0; h->pose_lam = h->pose_imu = nullptr; }
   if (&r == &h->plant) h->plant_S = h->plant_form = 0;
   select_kernels(h);
 }
@@ -6296,6 +6370,23 @@ struct AlRows {
     const double g = r * r - (dx * dx + dy * dy + dz * dz);
     return kd == TOLG_OBS_KEEP_IN ? -g : g;
   }
+  // ... and pose slot k at knot i (tolg_set_al_pose_constraints; k_al_update_state alone is given them), the row of its kind on
+  // the 4x4 pose of xs_q: the tilt cone c - n^T R e3, the view cone c |b| - e1^T b with b = R^T (p - t)
+  const double* pgeo = nullptr;
+  size_t pgeo_stride = 0;
+  unsigned pkinds = 0;
+  TOLG_DEV double g_pose(int i, int k) const {
+    const double* x = xs_q + ((size_t)b * (N + 1) + i) * 16;
+    const double* o = pgeo + (size_t)i * pgeo_stride + (size_t)(4 * k) * Bp + b;
+    const double f0 = o[0], f1 = o[Bp], f2 = o[2 * (size_t)Bp], c = o[3 * (size_t)Bp];
+    if (((pkinds >> k) & 1u) == TOLG_POSE_VIEW_CONE) {
+      const double d0 = f0 - x[3], d1 = f1 - x[7], d2 = f2 - x[11];
+      const double b0 = x[0] * d0 + x[4] * d1 + x[8] * d2, b1 = x[1] * d0 + x[5] * d1 + x[9] * d2,
+                   b2 = x[2] * d0 + x[6] * d1 + x[10] * d2;
+      return c * sqrt(b0 * b0 + b1 * b1 + b2 * b2) - b0;
+    }
+    return c - (f0 * x[2] + f1 * x[6] + f2 * x[10]);
+  }
 };
 // lambda <- max(0, lambda + I_mu g), I_mu <- 0 where (g < 0 and lambda_new == 0) else mu_new
 TOLG_DEV void al_row_update(double& l, double& im, double g, double mu_new) {
@@ -6311,15 +6402,24 @@ TOLG_DEV void al_row_update(double& l, double& im, double g, double mu_new) {
 // [B][N+1][16].  lambda <- max(0, lambda + I_mu g), mu <- min(mu_scale mu, mu_max), I_mu <- 0 where (g < 0 and lambda_new ==
 // 0) else mu_new for both multiplier sets; maxviol = the largest g of them all (the box contributes the zero rows of its
 // terminal knot, traopt_constraints.py:160-161; the spheres have no such rows), one mu per problem.  tolg_al_update passes
-// the box of its own arguments and no geometry, tolg_al_update_state what the handle holds.
+// the box of its own arguments and no geometry, tolg_al_update_state what the handle holds.  ps: the pose slots
+// (tolg_set_al_pose_constraints; geo null: none), a third row set under the same rule, on the poses of xs_q.
+struct AlPose {
+  const double* geo;  // packed as Consts::pose; knot i's block `stride` doubles on
+  size_t stride;
+  unsigned kinds;
+  int K;
+  double *lam, *imu;  // [B][N+1][K]
+};
 __global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const double* __restrict__ xs_q, const double* __restrict__ us,
                                   const double* __restrict__ lb, const double* __restrict__ ub, double* __restrict__ lam,
                                   double* __restrict__ imu, const double* __restrict__ geo, size_t geo_stride, unsigned kinds,
                                   double* __restrict__ olam, double* __restrict__ oimu, double* __restrict__ mu, double mu_scale,
-                                  double mu_max, double tol_constr, double* __restrict__ maxviol, int* __restrict__ al_conv) {
+                                  double mu_max, double tol_constr, double* __restrict__ maxviol, int* __restrict__ al_conv,
+                                  AlPose ps) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B || al_conv[b]) return;  // a converged problem keeps its multipliers
-  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride, kinds};
+  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride, kinds, ps.geo, ps.stride, ps.kinds};
   double mv = lb ? 0.0 : -INFINITY;
   if (lb)
     for (int i = 0; i < N; i++)
@@ -6327,6 +6427,9 @@ __global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const doub
   if (geo)
     for (int i = 0; i <= N; i++)
       for (int k = 0; k < K; k++) mv = fmax(mv, R.g_sphere(i, k));
+  if (ps.geo)
+    for (int i = 0; i <= N; i++)
+      for (int k = 0; k < ps.K; k++) mv = fmax(mv, R.g_pose(i, k));
   maxviol[b] = mv;
   if (mv < tol_constr) { al_conv[b] = 1; return; }
   const double mu_new = fmin(mu[b] * mu_scale, mu_max);
@@ -6340,6 +6443,12 @@ __global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const doub
       for (int k = 0; k < K; k++) {
         const size_t o = ((size_t)b * (N + 1) + i) * K + k;
         al_row_update(olam[o], oimu[o], R.g_sphere(i, k), mu_new);
+      }
+  if (ps.geo)
+    for (int i = 0; i <= N; i++)
+      for (int k = 0; k < ps.K; k++) {
+        const size_t o = ((size_t)b * (N + 1) + i) * ps.K + k;
+        al_row_update(ps.lam[o], ps.imu[o], R.g_pose(i, k), mu_new);
       }
   mu[b] = mu_new;
 }
@@ -6433,6 +6542,12 @@ __global__ __launch_bounds__(AL_STEP_THREADS) void k_al_mpc_step(
   }
 }
 
+// A detach of one slot family while the other keeps the PT_OBS forms selected: its count in the constants goes to zero
+__global__ void k_clear_slots(Consts* c, int position, int pose) {
+  if (position) c->obsK = 0;
+  if (pose) c->poseK = 0;
+}
+
 static size_t obstacles_bytes_for(const tolg_problem*, int B, int K) { return (size_t)4 * K * (size_t)padded_batch(B) * sizeof(double); }
 static size_t obstacles_moving_bytes_for(const tolg_problem* p, int B, int K) { return (size_t)(p->N + 1) * obstacles_bytes_for(p, B, K); }
 extern "C" size_t tolg_obstacles_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K) {
@@ -6452,7 +6567,14 @@ static int set_obstacles(tolg_handle_t h, int B, int K, bool moving, const doubl
                          const int32_t* d_t0 = nullptr, int t = -1) {
   if (!h || h->running) return TOLG_E_ARG;
   Held& r = h->pt[H_OBS];
-  if (!d_obs) { drop(h, r); return 0; }
+  if (!d_obs) {
+    if (r.p && h->posec.p) {  // the PT_OBS forms stay selected for the pose slots: no position slot is left for them to read
+      hipLaunchKernelGGL(k_clear_slots, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), const_cast<Consts*>(h->P.c), 1, 0);
+      LAUNCH_CHECK();
+    }
+    drop(h, r);
+    return 0;
+  }
   if (so3_family(h->prob.kind) || K < 1 || K > TOLG_MAX_OBSTACLES || !d_lambda || !d_imu) return TOLG_E_ARG;
   if (!dest_ok(h, B, d_packed, packed_bytes, moving ? obstacles_moving_bytes_for : obstacles_bytes_for, K) || !one_batch(h, B, &r))
     return TOLG_E_ARG;
@@ -6500,6 +6622,67 @@ extern "C" int tolg_set_al_obstacle_kinds(tolg_handle_t h, int32_t K, const int3
   return 0;
 }
 
+// Pose constraints (tilt cone, view cone): the second slot family.  d_geo [B][src knots][K][4] into [knots][4K][Bp] as
+// k_pack_obstacles_moving packs the position slots (knots = 1: the static form, `stride` 0; N + 1: the per-knot form, `stride`
+// 4 K Bp; padded trajectories replicate B-1).  Thread 0 points the constants at the geometry, the caller's multipliers and the
+// kind word, and with clear_obs -- no position slots attached -- zeroes their count, which the PT_OBS forms read beside this one.
+__global__ void k_pack_pose_constraints(int B, int Bp, int K, int knots, size_t stride, const double* __restrict__ geo,
+                                        const double* lam, const double* imu, double* __restrict__ w, Consts* c, unsigned kinds,
+                                        int clear_obs) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t knot = (size_t)4 * K * Bp;
+  if (g == 0) {
+    c->pose = w; c->pose_lam = lam; c->pose_imu = imu; c->poseK = K; c->pose_kinds = kinds; c->pose_stride = stride;
+    if (clear_obs) c->obsK = 0;
+  }
+  if (g >= knot * (size_t)knots) return;
+  const size_t i = g / knot, r = g % knot;
+  const int b = (int)(r % Bp), f = (int)(r / Bp);
+  const int bs = b < B ? b : B - 1;
+  w[g] = geo[((size_t)bs * knots + i) * 4 * K + f];
+}
+static size_t pose_constraints_bytes_for(const tolg_problem* p, int B, int K, int per_knot) {
+  return (size_t)(per_knot ? p->N + 1 : 1) * 4 * K * (size_t)padded_batch(B) * sizeof(double);
+}
+extern "C" size_t tolg_pose_constraints_bytes(const tolg_problem* prob, int32_t max_batch, int32_t K, int32_t per_knot) {
+  if (check_problem(prob) || so3_family(prob->kind) || max_batch < 1 || K < 1 || K > TOLG_MAX_POSE_CONSTRAINTS) return 0;
+  return pose_constraints_bytes_for(prob, max_batch, K, per_knot != 0);
+}
+// d_geo = null detaches.  The held policy stays: its gains belong to the problem that was solved.
+extern "C" int tolg_set_al_pose_constraints(tolg_handle_t h, int32_t B, int32_t K, const int32_t* kinds, const double* d_geo,
+                                            int32_t per_knot, const double* d_lambda, const double* d_imu, void* d_packed,
+                                            size_t packed_bytes, void* stream) {
+  if (!h || h->running) return TOLG_E_ARG;
+  Held& r = h->posec;
+  if (!d_geo) {
+    if (r.p) {  // (the position slots, attached now or later, run the same forms: they must find no pose slot)
+      hipLaunchKernelGGL(k_clear_slots, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), const_cast<Consts*>(h->P.c), 0, 1);
+      LAUNCH_CHECK();
+    }
+    drop(h, r);
+    return 0;
+  }
+  if (so3_family(h->prob.kind) || K < 1 || K > TOLG_MAX_POSE_CONSTRAINTS || !kinds || !d_lambda || !d_imu) return TOLG_E_ARG;
+  if (B < 1 || B > h->max_batch || !d_packed || (reinterpret_cast<uintptr_t>(d_packed) & 7) != 0 ||
+      packed_bytes < pose_constraints_bytes_for(&h->prob, B, K, per_knot != 0) || !one_batch(h, B, &r))
+    return TOLG_E_ARG;
+  unsigned word = 0;
+  for (int k = 0; k < K; k++) {
+    if (kinds[k] < TOLG_POSE_TILT_CONE || kinds[k] > TOLG_POSE_VIEW_CONE) return TOLG_E_ARG;
+    word |= (unsigned)kinds[k] << k;
+  }
+  const int Bp = padded_batch(B), knots = per_knot ? h->prob.N + 1 : 1;
+  const size_t knot = (size_t)4 * K * Bp;
+  hipLaunchKernelGGL(k_pack_pose_constraints, dim3((unsigned)((knots * knot + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), B, Bp, K, knots, per_knot ? knot : (size_t)0, d_geo, d_lambda, d_imu,
+                     static_cast<double*>(d_packed), const_cast<Consts*>(h->P.c), word, h->pt[H_OBS].p ? 0 : 1);
+  LAUNCH_CHECK();
+  h->pose_K = K; h->pose_kinds = word; h->pose_stride = per_knot ? knot : 0;
+  h->pose_lam = const_cast<double*>(d_lambda); h->pose_imu = const_cast<double*>(d_imu);
+  hold(h, r, d_packed, B);
+  return 0;
+}
+
 // the box of the call's own arguments, no geometry (Bp, K = 0: nothing reads them)
 extern "C" int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, const double* d_lb, const double* d_ub,
                               double* d_lambda, double* d_imu, double* d_mu, double mu_scale, double mu_max,
@@ -6508,7 +6691,7 @@ extern "C" int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, co
     return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_update_state, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), B, 0, h->prob.N,
                      h->prob.m, 0, (const double*)nullptr, d_us, d_lb, d_ub, d_lambda, d_imu, (const double*)nullptr, (size_t)0,
-                     0u, (double*)nullptr, (double*)nullptr, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, d_al_converged);
+                     0u, (double*)nullptr, (double*)nullptr, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, d_al_converged, AlPose{});
   LAUNCH_CHECK();
   return 0;
 }
@@ -6517,14 +6700,15 @@ extern "C" int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_
                                     double mu_scale, double mu_max, double tol_constr, double* d_maxviol,
                                     int32_t* d_al_converged, void* stream) {
   if (!h || B < 1 || B > h->max_batch || !d_mu || !d_maxviol || !d_al_converged) return TOLG_E_ARG;
-  const Held& obs = h->pt[H_OBS];
-  if (!h->al_lb && !obs.p) return TOLG_E_ARG;     // nothing attached to update
+  const Held &obs = h->pt[H_OBS], &pose = h->posec;
+  if (!h->al_lb && !obs.p && !pose.p) return TOLG_E_ARG;     // nothing attached to update
   if (h->al_lb && !d_us) return TOLG_E_ARG;
   if (obs.p && (B != obs.B || !d_xs_q)) return TOLG_E_ARG;
+  if (pose.p && (B != pose.B || !d_xs_q)) return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_update_state, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), B, padded_batch(B),
                      h->prob.N, h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
                      const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_kinds, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
-                     d_maxviol, d_al_converged);
+                     d_maxviol, d_al_converged, AlPose{pose.p, h->pose_stride, h->pose_kinds, h->pose_K, h->pose_lam, h->pose_imu});
   LAUNCH_CHECK();
   return 0;
 }
@@ -6534,6 +6718,7 @@ extern "C" int tolg_al_mpc_step(tolg_handle_t h, int32_t B, const double* d_xs_q
                                 double mu_scale, double mu_max, double tol_constr, double* d_maxviol, int32_t shift,
                                 void* stream) {
   if (!h || h->running || B < 1 || B > h->max_batch || !d_mu || (shift != 0 && shift != 1)) return TOLG_E_ARG;
+  if (h->posec.p) return TOLG_E_ARG;  // pose constraints have no receding-horizon step: refused, never ignored
   const Held& obs = h->pt[H_OBS];
   if (!h->al_lb && !obs.p) return TOLG_E_ARG;     // nothing attached to update
   if (h->al_lb && !d_us) return TOLG_E_ARG;

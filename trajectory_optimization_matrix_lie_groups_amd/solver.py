@@ -317,6 +317,66 @@ def kind_clearance(t, geo, kinds):
     return (torch if isinstance(out[0], torch.Tensor) else np).stack(out, -1)
 
 
+# The kinds of a pose-constraint slot (TOLG_POSE_*, include/tolg.h has the table of rows, gradients and margins): the second
+# slot family, beside OBSTACLE_KINDS and apart from it
+POSE_CONSTRAINT_KINDS = {"tilt_cone": _capi.POSE_TILT_CONE, "view_cone": _capi.POSE_VIEW_CONE}
+
+
+def check_pose_kinds(kinds, K):
+    """The kinds of K pose slots as a tuple of ints 0..1: a length-K sequence of ints or of POSE_CONSTRAINT_KINDS names.
+    ValueError for None (a pose slot has no default kind), another length or an unknown kind."""
+    if kinds is None:
+        raise ValueError("pose constraints need their kinds: one of %s per slot" % sorted(POSE_CONSTRAINT_KINDS))
+    kinds = list(kinds)
+    if len(kinds) != int(K):
+        raise ValueError("pose kinds has %d entries, expected one per slot: K = %d" % (len(kinds), K))
+    out = []
+    for k in kinds:
+        if isinstance(k, str) and k in POSE_CONSTRAINT_KINDS:
+            out.append(POSE_CONSTRAINT_KINDS[k])
+        elif isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 0 <= int(k) <= 1:
+            out.append(int(k))
+        else:
+            raise ValueError("unknown pose constraint kind %r, expected 0..1 or one of %s" % (k, sorted(POSE_CONSTRAINT_KINDS)))
+    return tuple(out)
+
+
+def check_pose_geometry(name, a, kinds):
+    """The fields of every pose slot under its kind, a [..., K, 4] numpy or torch: a tilt cone needs a unit world axis (nx, ny,
+    nz), ||n| - 1| <= 1e-9 (never rescaled), a view cone a finite target (px, py, pz); both -1 < c < 1, the cosine of the
+    largest tilt / of the half angle.  ValueError otherwise."""
+    for k, kd in enumerate(kinds):
+        s = a[..., k, :]
+        if not bool(((s == s) & (abs(s) != float("inf"))).all()):
+            raise ValueError("%s must be finite (slot %d)" % (name, k))
+        if kd == _capi.POSE_TILT_CONE:
+            n2 = (s[..., :3] ** 2).sum(-1)
+            if bool((abs(n2 ** 0.5 - 1.0) > 1e-9).any()):
+                raise ValueError("%s: slot %d is a tilt cone and needs a unit axis (nx, ny, nz), | |n| - 1 | <= 1e-9" % (name, k))
+        if not bool(((s[..., 3] > -1.0) & (s[..., 3] < 1.0)).all()):
+            raise ValueError("%s: slot %d needs -1 < c < 1, the cosine of its angle" % (name, k))
+
+
+def pose_margin(xs_q, slots, kinds):
+    """The margins of poses xs_q [..., 4, 4] under pose slots [..., K, 4] (leading shapes that broadcast against those of xs_q:
+    [K, 4], [B, K, 4], [B, N+1, K, 4], with a sample axis [B, 1, N+1, K, 4]) of `kinds`, [..., K], numpy or torch alike: >= 0
+    inside the allowed set.  Tilt cone n^T R e3 - c: the cosine of the tilt above that of the limit; view cone e1^T b / |b| - c
+    with b = R^T (p - t).  On the states of policy_rollout(trajectories=True) this is the Monte-Carlo check of a limit under
+    noise."""
+    kinds = check_pose_kinds(kinds, slots.shape[-2])
+    R, t = xs_q[..., :3, :3], xs_q[..., :3, 3]
+    out = []
+    for k, kd in enumerate(kinds):
+        f = slots[..., k, :]
+        if kd == _capi.POSE_TILT_CONE:
+            out.append((f[..., :3] * R[..., :, 2]).sum(-1) - f[..., 3])
+            continue
+        d = f[..., :3] - t
+        b = (R * d[..., :, None]).sum(-2)   # R^T d
+        out.append(b[..., 0] / (b ** 2).sum(-1) ** 0.5 - f[..., 3])
+    return (torch if isinstance(out[0], torch.Tensor) else np).stack(out, -1)
+
+
 def inflate_obstacles(obstacles, xs_q, pos_cov, kappa, kinds=None):
     """Keep-out spheres with a margin for the closed-loop spread: obstacles [K, 4], [B, K, 4] or [B, N+1, K, 4] rows (cx, cy,
     cz, r), xs_q [B, N+1, 4, 4] the nominal plan, pos_cov [B, N+1, 3, 3] its position covariance (policy_covariance().pos_cov).
@@ -389,12 +449,14 @@ _POLICY = {"tolg_solve_begin": "clear", "tolg_solve_begin_warm": "clear", "tolg_
            "tolg_solve_batch": "clear hold", "tolg_linearize_backward": "clear hold", "tolg_solve_end": "hold",
            "tolg_set_al_obstacles": "", "tolg_set_al_obstacles_moving": "",
            "tolg_al_update_state": "", "tolg_al_mpc_step": "",
-           "tolg_set_al_obstacle_windows": "", "tolg_set_al_obstacle_kinds": ""}  # (the last six leave it: listed for completeness)
+           "tolg_set_al_obstacle_windows": "", "tolg_set_al_obstacle_kinds": "",
+           "tolg_set_al_pose_constraints": ""}  # (the last seven leave it: listed for completeness)
 # A setter's detach call (BatchedTrackingILQR._detach): its arguments behind the handle with the source pointer null, the
 # stream's place included.  tolg_set_al_obstacles detaches the per-knot form too.
 _DETACH = {"tolg_set_refs": (0, None, None, None, 0, None), "tolg_set_weights": (0, None, None, None, None, 0, None),
            "tolg_set_pose_schedule": (0, None, None, 0, None),
            "tolg_set_al_obstacles": (0, 0, None, None, None, None, 0, None), "tolg_set_al": (None, None, None, None),
+           "tolg_set_al_pose_constraints": (0, 0, None, None, 0, None, None, None, 0, None),
            "tolg_set_plant": (0, 0, 0, None, None, None, 0, None)}
 
 
@@ -436,6 +498,8 @@ class BatchedTrackingILQR:
         self._al = None            # the augmented-Lagrangian terms the handle points at (set_al)
         self._obs = None           # ... and the keep-out spheres (set_al_obstacles): (obstacles, lam, imu) on the device
         self._obs_kinds = ()       # ... with the kinds the handle holds for them (tolg_set_al_obstacle_kinds), one per slot
+        self._pose = None          # ... and the pose constraints (set_al_pose_constraints): (slots, lam, imu, kinds)
+        self._pose_buf = self._pose_knot_buf = None  # their packed geometry: static for max_batch, per knot for the largest call
         p = _capi.Problem()
         p.kind, p.m, p.N, p.dt = _KIND[problem.kind], self.m, self.N, float(problem.dt)
         p.pend_mass, p.pend_length = float(problem.pend_mass), float(problem.pend_length)
@@ -942,6 +1006,56 @@ class BatchedTrackingILQR:
         self._hold((d, t0_d))
         self._set_obstacle_windows(B, d, t0_d, int(t), lam, imu, kinds)
 
+    def _check_pose_constraints(self, B, slots, kinds):
+        """Pose slots [K, 4] (every trajectory the same), [B, K, 4], or per knot [B, N+1, K, 4], fields per kind (check_pose_kinds,
+        check_pose_geometry), checked on the host: ValueError before anything reaches the device for a model of the SO3 family,
+        a wrong shape, K outside 1..MAX_POSE_CONSTRAINTS, a non-finite value, an axis that is not unit or a cosine outside
+        (-1, 1).  B = None takes B from a [B, ...] array.  Returns (B, [B, K, 4] or [B, N+1, K, 4] float64 numpy, kinds)."""
+        if self.problem.kind in ("so3", "pendulum3d"):
+            raise ValueError("pose constraints are not offered for the %s model" % self.problem.kind)
+        a = slots.detach().cpu().numpy() if isinstance(slots, torch.Tensor) else slots
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim not in (2, 3, 4):
+            raise ValueError("pose constraints have shape %s, expected (K, 4), (B, K, 4) or (B, N+1, K, 4)" % (a.shape,))
+        a = _checked("pose_constraints", a, (None,) * a.ndim, finite=True)
+        if a.ndim == 2:
+            if B is None:
+                raise ValueError("pose constraints [K, 4] need the batch: give lam / imu [B, N+1, K] or slots [B, K, 4]")
+            a = np.broadcast_to(a, (B,) + a.shape)
+        B = a.shape[0] if B is None else B
+        a = _checked("pose_constraints", a, (B, None, 4) if a.ndim == 3 else (B, self.N + 1, None, 4))
+        if not 1 <= a.shape[-2] <= _capi.MAX_POSE_CONSTRAINTS:
+            raise ValueError("pose constraints: K = %d slots per trajectory, expected 1..%d" % (a.shape[-2], _capi.MAX_POSE_CONSTRAINTS))
+        if not 1 <= B <= self.max_batch:
+            raise ValueError("pose constraints for B = %d trajectories, expected 1..%d" % (B, self.max_batch))
+        kinds = check_pose_kinds(kinds, a.shape[-2])
+        check_pose_geometry("pose_constraints", a, kinds)
+        return B, np.ascontiguousarray(a), kinds
+
+    def set_al_pose_constraints(self, slots=None, kinds=None, lam=None, imu=None):
+        """Attach (or detach with slots=None) pose constraints, the second slot family (tolg_set_al_pose_constraints): the
+        augmented-Lagrangian terms of g_k(R, t) <= 0 at every knot, terminal included, beside whatever set_al /
+        set_al_obstacles attached.  slots [K, 4] (broadcast), [B, K, 4], or per knot [B, N+1, K, 4]; kinds a length-K sequence
+        of ints or of "tilt_cone" | "view_cone" (POSE_CONSTRAINT_KINDS), the kind of slot k in every trajectory and at every
+        knot.  A tilt cone has fields (nx, ny, nz, c): never tilt the body axis e3 more than acos(c) from the unit world axis
+        n, g = c - n^T R e3.  A view cone has fields (px, py, pz, c): keep the world target p within acos(c) of the forward
+        axis e1, g = c |b| - e1^T b with b = R^T (p - t).  lam, imu [B, N+1, K]: the multipliers and the diagonal of I_mu
+        (device tensors the handle reads in every solve until they are detached; None: zeros).  Every batch call must then
+        be for this B; mpc() and plan_fleet refuse while the family is attached."""
+        if slots is None:
+            self._pose = None
+            self._detach("tolg_set_al_pose_constraints")
+            return
+        Bl = None if lam is None else int(lam.shape[0])
+        B, a, kinds = self._check_pose_constraints(Bl, slots, kinds)
+        K, per_knot = a.shape[-2], a.ndim == 4
+        lam, imu = self._obs_multipliers(B, K, lam, imu)
+        fn = self.lib.tolg_pose_constraints_bytes
+        dest = self._packed("_pose_knot_buf", fn, K, 1, B=B) if per_knot else self._packed("_pose_buf", fn, _capi.MAX_POSE_CONSTRAINTS, 0)
+        d = self._dev(a, a.shape)
+        self._call("tolg_set_al_pose_constraints", B, K, (C.c_int32 * K)(*kinds), _ptr(d), int(per_knot), _ptr(lam), _ptr(imu), *dest)
+        self._pose = (d, lam, imu, kinds)  # the handle reads the multipliers in every solve until they are detached
+
     def al_mpc_step(self, xs_q, us, mu, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2, shift=True):
         """The outer augmented-Lagrangian update of one MPC step over everything attached (tolg_al_mpc_step): the multipliers
         of set_al / set_al_obstacles follow lambda <- max(0, lambda + I_mu g) on the controls us [B, N, m] and the positions of
@@ -967,7 +1081,7 @@ class BatchedTrackingILQR:
     def al_fit_batch(self, x0_q, x0_xi, us_init, lb=None, ub=None, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
                      tol_d_norm=1e-6, tol_constr=1e-2, mu0=1e-2, mu_scale=10.0, mu_max=1e8, line_search=False,
                      on_outer=None, q_ref=None, xi_ref=None, Q=None, P=None, R=None, obstacles=None, obstacle_kinds=None,
-                     pose_scale=None):
+                     pose_scale=None, pose_constraints=None, pose_kinds=None):
         """AL_iLQR_Tracking_SE3_MS.fit (reference traoptlibrary/traopt_controller.py:3218-3267) for B
         independent problems: every outer iteration re-solves from (x0, us_init) -- no warm start, as in
         the reference -- then updates multipliers on the device.  Returns (FitResult, info dict).
@@ -976,16 +1090,22 @@ class BatchedTrackingILQR:
         Constraints: the input box lb <= u <= ub, keep-out spheres obstacles ([K, 4], [B, K, 4] or per knot [B, N+1, K, 4],
         set_al_obstacles; obstacle_kinds: its kinds=, a kind per slot -- keep-in sphere, half-space, column), or both
         (one mu per problem, joint convergence: tolg_al_update_state).  With spheres the info dict also holds lmbd_obs and
-        Imu_obs [B, N+1, K]; max_violation covers every constraint."""
+        Imu_obs [B, N+1, K]; max_violation covers every constraint.
+        pose_constraints / pose_kinds: pose slots and their kinds (set_al_pose_constraints: tilt cones, view cones), alone or
+        beside the others under the same mu and the same convergence; the info dict then holds lmbd_pose and Imu_pose
+        [B, N+1, K]."""
         if (lb is None) != (ub is None):
             raise ValueError("the input box needs both lb and ub")
-        if lb is None and obstacles is None:
-            raise ValueError("al_fit_batch needs a constraint: lb / ub, obstacles, or both")
+        if lb is None and obstacles is None and pose_constraints is None:
+            raise ValueError("al_fit_batch needs a constraint: lb / ub, obstacles, pose_constraints, or several")
         b = self._stage(x0_q, x0_xi, us_init, (q_ref, xi_ref), (Q, P, R), pose_scale=pose_scale)
         B = b.B
         if obstacles is None and obstacle_kinds is not None:
             raise ValueError("obstacle_kinds describe obstacles: none were given")
         obs = None if obstacles is None else self._check_obstacles(B, obstacles, obstacle_kinds)[1]
+        if pose_constraints is None and pose_kinds is not None:
+            raise ValueError("pose_kinds describe pose_constraints: none were given")
+        pose = None if pose_constraints is None else self._check_pose_constraints(B, pose_constraints, pose_kinds)[1:]
         o = self._options("ms", n_ilqr_iters, line_search, "nonlinear", tol_grad_norm, tol_d_norm, 1e10)
         f64 = dict(dtype=torch.float64, device=self.device)
         box = lb is not None
@@ -1007,6 +1127,18 @@ class BatchedTrackingILQR:
                 if box:
                     self.set_al(None)
                 raise
+        lam_p = imu_p = None
+        if pose is not None:
+            lam_p = torch.zeros(B, self.N + 1, pose[0].shape[-2], **f64)
+            imu_p = torch.full((B, self.N + 1, pose[0].shape[-2]), float(mu0), **f64)
+            try:
+                self.set_al_pose_constraints(pose[0], pose[1], lam_p, imu_p)
+            except Exception:
+                if box:
+                    self.set_al(None)
+                if obs is not None:
+                    self.set_al_obstacles(None)
+                raise
         outer = 0
         res = None
         final = None
@@ -1025,7 +1157,7 @@ class BatchedTrackingILQR:
                     final = res
                 if on_outer is not None:  # before the multiplier update, like on_iteration_al (:3253-3259)
                     on_outer(outer, final, lam, imu, mu)
-                if obs is None:
+                if obs is None and pose is None:
                     self._call("tolg_al_update", B, _ptr(final.us), _ptr(lb_d), _ptr(ub_d), _ptr(lam), _ptr(imu), _ptr(mu),
                                float(mu_scale), float(mu_max), float(tol_constr), _ptr(maxviol), _ptr(alconv))
                 else:  # every attached constraint, one mu per problem
@@ -1038,9 +1170,13 @@ class BatchedTrackingILQR:
                 self.set_al(None)
             if obs is not None:
                 self.set_al_obstacles(None)
+            if pose is not None:
+                self.set_al_pose_constraints(None)
         info = dict(lmbd=lam, Imu=imu, mu=mu, max_violation=maxviol, al_converged=alconv, outer_iterations=outer + 1)
         if obs is not None:
             info.update(lmbd_obs=lam_o, Imu_obs=imu_o)
+        if pose is not None:
+            info.update(lmbd_pose=lam_p, Imu_pose=imu_p)
         return final, info
 
     def plan_fleet(self, x0_q, x0_xi, us_init, q_ref, xi_ref, fleet, separation, obstacles=None, lb=None, ub=None,
@@ -1060,6 +1196,8 @@ class BatchedTrackingILQR:
         the final plans (inf for fleet = 1), max_violation [B], al_converged [B] int32 (rounds without a constraint: 0 and
         1), outer_iterations [fleet] (python ints)."""
         G = int(fleet)
+        if self._pose is not None or al_kw.get("pose_constraints") is not None or al_kw.get("pose_kinds") is not None:
+            raise ValueError("plan_fleet with pose constraints is not supported: the rounds solve sub-batches")
         x0_q, x0_xi = (a if hasattr(a, "shape") else np.asarray(a, dtype=np.float64) for a in (x0_q, x0_xi))
         B = int(x0_q.shape[0])
         if G < 1 or B % G != 0:
@@ -1636,6 +1774,8 @@ class BatchedTrackingILQR:
             raise ValueError("mpc under an augmented-Lagrangian constraint is not supported: detach it with set_al(None)")
         if self._obs is not None:
             raise ValueError("mpc with keep-out spheres is not supported: detach them with set_al_obstacles(None)")
+        if self._pose is not None:
+            raise ValueError("mpc with pose constraints is not supported: detach them with set_al_pose_constraints(None)")
         if warm not in ("states", "controls"):
             raise ValueError("warm must be 'states' or 'controls'")
         if mode not in ("ms", "ss"):

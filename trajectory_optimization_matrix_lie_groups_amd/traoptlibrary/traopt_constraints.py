@@ -191,6 +191,71 @@ class PositionObstacleConstraint(BaseConstraint):
         return np.zeros((self._constr_size, self._action_size))
 
 
+class PoseConstraint(BaseConstraint):
+    """Pose constraints of a kind per slot (tolg_set_al_pose_constraints), with the interface of the classes above: slots
+    [K, 4], or [N+1, K, 4] with the geometry of every knot, kinds a length-K sequence of 0..1.  Body axes e3 = (0, 0, 1), the
+    thrust axis, and e1 = (1, 0, 0), forward; X = (R, t) the pose of x = [X, xi]:
+      0 tilt cone  fields (nx, ny, nz, c), |n| = 1   g = c - n^T R e3                    g_omega = (R^T n) x e3   g_v = 0
+      1 view cone  fields (px, py, pz, c)            g = c |b| - e1^T b, b = R^T (p - t)   g_omega = b x e1         g_v = e1 - c b / |b|
+    In the error coordinates (X Exp(delta), twist order [omega, v]) g_x = [g_omega, g_v, 0], g_u = 0.  The tilt gradient
+    vanishes at the antipode of the axis; the view row is not differentiable at t = p."""
+
+    def __init__(self, slots, kinds, state_size=(6, 6), action_size=6):
+        o = np.asarray(slots, dtype=np.float64)
+        if o.ndim not in (2, 3) or o.shape[-1] != 4:
+            raise ValueError("slots has shape %s, expected (K, 4) or (N+1, K, 4)" % (o.shape,))
+        k = np.asarray(kinds)
+        if k.shape != (o.shape[-2],) or not np.issubdtype(k.dtype, np.integer) or np.any(k < 0) or np.any(k > 1):
+            raise ValueError("kinds: one of 0..1 per slot")
+        self._slots = o.copy()
+        self._kinds = k.astype(np.int64)
+        self._state_size = state_size[0] + state_size[1]
+        self._error_state_size = state_size[0]
+        self._vel_state_size = state_size[1]
+        self._action_size = action_size
+        self._constr_size = o.shape[-2]
+
+    kinds = property(lambda self: self._kinds)
+    constr_size = property(lambda self: self._constr_size)
+    state_size = property(lambda self: self._state_size)
+    error_state_size = property(lambda self: self._error_state_size)
+    vel_state_size = property(lambda self: self._vel_state_size)
+    action_size = property(lambda self: self._action_size)
+
+    def slots(self):
+        """The slots as given, [K, 4] or [N+1, K, 4]: a trajectory's slice of tolg_set_al_pose_constraints."""
+        return self._slots
+
+    def _rows(self, x, i):
+        """(g [K], g_omega [K, 3], g_v [K, 3]) at knot i"""
+        o = self._slots if self._slots.ndim == 2 else self._slots[i]
+        X = np.asarray(x[0])
+        R, t = X[:3, :3], X[:3, 3]
+        e1, e3 = np.array([1.0, 0.0, 0.0]), np.array([0.0, 0.0, 1.0])
+        g, gw, gv = np.empty(len(o)), np.zeros((len(o), 3)), np.zeros((len(o), 3))
+        for k, (f, kd) in enumerate(zip(o, self._kinds)):
+            if kd == 0:
+                a = R.T @ f[:3]
+                g[k], gw[k] = f[3] - a[2], np.cross(a, e3)
+            else:
+                b = R.T @ (f[:3] - t)
+                nb = np.sqrt(b @ b)
+                g[k], gw[k], gv[k] = f[3] * nb - b[0], np.cross(b, e1), e1 - f[3] * b / nb
+        return g, gw, gv
+
+    def g(self, x, u, i, terminal=False, *args, **kwargs):
+        return self._rows(x, i)[0]
+
+    def g_x(self, x, u, i, terminal=False, *args, **kwargs):
+        _, gw, gv = self._rows(x, i)
+        gx = np.zeros((self._constr_size, self._state_size))
+        gx[:, 0:3], gx[:, 3:6] = gw, gv
+        return gx
+
+    def g_u(self, x, u, i, terminal=False, *args, **kwargs):
+        return np.zeros((self._constr_size, self._action_size))
+
+
 class ConstraintStack(BaseConstraint):
     """Several constraints as one: g, g_x, g_u concatenated in the order given."""
 

@@ -302,17 +302,20 @@ class iLQR_Tracking_SE3_MS(_FusedController):
 
 
 def _route_constraints(constraints):
-    """(InputConstraint or None, SphereObstacleConstraint or None) of what AL_iLQR_Tracking_SE3_MS solves on the device: an
-    InputConstraint, a SphereObstacleConstraint (or its per-knot form, MovingSphereObstacleConstraint), or a ConstraintStack of
-    one of each.  TypeError for anything else: no constraint is ever treated as g_x = 0."""
-    from .traopt_constraints import ConstraintStack, InputConstraint, MovingSphereObstacleConstraint, SphereObstacleConstraint
+    """(InputConstraint or None, SphereObstacleConstraint or None, PoseConstraint or None) of what AL_iLQR_Tracking_SE3_MS
+    solves on the device: an InputConstraint, a SphereObstacleConstraint (or its per-knot form,
+    MovingSphereObstacleConstraint), a PoseConstraint, or a ConstraintStack of at most one of each.  TypeError for anything
+    else: no constraint is ever treated as g_x = 0."""
+    from .traopt_constraints import (ConstraintStack, InputConstraint, MovingSphereObstacleConstraint, PoseConstraint,
+                                     SphereObstacleConstraint)
     parts = constraints.constraints if type(constraints) is ConstraintStack else (constraints,)
     box = [c for c in parts if type(c) is InputConstraint]
     sph = [c for c in parts if type(c) in (SphereObstacleConstraint, MovingSphereObstacleConstraint)]
-    if len(box) > 1 or len(sph) > 1 or len(box) + len(sph) != len(parts):
-        raise TypeError("AL_iLQR_Tracking_SE3_MS supports an InputConstraint, a SphereObstacleConstraint, or a ConstraintStack "
-                        "of one of each; got %s" % ", ".join(type(c).__name__ for c in parts))
-    return (box[0] if box else None), (sph[0] if sph else None)
+    pose = [c for c in parts if type(c) is PoseConstraint]
+    if len(box) > 1 or len(sph) > 1 or len(pose) > 1 or len(box) + len(sph) + len(pose) != len(parts):
+        raise TypeError("AL_iLQR_Tracking_SE3_MS supports an InputConstraint, a SphereObstacleConstraint, a PoseConstraint, or a "
+                        "ConstraintStack of one of each; got %s" % ", ".join(type(c).__name__ for c in parts))
+    return (box[0] if box else None), (sph[0] if sph else None), (pose[0] if pose else None)
 
 
 class AL_iLQR_Tracking_SE3_MS(BaseController):
@@ -323,7 +326,7 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
 
     def __init__(self, dynamics, cost, constraints, N, q_ref, xi_ref, mu_scale=10., max_reg=1e10, hessians=False,
                  line_search=False, rollout='nonlinear', debug=None):
-        self._box, self._spheres = _route_constraints(constraints)
+        self._box, self._spheres, self._pose = _route_constraints(constraints)
         self.dynamics = dynamics
         self.cost = cost
         self.constr = constraints
@@ -363,11 +366,16 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
         obstacles = sph.obstacles() if sph else None
         if obstacles is not None and obstacles.ndim == 3:  # a field per knot [N+1, K, 4]: the same for every trajectory
             obstacles = np.broadcast_to(obstacles, (B,) + obstacles.shape)
+        pose = self._pose
+        slots = pose.slots() if pose else None
+        if slots is not None and slots.ndim == 3:  # per knot [N+1, K, 4]: the same for every trajectory
+            slots = np.broadcast_to(slots, (B,) + slots.shape)
         return solver.al_fit_batch(q, xi, us_init, box.lb if box else None, box.ub if box else None, n_al_iters=n_al_iters,
                                    n_ilqr_iters=n_ilqr_iters, tol_grad_norm=tol_grad_norm, tol_constr=tol_constr,
                                    mu0=self._mu0, mu_scale=self._mu_scale, mu_max=self._mu_max,
                                    line_search=self.ilqr_solver._line_search, on_outer=on_outer, q_ref=q_ref,
-                                   xi_ref=xi_ref, Q=Qs, P=Ps, R=Rs, obstacles=obstacles)
+                                   xi_ref=xi_ref, Q=Qs, P=Ps, R=Rs, obstacles=obstacles, pose_constraints=slots,
+                                   pose_kinds=None if pose is None else tuple(int(k) for k in pose.kinds))
 
     def fit(self, x0, us_init, n_al_iters=100, n_ilqr_iters=200, tol_J=1e-6, tol_grad_norm=1e-6, tol_constr=1e-2,
             on_iteration_al=None, on_iteration_ilqr=None):
@@ -377,8 +385,9 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
         def outer(iteration, res, lam, imu, mu):
             if not on_iteration_al:
                 return
-            if self._spheres is not None:
-                raise NotImplementedError("on_iteration_al reports the input box only; keep-out spheres: use fit_batch(on_outer=)")
+            if self._spheres is not None or self._pose is not None:
+                raise NotImplementedError("on_iteration_al reports the input box only; keep-out spheres, pose constraints: "
+                                          "use fit_batch(on_outer=)")
             us = _bridge.host(res.us)[0]
             g = np.concatenate([self.constr.lb - us, us - self.constr.ub], axis=1)
             constr_eval = np.vstack([g, np.zeros((1, 2 * m))])

@@ -460,6 +460,39 @@ def se3_corridor(B, N=200, seed=SEED):
     return prob, x0_q, x0_xi, us0, _corridor(prob.q_ref, x0_q, 0.15, 0.3, seed + 7), CORRIDOR_KINDS
 
 
+INSPECTION_KINDS = ("tilt_cone", "view_cone")
+
+
+def se3_inspection(B, N=200, seed=SEED):
+    """se3_tracking's workload (R_scale 1e-3) under two pose constraints per trajectory (kinds INSPECTION_KINDS,
+    tolg_set_al_pose_constraints), given per knot:
+      a tilt cone about world z, (0, 0, 1, c): c lies 0.2 above the smallest n^T R e3 of the reference path (and at most
+               0.9), so the path's most tilted knots leave the cone by up to 0.2 while every start, all far more upright,
+               is inside;
+      a view cone on a target that drifts per knot, (p_i, c): p_i moves on a line from 3 ahead of trajectory b's own start
+               pose (along its forward axis: on the cone's axis at knot 0) to 3 ahead of the reference's last pose, bent
+               sideways by a seeded offset of up to 0.5; c lies a fifth of the way from the smallest e1^T b / |b| of the
+               second half of the reference path under that target to 1, so the path leaves the cone where it looks
+               furthest away, on a stretch that a solve from the trajectory's own start has reached.
+    The reference path leaves both cones in every trajectory; the start of every trajectory satisfies both.  Returns (prob,
+    x0_q, x0_xi, us0, slots [B, N+1, 2, 4], kinds): what al_fit_batch(pose_constraints=, pose_kinds=) takes."""
+    prob, x0_q, x0_xi, us0 = se3_tracking(B, N=N, R_scale=1e-3, seed=seed)
+    rng = np.random.default_rng(seed + 9)
+    R, t = prob.q_ref[:, :3, :3], prob.q_ref[:, :3, 3]
+    slots = np.empty((B, N + 1, 2, 4))
+    slots[:, :, 0] = (0.0, 0.0, 1.0, min(R[:, 2, 2].min() + 0.2, 0.9))
+    s = np.linspace(0.0, 1.0, N + 1)[:, None]
+    for b in range(B):
+        X0 = np.asarray(x0_q[b]).reshape(4, 4)
+        p0, p1 = X0[:3, 3] + 3.0 * X0[:3, 0], t[N] + 3.0 * R[N][:, 0]
+        p = (1.0 - s) * p0 + s * p1 + np.sin(np.pi * s) * rng.uniform(-0.5, 0.5, 3)
+        bv = np.einsum("iac,ia->ic", R, p - t)
+        cv = bv[:, 0] / np.linalg.norm(bv, axis=1)
+        late = cv[N // 2:].min()   # (the second half: where a solve from the trajectory's own start has reached the path)
+        slots[b, :, 1, :3], slots[b, :, 1, 3] = p, late + 0.2 * (1.0 - late)
+    return prob, x0_q, x0_xi, us0, slots, INSPECTION_KINDS
+
+
 def drone_corridor(B, N=400, seed=SEED):
     """The drone variant (drone_tracking's workload) of se3_corridor, columns and sphere of radius 0.08 .. 0.15.  Returns
     (prob, x0_q, x0_xi, us0, obstacles [B, 6, 4], kinds)."""
