@@ -343,7 +343,8 @@ int tolg_set_al_obstacles_moving(tolg_handle_t h, int32_t B, int32_t K, const do
  * the handle runs the kernels it runs with position slots attached, whether any are or not.  tolg_al_update_state evaluates
  * the pose rows on the poses it is handed and moves these multipliers under its one rule, the one mu per problem, the joint
  * d_maxviol and d_al_converged.  tolg_eval_knot, the policy rollouts, the covariance and the value sweep ignore the family, as
- * they ignore the spheres.  tolg_al_mpc_step refuses while the family is attached.  d_geo = NULL detaches.  The held policy is
+ * they ignore the spheres.  tolg_al_mpc_step refuses while the family is attached; tolg_al_mpc_step_pose is the step that takes
+ * the pose rows as its third row set and shifts these multipliers with the others.  d_geo = NULL detaches.  The held policy is
  * left alone.
  * TOLG_E_ARG: K outside 1..TOLG_MAX_POSE_CONSTRAINTS, a kind outside 0..1, NULL kinds, multipliers or buffer, B < 1 or B >
  * max_batch, packed_bytes below tolg_pose_constraints_bytes(prob, B, K, per_knot), a solve in flight, another per-trajectory
@@ -355,6 +356,18 @@ size_t tolg_pose_constraints_bytes(const tolg_problem* prob, int32_t max_batch, 
 int tolg_set_al_pose_constraints(tolg_handle_t h, int32_t B, int32_t K, const int32_t* kinds, const double* d_geo,
                                  int32_t per_knot, const double* d_lambda, const double* d_imu, void* d_packed,
                                  size_t packed_bytes, void* stream);
+
+/* tolg_set_al_pose_constraint_windows: the pose slots of step t gathered on the device from world-time paths, d_path_geo
+ * [B][T+1][K][4] = the four fields of trajectory b's slots at world knot s (a view target that moves in world time): knot i of
+ * the window takes world knot min(t0[b] + t + i, T) (tolg_set_ref_windows' rule, one index helper for every window form; d_t0
+ * NULL: 0; any T >= 1, T < N included).  Afterwards the handle is exactly as after tolg_set_al_pose_constraints(..., per_knot
+ * = 1, ...) with the gathered [B][N+1][K][4] array: the same packed bytes (tolg_pose_constraints_bytes(prob, B, K, 1)), the
+ * same multipliers, the same rules for B.  A re-attach with the same K, an MPC loop's at every step, leaves the position
+ * slots and the kernels the handle runs as they are.  d_path_geo = NULL detaches.  The held policy is left alone.
+ * TOLG_E_ARG: those of tolg_set_al_pose_constraints, T < 1, t < 0. */
+int tolg_set_al_pose_constraint_windows(tolg_handle_t h, int32_t B, int32_t K, const int32_t* kinds, const double* d_path_geo,
+                                        int32_t T, const int32_t* d_t0, int32_t t, const double* d_lambda, const double* d_imu,
+                                        void* d_packed, size_t packed_bytes, void* stream);
 
 /* One outer iteration of AL_iLQR_Tracking_SE3_MS (traoptlibrary/traopt_controller.py:3242-3250, :3270-3290) over every
  * constraint attached to the handle: the input box of tolg_set_al on d_us [B][N][m] and the spheres of tolg_set_al_obstacles
@@ -392,6 +405,18 @@ int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_xs_q, const
  * need, a NULL d_mu, shift other than 0 or 1, a solve in flight, pose constraints attached (tolg_set_al_pose_constraints). */
 int tolg_al_mpc_step(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu, double mu_scale,
                      double mu_max, double tol_constr, double* d_maxviol, int32_t shift, void* stream);
+
+/* tolg_al_mpc_step_pose: tolg_al_mpc_step with the pose slots attached (tolg_set_al_pose_constraints, static or per knot, or
+ * tolg_set_al_pose_constraint_windows) as a third row set -- the step of a loop whose planner holds attitude limits.
+ * tolg_al_mpc_step itself keeps its contract and refuses while the family is attached; this call takes the same arguments and
+ * adds the pose rows c - n^T R e3 or c |b| - e1^T b, i <= N, on the poses of d_xs_q: they join mv (which still starts at 0 with
+ * a box and at -inf without), the one mu per problem and d_maxviol, their multipliers [B][N+1][Kp] follow the same rule, and
+ * with shift == 1 they shift as the sphere multipliers do: row i takes row' i+1, i = 0..N-1, row N keeps row' N.  With no pose
+ * family attached the call is tolg_al_mpc_step, bit for bit.  The held policy is left alone.
+ * TOLG_E_ARG: those of tolg_al_mpc_step but the family's presence, and as tolg_al_update_state has them: a pose family attached
+ * for another B, a NULL d_xs_q with one attached. */
+int tolg_al_mpc_step_pose(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu, double mu_scale,
+                          double mu_max, double tol_constr, double* d_maxviol, int32_t shift, void* stream);
 
 /* tolg_set_al_obstacle_windows: the moving spheres of step t gathered on the device from world-time paths, d_path_obs
  * [B][T+1][K][4] = (cx, cy, cz, r) of trajectory b's spheres at world knot s: knot i of the window takes world knot

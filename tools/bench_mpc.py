@@ -4,6 +4,7 @@ against warm controls.
 usage: python tools/bench_mpc.py [--B 4096] [--N 200,50] [--iters 0,1,3,5] [--steps 20] [--rounds 5]
                                  [--tol-steps 10] [--tol-rounds 2] [--max-iters 30] [--out FILE.json]
        python tools/bench_mpc.py --constrained [--B 4096] [--N 200] [--K 4] [--iters 5] [--steps 20] [--rounds 5]
+                                 [--loops unconstrained,box,spheres,box+spheres,pose,spheres+pose]
 
 One process, se3_mpc's workload (every trajectory its own path and phase, twist disturbances behind every step), multiple
 shooting, accept-always.
@@ -19,10 +20,15 @@ shooting, accept-always.
   the fraction of (trajectory, step) solves that stopped below the cap, and ms per step.
 - --constrained: se3_mpc_obstacles' workload instead.  For every N and k the unconstrained loop and the loops with the planner's
   box (the 90th percentile of the unconstrained loop's inputs), with K spheres per trajectory on world-time paths (a device
-  tensor, as the reference paths), and with both (first_al_iters = al_iters_per_step = 1: the same iteration count) alternate
-  round after round in one process; reported as above, with each loop's solves of status OK, its last step's largest violation
-  and its least clearance.  Then the step kernel alone: tolg_al_mpc_step (shift = 1) on the last
-  plan with both multiplier sets attached, `steps` calls between two device synchronisations."""
+  tensor, as the reference paths), with both, with the two pose slots of se3_mpc_inspection on world-time paths (the same paths,
+  starts and disturbances: both workloads are se3_mpc's) and with spheres and pose slots (first_al_iters = al_iters_per_step =
+  1: the same iteration count) alternate round after round in one process; reported as above, with each loop's solves of status
+  OK, its last step's largest violation, its least clearance and its least pose margin.  Then the step kernel alone:
+  tolg_al_mpc_step (shift = 1) on the last plan with the box and sphere multiplier sets attached, and again with the pose slots as
+  the third set (tolg_al_mpc_step_pose), `steps` calls between two device synchronisations.  The pose loops cap mu at 1 (mu_max): the path leaves the
+  cones for good, mu would grow at every step, and accept-always iterations diverge under a penalty that large; what a step
+  costs does not depend on mu.  --loops runs a subset of the loops (an A/B against a build without the pose loops runs the same
+  four in both)."""
 import argparse
 import os
 import statistics
@@ -46,6 +52,7 @@ def parse_args(argv=None):
     ap.add_argument("--max-iters", type=int, default=30)
     ap.add_argument("--constrained", action="store_true")
     ap.add_argument("--K", type=int, default=4)
+    ap.add_argument("--loops", default="unconstrained,box,spheres,box+spheres,pose,spheres+pose")
     add_common_args(ap, "out")
     a = ap.parse_args(argv)
     a.N = [int(x) for x in a.N.split(",")]
@@ -69,13 +76,18 @@ def constrained(a):
         inp = dict(x0_q=q, x0_xi=xi, path_q=dev(pq), path_xi=dev(px), t0=t0, noise=noise, steps=a.steps, warm="states",
                    check_every=0, **zero)
         mov_d = dev(mov)
+        pose_paths, pose_kinds = workloads.se3_mpc_inspection(B, a.steps, N=N)[7:]
+        pose_d = dev(pose_paths)
         for k in a.iters:
             free = s.mpc(first_iters=k, iters_per_step=k, **inp)
             u = np.abs(free.us.cpu().numpy())
             lim = np.percentile(u[np.isfinite(u).all(axis=(1, 2))].reshape(-1, prob.m), 90, axis=0)
             al = dict(first_al_iters=1, al_iters_per_step=1)
             loops = {"unconstrained": {}, "box": dict(lb=-lim, ub=lim, **al), "spheres": dict(obstacle_paths=mov_d, **al),
-                     "box+spheres": dict(lb=-lim, ub=lim, obstacle_paths=mov_d, **al)}
+                     "box+spheres": dict(lb=-lim, ub=lim, obstacle_paths=mov_d, **al),
+                     "pose": dict(pose_paths=pose_d, pose_kinds=pose_kinds, mu_max=1.0, **al),
+                     "spheres+pose": dict(obstacle_paths=mov_d, pose_paths=pose_d, pose_kinds=pose_kinds, mu_max=1.0, **al)}
+            loops = {name: loops[name] for name in a.loops.split(",")}
             times = {name: [] for name in loops}
             last = {}
             for r in range(a.rounds + 1):  # round 0 warms up
@@ -94,6 +106,8 @@ def constrained(a):
                     row.update(max_violation_last_step=float(res.max_violation[:, -1].max().item()), mu_max=float(res.mu.max().item()))
                 if res.clearance is not None:
                     row.update(min_clearance=float(res.clearance.min().item()))
+                if res.pose_margin is not None:
+                    row.update(min_pose_margin=float(res.pose_margin.min().item()))
                 rows.append(row)
                 print_row(row)
         # the step kernel alone, on a plan and both multiplier sets
@@ -103,21 +117,27 @@ def constrained(a):
         s.set_al(-lim, lim, lam, imu)
         s.set_al_obstacle_windows(mov_d, 0, t0=t0, lam=None, imu=torch.full((B, N + 1, a.K), 1e-2, **f64))
         mu = torch.full((B,), 1e-2, **f64)
-        ms = []
-        for r in range(a.rounds + 1):
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            for _ in range(a.steps):
-                s.al_mpc_step(plan.xs_q, plan.us, mu, shift=True)
-            torch.cuda.synchronize()
-            if r:
-                ms.append((time.perf_counter() - t) * 1e3 / a.steps)
+        moved = 8 * B * (2 * 2 * (N * 2 * prob.m + (N + 1) * a.K) + 2 * N * prob.m + 2 * (3 + 4 * a.K) * (N + 1))
+        Kp = pose_paths.shape[2]
+        for part in ("al_mpc_step_alone", "al_mpc_step_alone_with_pose")[:2 if "pose" in a.loops else 1]:
+            if part.endswith("pose"):  # the third row set: its multipliers twice; per pass the rest of the pose and its geometry
+                s.set_al_pose_constraint_windows(pose_d, 0, t0=t0, kinds=pose_kinds, imu=torch.full((B, N + 1, Kp), 1e-2, **f64))
+                moved += 8 * B * (2 * 2 * (N + 1) * Kp + 2 * (9 + 4 * Kp) * (N + 1))
+            ms = []
+            for r in range(a.rounds + 1):
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for _ in range(a.steps):
+                    s.al_mpc_step(plan.xs_q, plan.us, mu, shift=True)
+                torch.cuda.synchronize()
+                if r:
+                    ms.append((time.perf_counter() - t) * 1e3 / a.steps)
+            row = dict(part=part, N=N, K=a.K, **stats_row(ms, "ms_per_call"), bytes_needed=moved)
+            rows.append(row)
+            print_row(row)
         s.set_al(None)
         s.set_al_obstacles(None)
-        moved = 8 * B * (2 * 2 * (N * 2 * prob.m + (N + 1) * a.K) + 2 * N * prob.m + 2 * (3 + 4 * a.K) * (N + 1))
-        row = dict(part="al_mpc_step_alone", N=N, K=a.K, **stats_row(ms, "ms_per_call"), bytes_needed=moved)
-        rows.append(row)
-        print_row(row)
+        s.set_al_pose_constraints(None)
     res = dict(B=B, N=a.N, K=a.K, steps=a.steps, rounds=a.rounds, device=torch.cuda.get_device_name(0), rows=rows)
     emit(res, a.out)
     return res

@@ -35,7 +35,8 @@ SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_ba
            "tolg_pose_schedule_bytes", "tolg_set_pose_schedule", "tolg_set_pose_schedule_windows", "tolg_eval_knot", "tolg_linearize_backward",
            "tolg_rollout", "tolg_expected_change", "tolg_solve_gains", "tolg_policy_rollout",
            "tolg_solve_begin_warm", "tolg_set_ref_windows", "tolg_mpc_advance", "tolg_obstacles_bytes", "tolg_set_al_obstacles", "tolg_obstacles_moving_bytes", "tolg_set_al_obstacles_moving",
-           "tolg_al_update_state", "tolg_al_mpc_step", "tolg_set_al_obstacle_windows", "tolg_set_al_obstacle_kinds", "tolg_pose_constraints_bytes", "tolg_set_al_pose_constraints", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_policy_covariance_estimated", "tolg_policy_rollout_estimated", "tolg_policy_rollout_limited", "tolg_mpc_advance_limited", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
+           "tolg_al_update_state", "tolg_al_mpc_step", "tolg_set_al_obstacle_windows", "tolg_set_al_obstacle_kinds", "tolg_pose_constraints_bytes", "tolg_set_al_pose_constraints",
+           "tolg_set_al_pose_constraint_windows", "tolg_al_mpc_step_pose", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_policy_covariance_estimated", "tolg_policy_rollout_estimated", "tolg_policy_rollout_limited", "tolg_mpc_advance_limited", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
 
 
 def load():
@@ -119,6 +120,8 @@ def load():
     lib.tolg_al_update_state.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_double, C.c_double, C.c_double, dp, ip, vp]
     lib.tolg_al_mpc_step.restype = C.c_int
     lib.tolg_al_mpc_step.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_double, C.c_double, C.c_double, dp, C.c_int32, vp]
+    lib.tolg_al_mpc_step_pose.restype = C.c_int
+    lib.tolg_al_mpc_step_pose.argtypes = lib.tolg_al_mpc_step.argtypes
     lib.tolg_set_al_obstacle_windows.restype = C.c_int
     lib.tolg_set_al_obstacle_windows.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32, ip, C.c_int32, dp, dp, vp, C.c_size_t, vp]
     lib.tolg_set_al_obstacle_kinds.restype = C.c_int
@@ -127,6 +130,9 @@ def load():
     lib.tolg_pose_constraints_bytes.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32]
     lib.tolg_set_al_pose_constraints.restype = C.c_int
     lib.tolg_set_al_pose_constraints.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), dp, C.c_int32, dp, dp, vp, C.c_size_t, vp]
+    lib.tolg_set_al_pose_constraint_windows.restype = C.c_int
+    lib.tolg_set_al_pose_constraint_windows.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), dp, C.c_int32, ip, C.c_int32, dp, dp,
+                                                        vp, C.c_size_t, vp]
     lib.tolg_plant_bytes.restype = C.c_size_t
     lib.tolg_plant_bytes.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32]
     lib.tolg_set_plant.restype = C.c_int

@@ -866,9 +866,9 @@ __global__ void k_pack_refs(int B, int Bp, int N, const double* __restrict__ q_r
   pack_ref_knot(X, xi_ref + ((size_t)bs * (N + 1) + i) * 6, refs + (size_t)i * 13 * Bp + b, Bp);
 }
 // The window rule of every input gathered from a world-time path of T + 1 knots (tolg_set_ref_windows,
-// tolg_set_al_obstacle_windows, tolg_set_pose_schedule_windows): knot i of the window of a trajectory whose phase is t0 (null:
-// 0), at step t, is path knot min(t0 + t + i, T) -- the last knot held past the end; a negative phase reads knot 0 (the loads
-// stay inside the path).
+// tolg_set_al_obstacle_windows, tolg_set_pose_schedule_windows, tolg_set_al_pose_constraint_windows): knot i of the window of
+// a trajectory whose phase is t0 (null: 0), at step t, is path knot min(t0 + t + i, T) -- the last knot held past the end; a
+// negative phase reads knot 0 (the loads stay inside the path).
 TOLG_DEV size_t window_knot(const int* __restrict__ t0, int bs, int t, long long i, int T) {
   const long long k = (long long)(t0 ? t0[bs] : 0) + t + i;
   return (size_t)(k < 0 ? 0 : (k > T ? T : k));
@@ -6370,7 +6370,7 @@ struct AlRows {
     const double g = r * r - (dx * dx + dy * dy + dz * dz);
     return kd == TOLG_OBS_KEEP_IN ? -g : g;
   }
-  // ... and pose slot k at knot i (tolg_set_al_pose_constraints; k_al_update_state alone is given them), the row of its kind on
+  // ... and pose slot k at knot i (tolg_set_al_pose_constraints; both outer updates are given them), the row of its kind on
   // the 4x4 pose of xs_q: the tilt cone c - n^T R e3, the view cone c |b| - e1^T b with b = R^T (p - t)
   const double* pgeo = nullptr;
   size_t pgeo_stride = 0;
@@ -6453,11 +6453,12 @@ __global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const doub
   mu[b] = mu_new;
 }
 
-// The outer update of a receding-horizon step (tolg_al_mpc_step): k_al_update_state's rows and rule without the sticky
-// al_converged -- every step is a new problem: below tol_constr mu stops growing, the multipliers still relax -- followed by the
-// one-knot shift of both multiplier sets, in place.  One workgroup of AL_STEP_THREADS lanes per trajectory; the lanes run along
-// the contiguous rows of trajectory b ([N][2m], then [N+1][K]) in tiles of AL_STEP_TILE doubles, a pair per lane.
-//   pass 1: mv = max g over every row (the rows' inputs only: controls, positions, geometry), a wave reduction and one over the
+// The outer update of a receding-horizon step (tolg_al_mpc_step, tolg_al_mpc_step_pose): k_al_update_state's rows and rule
+// without the sticky al_converged -- every step is a new problem: below tol_constr mu stops growing, the multipliers still relax -- followed by the
+// one-knot shift of every multiplier set, in place.  One workgroup of AL_STEP_THREADS lanes per trajectory; the lanes run along
+// the contiguous rows of trajectory b ([N][2m], then [N+1][K], then the pose slots' [N+1][Kp]: ps as k_al_update_state takes it,
+// geo null: none) in tiles of AL_STEP_TILE doubles, a pair per lane.
+//   pass 1: mv = max g over every row (the rows' inputs only: controls, poses, geometry), a wave reduction and one over the
 //           group's waves in LDS; mu_new follows from it;
 //   pass 2: g again (the same loads, from cache) with the multipliers, read and written once: al_row_update, then the store at
 //           the shifted place.
@@ -6523,19 +6524,21 @@ __global__ __launch_bounds__(AL_STEP_THREADS) void k_al_mpc_step(
     int Bp, int N, int m, int K, const double* __restrict__ xs_q, const double* __restrict__ us, const double* __restrict__ lb,
     const double* __restrict__ ub, double* __restrict__ lam, double* __restrict__ imu, const double* __restrict__ geo,
     size_t geo_stride, unsigned kinds, double* __restrict__ olam, double* __restrict__ oimu, double* __restrict__ mu,
-    double mu_scale, double mu_max, double tol_constr, double* __restrict__ maxviol, int shift) {
+    double mu_scale, double mu_max, double tol_constr, double* __restrict__ maxviol, int shift, AlPose ps) {
   __shared__ double red[AL_STEP_THREADS / 64];
   const int b = blockIdx.x;
-  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride, kinds};
-  const int W = 2 * m, nb = lb ? N * W : 0, no = geo ? (N + 1) * K : 0;
+  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride, kinds, ps.geo, ps.stride, ps.kinds};
+  const int W = 2 * m, nb = lb ? N * W : 0, no = geo ? (N + 1) * K : 0, Kp = ps.K, np = ps.geo ? (N + 1) * Kp : 0;
   const double mu_old = mu[b];
   double mv = lb ? 0.0 : -INFINITY;
   for (int e = threadIdx.x; e < nb; e += AL_STEP_THREADS) mv = fmax(mv, R.g_box(e / W, e % W));
   for (int e = threadIdx.x; e < no; e += AL_STEP_THREADS) mv = fmax(mv, R.g_sphere(e / K, e % K));
+  for (int e = threadIdx.x; e < np; e += AL_STEP_THREADS) mv = fmax(mv, R.g_pose(e / Kp, e % Kp));
   mv = al_group_max(mv, red);
   const double mu_new = (mv < tol_constr) ? mu_old : fmin(mu_old * mu_scale, mu_max);
   if (nb) al_step_rows(lam + (size_t)b * nb, imu + (size_t)b * nb, nb, W, mu_new, shift, [&](int e) { return R.g_box(e / W, e % W); });
   if (no) al_step_rows(olam + (size_t)b * no, oimu + (size_t)b * no, no, K, mu_new, shift, [&](int e) { return R.g_sphere(e / K, e % K); });
+  if (np) al_step_rows(ps.lam + (size_t)b * np, ps.imu + (size_t)b * np, np, Kp, mu_new, shift, [&](int e) { return R.g_pose(e / Kp, e % Kp); });
   if (threadIdx.x == 0) {
     if (maxviol) maxviol[b] = mv;
     mu[b] = mu_new;
@@ -6622,13 +6625,16 @@ extern "C" int tolg_set_al_obstacle_kinds(tolg_handle_t h, int32_t K, const int3
   return 0;
 }
 
-// Pose constraints (tilt cone, view cone): the second slot family.  d_geo [B][src knots][K][4] into [knots][4K][Bp] as
+// Pose constraints (tilt cone, view cone): the second slot family.  d_geo [B][src_knots][K][4] into [knots][4K][Bp] as
 // k_pack_obstacles_moving packs the position slots (knots = 1: the static form, `stride` 0; N + 1: the per-knot form, `stride`
-// 4 K Bp; padded trajectories replicate B-1).  Thread 0 points the constants at the geometry, the caller's multipliers and the
-// kind word, and with clear_obs -- no position slots attached -- zeroes their count, which the PT_OBS forms read beside this one.
+// 4 K Bp; padded trajectories replicate B-1), with its source knots: knot i from source knot i (t < 0: src_knots = knots), or
+// gathered from a world-time path of src_knots = T + 1 knots (tolg_set_al_pose_constraint_windows, t >= 0): source knot
+// min(t0[b] + t + i, T), t0 = null: 0 -- window_knot, the packed bits of the per-knot form on host-sliced windows.  Thread 0
+// points the constants at the geometry, the caller's multipliers and the kind word, and with clear_obs -- no position slots
+// attached -- zeroes their count, which the PT_OBS forms read beside this one.
 __global__ void k_pack_pose_constraints(int B, int Bp, int K, int knots, size_t stride, const double* __restrict__ geo,
-                                        const double* lam, const double* imu, double* __restrict__ w, Consts* c, unsigned kinds,
-                                        int clear_obs) {
+                                        int src_knots, const int* __restrict__ t0, int t, const double* lam, const double* imu,
+                                        double* __restrict__ w, Consts* c, unsigned kinds, int clear_obs) {
   size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t knot = (size_t)4 * K * Bp;
   if (g == 0) {
@@ -6639,7 +6645,9 @@ __global__ void k_pack_pose_constraints(int B, int Bp, int K, int knots, size_t 
   const size_t i = g / knot, r = g % knot;
   const int b = (int)(r % Bp), f = (int)(r / Bp);
   const int bs = b < B ? b : B - 1;
-  w[g] = geo[((size_t)bs * knots + i) * 4 * K + f];
+  size_t src = i;
+  if (t >= 0) src = window_knot(t0, bs, t, (long long)i, src_knots - 1);
+  w[g] = geo[((size_t)bs * src_knots + src) * 4 * K + f];
 }
 static size_t pose_constraints_bytes_for(const tolg_problem* p, int B, int K, int per_knot) {
   return (size_t)(per_knot ? p->N + 1 : 1) * 4 * K * (size_t)padded_batch(B) * sizeof(double);
@@ -6649,9 +6657,11 @@ extern "C" size_t tolg_pose_constraints_bytes(const tolg_problem* prob, int32_t 
   return pose_constraints_bytes_for(prob, max_batch, K, per_knot != 0);
 }
 // d_geo = null detaches.  The held policy stays: its gains belong to the problem that was solved.
-extern "C" int tolg_set_al_pose_constraints(tolg_handle_t h, int32_t B, int32_t K, const int32_t* kinds, const double* d_geo,
-                                            int32_t per_knot, const double* d_lambda, const double* d_imu, void* d_packed,
-                                            size_t packed_bytes, void* stream) {
+// The window form (tolg_set_al_pose_constraint_windows) is the per-knot one gathered from a path of T + 1 knots at step t >= 0
+// (the others: t = -1).
+static int set_pose_constraints(tolg_handle_t h, int B, int K, const int32_t* kinds, const double* d_geo, int per_knot,
+                                const double* d_lambda, const double* d_imu, void* d_packed, size_t packed_bytes, void* stream,
+                                int T = 0, const int32_t* d_t0 = nullptr, int t = -1) {
   if (!h || h->running) return TOLG_E_ARG;
   Held& r = h->posec;
   if (!d_geo) {
@@ -6674,13 +6684,26 @@ extern "C" int tolg_set_al_pose_constraints(tolg_handle_t h, int32_t B, int32_t 
   const int Bp = padded_batch(B), knots = per_knot ? h->prob.N + 1 : 1;
   const size_t knot = (size_t)4 * K * Bp;
   hipLaunchKernelGGL(k_pack_pose_constraints, dim3((unsigned)((knots * knot + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), B, Bp, K, knots, per_knot ? knot : (size_t)0, d_geo, d_lambda, d_imu,
-                     static_cast<double*>(d_packed), const_cast<Consts*>(h->P.c), word, h->pt[H_OBS].p ? 0 : 1);
+                     static_cast<hipStream_t>(stream), B, Bp, K, knots, per_knot ? knot : (size_t)0, d_geo, t >= 0 ? T + 1 : knots,
+                     reinterpret_cast<const int*>(d_t0), t, d_lambda, d_imu, static_cast<double*>(d_packed),
+                     const_cast<Consts*>(h->P.c), word, h->pt[H_OBS].p ? 0 : 1);
   LAUNCH_CHECK();
   h->pose_K = K; h->pose_kinds = word; h->pose_stride = per_knot ? knot : 0;
   h->pose_lam = const_cast<double*>(d_lambda); h->pose_imu = const_cast<double*>(d_imu);
   hold(h, r, d_packed, B);
   return 0;
+}
+extern "C" int tolg_set_al_pose_constraints(tolg_handle_t h, int32_t B, int32_t K, const int32_t* kinds, const double* d_geo,
+                                            int32_t per_knot, const double* d_lambda, const double* d_imu, void* d_packed,
+                                            size_t packed_bytes, void* stream) {
+  return set_pose_constraints(h, B, K, kinds, d_geo, per_knot != 0, d_lambda, d_imu, d_packed, packed_bytes, stream);
+}
+extern "C" int tolg_set_al_pose_constraint_windows(tolg_handle_t h, int32_t B, int32_t K, const int32_t* kinds,
+                                                   const double* d_path_geo, int32_t T, const int32_t* d_t0, int32_t t,
+                                                   const double* d_lambda, const double* d_imu, void* d_packed,
+                                                   size_t packed_bytes, void* stream) {
+  if (d_path_geo && (T < 1 || t < 0)) return TOLG_E_ARG;
+  return set_pose_constraints(h, B, K, kinds, d_path_geo, 1, d_lambda, d_imu, d_packed, packed_bytes, stream, T, d_t0, t);
 }
 
 // the box of the call's own arguments, no geometry (Bp, K = 0: nothing reads them)
@@ -6713,22 +6736,34 @@ extern "C" int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_
   return 0;
 }
 
-// tolg_al_update_state's conditions, and: not during a solve (the solve reads the multipliers this call moves)
-extern "C" int tolg_al_mpc_step(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu,
-                                double mu_scale, double mu_max, double tol_constr, double* d_maxviol, int32_t shift,
-                                void* stream) {
+// tolg_al_update_state's conditions, and: not during a solve (the solve reads the multipliers this call moves).  with_pose:
+// tolg_al_mpc_step_pose, which takes the pose slots as the third row set; tolg_al_mpc_step keeps the contract it had before the
+// step knew them and refuses while the family is attached -- refused, never ignored.
+static int al_mpc_step(tolg_handle_t h, int B, const double* d_xs_q, const double* d_us, double* d_mu, double mu_scale,
+                       double mu_max, double tol_constr, double* d_maxviol, int shift, void* stream, bool with_pose) {
   if (!h || h->running || B < 1 || B > h->max_batch || !d_mu || (shift != 0 && shift != 1)) return TOLG_E_ARG;
-  if (h->posec.p) return TOLG_E_ARG;  // pose constraints have no receding-horizon step: refused, never ignored
-  const Held& obs = h->pt[H_OBS];
-  if (!h->al_lb && !obs.p) return TOLG_E_ARG;     // nothing attached to update
+  if (h->posec.p && !with_pose) return TOLG_E_ARG;
+  const Held &obs = h->pt[H_OBS], &pose = h->posec;
+  if (!h->al_lb && !obs.p && !pose.p) return TOLG_E_ARG;     // nothing attached to update
   if (h->al_lb && !d_us) return TOLG_E_ARG;
   if (obs.p && (B != obs.B || !d_xs_q)) return TOLG_E_ARG;
+  if (pose.p && (B != pose.B || !d_xs_q)) return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_mpc_step, dim3(B), dim3(AL_STEP_THREADS), 0, static_cast<hipStream_t>(stream), padded_batch(B), h->prob.N,
                      h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
                      const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_kinds, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
-                     d_maxviol, (int)shift);
+                     d_maxviol, shift, AlPose{pose.p, h->pose_stride, h->pose_kinds, h->pose_K, h->pose_lam, h->pose_imu});
   LAUNCH_CHECK();
   return 0;
+}
+extern "C" int tolg_al_mpc_step(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu,
+                                double mu_scale, double mu_max, double tol_constr, double* d_maxviol, int32_t shift,
+                                void* stream) {
+  return al_mpc_step(h, B, d_xs_q, d_us, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, shift, stream, false);
+}
+extern "C" int tolg_al_mpc_step_pose(tolg_handle_t h, int32_t B, const double* d_xs_q, const double* d_us, double* d_mu,
+                                     double mu_scale, double mu_max, double tol_constr, double* d_maxviol, int32_t shift,
+                                     void* stream) {
+  return al_mpc_step(h, B, d_xs_q, d_us, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, shift, stream, true);
 }
 
 extern "C" int tolg_linearize_backward(tolg_handle_t h, int32_t ms, double max_reg, int32_t B, const double* d_xs_q,

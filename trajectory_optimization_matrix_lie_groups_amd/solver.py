@@ -232,6 +232,8 @@ class MPCResult:
     mu: Optional[torch.Tensor] = None             # [B] the penalty the loop ended with
     # ... with spheres: min_k |t_s - c_k(s)| - r_k(s) of the realised states at their world knots (negative: inside one)
     clearance: Optional[torch.Tensor] = None      # [B, steps+1]
+    # mpc(pose_constraints=, pose_paths=): min_k pose_margin of the realised states at their world knots (negative: outside a cone)
+    pose_margin: Optional[torch.Tensor] = None    # [B, steps+1]
 
 
 def check_box(u_lb, u_ub, B, m, so3=False):
@@ -407,6 +409,45 @@ def inflate_obstacles(obstacles, xs_q, pos_cov, kappa, kinds=None):
     return out
 
 
+def tighten_pose_constraints(slots, kinds, xs_q, Sigma, kappa):
+    """Pose slots with a margin for the closed-loop spread, the pose family's inflate_obstacles: slots [K, 4], [B, K, 4] or
+    [B, N+1, K, 4] of `kinds` (check_pose_kinds), xs_q [B, N+1, 4, 4] the nominal plan, Sigma [B, N+1, 12, 12] its covariance
+    (policy_covariance(full=True).Sigma), whose pose block Sigma[..., :6, :6] is in the error coordinates X Exp(delta), delta =
+    [omega, v], of the rows' gradients g_x = [g_omega, g_v] (include/tolg.h has the table).  With sigma_ik = sqrt(g_x^T
+    Sigma_pose g_x) at the nominal pose -- one standard deviation of the row to first order -- a tilt cone gets the cosine c +
+    kappa sigma, a view cone c + kappa sigma / |b|: its row is |b| times the gap of the cosines, b = R^T (p - t), so that is
+    kappa standard deviations of the margin (exactly so, to first order, for a pose on the cone; off it the row's gradient and
+    the margin's differ by (c - cos) along the line of sight).  Returns [B, N+1, K, 4] (numpy), the per-knot form
+    al_fit_batch(pose_constraints=) and mpc(pose_paths=) take.  ValueError where a cosine reaches 1: no cone is left."""
+    host = lambda a: np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)  # noqa: E731
+    x, cov, o = host(xs_q), host(Sigma), host(slots)
+    if x.ndim != 4 or x.shape[-2:] != (4, 4):
+        raise ValueError("tighten_pose_constraints: xs_q has shape %s, expected (B, N+1, 4, 4)" % (x.shape,))
+    B, N1 = x.shape[:2]
+    if o.ndim in (2, 3):
+        o = np.broadcast_to(o if o.ndim == 2 else o[:, None], (B, N1) + o.shape[-2:])
+    if o.ndim != 4 or o.shape[:2] != (B, N1) or o.shape[-1] != 4 or cov.shape != (B, N1, 12, 12):
+        raise ValueError("tighten_pose_constraints: slots %s and Sigma %s do not fit xs_q [%d, %d, 4, 4]" % (o.shape, cov.shape, B, N1))
+    kd = check_pose_kinds(kinds, o.shape[2])
+    R, t = x[..., :3, :3], x[..., :3, 3]
+    e1, e3 = np.array([1.0, 0.0, 0.0]), np.array([0.0, 0.0, 1.0])
+    out = o.copy()
+    for k, kind in enumerate(kd):
+        f, c = o[:, :, k, :3], o[:, :, k, 3]
+        if kind == _capi.POSE_TILT_CONE:
+            a = np.einsum("biac,bia->bic", R, f)                    # R^T n
+            gx, scale = np.concatenate([np.cross(a, e3), np.zeros_like(a)], axis=-1), 1.0
+        else:
+            b = np.einsum("biac,bia->bic", R, f - t)                # R^T (p - t)
+            nb = np.linalg.norm(b, axis=-1)
+            gx, scale = np.concatenate([np.cross(b, e1), e1 - (c / nb)[..., None] * b], axis=-1), 1.0 / nb
+        var = np.einsum("bia,biac,bic->bi", gx, cov[:, :, :6, :6], gx)
+        out[:, :, k, 3] = c + float(kappa) * np.sqrt(np.maximum(var, 0.0)) * scale
+    if np.any(out[..., 3] >= 1.0):
+        raise ValueError("tighten_pose_constraints: a cosine reaches 1 once kappa sigma is added: no cone is left")
+    return out
+
+
 def mpc_window_index(t0, t, N, T):
     """Knot of the path that knot i of step t's window tracks (tolg_set_ref_windows): min(t0[b] + t + i, T), [B, N+1]."""
     t0 = np.asarray(t0, dtype=np.int64).reshape(-1)
@@ -448,9 +489,9 @@ def _checked(name, a, shape, finite=False):
 _POLICY = {"tolg_solve_begin": "clear", "tolg_solve_begin_warm": "clear", "tolg_eval_knot": "clear",
            "tolg_solve_batch": "clear hold", "tolg_linearize_backward": "clear hold", "tolg_solve_end": "hold",
            "tolg_set_al_obstacles": "", "tolg_set_al_obstacles_moving": "",
-           "tolg_al_update_state": "", "tolg_al_mpc_step": "",
+           "tolg_al_update_state": "", "tolg_al_mpc_step": "", "tolg_al_mpc_step_pose": "",
            "tolg_set_al_obstacle_windows": "", "tolg_set_al_obstacle_kinds": "",
-           "tolg_set_al_pose_constraints": ""}  # (the last seven leave it: listed for completeness)
+           "tolg_set_al_pose_constraints": "", "tolg_set_al_pose_constraint_windows": ""}  # (the last nine leave it: listed for completeness)
 # A setter's detach call (BatchedTrackingILQR._detach): its arguments behind the handle with the source pointer null, the
 # stream's place included.  tolg_set_al_obstacles detaches the per-knot form too.
 _DETACH = {"tolg_set_refs": (0, None, None, None, 0, None), "tolg_set_weights": (0, None, None, None, None, 0, None),
@@ -1041,7 +1082,8 @@ class BatchedTrackingILQR:
         n, g = c - n^T R e3.  A view cone has fields (px, py, pz, c): keep the world target p within acos(c) of the forward
         axis e1, g = c |b| - e1^T b with b = R^T (p - t).  lam, imu [B, N+1, K]: the multipliers and the diagonal of I_mu
         (device tensors the handle reads in every solve until they are detached; None: zeros).  Every batch call must then
-        be for this B; mpc() and plan_fleet refuse while the family is attached."""
+        be for this B; mpc() and plan_fleet take pose slots of their own (pose_constraints=) and refuse a family the caller
+        attached here."""
         if slots is None:
             self._pose = None
             self._detach("tolg_set_al_pose_constraints")
@@ -1056,12 +1098,56 @@ class BatchedTrackingILQR:
         self._call("tolg_set_al_pose_constraints", B, K, (C.c_int32 * K)(*kinds), _ptr(d), int(per_knot), _ptr(lam), _ptr(imu), *dest)
         self._pose = (d, lam, imu, kinds)  # the handle reads the multipliers in every solve until they are detached
 
+    def _check_pose_paths(self, B, path_slots, kinds):
+        """World-time pose slots [B, T+1, K, 4] checked on the host under _check_pose_constraints' rules (T >= 1 in place of the
+        horizon), the geometry over the whole path.  As _check_obstacle_paths, a tensor that is on the solver's device already is
+        checked there (check_pose_geometry's reductions) and never copied through the host.  B = None takes it from the array.
+        Returns (B, the paths: that device tensor, or a float64 numpy array, kinds)."""
+        if self.problem.kind in ("so3", "pendulum3d"):
+            raise ValueError("pose constraints are not offered for the %s model" % self.problem.kind)
+        on_device = isinstance(path_slots, torch.Tensor) and path_slots.device == self.device
+        a = _checked("pose_paths", path_slots, (B, None, None, 4), finite=not on_device)
+        if a.shape[1] < 2:
+            raise ValueError("pose_paths has %d knots, expected T+1 >= 2" % a.shape[1])
+        if not 1 <= a.shape[2] <= _capi.MAX_POSE_CONSTRAINTS:
+            raise ValueError("pose_paths: K = %d slots per trajectory, expected 1..%d" % (a.shape[2], _capi.MAX_POSE_CONSTRAINTS))
+        if not 1 <= a.shape[0] <= self.max_batch:
+            raise ValueError("pose_paths for B = %d trajectories, expected 1..%d" % (a.shape[0], self.max_batch))
+        kinds = check_pose_kinds(kinds, a.shape[2])
+        check_pose_geometry("pose_paths", a.detach() if on_device else a, kinds)
+        return a.shape[0], a if on_device else np.ascontiguousarray(a), kinds
+
+    def _set_pose_windows(self, B, d_paths, t0_d, t, lam, imu, kinds):
+        K, T = d_paths.shape[2], d_paths.shape[1] - 1
+        self._call("tolg_set_al_pose_constraint_windows", B, K, (C.c_int32 * K)(*kinds), _ptr(d_paths), int(T), _ptr(t0_d), int(t),
+                   _ptr(lam), _ptr(imu), *self._packed("_pose_knot_buf", self.lib.tolg_pose_constraints_bytes, K, 1, B=B))
+        self._pose = (d_paths, lam, imu, kinds)
+
+    def set_al_pose_constraint_windows(self, path_slots, t, t0=None, kinds=None, lam=None, imu=None):
+        """Attach the pose slots of step t, gathered on the device from world-time paths (tolg_set_al_pose_constraint_windows):
+        path_slots [B, T+1, K, 4], the fields of trajectory b's slots at world knot s (a view target that moves in world time);
+        knot i of the window takes world knot min(t0[b] + t + i, T), set_ref_windows' rule (t0 an int array [B], None: 0).  The
+        handle is then as after set_al_pose_constraints with the gathered [B, N+1, K, 4] slots; kinds, lam, imu [B, N+1, K] as
+        there, the geometry checked over the whole path (check_pose_geometry).  path_slots = None detaches."""
+        if path_slots is None:
+            return self.set_al_pose_constraints(None)
+        if int(t) < 0:
+            raise ValueError("t must be non-negative")
+        B, a, kinds = self._check_pose_paths(None if lam is None else int(lam.shape[0]), path_slots, kinds)
+        lam, imu = self._obs_multipliers(B, a.shape[2], lam, imu)
+        t0_d = self._check_t0(B, t0)
+        d = self._dev(a, a.shape)
+        self._hold((d, t0_d))
+        self._set_pose_windows(B, d, t0_d, int(t), lam, imu, kinds)
+
     def al_mpc_step(self, xs_q, us, mu, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2, shift=True):
-        """The outer augmented-Lagrangian update of one MPC step over everything attached (tolg_al_mpc_step): the multipliers
-        of set_al / set_al_obstacles follow lambda <- max(0, lambda + I_mu g) on the controls us [B, N, m] and the positions of
-        xs_q [B, N+1, 4, 4] (device tensors; either may be None where nothing attached reads it), mu [B] (a float64 device
-        tensor, updated in place) grows by mu_scale up to mu_max where the largest g reaches tol_constr, and with shift both
-        multiplier sets then move one knot towards the start, the last knot held.  Nothing is sticky: a satisfied problem's
+        """The outer augmented-Lagrangian update of one MPC step over everything attached (tolg_al_mpc_step; with a pose family
+        attached through this object tolg_al_mpc_step_pose): the multipliers
+        of set_al / set_al_obstacles / set_al_pose_constraints follow lambda <- max(0, lambda + I_mu g) on the controls us
+        [B, N, m] and the poses of xs_q [B, N+1, 4, 4] (device tensors; either may be None where nothing attached reads it: the
+        spheres read the positions, the pose slots the whole pose), mu [B] (a float64 device tensor, updated in place) grows
+        by mu_scale up to mu_max where the largest g reaches tol_constr, and with shift every multiplier set then moves one
+        knot towards the start, the last knot held.  Nothing is sticky: a satisfied problem's
         multipliers still relax.  The held policy is left alone.  Returns max_violation [B]."""
         if not isinstance(mu, torch.Tensor) or mu.dtype != torch.float64 or mu.device != self.device or mu.dim() != 1 \
                 or not mu.is_contiguous():
@@ -1075,7 +1161,8 @@ class BatchedTrackingILQR:
         return maxviol
 
     def _al_step(self, B, xs_q, us, mu, mu_scale, mu_max, tol_constr, maxviol, shift):
-        self._call("tolg_al_mpc_step", B, _ptr(xs_q), _ptr(us), _ptr(mu), float(mu_scale), float(mu_max), float(tol_constr),
+        # (tolg_al_mpc_step keeps refusing a pose family: the step that takes it as a third row set is a call of its own)
+        self._call("tolg_al_mpc_step_pose" if self._pose is not None else "tolg_al_mpc_step", B, _ptr(xs_q), _ptr(us), _ptr(mu), float(mu_scale), float(mu_max), float(tol_constr),
                    _ptr(maxviol), int(bool(shift)))
 
     def al_fit_batch(self, x0_q, x0_xi, us_init, lb=None, ub=None, n_al_iters=100, n_ilqr_iters=200, tol_grad_norm=1e-6,
@@ -1180,7 +1267,7 @@ class BatchedTrackingILQR:
         return final, info
 
     def plan_fleet(self, x0_q, x0_xi, us_init, q_ref, xi_ref, fleet, separation, obstacles=None, lb=None, ub=None,
-                   obstacle_kinds=None, pose_scale=None, **al_kw):
+                   obstacle_kinds=None, pose_scale=None, pose_constraints=None, pose_kinds=None, **al_kw):
         """Prioritised planning for F = B / fleet independent fleets in one batch: trajectory b is member p = b % fleet of
         fleet b // fleet.  Round p = 0 .. fleet-1 solves the F members p, each on its own reference (q_ref [B, N+1, 4, 4],
         xi_ref [B, N+1, 6]), keeping out of the caller's static `obstacles` ([K0, 4] or [B, K0, 4]) and of p moving spheres of
@@ -1191,13 +1278,17 @@ class BatchedTrackingILQR:
         A lower-priority member yields to a higher one: member 0 plans as if alone, and whether member p finds a way round the
         others is its own round's convergence.  K0 + fleet - 1 <= MAX_OBSTACLES.  obstacle_kinds: the kinds of the caller's K0
         static slots (set_al_obstacles' kinds=); the member spheres behind them are keep-out spheres.  pose_scale: a per-knot
-        schedule on the pose weights in batch order (fit_batch's; every round takes its members' rows).
+        schedule on the pose weights in batch order (fit_batch's; every round takes its members' rows).  pose_constraints /
+        pose_kinds: pose slots in batch order ([K, 4], [B, K, 4] or per knot [B, N+1, K, 4]; al_fit_batch's), every round takes
+        its members' rows, and a round that would be a plain fit_batch is an al_fit_batch on them; a family the caller attached
+        beforehand (set_al_pose_constraints) is refused.
         Returns (FitResult in batch order, info): min_separation [F] the smallest centre distance over knots and pairs of
         the final plans (inf for fleet = 1), max_violation [B], al_converged [B] int32 (rounds without a constraint: 0 and
         1), outer_iterations [fleet] (python ints)."""
         G = int(fleet)
-        if self._pose is not None or al_kw.get("pose_constraints") is not None or al_kw.get("pose_kinds") is not None:
-            raise ValueError("plan_fleet with pose constraints is not supported: the rounds solve sub-batches")
+        if self._pose is not None:
+            raise ValueError("plan_fleet under pose constraints the caller attached is not supported (the rounds solve "
+                             "sub-batches): detach them with set_al_pose_constraints(None) and give pose_constraints=")
         x0_q, x0_xi = (a if hasattr(a, "shape") else np.asarray(a, dtype=np.float64) for a in (x0_q, x0_xi))
         B = int(x0_q.shape[0])
         if G < 1 or B % G != 0:
@@ -1218,6 +1309,9 @@ class BatchedTrackingILQR:
         if K0 + G - 1 > _capi.MAX_OBSTACLES:
             raise ValueError("plan_fleet: %d spheres + %d other members exceed %d spheres per trajectory"
                              % (K0, G - 1, _capi.MAX_OBSTACLES))
+        if pose_constraints is None and pose_kinds is not None:
+            raise ValueError("pose_kinds describe pose_constraints: none were given")
+        pose = None if pose_constraints is None else self._check_pose_constraints(B, pose_constraints, pose_kinds)[1:]
         if us_init is None:
             us_init = np.zeros((B, self.N, self.m))
         per = {k: al_kw.pop(k) for k in ("Q", "P", "R") if k in al_kw}
@@ -1232,7 +1326,9 @@ class BatchedTrackingILQR:
             field = [] if static is None else [np.broadcast_to(static[sl][:, None], (F, self.N + 1, K0, 4))]
             for t in pos:  # the members before p: [F, N+1, 3] each
                 field.append(np.concatenate([t, np.full((F, self.N + 1, 1), float(separation))], axis=-1)[:, :, None])
-            if not pos and static is None and lb is None:
+            if pose is not None:
+                kw.update(pose_constraints=pose[0][sl], pose_kinds=pose[1])
+            if not pos and static is None and lb is None and pose is None:
                 o = {k: al_kw[k] for k in ("tol_grad_norm", "tol_d_norm", "line_search") if k in al_kw}
                 res = self.fit_batch(x0_q[sl], x0_xi[sl], us_init[sl], mode="ms", n_iterations=al_kw.get("n_ilqr_iters", 200),
                                      **o, **kw)
@@ -1741,7 +1837,8 @@ class BatchedTrackingILQR:
             warm="states", noise=None, mode="ms", line_search=False, rollout="nonlinear", tol_grad_norm=1e-6, tol_d_norm=1e-6,
             check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None, plant_J=None, plant_pend=None, u_lb=None,
             u_ub=None, lb=None, ub=None, obstacles=None, obstacle_paths=None, obstacle_kinds=None, first_al_iters=3,
-            al_iters_per_step=1, mu0=1e-2, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2, pose_scale_path=None) -> MPCResult:
+            al_iters_per_step=1, mu0=1e-2, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2, pose_scale_path=None,
+            pose_constraints=None, pose_paths=None, pose_kinds=None) -> MPCResult:
         """Receding-horizon MPC: `steps` closed-loop steps of B trajectories, each tracking its own path from its own phase.
         Step t: windows min(t0[b] + t + i, T) of the paths (tolg_set_ref_windows), a solve of first_iters (t = 0) or
         iters_per_step iterations, then tolg_mpc_advance applies u*_0, steps the plant with the exact dynamics and adds the
@@ -1764,12 +1861,16 @@ class BatchedTrackingILQR:
         [m], the input box of set_al (the SO3 family takes the box only); obstacles [K, 4] or [B, K, 4], static keep-out
         spheres, or obstacle_paths [B, T_o+1, K, 4], spheres in world time indexed with the same t0 (window t is gathered by
         tolg_set_al_obstacle_windows); at most one of the two; obstacle_kinds: the kind of each of their K slots
-        (set_al_obstacles' kinds=; the clearance is then each kind's own).  Step t then runs first_al_iters (t = 0) or al_iters_per_step
+        (set_al_obstacles' kinds=; the clearance is then each kind's own); pose_constraints [K, 4] or [B, K, 4], static pose slots
+        (tilt cones, view cones: set_al_pose_constraints), or pose_paths [B, T_p+1, K, 4], pose slots in world time indexed with
+        the same t0 (window t is gathered by tolg_set_al_pose_constraint_windows); at most one of the two, pose_kinds with
+        either; alone or beside the others, not for the SO3 family; the rounds then end in tolg_al_mpc_step_pose.  Step t then runs first_al_iters (t = 0) or al_iters_per_step
         outer rounds: each a solve as above followed by tolg_al_mpc_step, which shifts the multipliers by one knot behind the
         step's last round; round 0 starts as above, round a > 0 from round a-1's solution under the `warm` rule.  The
         multipliers start at lambda = 0, I_mu = mu = mu0 (mu_scale, mu_max, tol_constr: al_fit_batch's).  The result carries
         max_violation [B, steps] (each step's last round), mu [B] and, with spheres, clearance [B, steps+1] of the realised
-        states.  iters and status are those of each step's last round."""
+        states, with pose slots pose_margin [B, steps+1], the smallest pose_margin() of each realised state under the slots of
+        its world knot t0[b] + s (pose_paths: held past the path's end).  iters and status are those of each step's last round."""
         if self._al is not None:
             raise ValueError("mpc under an augmented-Lagrangian constraint is not supported: detach it with set_al(None)")
         if self._obs is not None:
@@ -1792,7 +1893,12 @@ class BatchedTrackingILQR:
             raise ValueError("give obstacles (static) or obstacle_paths (world time), not both")
         if obstacle_kinds is not None and obstacles is None and obstacle_paths is None:
             raise ValueError("obstacle_kinds describe obstacles: none were given")
-        constrained = lb is not None or obstacles is not None or obstacle_paths is not None
+        if pose_constraints is not None and pose_paths is not None:
+            raise ValueError("give pose_constraints (static) or pose_paths (world time), not both")
+        if pose_kinds is not None and pose_constraints is None and pose_paths is None:
+            raise ValueError("pose_kinds describe pose_constraints or pose_paths: none were given")
+        posed = pose_constraints is not None or pose_paths is not None
+        constrained = lb is not None or obstacles is not None or obstacle_paths is not None or posed
         if constrained and mode != "ms":
             raise ValueError("the augmented-Lagrangian constraints need mode='ms'")
         if constrained and (int(first_al_iters) < 1 or int(al_iters_per_step) < 1):
@@ -1818,7 +1924,15 @@ class BatchedTrackingILQR:
             noise = self._dev(np.ascontiguousarray(noise.transpose(1, 0, 2)), (steps, B, 6))  # step t: one contiguous [B, 6]
         f64 = dict(dtype=torch.float64, device=self.device)
         # the planner's constraints, checked before anything is attached: (lb, ub, lam, imu), (geometry, lam, imu, in world time)
-        al = obs = mu = maxviol = None
+        al = obs = pose = mu = maxviol = None
+        if posed:  # (slots, lam, imu, in world time, kinds)
+            slots, pkinds = (self._check_pose_constraints(B, pose_constraints, pose_kinds)[1:] if pose_constraints is not None else
+                             self._check_pose_paths(B, pose_paths, pose_kinds)[1:])
+            if pose_constraints is not None and slots.ndim != 3:
+                raise ValueError("mpc: pose_constraints are static, [K, 4] or [B, K, 4]; slots that move are pose_paths")
+            Kp = slots.shape[-2]
+            pose = (self._dev(slots, slots.shape), torch.zeros(B, self.N + 1, Kp, **f64),
+                    torch.full((B, self.N + 1, Kp), float(mu0), **f64), pose_paths is not None, pkinds)
         if lb is not None:
             al = (self._dev(_checked("lb", lb, (self.m,)), (self.m,)), self._dev(_checked("ub", ub, (self.m,)), (self.m,)),
                   torch.zeros(B, self.N, 2 * self.m, **f64), torch.full((B, self.N, 2 * self.m), float(mu0), **f64))
@@ -1847,12 +1961,14 @@ class BatchedTrackingILQR:
         try:
             # the plant survives the solves of the loop (tolg_set_plant): set once, detached behind it
             d_plant = self._use_plant(B, plant)
-            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box, al, obs, mu, maxviol, spath))
+            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box, al, obs, pose, mu, maxviol, spath))
             self._use_pt(B, None, b.wts)
             if al is not None:
                 self.set_al(*al)
             if obs is not None and not obs[3]:
                 self.set_al_obstacles(*obs[:3], kinds)
+            if pose is not None and not pose[3]:
+                self.set_al_pose_constraints(pose[0], pose[4], pose[1], pose[2])
             if constrained:
                 res.max_violation, res.mu = torch.empty(B, steps, **f64), mu
             for t in range(steps):
@@ -1861,6 +1977,8 @@ class BatchedTrackingILQR:
                     self._set_pose_schedule(B, (spath[0], spath[1], t0_d, t))
                 if obs is not None and obs[3]:
                     self._set_obstacle_windows(B, obs[0], t0_d, t, obs[1], obs[2], kinds)
+                if pose is not None and pose[3]:
+                    self._set_pose_windows(B, pose[0], t0_d, t, pose[1], pose[2], pose[4])
                 n = K0 if t == 0 else K
                 o = self._options(mode, n, line_search, rollout, tol_grad_norm, tol_d_norm, max_reg)
                 xs = None
@@ -1907,6 +2025,14 @@ class BatchedTrackingILQR:
                 else:
                     d = (res.xs_q[:, :, None, :3, 3] - geo[..., :3]).norm(dim=-1) - geo[..., 3]
                 res.clearance = d.amin(dim=-1)
+            if pose is not None:  # likewise: on the device tensors, the slots of world knot t0[b] + s
+                geo = pose[0]
+                if pose[3]:
+                    s = torch.arange(steps + 1, device=self.device)[None, :] + (0 if t0_d is None else t0_d.long()[:, None])
+                    geo = geo[torch.arange(B, device=self.device)[:, None], s.clamp(max=geo.shape[1] - 1).expand(B, steps + 1)]
+                else:
+                    geo = geo[:, None]
+                res.pose_margin = pose_margin(res.xs_q, geo, pose[4]).amin(dim=-1)
         finally:
             self._use_pt(B, None, None)
             if plant is not None:
@@ -1915,6 +2041,8 @@ class BatchedTrackingILQR:
                 self.set_al(None)
             if self._obs is not None:
                 self.set_al_obstacles(None)
+            if self._pose is not None:
+                self.set_al_pose_constraints(None)
         return res
 
     # ------------------------------------------------------------------------------------------

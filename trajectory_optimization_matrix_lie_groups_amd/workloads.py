@@ -560,6 +560,57 @@ def se3_mpc_obstacles(B, steps, N=200, K=1, seed=SEED, **mpc_kw):
     return prob, x0_q, x0_xi, path_q, path_xi, t0, noise, obs, mov
 
 
+def se3_mpc_inspection(B, steps, N=200, seed=SEED, **mpc_kw):
+    """se3_mpc's inputs (mpc_kw: its T, R and sigmas) under se3_inspection's two pose slots per trajectory (kinds
+    INSPECTION_KINDS), stated in world time over the stretch of world knots t0[b] .. t0[b] + steps that the loop travels:
+      a tilt cone about world z, (0, 0, 1, c_s): behind a ramp-in of r = max(2, steps // 4) knots, c lies 0.2 above the smallest
+               n^T R e3 of trajectory b's path on the rest of the stretch (and at most 0.9; half-way from that smallest value
+               to 1 where the stretch is more upright than 0.9 throughout), so the path's most tilted knot there leaves the
+               cone, by up to 0.2.  A path moved by a rigid motion may be at its most tilted right where the loop
+               starts, so at world knot t0[b] (and before it) the cosine lies 0.1 below the smaller of the start's own n^T R e3
+               and the path's there (half-way to -1 where that is nearer), never above c, and rises to c linearly over the
+               ramp-in: the start is inside;
+      a view cone on a target that drifts along a world-time line, (p_s, c): p_s moves from 3 ahead of trajectory b's own start
+               pose (along its forward axis: on the cone's axis at the start) at world knot t0[b] to 3 ahead of the path's last
+               pose at world knot T, as se3_inspection's target runs to the end of its horizon -- every window of the loop looks
+               N knots ahead, and a target that stopped at the end of the stretch would be run over by the path behind it, where
+               the view row has no gradient -- and rests before t0[b]; the distance ahead, 3, grows by half until the target
+               keeps 1 away from the path at every world knot from t0[b] on; c lies a fifth of the way from the smallest e1^T b / |b|
+               of the second half of the stretch under that target to 1.
+    The reference path leaves both cones on the stretch in every trajectory; the start of every trajectory satisfies both at its
+    world knot.  Both are checkable with pose_margin (tests/test_pose_mpc_cpu.py).  Returns (prob, x0_q, x0_xi, path_q, path_xi, t0, noise, pose_paths [B, T+1, 2, 4], kinds): the
+    first seven are se3_mpc's, the last two what mpc(pose_paths=, pose_kinds=) takes."""
+    prob, x0_q, x0_xi, path_q, path_xi, t0, noise = se3_mpc(B, steps, N=N, seed=seed, **mpc_kw)
+    T = path_q.shape[1] - 1
+    slots = np.empty((B, T + 1, 2, 4))
+    s = np.arange(T + 1, dtype=np.float64)
+    ramp = max(2, steps // 4)
+    for b in range(B):
+        R, t, X0 = path_q[b, :, :3, :3], path_q[b, :, :3, 3], np.asarray(x0_q[b]).reshape(4, 4)
+        a, e = int(t0[b]), min(int(t0[b]) + steps, T)
+        if e - a <= ramp:
+            raise ValueError("se3_mpc_inspection: trajectory %d travels %d knots, the ramp-in alone takes %d" % (b, e - a, ramp))
+        m = R[:, 2, 2]
+        lo = m[a + ramp: e + 1].min()
+        c = min(lo + 0.2, max(0.9, 0.5 * (lo + 1.0)))
+        m_in = min(X0[2, 2], m[a])
+        c_in = min(c, m_in - min(0.1, 0.5 * (m_in + 1.0)))
+        slots[b, :, 0, :3] = (0.0, 0.0, 1.0)
+        slots[b, :, 0, 3] = c_in + np.clip((s - a) / ramp, 0.0, 1.0) * (c - c_in)
+        ahead = 3.0
+        while True:
+            p0, p1 = X0[:3, 3] + ahead * X0[:3, 0], t[T] + ahead * R[T][:, 0]
+            p = p0 + np.clip((s - a) / (T - a), 0.0, 1.0)[:, None] * (p1 - p0)
+            if np.linalg.norm(p[a:] - t[a:], axis=1).min() >= 1.0:
+                break
+            ahead *= 1.5
+        bv = np.einsum("iac,ia->ic", R, p - t)
+        cv = bv[:, 0] / np.linalg.norm(bv, axis=1)
+        late = cv[(a + e + 1) // 2: e + 1].min()
+        slots[b, :, 1, :3], slots[b, :, 1, 3] = p, late + 0.2 * (1.0 - late)
+    return prob, x0_q, x0_xi, path_q, path_xi, t0, noise, slots, INSPECTION_KINDS
+
+
 def se3_crossing_fleet(F, G, N=40, separation=0.3, seed=SEED):
     """F fleets of G members whose paths cross: member p tracks g_p q_ref, with g_p the rotation by p pi / G about world z
     through the reference's position at knot N // 2 plus a z shift of 0.3 separation p -- every pair of paths passes within
