@@ -342,8 +342,9 @@ int tolg_set_al_obstacles_moving(tolg_handle_t h, int32_t B, int32_t K, const do
  * From then on every batch entry point that adds the terms of the position slots adds these too and must be called with this B;
  * the handle runs the kernels it runs with position slots attached, whether any are or not.  tolg_al_update_state evaluates
  * the pose rows on the poses it is handed and moves these multipliers under its one rule, the one mu per problem, the joint
- * d_maxviol and d_al_converged.  tolg_eval_knot, the policy rollouts, the covariance and the value sweep ignore the family, as
- * they ignore the spheres.  tolg_al_mpc_step refuses while the family is attached; tolg_al_mpc_step_pose is the step that takes
+ * d_maxviol and d_al_converged.  tolg_eval_knot, the covariance and the value sweep ignore the family, as they ignore the
+ * spheres; the policy rollouts ignore it in J (the tracking cost alone) and report its margins where asked
+ * (tolg_policy_rollout_margins, tolg_policy_rollout_estimated_limited).  tolg_al_mpc_step refuses while the family is attached; tolg_al_mpc_step_pose is the step that takes
  * the pose rows as its third row set and shifts these multipliers with the others.  d_geo = NULL detaches.  The held policy is
  * left alone.
  * TOLG_E_ARG: K outside 1..TOLG_MAX_POSE_CONSTRAINTS, a kind outside 0..1, NULL kinds, multipliers or buffer, B < 1 or B >
@@ -479,7 +480,8 @@ int tolg_expected_change(tolg_handle_t h, int32_t form, int32_t B, double* d_ecc
  * tolg_create, tolg_solve_begin and tolg_solve_begin_warm clear it; so does tolg_eval_knot (it overwrites the nominal
  * trajectory).  tolg_rollout (writes the candidate arrays only), tolg_expected_change, tolg_set_al, tolg_al_update,
  * tolg_set_refs, tolg_set_ref_windows, tolg_set_weights, tolg_set_al_obstacles, tolg_al_update_state, tolg_mpc_advance,
- * tolg_policy_covariance, tolg_policy_value, tolg_policy_rollout_limited and tolg_mpc_advance_limited leave it; the calls that
+ * tolg_policy_covariance, tolg_policy_value, tolg_policy_rollout_limited, tolg_mpc_advance_limited,
+ * tolg_policy_rollout_margins and tolg_policy_rollout_estimated_limited leave it; the calls that
  * read it use the
  * references and weights set when they run.
  * Both calls return TOLG_E_ARG when no policy is held, during a solve in flight, for a B other than the held batch's, when
@@ -565,6 +567,37 @@ int tolg_policy_rollout_limited(tolg_handle_t h, int32_t B, int32_t S, const dou
 int tolg_mpc_advance_limited(tolg_handle_t h, int32_t B, const double* d_w, const double* d_u_lb, const double* d_u_ub,
                              double* d_x_next_q, double* d_x_next_xi, double* d_u_applied, double* d_xs_q_warm,
                              double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl, int32_t* d_n_sat, void* stream);
+
+/* tolg_policy_rollout_margins: tolg_policy_rollout_limited with the sampled check of the attitude margin
+ * (tighten_pose_constraints in the binding: kappa standard deviations on the cones' cosines) and, per knot, how many samples
+ * left a family's allowed set.  Everything tolg_policy_rollout_limited states holds: the sample definition, the clamp, the
+ * plant, references and weights per trajectory, the sample orders, J the tracking cost alone.  Four more outputs:
+ *        d_pose_margin [B][S]  min_{i = 0..N, k < K} of the margin of pose slot k (the table at tolg_set_al_pose_constraints:
+ *                              tilt cone n^T R e3 - c, view cone e1^T b / |b| - c with b = R^T (p - t)) at the sample's state
+ *                              at knot i -- the state each step starts from, and the terminal one -- over the slots attached to
+ *                              the handle: the static form, the per-knot form with knot i's own geometry, the window form as
+ *                              gathered; negative: outside a cone (+inf if no margin is a number: a NaN margin, a view target
+ *                              at the sample's position, is passed over)
+ *        d_pose_knot [B][S]    the first knot that attains it (strict <, knots ascending, slots ascending)
+ *        d_viol_pos [B][N+1]   the number of samples s whose clearance at knot i -- min over the position slots of the
+ *                              clearance of the slot's kind, d_clear's terms -- is < 0
+ *        d_viol_pose [B][N+1]  the same for the pose margins
+ *        every output may be NULL.  A NaN is not a violation.  The library zeroes the two count arrays on `stream` ahead of the
+ *        launch and the kernel adds to them with integer atomics: the counts do not depend on the order of the samples and are
+ *        the same bits on every call.  A kappa-sigma margin promises a violation probability at EACH knot (Phi(-kappa) to
+ *        first order, for Gaussian deviations): d_viol_*[b][i] / S is its estimate there, which a minimum over the horizon
+ *        cannot give, and it shows where along the path a margin is thin.
+ * With the four NULL the call is tolg_policy_rollout_limited, bit for bit.  Every output's bits are independent of which other
+ * outputs are asked for.
+ * TOLG_E_ARG: the conditions of tolg_policy_rollout_limited; a non-NULL d_pose_margin, d_pose_knot or d_viol_pose with no pose
+ * family attached; a non-NULL d_viol_pos with no position slots attached (a family attached for another B refuses every batch
+ * call; the SO3 family can attach neither).  A refused call changes nothing.
+ * Cost on an MI355X: INTEGRATION.md 3s. */
+int tolg_policy_rollout_margins(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w,
+                                const double* d_u_lb, const double* d_u_ub, double* d_J, int32_t* d_status, double* d_xs_q,
+                                double* d_xs_xi, double* d_us, int32_t* d_n_sat, double* d_u_excess, double* d_clear,
+                                int32_t* d_clear_knot, double* d_pose_margin, int32_t* d_pose_knot, int32_t* d_viol_pos,
+                                int32_t* d_viol_pose, void* stream);
 
 /* tolg_policy_covariance: the closed-loop covariance of the held policy to first order ("LinCov"), the analytic companion of
  * tolg_policy_rollout's sampling.  In the coordinates of tolg_policy_rollout and of K, e_i = [Log(q*_i^-1 q^_i); xi^_i - xi*_i]
@@ -692,14 +725,33 @@ int tolg_policy_value(tolg_handle_t h, int32_t B, const double* d_Sigma0, const 
  *        every output may be NULL.
  * A sample's bits depend on neither S nor the other samples; the held policy is left alone.  This call steps both chains with
  * the MODEL: an attached plant (tolg_set_plant) is ignored, as by every entry point outside the two rollouts, and the call
- * takes no input box.
- * TOLG_E_ARG: the conditions of tolg_policy_rollout; a bad mask (above); a NULL d_L. */
+ * takes no input box (the call below does).
+ * TOLG_E_ARG: the conditions of tolg_policy_rollout; a bad mask (above); a NULL d_L.
+ *
+ * tolg_policy_rollout_estimated_limited: the same loop under an actuator box and with the reports of
+ * tolg_policy_rollout_margins -- what a clipped actuator does to a vehicle that sees through sensors, and whether a sample
+ * hit anything.  The input u = u*_i + K_i e^ is clamped by tolg_policy_rollout_limited's three-way select to trajectory b's
+ * box; BOTH chains step with the clamped input (the filter knows what the actuator did), and the cost and d_us take it.
+ *   in : as above, then d_u_lb, d_u_ub [B][m], both or neither
+ *   out: as above, then d_n_sat, d_u_excess, d_clear, d_clear_knot [B][S] as tolg_policy_rollout_limited and d_pose_margin,
+ *        d_pose_knot [B][S], d_viol_pos, d_viol_pose [B][N+1] as tolg_policy_rollout_margins, all of them evaluated on the TRUE
+ *        state x_i, never on the estimate; every output may be NULL.
+ * With both bounds and every new output NULL the call is tolg_policy_rollout_estimated, bit for bit; every output's bits are
+ * independent of which others are asked for.  An attached plant stays ignored: both chains step with the model.
+ * TOLG_E_ARG: the conditions of tolg_policy_rollout_estimated; exactly one NULL bound; a report on a family that is not
+ * attached, as tolg_policy_rollout_margins has it.  A refused call changes nothing. */
 int tolg_policy_covariance_estimated(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, int32_t mask,
                                      const double* d_V, double* d_Sigma, double* d_P_post, double* d_L, double* d_var_x,
                                      double* d_var_est, double* d_var_u, double* d_pos_cov, void* stream);
 int tolg_policy_rollout_estimated(tolg_handle_t h, int32_t B, int32_t S, int32_t mask, const double* d_L, const double* d_dx0,
                                   const double* d_w, const double* d_n, double* d_J, int32_t* d_status, double* d_xs_q,
                                   double* d_xs_xi, double* d_us, double* d_est_q, double* d_est_xi, void* stream);
+int tolg_policy_rollout_estimated_limited(tolg_handle_t h, int32_t B, int32_t S, int32_t mask, const double* d_L,
+                                          const double* d_dx0, const double* d_w, const double* d_n, const double* d_u_lb,
+                                          const double* d_u_ub, double* d_J, int32_t* d_status, double* d_xs_q, double* d_xs_xi,
+                                          double* d_us, double* d_est_q, double* d_est_xi, int32_t* d_n_sat, double* d_u_excess,
+                                          double* d_clear, int32_t* d_clear_knot, double* d_pose_margin, int32_t* d_pose_knot,
+                                          int32_t* d_viol_pos, int32_t* d_viol_pose, void* stream);
 
 /* Plants: per-sample dynamics parameters that step the closed loops of tolg_policy_rollout and tolg_mpc_advance in place of
  * the model's (model mismatch: a payload change, a mis-identified inertia, domain randomisation).  The planner's model stays

@@ -1,14 +1,21 @@
 """What output feedback costs: tolg_policy_covariance_estimated beside tolg_policy_covariance, and tolg_policy_rollout_estimated
 beside tolg_policy_rollout, on a solved 4096 x 200 SE3 tracking batch.
 
-usage: python tools/bench_estimated.py [--B 4096] [--N 200] [--S 16] [--mask 0x03F] [--rounds 7] [--iters 10] [--out FILE.json]
+usage: python tools/bench_estimated.py [--B 4096] [--N 200] [--S 16] [--mask 0x03F] [--rounds 7] [--iters 10] [--limits]
+                                       [--out FILE.json]
 
 One process.  The batch is solved once, untimed (multiple shooting, accept-always, 20 iterations), and the Kalman gains the
 estimated rollout takes come from one untimed call of the estimated covariance.  Then, round after round, the four cases are
 timed in alternation: `iters` back-to-back calls between two events, through the C ABI (no host-side input checks).  The two
 covariance calls write their reduced outputs (var_x, var_u, pos_cov; the estimated one var_est too), the two rollouts J and
 status.  Reported per case: the median ms per call over the rounds, min and max, and the ratio to the existing call it stands
-beside."""
+beside.
+
+--limits: instead, tolg_policy_rollout_estimated and the reports of tolg_policy_rollout_estimated_limited added in turn, in the
+same alternating rounds: `estimated` (the existing call, the base of every ratio), `box` (the input range of every trajectory's
+unperturbed sample; n_sat and u_excess written), `box+clearance` (K = 8 keep-out spheres about the nominal path), `+pose K=8`
+(pose_margin and its knot from 8 pose slots), `+counts few` and `+counts most` (both violation counts; slot sets as
+tools/bench_policy.py --margins builds them)."""
 import argparse
 import ctypes as C
 import os
@@ -28,6 +35,7 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     add_common_args(ap, "B", "N", "S", "rounds", "iters", "out", iters=10, S="16")
     ap.add_argument("--mask", default="0x03F", help="the measured coordinates (12 bits)")
+    ap.add_argument("--limits", action="store_true", help="time tolg_policy_rollout_estimated_limited, its reports added in turn")
     a = ap.parse_args(argv)
     a.S, a.mask = int(a.S), int(a.mask, 0)
     if a.B < 1 or a.N < 1 or a.S < 1 or a.rounds < 1 or a.iters < 1 or not 0 <= a.mask <= 0xFFF:
@@ -72,6 +80,8 @@ def main(argv=None):
         return s.lib.tolg_policy_rollout_estimated(s._h, B, S, mask, p(L), p(dx0), p(w), p(n), p(J), p(st), None, None, None,
                                                    None, None, s._stream())
 
+    if a.limits:
+        return limits(a, prob, (q, xi, us), s, (L, dx0, w, n, J, st), p)
     names = list(CASES)
     times = event_rounds(names, call, a.rounds, a.iters)
     rows = {}
@@ -85,6 +95,70 @@ def main(argv=None):
     res = dict(B=B, N=N, S=S, mask="%#05x" % mask, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(dev),
                outputs_finite=finite, rows=[rows[n_] for n_ in names])
     print_row(dict(outputs_finite=finite))
+    emit(res, a.out)
+    return res
+
+
+LIMIT_FORMS = {"estimated": 0, "box": 2, "box+clearance": 4, "+pose K=8": 6, "+counts few": 8, "+counts most": 8}
+
+
+def limits(a, prob, start, s, data, p):
+    import torch
+    from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
+    from bench_policy import limit_spheres, margin_cones
+    B, N, S, mask = a.B, a.N, a.S, a.mask
+    L, dx0, w, n, J, st = data
+    f64 = dict(dtype=torch.float64, device=s.device)
+    i32 = dict(dtype=torch.int32, device=s.device)
+    tight = BatchedTrackingILQR(prob, B)  # a handle per slot set: attaching between timed calls would time the packing
+    tight.fit_batch(*start, mode="ms", n_iterations=20, tol_grad_norm=0.0, tol_d_norm=0.0)
+    nom = s.policy_rollout(S=1, trajectories=True)
+    lb, ub = nom.us[:, 0].amin(dim=1).contiguous(), nom.us[:, 0].amax(dim=1).contiguous()
+    xq = nom.xs_q[:, 0]
+    for h, is_tight in ((s, False), (tight, True)):
+        sp = limit_spheres(xq[:, :, :3, 3])
+        if is_tight:
+            sp[:, :, 3] = 0.5  # the nominal grazes every sphere
+        h.set_al_obstacles(sp)
+        sl, kinds = margin_cones(xq, 8, is_tight)
+        h.set_al_pose_constraints(sl, kinds=kinds)
+    outs = (torch.empty(B, S, **i32), torch.empty(B, S, **f64), torch.empty(B, S, **f64), torch.empty(B, S, **i32),
+            torch.empty(B, S, **f64), torch.empty(B, S, **i32), torch.empty(B, N + 1, **i32), torch.empty(B, N + 1, **i32))
+
+    def call(form):
+        h = tight if form == "+counts most" else s
+        if form == "estimated":
+            return h.lib.tolg_policy_rollout_estimated(h._h, B, S, mask, p(L), p(dx0), p(w), p(n), p(J), p(st), None, None, None,
+                                                       None, None, h._stream())
+        k = LIMIT_FORMS[form]
+        o = [p(t) for t in outs[:k]] + [None] * (8 - k)
+        return h.lib.tolg_policy_rollout_estimated_limited(h._h, B, S, mask, p(L), p(dx0), p(w), p(n), p(lb), p(ub), p(J), p(st),
+                                                           None, None, None, None, None, *o, h._stream())
+
+    names = list(LIMIT_FORMS)
+    times = event_rounds(names, call, a.rounds, a.iters)
+    base = stats_row(times["estimated"])
+    rows = []
+    for form in names:
+        row = dict(kernel="tolg_policy_rollout_estimated" + ("" if form == "estimated" else "_limited"), form=form, S=S,
+                   **stats_row(times[form]))
+        row.update(vs_estimated=row["ms_median"] / base["ms_median"] - 1, estimated_spread=(base["ms_max"] - base["ms_min"]) / base["ms_median"])
+        assert call(form) == 0
+        torch.cuda.synchronize()
+        k = LIMIT_FORMS[form]
+        if k >= 2:
+            row.update(saturated_samples=int((outs[0] > 0).sum().item()), status_ok=int((st == 0).sum().item()))
+        if k >= 6:
+            row.update(outside_a_cone=int((outs[4] < 0).sum().item()))
+        if k == 8:
+            row.update(viol_pos_share=float(outs[6].sum().item()) / (B * S * (N + 1)),
+                       viol_pose_share=float(outs[7].sum().item()) / (B * S * (N + 1)))
+        rows.append(row)
+        print_row(row)
+    for h in (s, tight):
+        h.set_al_obstacles(None)
+        h.set_al_pose_constraints(None)
+    res = dict(B=B, N=N, S=S, mask="%#05x" % mask, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(s.device), rows=rows)
     emit(res, a.out)
     return res
 

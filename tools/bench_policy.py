@@ -2,7 +2,7 @@
 solved 4096 x 200 SE3 tracking batch, J and status only.
 
 usage: python tools/bench_policy.py [--B 4096] [--N 200] [--S 1,16,64] [--rounds 7] [--iters 20] [--layouts samples,traj]
-                                    [--limits] [--out FILE.json]
+                                    [--limits | --margins] [--out FILE.json]
 
 One process.  The batch is solved once, untimed (multiple shooting, accept-always, 20 iterations), once per sample order of
 k_policy_rollout: `samples` (the default order, the samples of one trajectory side by side in a wavefront) and `traj`
@@ -16,7 +16,15 @@ and trajectory -- read once per wavefront that needs it: ceil(S / 16) times in `
 --limits: instead, per S and in the first layout, tolg_policy_rollout and tolg_policy_rollout_limited back to back in the same
 alternating rounds: `unlimited` (tolg_policy_rollout), `box` (the box alone: the input range of every trajectory's unperturbed
 sample, which the perturbed ones leave; n_sat and u_excess written) and `box+clearance` (the box and the clearance from K = 8 static keep-out
-spheres per trajectory, placed about its nominal path; clearance and its knot written too).  J and status in all three."""
+spheres per trajectory, placed about its nominal path; clearance and its knot written too).  J and status in all three.
+
+--margins: instead, per S and in the first layout, the reports of tolg_policy_rollout_margins added in turn to `box+clearance`
+(the limited call above, the base of every ratio): `+pose K=2` and `+pose K=8` (pose_margin and its knot from K pose slots per
+trajectory, tilt and view cones alternating, built on its nominal path), `+counts few` (both violation counts too, cones the
+nominal clears by 0.2 in the cosine: few pairs (sample, knot) outside) and `+counts most` (cones at the median of the nominal's own cosines
+and spheres the nominal grazes: most samples outside at most knots, the worst case for the atomics).  Last, at the middle S,
+the alternative the report replaces: policy_rollout(trajectories=True) and the host rollout_margins on the device tensors,
+wall clock with a synchronisation, and the bytes of the trajectories it writes."""
 import argparse
 import ctypes as C
 import os
@@ -32,6 +40,7 @@ def parse_args(argv=None):
     add_common_args(ap, "B", "N", "S", "rounds", "iters")
     ap.add_argument("--layouts", default="samples,traj")
     ap.add_argument("--limits", action="store_true", help="time tolg_policy_rollout_limited beside tolg_policy_rollout")
+    ap.add_argument("--margins", action="store_true", help="time the reports of tolg_policy_rollout_margins, each added in turn")
     add_common_args(ap, "out")
     a = ap.parse_args(argv)
     a.S = [int(s) for s in a.S.split(",")]
@@ -86,6 +95,8 @@ def main(argv=None):
 
     if a.limits:
         return limits(a, solvers[a.layouts[0]], a.layouts[0], inputs, p)
+    if a.margins:
+        return margins(a, prob, (q, xi, us), solvers[a.layouts[0]], a.layouts[0], inputs, p)
     names = [(layout, S) for S in a.S for layout in a.layouts] + ["rollout"]
     times = event_rounds(names, call, a.rounds, a.iters)
     rows = []
@@ -166,6 +177,127 @@ def limits(a, s, layout, inputs, p):
             print_row(row)
     s.set_al_obstacles(None)
     res = dict(B=B, N=N, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(s.device), rows=rows)
+    emit(res, a.out)
+    return res
+
+
+MARGIN_FORMS = ("box+clearance", "+pose K=2", "+pose K=8", "+counts few", "+counts most")
+
+
+def margin_cones(xs_q, K, tight):
+    """K pose slots per trajectory on its nominal poses xs_q [B, N+1, 4, 4], tilt cones (even k: the nominal thrust axis at an
+    anchor knot) and view cones (odd k: a target 2 ahead of the nominal pose there) alternating; the cosine is the slot's
+    smallest nominal cosine less 0.2, or with `tight` the median of its nominal cosines.  Returns ([B, K, 4], kinds)."""
+    import torch
+    B, N1 = xs_q.shape[:2]
+    R, t = xs_q[..., :3, :3], xs_q[..., :3, 3]
+    knots = torch.linspace(0, N1 - 1, K + 2, device=xs_q.device).long()[1:-1]
+    sl = torch.empty(B, K, 4, dtype=xs_q.dtype, device=xs_q.device)
+    kinds = []
+    for k, a_ in enumerate(knots.tolist()):
+        if k % 2 == 0:
+            n = R[:, a_, :, 2]
+            cos = (R[:, :, :, 2] * n[:, None]).sum(-1)
+            sl[:, k, :3] = n
+        else:
+            tg = t[:, a_] + 2.0 * R[:, a_, :, 0]
+            d = (R * (tg[:, None] - t)[..., :, None]).sum(-2)
+            cos = d[..., 0] / d.norm(dim=-1)
+            sl[:, k, :3] = tg
+        sl[:, k, 3] = (cos.median(dim=1).values if tight else cos.amin(dim=1) - 0.2).clamp(-0.99, 0.99)
+        kinds.append(k % 2)
+    return sl, kinds
+
+
+def margins(a, prob, start, s2, layout, inputs, p):
+    import time
+    import torch
+    from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR, rollout_margins
+    B, N = a.B, a.N
+    dev = s2.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    os.environ["TOLG_POLICY_TRAJ_FAST"] = "1" if layout == "traj" else "0"
+    handles = {"K2": s2}
+    for name in ("K8", "K8 tight"):  # a handle per slot set: attaching between timed calls would time the packing
+        h = BatchedTrackingILQR(prob, B)
+        h.fit_batch(*start, mode="ms", n_iterations=20, tol_grad_norm=0.0, tol_d_norm=0.0)
+        handles[name] = h
+    os.environ.pop("TOLG_POLICY_TRAJ_FAST", None)
+    nom = s2.policy_rollout(S=1, trajectories=True)
+    lb, ub = nom.us[:, 0].amin(dim=1).contiguous(), nom.us[:, 0].amax(dim=1).contiguous()
+    xq = nom.xs_q[:, 0]
+    slots = {}
+    for name, h in handles.items():
+        sp = limit_spheres(xq[:, :, :3, 3])
+        if name == "K8 tight":
+            sp[:, :, 3] = 0.5  # the nominal grazes every sphere
+        h.set_al_obstacles(sp)
+        sl, kinds = margin_cones(xq, 2 if name == "K2" else 8, name == "K8 tight")
+        h.set_al_pose_constraints(sl, kinds=kinds)
+        slots[name] = (sp, sl, kinds)
+    outs = {S: (torch.empty(B, S, **i32), torch.empty(B, S, **f64), torch.empty(B, S, **f64), torch.empty(B, S, **i32),
+                torch.empty(B, S, **f64), torch.empty(B, S, **i32), torch.empty(B, N + 1, **i32), torch.empty(B, N + 1, **i32))
+            for S in a.S}
+    which = {"box+clearance": ("K2", 4), "+pose K=2": ("K2", 6), "+pose K=8": ("K8", 6), "+counts few": ("K8", 8),
+             "+counts most": ("K8 tight", 8)}
+
+    def call(name):
+        S, form = name
+        dx0, w, J, st = inputs[S]
+        hname, n_out = which[form]
+        h = handles[hname]
+        o = [p(t) for t in outs[S][:n_out]]
+        if form == "box+clearance":
+            return h.lib.tolg_policy_rollout_limited(h._h, B, S, p(dx0), p(w), p(lb), p(ub), p(J), p(st), None, None, None, *o,
+                                                     h._stream())
+        o += [None] * (8 - n_out)
+        return h.lib.tolg_policy_rollout_margins(h._h, B, S, p(dx0), p(w), p(lb), p(ub), p(J), p(st), None, None, None, *o,
+                                                 h._stream())
+
+    names = [(S, form) for S in a.S for form in MARGIN_FORMS]
+    times = event_rounds(names, call, a.rounds, a.iters)
+    rows = []
+    for S in a.S:
+        base = stats_row(times[(S, MARGIN_FORMS[0])])
+        for form in MARGIN_FORMS:
+            row = dict(kernel="tolg_policy_rollout_limited" if form == MARGIN_FORMS[0] else "tolg_policy_rollout_margins",
+                       form=form, layout=layout, S=S, **stats_row(times[(S, form)]))
+            row.update(vs_base=row["ms_median"] / base["ms_median"] - 1, base_spread=(base["ms_max"] - base["ms_min"]) / base["ms_median"])
+            assert call((S, form)) == 0
+            torch.cuda.synchronize()
+            o = outs[S]
+            if which[form][1] >= 6:
+                row.update(outside_a_cone=int((o[4] < 0).sum().item()))
+            if which[form][1] == 8:
+                row.update(viol_pos_share=float(o[6].sum().item()) / (B * S * (N + 1)),
+                           viol_pose_share=float(o[7].sum().item()) / (B * S * (N + 1)))
+            rows.append(row)
+            print_row(row)
+    # the alternative: trajectories to HBM, then the host function on the device tensors
+    S = a.S[len(a.S) // 2]
+    dx0, w, _, _ = inputs[S]
+    h = handles["K8"]
+    sp, sl, kinds = slots["K8"]
+    wall = []
+    J, st = inputs[S][2:]
+    tr = (torch.empty(B, S, N + 1, 4, 4, **f64), torch.empty(B, S, N + 1, 6, **f64), torch.empty(B, S, N, prob.m, **f64))
+    for _ in range(3):  # (through the C ABI as the timed calls above: no host-side input checks)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        assert h.lib.tolg_policy_rollout_limited(h._h, B, S, p(dx0), p(w), p(lb), p(ub), p(J), p(st), p(tr[0]), p(tr[1]), p(tr[2]),
+                                                 None, None, None, None, h._stream()) == 0
+        rep = rollout_margins(tr[0], obstacles=sp, pose_slots=sl, pose_kinds=kinds)
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+    row = dict(kernel="policy_rollout(trajectories=True) + rollout_margins", S=S, ms_wall_min=min(wall), ms_wall_max=max(wall),
+               trajectory_bytes=B * S * ((N + 1) * 22 + N * prob.m) * 8, outside_a_cone=int((rep["pose_margin"] < 0).sum().item()))
+    rows.append(row)
+    print_row(row)
+    for h in handles.values():
+        h.set_al_obstacles(None)
+        h.set_al_pose_constraints(None)
+    res = dict(B=B, N=N, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(dev), rows=rows)
     emit(res, a.out)
     return res
 

@@ -36,7 +36,8 @@ SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_ba
            "tolg_rollout", "tolg_expected_change", "tolg_solve_gains", "tolg_policy_rollout",
            "tolg_solve_begin_warm", "tolg_set_ref_windows", "tolg_mpc_advance", "tolg_obstacles_bytes", "tolg_set_al_obstacles", "tolg_obstacles_moving_bytes", "tolg_set_al_obstacles_moving",
            "tolg_al_update_state", "tolg_al_mpc_step", "tolg_set_al_obstacle_windows", "tolg_set_al_obstacle_kinds", "tolg_pose_constraints_bytes", "tolg_set_al_pose_constraints",
-           "tolg_set_al_pose_constraint_windows", "tolg_al_mpc_step_pose", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_policy_covariance_estimated", "tolg_policy_rollout_estimated", "tolg_policy_rollout_limited", "tolg_mpc_advance_limited", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
+           "tolg_set_al_pose_constraint_windows", "tolg_al_mpc_step_pose", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_policy_covariance_estimated", "tolg_policy_rollout_estimated", "tolg_policy_rollout_limited", "tolg_mpc_advance_limited",
+           "tolg_policy_rollout_margins", "tolg_policy_rollout_estimated_limited", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
 
 
 def load():
@@ -147,6 +148,12 @@ def load():
     lib.tolg_policy_rollout_estimated.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, ip, dp, dp, dp, dp, dp, vp]
     lib.tolg_policy_rollout_limited.restype = C.c_int
     lib.tolg_policy_rollout_limited.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, ip, dp, dp, dp, ip, dp, dp, ip, vp]
+    lib.tolg_policy_rollout_margins.restype = C.c_int
+    lib.tolg_policy_rollout_margins.argtypes = lib.tolg_policy_rollout_limited.argtypes[:-1] + [dp, ip, ip, ip, vp]
+    lib.tolg_policy_rollout_estimated_limited.restype = C.c_int
+    lib.tolg_policy_rollout_estimated_limited.argtypes = (lib.tolg_policy_rollout_estimated.argtypes[:8] + [dp, dp]
+                                                          + lib.tolg_policy_rollout_estimated.argtypes[8:-1]
+                                                          + [ip, dp, dp, ip, dp, ip, ip, ip, vp])
     lib.tolg_mpc_advance_limited.restype = C.c_int
     lib.tolg_mpc_advance_limited.argtypes = [vp, C.c_int32] + [dp] * 10 + [ip, vp]
     lib.tolg_kernel_time.restype = C.c_int

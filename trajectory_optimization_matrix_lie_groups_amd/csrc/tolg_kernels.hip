@@ -3274,15 +3274,25 @@ __global__ __launch_bounds__(64) void k_rollout_eval_t(Params P, int a0, int nsl
 //    read as obs_terms reads it (field 4k + c of knot i at (i obs_stride + (4k + c) Bp + b): one address per wave in the
 //    default sample order), strict < with knots and spheres ascending: the first knot that attains the minimum.  It stands
 //    behind the step in the source and depends on the state alone, not on the gains or the control.
+//  - with L.pose (tolg_policy_rollout_margins), the same minimum and first knot over the pose slots' margins (pose_knot_min),
+//    and with L.viol_pos / L.viol_pose the per-knot counts of the samples outside a family's allowed set (count_violation):
+//    margins_knot has the three together.
 // The geometry pointer, K and the knot stride come from the constants at run time (the host refuses L.clearance with no
-// spheres attached): one limited kernel per model and plant form, in every table.
+// spheres attached, L.pose with no pose slots): one limited kernel per model and plant form, in every table -- the margins
+// call runs it too (registers of the form with and without these additions: DESIGN.md).
 struct PolicyLim {
   const double *lb, *ub;  // [B][M], or both null
   int* n_sat;             // [B][S] outputs, each may be null
   double* u_excess;
   double* clear;
   int* clear_knot;
-  int clearance;          // clear or clear_knot asked for
+  int clearance;          // clear, clear_knot or viol_pos asked for
+  // tolg_policy_rollout_margins: the margin of the pose slots the handle holds (pose_knot_min) and, per knot, the samples
+  // outside a family's allowed set (count_violation).  All null: the limited call
+  double* pose_margin;    // [B][S]
+  int* pose_knot;
+  int *viol_pos, *viol_pose;  // [B][N+1], zeroed on the stream ahead of the launch
+  int pose;               // pose_margin, pose_knot or viol_pose asked for
 };
 TOLG_DEV void clear_knot_min(const Consts& C, size_t Bp, int b, int i, const V3& t, double& cmin, int& cknot) {
   const double* geo = C.obs + b + (size_t)i * C.obs_stride;
@@ -3312,6 +3322,79 @@ TOLG_DEV void clear_knot_min(const Consts& C, size_t Bp, int b, int i, const V3&
       }
       if (c < cmin) { cmin = c; cknot = i; }
     }
+  }
+}
+// The pose family's clear_knot_min: the margins of the pose slots the handle holds (tolg_set_al_pose_constraints; K = C.poseK
+// > 0, the host's test) at the pose X of knot i -- tilt cone n^T R e3 - c, view cone e1^T b / |b| - c with b = R^T (p - t)
+// (include/tolg.h has the table) -- geometry read as pose_terms reads it (the static form, the per-knot one and the windows'
+// alike: knot i's block lies i C.pose_stride doubles on), four slots a trip with their sixteen loads in flight together, a
+// trip past K replaying slot K - 1.  Strict <, knots and slots ascending; a NaN margin is passed over (at t = p, |b| = 0).
+TOLG_DEV void pose_knot_min(const Consts& C, size_t Bp, int b, int i, const Pose& X, double& pmin, int& pknot) {
+  const double* geo = C.pose + b + (size_t)i * C.pose_stride;
+  const int K = C.poseK;
+  const unsigned kinds = C.pose_kinds;
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    double g[4][4];
+    unsigned kd[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int k = k0 + j < K ? k0 + j : K - 1;
+      const double* o = geo + (size_t)(4 * k) * Bp;
+      g[j][0] = o[0]; g[j][1] = o[Bp]; g[j][2] = o[2 * Bp]; g[j][3] = o[3 * Bp];
+      kd[j] = (kinds >> k) & 1u;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      double m;
+      if (kd[j] == TOLG_POSE_VIEW_CONE) {
+        const V3 d = qrot_inv(X.q, v3(g[j][0], g[j][1], g[j][2]) - X.t);
+        m = d.x / sqrt(dot(d, d)) - g[j][3];
+      } else {
+        m = qrot_inv(X.q, v3(g[j][0], g[j][1], g[j][2])).z - g[j][3];
+      }
+      if (m < pmin) { pmin = m; pknot = i; }
+    }
+  }
+}
+// One knot's entry of a violation count, viol = &count[0][i] of an int [B][n1] array the host zeroed ahead of the launch: the
+// lanes with v set (the writer lanes of live quads whose margin at the knot is below zero; a replay quad never sets it) add one
+// each to count[b][i].  Integer atomics without a return value: the sums do not depend on the order they arrive in.  In the
+// default sample order the quads of a wave share b, or a few of them: one atomic per wave and distinct b, a ballot's popcount
+// added by the first lane of each group -- not sixteen adds to one address.  traj_fast: every quad of a wave its own b, one add
+// per violating quad.  Called by whole waves (the knot loop and the flags in front of it are wave-uniform).
+TOLG_DEV void count_violation(int* viol, int n1, int b, bool v, int traj_fast) {
+  if (traj_fast) {
+    if (v) atomicAdd(viol + (size_t)b * n1, 1);
+    return;
+  }
+  unsigned long long m = __ballot(v);
+  while (m) {
+    const int lead = __ffsll((long long)m) - 1;
+    const int bl = __builtin_amdgcn_readlane(b, lead);
+    const unsigned long long same = __ballot(v && b == bl);
+    if ((int)(threadIdx.x & 63u) == lead) atomicAdd(viol + (size_t)bl * n1, __popcll(same));
+    m &= ~same;
+  }
+}
+// The margin report of a closed-loop kernel at knot i, on the TRUE state's pose X: the running minima (cmin, cknot) over the
+// position slots and (pmin, pknot) over the pose slots -- each knot's own minimum first, merged with strict <, which is the
+// order rule of clear_knot_min over the whole horizon -- and the knot's violation counts from that minimum (a NaN or +inf
+// minimum is no violation).  It depends on the state alone and stands off the gain / control chain.
+TOLG_DEV void margins_knot(const Consts& C, const PolicyLim& L, size_t Bp, int N, int b, int i, const Pose& X, bool writer,
+                           int traj_fast, double& cmin, int& cknot, double& pmin, int& pknot) {
+  if (L.clearance) {
+    double kc = INFINITY;
+    int kn = i;  // (the helper sets it to i wherever it lowers kc)
+    clear_knot_min(C, Bp, b, i, X.t, kc, kn);
+    if (kc < cmin) { cmin = kc; cknot = kn; }
+    if (L.viol_pos) count_violation(L.viol_pos + i, N + 1, b, writer && kc < 0.0, traj_fast);
+  }
+  if (L.pose) {
+    double kp = INFINITY;
+    int kn = i;
+    pose_knot_min(C, Bp, b, i, X, kp, kn);
+    if (kp < pmin) { pmin = kp; pknot = kn; }
+    if (L.viol_pose) count_violation(L.viol_pose + i, N + 1, b, writer && kp < 0.0, traj_fast);
   }
 }
 template <int M, int PK, int PT, int PL = PL_NONE, class... PA>
@@ -3347,8 +3430,8 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
       ub[a] = L.ub ? L.ub[(size_t)b * M + a] : INFINITY;
     }
   }
-  int nsat = 0, cknot = 0;
-  double excess = 0.0, cmin = INFINITY;
+  int nsat = 0, cknot = 0, pknot = 0;
+  double excess = 0.0, cmin = INFINITY, pmin = INFINITY;
   auto limit = [&](double (&u)[M]) {  // (not LIM: no code, roll_step's default)
     if constexpr (LIM) {
 #pragma unroll
@@ -3380,8 +3463,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
     const State Nx = roll_step<M, false, true, PK, false>(P, CS, DK, i, b, q, false, vb, sB, 0.0, Sa, Sn, un,
                                                            [&](RollIn<M>& R) { roll_load<M, true>(P, i, b, q, vb, sB, R); },
                                                            nullptr, ST, RollPre(), limit);
-    if constexpr (LIM)
-      if (L.clearance) clear_knot_min(C, (size_t)P.Bp, b, i, Sn.X.t, cmin, cknot);
+    if constexpr (LIM) margins_knot(C, L, (size_t)P.Bp, N, b, i, Sn.X, writer, traj_fast, cmin, cknot, pmin, pknot);
     J += knot_cost<M, true, PT>(P, C, i, b, Sn, un, false);
     if (writer) {
       state_to_m16(Sn, xs_q, xs_xi, bs * (size_t)(N + 1) + i);
@@ -3401,8 +3483,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
   }
 #pragma unroll
   for (int a = 0; a < M; a++) un[a] = 0.0;
-  if constexpr (LIM)
-    if (L.clearance) clear_knot_min(C, (size_t)P.Bp, b, N, Sn.X.t, cmin, cknot);
+  if constexpr (LIM) margins_knot(C, L, (size_t)P.Bp, N, b, N, Sn.X, writer, traj_fast, cmin, cknot, pmin, pknot);
   J += knot_cost<M, true, PT>(P, C, N, b, Sn, un, true);
   if (writer) {
     state_to_m16(Sn, xs_q, xs_xi, bs * (size_t)(N + 1) + N);
@@ -3413,6 +3494,8 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
       if (L.u_excess) L.u_excess[bs] = excess;
       if (L.clear) L.clear[bs] = cmin;
       if (L.clear_knot) L.clear_knot[bs] = cknot;
+      if (L.pose_margin) L.pose_margin[bs] = pmin;
+      if (L.pose_knot) L.pose_knot[bs] = pknot;
     }
   }
 }
@@ -3426,14 +3509,24 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
 // loads per lane at most; with the samples of a trajectory side by side one address per wave), the columns of unmeasured
 // coordinates are neither read nor multiplied (mask is a kernel argument: wave-uniform branches), the three sums go round the
 // quad by DPP as roll_control's two do.  Both chains stay in one quad (registers and scratch per form: DESIGN.md).
-// J is the tracking cost of the TRUE trajectory and the applied inputs.  The model steps both chains: no plant, no box.
-template <int M, int PK, int PT>
+// J is the tracking cost of the TRUE trajectory and the applied inputs.  The model steps both chains: no plant.
+// The trailing arguments pl (pack_arg) select the form, as k_policy_rollout's do: none is the kernel of
+// tolg_policy_rollout_estimated, whose code the other form leaves as it is (every addition sits under `if constexpr (LIM)`).
+// With a PolicyLim (tolg_policy_rollout_estimated_limited) the input u = u*_i + K_i e^ is clamped to trajectory b's box by
+// k_policy_rollout's three-way select before BOTH chains step with it (the cost and us take the clamped input), and the
+// margin report of margins_knot runs on the TRUE state of every knot.  The box is read at the knot, 2 M loads from two
+// cached rows, not held across the loop: the two chains leave no registers for it.
+template <int M, int PK, int PT, class... PA>
 __global__ __launch_bounds__(64) void k_policy_rollout_est(Params P, int S, int traj_fast, int mask, const double* __restrict__ Lg,
                                                            const double* __restrict__ dx0, const double* __restrict__ noise,
                                                            const double* __restrict__ mnoise, double* __restrict__ Jout,
                                                            int* __restrict__ status, double* __restrict__ xs_q,
                                                            double* __restrict__ xs_xi, double* __restrict__ us,
-                                                           double* __restrict__ est_q, double* __restrict__ est_xi) {
+                                                           double* __restrict__ est_q, double* __restrict__ est_xi, PA... pl) {
+  constexpr bool LIM = pack_has<PolicyLim, PA...>;
+  const PolicyLim L = pack_arg<PolicyLim>(pl...);
+  int nsat = 0, cknot = 0, pknot = 0;
+  double excess = 0.0, cmin = INFINITY, pmin = INFINITY;
   const Consts& C = *P.c;
   const size_t n = (size_t)P.B * (size_t)S;
   size_t c = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
@@ -3502,6 +3595,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout_est(Params P, int S, int 
       state_to_m16(St, xs_q, xs_xi, k);
       state_to_m16(Se, est_q, est_xi, k);
     }
+    if constexpr (LIM) margins_knot(C, L, (size_t)P.Bp, N, b, i, St.X, writer, traj_fast, cmin, cknot, pmin, pknot);
     if (i == N) break;
     // (scheduling barriers between the phases: left to itself the scheduler raises the gain loads above the estimate's update
     // and the cost's reference and weight loads above the control, and the kernel no longer fits its registers)
@@ -3514,6 +3608,20 @@ __global__ __launch_bounds__(64) void k_policy_rollout_est(Params P, int S, int 
     double e[12], du[M];
     roll_deviation(ew, ev, Sa, Se, e);
     roll_control<M, false>(R, e, un, du, 0.0);
+    if constexpr (LIM) {
+      if (L.lb) {  // (both or neither: the host's rule)
+        const double *lb = L.lb + (size_t)b * M, *ub = L.ub + (size_t)b * M;
+#pragma unroll
+        for (int a = 0; a < M; a++) {
+          const double uc = un[a], lo_b = lb[a], hi_b = ub[a];
+          const bool lo = uc < lo_b, hi = uc > hi_b;
+          nsat += (lo || hi) ? 1 : 0;
+          const double v = lo ? lo_b : (hi ? hi_b : uc);
+          excess = fmax(excess, fabs(v - uc));  // (k_policy_rollout's limit has the note)
+          un[a] = v;
+        }
+      }
+    }
     __builtin_amdgcn_sched_barrier(0);
     J += knot_cost<M, true, PT>(P, C, i, b, St, un, false);
     __builtin_amdgcn_sched_barrier(0);
@@ -3536,6 +3644,14 @@ __global__ __launch_bounds__(64) void k_policy_rollout_est(Params P, int S, int 
   if (writer) {
     if (Jout) Jout[bs] = J;
     if (status) status[bs] = isfinite(J) ? TOLG_ST_OK : TOLG_ST_NONFINITE;
+    if constexpr (LIM) {
+      if (L.n_sat) L.n_sat[bs] = nsat;
+      if (L.u_excess) L.u_excess[bs] = excess;
+      if (L.clear) L.clear[bs] = cmin;
+      if (L.clear_knot) L.clear_knot[bs] = cknot;
+      if (L.pose_margin) L.pose_margin[bs] = pmin;
+      if (L.pose_knot) L.pose_knot[bs] = pknot;
+    }
   }
 }
 
@@ -5225,6 +5341,9 @@ struct KernelTable {
                                 double*, double*);
   void (*policy_rollout_est)(Params, int, int, int, const double*, const double*, const double*, const double*, double*, int*,
                              double*, double*, double*, double*, double*);
+  // ... under an actuator box and with the margin report (tolg_policy_rollout_estimated_limited)
+  void (*policy_rollout_est_lim)(Params, int, int, int, const double*, const double*, const double*, const double*, double*, int*,
+                                 double*, double*, double*, double*, double*, PolicyLim);
   struct Search {                    // per search kind: ls[0] backtracking (single shooting), ls[1] merit (multiple shooting)
     struct { SearchRollout k; int nt; } wave2[2];  // k_rollout_ls2 [first try] and its NT (twist waves per pose wave)
     SearchRollout wave1[2];          // the one-wave forms k_rollout_ls [linear]
@@ -5302,6 +5421,7 @@ static KernelTable kernel_table(int lds_per_block) {
   t.policy_value = k_policy_value<M, PK, PT & ~PT_OBS>;  // (the tracking cost's derivatives: reference and weights, no spheres)
   t.policy_covariance_est = k_policy_covariance_est<M, PK>;
   t.policy_rollout_est = k_policy_rollout_est<M, PK, PT & ~PT_OBS>;
+  t.policy_rollout_est_lim = k_policy_rollout_est<M, PK, PT & ~PT_OBS, PolicyLim>;
   t.ls[0] = search_kernels<M, false, PK, PT>();
   t.ls[1] = search_kernels<M, true, PK, PT>();
   return t;
@@ -6888,6 +7008,14 @@ static int launch_closed_loop(const tolg_handle_s* h, const ClosedLoop<A...>& k,
   return 0;
 }
 
+// The violation counts of a PolicyLim, zeroed on the stream once nothing can refuse the call any more, ahead of the launch
+// whose atomics fill them
+static int zero_counts(const PolicyLim& L, int B, int N, hipStream_t st) {
+  const size_t nv = (size_t)B * (size_t)(N + 1) * sizeof(int32_t);
+  if (L.viol_pos && hipMemsetAsync(L.viol_pos, 0, nv, st) != hipSuccess) return TOLG_E_LAUNCH;
+  if (L.viol_pose && hipMemsetAsync(L.viol_pose, 0, nv, st) != hipSuccess) return TOLG_E_LAUNCH;
+  return 0;
+}
 // tolg_policy_rollout and tolg_policy_rollout_limited: the rules both share, then the kernel of k with lim (none, or the
 // PolicyLim) behind the rollout's arguments
 template <class K, class... LIM>
@@ -6897,6 +7025,7 @@ static int policy_rollout(tolg_handle_t h, const K& k, int32_t B, int32_t S, con
   const size_t lanes = (size_t)B * (size_t)S * 4;
   if (lanes > 0x7fffffc0ull) return TOLG_E_ARG;  // one launch, 64-lane groups
   if (h->plant.p && (B != h->plant.B || (h->plant_S != 1 && h->plant_S != S))) return TOLG_E_ARG;
+  if ((... || (zero_counts(lim, B, h->prob.N, static_cast<hipStream_t>(stream)) != 0))) return TOLG_E_LAUNCH;
   Params P = params_for(h, B);
   P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // J is the tracking cost: no augmented-Lagrangian terms
   return launch_closed_loop(h, k, dim3((unsigned)((lanes + 63) / 64)), dim3(64), static_cast<hipStream_t>(stream), P, (int)S,
@@ -6908,16 +7037,37 @@ extern "C" int tolg_policy_rollout(tolg_handle_t h, int32_t B, int32_t S, const 
   return policy_rollout(h, h->kt.policy_rollout, B, S, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, stream);
 }
 
-// The box is an argument of the call and never held by the handle; the spheres are the ones it holds (policy_ok: for this B).
+// The box is an argument of the call and never held by the handle; the slots are the ones it holds (policy_ok: for this B).
+// What the limited calls of both sampled loops check of their box and their reports, and the PolicyLim they launch with: null
+// where the call is refused -- one bound without the other, a report on a family that is not attached.
+static bool policy_lim(const tolg_handle_s* h, int32_t B, const double* d_u_lb, const double* d_u_ub, int32_t* d_n_sat,
+                       double* d_u_excess, double* d_clear, int32_t* d_clear_knot, double* d_pose_margin, int32_t* d_pose_knot,
+                       int32_t* d_viol_pos, int32_t* d_viol_pose, PolicyLim& L) {
+  if (!policy_ok(h, B) || (d_u_lb == nullptr) != (d_u_ub == nullptr)) return false;
+  const bool clearance = d_clear || d_clear_knot || d_viol_pos, pose = d_pose_margin || d_pose_knot || d_viol_pose;
+  if (clearance && !h->pt[H_OBS].p) return false;  // (slots for another B: policy_ok)
+  if (pose && !h->posec.p) return false;
+  L = PolicyLim{d_u_lb, d_u_ub, d_n_sat, d_u_excess, d_clear, d_clear_knot, clearance ? 1 : 0,
+                d_pose_margin, d_pose_knot, d_viol_pos, d_viol_pose, pose ? 1 : 0};
+  return true;
+}
+extern "C" int tolg_policy_rollout_margins(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w,
+                                           const double* d_u_lb, const double* d_u_ub, double* d_J, int32_t* d_status,
+                                           double* d_xs_q, double* d_xs_xi, double* d_us, int32_t* d_n_sat, double* d_u_excess,
+                                           double* d_clear, int32_t* d_clear_knot, double* d_pose_margin, int32_t* d_pose_knot,
+                                           int32_t* d_viol_pos, int32_t* d_viol_pose, void* stream) {
+  PolicyLim L;
+  if (S < 1 || !policy_lim(h, B, d_u_lb, d_u_ub, d_n_sat, d_u_excess, d_clear, d_clear_knot, d_pose_margin, d_pose_knot, d_viol_pos,
+                           d_viol_pose, L))
+    return TOLG_E_ARG;
+  return policy_rollout(h, h->kt.policy_rollout_lim, B, S, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, stream, L);
+}
 extern "C" int tolg_policy_rollout_limited(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w,
                                            const double* d_u_lb, const double* d_u_ub, double* d_J, int32_t* d_status,
                                            double* d_xs_q, double* d_xs_xi, double* d_us, int32_t* d_n_sat, double* d_u_excess,
                                            double* d_clear, int32_t* d_clear_knot, void* stream) {
-  if (!h || (d_u_lb == nullptr) != (d_u_ub == nullptr)) return TOLG_E_ARG;
-  const bool clearance = d_clear || d_clear_knot;
-  if (clearance && !h->pt[H_OBS].p) return TOLG_E_ARG;  // (spheres for another B: policy_ok)
-  return policy_rollout(h, h->kt.policy_rollout_lim, B, S, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, stream,
-                        PolicyLim{d_u_lb, d_u_ub, d_n_sat, d_u_excess, d_clear, d_clear_knot, clearance ? 1 : 0});
+  return tolg_policy_rollout_margins(h, B, S, d_dx0, d_w, d_u_lb, d_u_ub, d_J, d_status, d_xs_q, d_xs_xi, d_us, d_n_sat, d_u_excess,
+                                     d_clear, d_clear_knot, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int tolg_policy_covariance(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, double* d_Sigma,
@@ -6971,6 +7121,30 @@ extern "C" int tolg_policy_rollout_estimated(tolg_handle_t h, int32_t B, int32_t
   hipLaunchKernelGGL(h->kt.policy_rollout_est, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P, (int)S,
                      h->pol_traj_fast ? 1 : 0, (int)mask, d_L, d_dx0, d_w, d_n, d_J, d_status, d_xs_q, d_xs_xi, d_us, d_est_q,
                      d_est_xi);
+  LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int tolg_policy_rollout_estimated_limited(tolg_handle_t h, int32_t B, int32_t S, int32_t mask, const double* d_L,
+                                                     const double* d_dx0, const double* d_w, const double* d_n,
+                                                     const double* d_u_lb, const double* d_u_ub, double* d_J, int32_t* d_status,
+                                                     double* d_xs_q, double* d_xs_xi, double* d_us, double* d_est_q,
+                                                     double* d_est_xi, int32_t* d_n_sat, double* d_u_excess, double* d_clear,
+                                                     int32_t* d_clear_knot, double* d_pose_margin, int32_t* d_pose_knot,
+                                                     int32_t* d_viol_pos, int32_t* d_viol_pose, void* stream) {
+  if (!policy_ok(h, B) || S < 1 || !mask_ok(h, mask) || !d_L) return TOLG_E_ARG;
+  const size_t lanes = (size_t)B * (size_t)S * 4;
+  if (lanes > 0x7fffffc0ull) return TOLG_E_ARG;  // one launch, 64-lane groups
+  PolicyLim L;
+  if (!policy_lim(h, B, d_u_lb, d_u_ub, d_n_sat, d_u_excess, d_clear, d_clear_knot, d_pose_margin, d_pose_knot, d_viol_pos,
+                  d_viol_pose, L))
+    return TOLG_E_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (zero_counts(L, B, h->prob.N, st)) return TOLG_E_LAUNCH;
+  Params P = params_for(h, B);
+  P.al_lb = P.al_ub = P.al_lambda = P.al_imu = nullptr;  // J is the tracking cost: no augmented-Lagrangian terms
+  hipLaunchKernelGGL(h->kt.policy_rollout_est_lim, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, P, (int)S,
+                     h->pol_traj_fast ? 1 : 0, (int)mask, d_L, d_dx0, d_w, d_n, d_J, d_status, d_xs_q, d_xs_xi, d_us, d_est_q,
+                     d_est_xi, L);
   LAUNCH_CHECK();
   return 0;
 }

@@ -96,6 +96,14 @@ class PolicyRollout:
     # kind_clearance), and the first knot that attains it
     clearance: Optional[torch.Tensor] = None       # [B, S]
     clearance_knot: Optional[torch.Tensor] = None  # [B, S] int32
+    # pose_margin=True: min over knots and pose slots of the slot's margin (pose_margin(); negative: outside a cone), and the
+    # first knot that attains it
+    pose_margin: Optional[torch.Tensor] = None       # [B, S]
+    pose_margin_knot: Optional[torch.Tensor] = None  # [B, S] int32
+    # violations=True: per knot, the samples whose clearance (viol_pos) / pose margin (viol_pose) is below zero there; each
+    # for the family attached (rollout_margins is the definition)
+    viol_pos: Optional[torch.Tensor] = None          # [B, N+1] int32
+    viol_pose: Optional[torch.Tensor] = None         # [B, N+1] int32
     # policy_rollout_estimated(estimates=True): the filter's posterior estimates x^_i (xs_q / xs_xi hold the true states)
     est_q: Optional[torch.Tensor] = None           # [B, S, N+1, 4, 4]
     est_xi: Optional[torch.Tensor] = None          # [B, S, N+1, 6]
@@ -379,6 +387,61 @@ def pose_margin(xs_q, slots, kinds):
     return (torch if isinstance(out[0], torch.Tensor) else np).stack(out, -1)
 
 
+def _min_first_knot(m):
+    """min over the knot and slot axes of m [..., N+1, K] and the first knot that attains it, under the kernels' order rule:
+    strict <, knots ascending, slots ascending; a NaN is passed over; +inf and knot 0 where no entry is a number."""
+    np_ = not isinstance(m, torch.Tensor)
+    inf = float("inf")
+    m = (np.where(np.isnan(m), inf, m) if np_ else torch.where(torch.isnan(m), torch.full_like(m, inf), m))
+    per_knot = m.min(-1) if np_ else m.amin(-1)           # [..., N+1]
+    # argmin returns the first index of the minimum in numpy and in torch alike
+    knot = per_knot.argmin(-1)
+    return (per_knot.min(-1) if np_ else per_knot.amin(-1)), (knot.astype(np.int32) if np_ else knot.to(torch.int32)), per_knot
+
+
+def rollout_margins(xs_q, obstacles=None, kinds=None, pose_slots=None, pose_kinds=None):
+    """The margin report of the sampled closed loops from stored trajectories, the definition tolg_policy_rollout_margins and
+    tolg_policy_rollout_estimated_limited are tested against and the fallback for whoever holds trajectories already: xs_q
+    [B, S, N+1, 4, 4] (policy_rollout(trajectories=True).xs_q), numpy or torch alike.  obstacles [K, 4], [B, K, 4] or
+    [B, N+1, K, 4] of `kinds` (check_kinds; None: keep-out spheres) and / or pose_slots of the same three shapes of
+    `pose_kinds` (check_pose_kinds); a family not given is not reported.  Returns a dict with, per family given,
+      clearance, clearance_knot [B, S]        min over knots and slots of kind_clearance, and the first knot that attains it
+      pose_margin, pose_margin_knot [B, S]    the same of pose_margin()
+      viol_pos, viol_pose [B, N+1] int32      per knot, the samples whose minimum over the slots is < 0 there
+    under the kernels' order rule: strict <, knots then slots ascending, a NaN passed over (and no violation), +inf and knot 0
+    where no margin is a number."""
+    if xs_q.ndim != 5 or tuple(xs_q.shape[-2:]) != (4, 4):
+        raise ValueError("rollout_margins: xs_q has shape %s, expected (B, S, N+1, 4, 4)" % (tuple(xs_q.shape),))
+    if obstacles is None and pose_slots is None:
+        raise ValueError("rollout_margins needs obstacles or pose_slots")
+    B, N1 = xs_q.shape[0], xs_q.shape[2]
+    is_t = isinstance(xs_q, torch.Tensor)
+
+    def slots_for(name, a):
+        a = (torch.as_tensor(a, dtype=xs_q.dtype, device=xs_q.device) if is_t
+             else np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64))
+        ok = a.ndim in (2, 3, 4) and a.shape[-1] == 4 and (a.ndim == 2 or a.shape[0] == B) and (a.ndim < 4 or a.shape[1] == N1)
+        if not ok:
+            raise ValueError("rollout_margins: %s has shape %s, expected (K, 4), (%d, K, 4) or (%d, %d, K, 4)"
+                             % (name, tuple(a.shape), B, B, N1))
+        # against the sample and knot axes of xs_q: [B or 1, 1, N+1 or 1, K, 4]
+        return a if a.ndim == 2 else (a[:, None, None] if a.ndim == 3 else a[:, None])
+
+    out = {}
+    count = lambda v: (v.sum(1).to(torch.int32) if is_t else v.sum(1).astype(np.int32))  # noqa: E731
+    if obstacles is not None:
+        o = slots_for("obstacles", obstacles)
+        c = kind_clearance(xs_q[..., :3, 3], o, check_kinds(kinds, o.shape[-2]))
+        out["clearance"], out["clearance_knot"], per_knot = _min_first_knot(c)
+        out["viol_pos"] = count(per_knot < 0.0)
+    if pose_slots is not None:
+        o = slots_for("pose_slots", pose_slots)
+        m = pose_margin(xs_q, o, pose_kinds)
+        out["pose_margin"], out["pose_margin_knot"], per_knot = _min_first_knot(m)
+        out["viol_pose"] = count(per_knot < 0.0)
+    return out
+
+
 def inflate_obstacles(obstacles, xs_q, pos_cov, kappa, kinds=None):
     """Keep-out spheres with a margin for the closed-loop spread: obstacles [K, 4], [B, K, 4] or [B, N+1, K, 4] rows (cx, cy,
     cz, r), xs_q [B, N+1, 4, 4] the nominal plan, pos_cov [B, N+1, 3, 3] its position covariance (policy_covariance().pos_cov).
@@ -491,7 +554,8 @@ _POLICY = {"tolg_solve_begin": "clear", "tolg_solve_begin_warm": "clear", "tolg_
            "tolg_set_al_obstacles": "", "tolg_set_al_obstacles_moving": "",
            "tolg_al_update_state": "", "tolg_al_mpc_step": "", "tolg_al_mpc_step_pose": "",
            "tolg_set_al_obstacle_windows": "", "tolg_set_al_obstacle_kinds": "",
-           "tolg_set_al_pose_constraints": "", "tolg_set_al_pose_constraint_windows": ""}  # (the last nine leave it: listed for completeness)
+           "tolg_set_al_pose_constraints": "", "tolg_set_al_pose_constraint_windows": "",
+           "tolg_policy_rollout_margins": "", "tolg_policy_rollout_estimated_limited": ""}  # (the last eleven leave it: listed for completeness)
 # A setter's detach call (BatchedTrackingILQR._detach): its arguments behind the handle with the source pointer null, the
 # stream's place included.  tolg_set_al_obstacles detaches the per-knot form too.
 _DETACH = {"tolg_set_refs": (0, None, None, None, 0, None), "tolg_set_weights": (0, None, None, None, None, 0, None),
@@ -1502,8 +1566,38 @@ class BatchedTrackingILQR:
         lb, ub = check_box(u_lb, u_ub, B, self.m, so3=self.problem.kind in ("so3", "pendulum3d"))
         return self._dev(lb, (B, self.m)), self._dev(ub, (B, self.m))
 
+    def _margin_flags(self, clearance, pose_margin, violations):
+        """The report keywords of the sampled loops checked against the families attached, ValueError before anything reaches
+        the device.  Returns (viol_pos, viol_pose): which counts violations=True fills -- those of every family attached."""
+        if clearance and self._obs is None:
+            raise ValueError("clearance=True needs keep-out spheres: attach them with set_al_obstacles")
+        if pose_margin and self._pose is None:
+            raise ValueError("pose_margin=True needs pose constraints: attach them with set_al_pose_constraints")
+        if violations and self._obs is None and self._pose is None:
+            raise ValueError("violations=True needs a constraint family: attach one with set_al_obstacles or "
+                             "set_al_pose_constraints")
+        return bool(violations) and self._obs is not None, bool(violations) and self._pose is not None
+
+    def _margin_outputs(self, r, B, S, box, clearance, pose_margin, viol):
+        """The report tensors of a sampled loop on r, and their pointers in the order of the C calls: n_sat, u_excess, clear,
+        clear_knot, then the four of tolg_policy_rollout_margins."""
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        if box is not None:
+            r.n_sat, r.u_excess = torch.empty(B, S, **i32), torch.empty(B, S, **f64)
+        if clearance:
+            r.clearance, r.clearance_knot = torch.empty(B, S, **f64), torch.empty(B, S, **i32)
+        if pose_margin:
+            r.pose_margin, r.pose_margin_knot = torch.empty(B, S, **f64), torch.empty(B, S, **i32)
+        if viol[0]:
+            r.viol_pos = torch.empty(B, self.N + 1, **i32)
+        if viol[1]:
+            r.viol_pose = torch.empty(B, self.N + 1, **i32)
+        return (_ptr(r.n_sat), _ptr(r.u_excess), _ptr(r.clearance), _ptr(r.clearance_knot), _ptr(r.pose_margin),
+                _ptr(r.pose_margin_knot), _ptr(r.viol_pos), _ptr(r.viol_pose))
+
     def policy_rollout(self, dx0=None, noise=None, S=None, trajectories=False, plant_J=None, plant_pend=None, u_lb=None,
-                       u_ub=None, clearance=False) -> PolicyRollout:
+                       u_ub=None, clearance=False, pose_margin=False, violations=False) -> PolicyRollout:
         """S closed-loop rollouts per trajectory of the held policy u = u*_i + K_i (x (-) x*_i) with exact dynamics
         (tolg_policy_rollout).  dx0 [B, S, 12]: start perturbation in the error coordinates of K (pose x*_0 Exp(dx0[:6]),
         twist xi*_0 + dx0[6:]); noise [B, S, N, 6]: added to the twist behind every step.  Either may be None (zero); S is
@@ -1517,10 +1611,16 @@ class BatchedTrackingILQR:
         left it.  clearance=True: the result carries clearance [B, S], min over knots and spheres of |t - c| - r for the
         keep-out spheres attached by set_al_obstacles (negative: the sample entered one; a slot of another kind enters with
         the clearance of its kind, kind_clearance), and clearance_knot, the first knot
-        that attains it; ValueError when none are attached.  With none of the three the call is tolg_policy_rollout."""
+        that attains it; ValueError when none are attached.  With none of the three the call is tolg_policy_rollout.
+        pose_margin=True: the result carries pose_margin [B, S], min over knots and slots of the margin of the pose slots
+        attached by set_al_pose_constraints (pose_margin(): negative, the sample left a cone) and pose_margin_knot, the first
+        knot that attains it -- the sampled check of tighten_pose_constraints; ValueError when none are attached.
+        violations=True: per knot, how many of the S samples are outside the allowed set there, viol_pos [B, N+1] for the
+        position slots and viol_pose [B, N+1] for the pose slots, each when its family is attached (ValueError if neither is):
+        viol / S estimates the violation probability a kappa-sigma margin promises at each knot.  rollout_margins() is the
+        definition of all four.  With either keyword the call is tolg_policy_rollout_margins."""
         B = self._held_B()
-        if clearance and self._obs is None:
-            raise ValueError("clearance=True needs keep-out spheres: attach them with set_al_obstacles")
+        viol = self._margin_flags(clearance, pose_margin, violations)
         box = self._box(B, u_lb, u_ub)
         shapes = []
         if dx0 is not None:
@@ -1550,20 +1650,17 @@ class BatchedTrackingILQR:
             r.xs_xi = torch.empty(B, S, self.N + 1, 6, **f64)
             r.us = torch.empty(B, S, self.N, self.m, **f64)
         limited = box is not None or clearance
-        if box is not None:
-            r.n_sat = torch.empty(B, S, dtype=torch.int32, device=self.device)
-            r.u_excess = torch.empty(B, S, **f64)
-        if clearance:
-            r.clearance = torch.empty(B, S, **f64)
-            r.clearance_knot = torch.empty(B, S, dtype=torch.int32, device=self.device)
+        margins = pose_margin or violations
+        out = self._margin_outputs(r, B, S, box, clearance, pose_margin, viol)
         d_plant = self._use_plant(B, plant)
         try:
             self._hold((d_dx0, d_w, d_plant, box))
-            if limited:
+            if limited or margins:
                 lb, ub = box if box is not None else (None, None)
-                self._call("tolg_policy_rollout_limited", B, S, _ptr(d_dx0), _ptr(d_w), _ptr(lb), _ptr(ub), _ptr(r.J),
-                           _ptr(r.status), _ptr(r.xs_q), _ptr(r.xs_xi), _ptr(r.us), _ptr(r.n_sat), _ptr(r.u_excess),
-                           _ptr(r.clearance), _ptr(r.clearance_knot))
+                # (a call with neither new keyword goes through the entry point it always did)
+                self._call("tolg_policy_rollout_margins" if margins else "tolg_policy_rollout_limited", B, S, _ptr(d_dx0),
+                           _ptr(d_w), _ptr(lb), _ptr(ub), _ptr(r.J), _ptr(r.status), _ptr(r.xs_q), _ptr(r.xs_xi), _ptr(r.us),
+                           *(out if margins else out[:4]))
             else:
                 self._call("tolg_policy_rollout", B, S, _ptr(d_dx0), _ptr(d_w), _ptr(r.J), _ptr(r.status), _ptr(r.xs_q),
                            _ptr(r.xs_xi), _ptr(r.us))
@@ -1642,7 +1739,8 @@ class BatchedTrackingILQR:
         return r
 
     def policy_rollout_estimated(self, L, mask, dx0=None, w=None, meas_noise=None, S=None, trajectories=False,
-                                 estimates=False) -> PolicyRollout:
+                                 estimates=False, u_lb=None, u_ub=None, clearance=False, pose_margin=False,
+                                 violations=False) -> PolicyRollout:
         """S sampled closed loops per trajectory of the held policy under output feedback (tolg_policy_rollout_estimated), the
         Monte-Carlo check of policy_covariance_estimated: the true state starts at x*_0 (+) dx0, the estimate at x*_0; at every
         knot the filter takes y = x (+) meas_noise on the coordinates `mask` and corrects x^ <- x^ (+) L_i r with the residual
@@ -1652,8 +1750,15 @@ class BatchedTrackingILQR:
         coordinates are not read).  dx0 [B, S, 12], w [B, S, N, 6], meas_noise [B, S, N+1, 12]: each may be None (zero); S is
         taken from them, or given when all are None.  J [B, S] is the tracking cost of the true trajectory and the applied
         inputs.  trajectories=True also returns xs_q, xs_xi, us (the true states); estimates=True est_q, est_xi (the posterior
-        estimates).  An attached plant is ignored and the call takes no input box."""
+        estimates).  An attached plant is ignored.
+        u_lb / u_ub, clearance, pose_margin, violations: policy_rollout's keywords under its rules
+        (tolg_policy_rollout_estimated_limited) -- the input computed from the estimate is clamped to the box and BOTH chains step
+        with the clamped input, n_sat / u_excess count it, and clearance, pose margin and the per-knot counts are those of the
+        TRUE states, never of the estimates: the check of inflate_obstacles / tighten_pose_constraints fed with the estimated
+        loop's covariance.  With none of them the call is tolg_policy_rollout_estimated."""
         B = self._held_B()
+        viol = self._margin_flags(clearance, pose_margin, violations)
+        box = self._box(B, u_lb, u_ub)
         m = measurement_mask(mask, so3=self._so3())
         if L is None:
             raise ValueError("policy_rollout_estimated needs the gains L [B, N+1, 12, 12]")
@@ -1690,9 +1795,16 @@ class BatchedTrackingILQR:
         if estimates:
             r.est_q = torch.empty(B, S, self.N + 1, 4, 4, **f64)
             r.est_xi = torch.empty(B, S, self.N + 1, 6, **f64)
-        self._hold((d_L, d_dx0, d_w, d_n))
-        self._call("tolg_policy_rollout_estimated", B, S, m, _ptr(d_L), _ptr(d_dx0), _ptr(d_w), _ptr(d_n), _ptr(r.J),
-                   _ptr(r.status), _ptr(r.xs_q), _ptr(r.xs_xi), _ptr(r.us), _ptr(r.est_q), _ptr(r.est_xi))
+        out = self._margin_outputs(r, B, S, box, clearance, pose_margin, viol)
+        self._hold((d_L, d_dx0, d_w, d_n, box))
+        if box is not None or clearance or pose_margin or violations:
+            lb, ub = box if box is not None else (None, None)
+            self._call("tolg_policy_rollout_estimated_limited", B, S, m, _ptr(d_L), _ptr(d_dx0), _ptr(d_w), _ptr(d_n), _ptr(lb),
+                       _ptr(ub), _ptr(r.J), _ptr(r.status), _ptr(r.xs_q), _ptr(r.xs_xi), _ptr(r.us), _ptr(r.est_q),
+                       _ptr(r.est_xi), *out)
+        else:
+            self._call("tolg_policy_rollout_estimated", B, S, m, _ptr(d_L), _ptr(d_dx0), _ptr(d_w), _ptr(d_n), _ptr(r.J),
+                       _ptr(r.status), _ptr(r.xs_q), _ptr(r.xs_xi), _ptr(r.us), _ptr(r.est_q), _ptr(r.est_xi))
         return r
 
     def policy_value(self, Sigma0=None, W=None, full=False) -> PolicyValue:
