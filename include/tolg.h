@@ -599,6 +599,67 @@ int tolg_policy_rollout_margins(tolg_handle_t h, int32_t B, int32_t S, const dou
                                 int32_t* d_clear_knot, double* d_pose_margin, int32_t* d_pose_knot, int32_t* d_viol_pos,
                                 int32_t* d_viol_pose, void* stream);
 
+/* The two closed loops behind an actuator model: the input the dynamics step on is no longer the input the policy commanded at
+ * that knot.  A motor or a reaction wheel has a first-order lag of one to three knots at the dt the workloads use, a slew limit
+ * and a transport or computation delay of a whole knot or more, and that decides whether time-varying LQR gains survive on a
+ * vehicle.  The model, per trajectory b and input a, at every knot i < N of a sample:
+ *   c_i  = u*_i + K_i e_i                              the command (what the policy asks for)
+ *   d_i  = c_{i-D}  for i >= D,  u_init  otherwise     transport delay of D = delay knots, one value for the whole call
+ *   s_i  = d_i < lb ? lb : (d_i > ub ? ub : d_i)       the box, tolg_policy_rollout_limited's select (a NaN stays NaN)
+ *   l_i  = s_i - beta * (s_i - a_{i-1})                lag, beta = exp(-dt / tau) in [0, 1), beta = 0: none
+ *   dl   = l_i - a_{i-1}
+ *   a_i  = dl > du ? a_{i-1} + du : (dl < -du ? a_{i-1} - du : l_i)    rate limit, du = du_max > 0 per knot, +inf: none
+ *   a_{-1} = u_init = d_u_init[b], or u*_0 of trajectory b when d_u_init is NULL
+ *   x_{i+1} = f(x_i, a_i) (+ noise)                    on the plant row where a plant is set
+ * The stage cost and d_us take a_i.  Written this way beta = 0 gives l_i = s_i and du = +inf selects l_i, exactly: with d_beta
+ * NULL or 0, d_du_max NULL or +inf and delay = 0 the rollout returns the bits of tolg_policy_rollout_margins for every output
+ * they share.  lb, ub, beta, du_max and u_init are [B][m]; the library does not read them on the host (beta in [0, 1), du_max
+ * > 0 and lb <= ub are the caller's promise; check_actuator in the binding converts tau and a rate and checks them).  For the
+ * SO3 family rows 3..5 of lb, ub and u_init must contain or equal 0, the box's rule. */
+#define TOLG_MAX_ACT_DELAY 4
+typedef struct tolg_actuator {
+  const double *d_lb, *d_ub;   /* [B][m], both or neither */
+  const double *d_beta;        /* [B][m] or NULL (= 0) */
+  const double *d_du_max;      /* [B][m] or NULL (= +inf) */
+  const double *d_u_init;      /* [B][m] or NULL (= u*_0); unused by the MPC call */
+  int32_t delay;               /* 0..TOLG_MAX_ACT_DELAY */
+} tolg_actuator;
+/* tolg_policy_rollout_actuated: tolg_policy_rollout_margins with the model above in place of the box alone.  Every rule of the
+ * margins call not named here holds: plant, references and weights per trajectory, both sample orders, clearance and pose
+ * outputs with their attach conditions, J the tracking cost alone, the held policy left alone, a sample's bits independent of S
+ * and of its neighbours, an output's bits independent of which others are asked for.  d_n_sat and d_u_excess keep their
+ * definitions, on the delayed command d_i.  Three more outputs, each may be NULL:
+ *        d_u_cmd [B][S][N][m]  the commands c_i
+ *        d_n_rate [B][S]       the number of pairs (i, a) the rate limit moved
+ *        d_u_gap [B][S]        max_{i,a} |a_i - c_i| (fmax: a NaN is passed over), the distance between what was asked for and
+ *                              what the vehicle got
+ * TOLG_E_ARG: the margins call's conditions; act NULL; exactly one NULL bound; delay outside 0..TOLG_MAX_ACT_DELAY.  A refused
+ * call changes nothing.
+ * Cost on an MI355X: INTEGRATION.md 3t (measured at 4096 x 200, S = 16, over the margins call with the same box and
+ * outputs: +20 % with delay = 0, +28 % with delay = 1, +33 % with delay = 4; the expectation of a few per cent did not hold).
+ *
+ * tolg_mpc_advance_actuated: tolg_mpc_advance_limited with the model on the single command c = u*_0 of the step.  The
+ * actuator's memory between steps is the caller's d_act_state [B][1 + delay][m], updated in place: row 0 the last applied
+ * input, rows 1..delay the pending commands, oldest first.  The row-1 command is applied at this step (delay = 0: c itself),
+ * rows 2.. move down one row and c goes to row delay.  d_u_applied, x_next, xs_warm[0] and d_J_cl take the applied input; the
+ * warm tail and us_warm are tolg_mpc_advance's (the planner does not know the actuator, as it does not know the box).
+ * d_n_sat [B], d_n_rate [B]: the inputs of this step the box / the rate limit moved; each may be NULL.  A second call with a
+ * restored d_act_state gives the same bits.
+ * TOLG_E_ARG: the conditions of tolg_mpc_advance; a NULL d_act_state; act NULL, exactly one NULL bound, delay out of range.
+ *
+ * Out of scope: the output-feedback loop (tolg_policy_rollout_estimated carries two chains in one quad and has no registers
+ * left for the actuator's state); an analytic companion in tolg_policy_covariance (the augmented state has 12 + m coordinates,
+ * the sweep's layout is one 16-lane row per trajectory); an actuator model inside the planner. */
+int tolg_policy_rollout_actuated(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w,
+                                 const tolg_actuator* act, double* d_J, int32_t* d_status, double* d_xs_q, double* d_xs_xi,
+                                 double* d_us, int32_t* d_n_sat, double* d_u_excess, double* d_clear, int32_t* d_clear_knot,
+                                 double* d_pose_margin, int32_t* d_pose_knot, int32_t* d_viol_pos, int32_t* d_viol_pose,
+                                 double* d_u_cmd, int32_t* d_n_rate, double* d_u_gap, void* stream);
+int tolg_mpc_advance_actuated(tolg_handle_t h, int32_t B, const double* d_w, const tolg_actuator* act, double* d_act_state,
+                              double* d_x_next_q, double* d_x_next_xi, double* d_u_applied, double* d_xs_q_warm,
+                              double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl, int32_t* d_n_sat, int32_t* d_n_rate,
+                              void* stream);
+
 /* tolg_policy_covariance: the closed-loop covariance of the held policy to first order ("LinCov"), the analytic companion of
  * tolg_policy_rollout's sampling.  In the coordinates of tolg_policy_rollout and of K, e_i = [Log(q*_i^-1 q^_i); xi^_i - xi*_i]
  * (twist order [omega, v]), about the held nominal x*_i, u*_i:

@@ -2,7 +2,7 @@
 solved 4096 x 200 SE3 tracking batch, J and status only.
 
 usage: python tools/bench_policy.py [--B 4096] [--N 200] [--S 1,16,64] [--rounds 7] [--iters 20] [--layouts samples,traj]
-                                    [--limits | --margins] [--out FILE.json]
+                                    [--limits | --margins | --actuator] [--out FILE.json]
 
 One process.  The batch is solved once, untimed (multiple shooting, accept-always, 20 iterations), once per sample order of
 k_policy_rollout: `samples` (the default order, the samples of one trajectory side by side in a wavefront) and `traj`
@@ -24,7 +24,14 @@ trajectory, tilt and view cones alternating, built on its nominal path), `+count
 nominal clears by 0.2 in the cosine: few pairs (sample, knot) outside) and `+counts most` (cones at the median of the nominal's own cosines
 and spheres the nominal grazes: most samples outside at most knots, the worst case for the atomics).  Last, at the middle S,
 the alternative the report replaces: policy_rollout(trajectories=True) and the host rollout_margins on the device tensors,
-wall clock with a synchronisation, and the bytes of the trajectories it writes."""
+wall clock with a synchronisation, and the bytes of the trajectories it writes.
+
+--actuator: instead, per S and in the first layout, tolg_policy_rollout_margins under the box of --limits (`margins`: J, status,
+n_sat, u_excess) and tolg_policy_rollout_actuated with the same box and the same outputs behind a lag of 1.5 knots and a rate
+limit of a twentieth of the box's width per knot, at delays of 0, 1 and 4 knots (`actuated D=...`), in the same alternating
+rounds; the ratio of each to `margins`.  The batch is solved with the input weight at 10 (ACT_R_SCALE), not the headline's
+1e-5: at the headline's gains no sample stays finite behind a knot of delay, and a call that carries NaNs down the horizon
+does not cost what a finite one costs."""
 import argparse
 import ctypes as C
 import os
@@ -41,6 +48,7 @@ def parse_args(argv=None):
     ap.add_argument("--layouts", default="samples,traj")
     ap.add_argument("--limits", action="store_true", help="time tolg_policy_rollout_limited beside tolg_policy_rollout")
     ap.add_argument("--margins", action="store_true", help="time the reports of tolg_policy_rollout_margins, each added in turn")
+    ap.add_argument("--actuator", action="store_true", help="time tolg_policy_rollout_actuated beside tolg_policy_rollout_margins")
     add_common_args(ap, "out")
     a = ap.parse_args(argv)
     a.S = [int(s) for s in a.S.split(",")]
@@ -62,7 +70,8 @@ def main(argv=None):
     from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
 
     B, N = a.B, a.N
-    prob, q, xi, us = workloads.se3_tracking(B, N=N)
+    # (--actuator: a loop soft enough to stay finite behind four knots of delay, so that both calls time finite samples)
+    prob, q, xi, us = workloads.se3_tracking(B, N=N, **(dict(R_scale=ACT_R_SCALE) if a.actuator else {}))
     m = prob.m
     solvers = {}
     for layout in a.layouts:
@@ -95,6 +104,8 @@ def main(argv=None):
 
     if a.limits:
         return limits(a, solvers[a.layouts[0]], a.layouts[0], inputs, p)
+    if a.actuator:
+        return actuator(a, solvers[a.layouts[0]], a.layouts[0], inputs, p)
     if a.margins:
         return margins(a, prob, (q, xi, us), solvers[a.layouts[0]], a.layouts[0], inputs, p)
     names = [(layout, S) for S in a.S for layout in a.layouts] + ["rollout"]
@@ -176,6 +187,67 @@ def limits(a, s, layout, inputs, p):
             rows.append(row)
             print_row(row)
     s.set_al_obstacles(None)
+    res = dict(B=B, N=N, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(s.device), rows=rows)
+    emit(res, a.out)
+    return res
+
+
+ACT_FORMS = ("margins", "actuated D=0", "actuated D=1", "actuated D=4")
+ACT_R_SCALE = 10.0  # the input weight of --actuator's batch: at the headline's 1e-5 no sample survives a knot of delay
+
+
+def actuator(a, s, layout, inputs, p):
+    """tolg_policy_rollout_margins under the box of --limits (J, status, n_sat, u_excess) and tolg_policy_rollout_actuated with
+    the same box and the same outputs behind a lag of 1.5 knots and a rate limit of a twentieth of the box's width per knot, at
+    delays of 0, 1 and 4 knots, in alternating rounds."""
+    import math
+    import torch
+    from trajectory_optimization_matrix_lie_groups_amd import _capi
+    B, N = a.B, a.N
+    f64 = dict(dtype=torch.float64, device=s.device)
+    nom = s.policy_rollout(S=1, trajectories=True)
+    lb, ub = nom.us[:, 0].amin(dim=1).contiguous(), nom.us[:, 0].amax(dim=1).contiguous()
+    beta = torch.full_like(lb, math.exp(-1.0 / 1.5))
+    du = (0.05 * (ub - lb)).clamp(min=1e-6).contiguous()
+    acts = {}
+    for D in (0, 1, 4):
+        st = _capi.Actuator()
+        st.d_lb, st.d_ub, st.d_beta, st.d_du_max, st.d_u_init, st.delay = (lb.data_ptr(), ub.data_ptr(), beta.data_ptr(),
+                                                                            du.data_ptr(), None, D)
+        acts["actuated D=%d" % D] = st
+    outs = {S: (torch.empty(B, S, dtype=torch.int32, device=s.device), torch.empty(B, S, **f64),
+                torch.empty(B, S, dtype=torch.int32, device=s.device), torch.empty(B, S, **f64)) for S in a.S}
+    none6, none3 = (None,) * 6, (None,) * 3
+
+    def call(name, reports=False):
+        S, form = name
+        dx0, w, J, st = inputs[S]
+        ns, ex, nr, gap = outs[S]
+        if form == "margins":
+            return s.lib.tolg_policy_rollout_margins(s._h, B, S, p(dx0), p(w), p(lb), p(ub), p(J), p(st), None, None, None, p(ns),
+                                                     p(ex), *none6, s._stream())
+        more = (None, p(nr), p(gap)) if reports else none3
+        return s.lib.tolg_policy_rollout_actuated(s._h, B, S, p(dx0), p(w), C.byref(acts[form]), p(J), p(st), None, None, None,
+                                                  p(ns), p(ex), *none6, *more, s._stream())
+
+    names = [(S, form) for S in a.S for form in ACT_FORMS]
+    times = event_rounds(names, call, a.rounds, a.iters)
+    rows = []
+    for S in a.S:
+        base = stats_row(times[(S, "margins")])
+        for form in ACT_FORMS:
+            row = dict(kernel="tolg_policy_rollout_margins" if form == "margins" else "tolg_policy_rollout_actuated", form=form,
+                       layout=layout, S=S, **stats_row(times[(S, form)]))
+            row.update(steps_per_s=B * S * N / (row["ms_median"] * 1e-3), vs_margins=row["ms_median"] / base["ms_median"] - 1,
+                       margins_spread=(base["ms_max"] - base["ms_min"]) / base["ms_median"])
+            assert call((S, form), reports=True) == 0
+            torch.cuda.synchronize()
+            ns, ex, nr, gap = outs[S]
+            row.update(saturated_samples=int((ns > 0).sum().item()), status_ok=int((inputs[S][3] == 0).sum().item()))
+            if form != "margins":
+                row.update(rate_limited_samples=int((nr > 0).sum().item()), u_gap_median=float(gap.nanmedian().item()))
+            rows.append(row)
+            print_row(row)
     res = dict(B=B, N=N, rounds=a.rounds, iters=a.iters, device=torch.cuda.get_device_name(s.device), rows=rows)
     emit(res, a.out)
     return res

@@ -13,6 +13,7 @@ OBS_KEEP_OUT, OBS_KEEP_IN, OBS_HALF_SPACE, OBS_COLUMN_Z = 0, 1, 2, 3  # TOLG_OBS
 MAX_POSE_CONSTRAINTS = 8  # TOLG_MAX_POSE_CONSTRAINTS
 POSE_TILT_CONE, POSE_VIEW_CONE = 0, 1  # TOLG_POSE_*
 PLANT_DIAG, PLANT_DENSE = 0, 1
+MAX_ACT_DELAY = 4  # TOLG_MAX_ACT_DELAY
 _ERR = {-1: "bad argument", -2: "workspace too small", -3: "kernel launch failed", -4: "inertia matrix singular"}
 
 
@@ -28,6 +29,12 @@ class Options(C.Structure):
                 ("max_reg", C.c_double), ("schedule", C.c_int32), ("check_every", C.c_int32)]
 
 
+class Actuator(C.Structure):
+    """tolg_actuator: device pointers [B][m] (0: the default of the header) and the delay in knots."""
+    _fields_ = [("d_lb", C.c_void_p), ("d_ub", C.c_void_p), ("d_beta", C.c_void_p), ("d_du_max", C.c_void_p),
+                ("d_u_init", C.c_void_p), ("delay", C.c_int32)]
+
+
 _lib = None
 SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_batch", "tolg_solve_begin",
            "tolg_solve_iterate", "tolg_solve_iterate_until", "tolg_solve_end", "tolg_solve_peek", "tolg_solve_active_count", "tolg_set_al", "tolg_al_update",
@@ -37,7 +44,8 @@ SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_ba
            "tolg_solve_begin_warm", "tolg_set_ref_windows", "tolg_mpc_advance", "tolg_obstacles_bytes", "tolg_set_al_obstacles", "tolg_obstacles_moving_bytes", "tolg_set_al_obstacles_moving",
            "tolg_al_update_state", "tolg_al_mpc_step", "tolg_set_al_obstacle_windows", "tolg_set_al_obstacle_kinds", "tolg_pose_constraints_bytes", "tolg_set_al_pose_constraints",
            "tolg_set_al_pose_constraint_windows", "tolg_al_mpc_step_pose", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_policy_covariance_estimated", "tolg_policy_rollout_estimated", "tolg_policy_rollout_limited", "tolg_mpc_advance_limited",
-           "tolg_policy_rollout_margins", "tolg_policy_rollout_estimated_limited", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
+           "tolg_policy_rollout_margins", "tolg_policy_rollout_estimated_limited", "tolg_policy_rollout_actuated",
+           "tolg_mpc_advance_actuated", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
 
 
 def load():
@@ -156,6 +164,11 @@ def load():
                                                           + [ip, dp, dp, ip, dp, ip, ip, ip, vp])
     lib.tolg_mpc_advance_limited.restype = C.c_int
     lib.tolg_mpc_advance_limited.argtypes = [vp, C.c_int32] + [dp] * 10 + [ip, vp]
+    lib.tolg_policy_rollout_actuated.restype = C.c_int
+    lib.tolg_policy_rollout_actuated.argtypes = ([vp, C.c_int32, C.c_int32, dp, dp, C.POINTER(Actuator)]
+                                                 + lib.tolg_policy_rollout_margins.argtypes[7:-1] + [dp, ip, dp, vp])
+    lib.tolg_mpc_advance_actuated.restype = C.c_int
+    lib.tolg_mpc_advance_actuated.argtypes = [vp, C.c_int32, dp, C.POINTER(Actuator)] + [dp] * 8 + [ip, ip, vp]
     lib.tolg_kernel_time.restype = C.c_int
     lib.tolg_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int64)]

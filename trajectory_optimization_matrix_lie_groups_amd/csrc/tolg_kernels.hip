@@ -3294,6 +3294,40 @@ struct PolicyLim {
   int *viol_pos, *viol_pose;  // [B][N+1], zeroed on the stream ahead of the launch
   int pose;               // pose_margin, pose_knot or viol_pose asked for
 };
+// The actuated form (tolg_policy_rollout_actuated; include/tolg.h states the model once): a PolicyAct in front in place of the
+// PolicyLim, which it carries -- the box, the reports and the margins are the limited form's, on the delayed command.  Between
+// the command c_i = u*_i + K_i e_i and the step stand a transport delay of `delay` knots, the box, a first-order lag and a rate
+// limit; the dynamics, the stage cost and us take the applied input a_i.  What it adds stays inside the quad:
+//  - a_{i-1}, beta and du_max of trajectory b: 3 M values in registers beside the box's 2 M, the same in all four lanes of a
+//    quad, as the command is;
+//  - the delay line, delay x M doubles per quad in an LDS ring private to the quad (act_ring: 16 quads x TOLG_MAX_ACT_DELAY x M
+//    doubles per workgroup, 3 KB at M = 6).  delay is a run-time, kernel-uniform argument.  The ring is filled with u_init ahead
+//    of the knot loop, so that knot i < delay reads u_init with no test of i; at knot i all four lanes read slot i mod delay
+//    (c_{i-delay}) at the top of the step, beside the gain loads and ahead of the Log and the gain product -- it depends on
+//    nothing the knot computes -- and lane 0 writes c_i to the same slot behind the gain product.  One wavefront per workgroup:
+//    LDS is in order, and a wave barrier (with wavefront-scope fences for the compiler) stands between a knot's write and the
+//    next knot's read.  delay = 0: no ring traffic, d_i = c_i.
+// The lag and the rate limit are written so that beta = 0 gives l = s and du_max = +inf selects l, to the bit: with both and
+// delay = 0 the form returns tolg_policy_rollout_margins' bits.
+struct PolicyAct {
+  PolicyLim lim;
+  const double *beta, *du_max, *u_init;  // [B][M], each may be null: 0, +inf, u*_0
+  double* u_cmd;                         // [B][S][N][M] outputs, each may be null
+  int* n_rate;                           // [B][S]
+  double* u_gap;
+  int delay;                             // 0..TOLG_MAX_ACT_DELAY
+};
+template <int M>
+TOLG_DEV double* act_ring() {
+  __shared__ double ring[16 * TOLG_MAX_ACT_DELAY * M];
+  return ring + (threadIdx.x >> 2) * (TOLG_MAX_ACT_DELAY * M);
+}
+// the PolicyLim of a closed-loop kernel's trailing arguments: its own, or the one its PolicyAct carries
+template <class... PA>
+TOLG_DEV PolicyLim policy_lim_arg(const PA&... pl) {
+  if constexpr (pack_has<PolicyAct, PA...>) return pack_arg<PolicyAct>(pl...).lim;
+  else return pack_arg<PolicyLim>(pl...);
+}
 TOLG_DEV void clear_knot_min(const Consts& C, size_t Bp, int b, int i, const V3& t, double& cmin, int& cknot) {
   const double* geo = C.obs + b + (size_t)i * C.obs_stride;
   const int K = C.obsK;
@@ -3402,11 +3436,13 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
                                                        const double* __restrict__ noise, double* __restrict__ Jout,
                                                        int* __restrict__ status, double* __restrict__ xs_q,
                                                        double* __restrict__ xs_xi, double* __restrict__ us, PA... pl) {
-  constexpr bool LIM = pack_has<PolicyLim, PA...>;
+  constexpr bool ACT = pack_has<PolicyAct, PA...>;
+  constexpr bool LIM = pack_has<PolicyLim, PA...> || ACT;
   Stamps<8> ST;
   const Consts& C = *P.c;
   const PlantArg pa = pack_arg<PlantArg>(pl...);
-  const PolicyLim L = pack_arg<PolicyLim>(pl...);
+  const PolicyLim L = policy_lim_arg(pl...);
+  const PolicyAct A = pack_arg<PolicyAct>(pl...);
   const size_t n = (size_t)P.B * (size_t)S;
   size_t c = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
   const int q = threadIdx.x & 3;
@@ -3432,8 +3468,56 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
   }
   int nsat = 0, cknot = 0, pknot = 0;
   double excess = 0.0, cmin = INFINITY, pmin = INFINITY;
+  // the actuated form: a_{i-1}, the lag and rate constants, the delayed command of the knot, the quad's ring and the slot of
+  // the knot in it, the knot itself (the lambdas below stand ahead of the knot loop), the two counts
+  double ap[M], beta[M], dum[M], dly[M], gap = 0.0;
+  double* ring = nullptr;
+  int sl = 0, ik = 0, nrate = 0;
+  if constexpr (ACT) {
+    ring = act_ring<M>();
+#pragma unroll
+    for (int a = 0; a < M; a++) {
+      ap[a] = A.u_init ? A.u_init[(size_t)b * M + a] : P.cur_u[UIDX(a, 0, b)];
+      beta[a] = A.beta ? A.beta[(size_t)b * M + a] : 0.0;
+      dum[a] = A.du_max ? A.du_max[(size_t)b * M + a] : INFINITY;
+    }
+    if (q == 0) {
+      for (int k = 0; k < A.delay; k++)
+#pragma unroll
+        for (int a = 0; a < M; a++) ring[k * M + a] = ap[a];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
   auto limit = [&](double (&u)[M]) {  // (not LIM: no code, roll_step's default)
-    if constexpr (LIM) {
+    if constexpr (ACT) {
+#pragma unroll
+      for (int a = 0; a < M; a++) {
+        const double cm = u[a];
+        const double uc = A.delay > 0 ? dly[a] : cm;  // d_i: the command of `delay` knots ago, u_init ahead of them
+        const bool lo = uc < lb[a], hi = uc > ub[a];
+        nsat += (lo || hi) ? 1 : 0;
+        const double sv = lo ? lb[a] : (hi ? ub[a] : uc);
+        excess = fmax(excess, fabs(sv - uc));
+        const double lg = sv - beta[a] * (sv - ap[a]);  // beta = 0: sv, to the bit
+        const double dl = lg - ap[a];
+        const bool up = dl > dum[a], dn = dl < -dum[a];  // du_max = +inf: neither
+        nrate += (up || dn) ? 1 : 0;
+        const double v = up ? ap[a] + dum[a] : (dn ? ap[a] - dum[a] : lg);
+        gap = fmax(gap, fabs(v - cm));
+        if (A.delay > 0 && q == 0) ring[sl * M + a] = cm;
+        if (A.u_cmd && writer) A.u_cmd[(bs * (size_t)N + ik) * M + a] = cm;
+        ap[a] = v;
+        u[a] = v;
+      }
+      if (A.delay > 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        sl = sl + 1 == A.delay ? 0 : sl + 1;
+      }
+    } else if constexpr (LIM) {
 #pragma unroll
       for (int a = 0; a < M; a++) {
         const double uc = u[a];
@@ -3460,8 +3544,16 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
     __builtin_amdgcn_sched_barrier(0);
     const PlantC Vi = plant_step<PL>(V);
     const auto& CS = plant_or_model<PL, PK>(C, Vi);
+    if constexpr (ACT) ik = i;
     const State Nx = roll_step<M, false, true, PK, false>(P, CS, DK, i, b, q, false, vb, sB, 0.0, Sa, Sn, un,
-                                                           [&](RollIn<M>& R) { roll_load<M, true>(P, i, b, q, vb, sB, R); },
+                                                           [&](RollIn<M>& R) {
+                                                             roll_load<M, true>(P, i, b, q, vb, sB, R);
+                                                             if constexpr (ACT) {  // the ring read, off the chain
+                                                               if (A.delay > 0)
+#pragma unroll
+                                                                 for (int a = 0; a < M; a++) dly[a] = ring[sl * M + a];
+                                                             }
+                                                           },
                                                            nullptr, ST, RollPre(), limit);
     if constexpr (LIM) margins_knot(C, L, (size_t)P.Bp, N, b, i, Sn.X, writer, traj_fast, cmin, cknot, pmin, pknot);
     J += knot_cost<M, true, PT>(P, C, i, b, Sn, un, false);
@@ -3496,6 +3588,10 @@ __global__ __launch_bounds__(64) void k_policy_rollout(Params P, int S, int traj
       if (L.clear_knot) L.clear_knot[bs] = cknot;
       if (L.pose_margin) L.pose_margin[bs] = pmin;
       if (L.pose_knot) L.pose_knot[bs] = pknot;
+    }
+    if constexpr (ACT) {
+      if (A.n_rate) A.n_rate[bs] = nrate;
+      if (A.u_gap) A.u_gap[bs] = gap;
     }
   }
 }
@@ -3669,6 +3765,17 @@ struct MpcLim {
   const double *lb, *ub;  // [B][M]
   int* n_sat;             // [B], may be null
 };
+// With an MpcAct in front (tolg_mpc_advance_actuated) end 0 runs the actuator model of include/tolg.h on the single command
+// c = u*_0 with the caller's state rows of trajectory b, state [B][1 + delay][M] updated in place by the one thread that owns
+// b: row 0 the last applied input, rows 1..delay the pending commands, oldest first.  lim's bounds may both be null here (no
+// box).  End 1 is untouched, as under the box.
+struct MpcAct {
+  MpcLim lim;
+  const double *beta, *du_max;  // [B][M], each may be null: 0, +inf
+  double* state;                // [B][1 + delay][M]
+  int* n_rate;                  // [B], may be null
+  int delay;
+};
 template <int M, int PK, int PT, int PL = PL_NONE, class... PA>
 __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __restrict__ w, double* __restrict__ x_next_q,
                                                      double* __restrict__ x_next_xi, double* __restrict__ u_applied,
@@ -3695,6 +3802,35 @@ __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __r
         u[a] = lo ? l : (hi ? h : uc);
       }
       if (L.n_sat) L.n_sat[b] = ns;
+    }
+  }
+  if constexpr (pack_has<MpcAct, PA...>) {
+    if (i == 0) {
+      const MpcAct A = pack_arg<MpcAct>(pl...);
+      double* st = A.state + (size_t)b * (size_t)(1 + A.delay) * M;
+      int ns = 0, nr = 0;
+#pragma unroll
+      for (int a = 0; a < M; a++) {
+        const double cm = u[a];
+        const double uc = A.delay > 0 ? st[M + a] : cm;  // row 1: the oldest pending command
+        const double l = A.lim.lb ? A.lim.lb[(size_t)b * M + a] : -INFINITY, h = A.lim.ub ? A.lim.ub[(size_t)b * M + a] : INFINITY;
+        const bool lo = uc < l, hi = uc > h;
+        ns += (lo || hi) ? 1 : 0;
+        const double sv = lo ? l : (hi ? h : uc);
+        const double be = A.beta ? A.beta[(size_t)b * M + a] : 0.0, dm = A.du_max ? A.du_max[(size_t)b * M + a] : INFINITY;
+        const double ap = st[a];
+        const double lg = sv - be * (sv - ap);
+        const double dl = lg - ap;
+        const bool up = dl > dm, dn = dl < -dm;
+        nr += (up || dn) ? 1 : 0;
+        const double v = up ? ap + dm : (dn ? ap - dm : lg);
+        for (int k = 1; k < A.delay; k++) st[k * M + a] = st[(k + 1) * M + a];  // the pending commands move down a row
+        if (A.delay > 0) st[A.delay * M + a] = cm;
+        st[a] = v;
+        u[a] = v;
+      }
+      if (A.lim.n_sat) A.lim.n_sat[b] = ns;
+      if (A.n_rate) A.n_rate[b] = nr;
     }
   }
   State S;
@@ -5334,6 +5470,9 @@ struct KernelTable {
   ClosedLoop<Params, int, int, const double*, const double*, double*, int*, double*, double*, double*, PolicyLim> policy_rollout_lim;
   ClosedLoop<Params, const double*, double*, double*, double*, double*, double*, double*> mpc_advance;
   ClosedLoop<Params, const double*, double*, double*, double*, double*, double*, double*, MpcLim> mpc_advance_lim;
+  // ... and behind the actuator model (tolg_policy_rollout_actuated, tolg_mpc_advance_actuated)
+  ClosedLoop<Params, int, int, const double*, const double*, double*, int*, double*, double*, double*, PolicyAct> policy_rollout_act;
+  ClosedLoop<Params, const double*, double*, double*, double*, double*, double*, double*, MpcAct> mpc_advance_act;
   void (*policy_covariance)(Params, const double*, const double*, double*, double*, double*, double*);  // tolg_policy_covariance
   void (*policy_value)(Params, const double*, const double*, double*, double*, double*, double*, double*);  // tolg_policy_value
   // output feedback: tolg_policy_covariance_estimated, tolg_policy_rollout_estimated
@@ -5417,6 +5556,11 @@ static KernelTable kernel_table(int lds_per_block) {
                    {k_mpc_advance<M, PK, PTC, PL_DIAG, PlantArg>, k_mpc_advance<M, PK, PTC, PL_DENSE, PlantArg>}};
   t.mpc_advance_lim = {k_mpc_advance<M, PK, PTC, PL_NONE, MpcLim>,
                        {k_mpc_advance<M, PK, PTC, PL_DIAG, MpcLim, PlantArg>, k_mpc_advance<M, PK, PTC, PL_DENSE, MpcLim, PlantArg>}};
+  t.policy_rollout_act = {k_policy_rollout<M, PK, PTC, PL_NONE, PolicyAct>,
+                          {k_policy_rollout<M, PK, PTC, PL_DIAG, PolicyAct, PlantArg>,
+                           k_policy_rollout<M, PK, PTC, PL_DENSE, PolicyAct, PlantArg>}};
+  t.mpc_advance_act = {k_mpc_advance<M, PK, PTC, PL_NONE, MpcAct>,
+                       {k_mpc_advance<M, PK, PTC, PL_DIAG, MpcAct, PlantArg>, k_mpc_advance<M, PK, PTC, PL_DENSE, MpcAct, PlantArg>}};
   t.policy_covariance = k_policy_covariance<M, PK>;  // (reads neither reference nor weights: one kernel for every PT)
   t.policy_value = k_policy_value<M, PK, PT & ~PT_OBS>;  // (the tracking cost's derivatives: reference and weights, no spheres)
   t.policy_covariance_est = k_policy_covariance_est<M, PK>;
@@ -7016,6 +7160,7 @@ static int zero_counts(const PolicyLim& L, int B, int N, hipStream_t st) {
   if (L.viol_pose && hipMemsetAsync(L.viol_pose, 0, nv, st) != hipSuccess) return TOLG_E_LAUNCH;
   return 0;
 }
+static int zero_counts(const PolicyAct& A, int B, int N, hipStream_t st) { return zero_counts(A.lim, B, N, st); }
 // tolg_policy_rollout and tolg_policy_rollout_limited: the rules both share, then the kernel of k with lim (none, or the
 // PolicyLim) behind the rollout's arguments
 template <class K, class... LIM>
@@ -7068,6 +7213,25 @@ extern "C" int tolg_policy_rollout_limited(tolg_handle_t h, int32_t B, int32_t S
                                            double* d_clear, int32_t* d_clear_knot, void* stream) {
   return tolg_policy_rollout_margins(h, B, S, d_dx0, d_w, d_u_lb, d_u_ub, d_J, d_status, d_xs_q, d_xs_xi, d_us, d_n_sat, d_u_excess,
                                      d_clear, d_clear_knot, nullptr, nullptr, nullptr, nullptr, stream);
+}
+// what both actuated calls check of their tolg_actuator (the arrays are not read on the host)
+static bool actuator_ok(const tolg_actuator* act) {
+  return act && (act->d_lb == nullptr) == (act->d_ub == nullptr) && act->delay >= 0 && act->delay <= TOLG_MAX_ACT_DELAY;
+}
+extern "C" int tolg_policy_rollout_actuated(tolg_handle_t h, int32_t B, int32_t S, const double* d_dx0, const double* d_w,
+                                            const tolg_actuator* act, double* d_J, int32_t* d_status, double* d_xs_q,
+                                            double* d_xs_xi, double* d_us, int32_t* d_n_sat, double* d_u_excess, double* d_clear,
+                                            int32_t* d_clear_knot, double* d_pose_margin, int32_t* d_pose_knot,
+                                            int32_t* d_viol_pos, int32_t* d_viol_pose, double* d_u_cmd, int32_t* d_n_rate,
+                                            double* d_u_gap, void* stream) {
+  PolicyAct A;
+  if (S < 1 || !actuator_ok(act) ||
+      !policy_lim(h, B, act->d_lb, act->d_ub, d_n_sat, d_u_excess, d_clear, d_clear_knot, d_pose_margin, d_pose_knot, d_viol_pos,
+                  d_viol_pose, A.lim))
+    return TOLG_E_ARG;
+  A.beta = act->d_beta; A.du_max = act->d_du_max; A.u_init = act->d_u_init;
+  A.u_cmd = d_u_cmd; A.n_rate = d_n_rate; A.u_gap = d_u_gap; A.delay = act->delay;
+  return policy_rollout(h, h->kt.policy_rollout_act, B, S, d_dx0, d_w, d_J, d_status, d_xs_q, d_xs_xi, d_us, stream, A);
 }
 
 extern "C" int tolg_policy_covariance(tolg_handle_t h, int32_t B, const double* d_Sigma0, const double* d_W, double* d_Sigma,
@@ -7180,6 +7344,15 @@ extern "C" int tolg_mpc_advance_limited(tolg_handle_t h, int32_t B, const double
   if (!h || !d_u_lb || !d_u_ub) return TOLG_E_ARG;
   return mpc_advance(h, h->kt.mpc_advance_lim, B, d_w, d_x_next_q, d_x_next_xi, d_u_applied, d_xs_q_warm, d_xs_xi_warm,
                      d_us_warm, d_J_cl, stream, MpcLim{d_u_lb, d_u_ub, d_n_sat});
+}
+extern "C" int tolg_mpc_advance_actuated(tolg_handle_t h, int32_t B, const double* d_w, const tolg_actuator* act,
+                                         double* d_act_state, double* d_x_next_q, double* d_x_next_xi, double* d_u_applied,
+                                         double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl,
+                                         int32_t* d_n_sat, int32_t* d_n_rate, void* stream) {
+  if (!h || !d_act_state || !actuator_ok(act)) return TOLG_E_ARG;
+  return mpc_advance(h, h->kt.mpc_advance_act, B, d_w, d_x_next_q, d_x_next_xi, d_u_applied, d_xs_q_warm, d_xs_xi_warm,
+                     d_us_warm, d_J_cl, stream,
+                     MpcAct{MpcLim{act->d_lb, act->d_ub, d_n_sat}, act->d_beta, act->d_du_max, d_act_state, d_n_rate, act->delay});
 }
 
 extern "C" size_t tolg_plant_bytes(const tolg_problem* prob, int32_t max_batch, int32_t S) {

@@ -107,6 +107,11 @@ class PolicyRollout:
     # policy_rollout_estimated(estimates=True): the filter's posterior estimates x^_i (xs_q / xs_xi hold the true states)
     est_q: Optional[torch.Tensor] = None           # [B, S, N+1, 4, 4]
     est_xi: Optional[torch.Tensor] = None          # [B, S, N+1, 6]
+    # policy_rollout(act_*=): the commands c_i behind which the applied inputs `us` lag (commands=True), the inputs the rate
+    # limit moved, and the largest distance between a command and the input applied at its knot
+    u_cmd: Optional[torch.Tensor] = None           # [B, S, N, m]
+    n_rate: Optional[torch.Tensor] = None          # [B, S] int32
+    u_gap: Optional[torch.Tensor] = None           # [B, S]
 
 
 @dataclass
@@ -235,6 +240,7 @@ class MPCResult:
     iters: torch.Tensor    # [B, steps] int32: iterations of each step's solve
     status: torch.Tensor   # [B, steps] int32: its status
     n_sat: Optional[torch.Tensor] = None  # [B, steps] int32 (mpc(u_lb=, u_ub=)): the inputs of each step the box moved
+    n_rate: Optional[torch.Tensor] = None  # [B, steps] int32 (mpc(act_*=)): the inputs of each step the rate limit moved
     # mpc(lb=, ub=, obstacles=, obstacle_paths=): the planner's constraints
     max_violation: Optional[torch.Tensor] = None  # [B, steps] the largest g of each step's last plan (tolg_al_mpc_step)
     mu: Optional[torch.Tensor] = None             # [B] the penalty the loop ended with
@@ -269,6 +275,77 @@ def check_box(u_lb, u_ub, B, m, so3=False):
     if so3 and (np.any(out[0][:, 3:] > 0.0) or np.any(out[1][:, 3:] < 0.0)):
         raise ValueError("inputs 3..5 of the %s are unused and zero: their bounds must contain 0" % "SO3 family")
     return out[0], out[1]
+
+
+def check_actuator(u_lb, u_ub, tau, rate, delay, u_init, B, m, dt, so3=False):
+    """An actuator model (include/tolg.h, tolg_actuator) checked and converted on the host, ValueError before anything reaches
+    the device.  u_lb / u_ub: the box of check_box, both or neither (None).  tau: the lag's time constant in seconds, [m] or
+    [B, m] (or one number for every input, as rate), finite and >= 0 with 0 meaning no lag, converted to beta = exp(-dt / tau) (tau = 0 gives beta = 0.0 exactly).
+    rate: the slew limit in units per second, > 0 with inf allowed, converted to du = rate * dt per knot.  delay: whole knots,
+    an int in 0..4 (TOLG_MAX_ACT_DELAY).  u_init [m] or [B, m], finite: the input the actuator holds before the first knot
+    (None: u*_0).  so3: as check_box -- tau, rate and u_init may also be [3] or [B, 3] (rows 3..5 filled with 0, inf and 0), the
+    box rows 3..5 must contain 0 and u_init rows 3..5 equal it.
+    Returns (lb, ub, beta, du, u_init, delay): float64 [B, m] numpy arrays, None for what was not given."""
+    if not (np.ndim(dt) == 0 and np.isfinite(dt) and dt > 0):
+        raise ValueError("dt must be a positive number")
+    if isinstance(delay, (bool, np.bool_)) or not isinstance(delay, (int, np.integer)):
+        raise ValueError("act_delay must be an int (whole knots), got %r" % (delay,))
+    if not 0 <= int(delay) <= _capi.MAX_ACT_DELAY:
+        raise ValueError("act_delay %d outside 0..%d" % (delay, _capi.MAX_ACT_DELAY))
+    lb = ub = None
+    if u_lb is not None or u_ub is not None:
+        lb, ub = (np.array(a) for a in check_box(u_lb, u_ub, B, m, so3=so3))  # (copies: a broadcast view is read-only)
+
+    def rows(name, a, fill, scalar=True):
+        a = np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+        if scalar and a.ndim == 0:  # one value for every input
+            a = np.full(m, float(a))
+        sizes = (m, 3) if so3 else (m,)
+        if a.ndim not in (1, 2) or a.shape[-1] not in sizes or (a.ndim == 2 and a.shape[0] != B):
+            raise ValueError("%s has shape %s, expected (%s) or (%d, %s)" % (name, tuple(a.shape), " or ".join(map(str, sizes)),
+                                                                          B, " or ".join(map(str, sizes))))
+        if np.isnan(a).any():
+            raise ValueError("%s must not hold NaN" % name)
+        a = np.broadcast_to(a, (B, a.shape[-1]))
+        if a.shape[-1] != m:
+            a = np.concatenate([a, np.full((B, m - a.shape[-1]), fill)], axis=1)
+        return np.array(a, order="C")  # (a copy: a broadcast view is read-only)
+
+    beta = du = ui = None
+    if tau is not None:
+        t = rows("act_tau", tau, 0.0)
+        if not np.all(np.isfinite(t)) or np.any(t < 0.0):
+            raise ValueError("act_tau must be finite and >= 0 (seconds; 0: no lag)")
+        with np.errstate(divide="ignore"):
+            beta = np.where(t > 0.0, np.exp(-float(dt) / np.where(t > 0.0, t, 1.0)), 0.0)
+    if rate is not None:
+        r = rows("act_rate", rate, np.inf)
+        if np.any(r <= 0.0):
+            raise ValueError("act_rate must be > 0 (units per second; inf: no limit)")
+        du = r * float(dt)
+    if u_init is not None:
+        ui = rows("act_u_init", u_init, 0.0, scalar=False)
+        if not np.all(np.isfinite(ui)):
+            raise ValueError("act_u_init must be finite")
+        if so3 and np.any(ui[:, 3:] != 0.0):
+            raise ValueError("inputs 3..5 of the SO3 family are unused and zero: act_u_init must be 0 there")
+    return lb, ub, beta, du, ui, int(delay)
+
+
+def actuator_state(us0, delay):
+    """The initial actuator state of mpc_advance(act_state=) from u*_0 = us0 [B, m]: [B, 1 + delay, m], row 0 (the last applied
+    input) and the `delay` pending commands all u*_0 -- an actuator at rest on the first command.  A torch tensor gives a new
+    contiguous tensor on its device, anything else a float64 numpy array."""
+    if isinstance(delay, (bool, np.bool_)) or not isinstance(delay, (int, np.integer)) or not 0 <= delay <= _capi.MAX_ACT_DELAY:
+        raise ValueError("delay must be an int in 0..%d" % _capi.MAX_ACT_DELAY)
+    if isinstance(us0, torch.Tensor):
+        if us0.ndim != 2:
+            raise ValueError("us0 has shape %s, expected (B, m)" % (tuple(us0.shape),))
+        return us0.to(torch.float64)[:, None, :].repeat(1, 1 + int(delay), 1).contiguous()
+    a = np.asarray(us0, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("us0 has shape %s, expected (B, m)" % (tuple(a.shape),))
+    return np.ascontiguousarray(np.repeat(a[:, None, :], 1 + int(delay), axis=1))
 
 
 # The kinds of a constraint slot (TOLG_OBS_*, include/tolg.h has the table of rows and clearances), by number or by name
@@ -1566,6 +1643,15 @@ class BatchedTrackingILQR:
         lb, ub = check_box(u_lb, u_ub, B, self.m, so3=self.problem.kind in ("so3", "pendulum3d"))
         return self._dev(lb, (B, self.m)), self._dev(ub, (B, self.m))
 
+    @staticmethod
+    def _actuator_struct(box, d_act, delay):
+        """The tolg_actuator of a call from its device tensors: box (lb, ub) or None, d_act (beta, du, u_init), each or None."""
+        a = _capi.Actuator()
+        a.d_lb, a.d_ub = (None, None) if box is None else (box[0].data_ptr(), box[1].data_ptr())
+        a.d_beta, a.d_du_max, a.d_u_init = (None if t is None else t.data_ptr() for t in d_act)
+        a.delay = int(delay)
+        return a
+
     def _margin_flags(self, clearance, pose_margin, violations):
         """The report keywords of the sampled loops checked against the families attached, ValueError before anything reaches
         the device.  Returns (viol_pos, viol_pose): which counts violations=True fills -- those of every family attached."""
@@ -1597,7 +1683,8 @@ class BatchedTrackingILQR:
                 _ptr(r.pose_margin_knot), _ptr(r.viol_pos), _ptr(r.viol_pose))
 
     def policy_rollout(self, dx0=None, noise=None, S=None, trajectories=False, plant_J=None, plant_pend=None, u_lb=None,
-                       u_ub=None, clearance=False, pose_margin=False, violations=False) -> PolicyRollout:
+                       u_ub=None, clearance=False, pose_margin=False, violations=False, act_tau=None, act_rate=None,
+                       act_delay=0, act_u_init=None, commands=False) -> PolicyRollout:
         """S closed-loop rollouts per trajectory of the held policy u = u*_i + K_i (x (-) x*_i) with exact dynamics
         (tolg_policy_rollout).  dx0 [B, S, 12]: start perturbation in the error coordinates of K (pose x*_0 Exp(dx0[:6]),
         twist xi*_0 + dx0[6:]); noise [B, S, N, 6]: added to the twist behind every step.  Either may be None (zero); S is
@@ -1618,10 +1705,25 @@ class BatchedTrackingILQR:
         violations=True: per knot, how many of the S samples are outside the allowed set there, viol_pos [B, N+1] for the
         position slots and viol_pose [B, N+1] for the pose slots, each when its family is attached (ValueError if neither is):
         viol / S estimates the violation probability a kappa-sigma margin promises at each knot.  rollout_margins() is the
-        definition of all four.  With either keyword the call is tolg_policy_rollout_margins."""
+        definition of all four.  With either keyword the call is tolg_policy_rollout_margins.
+        act_tau / act_rate / act_delay / act_u_init (check_actuator): the actuator between the command and the step -- a
+        transport delay of act_delay knots, the box u_lb / u_ub if given, a first-order lag of time constant act_tau seconds
+        and a slew limit of act_rate units per second (include/tolg.h states the model).  `us` and J then take the applied
+        input, n_sat / u_excess count on the delayed command, and the result carries n_rate [B, S], the inputs the rate limit
+        moved, u_gap [B, S], the largest |applied - commanded| of the sample, and with commands=True u_cmd [B, S, N, m], the
+        commands themselves.  With any of the five the call is tolg_policy_rollout_actuated, beside every other keyword; with
+        none of them it goes through the entry point it always did."""
         B = self._held_B()
         viol = self._margin_flags(clearance, pose_margin, violations)
-        box = self._box(B, u_lb, u_ub)
+        actuated = act_tau is not None or act_rate is not None or act_u_init is not None or commands or \
+            isinstance(act_delay, (bool, np.bool_)) or act_delay != 0
+        act = None
+        if actuated:
+            act = check_actuator(u_lb, u_ub, act_tau, act_rate, act_delay, act_u_init, B, self.m, self.problem.dt,
+                                 so3=self.problem.kind in ("so3", "pendulum3d"))
+            box = None if act[0] is None else (self._dev(act[0], (B, self.m)), self._dev(act[1], (B, self.m)))
+        else:
+            box = self._box(B, u_lb, u_ub)
         shapes = []
         if dx0 is not None:
             dx0 = _checked("dx0", dx0, (B, None, 12), finite=True)
@@ -1652,10 +1754,21 @@ class BatchedTrackingILQR:
         limited = box is not None or clearance
         margins = pose_margin or violations
         out = self._margin_outputs(r, B, S, box, clearance, pose_margin, viol)
+        d_act = None
+        if actuated:
+            d_act = tuple(None if a is None else self._dev(a, (B, self.m)) for a in act[2:5])
+            i32 = dict(dtype=torch.int32, device=self.device)
+            r.n_rate, r.u_gap = torch.empty(B, S, **i32), torch.empty(B, S, **f64)
+            if commands:
+                r.u_cmd = torch.empty(B, S, self.N, self.m, **f64)
         d_plant = self._use_plant(B, plant)
         try:
-            self._hold((d_dx0, d_w, d_plant, box))
-            if limited or margins:
+            self._hold((d_dx0, d_w, d_plant, box, d_act))
+            if actuated:
+                a = self._actuator_struct(box, d_act, act[5])
+                self._call("tolg_policy_rollout_actuated", B, S, _ptr(d_dx0), _ptr(d_w), C.byref(a), _ptr(r.J), _ptr(r.status),
+                           _ptr(r.xs_q), _ptr(r.xs_xi), _ptr(r.us), *out, _ptr(r.u_cmd), _ptr(r.n_rate), _ptr(r.u_gap))
+            elif limited or margins:
                 lb, ub = box if box is not None else (None, None)
                 # (a call with neither new keyword goes through the entry point it always did)
                 self._call("tolg_policy_rollout_margins" if margins else "tolg_policy_rollout_limited", B, S, _ptr(d_dx0),
@@ -1903,7 +2016,8 @@ class BatchedTrackingILQR:
         d, T = self._schedule_paths(B, path_scale)
         self._sched_next = (d, T, self._check_t0(B, t0), int(t))
 
-    def mpc_advance(self, w=None, J_cl=None, plant_J=None, plant_pend=None, u_lb=None, u_ub=None):
+    def mpc_advance(self, w=None, J_cl=None, plant_J=None, plant_pend=None, u_lb=None, u_ub=None, act_tau=None, act_rate=None,
+                    act_delay=0, act_state=None):
         """One receding-horizon step on the held policy (tolg_mpc_advance): x_next = f(x*_0, u*_0) + [0; w] with the exact
         dynamics, u = u*_0, and the warm start of the next step (xs_q / xs_xi [B, N+1, ...], us [B, N, m]: the solution
         shifted by one knot, x_next in front, the tail propagated with the last input).  w [B, 6] (None: 0) is added to the
@@ -1913,34 +2027,69 @@ class BatchedTrackingILQR:
         u_lb / u_ub [m] or [B, m] (check_box; both or neither): the actuator's box (tolg_mpc_advance_limited) -- u is
         clamp(u*_0), x_next and xs_q[:, 0] step with it, J_cl takes l(x*_0, u); the rest of the warm start is the unclamped
         one, and the dict also holds n_sat [B] int32, the inputs the box moved.
+        act_tau / act_rate / act_delay (check_actuator) with act_state: the actuator model between u*_0 and the plant
+        (tolg_mpc_advance_actuated) beside the box if one is given.  act_state is a contiguous float64 device tensor
+        [B, 1 + act_delay, m] (actuator_state builds the first one from u*_0) and is updated in place: row 0 the last applied
+        input, rows 1.. the pending commands, oldest first.  u, x_next, xs_q[:, 0] and J_cl take the applied input; the dict
+        also holds n_sat and n_rate [B] int32, the inputs of the step the box / the rate limit moved.
         Returns a dict of device tensors: x_next_q [B, 4, 4], x_next_xi, u [B, m], xs_q, xs_xi, us, J_cl."""
         B = self._held_B()
-        box = self._box(B, u_lb, u_ub)
+        actuated = act_tau is not None or act_rate is not None or act_state is not None or \
+            isinstance(act_delay, (bool, np.bool_)) or act_delay != 0
+        act = None
+        if actuated:
+            act = self._check_actuated(B, u_lb, u_ub, act_tau, act_rate, act_delay, act_state)
+            box = act[0]
+        else:
+            box = self._box(B, u_lb, u_ub)
         d_w = None if w is None else self._dev(_checked("w", w, (B, 6), finite=True), (B, 6))
         if J_cl is not None and (not isinstance(J_cl, torch.Tensor) or J_cl.dtype != torch.float64 or
                                  tuple(J_cl.shape) != (B,) or J_cl.device != self.device or not J_cl.is_contiguous()):
             raise ValueError("J_cl must be a contiguous float64 tensor of shape (%d,) on %s" % (B, self.device))
         plant = self._check_plant(B, plant_J, plant_pend, per_sample=False)
-        r = self._advance_out(B, J_cl, limited=box is not None)
+        r = self._advance_out(B, J_cl, limited=box is not None or actuated, actuated=actuated)
         d_plant = self._use_plant(B, plant)
         try:
-            self._hold((d_w, d_plant, box))
-            self._advance(B, d_w, r, box)
+            self._hold((d_w, d_plant, box, act))
+            self._advance(B, d_w, r, box, act)
         finally:
             if plant is not None:
                 self._clear_plant()
         return r
 
-    def _advance_out(self, B, J_cl, limited=False):
+    def _check_actuated(self, B, u_lb, u_ub, act_tau, act_rate, act_delay, act_state, own=False):
+        """The actuator of an MPC step checked (check_actuator) and on the device: (box or None, (beta, du, None), delay,
+        act_state).  act_state must be the caller's contiguous float64 device tensor [B, 1 + delay, m]; own: the loop's own,
+        allocated here and filled by it."""
+        lb, ub, beta, du, _, delay = check_actuator(u_lb, u_ub, act_tau, act_rate, act_delay, None, B, self.m, self.problem.dt,
+                                                    so3=self.problem.kind in ("so3", "pendulum3d"))
+        if own:
+            act_state = torch.empty(B, 1 + delay, self.m, dtype=torch.float64, device=self.device)
+        if (not isinstance(act_state, torch.Tensor) or act_state.dtype != torch.float64 or
+                tuple(act_state.shape) != (B, 1 + delay, self.m) or act_state.device != self.device or
+                not act_state.is_contiguous()):
+            raise ValueError("act_state must be a contiguous float64 tensor of shape (%d, %d, %d) on %s (actuator_state builds "
+                             "one)" % (B, 1 + delay, self.m, self.device))
+        box = None if lb is None else (self._dev(lb, (B, self.m)), self._dev(ub, (B, self.m)))
+        d_act = tuple(None if a is None else self._dev(a, (B, self.m)) for a in (beta, du)) + (None,)
+        return box, d_act, delay, act_state
+
+    def _advance_out(self, B, J_cl, limited=False, actuated=False):
         f64 = dict(dtype=torch.float64, device=self.device)
         more = dict(n_sat=torch.empty(B, dtype=torch.int32, device=self.device)) if limited else {}
+        if actuated:
+            more["n_rate"] = torch.empty(B, dtype=torch.int32, device=self.device)
         return dict(x_next_q=torch.empty(B, 4, 4, **f64), x_next_xi=torch.empty(B, 6, **f64), u=torch.empty(B, self.m, **f64),
                     xs_q=torch.empty(B, self.N + 1, 4, 4, **f64), xs_xi=torch.empty(B, self.N + 1, 6, **f64),
                     us=torch.empty(B, self.N, self.m, **f64), J_cl=J_cl, **more)
 
-    def _advance(self, B, d_w, r, box=None):
+    def _advance(self, B, d_w, r, box=None, act=None):
         out = tuple(_ptr(r[k]) for k in ("x_next_q", "x_next_xi", "u", "xs_q", "xs_xi", "us", "J_cl"))
-        if box is None:
+        if act is not None:
+            a = self._actuator_struct(act[0], act[1], act[2])
+            self._call("tolg_mpc_advance_actuated", B, _ptr(d_w), C.byref(a), _ptr(act[3]), *out, _ptr(r["n_sat"]),
+                       _ptr(r["n_rate"]))
+        elif box is None:
             self._call("tolg_mpc_advance", B, _ptr(d_w), *out)
         else:
             self._call("tolg_mpc_advance_limited", B, _ptr(d_w), _ptr(box[0]), _ptr(box[1]), *out, _ptr(r["n_sat"]))
@@ -1950,7 +2099,7 @@ class BatchedTrackingILQR:
             check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None, plant_J=None, plant_pend=None, u_lb=None,
             u_ub=None, lb=None, ub=None, obstacles=None, obstacle_paths=None, obstacle_kinds=None, first_al_iters=3,
             al_iters_per_step=1, mu0=1e-2, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2, pose_scale_path=None,
-            pose_constraints=None, pose_paths=None, pose_kinds=None) -> MPCResult:
+            pose_constraints=None, pose_paths=None, pose_kinds=None, act_tau=None, act_rate=None, act_delay=0) -> MPCResult:
         """Receding-horizon MPC: `steps` closed-loop steps of B trajectories, each tracking its own path from its own phase.
         Step t: windows min(t0[b] + t + i, T) of the paths (tolg_set_ref_windows), a solve of first_iters (t = 0) or
         iters_per_step iterations, then tolg_mpc_advance applies u*_0, steps the plant with the exact dynamics and adds the
@@ -1965,7 +2114,10 @@ class BatchedTrackingILQR:
         plant step; the FitResult carries histories then).  plant_J [B, 6, 6] / plant_pend [B, 2]: the plant every step's
         x_next is stepped with (model mismatch, as mpc_advance; None: the model); the solves plan on the model.  u_lb / u_ub [m] or
         [B, m]: the actuator's box (as mpc_advance: every step applies clamp(u*_0); it clips the plant only and is independent
-        of the planner's lb / ub), the result then carries n_sat [B, steps].  Not with an
+        of the planner's lb / ub), the result then carries n_sat [B, steps].  act_tau / act_rate / act_delay (check_actuator):
+        the actuator model between every step's u*_0 and the plant (as mpc_advance; the loop owns the actuator's state across
+        the steps, at rest on the first step's u*_0), beside the box, the planner's constraints and the plant; `us` holds the
+        applied inputs and the result carries n_sat and n_rate [B, steps].  Not with an
         augmented-Lagrangian constraint the caller attached.  The handle is left on the shared reference and weights, without a
         plant, with no constraint attached.
         x0_q [B, 4, 4], x0_xi [B, 6], path_q [B, T+1, 4, 4], path_xi [B, T+1, 6].
@@ -2030,7 +2182,13 @@ class BatchedTrackingILQR:
         if spath is not None and b.wts is None:
             b.wts = tuple(self._dev(a, a.shape) for a in self._own_weights(B))
         plant = self._check_plant(B, plant_J, plant_pend, per_sample=False)
-        box = self._box(B, u_lb, u_ub)
+        actuated = act_tau is not None or act_rate is not None or isinstance(act_delay, (bool, np.bool_)) or act_delay != 0
+        act = None
+        if actuated:  # (the state is filled from the first step's u*_0, behind its solve)
+            act = self._check_actuated(B, u_lb, u_ub, act_tau, act_rate, act_delay, None, own=True)
+            box = act[0]
+        else:
+            box = self._box(B, u_lb, u_ub)
         if noise is not None:
             noise = _checked("noise", noise, (B, steps, 6), finite=True)
             noise = self._dev(np.ascontiguousarray(noise.transpose(1, 0, 2)), (steps, B, 6))  # step t: one contiguous [B, 6]
@@ -2066,14 +2224,16 @@ class BatchedTrackingILQR:
         res.xs_q[:, 0] = b.x_q.reshape(B, 4, 4)
         res.xs_xi[:, 0] = b.x_xi
         # the plant state and the warm start: written by tolg_mpc_advance, read by the next begin (stream-ordered)
-        adv = self._advance_out(B, res.J, limited=box is not None)
-        if box is not None:
+        adv = self._advance_out(B, res.J, limited=box is not None or actuated, actuated=actuated)
+        if box is not None or actuated:
             res.n_sat = torch.empty(B, steps, dtype=torch.int32, device=self.device)
+        if actuated:
+            res.n_rate = torch.empty(B, steps, dtype=torch.int32, device=self.device)
         x_q, x_xi, us = b.x_q, b.x_xi, b.us
         try:
             # the plant survives the solves of the loop (tolg_set_plant): set once, detached behind it
             d_plant = self._use_plant(B, plant)
-            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box, al, obs, pose, mu, maxviol, spath))
+            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box, al, obs, pose, mu, maxviol, spath, act))
             self._use_pt(B, None, b.wts)
             if al is not None:
                 self.set_al(*al)
@@ -2119,9 +2279,13 @@ class BatchedTrackingILQR:
                 res.status[:, t] = out.status
                 if on_step is not None:
                     on_step(t, out)
-                self._advance(B, None if noise is None else noise[t], adv, box)
-                if box is not None:
+                if actuated and t == 0:  # at rest on the first command
+                    act[3][:] = out.us[:, 0, None, :]
+                self._advance(B, None if noise is None else noise[t], adv, box, act)
+                if box is not None or actuated:
                     res.n_sat[:, t] = adv["n_sat"]
+                if actuated:
+                    res.n_rate[:, t] = adv["n_rate"]
                 res.us[:, t] = adv["u"]
                 res.xs_q[:, t + 1] = adv["x_next_q"]
                 res.xs_xi[:, t + 1] = adv["x_next_xi"]

@@ -275,6 +275,50 @@ def se3_policy_eval(B, S, N=200, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=
     return prob, x0_q, x0_xi, us0, dx0, noise
 
 
+def drone_actuated(B, S, N=400, tau=0.03, rate=None, delay=1, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=0.01, seed=SEED):
+    """drone_tracking's workload with se3_policy_eval's perturbations and a motor model (policy_rollout(act_*=)): a first-order
+    lag of tau seconds (30 ms, 7.5 knots at dt = 0.004) on every input, a transport delay of `delay` knots and a slew limit of
+    `rate` units per second per input -- None: the thrust may cross four times its hover value (mass x 9.81) in a second, each
+    torque 2 units.  Returns (prob, x0_q, x0_xi, us0, dx0 [B, S, 12], noise [B, S, N, 6], act) with act the keywords
+    dict(act_tau=, act_rate=, act_delay=)."""
+    prob, x0_q, x0_xi, us0 = drone_tracking(B, N=N, seed=seed)
+    rng = np.random.default_rng(seed + 3)
+    dx0 = np.concatenate([rng.normal(0.0, sigma_pose, (B, S, 6)), rng.normal(0.0, sigma_twist, (B, S, 6))], axis=2)
+    noise = rng.normal(0.0, sigma_noise, (B, S, N, 6))
+    if rate is None:
+        rate = np.array([2.0, 2.0, 2.0, 4.0 * 9.81 * float(prob.J[3, 3])])
+    act = dict(act_tau=np.full(4, float(tau)), act_rate=np.broadcast_to(np.asarray(rate, float), (4,)).copy(), act_delay=int(delay))
+    return prob, x0_q, x0_xi, us0, dx0, noise, act
+
+
+def se3_gain_sweep_actuated(B, S, N=200, centre=0.1, spread=10.0, tau=0.03, delay=1, sigma_pose=0.02, sigma_twist=0.02,
+                            sigma_noise=0.002, seed=SEED):
+    """A weight sweep on se3_tracking's workload (se3_weight_sweep's shape) along ONE direction, the loop gain: member b scales
+    Q and P by g_b and R by 1 / g_b, g log-spaced from centre / spread (member 0) to centre spread (member B - 1), so that the
+    feedback gains grow with b.  Without an actuator nothing tells the members apart but their weights: every one of them
+    tracks, and the analytic companions (policy_value, policy_covariance) describe that loop.  Behind a 30 ms motor (a lag of
+    tau seconds, 0.6 knots at dt = 0.05) and a delay of `delay` knots the low-gain half barely notices (J up by a few per
+    cent) while the high-gain half loses its phase margin: J rises by tens of per cent and the top of the sweep leaves the
+    finite numbers.  Every member is costed with ITS OWN weights, so a member is compared with itself, with and without the
+    actuator.
+    Returns (prob, x0_q, x0_xi, us0, Q [B, 12, 12], P [B, 12, 12], R [B, 6, 6], gain [B], high [B] bool -- the upper half of
+    the sweep --, dx0 [B, S, 12], noise [B, S, N, 6], act) with act = dict(act_tau=, act_delay=).  Every member starts from
+    the same state, member 0's."""
+    prob, x0_q, x0_xi, us0 = se3_tracking(B, N=N, R_scale=1e-3, seed=seed)
+    x0_q = np.repeat(np.asarray(x0_q)[:1], B, axis=0)
+    x0_xi = np.repeat(np.asarray(x0_xi)[:1], B, axis=0)
+    gain = float(centre) * (np.exp(np.linspace(-np.log(spread), np.log(spread), B)) if B > 1 else np.ones(1))
+    Q = gain[:, None, None] * prob.Q[None]
+    P = gain[:, None, None] * prob.P[None]
+    R = prob.R[None] / gain[:, None, None]
+    high = np.arange(B) >= (B + 1) // 2
+    rng = np.random.default_rng(seed + 3)
+    dx0 = np.concatenate([rng.normal(0.0, sigma_pose, (B, S, 6)), rng.normal(0.0, sigma_twist, (B, S, 6))], axis=2)
+    noise = rng.normal(0.0, sigma_noise, (B, S, N, 6))
+    act = dict(act_tau=np.full(6, float(tau)), act_delay=int(delay))
+    return prob, x0_q, x0_xi, us0, Q, P, R, gain, high, dx0, noise, act
+
+
 def se3_covariance(B, N=200, sigma_pose=0.05, sigma_twist=0.05, sigma_noise=0.01, seed=SEED):
     """Covariance inputs for the closed loop of se3_tracking's workload (BatchedTrackingILQR.policy_covariance), the analytic
     counterpart of se3_policy_eval's samples.  Returns (prob, x0_q, x0_xi, us0, Sigma0 [B, 12, 12], W [B, 6, 6]): seeded, per
