@@ -814,6 +814,63 @@ int tolg_policy_rollout_estimated_limited(tolg_handle_t h, int32_t B, int32_t S,
                                           double* d_clear, int32_t* d_clear_knot, double* d_pose_margin, int32_t* d_pose_knot,
                                           int32_t* d_viol_pos, int32_t* d_viol_pose, void* stream);
 
+/* Output feedback inside the receding-horizon loop: the filter of the two calls above, one knot at a time, with its (x^, P)
+ * carried by the caller from step to step.  A step of the loop is: measure at the world knot, solve from the posterior
+ * estimate, advance.  Both calls are O(B).  The conventions are those above: error coordinates, twist order [omega, v], right
+ * perturbation, the 12-bit mask, d_V [B][12] read on measured coordinates only, the SO3-family rule with zeros in the
+ * embedding's unused coordinates.  The actuator model (the actuated forms of the rollout and the advance) stays out of scope for output
+ * feedback, here as above.
+ *
+ * tolg_mpc_measure: the filter's update at one world knot, on the caller's buffers alone.
+ *   y = x (+) n
+ *   r[j] = ([Log(q^^-1 q_y); xi_y - xi^])[j] for measured j, 0 otherwise
+ *   for each measured j ascending: s = P[j][j] + V[j], c = P[:, j], P -= c c^T / s
+ *   L[:, j] = P^+[:, j] / V[j] (measured j), 0 (unmeasured j)
+ *   x^ <- x^ (+) L r, the pose re-normalised as the rollouts do
+ *   in : mask, d_V above; d_x_q [B][16], d_x_xi [B][6] the true state; d_n [B][12] measurement noise or NULL (= 0)
+ *   in/out: d_est_q [B][16], d_est_xi [B][6]   prior in, posterior out
+ *           d_P [B][12][12]                    prior in (upper triangle read), posterior out, mirrored: equal to its
+ *                                              transpose to the bit
+ *   out: d_L [B][12][12], d_innov [B][12] (r), d_var_est [B][12] (diag P^+, the bits of d_P's diagonal); each may be NULL.
+ * mask == 0 leaves the estimate bit for bit, gives L = 0 and r = 0, and P is its mirrored upper triangle.  A trajectory's bits
+ * depend on neither B nor its neighbours.  The call needs no held policy and touches none; it does not read the workspace and
+ * is legal during a solve in flight.
+ * TOLG_E_ARG: B outside 1..max_batch; a bad mask (above); a NULL d_V with mask != 0; a NULL state, estimate or d_P.  A refused
+ * call changes nothing.
+ *
+ * tolg_mpc_advance_estimated: tolg_mpc_advance_limited for a loop whose solve began from the posterior estimate, so that x*_0 of
+ * the held policy IS that estimate: a solve keeps x*_0 = x0 to the bit in both modes (single and multiple shooting), whether
+ * it converged or stopped at max_iter.  (In the workspace's own representation: the pose is held as a unit quaternion, and a
+ * [16] matrix that passes through it comes back equal to rounding, not to the bit -- xs_q[0] of tolg_solve_end is the round
+ * trip of d_x0_q, the same bits for every solve that began from it; the twist comes back to the bit.)
+ *   u = clamp(u*_0), the three-way select of tolg_mpc_advance_limited; d_u_lb, d_u_ub [B][m], both or neither (no clamp)
+ *   the true state, in place: x_true <- f(x_true, u) on plant row b where tolg_set_plant is attached with S = 1, else on the
+ *     model; then xi_true += w[b]
+ *   the estimate's prior: x_next = f(x*_0, u) on the MODEL, always, and w is not added (the filter knows the applied input and
+ *     not the disturbance); xs_warm[0] = x_next; the tail xs_warm[N] and us_warm are those of tolg_mpc_advance
+ *   the covariance, in place: P <- A P A^T + E W E^T, A = f_x(x*_0, u*_0) linearised by this call at the held nominal exactly
+ *     as tolg_policy_covariance_estimated does, E = [0; I6]; d_W [B][6][6] or NULL (= 0); upper triangles read, the result
+ *     mirrored to the bit; P = 0 with d_W NULL stays exact zeros
+ *   d_J_cl[b] += l(x_true before the step, u) at knot 0 of the window, under the tracking-cost rules of tolg_mpc_advance
+ *   d_n_sat as in tolg_mpc_advance_limited; 0 without a box
+ *   in : d_w [B][6] or NULL; the box; d_W
+ *   in/out: d_x_true_q [B][16], d_x_true_xi [B][6], d_P [B][12][12]: required
+ *   out: d_x_next_q, d_x_next_xi, d_u_applied, d_J_cl, d_n_sat: each may be NULL; the three warm buffers: required.
+ * Without a plant and with d_w NULL, x_next, u_applied, the warm start and n_sat are the bits of tolg_mpc_advance_limited;
+ * with x_true = x*_0 to the bit, x_true and the increment of J_cl are those of its x_next and J_cl (plant and w included).  The
+ * held policy is left alone: a second call with x_true and P restored gives the same bits.  A trajectory's bits depend on
+ * neither B nor its neighbours.
+ * TOLG_E_ARG: the conditions of tolg_mpc_advance_limited, except that both bounds may be NULL (exactly one is refused); a NULL
+ * d_x_true_q, d_x_true_xi or d_P.  A refused call changes nothing.
+ * Cost on an MI355X: INTEGRATION.md 3u. */
+int tolg_mpc_measure(tolg_handle_t h, int32_t B, int32_t mask, const double* d_V, const double* d_x_q, const double* d_x_xi,
+                     const double* d_n, double* d_est_q, double* d_est_xi, double* d_P, double* d_L, double* d_innov,
+                     double* d_var_est, void* stream);
+int tolg_mpc_advance_estimated(tolg_handle_t h, int32_t B, const double* d_w, const double* d_u_lb, const double* d_u_ub,
+                               double* d_x_true_q, double* d_x_true_xi, double* d_P, const double* d_W, double* d_x_next_q,
+                               double* d_x_next_xi, double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm,
+                               double* d_us_warm, double* d_J_cl, int32_t* d_n_sat, void* stream);
+
 /* Plants: per-sample dynamics parameters that step the closed loops of tolg_policy_rollout and tolg_mpc_advance in place of
  * the model's (model mismatch: a payload change, a mis-identified inertia, domain randomisation).  The planner's model stays
  * the handle's tolg_problem, and so do dt, gravity, kind, m, the input map, the cost, the reference and the weights.

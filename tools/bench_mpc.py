@@ -5,6 +5,7 @@ usage: python tools/bench_mpc.py [--B 4096] [--N 200,50] [--iters 0,1,3,5] [--st
                                  [--tol-steps 10] [--tol-rounds 2] [--max-iters 30] [--out FILE.json]
        python tools/bench_mpc.py --constrained [--B 4096] [--N 200] [--K 4] [--iters 5] [--steps 20] [--rounds 5]
                                  [--loops unconstrained,box,spheres,box+spheres,pose,spheres+pose]
+       python tools/bench_mpc.py --estimated [--B 4096] [--N 200] [--mask 0x03F] [--steps 20] [--rounds 5]
 
 One process, se3_mpc's workload (every trajectory its own path and phase, twist disturbances behind every step), multiple
 shooting, accept-always.
@@ -28,7 +29,13 @@ shooting, accept-always.
   the third set (tolg_al_mpc_step_pose), `steps` calls between two device synchronisations.  The pose loops cap mu at 1 (mu_max): the path leaves the
   cones for good, mu would grow at every step, and accept-always iterations diverge under a penalty that large; what a step
   costs does not depend on mu.  --loops runs a subset of the loops (an A/B against a build without the pose loops runs the same
-  four in both)."""
+  four in both).
+- --estimated: what output feedback adds to a step.  On se3_mpc_estimated's workload and a held policy, with an actuator box
+  on: the pair tolg_mpc_measure + tolg_mpc_advance_estimated, and tolg_mpc_advance_limited alone, `steps` calls each between two
+  device synchronisations on preallocated buffers (the loop's own path: no host work per call), alternated round after round
+  behind a warm-up round; then, on the same handle, one accept-always solver iteration (tolg_solve_iterate(steps) inside a
+  solve in flight, per iteration).  Reported: the median ms per call (pair: per pair) over the rounds, min, max, and the two
+  ratios pair / limited and pair / iteration."""
 import argparse
 import os
 import statistics
@@ -51,6 +58,8 @@ def parse_args(argv=None):
     ap.add_argument("--tol-rounds", type=int, default=2)
     ap.add_argument("--max-iters", type=int, default=30)
     ap.add_argument("--constrained", action="store_true")
+    ap.add_argument("--estimated", action="store_true")
+    ap.add_argument("--mask", type=lambda x: int(x, 0), default=0x03F)
     ap.add_argument("--K", type=int, default=4)
     ap.add_argument("--loops", default="unconstrained,box,spheres,box+spheres,pose,spheres+pose")
     add_common_args(ap, "out")
@@ -143,10 +152,75 @@ def constrained(a):
     return res
 
 
+def estimated(a):
+    """measure + advance_estimated against advance_limited and one solver iteration (--estimated)"""
+    import numpy as np
+    import torch
+    from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
+
+    B, zero, rows = a.B, dict(tol_grad_norm=0.0, tol_d_norm=0.0), []
+    for N in a.N:
+        prob, q, xi, pq, px, t0, noise, est = workloads.se3_mpc_estimated(B, a.steps, N=N)
+        s = BatchedTrackingILQR(prob, B)
+        dev = lambda x: s._dev(x, np.shape(x))  # noqa: E731
+        r = s.fit_batch(q, xi, None, n_iterations=3, check_every=0, **zero)
+        u0 = np.abs(r.us[:, 0].cpu().numpy())
+        lim = np.percentile(u0[np.isfinite(u0).all(axis=1)], 90, axis=0)
+        box = (dev(np.broadcast_to(-lim, (B, prob.m)).copy()), dev(np.broadcast_to(lim, (B, prob.m)).copy()))
+        V, W, n, w = dev(est["meas_V"]), dev(est["est_W"]), dev(est["meas_noise"][:, 0]), dev(noise[:, 0])
+        xt_q, xt_xi = r.xs_q[:, 0].reshape(B, 16).clone(), r.xs_xi[:, 0].clone()
+        e_q, e_xi, P = xt_q.clone(), xt_xi.clone(), dev(est["est_Sigma0"])
+        innov, var = torch.empty(B, 12, dtype=torch.float64, device=s.device), torch.empty(B, 12, dtype=torch.float64, device=s.device)
+        adv = s._advance_out(B, torch.zeros(B, dtype=torch.float64, device=s.device), limited=True)
+
+        def pair():
+            s._measure(B, a.mask, V, xt_q, xt_xi, n, e_q, e_xi, P, None, innov, var)
+            s._advance_est(B, w, box, xt_q, xt_xi, P, W, adv)
+
+        parts = {"measure+advance_estimated": pair, "advance_limited": lambda: s._advance(B, w, adv, box)}
+        times = {name: [] for name in parts}
+        for rnd in range(a.rounds + 1):  # round 0 warms up
+            for name in rotated(list(parts), rnd):
+                xt_q.copy_(r.xs_q[:, 0].reshape(B, 16)); xt_xi.copy_(r.xs_xi[:, 0]); P.copy_(dev(est["est_Sigma0"]))
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for _ in range(a.steps):
+                    parts[name]()
+                torch.cuda.synchronize()
+                if rnd:
+                    times[name].append((time.perf_counter() - t) * 1e3 / a.steps)
+        s.solve_begin(q, xi, None, mode="ms", n_iterations=a.steps * (a.rounds + 1), histories=False, **zero)
+        times["solver_iteration"] = []
+        for rnd in range(a.rounds + 1):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            s.solve_iterate(a.steps)
+            torch.cuda.synchronize()
+            if rnd:
+                times["solver_iteration"].append((time.perf_counter() - t) * 1e3 / a.steps)
+        s.solve_end()
+        med = {}
+        for name, ms in times.items():
+            st = stats_row(ms, "ms_per_call")
+            med[name] = st["ms_per_call_median"]
+            row = dict(part="estimated", what=name, N=N, mask="%#05x" % a.mask, **st)
+            rows.append(row)
+            print_row(row)
+        row = dict(part="estimated_ratios", N=N, pair_over_advance_limited=med["measure+advance_estimated"] / med["advance_limited"],
+                   pair_over_solver_iteration=med["measure+advance_estimated"] / med["solver_iteration"])
+        rows.append(row)
+        print_row(row)
+    res = dict(B=B, N=a.N, steps=a.steps, rounds=a.rounds, device=torch.cuda.get_device_name(0), rows=rows)
+    emit(res, a.out)
+    return res
+
+
 def main(argv=None):
     a = parse_args(argv)
     if a.constrained:
         return constrained(a)
+    if a.estimated:
+        return estimated(a)
     import torch
     from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
 

@@ -45,7 +45,7 @@ SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_ba
            "tolg_al_update_state", "tolg_al_mpc_step", "tolg_set_al_obstacle_windows", "tolg_set_al_obstacle_kinds", "tolg_pose_constraints_bytes", "tolg_set_al_pose_constraints",
            "tolg_set_al_pose_constraint_windows", "tolg_al_mpc_step_pose", "tolg_plant_bytes", "tolg_set_plant", "tolg_policy_covariance", "tolg_policy_value", "tolg_policy_covariance_estimated", "tolg_policy_rollout_estimated", "tolg_policy_rollout_limited", "tolg_mpc_advance_limited",
            "tolg_policy_rollout_margins", "tolg_policy_rollout_estimated_limited", "tolg_policy_rollout_actuated",
-           "tolg_mpc_advance_actuated", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
+           "tolg_mpc_advance_actuated", "tolg_mpc_measure", "tolg_mpc_advance_estimated", "tolg_kernel_time", "tolg_enable_timing", "tolg_version", "tolg_selftest_series"]
 
 
 def load():
@@ -169,6 +169,10 @@ def load():
                                                  + lib.tolg_policy_rollout_margins.argtypes[7:-1] + [dp, ip, dp, vp])
     lib.tolg_mpc_advance_actuated.restype = C.c_int
     lib.tolg_mpc_advance_actuated.argtypes = [vp, C.c_int32, dp, C.POINTER(Actuator)] + [dp] * 8 + [ip, ip, vp]
+    lib.tolg_mpc_measure.restype = C.c_int
+    lib.tolg_mpc_measure.argtypes = [vp, C.c_int32, C.c_int32] + [dp] * 10 + [vp]
+    lib.tolg_mpc_advance_estimated.restype = C.c_int
+    lib.tolg_mpc_advance_estimated.argtypes = [vp, C.c_int32] + [dp] * 14 + [ip, vp]
     lib.tolg_kernel_time.restype = C.c_int
     lib.tolg_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int64)]

@@ -3776,16 +3776,94 @@ struct MpcAct {
   int* n_rate;                  // [B], may be null
   int delay;
 };
+// With an MpcEst in front (tolg_mpc_advance_estimated) the loop acts on an estimate: the held x*_0 is the filter's posterior,
+// and a third end carries the TRUE state.  Ends 0 and 1 stay what they are under an MpcLim, on the model
+// in every form and without the disturbance: x_next = f(x*_0, clamp(u*_0)) is the estimate's prior (the filter knows the input
+// the actuator applied and not w), the tail is the model's.  End 2 loads trajectory b's true state from the caller's rows,
+// steps it with the same clamped input -- on plant row b where one is set -- adds w, accumulates the stage cost of the true
+// state into J_cl and writes the rows back in place (the one thread that owns b reads them before it writes).  lim's bounds
+// may both be null (no box).  A launch runs the ends end0 .. end0 + ends - 1, ends B threads: all three on the model; with a
+// plant attached ends 0 and 1 in the model's form and end 2 alone in the plant's, so that the estimate's prior and the tail
+// are the code, and the bits, of the call without a plant.
+struct MpcEst {
+  MpcLim lim;
+  double *xt_q, *xt_xi;  // [B][16], [B][6]
+  int end0, ends;
+};
 template <int M, int PK, int PT, int PL = PL_NONE, class... PA>
 __global__ __launch_bounds__(256) void k_mpc_advance(Params P, const double* __restrict__ w, double* __restrict__ x_next_q,
                                                      double* __restrict__ x_next_xi, double* __restrict__ u_applied,
                                                      double* __restrict__ xs_q, double* __restrict__ xs_xi,
                                                      double* __restrict__ J_cl, PA... pl) {
+  constexpr bool EST = pack_has<MpcEst, PA...>;
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= 2 * (size_t)P.B) return;
+  if constexpr (EST) {
+    if (g >= (size_t)pack_arg<MpcEst>(pl...).ends * (size_t)P.B) return;
+  } else {
+    if (g >= 2 * (size_t)P.B) return;
+  }
   const int N = P.N, b = (int)(g % P.B), i = g < (size_t)P.B ? 0 : N;
   const Consts& C = *P.c;
   const DynK DK = dynk_load(C);
+  if constexpr (EST) {
+    // (a body of its own: the ends of the other forms keep their statements, and with them their code)
+    const MpcEst E = pack_arg<MpcEst>(pl...);
+    const int end = E.end0 + (int)(g / (size_t)P.B);
+    const bool truth = end == 2;
+    const int i = end == 1 ? N : 0;
+    const State Sx = truth ? state_from_m16(E.xt_q, E.xt_xi, (size_t)b) : load_state(P, P.cur, i, b);
+    double u[M];
+#pragma unroll
+    for (int a = 0; a < M; a++) u[a] = P.cur_u[UIDX(a, i == 0 ? 0 : N - 1, b)];
+    if (i == 0 && E.lim.lb) {  // (both or neither: the host's rule)
+      int ns = 0;
+#pragma unroll
+      for (int a = 0; a < M; a++) {
+        const double uc = u[a], l = E.lim.lb[(size_t)b * M + a], h = E.lim.ub[(size_t)b * M + a];
+        const bool lo = uc < l, hi = uc > h;
+        ns += (lo || hi) ? 1 : 0;
+        u[a] = lo ? l : (hi ? h : uc);
+      }
+      if (E.lim.n_sat && !truth) E.lim.n_sat[b] = ns;
+    } else if (i == 0 && E.lim.n_sat && !truth) {
+      E.lim.n_sat[b] = 0;
+    }
+    State S;
+    if constexpr (PL == PL_NONE) {
+      S = dyn_f_k<M, Consts, PK>(DK, C, Sx, u);
+    } else if (truth) {
+      const PlantArg pa = pack_arg<PlantArg>(pl...);
+      const PlantC V = plant_c<PL>(C, pa, (size_t)b);
+      const auto& CS = plant_or_model<PL, PK>(C, V);
+      S = dyn_f_k<M, std::decay_t<decltype(CS)>, PK>(plant_dynk<PL>(C, pa, (size_t)b), CS, Sx, u);
+    } else {
+      S = dyn_f_k<M, Consts, PK>(DK, C, Sx, u);
+    }
+    if (truth) {
+      if (w) {
+        const double* d = w + 6 * (size_t)b;
+        S.w = S.w + v3(d[0], d[1], d[2]);
+        S.v = S.v + v3(d[3], d[4], d[5]);
+      }
+      pose_to_m16(S.X, E.xt_q + 16 * (size_t)b);
+      double* x = E.xt_xi + 6 * (size_t)b;
+      x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z;
+      if (J_cl) J_cl[b] += knot_cost<M, false, PT>(P, C, 0, b, Sx, u, false);
+      return;
+    }
+    if (i == 0) {
+      if (x_next_q) pose_to_m16(S.X, x_next_q + 16 * (size_t)b);
+      if (x_next_xi) { double* x = x_next_xi + 6 * (size_t)b; x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z; }
+      if (u_applied)
+#pragma unroll
+        for (int a = 0; a < M; a++) u_applied[(size_t)b * M + a] = u[a];
+    }
+    const size_t k = (size_t)b * (N + 1) + i;
+    pose_to_m16(S.X, xs_q + 16 * k);
+    double* x = xs_xi + 6 * k;
+    x[0] = S.w.x; x[1] = S.w.y; x[2] = S.w.z; x[3] = S.v.x; x[4] = S.v.y; x[5] = S.v.z;
+    return;
+  }
   const State Sx = load_state(P, P.cur, i, b);
   double u[M];
 #pragma unroll
@@ -3882,7 +3960,7 @@ enum { PC_SG = 0, PC_TT = 144, PC_TOP = 288, PC_BOT = 324, PC_K = 396, PC_PU = 4
 // TAG, here and on the three helpers below: which kernel family calls.  The helpers are internal functions to the device
 // compiler, whose interprocedural passes run before they are inlined and merge what every caller passes: with a third caller
 // on the same instance the two existing kernels came out with other instructions (tools/symbol_diff.py).  A family of callers
-// that must not move the others takes an instance of its own (TAG = 1: k_policy_covariance_est).
+// that must not move the others takes an instance of its own (TAG = 1: k_policy_covariance_est; TAG = 2: k_mpc_cov_step).
 template <int TAG = 0>
 TOLG_DEV void pc_apply(const double* L, const double (&x)[12], double (&y)[12]) {
   const double *RI = L + PC_TOP, *TRI = RI + 9, *JR = RI + 18, *QR = RI + 27, *BOT = L + PC_BOT;  // 3x3 row-major; 6 x 12 row-major
@@ -4128,7 +4206,8 @@ TOLG_DEV double row_bcast(double x) {  // value of x in lane C of this lane's 16
   return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 // the measurement updates of one knot on column j of P (p), coordinates C .. 11 in turn; vm: the noise variances
-template <int C = 0>
+// (TAG: the note above pc_apply; TAG = 2: k_mpc_measure)
+template <int C = 0, int TAG = 0>
 TOLG_DEV void pe_measure(double (&p)[12], int mask, const double (&vm)[12]) {
   if constexpr (C < 12) {
     if ((mask >> C) & 1) {
@@ -4139,7 +4218,7 @@ TOLG_DEV void pe_measure(double (&p)[12], int mask, const double (&vm)[12]) {
 #pragma unroll
       for (int k = 0; k < 12; k++) p[k] -= (cc[k] * cj) * is;
     }
-    pe_measure<C + 1>(p, mask, vm);
+    pe_measure<C + 1, TAG>(p, mask, vm);
   }
 }
 template <int M, int PK>
@@ -4275,6 +4354,160 @@ __global__ __launch_bounds__(64) void k_policy_covariance_est(Params P, const do
     Sa = Sb;
   }
   measure(N, Sa);
+}
+
+// Output feedback inside the receding-horizon loop (tolg_mpc_advance_estimated): one knot of k_policy_covariance_est's push,
+// P <- A P A^T + E W E^T with A = f_x(x*_0, u*_0) linearised HERE at knot 0 of the held nominal, on the caller's P in place.
+// The same row layout: one 16-lane row per trajectory, four per wavefront, lane j < 12 holds column j of P (upper triangle
+// read), rows past B replay B - 1 and store nothing.  pc_build_acl puts the blocks of f_x into the row's LDS and the push runs
+// before any f_u K is folded into the lower half -- the fold is simply not run.  The result is read back from the upper
+// triangle (the entry lane min(r, c) computed) and stored mirrored, 144 entries over the 16 lanes.  The helpers take an
+// instance of their own (TAG = 2): the two families that share them keep their code.
+template <int M, int PK>
+__global__ __launch_bounds__(64) void k_mpc_cov_step(Params P, const double* __restrict__ Wn, double* Pm) {
+  __shared__ double lds[4 * PC_F];
+  const Consts& C = *P.c;
+  const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+  int b = blockIdx.x * 4 + g;
+  const bool live = b < P.B;
+  if (!live) b = P.B - 1;
+  const int j = l < 12 ? l : 11;
+  const bool col = l < 12;
+  double* L = lds + g * PC_F;
+  const unsigned sB = (unsigned)P.Bp * 8u, vb = (unsigned)b * 8u;
+  double p[12], wc[6], t[12], y[12], Bt[9];
+#pragma unroll
+  for (int i = 0; i < 12; i++) p[i] = Pm[(size_t)b * 144 + (i <= j ? 12 * i + j : 12 * j + i)];
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const int jw = j >= 6 ? j - 6 : 0;
+    wc[i] = (Wn && j >= 6) ? Wn[(size_t)b * 36 + (i <= jw ? 6 * i + jw : 6 * jw + i)] : 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < 9; k++) Bt[k] = C.Bt[k];
+  const State Sa = roll_load_state(P, 0, vb, sB);
+  RollIn<M> Rin;
+  roll_load<M, true>(P, 0, b, l, vb, sB, Rin);
+  pc_build_acl<M, PK, 2>(C, C.dt, Sa, Rin, l, L, Bt);
+  __syncthreads();  // (behind every lane's read of its column of P too: the stores below are in place)
+  pc_apply<2>(L, p, y);
+  if (col) {
+#pragma unroll
+    for (int r = 0; r < 12; r++) L[PC_TT + 12 * r + j] = y[r];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 12; k++) t[k] = L[PC_TT + 12 * j + k];
+  pc_apply<2>(L, t, y);
+#pragma unroll
+  for (int k = 0; k < 6; k++) y[6 + k] += wc[k];
+  if (col) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) L[PC_SG + 12 * j + k] = y[k];
+  }
+  __syncthreads();
+  if (live) {
+    double* o = Pm + (size_t)b * 144;
+#pragma unroll
+    for (int s = 0; s < 9; s++) {
+      const int e = l + 16 * s, r = e / 12, c = e - 12 * r;
+      o[e] = L[PC_SG + (r <= c ? 12 * r + c : 12 * c + r)];
+    }
+  }
+}
+
+// The filter's update at one world knot (tolg_mpc_measure), on the caller's buffers alone: no Params, no workspace, no held
+// policy.  The same row layout; lane j < 12 holds column j of P (upper triangle read) and runs pe_measure on it (an instance
+// of its own, TAG = 2).  Every lane of the row forms the residual r = [Log(q^^-1 q_y); xi_y - xi^] redundantly from the same
+// operands, with the series forms of k_policy_rollout_est.  d = L r, L[:, j] = P^+[:, j] / V[j]: lane j holds the products
+// (P^+[k][j] / V[j]) r[j] of its column and puts them into the row's LDS, lane k adds row k in lane order j = 0..11 (a fixed
+// order: the bits of d depend on the row alone), and the twelve sums go back round the row by row_bcast.  (The row's LDS and not
+// DPP row operations for the sum: fp64 has no DPP add, a rotation is two moves and an add per term, 144 terms per lane against
+// 12 stores, 12 loads and one barrier the posterior's mirrored store needs anyway.)  mask == 0: the estimate is not written.
+// LDS per row (doubles): P^+ 144, the products 144.
+enum { MM_P = 0, MM_T = 144, MM_F = 288 };
+__global__ __launch_bounds__(64) void k_mpc_measure(int B, int mask, const double* __restrict__ Vm, const double* __restrict__ x_q,
+                                                    const double* __restrict__ x_xi, const double* __restrict__ mnoise,
+                                                    double* est_q, double* est_xi, double* Pm, double* __restrict__ Lout,
+                                                    double* __restrict__ innov, double* __restrict__ var_est) {
+  __shared__ double lds[4 * MM_F];
+  const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+  int b = blockIdx.x * 4 + g;
+  const bool live = b < B;
+  if (!live) b = B - 1;
+  const int j = l < 12 ? l : 11;
+  const bool col = l < 12;
+  double* L = lds + g * MM_F;
+  double p[12], vm[12];
+#pragma unroll
+  for (int i = 0; i < 12; i++) p[i] = Pm[(size_t)b * 144 + (i <= j ? 12 * i + j : 12 * j + i)];
+#pragma unroll
+  for (int c = 0; c < 12; c++) vm[c] = ((mask >> c) & 1) ? Vm[(size_t)b * 12 + c] : 1.0;
+  const bool meas_j = ((mask >> j) & 1) != 0;
+  const double ivj = meas_j ? 1.0 / Vm[(size_t)b * 12 + j] : 0.0;
+  pe_measure<0, 2>(p, mask, vm);
+  double r[12], d[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) r[k] = d[k] = 0.0;
+  State Se = state_from_m16(est_q, est_xi, (size_t)b);
+  if (mask) {
+    const State St = state_from_m16(x_q, x_xi, (size_t)b);
+    State Y = St;
+    if (mnoise) {
+      const double* m = mnoise + 12 * (size_t)b;
+      Y.X = se3_project(se3_compose(St.X, se3_exp_fast(v3(m[0], m[1], m[2]), v3(m[3], m[4], m[5]))));
+      Y.w = St.w + v3(m[6], m[7], m[8]);
+      Y.v = St.v + v3(m[9], m[10], m[11]);
+    }
+    V3 rw, rv;
+    se3_log_fast(se3_compose(se3_inverse(Se.X), Y.X), rw, rv);
+    roll_deviation(rw, rv, Se, Y, r);
+    double rj = 0.0;
+#pragma unroll
+    for (int a = 0; a < 12; a++) {
+      if (!((mask >> a) & 1)) r[a] = 0.0;
+      rj = a == j ? r[a] : rj;
+    }
+    if (col) {
+#pragma unroll
+      for (int k = 0; k < 12; k++) L[MM_T + 12 * k + j] = (p[k] * ivj) * rj;
+    }
+  }
+  if (col) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) L[MM_P + 12 * j + k] = p[k];
+  }
+  __syncthreads();  // (behind every lane's read of its column of P too: the stores below are in place)
+  if (mask) {
+    double mine = 0.0;
+#pragma unroll
+    for (int c = 0; c < 12; c++) mine += L[MM_T + 12 * j + c];
+    d[0] = row_bcast<0>(mine); d[1] = row_bcast<1>(mine); d[2] = row_bcast<2>(mine); d[3] = row_bcast<3>(mine);
+    d[4] = row_bcast<4>(mine); d[5] = row_bcast<5>(mine); d[6] = row_bcast<6>(mine); d[7] = row_bcast<7>(mine);
+    d[8] = row_bcast<8>(mine); d[9] = row_bcast<9>(mine); d[10] = row_bcast<10>(mine); d[11] = row_bcast<11>(mine);
+    Se.X = se3_project(se3_compose(Se.X, se3_exp_fast(v3(d[0], d[1], d[2]), v3(d[3], d[4], d[5]))));
+    Se.w = Se.w + v3(d[6], d[7], d[8]);
+    Se.v = Se.v + v3(d[9], d[10], d[11]);
+  }
+  if (!live) return;
+  {  // the posterior, mirrored: every entry was stored by its column's lane
+    double* o = Pm + (size_t)b * 144;
+#pragma unroll
+    for (int s = 0; s < 9; s++) o[l + 16 * s] = L[MM_P + l + 16 * s];
+  }
+  if (var_est && col) var_est[(size_t)b * 12 + l] = L[MM_P + 13 * l];
+  if (Lout && col) {  // column j of the gain
+    double* o = Lout + (size_t)b * 144 + j;
+#pragma unroll
+    for (int k = 0; k < 12; k++) o[12 * k] = meas_j ? p[k] * ivj : 0.0;
+  }
+  if (l == 0) {
+    if (mask) state_to_m16(Se, est_q, est_xi, (size_t)b);
+    if (innov) {
+#pragma unroll
+      for (int k = 0; k < 12; k++) innov[(size_t)b * 12 + k] = r[k];
+    }
+  }
 }
 
 // Cost-to-go of the held policy (tolg_policy_value): V_i(e) ~ p_i . e + e^T P_i e / 2 about the held nominal, the backward twin
@@ -5483,6 +5716,12 @@ struct KernelTable {
   // ... under an actuator box and with the margin report (tolg_policy_rollout_estimated_limited)
   void (*policy_rollout_est_lim)(Params, int, int, int, const double*, const double*, const double*, const double*, double*, int*,
                                  double*, double*, double*, double*, double*, PolicyLim);
+  // output feedback in the receding-horizon loop: tolg_mpc_advance_estimated (the step, then the covariance's knot) and
+  // tolg_mpc_measure (one kernel for every model: it reads the caller's buffers alone)
+  ClosedLoop<Params, const double*, double*, double*, double*, double*, double*, double*, MpcEst> mpc_advance_est;
+  void (*mpc_cov_step)(Params, const double*, double*);
+  void (*mpc_measure)(int, int, const double*, const double*, const double*, const double*, double*, double*, double*, double*,
+                      double*, double*);
   struct Search {                    // per search kind: ls[0] backtracking (single shooting), ls[1] merit (multiple shooting)
     struct { SearchRollout k; int nt; } wave2[2];  // k_rollout_ls2 [first try] and its NT (twist waves per pose wave)
     SearchRollout wave1[2];          // the one-wave forms k_rollout_ls [linear]
@@ -5566,6 +5805,10 @@ static KernelTable kernel_table(int lds_per_block) {
   t.policy_covariance_est = k_policy_covariance_est<M, PK>;
   t.policy_rollout_est = k_policy_rollout_est<M, PK, PT & ~PT_OBS>;
   t.policy_rollout_est_lim = k_policy_rollout_est<M, PK, PT & ~PT_OBS, PolicyLim>;
+  t.mpc_advance_est = {k_mpc_advance<M, PK, PTC, PL_NONE, MpcEst>,
+                       {k_mpc_advance<M, PK, PTC, PL_DIAG, MpcEst, PlantArg>, k_mpc_advance<M, PK, PTC, PL_DENSE, MpcEst, PlantArg>}};
+  t.mpc_cov_step = k_mpc_cov_step<M, PK>;
+  t.mpc_measure = k_mpc_measure;
   t.ls[0] = search_kernels<M, false, PK, PT>();
   t.ls[1] = search_kernels<M, true, PK, PT>();
   return t;
@@ -7314,7 +7557,7 @@ extern "C" int tolg_policy_rollout_estimated_limited(tolg_handle_t h, int32_t B,
 }
 
 // tolg_mpc_advance and tolg_mpc_advance_limited: the rules both share and the shift (of the unclamped solution in either),
-// then the kernel of k with lim (none, or the MpcLim) behind the step's arguments
+// then the kernel of k with lim (none, or the MpcLim) behind the step's arguments: one thread per (end, trajectory)
 template <class K, class... LIM>
 static int mpc_advance(tolg_handle_t h, const K& k, int32_t B, const double* d_w, double* d_x_next_q, double* d_x_next_xi,
                        double* d_u_applied, double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl,
@@ -7327,6 +7570,23 @@ static int mpc_advance(tolg_handle_t h, const K& k, int32_t B, const double* d_w
   hipLaunchKernelGGL(k_mpc_shift, knot_grid(P.N, P.Bp), dim3(256), 0, st, P, P.cur, P.cur_u, d_xs_q_warm,
                      d_xs_xi_warm, d_us_warm);
   LAUNCH_CHECK();
+  if constexpr ((std::is_same_v<LIM, MpcEst> || ...)) {
+    // the estimated step: the model's form runs the ends of the warm start (and the true state's when no plant is held), the
+    // plant's form the true state's alone
+    const auto grid = [&](int ends) { return dim3((unsigned)((ends * (size_t)B + 255) / 256)); };
+    MpcEst e = (lim, ...);
+    e.end0 = 0; e.ends = h->plant.p ? 2 : 3;
+    hipLaunchKernelGGL(k.model, grid(e.ends), dim3(256), 0, st, P, d_w, d_x_next_q, d_x_next_xi, d_u_applied, d_xs_q_warm,
+                       d_xs_xi_warm, d_J_cl, e);
+    LAUNCH_CHECK();
+    if (h->plant.p) {
+      e.end0 = 2; e.ends = 1;
+      hipLaunchKernelGGL(k.plant[h->plant_form], grid(1), dim3(256), 0, st, P, d_w, d_x_next_q, d_x_next_xi, d_u_applied,
+                         d_xs_q_warm, d_xs_xi_warm, d_J_cl, e, plant_arg(h));
+      LAUNCH_CHECK();
+    }
+    return 0;
+  }
   return launch_closed_loop(h, k, dim3((unsigned)((2 * (size_t)B + 255) / 256)), dim3(256), st, P, d_w, d_x_next_q, d_x_next_xi,
                             d_u_applied, d_xs_q_warm, d_xs_xi_warm, d_J_cl, lim...);
 }
@@ -7353,6 +7613,35 @@ extern "C" int tolg_mpc_advance_actuated(tolg_handle_t h, int32_t B, const doubl
   return mpc_advance(h, h->kt.mpc_advance_act, B, d_w, d_x_next_q, d_x_next_xi, d_u_applied, d_xs_q_warm, d_xs_xi_warm,
                      d_us_warm, d_J_cl, stream,
                      MpcAct{MpcLim{act->d_lb, act->d_ub, d_n_sat}, act->d_beta, act->d_du_max, d_act_state, d_n_rate, act->delay});
+}
+
+
+// Output feedback in the receding-horizon loop.  tolg_mpc_measure: the caller's buffers alone (legal during a solve in flight,
+// needs no held policy).  tolg_mpc_advance_estimated: every rule is checked before the first launch -- the shift, the step
+// with its third end, then the covariance's knot -- so a refused call changes nothing.
+extern "C" int tolg_mpc_measure(tolg_handle_t h, int32_t B, int32_t mask, const double* d_V, const double* d_x_q,
+                                const double* d_x_xi, const double* d_n, double* d_est_q, double* d_est_xi, double* d_P,
+                                double* d_L, double* d_innov, double* d_var_est, void* stream) {
+  if (!h || B < 1 || B > h->max_batch || !mask_ok(h, mask) || (mask != 0 && !d_V)) return TOLG_E_ARG;
+  if (!d_x_q || !d_x_xi || !d_est_q || !d_est_xi || !d_P) return TOLG_E_ARG;
+  hipLaunchKernelGGL(h->kt.mpc_measure, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, static_cast<hipStream_t>(stream), (int)B,
+                     (int)mask, d_V, d_x_q, d_x_xi, d_n, d_est_q, d_est_xi, d_P, d_L, d_innov, d_var_est);
+  LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int tolg_mpc_advance_estimated(tolg_handle_t h, int32_t B, const double* d_w, const double* d_u_lb,
+                                          const double* d_u_ub, double* d_x_true_q, double* d_x_true_xi, double* d_P,
+                                          const double* d_W, double* d_x_next_q, double* d_x_next_xi, double* d_u_applied,
+                                          double* d_xs_q_warm, double* d_xs_xi_warm, double* d_us_warm, double* d_J_cl,
+                                          int32_t* d_n_sat, void* stream) {
+  if (!h || (d_u_lb == nullptr) != (d_u_ub == nullptr) || !d_x_true_q || !d_x_true_xi || !d_P) return TOLG_E_ARG;
+  const int rc = mpc_advance(h, h->kt.mpc_advance_est, B, d_w, d_x_next_q, d_x_next_xi, d_u_applied, d_xs_q_warm, d_xs_xi_warm,
+                                d_us_warm, d_J_cl, stream, MpcEst{MpcLim{d_u_lb, d_u_ub, d_n_sat}, d_x_true_q, d_x_true_xi, 0, 3});
+  if (rc) return rc;
+  const Params P = params_for(h, B);
+  hipLaunchKernelGGL(h->kt.mpc_cov_step, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, static_cast<hipStream_t>(stream), P, d_W, d_P);
+  LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" size_t tolg_plant_bytes(const tolg_problem* prob, int32_t max_batch, int32_t S) {

@@ -248,6 +248,75 @@ class MPCResult:
     clearance: Optional[torch.Tensor] = None      # [B, steps+1]
     # mpc(pose_constraints=, pose_paths=): min_k pose_margin of the realised states at their world knots (negative: outside a cone)
     pose_margin: Optional[torch.Tensor] = None    # [B, steps+1]
+    # mpc(meas_*=, est_*=): the loop on an estimate.  xs_q, xs_xi, J, clearance and pose_margin above are then those of the TRUE
+    # states (the rule of policy_rollout_estimated: reports on the true state, never on the estimate); these are the filter's
+    est_q: Optional[torch.Tensor] = None    # [B, steps+1, 4, 4] the posterior estimates, one per world knot
+    est_xi: Optional[torch.Tensor] = None   # [B, steps+1, 6]
+    est_var: Optional[torch.Tensor] = None  # [B, steps+1, 12] diag P^+
+    innov: Optional[torch.Tensor] = None    # [B, steps+1, 12] the residuals r (0 on unmeasured coordinates)
+
+
+MPC_EST_ACT = ("mpc: the estimated loop (meas_* / est_*) does not take an actuator model (act_tau / act_rate / act_delay): "
+               "output feedback behind an actuator is out of scope, as it is for policy_rollout_estimated")
+
+
+def check_owned(name, t, shapes, device):
+    """A caller-owned in/out argument of mpc_measure / mpc_advance_estimated (act_state is the precedent): a contiguous
+    float64 tensor on `device` of one of `shapes`; ValueError otherwise.  Returns t."""
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) not in [tuple(s) for s in shapes] or
+            t.device != torch.device(device) or not t.is_contiguous()):
+        raise ValueError("%s must be a contiguous float64 tensor of shape %s on %s"
+                         % (name, " or ".join(str(tuple(s)) for s in shapes), device))
+    return t
+
+
+def check_mpc_estimated(B, steps, so3, meas_mask=None, meas_V=None, meas_noise=None, est_Sigma0=None, est_W=None, est_dx0=None,
+                        actuated=False):
+    """The six keywords of mpc()'s estimated loop checked on the host; ValueError before anything reaches the device.
+    meas_mask / meas_V: check_measurement's (None: nothing is measured); meas_noise [B, steps+1, 12], est_dx0 [B, 12]: finite,
+    None = 0 (the SO3 family: zero on coordinates 3..5 and 9..11); est_Sigma0 [12, 12] or [B, 12, 12], est_W [6, 6] or [B, 6, 6]:
+    check_covariance's, None = 0.  actuated: the call also names an actuator model, which the estimated loop refuses.
+    Returns (mask int, V [B, 12] or None, meas_noise [steps+1, B, 12] step-major or None, Sigma0 [B, 12, 12] (zeros for None),
+    W [B, 6, 6] or None, dx0 [B, 12] or None), float64 numpy arrays."""
+    if actuated:
+        raise ValueError(MPC_EST_ACT)
+    m, V = check_measurement(0 if meas_mask is None else meas_mask, meas_V, B, so3=so3)
+    unused = [3, 4, 5, 9, 10, 11]
+    n = None
+    if meas_noise is not None:
+        n = _checked("meas_noise", meas_noise, (B, steps + 1, 12), finite=True)
+        if so3 and np.any(n[..., unused] != 0.0):
+            raise ValueError("meas_noise: the SO3 family has no translation or linear velocity, coordinates 3..5 and 9..11 are 0")
+        n = np.ascontiguousarray(n.transpose(1, 0, 2))  # step t: one contiguous [B, 12]
+    S0 = np.zeros((B, 12, 12)) if est_Sigma0 is None else \
+        check_covariance("est_Sigma0", est_Sigma0, B, 12, (6, _SO3_COORDS) if so3 else None)
+    W = None if est_W is None else check_covariance("est_W", est_W, B, 6, (3, [0, 1, 2]) if so3 else None)
+    d = None
+    if est_dx0 is not None:
+        d = _checked("est_dx0", est_dx0, (B, 12), finite=True)
+        if so3 and np.any(d[:, unused] != 0.0):
+            raise ValueError("est_dx0: the SO3 family has no translation or linear velocity, coordinates 3..5 and 9..11 are 0")
+    return m, V, n, S0, W, d
+
+
+def perturbed_state(x_q, x_xi, dx):
+    """x (+) dx on the host, the right perturbation of the C ABI: x_q [B, 4, 4] Exp(dx[:, :6]) in the twist order [omega, v],
+    x_xi + dx[:, 6:].  numpy in, numpy out."""
+    x_q, x_xi, dx = (np.asarray(a, dtype=np.float64) for a in (x_q, x_xi, dx))
+    out = np.empty((x_q.shape[0], 4, 4))
+    for b in range(x_q.shape[0]):
+        w, v = dx[b, :3], dx[b, 3:6]
+        th = float(np.linalg.norm(w))
+        Wx = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+        if th < 1e-6:
+            a, bb, c = 1.0 - th * th / 6.0, 0.5 - th * th / 24.0, 1.0 / 6.0 - th * th / 120.0
+        else:
+            a, bb, c = np.sin(th) / th, (1.0 - np.cos(th)) / th ** 2, (th - np.sin(th)) / th ** 3
+        E = np.eye(4)
+        E[:3, :3] = np.eye(3) + a * Wx + bb * Wx @ Wx
+        E[:3, 3] = (np.eye(3) + bb * Wx + c * Wx @ Wx) @ v
+        out[b] = x_q[b].reshape(4, 4) @ E
+    return out, x_xi + dx[:, 6:]
 
 
 def check_box(u_lb, u_ub, B, m, so3=False):
@@ -2094,12 +2163,88 @@ class BatchedTrackingILQR:
         else:
             self._call("tolg_mpc_advance_limited", B, _ptr(d_w), _ptr(box[0]), _ptr(box[1]), *out, _ptr(r["n_sat"]))
 
+    def mpc_measure(self, mask, V, x_q, x_xi, est_q, est_xi, P, noise=None, gains=True):
+        """The filter's update at one world knot (tolg_mpc_measure): y = x (+) noise is measured on the coordinates `mask` with
+        variances V (check_measurement), the sequential scalar updates take P to P^+, L[:, j] = P^+[:, j] / V[j], and the estimate
+        becomes x^ (+) L r with the residual r = [Log(q^^-1 q_y); xi_y - xi^] on the measured coordinates.  x_q [B, 4, 4] (or
+        [B, 16]) and x_xi [B, 6]: the true state; est_q, est_xi, P [B, 12, 12]: the caller's contiguous float64 device tensors,
+        updated in place (check_owned; prior in, posterior out, P mirrored from its upper triangle).  noise [B, 12] or None.
+        Needs no held policy and is legal during a solve in flight.  Returns a dict of device tensors: innov [B, 12], var_est
+        [B, 12] and, with gains=True, L [B, 12, 12]."""
+        if not isinstance(est_xi, torch.Tensor) or est_xi.ndim != 2:
+            raise ValueError("est_xi must be a contiguous float64 tensor of shape (B, 6) on %s" % (self.device,))
+        B = est_xi.shape[0]
+        if not 1 <= B <= self.max_batch:
+            raise ValueError("batch %d outside 1..%d" % (B, self.max_batch))
+        m, Vn = check_measurement(mask, V, B, so3=self._so3())
+        for name, t, shapes in (("x_q", x_q, ((B, 4, 4), (B, 16))), ("x_xi", x_xi, ((B, 6),)), ("est_q", est_q, ((B, 4, 4), (B, 16))),
+                                ("est_xi", est_xi, ((B, 6),)), ("P", P, ((B, 12, 12),))):
+            check_owned(name, t, shapes, self.device)
+        d_V = None if Vn is None else self._dev(Vn, (B, 12))
+        d_n = None if noise is None else self._dev(_checked("noise", noise, (B, 12), finite=True), (B, 12))
+        f64 = dict(dtype=torch.float64, device=self.device)
+        r = dict(innov=torch.empty(B, 12, **f64), var_est=torch.empty(B, 12, **f64), L=torch.empty(B, 12, 12, **f64) if gains else None)
+        self._meas_inflight = (d_V, d_n)  # (a keep-alive of its own: a solve in flight keeps its inputs in the other)
+        self._measure(B, m, d_V, x_q, x_xi, d_n, est_q, est_xi, P, r["L"], r["innov"], r["var_est"])
+        return r
+
+    def _measure(self, B, m, d_V, x_q, x_xi, d_n, est_q, est_xi, P, L, innov, var_est):
+        self._call("tolg_mpc_measure", B, m, _ptr(d_V), _ptr(x_q), _ptr(x_xi), _ptr(d_n), _ptr(est_q), _ptr(est_xi), _ptr(P),
+                   _ptr(L), _ptr(innov), _ptr(var_est))
+
+    def mpc_advance_estimated(self, x_true_q, x_true_xi, P, w=None, W=None, J_cl=None, plant_J=None, plant_pend=None, u_lb=None,
+                              u_ub=None):
+        """One receding-horizon step of a loop that acts on an estimate (tolg_mpc_advance_estimated): the held policy's solve
+        began from the filter's posterior, so x*_0 is that estimate.  u = clamp(u*_0) (u_lb / u_ub as mpc_advance; both or
+        neither).  The TRUE state x_true_q [B, 4, 4] (or [B, 16]), x_true_xi [B, 6] steps in place with u -- on the plant
+        (plant_J / plant_pend, as mpc_advance) where one is given, else on the model -- and takes the twist disturbance w
+        [B, 6]; x_next = f(x*_0, u) on the model without w is the estimate's prior and xs_q[:, 0]; P [B, 12, 12] becomes
+        A P A^T + E W E^T in place with A = f_x(x*_0, u*_0) and W [6, 6] or [B, 6, 6] (check_covariance; None: 0).  J_cl is
+        accumulated with the stage cost of the true state before the step.  x_true_q, x_true_xi and P are the caller's
+        contiguous float64 device tensors (check_owned).  No actuator model: output feedback behind one is out of scope.
+        Returns mpc_advance's dict (x_next_q, x_next_xi, u, xs_q, xs_xi, us, J_cl, n_sat)."""
+        B = self._held_B()
+        for name, t, shapes in (("x_true_q", x_true_q, ((B, 4, 4), (B, 16))), ("x_true_xi", x_true_xi, ((B, 6),)),
+                                ("P", P, ((B, 12, 12),))):
+            check_owned(name, t, shapes, self.device)
+        box = self._box(B, u_lb, u_ub)
+        d_w = None if w is None else self._dev(_checked("w", w, (B, 6), finite=True), (B, 6))
+        d_W = None if W is None else self._dev(check_covariance("W", W, B, 6, (3, [0, 1, 2]) if self._so3() else None), (B, 6, 6))
+        if J_cl is not None:
+            check_owned("J_cl", J_cl, ((B,),), self.device)
+        plant = self._check_plant(B, plant_J, plant_pend, per_sample=False)
+        r = self._advance_out(B, J_cl, limited=True)
+        d_plant = self._use_plant(B, plant)
+        try:
+            self._hold((d_w, d_W, d_plant, box))
+            self._advance_est(B, d_w, box, x_true_q, x_true_xi, P, d_W, r)
+        finally:
+            if plant is not None:
+                self._clear_plant()
+        return r
+
+    def _measure_step(self, B, est, t, res):
+        """The loop's measure at world knot t on its own buffers (est: mpc()'s dict), recorded in res."""
+        self._measure(B, est["mask"], est["V"], est["xt_q"], est["xt_xi"], None if est["n"] is None else est["n"][t], est["e_q"],
+                      est["e_xi"], est["P"], None, est["innov"], est["var"])
+        res.est_q[:, t] = est["e_q"].reshape(B, 4, 4)
+        res.est_xi[:, t] = est["e_xi"]
+        res.est_var[:, t] = est["var"]
+        res.innov[:, t] = est["innov"]
+
+    def _advance_est(self, B, d_w, box, x_true_q, x_true_xi, P, d_W, r):
+        out = tuple(_ptr(r[k]) for k in ("x_next_q", "x_next_xi", "u", "xs_q", "xs_xi", "us", "J_cl"))
+        lb, ub = box if box is not None else (None, None)
+        self._call("tolg_mpc_advance_estimated", B, _ptr(d_w), _ptr(lb), _ptr(ub), _ptr(x_true_q), _ptr(x_true_xi), _ptr(P),
+                   _ptr(d_W), *out, _ptr(r["n_sat"]))
+
     def mpc(self, x0_q, x0_xi, path_q, path_xi, steps, us_init=None, t0=None, iters_per_step=5, first_iters=50,
             warm="states", noise=None, mode="ms", line_search=False, rollout="nonlinear", tol_grad_norm=1e-6, tol_d_norm=1e-6,
             check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None, plant_J=None, plant_pend=None, u_lb=None,
             u_ub=None, lb=None, ub=None, obstacles=None, obstacle_paths=None, obstacle_kinds=None, first_al_iters=3,
             al_iters_per_step=1, mu0=1e-2, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2, pose_scale_path=None,
-            pose_constraints=None, pose_paths=None, pose_kinds=None, act_tau=None, act_rate=None, act_delay=0) -> MPCResult:
+            pose_constraints=None, pose_paths=None, pose_kinds=None, act_tau=None, act_rate=None, act_delay=0, meas_mask=None,
+            meas_V=None, meas_noise=None, est_Sigma0=None, est_W=None, est_dx0=None) -> MPCResult:
         """Receding-horizon MPC: `steps` closed-loop steps of B trajectories, each tracking its own path from its own phase.
         Step t: windows min(t0[b] + t + i, T) of the paths (tolg_set_ref_windows), a solve of first_iters (t = 0) or
         iters_per_step iterations, then tolg_mpc_advance applies u*_0, steps the plant with the exact dynamics and adds the
@@ -2134,7 +2279,19 @@ class BatchedTrackingILQR:
         multipliers start at lambda = 0, I_mu = mu = mu0 (mu_scale, mu_max, tol_constr: al_fit_batch's).  The result carries
         max_violation [B, steps] (each step's last round), mu [B] and, with spheres, clearance [B, steps+1] of the realised
         states, with pose slots pose_margin [B, steps+1], the smallest pose_margin() of each realised state under the slots of
-        its world knot t0[b] + s (pose_paths: held past the path's end).  iters and status are those of each step's last round."""
+        its world knot t0[b] + s (pose_paths: held past the path's end).  iters and status are those of each step's last round.
+        Output feedback (any of meas_mask, meas_V, meas_noise, est_Sigma0, est_W, est_dx0; check_mpc_estimated): the loop acts
+        on the estimate of a Kalman filter carried from step to step instead of on the plant's exact state.  x0 is then what the
+        vehicle BELIEVES, the filter's prior with covariance est_Sigma0 ([12, 12] or [B, 12, 12], None: 0); the true state starts
+        at x0 (+) est_dx0 ([B, 12], None: 0).  Step t: the windows are set; tolg_mpc_measure takes y = x_true (+) meas_noise[:, t]
+        ([B, steps+1, 12], None: 0) on the coordinates meas_mask with variances meas_V ([12] or [B, 12]); the solve starts from
+        the posterior (its x0 and, for warm="states", xs_warm[:, 0]); the AL rounds, if any; tolg_mpc_advance_estimated steps the
+        true state with clamp(u*_0) on the plant and adds noise[:, t], steps the estimate on the model and P <- A P A^T + E est_W
+        E^T (est_W [6, 6] or [B, 6, 6], None: 0).  One more measure follows the last step.  xs_q, xs_xi, J, clearance and
+        pose_margin are those of the TRUE states; the result also carries est_q, est_xi, est_var (diag P^+) and innov, steps+1
+        entries each.  It composes with plant_*, u_lb / u_ub and the planner's constraints, and raises ValueError with act_*
+        (output feedback behind an actuator model is out of scope).  No host read in the loop.  on_step's FitResult also carries
+        extra["est_P"] [B, 12, 12], the posterior covariance of the step (the loop's own buffer: copy it to keep it)."""
         if self._al is not None:
             raise ValueError("mpc under an augmented-Lagrangian constraint is not supported: detach it with set_al(None)")
         if self._obs is not None:
@@ -2193,6 +2350,18 @@ class BatchedTrackingILQR:
             noise = _checked("noise", noise, (B, steps, 6), finite=True)
             noise = self._dev(np.ascontiguousarray(noise.transpose(1, 0, 2)), (steps, B, 6))  # step t: one contiguous [B, 6]
         f64 = dict(dtype=torch.float64, device=self.device)
+        est = None
+        if any(a is not None for a in (meas_mask, meas_V, meas_noise, est_Sigma0, est_W, est_dx0)):
+            em, eV, en, eS0, eW, edx = check_mpc_estimated(B, steps, self._so3(), meas_mask, meas_V, meas_noise, est_Sigma0, est_W,
+                                                           est_dx0, actuated=actuated)
+            est = dict(mask=em, V=None if eV is None else self._dev(eV, (B, 12)),
+                       n=None if en is None else self._dev(en, (steps + 1, B, 12)), P=self._dev(eS0, (B, 12, 12)),
+                       W=None if eW is None else self._dev(eW, (B, 6, 6)),
+                       # the true state, stepped in place by tolg_mpc_advance_estimated; the estimate, updated in place by the measure
+                       xt_q=b.x_q.reshape(B, 16).clone(), xt_xi=b.x_xi.clone(), e_q=b.x_q.reshape(B, 16).clone(), e_xi=b.x_xi.clone())
+            if edx is not None:
+                tq, txi = perturbed_state(b.x_q.reshape(B, 4, 4).cpu().numpy(), b.x_xi.cpu().numpy(), edx)
+                est["xt_q"], est["xt_xi"] = self._dev(tq, (B, 16)), self._dev(txi, (B, 6))
         # the planner's constraints, checked before anything is attached: (lb, ub, lam, imu), (geometry, lam, imu, in world time)
         al = obs = pose = mu = maxviol = None
         if posed:  # (slots, lam, imu, in world time, kinds)
@@ -2223,8 +2392,13 @@ class BatchedTrackingILQR:
                         status=torch.empty(B, steps, dtype=torch.int32, device=self.device))
         res.xs_q[:, 0] = b.x_q.reshape(B, 4, 4)
         res.xs_xi[:, 0] = b.x_xi
+        if est is not None:
+            res.xs_q[:, 0], res.xs_xi[:, 0] = est["xt_q"].reshape(B, 4, 4), est["xt_xi"]
+            res.est_q, res.est_xi = torch.empty(B, steps + 1, 4, 4, **f64), torch.empty(B, steps + 1, 6, **f64)
+            res.est_var, res.innov = torch.empty(B, steps + 1, 12, **f64), torch.empty(B, steps + 1, 12, **f64)
+            est["var"], est["innov"] = torch.empty(B, 12, **f64), torch.empty(B, 12, **f64)
         # the plant state and the warm start: written by tolg_mpc_advance, read by the next begin (stream-ordered)
-        adv = self._advance_out(B, res.J, limited=box is not None or actuated, actuated=actuated)
+        adv = self._advance_out(B, res.J, limited=box is not None or actuated or est is not None, actuated=actuated)
         if box is not None or actuated:
             res.n_sat = torch.empty(B, steps, dtype=torch.int32, device=self.device)
         if actuated:
@@ -2233,7 +2407,7 @@ class BatchedTrackingILQR:
         try:
             # the plant survives the solves of the loop (tolg_set_plant): set once, detached behind it
             d_plant = self._use_plant(B, plant)
-            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box, al, obs, pose, mu, maxviol, spath, act))
+            self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box, al, obs, pose, mu, maxviol, spath, act, est))
             self._use_pt(B, None, b.wts)
             if al is not None:
                 self.set_al(*al)
@@ -2259,6 +2433,15 @@ class BatchedTrackingILQR:
                     us = adv["us"]
                     if warm == "states":
                         xs = (adv["xs_q"].reshape(B, self.N + 1, 16), adv["xs_xi"])
+                if est is not None:  # the filter's update at world knot t; the solve starts from the posterior
+                    if t > 0:
+                        est["e_q"].copy_(x_q)
+                        est["e_xi"].copy_(x_xi)
+                    self._measure_step(B, est, t, res)
+                    x_q, x_xi = est["e_q"], est["e_xi"]
+                    if xs is not None:
+                        xs[0][:, 0] = x_q
+                        xs[1][:, 0] = x_xi
                 rounds = (int(first_al_iters) if t == 0 else int(al_iters_per_step)) if constrained else 1
                 for a in range(rounds):
                     if a > 0:  # from the round before, under the rule of `warm`
@@ -2278,17 +2461,30 @@ class BatchedTrackingILQR:
                 res.iters[:, t] = out.iters
                 res.status[:, t] = out.status
                 if on_step is not None:
+                    if est is not None:  # the filter's posterior covariance of this step: the loop's own buffer, copy to keep
+                        out.extra["est_P"] = est["P"]
                     on_step(t, out)
                 if actuated and t == 0:  # at rest on the first command
                     act[3][:] = out.us[:, 0, None, :]
-                self._advance(B, None if noise is None else noise[t], adv, box, act)
+                if est is not None:
+                    self._advance_est(B, None if noise is None else noise[t], box, est["xt_q"], est["xt_xi"], est["P"], est["W"], adv)
+                else:
+                    self._advance(B, None if noise is None else noise[t], adv, box, act)
                 if box is not None or actuated:
                     res.n_sat[:, t] = adv["n_sat"]
                 if actuated:
                     res.n_rate[:, t] = adv["n_rate"]
                 res.us[:, t] = adv["u"]
-                res.xs_q[:, t + 1] = adv["x_next_q"]
-                res.xs_xi[:, t + 1] = adv["x_next_xi"]
+                if est is not None:
+                    res.xs_q[:, t + 1] = est["xt_q"].reshape(B, 4, 4)
+                    res.xs_xi[:, t + 1] = est["xt_xi"]
+                else:
+                    res.xs_q[:, t + 1] = adv["x_next_q"]
+                    res.xs_xi[:, t + 1] = adv["x_next_xi"]
+            if est is not None:  # one more measure behind the last step: steps + 1 estimates
+                est["e_q"].copy_(adv["x_next_q"].reshape(B, 16))
+                est["e_xi"].copy_(adv["x_next_xi"])
+                self._measure_step(B, est, steps, res)
             if obs is not None:  # the realised state s of trajectory b is at world knot t0[b] + s
                 geo = obs[0]
                 if obs[3]:

@@ -422,6 +422,27 @@ def se3_mpc(B, steps, N=200, T=None, R=4, sigma_pose=0.05, sigma_twist=0.05, sig
     return prob, x0_q, x0_xi, path_q, path_xi, t0, noise
 
 
+def se3_mpc_estimated(B, steps, N=200, sigma_est=0.02, sigma_meas=0.01, seed=SEED, **mpc_kw):
+    """Output-feedback receding-horizon inputs (BatchedTrackingILQR.mpc with meas_* / est_*): se3_mpc's
+    (prob, x0_q, x0_xi, path_q, path_xi, t0, noise) -- x0 is now what the vehicle BELIEVES -- plus a dict of the seeded
+    keywords of the estimated loop: est_Sigma0 [B, 12, 12] = diag(sigma_est^2 U[0.5, 1.5]^2), the initial belief's covariance;
+    est_dx0 [B, 12] ~ N(0, est_Sigma0), where the true state starts relative to the belief; est_W [B, 6, 6] = sigma_noise^2 I,
+    the covariance se3_mpc draws its twist disturbance from; meas_V [B, 12] = sigma_meas^2 U[0.25, 4] and meas_noise
+    [B, steps+1, 12] ~ N(0, meas_V).  Which coordinates are measured (meas_mask) is the caller's choice."""
+    sigma_noise = mpc_kw.get("sigma_noise", 0.01)
+    prob, x0_q, x0_xi, path_q, path_xi, t0, noise = se3_mpc(B, steps, N=N, seed=seed, **mpc_kw)
+    rng = np.random.default_rng(seed + 13)
+    sd = sigma_est * rng.uniform(0.5, 1.5, (B, 12))
+    Sigma0 = np.zeros((B, 12, 12))
+    Sigma0[:, np.arange(12), np.arange(12)] = sd ** 2
+    dx0 = rng.normal(size=(B, 12)) * sd
+    W = np.broadcast_to(np.eye(6) * float(sigma_noise) ** 2, (B, 6, 6)).copy()
+    V = float(sigma_meas) ** 2 * rng.uniform(0.25, 4.0, (B, 12))
+    meas_noise = rng.normal(size=(B, steps + 1, 12)) * np.sqrt(V)[:, None, :]
+    est = dict(meas_V=V, meas_noise=meas_noise, est_Sigma0=Sigma0, est_W=W, est_dx0=dx0)
+    return prob, x0_q, x0_xi, path_q, path_xi, t0, noise, est
+
+
 def _obstacle_field(q_ref, B, K, r_lo, r_hi, seed):
     """K seeded keep-out spheres per trajectory on its reference path: sphere k of trajectory b is centred on the reference
     position of a knot drawn from the middle half of the horizon (ordered, one per K-th of it), moved by at most 0.3 r, with a
