@@ -236,6 +236,41 @@ int tolg_set_pose_schedule_windows(tolg_handle_t h, int32_t B, const double* d_p
 int tolg_set_al(tolg_handle_t h, const double* d_lb, const double* d_ub, const double* d_lambda,
                 const double* d_imu);
 
+/* The input box per trajectory or per knot: tolg_set_al's constraint with bounds that differ over the batch (two vehicles
+ * with different thrust limits, a sweep of a saturation level) or over the horizon as well (a derating that starts
+ * mid-horizon, a box tightened by kappa sigma_u of tolg_policy_covariance's var_u).
+ *   TOLG_BOX_PER_TRAJECTORY 1   d_lb, d_ub [B][m]
+ *   TOLG_BOX_PER_KNOT       2   d_lb, d_ub [B][N][m]
+ * The rows g = [lb - u_i; u_i - ub], i < N, the cost terms, the multipliers d_lambda, d_imu [B][N][2m] and the terminal knot
+ * (g = 0) are tolg_set_al's; only where lb and ub of a row are read changes.  Nothing is packed: the bounds stay
+ * caller-owned and are read in place by every later solve, entry a of knot i of trajectory b at b * stride_b + i * stride_i
+ * + a with element strides (m, 0) or (N m, m), beside the multipliers.  The bounds must be finite (lambda * g with an
+ * infinite g is NaN; a missing limit is a wide finite one) and are not read here.
+ * It and tolg_set_al replace each other; d_lb = NULL detaches the box, whichever call attached it.  While attached, the
+ * handle runs the kernels it runs with position slots attached, whether any are or not (those forms read the box strided;
+ * with tolg_set_al's shared box they read it with strides 0), every batch entry point must be called with this B, and
+ * tolg_eval_knot, which probes with the shared forms, is refused.  tolg_al_update_state, tolg_al_mpc_step and
+ * tolg_al_mpc_step_pose read whichever box the handle holds; tolg_al_update takes the [m] box of its own arguments.  The held
+ * policy is left alone: its gains belong to the problem that was solved.
+ * TOLG_E_ARG, the handle unchanged: form outside 1..2; B < 1 or B > max_batch; a NULL d_ub, d_lambda or d_imu; a solve in
+ * flight; another per-trajectory input held for another B; a model of the SO3 family or the pendulum (refused, they keep
+ * the shared box: the per-trajectory forms are not offered for them); bounds of 4 GB or more (B m >= 2^29 for form 1, B N m >= 2^29 for form 2:
+ * the kernels address them with 32-bit byte offsets).
+ * Not offered: box bounds on the twist.  They would be state rows whose l_xx falls on the velocity block, which the knot
+ * record does not carry and both backward sweeps rebuild from the weights.
+ * tolg_set_al_box_windows: the boxes of step t of a receding-horizon loop gathered on `stream` from world-time paths
+ * d_path_lb, d_path_ub [B][T+1][m] into the caller-owned d_lb_win, d_ub_win [B][N][m] by the rule of tolg_set_ref_windows:
+ * knot i of trajectory b takes path knot min(t0[b] + t + i, T), d_t0 = NULL: 0; any T >= 1, T < N included.  It then leaves
+ * the handle as tolg_set_al_box(h, B, TOLG_BOX_PER_KNOT, d_lb_win, d_ub_win, d_lambda, d_imu) would.
+ * TOLG_E_ARG: those above, a NULL path or window buffer, T < 1, t < 0. */
+#define TOLG_BOX_PER_TRAJECTORY 1
+#define TOLG_BOX_PER_KNOT 2
+int tolg_set_al_box(tolg_handle_t h, int32_t B, int32_t form, const double* d_lb, const double* d_ub, const double* d_lambda,
+                    const double* d_imu);
+int tolg_set_al_box_windows(tolg_handle_t h, int32_t B, const double* d_path_lb, const double* d_path_ub, int32_t T,
+                            const int32_t* d_t0, int32_t t, double* d_lb_win, double* d_ub_win, const double* d_lambda,
+                            const double* d_imu, void* stream);
+
 /* One outer iteration of AL_iLQR_Tracking_SE3_MS (traoptlibrary/traopt_controller.py:3242-3250,
  * :3270-3290) for B independent problems on the controls d_us [B][N][m] of the inner solve:
  * d_maxviol[b] = max_k g_k over all knots; if it is below tol_constr the problem is marked in

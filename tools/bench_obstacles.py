@@ -3,7 +3,8 @@
 (al_fit_batch(obstacles=...)) on the K = 8 field: its outer-iteration count and time.
 
 usage: python tools/bench_obstacles.py [--lines headline,merit,ss] [--Ks 0,1,4,8] [--B 4096] [--N 200] [--rounds 7]
-                                       [--steps K] [--warmup W] [--al] [--moving] [--kinds] [--pose] [--out FILE.json] [--dry]
+                                       [--steps K] [--warmup W] [--al] [--moving] [--kinds] [--pose] [--box] [--out FILE.json]
+                                       [--dry]
 
 One process, one handle per line; the variants are timed in alternation, round after round (the order rotates every round),
 each region being iterations W .. W+K of a fresh solve between two device synchronisations (tools/_benchlib.py's
@@ -23,7 +24,12 @@ spheres that face the start of the path).  One line per mix for every solve line
 
 --pose times what the second slot family costs (tolg_set_al_pose_constraints) in place of the K sweep: nothing attached, the
 two pose slots of workloads.se3_inspection (a tilt cone and a view cone whose target drifts: the per-knot form), six keep-out
-spheres, and both families together."""
+spheres, and both families together.
+
+--box times what the forms of the input box cost (tolg_set_al, tolg_set_al_box) in place of the K sweep, the same bounds in
+every variant (+-10, workloads.al_tracking's, under lambda 0.1, I_mu 1e-2): no box; the shared [m] box, which runs the kernels
+without PT_OBS; the same box as [B, m] and as [B, N, m], which select the PT_OBS forms with no slot attached; and, beside six
+keep-out spheres (the PT_OBS forms in every variant), the shared box (read with strides 0), [B, m] and [B, N, m]."""
 import argparse
 import json
 import os
@@ -44,6 +50,7 @@ def parse_args(argv=None):
     ap.add_argument("--moving", action="store_true", help="attach each field per knot (tolg_set_al_obstacles_moving)")
     ap.add_argument("--kinds", action="store_true", help="time the kind mixes at K = 6 (spheres, corridor, half-spaces)")
     ap.add_argument("--pose", action="store_true", help="time two pose slots (tilt cone, view cone) alone and beside six spheres")
+    ap.add_argument("--box", action="store_true", help="time the forms of the input box, alone and beside six spheres")
     add_common_args(ap, "out", "dry")
     a = ap.parse_args(argv)
     a.lines = a.lines.split(",")
@@ -168,6 +175,46 @@ def run_pose_line(name, a, prob, q0, xi0, us, sph, slots, kinds):
     return out
 
 
+BOX_MIXES = ("none", "shared", "trajectory", "knot", "spheres", "spheres+shared", "spheres+trajectory", "spheres+knot")
+
+
+def run_box_line(name, a, prob, q0, xi0, us, sph):
+    import torch
+    from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
+    kw, K0 = LINES[name]
+    K, W = a.steps or K0, a.warmup
+    solver = BatchedTrackingILQR(prob, a.B)
+    dev = solver.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    q_d, xi_d, us_d = (torch.as_tensor(x, **f64) for x in (q0, xi0, us))
+    m = prob.m
+    mult = (torch.full((a.B, a.N + 1, 6), 0.1, **f64), torch.full((a.B, a.N + 1, 6), 1e-2, **f64))
+    bmult = (torch.full((a.B, a.N, 2 * m), 0.1, **f64), torch.full((a.B, a.N, 2 * m), 1e-2, **f64))
+    shape = {"shared": (m,), "trajectory": (a.B, m), "knot": (a.B, a.N, m)}
+    box = {k: (torch.full(v, -10.0, **f64), torch.full(v, 10.0, **f64)) for k, v in shape.items()}
+
+    def region(mix):
+        form = mix.split("+")[-1]
+        if mix.startswith("spheres"):
+            solver.set_al_obstacles(sph, *mult)
+        if form in box:
+            solver.set_al(*box[form], *bmult)
+        rate, _ = solve_rate_region(solver, (q_d, xi_d, us_d), kw, W, K)
+        solver.set_al(None)
+        solver.set_al_obstacles(None)
+        torch.cuda.synchronize(dev)
+        return rate
+
+    rates = rate_rounds(BOX_MIXES, region, a.rounds)
+    out = dict(line=name, B=a.B, N=a.N, K=6, steps=K, warmup=W, rounds=a.rounds, unit="batch-iterations/s",
+               variants={v: summary(rates[v]) for v in BOX_MIXES})
+    base = out["variants"]["none"]["median"]
+    out["ratio_to_none"] = {v: s["median"] / base for v, s in out["variants"].items()}
+    del solver
+    torch.cuda.synchronize(dev)
+    return out
+
+
 def run_al(a, prob, q0, xi0, us, obs):
     import torch
     from trajectory_optimization_matrix_lie_groups_amd import BatchedTrackingILQR
@@ -192,15 +239,20 @@ def main(argv=None):
     if a.pose:  # (se3_tracking's starts and path under both workloads: the slots fit the sphere field's problem)
         prob, q0, xi0, us, sph6 = workloads.se3_obstacle_field(a.B, 6, N=a.N)
         slots, pose_kinds = workloads.se3_inspection(a.B, N=a.N)[4:]
+    if a.box:
+        prob, q0, xi0, us, sph6 = workloads.se3_obstacle_field(a.B, 6, N=a.N)
     if a.dry:
         print(json.dumps(dict(plan=a.lines, Ks=a.Ks, B=a.B, N=prob.N, rounds=a.rounds, al=a.al, moving=a.moving,
                               kinds=list(KIND_MIXES) if a.kinds else None, pose=list(POSE_MIXES) if a.pose else None,
+                              box=list(BOX_MIXES) if a.box else None,
                               steps={n: a.steps or LINES[n][1] for n in a.lines}, warmup=a.warmup)))
         return 0
     require_gpu("bench_obstacles")
     results = []
     for name in a.lines:
-        if a.pose:
+        if a.box:
+            r = run_box_line(name, a, prob, q0, xi0, us, sph6)
+        elif a.pose:
             r = run_pose_line(name, a, prob, q0, xi0, us, sph6, slots, pose_kinds)
         else:
             r = run_kinds_line(name, a, prob, q0, xi0, us, mixes) if a.kinds else run_line(name, a, prob, q0, xi0, us, obs)
@@ -210,10 +262,10 @@ def main(argv=None):
         r = run_al(a, prob, q0, xi0, us, obs)
         results.append(r)
         print_row(r)
-    print("%-9s %-6s %10s %10s %10s %8s %7s" % ("line", "K", "median", "min", "max", "spread", "ratio"))
+    print("%-9s %-18s %10s %10s %10s %8s %7s" % ("line", "K", "median", "min", "max", "spread", "ratio"))
     for r in results:
         for v, s in r.get("variants", {}).items():
-            print("%-9s %-6s %10.1f %10.1f %10.1f %7.2f%% %7.4f" % (r["line"], v, s["median"], s["min"], s["max"],
+            print("%-9s %-18s %10.1f %10.1f %10.1f %7.2f%% %7.4f" % (r["line"], v, s["median"], s["min"], s["max"],
                                                                    100 * s["spread"], r.get("ratio_to_none", {}).get(v, float("nan"))))
     emit(results, a.out)
     return 0

@@ -9,10 +9,10 @@ or no GPU is visible.  There is no CPU fallback in this package (the CPU restate
 ``oracle/`` is test infrastructure and is never imported from here).
 """
 from ._build import build_extension, lib_path  # noqa: F401
-from .solver import BatchedTrackingILQR, TrackingProblem, FitResult, PolicyRollout, PolicyCovariance, PolicyValue, MPCResult, inflate_obstacles, tighten_pose_constraints, check_box, rollout_margins, check_actuator, actuator_state  # noqa: F401
+from .solver import BatchedTrackingILQR, TrackingProblem, FitResult, PolicyRollout, PolicyCovariance, PolicyValue, MPCResult, inflate_obstacles, tighten_pose_constraints, tighten_input_box, check_box, check_input_box, rollout_margins, check_actuator, actuator_state  # noqa: F401
 
 __all__ = ["build_extension", "lib_path", "BatchedTrackingILQR", "TrackingProblem", "FitResult", "PolicyRollout", "PolicyCovariance", "PolicyValue",
-           "MPCResult", "inflate_obstacles", "tighten_pose_constraints", "check_box", "rollout_margins", "check_actuator", "actuator_state",
+           "MPCResult", "inflate_obstacles", "tighten_pose_constraints", "tighten_input_box", "check_box", "check_input_box", "rollout_margins", "check_actuator", "actuator_state",
            "install_as_traoptlibrary"]
 
 

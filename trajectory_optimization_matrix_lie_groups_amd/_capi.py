@@ -12,6 +12,7 @@ MAX_OBSTACLES = 16  # TOLG_MAX_OBSTACLES
 OBS_KEEP_OUT, OBS_KEEP_IN, OBS_HALF_SPACE, OBS_COLUMN_Z = 0, 1, 2, 3  # TOLG_OBS_*
 MAX_POSE_CONSTRAINTS = 8  # TOLG_MAX_POSE_CONSTRAINTS
 POSE_TILT_CONE, POSE_VIEW_CONE = 0, 1  # TOLG_POSE_*
+BOX_PER_TRAJECTORY, BOX_PER_KNOT = 1, 2  # TOLG_BOX_*
 PLANT_DIAG, PLANT_DENSE = 0, 1
 MAX_ACT_DELAY = 4  # TOLG_MAX_ACT_DELAY
 _ERR = {-1: "bad argument", -2: "workspace too small", -3: "kernel launch failed", -4: "inertia matrix singular"}
@@ -37,7 +38,7 @@ class Actuator(C.Structure):
 
 _lib = None
 SYMBOLS = ["tolg_workspace_bytes", "tolg_create", "tolg_destroy", "tolg_solve_batch", "tolg_solve_begin",
-           "tolg_solve_iterate", "tolg_solve_iterate_until", "tolg_solve_end", "tolg_solve_peek", "tolg_solve_active_count", "tolg_set_al", "tolg_al_update",
+           "tolg_solve_iterate", "tolg_solve_iterate_until", "tolg_solve_end", "tolg_solve_peek", "tolg_solve_active_count", "tolg_set_al", "tolg_set_al_box", "tolg_set_al_box_windows", "tolg_al_update",
            "tolg_refs_bytes", "tolg_set_refs", "tolg_weights_bytes", "tolg_set_weights",
            "tolg_pose_schedule_bytes", "tolg_set_pose_schedule", "tolg_set_pose_schedule_windows", "tolg_eval_knot", "tolg_linearize_backward",
            "tolg_rollout", "tolg_expected_change", "tolg_solve_gains", "tolg_policy_rollout",
@@ -83,6 +84,10 @@ def load():
     lib.tolg_solve_active_count.argtypes = [vp, ip, vp]
     lib.tolg_set_al.restype = C.c_int
     lib.tolg_set_al.argtypes = [vp, dp, dp, dp, dp]
+    lib.tolg_set_al_box.restype = C.c_int
+    lib.tolg_set_al_box.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp]
+    lib.tolg_set_al_box_windows.restype = C.c_int
+    lib.tolg_set_al_box_windows.argtypes = [vp, C.c_int32, dp, dp, C.c_int32, ip, C.c_int32, dp, dp, dp, dp, vp]
     lib.tolg_refs_bytes.restype = C.c_size_t
     lib.tolg_refs_bytes.argtypes = [C.POINTER(Problem), C.c_int32]
     lib.tolg_set_refs.restype = C.c_int

@@ -154,7 +154,7 @@ struct Params {
   double *mu, *delta, *Jc, *dn, *grad;
   int *active, *iters, *status, *conv;
   double *J_hist, *grad_hist, *defect_hist, *alpha_hist, *mu_hist;
-  int max_iter, pad;
+  int max_iter, box_sb;  // box_sb, box_si (below): the element strides of the input box over trajectories and knots (al_lb)
   double tol_grad, tol_defect, max_reg;
   // line search (SS backtracking, MS merit search): speculative candidates live in NSLOT slot buffers
   double* slot_x;      // [NSLOT][N+1][13][Bp]
@@ -171,7 +171,7 @@ struct Params {
   int* ec_redo;        // [Bp]     trajectories k_expected_change_ring hands to k_expected_change (tolg_expected_change.h)
   double* ED;          // [N+1][Bp][32] rollout = 'linear': deviation e_i (0..11) and control step du_i (16..16+m) of the alpha = 1
                        //          linear rollout, written by k_expected_change_ring<.., STORE>
-  int affine, pad3;    // this solve takes its linear-rollout candidates from ED (every trajectory with ec_redo == 0)
+  int affine, box_si;  // this solve takes its linear-rollout candidates from ED (every trajectory with ec_redo == 0)
   // line search, round 3 form: the stages roll out only (quad rollouts over a compacted list of the undecided
   // trajectories), costs and defects of the candidates are evaluated in parallel over the knots
   int* ls_list;        // [2][Bp]  undecided trajectories after a stage (two lists: a select builds the next while ...)
@@ -180,8 +180,11 @@ struct Params {
   double* LSC;         // [NSLOT][N+1][Bp] stage costs of the candidates
   double* LSD;         // [NSLOT][N][Bp]   squared defects of the candidates (MS)
   // augmented-Lagrangian box input constraint (ALConstrainedCost + InputConstraint), caller-owned
-  const double* al_lb;      // [m] or null (= AL off)
-  const double* al_ub;      // [m]
+  // The kernels without PT_OBS read al_lb[a].  The PT_OBS forms read al_lb[bs * box_sb + i * box_si + a] (bs the trajectory,
+  // clamped to B - 1 as for the multipliers): strides (0, 0) the shared box of tolg_set_al, (m, 0) tolg_set_al_box's [B][m],
+  // (N m, m) its [B][N][m].  The strides sit in what was padding: no kernel argument moves.
+  const double* al_lb;      // [m], [B][m] or [B][N][m]; null (= AL off)
+  const double* al_ub;      // as al_lb
   const double* al_lambda;  // [B][N][2m]
   const double* al_imu;     // [B][N][2m] diagonal of I_mu
 };
@@ -209,6 +212,30 @@ template <> struct RefAt<true> {
 // weights (tolg_set_weights).  0 is the batch-shared form of every kernel.
 // PT_OBS: the augmented-Lagrangian terms of its keep-out spheres (tolg_set_al_obstacles; the cost-evaluating kernels only).
 enum { PT_REF = 1, PT_W = 2, PT_OBS = 4 };
+// The input box of knot i of trajectory bs (< B).  Without PT_OBS the batch-shared [m] arrays, read as they have always been;
+// the PT_OBS forms read them strided (Params::box_sb, box_si), so one form serves tolg_set_al (strides 0) and both forms of
+// tolg_set_al_box.
+template <bool STRIDED> struct BoxAt {
+  TOLG_DEV BoxAt(const Params&, int, int) {}
+  TOLG_DEV static void fence() {}
+  TOLG_DEV double lb(const Params& P, int a) const { return P.al_lb[a]; }
+  TOLG_DEV double ub(const Params& P, int a) const { return P.al_ub[a]; }
+};
+template <> struct BoxAt<true> {
+  // one 32-bit byte offset per lane for both bounds (the loads take the pointers from scalar registers): the arrays stay below
+  // 4 GB, which tolg_set_al_box checks
+  unsigned o;
+  TOLG_DEV BoxAt(const Params& P, int bs, int i) : o(((unsigned)bs * (unsigned)P.box_sb + (unsigned)i * (unsigned)P.box_si) * 8u) {}
+  // Between two inputs' rows: the bounds are per-lane loads here (scalar ones in the shared form), and a scheduler free to
+  // issue all 2m of them ahead of the rows holds 4m more registers across the kernel's peak -- a wave of occupancy in the
+  // line-search evaluations, scratch in the fused launch.  Row by row the block needs no more than it did.
+  TOLG_DEV static void fence() { __builtin_amdgcn_sched_barrier(0); }
+  TOLG_DEV double at(const double* p, int a) const {
+    return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(p) + ((size_t)o + 8u * (unsigned)a));
+  }
+  TOLG_DEV double lb(const Params& P, int a) const { return at(P.al_lb, a); }
+  TOLG_DEV double ub(const Params& P, int a) const { return at(P.al_ub, a); }
+};
 // Per-trajectory cost weights (tolg_set_weights): the diagonals of W1, W2 (Q), P1, P2 (P) and R, packed [WT_F][Bp] (field
 // f of trajectory b at f * Bp + b: a weight load is coalesced over the batch like a state load)
 enum { WT_W1 = 0, WT_W2 = 6, WT_P1 = 12, WT_P2 = 18, WT_R = 24 };
@@ -1225,12 +1252,15 @@ TOLG_DEV void lin_knot(const Params& P, const CT& C, int i, int b, int ms, const
         const int bs = b < P.B ? b : P.B - 1;
         const double* lam = P.al_lambda + ((size_t)bs * P.N + i) * 2 * M;
         const double* imu = P.al_imu + ((size_t)bs * P.N + i) * 2 * M;
+        const BoxAt<PTO> box(P, bs, i);
+        box.fence();
 #pragma unroll
         for (int a = 0; a < M; a++) {
-          double g1 = P.al_lb[a] - u[a], g2 = u[a] - P.al_ub[a];
+          double g1 = box.lb(P, a) - u[a], g2 = u[a] - box.ub(P, a);
           l += lam[a] * g1 + lam[M + a] * g2 + 0.5 * (g1 * imu[a] * g1 + g2 * imu[M + a] * g2);
           lu[a] += -(lam[a] + imu[a] * g1) + (lam[M + a] + imu[M + a] * g2);
           luu[a] = imu[a] + imu[M + a];
+          box.fence();
         }
       }
       rec_run<REC_LU, M, RP>(P, i, b, lu);
@@ -3140,10 +3170,13 @@ TOLG_DEV double knot_cost(const Params& P, const Consts& C, int i, int b, const 
       const int bs = b < P.B ? b : P.B - 1;
       const double* lam = P.al_lambda + ((size_t)bs * P.N + i) * 2 * M;
       const double* imu = P.al_imu + ((size_t)bs * P.N + i) * 2 * M;
+      const BoxAt<(PT & PT_OBS) != 0> box(P, bs, i);
+      box.fence();
 #pragma unroll
       for (int a = 0; a < M; a++) {
-        double g1 = P.al_lb[a] - u[a], g2 = u[a] - P.al_ub[a];
+        double g1 = box.lb(P, a) - u[a], g2 = u[a] - box.ub(P, a);
         l += lam[a] * g1 + lam[M + a] * g2 + 0.5 * (g1 * imu[a] * g1 + g2 * imu[M + a] * g2);
+        box.fence();
       }
     }
   }
@@ -5933,6 +5966,11 @@ struct tolg_handle_s {
   // (TOLG_K2_FULL_ONLY=1), the one-wave forms of the line-search rollouts (TOLG_LS_ONEWAVE=1)
   bool k2_full_only = false, ls_one_wave = false;
   const double *al_lb = nullptr, *al_ub = nullptr, *al_lambda = nullptr, *al_imu = nullptr;  // tolg_set_al: the input box (null = off)
+  // tolg_set_al_box: al_lb / al_ub above are [B][m] or [B][N][m] (box.p = al_lb; nothing held: the shared [m] box of tolg_set_al,
+  // or none).  Under the one-batch rule; no PT bit of its own: held, it selects the PT_OBS tables as posec does, whose kernels
+  // read the box with the element strides box_sb, box_si (Params) -- both 0 for the shared box
+  Held box;
+  int box_sb = 0, box_si = 0;
   // early exit of a sliced solve (tolg_solve_iterate_until): two device counters, their pinned host copies, two events
   LazyRes cnt;
   // merit search: the linear alpha = 1 rollout (k_expected_change) runs on a side stream beside the first line-search stage
@@ -5959,6 +5997,7 @@ static bool one_batch(const tolg_handle_s* h, int B, const Held* except = nullpt
   for (const Held& r : h->pt) if (&r != except && r.p && B != r.B) return false;
   if (&h->sched != except && h->sched.p && B != h->sched.B) return false;
   if (&h->posec != except && h->posec.p && B != h->posec.B) return false;
+  if (&h->box != except && h->box.p && B != h->box.B) return false;
   return true;
 }
 // B trajectories fit the handle and the per-trajectory inputs it holds: what every batch call on the handle's workspace requires
@@ -5974,6 +6013,7 @@ static void select_kernels(tolg_handle_s* h) {
   int pt = 0;
   for (int k = 0; k < H_PT; k++) if (h->pt[k].p) pt |= 1 << k;
   if (h->posec.p) pt |= PT_OBS;  // the pose slots ride on the forms of the position slots (Consts::obsK = 0 without those)
+  if (h->box.p) pt |= PT_OBS;    // ... and so does a box per trajectory or per knot: only those forms read it strided
   h->kt = h->kt_pt[pt];
 }
 // kt_pt[PT] = kernel_table_for<PT>, for every set PT of the PT_* bits (tolg_create)
@@ -5992,6 +6032,7 @@ static void drop(tolg_handle_s* h, Held& r) {
   if (&r == &h->pt[H_OBS]) { h->obs_K = 0; h->obs_kinds = 0; h->obs_stride = 0; h->obs_lam = h->obs_imu = nullptr; }
   if (&r == &h->posec) { h->pose_K = 0; h->pose_kinds = 0; h->pose_stride = 0; h->pose_lam = h->pose_imu = nullptr; }
   if (&r == &h->plant) h->plant_S = h->plant_form = 0;
+  if (&r == &h->box) h->box_sb = h->box_si = 0;
   select_kernels(h);
 }
 
@@ -6294,6 +6335,7 @@ static Params params_for(tolg_handle_s* h, int B) {
   P.J_hist = P.grad_hist = P.defect_hist = P.alpha_hist = P.mu_hist = nullptr;
   P.max_iter = 0; P.tol_grad = 0; P.tol_defect = 0; P.max_reg = 1e10;
   P.al_lb = h->al_lb; P.al_ub = h->al_ub; P.al_lambda = h->al_lambda; P.al_imu = h->al_imu;
+  P.box_sb = h->box_sb; P.box_si = h->box_si;
   P.ref = h->pt[H_REFS].p ? h->pt[H_REFS].p : h->ref_shared;  // the layout h->kt's kernels read
   const bool grav = h->hc.grav != 0.0;
   // the velocity block of F_x is stored only for the models the third form of the backward sweep does not cover
@@ -6698,9 +6740,57 @@ extern "C" int tolg_set_al(tolg_handle_t h, const double* d_lb, const double* d_
                            const double* d_imu) {
   if (!h || h->running) return TOLG_E_ARG;
   if (d_lb && (!d_ub || !d_lambda || !d_imu)) return TOLG_E_ARG;
+  drop(h, h->box);  // the shared box replaces a box of tolg_set_al_box: strides 0, the kernel tables of what else is held
   h->al_lb = d_lb; h->al_ub = d_lb ? d_ub : nullptr;
   h->al_lambda = d_lb ? d_lambda : nullptr; h->al_imu = d_lb ? d_imu : nullptr;
   return 0;
+}
+
+// The input box per trajectory ([B][m]) or per knot ([B][N][m]), read in place like the multipliers: nothing is packed, the
+// PT_OBS forms read entry a of knot i of trajectory b at b * box_sb + i * box_si + a (BoxAt).  The slot counts of the constants
+// are zero whenever their family is not attached (the detaches clear them), so a box alone runs those forms with no slot.
+static bool box_model_ok(const tolg_handle_s* h) { return !so3_family(h->prob.kind) && h->prob.kind != TOLG_DYN_PENDULUM3D; }
+extern "C" int tolg_set_al_box(tolg_handle_t h, int32_t B, int32_t form, const double* d_lb, const double* d_ub,
+                               const double* d_lambda, const double* d_imu) {
+  if (!h || h->running) return TOLG_E_ARG;
+  if (!d_lb) {  // detach: no box at all, whichever call attached it
+    drop(h, h->box);
+    h->al_lb = h->al_ub = h->al_lambda = h->al_imu = nullptr;
+    return 0;
+  }
+  if (form != TOLG_BOX_PER_TRAJECTORY && form != TOLG_BOX_PER_KNOT) return TOLG_E_ARG;
+  if (!box_model_ok(h) || B < 1 || B > h->max_batch || !d_ub || !d_lambda || !d_imu || !one_batch(h, B, &h->box)) return TOLG_E_ARG;
+  const int N = h->prob.N, m = h->prob.m;
+  // (the kernels address the bounds with 32-bit byte offsets: BoxAt)
+  if ((size_t)B * (form == TOLG_BOX_PER_KNOT ? (size_t)N : 1) * m * sizeof(double) > 0xffffffffull) return TOLG_E_ARG;
+  h->al_lb = d_lb; h->al_ub = d_ub; h->al_lambda = d_lambda; h->al_imu = d_imu;
+  h->box_sb = form == TOLG_BOX_PER_KNOT ? N * m : m;
+  h->box_si = form == TOLG_BOX_PER_KNOT ? m : 0;
+  hold(h, h->box, d_lb, B);
+  return 0;
+}
+// knot i of trajectory b's window from its world-time path [B][T+1][m] (window_knot), both bounds; one thread per entry
+__global__ void k_gather_box_windows(int B, int N, int m, int T, const double* __restrict__ path_lb, const double* __restrict__ path_ub,
+                                     const int* __restrict__ t0, int t, double* __restrict__ lb, double* __restrict__ ub) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (size_t)B * N * m) return;
+  const int a = (int)(g % m), i = (int)((g / m) % N), b = (int)(g / ((size_t)N * m));
+  const size_t src = ((size_t)b * (T + 1) + window_knot(t0, b, t, i, T)) * m + a;
+  lb[g] = path_lb[src];
+  ub[g] = path_ub[src];
+}
+extern "C" int tolg_set_al_box_windows(tolg_handle_t h, int32_t B, const double* d_path_lb, const double* d_path_ub, int32_t T,
+                                       const int32_t* d_t0, int32_t t, double* d_lb_win, double* d_ub_win, const double* d_lambda,
+                                       const double* d_imu, void* stream) {
+  if (!h || h->running || !d_path_lb || !d_path_ub || !d_lb_win || !d_ub_win || !d_lambda || !d_imu || T < 1 || t < 0)
+    return TOLG_E_ARG;
+  if (!box_model_ok(h) || B < 1 || B > h->max_batch || !one_batch(h, B, &h->box)) return TOLG_E_ARG;
+  const size_t n = (size_t)B * h->prob.N * h->prob.m;
+  if (n * sizeof(double) > 0xffffffffull) return TOLG_E_ARG;  // (tolg_set_al_box's rule, ahead of the gather: a refused call writes nothing)
+  hipLaunchKernelGGL(k_gather_box_windows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), B,
+                     h->prob.N, h->prob.m, T, d_path_lb, d_path_ub, reinterpret_cast<const int*>(d_t0), t, d_lb_win, d_ub_win);
+  LAUNCH_CHECK();
+  return tolg_set_al_box(h, B, TOLG_BOX_PER_KNOT, d_lb_win, d_ub_win, d_lambda, d_imu);
 }
 
 static size_t refs_bytes_for(const tolg_problem* p, int B, int = 0) {
@@ -6865,7 +6955,8 @@ struct AlRows {
   unsigned kinds;
   TOLG_DEV double g_box(int i, int k) const {
     const double* u = us + ((size_t)b * N + i) * m;
-    return (k < m) ? lb[k] - u[k] : u[k - m] - ub[k - m];
+    const size_t o = (size_t)b * (size_t)box_sb + (size_t)i * (size_t)box_si;  // (0: the shared [m] box)
+    return (k < m) ? lb[o + k] - u[k] : u[k - m] - ub[o + k - m];
   }
   TOLG_DEV double g_sphere(int i, int k) const {
     const double* x = xs_q + ((size_t)b * (N + 1) + i) * 16;
@@ -6882,6 +6973,7 @@ struct AlRows {
   const double* pgeo = nullptr;
   size_t pgeo_stride = 0;
   unsigned pkinds = 0;
+  int box_sb = 0, box_si = 0;  // the element strides of lb / ub over trajectories and knots (Params::box_sb, box_si)
   TOLG_DEV double g_pose(int i, int k) const {
     const double* x = xs_q + ((size_t)b * (N + 1) + i) * 16;
     const double* o = pgeo + (size_t)i * pgeo_stride + (size_t)(4 * k) * Bp + b;
@@ -6923,10 +7015,10 @@ __global__ void k_al_update_state(int B, int Bp, int N, int m, int K, const doub
                                   double* __restrict__ imu, const double* __restrict__ geo, size_t geo_stride, unsigned kinds,
                                   double* __restrict__ olam, double* __restrict__ oimu, double* __restrict__ mu, double mu_scale,
                                   double mu_max, double tol_constr, double* __restrict__ maxviol, int* __restrict__ al_conv,
-                                  AlPose ps) {
+                                  AlPose ps, int box_sb, int box_si) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B || al_conv[b]) return;  // a converged problem keeps its multipliers
-  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride, kinds, ps.geo, ps.stride, ps.kinds};
+  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride, kinds, ps.geo, ps.stride, ps.kinds, box_sb, box_si};
   double mv = lb ? 0.0 : -INFINITY;
   if (lb)
     for (int i = 0; i < N; i++)
@@ -7031,10 +7123,10 @@ __global__ __launch_bounds__(AL_STEP_THREADS) void k_al_mpc_step(
     int Bp, int N, int m, int K, const double* __restrict__ xs_q, const double* __restrict__ us, const double* __restrict__ lb,
     const double* __restrict__ ub, double* __restrict__ lam, double* __restrict__ imu, const double* __restrict__ geo,
     size_t geo_stride, unsigned kinds, double* __restrict__ olam, double* __restrict__ oimu, double* __restrict__ mu,
-    double mu_scale, double mu_max, double tol_constr, double* __restrict__ maxviol, int shift, AlPose ps) {
+    double mu_scale, double mu_max, double tol_constr, double* __restrict__ maxviol, int shift, AlPose ps, int box_sb, int box_si) {
   __shared__ double red[AL_STEP_THREADS / 64];
   const int b = blockIdx.x;
-  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride, kinds, ps.geo, ps.stride, ps.kinds};
+  const AlRows R{b, Bp, N, m, K, xs_q, us, lb, ub, geo, geo_stride, kinds, ps.geo, ps.stride, ps.kinds, box_sb, box_si};
   const int W = 2 * m, nb = lb ? N * W : 0, no = geo ? (N + 1) * K : 0, Kp = ps.K, np = ps.geo ? (N + 1) * Kp : 0;
   const double mu_old = mu[b];
   double mv = lb ? 0.0 : -INFINITY;
@@ -7078,7 +7170,7 @@ static int set_obstacles(tolg_handle_t h, int B, int K, bool moving, const doubl
   if (!h || h->running) return TOLG_E_ARG;
   Held& r = h->pt[H_OBS];
   if (!d_obs) {
-    if (r.p && h->posec.p) {  // the PT_OBS forms stay selected for the pose slots: no position slot is left for them to read
+    if (r.p) {  // the PT_OBS forms stay selected, or are selected later, for the pose slots or a box: they must find no position slot
       hipLaunchKernelGGL(k_clear_slots, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), const_cast<Consts*>(h->P.c), 1, 0);
       LAUNCH_CHECK();
     }
@@ -7221,7 +7313,7 @@ extern "C" int tolg_al_update(tolg_handle_t h, int32_t B, const double* d_us, co
     return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_update_state, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), B, 0, h->prob.N,
                      h->prob.m, 0, (const double*)nullptr, d_us, d_lb, d_ub, d_lambda, d_imu, (const double*)nullptr, (size_t)0,
-                     0u, (double*)nullptr, (double*)nullptr, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, d_al_converged, AlPose{});
+                     0u, (double*)nullptr, (double*)nullptr, d_mu, mu_scale, mu_max, tol_constr, d_maxviol, d_al_converged, AlPose{}, 0, 0);
   LAUNCH_CHECK();
   return 0;
 }
@@ -7235,10 +7327,12 @@ extern "C" int tolg_al_update_state(tolg_handle_t h, int32_t B, const double* d_
   if (h->al_lb && !d_us) return TOLG_E_ARG;
   if (obs.p && (B != obs.B || !d_xs_q)) return TOLG_E_ARG;
   if (pose.p && (B != pose.B || !d_xs_q)) return TOLG_E_ARG;
+  if (h->box.p && B != h->box.B) return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_update_state, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), B, padded_batch(B),
                      h->prob.N, h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
                      const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_kinds, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
-                     d_maxviol, d_al_converged, AlPose{pose.p, h->pose_stride, h->pose_kinds, h->pose_K, h->pose_lam, h->pose_imu});
+                     d_maxviol, d_al_converged, AlPose{pose.p, h->pose_stride, h->pose_kinds, h->pose_K, h->pose_lam, h->pose_imu},
+                     h->box_sb, h->box_si);
   LAUNCH_CHECK();
   return 0;
 }
@@ -7255,10 +7349,12 @@ static int al_mpc_step(tolg_handle_t h, int B, const double* d_xs_q, const doubl
   if (h->al_lb && !d_us) return TOLG_E_ARG;
   if (obs.p && (B != obs.B || !d_xs_q)) return TOLG_E_ARG;
   if (pose.p && (B != pose.B || !d_xs_q)) return TOLG_E_ARG;
+  if (h->box.p && B != h->box.B) return TOLG_E_ARG;
   hipLaunchKernelGGL(k_al_mpc_step, dim3(B), dim3(AL_STEP_THREADS), 0, static_cast<hipStream_t>(stream), padded_batch(B), h->prob.N,
                      h->prob.m, h->obs_K, d_xs_q, d_us, h->al_lb, h->al_ub, const_cast<double*>(h->al_lambda),
                      const_cast<double*>(h->al_imu), obs.p, h->obs_stride, h->obs_kinds, h->obs_lam, h->obs_imu, d_mu, mu_scale, mu_max, tol_constr,
-                     d_maxviol, shift, AlPose{pose.p, h->pose_stride, h->pose_kinds, h->pose_K, h->pose_lam, h->pose_imu});
+                     d_maxviol, shift, AlPose{pose.p, h->pose_stride, h->pose_kinds, h->pose_K, h->pose_lam, h->pose_imu},
+                     h->box_sb, h->box_si);
   LAUNCH_CHECK();
   return 0;
 }
@@ -7307,6 +7403,7 @@ extern "C" int tolg_eval_knot(tolg_handle_t h, int32_t i, int32_t n, const doubl
                               void* stream) {
   if (!h || h->running || n < 1 || n > h->max_batch || i < 0 || i > h->prob.N || !d_x_q || !d_x_xi) return TOLG_E_ARG;
   if (i < h->prob.N && !d_u) return TOLG_E_ARG;
+  if (h->box.p) return TOLG_E_ARG;  // the probe runs the shared forms, which read one [m] box
   hipStream_t st = static_cast<hipStream_t>(stream);
   h->pol_B = 0;  // k_probe_pack overwrites knot i of the nominal trajectory
   Params P = params_for(h, n);

@@ -346,6 +346,29 @@ def check_box(u_lb, u_ub, B, m, so3=False):
     return out[0], out[1]
 
 
+def check_input_box(lb, ub, B, N, m):
+    """The planner's input box (set_al, al_fit_batch, plan_fleet, mpc) checked on the host, ValueError before anything
+    reaches the device: lb, ub of one shape, [m] (every trajectory and knot the same: tolg_set_al), [B, m] (a box per
+    trajectory) or [B, N, m] (per knot: tolg_set_al_box); finite -- the augmented-Lagrangian terms multiply lambda by g = lb -
+    u, and an infinite bound makes that NaN: a missing limit is a wide finite one, unlike the actuator box of check_box --
+    and lb <= ub in every entry.  Returns (lb, ub) as contiguous float64 numpy arrays of the shape given."""
+    out = []
+    for name, a in (("lb", lb), ("ub", ub)):
+        if a is None:
+            raise ValueError("lb and ub come together: %s is missing" % name)
+        a = np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+        if tuple(a.shape) not in ((m,), (B, m), (B, N, m)):
+            raise ValueError("%s has shape %s, expected (%d), (%d, %d) or (%d, %d, %d)" % (name, tuple(a.shape), m, B, m, B, N, m))
+        if not np.all(np.isfinite(a)):
+            raise ValueError("%s must be finite (a missing limit is a wide finite one: lambda * g with an infinite g is NaN)" % name)
+        out.append(np.ascontiguousarray(a))
+    if out[0].shape != out[1].shape:
+        raise ValueError("lb %s and ub %s must have the same shape" % (out[0].shape, out[1].shape))
+    if np.any(out[0] > out[1]):
+        raise ValueError("lb must not exceed ub")
+    return out[0], out[1]
+
+
 def check_actuator(u_lb, u_ub, tau, rate, delay, u_init, B, m, dt, so3=False):
     """An actuator model (include/tolg.h, tolg_actuator) checked and converted on the host, ValueError before anything reaches
     the device.  u_lb / u_ub: the box of check_box, both or neither (None).  tau: the lag's time constant in seconds, [m] or
@@ -657,6 +680,28 @@ def tighten_pose_constraints(slots, kinds, xs_q, Sigma, kappa):
     return out
 
 
+def tighten_input_box(lb, ub, var_u, kappa):
+    """The input box with a margin for the closed-loop spread, the input half of inflate_obstacles and
+    tighten_pose_constraints: lb, ub [m], [B, m] or [B, N, m], var_u [B, N, m] the variance of the held policy's inputs
+    (policy_covariance().var_u).  Returns (lb + kappa sqrt(var_u), ub - kappa sqrt(var_u)), [B, N, m] each (numpy): kappa
+    standard deviations of room for the feedback on either side at every knot, the per-knot form al_fit_batch(lb=, ub=) and
+    mpc(lb=, ub=) take.  ValueError where the box would become empty."""
+    host = lambda a: np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)  # noqa: E731
+    var = host(var_u)
+    if var.ndim != 3:
+        raise ValueError("tighten_input_box: var_u has shape %s, expected (B, N, m)" % (var.shape,))
+    B, N, m = var.shape
+    lo, hi = check_input_box(lb, ub, B, N, m)
+    if not np.all(np.isfinite(var)) or np.any(var < 0.0) or not np.isfinite(float(kappa)) or float(kappa) < 0.0:
+        raise ValueError("tighten_input_box: var_u must be finite and not negative, kappa finite and not negative")
+    grow = lambda a: a if a.ndim == 3 else np.broadcast_to(a if a.ndim == 1 else a[:, None], (B, N, m))  # noqa: E731
+    s = float(kappa) * np.sqrt(var)
+    lo, hi = grow(lo) + s, grow(hi) - s
+    if np.any(lo > hi):
+        raise ValueError("tighten_input_box: the box is empty once kappa sigma is taken off both sides")
+    return np.ascontiguousarray(lo), np.ascontiguousarray(hi)
+
+
 def mpc_window_index(t0, t, N, T):
     """Knot of the path that knot i of step t's window tracks (tolg_set_ref_windows): min(t0[b] + t + i, T), [B, N+1]."""
     t0 = np.asarray(t0, dtype=np.int64).reshape(-1)
@@ -751,6 +796,7 @@ class BatchedTrackingILQR:
         self._obs_kinds = ()       # ... with the kinds the handle holds for them (tolg_set_al_obstacle_kinds), one per slot
         self._pose = None          # ... and the pose constraints (set_al_pose_constraints): (slots, lam, imu, kinds)
         self._pose_buf = self._pose_knot_buf = None  # their packed geometry: static for max_batch, per knot for the largest call
+        self._box_win = None       # set_al_box_windows: the gathered windows (lb, ub) [B, N, m] the handle reads in place
         p = _capi.Problem()
         p.kind, p.m, p.N, p.dt = _KIND[problem.kind], self.m, self.N, float(problem.dt)
         p.pend_mass, p.pend_length = float(problem.pend_mass), float(problem.pend_length)
@@ -1120,14 +1166,72 @@ class BatchedTrackingILQR:
     # ------------------------------------------------------------------------------------------
     def set_al(self, lb=None, ub=None, lam=None, imu=None):
         """Attach (or detach with lb=None) the augmented-Lagrangian box input constraint terms
-        (ALConstrainedCost + InputConstraint).  lam, imu: device tensors [B, N, 2m]."""
+        (ALConstrainedCost + InputConstraint).  lam, imu: device tensors [B, N, 2m].  lb, ub [m]: one box for every
+        trajectory and knot (tolg_set_al); [B, m]: a box per trajectory, or [B, N, m]: per knot as well (check_input_box;
+        tolg_set_al_box, which reads the bounds in place beside the multipliers: every batch call must then be for this B;
+        not for the SO3 family and the pendulum).  Each attach replaces the one before, whatever its shape."""
         if lb is None:
             self._al = None
             self._detach("tolg_set_al")
-        else:
+        elif np.ndim(lb) <= 1:
             lb = self._dev(lb, (self.m,)); ub = self._dev(ub, (self.m,))
             self._al = (lb, ub, lam, imu)  # the handle reads them in every solve until they are detached
             self._call("tolg_set_al", _ptr(lb), _ptr(ub), _ptr(lam), _ptr(imu), stream=False)
+        else:
+            B = self._box_multipliers(lam, imu)
+            lo, hi = check_input_box(lb, ub, B, self.N, self.m)
+            lo, hi = self._dev(lo, lo.shape), self._dev(hi, hi.shape)
+            self._call("tolg_set_al_box", B, _capi.BOX_PER_KNOT if lo.dim() == 3 else _capi.BOX_PER_TRAJECTORY, _ptr(lo), _ptr(hi),
+                       _ptr(lam), _ptr(imu), stream=False)
+            self._al = (lo, hi, lam, imu)
+
+    def _box_multipliers(self, lam, imu):
+        """The box's multipliers lam, imu [B, N, 2m] checked where their batch decides how the bounds are read (contiguous
+        float64 on the device); returns B."""
+        if self.problem.kind in ("so3", "pendulum3d"):
+            raise ValueError("an input box per trajectory or per knot is not offered for the %s model: it takes lb, ub [m]"
+                             % self.problem.kind)
+        for name, t in (("lam", lam), ("imu", imu)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float64 tensor on %s" % (name, self.device))
+            _checked(name, t, (lam.shape[0] if lam.dim() else None, self.N, 2 * self.m))
+        B = int(lam.shape[0])
+        if not 1 <= B <= self.max_batch:
+            raise ValueError("an input box for B = %d trajectories, expected 1..%d" % (B, self.max_batch))
+        return B
+
+    def set_al_box_windows(self, path_lb, path_ub, t, t0=None, lam=None, imu=None):
+        """Attach the input boxes of step t, gathered on the device from world-time paths (tolg_set_al_box_windows): path_lb,
+        path_ub [B, T+1, m], the bounds of trajectory b at world knot s (finite, lb <= ub); knot i of the window takes world
+        knot min(t0[b] + t + i, T), set_ref_windows' rule (t0 an int array [B], None: 0).  The handle is then as after set_al
+        with the gathered [B, N, m] bounds; lam, imu [B, N, 2m] as there.  path_lb = None detaches."""
+        if path_lb is None:
+            return self.set_al(None)
+        if int(t) < 0:
+            raise ValueError("t must be non-negative")
+        B = self._box_multipliers(lam, imu)
+        lo, hi = self._box_paths(B, path_lb, path_ub)
+        t0_d = self._check_t0(B, t0)
+        self._hold((lo, hi, t0_d))
+        self._set_box_windows(B, lo, hi, t0_d, int(t), lam, imu)
+
+    def _box_paths(self, B, path_lb, path_ub):
+        """World-time box paths [B, T+1, m] checked on the host under check_input_box's rule (T >= 1 in place of the horizon)
+        and moved to the device."""
+        n = np.shape(path_lb)[1] if np.ndim(path_lb) == 3 else 0
+        if n < 2:
+            raise ValueError("lb_path has shape %s, expected (%d, T+1 >= 2, %d)" % (tuple(np.shape(path_lb)), B, self.m))
+        lo, hi = check_input_box(path_lb, path_ub, B, n, self.m)
+        return self._dev(lo, lo.shape), self._dev(hi, hi.shape)
+
+    def _set_box_windows(self, B, d_lb, d_ub, t0_d, t, lam, imu):
+        f64 = dict(dtype=torch.float64, device=self.device)
+        win = self._box_win
+        if win is None or win[0].shape[0] != B:  # the caller-owned windows the handle reads in place until the next attach
+            win = self._box_win = (torch.empty(B, self.N, self.m, **f64), torch.empty(B, self.N, self.m, **f64))
+        self._call("tolg_set_al_box_windows", B, _ptr(d_lb), _ptr(d_ub), int(d_lb.shape[1] - 1), _ptr(t0_d), int(t), _ptr(win[0]),
+                   _ptr(win[1]), _ptr(lam), _ptr(imu))
+        self._al = (win[0], win[1], lam, imu, d_lb, d_ub)
 
     def _check_obstacles(self, B, obstacles, kinds=None):
         """Keep-out spheres [K, 4] (every trajectory the same), [B, K, 4], or per knot [B, N+1, K, 4], rows (cx, cy, cz, r),
@@ -1384,7 +1488,8 @@ class BatchedTrackingILQR:
         the reference -- then updates multipliers on the device.  Returns (FitResult, info dict).
         q_ref / xi_ref: a reference per trajectory, Q / P / R: weights per trajectory, pose_scale: a per-knot schedule on the
         pose weights, as for fit_batch.
-        Constraints: the input box lb <= u <= ub, keep-out spheres obstacles ([K, 4], [B, K, 4] or per knot [B, N+1, K, 4],
+        Constraints: the input box lb <= u <= ub (lb, ub [m], or a box per trajectory [B, m], or per trajectory and knot
+        [B, N, m]: check_input_box, set_al), keep-out spheres obstacles ([K, 4], [B, K, 4] or per knot [B, N+1, K, 4],
         set_al_obstacles; obstacle_kinds: its kinds=, a kind per slot -- keep-in sphere, half-space, column), or both
         (one mu per problem, joint convergence: tolg_al_update_state).  With spheres the info dict also holds lmbd_obs and
         Imu_obs [B, N+1, K]; max_violation covers every constraint.
@@ -1413,8 +1518,10 @@ class BatchedTrackingILQR:
         alconv = torch.zeros(B, dtype=torch.int32, device=self.device)
         lam_o = imu_o = None
         if box:
-            lb_d = self._dev(lb, (self.m,)); ub_d = self._dev(ub, (self.m,))
-            self.set_al(lb_d, ub_d, lam, imu)
+            lb_h, ub_h = check_input_box(lb, ub, B, self.N, self.m)
+            self.set_al(lb_h, ub_h, lam, imu)  # (uploads them, once)
+            lb_d, ub_d = self._al[0], self._al[1]
+        shared_box = box and lb_d.dim() == 1  # tolg_al_update takes a [m] box of its own; the other forms are the handle's
         if obs is not None:
             lam_o = torch.zeros(B, self.N + 1, obs.shape[-2], **f64)
             imu_o = torch.full((B, self.N + 1, obs.shape[-2]), float(mu0), **f64)
@@ -1454,7 +1561,7 @@ class BatchedTrackingILQR:
                     final = res
                 if on_outer is not None:  # before the multiplier update, like on_iteration_al (:3253-3259)
                     on_outer(outer, final, lam, imu, mu)
-                if obs is None and pose is None:
+                if obs is None and pose is None and shared_box:
                     self._call("tolg_al_update", B, _ptr(final.us), _ptr(lb_d), _ptr(ub_d), _ptr(lam), _ptr(imu), _ptr(mu),
                                float(mu_scale), float(mu_max), float(tol_constr), _ptr(maxviol), _ptr(alconv))
                 else:  # every attached constraint, one mu per problem
@@ -1482,7 +1589,8 @@ class BatchedTrackingILQR:
         fleet b // fleet.  Round p = 0 .. fleet-1 solves the F members p, each on its own reference (q_ref [B, N+1, 4, 4],
         xi_ref [B, N+1, 6]), keeping out of the caller's static `obstacles` ([K0, 4] or [B, K0, 4]) and of p moving spheres of
         radius `separation` centred on the positions of members 0..p-1 of its fleet as their rounds left them
-        (al_fit_batch with a per-knot field; lb / ub and al_kw -- n_al_iters, n_ilqr_iters, tol_constr, mu0, ..., Q / P / R
+        (al_fit_batch with a per-knot field; lb / ub -- [m], or in batch order [B, m] / [B, N, m], every round takes
+        its members' rows -- and al_kw -- n_al_iters, n_ilqr_iters, tol_constr, mu0, ..., Q / P / R
         [B, ...] -- go to it).  Round 0 with neither obstacles nor a box is a plain fit_batch with al_fit_batch's inner options.
         The constraint holds at the knots, not between them: two members may pass closer than `separation` between two knots.
         A lower-priority member yields to a higher one: member 0 plans as if alone, and whether member p finds a way round the
@@ -1522,6 +1630,10 @@ class BatchedTrackingILQR:
         if pose_constraints is None and pose_kinds is not None:
             raise ValueError("pose_kinds describe pose_constraints: none were given")
         pose = None if pose_constraints is None else self._check_pose_constraints(B, pose_constraints, pose_kinds)[1:]
+        if (lb is None) != (ub is None):
+            raise ValueError("the input box needs both lb and ub")
+        if lb is not None:  # [m], or in batch order [B, m] / [B, N, m]: every round takes its members' rows
+            lb, ub = check_input_box(lb, ub, B, self.N, self.m)
         if us_init is None:
             us_init = np.zeros((B, self.N, self.m))
         per = {k: al_kw.pop(k) for k in ("Q", "P", "R") if k in al_kw}
@@ -1545,7 +1657,8 @@ class BatchedTrackingILQR:
                 outers.append(1)
             else:
                 obs = np.concatenate(field, axis=2) if pos else None if static is None else static[sl]
-                res, info = self.al_fit_batch(x0_q[sl], x0_xi[sl], us_init[sl], lb, ub, obstacles=obs,
+                box = (lb, ub) if lb is None or lb.ndim == 1 else (lb[sl], ub[sl])
+                res, info = self.al_fit_batch(x0_q[sl], x0_xi[sl], us_init[sl], *box, obstacles=obs,
                                               obstacle_kinds=None if obs is None else kinds0 + (0,) * len(pos), **al_kw, **kw)
                 maxviol[sl], alconv[sl] = info["max_violation"], info["al_converged"]
                 outers.append(info["outer_iterations"])
@@ -2241,7 +2354,7 @@ class BatchedTrackingILQR:
     def mpc(self, x0_q, x0_xi, path_q, path_xi, steps, us_init=None, t0=None, iters_per_step=5, first_iters=50,
             warm="states", noise=None, mode="ms", line_search=False, rollout="nonlinear", tol_grad_norm=1e-6, tol_d_norm=1e-6,
             check_every=0, Q=None, P=None, R=None, max_reg=1e10, on_step=None, plant_J=None, plant_pend=None, u_lb=None,
-            u_ub=None, lb=None, ub=None, obstacles=None, obstacle_paths=None, obstacle_kinds=None, first_al_iters=3,
+            u_ub=None, lb=None, ub=None, lb_path=None, ub_path=None, obstacles=None, obstacle_paths=None, obstacle_kinds=None, first_al_iters=3,
             al_iters_per_step=1, mu0=1e-2, mu_scale=10.0, mu_max=1e8, tol_constr=1e-2, pose_scale_path=None,
             pose_constraints=None, pose_paths=None, pose_kinds=None, act_tau=None, act_rate=None, act_delay=0, meas_mask=None,
             meas_V=None, meas_noise=None, est_Sigma0=None, est_W=None, est_dx0=None) -> MPCResult:
@@ -2267,7 +2380,10 @@ class BatchedTrackingILQR:
         plant, with no constraint attached.
         x0_q [B, 4, 4], x0_xi [B, 6], path_q [B, T+1, 4, 4], path_xi [B, T+1, 6].
         The planner's constraints (augmented Lagrangian, mode="ms" only; with none of them the loop is the one above): lb / ub
-        [m], the input box of set_al (the SO3 family takes the box only); obstacles [K, 4] or [B, K, 4], static keep-out
+        [m], the input box of set_al (the SO3 family takes the box only), or a box per trajectory [B, m], or [B, N, m], per
+        knot and fixed in window coordinates (knot i of every step's window; check_input_box), or lb_path / ub_path
+        [B, T_b+1, m], boxes in world time indexed with the same t0 (window t is gathered by tolg_set_al_box_windows; the
+        static pair or the path pair, never both; the plant's u_lb / u_ub are another matter: they clip, these plan); obstacles [K, 4] or [B, K, 4], static keep-out
         spheres, or obstacle_paths [B, T_o+1, K, 4], spheres in world time indexed with the same t0 (window t is gathered by
         tolg_set_al_obstacle_windows); at most one of the two; obstacle_kinds: the kind of each of their K slots
         (set_al_obstacles' kinds=; the clearance is then each kind's own); pose_constraints [K, 4] or [B, K, 4], static pose slots
@@ -2310,6 +2426,10 @@ class BatchedTrackingILQR:
             raise ValueError("steps must be >= 1, first_iters, iters_per_step and check_every >= 0")
         if (lb is None) != (ub is None):
             raise ValueError("the input box needs both lb and ub")
+        if (lb_path is None) != (ub_path is None):
+            raise ValueError("the input box in world time needs both lb_path and ub_path")
+        if lb is not None and lb_path is not None:
+            raise ValueError("give lb / ub (fixed in window coordinates) or lb_path / ub_path (world time), not both")
         if obstacles is not None and obstacle_paths is not None:
             raise ValueError("give obstacles (static) or obstacle_paths (world time), not both")
         if obstacle_kinds is not None and obstacles is None and obstacle_paths is None:
@@ -2319,7 +2439,7 @@ class BatchedTrackingILQR:
         if pose_kinds is not None and pose_constraints is None and pose_paths is None:
             raise ValueError("pose_kinds describe pose_constraints or pose_paths: none were given")
         posed = pose_constraints is not None or pose_paths is not None
-        constrained = lb is not None or obstacles is not None or obstacle_paths is not None or posed
+        constrained = lb is not None or lb_path is not None or obstacles is not None or obstacle_paths is not None or posed
         if constrained and mode != "ms":
             raise ValueError("the augmented-Lagrangian constraints need mode='ms'")
         if constrained and (int(first_al_iters) < 1 or int(al_iters_per_step) < 1):
@@ -2372,9 +2492,15 @@ class BatchedTrackingILQR:
             Kp = slots.shape[-2]
             pose = (self._dev(slots, slots.shape), torch.zeros(B, self.N + 1, Kp, **f64),
                     torch.full((B, self.N + 1, Kp), float(mu0), **f64), pose_paths is not None, pkinds)
-        if lb is not None:
-            al = (self._dev(_checked("lb", lb, (self.m,)), (self.m,)), self._dev(_checked("ub", ub, (self.m,)), (self.m,)),
-                  torch.zeros(B, self.N, 2 * self.m, **f64), torch.full((B, self.N, 2 * self.m), float(mu0), **f64))
+        if lb is not None or lb_path is not None:  # (lb, ub, lam, imu, in world time)
+            if lb_path is not None:
+                if self._so3() or self.problem.kind == "pendulum3d":
+                    raise ValueError("mpc: lb_path / ub_path are not offered for the %s model" % self.problem.kind)
+                lo, hi = self._box_paths(B, lb_path, ub_path)
+            else:
+                lo, hi = check_input_box(lb, ub, B, self.N, self.m)  # (on the host: set_al uploads them, once)
+            al = (lo, hi, torch.zeros(B, self.N, 2 * self.m, **f64), torch.full((B, self.N, 2 * self.m), float(mu0), **f64),
+                  lb_path is not None)
         if obstacles is not None or obstacle_paths is not None:
             geo = (self._check_obstacles(B, obstacles, obstacle_kinds)[1] if obstacles is not None else
                    self._check_obstacle_paths(B, obstacle_paths, obstacle_kinds)[1])
@@ -2409,8 +2535,8 @@ class BatchedTrackingILQR:
             d_plant = self._use_plant(B, plant)
             self._hold((b, pq, pxi, t0_d, noise, adv, d_plant, box, al, obs, pose, mu, maxviol, spath, act, est))
             self._use_pt(B, None, b.wts)
-            if al is not None:
-                self.set_al(*al)
+            if al is not None and not al[4]:
+                self.set_al(*al[:4])
             if obs is not None and not obs[3]:
                 self.set_al_obstacles(*obs[:3], kinds)
             if pose is not None and not pose[3]:
@@ -2421,6 +2547,8 @@ class BatchedTrackingILQR:
                 self._set_ref_windows(B, pq, pxi, T, t0_d, t)
                 if spath is not None:
                     self._set_pose_schedule(B, (spath[0], spath[1], t0_d, t))
+                if al is not None and al[4]:
+                    self._set_box_windows(B, al[0], al[1], t0_d, t, al[2], al[3])
                 if obs is not None and obs[3]:
                     self._set_obstacle_windows(B, obs[0], t0_d, t, obs[1], obs[2], kinds)
                 if pose is not None and pose[3]:

@@ -23,7 +23,8 @@ class BaseConstraint():
 class InputConstraint(BaseConstraint):
     """Box input constraint g = [lb - u; u - ub] <= 0 (traopt_constraints.py:66-169).  The values are
     trivial affine maps of u (host code in the reference as well); the augmented-Lagrangian terms
-    built from them run on the device (tolg_set_al / tolg_al_update)."""
+    built from them run on the device (tolg_set_al / tolg_al_update).  input_lb, input_ub [m], or [N, m]: a box per knot,
+    g(x, u, i) then uses row i (on the device tolg_set_al_box's per-knot form / tolg_al_update_state)."""
 
     def __init__(self, input_lb, input_ub, state_size=(6, 6), action_size=6):
         self._state_size = state_size[0] + state_size[1]
@@ -45,7 +46,10 @@ class InputConstraint(BaseConstraint):
     def g(self, x, u, i, terminal=False, *args, **kwargs):
         if terminal:
             return np.zeros((self._constr_size,))
-        return np.concatenate([self.lb - u, u - self.ub])
+        lb, ub = np.asarray(self.lb), np.asarray(self.ub)
+        if lb.ndim == 2:  # [N, m]: the box of knot i
+            lb, ub = lb[i], ub[i]
+        return np.concatenate([lb - u, u - ub])
 
     def g_x(self, x, u, i, terminal=False, *args, **kwargs):
         return np.zeros([self.constr_size, self.state_size])

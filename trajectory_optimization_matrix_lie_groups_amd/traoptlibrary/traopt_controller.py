@@ -134,7 +134,7 @@ class _FusedController(BaseController):
                               **f64)
         d = np.stack([np.diag(a) for a in self.cost.Imu[: self.N]])
         imu = torch.as_tensor(np.broadcast_to(d[None], (B,) + d.shape).copy(), **f64)
-        solver.set_al(self.cost.constr.lb, self.cost.constr.ub, lam, imu)
+        solver.set_al(*_box_bounds(self.cost.constr, B), lam, imu)
         return True
 
     def fit_batch(self, x0s, us_init=None, n_iterations=100, tol_grad_norm=None, tol_d_norm=1e-6, refs=None, weights=None):
@@ -301,6 +301,15 @@ class iLQR_Tracking_SE3_MS(_FusedController):
         return self._fit_single(x0, us_init, n_iterations, tol_grad_norm, tol_d_norm, on_iteration, ms=True)
 
 
+def _box_bounds(box, B):
+    """(lb, ub) of an InputConstraint as the device takes them: [m] as given, a box per knot [N, m] as [B, N, m], the same for
+    every trajectory (tolg_set_al_box's per-knot form)."""
+    lb, ub = np.asarray(box.lb, float), np.asarray(box.ub, float)
+    if lb.ndim == 2:
+        lb, ub = np.broadcast_to(lb, (B,) + lb.shape).copy(), np.broadcast_to(ub, (B,) + ub.shape).copy()
+    return lb, ub
+
+
 def _route_constraints(constraints):
     """(InputConstraint or None, SphereObstacleConstraint or None, PoseConstraint or None) of what AL_iLQR_Tracking_SE3_MS
     solves on the device: an InputConstraint, a SphereObstacleConstraint (or its per-knot form,
@@ -370,7 +379,8 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
         slots = pose.slots() if pose else None
         if slots is not None and slots.ndim == 3:  # per knot [N+1, K, 4]: the same for every trajectory
             slots = np.broadcast_to(slots, (B,) + slots.shape)
-        return solver.al_fit_batch(q, xi, us_init, box.lb if box else None, box.ub if box else None, n_al_iters=n_al_iters,
+        lb, ub = _box_bounds(box, B) if box else (None, None)
+        return solver.al_fit_batch(q, xi, us_init, lb, ub, n_al_iters=n_al_iters,
                                    n_ilqr_iters=n_ilqr_iters, tol_grad_norm=tol_grad_norm, tol_constr=tol_constr,
                                    mu0=self._mu0, mu_scale=self._mu_scale, mu_max=self._mu_max,
                                    line_search=self.ilqr_solver._line_search, on_outer=on_outer, q_ref=q_ref,
@@ -389,7 +399,7 @@ class AL_iLQR_Tracking_SE3_MS(BaseController):
                 raise NotImplementedError("on_iteration_al reports the input box only; keep-out spheres, pose constraints: "
                                           "use fit_batch(on_outer=)")
             us = _bridge.host(res.us)[0]
-            g = np.concatenate([self.constr.lb - us, us - self.constr.ub], axis=1)
+            g = np.concatenate([np.asarray(self.constr.lb) - us, us - np.asarray(self.constr.ub)], axis=1)
             constr_eval = np.vstack([g, np.zeros((1, 2 * m))])
             lam_h = np.vstack([_bridge.host(lam)[0], np.zeros((1, 2 * m))])
             imu_h = np.stack([np.diag(d) for d in np.vstack([_bridge.host(imu)[0], np.zeros((1, 2 * m))])])

@@ -479,6 +479,23 @@ def drone_obstacle_field(B, K, N=400, seed=SEED):
     return prob, x0_q, x0_xi, us0, _obstacle_field(prob.q_ref, B, K, 0.1, 0.2, seed + 3)
 
 
+DERATED_SPAN = np.array([300.0, 450.0, 40.0, 30.0])  # the free solve's input range at R_scale = 1e-3: torques, thrust
+DERATED_CENTRE = np.array([0.0, 0.0, 0.0, 15.0])
+
+
+def drone_derated(B, N=400, tight=0.5, wide=4.0, derate=0.5, seed=SEED):
+    """A drone fleet whose members have different actuators, each derated mid-flight: drone_tracking's workload (R = 1e-3 I)
+    with an input box per trajectory and knot (al_fit_batch(lb=, ub=), [B, N, m]).  Trajectory b's box is DERATED_CENTRE +-
+    w_b DERATED_SPAN with w_b spaced geometrically from `tight` (binds hard on the roll and pitch torques) to `wide` (never
+    binds) and shuffled by the seed; from knot N // 2 on every width is `derate` times that (a derating that starts
+    mid-horizon: the narrow members then bind there as well).  Returns (prob, x0_q, x0_xi, us0, lb, ub, width [B])."""
+    prob, x0_q, x0_xi, us0 = drone_tracking(B, N=N, R_scale=1e-3, seed=seed)
+    w = tight * (wide / tight) ** (np.arange(B) / max(B - 1, 1))
+    w = w[np.random.default_rng(seed + 11).permutation(B)]
+    half = w[:, None, None] * DERATED_SPAN[None, None, :] * np.where(np.arange(N) >= N // 2, derate, 1.0)[None, :, None]
+    return prob, x0_q, x0_xi, us0, DERATED_CENTRE - half, DERATED_CENTRE + half, w
+
+
 CORRIDOR_KINDS = ("half_space", "half_space", "keep_in", "column", "column", "sphere")
 
 
