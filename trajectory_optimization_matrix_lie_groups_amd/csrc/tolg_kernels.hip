@@ -6085,6 +6085,7 @@ static size_t carve_all(const tolg_problem* pr, int Bp, char* base, Params& P) {
   P.Jc = c.take<double>(B);
   P.dn = c.take<double>(B);
   P.grad = c.take<double>(B);
+  // (first flag run, active .. conv: tolg_create zeroes it from P.active to the end of P.conv -- ints only, and in this order)
   P.active = c.take<int>(B);
   P.iters = c.take<int>(B);
   P.status = c.take<int>(B);
@@ -6096,6 +6097,8 @@ static size_t carve_all(const tolg_problem* pr, int Bp, char* base, Params& P) {
   P.ecc = c.take<double>(2 * B);
   P.dweight = c.take<double>(2 * B);
   P.ls_alpha = c.take<double>(B);
+  // (second flag run, ls_accept .. ls_pos: tolg_create zeroes it from P.ls_accept to the end of P.ls_pos.  A new flag or index
+  // array goes INSIDE one of the two runs; an array of doubles goes outside both, or it starts at zero as well)
   P.ls_accept = c.take<int>(B);
   P.ls_slot = c.take<int>(B);
   P.k2_redo = c.take<int>(B / 4 + 1);
@@ -6103,7 +6106,7 @@ static size_t carve_all(const tolg_problem* pr, int Bp, char* base, Params& P) {
   P.ec_redo = c.take<int>(B);
   P.ls_list = c.take<int>(2 * B);
   P.ls_count = c.take<int>(64);
-  P.ls_pos = c.take<int>(2 * B);
+  P.ls_pos = c.take<int>(2 * B);  // (the end of the second flag run)
   P.LSC = c.take<double>((size_t)NSLOT * (N + 1) * B);
   P.LSD = c.take<double>((size_t)NSLOT * N * B);
   P.ED = c.take<double>((N + 1) * 32 * B);
@@ -6249,6 +6252,18 @@ extern "C" int tolg_create(const tolg_problem* prob, const double* d_q_ref, cons
   h->ref_shared = h->P.ref;
   Consts* dc = const_cast<Consts*>(h->P.c);
   if (hipMemcpyAsync(dc, &h->hc, sizeof(Consts), hipMemcpyHostToDevice, st) != hipSuccess) { tolg_destroy(h); return TOLG_E_LAUNCH; }
+  // The int flags and index lists start at zero ("What initialises the workspace"): the begin kernels state the
+  // per-trajectory ones again, but the full backward sweep of a one-sweep entry point (it < 0) reads k2_hint, which only an
+  // earlier sweep writes.  Two runs of the carve order: active .. conv, and ls_accept .. ls_pos.
+  {
+    const size_t Bp = (size_t)h->Bp_max;
+    char *a0 = reinterpret_cast<char*>(h->P.active), *a1 = reinterpret_cast<char*>(h->P.conv + Bp);
+    char *l0 = reinterpret_cast<char*>(h->P.ls_accept), *l1 = reinterpret_cast<char*>(h->P.ls_pos + 2 * Bp);
+    if (hipMemsetAsync(a0, 0, (size_t)(a1 - a0), st) != hipSuccess || hipMemsetAsync(l0, 0, (size_t)(l1 - l0), st) != hipSuccess) {
+      tolg_destroy(h);
+      return TOLG_E_LAUNCH;
+    }
+  }
   int N = prob->N;
   hipLaunchKernelGGL(k_pack_ref, dim3((N + 1 + 63) / 64), dim3(64), 0, st, N, d_q_ref, d_xi_ref,
                      const_cast<double*>(h->P.ref));
